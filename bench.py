@@ -7,13 +7,18 @@ A step = one pass of the hot path (u8 tiles resident in HBM -> UNet forward -> u
 weights were broadcast from rank 0 over RCCL at start-up (north_star: "RCCL-over-xGMI broadcast of weights and
 per-rank gather of mask tensors").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extras]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts that torchrun command itself as a CHILD
 process (before this process touches the GPU) and returns its exit code.
 
-What is timed, in this order (DESIGN.md "Measurement" describes every field of the ONE JSON line rank 0 prints):
+A plain run measures the headline and nothing else: set-up (weights, image sets, the first eager pass of each graph key), W
+warm-up steps, K timed steps (`value`, `ms_per_step`), the label maps of the last timed step written to DIR/labels.npy
+(float32; beyond 64 MB a fixed, seeded sample of whole images, listed in DIR/labels_index.npy) when --dump-outputs is given,
+and the JSON line.  Every other record and check below (1 and 3-7, the label-map checks of 2) runs only under --full.
+
+What --full runs, in this order (DESIGN.md "Measurement" describes every field of the ONE JSON line rank 0 prints):
   1. parity gate   the first images of the timed batch against the oracle (labels equal wherever the oracle's top-2
                    margin exceeds 1e-3, logits within 1e-3); a mismatch makes the run exit non-zero
   2. `value`       W warm-up steps, then K steps of the SHIPPED path (hipGraph replay, profiling off) between
@@ -476,6 +481,37 @@ def summary_of(out):
     return s
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(d, labels):
+    """--dump-outputs DIR: the label maps [N, H, W] a caller of the timed path receives from its last step, as DIR/labels.npy in
+    float32.  Past DUMP_LIMIT_BYTES a fixed, seeded sample of whole images is kept (their indices, ascending, in
+    DIR/labels_index.npy); if not even one image fits, a seeded sample of pixels of the flattened maps."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    labels = np.asarray(labels)
+    n, per = labels.shape[0], labels[0].size * 4
+    budget = DUMP_LIMIT_BYTES - 4096 - 8 * max(n, 1)              # npy headers and the index array
+    index = None
+    if labels.size * 4 > budget:
+        rng = np.random.default_rng(0x5EED)
+        if per <= budget:
+            index = np.sort(rng.choice(n, budget // per, replace=False))
+            labels = labels[index]
+        else:
+            flat = labels.reshape(-1)
+            index = np.sort(rng.choice(flat.size, (DUMP_LIMIT_BYTES - 4096) // 12, replace=False))   # 4 + 8 bytes a pixel
+            labels = flat[index]
+    np.save(os.path.join(d, "labels.npy"), labels.astype(np.float32))
+    ip = os.path.join(d, "labels_index.npy")
+    if index is not None:
+        np.save(ip, index.astype(np.float64))
+    elif os.path.exists(ip):
+        os.remove(ip)                                                # left by an earlier, sampled dump
+    return {"labels": list(labels.shape), "sampled": index is not None}
+
+
 def group_child_main():
     """`bench.py --group-child`: the C++ host's own multi-GPU path (mi_unet_group_*: ONE process, one worker thread per device,
     weights packed once and sent device-to-device, contiguous image shards -- the slot of the reference's sequential file
@@ -589,15 +625,23 @@ def main():
     ap.add_argument("--in-ch", type=int, default=1)
     ap.add_argument("--base", type=int, default=64)
     ap.add_argument("--levels", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the e2e_host / configs / pipeline records")
-    ap.add_argument("--per-layer", action="store_true", help="also print a per-layer table to stderr")
+    ap.add_argument("--full", action="store_true", help="also run every record and check besides the headline: parity gate, label-map "
+                    "checks, roofline pass, e2e_host, configs, pipeline, group, cpu_baseline (off: set-up, warm-up, timed steps, line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the label maps of the last timed step to DIR/labels.npy (float32, "
+                    "at most 64 MB: a fixed, seeded sample of images beyond that, indices in DIR/labels_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline record")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the e2e_host / configs / pipeline records")
+    ap.add_argument("--per-layer", action="store_true", help="(--full) also print a per-layer table to stderr")
     ap.add_argument("--conv-algo", choices=["auto", "direct", "winograd", "winograd16", "bf16", "fp16"], default="auto")
     ap.add_argument("--no-group", action="store_true", help="skip the `group` record (mi_unet_group_* in one process)")
     ap.add_argument("--group-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--verbose", action="store_true", help="keep the per-kernel-family arrays of every roofline record in the JSON line "
                     "(default: compact form in the line, full arrays in gpurun_out/bench_families.json)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.per_layer and not args.full:
+        ap.error("--per-layer needs --full (the per-kernel pass runs only there)")
     global VERBOSE
     VERBOSE = args.verbose
 
@@ -607,7 +651,7 @@ def main():
         raise SystemExit(spawn_torchrun(args))
     # the `group` record's process: started now, while this process has not touched the GPU; it idles until told to run
     default_workload = (args.in_ch, args.base, args.levels, args.size, args.conv_algo, args.global_batch) == (1, 64, 4, 512, "auto", 0)
-    want_group = (int(os.environ.get("RANK", "0")) == 0 and not args.no_group and not args.no_extras and default_workload)
+    want_group = (int(os.environ.get("RANK", "0")) == 0 and args.full and not args.no_group and not args.no_extras and default_workload)
     group_skipped = None
     if want_group and under_profiler():
         want_group, group_skipped = False, "a profiler's preloaded library has initialised the GPU: no child process is started from here"
@@ -667,7 +711,7 @@ def main():
 
     # ---- 1. parity gate on the timed batch (rank 0: the oracle is a CPU program)
     parity, oracle_s = (None, 1.0)
-    if rank == 0:
+    if rank == 0 and args.full:
         parity, oracle_s = parity_gate(eng, blob, sets_host[0], 1 if (world > 1 or args.no_cpu_baseline) else min(B, 2), lp_mode)
 
     # Everything below runs on ONE explicit, non-default stream shared by the engine, the copies and the collectives: the
@@ -690,12 +734,13 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize(dev)
 
-        # expected label maps of both sets (also the first, eager, pass of each graph key)
+        # the first, eager, pass of each graph key (--full: also the expected label maps of both sets)
         expect = []
         for j in range(2):
             eng.infer_device(sets[j].data_ptr(), B, labels.data_ptr(), 0)
             stream.synchronize()
-            expect.append(labels.clone())
+            if args.full:
+                expect.append(labels.clone())
 
         # ---- 2. the shipped path: hipGraph replay, profiling off
         for i in range(args.warmup):
@@ -706,18 +751,21 @@ def main():
             step(i)
         fence()
         dt = time.perf_counter() - t0
+        # what a caller of the timed path receives from its last step (rank 0: the maps of every rank, gathered)
+        outputs = (torch.cat(gathered) if use_dist else labels).cpu().numpy() if (args.dump_outputs and rank == 0) else None
         last = (args.steps - 1) & 1
-        if not torch.equal(labels, expect[last]) and os.environ.get("BENCH_TIMING_ONLY") != "1":    # (timing-only kernel experiments, tools/dev)
-            raise SystemExit("label maps of the last timed step differ from that image set's expected maps")
-        if use_dist:
-            sums = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-            dist.all_gather(sums, expect[last].to(torch.int64).sum().reshape(1))
-            if rank == 0:
-                for r in range(world):
-                    if int(gathered[r].to(torch.int64).sum()) != int(sums[r]):
-                        raise SystemExit(f"gathered label maps of rank {r} are stale or corrupt")
-                if not torch.equal(gathered[0], expect[last]):
-                    raise SystemExit("gathered label maps differ from rank 0's own")
+        if args.full:
+            if not torch.equal(labels, expect[last]) and os.environ.get("BENCH_TIMING_ONLY") != "1":    # (timing-only kernel experiments, tools/dev)
+                raise SystemExit("label maps of the last timed step differ from that image set's expected maps")
+            if use_dist:
+                sums = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+                dist.all_gather(sums, expect[last].to(torch.int64).sum().reshape(1))
+                if rank == 0:
+                    for r in range(world):
+                        if int(gathered[r].to(torch.int64).sum()) != int(sums[r]):
+                            raise SystemExit(f"gathered label maps of rank {r} are stale or corrupt")
+                    if not torch.equal(gathered[0], expect[last]):
+                        raise SystemExit("gathered label maps differ from rank 0's own")
 
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         if use_dist:
@@ -725,17 +773,19 @@ def main():
         dt = float(tmax.item())
 
         # ---- 3. per-kernel pass: K more steps, eager, an event pair around every launch on the launch stream
-        eng.set_profiling(True)
-        for i in range(args.steps):
-            eng.infer_device(sets[i & 1].data_ptr(), B, labels.data_ptr(), 0)
-        stats = eng.kernel_stats()
-        eng.set_profiling(False)
-        stream.synchronize()
+        stats = []
+        if args.full:
+            eng.set_profiling(True)
+            for i in range(args.steps):
+                eng.infer_device(sets[i & 1].data_ptr(), B, labels.data_ptr(), 0)
+            stats = eng.kernel_stats()
+            eng.set_profiling(False)
+            stream.synchronize()
 
         # ---- 3b. BASELINE configs[3] in the same launch: a GLOBAL batch of 512 cut into contiguous shards (strong scaling),
         # each rank walking its shard in micro-batches, the label maps gathered to rank 0 inside the timed region
         cfg4 = None
-        if use_dist and default_workload and 512 % world == 0:
+        if args.full and use_dist and default_workload and 512 % world == 0:
             lo4, hi4 = shard.shard_range(512, rank, world)
             B4 = hi4 - lo4
             imgs4 = torch.from_numpy(synth.make_images(512, H, W, spec.in_ch, 0xC0F4, "bytes")[lo4:hi4]).to(dev)
@@ -795,11 +845,12 @@ def main():
                                    f"batch {B} x {H}x{W}x{spec.in_ch} u8 per GPU, {spec.levels}-level UNet base {spec.base}, "
                                    f"{arith}, argmax label maps", "images_per_gpu_per_step": B, "global_batch": B * world,
                        "parallelism": f"dp{world}" + (" (RCCL weight broadcast + per-step label-map gather)" if use_dist else "")},
-            "parity": parity,
-            "roofline": roofline_from_stats(stats, spec.macs_per_image(H, W), ips / world, lp_mode),
         }
-        prof_ms = sum(s["ms"] for s in stats) / args.steps
-        out["roofline"]["kernel_ms_per_step_eager_profiled"] = prof_ms
+        if args.full:
+            out["parity"] = parity
+            out["roofline"] = roofline_from_stats(stats, spec.macs_per_image(H, W), ips / world, lp_mode)
+            prof_ms = sum(s["ms"] for s in stats) / args.steps
+            out["roofline"]["kernel_ms_per_step_eager_profiled"] = prof_ms
         if cfg4 is not None:
             out["configs"] = [cfg4]
         if args.per_layer:
@@ -811,6 +862,15 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         eng.close()
+        sys.exit(0)
+
+    if not args.full:
+        # a plain run ends here: the headline, the outputs if asked for, the line
+        eng.close()
+        if args.dump_outputs:
+            print("dump-outputs: " + json.dumps(write_outputs(args.dump_outputs, outputs)), file=sys.stderr)
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
         sys.exit(0)
 
     if rank == 0:
@@ -867,6 +927,8 @@ def main():
             json.dump(FAMILY_TABLES, open(os.path.join(ROOT, "gpurun_out", "bench_families.json"), "w"), indent=1)
         except OSError:
             pass
+        if args.dump_outputs:
+            print("dump-outputs: " + json.dumps(write_outputs(args.dump_outputs, outputs)), file=sys.stderr)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
         bad = [k for k in ("parity",) if out.get(k) and not out[k]["ok"]]

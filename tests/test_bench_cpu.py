@@ -96,3 +96,35 @@ def test_the_newest_pmc_summary_describes_this_tree():
     profile round must have run on the final kernels"""
     d, src = bench.pmc_summary("fp32")
     assert d is not None, src
+
+
+def test_dump_outputs_are_float32_bounded_and_reproducible(tmp_path, monkeypatch):
+    """--dump-outputs: the label maps of the last timed step as float32 .npy; past the size limit a fixed, seeded sample of whole
+    images (or, when not even one image fits, of pixels), with the indices stored next to it, the same from run to run."""
+    import numpy as np
+    labels = (np.arange(5 * 8 * 8) % 3).astype(np.uint8).reshape(5, 8, 8)
+    rec = bench.write_outputs(str(tmp_path / "all"), labels)
+    got = np.load(tmp_path / "all" / "labels.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, labels) and not rec["sampled"]
+    assert not (tmp_path / "all" / "labels_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 8 * 5 + 2 * 8 * 8 * 4)           # room for two images
+    for d in ("s1", "s2"):
+        assert bench.write_outputs(str(tmp_path / d), labels) == {"labels": [2, 8, 8], "sampled": True}
+    idx = np.load(tmp_path / "s1" / "labels_index.npy")
+    assert idx.dtype == np.float64 and len(set(idx)) == 2 and list(idx) == sorted(idx)
+    assert np.array_equal(np.load(tmp_path / "s1" / "labels.npy"), labels[idx.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "s2" / "labels.npy"), np.load(tmp_path / "s1" / "labels.npy"))
+    assert np.array_equal(np.load(tmp_path / "s2" / "labels_index.npy"), idx)
+    size = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert size <= bench.DUMP_LIMIT_BYTES
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 8 * 5 + 100)                      # not even one image: pixels
+    rec = bench.write_outputs(str(tmp_path / "px"), labels)
+    idx = np.load(tmp_path / "px" / "labels_index.npy").astype(int)
+    assert rec["sampled"] and np.array_equal(np.load(tmp_path / "px" / "labels.npy"), labels.reshape(-1)[idx])
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 20)
+    bench.write_outputs(str(tmp_path / "s1"), labels)                                      # a later, whole dump
+    assert not (tmp_path / "s1" / "labels_index.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "s1" / "labels.npy"), labels)

@@ -256,16 +256,35 @@ def test_size_json_bytes_match_reference_nlohmann(golden_dir, tmp_path):
         assert js.read_bytes() == want, c["case"]
 
 
-@pytest.mark.skipif(not os.path.exists(PROBE), reason="oracle/_ref/json_probe only exists where /root/reference does")
-@settings(max_examples=25, deadline=None)
-@given(st.lists(st.lists(st.tuples(st.integers(-9999, 99999), st.integers(-9999, 99999)), min_size=1, max_size=6), min_size=1, max_size=4),
-       st.text(alphabet=st.characters(blacklist_categories=("Cs",), blacklist_characters="\x00/"), min_size=1, max_size=8))
-def test_polygon_json_live_against_probe(tmp_path_factory, contours, base):
-    out = tmp_path_factory.mktemp("j") / "o.json"
-    hostlib.generate_json(contours, str(out), base, 1234, 987)
-    stdin = f"{len(contours)}\n" + "".join(f"{len(c)} " + " ".join(f"{x} {y}" for x, y in c) + "\n" for c in contours)
-    want = subprocess.run([PROBE, "poly", base, "1234", "987"], input=stdin.encode(), check=True, capture_output=True).stdout
-    assert out.read_bytes() == want
+_POLY_LIVE = (st.lists(st.lists(st.tuples(st.integers(-9999, 99999), st.integers(-9999, 99999)), min_size=1, max_size=6), min_size=1, max_size=4),
+              st.text(alphabet=st.characters(blacklist_categories=("Cs",), blacklist_characters="\x00/"), min_size=1, max_size=8))
+
+
+def test_polygon_json_live_against_probe(golden_dir, tmp_path_factory):
+    """Our polygon JSON bytes against what the reference's nlohmann header emits for the same contours and base name: live through
+    oracle/_ref/json_probe where it was built, and always on the seeded cases it emitted bytes for (quotes, backslashes, control
+    characters, CJK, astral code points: tests/golden/make_json_golden.py), so the check does not depend on the probe."""
+    cases = json.load(open(os.path.join(golden_dir, "json", "poly_random.json"), encoding="utf-8"))
+    assert len(cases) == 30
+    d = tmp_path_factory.mktemp("stored")
+    for i, c in enumerate(cases):
+        out = d / f"r{i:02d}.json"
+        hostlib.generate_json([[tuple(p) for p in cc] for cc in c["contours"]], str(out), c["base_name"],
+                              c["original_width"], c["original_height"])
+        assert out.read_bytes() == c["expected"].encode("utf-8"), (i, c["base_name"])
+    if not os.path.exists(PROBE):
+        return
+
+    @settings(max_examples=25, deadline=None)
+    @given(*_POLY_LIVE)
+    def live(contours, base):
+        out = tmp_path_factory.mktemp("j") / "o.json"
+        hostlib.generate_json(contours, str(out), base, 1234, 987)
+        stdin = f"{len(contours)}\n" + "".join(f"{len(c)} " + " ".join(f"{x} {y}" for x, y in c) + "\n" for c in contours)
+        want = subprocess.run([PROBE, "poly", base, "1234", "987"], input=stdin.encode(), check=True, capture_output=True).stdout
+        assert out.read_bytes() == want
+
+    live()
 
 
 # ---------------------------------------------------------------- PNG codec vs PIL, and process_single_mask end to end

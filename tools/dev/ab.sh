@@ -8,7 +8,7 @@ extra=""; [ "$algo" = bf16 ] && extra="--conv-algo bf16 --batch 128"
 for round in 1 2; do
   for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}
-    env $envs python bench.py $extra --steps 10 --warmup 3 --no-cpu-baseline --no-extras --per-layer \
+    env $envs python bench.py --full $extra --steps 10 --warmup 3 --no-cpu-baseline --no-extras --per-layer \
         > "$out/${name}_r${round}.json" 2> "$out/${name}_r${round}.txt" || echo "  ($name: bench exit code $? -- expected for timing-only experiment builds whose results are wrong)"
     python - "$out/${name}_r${round}.json" "$name r$round" <<'PY'
 import json,sys

@@ -18,9 +18,9 @@ PY
 for round in 1 2; do
   for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}
-    env $envs python bench.py $C3 --no-cpu-baseline --no-extras --per-layer > "$out/c3_${name}_r${round}.json" 2> "$out/c3_${name}_r${round}.txt" || echo "  (config3 $name: bench exit code $?)"
+    env $envs python bench.py --full $C3 --no-cpu-baseline --no-extras --per-layer > "$out/c3_${name}_r${round}.json" 2> "$out/c3_${name}_r${round}.txt" || echo "  (config3 $name: bench exit code $?)"
     show "$out/c3_${name}_r${round}.json" "config3 $name r$round"
-    env $envs python bench.py $C5 --no-cpu-baseline --no-extras --per-layer > "$out/c5_${name}_r${round}.json" 2> "$out/c5_${name}_r${round}.txt" || echo "  (config5 $name: bench exit code $?)"
+    env $envs python bench.py --full $C5 --no-cpu-baseline --no-extras --per-layer > "$out/c5_${name}_r${round}.json" 2> "$out/c5_${name}_r${round}.txt" || echo "  (config5 $name: bench exit code $?)"
     show "$out/c5_${name}_r${round}.json" "config5 $name r$round"
   done
 done

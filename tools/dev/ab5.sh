@@ -6,7 +6,7 @@ mkdir -p "$out"
 for round in 1 2; do
   for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}
-    env $envs python bench.py --conv-algo fp16 --size 1024 --in-ch 3 --base 32 --levels 5 --batch 8 --micro-batch 8 --steps 10 --warmup 3 \
+    env $envs python bench.py --full --conv-algo fp16 --size 1024 --in-ch 3 --base 32 --levels 5 --batch 8 --micro-batch 8 --steps 10 --warmup 3 \
         --no-cpu-baseline --no-extras --per-layer > "$out/${name}_r${round}.json" 2> "$out/${name}_r${round}.txt"
     python - "$out/${name}_r${round}.json" "$name r$round" <<'PY'
 import json,sys

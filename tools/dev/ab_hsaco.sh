@@ -8,7 +8,7 @@ export MIUNET_LIB=$PWD/unet-medical-image-contour-segmentation-cpp_amd/libmiunet
 for round in 1 2; do
   for v in "$@"; do
     name=${v%%=*}; file=${v#*=}
-    MIUNET_WINO4A_HSACO=$PWD/$file python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --per-layer > $out/${name}_r$round.json 2> $out/${name}_r$round.txt || echo "($name: bench exit code $?)"
+    MIUNET_WINO4A_HSACO=$PWD/$file python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --per-layer > $out/${name}_r$round.json 2> $out/${name}_r$round.txt || echo "($name: bench exit code $?)"
     python - $out/${name}_r$round.json $out/${name}_r$round.txt "$name r$round" <<'PY'
 import json,sys,re
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -16,9 +16,9 @@ PY
 for round in 1 2; do
   for v in "$@"; do
     name=${v%%:*}; lib=${v#*:}
-    MIUNET_LIB=$lib python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$out/fp32_${name}_r$round.json" 2> "$out/fp32_${name}_r$round.err"; show "$out/fp32_${name}_r$round.json" "configs[1] fp32 $name r$round"
-    MIUNET_LIB=$lib python bench.py --conv-algo bf16 --batch 128 --steps 5 --no-cpu-baseline --no-extras > "$out/bf16_${name}_r$round.json" 2> "$out/bf16_${name}_r$round.err"; show "$out/bf16_${name}_r$round.json" "configs[2] bf16 $name r$round"
-    MIUNET_LIB=$lib python bench.py $C5 --steps 10 --no-cpu-baseline --no-extras > "$out/fp16_${name}_r$round.json" 2> "$out/fp16_${name}_r$round.err"; show "$out/fp16_${name}_r$round.json" "configs[4] fp16 $name r$round"
+    MIUNET_LIB=$lib python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$out/fp32_${name}_r$round.json" 2> "$out/fp32_${name}_r$round.err"; show "$out/fp32_${name}_r$round.json" "configs[1] fp32 $name r$round"
+    MIUNET_LIB=$lib python bench.py --full --conv-algo bf16 --batch 128 --steps 5 --no-cpu-baseline --no-extras > "$out/bf16_${name}_r$round.json" 2> "$out/bf16_${name}_r$round.err"; show "$out/bf16_${name}_r$round.json" "configs[2] bf16 $name r$round"
+    MIUNET_LIB=$lib python bench.py --full $C5 --steps 10 --no-cpu-baseline --no-extras > "$out/fp16_${name}_r$round.json" 2> "$out/fp16_${name}_r$round.err"; show "$out/fp16_${name}_r$round.json" "configs[4] fp16 $name r$round"
     MIUNET_LIB=$lib python tools/dev/seg_once.py 2>&1 | grep "segment ms" | tail -1 | cut -c1-200 | sed "s/^/one-call 512^2 x16 $name r$round: /"
     MIUNET_LIB=$lib python tools/dev/seg_once.py c5 2>&1 | grep "segment ms" | tail -1 | cut -c1-200 | sed "s/^/one-call config 5 $name r$round: /"
   done

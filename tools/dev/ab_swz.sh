@@ -16,16 +16,16 @@ PY
 }
 for round in 1 2; do
   for swz in 0 1; do
-    MIUNET_LDS_SWZ=$swz python bench.py $C3 --no-cpu-baseline --no-extras --per-layer > "$out/c3_swz${swz}_r${round}.json" 2> "$out/c3_swz${swz}_r${round}.txt"
+    MIUNET_LDS_SWZ=$swz python bench.py --full $C3 --no-cpu-baseline --no-extras --per-layer > "$out/c3_swz${swz}_r${round}.json" 2> "$out/c3_swz${swz}_r${round}.txt"
     show "$out/c3_swz${swz}_r${round}.json" "config3 swz=$swz r$round"
-    MIUNET_LDS_SWZ=$swz python bench.py $C5 --no-cpu-baseline --no-extras --per-layer > "$out/c5_swz${swz}_r${round}.json" 2> "$out/c5_swz${swz}_r${round}.txt"
+    MIUNET_LDS_SWZ=$swz python bench.py --full $C5 --no-cpu-baseline --no-extras --per-layer > "$out/c5_swz${swz}_r${round}.json" 2> "$out/c5_swz${swz}_r${round}.txt"
     show "$out/c5_swz${swz}_r${round}.json" "config5 swz=$swz r$round"
   done
 done
 # counters: the program sits directly behind `--`; the switch travels in the environment of rocprofv3 itself
 for swz in 0 1; do
   export MIUNET_LDS_SWZ=$swz
-  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT --kernel-trace --output-format csv -d "$out/pmc_c3_swz$swz" -o run -- python bench.py $C3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$out/pmc_c3_swz$swz.log" || echo "pmc pass swz=$swz failed (see log)"
+  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT --kernel-trace --output-format csv -d "$out/pmc_c3_swz$swz" -o run -- python bench.py --full $C3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$out/pmc_c3_swz$swz.log" || echo "pmc pass swz=$swz failed (see log)"
   python - "$out/pmc_c3_swz$swz" "swz=$swz" <<'PY'
 import csv,glob,sys,collections
 f=glob.glob(sys.argv[1]+'/**/*counter_collection.csv', recursive=True)

@@ -10,8 +10,8 @@ tail -3 $out/tests.txt
 C5="--conv-algo fp16 --size 1024 --in-ch 3 --base 32 --levels 5 --batch 8 --micro-batch 8"
 for round in 1 2; do
   for mode in 1 0; do
-    MIUNET_FUSE_FIRST=$mode python bench.py --conv-algo bf16 --batch 128 --steps 5 --no-cpu-baseline --no-extras --per-layer > $out/bf16_ff${mode}_r$round.json 2> $out/bf16_ff${mode}_r$round.txt || exit 1
-    MIUNET_FUSE_FIRST=$mode python bench.py $C5 --steps 10 --no-cpu-baseline --no-extras --per-layer > $out/fp16_ff${mode}_r$round.json 2> $out/fp16_ff${mode}_r$round.txt || exit 1
+    MIUNET_FUSE_FIRST=$mode python bench.py --full --conv-algo bf16 --batch 128 --steps 5 --no-cpu-baseline --no-extras --per-layer > $out/bf16_ff${mode}_r$round.json 2> $out/bf16_ff${mode}_r$round.txt || exit 1
+    MIUNET_FUSE_FIRST=$mode python bench.py --full $C5 --steps 10 --no-cpu-baseline --no-extras --per-layer > $out/fp16_ff${mode}_r$round.json 2> $out/fp16_ff${mode}_r$round.txt || exit 1
     for k in bf16 fp16; do
       python - $out/${k}_ff${mode}_r$round.json "$k MIUNET_FUSE_FIRST=$mode r$round" <<'PY'
 import json, sys
