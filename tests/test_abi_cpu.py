@@ -87,3 +87,21 @@ def test_product_library_has_no_experiment_kernels():
     for name in (b"MIUNET_W4_EXP", b"MIUNET_W4S_EXP", b"MIUNET_LP2_EXP", b"MIUNET_LPR_EXP", b"MIUNET_WINO4S_ONE_WG", b"MIUNET_W4S_UD",
                  b"MIUNET_LP2_WD", b"MIUNET_LP2_NSPLIT", b"MIUNET_LP2_MINCIN", b"MIUNET_CONVT_CFG", b"MIUNET_CONVT_WPS", b"MIUNET_FIRST_RBW", b"MIUNET_WINO4A_HSACO", b"MIUNET_WINO4B_HSACO"):
         assert name not in blob, name.decode()
+    # the routing switches no test, tool or benchmark set (removed with the routes only they reached); MIUNET_WINO4 is a prefix of
+    # switches that stay, so it is looked for as a whole string
+    for name in (b"MIUNET_WINO4\0", b"MIUNET_WINO4_SPLITK", b"MIUNET_CONVT_TAPS", b"MIUNET_WINO4_ASM_B", b"MIUNET_LPR_RB"):
+        assert name not in blob, name.decode()
+
+
+def test_routing_of_every_shipped_layer(tmp_path):
+    """csrc/routing.cpp on a CPU: the kernel of every conv layer of the fp32, bf16 and fp16 plans (batch 1 to 16, numeric guard
+    tripped, MIUNET_SPLITK=0) is the one the engine launched before the routing had one owner (tests/cpu/route_test.cpp)."""
+    import subprocess
+
+    exe = tmp_path / "route_test"
+    pkg = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "route_test.cpp"), os.path.join(pkg, "csrc", "routing.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, timeout=120)
+    assert r.returncode == 0, r.stdout.decode()[-4000:] + r.stderr.decode()[-2000:]
+    assert b"all routing checks passed" in r.stdout

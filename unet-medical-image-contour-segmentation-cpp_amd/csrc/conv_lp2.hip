@@ -56,13 +56,14 @@
 #endif
 #include "kernel_common.h"
 #include "lpr_common.h"
+#include "routing.h"
 
 namespace miunet {
 
 template <typename T> struct Lp2Vec { typedef T x8 __attribute__((ext_vector_type(8))); };
 
 struct LP2 {
-    static constexpr int TH = 16, MT = 4;
+    static constexpr int TH = LP2_TILE_ROWS, MT = 4;
     static constexpr int ROW = KC_BF16;                      // 16-bit elements per pixel (64 bytes, unpadded: pieces are swizzled)
     static constexpr int PW = 34, PH = TH + 2, NPIX = PW * PH;
     static constexpr int A_LOADS = (NPIX + 15) / 16;         // wave-wide LDS-DMA loads of 16 pixels
@@ -537,26 +538,6 @@ static hipError_t launch_lp2_cfg(const ConvArgs &a, hipStream_t s)
 #endif
     hipError_t e = launch(conv3x3_lp2<T, OUT_LP, 0>);
     return e;
-}
-
-// Which layers it takes (measured per layer at batch 16, r02): faster than the 2 x 2 kernel of conv_lp.hip from Cin = 256 up
-// (down4.c2 0.280 -> 0.226 ms, up1.c1 0.552 -> 0.459), 3-5 % faster at Cin = 128 with the LDS-transposed stores (level with the
-// 256-store epilogue it had first), slower below.  MIUNET_LP2: 0 = never; 2 = every Cout % 128 == 0 layer whatever its size (parity tests).
-bool conv3x3_lp2_takes(const ConvArgs &a)
-{
-    const int mode = routing_of(a).lp2;
-    if (mode == 0) return false;
-    if (a.head_w != nullptr || a.Cout % 128 != 0 || a.Cin % 8 || a.ldc % 8 || a.CoutPad % NPAD) return false;
-    if (mode == 2) return true;
-    const long long nwg = (long long)((a.W + 31) / 32) * ((a.H + LP2::TH - 1) / LP2::TH) * a.B * (a.Cout / 128);
-    // from Cin = 128 since the 16-byte-store epilogue (same card, config 3: down1.c2 0.333 -> 0.322 ms, up3.c2 0.313 -> 0.298, down2.c1
-    // 0.159 -> 0.154; config 5 unchanged); MIUNET_LP2_MINCIN moves the threshold
-#ifdef MIUNET_EXPERIMENTS
-    static const int min_cin = [] { const char *m = getenv("MIUNET_LP2_MINCIN"); return m ? atoi(m) : 128; }();
-#else
-    constexpr int min_cin = 128;
-#endif
-    return a.Cin >= min_cin && nwg >= 192;
 }
 
 hipError_t launch_conv3x3_lp2(const ConvArgs &a, bool fp16, hipStream_t s)

@@ -4,6 +4,7 @@
 
 #include "kernel_common.h"
 #include "lpr_common.h"
+#include "routing.h"
 
 namespace miunet {
 
@@ -593,7 +594,7 @@ static hipError_t launch_lpr_cfg(const ConvArgs &a, hipStream_t s)
     using GEO = LprGeom<RB>;
     const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + GEO::TH - 1) / GEO::TH;
     const int ntiles = tiles_x * tiles_y * a.B;
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     const int grid = ntiles < cus ? ntiles : cus;
     constexpr size_t lds = LPR::lds_bytes(GEO::PLANE_BYTES, CIN, NBUF, HEAD, FIRST ? LprFirst<RB, CIN, FIRST ? FIRST : 1>::BYTES : 0);
     static_assert(lds <= 160 * 1024, "LDS of one CU");
@@ -608,63 +609,22 @@ static hipError_t launch_lpr_cfg(const ConvArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// The fused first layer (ConvArgs::first_img): 32 -> 32 channels behind a three-channel image (BASELINE config 5's inc.c2);
-// `first_cin` = channels of the image.  Not 64 -> 64: see the kernel's header.
-bool conv3x3_lpr_can_fuse_first(const ConvArgs &a, int first_cin)
-{
-    if (a.head_w != nullptr || !a.out_lp) return false;
-    return first_cin == 3 && a.Cin == 32 && a.Cout == 32;
-}
-
-static bool lpr_shape_ok(const ConvArgs &a)
-{
-    if (a.wpk == nullptr) return false;
-    if (a.head_w != nullptr) {                // fused head: 32 -> 32 channels, at most three classes, fp32 tile (never stored), no pooling
-        if (a.Cin != 32 || a.Cout != 32 || a.head_classes < 1 || a.head_classes > 3 || a.out_lp || a.pool_out != nullptr || a.head_labels == nullptr ||
-            a.head_b == nullptr)
-            return false;
-    } else if (!a.out_lp) {
-        return false;
-    }
-    if ((a.Cin != 32 && a.Cin != 64) || (a.Cout != 32 && a.Cout != 64)) return false;
-    if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < a.Cout) return false;
-    if (a.pool_out != nullptr && (a.pool_ld % 8 || (a.H & 1) || (a.W & 1))) return false;
-    // 32-bit byte offsets inside one image
-    return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && (long long)a.H * a.W * a.ldo * 2 < (1ll << 31);
-}
-
-// MIUNET_LPR = 0: never; 1 (default): the shapes above when the tiles fill the chip four times over; 2: whatever the grid
-// (parity tests on small inputs)
-bool conv3x3_lpr_takes(const ConvArgs &a)
-{
-    const Routing rt = routing_of(a);
-    const int mode = rt.lpr;
-    if (mode == 0 || !lpr_shape_ok(a)) return false;
-    const long long ntiles = (long long)((a.W + 31) / 32) * ((a.H + 15) / 16) * a.B;     // 16-row tiles (Cin = 32); twice as many of 8 rows
-    return mode == 2 || ntiles >= 4 * rt.cus;
-}
-
 template <typename T>
 static hipError_t launch_lpr(const ConvArgs &a, hipStream_t s)
 {
-    const int rb_env = routing_of(a).lpr_rb;                // MIUNET_LPR_RB = 1: 8-row tiles for every shape (A/B, parity tests)
     // the fused head keeps 8-row tiles: with two row blocks its 96 head-weight registers spill, and scratch traffic shares
     // vmcnt with the patch DMA (the compiler's waits for it drain the ring: measured 0.27 -> 0.53 ms)
-    if (a.first_img != nullptr)               // (the caller asked conv3x3_lpr_can_fuse_first)
+    if (a.first_img != nullptr)               // (routed by conv3x3_lpr_can_fuse_first)
         return (a.Cin == 32 && a.Cout == 32 && a.first_cin == 3) ? launch_lpr_cfg<T, 32, 1, 2, 2, false, 3>(a, s) : hipErrorInvalidValue;
     if (a.head_w != nullptr) return launch_lpr_cfg<T, 32, 1, 4, 1, true>(a, s);
-    if (rb_env == 2) {
-        if (a.Cin == 32 && a.Cout == 32) return launch_lpr_cfg<T, 32, 1, 3, 2>(a, s);
-        if (a.Cin == 32) return launch_lpr_cfg<T, 32, 2, 4, 1>(a, s);      // 32 -> 64 with two row blocks spills (144 weight + 64 accumulator registers)
-    } else {
-        if (a.Cin == 32) return a.Cout == 32 ? launch_lpr_cfg<T, 32, 1, 4, 1>(a, s) : launch_lpr_cfg<T, 32, 2, 4, 1>(a, s);
-    }
+    if (a.Cin == 32 && a.Cout == 32) return launch_lpr_cfg<T, 32, 1, 3, 2>(a, s);
+    if (a.Cin == 32) return launch_lpr_cfg<T, 32, 2, 4, 1>(a, s);      // 32 -> 64 with two row blocks spills (144 weight + 64 accumulator registers)
     return a.Cout == 32 ? launch_lpr_cfg<T, 64, 1, 3, 1>(a, s) : launch_lpr_cfg<T, 64, 2, 3, 1>(a, s);
 }
 
 hipError_t launch_conv3x3_lpr(const ConvArgs &a, bool fp16, hipStream_t s)
 {
-    if (!lpr_shape_ok(a)) return hipErrorInvalidValue;
+    if (!conv3x3_lpr_shape_ok(a)) return hipErrorInvalidValue;
     return fp16 ? launch_lpr<_Float16>(a, s) : launch_lpr<__bf16>(a, s);
 }
 

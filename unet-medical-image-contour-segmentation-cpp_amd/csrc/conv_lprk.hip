@@ -4,6 +4,7 @@
 
 #include "kernel_common.h"
 #include "lpr_common.h"
+#include "routing.h"
 
 namespace miunet {
 
@@ -26,7 +27,7 @@ namespace miunet {
 // (the other resident-weight kernels are), identical to fp32 re-association noise before the single 16-bit rounding
 // (tests/test_gpu_bf16.py::test_conv3x3_resident_weights_k_split, tests/test_gpu_insitu.py).
 struct LPRK {
-    static constexpr int CIN = 128, COUT = 64, TH = 4, PW = 34, PH = TH + 2, NPIX = PW * PH;
+    static constexpr int CIN = LPRK_CIN, COUT = LPRK_COUT, TH = LPRK_TILE_ROWS, PW = 34, PH = TH + 2, NPIX = PW * PH;
     static constexpr int PLANES = CIN / 32;
     static constexpr int PLANE_LOADS = (NPIX + 15) / 16;          // 13 wave-wide LDS-DMA loads per 32-channel plane
     static constexpr int PLANE_BYTES = PLANE_LOADS * 1024;
@@ -242,30 +243,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_lprk(const ConvArgs a, const i
     }
 }
 
-static bool lprk_shape_ok(const ConvArgs &a)
-{
-    if (a.wpk == nullptr || !a.out_lp || a.head_w != nullptr || a.pool_out != nullptr) return false;
-    if (a.Cin != LPRK::CIN || a.Cout != LPRK::COUT) return false;
-    if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < a.Cout) return false;
-    return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && (long long)a.H * a.W * a.ldo * 2 < (1ll << 31);
-}
-
-// MIUNET_LPRK (Routing::lprk) = 0: never; 1 (default): 128 -> 64, 16-bit output, no pooling, when the tiles fill the chip four
-// times over; 2: whatever the grid (parity tests on small inputs)
-bool conv3x3_lprk_takes(const ConvArgs &a)
-{
-    const Routing rt = routing_of(a);
-    if (rt.lprk == 0 || !lprk_shape_ok(a)) return false;
-    const long long ntiles = (long long)((a.W + 31) / 32) * ((a.H + LPRK::TH - 1) / LPRK::TH) * a.B;
-    return rt.lprk == 2 || ntiles >= 4 * rt.cus;
-}
-
 template <typename T>
 static hipError_t launch_lprk(const ConvArgs &a, hipStream_t s)
 {
     const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + LPRK::TH - 1) / LPRK::TH;
     const int ntiles = tiles_x * tiles_y * a.B;
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     const int grid = ntiles < cus ? ntiles : cus;
     static_assert(LPRK::LDS_BYTES <= 160 * 1024, "LDS of one CU");
     auto kern = conv3x3_lprk<T>;
@@ -276,7 +259,7 @@ static hipError_t launch_lprk(const ConvArgs &a, hipStream_t s)
 
 hipError_t launch_conv3x3_lprk(const ConvArgs &a, bool fp16, hipStream_t s)
 {
-    if (!lprk_shape_ok(a)) return hipErrorInvalidValue;
+    if (!conv3x3_lprk_shape_ok(a)) return hipErrorInvalidValue;
     return fp16 ? launch_lprk<_Float16>(a, s) : launch_lprk<__bf16>(a, s);
 }
 

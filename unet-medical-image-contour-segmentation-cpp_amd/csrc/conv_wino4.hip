@@ -527,7 +527,7 @@ static hipError_t launch_wino4_cfg(const ConvArgs &a0, hipStream_t s)
                     : exp == 3 ? conv3x3_wino4_f32<2, false, false, 3> : exp == 4 ? conv3x3_wino4_f32<2, false, false, 4>
                     : conv3x3_wino4_f32<2, false, false, 5>;
             if (hipError_t e = ensure_dynamic_lds(ke, W4::LDS_BYTES); e != hipSuccess) return e;
-            const int cus = routing_of(a).cus;
+            const int cus = a.rt.cus;
             const int ge = (exp == 5 && nwg > cus) ? cus : nwg;
             hipLaunchKernelGGL(ke, dim3(ge), dim3(256), W4::LDS_BYTES, s, a, tiles_x, tiles_y, m_tiles, nwg);
             return hipGetLastError();
@@ -537,62 +537,21 @@ static hipError_t launch_wino4_cfg(const ConvArgs &a0, hipStream_t s)
     auto kern = conv3x3_wino4_f32<NB, HEAD, false>;
     if (hipError_t e = ensure_dynamic_lds(kern, W4::LDS_BYTES); e != hipSuccess) return e;
     // one-block variant: persistent, one workgroup per CU (144 KB of LDS each); two-block variant: one tile per workgroup
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     const int grid = (NB == 1 && nwg > cus) ? cus : nwg;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), W4::LDS_BYTES, s, a, tiles_x, tiles_y, m_tiles, nwg);
     return hipGetLastError();
 }
 
-// one-block cases whose grid fills the chip twice over go to the two-workgroups-per-CU kernel (conv_wino4s.hip); small
-// grids keep the persistent kernel and its split-K
-// (MIUNET_WINO4S = 0: never; 2: every one-block case whatever its grid -- for parity tests on small shapes)
-bool conv3x3_wino4_runs_staged(const ConvArgs &a)
-{
-    const Routing rt = routing_of(a);
-    const int staged = rt.wino4s;
-    const int rem = a.Cout % 128;
-    const long long wg1 = (long long)((a.W + 15) / 16) * ((a.H + 15) / 16) * a.B * ((a.Cout + 63) / 64);
-    // ... and wider layers whose K loop is at most four chunks (down1.c1, 64 -> 128: 0.521 -> 0.488 ms); with eight chunks and
-    // more the two-block kernel's shared forward transform wins (measured on every such layer: 7-20 % slower staged)
-    // ... unless the assembly kernel can take the layer (down1.c1, 64 -> 128: 0.459 -> 0.415 ms same card, profiles/r04_ab_asm_routing.txt;
-    // MIUNET_WINO4_ASM = 3 keeps such a layer on the staged kernel -- A/B switch)
-    const bool asm_takes_k4 = rt.wino4_asm != 0 && rt.wino4_asm != 3 && a.Cin == 64 && conv3x3_wino4a_shape_ok(a);
-    const bool one_block = a.head_w != nullptr || !(a.Cout >= 128 && (rem == 0 || rem > 64)) || (a.Cin <= 64 && !asm_takes_k4);
-    // a.ksplit_ws == nullptr is the batch-invariant mode (MIUNET_SPLITK=0): there the choice must not depend on the batch
-    return one_block && (staged == 2 || (staged == 1 && (wg1 >= 2 * rt.cus || a.ksplit_ws == nullptr)));
-}
-
-// the hand-scheduled persistent form of the two-block kernel (csrc/wino4_asm.cpp) takes the layer when its shape fits the assembly's
-// contract and the grid is not one the launcher below would split K for (single images, deep levels: those keep the hipcc kernel)
-bool conv3x3_wino4_runs_asm(const ConvArgs &a)
-{
-    if (routing_of(a).wino4_asm == 0 || !conv3x3_wino4a_shape_ok(a) || conv3x3_wino4_runs_staged(a)) return false;
-    const long long nwg = (long long)(a.W / 16) * (a.H / 16) * a.B * (a.Cout / 128);
-    const bool split_k = a.ksplit_ws != nullptr && nwg <= 128 && a.Cin / WINO4_KC >= 8;
-    return !split_k;
-}
-
-// ... and conv3x3_wino4b for the layers conv3x3_wino4s would take (64 output channels per workgroup, big grids) when the shape fits
-bool conv3x3_wino4_runs_asm_b(const ConvArgs &a)
-{
-    return routing_of(a).wino4_asm_b != 0 && conv3x3_wino4b_shape_ok(a) && conv3x3_wino4_runs_staged(a) && a.Cout % 128 != 0;
-}
-
-hipError_t launch_conv3x3_wino4(const ConvArgs &a, hipStream_t s)
+hipError_t launch_conv3x3_wino4(const ConvArgs &a, bool one_block, hipStream_t s)
 {
     if (a.wpk4 == nullptr || a.Cin % 4 || a.ldc % 4 || a.CoutPad % NPAD) return hipErrorInvalidValue;
-    // 128 output channels per workgroup when Cout fills them; 64 for the Cout = 64 layers (and any Cout % 128 in (0, 64])
-    const int rem = a.Cout % 128;
-    if (conv3x3_wino4_runs_asm_b(a)) return launch_conv3x3_wino4b(a, s);
-    if (conv3x3_wino4_runs_staged(a)) return launch_conv3x3_wino4s(a, s);
     if (a.head_w != nullptr) {
-        if (a.Cout > 64 || a.head_classes < 1 || a.head_classes > 4 || a.pool_out != nullptr || a.head_labels == nullptr)
+        if (!one_block || a.Cout > 64 || a.head_classes < 1 || a.head_classes > 4 || a.pool_out != nullptr || a.head_labels == nullptr)
             return hipErrorInvalidValue;
         return launch_wino4_cfg<1, true>(a, s);
     }
-    if (conv3x3_wino4_runs_asm(a)) return launch_conv3x3_wino4a(a, s);
-    if (a.Cout >= 128 && (rem == 0 || rem > 64)) return launch_wino4_cfg<2, false>(a, s);
-    return launch_wino4_cfg<1, false>(a, s);
+    return one_block ? launch_wino4_cfg<1, false>(a, s) : launch_wino4_cfg<2, false>(a, s);
 }
 
 }  // namespace miunet

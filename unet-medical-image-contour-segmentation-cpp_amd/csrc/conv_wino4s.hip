@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "routing.h"
 #include "wino4_common.h"
 
 namespace miunet {
@@ -34,7 +35,7 @@ struct W4S {
     static constexpr size_t LDS_BYTES = sizeof(float) * (W4::VBUF + W4::RAW_FLOATS);          // 60,416
     static constexpr size_t LDS_BYTES_HEAD = sizeof(float) * (256 * HEAD_ROW + 4 * 64);       // the head tile (larger than V + raw) + its weights
     static constexpr int FIRST_WIN = 20;                    // fused first layer: the normalised (16 + 4)^2 window of the image behind V + raw
-    static constexpr int FIRST_WMAX = 64;                   // ... and the first layer's weights [9][Cin] + shift [Cin] (Cin <= 64: no long-lived registers)
+    static constexpr int FIRST_WMAX = WINO4S_FIRST_WMAX;                  // ... and the first layer's weights [9][Cin] + shift [Cin] (Cin <= 64: no long-lived registers)
     static constexpr size_t LDS_BYTES_FIRST = LDS_BYTES + sizeof(float) * (FIRST_WIN * FIRST_WIN + 10 * FIRST_WMAX);
     static_assert(LDS_BYTES <= sizeof(float) * 256 * HEAD_ROW, "the head launch's allocation must cover the K loop's V + raw images");
 };
@@ -429,11 +430,6 @@ static hipError_t launch_wino4s_cfg(const ConvArgs &a, hipStream_t s)
 }
 
 // the fused first layer: one input channel, whole 16-channel chunks of its output (= this layer's input), no fused head
-bool conv3x3_wino4s_can_fuse_first(const ConvArgs &a, int first_cin)
-{
-    return first_cin == 1 && a.Cin % WINO4_KC == 0 && a.Cin >= WINO4_KC && a.Cin <= W4S::FIRST_WMAX && a.head_w == nullptr && a.wpk4 != nullptr;
-}
-
 // Same contract as the one-block variant of launch_conv3x3_wino4 (a.wpk4 = U packed [Cin/16][36][CoutPad][16]); no split-K.
 hipError_t launch_conv3x3_wino4s(const ConvArgs &a, hipStream_t s)
 {

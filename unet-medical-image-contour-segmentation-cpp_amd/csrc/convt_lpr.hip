@@ -4,6 +4,7 @@
 
 #include "kernel_common.h"
 #include "lpr_common.h"
+#include "routing.h"
 
 namespace miunet {
 
@@ -198,7 +199,7 @@ static hipError_t launch_convt_lpr_cfg(const ConvArgs &a, hipStream_t s)
     constexpr int TR = 32 * 1024 / (CIN * 2) / 32;
     const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + TR - 1) / TR;
     const int ntiles = tiles_x * tiles_y * a.B;
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     const int grid = ntiles < cus ? ntiles : cus;
     constexpr size_t lds = 3 * 32 * 1024 + 8 * (size_t)(32 * (32 * NBW + 8) * 2);
     static_assert(lds <= 160 * 1024, "LDS of one CU");
@@ -206,27 +207,6 @@ static hipError_t launch_convt_lpr_cfg(const ConvArgs &a, hipStream_t s)
     if (hipError_t e = ensure_dynamic_lds(kern, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, tiles_x, tiles_y, ntiles);
     return hipGetLastError();
-}
-
-// the shapes with at most 128 weight registers per wave: Cin -> Cout = 64 -> 32, 128 -> 64, 256 -> 128 (the three largest
-// transposed convolutions of a base-32 or base-64 network); 16-bit output
-static bool convt_lpr_shape_ok(const ConvArgs &a)
-{
-    if (a.wpk == nullptr || !a.out_lp || a.head_w != nullptr || a.pool_out != nullptr) return false;
-    if (!((a.Cin == 64 && a.Cout == 32) || (a.Cin == 128 && a.Cout == 64) || (a.Cin == 256 && a.Cout == 128))) return false;
-    if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < 4 * a.Cout) return false;
-    return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && 4ll * a.H * a.W * a.ldo * 2 < (1ll << 31);
-}
-
-// MIUNET_CONVT_LPR = 0: never; 1 (default): those shapes when the tiles fill the chip four times over; 2: whatever the grid
-bool convT2x2_lpr_takes(const ConvArgs &a)
-{
-    const Routing rt = routing_of(a);
-    const int mode = rt.convt_lpr;
-    if (mode == 0 || !convt_lpr_shape_ok(a)) return false;
-    const int tr = 32 * 1024 / (a.Cin * 2) / 32;
-    const long long ntiles = (long long)((a.W + 31) / 32) * ((a.H + tr - 1) / tr) * a.B;
-    return mode == 2 || ntiles >= 4 * rt.cus;
 }
 
 template <typename T>
@@ -239,7 +219,7 @@ static hipError_t launch_convt_lpr(const ConvArgs &a, hipStream_t s)
 
 hipError_t launch_convT2x2_lpr(const ConvArgs &a, bool fp16, hipStream_t s)
 {
-    if (!convt_lpr_shape_ok(a)) return hipErrorInvalidValue;
+    if (!convT2x2_lpr_shape_ok(a)) return hipErrorInvalidValue;
     return fp16 ? launch_convt_lpr<_Float16>(a, s) : launch_convt_lpr<__bf16>(a, s);
 }
 

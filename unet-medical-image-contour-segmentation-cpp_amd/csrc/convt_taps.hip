@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "routing.h"
 
 namespace miunet {
 
@@ -213,36 +214,6 @@ static hipError_t launch_taps_cfg(const ConvArgs &a, int cpad, hipStream_t s)
     return hipGetLastError();
 }
 
-// The shape the launcher gives a layer: {MB image rows, NBK 32-channel blocks, waves per SIMD}.  Whole batches get the
-// measured-best shapes of DESIGN.md 4.4; when those leave the chip short of ~one workgroup per CU (single images, the deep
-// levels: 32 x 32 pixels x 512 channels is 64 of the large tiles) the tile shrinks to one row x 128 or 64 channels with
-// four workgroups per CU, which is latency cover for a K loop of 1024 channels rather than operand reuse.
-struct TapsShape { int mb, nbk, wps; };
-static long long taps_grid(const ConvArgs &a, const TapsShape &t)
-{
-    return (long long)((a.W + 31) / 32) * ((a.H + t.mb - 1) / t.mb) * a.B * ((a.Cout + 32 * t.nbk - 1) / (32 * t.nbk));
-}
-static TapsShape taps_shape(const ConvArgs &a)
-{
-#ifdef MIUNET_EXPERIMENTS                              // lab build only: the product library has one route per shape
-    static const int mode = [] { const char *e = getenv("MIUNET_CONVT_WPS"); return e ? atoi(e) : 2; }();
-#else
-    constexpr int mode = 2;
-#endif
-    if (mode != 2) {
-        if (a.Cout > 256) return { 1, 16, 1 };
-        if (a.Cout > 128) return { 2, 8, 1 };
-        if (a.Cout > 64) return { 4, 4, 1 };
-        return { 8, 2, 1 };
-    }
-    const TapsShape big = a.Cout > 256 ? TapsShape{ 1, 8, 2 } : a.Cout > 64 ? TapsShape{ 2, 4, 2 } : TapsShape{ 4, 2, 2 };
-    // MIUNET_CONVT_SMALL = 0: never shrink (parity tests of the large shapes on small inputs)
-    if (taps_grid(a, big) >= 192 || !routing_of(a).convt_small) return big;
-    if (a.Cout > 64 && taps_grid(a, { 1, 4, 4 }) >= 192) return { 1, 4, 4 };
-    return { 1, 2, 4 };
-}
-long long convT_taps_grid(const ConvArgs &a) { return taps_grid(a, taps_shape(a)); }
-
 // a.wpk4 = the per-tap packing [Cin^32 / 8][4 taps][convT_taps_cpad(Cout)][8]; everything else as launch_convT2x2_mfma
 hipError_t launch_convT2x2_taps(const ConvArgs &a, hipStream_t s)
 {
@@ -252,7 +223,7 @@ hipError_t launch_convT2x2_taps(const ConvArgs &a, hipStream_t s)
     // sixteen-accumulator tiles on all four layers at batch 16: up1.t 0.501 -> 0.488 ms, up2.t 0.511 -> 0.499, up3.t 0.576 ->
     // 0.529, up4.t 0.706 -> 0.630; the other eight-accumulator shapes -- <1,8> at Cout 256, <4,2> at 128, and four workgroups
     // per CU with <2,2> at 64 -- were each within 2 % or slower); MIUNET_CONVT_WPS=1 keeps the large tiles
-    const TapsShape t = taps_shape(a);
+    const TapsShape t = convT_taps_shape(a);
     const int key = t.mb * 100 + t.nbk * 10 + t.wps;
     switch (key) {
     case 182: return launch_taps_cfg<1, 8, 2>(a, cpad, s);

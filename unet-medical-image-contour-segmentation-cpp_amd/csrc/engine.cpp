@@ -23,6 +23,7 @@
 #include "copy_pool.h"
 #include "engine_internal.h"
 #include "kernels.h"
+#include "routing.h"
 
 using namespace miunet;
 
@@ -69,7 +70,6 @@ struct mi_unet {
     int algo = MI_UNET_CONV_DIRECT; // resolved conv3x3 algorithm (MI_UNET_CONV_DIRECT / _WINOGRAD / _WINOGRAD16)
     bool fuse_pool = true;          // MIUNET_FUSE_POOL=0 keeps the stand-alone pooling kernel (A/B and parity checks)
     int wino4_min_wg = 256;         // MIUNET_WINO4_MIN_WG: smallest grid the F(4x4,3x3) kernel takes (else F(2x2) + split-K)
-    bool wino4_splitk = true;       // MIUNET_WINO4_SPLITK=0: small grids go to the F(2x2) kernel's split-K instead
     Routing routing;                // kernel-routing switches + CU count, resolved at create (kernels.h)
     // numeric guard of the default fp32 plan (engine_calibrate): F(4x4,3x3) is kept only if, for THIS weight set, a probe tile's
     // logits agree with the F(2x2,3x3) plan's within `guard_limit`; otherwise every layer runs F(2x2,3x3)
@@ -299,6 +299,24 @@ void pack_conv_bf16(const float *w, const double *scale, int cin, int cout, uint
                     cvt((float)((double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0)));
 }
 
+// conv3x3 (PyTorch [Cout][Cin][3][3], per-channel scale) -> MFMA layout [Cin/16][9][CoutPad][16]
+void pack_conv_mfma(const float *w, const double *scale, int cin, int cout, float *dst, size_t cpad)
+{
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < 9; ++t)
+                dst[(((size_t)(ci / KC) * 9 + t) * cpad + co) * KC + ci % KC] = (float)((double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0));
+}
+
+// convT (PyTorch [Cin][Cout][2][2]) -> MFMA layout [Cin/16][1][NPad][16] with n = k * Cout + co
+void pack_convT_mfma(const float *w, int cin, int cout, float *dst, size_t npad)
+{
+    for (int ci = 0; ci < cin; ++ci)
+        for (int co = 0; co < cout; ++co)
+            for (int k = 0; k < 4; ++k)
+                dst[((size_t)(ci / KC) * npad + (size_t)k * cout + co) * KC + ci % KC] = w[((size_t)ci * cout + co) * 4 + k];
+}
+
 // convT (PyTorch [Cin][Cout][2][2]) -> bf16 [Cin/32][1][NPad][32] with n = k * Cout + co
 void pack_convT_bf16(const float *w, int cin, int cout, uint16_t *dst, size_t npad, lp_cvt_fn cvt = nullptr)
 {
@@ -308,18 +326,6 @@ void pack_convT_bf16(const float *w, int cin, int cout, uint16_t *dst, size_t np
             for (int k = 0; k < 4; ++k)
                 dst[((size_t)(ci / KC_BF16) * npad + (size_t)k * cout + co) * KC_BF16 + ci % KC_BF16] =
                     cvt(w[((size_t)ci * cout + co) * 4 + k]);
-}
-
-bool convT_taps_enabled()
-{
-    const char *e = std::getenv("MIUNET_CONVT_TAPS");
-    return !(e && e[0] == '0');
-}
-
-bool wino4_enabled()
-{
-    const char *e = std::getenv("MIUNET_WINO4");
-    return !(e && e[0] == '0');
 }
 
 // parse "MIUNETW1" (miunet/spec.py), fold BN, repack
@@ -381,7 +387,7 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
             off.w = alloc((size_t)nch * 16 * cpad * WINO_KC);
             if (algo == MI_UNET_CONV_WINOGRAD16) pack_wino16(w, sc.data(), cin, cout, &out[off.w], cpad);
             else pack_wino(w, sc.data(), cin, cout, &out[off.w], cpad);
-            if (algo == MI_UNET_CONV_WINOGRAD && cout % 64 == 0 && wino4_enabled()) {   // second packing: the F(4x4,3x3) kernel takes
+            if (algo == MI_UNET_CONV_WINOGRAD && cout % 64 == 0) {   // second packing: the F(4x4,3x3) kernel takes
                 const int nch4 = (cin + WINO4_KC - 1) / WINO4_KC;                      // the layer whenever its grid fills the chip
                 off.w4 = alloc((size_t)nch4 * 36 * cpad * WINO4_KC);
                 pack_wino4(w, sc.data(), cin, cout, &out[off.w4], cpad);
@@ -390,11 +396,7 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
             const int nch = (cin + KC - 1) / KC;
             const size_t cpad = round_up(cout, NPAD);
             off.w = alloc((size_t)nch * 9 * cpad * KC);
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        out[off.w + (((size_t)(ci / KC) * 9 + t) * cpad + co) * KC + ci % KC] =
-                            (float)((double)w[((size_t)co * cin + ci) * 9 + t] * sc[co]);
+            pack_conv_mfma(w, sc.data(), cin, cout, &out[off.w], cpad);
         }
         hw.conv.push_back(off);
         return 0;
@@ -421,11 +423,8 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
         } else {
             const int nch = (cin + KC - 1) / KC;
             off.w = alloc((size_t)nch * npad * KC);
-            for (int ci = 0; ci < cin; ++ci)
-                for (int co = 0; co < cout; ++co)
-                    for (int k = 0; k < 4; ++k)
-                        out[off.w + ((size_t)(ci / KC) * npad + (size_t)k * cout + co) * KC + ci % KC] = w[((size_t)ci * cout + co) * 4 + k];
-            if (cout % 64 == 0 && convT_taps_enabled()) {      // second packing: the per-tap GEMM kernel (convt_taps.hip)
+            pack_convT_mfma(w, cin, cout, &out[off.w], npad);
+            if (cout % 64 == 0) {      // second packing: the per-tap GEMM kernel (convt_taps.hip)
                 off.w4 = alloc(convT_taps_floats(cin, cout));
                 pack_convT_taps(w, cin, cout, &out[off.w4]);
             }
@@ -601,68 +600,158 @@ int download_tensor(hipStream_t s, const void *d, int bits, int lp_kind, size_t 
     return 0;
 }
 
+// One step of the plan as this micro-batch launches it: its arguments (CONV / CONVT) and the route with the fusions granted.
+struct Launch {
+    ConvArgs a{};
+    RouteChoice rc{ Route::FIRST, 0 };
+    bool skip = false;            // done by a neighbour: pooling by its producer, the first layer by inc.c2, the head by the last conv
+};
+
+// Route every step for batch B (routing.cpp decides; the engine only fills in the arguments and the fusions it asks for).
+void route_plan(const mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits, int lp_kind, std::vector<Launch> &out)
+{
+    const RoutePolicy pol{ h->algo, h->wino4_guard_tripped, h->wino4_min_wg };
+    out.assign(h->plan.size(), Launch{});
+    for (size_t i = 0; i < h->plan.size(); ++i) {
+        const Step &st = h->plan[i];
+        Launch &l = out[i];
+        if (st.fused_away) l.skip = true;
+        if (st.kind == Step::FIRST) l.rc.route = Route::FIRST;
+        else if (st.kind == Step::POOL) l.rc.route = Route::POOL;
+        else if (st.kind == Step::HEAD) l.rc.route = Route::HEAD;
+        else if (st.kind == Step::CONVT) {
+            l.a = st.a; l.a.B = B; l.a.rt = h->routing;
+            l.a.out_lp = lp_kind != 0 ? 1 : 0;
+            l.rc.route = route_convT(l.a, pol);
+        } else {
+            ConvArgs &a = l.a;
+            a = st.a; a.B = B; a.rt = h->routing;
+            a.ksplit_ws = h->d_ksplit; a.ksplit_ws_bytes = h->ksplit_bytes;
+            // 16-bit pipelines: every activation tensor is bf16 / fp16 in HBM except the fp32 head's input
+            a.out_lp = (lp_kind != 0 && !st.feeds_head) ? 1 : 0;
+            unsigned want = 0;
+            if (st.head_step >= 0) {              // the 1x1 head + argmax in the epilogue: this layer's activations never reach HBM
+                const Step &hd = h->plan[st.head_step];
+                a.head_w = hd.w; a.head_b = hd.shift; a.head_classes = hd.Cout;
+                a.head_logits = d_logits; a.head_labels = d_labels;
+                want |= FUSE_HEAD;
+            }
+            const Step *first = (i == 1 && h->plan[0].kind == Step::FIRST) ? &h->plan[0] : nullptr;
+            if (first) {                          // the first layer in this launch's loader: its tensor is neither written nor read back
+                a.first_cin = first->C;
+                want |= FUSE_FIRST;
+            }
+            l.rc = route_conv(a, pol, want);
+            if (l.rc.fused & FUSE_HEAD) out[st.head_step].skip = true;
+            else { a.head_w = a.head_b = nullptr; a.head_classes = 0; a.head_logits = nullptr; a.head_labels = nullptr; }
+            if (l.rc.fused & FUSE_FIRST) {
+                a.first_img = d_imgs; a.first_lut = h->d_lut; a.first_w = first->w; a.first_shift = first->shift;
+                out[0].skip = true;
+            } else {
+                a.first_cin = 0;
+            }
+        }
+    }
+}
+
+hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s)
+{
+    switch (r) {
+#define MIUNET_ROUTE_LAUNCH(id, name, call) case Route::id: return call;
+        MIUNET_ROUTES(MIUNET_ROUTE_LAUNCH)
+#undef MIUNET_ROUTE_LAUNCH
+    }
+    return hipErrorInvalidValue;
+}
+
+// mi_unet_debug_capture: the tensor step `st` is about to read ...
+int tap_input(mi_unet *h, const Step &st, const Launch &l, const uint8_t *d_imgs, int lp_kind)
+{
+    hipStream_t s = h->stream;
+    const size_t im = (size_t)h->tap.img;
+    const int abits = lp_kind ? 16 : 32;
+    if (st.kind == Step::FIRST || (l.rc.fused & FUSE_FIRST)) {
+        // (a step that runs the first layer in its loader reads the u8 image: that is what the caller's `in` buffer receives)
+        const Step &f = h->plan[0];
+        h->tap.info->in_bits = 8;
+        h->tap.info->fused_first = st.kind != Step::FIRST;
+        return download_tensor(s, d_imgs + im * f.H * f.W * f.C, 8, 0, (size_t)f.H * f.W, f.C, f.C, h->tap.in);
+    }
+    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
+        h->tap.info->in_bits = abits;
+        const size_t npix = (size_t)st.a.H * st.a.W;
+        return download_tensor(s, reinterpret_cast<const char *>(st.a.in) + im * npix * st.a.ldc * (abits / 8), abits, lp_kind, npix, st.a.Cin,
+                               st.a.ldc, h->tap.in);
+    }
+    const int b = st.kind == Step::HEAD ? 32 : abits;           // POOL (activation type), HEAD (always fp32)
+    h->tap.info->in_bits = b;
+    const size_t npix = (size_t)st.H * st.W;
+    const int ld = st.kind == Step::HEAD ? st.C : st.ld;
+    return download_tensor(s, reinterpret_cast<const char *>(st.src) + im * npix * ld * (b / 8), b, lp_kind, npix, st.C, ld, h->tap.in);
+}
+
+// ... and what it stored
+int tap_output(mi_unet *h, const Step &st, const Launch &l, uint8_t *d_labels, float *d_logits, int lp_kind)
+{
+    hipStream_t s = h->stream;
+    mi_unet_layer_info *ti = h->tap.info;
+    snprintf(ti->kernel, sizeof ti->kernel, "%s", route_name(l.rc.route, l.rc.fused).c_str());
+    const size_t im = (size_t)h->tap.img;
+    const int abits = lp_kind ? 16 : 32;
+    const ConvArgs &ta = l.a;
+    if (st.kind == Step::HEAD || (l.rc.fused & FUSE_HEAD)) {
+        const size_t hw = (size_t)h->cfg.height * h->cfg.width;
+        const int classes = h->cfg.classes;
+        ti->fused_head = st.kind == Step::CONV;
+        ti->out_bits = 32;
+        if (d_logits)
+            if (int rc = download_tensor(s, d_logits + im * classes * hw, 32, 0, classes * hw, 1, 1, h->tap.out)) return rc;
+        if (h->tap.labels) {
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpy(h->tap.labels, d_labels + im * hw, hw, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+    if (st.kind == Step::FIRST) {
+        ti->out_bits = abits;
+        const size_t npix = (size_t)st.H * st.W;
+        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.ld * (abits / 8), abits, lp_kind, npix, st.Cout, st.ld, h->tap.out);
+    }
+    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
+        const int ob = (lp_kind && ta.out_lp) ? 16 : 32;
+        ti->out_bits = ob;
+        const size_t npix = (size_t)ta.H * ta.W * (st.kind == Step::CONVT ? 4 : 1);
+        if (int rc = download_tensor(s, reinterpret_cast<const char *>(ta.out) + (im * npix * ta.ldo + ta.co_off) * (ob / 8), ob, lp_kind, npix, ta.Cout,
+                                     ta.ldo, h->tap.out))
+            return rc;
+        if (st.kind == Step::CONV && ta.pool_out) {
+            ti->pooled = 1;
+            return download_tensor(s, reinterpret_cast<const char *>(ta.pool_out) + im * (npix / 4) * ta.pool_ld * (ob / 8), ob, lp_kind, npix / 4,
+                                   ta.Cout, ta.pool_ld, h->tap.pooled);
+        }
+        return 0;
+    }
+    ti->out_bits = abits;                                        // POOL
+    const size_t npix = (size_t)(st.H / 2) * (st.W / 2);
+    return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.C * (abits / 8), abits, lp_kind, npix, st.C, st.C, h->tap.out);
+}
+
 int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits)
 {
     hipStream_t s = h->stream;
-    // 16-bit pipelines: every activation tensor is bf16 / fp16 in HBM except the last conv's output (the fp32 head's input)
     const int lp_kind = h->algo == MI_UNET_CONV_BF16 ? 1 : h->algo == MI_UNET_CONV_FP16 ? 2 : 0;
-    bool head_done = false;
-    int step_index = -1;
-    // The first layer can run inside its consumer (conv_wino4s.hip, FIRST): when the default fp32 plan sends inc.c2 to the staged
-    // F(4x4) kernel at this batch size, one input channel ...  Decided per launch, like every routing choice that depends on the grid.
-    const Step *fused_first = nullptr;
-    if (h->plan.size() >= 2 && h->plan[0].kind == Step::FIRST && h->plan[1].kind == Step::CONV && lp_kind != 0 && h->routing.fuse_first &&
-        h->plan[1].head_step < 0) {
-        // ... and in the 16-bit plans when inc.c2 goes to the resident-weight kernel (conv_lpr.hip, FIRST) with one of its two fused shapes
-        ConvArgs a = h->plan[1].a; a.B = B; a.rt = h->routing;
-        a.out_lp = h->plan[1].feeds_head ? 0 : 1;
-        if (!conv3x3_lp2_takes(a) && !conv3x3_lprk_takes(a) && conv3x3_lpr_takes(a) && conv3x3_lpr_can_fuse_first(a, h->plan[0].C))
-            fused_first = &h->plan[0];
-    }
-    if (h->plan.size() >= 2 && h->plan[0].kind == Step::FIRST && h->plan[1].kind == Step::CONV && lp_kind == 0 && h->routing.fuse_first &&
-        h->algo == MI_UNET_CONV_WINOGRAD && !h->wino4_guard_tripped && h->plan[1].a.wpk4 != nullptr && h->plan[1].head_step < 0) {
-        ConvArgs a = h->plan[1].a; a.B = B; a.rt = h->routing;
-        a.ksplit_ws = h->d_ksplit; a.ksplit_ws_bytes = h->ksplit_bytes;
-        const long long wg4 = (long long)((a.W + 15) / 16) * ((a.H + 15) / 16) * B * ((a.Cout + 127) / 128);
-        if ((wg4 >= h->wino4_min_wg || h->d_ksplit == nullptr) && conv3x3_wino4_runs_staged(a) && conv3x3_wino4s_can_fuse_first(a, h->plan[0].C))
-            fused_first = &h->plan[0];
-    }
-    for (Step &st : h->plan) {
-        ++step_index;
-        const bool tapped = h->tap.layer == step_index;
-        if (st.fused_away || (st.kind == Step::HEAD && head_done) || (&st == fused_first)) {
+    std::vector<Launch> launches;
+    route_plan(h, d_imgs, B, d_labels, d_logits, lp_kind, launches);
+    for (size_t i = 0; i < h->plan.size(); ++i) {
+        const Step &st = h->plan[i];
+        const Launch &l = launches[i];
+        const bool tapped = h->tap.layer == (int)i;
+        if (l.skip) {
             if (tapped) { h->tap.info->skipped = 1; h->tap.hit = true; return 0; }
             continue;
         }
-        const bool head_was_done = head_done;
-        ConvArgs ta{};                             // the launched arguments of a tapped CONV / CONVT step
-        if (tapped) {                              // the tensor this step is about to read
-            const size_t im = (size_t)h->tap.img;
-            const int abits = lp_kind ? 16 : 32;
-            int rc = 0;
-            if (st.kind == Step::FIRST) {
-                h->tap.info->in_bits = 8;
-                rc = download_tensor(s, d_imgs + im * st.H * st.W * st.C, 8, 0, (size_t)st.H * st.W, st.C, st.C, h->tap.in);
-            } else if (st.kind == Step::CONV && fused_first != nullptr && step_index == 1) {
-                // the step reads the u8 image: the first layer runs inside it (what the caller's `in` buffer receives is the image)
-                h->tap.info->in_bits = 8;
-                h->tap.info->fused_first = 1;
-                rc = download_tensor(s, d_imgs + im * fused_first->H * fused_first->W * fused_first->C, 8, 0, (size_t)fused_first->H * fused_first->W,
-                                     fused_first->C, fused_first->C, h->tap.in);
-            } else if (st.kind == Step::CONV || st.kind == Step::CONVT) {
-                h->tap.info->in_bits = abits;
-                const size_t npix = (size_t)st.a.H * st.a.W;
-                rc = download_tensor(s, reinterpret_cast<const char *>(st.a.in) + im * npix * st.a.ldc * (abits / 8), abits, lp_kind, npix,
-                                     st.a.Cin, st.a.ldc, h->tap.in);
-            } else {                               // POOL (activation type), HEAD (always fp32)
-                const int b = st.kind == Step::HEAD ? 32 : abits;
-                h->tap.info->in_bits = b;
-                const size_t npix = (size_t)st.H * st.W;
-                const int ld = st.kind == Step::HEAD ? st.C : st.ld;
-                rc = download_tensor(s, reinterpret_cast<const char *>(st.src) + im * npix * ld * (b / 8), b, lp_kind, npix, st.C, ld, h->tap.in);
-            }
-            if (rc) return rc;
-        }
+        if (tapped)
+            if (int rc = tap_input(h, st, l, d_imgs, lp_kind)) return rc;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->profiling) {
             while (h->ev_pool.size() < h->ev_used + 2) {
@@ -674,134 +763,24 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
             e1 = h->ev_pool[h->ev_used++];
             HIP_TRY(hipEventRecord(e0, s));
         }
-        const char *kname = "";
-        hipError_t e = hipSuccess;
-        switch (st.kind) {
-        case Step::FIRST:
-            kname = "conv3x3_first";
-            e = launch_conv3x3_first(d_imgs, h->d_lut, st.w, st.shift, st.dst, B, st.H, st.W, st.C, st.Cout, st.ld, lp_kind, s, &h->routing);
+        hipError_t e;
+        switch (l.rc.route) {
+        case Route::FIRST:
+            e = launch_conv3x3_first(d_imgs, h->d_lut, st.w, st.shift, st.dst, B, st.H, st.W, st.C, st.Cout, st.ld, lp_kind, h->routing, s);
             break;
-        case Step::CONV: {
-            ConvArgs a = st.a; a.B = B; a.rt = h->routing;
-            a.ksplit_ws = h->d_ksplit; a.ksplit_ws_bytes = h->ksplit_bytes;
-            a.out_lp = (lp_kind != 0 && !st.feeds_head) ? 1 : 0;
-            if (lp_kind != 0 && st.head_step >= 0) {   // fused 1x1 head + argmax: this layer's activations never reach HBM
-                const Step &hd = h->plan[st.head_step];
-                a.head_w = hd.w; a.head_b = hd.shift; a.head_classes = hd.Cout;
-                a.head_logits = d_logits; a.head_labels = d_labels;
-                head_done = true;
-            }
-            if (lp_kind != 0 && conv3x3_lp2_takes(a)) {          // wide layer: 4 x 4 register tile per wave (conv_lp2.hip)
-                kname = lp_kind == 1 ? "conv3x3_bf16w" : "conv3x3_fp16w";
-                e = launch_conv3x3_lp2(a, lp_kind == 2, s);
-            }
-            else if (lp_kind != 0 && conv3x3_lprk_takes(a)) {    // 128 -> 64: weights in registers, K split over a wave pair (conv_lprk.hip)
-                kname = lp_kind == 1 ? "conv3x3_bf16k" : "conv3x3_fp16k";
-                e = launch_conv3x3_lprk(a, lp_kind == 2, s);
-            }
-            else if (lp_kind != 0 && conv3x3_lpr_takes(a)) {     // narrow layer: weights in registers, persistent (conv_lpr.hip)
-                if (fused_first != nullptr && step_index == 1) {           // the first layer runs in this launch's loader
-                    a.first_img = d_imgs; a.first_cin = fused_first->C; a.first_lut = h->d_lut; a.first_w = fused_first->w; a.first_shift = fused_first->shift;
-                }
-                kname = lp_kind == 1 ? (head_done ? "conv3x3_bf16r+head" : a.first_img ? "conv3x3_bf16r+first" : "conv3x3_bf16r")
-                                     : (head_done ? "conv3x3_fp16r+head" : a.first_img ? "conv3x3_fp16r+first" : "conv3x3_fp16r");
-                e = launch_conv3x3_lpr(a, lp_kind == 2, s);
-            }
-            else if (h->algo == MI_UNET_CONV_BF16) { kname = head_done ? "conv3x3_bf16+head" : "conv3x3_bf16"; e = launch_conv3x3_bf16(a, s); }
-            else if (h->algo == MI_UNET_CONV_FP16) { kname = head_done ? "conv3x3_fp16+head" : "conv3x3_fp16"; e = launch_conv3x3_fp16(a, s); }
-            else if (h->algo == MI_UNET_CONV_WINOGRAD16) { kname = "conv3x3_wino16"; e = launch_conv3x3_wino16(a, s); }
-            else if (h->algo == MI_UNET_CONV_WINOGRAD) {
-                // F(4x4,3x3) where it was packed (Cout % 64 == 0) and its 16x16-pixel x 128-channel grid fills the chip;
-                // small grids (single images, deep levels) stay on F(2x2,3x3), which can split K
-                // (MIUNET_SPLITK=0 = batch-invariant mode: no split-K workspace, and the choice must not depend on B either)
-                const long long wg4 = (long long)((a.W + 15) / 16) * ((a.H + 15) / 16) * B * ((a.Cout + 127) / 128);
-                const int min_wg4 = h->wino4_min_wg;
-                // ... or whose grid is so small that the launcher splits K (<= 128 workgroups, >= 8 chunks of 16 channels)
-                const bool split4 = h->wino4_splitk && h->d_ksplit != nullptr && wg4 <= 128 && a.Cin >= 128 && st.head_step < 0;
-                if (a.wpk4 != nullptr && !h->wino4_guard_tripped && (wg4 >= min_wg4 || h->d_ksplit == nullptr || split4)) {
-                    if (st.head_step >= 0) {   // fused 1x1 head + argmax: this layer's activations never reach HBM
-                        const Step &hd = h->plan[st.head_step];
-                        a.head_w = hd.w; a.head_b = hd.shift; a.head_classes = hd.Cout;
-                        a.head_logits = d_logits; a.head_labels = d_labels;
-                        head_done = true;
-                    }
-                    const bool staged = conv3x3_wino4_runs_staged(a);      // conv_wino4s.hip: two workgroups per CU
-                    if (fused_first != nullptr && step_index == 1) {        // the first layer runs in this launch's loader
-                        a.first_img = d_imgs; a.first_lut = h->d_lut; a.first_w = fused_first->w; a.first_shift = fused_first->shift;
-                    }
-                    kname = (staged && conv3x3_wino4_runs_asm_b(a)) ? "conv3x3_wino4b"
-                          : staged ? (head_done ? "conv3x3_wino4s+head" : a.first_img ? "conv3x3_wino4s+first" : "conv3x3_wino4s")
-                          : conv3x3_wino4_runs_asm(a) ? "conv3x3_wino4a" : (head_done ? "conv3x3_wino4+head" : "conv3x3_wino4");
-                    e = launch_conv3x3_wino4(a, s);
-                }
-                else { kname = "conv3x3_wino"; e = launch_conv3x3_wino(a, s); }
-            }
-            else { kname = "conv3x3_mfma"; e = launch_conv3x3_mfma(a, s); }
-            ta = a;
-            break;
-        }
-        case Step::CONVT: {
-            ConvArgs a = st.a; a.B = B; a.rt = h->routing;
-            a.out_lp = lp_kind != 0 ? 1 : 0;
-            if (lp_kind != 0 && convT2x2_lpr_takes(a)) {          // the large 16-bit transposed convs: weights in registers (convt_lpr.hip)
-                kname = lp_kind == 1 ? "convT2x2_bf16r" : "convT2x2_fp16r";
-                e = launch_convT2x2_lpr(a, lp_kind == 2, s);
-            }
-            else if (h->algo == MI_UNET_CONV_BF16) { kname = "convT2x2_bf16"; e = launch_convT2x2_bf16(a, s); }
-            else if (h->algo == MI_UNET_CONV_FP16) { kname = "convT2x2_fp16"; e = launch_convT2x2_fp16(a, s); }
-            else if (a.wpk4 != nullptr && convT_taps_grid(a) >= 128) { kname = "convT2x2_taps"; e = launch_convT2x2_taps(a, s); }
-            else { kname = "convT2x2_mfma"; e = launch_convT2x2_mfma(a, s); }
-            ta = a;
-            break;
-        }
-        case Step::POOL:
-            kname = "maxpool2x2";
+        case Route::POOL:
             e = lp_kind ? launch_maxpool2x2_u16(st.src, st.ld, st.dst, B, st.H, st.W, st.C, s)
                         : launch_maxpool2x2(st.src, st.ld, st.dst, B, st.H, st.W, st.C, s);
             break;
-        case Step::HEAD:
-            kname = "head_argmax";
+        case Route::HEAD:
             e = launch_head_argmax(st.src, st.C, st.w, st.shift, st.Cout, d_logits, d_labels, B, st.H * st.W, s);
             break;
+        default:
+            e = launch_route(l.rc.route, l.a, s);
         }
         if (e != hipSuccess) return fail(MI_UNET_EHIP, "launch " + st.name + ": " + hipGetErrorString(e));
-        if (tapped) {                              // what the step stored
-            mi_unet_layer_info *ti = h->tap.info;
-            snprintf(ti->kernel, sizeof ti->kernel, "%s", kname);
-            const size_t im = (size_t)h->tap.img;
-            const int abits = lp_kind ? 16 : 32;
-            const int classes = h->cfg.classes;
-            int rc = 0;
-            if (st.kind == Step::HEAD || (st.kind == Step::CONV && head_done && !head_was_done)) {
-                const size_t hw = (size_t)h->cfg.height * h->cfg.width;
-                ti->fused_head = st.kind == Step::CONV;
-                ti->out_bits = 32;
-                if (d_logits) rc = download_tensor(s, d_logits + im * classes * hw, 32, 0, classes * hw, 1, 1, h->tap.out);
-                if (!rc && h->tap.labels) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    HIP_TRY(hipMemcpy(h->tap.labels, d_labels + im * hw, hw, hipMemcpyDeviceToHost));
-                }
-            } else if (st.kind == Step::FIRST) {
-                ti->out_bits = abits;
-                const size_t npix = (size_t)st.H * st.W;
-                rc = download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.ld * (abits / 8), abits, lp_kind, npix, st.Cout, st.ld, h->tap.out);
-            } else if (st.kind == Step::CONV || st.kind == Step::CONVT) {
-                const int ob = (lp_kind && ta.out_lp) ? 16 : 32;
-                ti->out_bits = ob;
-                const size_t npix = (size_t)ta.H * ta.W * (st.kind == Step::CONVT ? 4 : 1);
-                rc = download_tensor(s, reinterpret_cast<const char *>(ta.out) + (im * npix * ta.ldo + ta.co_off) * (ob / 8), ob, lp_kind, npix, ta.Cout,
-                                     ta.ldo, h->tap.out);
-                if (!rc && st.kind == Step::CONV && ta.pool_out) {
-                    ti->pooled = 1;
-                    rc = download_tensor(s, reinterpret_cast<const char *>(ta.pool_out) + im * (npix / 4) * ta.pool_ld * (ob / 8), ob, lp_kind, npix / 4,
-                                         ta.Cout, ta.pool_ld, h->tap.pooled);
-                }
-            } else {                               // POOL
-                ti->out_bits = abits;
-                const size_t npix = (size_t)(st.H / 2) * (st.W / 2);
-                rc = download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.C * (abits / 8), abits, lp_kind, npix, st.C, st.C, h->tap.out);
-            }
-            if (rc) return rc;
+        if (tapped) {
+            if (int rc = tap_output(h, st, l, d_labels, d_logits, lp_kind)) return rc;
             h->tap.hit = true;
             return 0;
         }
@@ -809,13 +788,14 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
             HIP_TRY(hipEventRecord(e1, s));
             mi_unet_kernel_stat ks{};
             snprintf(ks.name, sizeof ks.name, "%s", st.name.c_str());
-            snprintf(ks.kernel, sizeof ks.kernel, "%s", kname);
+            snprintf(ks.kernel, sizeof ks.kernel, "%s", route_name(l.rc.route, l.rc.fused).c_str());
             ks.flops = st.flops_per_img * B;
             // algorithmic bytes: the 16-bit pipelines move half of them (activations and weights are 2 bytes)
             ks.bytes = (st.bytes_per_img * B + st.weight_bytes) * ((lp_kind && (st.kind == Step::CONV || st.kind == Step::CONVT)) ? 0.5 : 1.0);
-            if (fused_first != nullptr && step_index == 1) {           // + the first layer's arithmetic; the image in place of its output tensor
-                ks.flops += fused_first->flops_per_img * B;
-                ks.bytes += ((double)fused_first->H * fused_first->W * fused_first->C - (lp_kind ? 2.0 : 4.0) * st.a.H * st.a.W * st.a.Cin) * B;
+            if (l.rc.fused & FUSE_FIRST) {        // + the first layer's arithmetic; the image in place of its output tensor
+                const Step &f = h->plan[0];
+                ks.flops += f.flops_per_img * B;
+                ks.bytes += ((double)f.H * f.W * f.C - (lp_kind ? 2.0 : 4.0) * st.a.H * st.a.W * st.a.Cin) * B;
             }
             ks.ms = -1.f;                      // filled by mi_unet_get_kernel_stats
             h->stats.push_back(ks);
@@ -872,20 +852,17 @@ Routing Routing::from_env()
     auto num = [](const char *name, int fallback) { const char *e = getenv(name); return e ? atoi(e) : fallback; };
     r.lp2 = num("MIUNET_LP2", 1);
     r.lpr = num("MIUNET_LPR", 1);
-    r.lpr_rb = num("MIUNET_LPR_RB", 2);
     r.lprk = num("MIUNET_LPRK", 1);
     r.convt_lpr = num("MIUNET_CONVT_LPR", 1);
     r.wino4s = num("MIUNET_WINO4S", 1);
     r.wino4_asm = num("MIUNET_WINO4_ASM", 1);
     r.fuse_first = num("MIUNET_FUSE_FIRST", 1);
-    r.wino4_asm_b = num("MIUNET_WINO4_ASM_B", 1);
     r.convt_small = num("MIUNET_CONVT_SMALL", 1) != 0;
     r.first_mfma = num("MIUNET_FIRST_MFMA", 1) != 0;
     int dev = 0;
     hipDeviceProp_t p;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
         r.cus = p.multiProcessorCount;
-    r.resolved = true;
     return r;
 }
 
@@ -975,7 +952,6 @@ int engine_calibrate(mi_unet_t *h)
     }
     std::vector<float> lg4(n_lg), lg2(n_lg);
     const int keep_min = h->wino4_min_wg;
-    const bool keep_split = h->wino4_splitk;
     float diff = 0.f, range = 0.f, diffs[2] = { 0.f, 0.f };
     bool finite = true;
     const int n_probes = mode == 3 ? 1 : 2;             // MIUNET_WINO4_GUARD=3: the noise tile alone (round 3's guard; tests)
@@ -994,7 +970,7 @@ int engine_calibrate(mi_unet_t *h)
             if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(MI_UNET_EHIP, "numeric guard: probe pass failed");
             if (!rc && hipMemcpy(lg2.data(), h->d_logits, sizeof(float) * n_lg, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_UNET_EHIP, "numeric guard: D2H failed");
         }
-        h->wino4_min_wg = keep_min; h->wino4_splitk = keep_split;
+        h->wino4_min_wg = keep_min;
         if (rc) return rc;
         for (size_t i = 0; i < n_lg; ++i) {
             const float d = std::fabs(lg4[i] - lg2[i]);
@@ -1119,7 +1095,6 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
         const char *fp = getenv("MIUNET_FUSE_POOL");
         h->fuse_pool = !(fp && !strcmp(fp, "0"));
         if (const char *mw = getenv("MIUNET_WINO4_MIN_WG")) h->wino4_min_wg = atoi(mw);
-        if (const char *sk4 = getenv("MIUNET_WINO4_SPLITK")) h->wino4_splitk = sk4[0] != '0';
         h->routing = Routing::from_env();
         const char *gr = getenv("MIUNET_GRAPH");
         h->use_graph = !(gr && !strcmp(gr, "0"));
@@ -1194,7 +1169,7 @@ int mi_unet_clone(const mi_unet_t *src, int max_batch, mi_unet_t **out)
     cfg.conv_algo = src->algo;                       // the resolved algorithm: the shared blob is packed for it
     mi_unet_t *h = nullptr;
     if (int rc = mi_unet_create(&cfg, &h)) return rc;
-    h->fuse_pool = src->fuse_pool; h->wino4_min_wg = src->wino4_min_wg; h->wino4_splitk = src->wino4_splitk;
+    h->fuse_pool = src->fuse_pool; h->wino4_min_wg = src->wino4_min_wg;
     h->routing = src->routing;                       // a clone routes exactly as its source (same device)
     h->wino4_guard_tripped = src->wino4_guard_tripped; h->guard_diff = src->guard_diff; h->guard_text = src->guard_text;
     h->weights = src->weights;                       // shared: freed with the last handle that holds it
@@ -1707,6 +1682,30 @@ int mi_unet_get_kernel_stats(mi_unet_t *h, mi_unet_kernel_stat *stats, int cap, 
     return MI_UNET_OK;
 }
 
+namespace {
+
+// mi_unet_layer_debug's ops: each runs one route -- or, for "conv3x3_wino4", the F(4x4,3x3) family as route_wino4 picks it --
+// on weights packed for it.  lp: the operands are 0 fp32, 1 bf16, 2 fp16.
+enum class Pack { NONE, FIRST, MFMA, MFMA_T, TAPS, WINO, WINO16, WINO4, LP, LP_T };
+struct DebugOp { const char *op; Route route; Pack pack; int lp; bool routed; };
+const DebugOp kDebugOps[] = {
+    { "conv3x3", Route::CONV_MFMA, Pack::MFMA, 0, false },         { "convT2x2", Route::CONVT_MFMA, Pack::MFMA_T, 0, false },
+    { "convT2x2_taps", Route::CONVT_TAPS, Pack::TAPS, 0, false },   { "conv3x3_wino", Route::CONV_WINO, Pack::WINO, 0, false },
+    { "conv3x3_wino16", Route::CONV_WINO16, Pack::WINO16, 0, false }, { "conv3x3_wino4", Route::CONV_WINO4, Pack::WINO4, 0, true },
+    { "conv3x3_wino4s", Route::CONV_WINO4S, Pack::WINO4, 0, false }, { "conv3x3_wino4a", Route::CONV_WINO4A, Pack::WINO4, 0, false },
+    { "conv3x3_wino4b", Route::CONV_WINO4B, Pack::WINO4, 0, false },
+    { "conv3x3_bf16", Route::CONV_BF16, Pack::LP, 1, false },       { "conv3x3_fp16", Route::CONV_FP16, Pack::LP, 2, false },
+    { "conv3x3_bf16w", Route::CONV_BF16W, Pack::LP, 1, false },     { "conv3x3_fp16w", Route::CONV_FP16W, Pack::LP, 2, false },
+    { "conv3x3_bf16r", Route::CONV_BF16R, Pack::LP, 1, false },     { "conv3x3_fp16r", Route::CONV_FP16R, Pack::LP, 2, false },
+    { "conv3x3_bf16k", Route::CONV_BF16K, Pack::LP, 1, false },     { "conv3x3_fp16k", Route::CONV_FP16K, Pack::LP, 2, false },
+    { "convT2x2_bf16", Route::CONVT_BF16, Pack::LP_T, 1, false },   { "convT2x2_fp16", Route::CONVT_FP16, Pack::LP_T, 2, false },
+    { "convT2x2_bf16r", Route::CONVT_BF16R, Pack::LP_T, 1, false }, { "convT2x2_fp16r", Route::CONVT_FP16R, Pack::LP_T, 2, false },
+    { "conv3x3_first", Route::FIRST, Pack::FIRST, 0, false },        { "conv3x3_first_bf16", Route::FIRST, Pack::FIRST, 1, false },
+    { "conv3x3_first_fp16", Route::FIRST, Pack::FIRST, 2, false },   { "maxpool", Route::POOL, Pack::NONE, 0, false },
+};
+
+}  // namespace
+
 int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
                         const float *scale, const float *shift, int Cout, int relu, float *out)
 {
@@ -1720,11 +1719,16 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
     if (o.size() > 5 && o.compare(o.size() - 5, 5, "_pool") == 0) { want_pool = true; o.resize(o.size() - 5); }
     float *d_pool = nullptr;
     const size_t in_n = (size_t)B * H * W * Cin;
-    if (o == "conv3x3_first" || o == "conv3x3_first_bf16" || o == "conv3x3_first_fp16") {
+    const DebugOp *dop = nullptr;
+    for (const DebugOp &k : kDebugOps)
+        if (o == k.op) dop = &k;
+    if (!dop) return fail(MI_UNET_EARG, "layer_debug: unknown op " + o);
+    const Routing rt = Routing::from_env();
+    if (dop->pack == Pack::FIRST) {
         // the first layer: `in` holds byte values 0..255 (as floats), the kernel sees the u8 image and the /255 table;
         // _bf16 / _fp16: the 16-bit pipelines' output tensor (converted back to float here)
         if (!w || Cout <= 0 || Cout % 4 || (Cin != 1 && Cin != 3) || want_pool || lp_out) return fail(MI_UNET_EARG, "layer_debug: conv3x3_first needs weights, Cin 1 or 3, Cout % 4 == 0");
-        const int kind = o == "conv3x3_first" ? 0 : o == "conv3x3_first_bf16" ? 1 : 2;
+        const int kind = dop->lp;
         std::vector<uint8_t> img(in_n);
         for (size_t i = 0; i < in_n; ++i) img[i] = (uint8_t)in[i];
         float lut[256];
@@ -1747,7 +1751,7 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
             ok(hipMemcpy(d_wf, wf.data(), sizeof(float) * wf.size(), hipMemcpyHostToDevice), "hipMemcpy") &&
             ok(hipMemcpy(d_sh, sh.data(), sizeof(float) * Cout, hipMemcpyHostToDevice), "hipMemcpy") &&
             ok(hipMemset(d_o, 0xFF, sizeof(float) * n_out), "hipMemset") &&
-            ok(launch_conv3x3_first(d_img, d_l, d_wf, d_sh, d_o, B, H, W, Cin, Cout, Cout, kind, nullptr), "launch_conv3x3_first") &&
+            ok(launch_conv3x3_first(d_img, d_l, d_wf, d_sh, d_o, B, H, W, Cin, Cout, Cout, kind, rt, nullptr), "launch_conv3x3_first") &&
             ok(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
             if (kind == 0) {
                 ok(hipMemcpy(out, d_o, sizeof(float) * n_out, hipMemcpyDeviceToHost), "hipMemcpy");
@@ -1764,89 +1768,49 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
     }
     float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr;
     std::vector<float> wpk, bias;
-    size_t out_n = 0;
+    const bool T = dop->pack == Pack::MFMA_T || dop->pack == Pack::TAPS || dop->pack == Pack::LP_T;
+    size_t out_n = dop->pack == Pack::NONE ? (size_t)B * (H / 2) * (W / 2) * Cin : (size_t)B * (T ? 4 : 1) * H * W * Cout;
     ConvArgs a{};
-    if (o == "convT2x2_taps") {
-        if (!w || Cout <= 0 || Cin % 4) return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
-        wpk.assign(convT_taps_floats(Cin, Cout), 0.f);
-        bias.assign(Cout, 0.f);
-        for (int co = 0; co < Cout; ++co) bias[co] = shift ? shift[co] : 0.f;
-        pack_convT_taps(w, Cin, Cout, wpk.data());
-        out_n = (size_t)B * 4 * H * W * Cout;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = convT_taps_cpad(Cout); a.ldo = Cout; a.co_off = 0;
-        a.relu = relu;
-    } else if (o == "conv3x3_wino4" || o == "conv3x3_wino4s" || o == "conv3x3_wino4a" || o == "conv3x3_wino4b") {
-        if (!w || Cout <= 0 || Cin % 4) return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
-        const int nch = (Cin + WINO4_KC - 1) / WINO4_KC;
-        const size_t npad = round_up((size_t)Cout, NPAD);
-        wpk.assign((size_t)nch * 36 * npad * WINO4_KC, 0.f);
-        bias.assign(Cout, 0.f);
-        std::vector<double> sc(Cout, 1.0);
-        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
-        pack_wino4(w, sc.data(), Cin, Cout, wpk.data(), npad);
-        out_n = (size_t)B * H * W * Cout;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)npad; a.ldo = Cout; a.co_off = 0;
-        a.relu = relu;
-    } else if (o == "conv3x3_wino" || o == "conv3x3_wino16") {
-        if (!w || Cout <= 0 || Cin % 4) return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
-        const int nch = (Cin + WINO_KC - 1) / WINO_KC;
-        const size_t npad = round_up((size_t)Cout, NPAD);
-        wpk.assign((size_t)nch * 16 * npad * WINO_KC, 0.f);
-        bias.assign(Cout, 0.f);
-        std::vector<double> sc(Cout, 1.0);
-        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
-        if (o == "conv3x3_wino16") pack_wino16(w, sc.data(), Cin, Cout, wpk.data(), npad);
-        else pack_wino(w, sc.data(), Cin, Cout, wpk.data(), npad);
-        out_n = (size_t)B * H * W * Cout;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)npad; a.ldo = Cout; a.co_off = 0;
-        a.relu = relu;
-    } else if (o == "conv3x3_bf16" || o == "convT2x2_bf16" || o == "conv3x3_fp16" || o == "convT2x2_fp16" || o == "conv3x3_bf16w" || o == "conv3x3_fp16w" || o == "conv3x3_bf16r" || o == "conv3x3_fp16r" || o == "conv3x3_bf16k" || o == "conv3x3_fp16k" || o == "convT2x2_bf16r" || o == "convT2x2_fp16r") {
+    a.rt = rt;
+    if (dop->pack == Pack::NONE) {
+        if (Cin % 4 || H % 2 || W % 2) return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 and even H, W");
+    } else if (dop->lp) {
         if (!w || Cout <= 0 || Cin % 8) return fail(MI_UNET_EARG, "layer_debug: 16-bit conv needs weights and Cin % 8 == 0");
-        const bool T = (o == "convT2x2_bf16" || o == "convT2x2_fp16" || o == "convT2x2_bf16r" || o == "convT2x2_fp16r");
-        const lp_cvt_fn cvt = (o == "conv3x3_fp16" || o == "convT2x2_fp16" || o == "conv3x3_fp16w" || o == "conv3x3_fp16r" || o == "conv3x3_fp16k" || o == "convT2x2_fp16r") ? fp16_bits : bf16_bits;
-        const int nch = (Cin + KC_BF16 - 1) / KC_BF16;
-        const size_t npad = round_up(T ? (size_t)4 * Cout : (size_t)Cout, NPAD);
-        wpk.assign(((size_t)nch * (T ? 1 : 9) * npad * KC_BF16 + 1) / 2, 0.f);
-        bias.assign(Cout, 0.f);
+    } else if (!w || Cout <= 0 || Cin % 4) {
+        return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
+    }
+    if (dop->pack != Pack::NONE) {
         std::vector<double> sc(Cout, 1.0);
-        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
-        if (T) pack_convT_bf16(w, Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
-        else pack_conv_bf16(w, sc.data(), Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
-        out_n = T ? (size_t)B * 4 * H * W * Cout : (size_t)B * H * W * Cout;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)npad; a.ldo = Cout; a.co_off = 0;
-        a.relu = relu;
-    } else if (o == "conv3x3" || o == "convT2x2") {
-        if (!w || Cout <= 0 || Cin % 4) return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
-        const bool T = (o == "convT2x2");
-        const int nch = (Cin + KC - 1) / KC;
-        const size_t npad = round_up(T ? (size_t)4 * Cout : (size_t)Cout, NPAD);
-        wpk.assign((size_t)nch * (T ? 1 : 9) * npad * KC, 0.f);
         bias.assign(Cout, 0.f);
-        for (int co = 0; co < Cout; ++co) bias[co] = shift ? shift[co] : 0.f;
-        if (!T) {
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        wpk[(((size_t)(ci / KC) * 9 + t) * npad + co) * KC + ci % KC] =
-                            (float)((double)w[((size_t)co * Cin + ci) * 9 + t] * (scale ? (double)scale[co] : 1.0));
-            out_n = (size_t)B * H * W * Cout;
-        } else {
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int co = 0; co < Cout; ++co)
-                    for (int k = 0; k < 4; ++k)
-                        wpk[((size_t)(ci / KC) * npad + (size_t)k * Cout + co) * KC + ci % KC] = w[((size_t)ci * Cout + co) * 4 + k];
-            out_n = (size_t)B * 4 * H * W * Cout;
+        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
+        size_t npad = round_up(T ? (size_t)4 * Cout : (size_t)Cout, NPAD);
+        const lp_cvt_fn cvt = dop->lp == 2 ? fp16_bits : bf16_bits;
+        switch (dop->pack) {
+        case Pack::MFMA: wpk.assign((size_t)((Cin + KC - 1) / KC) * 9 * npad * KC, 0.f); pack_conv_mfma(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
+        case Pack::MFMA_T: wpk.assign((size_t)((Cin + KC - 1) / KC) * npad * KC, 0.f); pack_convT_mfma(w, Cin, Cout, wpk.data(), npad); break;
+        case Pack::TAPS:
+            npad = convT_taps_cpad(Cout);
+            wpk.assign(convT_taps_floats(Cin, Cout), 0.f);
+            pack_convT_taps(w, Cin, Cout, wpk.data());
+            break;
+        case Pack::WINO: wpk.assign((size_t)((Cin + WINO_KC - 1) / WINO_KC) * 16 * npad * WINO_KC, 0.f); pack_wino(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
+        case Pack::WINO16: wpk.assign((size_t)((Cin + WINO_KC - 1) / WINO_KC) * 16 * npad * WINO_KC, 0.f); pack_wino16(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
+        case Pack::WINO4: wpk.assign((size_t)((Cin + WINO4_KC - 1) / WINO4_KC) * 36 * npad * WINO4_KC, 0.f); pack_wino4(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
+        case Pack::LP:
+            wpk.assign(((size_t)((Cin + KC_BF16 - 1) / KC_BF16) * 9 * npad * KC_BF16 + 1) / 2, 0.f);
+            pack_conv_bf16(w, sc.data(), Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
+            break;
+        case Pack::LP_T:
+            wpk.assign(((size_t)((Cin + KC_BF16 - 1) / KC_BF16) * npad * KC_BF16 + 1) / 2, 0.f);
+            pack_convT_bf16(w, Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
+            break;
+        default: break;
         }
         a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)npad; a.ldo = Cout; a.co_off = 0;
         a.relu = relu;
-    } else if (o == "maxpool") {
-        if (Cin % 4 || H % 2 || W % 2) return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 and even H, W");
-        out_n = (size_t)B * (H / 2) * (W / 2) * Cin;
-    } else {
-        return fail(MI_UNET_EARG, "layer_debug: unknown op " + o);
     }
-    const bool lp_in = (o == "conv3x3_bf16" || o == "convT2x2_bf16" || o == "conv3x3_fp16" || o == "convT2x2_fp16" || o == "conv3x3_bf16w" || o == "conv3x3_fp16w" || o == "conv3x3_bf16r" || o == "conv3x3_fp16r" || o == "conv3x3_bf16k" || o == "conv3x3_fp16k" || o == "convT2x2_bf16r" || o == "convT2x2_fp16r");
-    const bool lp_fp16 = (o == "conv3x3_fp16" || o == "convT2x2_fp16" || o == "conv3x3_fp16w" || o == "conv3x3_fp16r" || o == "conv3x3_fp16k" || o == "convT2x2_fp16r");
+    const bool lp_in = dop->lp != 0;
+    const bool lp_fp16 = dop->lp == 2;
     if (lp_out && !lp_in) return fail(MI_UNET_EARG, "layer_debug: _lpout is for the 16-bit conv ops");
     a.out_lp = lp_out ? 1 : 0;
     int rc = MI_UNET_OK;
@@ -1875,27 +1839,8 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
         DBG_TRY(hipMemcpy(d_w, wpk.data(), sizeof(float) * wpk.size(), hipMemcpyHostToDevice));
         DBG_TRY(hipMemcpy(d_b, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
         a.in = d_in; a.wpk = d_w; a.bias = d_b; a.out = d_out;
-        if (o == "conv3x3_wino4" || o == "conv3x3_wino4s" || o == "conv3x3_wino4a" || o == "conv3x3_wino4b" || o == "convT2x2_taps") a.wpk4 = d_w;
-        DBG_TRY(o == "conv3x3" ? launch_conv3x3_mfma(a, nullptr)
-                : o == "conv3x3_wino4" ? launch_conv3x3_wino4(a, nullptr)
-                : o == "conv3x3_wino4s" ? launch_conv3x3_wino4s(a, nullptr)
-                : o == "conv3x3_wino4a" ? launch_conv3x3_wino4a(a, nullptr)
-                : o == "conv3x3_wino4b" ? launch_conv3x3_wino4b(a, nullptr)
-                : o == "convT2x2_taps" ? launch_convT2x2_taps(a, nullptr)
-                : o == "conv3x3_wino" ? launch_conv3x3_wino(a, nullptr)
-                : o == "conv3x3_wino16" ? launch_conv3x3_wino16(a, nullptr)
-                : o == "conv3x3_bf16w" ? launch_conv3x3_lp2(a, false, nullptr)
-                : o == "conv3x3_fp16w" ? launch_conv3x3_lp2(a, true, nullptr)
-                : o == "conv3x3_bf16k" ? launch_conv3x3_lprk(a, false, nullptr)
-                : o == "conv3x3_fp16k" ? launch_conv3x3_lprk(a, true, nullptr)
-                : o == "conv3x3_bf16r" ? launch_conv3x3_lpr(a, false, nullptr)
-                : o == "conv3x3_fp16r" ? launch_conv3x3_lpr(a, true, nullptr)
-                : o == "convT2x2_bf16r" ? launch_convT2x2_lpr(a, false, nullptr)
-                : o == "convT2x2_fp16r" ? launch_convT2x2_lpr(a, true, nullptr)
-                : o == "conv3x3_bf16" ? launch_conv3x3_bf16(a, nullptr)
-                : o == "convT2x2_bf16" ? launch_convT2x2_bf16(a, nullptr)
-                : o == "conv3x3_fp16" ? launch_conv3x3_fp16(a, nullptr)
-                : o == "convT2x2_fp16" ? launch_convT2x2_fp16(a, nullptr) : launch_convT2x2_mfma(a, nullptr));
+        if (dop->pack == Pack::WINO4 || dop->pack == Pack::TAPS) a.wpk4 = d_w;
+        DBG_TRY(launch_route(dop->routed ? route_wino4(a) : dop->route, a, nullptr));
     } else {
         DBG_TRY(launch_maxpool2x2(d_in, Cin, d_out, B, H, W, Cin, nullptr));
     }

@@ -11,20 +11,17 @@ constexpr int KC = 16;        // input channels staged per K-chunk
 constexpr int NPAD = 128;     // packed Cout granule (covers both BN = 64 and BN = 128 tiles)
 
 // Kernel-routing switches (the MIUNET_* A/B variables) and the device's CU count, resolved ONCE per engine handle at
-// mi_unet_create and carried in every launch's arguments: a launch never calls getenv or touches shared tables, so cloned
-// contexts launching from several threads share nothing mutable, and an engine's routing cannot change under it.
-// A default-constructed Routing is unresolved: routing_of() then reads the environment at the call (mi_unet_layer_debug).
+// mi_unet_create (once per call in mi_unet_layer_debug) and carried in every launch's arguments: a launch never calls getenv or
+// touches shared tables, so cloned contexts launching from several threads share nothing mutable, and an engine's routing cannot
+// change under it.  Which kernel a layer gets is decided in routing.cpp.
 struct Routing {
-    bool resolved = false;
     int cus = 256;            // compute units of the launch device
     int lp2 = 1;              // MIUNET_LP2: 0 never, 1 default thresholds, 2 every Cout % 128 == 0 layer
     int lpr = 1;              // MIUNET_LPR: 0 never, 1 when the tiles fill the chip four times over, 2 whatever the grid
-    int lpr_rb = 2;           // MIUNET_LPR_RB: 1 = 8-row tiles for every shape
     int lprk = 1;             // MIUNET_LPRK: the 128 -> 64 K-split resident-weight kernel (conv_lprk.hip), as lpr
     int convt_lpr = 1;        // MIUNET_CONVT_LPR: as lpr
     int wino4s = 1;           // MIUNET_WINO4S: 0 never, 1 grids that fill the chip twice over, 2 every one-block case
     int fuse_first = 1;       // MIUNET_FUSE_FIRST=0: the first layer stays a kernel of its own (A/B, parity checks)
-    int wino4_asm_b = 1;      // MIUNET_WINO4_ASM_B=0: the 64-channel layers stay on conv3x3_wino4s
     int wino4_asm = 1;        // MIUNET_WINO4_ASM: 0 never, 1 the hand-scheduled persistent two-block kernel for the shapes it takes
     bool convt_small = true;  // MIUNET_CONVT_SMALL=0: the per-tap transposed conv never shrinks its tile
     bool first_mfma = true;   // MIUNET_FIRST_MFMA=0: the 16-bit pipelines' first layer stays on the VALU kernel
@@ -63,7 +60,7 @@ struct ConvArgs {
     // 16-bit kernels (conv_lp.hip): `in` always points at 16-bit activations (bf16 / fp16, NHWC, ldc in elements); out_lp
     // selects a 16-bit `out` / `pool_out` (everything but the layer in front of the fp32 head)
     int out_lp;
-    Routing rt;           // resolved by the engine; unresolved = read the environment at the call
+    Routing rt;           // resolved by the caller
     const float *head_w;
     const float *head_b;
     int head_classes;
@@ -78,8 +75,6 @@ struct ConvArgs {
     const float *first_lut, *first_w, *first_shift;
 };
 
-inline Routing routing_of(const ConvArgs &a) { return a.rt.resolved ? a.rt : Routing::from_env(); }
-
 hipError_t launch_conv3x3_mfma(const ConvArgs &a, hipStream_t s);
 
 // Winograd F(2x2,3x3) form of the same layer: a.wpk holds the TRANSFORMED weights U = G g G^T packed as
@@ -90,37 +85,26 @@ hipError_t launch_conv3x3_wino(const ConvArgs &a, hipStream_t s);
 // 8-wave / two-waves-per-SIMD re-tiling of the same algorithm on v_mfma_f32_16x16x4_f32; a.wpk is packed as
 // [Cin/8][8 position pairs][CoutPad][16] with element 4*kq + 2*(pos & 1) + s = U_pos[k = 2*kq + s].
 hipError_t launch_conv3x3_wino16(const ConvArgs &a, hipStream_t s);
-// Winograd F(4x4,3x3) on v_mfma_f32_16x16x4_f32: 16 tiles (16x16 output pixels) x 128 channels per workgroup.  a.wpk4 holds
-// U = G g G^T (6x6) packed as [Cin/16][36 positions][CoutPad][16]; no split-K (small grids stay on the F(2x2) kernel).
+// Winograd F(4x4,3x3) on v_mfma_f32_16x16x4_f32: 16 tiles (16x16 output pixels) x 128 channels per workgroup, or 64 channels
+// (one_block: persistent, the only form that fuses the 1x1 head).  a.wpk4 holds U = G g G^T (6x6) packed as
+// [Cin/16][36 positions][CoutPad][16]; the launcher splits K for grids that leave most CUs idle.
 constexpr int WINO4_KC = 16;
 constexpr int WINO4_SC = 32;
-hipError_t launch_conv3x3_wino4(const ConvArgs &a, hipStream_t s);
-// The same algorithm for Cout <= 64 per workgroup with single-buffered 70 KB of LDS and <= 256 registers, so that two
-// workgroups share a CU (conv_wino4s.hip); same packing (a.wpk4), bit-identical results, no split-K.  launch_conv3x3_wino4
-// routes its one-block cases here unless MIUNET_WINO4S=0.
+hipError_t launch_conv3x3_wino4(const ConvArgs &a, bool one_block, hipStream_t s);
+// The one-block algorithm with single-buffered 70 KB of LDS and <= 256 registers, so that two workgroups share a CU
+// (conv_wino4s.hip); same packing (a.wpk4), bit-identical results, no split-K; can run the first layer in its loader.
 hipError_t launch_conv3x3_wino4s(const ConvArgs &a, hipStream_t s);
-bool conv3x3_wino4_runs_staged(const ConvArgs &a);   // the routing decision of launch_conv3x3_wino4 (for the launch log)
-bool conv3x3_wino4s_can_fuse_first(const ConvArgs &a, int first_cin);   // shape contract of the fused first layer (conv_wino4s.hip)
-bool conv3x3_lpr_can_fuse_first(const ConvArgs &a, int first_cin);      // ... of the 16-bit resident-weight kernel (conv_lpr.hip)
 // The two-block kernel hand-scheduled in gfx950 assembly and persistent (csrc/asm/gen_wino4_asm.py, csrc/wino4_asm.cpp): same
-// packing (a.wpk4), same tensors.  shape_ok = the contract of the assembly (whole 16x16 blocks, Cin % 32 == 0 and >= 64, Cout % 128
-// == 0, fp32, no fused head); runs_asm = what launch_conv3x3_wino4 decides (shape, MIUNET_WINO4_ASM, not a split-K grid).
-bool conv3x3_wino4a_shape_ok(const ConvArgs &a);
-bool conv3x3_wino4_runs_asm(const ConvArgs &a);
+// packing (a.wpk4), same tensors; its contract is conv3x3_wino4a_shape_ok (routing.h).
 hipError_t launch_conv3x3_wino4a(const ConvArgs &a, hipStream_t s);
 // ... and its sibling for the layers with 64 output channels per workgroup: blocks of 16 x 32 pixels (32 tiles) x 64 channels, a wave
 // = 32 tiles x 16 channels, V single-buffered with a transform phase and an MFMA phase per chunk (csrc/asm/gen_wino4b_asm.py)
-bool conv3x3_wino4b_shape_ok(const ConvArgs &a);
-bool conv3x3_wino4_runs_asm_b(const ConvArgs &a);
 hipError_t launch_conv3x3_wino4b(const ConvArgs &a, hipStream_t s);
 hipError_t launch_wino_splitk_reduce(const ConvArgs &a, hipStream_t s);   // sums a.ksplit slabs of a.ksplit_ws into a.out
 hipError_t launch_convT2x2_mfma(const ConvArgs &a, hipStream_t s);
 // The transposed conv as four per-tap GEMMs sharing one A operand (convt_taps.hip): a.wpk4 holds the weights packed
 // [ceil(Cin/32)*4 chunks of 8][4 taps (dy*2+dx)][convT_taps_cpad(Cout)][8], zero-padded; other fields as above.
 inline int convT_taps_cpad(int cout) { return (cout + NPAD - 1) / NPAD * NPAD; }
-// workgroups launch_convT2x2_taps would start with the tile shape it picks for this layer (the engine keeps the direct
-// kernel below half a workgroup per CU)
-long long convT_taps_grid(const ConvArgs &a);
 hipError_t launch_convT2x2_taps(const ConvArgs &a, hipStream_t s);
 
 // BASELINE config 3: bf16 operands, fp32 accumulate on v_mfma_f32_16x16x32_bf16 (lpr_common.h: the shape the chip clocks highest).  Activations are bf16 in HBM too (rounded
@@ -132,27 +116,21 @@ hipError_t launch_convT2x2_bf16(const ConvArgs &a, hipStream_t s);
 hipError_t launch_conv3x3_fp16(const ConvArgs &a, hipStream_t s);
 hipError_t launch_convT2x2_fp16(const ConvArgs &a, hipStream_t s);
 // The wide layers (Cout % 128 == 0) of the same pipelines on a 4 x 4 register tile per wave (conv_lp2.hip): half the LDS bytes
-// per MFMA.  Same packing (a.wpk), same arithmetic; conv3x3_lp2_takes says whether the layer's grid fills the chip.
-bool conv3x3_lp2_takes(const ConvArgs &a);
+// per MFMA.  Same packing (a.wpk), same arithmetic.
 hipError_t launch_conv3x3_lp2(const ConvArgs &a, bool fp16, hipStream_t s);
 // The narrow layers (Cin, Cout in {32, 64}, 16-bit output, no fused head) with the weights resident in registers and a
 // persistent workgroup per CU streaming input patches through an LDS ring (conv_lpr.hip).  Same packing, same arithmetic.
-bool conv3x3_lpr_takes(const ConvArgs &a);
 hipError_t launch_conv3x3_lpr(const ConvArgs &a, bool fp16, hipStream_t s);
 // 128 -> 64 channels (the first convolution behind the top-level concat): the same scheme with the reduction split over a wave
 // pair, partial sums through LDS (conv_lprk.hip).  Same packing; fp32 re-association differs from conv_mfma_bf16 by one add.
-bool conv3x3_lprk_takes(const ConvArgs &a);
 hipError_t launch_conv3x3_lprk(const ConvArgs &a, bool fp16, hipStream_t s);
 // ... and the three largest transposed convolutions (Cin -> Cout = 64 -> 32, 128 -> 64, 256 -> 128; convt_lpr.hip)
-bool convT2x2_lpr_takes(const ConvArgs &a);
 hipError_t launch_convT2x2_lpr(const ConvArgs &a, bool fp16, hipStream_t s);
 
 // First layer: u8 image -> (LUT /255) -> conv3x3 (Cin = 1..4) + shift + ReLU.  w is [9][Cin][Cout] (BN scale folded).
 // out_kind: 0 = fp32 output, 1 = bf16, 2 = fp16 (the 16-bit pipelines keep every activation tensor 16-bit in HBM)
 hipError_t launch_conv3x3_first(const uint8_t *img, const float *lut256, const float *w, const float *shift, float *out,
-                                int B, int H, int W, int Cin, int Cout, int ldo, int out_kind, hipStream_t s,
-                                const Routing *rt = nullptr);
-// Same arithmetic on an fp32 NHWC input (layer_debug / small-Cin fallback is not needed elsewhere).
+                                int B, int H, int W, int Cin, int Cout, int ldo, int out_kind, const Routing &rt, hipStream_t s);
 
 hipError_t launch_maxpool2x2(const float *in, int ldc, float *out, int B, int H, int W, int C, hipStream_t s);
 // the same on 16-bit post-ReLU tensors (bf16 or fp16: non-negative values order like their bit patterns)

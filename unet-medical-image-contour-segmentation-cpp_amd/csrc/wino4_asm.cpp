@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "routing.h"
 
 extern "C" const unsigned char miunet_wino4a_hsaco[];
 extern "C" const unsigned char miunet_wino4a_hsaco_end[];
@@ -81,23 +82,6 @@ uint32_t magic_of(uint32_t d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + 
 
 }  // namespace
 
-// The shapes the assembly kernel takes: whole 16x16 blocks, an even number (>= 4) of 16-channel K chunks, whole 128-channel
-// groups, fp32 in and out, no fused head; every byte offset inside one image below 2^31 and the tile decode exact.
-bool conv3x3_wino4a_shape_ok(const ConvArgs &a)
-{
-    if (a.wpk4 == nullptr || a.head_w != nullptr || a.out_lp) return false;
-    if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.H % 16 || a.W % 16) return false;
-    if (a.Cin % 32 || a.Cin < 64 || a.ldc % 4 || a.ldc < a.Cin) return false;
-    if (a.Cout % 128 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4) return false;
-    if (a.pool_out != nullptr && a.pool_ld % 4) return false;
-    const long long lim = 1ll << 31;
-    if ((long long)a.H * a.W * a.ldc * 4 >= lim || (long long)a.H * a.W * a.ldo * 4 >= lim) return false;
-    if ((long long)(a.Cin / 16) * 36 * a.CoutPad * 64 >= lim) return false;
-    const long long m_tiles = (long long)(a.W / 16) * (a.H / 16) * a.B, nwg = m_tiles * (a.Cout / 128);
-    if (nwg >= (1ll << 24) || nwg * m_tiles >= (1ll << 32)) return false;
-    return true;
-}
-
 hipError_t launch_conv3x3_wino4a(const ConvArgs &a, hipStream_t s)
 {
     if (!conv3x3_wino4a_shape_ok(a)) return hipErrorInvalidValue;
@@ -118,7 +102,7 @@ hipError_t launch_conv3x3_wino4a(const ConvArgs &a, hipStream_t s)
     k.pix_pool_bytes = pool ? (uint32_t)a.pool_ld * 4u : 0u;
     k.img_pool_bytes = pool ? (uint32_t)(a.H / 2) * (a.W / 2) * a.pool_ld * 4u : 0u;
     k.relu_lo = a.relu ? 0.f : -3.402823466e+38f;
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     k.grid = k.nwg < cus ? k.nwg : cus;             // persistent: one workgroup per CU walks its XCD's tiles
     k.flags = pool ? 1 : 0;
     size_t size = sizeof k;
@@ -127,21 +111,6 @@ hipError_t launch_conv3x3_wino4a(const ConvArgs &a, hipStream_t s)
 }
 
 // ---- conv3x3_wino4b_f32: blocks of 16 x 32 pixels x 64 channels (the layers with 64 output channels per workgroup)
-bool conv3x3_wino4b_shape_ok(const ConvArgs &a)
-{
-    if (a.wpk4 == nullptr || a.head_w != nullptr || a.out_lp || a.first_img != nullptr) return false;
-    if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.H % 16 || a.W % 32) return false;
-    if (a.Cin % 32 || a.Cin < 64 || a.ldc % 4 || a.ldc < a.Cin) return false;
-    if (a.Cout % 64 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4) return false;
-    if (a.pool_out != nullptr && a.pool_ld % 4) return false;
-    const long long lim = 1ll << 31;
-    if ((long long)a.H * a.W * a.ldc * 4 >= lim || (long long)a.H * a.W * a.ldo * 4 >= lim) return false;
-    if ((long long)(a.Cin / 16) * 36 * a.CoutPad * 64 >= lim) return false;
-    const long long m_tiles = (long long)(a.W / 32) * (a.H / 16) * a.B, nwg = m_tiles * (a.Cout / 64);
-    if (nwg >= (1ll << 24) || nwg * m_tiles >= (1ll << 32)) return false;
-    return true;
-}
-
 hipError_t launch_conv3x3_wino4b(const ConvArgs &a, hipStream_t s)
 {
     if (!conv3x3_wino4b_shape_ok(a)) return hipErrorInvalidValue;
@@ -162,7 +131,7 @@ hipError_t launch_conv3x3_wino4b(const ConvArgs &a, hipStream_t s)
     k.pix_pool_bytes = pool ? (uint32_t)a.pool_ld * 4u : 0u;
     k.img_pool_bytes = pool ? (uint32_t)(a.H / 2) * (a.W / 2) * a.pool_ld * 4u : 0u;
     k.relu_lo = a.relu ? 0.f : -3.402823466e+38f;
-    const int cus = routing_of(a).cus;
+    const int cus = a.rt.cus;
     k.grid = k.nwg < cus ? k.nwg : cus;
     k.flags = pool ? 1 : 0;
     size_t size = sizeof k;
