@@ -67,7 +67,11 @@ void mi_unet_default_config(mi_unet_config *cfg);
 int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out);
 
 /* Replaces reading + deserialising the .trt engine (src/initialize.cpp:49-60).  File format: miunet/spec.py
- * ("MIUNETW1").  Folds eval-mode BatchNorm into the conv weights, repacks for the MFMA kernels, uploads. */
+ * ("MIUNETW1").  Folds eval-mode BatchNorm into the conv weights, repacks for the MFMA kernels, uploads.
+ * Version 1 files hold the transposed-conv decoder; version 2 files add a u32 up_mode after the header (0 = transposed 2x2,
+ * 1 = bilinear x2 with align_corners=True, Pytorch-UNet's bilinear=True: halved bottleneck, narrower up convolutions).  The
+ * decoder comes from the file, not from mi_unet_config; the buffers mi_unet_create allocates hold either plan.  An unknown
+ * version or up_mode, or a payload whose length does not match the topology, is MI_UNET_EFILE. */
 int mi_unet_load_weights(mi_unet_t *h, const char *path);
 int mi_unet_load_weights_from_memory(mi_unet_t *h, const void *blob, size_t len);
 
@@ -168,6 +172,8 @@ int mi_unet_get_kernel_stats(mi_unet_t *h, mi_unet_kernel_stat *stats, int cap, 
  *   op = "conv3x3_bf16" / "convT2x2_bf16" / "conv3x3_fp16" / "convT2x2_fp16" : the 16-bit-operand kernels
  *   op = "convT2x2" : in [B][H][W][Cin], w [Cin][Cout][2][2], shift = bias [Cout]  -> out [B][2H][2W][Cout]
  *   op = "maxpool"  : in [B][H][W][Cin]                                          -> out [B][H/2][W/2][Cin]
+ *   op = "upsample2x" / "upsample2x_bf16" / "upsample2x_fp16" : in [B][H][W][Cin] -> out [B][2H][2W][Cin], bilinear with
+ *                     align_corners=True, Cin % 16 == 0, no weights (the 16-bit ops round the input to 16 bits first)
  * Weights are given in PyTorch layout exactly as in the weight file. */
 int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
                         const float *scale, const float *shift, int Cout, int relu, float *out);
@@ -200,7 +206,8 @@ const char *mi_unet_numeric_guard(const mi_unet_t *h, int *tripped, float *diff)
 typedef struct mi_unet_layer_info {
     char name[48];
     char kernel[32];       /* kernel family launched (capture only) */
-    int kind;              /* 0 first conv, 1 conv3x3, 2 convT2x2, 3 maxpool2x2, 4 head+argmax */
+    int kind;              /* 0 first conv, 1 conv3x3, 2 convT2x2, 3 maxpool2x2, 4 head+argmax, 5 bilinear x2 upsample
+                              (bilinear decoder: in = the low-resolution tensor, out = the concat slice it wrote) */
     int in_h, in_w, in_c;
     int out_h, out_w, out_c;
     int in_bits, out_bits; /* 8 = u8 image, 16 = bf16 / fp16 (per conv_algo), 32 = fp32: storage type in HBM (capture only) */

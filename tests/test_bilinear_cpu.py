@@ -1,0 +1,237 @@
+"""The bilinear decoder (Pytorch-UNet bilinear=True) on the CPU: weight-file version 2, the importer, and the routing of the
+bilinear plan's conv layers.  The Pytorch-UNet module is defined here, as that repository builds it, for any base and depth."""
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from miunet import synth
+from miunet.spec import HEADER, UNetSpec, pack_weights, unpack_weights
+
+torch = pytest.importorskip("torch")
+nn = torch.nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+class DoubleConv(nn.Module):
+    def __init__(self, cin, cout, mid=None, bias=False):
+        super().__init__()
+        mid = mid or cout
+        self.double_conv = nn.Sequential(nn.Conv2d(cin, mid, 3, padding=1, bias=bias), nn.BatchNorm2d(mid), nn.ReLU(inplace=True),
+                                         nn.Conv2d(mid, cout, 3, padding=1, bias=bias), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        return self.double_conv(x)
+
+
+class Down(nn.Module):
+    def __init__(self, cin, cout, bias=False):
+        super().__init__()
+        self.maxpool_conv = nn.Sequential(nn.MaxPool2d(2), DoubleConv(cin, cout, bias=bias))
+
+    def forward(self, x):
+        return self.maxpool_conv(x)
+
+
+class Up(nn.Module):
+    def __init__(self, cin, cout, bilinear=True, bias=False):
+        super().__init__()
+        if bilinear:
+            self.up = nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True)
+            self.conv = DoubleConv(cin, cout, cin // 2, bias=bias)
+        else:
+            self.up = nn.ConvTranspose2d(cin, cin // 2, kernel_size=2, stride=2)
+            self.conv = DoubleConv(cin, cout, bias=bias)
+
+    def forward(self, x1, x2):
+        return self.conv(torch.cat([x2, self.up(x1)], dim=1))
+
+
+class OutConv(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel_size=1)
+
+    def forward(self, x):
+        return self.conv(x)
+
+
+class PytorchUNet(nn.Module):
+    """Pytorch-UNet's UNet(n_channels, n_classes, bilinear) with the widths base << i over `levels` levels (64 / 4 = the original)."""
+
+    def __init__(self, n_channels, n_classes, bilinear=True, base=64, levels=4, conv_bias=False):
+        super().__init__()
+        ch = [base << i for i in range(levels + 1)]
+        factor = 2 if bilinear else 1
+        self.levels = levels
+        self.inc = DoubleConv(n_channels, ch[0], bias=conv_bias)
+        for i in range(1, levels + 1):
+            setattr(self, f"down{i}", Down(ch[i - 1], ch[i] // (factor if i == levels else 1), bias=conv_bias))
+        for i in range(1, levels + 1):
+            lvl = levels - i
+            setattr(self, f"up{i}", Up(ch[lvl + 1], ch[lvl] // (factor if lvl > 0 else 1), bilinear, bias=conv_bias))
+        self.outc = OutConv(ch[0], n_classes)
+
+    def forward(self, x):
+        skips = [self.inc(x)]
+        for i in range(1, self.levels + 1):
+            skips.append(getattr(self, f"down{i}")(skips[-1]))
+        y = skips.pop()
+        for i in range(1, self.levels + 1):
+            y = getattr(self, f"up{i}")(y, skips.pop())
+        return self.outc(y)
+
+
+def module_key(name):
+    """spec tensor name -> the Pytorch-UNet state-dict key it is read from"""
+    parts = name.split(".")
+    if parts[0] == "outc":
+        return f"outc.conv.{'weight' if parts[1] == 'w' else 'bias'}"
+    if parts[1] == "t":
+        return f"{parts[0]}.up.{'weight' if parts[2] == 'w' else 'bias'}"
+    prefix = {"inc": "inc.double_conv"}.get(parts[0])
+    if prefix is None:
+        prefix = f"{parts[0]}.maxpool_conv.1.double_conv" if parts[0].startswith("down") else f"{parts[0]}.conv.double_conv"
+    k = int(parts[1][-1])
+    if parts[1].startswith("c"):
+        return f"{prefix}.{3 * (k - 1)}.weight"
+    bn = f"{prefix}.{3 * (k - 1) + 1}"
+    return {"gamma": f"{bn}.weight", "beta": f"{bn}.bias", "mean": f"{bn}.running_mean", "var": f"{bn}.running_var"}[parts[2]]
+
+
+def load_spec_weights(model, spec, t, conv_bias=None):
+    """Put the spec tensors `t` into the module; conv_bias (rng): give every 3x3 conv a bias and move it out of the BN mean."""
+    sd = model.state_dict()
+    for name, shape in spec.tensor_list():
+        key = module_key(name)
+        v = t[name].reshape(sd[key].shape)
+        sd[key] = torch.from_numpy(np.ascontiguousarray(v, np.float32))
+    if conv_bias is not None:
+        for key in list(sd):
+            if key.endswith(".weight") and sd[key].ndim == 4 and sd[key].shape[-1] == 3:
+                bkey = key[:-6] + "bias"
+                b = torch.from_numpy(conv_bias.standard_normal(sd[key].shape[0]).astype(np.float32) * 0.1)
+                sd[bkey] = b
+                bn = key.rsplit(".", 1)[0]
+                bn = bn[: bn.rfind(".") + 1] + str(int(bn[bn.rfind(".") + 1:]) + 1)
+                sd[bn + ".running_mean"] = sd[bn + ".running_mean"] + b
+    model.load_state_dict(sd)
+    return model
+
+
+@pytest.mark.parametrize("base,levels", [(64, 4), (16, 3)])
+def test_module_tree_matches_the_bilinear_spec(base, levels):
+    spec = UNetSpec(1, base, levels, 3, up="bilinear")
+    sd = PytorchUNet(1, 3, bilinear=True, base=base, levels=levels).state_dict()
+    for name, shape in spec.tensor_list():
+        want = tuple(sd[module_key(name)].shape)
+        assert (want if name != "outc.w" else want[:2]) == tuple(shape), name
+    n_module = sum(v.numel() for k, v in sd.items() if not k.endswith("num_batches_tracked"))
+    assert n_module == spec.n_params()
+    if (base, levels) == (64, 4):
+        # exactly UNet(1, 3, bilinear=True): 17.27 M parameters (the transposed net: 31.05 M)
+        assert spec.n_params() == 17270787 and UNetSpec().n_params() == 31048387
+
+
+def test_importer_reads_a_bilinear_state_dict():
+    import import_state_dict as imp
+
+    spec = UNetSpec(1, 16, 3, 3, up="bilinear")
+    t = synth.make_weights(spec, 9)
+    model = load_spec_weights(PytorchUNet(1, 3, bilinear=True, base=16, levels=3), spec, t)
+    spec2, blob = imp.convert(model.state_dict())
+    assert (spec2.in_ch, spec2.base, spec2.levels, spec2.classes, spec2.up) == (1, 16, 3, 3, "bilinear")
+    assert blob == pack_weights(spec, t)
+    assert struct.unpack_from("<I", blob, 8)[0] == 2 and struct.unpack_from("<I", blob, HEADER.size)[0] == 1
+    spec3, t3 = unpack_weights(blob)
+    assert spec3.up == "bilinear" and spec3.tensor_list() == spec.tensor_list()
+    for k in t:
+        assert np.array_equal(t3[k], t[k]), k
+    # conv biases are folded into the BatchNorm mean: the module's function is unchanged, and so are the folded tensors
+    model_b = load_spec_weights(PytorchUNet(1, 3, bilinear=True, base=16, levels=3, conv_bias=True), spec, t, conv_bias=np.random.default_rng(1))
+    _, blob_b = imp.convert(model_b.state_dict())
+    _, tb = unpack_weights(blob_b)
+    for k in t:
+        assert np.allclose(tb[k], t[k], atol=1e-6), k
+    x = torch.from_numpy(synth.make_images(1, 16, 24, 1, 3).transpose(0, 3, 1, 2).astype(np.float32) / 255.0)
+    with torch.no_grad():
+        assert float((model.eval()(x) - model_b.eval()(x)).abs().max()) < 1e-5
+
+
+def test_importer_names_the_first_bad_key():
+    import import_state_dict as imp
+
+    spec = UNetSpec(1, 16, 3, 3, up="bilinear")
+    sd = load_spec_weights(PytorchUNet(1, 3, bilinear=True, base=16, levels=3), spec, synth.make_weights(spec, 2)).state_dict()
+    broken = dict(sd)
+    del broken["up2.conv.double_conv.4.running_var"]
+    with pytest.raises(ValueError, match="up2.conv.double_conv.4.running_var"):
+        imp.convert(broken)
+    # the transposed module's bottleneck with bilinear up blocks: neither variant's widths
+    odd = dict(sd)
+    odd["down3.maxpool_conv.1.double_conv.0.weight"] = np.zeros((128, 64, 3, 3), np.float32)
+    with pytest.raises(ValueError, match="down3.c1.w"):
+        imp.convert(odd)
+    no_up = {k: v for k, v in sd.items() if not k.startswith("up1.")}
+    with pytest.raises(ValueError, match="up1"):
+        imp.convert(no_up)
+
+
+def test_transposed_files_stay_version_1():
+    spec = UNetSpec(1, 16, 3, 3)
+    blob = pack_weights(spec, synth.make_weights(spec, 4))
+    assert blob[:8] == b"MIUNETW1" and struct.unpack_from("<I", blob, 8)[0] == 1
+    assert len(blob) == HEADER.size + 4 * spec.n_params()
+    s2, _ = unpack_weights(blob)
+    assert s2.up == "transpose"
+
+
+def test_unknown_mode_or_version_is_refused():
+    spec = UNetSpec(1, 16, 2, 3, up="bilinear")
+    blob = bytearray(pack_weights(spec, synth.make_weights(spec, 5)))
+    bad_mode = bytearray(blob)
+    struct.pack_into("<I", bad_mode, HEADER.size, 7)
+    with pytest.raises(ValueError, match="up_mode"):
+        unpack_weights(bytes(bad_mode))
+    bad_ver = bytearray(blob)
+    struct.pack_into("<I", bad_ver, 8, 3)
+    with pytest.raises(ValueError, match="version"):
+        unpack_weights(bytes(bad_ver))
+    with pytest.raises(ValueError):
+        unpack_weights(bytes(blob[:-4]))
+    with pytest.raises(ValueError):
+        UNetSpec(up="nearest")
+
+
+def test_bilinear_spec_macs_and_synthetic_weights():
+    spec = UNetSpec(up="bilinear")
+    # conv3x3 MACs of UNet(1, 3, bilinear=True) at 512 x 512, the 1x1 head included, the upsampling counting 0
+    ch = [64, 128, 256, 512, 512]
+    m = 512 * 512 * 9 * (1 * 64 + 64 * 64)
+    for i in range(1, 5):
+        m += (512 >> i) ** 2 * 9 * (ch[i - 1] * ch[i] + ch[i] * ch[i])
+    for lvl, (cin, mid, cout) in zip((3, 2, 1, 0), ((1024, 512, 256), (512, 256, 128), (256, 128, 64), (128, 64, 64))):
+        m += (512 >> lvl) ** 2 * 9 * (cin * mid + mid * cout)
+    m += 512 * 512 * 64 * 3
+    assert spec.macs_per_image(512, 512) == m
+    for t in (synth.make_weights(spec, 1), synth.make_threshold_weights(spec)):
+        assert sorted(t) == sorted(n for n, _ in spec.tensor_list())
+        pack_weights(spec, t)
+
+
+def test_bilinear_plan_routes(tmp_path):
+    """every conv3x3 layer of the bilinear plan (fp32 winograd with and without the tripped guard, bf16, fp16; batch 1..16; the
+    512 x 512 base-64 and the 1024 x 1024 x 3 base-32 five-level nets) gets a route whose shape predicate accepts it"""
+    exe = tmp_path / "route_bilinear_test"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "route_bilinear_test.cpp"), os.path.join(PKG, "csrc", "routing.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "upsample2x_bilinear" not in r.stdout and "all 760 bilinear routing checks passed" in r.stdout

@@ -45,14 +45,14 @@ int fail(int code, const std::string &msg)
     } while (0)
 
 struct Step {
-    enum Kind { FIRST, CONV, CONVT, POOL, HEAD } kind;
+    enum Kind { FIRST, CONV, CONVT, POOL, HEAD, UPSAMPLE } kind;
     std::string name;
     ConvArgs a{};                 // CONV / CONVT
-    // FIRST / POOL / HEAD operands
+    // FIRST / POOL / HEAD / UPSAMPLE operands (UPSAMPLE: src [H][W][C] -> channels [co_off, co_off + C) of dst [2H][2W][ld])
     const float *src = nullptr;
     float *dst = nullptr;
     const float *w = nullptr, *shift = nullptr;
-    int H = 0, W = 0, C = 0, Cout = 0, ld = 0;
+    int H = 0, W = 0, C = 0, Cout = 0, ld = 0, co_off = 0;
     double flops_per_img = 0, bytes_per_img = 0, weight_bytes = 0;
     bool fused_away = false;      // POOL steps whose work is done by the preceding conv's epilogue
     int head_step = -1;           // CONV: index of the HEAD step this layer feeds (candidate for the fused head), else -1
@@ -85,6 +85,7 @@ struct mi_unet {
     float *d_lut = nullptr;         // 256 floats: i / 255.0f
     float *d_cat[8]{};              // concat buffers [Bm][h_i][w_i][2*ch_i]
     float *d_s0 = nullptr, *d_s1 = nullptr;
+    size_t cat_floats[8]{}, s_floats = 0;   // their sizes (build_plan checks every step's tensors against them)
     uint8_t *d_img = nullptr;       // staging for the host-buffer entry point
     uint8_t *d_labels = nullptr;
     float *d_logits = nullptr;
@@ -328,7 +329,7 @@ void pack_convT_bf16(const float *w, int cin, int cout, uint16_t *dst, size_t np
                     cvt(w[((size_t)ci * cout + co) * 4 + k]);
 }
 
-// parse "MIUNETW1" (miunet/spec.py), fold BN, repack
+// parse "MIUNETW1" (miunet/spec.py): version 1, or version 2 with its up_mode; fold BN, repack
 int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, size_t len, HostWeights &hw)
 {
     const unsigned char *p = static_cast<const unsigned char *>(blob);
@@ -338,11 +339,24 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
     memcpy(h, p + 8, 20);
     memcpy(&eps, p + 28, 4);
     memcpy(&n, p + 32, 4);
-    if (h[0] != 1) return fail(MI_UNET_EFILE, "weight blob: unsupported version");
+    size_t payload_at = 36;
+    hw.up_mode = UP_TRANSPOSE;
+    if (h[0] == 2) {                             // version 2: u32 up_mode between the header and the payload
+        uint32_t mode;
+        if (len < 40) return fail(MI_UNET_EFILE, "weight blob: version 2 header truncated");
+        memcpy(&mode, p + 36, 4);
+        if (mode != UP_TRANSPOSE && mode != UP_BILINEAR)
+            return fail(MI_UNET_EFILE, "weight blob: unknown up_mode " + std::to_string(mode) + " (want 0 transposed 2x2 or 1 bilinear x2)");
+        hw.up_mode = (int)mode;
+        payload_at = 40;
+    } else if (h[0] != 1) {
+        return fail(MI_UNET_EFILE, "weight blob: unsupported version " + std::to_string(h[0]) + " (want 1 or 2)");
+    }
+    const bool bilinear = hw.up_mode == UP_BILINEAR;
     if ((int)h[1] != cfg.in_ch || (int)h[2] != cfg.base || (int)h[3] != cfg.levels || (int)h[4] != cfg.classes)
         return fail(MI_UNET_EFILE, "weight blob: topology (in_ch/base/levels/classes) does not match the engine config");
-    if (len < 36 + (size_t)n * 4) return fail(MI_UNET_EFILE, "weight blob: truncated payload");
-    const float *cur = reinterpret_cast<const float *>(p + 36);
+    if (len < payload_at + (size_t)n * 4) return fail(MI_UNET_EFILE, "weight blob: truncated payload");
+    const float *cur = reinterpret_cast<const float *>(p + payload_at);
     size_t left = n;
     auto take = [&](size_t k) -> const float * {
         if (left < k) return nullptr;
@@ -401,13 +415,20 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
         hw.conv.push_back(off);
         return 0;
     };
-    auto add_dconv = [&](int cin, int cout) -> int {
-        int rc = add_conv(cin, cout);
-        return rc ? rc : add_conv(cout, cout);
+    auto add_dconv = [&](int cin, int cout, int mid) -> int {
+        int rc = add_conv(cin, mid);
+        return rc ? rc : add_conv(mid, cout);
     };
-    int rc = add_dconv(cfg.in_ch, ch[0]);
-    for (int i = 1; i <= L && !rc; ++i) rc = add_dconv(ch[i - 1], ch[i]);
+    int rc = add_dconv(cfg.in_ch, ch[0], ch[0]);
     for (int i = 1; i <= L && !rc; ++i) {
+        const int c = (bilinear && i == L) ? ch[L - 1] : ch[i];       // the bilinear net's bottleneck keeps ch[L-1] channels
+        rc = add_dconv(ch[i - 1], c, c);
+    }
+    for (int i = 1; i <= L && !rc && bilinear; ++i) {                  // up_i: 2 ch[lvl] -> ch[lvl] -> ch[lvl] / 2 (ch[0] last)
+        const int lvl = L - i, c = ch[lvl];
+        rc = add_dconv(2 * c, lvl > 0 ? c / 2 : c, c);
+    }
+    for (int i = 1; i <= L && !rc && !bilinear; ++i) {
         const int cin = ch[L - i + 1], cout = cin / 2;
         const float *w = take((size_t)cin * cout * 4), *b = take(cout);
         if (!w || !b) return fail(MI_UNET_EFILE, "weight blob: payload shorter than the topology needs");
@@ -430,7 +451,7 @@ int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, si
             }
         }
         hw.convT.push_back(off);
-        rc = add_dconv(cin, cout);
+        rc = add_dconv(cin, cout, cout);
     }
     if (rc) return rc;
     const float *ow = take((size_t)cfg.classes * ch[0]), *ob = take(cfg.classes);
@@ -451,12 +472,56 @@ void conv_cost(Step &s, int H, int W, int cin, int cout, int taps_flops, bool co
     s.weight_bytes = 4.0 * (double)cin * cout * taps_flops;
 }
 
+// Every tensor a step reads or writes must lie inside the buffer mi_unet_create allocated for it at max_batch.  The buffers are
+// sized for the transposed decoder and every tensor of the bilinear plan is at most its transposed counterpart, but the plan
+// comes from a weight file: one that does not fit is refused here, never launched.  (The split-K workspace needs no check: its
+// launchers shrink the split until the slabs fit a.ksplit_ws_bytes.)
+int check_plan_fits(const mi_unet *h)
+{
+    const size_t Bm = (size_t)h->cfg.max_batch;
+    auto cap = [&](const void *p) -> size_t {
+        if (p == nullptr) return 0;
+        if (p == h->d_s0 || p == h->d_s1) return h->s_floats;
+        for (int i = 0; i < 8; ++i)
+            if (p == h->d_cat[i]) return h->cat_floats[i];
+        return 0;
+    };
+    for (const Step &st : h->plan) {
+        struct Use { const void *p; size_t floats; } use[3] = {};
+        bool ok = true;
+        const size_t px = Bm * st.H * st.W, apx = Bm * st.a.H * st.a.W;
+        switch (st.kind) {
+        case Step::FIRST: use[0] = { st.dst, px * st.ld }; break;
+        case Step::CONV:
+            use[0] = { st.a.in, apx * st.a.ldc }; use[1] = { st.a.out, apx * st.a.ldo };
+            if (st.a.pool_out) use[2] = { st.a.pool_out, apx / 4 * st.a.pool_ld };
+            ok = st.a.Cin <= st.a.ldc && st.a.co_off + st.a.Cout <= st.a.ldo;
+            break;
+        case Step::CONVT:
+            use[0] = { st.a.in, apx * st.a.ldc }; use[1] = { st.a.out, 4 * apx * st.a.ldo };
+            ok = st.a.Cin <= st.a.ldc && st.a.co_off + st.a.Cout <= st.a.ldo;
+            break;
+        case Step::POOL: use[0] = { st.src, px * st.ld }; use[1] = { st.dst, px / 4 * st.C }; break;
+        case Step::UPSAMPLE:
+            use[0] = { st.src, px * st.C }; use[1] = { st.dst, 4 * px * st.ld };
+            ok = st.co_off + st.C <= st.ld;
+            break;
+        case Step::HEAD: use[0] = { st.src, px * st.C }; break;
+        }
+        for (const Use &u : use)
+            if (u.p && u.floats > cap(u.p)) ok = false;
+        if (!ok) return fail(MI_UNET_EFILE, "weight file: step " + st.name + " of its network does not fit the engine's buffers");
+    }
+    return 0;
+}
+
 // (re)build the launch plan for micro-batch capacity cfg.max_batch; pointers into d_weights need the offsets
 int build_plan(mi_unet *h, const HostWeights &hw)
 {
     const mi_unet_config &c = h->cfg;
     const int L = c.levels;
     const int *ch = h->ch;
+    const bool bilinear = hw.up_mode == UP_BILINEAR;
     h->plan.clear();
     size_t ci = 0, ti = 0;
     auto W_ = [&](size_t off) { return h->d_weights + off; };
@@ -503,14 +568,28 @@ int build_plan(mi_unet *h, const HostWeights &hw)
         p.fused_away = fuse;
         h->plan.push_back(p);
         H /= 2; Wd /= 2;
-        conv_step("down" + std::to_string(i) + ".c1", h->d_s0, ch[i - 1], ch[i - 1], h->d_s1, ch[i], 0, ch[i], H, Wd);
+        const int co = (bilinear && i == L) ? ch[L - 1] : ch[i];      // the bilinear net's bottleneck keeps ch[L-1] channels
+        conv_step("down" + std::to_string(i) + ".c1", h->d_s0, ch[i - 1], ch[i - 1], h->d_s1, co, 0, co, H, Wd);
         if (i < L)
             conv_step("down" + std::to_string(i) + ".c2", h->d_s1, ch[i], ch[i], h->d_cat[i], 2 * ch[i], 0, ch[i], H, Wd);
         else
-            conv_step("down" + std::to_string(i) + ".c2", h->d_s1, ch[i], ch[i], h->d_s0, ch[i], 0, ch[i], H, Wd);
+            conv_step("down" + std::to_string(i) + ".c2", h->d_s1, co, co, h->d_s0, co, 0, co, H, Wd);
     }
     float *cur = h->d_s0;         // bottleneck feature map (levels >= 1 is enforced by mi_unet_create)
-    for (int i = 1; i <= L; ++i) {
+    for (int i = 1; i <= L && bilinear; ++i) {
+        // bilinear x2 into the upper half of the concat buffer, then 2 ch[lvl] -> ch[lvl] -> ch[lvl] / 2 (ch[0] at the last level)
+        const int lvl = L - i, c = ch[lvl], cout = lvl > 0 ? c / 2 : c;
+        Step u;
+        u.kind = Step::UPSAMPLE; u.name = "up" + std::to_string(i) + ".up";
+        u.src = cur; u.dst = h->d_cat[lvl]; u.H = H; u.W = Wd; u.C = c; u.ld = 2 * c; u.co_off = c;
+        u.bytes_per_img = 4.0 * H * Wd * c * (1 + 4);           // the input once, the output slice once
+        h->plan.push_back(u);
+        H *= 2; Wd *= 2;
+        conv_step("up" + std::to_string(i) + ".c1", h->d_cat[lvl], 2 * c, 2 * c, h->d_s1, c, 0, c, H, Wd);
+        conv_step("up" + std::to_string(i) + ".c2", h->d_s1, c, c, h->d_s0, cout, 0, cout, H, Wd);
+        cur = h->d_s0;
+    }
+    for (int i = 1; i <= L && !bilinear; ++i) {
         const int lvl = L - i, cin = ch[lvl + 1], cout = ch[lvl];
         Step t;
         t.kind = Step::CONVT; t.name = "up" + std::to_string(i) + ".t";
@@ -544,7 +623,7 @@ int build_plan(mi_unet *h, const HostWeights &hw)
             lc.a.pool_out == nullptr)
             lc.head_step = last;
     }
-    return 0;
+    return check_plan_fits(h);
 }
 
 int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);
@@ -618,6 +697,7 @@ void route_plan(const mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_label
         if (st.fused_away) l.skip = true;
         if (st.kind == Step::FIRST) l.rc.route = Route::FIRST;
         else if (st.kind == Step::POOL) l.rc.route = Route::POOL;
+        else if (st.kind == Step::UPSAMPLE) l.rc.route = Route::UPSAMPLE;
         else if (st.kind == Step::HEAD) l.rc.route = Route::HEAD;
         else if (st.kind == Step::CONVT) {
             l.a = st.a; l.a.B = B; l.a.rt = h->routing;
@@ -683,10 +763,10 @@ int tap_input(mi_unet *h, const Step &st, const Launch &l, const uint8_t *d_imgs
         return download_tensor(s, reinterpret_cast<const char *>(st.a.in) + im * npix * st.a.ldc * (abits / 8), abits, lp_kind, npix, st.a.Cin,
                                st.a.ldc, h->tap.in);
     }
-    const int b = st.kind == Step::HEAD ? 32 : abits;           // POOL (activation type), HEAD (always fp32)
+    const int b = st.kind == Step::HEAD ? 32 : abits;           // POOL, UPSAMPLE (activation type), HEAD (always fp32)
     h->tap.info->in_bits = b;
     const size_t npix = (size_t)st.H * st.W;
-    const int ld = st.kind == Step::HEAD ? st.C : st.ld;
+    const int ld = (st.kind == Step::HEAD || st.kind == Step::UPSAMPLE) ? st.C : st.ld;
     return download_tensor(s, reinterpret_cast<const char *>(st.src) + im * npix * ld * (b / 8), b, lp_kind, npix, st.C, ld, h->tap.in);
 }
 
@@ -731,8 +811,13 @@ int tap_output(mi_unet *h, const Step &st, const Launch &l, uint8_t *d_labels, f
         }
         return 0;
     }
-    ti->out_bits = abits;                                        // POOL
-    const size_t npix = (size_t)(st.H / 2) * (st.W / 2);
+    ti->out_bits = abits;
+    if (st.kind == Step::UPSAMPLE) {                             // the slice it wrote: channels [co_off, co_off + C) of the concat buffer
+        const size_t npix = (size_t)(2 * st.H) * (2 * st.W);
+        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + (im * npix * st.ld + st.co_off) * (abits / 8), abits, lp_kind, npix, st.C,
+                               st.ld, h->tap.out);
+    }
+    const size_t npix = (size_t)(st.H / 2) * (st.W / 2);         // POOL
     return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.C * (abits / 8), abits, lp_kind, npix, st.C, st.C, h->tap.out);
 }
 
@@ -775,6 +860,9 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
         case Route::HEAD:
             e = launch_head_argmax(st.src, st.C, st.w, st.shift, st.Cout, d_logits, d_labels, B, st.H * st.W, s);
             break;
+        case Route::UPSAMPLE:
+            e = launch_upsample2x_bilinear(st.src, st.C, st.dst, st.ld, st.co_off, B, st.H, st.W, st.C, lp_kind, h->routing, s);
+            break;
         default:
             e = launch_route(l.rc.route, l.a, s);
         }
@@ -791,7 +879,8 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
             snprintf(ks.kernel, sizeof ks.kernel, "%s", route_name(l.rc.route, l.rc.fused).c_str());
             ks.flops = st.flops_per_img * B;
             // algorithmic bytes: the 16-bit pipelines move half of them (activations and weights are 2 bytes)
-            ks.bytes = (st.bytes_per_img * B + st.weight_bytes) * ((lp_kind && (st.kind == Step::CONV || st.kind == Step::CONVT)) ? 0.5 : 1.0);
+            ks.bytes = (st.bytes_per_img * B + st.weight_bytes) *
+                       ((lp_kind && (st.kind == Step::CONV || st.kind == Step::CONVT || st.kind == Step::UPSAMPLE)) ? 0.5 : 1.0);
             if (l.rc.fused & FUSE_FIRST) {        // + the first layer's arithmetic; the image in place of its output tensor
                 const Step &f = h->plan[0];
                 ks.flops += f.flops_per_img * B;
@@ -887,7 +976,7 @@ int engine_adopt_weights(mi_unet_t *h, const HostWeights &hw, bool upload)
     dw->floats = hw.blob.size();
     HIP_TRY(hipMalloc(&dw->d, sizeof(float) * hw.blob.size()));
     if (upload) HIP_TRY(hipMemcpy(dw->d, hw.blob.data(), sizeof(float) * hw.blob.size(), hipMemcpyHostToDevice));
-    dw->layout.conv = hw.conv; dw->layout.convT = hw.convT; dw->layout.head = hw.head;
+    dw->layout.conv = hw.conv; dw->layout.convT = hw.convT; dw->layout.head = hw.head; dw->layout.up_mode = hw.up_mode;
     h->weights = dw;
     h->d_weights = dw->d;
     h->weight_floats = dw->floats;
@@ -1111,10 +1200,13 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
     HIP_TRY_H(hipEventCreate(&h->tev0));
     HIP_TRY_H(hipEventCreate(&h->tev1));
     const size_t Bm = cfg->max_batch, npix0 = Bm * cfg->height * cfg->width;
-    for (int i = 0; i < L; ++i)
-        HIP_TRY_H(hipMalloc(&h->d_cat[i], sizeof(float) * (npix0 >> (2 * i)) * 2 * h->ch[i]));
-    HIP_TRY_H(hipMalloc(&h->d_s0, sizeof(float) * npix0 * h->ch[0]));
-    HIP_TRY_H(hipMalloc(&h->d_s1, sizeof(float) * npix0 * h->ch[0]));
+    for (int i = 0; i < L; ++i) {
+        h->cat_floats[i] = (npix0 >> (2 * i)) * 2 * h->ch[i];
+        HIP_TRY_H(hipMalloc(&h->d_cat[i], sizeof(float) * h->cat_floats[i]));
+    }
+    h->s_floats = npix0 * h->ch[0];
+    HIP_TRY_H(hipMalloc(&h->d_s0, sizeof(float) * h->s_floats));
+    HIP_TRY_H(hipMalloc(&h->d_s1, sizeof(float) * h->s_floats));
     HIP_TRY_H(hipMalloc(&h->d_img, npix0 * cfg->in_ch));
     HIP_TRY_H(hipMalloc(&h->d_labels, npix0));
     HIP_TRY_H(hipMalloc(&h->d_logits, sizeof(float) * npix0 * cfg->classes));
@@ -1686,7 +1778,7 @@ namespace {
 
 // mi_unet_layer_debug's ops: each runs one route -- or, for "conv3x3_wino4", the F(4x4,3x3) family as route_wino4 picks it --
 // on weights packed for it.  lp: the operands are 0 fp32, 1 bf16, 2 fp16.
-enum class Pack { NONE, FIRST, MFMA, MFMA_T, TAPS, WINO, WINO16, WINO4, LP, LP_T };
+enum class Pack { NONE, FIRST, MFMA, MFMA_T, TAPS, WINO, WINO16, WINO4, LP, LP_T, UP };
 struct DebugOp { const char *op; Route route; Pack pack; int lp; bool routed; };
 const DebugOp kDebugOps[] = {
     { "conv3x3", Route::CONV_MFMA, Pack::MFMA, 0, false },         { "convT2x2", Route::CONVT_MFMA, Pack::MFMA_T, 0, false },
@@ -1702,6 +1794,8 @@ const DebugOp kDebugOps[] = {
     { "convT2x2_bf16r", Route::CONVT_BF16R, Pack::LP_T, 1, false }, { "convT2x2_fp16r", Route::CONVT_FP16R, Pack::LP_T, 2, false },
     { "conv3x3_first", Route::FIRST, Pack::FIRST, 0, false },        { "conv3x3_first_bf16", Route::FIRST, Pack::FIRST, 1, false },
     { "conv3x3_first_fp16", Route::FIRST, Pack::FIRST, 2, false },   { "maxpool", Route::POOL, Pack::NONE, 0, false },
+    { "upsample2x", Route::UPSAMPLE, Pack::UP, 0, false },           { "upsample2x_bf16", Route::UPSAMPLE, Pack::UP, 1, false },
+    { "upsample2x_fp16", Route::UPSAMPLE, Pack::UP, 2, false },
 };
 
 }  // namespace
@@ -1724,6 +1818,33 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
         if (o == k.op) dop = &k;
     if (!dop) return fail(MI_UNET_EARG, "layer_debug: unknown op " + o);
     const Routing rt = Routing::from_env();
+    if (dop->pack == Pack::UP) {
+        // bilinear x2: in [B][H][W][Cin] -> out [B][2H][2W][Cin]; _bf16 / _fp16 round the input to 16 bits first (RNE) and
+        // return the 16-bit output converted back
+        if (Cin % 16 || want_pool || lp_out) return fail(MI_UNET_EARG, "layer_debug: upsample2x needs Cin % 16 == 0");
+        const int kind = dop->lp;
+        const size_t es = kind ? 2 : 4, out_n = in_n * 4;
+        std::vector<uint16_t> io16(kind ? std::max(in_n, out_n) : 0);
+        if (kind)
+            for (size_t i = 0; i < in_n; ++i) io16[i] = kind == 2 ? fp16_bits(in[i]) : bf16_bits(in[i]);
+        void *d_i = nullptr, *d_o = nullptr;
+        int rc1 = MI_UNET_OK;
+        auto ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc1 == MI_UNET_OK) rc1 = fail(MI_UNET_EHIP, std::string(what) + ": " + hipGetErrorString(e)); return rc1 == MI_UNET_OK; };
+        if (ok(hipMalloc(&d_i, es * in_n), "hipMalloc") && ok(hipMalloc(&d_o, es * out_n), "hipMalloc") &&
+            ok(hipMemcpy(d_i, kind ? static_cast<const void *>(io16.data()) : static_cast<const void *>(in), es * in_n, hipMemcpyHostToDevice), "hipMemcpy") &&
+            ok(hipMemset(d_o, 0xFF, es * out_n), "hipMemset") &&                  // NaN poison: unwritten outputs are visible
+            ok(launch_upsample2x_bilinear(d_i, Cin, d_o, Cin, 0, B, H, W, Cin, kind, rt, nullptr), "launch_upsample2x_bilinear") &&
+            ok(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
+            if (kind == 0) {
+                ok(hipMemcpy(out, d_o, es * out_n, hipMemcpyDeviceToHost), "hipMemcpy");
+            } else if (ok(hipMemcpy(io16.data(), d_o, es * out_n, hipMemcpyDeviceToHost), "hipMemcpy")) {
+                for (size_t i = 0; i < out_n; ++i) out[i] = kind == 2 ? fp16_to_float(io16[i]) : bf16_to_float(io16[i]);
+            }
+        }
+        if (d_i) (void)hipFree(d_i);
+        if (d_o) (void)hipFree(d_o);
+        return rc1;
+    }
     if (dop->pack == Pack::FIRST) {
         // the first layer: `in` holds byte values 0..255 (as floats), the kernel sees the u8 image and the /255 table;
         // _bf16 / _fp16: the 16-bit pipelines' output tensor (converted back to float here)
@@ -1887,6 +2008,7 @@ int mi_unet_debug_layer_info(const mi_unet_t *h, int layer, mi_unet_layer_info *
     case Step::CONVT: info->kind = 2; info->in_h = st.a.H; info->in_w = st.a.W; info->out_h = 2 * st.a.H; info->out_w = 2 * st.a.W; info->in_c = st.a.Cin; info->out_c = st.a.Cout; break;
     case Step::POOL: info->kind = 3; info->in_h = st.H; info->in_w = st.W; info->out_h = st.H / 2; info->out_w = st.W / 2; info->in_c = info->out_c = st.C; break;
     case Step::HEAD: info->kind = 4; info->in_h = info->out_h = st.H; info->in_w = info->out_w = st.W; info->in_c = st.C; info->out_c = st.Cout; break;
+    case Step::UPSAMPLE: info->kind = 5; info->in_h = st.H; info->in_w = st.W; info->out_h = 2 * st.H; info->out_w = 2 * st.W; info->in_c = info->out_c = st.C; break;
     }
     return MI_UNET_OK;
 }

@@ -11,14 +11,19 @@
 
 namespace miunet {
 
+// The decoder's upsampling (weight-file version 2, miunet/spec.py): 2x2 transposed conv (version 1 files) or parameter-free
+// bilinear x2 with align_corners=True followed by narrower convolutions (Pytorch-UNet's bilinear=True)
+enum : int { UP_TRANSPOSE = 0, UP_BILINEAR = 1 };
+
 // Weights after BN folding and repacking, in device layout, still on the host: one contiguous blob (one upload or one
 // broadcast) plus the offsets the launch plan points at.
 struct HostWeights {
     std::vector<float> blob;
     struct Off { size_t w, shift, w4; };        // w4: second packing of the same layer (F(4x4) / per-tap kernels), 0 = none
     std::vector<Off> conv;                      // per 3x3 conv in file order (first one = first-layer layout)
-    std::vector<Off> convT;
+    std::vector<Off> convT;                     // empty for the bilinear decoder
     Off head{};
+    int up_mode = UP_TRANSPOSE;                 // the decoder the file describes (weight-file version 2's up_mode)
 };
 
 // The device copy of that blob.  Shared (std::shared_ptr) by a handle and its clones; freed with the last of them.
@@ -31,7 +36,7 @@ struct DeviceWeights {
 };
 
 int engine_fail(int code, const std::string &msg);                 // sets this thread's mi_unet_last_error()
-// parse "MIUNETW1", fold BN, repack for `algo` (a resolved MI_UNET_CONV_* value, see engine_algo)
+// parse "MIUNETW1" (version 1, or 2 with its up_mode), fold BN, repack for `algo` (a resolved MI_UNET_CONV_* value, see engine_algo)
 int engine_pack_weights(const mi_unet_config &cfg, int algo, const void *blob, size_t len, HostWeights &hw);
 // allocate the device blob of `h` for `hw` (uploading hw.blob when `upload`, else leaving the bytes to the caller: a
 // broadcast or a peer copy fills engine_weight_ptr()), then build the launch plan

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, image_stages.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -135,6 +135,13 @@ hipError_t launch_conv3x3_first(const uint8_t *img, const float *lut256, const f
 hipError_t launch_maxpool2x2(const float *in, int ldc, float *out, int B, int H, int W, int C, hipStream_t s);
 // the same on 16-bit post-ReLU tensors (bf16 or fp16: non-negative values order like their bit patterns)
 hipError_t launch_maxpool2x2_u16(const void *in, int ldc, void *out, int B, int H, int W, int C, hipStream_t s);
+
+// Bilinear x2 upsampling with align_corners=True (the decoder of a bilinear=True UNet, upsample.hip): in [B][H][W][ldi] ->
+// channels [co_off, co_off + C) of out [B][2H][2W][ldo]; elem_kind 0 = fp32, 1 = bf16, 2 = fp16 tensors (16-bit: fp32 arithmetic,
+// one RNE rounding).  Weights as PyTorch's CPU kernel computes them, in fp32.  C % 16 == 0; `in`, `out + co_off` and both pixel
+// strides 16-byte aligned.
+hipError_t launch_upsample2x_bilinear(const void *in, int ldi, void *out, int ldo, int co_off, int B, int H, int W, int C, int elem_kind,
+                                      const Routing &rt, hipStream_t s);
 
 // 1x1 head + first-max-wins argmax: in [npix][Cin] -> planar logits [B][classes][H*W] (may be null) + u8 labels.
 hipError_t launch_head_argmax(const float *in, int Cin, const float *w, const float *bias, int classes, float *logits,

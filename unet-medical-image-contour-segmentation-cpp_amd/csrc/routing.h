@@ -9,8 +9,8 @@
 namespace miunet {
 
 // One row per kernel entry the engine can launch: route, the kernel name the launch log reports (bench.py maps kernel families
-// by these names), and the launcher call (engine.cpp expands it with the launch's `a` and stream `s`).  FIRST, POOL and HEAD take
-// operands of their own, not a ConvArgs: the engine launches those itself.
+// by these names), and the launcher call (engine.cpp expands it with the launch's `a` and stream `s`).  FIRST, POOL, HEAD and
+// UPSAMPLE take operands of their own, not a ConvArgs: the engine launches those itself.
 #define MIUNET_ROUTES(X)                                                                  \
     X(CONV_MFMA, "conv3x3_mfma", launch_conv3x3_mfma(a, s))                               \
     X(CONV_WINO, "conv3x3_wino", launch_conv3x3_wino(a, s))                               \
@@ -36,7 +36,8 @@ namespace miunet {
     X(CONVT_FP16R, "convT2x2_fp16r", launch_convT2x2_lpr(a, true, s))                     \
     X(FIRST, "conv3x3_first", hipErrorInvalidValue)                                       \
     X(POOL, "maxpool2x2", hipErrorInvalidValue)                                           \
-    X(HEAD, "head_argmax", hipErrorInvalidValue)
+    X(HEAD, "head_argmax", hipErrorInvalidValue)                                          \
+    X(UPSAMPLE, "upsample2x_bilinear", hipErrorInvalidValue)
 
 enum class Route {
 #define MIUNET_ROUTE_ENUM(id, name, call) id,

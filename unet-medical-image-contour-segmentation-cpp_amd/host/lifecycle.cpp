@@ -75,14 +75,21 @@ int env_algo()
 }
 
 // topology of a MIUNETW1 file (miunet/spec.py): magic[8], u32 version, in_ch, base, levels, classes
-bool read_weight_header(const std::string &path, mi_unet_config &cfg)
+// version 1, or version 2 with its u32 up_mode after the 36-byte header (miunet/spec.py); the engine validates the mode
+bool read_weight_header(const std::string &path, mi_unet_config &cfg, uint32_t &up_mode)
 {
     std::ifstream f(path, std::ios::binary);
-    unsigned char hdr[28];
-    if (!f.read(reinterpret_cast<char *>(hdr), sizeof hdr) || std::memcmp(hdr, "MIUNETW1", 8) != 0) return false;
+    unsigned char hdr[40];
+    if (!f.read(reinterpret_cast<char *>(hdr), 28) || std::memcmp(hdr, "MIUNETW1", 8) != 0) return false;
     uint32_t v[5];
     std::memcpy(v, hdr + 8, sizeof v);
-    if (v[0] != 1) return false;
+    up_mode = 0;
+    if (v[0] == 2) {
+        if (!f.read(reinterpret_cast<char *>(hdr + 28), 12)) return false;
+        std::memcpy(&up_mode, hdr + 36, 4);
+    } else if (v[0] != 1) {
+        return false;
+    }
     cfg.in_ch = (int)v[1]; cfg.base = (int)v[2]; cfg.levels = (int)v[3]; cfg.classes = (int)v[4];
     return true;
 }
@@ -118,7 +125,8 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
         if (g_group) { mi_unet_group_destroy(g_group); g_group = nullptr; }
         ++g_generation;
         mi_unet_default_config(&g_cfg);            // 512x512x1, 3 classes (src/process.cpp:70, :162)
-        if (!read_weight_header(trt_cache_path, g_cfg)) {
+        uint32_t up_mode = 0;
+        if (!read_weight_header(trt_cache_path, g_cfg, up_mode)) {
             g_log_file << "Error: not a MIUNETW1 weight file - " << trt_cache_path << std::endl;
             std::cerr << "Initialization error: not a MIUNETW1 weight file" << std::endl;
             return false;
@@ -150,7 +158,8 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
         }
         g_log_file << "MI355X UNet engine initialized successfully" << std::endl;
         g_log_file << "  Topology: in_ch=" << g_cfg.in_ch << " base=" << g_cfg.base << " levels=" << g_cfg.levels
-                   << " classes=" << g_cfg.classes << ", tile " << g_cfg.width << "x" << g_cfg.height << std::endl;
+                   << " classes=" << g_cfg.classes << ", tile " << g_cfg.width << "x" << g_cfg.height
+                   << ", upsample=" << (up_mode == 1 ? "bilinear" : "transpose") << std::endl;
         g_log_file << "  Devices: " << mi_unet_group_size(g_group) << " (weights to ranks > 0 by "
                    << mi_unet_group_weight_transport(g_group) << "), micro-batch " << g_cfg.max_batch << " per device" << std::endl;
         g_log_file << "  " << mi_unet_numeric_guard(mi_unet_group_handle(g_group, 0), nullptr, nullptr) << std::endl;

@@ -42,7 +42,7 @@ class LayerInfo(C.Structure):
                 ("in_c", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("out_c", C.c_int), ("in_bits", C.c_int),
                 ("out_bits", C.c_int), ("pooled", C.c_int), ("fused_head", C.c_int), ("skipped", C.c_int), ("fused_first", C.c_int)]
 
-    KINDS = ("first", "conv3x3", "convT2x2", "maxpool", "head")
+    KINDS = ("first", "conv3x3", "convT2x2", "maxpool", "head", "upsample2x")
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -498,6 +498,8 @@ def layer_debug(op, x, w=None, scale=None, shift=None, relu=False, device=0):
         out = np.empty((b, 2 * h, 2 * ww, cout), np.float32)
     elif op == "maxpool":
         out = np.empty((b, h // 2, ww // 2, cin), np.float32)
+    elif op in ("upsample2x", "upsample2x_bf16", "upsample2x_fp16"):   # bilinear x2, align_corners=True (16-bit: input rounded first)
+        out = np.empty((b, 2 * h, 2 * ww, cin), np.float32)
     else:
         raise ValueError(op)
     scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
