@@ -124,6 +124,45 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
                           uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                           int32_t *counts);
 
+/* ---- Tiled inference: one image LARGER than the engine's tile, segmented at its own resolution ---------------------------
+ * The entry points above run images of exactly height x width; larger RAW images are resampled down to that size first (the
+ * reference's behaviour, and the default).  The tiled forms instead cut one image of H x W (H >= height, W >= width) into
+ * overlapping tiles of the engine's size on the device, run them in tile order in micro-batches of max_batch, and stitch the
+ * per-tile label maps (and logits) back into one H x W result before anything else happens to it.
+ *
+ * The grid, per axis (image length L, tile length T, halo h; L >= T, h >= 0, 2h < T):
+ *     S = T - 2h;  n = 1 + ceil((L - T) / S);  origin o_k = min(k S, L - T)   (the last tile ends at the image edge)
+ *     cuts c_0 = 0, c_n = L, c_k = (o_{k-1} + T + o_k) / 2;  tile k owns positions [c_k, c_{k+1})
+ * Tiles are numbered row-major (t = ty * nx + tx).  mi_unet_tile_axis returns n and, where the pointers are not NULL,
+ * origins[n] and cuts[n + 1]; -1 for an illegal (L, T, halo).  Pure host arithmetic, needs no device.
+ *
+ * What the halo promises: a tile border that is an image border is the network's own zero padding, and every owned pixel lies
+ * at least `halo` pixels inside every other tile border.  What it does not: a pixel of the default 4-level network sees roughly a
+ * hundred pixels to every side (two 3x3 convolutions per level at strides 1 .. 16, down and up), and with a halo smaller than
+ * that receptive field the tiled result is NOT the result of one pass over the whole image.  The result is exactly defined as "each pixel from the tile that owns it": equal, bit
+ * for bit, to mi_unet_infer_u8 on the same tiles stacked in tile order followed by a copy of the owned rectangles.  No blending.
+ *
+ *   mi_unet_infer_tiled_u8    : img u8 [H][W][in_ch] (host) -> labels u8 [H][W], logits f32 [classes][H][W] or NULL
+ *   mi_unet_infer_tiled_raw16 : in_ch planes of u16 [H][W] (argument order W, H as in mi_unet_infer_raw16; a caller holding one
+ *                               plane passes its pointer in_ch times) -> exact min/max per plane and the quantisation of
+ *                               mi_unet_infer_raw16 WITHOUT resampling -> norm u8 [H][W][in_ch] (may be NULL) -> as above
+ *   mi_unet_segment_tiled_raw16 : ... -> postprocess_mask -> mask_to_image -> extract_contours, all on the stitched image:
+ *                               mask u8 [H][W] (0 / 255), contours in the layout of mi_unet_extract_contours with B = 1, points in
+ *                               full-image coordinates (no rescaling); *count = -1 when a capacity was too small
+ * mi_unet_set_postprocess(h, 1) applies to the infer_tiled forms on the STITCHED image: one image, min_area = 6 % of H x W, never
+ * per tile.  The postprocess and contour stages borrow the network's scratch buffer (4 * max_batch * height * width * base bytes);
+ * an image whose workspace exceeds it fails with MI_UNET_EARG before anything runs.  Also MI_UNET_EARG: null pointers,
+ * H < height, W < width, halo < 0, 2 * halo >= min(height, width); MI_UNET_ESTATE before weights are loaded.
+ * The image is uploaded once; its full-size device buffers belong to the handle (a clone owns its own), grow on demand and are
+ * freed by mi_unet_destroy.  mi_unet_last_stage_ms covers these calls: upload + min/max + normalise + gather in UPLOAD_PRE,
+ * network + stitch in NETWORK, the rest as named. */
+int mi_unet_tile_axis(int L, int T, int halo, int *origins, int *cuts);
+int mi_unet_infer_tiled_u8(mi_unet_t *h, const uint8_t *img, int H, int W, int halo, uint8_t *labels, float *logits);
+int mi_unet_infer_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *labels,
+                              float *logits);
+int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
+                                int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only
@@ -131,7 +170,7 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
 int mi_unet_host_alloc(size_t bytes, void **p);
 void mi_unet_host_free(void *p);
 
-/* Device time of the stages of the LAST mi_unet_infer_raw16 / mi_unet_segment_raw16 call on this handle, in milliseconds, summed
+/* Device time of the stages of the LAST mi_unet_infer_raw16 / mi_unet_segment_raw16 (or tiled) call on this handle, in milliseconds, summed
  * over its micro-batches (hipEvent pairs on the streams the stages run on; the upload / preprocess stage of micro-batch k + 1
  * runs on a second stream under the network of micro-batch k, so the stages may add up to more than the call took).  The
  * reference logs two durations per image (src/process.cpp:223-228, :245-253); these are the terms of its "Inference time". */

@@ -24,6 +24,7 @@
 #include "engine_internal.h"
 #include "kernels.h"
 #include "routing.h"
+#include "tile_grid.h"
 
 using namespace miunet;
 
@@ -125,6 +126,18 @@ struct mi_unet {
     std::unique_ptr<CopyPool> copy_pool;   // helpers of the pageable -> pinned staging copy (created on first use)
     uint8_t *h_tiles[2] = {};       // pinned mirrors of the tile buffers (a D2H into the caller's pageable memory would block the host)   // second pinned result buffer: micro-batch k + 1 downloads while the host still copies k out
     float stage_ms[MI_UNET_N_STAGES] = {};
+    // tiled entry points (mi_unet_infer_tiled_*): the full-size image, its label map / visualisation, logits and u16 planes stay
+    // on the device for the whole call.  Grown on demand (ensure_tiled_buffers), owned by this handle, never shared with a clone.
+    struct Tiled {
+        uint8_t *d_img = nullptr, *d_labels = nullptr, *d_vis = nullptr;     // u8 [H][W][in_ch] (+ slack to a dword), [H][W], [H][W]
+        uint8_t *h_img = nullptr, *h_out = nullptr;                          // pinned mirrors of d_img and of d_labels / d_vis
+        size_t px_cap = 0;                                                   // pixels the five above hold
+        float *d_logits = nullptr;
+        size_t logit_cap = 0;                                                // pixels
+        uint16_t *d_raw = nullptr, *h_raw = nullptr;                         // in_ch planes of u16 [H][W], device and pinned
+        size_t raw_cap = 0;                                                  // pixels per plane
+        std::vector<hipEvent_t> ev;                                          // stage boundaries of the last call
+    } tiled;
     // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
     uint8_t *h_img = nullptr;
     uint8_t *h_labels = nullptr;
@@ -1681,6 +1694,246 @@ int run_raw_call(mi_unet *h, const RawCall &c)
 
 }  // namespace
 
+namespace {
+
+// ---- tiled inference (include/mi_unet.h: mi_unet_infer_tiled_*) ------------------------------------------------
+// One image of any size >= the engine's tile: uploaded once, cut into the overlapping tiles of tile_grid.h on the device, run in
+// tile order through run_microbatch in micro-batches of max_batch (the buffers, routes, graphs and numeric guard of
+// mi_unet_infer_u8), stitched on the device, and only then postprocessed / traced at full size.  Everything is enqueued on the
+// engine's stream; the host waits once, at the end.
+struct TiledCall {
+    const char *fn;
+    const uint8_t *img;                    // u8 form: [H][W][in_ch] ...
+    const uint16_t *const *planes;         // ... or RAW form: in_ch planes of u16 [H][W]
+    int H, W, halo;
+    uint8_t *norm, *out_u8;                // out_u8: label map (infer) or 0 / 255 mask (segment)
+    float *logits;
+    bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
+};
+
+int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw)
+{
+    mi_unet::Tiled &t = h->tiled;
+    const size_t C = (size_t)h->cfg.in_ch;
+    if (npix <= t.px_cap && (!want_logits || npix <= t.logit_cap) && (!raw || npix <= t.raw_cap)) return 0;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (npix > t.px_cap) {
+        for (uint8_t **p : { &t.d_img, &t.d_labels, &t.d_vis })
+            if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
+        for (uint8_t **p : { &t.h_img, &t.h_out })
+            if (*p) { HIP_TRY(hipHostFree(*p)); *p = nullptr; }
+        t.px_cap = 0;
+        HIP_TRY(hipMalloc(&t.d_img, round_up(npix * C, 4)));            // whole dwords: launch_tile_gather reads aligned dwords
+        HIP_TRY(hipMalloc(&t.d_labels, npix));
+        HIP_TRY(hipMalloc(&t.d_vis, npix));
+        HIP_TRY(hipHostMalloc(&t.h_img, npix * C, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&t.h_out, npix, hipHostMallocDefault));
+        t.px_cap = npix;
+    }
+    if (want_logits && npix > t.logit_cap) {
+        if (t.d_logits) { HIP_TRY(hipFree(t.d_logits)); t.d_logits = nullptr; }
+        t.logit_cap = 0;
+        HIP_TRY(hipMalloc(&t.d_logits, sizeof(float) * npix * h->cfg.classes));
+        t.logit_cap = npix;
+    }
+    if (raw && npix > t.raw_cap) {
+        if (t.d_raw) { HIP_TRY(hipFree(t.d_raw)); t.d_raw = nullptr; }
+        if (t.h_raw) { HIP_TRY(hipHostFree(t.h_raw)); t.h_raw = nullptr; }
+        t.raw_cap = 0;
+        HIP_TRY(hipMalloc(&t.d_raw, sizeof(uint16_t) * round_up(npix, 8) * C));            // every plane starts on 16 bytes
+        HIP_TRY(hipHostMalloc(&t.h_raw, sizeof(uint16_t) * round_up(npix, 8) * C, hipHostMallocDefault));
+        t.raw_cap = npix;
+    }
+    return 0;
+}
+
+// the launch log of mi_unet_get_kernel_stats for a launch outside the plan: the event pair of launch_plan, algorithmic bytes
+int stat_begin(mi_unet *h, hipStream_t s, hipEvent_t &e1)
+{
+    e1 = nullptr;
+    if (!h->profiling) return 0;
+    while (h->ev_pool.size() < h->ev_used + 2) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        h->ev_pool.push_back(ev);
+    }
+    hipEvent_t e0 = h->ev_pool[h->ev_used++];
+    e1 = h->ev_pool[h->ev_used++];
+    HIP_TRY(hipEventRecord(e0, s));
+    return 0;
+}
+
+int stat_end(mi_unet *h, hipStream_t s, hipEvent_t e1, const char *name, const char *kernel, double bytes)
+{
+    if (!e1) return 0;
+    HIP_TRY(hipEventRecord(e1, s));
+    mi_unet_kernel_stat ks{};
+    snprintf(ks.name, sizeof ks.name, "%s", name);
+    snprintf(ks.kernel, sizeof ks.kernel, "%s", kernel);
+    ks.bytes = bytes;
+    ks.ms = -1.f;
+    h->stats.push_back(ks);
+    return 0;
+}
+
+int check_planes(const mi_unet *h, const uint16_t *const *planes, const char *fn)
+{
+    if (!planes) return fail(MI_UNET_EARG, std::string(fn) + ": null plane list");
+    for (int p = 0; p < h->cfg.in_ch; ++p)
+        if (!planes[p]) return fail(MI_UNET_EARG, std::string(fn) + ": plane " + std::to_string(p) + " is null");
+    return 0;
+}
+
+int run_tiled_call(mi_unet *h, const TiledCall &c)
+{
+    const std::string fn = c.fn;
+    const int th = h->cfg.height, tw = h->cfg.width, C = h->cfg.in_ch, Bm = h->cfg.max_batch, classes = h->cfg.classes;
+    const int H = c.H, W = c.W;
+    if (H < th || W < tw)
+        return fail(MI_UNET_EARG, fn + ": image " + std::to_string(H) + " x " + std::to_string(W) + " is smaller than the engine's tile " +
+                                      std::to_string(th) + " x " + std::to_string(tw));
+    if (c.halo < 0 || 2 * (long long)c.halo >= std::min(th, tw))
+        return fail(MI_UNET_EARG, fn + ": halo " + std::to_string(c.halo) + " must satisfy 0 <= 2 * halo < min(tile height, tile width) = " +
+                                      std::to_string(std::min(th, tw)));
+    if ((long long)H * W > (1ll << 30) || W > (1 << 28))                    // 32-bit byte offsets inside a row of logits
+        return fail(MI_UNET_EARG, fn + ": images of more than 2^30 pixels or wider than 2^28 are not supported");
+    TileGrid g;
+    if (!tile_grid(H, W, th, tw, c.halo, g)) return fail(MI_UNET_EARG, fn + ": illegal tile grid");
+    const size_t npix = (size_t)H * W, thw = (size_t)th * tw;
+    const int nt = g.ny * g.nx;
+    const bool post = c.segment || h->postprocess;
+    // the full-size tail stages borrow the network's scratch buffer: checked before anything is enqueued
+    const size_t scratch = sizeof(float) * h->s_floats;
+    if (post && postprocess_workspace_bytes(1, H, W) > scratch)
+        return fail(MI_UNET_EARG, fn + ": the postprocess workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
+                                      std::to_string(postprocess_workspace_bytes(1, H, W)) + " bytes) exceeds the scratch buffer (" +
+                                      std::to_string(scratch) + " bytes)");
+    if (c.segment && contour_workspace_bytes(1, H, W, c.cap_contours) > scratch)
+        return fail(MI_UNET_EARG, fn + ": the contour workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
+                                      std::to_string(contour_workspace_bytes(1, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
+                                      std::to_string(scratch) + " bytes)");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = h->stream;
+    if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr, c.planes != nullptr)) return rc;
+    if (c.segment)
+        if (int rc = grow_contour_buffers(h, 1, c.cap_points, c.cap_contours)) return rc;
+    if (c.planes && !h->d_mnmx) HIP_TRY(hipMalloc(&h->d_mnmx, sizeof(unsigned) * 2 * Bm * C));
+    mi_unet::Tiled &t = h->tiled;
+    // stage boundaries: start | pre | (gather | network + stitch) per micro-batch | postprocess | contours | download
+    const int nmb = (nt + Bm - 1) / Bm;
+    const size_t n_marks = 2 + 2 * (size_t)nmb + 3;
+    while (t.ev.size() < n_marks) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        t.ev.push_back(ev);
+    }
+    size_t mark = 0;
+    hipEvent_t e1 = nullptr;
+    hipError_t e = hipSuccess;
+    HIP_TRY(hipEventRecord(t.ev[mark++], s));
+
+    // ---- the image onto the device, once
+    if (c.img) {
+        host_copy(h, t.h_img, c.img, npix * C);
+        HIP_TRY(hipMemcpyAsync(t.d_img, t.h_img, npix * C, hipMemcpyHostToDevice, s));
+    } else {
+        const size_t plane_stride = round_up(npix, 8);                       // launch_minmax_u16 / launch_normalise_u16 read 16-byte groups
+        int src_of[4] = {};                        // a caller holding one plane passes its pointer in_ch times: upload and scan it once
+        for (int p = 0; p < C; ++p) {
+            src_of[p] = (p > 0 && c.planes[p] == c.planes[p - 1]) ? src_of[p - 1] : p;
+            const int mn = src_of[p];
+            uint16_t *d_plane = t.d_raw + (size_t)mn * plane_stride;
+            if (mn == p) {
+                hipPointerAttribute_t attr;                    // pinned caller memory is read by the DMA engine directly (as stage_raw16)
+                const bool pinned = hipPointerGetAttributes(&attr, c.planes[p]) == hipSuccess && attr.type == hipMemoryTypeHost;
+                if (!pinned) {
+                    (void)hipGetLastError();
+                    host_copy(h, t.h_raw + (size_t)p * plane_stride, c.planes[p], npix * sizeof(uint16_t));
+                }
+                HIP_TRY(hipMemcpyAsync(d_plane, pinned ? c.planes[p] : t.h_raw + (size_t)p * plane_stride, npix * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+                e = launch_minmax_u16(d_plane, npix, h->d_mnmx + 2 * p, s);
+                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": min/max launch: " + hipGetErrorString(e));
+            }
+            if (int rc = stat_begin(h, s, e1)) return rc;
+            e = launch_normalise_u16(d_plane, W, H, h->d_mnmx + 2 * mn, t.d_img + p, C, s);
+            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": normalise launch: " + hipGetErrorString(e));
+            if (int rc = stat_end(h, s, e1, ("tiled.normalise." + std::to_string(p)).c_str(), "normalise_u16", 3.0 * npix)) return rc;
+        }
+    }
+    HIP_TRY(hipEventRecord(t.ev[mark++], s));
+
+    // ---- tiles in tile order, micro-batches of max_batch: gather -> network -> stitch
+    float *d_tile_logits = c.logits ? h->d_logits : nullptr;
+    for (int t0 = 0; t0 < nt; t0 += Bm) {
+        const int nb = std::min(Bm, nt - t0);
+        const std::string tag = "[" + std::to_string(t0) + "," + std::to_string(t0 + nb) + ")";
+        if (int rc = stat_begin(h, s, e1)) return rc;
+        e = launch_tile_gather(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, t0, nb, h->d_img, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": gather launch: " + hipGetErrorString(e));
+        if (int rc = stat_end(h, s, e1, ("tiled.gather" + tag).c_str(), "tile_gather", 2.0 * nb * thw * C)) return rc;
+        HIP_TRY(hipEventRecord(t.ev[mark++], s));
+        if (int rc = run_microbatch(h, h->d_img, nb, h->d_labels, d_tile_logits)) return rc;
+        // owned pixels of this micro-batch: read once from the tile results, written once
+        double owned = 0;
+        for (int k = t0; k < t0 + nb; ++k) {
+            const int ty = k / g.nx, tx = k % g.nx;
+            owned += (double)(tile_cut(H, th, g.sy, g.ny, ty + 1) - tile_cut(H, th, g.sy, g.ny, ty)) *
+                     (tile_cut(W, tw, g.sx, g.nx, tx + 1) - tile_cut(W, tw, g.sx, g.nx, tx));
+        }
+        if (int rc = stat_begin(h, s, e1)) return rc;
+        e = launch_tile_stitch(h->d_labels, d_tile_logits, classes, H, W, th, tw, c.halo, t0, nb, t.d_labels, c.logits ? t.d_logits : nullptr, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": stitch launch: " + hipGetErrorString(e));
+        if (int rc = stat_end(h, s, e1, ("tiled.stitch" + tag).c_str(), "tile_stitch", 2.0 * owned * (1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
+        HIP_TRY(hipEventRecord(t.ev[mark++], s));
+    }
+
+    // ---- the tail, on the stitched image: one image of H x W, never per tile
+    const uint8_t *d_result = t.d_labels;
+    if (post) {
+        const int min_area = static_cast<int>(W * H * 0.06f);                // src/postprocess.cpp:9 (evaluated in float), of the full image
+        e = launch_postprocess_masks(t.d_labels, t.d_labels, 1, H, W, min_area, h->d_s1, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
+    }
+    HIP_TRY(hipEventRecord(t.ev[mark++], s));
+    if (c.segment) {
+        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)c.cap_points * 2, *d_count = d_start + (c.cap_contours + 1);
+        e = launch_mask_to_image(t.d_labels, t.d_vis, npix, s);
+        if (e == hipSuccess) e = launch_extract_contours(t.d_vis, 1, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": segment launch: " + hipGetErrorString(e));
+        d_result = t.d_vis;
+    }
+    HIP_TRY(hipEventRecord(t.ev[mark++], s));
+    HIP_TRY(hipMemcpyAsync(t.h_out, d_result, npix, hipMemcpyDeviceToHost, s));
+    if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
+    if (c.segment)
+        if (int rc = contours_to_pinned(h, 1, c.cap_points, c.cap_contours)) return rc;
+    if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(t.ev[mark++], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    host_copy(h, c.out_u8, t.h_out, npix);
+    if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
+    if (c.segment) contours_to_caller(h, 1, c.cap_points, c.cap_contours, c.xy, c.start, c.count);
+
+    for (float &m : h->stage_ms) m = 0.f;
+    auto span = [&](size_t a, size_t b, int stage) -> int {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, t.ev[a], t.ev[b]));
+        h->stage_ms[stage] += ms;
+        return 0;
+    };
+    if (int rc = span(0, 1, MI_UNET_STAGE_UPLOAD_PRE)) return rc;
+    for (int k = 0; k < nmb; ++k) {
+        if (int rc = span(1 + 2 * (size_t)k, 2 + 2 * (size_t)k, MI_UNET_STAGE_UPLOAD_PRE)) return rc;
+        if (int rc = span(2 + 2 * (size_t)k, 3 + 2 * (size_t)k, MI_UNET_STAGE_NETWORK)) return rc;
+    }
+    const size_t m0 = 1 + 2 * (size_t)nmb;
+    if (int rc = span(m0, m0 + 1, MI_UNET_STAGE_POSTPROCESS)) return rc;
+    if (int rc = span(m0 + 1, m0 + 2, MI_UNET_STAGE_CONTOURS)) return rc;
+    return span(m0 + 2, m0 + 3, MI_UNET_STAGE_DOWNLOAD);
+}
+
+}  // namespace
+
 extern "C" {
 
 int mi_unet_infer_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
@@ -1699,6 +1952,37 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
     if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
         return fail(MI_UNET_EARG, "mi_unet_segment_raw16: bad argument");
     return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts });
+}
+
+int mi_unet_tile_axis(int L, int T, int halo, int *origins, int *cuts) { return tile_axis(L, T, halo, origins, cuts); }
+
+int mi_unet_infer_tiled_u8(mi_unet_t *h, const uint8_t *img, int H, int W, int halo, uint8_t *labels, float *logits)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (!img || !labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_u8: null image or label buffer");
+    const TiledCall c{ "mi_unet_infer_tiled_u8", img, nullptr, H, W, halo, nullptr, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
+    return run_tiled_call(h, c);
+}
+
+int mi_unet_infer_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *labels,
+                              float *logits)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (int rc = check_planes(h, planes, "mi_unet_infer_tiled_raw16")) return rc;
+    if (!labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_raw16: null label buffer");
+    const TiledCall c{ "mi_unet_infer_tiled_raw16", nullptr, planes, H, W, halo, norm, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
+    return run_tiled_call(h, c);
+}
+
+int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
+                                int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (int rc = check_planes(h, planes, "mi_unet_segment_tiled_raw16")) return rc;
+    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
+        return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16: null output buffer or non-positive capacity");
+    const TiledCall c{ "mi_unet_segment_tiled_raw16", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count };
+    return run_tiled_call(h, c);
 }
 
 int mi_unet_host_alloc(size_t bytes, void **p)
@@ -2079,6 +2363,13 @@ void mi_unet_destroy(mi_unet_t *h)
         if (h->h_raw[r]) (void)hipHostFree(h->h_raw[r]);
         if (h->raw_done[r]) (void)hipEventDestroy(h->raw_done[r]);
     }
+    void *tiled_dev[] = { h->tiled.d_img, h->tiled.d_labels, h->tiled.d_vis, h->tiled.d_logits, h->tiled.d_raw };
+    for (void *q : tiled_dev)
+        if (q) (void)hipFree(q);
+    void *tiled_host[] = { h->tiled.h_img, h->tiled.h_out, h->tiled.h_raw };
+    for (void *q : tiled_host)
+        if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : h->tiled.ev) (void)hipEventDestroy(e);
     hipEvent_t evs[] = { h->tev0, h->tev1 };
     for (hipEvent_t e : evs)
         if (e) (void)hipEventDestroy(e);

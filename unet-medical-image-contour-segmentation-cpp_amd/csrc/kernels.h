@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, tiles.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -155,6 +155,20 @@ hipError_t launch_minmax_u16(const uint16_t *raw, size_t n, unsigned *mnmx, hipS
 // dst_stride = bytes between consecutive output pixels (1 = planar tile; C = plane c of an interleaved HWC tile at dst + c)
 hipError_t launch_resample_u8(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int outW, int outH,
                               int dst_stride, hipStream_t s);
+
+// Tiled inference (tiles.hip).  The grid is tile_grid.h's: tiles of th x tw with `halo`, numbered row-major.  Every
+// launcher rebuilds the grid from (H, W, th, tw, halo) and checks the tile range [t0, t0 + nb) against it.
+//   gather    : image u8 [H][W][C] -> tiles t0 .. t0 + nb - 1 as u8 [nb][th][tw][C].  img_bytes = bytes readable behind `img`; the
+//               wide path reads the image as aligned dwords and needs img on a dword and img_bytes up to the next multiple of 4
+//   normalise : u16 [h][w] + the mnmx pair of launch_minmax_u16 -> u8, the bytes of launch_resample_u8 at outW == w, outH == h;
+//               dst_stride as there (1 = planar, C = plane c of an interleaved image at dst + c).  raw 16-byte aligned
+//   stitch    : tile labels u8 [nb][th][tw] -> the rectangle each tile owns in labels [H][W]; tile_logits / logits (both or
+//               neither) planar f32 [nb][classes][th][tw] -> [classes][H][W].  Over the tiles of a grid every pixel is written once
+hipError_t launch_tile_gather(const uint8_t *img, size_t img_bytes, int H, int W, int C, int th, int tw, int halo, int t0, int nb,
+                              uint8_t *tiles, hipStream_t s);
+hipError_t launch_normalise_u16(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int dst_stride, hipStream_t s);
+hipError_t launch_tile_stitch(const uint8_t *tile_labels, const float *tile_logits, int classes, int H, int W, int th, int tw, int halo,
+                              int t0, int nb, uint8_t *labels, float *logits, hipStream_t s);
 
 // Device form of postprocess_mask (reference: src/postprocess.cpp:13-79), integer-exact.  Workspace `ws` must hold
 // postprocess_workspace_bytes(B, H, W) bytes; labels_in/out are u8 [B][H][W] (in-place allowed).

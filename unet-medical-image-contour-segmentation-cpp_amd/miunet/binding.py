@@ -24,6 +24,7 @@ EXPORTS = [
     "mi_unet_group_load_weights_from_memory", "mi_unet_group_set_gather", "mi_unet_group_set_postprocess",
     "mi_unet_group_weight_transport", "mi_unet_group_gather", "mi_unet_group_infer_u8", "mi_unet_group_infer_raw16",
     "mi_unet_group_segment_raw16", "mi_unet_group_destroy", "mi_unet_shard_range",
+    "mi_unet_tile_axis", "mi_unet_infer_tiled_u8", "mi_unet_infer_tiled_raw16", "mi_unet_segment_tiled_raw16",
 ]
 
 
@@ -122,6 +123,12 @@ def lib():
         L.mi_unet_group_destroy.argtypes = [C.c_void_p]
         L.mi_unet_group_destroy.restype = None
         L.mi_unet_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi_unet_tile_axis.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi_unet_infer_tiled_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi_unet_infer_tiled_raw16.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
+        L.mi_unet_segment_tiled_raw16.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -303,6 +310,65 @@ class Engine:
         self.segment_raw16_run(p)
         return self.segment_raw16_decode(p)
 
+    def infer_tiled(self, img: np.ndarray, halo: int, want_logits=False):
+        """One image u8 [H,W(,C)] of any size >= the engine's tile -> labels u8 [H,W], logits f32 [classes,H,W] or None; run as
+        overlapping tiles of the engine's size, each pixel taken from the tile that owns it (tile_axis)."""
+        c = self.cfg
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.ndim == 2:
+            img = img[:, :, None]
+        if img.ndim != 3 or img.shape[2] != c.in_ch:
+            raise ValueError(f"Input must be [H,W,{c.in_ch}], got {img.shape}")
+        hh, ww = img.shape[:2]
+        labels = np.empty((hh, ww), np.uint8)
+        logits = np.empty((c.classes, hh, ww), np.float32) if want_logits else None
+        _check(lib().mi_unet_infer_tiled_u8(self._h, _ptr(img), hh, ww, halo, _ptr(labels), _ptr(logits)))
+        return labels, logits
+
+    def _tiled_planes(self, planes):
+        """in_ch u16 planes of one size [H,W] -> (keep-alive list, pointer array, H, W)"""
+        c = self.cfg
+        if isinstance(planes, np.ndarray) and planes.ndim == 2:
+            planes = [planes] * c.in_ch
+        keep = []
+        for p in planes:                                     # the same array passed twice keeps ONE pointer (uploaded once)
+            q = next((k for k, orig in keep if orig is p), None)
+            keep.append((np.ascontiguousarray(p, dtype=np.uint16) if q is None else q, p))
+        arrs = [k for k, _ in keep]
+        if len(arrs) != c.in_ch or any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+            raise ValueError(f"need {c.in_ch} u16 planes of one [H,W] shape")
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return arrs, ptrs, arrs[0].shape[0], arrs[0].shape[1]
+
+    def _norm_buf(self, hh, ww):
+        return np.empty((hh, ww) if self.cfg.in_ch == 1 else (hh, ww, self.cfg.in_ch), np.uint8)
+
+    def infer_tiled_raw16(self, planes, halo: int, want_norm=True, want_logits=False):
+        """planes: in_ch u16 [H,W] arrays (or one array, used for every channel) -> (norm u8 [H,W(,C)] or None, labels u8 [H,W],
+        logits f32 [classes,H,W] or None) at the image's own resolution"""
+        c = self.cfg
+        arrs, ptrs, hh, ww = self._tiled_planes(planes)
+        norm = self._norm_buf(hh, ww) if want_norm else None
+        labels = np.empty((hh, ww), np.uint8)
+        logits = np.empty((c.classes, hh, ww), np.float32) if want_logits else None
+        _check(lib().mi_unet_infer_tiled_raw16(self._h, ptrs, ww, hh, halo, _ptr(norm), _ptr(labels), _ptr(logits)))
+        return norm, labels, logits
+
+    def segment_tiled_raw16(self, planes, halo: int, cap_points=65536, cap_contours=256, want_norm=True):
+        """-> (norm or None, mask image 0/255 u8 [H,W], contours [[(x, y), ...], ...] in full-image coordinates, or None when a
+        capacity was too small)"""
+        arrs, ptrs, hh, ww = self._tiled_planes(planes)
+        norm = self._norm_buf(hh, ww) if want_norm else None
+        mask = np.empty((hh, ww), np.uint8)
+        xy = np.zeros((cap_points, 2), np.int32)
+        start = np.zeros(cap_contours + 1, np.int32)
+        count = C.c_int32(0)
+        _check(lib().mi_unet_segment_tiled_raw16(self._h, ptrs, ww, hh, halo, _ptr(norm), _ptr(mask), _ptr(xy), cap_points, _ptr(start),
+                                                 cap_contours, C.byref(count)))
+        n = count.value
+        cont = None if n < 0 else [[tuple(q) for q in xy[start[k]:start[k + 1]].tolist()] for k in range(n)]
+        return norm, mask, cont
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -391,6 +457,16 @@ def shard_range(n_items: int, rank: int, world: int):
     lo, hi = C.c_int(), C.c_int()
     _check(lib().mi_unet_shard_range(n_items, rank, world, C.byref(lo), C.byref(hi)))
     return lo.value, hi.value
+
+
+def tile_axis(L: int, T: int, halo: int):
+    """The tile grid of one axis (mi_unet_tile_axis): (origins[n], cuts[n + 1]); tile k owns [cuts[k], cuts[k + 1])."""
+    n = lib().mi_unet_tile_axis(L, T, halo, None, None)
+    if n < 0:
+        raise ValueError(f"illegal tile axis: L={L}, T={T}, halo={halo} (need L >= T, halo >= 0, 2 * halo < T)")
+    origins, cuts = (C.c_int * n)(), (C.c_int * (n + 1))()
+    lib().mi_unet_tile_axis(L, T, halo, origins, cuts)
+    return list(origins), list(cuts)
 
 
 class Group:
