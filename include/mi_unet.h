@@ -139,8 +139,9 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
  * What the halo promises: a tile border that is an image border is the network's own zero padding, and every owned pixel lies
  * at least `halo` pixels inside every other tile border.  What it does not: a pixel of the default 4-level network sees roughly a
  * hundred pixels to every side (two 3x3 convolutions per level at strides 1 .. 16, down and up), and with a halo smaller than
- * that receptive field the tiled result is NOT the result of one pass over the whole image.  The result is exactly defined as "each pixel from the tile that owns it": equal, bit
- * for bit, to mi_unet_infer_u8 on the same tiles stacked in tile order followed by a copy of the owned rectangles.  No blending.
+ * that receptive field the tiled result is NOT the result of one pass over the whole image.  By default the result is exactly defined as "each pixel from the tile that owns it": equal, bit
+ * for bit, to mi_unet_infer_u8 on the same tiles stacked in tile order followed by a copy of the owned rectangles.  No blending
+ * (MI_UNET_BLEND_OWNER without mirrors); the tile blend setting below replaces the copy with a weighted mean of the overlapping tiles.
  *
  *   mi_unet_infer_tiled_u8    : img u8 [H][W][in_ch] (host) -> labels u8 [H][W], logits f32 [classes][H][W] or NULL
  *   mi_unet_infer_tiled_raw16 : in_ch planes of u16 [H][W] (argument order W, H as in mi_unet_infer_raw16; a caller holding one
@@ -162,6 +163,42 @@ int mi_unet_infer_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W
                               float *logits);
 int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
                                 int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count);
+
+/* ---- Tile blending and mirror averaging: a per-handle setting that all three tiled entry points obey ------------
+ * The default { MI_UNET_BLEND_OWNER, 0.125, 0 } is the ownership stitch above, unchanged bit for bit.  Any other setting runs:
+ *   views   : each tile has nv views, in this order: identity; X if mirror & MI_UNET_MIRROR_X; Y if mirror & MI_UNET_MIRROR_Y; XY if
+ *             mirror == 3.  View images run through the network in the order k = t * nv + v (t = the row-major tile index), in
+ *             micro-batches of max_batch taken over k.  A view image is the tile cut at its origin and then mirrored (X: column j
+ *             <- tw - 1 - j; Y: row i <- th - 1 - i); its logits are mirrored back before use.
+ *   weights : the table of one axis of length T (mi_unet_tile_blend_weights), computed in double and rounded to float once:
+ *             CONSTANT (and OWNER) w(i) = 1;  GAUSSIAN w(i) = max(exp(-(d * d) / (2 s s)), 2^-20), d = i - (T - 1) / 2,
+ *             s = sigma_scale * T.  The floor keeps the 2-D product normal; the table is symmetric bit for bit.
+ *             A view of tile (ty, tx) with origin (oy, ox) weighs image pixel (Y, X) with w = fl32(wy[Y - oy] * wx[X - ox])
+ *             (wy: the table of the tile height, wx: of the tile width).
+ *   sum     : per pixel and class, over the views that cover the pixel in increasing k: acc = fl32(acc + fl32(w * logit)) from +0,
+ *             wsum = fl32(wsum + w) in the same order; no fused multiply-add.  The order is fixed by k, not by the micro-batches.
+ *   result  : logit = acc / wsum, correctly rounded; label = the first-max-wins argmax of those logits (as the untiled head).
+ *   OWNER with mirror != 0: only the owning tile's views contribute, with w = 1: their mean.
+ * The logits of every view are computed (the network always writes logits in these modes) and accumulated on the device in a
+ * full-size fp32 buffer of the handle; postprocessing and the segment form's tail run on the blended label map.
+ * mi_unet_last_stage_ms: gather in UPLOAD_PRE, network + tile_blend + blend_finalize in NETWORK.
+ * MI_UNET_EARG, setting unchanged: an unknown mode, a mirror outside 0..3, for GAUSSIAN a sigma_scale that is not finite or <= 0.
+ * b == NULL restores the default.  A clone starts at the default. */
+#define MI_UNET_BLEND_OWNER 0      /* default: each pixel from the tile that owns it */
+#define MI_UNET_BLEND_CONSTANT 1   /* plain mean over every view that covers the pixel */
+#define MI_UNET_BLEND_GAUSSIAN 2   /* weighted mean, separable Gaussian importance map centred on each tile */
+#define MI_UNET_MIRROR_X 1         /* also run each tile mirrored left-right */
+#define MI_UNET_MIRROR_Y 2         /* ... and/or top-bottom (both: 4 views including the XY mirror) */
+typedef struct mi_unet_tile_blend {
+    int mode;            /* MI_UNET_BLEND_* */
+    float sigma_scale;   /* GAUSSIAN: sigma as a fraction of the tile length (0.125 = nnU-Net's 1/8) */
+    int mirror;          /* MI_UNET_MIRROR_* bits, 0..3 */
+} mi_unet_tile_blend;
+int mi_unet_set_tile_blend(mi_unet_t *h, const mi_unet_tile_blend *b);
+int mi_unet_get_tile_blend(const mi_unet_t *h, mi_unet_tile_blend *b);
+/* Pure host arithmetic, needs no device: the weight table of one axis (w[T]) that the kernels use for the setting *b; MI_UNET_EARG for
+ * T < 1, null pointers or an invalid setting. */
+int mi_unet_tile_blend_weights(int T, const mi_unet_tile_blend *b, float *w);
 
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:

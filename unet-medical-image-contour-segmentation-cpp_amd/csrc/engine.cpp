@@ -137,7 +137,13 @@ struct mi_unet {
         uint16_t *d_raw = nullptr, *h_raw = nullptr;                         // in_ch planes of u16 [H][W], device and pinned
         size_t raw_cap = 0;                                                  // pixels per plane
         std::vector<hipEvent_t> ev;                                          // stage boundaries of the last call
+        float *d_acc = nullptr;                                              // blending: fp32 accumulator [classes][H][W]
+        size_t acc_cap = 0;                                                  // pixels
     } tiled;
+    // mi_unet_set_tile_blend: how the tiled entry points combine overlapping tiles; d_blend_w = the weight tables of the tile height
+    // and width (height + width floats), uploaded when the setting changes
+    mi_unet_tile_blend blend{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
+    float *d_blend_w = nullptr;
     // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
     uint8_t *h_img = nullptr;
     uint8_t *h_labels = nullptr;
@@ -1711,11 +1717,11 @@ struct TiledCall {
     bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
 };
 
-int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw)
+int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bool blend)
 {
     mi_unet::Tiled &t = h->tiled;
     const size_t C = (size_t)h->cfg.in_ch;
-    if (npix <= t.px_cap && (!want_logits || npix <= t.logit_cap) && (!raw || npix <= t.raw_cap)) return 0;
+    if (npix <= t.px_cap && (!want_logits || npix <= t.logit_cap) && (!raw || npix <= t.raw_cap) && (!blend || npix <= t.acc_cap)) return 0;
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (npix > t.px_cap) {
         for (uint8_t **p : { &t.d_img, &t.d_labels, &t.d_vis })
@@ -1743,6 +1749,12 @@ int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw)
         HIP_TRY(hipMalloc(&t.d_raw, sizeof(uint16_t) * round_up(npix, 8) * C));            // every plane starts on 16 bytes
         HIP_TRY(hipHostMalloc(&t.h_raw, sizeof(uint16_t) * round_up(npix, 8) * C, hipHostMallocDefault));
         t.raw_cap = npix;
+    }
+    if (blend && npix > t.acc_cap) {
+        if (t.d_acc) { HIP_TRY(hipFree(t.d_acc)); t.d_acc = nullptr; }
+        t.acc_cap = 0;
+        HIP_TRY(hipMalloc(&t.d_acc, sizeof(float) * npix * h->cfg.classes));
+        t.acc_cap = npix;
     }
     return 0;
 }
@@ -1812,15 +1824,21 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
         return fail(MI_UNET_EARG, fn + ": the contour workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
                                       std::to_string(contour_workspace_bytes(1, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
+    // blending or mirror averaging (mi_unet_set_tile_blend): nv views per tile, view k = t * nv + v, the network's logits
+    // accumulated into t.d_acc, which also returns the blended logits; otherwise the ownership stitch
+    const mi_unet_tile_blend bl = h->blend;
+    const bool blend = bl.mode != MI_UNET_BLEND_OWNER || bl.mirror != 0, owner = bl.mode == MI_UNET_BLEND_OWNER;
+    const int nv = blend ? tile_view_count(bl.mirror) : 1, nk = nt * nv;
+    const float *d_wy = h->d_blend_w, *d_wx = h->d_blend_w ? h->d_blend_w + th : nullptr;
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = h->stream;
-    if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr, c.planes != nullptr)) return rc;
+    if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr && !blend, c.planes != nullptr, blend)) return rc;
     if (c.segment)
         if (int rc = grow_contour_buffers(h, 1, c.cap_points, c.cap_contours)) return rc;
     if (c.planes && !h->d_mnmx) HIP_TRY(hipMalloc(&h->d_mnmx, sizeof(unsigned) * 2 * Bm * C));
     mi_unet::Tiled &t = h->tiled;
-    // stage boundaries: start | pre | (gather | network + stitch) per micro-batch | postprocess | contours | download
-    const int nmb = (nt + Bm - 1) / Bm;
+    // stage boundaries: start | pre | (gather | network + stitch or blend) per micro-batch | postprocess | contours | download
+    const int nmb = (nk + Bm - 1) / Bm;
     const size_t n_marks = 2 + 2 * (size_t)nmb + 3;
     while (t.ev.size() < n_marks) {
         hipEvent_t ev;
@@ -1860,30 +1878,49 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
             if (int rc = stat_end(h, s, e1, ("tiled.normalise." + std::to_string(p)).c_str(), "normalise_u16", 3.0 * npix)) return rc;
         }
     }
+    if (blend) HIP_TRY(hipMemsetAsync(t.d_acc, 0, sizeof(float) * npix * classes, s));
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
 
-    // ---- tiles in tile order, micro-batches of max_batch: gather -> network -> stitch
-    float *d_tile_logits = c.logits ? h->d_logits : nullptr;
-    for (int t0 = 0; t0 < nt; t0 += Bm) {
-        const int nb = std::min(Bm, nt - t0);
+    // ---- tiles (views) in order, micro-batches of max_batch: gather -> network -> stitch, or -> blend (+ finalize after the last)
+    auto owned_px = [&](int tile) {
+        const int ty = tile / g.nx, tx = tile % g.nx;
+        return (double)(tile_cut(H, th, g.sy, g.ny, ty + 1) - tile_cut(H, th, g.sy, g.ny, ty)) *
+               (tile_cut(W, tw, g.sx, g.nx, tx + 1) - tile_cut(W, tw, g.sx, g.nx, tx));
+    };
+    float *d_tile_logits = (c.logits || blend) ? h->d_logits : nullptr;
+    for (int t0 = 0; t0 < nk; t0 += Bm) {
+        const int nb = std::min(Bm, nk - t0);
         const std::string tag = "[" + std::to_string(t0) + "," + std::to_string(t0 + nb) + ")";
         if (int rc = stat_begin(h, s, e1)) return rc;
-        e = launch_tile_gather(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, t0, nb, h->d_img, s);
+        e = nv > 1 ? launch_tile_gather_views(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, bl.mirror, t0, nb, h->d_img, s)
+                   : launch_tile_gather(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, t0, nb, h->d_img, s);
         if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": gather launch: " + hipGetErrorString(e));
         if (int rc = stat_end(h, s, e1, ("tiled.gather" + tag).c_str(), "tile_gather", 2.0 * nb * thw * C)) return rc;
         HIP_TRY(hipEventRecord(t.ev[mark++], s));
         if (int rc = run_microbatch(h, h->d_img, nb, h->d_labels, d_tile_logits)) return rc;
-        // owned pixels of this micro-batch: read once from the tile results, written once
-        double owned = 0;
-        for (int k = t0; k < t0 + nb; ++k) {
-            const int ty = k / g.nx, tx = k % g.nx;
-            owned += (double)(tile_cut(H, th, g.sy, g.ny, ty + 1) - tile_cut(H, th, g.sy, g.ny, ty)) *
-                     (tile_cut(W, tw, g.sx, g.nx, tx + 1) - tile_cut(W, tw, g.sx, g.nx, tx));
+        if (!blend) {
+            // owned pixels of this micro-batch: read once from the tile results, written once
+            double owned = 0;
+            for (int k = t0; k < t0 + nb; ++k) owned += owned_px(k);
+            if (int rc = stat_begin(h, s, e1)) return rc;
+            e = launch_tile_stitch(h->d_labels, d_tile_logits, classes, H, W, th, tw, c.halo, t0, nb, t.d_labels, c.logits ? t.d_logits : nullptr, s);
+            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": stitch launch: " + hipGetErrorString(e));
+            if (int rc = stat_end(h, s, e1, ("tiled.stitch" + tag).c_str(), "tile_stitch", 2.0 * owned * (1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
+        } else {
+            // per (view, pixel it contributes to): its logits read once, the accumulator read and written once
+            double covered = 0;
+            for (int k = t0; k < t0 + nb; ++k) covered += owner ? owned_px(k / nv) : (double)thw;
+            if (int rc = stat_begin(h, s, e1)) return rc;
+            e = launch_tile_blend(h->d_logits, classes, H, W, th, tw, c.halo, bl.mirror, owner, d_wy, d_wx, t0, nb, t.d_acc, s);
+            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": blend launch: " + hipGetErrorString(e));
+            if (int rc = stat_end(h, s, e1, ("tiled.blend" + tag).c_str(), "tile_blend", 12.0 * classes * covered)) return rc;
+            if (t0 + nb == nk) {
+                if (int rc = stat_begin(h, s, e1)) return rc;
+                e = launch_blend_finalize(t.d_acc, classes, H, W, th, tw, c.halo, bl.mirror, owner, d_wy, d_wx, t.d_labels, c.logits ? t.d_acc : nullptr, s);
+                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": blend finalize launch: " + hipGetErrorString(e));
+                if (int rc = stat_end(h, s, e1, "tiled.finalize", "blend_finalize", (double)npix * (4.0 * classes + 1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
+            }
         }
-        if (int rc = stat_begin(h, s, e1)) return rc;
-        e = launch_tile_stitch(h->d_labels, d_tile_logits, classes, H, W, th, tw, c.halo, t0, nb, t.d_labels, c.logits ? t.d_logits : nullptr, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": stitch launch: " + hipGetErrorString(e));
-        if (int rc = stat_end(h, s, e1, ("tiled.stitch" + tag).c_str(), "tile_stitch", 2.0 * owned * (1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
         HIP_TRY(hipEventRecord(t.ev[mark++], s));
     }
 
@@ -1907,7 +1944,7 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
     if (c.segment)
         if (int rc = contours_to_pinned(h, 1, c.cap_points, c.cap_contours)) return rc;
-    if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
+    if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, blend ? t.d_acc : t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipStreamSynchronize(s));
     host_copy(h, c.out_u8, t.h_out, npix);
@@ -1955,6 +1992,48 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
 }
 
 int mi_unet_tile_axis(int L, int T, int halo, int *origins, int *cuts) { return tile_axis(L, T, halo, origins, cuts); }
+
+int mi_unet_tile_blend_weights(int T, const mi_unet_tile_blend *b, float *w)
+{
+    if (T < 1 || !b || !w) return fail(MI_UNET_EARG, "mi_unet_tile_blend_weights: T < 1 or a null pointer");
+    if (b->mode < MI_UNET_BLEND_OWNER || b->mode > MI_UNET_BLEND_GAUSSIAN)
+        return fail(MI_UNET_EARG, "tile blend: unknown mode " + std::to_string(b->mode));
+    if (b->mirror < 0 || b->mirror > (MI_UNET_MIRROR_X | MI_UNET_MIRROR_Y))
+        return fail(MI_UNET_EARG, "tile blend: mirror " + std::to_string(b->mirror) + " is outside 0..3");
+    if (b->mode == MI_UNET_BLEND_GAUSSIAN && !(std::isfinite(b->sigma_scale) && b->sigma_scale > 0.f))
+        return fail(MI_UNET_EARG, "tile blend: the Gaussian needs a finite sigma_scale > 0");
+    // the definition of include/mi_unet.h: double, one rounding to float; i - c is exact, so w(i) == w(T - 1 - i)
+    const double c = (T - 1) / 2.0, s = (double)b->sigma_scale * T;
+    for (int i = 0; i < T; ++i) {
+        const double d = i - c;
+        w[i] = b->mode == MI_UNET_BLEND_GAUSSIAN ? (float)std::max(std::exp(-(d * d) / (2.0 * s * s)), 0x1p-20) : 1.f;
+    }
+    return MI_UNET_OK;
+}
+
+int mi_unet_set_tile_blend(mi_unet_t *h, const mi_unet_tile_blend *b)
+{
+    if (int rc = check_handle(h, false)) return rc;
+    const mi_unet_tile_blend def{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
+    const mi_unet_tile_blend nb = b ? *b : def;
+    const int th = h->cfg.height, tw = h->cfg.width;
+    std::vector<float> tab((size_t)th + tw);
+    if (int rc = mi_unet_tile_blend_weights(th, &nb, tab.data())) return rc;
+    if (int rc = mi_unet_tile_blend_weights(tw, &nb, tab.data() + th)) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (!h->d_blend_w) HIP_TRY(hipMalloc(&h->d_blend_w, sizeof(float) * tab.size()));
+    HIP_TRY(hipStreamSynchronize(h->stream));                            // no call of this handle still reads the old tables
+    HIP_TRY(hipMemcpy(h->d_blend_w, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    h->blend = nb;
+    return MI_UNET_OK;
+}
+
+int mi_unet_get_tile_blend(const mi_unet_t *h, mi_unet_tile_blend *b)
+{
+    if (!h || !b) return fail(MI_UNET_EARG, "mi_unet_get_tile_blend: null argument");
+    *b = h->blend;
+    return MI_UNET_OK;
+}
 
 int mi_unet_infer_tiled_u8(mi_unet_t *h, const uint8_t *img, int H, int W, int halo, uint8_t *labels, float *logits)
 {
@@ -2363,7 +2442,7 @@ void mi_unet_destroy(mi_unet_t *h)
         if (h->h_raw[r]) (void)hipHostFree(h->h_raw[r]);
         if (h->raw_done[r]) (void)hipEventDestroy(h->raw_done[r]);
     }
-    void *tiled_dev[] = { h->tiled.d_img, h->tiled.d_labels, h->tiled.d_vis, h->tiled.d_logits, h->tiled.d_raw };
+    void *tiled_dev[] = { h->tiled.d_img, h->tiled.d_labels, h->tiled.d_vis, h->tiled.d_logits, h->tiled.d_raw, h->tiled.d_acc, h->d_blend_w };
     for (void *q : tiled_dev)
         if (q) (void)hipFree(q);
     void *tiled_host[] = { h->tiled.h_img, h->tiled.h_out, h->tiled.h_raw };

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, tiles.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -169,6 +169,21 @@ hipError_t launch_tile_gather(const uint8_t *img, size_t img_bytes, int H, int W
 hipError_t launch_normalise_u16(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int dst_stride, hipStream_t s);
 hipError_t launch_tile_stitch(const uint8_t *tile_labels, const float *tile_logits, int classes, int H, int W, int th, int tw, int halo,
                               int t0, int nb, uint8_t *labels, float *logits, hipStream_t s);
+
+// Blended tiled inference (tiles.hip, blend.hip; DESIGN.md 7.3, the definition in include/mi_unet.h).  Views k = t * nv + v,
+// nv = tile_view_count(mirror), view v mirrored by tile_view_flip(mirror, v) (tile_grid.h).
+//   gather_views : image u8 [H][W][C] -> views k0 .. k0 + nb - 1 as u8 [nb][th][tw][C], each cut at its tile's origin and mirrored
+//   tile_blend   : their planar logits f32 [nb][classes][th][tw] -> acc [classes][H][W] += w * un-mirrored logit, per pixel in k
+//                  order; w = wy[i] * wx[j] (tables of th and tw floats, mi_unet_tile_blend_weights), or 1 and only the owning
+//                  tile's views when `owner`
+//   blend_finalize : acc / (the weights summed in k order) -> labels u8 [H][W] (first-max-wins argmax) and logits [classes][H][W]
+//                  when not null (may be acc: in place)
+hipError_t launch_tile_gather_views(const uint8_t *img, size_t img_bytes, int H, int W, int C, int th, int tw, int halo, int mirror,
+                                    int k0, int nb, uint8_t *tiles, hipStream_t s);
+hipError_t launch_tile_blend(const float *tile_logits, int classes, int H, int W, int th, int tw, int halo, int mirror, bool owner,
+                             const float *wy, const float *wx, int k0, int nb, float *acc, hipStream_t s);
+hipError_t launch_blend_finalize(const float *acc, int classes, int H, int W, int th, int tw, int halo, int mirror, bool owner,
+                                 const float *wy, const float *wx, uint8_t *labels, float *logits, hipStream_t s);
 
 // Device form of postprocess_mask (reference: src/postprocess.cpp:13-79), integer-exact.  Workspace `ws` must hold
 // postprocess_workspace_bytes(B, H, W) bytes; labels_in/out are u8 [B][H][W] (in-place allowed).

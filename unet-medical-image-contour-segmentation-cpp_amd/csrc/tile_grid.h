@@ -42,6 +42,15 @@ MIUNET_HD inline int tile_cut(int L, int T, int S, int n, int k)
     return (int)(((long long)tile_origin(L, T, S, k - 1) + T + tile_origin(L, T, S, k)) / 2);
 }
 
+// the tiles whose extent [o_k, o_k + T) holds position pos (0 <= pos < L) are exactly first .. last (blending)
+MIUNET_HD inline int tile_first_cover(int T, int S, int pos) { return pos < T ? 0 : (pos - T) / S + 1; }
+MIUNET_HD inline int tile_last_cover(int L, int T, int S, int n, int pos) { return pos >= L - T ? n - 1 : pos / S; }
+
+// mirror averaging (mirror = MI_UNET_MIRROR_X | MI_UNET_MIRROR_Y bits, 0..3): the views of one tile, in the order identity, X (if
+// bit 0), Y (if bit 1), XY (if both); view v's own flips as the same bits (1: columns reversed, 2: rows reversed)
+MIUNET_HD inline int tile_view_count(int mirror) { return mirror == 3 ? 4 : mirror ? 2 : 1; }
+MIUNET_HD inline int tile_view_flip(int mirror, int v) { return mirror == 3 ? v : v ? mirror : 0; }
+
 // origins[n] and cuts[n + 1] (either may be null); returns n, or -1 for an illegal (L, T, halo)
 inline int tile_axis(int L, int T, int halo, int *origins, int *cuts)
 {

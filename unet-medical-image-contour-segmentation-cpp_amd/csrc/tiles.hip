@@ -67,6 +67,41 @@ __global__ __launch_bounds__(256) void tile_gather_kernel(const uint8_t *__restr
     }
 }
 
+// The mirrored form (blending): views k0 .. k0 + nb - 1, nv views per tile (view v of tile t is k = t * nv + v), view
+// v mirrored by the bits (flips >> 2v) & 3 (1: X, column j <- tw - 1 - j; 2: Y, row i <- th - 1 - i).  Same lane layout as above.
+// An X-mirrored group of VEC bytes is the source group that ends where the output group starts, read the same way and byte-reversed;
+// VEC > 1 with X mirrors needs C == 1 (the launcher's choice), a multi-byte pixel takes the byte-wise path.
+template <int VEC>
+__global__ __launch_bounds__(256) void tile_gather_views_kernel(const uint8_t *__restrict__ img, uint8_t *__restrict__ tiles, TileGrid g,
+                                                                int C, int k0, int nv, unsigned flips, unsigned rpt, unsigned total)
+{
+    for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
+        const unsigned r = e / rpt, c = e - r * rpt;
+        const unsigned j = r / (unsigned)g.th, y = r - j * (unsigned)g.th;
+        const int k = k0 + (int)j, t = k / nv, v = k - t * nv, ty = t / g.nx, tx = t - ty * g.nx;
+        const unsigned f = (flips >> (2 * v)) & 3u;
+        const int oy = tile_origin(g.H, g.th, g.sy, ty), ox = tile_origin(g.W, g.tw, g.sx, tx);
+        const int sy = (f & 2u) ? g.th - 1 - (int)y : (int)y;
+        const uint8_t *row = img + ((size_t)(oy + sy) * g.W + ox) * C;
+        if constexpr (VEC >= 4) {
+            uint32_t w[VEC / 4];
+            if (!(f & 1u)) {
+                load_unaligned<VEC / 4>(row + (size_t)c * VEC, w);
+                store_words<VEC / 4>(tiles + (size_t)e * VEC, w);
+            } else {
+                load_unaligned<VEC / 4>(row + (size_t)g.tw - (size_t)(c + 1) * VEC, w);
+                uint32_t o[VEC / 4];
+#pragma unroll
+                for (int q = 0; q < VEC / 4; ++q) o[q] = __builtin_bswap32(w[VEC / 4 - 1 - q]);
+                store_words<VEC / 4>(tiles + (size_t)e * VEC, o);
+            }
+        } else {
+            const unsigned x = c / (unsigned)C, ch = c - x * (unsigned)C;
+            tiles[e] = row[(size_t)((f & 1u) ? (unsigned)g.tw - 1 - x : x) * C + ch];
+        }
+    }
+}
+
 // RAW16 -> u8 at the image's own size: resample_u8_kernel (image_stages.hip) at outW == w, outH == h, where dx = dy = 0 and the
 // four-tap sum is the pixel itself.  The quantisation is that kernel's, operation for operation (fp64, one rounding each, no
 // contraction); 8 samples per lane, one 16-byte load.
@@ -204,6 +239,33 @@ hipError_t launch_tile_gather(const uint8_t *img, size_t img_bytes, int H, int W
     else if (vec == 4) MIUNET_GATHER(4);
     else MIUNET_GATHER(1);
 #undef MIUNET_GATHER
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_gather_views(const uint8_t *img, size_t img_bytes, int H, int W, int C, int th, int tw, int halo, int mirror,
+                                    int k0, int nb, uint8_t *tiles, hipStream_t s)
+{
+    TileGrid g;
+    if (!img || !tiles || C < 1 || C > 4 || mirror < 0 || mirror > 3 || !tile_grid(H, W, th, tw, halo, g)) return hipErrorInvalidValue;
+    const int nv = tile_view_count(mirror);
+    if (k0 < 0 || nb < 0 || (long long)k0 + nb > (long long)g.ny * g.nx * nv) return hipErrorInvalidValue;
+    const size_t need = (size_t)H * W * C, row = (size_t)tw * C;
+    if (img_bytes < need) return hipErrorInvalidValue;
+    if (nb == 0) return hipSuccess;
+    unsigned flips = 0;
+    for (int v = 0; v < nv; ++v) flips |= (unsigned)tile_view_flip(mirror, v) << (2 * v);
+    const uintptr_t pi = reinterpret_cast<uintptr_t>(img), pt = reinterpret_cast<uintptr_t>(tiles);
+    const bool dwords = pi % 4 == 0 && img_bytes >= (need + 3) / 4 * 4 && row % 4 == 0 && (C == 1 || !(mirror & 1));
+    const int vec = !dwords ? 1 : (row % 16 == 0 && pt % 16 == 0) ? 16 : (row % 8 == 0 && pt % 8 == 0) ? 8 : pt % 4 == 0 ? 4 : 1;
+    const unsigned long long rpt = row / vec, total = rpt * th * nb;
+    if (total >= (1ull << 31)) return hipErrorInvalidValue;
+#define MIUNET_GATHER_VIEWS(V) \
+    hipLaunchKernelGGL(tile_gather_views_kernel<V>, dim3(grid_for((unsigned)total)), dim3(256), 0, s, img, tiles, g, C, k0, nv, flips, (unsigned)rpt, (unsigned)total)
+    if (vec == 16) MIUNET_GATHER_VIEWS(16);
+    else if (vec == 8) MIUNET_GATHER_VIEWS(8);
+    else if (vec == 4) MIUNET_GATHER_VIEWS(4);
+    else MIUNET_GATHER_VIEWS(1);
+#undef MIUNET_GATHER_VIEWS
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@ EXPORTS = [
     "mi_unet_group_weight_transport", "mi_unet_group_gather", "mi_unet_group_infer_u8", "mi_unet_group_infer_raw16",
     "mi_unet_group_segment_raw16", "mi_unet_group_destroy", "mi_unet_shard_range",
     "mi_unet_tile_axis", "mi_unet_infer_tiled_u8", "mi_unet_infer_tiled_raw16", "mi_unet_segment_tiled_raw16",
+    "mi_unet_set_tile_blend", "mi_unet_get_tile_blend", "mi_unet_tile_blend_weights",
 ]
 
 
@@ -49,6 +50,20 @@ class LayerInfo(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["name"], d["kernel"], d["kind"] = self.name.decode(), self.kernel.decode(), self.KINDS[self.kind]
         return d
+
+
+class TileBlend(C.Structure):
+    _fields_ = [("mode", C.c_int), ("sigma_scale", C.c_float), ("mirror", C.c_int)]
+
+
+BLEND_MODES = {"owner": 0, "constant": 1, "gaussian": 2}
+MIRRORS = {"": 0, "x": 1, "y": 2, "xy": 3}
+
+
+def _tile_blend(mode, sigma_scale, mirror) -> TileBlend:
+    """mode / mirror by name (BLEND_MODES, MIRRORS) or as the raw C values, which the library checks"""
+    return TileBlend(BLEND_MODES[mode] if isinstance(mode, str) else int(mode), float(sigma_scale),
+                     MIRRORS[mirror] if isinstance(mirror, str) else int(mirror))
 
 
 class MiUnetError(RuntimeError):
@@ -129,6 +144,9 @@ def lib():
                                                 C.c_void_p]
         L.mi_unet_segment_tiled_raw16.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.mi_unet_set_tile_blend.argtypes = [C.c_void_p, C.POINTER(TileBlend)]
+        L.mi_unet_get_tile_blend.argtypes = [C.c_void_p, C.POINTER(TileBlend)]
+        L.mi_unet_tile_blend_weights.argtypes = [C.c_int, C.POINTER(TileBlend), C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -312,7 +330,8 @@ class Engine:
 
     def infer_tiled(self, img: np.ndarray, halo: int, want_logits=False):
         """One image u8 [H,W(,C)] of any size >= the engine's tile -> labels u8 [H,W], logits f32 [classes,H,W] or None; run as
-        overlapping tiles of the engine's size, each pixel taken from the tile that owns it (tile_axis)."""
+        overlapping tiles of the engine's size, each pixel taken from the tile that owns it (tile_axis) or, after set_tile_blend,
+        the weighted mean of the tiles (and mirrored views) that cover it."""
         c = self.cfg
         img = np.ascontiguousarray(img, dtype=np.uint8)
         if img.ndim == 2:
@@ -324,6 +343,19 @@ class Engine:
         logits = np.empty((c.classes, hh, ww), np.float32) if want_logits else None
         _check(lib().mi_unet_infer_tiled_u8(self._h, _ptr(img), hh, ww, halo, _ptr(labels), _ptr(logits)))
         return labels, logits
+
+    def set_tile_blend(self, mode="owner", sigma_scale=0.125, mirror=""):
+        """How the tiled calls combine overlapping tiles (mi_unet_set_tile_blend): mode "owner" | "constant" | "gaussian", mirror
+        "" | "x" | "y" | "xy" (test-time mirror averaging).  mode=None restores the default (owner, 0.125, no mirror)."""
+        b = None if mode is None else C.byref(_tile_blend(mode, sigma_scale, mirror))
+        _check(lib().mi_unet_set_tile_blend(self._h, b))
+
+    def get_tile_blend(self):
+        """-> {"mode": name, "sigma_scale": float, "mirror": name}"""
+        b = TileBlend()
+        _check(lib().mi_unet_get_tile_blend(self._h, C.byref(b)))
+        return {"mode": {v: k for k, v in BLEND_MODES.items()}[b.mode], "sigma_scale": b.sigma_scale,
+                "mirror": {v: k for k, v in MIRRORS.items()}[b.mirror]}
 
     def _tiled_planes(self, planes):
         """in_ch u16 planes of one size [H,W] -> (keep-alive list, pointer array, H, W)"""
@@ -467,6 +499,13 @@ def tile_axis(L: int, T: int, halo: int):
     origins, cuts = (C.c_int * n)(), (C.c_int * (n + 1))()
     lib().mi_unet_tile_axis(L, T, halo, origins, cuts)
     return list(origins), list(cuts)
+
+
+def tile_blend_weights(T: int, mode="gaussian", sigma_scale=0.125, mirror=""):
+    """The weight table of one tile axis of length T that the blending kernels use (mi_unet_tile_blend_weights): f32 [T]."""
+    w = np.empty(T if T > 0 else 0, np.float32)
+    _check(lib().mi_unet_tile_blend_weights(T, C.byref(_tile_blend(mode, sigma_scale, mirror)), _ptr(w)))
+    return w
 
 
 class Group:
