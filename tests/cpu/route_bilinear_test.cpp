@@ -1,65 +1,19 @@
-// route_bilinear_test.cpp -- the conv3x3 layers of the bilinear decoder's plan (engine.cpp build_plan with a version 2 weight file,
-// up_mode 1) through the routing of csrc/routing.cpp, on a CPU: every layer gets a route, and the shape predicate that guards
-// the route's launcher (where routing.h has one) accepts the layer.  The upsample steps themselves are launched by the engine
-// (Route::UPSAMPLE) and take no ConvArgs.  Prints the route table.
-// Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include route_bilinear_test.cpp ../../<pkg>/csrc/routing.cpp
-#include <cstdio>
-#include <string>
-#include <vector>
-
-#include "../../include/mi_unet.h"
-#include "../../unet-medical-image-contour-segmentation-cpp_amd/csrc/routing.h"
+// route_bilinear_test.cpp -- the conv3x3 layers of the bilinear decoder's plan (csrc/plan.cpp build_plan on a version 2 weight file,
+// up_mode 1, laid out by csrc/weights.cpp) through route_plan and the routing of csrc/routing.cpp, on a CPU with made-up buffer
+// addresses: every layer gets a route, and the shape predicate that guards the route's launcher (where routing.h has one) accepts
+// the layer.  The upsample steps themselves are launched by the engine (Route::UPSAMPLE) and take no ConvArgs.  Prints the route table.
+// Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include route_bilinear_test.cpp ../../<pkg>/csrc/{routing,plan,weights}.cpp
+// Run: route_bilinear_test <bilinear weights of NETS[0]> <bilinear weights of NETS[1]>   (MIUNETW1 files of miunet.spec)
+#include "real_plan.h"
 
 using namespace miunet;
+using real_plan::dummy;
+using real_plan::dummy_u8;
 
 namespace {
 
-float dummy[1];
-uint8_t dummy_u8[1];
-
 struct Net { const char *what; int size, in_ch, base, levels, classes; };
 const Net NETS[] = { { "512 x 512 x 1, base 64, 4 levels", 512, 1, 64, 4, 3 }, { "1024 x 1024 x 3, base 32, 5 levels", 1024, 3, 32, 5, 3 } };
-
-struct Layer { std::string name; ConvArgs a; };
-
-// the conv3x3 layers of the bilinear plan, inc.c2 first (inc.c1 is the stand-alone first layer)
-std::vector<Layer> bilinear_unet(const Net &n, int algo)
-{
-    std::vector<Layer> out;
-    int ch[8];
-    for (int i = 0; i <= n.levels; ++i) ch[i] = n.base << i;
-    const bool packed4 = algo == MI_UNET_CONV_WINOGRAD;
-    auto layer = [&](const std::string &name, int H, int cin, int cout, int ldc, int ldo, int pool_ld) {
-        Layer l{ name, ConvArgs{} };
-        ConvArgs &a = l.a;
-        a.in = dummy; a.wpk = dummy; a.bias = dummy; a.out = dummy;
-        a.wpk4 = cout % 64 == 0 && packed4 ? dummy : nullptr;
-        a.H = H; a.W = H; a.Cin = cin; a.ldc = ldc; a.Cout = cout;
-        a.CoutPad = (cout + NPAD - 1) / NPAD * NPAD;
-        a.ldo = ldo; a.co_off = 0; a.relu = 1;
-        if (pool_ld) { a.pool_out = dummy; a.pool_ld = pool_ld; }
-        out.push_back(l);
-    };
-    const int L = n.levels;
-    int H = n.size;
-    layer("inc.c2", H, ch[0], ch[0], ch[0], 2 * ch[0], ch[0]);
-    for (int i = 1; i <= L; ++i) {
-        H /= 2;
-        const std::string d = "down" + std::to_string(i);
-        const int co = i == L ? ch[L - 1] : ch[i];
-        layer(d + ".c1", H, ch[i - 1], co, ch[i - 1], co, 0);
-        if (i < L) layer(d + ".c2", H, ch[i], ch[i], ch[i], 2 * ch[i], ch[i]);
-        else layer(d + ".c2", H, co, co, co, co, 0);
-    }
-    for (int i = 1; i <= L; ++i) {
-        const int lvl = L - i, c = ch[lvl], cout = lvl > 0 ? c / 2 : c;
-        const std::string u = "up" + std::to_string(i);
-        H *= 2;
-        layer(u + ".c1", H, 2 * c, c, 2 * c, c, 0);
-        layer(u + ".c2", H, c, cout, c, cout, 0);
-    }
-    return out;
-}
 
 // the predicate routing.h names for the launcher of route `r` (true where there is none)
 bool predicate_accepts(Route r, unsigned fused, const ConvArgs &a, int first_cin)
@@ -87,49 +41,49 @@ const Plan PLANS[] = {
 
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc != 3) { printf("usage: route_bilinear_test <bilinear weights of net 0> <bilinear weights of net 1>\n"); return 2; }
     int bad = 0, checked = 0;
-    for (const Net &n : NETS)
+    for (size_t ni = 0; ni < 2; ++ni)
         for (const Plan &p : PLANS) {
+            const Net &n = NETS[ni];
             const bool lp = p.algo == MI_UNET_CONV_BF16 || p.algo == MI_UNET_CONV_FP16;
-            const RoutePolicy pol{ p.algo, p.guard_tripped, 256 };
-            const std::vector<Layer> layers = bilinear_unet(n, p.algo);
-            printf("== %s, %s\n%-10s", n.what, p.what, "layer");
+            PlanInput in;
+            const std::vector<Step> plan = real_plan::load(argv[1 + ni], n.size, n.in_ch, n.base, n.levels, n.classes, 16, p.algo, UP_BILINEAR, in);
+            in.guard_tripped = p.guard_tripped;
             const int batches[] = { 1, 2, 4, 8, 16 };
+            std::vector<std::vector<Launch>> launches(5);
+            for (int b = 0; b < 5; ++b)
+                route_plan(in, plan, dummy_u8, batches[b], dummy_u8, dummy + 12, real_plan::lp_kind(p.algo), launches[b]);
+            printf("== %s, %s\n%-10s", n.what, p.what, "layer");
             for (int B : batches) printf(" %-22s", ("batch " + std::to_string(B)).c_str());
             printf("\n");
-            for (size_t i = 0; i < layers.size(); ++i) {
-                printf("%-10s", layers[i].name.c_str());
-                for (int B : batches) {
-                    ConvArgs a = layers[i].a;
-                    a.B = B;
-                    a.rt = Routing{};
-                    a.ksplit_ws = dummy;
-                    a.ksplit_ws_bytes = (size_t)64 << 20;
-                    const bool last = i + 1 == layers.size();
-                    a.out_lp = lp && !last;
-                    unsigned want = 0;
-                    if (last && (a.wpk4 != nullptr || lp)) {
-                        a.head_w = dummy; a.head_b = dummy; a.head_classes = n.classes; a.head_logits = dummy; a.head_labels = dummy_u8;
-                        want |= FUSE_HEAD;
-                    }
-                    if (i == 0) { a.first_cin = n.in_ch; want |= FUSE_FIRST; }
-                    const RouteChoice rc = route_conv(a, pol, want);
-                    if (!(rc.fused & FUSE_HEAD)) { a.head_w = a.head_b = nullptr; a.head_classes = 0; a.head_logits = nullptr; a.head_labels = nullptr; }
+            // the plan routed is the whole network: 4 conv3x3 per level + inc.c2 (17, config 5: 21) and no transposed conv
+            int convs = 0, convTs = 0;
+            for (const Step &st : plan) { convs += st.kind == Step::CONV; convTs += st.kind == Step::CONVT; }
+            if (convs != 4 * n.levels + 1 || convTs != 0) { printf("%s, %s: the plan has %d conv3x3 and %d transposed-conv steps\n", n.what, p.what, convs, convTs); ++bad; }
+            for (size_t i = 0; i < plan.size(); ++i) {
+                if (plan[i].kind != Step::CONV) continue;
+                const char *layer = plan[i].name.c_str();
+                printf("%-10s", layer);
+                for (int b = 0; b < 5; ++b) {
+                    const int B = batches[b];
+                    const ConvArgs &a = launches[b][i].a;
+                    const RouteChoice rc = launches[b][i].rc;
                     const std::string name = route_name(rc.route, rc.fused);
                     printf(" %-22s", name.c_str());
                     ++checked;
                     if (!predicate_accepts(rc.route, rc.fused, a, n.in_ch)) {
-                        printf("\n%s, %s, batch %d: %s routed to %s, whose shape predicate refuses it\n", n.what, p.what, B, layers[i].name.c_str(), name.c_str());
+                        printf("\n%s, %s, batch %d: %s routed to %s, whose shape predicate refuses it\n", n.what, p.what, B, layer, name.c_str());
                         ++bad;
                     }
                     if (lp != (name.find("bf16") != std::string::npos || name.find("fp16") != std::string::npos)) {
-                        printf("\n%s, %s, batch %d: %s routed to %s, a kernel of the other precision\n", n.what, p.what, B, layers[i].name.c_str(), name.c_str());
+                        printf("\n%s, %s, batch %d: %s routed to %s, a kernel of the other precision\n", n.what, p.what, B, layer, name.c_str());
                         ++bad;
                     }
                     if (p.guard_tripped && rc.route != Route::CONV_WINO) {
-                        printf("\n%s: the tripped guard must keep %s on F(2x2,3x3)\n", n.what, layers[i].name.c_str());
+                        printf("\n%s: the tripped guard must keep %s on F(2x2,3x3)\n", n.what, layer);
                         ++bad;
                     }
                 }

@@ -1,65 +1,39 @@
-// route_test.cpp -- the kernel every layer of the shipped plans is routed to (csrc/routing.cpp), on a CPU.  The expected names are
-// what the engine launched before the routing had one owner: mi_unet_get_kernel_stats of the fp32, bf16 and fp16 plans on an
-// MI355X (256 CUs), the same as profiles/r04_per_layer.txt, r04_bf16_per_layer.txt and r04_fp16_per_layer.txt where those cover
-// the case.  Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include route_test.cpp ../../<pkg>/csrc/routing.cpp
-#include <cstdio>
-#include <string>
-#include <vector>
+// route_test.cpp -- the kernel every layer of the shipped plans is routed to (csrc/routing.cpp), on a CPU.  The plan is the engine's
+// own: engine_pack_weights (csrc/weights.cpp) lays out a real weight file, build_plan and route_plan (csrc/plan.cpp) run on made-up
+// buffer addresses.  The expected names are what the engine launched before the routing had one owner: mi_unet_get_kernel_stats of
+// the fp32, bf16 and fp16 plans on an MI355X (256 CUs), the same as profiles/r04_per_layer.txt, r04_bf16_per_layer.txt and
+// r04_fp16_per_layer.txt where those cover the case.
+// Build (with real_plan.h): g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include route_test.cpp ../../<pkg>/csrc/{routing,plan,weights}.cpp
+// Run: route_test <weights of FP32> <weights of CFG5>   (MIUNETW1 files of miunet.spec, transposed decoder)
+#include <map>
+#include <utility>
 
-#include "../../include/mi_unet.h"
-#include "../../unet-medical-image-contour-segmentation-cpp_amd/csrc/routing.h"
+#include "real_plan.h"
 
 using namespace miunet;
+using real_plan::dummy;
+using real_plan::dummy_u8;
 
 namespace {
 
-float dummy[1];
-uint8_t dummy_u8[1];
+struct Net { int size, in_ch, base, levels, classes, file; };    // file: index of the weight file on the command line
+const Net FP32 = { 512, 1, 64, 4, 3, 0 };     // BASELINE configs 1-3 (the bf16 and fp16 plans of config 3 too)
+const Net CFG5 = { 1024, 3, 32, 5, 3, 1 };    // BASELINE config 5
+const char *weight_files[2];
+const int MAX_BATCH = 64;
 
-struct Net { int size, in_ch, base, levels, classes; };
-const Net FP32 = { 512, 1, 64, 4, 3 };        // BASELINE configs 1-3 (the bf16 and fp16 plans of config 3 too)
-const Net CFG5 = { 1024, 3, 32, 5, 3 };       // BASELINE config 5
-
-struct Layer { std::string name; bool convT; ConvArgs a; };
-
-// The conv3x3 and transposed-conv layers of the plan (engine.cpp build_plan), inc.c2 first: input size, channels, channel
-// strides of the concat buffers, fused pooling; the weights packed for F(4x4) / per-tap where the fp32 plans pack them.
-std::vector<Layer> unet(const Net &n, int algo)
+// the engine's plan of net `n` for `algo`: built once per pair
+const std::vector<Step> &plan_of(const Net &n, int algo, PlanInput &in)
 {
-    std::vector<Layer> out;
-    int ch[8];
-    for (int i = 0; i <= n.levels; ++i) ch[i] = n.base << i;
-    const bool packed4 = algo == MI_UNET_CONV_WINOGRAD;
-    const bool lp = algo == MI_UNET_CONV_BF16 || algo == MI_UNET_CONV_FP16;
-    auto layer = [&](const std::string &name, bool convT, int H, int cin, int cout, int ldo, int co_off, int pool_ld) {
-        Layer l{ name, convT, ConvArgs{} };
-        ConvArgs &a = l.a;
-        a.in = dummy; a.wpk = dummy; a.bias = dummy; a.out = dummy;
-        a.wpk4 = cout % 64 == 0 && (convT ? !lp : packed4) ? dummy : nullptr;
-        a.H = H; a.W = H; a.Cin = cin; a.ldc = cin; a.Cout = cout;
-        a.CoutPad = ((convT ? 4 * cout : cout) + NPAD - 1) / NPAD * NPAD;
-        a.ldo = ldo; a.co_off = co_off; a.relu = !convT;
-        if (pool_ld) { a.pool_out = dummy; a.pool_ld = pool_ld; }
-        out.push_back(l);
-    };
-    int H = n.size;
-    layer("inc.c2", false, H, ch[0], ch[0], 2 * ch[0], 0, ch[0]);
-    for (int i = 1; i <= n.levels; ++i) {
-        H /= 2;
-        const std::string d = "down" + std::to_string(i);
-        layer(d + ".c1", false, H, ch[i - 1], ch[i], ch[i], 0, 0);
-        if (i < n.levels) layer(d + ".c2", false, H, ch[i], ch[i], 2 * ch[i], 0, ch[i]);
-        else layer(d + ".c2", false, H, ch[i], ch[i], ch[i], 0, 0);
+    static std::map<std::pair<int, int>, std::pair<PlanInput, std::vector<Step>>> cache;
+    auto it = cache.find({ n.file, algo });
+    if (it == cache.end()) {
+        PlanInput pi;
+        std::vector<Step> plan = real_plan::load(weight_files[n.file], n.size, n.in_ch, n.base, n.levels, n.classes, MAX_BATCH, algo, UP_TRANSPOSE, pi);
+        it = cache.emplace(std::make_pair(n.file, algo), std::make_pair(pi, std::move(plan))).first;
     }
-    for (int i = 1; i <= n.levels; ++i) {
-        const int cin = ch[n.levels - i + 1], cout = cin / 2;
-        const std::string u = "up" + std::to_string(i);
-        layer(u + ".t", true, H, cin, cout, 2 * cout, cout, 0);
-        H *= 2;
-        layer(u + ".c1", false, H, cin, cout, cout, 0, 0);
-        layer(u + ".c2", false, H, cout, cout, cout, 0, 0);
-    }
-    return out;
+    in = it->second.first;
+    return it->second.second;
 }
 
 struct Case {
@@ -70,36 +44,26 @@ struct Case {
     std::vector<std::string> expect;       // per layer, in plan order
 };
 
-// The route of every layer as the engine asks for it: the last conv with the head, inc.c2 with the first layer.
-std::vector<std::string> route_names(const Net &n, int algo, int B, bool guard_tripped, bool ksplit)
+struct Routed { std::vector<std::string> layer, route; int convs = 0, convTs = 0; };
+
+// The route of every conv3x3 (after the stand-alone first layer) and transposed-conv step, as route_plan launches a batch of B
+Routed route_names(const Net &n, int algo, int B, bool guard_tripped, bool ksplit)
 {
-    const RoutePolicy pol{ algo, guard_tripped, 256 };
-    const bool lp = algo == MI_UNET_CONV_BF16 || algo == MI_UNET_CONV_FP16;
-    std::vector<Layer> layers = unet(n, algo);
-    std::vector<std::string> names;
-    for (size_t i = 0; i < layers.size(); ++i) {
-        ConvArgs a = layers[i].a;
-        a.B = B;
-        a.rt = Routing{};
-        if (layers[i].convT) {
-            a.out_lp = lp;
-            names.push_back(route_name(route_convT(a, pol)));
-            continue;
-        }
-        const bool last = i + 1 == layers.size();
-        a.ksplit_ws = ksplit ? dummy : nullptr;
-        a.ksplit_ws_bytes = ksplit ? (size_t)64 << 20 : 0;
-        a.out_lp = lp && !last;
-        unsigned want = 0;
-        if (last && (a.wpk4 != nullptr || lp)) {
-            a.head_w = dummy; a.head_b = dummy; a.head_classes = n.classes; a.head_logits = dummy; a.head_labels = dummy_u8;
-            want |= FUSE_HEAD;
-        }
-        if (i == 0) { a.first_cin = n.in_ch; want |= FUSE_FIRST; }
-        const RouteChoice rc = route_conv(a, pol, want);
-        names.push_back(route_name(rc.route, rc.fused));
+    PlanInput in;
+    const std::vector<Step> &plan = plan_of(n, algo, in);
+    in.guard_tripped = guard_tripped;
+    in.ksplit = ksplit ? dummy + 11 : nullptr;
+    in.ksplit_bytes = ksplit ? (size_t)64 << 20 : 0;
+    std::vector<Launch> launches;
+    route_plan(in, plan, dummy_u8, B, dummy_u8, dummy + 12, real_plan::lp_kind(algo), launches);
+    Routed r;
+    for (size_t i = 0; i < plan.size(); ++i) {
+        if (plan[i].kind != Step::CONV && plan[i].kind != Step::CONVT) continue;
+        ++(plan[i].kind == Step::CONV ? r.convs : r.convTs);
+        r.layer.push_back(plan[i].name);
+        r.route.push_back(route_name(launches[i].rc.route, launches[i].rc.fused));
     }
-    return names;
+    return r;
 }
 
 const Case cases[] = {
@@ -193,20 +157,24 @@ const Case cases[] = {
 
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc != 3) { printf("usage: route_test <weights of the 512 x 512 x 1 base-64 net> <weights of config 5>\n"); return 2; }
+    weight_files[0] = argv[1]; weight_files[1] = argv[2];
     int bad = 0;
     for (const Case &c : cases) {
-        const std::vector<Layer> layers = unet(c.net, c.algo);
-        const std::vector<std::string> got = route_names(c.net, c.algo, c.B, c.guard_tripped, c.ksplit);
+        const Routed r = route_names(c.net, c.algo, c.B, c.guard_tripped, c.ksplit);
+        const std::vector<std::string> &got = r.route;
+        // the plan routed is the whole network: 4 conv3x3 + 1 transposed conv per level, inc.c2 (17 + 4, config 5: 21 + 5)
+        if (r.convs != 4 * c.net.levels + 1 || r.convTs != c.net.levels) { printf("%s: the plan has %d conv3x3 and %d transposed-conv steps\n", c.what, r.convs, r.convTs); ++bad; }
         if (got.size() != c.expect.size()) { printf("%s: %zu layers, expected %zu\n", c.what, got.size(), c.expect.size()); ++bad; continue; }
         for (size_t i = 0; i < got.size(); ++i)
-            if (got[i] != c.expect[i]) { printf("%s: %s routed to %s, expected %s\n", c.what, layers[i].name.c_str(), got[i].c_str(), c.expect[i].c_str()); ++bad; }
+            if (got[i] != c.expect[i]) { printf("%s: %s routed to %s, expected %s\n", c.what, r.layer[i].c_str(), got[i].c_str(), c.expect[i].c_str()); ++bad; }
     }
     // batch-invariant mode (MIUNET_SPLITK=0: no split-K workspace): no layer's route depends on B
-    const std::vector<std::string> b1 = route_names(FP32, MI_UNET_CONV_WINOGRAD, 1, false, false);
+    const std::vector<std::string> b1 = route_names(FP32, MI_UNET_CONV_WINOGRAD, 1, false, false).route;
     for (int B = 2; B <= 64; ++B)
-        if (route_names(FP32, MI_UNET_CONV_WINOGRAD, B, false, false) != b1) { printf("MIUNET_SPLITK=0: the routes at batch %d differ from batch 1\n", B); ++bad; }
+        if (route_names(FP32, MI_UNET_CONV_WINOGRAD, B, false, false).route != b1) { printf("MIUNET_SPLITK=0: the routes at batch %d differ from batch 1\n", B); ++bad; }
     // the steps the engine launches itself
     if (route_name(Route::FIRST) != "conv3x3_first" || route_name(Route::POOL) != "maxpool2x2" || route_name(Route::HEAD) != "head_argmax") {
         printf("first / pool / head kernel names changed\n");

@@ -101,7 +101,16 @@ def test_routing_of_every_shipped_layer(tmp_path):
     exe = tmp_path / "route_test"
     pkg = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", str(exe),
-                           os.path.join(ROOT, "tests", "cpu", "route_test.cpp"), os.path.join(pkg, "csrc", "routing.cpp")])
-    r = subprocess.run([str(exe)], capture_output=True, timeout=120)
+                           os.path.join(ROOT, "tests", "cpu", "route_test.cpp")] +
+                          [os.path.join(pkg, "csrc", f) for f in ("routing.cpp", "plan.cpp", "weights.cpp")])
+    # the test routes the engine's own plan of real weight files: the two shipped networks, synthetic weights
+    from miunet import synth
+    from miunet.spec import UNetSpec, pack_weights
+    files = []
+    for i, spec in enumerate((UNetSpec(1, 64, 4, 3), UNetSpec(3, 32, 5, 3))):
+        files.append(str(tmp_path / f"net{i}.bin"))
+        with open(files[-1], "wb") as f:
+            f.write(pack_weights(spec, synth.make_weights(spec, 1234)))
+    r = subprocess.run([str(exe)] + files, capture_output=True, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-4000:] + r.stderr.decode()[-2000:]
     assert b"all routing checks passed" in r.stdout

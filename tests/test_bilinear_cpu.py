@@ -230,8 +230,14 @@ def test_bilinear_plan_routes(tmp_path):
     512 x 512 base-64 and the 1024 x 1024 x 3 base-32 five-level nets) gets a route whose shape predicate accepts it"""
     exe = tmp_path / "route_bilinear_test"
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", str(exe),
-                           os.path.join(ROOT, "tests", "cpu", "route_bilinear_test.cpp"), os.path.join(PKG, "csrc", "routing.cpp")])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+                           os.path.join(ROOT, "tests", "cpu", "route_bilinear_test.cpp")] +
+                          [os.path.join(PKG, "csrc", f) for f in ("routing.cpp", "plan.cpp", "weights.cpp")])
+    files = []                                   # the test routes the engine's own plan of real (version 2, bilinear) weight files
+    for i, spec in enumerate((UNetSpec(1, 64, 4, 3, up="bilinear"), UNetSpec(3, 32, 5, 3, up="bilinear"))):
+        files.append(str(tmp_path / f"net{i}.bin"))
+        with open(files[-1], "wb") as f:
+            f.write(pack_weights(spec, synth.make_weights(spec, 1234)))
+    r = subprocess.run([str(exe)] + files, capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-4000:]
     assert "upsample2x_bilinear" not in r.stdout and "all 760 bilinear routing checks passed" in r.stdout

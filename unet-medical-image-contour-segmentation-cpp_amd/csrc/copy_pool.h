@@ -1,4 +1,4 @@
-// copy_pool.h -- the pageable -> pinned staging copy of the RAW-in entry points (engine.cpp), free of any device API so that
+// copy_pool.h -- the pageable -> pinned staging copy of the RAW-in entry points (pipeline_raw.cpp), free of any device API so that
 // it can be compiled and tested without a GPU (tests/cpu/copy_pool_test.cpp).  Internal to libmiunet.so.
 #pragma once
 #include <algorithm>

@@ -1,0 +1,310 @@
+// debug.cpp -- the test and diagnosis entry points: mi_unet_layer_debug (one kernel on caller-supplied operands),
+// mi_unet_debug_layer_info / mi_unet_debug_capture and the taps launch_plan calls for them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "engine_handle.h"
+
+using namespace miunet;
+
+namespace {
+
+// one image's [npix][C] tensor (pixel stride `ld` elements of `bits` bits, kind: 1 = bf16, 2 = fp16 for 16-bit storage) -> dense floats
+int download_tensor(hipStream_t s, const void *d, int bits, int lp_kind, size_t npix, int C, int ld, float *dst)
+{
+    if (!dst) return 0;
+    const size_t eb = (size_t)bits / 8;
+    std::vector<unsigned char> raw(npix * C * eb);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy2D(raw.data(), C * eb, d, (size_t)ld * eb, C * eb, npix, hipMemcpyDeviceToHost));
+    const size_t n = npix * C;
+    if (bits == 32) memcpy(dst, raw.data(), n * 4);
+    else if (bits == 8) for (size_t i = 0; i < n; ++i) dst[i] = (float)raw[i];
+    else {
+        const uint16_t *r16 = reinterpret_cast<const uint16_t *>(raw.data());
+        for (size_t i = 0; i < n; ++i) dst[i] = lp_kind == 2 ? fp16_to_float(r16[i]) : bf16_to_float(r16[i]);
+    }
+    return 0;
+}
+
+}  // namespace
+
+namespace miunet {
+
+// mi_unet_debug_capture: the tensor step `st` is about to read ...
+int tap_input(mi_unet *h, const Step &st, const Launch &l, const uint8_t *d_imgs, int lp_kind)
+{
+    hipStream_t s = h->stream;
+    const size_t im = (size_t)h->tap.img;
+    const int abits = lp_kind ? 16 : 32;
+    if (st.kind == Step::FIRST || (l.rc.fused & FUSE_FIRST)) {
+        // (a step that runs the first layer in its loader reads the u8 image: that is what the caller's `in` buffer receives)
+        const Step &f = h->plan[0];
+        h->tap.info->in_bits = 8;
+        h->tap.info->fused_first = st.kind != Step::FIRST;
+        return download_tensor(s, d_imgs + im * f.H * f.W * f.C, 8, 0, (size_t)f.H * f.W, f.C, f.C, h->tap.in);
+    }
+    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
+        h->tap.info->in_bits = abits;
+        const size_t npix = (size_t)st.a.H * st.a.W;
+        return download_tensor(s, reinterpret_cast<const char *>(st.a.in) + im * npix * st.a.ldc * (abits / 8), abits, lp_kind, npix, st.a.Cin,
+                               st.a.ldc, h->tap.in);
+    }
+    const int b = st.kind == Step::HEAD ? 32 : abits;           // POOL, UPSAMPLE (activation type), HEAD (always fp32)
+    h->tap.info->in_bits = b;
+    const size_t npix = (size_t)st.H * st.W;
+    const int ld = (st.kind == Step::HEAD || st.kind == Step::UPSAMPLE) ? st.C : st.ld;
+    return download_tensor(s, reinterpret_cast<const char *>(st.src) + im * npix * ld * (b / 8), b, lp_kind, npix, st.C, ld, h->tap.in);
+}
+
+// ... and what it stored
+int tap_output(mi_unet *h, const Step &st, const Launch &l, uint8_t *d_labels, float *d_logits, int lp_kind)
+{
+    hipStream_t s = h->stream;
+    mi_unet_layer_info *ti = h->tap.info;
+    snprintf(ti->kernel, sizeof ti->kernel, "%s", route_name(l.rc.route, l.rc.fused).c_str());
+    const size_t im = (size_t)h->tap.img;
+    const int abits = lp_kind ? 16 : 32;
+    const ConvArgs &ta = l.a;
+    if (st.kind == Step::HEAD || (l.rc.fused & FUSE_HEAD)) {
+        const size_t hw = (size_t)h->cfg.height * h->cfg.width;
+        const int classes = h->cfg.classes;
+        ti->fused_head = st.kind == Step::CONV;
+        ti->out_bits = 32;
+        if (d_logits)
+            if (int rc = download_tensor(s, d_logits + im * classes * hw, 32, 0, classes * hw, 1, 1, h->tap.out)) return rc;
+        if (h->tap.labels) {
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpy(h->tap.labels, d_labels + im * hw, hw, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+    if (st.kind == Step::FIRST) {
+        ti->out_bits = abits;
+        const size_t npix = (size_t)st.H * st.W;
+        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.ld * (abits / 8), abits, lp_kind, npix, st.Cout, st.ld, h->tap.out);
+    }
+    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
+        const int ob = (lp_kind && ta.out_lp) ? 16 : 32;
+        ti->out_bits = ob;
+        const size_t npix = (size_t)ta.H * ta.W * (st.kind == Step::CONVT ? 4 : 1);
+        if (int rc = download_tensor(s, reinterpret_cast<const char *>(ta.out) + (im * npix * ta.ldo + ta.co_off) * (ob / 8), ob, lp_kind, npix, ta.Cout,
+                                     ta.ldo, h->tap.out))
+            return rc;
+        if (st.kind == Step::CONV && ta.pool_out) {
+            ti->pooled = 1;
+            return download_tensor(s, reinterpret_cast<const char *>(ta.pool_out) + im * (npix / 4) * ta.pool_ld * (ob / 8), ob, lp_kind, npix / 4,
+                                   ta.Cout, ta.pool_ld, h->tap.pooled);
+        }
+        return 0;
+    }
+    ti->out_bits = abits;
+    if (st.kind == Step::UPSAMPLE) {                             // the slice it wrote: channels [co_off, co_off + C) of the concat buffer
+        const size_t npix = (size_t)(2 * st.H) * (2 * st.W);
+        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + (im * npix * st.ld + st.co_off) * (abits / 8), abits, lp_kind, npix, st.C,
+                               st.ld, h->tap.out);
+    }
+    const size_t npix = (size_t)(st.H / 2) * (st.W / 2);         // POOL
+    return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.C * (abits / 8), abits, lp_kind, npix, st.C, st.C, h->tap.out);
+}
+
+}  // namespace miunet
+
+namespace {
+
+// mi_unet_layer_debug's ops: each runs one route -- or, for "conv3x3_wino4", the F(4x4,3x3) family as route_wino4 picks it --
+// on weights packed for it.  lp: the operands are 0 fp32, 1 bf16, 2 fp16.
+struct DebugOp { const char *op; Route route; Pack pack; int lp; bool routed; };
+const DebugOp kDebugOps[] = {
+    { "conv3x3", Route::CONV_MFMA, Pack::MFMA, 0, false },         { "convT2x2", Route::CONVT_MFMA, Pack::MFMA_T, 0, false },
+    { "convT2x2_taps", Route::CONVT_TAPS, Pack::TAPS, 0, false },   { "conv3x3_wino", Route::CONV_WINO, Pack::WINO, 0, false },
+    { "conv3x3_wino16", Route::CONV_WINO16, Pack::WINO16, 0, false }, { "conv3x3_wino4", Route::CONV_WINO4, Pack::WINO4, 0, true },
+    { "conv3x3_wino4s", Route::CONV_WINO4S, Pack::WINO4, 0, false }, { "conv3x3_wino4a", Route::CONV_WINO4A, Pack::WINO4, 0, false },
+    { "conv3x3_wino4b", Route::CONV_WINO4B, Pack::WINO4, 0, false },
+    { "conv3x3_bf16", Route::CONV_BF16, Pack::LP, 1, false },       { "conv3x3_fp16", Route::CONV_FP16, Pack::LP, 2, false },
+    { "conv3x3_bf16w", Route::CONV_BF16W, Pack::LP, 1, false },     { "conv3x3_fp16w", Route::CONV_FP16W, Pack::LP, 2, false },
+    { "conv3x3_bf16r", Route::CONV_BF16R, Pack::LP, 1, false },     { "conv3x3_fp16r", Route::CONV_FP16R, Pack::LP, 2, false },
+    { "conv3x3_bf16k", Route::CONV_BF16K, Pack::LP, 1, false },     { "conv3x3_fp16k", Route::CONV_FP16K, Pack::LP, 2, false },
+    { "convT2x2_bf16", Route::CONVT_BF16, Pack::LP_T, 1, false },   { "convT2x2_fp16", Route::CONVT_FP16, Pack::LP_T, 2, false },
+    { "convT2x2_bf16r", Route::CONVT_BF16R, Pack::LP_T, 1, false }, { "convT2x2_fp16r", Route::CONVT_FP16R, Pack::LP_T, 2, false },
+    { "conv3x3_first", Route::FIRST, Pack::FIRST, 0, false },        { "conv3x3_first_bf16", Route::FIRST, Pack::FIRST, 1, false },
+    { "conv3x3_first_fp16", Route::FIRST, Pack::FIRST, 2, false },   { "maxpool", Route::POOL, Pack::NONE, 0, false },
+    { "upsample2x", Route::UPSAMPLE, Pack::UP, 0, false },           { "upsample2x_bf16", Route::UPSAMPLE, Pack::UP, 1, false },
+    { "upsample2x_fp16", Route::UPSAMPLE, Pack::UP, 2, false },
+};
+
+}  // namespace
+
+extern "C" {
+
+int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
+                        const float *scale, const float *shift, int Cout, int relu, float *out)
+{
+    if (!op || !in || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(MI_UNET_EARG, "layer_debug: bad argument");
+    if (mi_unet_device_count() <= 0) return fail(MI_UNET_ENODEVICE, "no HIP device visible: libmiunet has no CPU fallback");
+    HIP_TRY(hipSetDevice(device));
+    // ---- resolve the op: "<op>[_pool][_lpout]"; _pool returns the fused 2x2 max-pooled tensor [B][H/2][W/2][Cout] instead
+    std::string o(op);
+    auto strip = [&](const char *suffix) {
+        const size_t n = strlen(suffix);
+        if (o.size() <= n || o.compare(o.size() - n, n, suffix) != 0) return false;
+        o.resize(o.size() - n);
+        return true;
+    };
+    const bool lp_out = strip("_lpout"), want_pool = strip("_pool");
+    const DebugOp *dop = nullptr;
+    for (const DebugOp &k : kDebugOps)
+        if (o == k.op) dop = &k;
+    if (!dop) return fail(MI_UNET_EARG, "layer_debug: unknown op " + o);
+    const Pack pk = dop->pack;
+    const int kind = dop->lp;                                  // operands: 0 fp32, 1 bf16, 2 fp16
+    const bool up = pk == Pack::UP, first = pk == Pack::FIRST, pool = pk == Pack::NONE;
+    const bool T = pk == Pack::MFMA_T || pk == Pack::TAPS || pk == Pack::LP_T;
+    if (up) {
+        if (Cin % 16 || want_pool || lp_out) return fail(MI_UNET_EARG, "layer_debug: upsample2x needs Cin % 16 == 0");
+    } else if (first) {
+        if (!w || Cout <= 0 || Cout % 4 || (Cin != 1 && Cin != 3) || want_pool || lp_out)
+            return fail(MI_UNET_EARG, "layer_debug: conv3x3_first needs weights, Cin 1 or 3, Cout % 4 == 0");
+    } else if (pool) {
+        if (Cin % 4 || H % 2 || W % 2) return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 and even H, W");
+    } else if (kind) {
+        if (!w || Cout <= 0 || Cin % 8) return fail(MI_UNET_EARG, "layer_debug: 16-bit conv needs weights and Cin % 8 == 0");
+    } else if (!w || Cout <= 0 || Cin % 4) {
+        return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
+    }
+    if (lp_out && !kind) return fail(MI_UNET_EARG, "layer_debug: _lpout is for the 16-bit conv ops");
+    if (want_pool && (pool || T || (H & 1) || (W & 1))) return fail(MI_UNET_EARG, "layer_debug: _pool is for the conv3x3 ops on even sizes");
+    const size_t in_n = (size_t)B * H * W * Cin;
+    size_t out_n = up ? in_n * 4 : pool ? in_n / 4 : (size_t)B * (T ? 4 : 1) * H * W * Cout;
+    // the first layer reads the u8 image (`in` holds byte values 0..255), the 16-bit kernels 16-bit activations (rounded here, RNE);
+    // the 16-bit upsample and first layer and the _lpout ops store 16 bits, which come back converted to float
+    const size_t in_es = first ? 1 : (kind && !pool) ? 2 : 4;
+    const bool out16 = kind && (up || first || lp_out);
+    const Routing rt = Routing::from_env();
+
+    // ---- pack (weights.cpp)
+    std::vector<unsigned char> in_raw(in_es == 4 ? 0 : in_n * in_es);
+    for (size_t i = 0; i < in_raw.size() / in_es; ++i) {
+        if (first) in_raw[i] = (uint8_t)in[i];
+        else reinterpret_cast<uint16_t *>(in_raw.data())[i] = kind == 2 ? fp16_bits(in[i]) : bf16_bits(in[i]);
+    }
+    std::vector<float> wpk, bias;
+    if (!up && !pool) {
+        std::vector<double> sc(Cout, 1.0);
+        bias.assign(Cout, 0.f);
+        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
+        wpk.assign(packed_floats(pk, Cin, Cout), 0.f);
+        pack_weights(pk, kind == 2, w, sc.data(), Cin, Cout, wpk.data());
+    }
+    float lut[256];
+    first_layer_lut(lut);
+
+    // ---- upload; the outputs poisoned with NaN bytes, so that unwritten elements are visible
+    DeviceBuf<unsigned char> d_in;
+    DeviceBuf<float> d_out, d_pool, d_w, d_b, d_lut;
+    HIP_TRY(d_in.reset(first ? in_n : sizeof(float) * in_n));
+    HIP_TRY(d_out.reset(out_n));
+    HIP_TRY(hipMemcpy(d_in, in_es == 4 ? static_cast<const void *>(in) : in_raw.data(), in_n * in_es, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out, 0xFF, sizeof(float) * out_n));
+    if (want_pool) {
+        HIP_TRY(d_pool.reset(out_n / 4));
+        HIP_TRY(hipMemset(d_pool, 0xFF, sizeof(float) * (out_n / 4)));
+    }
+    if (!wpk.empty()) {
+        HIP_TRY(d_w.reset(wpk.size()));
+        HIP_TRY(d_b.reset(bias.size()));
+        HIP_TRY(hipMemcpy(d_w, wpk.data(), sizeof(float) * wpk.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_b, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
+    }
+    if (first) {
+        HIP_TRY(d_lut.reset(256));
+        HIP_TRY(hipMemcpy(d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
+    }
+
+    // ---- launch, synchronise
+    const float *d_inf = reinterpret_cast<const float *>(d_in.get());
+    if (up) {
+        HIP_TRY(launch_upsample2x_bilinear(d_in, Cin, d_out, Cin, 0, B, H, W, Cin, kind, rt, nullptr));
+    } else if (first) {
+        HIP_TRY(launch_conv3x3_first(d_in, d_lut, d_w, d_b, d_out, B, H, W, Cin, Cout, Cout, kind, rt, nullptr));
+    } else if (pool) {
+        HIP_TRY(launch_maxpool2x2(d_inf, Cin, d_out, B, H, W, Cin, nullptr));
+    } else {
+        ConvArgs a{};
+        a.rt = rt;
+        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)packed_npad(pk, Cout); a.ldo = Cout; a.co_off = 0;
+        a.relu = relu;
+        a.out_lp = lp_out ? 1 : 0;
+        if (want_pool) { a.pool_out = d_pool; a.pool_ld = Cout; }
+        a.in = d_inf; a.wpk = d_w; a.bias = d_b; a.out = d_out;
+        if (pk == Pack::WINO4 || pk == Pack::TAPS) a.wpk4 = d_w;
+        HIP_TRY(launch_route(dop->routed ? route_wino4(a) : dop->route, a, nullptr));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+
+    // ---- download and convert
+    const float *d_res = want_pool ? d_pool.get() : d_out.get();
+    if (want_pool) out_n /= 4;
+    if (!out16) {
+        HIP_TRY(hipMemcpy(out, d_res, sizeof(float) * out_n, hipMemcpyDeviceToHost));
+        return MI_UNET_OK;
+    }
+    std::vector<uint16_t> out16v(out_n);
+    HIP_TRY(hipMemcpy(out16v.data(), d_res, sizeof(uint16_t) * out_n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < out_n; ++i) out[i] = kind == 2 ? fp16_to_float(out16v[i]) : bf16_to_float(out16v[i]);
+    return MI_UNET_OK;
+}
+
+int mi_unet_debug_layer_count(const mi_unet_t *h) { return h ? (int)h->plan.size() : 0; }
+
+int mi_unet_debug_layer_info(const mi_unet_t *h, int layer, mi_unet_layer_info *info)
+{
+    if (!h || !info) return fail(MI_UNET_EARG, "mi_unet_debug_layer_info: null argument");
+    if (!h->weights_loaded) return fail(MI_UNET_ESTATE, "Engine not initialized: load weights before inference");
+    if (layer < 0 || layer >= (int)h->plan.size()) return fail(MI_UNET_EARG, "mi_unet_debug_layer_info: no such layer");
+    const Step &st = h->plan[layer];
+    *info = mi_unet_layer_info{};
+    snprintf(info->name, sizeof info->name, "%s", st.name.c_str());
+    switch (st.kind) {
+    case Step::FIRST: info->kind = 0; info->in_h = info->out_h = st.H; info->in_w = info->out_w = st.W; info->in_c = st.C; info->out_c = st.Cout; break;
+    case Step::CONV: info->kind = 1; info->in_h = info->out_h = st.a.H; info->in_w = info->out_w = st.a.W; info->in_c = st.a.Cin; info->out_c = st.a.Cout; break;
+    case Step::CONVT: info->kind = 2; info->in_h = st.a.H; info->in_w = st.a.W; info->out_h = 2 * st.a.H; info->out_w = 2 * st.a.W; info->in_c = st.a.Cin; info->out_c = st.a.Cout; break;
+    case Step::POOL: info->kind = 3; info->in_h = st.H; info->in_w = st.W; info->out_h = st.H / 2; info->out_w = st.W / 2; info->in_c = info->out_c = st.C; break;
+    case Step::HEAD: info->kind = 4; info->in_h = info->out_h = st.H; info->in_w = info->out_w = st.W; info->in_c = st.C; info->out_c = st.Cout; break;
+    case Step::UPSAMPLE: info->kind = 5; info->in_h = st.H; info->in_w = st.W; info->out_h = 2 * st.H; info->out_w = 2 * st.W; info->in_c = info->out_c = st.C; break;
+    }
+    return MI_UNET_OK;
+}
+
+int mi_unet_debug_capture(mi_unet_t *h, const uint8_t *imgs, int B, int layer, int img, float *in, float *out, float *pooled,
+                          uint8_t *labels, mi_unet_layer_info *info)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (!imgs || !info || B < 1 || B > h->cfg.max_batch || img < 0 || img >= B)
+        return fail(MI_UNET_EARG, "mi_unet_debug_capture: bad argument (1 <= B <= max_batch, 0 <= img < B)");
+    if (int rc = mi_unet_debug_layer_info(h, layer, info)) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t in_bytes = (size_t)B * h->cfg.height * h->cfg.width * h->cfg.in_ch;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->d_img, imgs, in_bytes, hipMemcpyHostToDevice));
+    h->tap = mi_unet::Tap{};
+    h->tap.layer = layer; h->tap.img = img; h->tap.in = in; h->tap.out = out; h->tap.pooled = pooled; h->tap.labels = labels; h->tap.info = info;
+    const int rc = launch_plan(h, h->d_img, B, h->d_labels, h->d_logits);       // eager: the kernels a batch of B takes
+    const bool hit = h->tap.hit;
+    h->tap = mi_unet::Tap{};
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(MI_UNET_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    if (!hit) return fail(MI_UNET_ESTATE, "mi_unet_debug_capture: the plan never reached the layer");
+    return MI_UNET_OK;
+}
+
+}  // extern "C"

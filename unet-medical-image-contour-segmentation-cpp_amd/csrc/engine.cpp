@@ -1,651 +1,36 @@
-// engine.cpp -- the C-ABI of include/mi_unet.h: handle, weight loading (BN fold + MFMA repack), device buffers,
-// the forward plan and its launches.  Host code only; every device kernel lives in the .hip files next to it.
+// engine.cpp -- the C-ABI of include/mi_unet.h: the handle (create / clone / destroy), weight adoption, the numeric guard, the
+// launches of the forward plan and their graph replay, the u8, postprocess and contour entry points.  The RAW-in and tiled entry
+// points are pipeline_raw.cpp and pipeline_tiled.cpp, the debug entry points debug.cpp; weights.cpp packs, plan.cpp plans.
+// Host code only; every device kernel lives in the .hip files next to it.
 //
 // Replaces, for the reference's hot path, initialize_engine's engine deserialisation (src/initialize.cpp:49-60),
 // initialize_context's buffers/stream (src/process.cpp:45-120) and execute_inference (src/process.cpp:123-175).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mi_unet.h"
-#include "copy_pool.h"
-#include "engine_internal.h"
-#include "kernels.h"
-#include "routing.h"
-#include "tile_grid.h"
+#include "engine_handle.h"
 
 using namespace miunet;
 
-namespace {
+namespace miunet {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg)
+PlanInput plan_input(const mi_unet *h)
 {
-    g_err = msg;
-    return code;
+    PlanInput in;
+    in.cfg = h->cfg; in.algo = h->algo; in.fuse_pool = h->fuse_pool; in.fuse_head = h->fuse_head;
+    in.weights = h->d_weights;
+    for (int i = 0; i < 8; ++i) { in.cat[i] = h->d_cat[i]; in.cat_floats[i] = h->cat_floats[i]; }
+    in.s0 = h->d_s0; in.s1 = h->d_s1; in.s_floats = h->s_floats;
+    in.routing = h->routing; in.guard_tripped = h->wino4_guard_tripped; in.wino4_min_wg = h->wino4_min_wg;
+    in.lut = h->d_lut; in.ksplit = h->d_ksplit; in.ksplit_bytes = h->ksplit_bytes;
+    return in;
 }
-
-#define HIP_TRY(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e__ = (expr);                                                                               \
-        if (e__ != hipSuccess)                                                                                 \
-            return fail(MI_UNET_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));                    \
-    } while (0)
-
-struct Step {
-    enum Kind { FIRST, CONV, CONVT, POOL, HEAD, UPSAMPLE } kind;
-    std::string name;
-    ConvArgs a{};                 // CONV / CONVT
-    // FIRST / POOL / HEAD / UPSAMPLE operands (UPSAMPLE: src [H][W][C] -> channels [co_off, co_off + C) of dst [2H][2W][ld])
-    const float *src = nullptr;
-    float *dst = nullptr;
-    const float *w = nullptr, *shift = nullptr;
-    int H = 0, W = 0, C = 0, Cout = 0, ld = 0, co_off = 0;
-    double flops_per_img = 0, bytes_per_img = 0, weight_bytes = 0;
-    bool fused_away = false;      // POOL steps whose work is done by the preceding conv's epilogue
-    int head_step = -1;           // CONV: index of the HEAD step this layer feeds (candidate for the fused head), else -1
-    bool feeds_head = false;      // CONV: its output is the fp32 head's input (stays fp32 in the 16-bit pipelines)
-};
-
-}  // namespace
-
-struct mi_unet {
-    mi_unet_config cfg{};
-    int ch[8]{};
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    bool weights_loaded = false;
-    int algo = MI_UNET_CONV_DIRECT; // resolved conv3x3 algorithm (MI_UNET_CONV_DIRECT / _WINOGRAD / _WINOGRAD16)
-    bool fuse_pool = true;          // MIUNET_FUSE_POOL=0 keeps the stand-alone pooling kernel (A/B and parity checks)
-    int wino4_min_wg = 256;         // MIUNET_WINO4_MIN_WG: smallest grid the F(4x4,3x3) kernel takes (else F(2x2) + split-K)
-    Routing routing;                // kernel-routing switches + CU count, resolved at create (kernels.h)
-    // numeric guard of the default fp32 plan (engine_calibrate): F(4x4,3x3) is kept only if, for THIS weight set, a probe tile's
-    // logits agree with the F(2x2,3x3) plan's within `guard_limit`; otherwise every layer runs F(2x2,3x3)
-    bool wino4_guard_tripped = false;
-    float guard_diff = -1.f, guard_limit = 5e-4f;
-    std::string guard_text = "numeric guard: not run (no weights, or not the default fp32 plan)";
-    // device memory
-    // one blob: every packed tensor (single allocation -> one broadcast / one free).  Owned by `weights`, which clones of
-    // this handle share (mi_unet_clone: the reference's engine is shared by its per-thread contexts, src/process.cpp:15, :69)
-    std::shared_ptr<DeviceWeights> weights;
-    float *d_weights = nullptr;     // = weights->d
-    size_t weight_floats = 0;
-    float *d_lut = nullptr;         // 256 floats: i / 255.0f
-    float *d_cat[8]{};              // concat buffers [Bm][h_i][w_i][2*ch_i]
-    float *d_s0 = nullptr, *d_s1 = nullptr;
-    size_t cat_floats[8]{}, s_floats = 0;   // their sizes (build_plan checks every step's tensors against them)
-    uint8_t *d_img = nullptr;       // staging for the host-buffer entry point
-    uint8_t *d_labels = nullptr;
-    float *d_logits = nullptr;
-    // RAW16 staging for mi_unet_infer_raw16: a ring of (pinned host, device) buffer pairs, grown on demand, so the host copy
-    // of image i+1 into its pinned buffer overlaps the PCIe transfer and the preprocessing kernels of image i
-    static constexpr int RAW_RING = 3;
-    uint16_t *d_raw[RAW_RING] = {};
-    uint16_t *h_raw[RAW_RING] = {}; // pinned
-    hipEvent_t raw_done[RAW_RING] = {};   // the slot's transfer and kernels have completed
-    bool raw_busy[RAW_RING] = {};
-    size_t raw_cap = 0;             // samples per slot
-    unsigned *d_mnmx = nullptr;     // [max_batch][2]
-    float *d_ksplit = nullptr;      // split-K slabs of the Winograd kernel (small batches / deep levels only)
-    size_t ksplit_bytes = 0;
-    int *d_cont = nullptr;          // contour outputs of mi_unet_extract_contours (grown on demand)
-    int *h_cont = nullptr;          // pinned mirror: one async D2H, then only the points that exist are copied to the caller
-    size_t cont_cap = 0;            // ints
-    // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
-    // network of micro-batch k runs (d_img / d_img2 alternate)
-    hipStream_t pre_stream = nullptr;
-    uint8_t *d_img2 = nullptr;
-    hipEvent_t tile_ready[2] = {};
-    // stage timing of the last RAW-in call (mi_unet_last_stage_ms): event pairs per micro-batch, summed
-    hipEvent_t stage_ev[2][5] = {}, out_done[2] = {};
-    hipEvent_t pre_ev[3][2] = {};   // three pairs: micro-batch k + 2 is staged before k's times are read
-    uint8_t *h_labels2 = nullptr;
-    // third stream of the RAW-in entry points: postprocess, mask_to_image, contours and the downloads of micro-batch k run
-    // here while the engine's stream already works on the network of k + 1; own workspace (the network's scratch buffers,
-    // which the single-stage entry points borrow, are in use by then), second label buffer
-    hipStream_t tail_stream = nullptr;
-    hipStream_t dl_stream = nullptr;          // tile downloads: behind the network of k, beside its tail and the upload of k + 1
-    hipEvent_t tiles_done[2] = {};
-    void *d_tail_ws = nullptr;
-    size_t tail_ws_bytes = 0;
-    uint8_t *d_tail_vis = nullptr, *d_labels2 = nullptr;
-    hipEvent_t net_done[2] = {}, tail_ev[2][4] = {};
-    std::unique_ptr<CopyPool> copy_pool;   // helpers of the pageable -> pinned staging copy (created on first use)
-    uint8_t *h_tiles[2] = {};       // pinned mirrors of the tile buffers (a D2H into the caller's pageable memory would block the host)   // second pinned result buffer: micro-batch k + 1 downloads while the host still copies k out
-    float stage_ms[MI_UNET_N_STAGES] = {};
-    // tiled entry points (mi_unet_infer_tiled_*): the full-size image, its label map / visualisation, logits and u16 planes stay
-    // on the device for the whole call.  Grown on demand (ensure_tiled_buffers), owned by this handle, never shared with a clone.
-    struct Tiled {
-        uint8_t *d_img = nullptr, *d_labels = nullptr, *d_vis = nullptr;     // u8 [H][W][in_ch] (+ slack to a dword), [H][W], [H][W]
-        uint8_t *h_img = nullptr, *h_out = nullptr;                          // pinned mirrors of d_img and of d_labels / d_vis
-        size_t px_cap = 0;                                                   // pixels the five above hold
-        float *d_logits = nullptr;
-        size_t logit_cap = 0;                                                // pixels
-        uint16_t *d_raw = nullptr, *h_raw = nullptr;                         // in_ch planes of u16 [H][W], device and pinned
-        size_t raw_cap = 0;                                                  // pixels per plane
-        std::vector<hipEvent_t> ev;                                          // stage boundaries of the last call
-        float *d_acc = nullptr;                                              // blending: fp32 accumulator [classes][H][W]
-        size_t acc_cap = 0;                                                  // pixels
-    } tiled;
-    // mi_unet_set_tile_blend: how the tiled entry points combine overlapping tiles; d_blend_w = the weight tables of the tile height
-    // and width (height + width floats), uploaded when the setting changes
-    mi_unet_tile_blend blend{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
-    float *d_blend_w = nullptr;
-    // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
-    uint8_t *h_img = nullptr;
-    uint8_t *h_labels = nullptr;
-    std::vector<Step> plan;
-    // hipGraph replay of the forward pass (the reference replays a captured CUDA graph per image, src/process.cpp:99-105,
-    // :147): one captured graph per (stream, buffers, batch) key; the first call of a key runs eagerly.
-    struct GraphEntry {
-        hipStream_t stream; const uint8_t *imgs; uint8_t *labels; float *logits; int B;
-        int uses; hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs;
-    bool use_graph = true;          // MIUNET_GRAPH=0 disables
-    bool postprocess = false;       // mi_unet_set_postprocess: label maps -> postprocess_mask output before they leave the device
-    // profiling: one event pair per launch, recorded on the launch stream and only read back (synchronised) in
-    // mi_unet_get_kernel_stats, so the launches themselves never wait on the host
-    bool profiling = false;
-    std::vector<mi_unet_kernel_stat> stats;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    hipEvent_t tev0 = nullptr, tev1 = nullptr;
-    // mi_unet_debug_capture: stop launch_plan after step `layer` and hand its operands of image `img` to the host
-    struct Tap {
-        int layer = -1, img = 0;
-        float *in = nullptr, *out = nullptr, *pooled = nullptr;
-        uint8_t *labels = nullptr;
-        mi_unet_layer_info *info = nullptr;
-        bool hit = false;
-    } tap;
-};
-
-namespace {
-
-size_t round_up(size_t v, size_t g) { return (v + g - 1) / g * g; }
-
-// U = G g G^T for F(2x2,3x3); g is one 3x3 filter (row-major), out is 4x4 (row-major, position p = 4*xi + nu)
-void wino_filter_transform(const double g[9], double out[16])
-{
-    static const double G[4][3] = { { 1, 0, 0 }, { 0.5, 0.5, 0.5 }, { 0.5, -0.5, 0.5 }, { 0, 0, 1 } };
-    double t[4][3];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 3; ++j) t[i][j] = G[i][0] * g[0 * 3 + j] + G[i][1] * g[1 * 3 + j] + G[i][2] * g[2 * 3 + j];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) out[i * 4 + j] = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];
-}
-
-// pack one conv3x3 (PyTorch [Cout][Cin][3][3], per-channel scale) into the Winograd layout [Cin/8][16][CoutPad][8]
-void pack_wino(const float *w, const double *scale, int cin, int cout, float *dst, size_t cpad)
-{
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            double g[9], u[16];
-            for (int t = 0; t < 9; ++t) g[t] = (double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0);
-            wino_filter_transform(g, u);
-            for (int p = 0; p < 16; ++p)
-                dst[(((size_t)(ci / WINO_KC) * 16 + p) * cpad + co) * WINO_KC + ci % WINO_KC] = (float)u[p];
-        }
-}
-
-// U = G g G^T for F(4x4,3x3) (6x6, position p = 6*xi + nu), packed for conv3x3_wino4_f32 as [Cin/16][36][CoutPad][16]
-void pack_wino4(const float *w, const double *scale, int cin, int cout, float *dst, size_t cpad)
-{
-    static const double G[6][3] = { { 1.0 / 4, 0, 0 },          { -1.0 / 6, -1.0 / 6, -1.0 / 6 }, { -1.0 / 6, 1.0 / 6, -1.0 / 6 },
-                                    { 1.0 / 24, 1.0 / 12, 1.0 / 6 }, { 1.0 / 24, -1.0 / 12, 1.0 / 6 }, { 0, 0, 1 } };
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            double g[9], t[6][3];
-            for (int k = 0; k < 9; ++k) g[k] = (double)w[((size_t)co * cin + ci) * 9 + k] * (scale ? scale[co] : 1.0);
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 3; ++j) t[i][j] = G[i][0] * g[0 * 3 + j] + G[i][1] * g[1 * 3 + j] + G[i][2] * g[2 * 3 + j];
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 6; ++j)
-                    dst[(((size_t)(ci / WINO4_KC) * 36 + i * 6 + j) * cpad + co) * WINO4_KC + ci % WINO4_KC] =
-                        (float)(t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2]);
-        }
-}
-
-// convT [Cin][Cout][2][2] packed per tap for convT2x2_taps_f32: [ceil(Cin/32)*4][4 taps][cpad][8], zeros elsewhere
-size_t convT_taps_floats(int cin, int cout) { return (size_t)((cin + 31) / 32) * 4 * 4 * convT_taps_cpad(cout) * 8; }
-void pack_convT_taps(const float *w, int cin, int cout, float *dst)
-{
-    const size_t cpad = (size_t)convT_taps_cpad(cout);
-    for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-            for (int tap = 0; tap < 4; ++tap)
-                dst[(((size_t)(ci / 8) * 4 + tap) * cpad + co) * 8 + ci % 8] = w[((size_t)ci * cout + co) * 4 + tap];
-}
-
-// same U, packed for conv3x3_wino16_f32: [Cin/8][8 position pairs][CoutPad][16], element 4*(k/2) + 2*(pos&1) + (k&1)
-void pack_wino16(const float *w, const double *scale, int cin, int cout, float *dst, size_t cpad)
-{
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            double g[9], u[16];
-            for (int t = 0; t < 9; ++t) g[t] = (double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0);
-            wino_filter_transform(g, u);
-            const int k = ci % WINO_KC;
-            for (int p = 0; p < 16; ++p)
-                dst[(((size_t)(ci / WINO_KC) * 8 + p / 2) * cpad + co) * 16 + (k >> 1) * 4 + (p & 1) * 2 + (k & 1)] = (float)u[p];
-        }
-}
-
-// float -> bfloat16 bits, round-to-nearest-even (what the device's v_cvt_pk_bf16_f32 does to the activations)
-uint16_t bf16_bits(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);   // quiet NaN
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// float -> IEEE binary16 bits, round-to-nearest-even (v_cvt_f16_f32 semantics incl. subnormals and overflow to inf)
-uint16_t fp16_bits(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t e = (int32_t)((u >> 23) & 0xFF) - 127;
-    uint32_t m = u & 0x7FFFFFu;
-    if (e == 128) return (uint16_t)(sign | 0x7C00u | (m ? 0x200u : 0));                 // inf / NaN
-    if (e > 15) return (uint16_t)(sign | 0x7C00u);                                       // overflow
-    if (e >= -14) {                                                                      // normal
-        uint32_t h = ((uint32_t)(e + 15) << 10) | (m >> 13);
-        const uint32_t rem = m & 0x1FFFu;
-        if (rem > 0x1000u || (rem == 0x1000u && (h & 1))) ++h;                           // carries into the exponent correctly
-        return (uint16_t)(sign | h);
-    }
-    if (e < -25) return (uint16_t)sign;                                                  // underflow to zero
-    m |= 0x800000u;                                                                      // subnormal: shift the 24-bit significand
-    const int shift = -14 - e + 13;
-    uint32_t h = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (h & 1))) ++h;
-    return (uint16_t)(sign | h);
-}
-
-typedef uint16_t (*lp_cvt_fn)(float);
-
-float bf16_to_float(uint16_t b)
-{
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-float fp16_to_float(uint16_t h)
-{
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
-    uint32_t u;
-    if (exp == 0) {
-        if (man == 0) u = sign;
-        else {                                              // subnormal: renormalise
-            int e = -1;
-            uint32_t m = man;
-            do { ++e; m <<= 1; } while (!(m & 0x400u));
-            u = sign | ((uint32_t)(127 - 15 - e) << 23) | ((m & 0x3FFu) << 13);
-        }
-    } else if (exp == 31) u = sign | 0x7F800000u | (man << 13);
-    else u = sign | ((exp + 127 - 15) << 23) | (man << 13);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// conv3x3 (PyTorch [Cout][Cin][3][3], per-channel scale) -> 16-bit [Cin/32][9][CoutPad][32]; dst counts uint16 elements
-void pack_conv_bf16(const float *w, const double *scale, int cin, int cout, uint16_t *dst, size_t cpad, lp_cvt_fn cvt = nullptr)
-{
-    if (!cvt) cvt = bf16_bits;
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < 9; ++t)
-                dst[(((size_t)(ci / KC_BF16) * 9 + t) * cpad + co) * KC_BF16 + ci % KC_BF16] =
-                    cvt((float)((double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0)));
-}
-
-// conv3x3 (PyTorch [Cout][Cin][3][3], per-channel scale) -> MFMA layout [Cin/16][9][CoutPad][16]
-void pack_conv_mfma(const float *w, const double *scale, int cin, int cout, float *dst, size_t cpad)
-{
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < 9; ++t)
-                dst[(((size_t)(ci / KC) * 9 + t) * cpad + co) * KC + ci % KC] = (float)((double)w[((size_t)co * cin + ci) * 9 + t] * (scale ? scale[co] : 1.0));
-}
-
-// convT (PyTorch [Cin][Cout][2][2]) -> MFMA layout [Cin/16][1][NPad][16] with n = k * Cout + co
-void pack_convT_mfma(const float *w, int cin, int cout, float *dst, size_t npad)
-{
-    for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-            for (int k = 0; k < 4; ++k)
-                dst[((size_t)(ci / KC) * npad + (size_t)k * cout + co) * KC + ci % KC] = w[((size_t)ci * cout + co) * 4 + k];
-}
-
-// convT (PyTorch [Cin][Cout][2][2]) -> bf16 [Cin/32][1][NPad][32] with n = k * Cout + co
-void pack_convT_bf16(const float *w, int cin, int cout, uint16_t *dst, size_t npad, lp_cvt_fn cvt = nullptr)
-{
-    if (!cvt) cvt = bf16_bits;
-    for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-            for (int k = 0; k < 4; ++k)
-                dst[((size_t)(ci / KC_BF16) * npad + (size_t)k * cout + co) * KC_BF16 + ci % KC_BF16] =
-                    cvt(w[((size_t)ci * cout + co) * 4 + k]);
-}
-
-// parse "MIUNETW1" (miunet/spec.py): version 1, or version 2 with its up_mode; fold BN, repack
-int build_host_weights(const mi_unet_config &cfg, int algo, const void *blob, size_t len, HostWeights &hw)
-{
-    const unsigned char *p = static_cast<const unsigned char *>(blob);
-    if (len < 36 || memcmp(p, "MIUNETW1", 8) != 0) return fail(MI_UNET_EFILE, "weight blob: bad magic (want MIUNETW1)");
-    uint32_t h[5], n;
-    float eps;
-    memcpy(h, p + 8, 20);
-    memcpy(&eps, p + 28, 4);
-    memcpy(&n, p + 32, 4);
-    size_t payload_at = 36;
-    hw.up_mode = UP_TRANSPOSE;
-    if (h[0] == 2) {                             // version 2: u32 up_mode between the header and the payload
-        uint32_t mode;
-        if (len < 40) return fail(MI_UNET_EFILE, "weight blob: version 2 header truncated");
-        memcpy(&mode, p + 36, 4);
-        if (mode != UP_TRANSPOSE && mode != UP_BILINEAR)
-            return fail(MI_UNET_EFILE, "weight blob: unknown up_mode " + std::to_string(mode) + " (want 0 transposed 2x2 or 1 bilinear x2)");
-        hw.up_mode = (int)mode;
-        payload_at = 40;
-    } else if (h[0] != 1) {
-        return fail(MI_UNET_EFILE, "weight blob: unsupported version " + std::to_string(h[0]) + " (want 1 or 2)");
-    }
-    const bool bilinear = hw.up_mode == UP_BILINEAR;
-    if ((int)h[1] != cfg.in_ch || (int)h[2] != cfg.base || (int)h[3] != cfg.levels || (int)h[4] != cfg.classes)
-        return fail(MI_UNET_EFILE, "weight blob: topology (in_ch/base/levels/classes) does not match the engine config");
-    if (len < payload_at + (size_t)n * 4) return fail(MI_UNET_EFILE, "weight blob: truncated payload");
-    const float *cur = reinterpret_cast<const float *>(p + payload_at);
-    size_t left = n;
-    auto take = [&](size_t k) -> const float * {
-        if (left < k) return nullptr;
-        const float *r = cur;
-        cur += k; left -= k;
-        return r;
-    };
-    const int L = cfg.levels;
-    int ch[8];
-    for (int i = 0; i <= L; ++i) ch[i] = cfg.base << i;
-    auto &out = hw.blob;
-    auto alloc = [&](size_t k) { size_t o = out.size(); out.resize(o + round_up(k, 4), 0.f); return o; };
-
-    bool first_done = false;
-    auto add_conv = [&](int cin, int cout) -> int {
-        const float *w = take((size_t)cout * cin * 9);
-        const float *g = take(cout), *be = take(cout), *mu = take(cout), *va = take(cout);
-        if (!w || !g || !be || !mu || !va) return fail(MI_UNET_EFILE, "weight blob: payload shorter than the topology needs");
-        std::vector<double> sc(cout);
-        HostWeights::Off off{};
-        off.shift = alloc(cout);
-        for (int co = 0; co < cout; ++co) {
-            sc[co] = (double)g[co] / std::sqrt((double)va[co] + (double)eps);
-            out[off.shift + co] = (float)((double)be[co] - (double)mu[co] * sc[co]);
-        }
-        if (!first_done) {                       // FIRST layer layout: [tap][ci][co]
-            first_done = true;
-            off.w = alloc((size_t)9 * cin * cout);
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < 9; ++t)
-                        out[off.w + ((size_t)t * cin + ci) * cout + co] = (float)((double)w[((size_t)co * cin + ci) * 9 + t] * sc[co]);
-        } else if (algo == MI_UNET_CONV_BF16 || algo == MI_UNET_CONV_FP16) {   // 16-bit [chunk32][tap][n (padded)][32], BN scale folded before rounding
-            const int nch = (cin + KC_BF16 - 1) / KC_BF16;
-            const size_t cpad = round_up(cout, NPAD);
-            off.w = alloc(((size_t)nch * 9 * cpad * KC_BF16 + 1) / 2);
-            pack_conv_bf16(w, sc.data(), cin, cout, reinterpret_cast<uint16_t *>(&out[off.w]), cpad,
-                           algo == MI_UNET_CONV_FP16 ? fp16_bits : bf16_bits);
-        } else if (algo != MI_UNET_CONV_DIRECT) {  // Winograd layouts (same size): U = G g G^T
-            const int nch = (cin + WINO_KC - 1) / WINO_KC;
-            const size_t cpad = round_up(cout, NPAD);
-            off.w = alloc((size_t)nch * 16 * cpad * WINO_KC);
-            if (algo == MI_UNET_CONV_WINOGRAD16) pack_wino16(w, sc.data(), cin, cout, &out[off.w], cpad);
-            else pack_wino(w, sc.data(), cin, cout, &out[off.w], cpad);
-            if (algo == MI_UNET_CONV_WINOGRAD && cout % 64 == 0) {   // second packing: the F(4x4,3x3) kernel takes
-                const int nch4 = (cin + WINO4_KC - 1) / WINO4_KC;                      // the layer whenever its grid fills the chip
-                off.w4 = alloc((size_t)nch4 * 36 * cpad * WINO4_KC);
-                pack_wino4(w, sc.data(), cin, cout, &out[off.w4], cpad);
-            }
-        } else {                                 // MFMA layout: [chunk][tap][n (padded)][KC]
-            const int nch = (cin + KC - 1) / KC;
-            const size_t cpad = round_up(cout, NPAD);
-            off.w = alloc((size_t)nch * 9 * cpad * KC);
-            pack_conv_mfma(w, sc.data(), cin, cout, &out[off.w], cpad);
-        }
-        hw.conv.push_back(off);
-        return 0;
-    };
-    auto add_dconv = [&](int cin, int cout, int mid) -> int {
-        int rc = add_conv(cin, mid);
-        return rc ? rc : add_conv(mid, cout);
-    };
-    int rc = add_dconv(cfg.in_ch, ch[0], ch[0]);
-    for (int i = 1; i <= L && !rc; ++i) {
-        const int c = (bilinear && i == L) ? ch[L - 1] : ch[i];       // the bilinear net's bottleneck keeps ch[L-1] channels
-        rc = add_dconv(ch[i - 1], c, c);
-    }
-    for (int i = 1; i <= L && !rc && bilinear; ++i) {                  // up_i: 2 ch[lvl] -> ch[lvl] -> ch[lvl] / 2 (ch[0] last)
-        const int lvl = L - i, c = ch[lvl];
-        rc = add_dconv(2 * c, lvl > 0 ? c / 2 : c, c);
-    }
-    for (int i = 1; i <= L && !rc && !bilinear; ++i) {
-        const int cin = ch[L - i + 1], cout = cin / 2;
-        const float *w = take((size_t)cin * cout * 4), *b = take(cout);
-        if (!w || !b) return fail(MI_UNET_EFILE, "weight blob: payload shorter than the topology needs");
-        HostWeights::Off off{};
-        off.shift = alloc(cout);
-        for (int co = 0; co < cout; ++co) out[off.shift + co] = b[co];
-        const size_t npad = round_up((size_t)4 * cout, NPAD);
-        if (algo == MI_UNET_CONV_BF16 || algo == MI_UNET_CONV_FP16) {
-            const int nch = (cin + KC_BF16 - 1) / KC_BF16;
-            off.w = alloc(((size_t)nch * npad * KC_BF16 + 1) / 2);
-            pack_convT_bf16(w, cin, cout, reinterpret_cast<uint16_t *>(&out[off.w]), npad,
-                            algo == MI_UNET_CONV_FP16 ? fp16_bits : bf16_bits);
-        } else {
-            const int nch = (cin + KC - 1) / KC;
-            off.w = alloc((size_t)nch * npad * KC);
-            pack_convT_mfma(w, cin, cout, &out[off.w], npad);
-            if (cout % 64 == 0) {      // second packing: the per-tap GEMM kernel (convt_taps.hip)
-                off.w4 = alloc(convT_taps_floats(cin, cout));
-                pack_convT_taps(w, cin, cout, &out[off.w4]);
-            }
-        }
-        hw.convT.push_back(off);
-        rc = add_dconv(cin, cout, cout);
-    }
-    if (rc) return rc;
-    const float *ow = take((size_t)cfg.classes * ch[0]), *ob = take(cfg.classes);
-    if (!ow || !ob || left != 0) return fail(MI_UNET_EFILE, "weight blob: payload length does not match the topology");
-    hw.head.w = alloc((size_t)cfg.classes * ch[0]);
-    memcpy(&out[hw.head.w], ow, sizeof(float) * cfg.classes * ch[0]);
-    hw.head.shift = alloc(cfg.classes);
-    memcpy(&out[hw.head.shift], ob, sizeof(float) * cfg.classes);
-    return 0;
-}
-
-void conv_cost(Step &s, int H, int W, int cin, int cout, int taps_flops, bool convT)
-{
-    const double px = (double)H * W;
-    s.flops_per_img = 2.0 * px * cin * cout * taps_flops;
-    const double out_px = convT ? 4.0 * px : px;
-    s.bytes_per_img = 4.0 * (px * cin + out_px * cout);
-    s.weight_bytes = 4.0 * (double)cin * cout * taps_flops;
-}
-
-// Every tensor a step reads or writes must lie inside the buffer mi_unet_create allocated for it at max_batch.  The buffers are
-// sized for the transposed decoder and every tensor of the bilinear plan is at most its transposed counterpart, but the plan
-// comes from a weight file: one that does not fit is refused here, never launched.  (The split-K workspace needs no check: its
-// launchers shrink the split until the slabs fit a.ksplit_ws_bytes.)
-int check_plan_fits(const mi_unet *h)
-{
-    const size_t Bm = (size_t)h->cfg.max_batch;
-    auto cap = [&](const void *p) -> size_t {
-        if (p == nullptr) return 0;
-        if (p == h->d_s0 || p == h->d_s1) return h->s_floats;
-        for (int i = 0; i < 8; ++i)
-            if (p == h->d_cat[i]) return h->cat_floats[i];
-        return 0;
-    };
-    for (const Step &st : h->plan) {
-        struct Use { const void *p; size_t floats; } use[3] = {};
-        bool ok = true;
-        const size_t px = Bm * st.H * st.W, apx = Bm * st.a.H * st.a.W;
-        switch (st.kind) {
-        case Step::FIRST: use[0] = { st.dst, px * st.ld }; break;
-        case Step::CONV:
-            use[0] = { st.a.in, apx * st.a.ldc }; use[1] = { st.a.out, apx * st.a.ldo };
-            if (st.a.pool_out) use[2] = { st.a.pool_out, apx / 4 * st.a.pool_ld };
-            ok = st.a.Cin <= st.a.ldc && st.a.co_off + st.a.Cout <= st.a.ldo;
-            break;
-        case Step::CONVT:
-            use[0] = { st.a.in, apx * st.a.ldc }; use[1] = { st.a.out, 4 * apx * st.a.ldo };
-            ok = st.a.Cin <= st.a.ldc && st.a.co_off + st.a.Cout <= st.a.ldo;
-            break;
-        case Step::POOL: use[0] = { st.src, px * st.ld }; use[1] = { st.dst, px / 4 * st.C }; break;
-        case Step::UPSAMPLE:
-            use[0] = { st.src, px * st.C }; use[1] = { st.dst, 4 * px * st.ld };
-            ok = st.co_off + st.C <= st.ld;
-            break;
-        case Step::HEAD: use[0] = { st.src, px * st.C }; break;
-        }
-        for (const Use &u : use)
-            if (u.p && u.floats > cap(u.p)) ok = false;
-        if (!ok) return fail(MI_UNET_EFILE, "weight file: step " + st.name + " of its network does not fit the engine's buffers");
-    }
-    return 0;
-}
-
-// (re)build the launch plan for micro-batch capacity cfg.max_batch; pointers into d_weights need the offsets
-int build_plan(mi_unet *h, const HostWeights &hw)
-{
-    const mi_unet_config &c = h->cfg;
-    const int L = c.levels;
-    const int *ch = h->ch;
-    const bool bilinear = hw.up_mode == UP_BILINEAR;
-    h->plan.clear();
-    size_t ci = 0, ti = 0;
-    auto W_ = [&](size_t off) { return h->d_weights + off; };
-
-    auto conv_step = [&](const std::string &name, const float *in, int ldc, int cin, float *out, int ldo, int co_off, int cout,
-                         int H, int Wd) {
-        Step s;
-        s.kind = Step::CONV; s.name = name;
-        s.a.in = in; s.a.wpk = W_(hw.conv[ci].w); s.a.bias = W_(hw.conv[ci].shift); s.a.out = out;
-        s.a.wpk4 = hw.conv[ci].w4 ? W_(hw.conv[ci].w4) : nullptr;
-        s.a.B = 0; s.a.H = H; s.a.W = Wd; s.a.Cin = cin; s.a.ldc = ldc; s.a.Cout = cout;
-        s.a.CoutPad = (int)round_up(cout, NPAD); s.a.ldo = ldo; s.a.co_off = co_off; s.a.relu = 1;
-        conv_cost(s, H, Wd, cin, cout, 9, false);
-        ++ci;
-        h->plan.push_back(s);
-    };
-
-    int H = c.height, Wd = c.width;
-    {   // inc.c1 : u8 image -> s0
-        Step s;
-        s.kind = Step::FIRST; s.name = "inc.c1";
-        s.w = W_(hw.conv[ci].w); s.shift = W_(hw.conv[ci].shift); s.dst = h->d_s1;   // s0 receives inc.c2's pooled output
-        s.H = H; s.W = Wd; s.C = c.in_ch; s.Cout = ch[0]; s.ld = ch[0];
-        s.flops_per_img = 2.0 * H * Wd * 9.0 * c.in_ch * ch[0];
-        s.bytes_per_img = (double)H * Wd * (c.in_ch + 4.0 * ch[0]);
-        ++ci;
-        h->plan.push_back(s);
-    }
-    conv_step("inc.c2", h->d_s1, ch[0], ch[0], h->d_cat[0], 2 * ch[0], 0, ch[0], H, Wd);
-    for (int i = 1; i <= L; ++i) {
-        // 2x2 max pooling: fused into the epilogue of the conv that produced the skip tensor (it holds every pooling
-        // window inside one lane); the stand-alone kernel stays in the plan for configurations that cannot fuse
-        Step &prod = h->plan.back();
-        const bool fuse = h->fuse_pool && prod.kind == Step::CONV && H % 2 == 0 && Wd % 2 == 0;
-        if (fuse) {
-            prod.a.pool_out = h->d_s0;
-            prod.a.pool_ld = ch[i - 1];
-            prod.bytes_per_img += 4.0 * (H / 2) * (Wd / 2) * ch[i - 1];
-        }
-        Step p;
-        p.kind = Step::POOL; p.name = "down" + std::to_string(i) + ".pool";
-        p.src = h->d_cat[i - 1]; p.ld = 2 * ch[i - 1]; p.dst = h->d_s0; p.H = H; p.W = Wd; p.C = ch[i - 1];
-        p.bytes_per_img = 4.0 * H * Wd * ch[i - 1] * 1.25;
-        p.fused_away = fuse;
-        h->plan.push_back(p);
-        H /= 2; Wd /= 2;
-        const int co = (bilinear && i == L) ? ch[L - 1] : ch[i];      // the bilinear net's bottleneck keeps ch[L-1] channels
-        conv_step("down" + std::to_string(i) + ".c1", h->d_s0, ch[i - 1], ch[i - 1], h->d_s1, co, 0, co, H, Wd);
-        if (i < L)
-            conv_step("down" + std::to_string(i) + ".c2", h->d_s1, ch[i], ch[i], h->d_cat[i], 2 * ch[i], 0, ch[i], H, Wd);
-        else
-            conv_step("down" + std::to_string(i) + ".c2", h->d_s1, co, co, h->d_s0, co, 0, co, H, Wd);
-    }
-    float *cur = h->d_s0;         // bottleneck feature map (levels >= 1 is enforced by mi_unet_create)
-    for (int i = 1; i <= L && bilinear; ++i) {
-        // bilinear x2 into the upper half of the concat buffer, then 2 ch[lvl] -> ch[lvl] -> ch[lvl] / 2 (ch[0] at the last level)
-        const int lvl = L - i, c = ch[lvl], cout = lvl > 0 ? c / 2 : c;
-        Step u;
-        u.kind = Step::UPSAMPLE; u.name = "up" + std::to_string(i) + ".up";
-        u.src = cur; u.dst = h->d_cat[lvl]; u.H = H; u.W = Wd; u.C = c; u.ld = 2 * c; u.co_off = c;
-        u.bytes_per_img = 4.0 * H * Wd * c * (1 + 4);           // the input once, the output slice once
-        h->plan.push_back(u);
-        H *= 2; Wd *= 2;
-        conv_step("up" + std::to_string(i) + ".c1", h->d_cat[lvl], 2 * c, 2 * c, h->d_s1, c, 0, c, H, Wd);
-        conv_step("up" + std::to_string(i) + ".c2", h->d_s1, c, c, h->d_s0, cout, 0, cout, H, Wd);
-        cur = h->d_s0;
-    }
-    for (int i = 1; i <= L && !bilinear; ++i) {
-        const int lvl = L - i, cin = ch[lvl + 1], cout = ch[lvl];
-        Step t;
-        t.kind = Step::CONVT; t.name = "up" + std::to_string(i) + ".t";
-        t.a.in = cur; t.a.wpk = W_(hw.convT[ti].w); t.a.bias = W_(hw.convT[ti].shift); t.a.out = h->d_cat[lvl];
-        t.a.wpk4 = hw.convT[ti].w4 ? W_(hw.convT[ti].w4) : nullptr;
-        t.a.H = H; t.a.W = Wd; t.a.Cin = cin; t.a.ldc = cin; t.a.Cout = cout;
-        t.a.CoutPad = (int)round_up((size_t)4 * cout, NPAD); t.a.ldo = 2 * cout; t.a.co_off = cout; t.a.relu = 0;
-        conv_cost(t, H, Wd, cin, cout, 4, true);
-        t.flops_per_img = 2.0 * (double)H * Wd * cin * cout * 4;
-        ++ti;
-        h->plan.push_back(t);
-        H *= 2; Wd *= 2;
-        conv_step("up" + std::to_string(i) + ".c1", h->d_cat[lvl], cin, cin, h->d_s1, cout, 0, cout, H, Wd);
-        conv_step("up" + std::to_string(i) + ".c2", h->d_s1, cout, cout, h->d_s0, cout, 0, cout, H, Wd);
-        cur = h->d_s0;
-    }
-    Step hd;
-    hd.kind = Step::HEAD; hd.name = "outc+argmax";
-    hd.src = cur; hd.w = W_(hw.head.w); hd.shift = W_(hw.head.shift); hd.H = H; hd.W = Wd; hd.C = ch[0]; hd.Cout = c.classes;
-    hd.flops_per_img = 2.0 * H * Wd * ch[0] * c.classes;
-    hd.bytes_per_img = (double)H * Wd * (4.0 * ch[0] + 1.0);
-    h->plan.push_back(hd);
-    // the last conv may run the head in its epilogue (F(4x4) one-block kernel: every channel of a pixel in one workgroup)
-    {
-        const char *fh = getenv("MIUNET_FUSE_HEAD");
-        const int last = (int)h->plan.size() - 1;
-        Step &lc = h->plan[last - 1];
-        if (lc.kind == Step::CONV) lc.feeds_head = true;
-        const bool lp_algo = h->algo == MI_UNET_CONV_BF16 || h->algo == MI_UNET_CONV_FP16;
-        if (!(fh && fh[0] == '0') && lc.kind == Step::CONV && (lc.a.wpk4 != nullptr || lp_algo) && lc.a.Cout <= 64 && c.classes <= 4 &&
-            lc.a.pool_out == nullptr)
-            lc.head_step = last;
-    }
-    return check_plan_fits(h);
-}
-
-int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);
 
 int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits)
 {
@@ -680,79 +65,6 @@ int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, 
     return 0;
 }
 
-// one image's [npix][C] tensor (pixel stride `ld` elements of `bits` bits, kind: 1 = bf16, 2 = fp16 for 16-bit storage) -> dense floats
-int download_tensor(hipStream_t s, const void *d, int bits, int lp_kind, size_t npix, int C, int ld, float *dst)
-{
-    if (!dst) return 0;
-    const size_t eb = (size_t)bits / 8;
-    std::vector<unsigned char> raw(npix * C * eb);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy2D(raw.data(), C * eb, d, (size_t)ld * eb, C * eb, npix, hipMemcpyDeviceToHost));
-    const size_t n = npix * C;
-    if (bits == 32) memcpy(dst, raw.data(), n * 4);
-    else if (bits == 8) for (size_t i = 0; i < n; ++i) dst[i] = (float)raw[i];
-    else {
-        const uint16_t *r16 = reinterpret_cast<const uint16_t *>(raw.data());
-        for (size_t i = 0; i < n; ++i) dst[i] = lp_kind == 2 ? fp16_to_float(r16[i]) : bf16_to_float(r16[i]);
-    }
-    return 0;
-}
-
-// One step of the plan as this micro-batch launches it: its arguments (CONV / CONVT) and the route with the fusions granted.
-struct Launch {
-    ConvArgs a{};
-    RouteChoice rc{ Route::FIRST, 0 };
-    bool skip = false;            // done by a neighbour: pooling by its producer, the first layer by inc.c2, the head by the last conv
-};
-
-// Route every step for batch B (routing.cpp decides; the engine only fills in the arguments and the fusions it asks for).
-void route_plan(const mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits, int lp_kind, std::vector<Launch> &out)
-{
-    const RoutePolicy pol{ h->algo, h->wino4_guard_tripped, h->wino4_min_wg };
-    out.assign(h->plan.size(), Launch{});
-    for (size_t i = 0; i < h->plan.size(); ++i) {
-        const Step &st = h->plan[i];
-        Launch &l = out[i];
-        if (st.fused_away) l.skip = true;
-        if (st.kind == Step::FIRST) l.rc.route = Route::FIRST;
-        else if (st.kind == Step::POOL) l.rc.route = Route::POOL;
-        else if (st.kind == Step::UPSAMPLE) l.rc.route = Route::UPSAMPLE;
-        else if (st.kind == Step::HEAD) l.rc.route = Route::HEAD;
-        else if (st.kind == Step::CONVT) {
-            l.a = st.a; l.a.B = B; l.a.rt = h->routing;
-            l.a.out_lp = lp_kind != 0 ? 1 : 0;
-            l.rc.route = route_convT(l.a, pol);
-        } else {
-            ConvArgs &a = l.a;
-            a = st.a; a.B = B; a.rt = h->routing;
-            a.ksplit_ws = h->d_ksplit; a.ksplit_ws_bytes = h->ksplit_bytes;
-            // 16-bit pipelines: every activation tensor is bf16 / fp16 in HBM except the fp32 head's input
-            a.out_lp = (lp_kind != 0 && !st.feeds_head) ? 1 : 0;
-            unsigned want = 0;
-            if (st.head_step >= 0) {              // the 1x1 head + argmax in the epilogue: this layer's activations never reach HBM
-                const Step &hd = h->plan[st.head_step];
-                a.head_w = hd.w; a.head_b = hd.shift; a.head_classes = hd.Cout;
-                a.head_logits = d_logits; a.head_labels = d_labels;
-                want |= FUSE_HEAD;
-            }
-            const Step *first = (i == 1 && h->plan[0].kind == Step::FIRST) ? &h->plan[0] : nullptr;
-            if (first) {                          // the first layer in this launch's loader: its tensor is neither written nor read back
-                a.first_cin = first->C;
-                want |= FUSE_FIRST;
-            }
-            l.rc = route_conv(a, pol, want);
-            if (l.rc.fused & FUSE_HEAD) out[st.head_step].skip = true;
-            else { a.head_w = a.head_b = nullptr; a.head_classes = 0; a.head_logits = nullptr; a.head_labels = nullptr; }
-            if (l.rc.fused & FUSE_FIRST) {
-                a.first_img = d_imgs; a.first_lut = h->d_lut; a.first_w = first->w; a.first_shift = first->shift;
-                out[0].skip = true;
-            } else {
-                a.first_cin = 0;
-            }
-        }
-    }
-}
-
 hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s)
 {
     switch (r) {
@@ -763,81 +75,13 @@ hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s)
     return hipErrorInvalidValue;
 }
 
-// mi_unet_debug_capture: the tensor step `st` is about to read ...
-int tap_input(mi_unet *h, const Step &st, const Launch &l, const uint8_t *d_imgs, int lp_kind)
+int grow_events(std::vector<Event> &ev, size_t n)
 {
-    hipStream_t s = h->stream;
-    const size_t im = (size_t)h->tap.img;
-    const int abits = lp_kind ? 16 : 32;
-    if (st.kind == Step::FIRST || (l.rc.fused & FUSE_FIRST)) {
-        // (a step that runs the first layer in its loader reads the u8 image: that is what the caller's `in` buffer receives)
-        const Step &f = h->plan[0];
-        h->tap.info->in_bits = 8;
-        h->tap.info->fused_first = st.kind != Step::FIRST;
-        return download_tensor(s, d_imgs + im * f.H * f.W * f.C, 8, 0, (size_t)f.H * f.W, f.C, f.C, h->tap.in);
+    while (ev.size() < n) {
+        ev.emplace_back();
+        HIP_TRY(ev.back().reset());
     }
-    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
-        h->tap.info->in_bits = abits;
-        const size_t npix = (size_t)st.a.H * st.a.W;
-        return download_tensor(s, reinterpret_cast<const char *>(st.a.in) + im * npix * st.a.ldc * (abits / 8), abits, lp_kind, npix, st.a.Cin,
-                               st.a.ldc, h->tap.in);
-    }
-    const int b = st.kind == Step::HEAD ? 32 : abits;           // POOL, UPSAMPLE (activation type), HEAD (always fp32)
-    h->tap.info->in_bits = b;
-    const size_t npix = (size_t)st.H * st.W;
-    const int ld = (st.kind == Step::HEAD || st.kind == Step::UPSAMPLE) ? st.C : st.ld;
-    return download_tensor(s, reinterpret_cast<const char *>(st.src) + im * npix * ld * (b / 8), b, lp_kind, npix, st.C, ld, h->tap.in);
-}
-
-// ... and what it stored
-int tap_output(mi_unet *h, const Step &st, const Launch &l, uint8_t *d_labels, float *d_logits, int lp_kind)
-{
-    hipStream_t s = h->stream;
-    mi_unet_layer_info *ti = h->tap.info;
-    snprintf(ti->kernel, sizeof ti->kernel, "%s", route_name(l.rc.route, l.rc.fused).c_str());
-    const size_t im = (size_t)h->tap.img;
-    const int abits = lp_kind ? 16 : 32;
-    const ConvArgs &ta = l.a;
-    if (st.kind == Step::HEAD || (l.rc.fused & FUSE_HEAD)) {
-        const size_t hw = (size_t)h->cfg.height * h->cfg.width;
-        const int classes = h->cfg.classes;
-        ti->fused_head = st.kind == Step::CONV;
-        ti->out_bits = 32;
-        if (d_logits)
-            if (int rc = download_tensor(s, d_logits + im * classes * hw, 32, 0, classes * hw, 1, 1, h->tap.out)) return rc;
-        if (h->tap.labels) {
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpy(h->tap.labels, d_labels + im * hw, hw, hipMemcpyDeviceToHost));
-        }
-        return 0;
-    }
-    if (st.kind == Step::FIRST) {
-        ti->out_bits = abits;
-        const size_t npix = (size_t)st.H * st.W;
-        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.ld * (abits / 8), abits, lp_kind, npix, st.Cout, st.ld, h->tap.out);
-    }
-    if (st.kind == Step::CONV || st.kind == Step::CONVT) {
-        const int ob = (lp_kind && ta.out_lp) ? 16 : 32;
-        ti->out_bits = ob;
-        const size_t npix = (size_t)ta.H * ta.W * (st.kind == Step::CONVT ? 4 : 1);
-        if (int rc = download_tensor(s, reinterpret_cast<const char *>(ta.out) + (im * npix * ta.ldo + ta.co_off) * (ob / 8), ob, lp_kind, npix, ta.Cout,
-                                     ta.ldo, h->tap.out))
-            return rc;
-        if (st.kind == Step::CONV && ta.pool_out) {
-            ti->pooled = 1;
-            return download_tensor(s, reinterpret_cast<const char *>(ta.pool_out) + im * (npix / 4) * ta.pool_ld * (ob / 8), ob, lp_kind, npix / 4,
-                                   ta.Cout, ta.pool_ld, h->tap.pooled);
-        }
-        return 0;
-    }
-    ti->out_bits = abits;
-    if (st.kind == Step::UPSAMPLE) {                             // the slice it wrote: channels [co_off, co_off + C) of the concat buffer
-        const size_t npix = (size_t)(2 * st.H) * (2 * st.W);
-        return download_tensor(s, reinterpret_cast<const char *>(st.dst) + (im * npix * st.ld + st.co_off) * (abits / 8), abits, lp_kind, npix, st.C,
-                               st.ld, h->tap.out);
-    }
-    const size_t npix = (size_t)(st.H / 2) * (st.W / 2);         // POOL
-    return download_tensor(s, reinterpret_cast<const char *>(st.dst) + im * npix * st.C * (abits / 8), abits, lp_kind, npix, st.C, st.C, h->tap.out);
+    return 0;
 }
 
 int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits)
@@ -845,7 +89,7 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
     hipStream_t s = h->stream;
     const int lp_kind = h->algo == MI_UNET_CONV_BF16 ? 1 : h->algo == MI_UNET_CONV_FP16 ? 2 : 0;
     std::vector<Launch> launches;
-    route_plan(h, d_imgs, B, d_labels, d_logits, lp_kind, launches);
+    route_plan(plan_input(h), h->plan, d_imgs, B, d_labels, d_logits, lp_kind, launches);
     for (size_t i = 0; i < h->plan.size(); ++i) {
         const Step &st = h->plan[i];
         const Launch &l = launches[i];
@@ -858,11 +102,7 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
             if (int rc = tap_input(h, st, l, d_imgs, lp_kind)) return rc;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->profiling) {
-            while (h->ev_pool.size() < h->ev_used + 2) {
-                hipEvent_t ev;
-                HIP_TRY(hipEventCreate(&ev));
-                h->ev_pool.push_back(ev);
-            }
+            if (int rc = grow_events(h->ev_pool, h->ev_used + 2)) return rc;
             e0 = h->ev_pool[h->ev_used++];
             e1 = h->ev_pool[h->ev_used++];
             HIP_TRY(hipEventRecord(e0, s));
@@ -937,10 +177,6 @@ int check_handle(mi_unet *h, bool need_weights)
     return 0;
 }
 
-}  // namespace
-
-namespace miunet {
-
 DeviceWeights::~DeviceWeights()
 {
     if (d) {
@@ -951,8 +187,6 @@ DeviceWeights::~DeviceWeights()
         if (have) (void)hipSetDevice(cur);
     }
 }
-
-int engine_fail(int code, const std::string &msg) { return fail(code, msg); }
 
 Routing Routing::from_env()
 {
@@ -972,11 +206,6 @@ Routing Routing::from_env()
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
         r.cus = p.multiProcessorCount;
     return r;
-}
-
-int engine_pack_weights(const mi_unet_config &cfg, int algo, const void *blob, size_t len, HostWeights &hw)
-{
-    return build_host_weights(cfg, algo, blob, len, hw);
 }
 
 int engine_adopt_weights(mi_unet_t *h, const HostWeights &hw, bool upload)
@@ -999,7 +228,7 @@ int engine_adopt_weights(mi_unet_t *h, const HostWeights &hw, bool upload)
     h->weights = dw;
     h->d_weights = dw->d;
     h->weight_floats = dw->floats;
-    if (int rc = build_plan(h, dw->layout)) return rc;
+    if (int rc = build_plan(plan_input(h), dw->layout, h->plan)) return rc;
     h->weights_loaded = true;
     return MI_UNET_OK;
 }
@@ -1103,10 +332,6 @@ int engine_algo(const mi_unet_t *h) { return h->algo; }
 const mi_unet_config &engine_config(const mi_unet_t *h) { return h->cfg; }
 hipStream_t engine_stream(const mi_unet_t *h) { return h->stream; }
 
-}  // namespace miunet
-
-namespace {
-
 // contour outputs of `bm` images: device -> pinned mirror (async, behind the kernels), and after the stream has been
 // synchronised only what exists goes on to the caller's arrays (the capacity is mostly air: 2 x 32768 ints per image)
 int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours)
@@ -1114,16 +339,14 @@ int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours)
     const size_t need = (size_t)bm * ((size_t)cap_points * 2 + cap_contours + 1 + 1);
     if (need <= h->cont_cap) return 0;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->d_cont) HIP_TRY(hipFree(h->d_cont));
-    if (h->h_cont) HIP_TRY(hipHostFree(h->h_cont));
-    h->d_cont = nullptr; h->h_cont = nullptr; h->cont_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_cont, need * sizeof(int)));
-    HIP_TRY(hipHostMalloc(&h->h_cont, 2 * need * sizeof(int), hipHostMallocDefault));       // two halves: see run_raw_call
+    h->cont_cap = 0;
+    HIP_TRY(h->d_cont.reset(need));
+    HIP_TRY(h->h_cont.reset(2 * need));       // two halves: see run_raw_call
     h->cont_cap = need;
     return 0;
 }
 
-int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int half = 0)
+int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int half)
 {
     // counts and starts whole (small), the points whole as well: 4 MB at 16 images rides PCIe in 0.1 ms once it is pinned
     const size_t n = (size_t)bm * ((size_t)cap_points * 2 + cap_contours + 1 + 1);
@@ -1131,7 +354,7 @@ int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int
     return 0;
 }
 
-void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contours, int32_t *xy, int32_t *start, int32_t *counts, int half = 0)
+void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contours, int32_t *xy, int32_t *start, int32_t *counts, int half)
 {
     const int *p_xy = h->h_cont + half * h->cont_cap, *p_start = p_xy + (size_t)bm * cap_points * 2, *p_count = p_start + (size_t)bm * (cap_contours + 1);
     for (int i = 0; i < bm; ++i) {
@@ -1145,11 +368,11 @@ void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contou
     }
 }
 
-}  // namespace
+}  // namespace miunet
 
 extern "C" {
 
-const char *mi_unet_last_error(void) { return g_err.c_str(); }
+const char *mi_unet_last_error(void) { return engine_last_error().c_str(); }
 
 int mi_unet_device_count(void)
 {
@@ -1202,6 +425,8 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
         h->algo = algo;
         const char *fp = getenv("MIUNET_FUSE_POOL");
         h->fuse_pool = !(fp && !strcmp(fp, "0"));
+        const char *fh = getenv("MIUNET_FUSE_HEAD");
+        h->fuse_head = !(fh && fh[0] == '0');
         if (const char *mw = getenv("MIUNET_WINO4_MIN_WG")) h->wino4_min_wg = atoi(mw);
         h->routing = Routing::from_env();
         const char *gr = getenv("MIUNET_GRAPH");
@@ -1216,31 +441,28 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
     } while (0)
     HIP_TRY_H(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
-    HIP_TRY_H(hipEventCreate(&h->tev0));
-    HIP_TRY_H(hipEventCreate(&h->tev1));
-    const size_t Bm = cfg->max_batch, npix0 = Bm * cfg->height * cfg->width;
-    for (int i = 0; i < L; ++i) {
-        h->cat_floats[i] = (npix0 >> (2 * i)) * 2 * h->ch[i];
-        HIP_TRY_H(hipMalloc(&h->d_cat[i], sizeof(float) * h->cat_floats[i]));
-    }
-    h->s_floats = npix0 * h->ch[0];
-    HIP_TRY_H(hipMalloc(&h->d_s0, sizeof(float) * h->s_floats));
-    HIP_TRY_H(hipMalloc(&h->d_s1, sizeof(float) * h->s_floats));
-    HIP_TRY_H(hipMalloc(&h->d_img, npix0 * cfg->in_ch));
-    HIP_TRY_H(hipMalloc(&h->d_labels, npix0));
-    HIP_TRY_H(hipMalloc(&h->d_logits, sizeof(float) * npix0 * cfg->classes));
-    HIP_TRY_H(hipHostMalloc(&h->h_img, npix0 * cfg->in_ch, hipHostMallocDefault));
-    HIP_TRY_H(hipHostMalloc(&h->h_labels, npix0, hipHostMallocDefault));
+    HIP_TRY_H(h->tev0.reset());
+    HIP_TRY_H(h->tev1.reset());
+    const size_t npix0 = (size_t)cfg->max_batch * cfg->height * cfg->width;
+    plan_buffer_floats(*cfg, h->cat_floats, h->s_floats);
+    for (int i = 0; i < L; ++i) HIP_TRY_H(h->d_cat[i].reset(h->cat_floats[i]));
+    HIP_TRY_H(h->d_s0.reset(h->s_floats));
+    HIP_TRY_H(h->d_s1.reset(h->s_floats));
+    HIP_TRY_H(h->d_img.reset(npix0 * cfg->in_ch));
+    HIP_TRY_H(h->d_labels.reset(npix0));
+    HIP_TRY_H(h->d_logits.reset(npix0 * cfg->classes));
+    HIP_TRY_H(h->h_img.reset(npix0 * cfg->in_ch));
+    HIP_TRY_H(h->h_labels.reset(npix0));
     {
         const char *sk = getenv("MIUNET_SPLITK");
         if (!(sk && !strcmp(sk, "0"))) {
             h->ksplit_bytes = (size_t)64 << 20;
-            HIP_TRY_H(hipMalloc(&h->d_ksplit, h->ksplit_bytes));
+            HIP_TRY_H(h->d_ksplit.reset(h->ksplit_bytes / sizeof(float)));
         }
     }
-    HIP_TRY_H(hipMalloc(&h->d_lut, sizeof(float) * 256));
+    HIP_TRY_H(h->d_lut.reset(256));
     float lut[256];
-    for (int i = 0; i < 256; ++i) lut[i] = static_cast<float>(i) / 255.0f;   // src/process.cpp:38, true division
+    first_layer_lut(lut);
     HIP_TRY_H(hipMemcpy(h->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
 #undef HIP_TRY_H
     *out = h;
@@ -1252,7 +474,7 @@ int mi_unet_load_weights_from_memory(mi_unet_t *h, const void *blob, size_t len)
     if (int rc = check_handle(h, false)) return rc;
     if (!blob) return fail(MI_UNET_EARG, "null weight blob");
     HostWeights hw;
-    if (int rc = build_host_weights(h->cfg, h->algo, blob, len, hw)) return rc;
+    if (int rc = engine_pack_weights(h->cfg, h->algo, blob, len, hw)) return rc;
     if (int rc = engine_adopt_weights(h, hw, /*upload=*/true)) return rc;
     return engine_calibrate(h);
 }
@@ -1280,13 +502,13 @@ int mi_unet_clone(const mi_unet_t *src, int max_batch, mi_unet_t **out)
     cfg.conv_algo = src->algo;                       // the resolved algorithm: the shared blob is packed for it
     mi_unet_t *h = nullptr;
     if (int rc = mi_unet_create(&cfg, &h)) return rc;
-    h->fuse_pool = src->fuse_pool; h->wino4_min_wg = src->wino4_min_wg;
+    h->fuse_pool = src->fuse_pool; h->fuse_head = src->fuse_head; h->wino4_min_wg = src->wino4_min_wg;
     h->routing = src->routing;                       // a clone routes exactly as its source (same device)
     h->wino4_guard_tripped = src->wino4_guard_tripped; h->guard_diff = src->guard_diff; h->guard_text = src->guard_text;
     h->weights = src->weights;                       // shared: freed with the last handle that holds it
     h->d_weights = h->weights->d;
     h->weight_floats = h->weights->floats;
-    if (int rc = build_plan(h, h->weights->layout)) { mi_unet_destroy(h); return rc; }
+    if (int rc = build_plan(plan_input(h), h->weights->layout, h->plan)) { mi_unet_destroy(h); return rc; }
     h->weights_loaded = true;
     *out = h;
     return MI_UNET_OK;
@@ -1384,686 +606,6 @@ int mi_unet_extract_contours(mi_unet_t *h, const uint8_t *masks, int B, int32_t 
     return MI_UNET_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// upload + min/max + resample `bm` RAW images into h->d_img.  An engine with in_ch = C > 1 takes C planes per image
-// (plane c of image i at index i*C + c, each with its own size and its own min/max, as if every plane went through
-// preprocess_raw on its own) and interleaves them into the HWC tile the first layer reads; a caller holding one plane per
-// image passes its pointer C times (the grey -> B,G,R replication cv::imread(IMREAD_COLOR) does at src/mask2polygon.cpp:117).
-// large host copies (RAW staging in, tiles / masks out) on the handle's helper threads (MIUNET_COPY_THREADS, default 4; 1 = plain memcpy)
-void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes)
-{
-    static const int copy_threads = [] { const char *e = getenv("MIUNET_COPY_THREADS"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v > 16 ? 16 : v; }();
-    if (copy_threads > 1 && bytes >= (1u << 20)) {
-        if (!h->copy_pool) h->copy_pool.reset(new CopyPool(copy_threads - 1));
-        h->copy_pool->copy(dst, src, bytes);
-    } else {
-        memcpy(dst, src, bytes);
-    }
-}
-
-int stage_raw16(mi_unet *h, const uint16_t *const *raws, const int *widths, const int *heights, int bm, hipStream_t s, uint8_t *d_tiles)
-{
-    const int C = h->cfg.in_ch;
-    const size_t hw = (size_t)h->cfg.height * h->cfg.width;
-    if (!h->d_mnmx) HIP_TRY(hipMalloc(&h->d_mnmx, sizeof(unsigned) * 2 * h->cfg.max_batch * C));
-    int slot = mi_unet::RAW_RING - 1, mn_src = 0;
-    for (int i = 0; i < bm * C; ++i) {
-        const int w = widths[i], ht = heights[i];
-        if (!raws[i] || w <= 0 || ht <= 0) return fail(MI_UNET_EARG, "RAW16 input: bad image description");
-        const size_t n = (size_t)w * ht;
-        if (n > h->raw_cap) {                    // grow the staging ring (outside any captured region)
-            HIP_TRY(hipStreamSynchronize(s));
-            for (int r = 0; r < mi_unet::RAW_RING; ++r) {
-                if (h->d_raw[r]) HIP_TRY(hipFree(h->d_raw[r]));
-                if (h->h_raw[r]) HIP_TRY(hipHostFree(h->h_raw[r]));
-                h->d_raw[r] = nullptr; h->h_raw[r] = nullptr; h->raw_busy[r] = false;
-            }
-            h->raw_cap = 0;
-            for (int r = 0; r < mi_unet::RAW_RING; ++r) {
-                HIP_TRY(hipMalloc(&h->d_raw[r], n * sizeof(uint16_t)));
-                HIP_TRY(hipHostMalloc(&h->h_raw[r], n * sizeof(uint16_t), hipHostMallocDefault));
-                if (!h->raw_done[r]) HIP_TRY(hipEventCreateWithFlags(&h->raw_done[r], hipEventDisableTiming));
-            }
-            h->raw_cap = n;
-        }
-        // a caller holding one plane per image passes its pointer C times: upload and scan it once, resample it C times
-        const bool same_plane = i % C != 0 && raws[i] == raws[i - 1] && w == widths[i - 1] && ht == heights[i - 1];
-        if (!same_plane) {
-            slot = (slot + 1) % mi_unet::RAW_RING;
-            mn_src = i;
-            if (h->raw_busy[slot]) { HIP_TRY(hipEventSynchronize(h->raw_done[slot])); h->raw_busy[slot] = false; }   // slot consumed
-            // a caller that keeps its RAW images in pinned memory (mi_unet_host_alloc) skips the staging copy: the DMA engine
-            // reads its buffer directly, the host thread only enqueues
-            hipPointerAttribute_t attr;
-            const bool pinned = hipPointerGetAttributes(&attr, raws[i]) == hipSuccess && attr.type == hipMemoryTypeHost;
-            if (!pinned) {
-                (void)hipGetLastError();             // an ordinary host pointer is "invalid value" to the query: not an error of ours
-                host_copy(h, h->h_raw[slot], raws[i], n * sizeof(uint16_t));
-            }
-            HIP_TRY(hipMemcpyAsync(h->d_raw[slot], pinned ? raws[i] : h->h_raw[slot], n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        }
-        const int r = slot;
-        hipError_t e = same_plane ? hipSuccess : launch_minmax_u16(h->d_raw[r], n, h->d_mnmx + 2 * mn_src, s);
-        if (e == hipSuccess)
-            e = launch_resample_u8(h->d_raw[r], w, ht, h->d_mnmx + 2 * mn_src, d_tiles + (size_t)(i / C) * hw * C + i % C, h->cfg.width,
-                                   h->cfg.height, C, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("preprocess launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipEventRecord(h->raw_done[r], s));
-        h->raw_busy[r] = true;
-    }
-    return 0;
-}
-}  // namespace
-
-namespace {
-
-int ensure_raw_pipeline(mi_unet *h, bool two_buffers)
-{
-    if (!h->pre_stream) HIP_TRY(hipStreamCreateWithFlags(&h->pre_stream, hipStreamNonBlocking));
-    if (!h->tail_stream) HIP_TRY(hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking));
-    if (!h->dl_stream) HIP_TRY(hipStreamCreateWithFlags(&h->dl_stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : h->tiles_done)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const size_t npix = (size_t)h->cfg.max_batch * h->cfg.height * h->cfg.width;
-    if (!h->d_tail_vis) HIP_TRY(hipMalloc(&h->d_tail_vis, npix));
-    if (!h->d_labels2) HIP_TRY(hipMalloc(&h->d_labels2, npix));
-    for (int i = 0; i < 2; ++i) {
-        if (!h->net_done[i]) HIP_TRY(hipEventCreateWithFlags(&h->net_done[i], hipEventDisableTiming));
-        for (hipEvent_t &e : h->tail_ev[i])
-            if (!e) HIP_TRY(hipEventCreate(&e));
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (!h->tile_ready[i]) HIP_TRY(hipEventCreateWithFlags(&h->tile_ready[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < 2; ++i) {
-        for (hipEvent_t &e : h->stage_ev[i])
-            if (!e) HIP_TRY(hipEventCreate(&e));
-        if (!h->out_done[i]) HIP_TRY(hipEventCreateWithFlags(&h->out_done[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 2; ++j)
-            if (!h->pre_ev[i][j]) HIP_TRY(hipEventCreate(&h->pre_ev[i][j]));
-    if (two_buffers && !h->h_labels2)
-        HIP_TRY(hipHostMalloc(&h->h_labels2, (size_t)h->cfg.max_batch * h->cfg.height * h->cfg.width, hipHostMallocDefault));
-    for (int i = 0; i < (two_buffers ? 2 : 1); ++i)
-        if (!h->h_tiles[i])
-            HIP_TRY(hipHostMalloc(&h->h_tiles[i], (size_t)h->cfg.max_batch * h->cfg.height * h->cfg.width * h->cfg.in_ch, hipHostMallocDefault));
-    if (two_buffers && !h->d_img2)
-        HIP_TRY(hipMalloc(&h->d_img2, (size_t)h->cfg.max_batch * h->cfg.height * h->cfg.width * h->cfg.in_ch));
-    return 0;
-}
-
-// The RAW-in entry points as one loop over micro-batches.  Per micro-batch k on the engine's stream: network -> [postprocess ->
-// mask_to_image -> contours] -> D2H; on the second stream, meanwhile: the host staging copies, H2D transfers and
-// preprocessing kernels of micro-batch k + 1 into the other tile buffer.
-struct RawCall {
-    const uint16_t *const *raws; const int *widths, *heights; int B;
-    uint8_t *tiles, *out_u8; float *logits;            // out_u8: label maps (infer) or 0 / 255 masks (segment)
-    bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *counts;
-};
-
-int run_raw_call(mi_unet *h, const RawCall &c)
-{
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    const int H = h->cfg.height, W = h->cfg.width, Bm = h->cfg.max_batch;
-    const size_t hw = (size_t)H * W, C = (size_t)h->cfg.in_ch;
-    hipStream_t s = h->stream;
-    if (c.B <= 0) return MI_UNET_OK;
-    // every image description is checked BEFORE anything is enqueued: a bad width in image k + 1 must not be found after the
-    // network of micro-batch k has started
-    for (size_t i = 0; i < (size_t)c.B * C; ++i)
-        if (!c.raws[i] || c.widths[i] <= 0 || c.heights[i] <= 0)
-            return fail(MI_UNET_EARG, "RAW16 input: bad image description (image " + std::to_string(i / C) + ", plane " + std::to_string(i % C) + ")");
-    // micro-batches: chunks of max_batch images -- and the FIRST chunk is cut once more when it is large (a quarter, at least
-    // four images, then the rest), so that the network starts as soon as a few images have been uploaded and preprocessed
-    // and the upload of the rest hides under it.
-    struct MB { int b0, bm; };
-    std::vector<MB> mbs;
-    for (int b0 = 0; b0 < c.B; b0 += Bm) mbs.push_back({ b0, std::min(Bm, c.B - b0) });
-    // MIUNET_RAW_SPLIT = 0: whole chunks only; "a" or "a,b,...": the first chunk is cut into a, b, ... images and the rest
-    // (default: a quarter of the chunk, at least four, then the rest -- same-card sweep at 16 images: 0 -> 749, 2 -> 780, 4 -> 787,
-    // 6 -> 737, 8 -> 779 images/s from pinned memory, tools/dev/split_sweep.py)
-    static const std::vector<int> split_env = [] {
-        std::vector<int> v;
-        const char *e = getenv("MIUNET_RAW_SPLIT");
-        if (!e) return std::vector<int>{ -1 };
-        for (const char *q = e; *q;) {
-            v.push_back(atoi(q));
-            while (*q && *q != ',') ++q;
-            if (*q == ',') ++q;
-        }
-        return v;
-    }();
-    if (!(split_env.size() == 1 && split_env[0] == 0) && mbs[0].bm >= 8) {
-        std::vector<int> cuts = split_env;
-        if (cuts.size() == 1 && cuts[0] < 0) cuts[0] = std::max(4, mbs[0].bm / 4);
-        int left = mbs[0].bm, b0 = 0;
-        std::vector<MB> parts;
-        for (int cnt : cuts) {
-            if (cnt <= 0 || cnt >= left) break;
-            parts.push_back({ b0, cnt });
-            b0 += cnt; left -= cnt;
-        }
-        parts.push_back({ b0, left });
-        mbs.erase(mbs.begin());
-        mbs.insert(mbs.begin(), parts.begin(), parts.end());
-    }
-    const int n_mb = (int)mbs.size();
-    if (int rc = ensure_raw_pipeline(h, n_mb > 1)) return rc;
-    for (float &m : h->stage_ms) m = 0.f;
-    auto tile_buf = [&](int k) { return (k & 1) ? h->d_img2 : h->d_img; };
-    auto out_buf = [&](int k) { return (k & 1) ? h->h_labels2 : h->h_labels; };
-    auto stage = [&](int k) -> int {                   // upload + preprocess micro-batch k on the second stream
-        const int bm = mbs[k].bm, par = k & 1;
-        const size_t b0 = (size_t)mbs[k].b0;
-        if (k >= 2) HIP_TRY(hipStreamWaitEvent(h->pre_stream, c.tiles ? h->tiles_done[par] : h->net_done[par], 0));   // its last readers: network and tile download of k - 2
-        HIP_TRY(hipEventRecord(h->pre_ev[k % 3][0], h->pre_stream));
-        if (int rc = stage_raw16(h, c.raws + b0 * C, c.widths + b0 * C, c.heights + b0 * C, bm, h->pre_stream, tile_buf(k))) return rc;
-        HIP_TRY(hipEventRecord(h->pre_ev[k % 3][1], h->pre_stream));
-        HIP_TRY(hipEventRecord(h->tile_ready[par], h->pre_stream));
-        return 0;
-    };
-    auto enqueue = [&](int k) -> int {                 // micro-batch k: network on the engine's stream, everything behind it on the tail stream
-        const int bm = mbs[k].bm, par = k & 1;
-        const size_t b0 = (size_t)mbs[k].b0;
-        uint8_t *d_tiles = tile_buf(k);
-        uint8_t *d_lab = par ? h->d_labels2 : h->d_labels;
-        hipStream_t ts = h->tail_stream;
-        if (c.segment && contour_workspace_bytes(bm, H, W, c.cap_contours) > h->tail_ws_bytes)
-            return fail(MI_UNET_EARG, "contour workspace does not fit (cap_contours too large)");
-        HIP_TRY(hipStreamWaitEvent(s, h->tile_ready[par], 0));
-        if (k >= 2) HIP_TRY(hipStreamWaitEvent(s, h->out_done[par], 0));                      // the tail of k - 2 has read this label buffer
-        HIP_TRY(hipEventRecord(h->stage_ev[par][0], s));
-        float *d_lg = c.logits ? h->d_logits : nullptr;
-        if (int rc = run_microbatch(h, d_tiles, bm, d_lab, d_lg)) return rc;                   // UNet + argmax
-        HIP_TRY(hipEventRecord(h->stage_ev[par][1], s));
-        if (c.logits)                                  // (a debugging output: into the caller's pageable memory, which blocks the host)
-            HIP_TRY(hipMemcpyAsync(c.logits + b0 * hw * h->cfg.classes, h->d_logits, sizeof(float) * bm * hw * h->cfg.classes,
-                                   hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(h->net_done[par], s));
-        if (c.tiles) {                                 // the tiles leave on their own stream, beside the tail kernels
-            HIP_TRY(hipStreamWaitEvent(h->dl_stream, h->net_done[par], 0));
-            HIP_TRY(hipMemcpyAsync(h->h_tiles[par], d_tiles, bm * hw * C, hipMemcpyDeviceToHost, h->dl_stream));
-            HIP_TRY(hipEventRecord(h->tiles_done[par], h->dl_stream));
-        }
-        // ---- tail: ordered behind the network of k, concurrent with the network of k + 1
-        HIP_TRY(hipStreamWaitEvent(ts, h->net_done[par], 0));
-        hipEvent_t *tv = h->tail_ev[par];
-        HIP_TRY(hipEventRecord(tv[0], ts));
-        const uint8_t *d_result = d_lab;
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)bm * c.cap_points * 2, *d_count = d_start + (size_t)bm * (c.cap_contours + 1);
-        if (c.segment || h->postprocess) {
-            const int min_area = static_cast<int>(W * H * 0.06f);                              // src/postprocess.cpp:9, :30, :66
-            const hipError_t e = launch_postprocess_masks(d_lab, d_lab, bm, H, W, min_area, h->d_tail_ws, ts);      // {0, 2}
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
-        }
-        HIP_TRY(hipEventRecord(tv[1], ts));
-        if (c.segment) {
-            hipError_t e = launch_mask_to_image(d_lab, h->d_tail_vis, bm * hw, ts);
-            if (e == hipSuccess)
-                e = launch_extract_contours(h->d_tail_vis, bm, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_tail_ws, ts);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("segment launch: ") + hipGetErrorString(e));
-            d_result = h->d_tail_vis;
-        }
-        HIP_TRY(hipEventRecord(tv[2], ts));
-        HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, bm * hw, hipMemcpyDeviceToHost, ts));
-        if (c.segment) {
-            const size_t n = (size_t)bm * ((size_t)c.cap_points * 2 + c.cap_contours + 1 + 1);
-            HIP_TRY(hipMemcpyAsync(h->h_cont + par * h->cont_cap, h->d_cont, n * sizeof(int), hipMemcpyDeviceToHost, ts));
-        }
-        HIP_TRY(hipEventRecord(tv[3], ts));
-        HIP_TRY(hipEventRecord(h->out_done[par], ts));
-        return 0;
-    };
-    auto finalize = [&](int k) -> int {                // micro-batch k has left the device: pinned halves -> the caller's arrays
-        const int bm = mbs[k].bm, par = k & 1;
-        const size_t b0 = (size_t)mbs[k].b0;
-        if (c.tiles) {                                 // (done long before the tail: copied out while the tail still runs)
-            HIP_TRY(hipEventSynchronize(h->tiles_done[par]));
-            host_copy(h, c.tiles + b0 * hw * C, h->h_tiles[par], bm * hw * C);
-        }
-        HIP_TRY(hipEventSynchronize(h->out_done[par]));
-        host_copy(h, c.out_u8 + b0 * hw, out_buf(k), bm * hw);
-        if (c.segment)
-            contours_to_caller(h, bm, c.cap_points, c.cap_contours, c.xy + b0 * c.cap_points * 2, c.start + b0 * (c.cap_contours + 1), c.counts + b0, par);
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->pre_ev[k % 3][0], h->pre_ev[k % 3][1]));
-        h->stage_ms[MI_UNET_STAGE_UPLOAD_PRE] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, h->stage_ev[par][0], h->stage_ev[par][1]));
-        h->stage_ms[MI_UNET_STAGE_NETWORK] += ms;
-        for (int st = 0; st < 3; ++st) {
-            HIP_TRY(hipEventElapsedTime(&ms, h->tail_ev[par][st], h->tail_ev[par][st + 1]));
-            h->stage_ms[MI_UNET_STAGE_POSTPROCESS + st] += ms;
-        }
-        return 0;
-    };
-    // MIUNET_RAW_TRACE=1: host-side timeline of the call on stderr (when did each enqueue / staging / copy-out start and end)
-    static const bool trace = [] { const char *e = getenv("MIUNET_RAW_TRACE"); return e && e[0] == '1'; }();
-    const auto t_call = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what, int k) {
-        if (trace) fprintf(stderr, "[raw %8.3f ms] %s %d\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), what, k);
-    };
-    {
-        int bmax = 0;
-        for (const MB &m : mbs) bmax = std::max(bmax, m.bm);
-        if (c.segment)
-            if (int rc = grow_contour_buffers(h, bmax, c.cap_points, c.cap_contours)) return rc;
-        size_t need = postprocess_workspace_bytes(bmax, H, W);
-        if (c.segment) need = std::max(need, contour_workspace_bytes(bmax, H, W, c.cap_contours));
-        if (need > h->tail_ws_bytes) {
-            HIP_TRY(hipStreamSynchronize(h->tail_stream));
-            if (h->d_tail_ws) HIP_TRY(hipFree(h->d_tail_ws));
-            h->d_tail_ws = nullptr; h->tail_ws_bytes = 0;
-            HIP_TRY(hipMalloc(&h->d_tail_ws, need));
-            h->tail_ws_bytes = need;
-        }
-    }
-    // Once the first micro-batch is enqueued, H2D copies read the caller's (possibly page-locked) RAW buffers directly and the tail
-    // writes the handle's pinned mirrors: an error return with work still in flight would let the caller free buffers under the
-    // DMA engine.  Every failure path below therefore drains ALL four streams before the call returns.
-    auto pipeline = [&]() -> int {
-        HIP_TRY(hipStreamSynchronize(s));                  // an external stream may still be reading the tile buffers
-        mark("stage begin", 0);
-        if (int rc = stage(0)) return rc;
-        mark("stage end", 0);
-        for (int k = 0; k < n_mb; ++k) {
-            if (int rc = enqueue(k)) return rc;
-            mark("enqueued", k);
-            if (k + 1 < n_mb) {                            // the host's staging copies of k + 1 run while the device works on k
-                if (int rc = stage(k + 1)) return rc;
-                mark("stage end", k + 1);
-            }
-            if (k >= 1) {
-                if (int rc = finalize(k - 1)) return rc;   // ... and so does the copy-out of k - 1
-                mark("finalized", k - 1);
-            }
-        }
-        if (int rc = finalize(n_mb - 1)) return rc;
-        mark("finalized", n_mb - 1);
-        HIP_TRY(hipStreamSynchronize(s));                  // D2H copies into the caller's own (pageable) logits included
-        return MI_UNET_OK;
-    };
-    const int rc = pipeline();
-    if (rc != MI_UNET_OK) {
-        const std::string keep = g_err;
-        for (hipStream_t q : { h->pre_stream, s, h->tail_stream, h->dl_stream })
-            if (q) (void)hipStreamSynchronize(q);
-        for (int i = 0; i < mi_unet::RAW_RING; ++i) h->raw_busy[i] = false;
-        g_err = keep;
-        return rc;
-    }
-    mark("done", 0);
-    return MI_UNET_OK;
-}
-
-}  // namespace
-
-namespace {
-
-// ---- tiled inference (include/mi_unet.h: mi_unet_infer_tiled_*) ------------------------------------------------
-// One image of any size >= the engine's tile: uploaded once, cut into the overlapping tiles of tile_grid.h on the device, run in
-// tile order through run_microbatch in micro-batches of max_batch (the buffers, routes, graphs and numeric guard of
-// mi_unet_infer_u8), stitched on the device, and only then postprocessed / traced at full size.  Everything is enqueued on the
-// engine's stream; the host waits once, at the end.
-struct TiledCall {
-    const char *fn;
-    const uint8_t *img;                    // u8 form: [H][W][in_ch] ...
-    const uint16_t *const *planes;         // ... or RAW form: in_ch planes of u16 [H][W]
-    int H, W, halo;
-    uint8_t *norm, *out_u8;                // out_u8: label map (infer) or 0 / 255 mask (segment)
-    float *logits;
-    bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
-};
-
-int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bool blend)
-{
-    mi_unet::Tiled &t = h->tiled;
-    const size_t C = (size_t)h->cfg.in_ch;
-    if (npix <= t.px_cap && (!want_logits || npix <= t.logit_cap) && (!raw || npix <= t.raw_cap) && (!blend || npix <= t.acc_cap)) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (npix > t.px_cap) {
-        for (uint8_t **p : { &t.d_img, &t.d_labels, &t.d_vis })
-            if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
-        for (uint8_t **p : { &t.h_img, &t.h_out })
-            if (*p) { HIP_TRY(hipHostFree(*p)); *p = nullptr; }
-        t.px_cap = 0;
-        HIP_TRY(hipMalloc(&t.d_img, round_up(npix * C, 4)));            // whole dwords: launch_tile_gather reads aligned dwords
-        HIP_TRY(hipMalloc(&t.d_labels, npix));
-        HIP_TRY(hipMalloc(&t.d_vis, npix));
-        HIP_TRY(hipHostMalloc(&t.h_img, npix * C, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc(&t.h_out, npix, hipHostMallocDefault));
-        t.px_cap = npix;
-    }
-    if (want_logits && npix > t.logit_cap) {
-        if (t.d_logits) { HIP_TRY(hipFree(t.d_logits)); t.d_logits = nullptr; }
-        t.logit_cap = 0;
-        HIP_TRY(hipMalloc(&t.d_logits, sizeof(float) * npix * h->cfg.classes));
-        t.logit_cap = npix;
-    }
-    if (raw && npix > t.raw_cap) {
-        if (t.d_raw) { HIP_TRY(hipFree(t.d_raw)); t.d_raw = nullptr; }
-        if (t.h_raw) { HIP_TRY(hipHostFree(t.h_raw)); t.h_raw = nullptr; }
-        t.raw_cap = 0;
-        HIP_TRY(hipMalloc(&t.d_raw, sizeof(uint16_t) * round_up(npix, 8) * C));            // every plane starts on 16 bytes
-        HIP_TRY(hipHostMalloc(&t.h_raw, sizeof(uint16_t) * round_up(npix, 8) * C, hipHostMallocDefault));
-        t.raw_cap = npix;
-    }
-    if (blend && npix > t.acc_cap) {
-        if (t.d_acc) { HIP_TRY(hipFree(t.d_acc)); t.d_acc = nullptr; }
-        t.acc_cap = 0;
-        HIP_TRY(hipMalloc(&t.d_acc, sizeof(float) * npix * h->cfg.classes));
-        t.acc_cap = npix;
-    }
-    return 0;
-}
-
-// the launch log of mi_unet_get_kernel_stats for a launch outside the plan: the event pair of launch_plan, algorithmic bytes
-int stat_begin(mi_unet *h, hipStream_t s, hipEvent_t &e1)
-{
-    e1 = nullptr;
-    if (!h->profiling) return 0;
-    while (h->ev_pool.size() < h->ev_used + 2) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        h->ev_pool.push_back(ev);
-    }
-    hipEvent_t e0 = h->ev_pool[h->ev_used++];
-    e1 = h->ev_pool[h->ev_used++];
-    HIP_TRY(hipEventRecord(e0, s));
-    return 0;
-}
-
-int stat_end(mi_unet *h, hipStream_t s, hipEvent_t e1, const char *name, const char *kernel, double bytes)
-{
-    if (!e1) return 0;
-    HIP_TRY(hipEventRecord(e1, s));
-    mi_unet_kernel_stat ks{};
-    snprintf(ks.name, sizeof ks.name, "%s", name);
-    snprintf(ks.kernel, sizeof ks.kernel, "%s", kernel);
-    ks.bytes = bytes;
-    ks.ms = -1.f;
-    h->stats.push_back(ks);
-    return 0;
-}
-
-int check_planes(const mi_unet *h, const uint16_t *const *planes, const char *fn)
-{
-    if (!planes) return fail(MI_UNET_EARG, std::string(fn) + ": null plane list");
-    for (int p = 0; p < h->cfg.in_ch; ++p)
-        if (!planes[p]) return fail(MI_UNET_EARG, std::string(fn) + ": plane " + std::to_string(p) + " is null");
-    return 0;
-}
-
-int run_tiled_call(mi_unet *h, const TiledCall &c)
-{
-    const std::string fn = c.fn;
-    const int th = h->cfg.height, tw = h->cfg.width, C = h->cfg.in_ch, Bm = h->cfg.max_batch, classes = h->cfg.classes;
-    const int H = c.H, W = c.W;
-    if (H < th || W < tw)
-        return fail(MI_UNET_EARG, fn + ": image " + std::to_string(H) + " x " + std::to_string(W) + " is smaller than the engine's tile " +
-                                      std::to_string(th) + " x " + std::to_string(tw));
-    if (c.halo < 0 || 2 * (long long)c.halo >= std::min(th, tw))
-        return fail(MI_UNET_EARG, fn + ": halo " + std::to_string(c.halo) + " must satisfy 0 <= 2 * halo < min(tile height, tile width) = " +
-                                      std::to_string(std::min(th, tw)));
-    if ((long long)H * W > (1ll << 30) || W > (1 << 28))                    // 32-bit byte offsets inside a row of logits
-        return fail(MI_UNET_EARG, fn + ": images of more than 2^30 pixels or wider than 2^28 are not supported");
-    TileGrid g;
-    if (!tile_grid(H, W, th, tw, c.halo, g)) return fail(MI_UNET_EARG, fn + ": illegal tile grid");
-    const size_t npix = (size_t)H * W, thw = (size_t)th * tw;
-    const int nt = g.ny * g.nx;
-    const bool post = c.segment || h->postprocess;
-    // the full-size tail stages borrow the network's scratch buffer: checked before anything is enqueued
-    const size_t scratch = sizeof(float) * h->s_floats;
-    if (post && postprocess_workspace_bytes(1, H, W) > scratch)
-        return fail(MI_UNET_EARG, fn + ": the postprocess workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
-                                      std::to_string(postprocess_workspace_bytes(1, H, W)) + " bytes) exceeds the scratch buffer (" +
-                                      std::to_string(scratch) + " bytes)");
-    if (c.segment && contour_workspace_bytes(1, H, W, c.cap_contours) > scratch)
-        return fail(MI_UNET_EARG, fn + ": the contour workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
-                                      std::to_string(contour_workspace_bytes(1, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
-                                      std::to_string(scratch) + " bytes)");
-    // blending or mirror averaging (mi_unet_set_tile_blend): nv views per tile, view k = t * nv + v, the network's logits
-    // accumulated into t.d_acc, which also returns the blended logits; otherwise the ownership stitch
-    const mi_unet_tile_blend bl = h->blend;
-    const bool blend = bl.mode != MI_UNET_BLEND_OWNER || bl.mirror != 0, owner = bl.mode == MI_UNET_BLEND_OWNER;
-    const int nv = blend ? tile_view_count(bl.mirror) : 1, nk = nt * nv;
-    const float *d_wy = h->d_blend_w, *d_wx = h->d_blend_w ? h->d_blend_w + th : nullptr;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    hipStream_t s = h->stream;
-    if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr && !blend, c.planes != nullptr, blend)) return rc;
-    if (c.segment)
-        if (int rc = grow_contour_buffers(h, 1, c.cap_points, c.cap_contours)) return rc;
-    if (c.planes && !h->d_mnmx) HIP_TRY(hipMalloc(&h->d_mnmx, sizeof(unsigned) * 2 * Bm * C));
-    mi_unet::Tiled &t = h->tiled;
-    // stage boundaries: start | pre | (gather | network + stitch or blend) per micro-batch | postprocess | contours | download
-    const int nmb = (nk + Bm - 1) / Bm;
-    const size_t n_marks = 2 + 2 * (size_t)nmb + 3;
-    while (t.ev.size() < n_marks) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        t.ev.push_back(ev);
-    }
-    size_t mark = 0;
-    hipEvent_t e1 = nullptr;
-    hipError_t e = hipSuccess;
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-
-    // ---- the image onto the device, once
-    if (c.img) {
-        host_copy(h, t.h_img, c.img, npix * C);
-        HIP_TRY(hipMemcpyAsync(t.d_img, t.h_img, npix * C, hipMemcpyHostToDevice, s));
-    } else {
-        const size_t plane_stride = round_up(npix, 8);                       // launch_minmax_u16 / launch_normalise_u16 read 16-byte groups
-        int src_of[4] = {};                        // a caller holding one plane passes its pointer in_ch times: upload and scan it once
-        for (int p = 0; p < C; ++p) {
-            src_of[p] = (p > 0 && c.planes[p] == c.planes[p - 1]) ? src_of[p - 1] : p;
-            const int mn = src_of[p];
-            uint16_t *d_plane = t.d_raw + (size_t)mn * plane_stride;
-            if (mn == p) {
-                hipPointerAttribute_t attr;                    // pinned caller memory is read by the DMA engine directly (as stage_raw16)
-                const bool pinned = hipPointerGetAttributes(&attr, c.planes[p]) == hipSuccess && attr.type == hipMemoryTypeHost;
-                if (!pinned) {
-                    (void)hipGetLastError();
-                    host_copy(h, t.h_raw + (size_t)p * plane_stride, c.planes[p], npix * sizeof(uint16_t));
-                }
-                HIP_TRY(hipMemcpyAsync(d_plane, pinned ? c.planes[p] : t.h_raw + (size_t)p * plane_stride, npix * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                e = launch_minmax_u16(d_plane, npix, h->d_mnmx + 2 * p, s);
-                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": min/max launch: " + hipGetErrorString(e));
-            }
-            if (int rc = stat_begin(h, s, e1)) return rc;
-            e = launch_normalise_u16(d_plane, W, H, h->d_mnmx + 2 * mn, t.d_img + p, C, s);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": normalise launch: " + hipGetErrorString(e));
-            if (int rc = stat_end(h, s, e1, ("tiled.normalise." + std::to_string(p)).c_str(), "normalise_u16", 3.0 * npix)) return rc;
-        }
-    }
-    if (blend) HIP_TRY(hipMemsetAsync(t.d_acc, 0, sizeof(float) * npix * classes, s));
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-
-    // ---- tiles (views) in order, micro-batches of max_batch: gather -> network -> stitch, or -> blend (+ finalize after the last)
-    auto owned_px = [&](int tile) {
-        const int ty = tile / g.nx, tx = tile % g.nx;
-        return (double)(tile_cut(H, th, g.sy, g.ny, ty + 1) - tile_cut(H, th, g.sy, g.ny, ty)) *
-               (tile_cut(W, tw, g.sx, g.nx, tx + 1) - tile_cut(W, tw, g.sx, g.nx, tx));
-    };
-    float *d_tile_logits = (c.logits || blend) ? h->d_logits : nullptr;
-    for (int t0 = 0; t0 < nk; t0 += Bm) {
-        const int nb = std::min(Bm, nk - t0);
-        const std::string tag = "[" + std::to_string(t0) + "," + std::to_string(t0 + nb) + ")";
-        if (int rc = stat_begin(h, s, e1)) return rc;
-        e = nv > 1 ? launch_tile_gather_views(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, bl.mirror, t0, nb, h->d_img, s)
-                   : launch_tile_gather(t.d_img, round_up(npix * C, 4), H, W, C, th, tw, c.halo, t0, nb, h->d_img, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": gather launch: " + hipGetErrorString(e));
-        if (int rc = stat_end(h, s, e1, ("tiled.gather" + tag).c_str(), "tile_gather", 2.0 * nb * thw * C)) return rc;
-        HIP_TRY(hipEventRecord(t.ev[mark++], s));
-        if (int rc = run_microbatch(h, h->d_img, nb, h->d_labels, d_tile_logits)) return rc;
-        if (!blend) {
-            // owned pixels of this micro-batch: read once from the tile results, written once
-            double owned = 0;
-            for (int k = t0; k < t0 + nb; ++k) owned += owned_px(k);
-            if (int rc = stat_begin(h, s, e1)) return rc;
-            e = launch_tile_stitch(h->d_labels, d_tile_logits, classes, H, W, th, tw, c.halo, t0, nb, t.d_labels, c.logits ? t.d_logits : nullptr, s);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": stitch launch: " + hipGetErrorString(e));
-            if (int rc = stat_end(h, s, e1, ("tiled.stitch" + tag).c_str(), "tile_stitch", 2.0 * owned * (1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
-        } else {
-            // per (view, pixel it contributes to): its logits read once, the accumulator read and written once
-            double covered = 0;
-            for (int k = t0; k < t0 + nb; ++k) covered += owner ? owned_px(k / nv) : (double)thw;
-            if (int rc = stat_begin(h, s, e1)) return rc;
-            e = launch_tile_blend(h->d_logits, classes, H, W, th, tw, c.halo, bl.mirror, owner, d_wy, d_wx, t0, nb, t.d_acc, s);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": blend launch: " + hipGetErrorString(e));
-            if (int rc = stat_end(h, s, e1, ("tiled.blend" + tag).c_str(), "tile_blend", 12.0 * classes * covered)) return rc;
-            if (t0 + nb == nk) {
-                if (int rc = stat_begin(h, s, e1)) return rc;
-                e = launch_blend_finalize(t.d_acc, classes, H, W, th, tw, c.halo, bl.mirror, owner, d_wy, d_wx, t.d_labels, c.logits ? t.d_acc : nullptr, s);
-                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": blend finalize launch: " + hipGetErrorString(e));
-                if (int rc = stat_end(h, s, e1, "tiled.finalize", "blend_finalize", (double)npix * (4.0 * classes + 1.0 + (c.logits ? 4.0 * classes : 0.0)))) return rc;
-            }
-        }
-        HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    }
-
-    // ---- the tail, on the stitched image: one image of H x W, never per tile
-    const uint8_t *d_result = t.d_labels;
-    if (post) {
-        const int min_area = static_cast<int>(W * H * 0.06f);                // src/postprocess.cpp:9 (evaluated in float), of the full image
-        e = launch_postprocess_masks(t.d_labels, t.d_labels, 1, H, W, min_area, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
-    }
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    if (c.segment) {
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)c.cap_points * 2, *d_count = d_start + (c.cap_contours + 1);
-        e = launch_mask_to_image(t.d_labels, t.d_vis, npix, s);
-        if (e == hipSuccess) e = launch_extract_contours(t.d_vis, 1, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": segment launch: " + hipGetErrorString(e));
-        d_result = t.d_vis;
-    }
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    HIP_TRY(hipMemcpyAsync(t.h_out, d_result, npix, hipMemcpyDeviceToHost, s));
-    if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
-    if (c.segment)
-        if (int rc = contours_to_pinned(h, 1, c.cap_points, c.cap_contours)) return rc;
-    if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, blend ? t.d_acc : t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    host_copy(h, c.out_u8, t.h_out, npix);
-    if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
-    if (c.segment) contours_to_caller(h, 1, c.cap_points, c.cap_contours, c.xy, c.start, c.count);
-
-    for (float &m : h->stage_ms) m = 0.f;
-    auto span = [&](size_t a, size_t b, int stage) -> int {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, t.ev[a], t.ev[b]));
-        h->stage_ms[stage] += ms;
-        return 0;
-    };
-    if (int rc = span(0, 1, MI_UNET_STAGE_UPLOAD_PRE)) return rc;
-    for (int k = 0; k < nmb; ++k) {
-        if (int rc = span(1 + 2 * (size_t)k, 2 + 2 * (size_t)k, MI_UNET_STAGE_UPLOAD_PRE)) return rc;
-        if (int rc = span(2 + 2 * (size_t)k, 3 + 2 * (size_t)k, MI_UNET_STAGE_NETWORK)) return rc;
-    }
-    const size_t m0 = 1 + 2 * (size_t)nmb;
-    if (int rc = span(m0, m0 + 1, MI_UNET_STAGE_POSTPROCESS)) return rc;
-    if (int rc = span(m0 + 1, m0 + 2, MI_UNET_STAGE_CONTOURS)) return rc;
-    return span(m0 + 2, m0 + 3, MI_UNET_STAGE_DOWNLOAD);
-}
-
-}  // namespace
-
-extern "C" {
-
-int mi_unet_infer_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
-                        uint8_t *tiles, uint8_t *labels, float *logits)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (!raws || !widths || !heights || !labels || B < 0) return fail(MI_UNET_EARG, "mi_unet_infer_raw16: bad argument");
-    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, labels, logits, false, nullptr, 0, nullptr, 0, nullptr });
-}
-
-int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
-                          uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
-                          int32_t *counts)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_raw16: bad argument");
-    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts });
-}
-
-int mi_unet_tile_axis(int L, int T, int halo, int *origins, int *cuts) { return tile_axis(L, T, halo, origins, cuts); }
-
-int mi_unet_tile_blend_weights(int T, const mi_unet_tile_blend *b, float *w)
-{
-    if (T < 1 || !b || !w) return fail(MI_UNET_EARG, "mi_unet_tile_blend_weights: T < 1 or a null pointer");
-    if (b->mode < MI_UNET_BLEND_OWNER || b->mode > MI_UNET_BLEND_GAUSSIAN)
-        return fail(MI_UNET_EARG, "tile blend: unknown mode " + std::to_string(b->mode));
-    if (b->mirror < 0 || b->mirror > (MI_UNET_MIRROR_X | MI_UNET_MIRROR_Y))
-        return fail(MI_UNET_EARG, "tile blend: mirror " + std::to_string(b->mirror) + " is outside 0..3");
-    if (b->mode == MI_UNET_BLEND_GAUSSIAN && !(std::isfinite(b->sigma_scale) && b->sigma_scale > 0.f))
-        return fail(MI_UNET_EARG, "tile blend: the Gaussian needs a finite sigma_scale > 0");
-    // the definition of include/mi_unet.h: double, one rounding to float; i - c is exact, so w(i) == w(T - 1 - i)
-    const double c = (T - 1) / 2.0, s = (double)b->sigma_scale * T;
-    for (int i = 0; i < T; ++i) {
-        const double d = i - c;
-        w[i] = b->mode == MI_UNET_BLEND_GAUSSIAN ? (float)std::max(std::exp(-(d * d) / (2.0 * s * s)), 0x1p-20) : 1.f;
-    }
-    return MI_UNET_OK;
-}
-
-int mi_unet_set_tile_blend(mi_unet_t *h, const mi_unet_tile_blend *b)
-{
-    if (int rc = check_handle(h, false)) return rc;
-    const mi_unet_tile_blend def{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
-    const mi_unet_tile_blend nb = b ? *b : def;
-    const int th = h->cfg.height, tw = h->cfg.width;
-    std::vector<float> tab((size_t)th + tw);
-    if (int rc = mi_unet_tile_blend_weights(th, &nb, tab.data())) return rc;
-    if (int rc = mi_unet_tile_blend_weights(tw, &nb, tab.data() + th)) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    if (!h->d_blend_w) HIP_TRY(hipMalloc(&h->d_blend_w, sizeof(float) * tab.size()));
-    HIP_TRY(hipStreamSynchronize(h->stream));                            // no call of this handle still reads the old tables
-    HIP_TRY(hipMemcpy(h->d_blend_w, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    h->blend = nb;
-    return MI_UNET_OK;
-}
-
-int mi_unet_get_tile_blend(const mi_unet_t *h, mi_unet_tile_blend *b)
-{
-    if (!h || !b) return fail(MI_UNET_EARG, "mi_unet_get_tile_blend: null argument");
-    *b = h->blend;
-    return MI_UNET_OK;
-}
-
-int mi_unet_infer_tiled_u8(mi_unet_t *h, const uint8_t *img, int H, int W, int halo, uint8_t *labels, float *logits)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (!img || !labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_u8: null image or label buffer");
-    const TiledCall c{ "mi_unet_infer_tiled_u8", img, nullptr, H, W, halo, nullptr, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
-    return run_tiled_call(h, c);
-}
-
-int mi_unet_infer_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *labels,
-                              float *logits)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (int rc = check_planes(h, planes, "mi_unet_infer_tiled_raw16")) return rc;
-    if (!labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_raw16: null label buffer");
-    const TiledCall c{ "mi_unet_infer_tiled_raw16", nullptr, planes, H, W, halo, norm, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
-    return run_tiled_call(h, c);
-}
-
-int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
-                                int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (int rc = check_planes(h, planes, "mi_unet_segment_tiled_raw16")) return rc;
-    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16: null output buffer or non-positive capacity");
-    const TiledCall c{ "mi_unet_segment_tiled_raw16", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count };
-    return run_tiled_call(h, c);
-}
-
 int mi_unet_host_alloc(size_t bytes, void **p)
 {
     if (!p || bytes == 0) return fail(MI_UNET_EARG, "mi_unet_host_alloc: bad argument");
@@ -2076,13 +618,6 @@ int mi_unet_host_alloc(size_t bytes, void **p)
 void mi_unet_host_free(void *p)
 {
     if (p) (void)hipHostFree(p);
-}
-
-int mi_unet_last_stage_ms(const mi_unet_t *h, float *ms)
-{
-    if (!h || !ms) return fail(MI_UNET_EARG, "mi_unet_last_stage_ms: null argument");
-    for (int i = 0; i < MI_UNET_N_STAGES; ++i) ms[i] = h->stage_ms[i];
-    return MI_UNET_OK;
 }
 
 int mi_unet_set_stream(mi_unet_t *h, void *hip_stream)
@@ -2137,216 +672,6 @@ int mi_unet_get_kernel_stats(mi_unet_t *h, mi_unet_kernel_stat *stats, int cap, 
     return MI_UNET_OK;
 }
 
-namespace {
-
-// mi_unet_layer_debug's ops: each runs one route -- or, for "conv3x3_wino4", the F(4x4,3x3) family as route_wino4 picks it --
-// on weights packed for it.  lp: the operands are 0 fp32, 1 bf16, 2 fp16.
-enum class Pack { NONE, FIRST, MFMA, MFMA_T, TAPS, WINO, WINO16, WINO4, LP, LP_T, UP };
-struct DebugOp { const char *op; Route route; Pack pack; int lp; bool routed; };
-const DebugOp kDebugOps[] = {
-    { "conv3x3", Route::CONV_MFMA, Pack::MFMA, 0, false },         { "convT2x2", Route::CONVT_MFMA, Pack::MFMA_T, 0, false },
-    { "convT2x2_taps", Route::CONVT_TAPS, Pack::TAPS, 0, false },   { "conv3x3_wino", Route::CONV_WINO, Pack::WINO, 0, false },
-    { "conv3x3_wino16", Route::CONV_WINO16, Pack::WINO16, 0, false }, { "conv3x3_wino4", Route::CONV_WINO4, Pack::WINO4, 0, true },
-    { "conv3x3_wino4s", Route::CONV_WINO4S, Pack::WINO4, 0, false }, { "conv3x3_wino4a", Route::CONV_WINO4A, Pack::WINO4, 0, false },
-    { "conv3x3_wino4b", Route::CONV_WINO4B, Pack::WINO4, 0, false },
-    { "conv3x3_bf16", Route::CONV_BF16, Pack::LP, 1, false },       { "conv3x3_fp16", Route::CONV_FP16, Pack::LP, 2, false },
-    { "conv3x3_bf16w", Route::CONV_BF16W, Pack::LP, 1, false },     { "conv3x3_fp16w", Route::CONV_FP16W, Pack::LP, 2, false },
-    { "conv3x3_bf16r", Route::CONV_BF16R, Pack::LP, 1, false },     { "conv3x3_fp16r", Route::CONV_FP16R, Pack::LP, 2, false },
-    { "conv3x3_bf16k", Route::CONV_BF16K, Pack::LP, 1, false },     { "conv3x3_fp16k", Route::CONV_FP16K, Pack::LP, 2, false },
-    { "convT2x2_bf16", Route::CONVT_BF16, Pack::LP_T, 1, false },   { "convT2x2_fp16", Route::CONVT_FP16, Pack::LP_T, 2, false },
-    { "convT2x2_bf16r", Route::CONVT_BF16R, Pack::LP_T, 1, false }, { "convT2x2_fp16r", Route::CONVT_FP16R, Pack::LP_T, 2, false },
-    { "conv3x3_first", Route::FIRST, Pack::FIRST, 0, false },        { "conv3x3_first_bf16", Route::FIRST, Pack::FIRST, 1, false },
-    { "conv3x3_first_fp16", Route::FIRST, Pack::FIRST, 2, false },   { "maxpool", Route::POOL, Pack::NONE, 0, false },
-    { "upsample2x", Route::UPSAMPLE, Pack::UP, 0, false },           { "upsample2x_bf16", Route::UPSAMPLE, Pack::UP, 1, false },
-    { "upsample2x_fp16", Route::UPSAMPLE, Pack::UP, 2, false },
-};
-
-}  // namespace
-
-int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
-                        const float *scale, const float *shift, int Cout, int relu, float *out)
-{
-    if (!op || !in || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(MI_UNET_EARG, "layer_debug: bad argument");
-    if (mi_unet_device_count() <= 0) return fail(MI_UNET_ENODEVICE, "no HIP device visible: libmiunet has no CPU fallback");
-    HIP_TRY(hipSetDevice(device));
-    std::string o(op);
-    bool lp_out = false;
-    if (o.size() > 6 && o.compare(o.size() - 6, 6, "_lpout") == 0) { lp_out = true; o.resize(o.size() - 6); }
-    bool want_pool = false;                    // "<conv op>_pool": return the fused 2x2 max-pooled tensor [B][H/2][W/2][Cout] instead
-    if (o.size() > 5 && o.compare(o.size() - 5, 5, "_pool") == 0) { want_pool = true; o.resize(o.size() - 5); }
-    float *d_pool = nullptr;
-    const size_t in_n = (size_t)B * H * W * Cin;
-    const DebugOp *dop = nullptr;
-    for (const DebugOp &k : kDebugOps)
-        if (o == k.op) dop = &k;
-    if (!dop) return fail(MI_UNET_EARG, "layer_debug: unknown op " + o);
-    const Routing rt = Routing::from_env();
-    if (dop->pack == Pack::UP) {
-        // bilinear x2: in [B][H][W][Cin] -> out [B][2H][2W][Cin]; _bf16 / _fp16 round the input to 16 bits first (RNE) and
-        // return the 16-bit output converted back
-        if (Cin % 16 || want_pool || lp_out) return fail(MI_UNET_EARG, "layer_debug: upsample2x needs Cin % 16 == 0");
-        const int kind = dop->lp;
-        const size_t es = kind ? 2 : 4, out_n = in_n * 4;
-        std::vector<uint16_t> io16(kind ? std::max(in_n, out_n) : 0);
-        if (kind)
-            for (size_t i = 0; i < in_n; ++i) io16[i] = kind == 2 ? fp16_bits(in[i]) : bf16_bits(in[i]);
-        void *d_i = nullptr, *d_o = nullptr;
-        int rc1 = MI_UNET_OK;
-        auto ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc1 == MI_UNET_OK) rc1 = fail(MI_UNET_EHIP, std::string(what) + ": " + hipGetErrorString(e)); return rc1 == MI_UNET_OK; };
-        if (ok(hipMalloc(&d_i, es * in_n), "hipMalloc") && ok(hipMalloc(&d_o, es * out_n), "hipMalloc") &&
-            ok(hipMemcpy(d_i, kind ? static_cast<const void *>(io16.data()) : static_cast<const void *>(in), es * in_n, hipMemcpyHostToDevice), "hipMemcpy") &&
-            ok(hipMemset(d_o, 0xFF, es * out_n), "hipMemset") &&                  // NaN poison: unwritten outputs are visible
-            ok(launch_upsample2x_bilinear(d_i, Cin, d_o, Cin, 0, B, H, W, Cin, kind, rt, nullptr), "launch_upsample2x_bilinear") &&
-            ok(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
-            if (kind == 0) {
-                ok(hipMemcpy(out, d_o, es * out_n, hipMemcpyDeviceToHost), "hipMemcpy");
-            } else if (ok(hipMemcpy(io16.data(), d_o, es * out_n, hipMemcpyDeviceToHost), "hipMemcpy")) {
-                for (size_t i = 0; i < out_n; ++i) out[i] = kind == 2 ? fp16_to_float(io16[i]) : bf16_to_float(io16[i]);
-            }
-        }
-        if (d_i) (void)hipFree(d_i);
-        if (d_o) (void)hipFree(d_o);
-        return rc1;
-    }
-    if (dop->pack == Pack::FIRST) {
-        // the first layer: `in` holds byte values 0..255 (as floats), the kernel sees the u8 image and the /255 table;
-        // _bf16 / _fp16: the 16-bit pipelines' output tensor (converted back to float here)
-        if (!w || Cout <= 0 || Cout % 4 || (Cin != 1 && Cin != 3) || want_pool || lp_out) return fail(MI_UNET_EARG, "layer_debug: conv3x3_first needs weights, Cin 1 or 3, Cout % 4 == 0");
-        const int kind = dop->lp;
-        std::vector<uint8_t> img(in_n);
-        for (size_t i = 0; i < in_n; ++i) img[i] = (uint8_t)in[i];
-        float lut[256];
-        for (int i = 0; i < 256; ++i) lut[i] = static_cast<float>(i) / 255.0f;
-        std::vector<float> wf((size_t)9 * Cin * Cout), sh(Cout);
-        for (int co = 0; co < Cout; ++co) {
-            sh[co] = shift ? shift[co] : 0.f;
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int t = 0; t < 9; ++t)
-                    wf[((size_t)t * Cin + ci) * Cout + co] = (float)((double)w[((size_t)co * Cin + ci) * 9 + t] * (scale ? (double)scale[co] : 1.0));
-        }
-        const size_t n_out = (size_t)B * H * W * Cout;
-        uint8_t *d_img = nullptr; float *d_l = nullptr, *d_wf = nullptr, *d_sh = nullptr, *d_o = nullptr;
-        int rc1 = MI_UNET_OK;
-        hipError_t e1 = hipSuccess;
-        auto ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc1 == MI_UNET_OK) { e1 = e; rc1 = fail(MI_UNET_EHIP, std::string(what) + ": " + hipGetErrorString(e)); } return rc1 == MI_UNET_OK; };
-        if (ok(hipMalloc(&d_img, in_n), "hipMalloc") && ok(hipMalloc(&d_l, sizeof lut), "hipMalloc") && ok(hipMalloc(&d_wf, sizeof(float) * wf.size()), "hipMalloc") &&
-            ok(hipMalloc(&d_sh, sizeof(float) * Cout), "hipMalloc") && ok(hipMalloc(&d_o, sizeof(float) * n_out), "hipMalloc") &&
-            ok(hipMemcpy(d_img, img.data(), in_n, hipMemcpyHostToDevice), "hipMemcpy") && ok(hipMemcpy(d_l, lut, sizeof lut, hipMemcpyHostToDevice), "hipMemcpy") &&
-            ok(hipMemcpy(d_wf, wf.data(), sizeof(float) * wf.size(), hipMemcpyHostToDevice), "hipMemcpy") &&
-            ok(hipMemcpy(d_sh, sh.data(), sizeof(float) * Cout, hipMemcpyHostToDevice), "hipMemcpy") &&
-            ok(hipMemset(d_o, 0xFF, sizeof(float) * n_out), "hipMemset") &&
-            ok(launch_conv3x3_first(d_img, d_l, d_wf, d_sh, d_o, B, H, W, Cin, Cout, Cout, kind, rt, nullptr), "launch_conv3x3_first") &&
-            ok(hipDeviceSynchronize(), "hipDeviceSynchronize")) {
-            if (kind == 0) {
-                ok(hipMemcpy(out, d_o, sizeof(float) * n_out, hipMemcpyDeviceToHost), "hipMemcpy");
-            } else {
-                std::vector<uint16_t> o16(n_out);
-                if (ok(hipMemcpy(o16.data(), d_o, sizeof(uint16_t) * n_out, hipMemcpyDeviceToHost), "hipMemcpy"))
-                    for (size_t i = 0; i < n_out; ++i) out[i] = kind == 2 ? fp16_to_float(o16[i]) : bf16_to_float(o16[i]);
-            }
-        }
-        (void)e1;
-        void *fr[] = { d_img, d_l, d_wf, d_sh, d_o };
-        for (void *p : fr) if (p) (void)hipFree(p);
-        return rc1;
-    }
-    float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr;
-    std::vector<float> wpk, bias;
-    const bool T = dop->pack == Pack::MFMA_T || dop->pack == Pack::TAPS || dop->pack == Pack::LP_T;
-    size_t out_n = dop->pack == Pack::NONE ? (size_t)B * (H / 2) * (W / 2) * Cin : (size_t)B * (T ? 4 : 1) * H * W * Cout;
-    ConvArgs a{};
-    a.rt = rt;
-    if (dop->pack == Pack::NONE) {
-        if (Cin % 4 || H % 2 || W % 2) return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 and even H, W");
-    } else if (dop->lp) {
-        if (!w || Cout <= 0 || Cin % 8) return fail(MI_UNET_EARG, "layer_debug: 16-bit conv needs weights and Cin % 8 == 0");
-    } else if (!w || Cout <= 0 || Cin % 4) {
-        return fail(MI_UNET_EARG, "layer_debug: conv needs weights and Cin % 4 == 0");
-    }
-    if (dop->pack != Pack::NONE) {
-        std::vector<double> sc(Cout, 1.0);
-        bias.assign(Cout, 0.f);
-        for (int co = 0; co < Cout; ++co) { bias[co] = shift ? shift[co] : 0.f; if (scale) sc[co] = scale[co]; }
-        size_t npad = round_up(T ? (size_t)4 * Cout : (size_t)Cout, NPAD);
-        const lp_cvt_fn cvt = dop->lp == 2 ? fp16_bits : bf16_bits;
-        switch (dop->pack) {
-        case Pack::MFMA: wpk.assign((size_t)((Cin + KC - 1) / KC) * 9 * npad * KC, 0.f); pack_conv_mfma(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
-        case Pack::MFMA_T: wpk.assign((size_t)((Cin + KC - 1) / KC) * npad * KC, 0.f); pack_convT_mfma(w, Cin, Cout, wpk.data(), npad); break;
-        case Pack::TAPS:
-            npad = convT_taps_cpad(Cout);
-            wpk.assign(convT_taps_floats(Cin, Cout), 0.f);
-            pack_convT_taps(w, Cin, Cout, wpk.data());
-            break;
-        case Pack::WINO: wpk.assign((size_t)((Cin + WINO_KC - 1) / WINO_KC) * 16 * npad * WINO_KC, 0.f); pack_wino(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
-        case Pack::WINO16: wpk.assign((size_t)((Cin + WINO_KC - 1) / WINO_KC) * 16 * npad * WINO_KC, 0.f); pack_wino16(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
-        case Pack::WINO4: wpk.assign((size_t)((Cin + WINO4_KC - 1) / WINO4_KC) * 36 * npad * WINO4_KC, 0.f); pack_wino4(w, sc.data(), Cin, Cout, wpk.data(), npad); break;
-        case Pack::LP:
-            wpk.assign(((size_t)((Cin + KC_BF16 - 1) / KC_BF16) * 9 * npad * KC_BF16 + 1) / 2, 0.f);
-            pack_conv_bf16(w, sc.data(), Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
-            break;
-        case Pack::LP_T:
-            wpk.assign(((size_t)((Cin + KC_BF16 - 1) / KC_BF16) * npad * KC_BF16 + 1) / 2, 0.f);
-            pack_convT_bf16(w, Cin, Cout, reinterpret_cast<uint16_t *>(wpk.data()), npad, cvt);
-            break;
-        default: break;
-        }
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)npad; a.ldo = Cout; a.co_off = 0;
-        a.relu = relu;
-    }
-    const bool lp_in = dop->lp != 0;
-    const bool lp_fp16 = dop->lp == 2;
-    if (lp_out && !lp_in) return fail(MI_UNET_EARG, "layer_debug: _lpout is for the 16-bit conv ops");
-    a.out_lp = lp_out ? 1 : 0;
-    int rc = MI_UNET_OK;
-    hipError_t e = hipSuccess;
-#define DBG_TRY(expr) do { e = (expr); if (e != hipSuccess) { rc = fail(MI_UNET_EHIP, std::string(#expr) + ": " + hipGetErrorString(e)); goto done; } } while (0)
-    DBG_TRY(hipMalloc(&d_in, sizeof(float) * in_n));
-    DBG_TRY(hipMalloc(&d_out, sizeof(float) * out_n));
-    if (lp_in) {                                                 // the 16-bit kernels read 16-bit activations: round here (RNE)
-        std::vector<uint16_t> in16(in_n);
-        const lp_cvt_fn cvt = lp_fp16 ? fp16_bits : bf16_bits;
-        for (size_t i = 0; i < in_n; ++i) in16[i] = cvt(in[i]);
-        DBG_TRY(hipMemcpy(d_in, in16.data(), sizeof(uint16_t) * in_n, hipMemcpyHostToDevice));
-    } else {
-        DBG_TRY(hipMemcpy(d_in, in, sizeof(float) * in_n, hipMemcpyHostToDevice));
-    }
-    DBG_TRY(hipMemset(d_out, 0xFF, sizeof(float) * out_n));      // NaN poison: unwritten outputs are visible
-    if (want_pool) {
-        if (wpk.empty() || (H & 1) || (W & 1) || out_n != (size_t)B * H * W * Cout) { rc = fail(MI_UNET_EARG, "layer_debug: _pool is for the conv3x3 ops on even sizes"); goto done; }
-        DBG_TRY(hipMalloc(&d_pool, sizeof(float) * out_n / 4));
-        DBG_TRY(hipMemset(d_pool, 0xFF, sizeof(float) * out_n / 4));
-        a.pool_out = d_pool; a.pool_ld = Cout;
-    }
-    if (!wpk.empty()) {
-        DBG_TRY(hipMalloc(&d_w, sizeof(float) * wpk.size()));
-        DBG_TRY(hipMalloc(&d_b, sizeof(float) * bias.size()));
-        DBG_TRY(hipMemcpy(d_w, wpk.data(), sizeof(float) * wpk.size(), hipMemcpyHostToDevice));
-        DBG_TRY(hipMemcpy(d_b, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
-        a.in = d_in; a.wpk = d_w; a.bias = d_b; a.out = d_out;
-        if (dop->pack == Pack::WINO4 || dop->pack == Pack::TAPS) a.wpk4 = d_w;
-        DBG_TRY(launch_route(dop->routed ? route_wino4(a) : dop->route, a, nullptr));
-    } else {
-        DBG_TRY(launch_maxpool2x2(d_in, Cin, d_out, B, H, W, Cin, nullptr));
-    }
-    DBG_TRY(hipDeviceSynchronize());
-    if (want_pool) { std::swap(d_out, d_pool); out_n /= 4; }
-    if (lp_out) {
-        std::vector<uint16_t> out16(out_n);
-        DBG_TRY(hipMemcpy(out16.data(), d_out, sizeof(uint16_t) * out_n, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < out_n; ++i) out[i] = lp_fp16 ? fp16_to_float(out16[i]) : bf16_to_float(out16[i]);
-    } else {
-        DBG_TRY(hipMemcpy(out, d_out, sizeof(float) * out_n, hipMemcpyDeviceToHost));
-    }
-#undef DBG_TRY
-done:
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pool) (void)hipFree(d_pool);
-    if (d_w) (void)hipFree(d_w);
-    if (d_b) (void)hipFree(d_b);
-    return rc;
-}
-
 const char *mi_unet_numeric_guard(const mi_unet_t *h, int *tripped, float *diff)
 {
     if (!h) return "";
@@ -2355,104 +680,16 @@ const char *mi_unet_numeric_guard(const mi_unet_t *h, int *tripped, float *diff)
     return h->guard_text.c_str();
 }
 
-int mi_unet_debug_layer_count(const mi_unet_t *h) { return h ? (int)h->plan.size() : 0; }
-
-int mi_unet_debug_layer_info(const mi_unet_t *h, int layer, mi_unet_layer_info *info)
-{
-    if (!h || !info) return fail(MI_UNET_EARG, "mi_unet_debug_layer_info: null argument");
-    if (!h->weights_loaded) return fail(MI_UNET_ESTATE, "Engine not initialized: load weights before inference");
-    if (layer < 0 || layer >= (int)h->plan.size()) return fail(MI_UNET_EARG, "mi_unet_debug_layer_info: no such layer");
-    const Step &st = h->plan[layer];
-    *info = mi_unet_layer_info{};
-    snprintf(info->name, sizeof info->name, "%s", st.name.c_str());
-    switch (st.kind) {
-    case Step::FIRST: info->kind = 0; info->in_h = info->out_h = st.H; info->in_w = info->out_w = st.W; info->in_c = st.C; info->out_c = st.Cout; break;
-    case Step::CONV: info->kind = 1; info->in_h = info->out_h = st.a.H; info->in_w = info->out_w = st.a.W; info->in_c = st.a.Cin; info->out_c = st.a.Cout; break;
-    case Step::CONVT: info->kind = 2; info->in_h = st.a.H; info->in_w = st.a.W; info->out_h = 2 * st.a.H; info->out_w = 2 * st.a.W; info->in_c = st.a.Cin; info->out_c = st.a.Cout; break;
-    case Step::POOL: info->kind = 3; info->in_h = st.H; info->in_w = st.W; info->out_h = st.H / 2; info->out_w = st.W / 2; info->in_c = info->out_c = st.C; break;
-    case Step::HEAD: info->kind = 4; info->in_h = info->out_h = st.H; info->in_w = info->out_w = st.W; info->in_c = st.C; info->out_c = st.Cout; break;
-    case Step::UPSAMPLE: info->kind = 5; info->in_h = st.H; info->in_w = st.W; info->out_h = 2 * st.H; info->out_w = 2 * st.W; info->in_c = info->out_c = st.C; break;
-    }
-    return MI_UNET_OK;
-}
-
-int mi_unet_debug_capture(mi_unet_t *h, const uint8_t *imgs, int B, int layer, int img, float *in, float *out, float *pooled,
-                          uint8_t *labels, mi_unet_layer_info *info)
-{
-    if (int rc = check_handle(h, true)) return rc;
-    if (!imgs || !info || B < 1 || B > h->cfg.max_batch || img < 0 || img >= B)
-        return fail(MI_UNET_EARG, "mi_unet_debug_capture: bad argument (1 <= B <= max_batch, 0 <= img < B)");
-    if (int rc = mi_unet_debug_layer_info(h, layer, info)) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    const size_t in_bytes = (size_t)B * h->cfg.height * h->cfg.width * h->cfg.in_ch;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->d_img, imgs, in_bytes, hipMemcpyHostToDevice));
-    h->tap = mi_unet::Tap{};
-    h->tap.layer = layer; h->tap.img = img; h->tap.in = in; h->tap.out = out; h->tap.pooled = pooled; h->tap.labels = labels; h->tap.info = info;
-    const int rc = launch_plan(h, h->d_img, B, h->d_labels, h->d_logits);       // eager: the kernels a batch of B takes
-    const bool hit = h->tap.hit;
-    h->tap = mi_unet::Tap{};
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc) return rc;
-    if (es != hipSuccess) return fail(MI_UNET_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
-    if (!hit) return fail(MI_UNET_ESTATE, "mi_unet_debug_capture: the plan never reached the layer");
-    return MI_UNET_OK;
-}
-
+// The handle's buffers and events free themselves (engine_handle.h); what is left has an order: no stream of the handle may still
+// be working when they go, and the graph executables go before the stream they were captured on.
 void mi_unet_destroy(mi_unet_t *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    for (int i = 0; i < 8; ++i)
-        if (h->d_cat[i]) (void)hipFree(h->d_cat[i]);
-    void *dev[] = { h->d_lut, h->d_s0, h->d_s1, h->d_img, h->d_labels, h->d_logits, h->d_raw[0], h->d_raw[1], h->d_raw[2], h->d_mnmx, h->d_cont, h->d_ksplit };
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (h->h_img) (void)hipHostFree(h->h_img);
-    if (h->h_labels) (void)hipHostFree(h->h_labels);
-    if (h->h_cont) (void)hipHostFree(h->h_cont);
-    if (h->h_labels2) (void)hipHostFree(h->h_labels2);
-    if (h->tail_stream) { (void)hipStreamSynchronize(h->tail_stream); (void)hipStreamDestroy(h->tail_stream); }
-    if (h->dl_stream) { (void)hipStreamSynchronize(h->dl_stream); (void)hipStreamDestroy(h->dl_stream); }
-    for (hipEvent_t e : h->tiles_done)
-        if (e) (void)hipEventDestroy(e);
-    void *tail_dev[] = { h->d_tail_ws, h->d_tail_vis, h->d_labels2 };
-    for (void *q : tail_dev)
-        if (q) (void)hipFree(q);
-    for (int i = 0; i < 2; ++i) {
-        if (h->net_done[i]) (void)hipEventDestroy(h->net_done[i]);
-        for (hipEvent_t e : h->tail_ev[i])
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (int i = 0; i < 3; ++i)
-        for (hipEvent_t e : h->pre_ev[i])
-            if (e) (void)hipEventDestroy(e);
-    if (h->d_img2) (void)hipFree(h->d_img2);
-    if (h->pre_stream) { (void)hipStreamSynchronize(h->pre_stream); (void)hipStreamDestroy(h->pre_stream); }
-    for (int i = 0; i < 2; ++i) {
-        if (h->h_tiles[i]) (void)hipHostFree(h->h_tiles[i]);
-        hipEvent_t evs2[] = { h->tile_ready[i], h->out_done[i] };
-        for (hipEvent_t e : evs2)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->stage_ev[i])
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (int r = 0; r < mi_unet::RAW_RING; ++r) {
-        if (h->h_raw[r]) (void)hipHostFree(h->h_raw[r]);
-        if (h->raw_done[r]) (void)hipEventDestroy(h->raw_done[r]);
-    }
-    void *tiled_dev[] = { h->tiled.d_img, h->tiled.d_labels, h->tiled.d_vis, h->tiled.d_logits, h->tiled.d_raw, h->tiled.d_acc, h->d_blend_w };
-    for (void *q : tiled_dev)
-        if (q) (void)hipFree(q);
-    void *tiled_host[] = { h->tiled.h_img, h->tiled.h_out, h->tiled.h_raw };
-    for (void *q : tiled_host)
-        if (q) (void)hipHostFree(q);
-    for (hipEvent_t e : h->tiled.ev) (void)hipEventDestroy(e);
-    hipEvent_t evs[] = { h->tev0, h->tev1 };
-    for (hipEvent_t e : evs)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
+    for (hipStream_t q : { h->own_stream, h->tail_stream, h->dl_stream, h->pre_stream })
+        if (q) (void)hipStreamSynchronize(q);
+    for (hipStream_t q : { h->tail_stream, h->dl_stream, h->pre_stream })
+        if (q) (void)hipStreamDestroy(q);
     for (auto &g : h->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);

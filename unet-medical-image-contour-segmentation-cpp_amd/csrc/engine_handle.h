@@ -1,0 +1,205 @@
+// engine_handle.h -- struct mi_unet and what the units that implement include/mi_unet.h share: engine.cpp (create / destroy, weights,
+// launch_plan, the u8 entry points), pipeline_raw.cpp, pipeline_tiled.cpp and debug.cpp.  Internal to libmiunet.so.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/mi_unet.h"
+#include "copy_pool.h"
+#include "engine_internal.h"
+#include "kernels.h"
+#include "plan.h"
+#include "routing.h"
+
+namespace miunet {
+
+inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
+
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e__ = (expr);                                                                               \
+        if (e__ != hipSuccess)                                                                                 \
+            return fail(MI_UNET_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));                    \
+    } while (0)
+
+// Owning device (hipMalloc) or pinned host (hipHostMalloc, hipHostMallocDefault) buffer of `n` elements: reset(n) frees what it
+// held and allocates anew (0 = only free); the destructor frees.  The caller synchronises whatever may still use the old memory.
+template <class T, bool PINNED>
+struct Buffer {
+    T *p = nullptr;
+    Buffer() = default;
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { (void)reset(0); }
+    hipError_t reset(size_t n)
+    {
+        hipError_t e = !p ? hipSuccess : PINNED ? hipHostFree(p) : hipFree(p);
+        p = nullptr;
+        if (e == hipSuccess && n) e = PINNED ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T));
+        return e;
+    }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
+template <class T> using DeviceBuf = Buffer<T, false>;
+template <class T> using PinnedBuf = Buffer<T, true>;
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t reset(unsigned flags = hipEventDefault)
+    {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+        return hipEventCreateWithFlags(&e, flags);
+    }
+    hipEvent_t get() const { return e; }
+    operator hipEvent_t() const { return e; }
+};
+
+}  // namespace miunet
+
+struct mi_unet {
+    mi_unet_config cfg{};
+    int ch[8]{};
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    bool weights_loaded = false;
+    int algo = MI_UNET_CONV_DIRECT; // resolved conv3x3 algorithm (MI_UNET_CONV_DIRECT / _WINOGRAD / _WINOGRAD16)
+    bool fuse_pool = true;          // MIUNET_FUSE_POOL=0 keeps the stand-alone pooling kernel (A/B and parity checks)
+    bool fuse_head = true;          // MIUNET_FUSE_HEAD=0 keeps the stand-alone head kernel
+    int wino4_min_wg = 256;         // MIUNET_WINO4_MIN_WG: smallest grid the F(4x4,3x3) kernel takes (else F(2x2) + split-K)
+    miunet::Routing routing;        // kernel-routing switches + CU count, resolved at create (kernels.h)
+    // numeric guard of the default fp32 plan (engine_calibrate): F(4x4,3x3) is kept only if, for THIS weight set, a probe tile's
+    // logits agree with the F(2x2,3x3) plan's within `guard_limit`; otherwise every layer runs F(2x2,3x3)
+    bool wino4_guard_tripped = false;
+    float guard_diff = -1.f, guard_limit = 5e-4f;
+    std::string guard_text = "numeric guard: not run (no weights, or not the default fp32 plan)";
+    // device memory
+    // one blob: every packed tensor (single allocation -> one broadcast / one free).  Owned by `weights`, which clones of
+    // this handle share (mi_unet_clone: the reference's engine is shared by its per-thread contexts, src/process.cpp:15, :69)
+    std::shared_ptr<miunet::DeviceWeights> weights;
+    float *d_weights = nullptr;     // = weights->d
+    size_t weight_floats = 0;
+    miunet::DeviceBuf<float> d_lut;         // 256 floats: i / 255.0f
+    miunet::DeviceBuf<float> d_cat[8];      // concat buffers [Bm][h_i][w_i][2*ch_i]
+    miunet::DeviceBuf<float> d_s0, d_s1;
+    size_t cat_floats[8]{}, s_floats = 0;   // their sizes (build_plan checks every step's tensors against them)
+    miunet::DeviceBuf<uint8_t> d_img;       // staging for the host-buffer entry point
+    miunet::DeviceBuf<uint8_t> d_labels;
+    miunet::DeviceBuf<float> d_logits;
+    // RAW16 staging for mi_unet_infer_raw16: a ring of (pinned host, device) buffer pairs, grown on demand, so the host copy
+    // of image i+1 into its pinned buffer overlaps the PCIe transfer and the preprocessing kernels of image i
+    static constexpr int RAW_RING = 3;
+    miunet::DeviceBuf<uint16_t> d_raw[RAW_RING];
+    miunet::PinnedBuf<uint16_t> h_raw[RAW_RING];
+    miunet::Event raw_done[RAW_RING];       // the slot's transfer and kernels have completed
+    bool raw_busy[RAW_RING] = {};
+    size_t raw_cap = 0;             // samples per slot
+    miunet::DeviceBuf<unsigned> d_mnmx;     // [max_batch][2]
+    miunet::DeviceBuf<float> d_ksplit;      // split-K slabs of the Winograd kernel (small batches / deep levels only)
+    size_t ksplit_bytes = 0;
+    miunet::DeviceBuf<int> d_cont;          // contour outputs of mi_unet_extract_contours (grown on demand)
+    miunet::PinnedBuf<int> h_cont;          // pinned mirror: one async D2H, then only the points that exist are copied to the caller
+    size_t cont_cap = 0;            // ints
+    // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
+    // network of micro-batch k runs (d_img / d_img2 alternate)
+    hipStream_t pre_stream = nullptr;
+    miunet::DeviceBuf<uint8_t> d_img2;
+    miunet::Event tile_ready[2];
+    // stage timing of the last RAW-in call (mi_unet_last_stage_ms): event pairs per micro-batch, summed
+    miunet::Event stage_ev[2][5], out_done[2];
+    miunet::Event pre_ev[3][2];             // three pairs: micro-batch k + 2 is staged before k's times are read
+    miunet::PinnedBuf<uint8_t> h_labels2;   // second pinned result buffer: micro-batch k + 1 downloads while the host still copies k out
+    // third stream of the RAW-in entry points: postprocess, mask_to_image, contours and the downloads of micro-batch k run
+    // here while the engine's stream already works on the network of k + 1; own workspace (the network's scratch buffers,
+    // which the single-stage entry points borrow, are in use by then), second label buffer
+    hipStream_t tail_stream = nullptr;
+    hipStream_t dl_stream = nullptr;          // tile downloads: behind the network of k, beside its tail and the upload of k + 1
+    miunet::Event tiles_done[2];
+    miunet::DeviceBuf<uint8_t> d_tail_ws;
+    size_t tail_ws_bytes = 0;
+    miunet::DeviceBuf<uint8_t> d_tail_vis, d_labels2;
+    miunet::Event net_done[2], tail_ev[2][4];
+    std::unique_ptr<miunet::CopyPool> copy_pool;   // helpers of the pageable -> pinned staging copy (created on first use)
+    miunet::PinnedBuf<uint8_t> h_tiles[2];  // pinned mirrors of the tile buffers (a D2H into the caller's pageable memory would block the host)
+    float stage_ms[MI_UNET_N_STAGES] = {};
+    // tiled entry points (mi_unet_infer_tiled_*): the full-size image, its label map / visualisation, logits and u16 planes stay
+    // on the device for the whole call.  Grown on demand (ensure_tiled_buffers), owned by this handle, never shared with a clone.
+    struct Tiled {
+        miunet::DeviceBuf<uint8_t> d_img, d_labels, d_vis;                           // u8 [H][W][in_ch] (+ slack to a dword), [H][W], [H][W]
+        miunet::PinnedBuf<uint8_t> h_img, h_out;                                     // pinned mirrors of d_img and of d_labels / d_vis
+        size_t px_cap = 0;                                                   // pixels the five above hold
+        miunet::DeviceBuf<float> d_logits;
+        size_t logit_cap = 0;                                                // pixels
+        miunet::DeviceBuf<uint16_t> d_raw;                                           // in_ch planes of u16 [H][W], device ...
+        miunet::PinnedBuf<uint16_t> h_raw;                                           // ... and pinned
+        size_t raw_cap = 0;                                                  // pixels per plane
+        std::vector<miunet::Event> ev;                                               // stage boundaries of the last call
+        miunet::DeviceBuf<float> d_acc;                                              // blending: fp32 accumulator [classes][H][W]
+        size_t acc_cap = 0;                                                  // pixels
+    } tiled;
+    // mi_unet_set_tile_blend: how the tiled entry points combine overlapping tiles; d_blend_w = the weight tables of the tile height
+    // and width (height + width floats), uploaded when the setting changes
+    mi_unet_tile_blend blend{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
+    miunet::DeviceBuf<float> d_blend_w;
+    // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
+    miunet::PinnedBuf<uint8_t> h_img;
+    miunet::PinnedBuf<uint8_t> h_labels;
+    std::vector<miunet::Step> plan;
+    // hipGraph replay of the forward pass (the reference replays a captured CUDA graph per image, src/process.cpp:99-105,
+    // :147): one captured graph per (stream, buffers, batch) key; the first call of a key runs eagerly.
+    struct GraphEntry {
+        hipStream_t stream; const uint8_t *imgs; uint8_t *labels; float *logits; int B;
+        int uses; hipGraphExec_t exec;
+    };
+    std::vector<GraphEntry> graphs;
+    bool use_graph = true;          // MIUNET_GRAPH=0 disables
+    bool postprocess = false;       // mi_unet_set_postprocess: label maps -> postprocess_mask output before they leave the device
+    // profiling: one event pair per launch, recorded on the launch stream and only read back (synchronised) in
+    // mi_unet_get_kernel_stats, so the launches themselves never wait on the host
+    bool profiling = false;
+    std::vector<mi_unet_kernel_stat> stats;
+    std::vector<miunet::Event> ev_pool;
+    size_t ev_used = 0;
+    miunet::Event tev0, tev1;
+    // mi_unet_debug_capture: stop launch_plan after step `layer` and hand its operands of image `img` to the host
+    struct Tap {
+        int layer = -1, img = 0;
+        float *in = nullptr, *out = nullptr, *pooled = nullptr;
+        uint8_t *labels = nullptr;
+        mi_unet_layer_info *info = nullptr;
+        bool hit = false;
+    } tap;
+};
+
+namespace miunet {
+
+// ---- engine.cpp
+int check_handle(mi_unet *h, bool need_weights);
+PlanInput plan_input(const mi_unet *h);                 // the handle's settings and buffers as build_plan / route_plan take them
+int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);
+int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);   // graph replay of launch_plan
+int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);  // ... + postprocess when set
+hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s);
+int device_postprocess(mi_unet *h, const uint8_t *d_in, uint8_t *d_out, int B);
+int grow_events(std::vector<Event> &ev, size_t n);      // at least n timing events (never inside a capture)
+// contour outputs of `bm` images: device -> pinned mirror half (async on h->stream) -> the caller's arrays (after the synchronise)
+int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours);
+int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int half = 0);
+void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contours, int32_t *xy, int32_t *start, int32_t *counts, int half = 0);
+// ---- pipeline_raw.cpp: large host copies on the handle's helper threads
+void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes);
+// ---- debug.cpp: mi_unet_debug_capture's taps, called by launch_plan around the tapped step
+int tap_input(mi_unet *h, const Step &st, const Launch &l, const uint8_t *d_imgs, int lp_kind);
+int tap_output(mi_unet *h, const Step &st, const Launch &l, uint8_t *d_labels, float *d_logits, int lp_kind);
+
+}  // namespace miunet

@@ -1,5 +1,5 @@
-// engine_internal.h -- what group.cpp (the multi-device group of include/mi_unet.h) needs from engine.cpp.  Internal to
-// libmiunet.so.
+// engine_internal.h -- the weight containers and packing functions of weights.cpp, and what group.cpp (the multi-device group of
+// include/mi_unet.h) needs from engine.cpp.  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,8 +35,26 @@ struct DeviceWeights {
     ~DeviceWeights();
 };
 
-int engine_fail(int code, const std::string &msg);                 // sets this thread's mi_unet_last_error()
+int engine_fail(int code, const std::string &msg);                 // sets this thread's mi_unet_last_error() (weights.cpp)
+const std::string &engine_last_error();                            // ... and reads it back
+
+// ---- weights.cpp: host-only, no HIP call
+size_t round_up(size_t v, size_t g);
+uint16_t bf16_bits(float x);                                       // round-to-nearest-even, as the device converts activations
+uint16_t fp16_bits(float x);
+float bf16_to_float(uint16_t b);
+float fp16_to_float(uint16_t h);
+void first_layer_lut(float lut[256]);                              // i / 255.0f
+// The packed layouts the kernels read.  FIRST [tap][ci][co]; MFMA / MFMA_T fp32 conv3x3 / convT2x2; TAPS per-tap convT; WINO,
+// WINO16 F(2x2,3x3); WINO4 F(4x4,3x3); LP / LP_T the 16-bit conv3x3 / convT2x2.  NONE and UP (pooling, upsampling) have no weights.
+enum class Pack { NONE, FIRST, MFMA, MFMA_T, TAPS, WINO, WINO16, WINO4, LP, LP_T, UP };
+size_t packed_npad(Pack p, int cout);                              // the padded N a launch passes as ConvArgs::CoutPad
+size_t packed_floats(Pack p, int cin, int cout);                   // size of the packed tensor, in floats
+// w: PyTorch [Cout][Cin][3][3] (conv) or [Cin][Cout][2][2] (convT); scale: per-channel BN scale folded in double before any
+// rounding (null = 1; the transposed layouts take none); fp16: LP / LP_T round to binary16 instead of bfloat16; dst: zero-filled
+void pack_weights(Pack p, bool fp16, const float *w, const double *scale, int cin, int cout, float *dst);
 // parse "MIUNETW1" (version 1, or 2 with its up_mode), fold BN, repack for `algo` (a resolved MI_UNET_CONV_* value, see engine_algo)
+// (weights.cpp)
 int engine_pack_weights(const mi_unet_config &cfg, int algo, const void *blob, size_t len, HostWeights &hw);
 // allocate the device blob of `h` for `hw` (uploading hw.blob when `upload`, else leaving the bytes to the caller: a
 // broadcast or a peer copy fills engine_weight_ptr()), then build the launch plan

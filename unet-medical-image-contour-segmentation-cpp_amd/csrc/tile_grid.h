@@ -1,5 +1,5 @@
 // tile_grid.h -- the overlap-tile grid of the tiled entry points (mi_unet_infer_tiled_*, include/mi_unet.h): which tiles cover an
-// image axis and which output positions each of them owns.  Pure integer arithmetic, shared by the host (engine.cpp, the
+// image axis and which output positions each of them owns.  Pure integer arithmetic, shared by the host (pipeline_tiled.cpp, the
 // exported mi_unet_tile_axis) and the kernels of tiles.hip, and free of any device API so that a host-only test can include it
 // (tests/cpu/tile_axis_test.cpp).  Internal to libmiunet.so.
 //
