@@ -16,6 +16,12 @@ struct Point {
 
 using Contour = std::vector<Point>;
 
+// The contours of one target class (MedicalSeg::set_targets), in the order extract_contours returns them.
+struct ClassContours {
+    int cls = 0;
+    std::vector<Contour> contours;
+};
+
 // Row-major, interleaved channels, 8 bits per sample.
 struct Image8 {
     int rows = 0, cols = 0, channels = 1;

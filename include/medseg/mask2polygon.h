@@ -37,4 +37,18 @@ void write_polygon_outputs(const std::vector<medseg::Contour> &contours, const m
 std::string polygon_json_text(const std::vector<medseg::Contour> &contours, const std::string &base_name, int original_width,
                               int original_height);
 
+// ---- several target classes (MedicalSeg::set_targets): groups of contours in target order
+// The document with "label": cls and "labelIndex": <index of the group> per shape; a group without contours contributes no shape.
+// A single group of class 2 (the default target list) gives the document above, byte for byte.
+std::string polygon_json_text(const std::vector<medseg::ClassContours> &groups, const std::string &base_name, int original_width,
+                              int original_height);
+// One overlay with every group's contours: group g in colour g of a fixed palette (B,G,R) -- red (the single-class colour), green,
+// blue, yellow, magenta; later groups are drawn over earlier ones.
+medseg::Image8 draw_overlay(const medseg::Image8 &gray_or_bgr, const std::vector<medseg::ClassContours> &groups);
+// write_polygon_outputs for groups: <base>_contour_overlay.png and <base>.json (points mapped to the original size) unless every
+// group is empty.
+void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const medseg::Image8 &normalized_tile,
+                           const std::string &output_dir, const std::string &base_name, int original_width, int original_height,
+                           std::ostream &console = std::cout);
+
 }  // namespace Mask2Polygon

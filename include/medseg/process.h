@@ -17,6 +17,20 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
 int process_image_batch(const std::vector<std::string> &raw_paths, const std::vector<int> &widths,
                         const std::vector<int> &heights, const std::string &output_dir);
 
+// Which classes the two functions above segment, and each one's area rule (mi_unet_target in include/mi_unet.h; at most
+// MI_UNET_MAX_TARGETS).  The default is { { 2, 0.06f } }: the reference's one foreground class, and with it every artefact is what it
+// always was.  With any other list an image gets, in place of <base>_mask.png, one <base>_mask_class<cls>.png (0 / 255) per target,
+// one <base>_contour_overlay.png with every target's contours (target k in colour k of Mask2Polygon::draw_overlay's palette) and one
+// <base>.json whose shapes carry "label": cls and "labelIndex": k.  set_targets needs an initialised engine (the classes are the
+// network's); it returns false, message on stderr, and changes nothing for a list the engine refuses.  An empty list restores the
+// default, and so does initialize_engine.
+struct Target {
+    int cls;
+    float min_area_frac;
+};
+bool set_targets(const std::vector<Target> &targets);
+std::vector<Target> get_targets();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

@@ -26,6 +26,21 @@ int medseg_resample_normalize(const uint16_t *src, int w, int h, uint8_t *dst, i
 int medseg_postprocess_mask(const uint8_t *mask, int w, int h, uint8_t *out);
 int medseg_mask_to_image(const uint8_t *mask, int w, int h, uint8_t *out);
 
+/* postprocess_mask(src, cls, min_area_frac) (include/medseg/postprocess.h): the chain for any class and area rule, output in {0, cls} */
+int medseg_postprocess_mask_target(const uint8_t *mask, int w, int h, int cls, float min_area_frac, uint8_t *out);
+/* MedicalSeg::set_targets / get_targets: n pairs (cls[i], min_area_frac[i]); n == 0 restores the default.  get returns the count and
+ * fills at most cap entries. */
+int medseg_set_targets(const int *cls, const float *min_area_frac, int n);
+int medseg_get_targets(int *cls, float *min_area_frac, int cap);
+/* Mask2Polygon::polygon_json_text for groups: group g has class group_cls[g] and the next group_contours[g] contours of the flattened
+ * list (xy / start as in medseg_generate_json).  Writes the document (no terminator) into out and returns its length, or -1 when cap
+ * bytes are too few. */
+int medseg_polygon_json_text_groups(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
+                                    const char *base_name, int original_width, int original_height, char *out, int cap);
+/* Mask2Polygon::draw_overlay for groups (same layout): group g in colour g of the palette; bgr_out is w*h*3 bytes */
+int medseg_draw_overlay_groups(const uint8_t *gray, int w, int h, const int32_t *xy, const int32_t *start, const int *group_cls,
+                               const int *group_contours, int ngroups, uint8_t *bgr_out);
+
 /* Mask2Polygon::extract_contours (src/mask2polygon.cpp:29): xy receives x,y pairs; start[c]..start[c+1] delimits contour c.
  * Returns the number of contours, or -1 when a capacity is too small. */
 int medseg_extract_contours(const uint8_t *mask, int w, int h, int32_t *xy, int cap_points, int32_t *start, int cap_contours);

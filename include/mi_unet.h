@@ -200,6 +200,43 @@ int mi_unet_get_tile_blend(const mi_unet_t *h, mi_unet_tile_blend *b);
  * T < 1, null pointers or an invalid setting. */
 int mi_unet_tile_blend_weights(int T, const mi_unet_tile_blend *b, float *w);
 
+/* ---- Targets: which classes the tail segments, and how small a structure may be ---------------------------------
+ * A target is a class and its area rule.  Its mask is postprocess_mask (above) with `== cls` in place of `== 2` and min_area_frac in
+ * place of 6 %: fill the 8-connected components of label != cls whose bounding box touches no image edge and whose area is below
+ * min_area, open 3x3 (the border neither constrains nor seeds), keep the 8-connected components of at least min_area pixels.
+ * min_area = mi_unet_target_min_area(H, W, min_area_frac) = (int)((float)(W * H) * min_area_frac): the int product converted to float
+ * and multiplied in float, so 0.06f gives the numbers of the single-class entry points (pure host arithmetic, needs no device).
+ * Targets are independent: after hole filling two of them may claim the same pixel.
+ * The setting is per handle.  Default { { 2, 0.06f } }; t == NULL or n == 0 restores it; a clone starts at the default.
+ * MI_UNET_EARG, setting unchanged: n < 0 or n > MI_UNET_MAX_TARGETS, cls < 1 or cls >= classes, a repeated cls, a min_area_frac that is
+ * not finite or lies outside [0, 1].  mi_unet_get_targets writes min(*n, cap) entries and the number of targets to *n.
+ * Only the _multi entry points read the setting; every other entry point -- mi_unet_set_postprocess included -- keeps class 2 and 6 %.
+ * With K = the number of targets, in target order:
+ *   mi_unet_postprocess_masks_multi   : labels u8 [B][H][W] (host) -> out u8 [B][K][H][W], values in {0, cls_k}
+ *   mi_unet_segment_raw16_multi       : mi_unet_segment_raw16 with masks u8 [B][K][H][W] (0 / 255), xy [B][K][cap_points][2],
+ *                                       start [B][K][cap_contours + 1], counts [B][K]; -1 marks only the (image, target) whose capacity
+ *                                       was too small
+ *   mi_unet_segment_tiled_raw16_multi : mi_unet_segment_tiled_raw16 with mask u8 [K][H][W], xy [K][cap_points][2],
+ *                                       start [K][cap_contours + 1], count [K]; min_area from the full image.  MI_UNET_EARG before
+ *                                       anything runs when the K-fold workspace exceeds the borrowed scratch buffer.
+ * The (image, target) pairs run as B * K independent planes through the same launches as one target; the label map is read in place.
+ * The RAW form's workspace and output buffers grow on demand and belong to the handle.  With the default setting every _multi call
+ * returns exactly the bytes of its single-class counterpart.  mi_unet_last_stage_ms covers these calls under the same stage names. */
+#define MI_UNET_MAX_TARGETS 5
+typedef struct mi_unet_target {
+    int cls;               /* class index, 1 .. classes - 1 */
+    float min_area_frac;   /* smallest structure kept / largest hole filled, as a fraction of the image area, in [0, 1] */
+} mi_unet_target;
+int mi_unet_target_min_area(int H, int W, float frac);
+int mi_unet_set_targets(mi_unet_t *h, const mi_unet_target *t, int n);
+int mi_unet_get_targets(const mi_unet_t *h, mi_unet_target *t, int cap, int *n);
+int mi_unet_postprocess_masks_multi(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out);
+int mi_unet_segment_raw16_multi(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
+                                uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
+                                int32_t *counts);
+int mi_unet_segment_tiled_raw16_multi(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
+                                      int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only
@@ -347,6 +384,11 @@ int mi_unet_group_infer_raw16(mi_unet_group_t *g, const uint16_t *const *raws, c
 int mi_unet_group_segment_raw16(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                                 uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                 int32_t *counts);
+/* mi_unet_set_targets on every rank (all or none), and the sharded form of mi_unet_segment_raw16_multi: same arguments, same results */
+int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n);
+int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
+                                      uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
+                                      int32_t *counts);
 void mi_unet_group_destroy(mi_unet_group_t *g);
 /* The split itself (pure host arithmetic, needs no device): rank's range [*lo, *hi) of n_items over `world` ranks. */
 int mi_unet_shard_range(int n_items, int rank, int world, int *lo, int *hi);

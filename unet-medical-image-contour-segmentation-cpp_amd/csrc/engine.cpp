@@ -158,9 +158,43 @@ int device_postprocess(mi_unet *h, const uint8_t *d_in, uint8_t *d_out, int B)
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t cap = sizeof(float) * (size_t)h->cfg.max_batch * H * W * h->ch[0];
     if (postprocess_workspace_bytes(B, H, W) > cap) return fail(MI_UNET_EARG, "postprocess workspace does not fit the scratch buffer");
-    const int min_area = static_cast<int>(W * H * 0.06f);            // src/postprocess.cpp:9, :30, :66 (evaluated in float)
+    const int min_area = mi_unet_target_min_area(H, W, 0.06f);       // src/postprocess.cpp:9, :30, :66 (evaluated in float)
     const hipError_t e = launch_postprocess_masks(d_in, d_out, B, H, W, min_area, h->d_s1, h->stream);
     if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
+    return 0;
+}
+
+TargetTable target_table(const mi_unet *h, int H, int W)
+{
+    TargetTable t;
+    t.K = h->n_targets;
+    for (int k = 0; k < t.K; ++k) {
+        t.cls[k] = h->targets[k].cls;
+        t.min_area[k] = mi_unet_target_min_area(H, W, h->targets[k].min_area_frac);
+    }
+    return t;
+}
+
+int ensure_tail_workspace(mi_unet *h, size_t bytes)
+{
+    if (bytes <= h->tail_ws_bytes) return 0;
+    if (h->tail_stream) HIP_TRY(hipStreamSynchronize(h->tail_stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->tail_ws_bytes = 0;
+    HIP_TRY(h->d_tail_ws.reset(bytes));
+    h->tail_ws_bytes = bytes;
+    return 0;
+}
+
+int ensure_multi_buffers(mi_unet *h, size_t bytes)
+{
+    if (bytes <= h->multi_cap) return 0;
+    if (h->tail_stream) HIP_TRY(hipStreamSynchronize(h->tail_stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->multi_cap = 0;
+    HIP_TRY(h->d_multi.reset(bytes));
+    for (auto &b : h->h_multi) HIP_TRY(b.reset(bytes));
+    h->multi_cap = bytes;
     return 0;
 }
 
@@ -574,6 +608,65 @@ int mi_unet_postprocess_masks(mi_unet_t *h, const uint8_t *labels, int B, uint8_
         HIP_TRY(hipMemcpyAsync(h->h_labels, h->d_labels, bm * hw, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         memcpy(out + b0 * hw, h->h_labels, bm * hw);
+    }
+    return MI_UNET_OK;
+}
+
+int mi_unet_target_min_area(int H, int W, float frac) { return static_cast<int>(W * H * frac); }
+
+int mi_unet_set_targets(mi_unet_t *h, const mi_unet_target *t, int n)
+{
+    if (int rc = check_handle(h, false)) return rc;
+    if (n < 0 || n > MI_UNET_MAX_TARGETS)
+        return fail(MI_UNET_EARG, "mi_unet_set_targets: " + std::to_string(n) + " targets (at most " + std::to_string(MI_UNET_MAX_TARGETS) + ")");
+    const mi_unet_target def{ 2, 0.06f };
+    if (!t || n == 0) { t = &def; n = 1; }
+    for (int k = 0; k < n; ++k) {
+        if (t[k].cls < 1 || t[k].cls >= h->cfg.classes)
+            return fail(MI_UNET_EARG, "mi_unet_set_targets: class " + std::to_string(t[k].cls) + " is outside 1.." + std::to_string(h->cfg.classes - 1));
+        for (int j = 0; j < k; ++j)
+            if (t[j].cls == t[k].cls) return fail(MI_UNET_EARG, "mi_unet_set_targets: class " + std::to_string(t[k].cls) + " is listed twice");
+        if (!(std::isfinite(t[k].min_area_frac) && t[k].min_area_frac >= 0.f && t[k].min_area_frac <= 1.f))
+            return fail(MI_UNET_EARG, "mi_unet_set_targets: min_area_frac of class " + std::to_string(t[k].cls) + " must be finite and in [0, 1]");
+    }
+    mi_unet_target keep[MI_UNET_MAX_TARGETS];        // (t may point into h->targets)
+    std::copy(t, t + n, keep);
+    std::copy(keep, keep + n, h->targets);
+    h->n_targets = n;
+    return MI_UNET_OK;
+}
+
+int mi_unet_get_targets(const mi_unet_t *h, mi_unet_target *t, int cap, int *n)
+{
+    if (!h || !n || cap < 0 || (cap > 0 && !t)) return fail(MI_UNET_EARG, "mi_unet_get_targets: bad argument");
+    *n = h->n_targets;
+    for (int k = 0; k < h->n_targets && k < cap; ++k) t[k] = h->targets[k];
+    return MI_UNET_OK;
+}
+
+int mi_unet_postprocess_masks_multi(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out)
+{
+    if (int rc = check_handle(h, false)) return rc;
+    if (!labels || !out || B < 0) return fail(MI_UNET_EARG, "mi_unet_postprocess_masks_multi: bad argument");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const int H = h->cfg.height, W = h->cfg.width, Bm = h->cfg.max_batch;
+    const size_t hw = (size_t)H * W;
+    const TargetTable tab = target_table(h, H, W);
+    const size_t K = (size_t)tab.K;
+    if ((size_t)std::min(B, Bm) * K * hw > 0x7FFFFFFFull)
+        return fail(MI_UNET_EARG, "mi_unet_postprocess_masks_multi: max_batch x targets x height x width exceeds 2^31 - 1");
+    hipStream_t s = h->stream;
+    for (int b0 = 0; b0 < B; b0 += Bm) {
+        const int bm = std::min(Bm, B - b0);
+        if (int rc = ensure_tail_workspace(h, postprocess_workspace_bytes(bm * tab.K, H, W))) return rc;
+        if (int rc = ensure_multi_buffers(h, bm * K * hw)) return rc;
+        memcpy(h->h_labels, labels + b0 * hw, bm * hw);
+        HIP_TRY(hipMemcpyAsync(h->d_labels, h->h_labels, bm * hw, hipMemcpyHostToDevice, s));
+        const hipError_t e = launch_postprocess_masks_multi(h->d_labels, h->d_multi, bm, H, W, tab, h->d_tail_ws, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
+        HIP_TRY(hipMemcpyAsync(h->h_multi[0], h->d_multi, bm * K * hw, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        memcpy(out + b0 * K * hw, h->h_multi[0], bm * K * hw);
     }
     return MI_UNET_OK;
 }

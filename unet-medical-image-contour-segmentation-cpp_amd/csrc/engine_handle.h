@@ -144,6 +144,9 @@ struct mi_unet {
         miunet::PinnedBuf<uint16_t> h_raw;                                           // ... and pinned
         size_t raw_cap = 0;                                                  // pixels per plane
         std::vector<miunet::Event> ev;                                               // stage boundaries of the last call
+        miunet::DeviceBuf<uint8_t> d_multi;                                          // the _multi form: [K][H][W] masks / pictures ...
+        miunet::PinnedBuf<uint8_t> h_multi;                                          // ... and their pinned mirror
+        size_t multi_cap = 0;                                                // bytes
         miunet::DeviceBuf<float> d_acc;                                              // blending: fp32 accumulator [classes][H][W]
         size_t acc_cap = 0;                                                  // pixels
     } tiled;
@@ -151,6 +154,13 @@ struct mi_unet {
     // and width (height + width floats), uploaded when the setting changes
     mi_unet_tile_blend blend{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
     miunet::DeviceBuf<float> d_blend_w;
+    // mi_unet_set_targets: what the _multi entry points segment.  d_multi / h_multi hold their [B][K][H][W] planes (masks, then their
+    // 0 / 255 pictures in place) and the pinned mirrors of two micro-batches in flight; grown on demand (ensure_multi_buffers)
+    mi_unet_target targets[MI_UNET_MAX_TARGETS] = { { 2, 0.06f } };
+    int n_targets = 1;
+    miunet::DeviceBuf<uint8_t> d_multi;
+    miunet::PinnedBuf<uint8_t> h_multi[2];
+    size_t multi_cap = 0;           // bytes of each of the three
     // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
     miunet::PinnedBuf<uint8_t> h_img;
     miunet::PinnedBuf<uint8_t> h_labels;
@@ -191,6 +201,9 @@ int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, 
 int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);  // ... + postprocess when set
 hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s);
 int device_postprocess(mi_unet *h, const uint8_t *d_in, uint8_t *d_out, int B);
+TargetTable target_table(const mi_unet *h, int H, int W);   // the handle's targets with min_area of an H x W image
+int ensure_tail_workspace(mi_unet *h, size_t bytes);    // h->d_tail_ws of at least `bytes` (synchronises its users before it grows)
+int ensure_multi_buffers(mi_unet *h, size_t bytes);     // h->d_multi / h->h_multi[0..1] of at least `bytes` each
 int grow_events(std::vector<Event> &ev, size_t n);      // at least n timing events (never inside a capture)
 // contour outputs of `bm` images: device -> pinned mirror half (async on h->stream) -> the caller's arrays (after the synchronise)
 int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours);

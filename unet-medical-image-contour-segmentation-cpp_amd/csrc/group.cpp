@@ -405,6 +405,38 @@ int mi_unet_group_segment_raw16(mi_unet_group_t *g, const uint16_t *const *raws,
     });
 }
 
+int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n)
+{
+    if (!g) return engine_fail(MI_UNET_EARG, "null group");
+    std::lock_guard<std::mutex> lk(g->call_mutex);       // never while a group call is in flight
+    // every rank has the same configuration, so the first rank's verdict is everybody's: all ranks change or none does
+    for (mi_unet_t *h : g->eng)
+        if (int rc = mi_unet_set_targets(h, t, n)) return rc;
+    return MI_UNET_OK;
+}
+
+int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
+                                      uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
+                                      int32_t *counts)
+{
+    if (!g || !raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
+        return engine_fail(MI_UNET_EARG, "mi_unet_group_segment_raw16_multi: bad argument");
+    std::lock_guard<std::mutex> lk(g->call_mutex);
+    const int R = (int)g->eng.size(), C = g->cfg.in_ch;
+    const size_t hw = (size_t)g->cfg.height * g->cfg.width;
+    int n_targets = 0;
+    if (int rc = mi_unet_get_targets(g->eng[0], nullptr, 0, &n_targets)) return rc;
+    const size_t K = (size_t)n_targets;
+    return for_all_ranks(g, [&](int r) {
+        int lo, hi;
+        shard_range(B, r, R, lo, hi);
+        if (hi == lo) return 0;
+        return mi_unet_segment_raw16_multi(g->eng[r], raws + (size_t)lo * C, widths + (size_t)lo * C, heights + (size_t)lo * C, hi - lo,
+                                           tiles ? tiles + lo * hw * C : nullptr, masks + lo * K * hw, xy + lo * K * cap_points * 2, cap_points,
+                                           start + lo * K * (cap_contours + 1), cap_contours, counts + lo * K);
+    });
+}
+
 void mi_unet_group_destroy(mi_unet_group_t *g)
 {
     if (!g) return;

@@ -281,6 +281,53 @@ __global__ __launch_bounds__(256) void k_filter(const int *__restrict__ parent, 
     out[i] = (r >= 0 && area[r] >= min_area) ? 2 : 0;          // src/postprocess.cpp:70, :75-76
 }
 
+// ---- K targets per image (launch_postprocess_masks_multi): plane p = i / hw of the output is target p % K of image p / K.  Only the
+// three kernels that look at a class or an area bound differ from the chain above; they read the label map of the plane's image
+// in place.  The table is a kernel argument; its entries are picked with a chain of selects, so it stays in registers.
+struct PlaneTarget { int cls, min_area; long long src; };
+__device__ __forceinline__ PlaneTarget plane_target(const TargetTable &t, long long i, int hw)
+{
+    const int p = (int)((unsigned)i / (unsigned)hw), img = p / t.K, k = p - img * t.K;      // i < n <= 2^31 - 1
+    int c = t.cls[0], a = t.min_area[0];
+#pragma unroll
+    for (int j = 1; j < POSTPROCESS_MAX_TARGETS; ++j)
+        if (k == j) { c = t.cls[j]; a = t.min_area[j]; }
+    return { c, a, (long long)img * hw + (i - (long long)p * hw) };
+}
+
+__global__ __launch_bounds__(256) void k_inv_multi(const uint8_t *__restrict__ labels, uint8_t *inv, int hw, TargetTable t, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const PlaneTarget pt = plane_target(t, i, hw);
+    inv[i] = labels[pt.src] == pt.cls ? 0 : 255;
+}
+
+__global__ __launch_bounds__(256) void k_fill_bin_multi(const uint8_t *__restrict__ labels, const int *__restrict__ parent,
+                                                        const int *__restrict__ area, const int *__restrict__ minx,
+                                                        const int *__restrict__ miny, const int *__restrict__ maxx,
+                                                        const int *__restrict__ maxy, uint8_t *bin, int H, int W, TargetTable t, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const PlaneTarget pt = plane_target(t, i, H * W);
+    bool fgd = labels[pt.src] == pt.cls;
+    const int r = parent[i];
+    if (!fgd && r >= 0)
+        fgd = minx[r] > 0 && miny[r] > 0 && maxx[r] < W - 1 && maxy[r] < H - 1 && area[r] < pt.min_area;
+    bin[i] = fgd ? 255 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_filter_multi(const int *__restrict__ parent, const int *__restrict__ area, uint8_t *out, int hw,
+                                                      TargetTable t, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const PlaneTarget pt = plane_target(t, i, hw);
+    const int r = parent[i];
+    out[i] = (r >= 0 && area[r] >= pt.min_area) ? (uint8_t)pt.cls : 0;
+}
+
 }  // namespace pp
 
 size_t postprocess_workspace_bytes(int B, int H, int W)
@@ -309,6 +356,31 @@ hipError_t launch_postprocess_masks(const uint8_t *labels_in, uint8_t *labels_ou
     hipLaunchKernelGGL(pp::k_morph3<true>, g, b, 0, s, u2, u1, H, W, n);
     label(u1);
     hipLaunchKernelGGL(pp::k_filter, g, b, 0, s, parent, area, labels_out, min_area, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, int B, int H, int W, const TargetTable &t, void *ws,
+                                          hipStream_t s)
+{
+    if (t.K < 1 || t.K > POSTPROCESS_MAX_TARGETS || B <= 0 || H <= 0 || W <= 0) return hipErrorInvalidValue;
+    const long long n = (long long)B * t.K * H * W;                // the planes of all (image, target) pairs
+    if (n <= 0 || n > 0x7FFFFFFFLL) return hipErrorInvalidValue;
+    const int hw = H * W;
+    int *parent = static_cast<int *>(ws), *area = parent + n, *minx = area + n, *miny = minx + n, *maxx = miny + n, *maxy = maxx + n;
+    uint8_t *u0 = reinterpret_cast<uint8_t *>(maxy + n), *u1 = u0 + n, *u2 = u1 + n;
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    auto label = [&](const uint8_t *fg) {
+        hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, fg, parent, area, minx, miny, maxx, maxy, W, n);
+        hipLaunchKernelGGL(pp::cc_merge, g, b, 0, s, fg, parent, H, W, n);
+        hipLaunchKernelGGL(pp::cc_stats, dim3((unsigned)((n + 256LL * pp::CC_RUN - 1) / (256LL * pp::CC_RUN))), b, 0, s, parent, area, minx, miny, maxx, maxy, H, W, n);
+    };
+    hipLaunchKernelGGL(pp::k_inv_multi, g, b, 0, s, labels, u0, hw, t, n);
+    label(u0);
+    hipLaunchKernelGGL(pp::k_fill_bin_multi, g, b, 0, s, labels, parent, area, minx, miny, maxx, maxy, u1, H, W, t, n);
+    hipLaunchKernelGGL(pp::k_morph3<false>, g, b, 0, s, u1, u2, H, W, n);
+    hipLaunchKernelGGL(pp::k_morph3<true>, g, b, 0, s, u2, u1, H, W, n);
+    label(u1);
+    hipLaunchKernelGGL(pp::k_filter_multi, g, b, 0, s, parent, area, out, hw, t, n);
     return hipGetLastError();
 }
 
@@ -580,6 +652,18 @@ __global__ __launch_bounds__(256) void mask_to_image_kernel(const uint8_t *__res
 hipError_t launch_mask_to_image(const uint8_t *labels, uint8_t *vis, size_t n, hipStream_t s)
 {
     hipLaunchKernelGGL(mask_to_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, labels, vis, n);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void mask_to_image_binary_kernel(const uint8_t *masks, uint8_t *vis, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) vis[i] = masks[i] ? 255 : 0;
+}
+
+hipError_t launch_mask_to_image_binary(const uint8_t *masks, uint8_t *vis, size_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(mask_to_image_binary_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, masks, vis, n);
     return hipGetLastError();
 }
 

@@ -195,6 +195,20 @@ size_t postprocess_workspace_bytes(int B, int H, int W);
 hipError_t launch_postprocess_masks(const uint8_t *labels_in, uint8_t *labels_out, int B, int H, int W, int min_area,
                                     void *ws, hipStream_t s);
 
+// The same chain for K targets at once (include/mi_unet.h: mi_unet_set_targets).  One label map u8 [B][H][W], read in place, never
+// replicated; out u8 [B][K][H][W] (must not alias it).  Plane p = b * K + k is the chain above on image p / K with `== cls[p % K]`
+// in place of `== 2` and min_area[p % K], its output in {0, cls[p % K]}.  The labelling, morphology and statistics kernels are the
+// ones above, run over B * K planes: the number of launches does not depend on K.  The table travels as a kernel argument (at most
+// POSTPROCESS_MAX_TARGETS entries).  Workspace: postprocess_workspace_bytes(B * K, H, W); B * K * H * W must not exceed 2^31 - 1.
+constexpr int POSTPROCESS_MAX_TARGETS = 5;
+struct TargetTable {
+    int K = 0;
+    int cls[POSTPROCESS_MAX_TARGETS] = {};
+    int min_area[POSTPROCESS_MAX_TARGETS] = {};
+};
+hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, int B, int H, int W, const TargetTable &t, void *ws,
+                                          hipStream_t s);
+
 // Device form of Mask2Polygon::extract_contours (reference: src/mask2polygon.cpp:29-36 = threshold 127 +
 // findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)), exact point sequences and contour order.
 //   masks u8 [B][H][W] (any values; > 127 = foreground).  Per image: at most cap_contours contours and cap_points points.
@@ -204,6 +218,8 @@ hipError_t launch_postprocess_masks(const uint8_t *labels_in, uint8_t *labels_ou
 // Workspace: contour_workspace_bytes(B, H, W, cap_contours).
 // mask_to_image (src/process.cpp:178-185): 0 -> 0, 1 -> 128, 2 -> 255, anything else -> 0
 hipError_t launch_mask_to_image(const uint8_t *labels, uint8_t *vis, size_t n, hipStream_t s);
+// the per-target form: a target's mask holds {0, cls}, its picture 0 / 255 (in place allowed)
+hipError_t launch_mask_to_image_binary(const uint8_t *masks, uint8_t *vis, size_t n, hipStream_t s);
 size_t contour_workspace_bytes(int B, int H, int W, int cap_contours);
 hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, int *out_xy, int cap_points, int *out_start,
                                    int cap_contours, int *out_count, void *ws, hipStream_t s);

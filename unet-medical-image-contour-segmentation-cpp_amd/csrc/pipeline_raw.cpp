@@ -118,6 +118,7 @@ struct RawCall {
     const uint16_t *const *raws; const int *widths, *heights; int B;
     uint8_t *tiles, *out_u8; float *logits;            // out_u8: label maps (infer) or 0 / 255 masks (segment)
     bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *counts;
+    bool multi = false;                                // segment, per target of the handle: out_u8 and the contour arrays are [B][K]...
 };
 
 int run_raw_call(mi_unet *h, const RawCall &c)
@@ -127,6 +128,11 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     const size_t hw = (size_t)H * W, C = (size_t)h->cfg.in_ch;
     hipStream_t s = h->stream;
     if (c.B <= 0) return MI_UNET_OK;
+    // the _multi form: K planes per image behind the network, (image, target) pairs as the batch of every tail stage
+    const TargetTable tab = c.multi ? target_table(h, H, W) : TargetTable{};
+    const int K = c.multi ? tab.K : 1;
+    if (c.multi && (size_t)std::min(c.B, Bm) * K * hw > 0x7FFFFFFFull)
+        return fail(MI_UNET_EARG, "segment_raw16_multi: max_batch x targets x height x width exceeds 2^31 - 1");
     // every image description is checked BEFORE anything is enqueued: a bad width in image k + 1 must not be found after the
     // network of micro-batch k has started
     for (size_t i = 0; i < (size_t)c.B * C; ++i)
@@ -170,7 +176,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     if (int rc = ensure_raw_pipeline(h, n_mb > 1)) return rc;
     for (float &m : h->stage_ms) m = 0.f;
     auto tile_buf = [&](int k) { return (k & 1) ? h->d_img2.get() : h->d_img.get(); };
-    auto out_buf = [&](int k) { return (k & 1) ? h->h_labels2.get() : h->h_labels.get(); };
+    auto out_buf = [&](int k) { return c.multi ? h->h_multi[k & 1].get() : (k & 1) ? h->h_labels2.get() : h->h_labels.get(); };
     auto stage = [&](int k) -> int {                   // upload + preprocess micro-batch k on the second stream
         const int bm = mbs[k].bm, par = k & 1;
         const size_t b0 = (size_t)mbs[k].b0;
@@ -187,7 +193,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         uint8_t *d_tiles = tile_buf(k);
         uint8_t *d_lab = par ? h->d_labels2.get() : h->d_labels.get();
         hipStream_t ts = h->tail_stream;
-        if (c.segment && contour_workspace_bytes(bm, H, W, c.cap_contours) > h->tail_ws_bytes)
+        if (c.segment && contour_workspace_bytes(bm * K, H, W, c.cap_contours) > h->tail_ws_bytes)
             return fail(MI_UNET_EARG, "contour workspace does not fit (cap_contours too large)");
         HIP_TRY(hipStreamWaitEvent(s, h->tile_ready[par], 0));
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(s, h->out_done[par], 0));                      // the tail of k - 2 has read this label buffer
@@ -209,14 +215,24 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         Event *tv = h->tail_ev[par];
         HIP_TRY(hipEventRecord(tv[0], ts));
         const uint8_t *d_result = d_lab;
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)bm * c.cap_points * 2, *d_count = d_start + (size_t)bm * (c.cap_contours + 1);
-        if (c.segment || h->postprocess) {
-            const int min_area = static_cast<int>(W * H * 0.06f);                              // src/postprocess.cpp:9, :30, :66
+        const int planes = bm * K;
+        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)planes * c.cap_points * 2, *d_count = d_start + (size_t)planes * (c.cap_contours + 1);
+        if (c.multi) {
+            const hipError_t e = launch_postprocess_masks_multi(d_lab, h->d_multi, bm, H, W, tab, h->d_tail_ws, ts);   // {0, cls_k}
+            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
+        } else if (c.segment || h->postprocess) {
+            const int min_area = mi_unet_target_min_area(H, W, 0.06f);                         // src/postprocess.cpp:9, :30, :66
             const hipError_t e = launch_postprocess_masks(d_lab, d_lab, bm, H, W, min_area, h->d_tail_ws, ts);      // {0, 2}
             if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
         }
         HIP_TRY(hipEventRecord(tv[1], ts));
-        if (c.segment) {
+        if (c.multi) {
+            hipError_t e = launch_mask_to_image_binary(h->d_multi, h->d_multi, planes * hw, ts);
+            if (e == hipSuccess)
+                e = launch_extract_contours(h->d_multi, planes, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_tail_ws, ts);
+            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("segment launch: ") + hipGetErrorString(e));
+            d_result = h->d_multi;
+        } else if (c.segment) {
             hipError_t e = launch_mask_to_image(d_lab, h->d_tail_vis, bm * hw, ts);
             if (e == hipSuccess)
                 e = launch_extract_contours(h->d_tail_vis, bm, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_tail_ws, ts);
@@ -224,9 +240,9 @@ int run_raw_call(mi_unet *h, const RawCall &c)
             d_result = h->d_tail_vis;
         }
         HIP_TRY(hipEventRecord(tv[2], ts));
-        HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, bm * hw, hipMemcpyDeviceToHost, ts));
+        HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, planes * hw, hipMemcpyDeviceToHost, ts));
         if (c.segment) {
-            const size_t n = (size_t)bm * ((size_t)c.cap_points * 2 + c.cap_contours + 1 + 1);
+            const size_t n = (size_t)planes * ((size_t)c.cap_points * 2 + c.cap_contours + 1 + 1);
             HIP_TRY(hipMemcpyAsync(h->h_cont + par * h->cont_cap, h->d_cont, n * sizeof(int), hipMemcpyDeviceToHost, ts));
         }
         HIP_TRY(hipEventRecord(tv[3], ts));
@@ -241,9 +257,10 @@ int run_raw_call(mi_unet *h, const RawCall &c)
             host_copy(h, c.tiles + b0 * hw * C, h->h_tiles[par], bm * hw * C);
         }
         HIP_TRY(hipEventSynchronize(h->out_done[par]));
-        host_copy(h, c.out_u8 + b0 * hw, out_buf(k), bm * hw);
+        host_copy(h, c.out_u8 + b0 * K * hw, out_buf(k), bm * K * hw);
         if (c.segment)
-            contours_to_caller(h, bm, c.cap_points, c.cap_contours, c.xy + b0 * c.cap_points * 2, c.start + b0 * (c.cap_contours + 1), c.counts + b0, par);
+            contours_to_caller(h, bm * K, c.cap_points, c.cap_contours, c.xy + b0 * K * c.cap_points * 2, c.start + b0 * K * (c.cap_contours + 1),
+                               c.counts + b0 * K, par);
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->pre_ev[k % 3][0], h->pre_ev[k % 3][1]));
         h->stage_ms[MI_UNET_STAGE_UPLOAD_PRE] += ms;
@@ -265,15 +282,12 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         int bmax = 0;
         for (const MB &m : mbs) bmax = std::max(bmax, m.bm);
         if (c.segment)
-            if (int rc = grow_contour_buffers(h, bmax, c.cap_points, c.cap_contours)) return rc;
-        size_t need = postprocess_workspace_bytes(bmax, H, W);
-        if (c.segment) need = std::max(need, contour_workspace_bytes(bmax, H, W, c.cap_contours));
-        if (need > h->tail_ws_bytes) {
-            HIP_TRY(hipStreamSynchronize(h->tail_stream));
-            h->tail_ws_bytes = 0;
-            HIP_TRY(h->d_tail_ws.reset(need));
-            h->tail_ws_bytes = need;
-        }
+            if (int rc = grow_contour_buffers(h, bmax * K, c.cap_points, c.cap_contours)) return rc;
+        size_t need = postprocess_workspace_bytes(bmax * K, H, W);
+        if (c.segment) need = std::max(need, contour_workspace_bytes(bmax * K, H, W, c.cap_contours));
+        if (int rc = ensure_tail_workspace(h, need)) return rc;
+        if (c.multi)
+            if (int rc = ensure_multi_buffers(h, (size_t)bmax * K * hw)) return rc;
     }
     // Once the first micro-batch is enqueued, H2D copies read the caller's (possibly page-locked) RAW buffers directly and the tail
     // writes the handle's pinned mirrors: an error return with work still in flight would let the caller free buffers under the
@@ -332,6 +346,16 @@ int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *
     if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
         return fail(MI_UNET_EARG, "mi_unet_segment_raw16: bad argument");
     return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts });
+}
+
+int mi_unet_segment_raw16_multi(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
+                                uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
+                                int32_t *counts)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
+        return fail(MI_UNET_EARG, "mi_unet_segment_raw16_multi: bad argument");
+    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts, true });
 }
 
 int mi_unet_last_stage_ms(const mi_unet_t *h, float *ms)

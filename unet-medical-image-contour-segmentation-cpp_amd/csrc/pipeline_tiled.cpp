@@ -31,6 +31,7 @@ struct TiledCall {
     uint8_t *norm, *out_u8;                // out_u8: label map (infer) or 0 / 255 mask (segment)
     float *logits;
     bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
+    bool multi = false;                    // segment, per target of the handle: out_u8 and the contour arrays are [K]...
 };
 
 int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bool blend)
@@ -118,16 +119,21 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     const size_t npix = (size_t)H * W, thw = (size_t)th * tw;
     const int nt = g.ny * g.nx;
     const bool post = c.segment || h->postprocess;
+    // the _multi form: the targets of the handle as K planes of the stitched image, min_area from the full image
+    const TargetTable tab = c.multi ? target_table(h, H, W) : TargetTable{};
+    const int K = c.multi ? tab.K : 1;
     // the full-size tail stages borrow the network's scratch buffer: checked before anything is enqueued
     const size_t scratch = sizeof(float) * h->s_floats;
-    if (post && postprocess_workspace_bytes(1, H, W) > scratch)
-        return fail(MI_UNET_EARG, fn + ": the postprocess workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
-                                      std::to_string(postprocess_workspace_bytes(1, H, W)) + " bytes) exceeds the scratch buffer (" +
+    const std::string what = (K > 1 ? std::to_string(K) + " targets of a " : std::string("a ")) + std::to_string(H) + " x " + std::to_string(W) + " image (";
+    if (post && postprocess_workspace_bytes(K, H, W) > scratch)
+        return fail(MI_UNET_EARG, fn + ": the postprocess workspace of " + what +
+                                      std::to_string(postprocess_workspace_bytes(K, H, W)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
-    if (c.segment && contour_workspace_bytes(1, H, W, c.cap_contours) > scratch)
-        return fail(MI_UNET_EARG, fn + ": the contour workspace of a " + std::to_string(H) + " x " + std::to_string(W) + " image (" +
-                                      std::to_string(contour_workspace_bytes(1, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
+    if (c.segment && contour_workspace_bytes(K, H, W, c.cap_contours) > scratch)
+        return fail(MI_UNET_EARG, fn + ": the contour workspace of " + what +
+                                      std::to_string(contour_workspace_bytes(K, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
+    if ((long long)K * H * W > 0x7FFFFFFFLL) return fail(MI_UNET_EARG, fn + ": targets x pixels exceeds 2^31 - 1");
     // blending or mirror averaging (mi_unet_set_tile_blend): nv views per tile, view k = t * nv + v, the network's logits
     // accumulated into t.d_acc, which also returns the blended logits; otherwise the ownership stitch
     const mi_unet_tile_blend bl = h->blend;
@@ -138,9 +144,16 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     hipStream_t s = h->stream;
     if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr && !blend, c.planes != nullptr, blend)) return rc;
     if (c.segment)
-        if (int rc = grow_contour_buffers(h, 1, c.cap_points, c.cap_contours)) return rc;
+        if (int rc = grow_contour_buffers(h, K, c.cap_points, c.cap_contours)) return rc;
     if (c.planes && !h->d_mnmx) HIP_TRY(h->d_mnmx.reset((size_t)2 * Bm * C));
     mi_unet::Tiled &t = h->tiled;
+    if (c.multi && K * npix > t.multi_cap) {
+        HIP_TRY(hipStreamSynchronize(s));
+        t.multi_cap = 0;
+        HIP_TRY(t.d_multi.reset(K * npix));
+        HIP_TRY(t.h_multi.reset(K * npix));
+        t.multi_cap = K * npix;
+    }
     // stage boundaries: start | pre | (gather | network + stitch or blend) per micro-batch | postprocess | contours | download
     const int nmb = (nk + Bm - 1) / Bm;
     const size_t n_marks = 2 + 2 * (size_t)nmb + 3;
@@ -226,13 +239,24 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
 
     // ---- the tail, on the stitched image: one image of H x W, never per tile
     const uint8_t *d_result = t.d_labels;
-    if (post) {
-        const int min_area = static_cast<int>(W * H * 0.06f);                // src/postprocess.cpp:9 (evaluated in float), of the full image
+    uint8_t *h_result = t.h_out;
+    if (c.multi) {
+        e = launch_postprocess_masks_multi(t.d_labels, t.d_multi, 1, H, W, tab, h->d_s1, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
+    } else if (post) {
+        const int min_area = mi_unet_target_min_area(H, W, 0.06f);          // src/postprocess.cpp:9 (evaluated in float), of the full image
         e = launch_postprocess_masks(t.d_labels, t.d_labels, 1, H, W, min_area, h->d_s1, s);
         if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
     }
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    if (c.segment) {
+    if (c.multi) {
+        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)K * c.cap_points * 2, *d_count = d_start + (size_t)K * (c.cap_contours + 1);
+        e = launch_mask_to_image_binary(t.d_multi, t.d_multi, K * npix, s);
+        if (e == hipSuccess) e = launch_extract_contours(t.d_multi, K, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": segment launch: " + hipGetErrorString(e));
+        d_result = t.d_multi;
+        h_result = t.h_multi;
+    } else if (c.segment) {
         int *d_xy = h->d_cont, *d_start = d_xy + (size_t)c.cap_points * 2, *d_count = d_start + (c.cap_contours + 1);
         e = launch_mask_to_image(t.d_labels, t.d_vis, npix, s);
         if (e == hipSuccess) e = launch_extract_contours(t.d_vis, 1, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
@@ -240,16 +264,16 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
         d_result = t.d_vis;
     }
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    HIP_TRY(hipMemcpyAsync(t.h_out, d_result, npix, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_result, d_result, K * npix, hipMemcpyDeviceToHost, s));
     if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
     if (c.segment)
-        if (int rc = contours_to_pinned(h, 1, c.cap_points, c.cap_contours)) return rc;
+        if (int rc = contours_to_pinned(h, K, c.cap_points, c.cap_contours)) return rc;
     if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, blend ? t.d_acc : t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipStreamSynchronize(s));
-    host_copy(h, c.out_u8, t.h_out, npix);
+    host_copy(h, c.out_u8, h_result, K * npix);
     if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
-    if (c.segment) contours_to_caller(h, 1, c.cap_points, c.cap_contours, c.xy, c.start, c.count);
+    if (c.segment) contours_to_caller(h, K, c.cap_points, c.cap_contours, c.xy, c.start, c.count);
 
     for (float &m : h->stage_ms) m = 0.f;
     auto span = [&](size_t a, size_t b, int stage) -> int {
@@ -343,6 +367,17 @@ int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int
     if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
         return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16: null output buffer or non-positive capacity");
     const TiledCall c{ "mi_unet_segment_tiled_raw16", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count };
+    return run_tiled_call(h, c);
+}
+
+int mi_unet_segment_tiled_raw16_multi(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
+                                      int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (int rc = check_planes(h, planes, "mi_unet_segment_tiled_raw16_multi")) return rc;
+    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
+        return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16_multi: null output buffer or non-positive capacity");
+    const TiledCall c{ "mi_unet_segment_tiled_raw16_multi", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count, true };
     return run_tiled_call(h, c);
 }
 

@@ -29,6 +29,21 @@ std::vector<Contour> unflatten(const int32_t *xy, const int32_t *start, int n)
         for (int k = start[c]; k < start[c + 1]; ++k) cs[c].emplace_back(xy[2 * k], xy[2 * k + 1]);
     return cs;
 }
+std::vector<medseg::ClassContours> ungroup(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups)
+{
+    std::vector<medseg::ClassContours> gs(ngroups);
+    int c0 = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        gs[g].cls = group_cls[g];
+        for (int c = c0; c < c0 + group_contours[g]; ++c) {
+            Contour cc;
+            for (int k = start[c]; k < start[c + 1]; ++k) cc.emplace_back(xy[2 * k], xy[2 * k + 1]);
+            gs[g].contours.push_back(std::move(cc));
+        }
+        c0 += group_contours[g];
+    }
+    return gs;
+}
 thread_local std::string t_log_path;
 }  // namespace
 
@@ -71,6 +86,44 @@ int medseg_postprocess_mask(const uint8_t *mask, int w, int h, uint8_t *out)
     try {
         const Image8 r = postprocess_mask(wrap(mask, w, h));
         memcpy(out, r.data.data(), r.data.size());
+        return 0;
+    } catch (...) { return 1; }
+}
+int medseg_postprocess_mask_target(const uint8_t *mask, int w, int h, int cls, float min_area_frac, uint8_t *out)
+{
+    try {
+        const Image8 r = postprocess_mask(wrap(mask, w, h), cls, min_area_frac);
+        memcpy(out, r.data.data(), r.data.size());
+        return 0;
+    } catch (...) { return 1; }
+}
+int medseg_set_targets(const int *cls, const float *min_area_frac, int n)
+{
+    std::vector<MedicalSeg::Target> t;
+    for (int i = 0; i < n; ++i) t.push_back({ cls[i], min_area_frac[i] });
+    return MedicalSeg::set_targets(t) ? 0 : 1;
+}
+int medseg_get_targets(int *cls, float *min_area_frac, int cap)
+{
+    const std::vector<MedicalSeg::Target> t = MedicalSeg::get_targets();
+    for (int i = 0; i < (int)t.size() && i < cap; ++i) { cls[i] = t[i].cls; min_area_frac[i] = t[i].min_area_frac; }
+    return (int)t.size();
+}
+int medseg_polygon_json_text_groups(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
+                                    const char *base_name, int original_width, int original_height, char *out, int cap)
+{
+    const std::string s = Mask2Polygon::polygon_json_text(ungroup(xy, start, group_cls, group_contours, ngroups), base_name, original_width,
+                                                          original_height);
+    if ((int)s.size() > cap) return -1;
+    memcpy(out, s.data(), s.size());
+    return (int)s.size();
+}
+int medseg_draw_overlay_groups(const uint8_t *gray, int w, int h, const int32_t *xy, const int32_t *start, const int *group_cls,
+                               const int *group_contours, int ngroups, uint8_t *bgr_out)
+{
+    try {
+        const Image8 r = Mask2Polygon::draw_overlay(wrap(gray, w, h), ungroup(xy, start, group_cls, group_contours, ngroups));
+        memcpy(bgr_out, r.data.data(), r.data.size());
         return 0;
     } catch (...) { return 1; }
 }

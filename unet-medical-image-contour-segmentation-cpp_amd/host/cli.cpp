@@ -141,6 +141,7 @@ public:
     {
         table_["init"] = [this](const Words &w) { cmd_init(w); return true; };
         table_["process"] = [this](const Words &w) { cmd_process(w); return true; };
+        table_["targets"] = [this](const Words &w) { cmd_targets(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -153,6 +154,7 @@ public:
             "Commands:",
             "  init <weight_file>            - Initialize the UNet engine",
             "  process [-r] <input> <width> <height> [output_dir] - Process file/directory",
+            "  targets <cls:frac,...>|default - Classes to segment, each with its minimum area fraction (e.g. 1:0.01,2:0.06)",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -219,6 +221,43 @@ private:
         } catch (const std::exception &err) {
             std::cerr << "Processing error: " << err.what() << std::endl;
         }
+    }
+
+    // targets 1:0.01,2:0.06 | targets default | targets (prints the list in force)
+    void cmd_targets(const Words &w)
+    {
+        if (!ready_) {
+            std::cerr << "Error: Engine not initialized" << std::endl;
+            return;
+        }
+        if (w.size() >= 2) {
+            std::vector<MedicalSeg::Target> t;
+            if (w[1] != "default") {
+                std::istringstream items(w[1]);
+                std::string item;
+                while (std::getline(items, item, ',')) {
+                    const size_t colon = item.find(':');
+                    MedicalSeg::Target x{ 0, 0.f };
+                    try {
+                        size_t used = 0;
+                        if (colon == std::string::npos || !to_int(item.substr(0, colon), x.cls)) throw std::invalid_argument(item);
+                        x.min_area_frac = std::stof(item.substr(colon + 1), &used);
+                        if (used != item.size() - colon - 1) throw std::invalid_argument(item);
+                    } catch (const std::exception &) {
+                        std::cerr << "Error: Invalid targets command (expected <class>:<fraction>[,...] or default)" << std::endl;
+                        return;
+                    }
+                    t.push_back(x);
+                }
+            }
+            if (!MedicalSeg::set_targets(t)) {
+                std::cerr << "Targets unchanged" << std::endl;
+                return;
+            }
+        }
+        std::cout << "Targets:";
+        for (const MedicalSeg::Target &x : MedicalSeg::get_targets()) std::cout << " " << x.cls << ":" << x.min_area_frac;
+        std::cout << std::endl;
     }
 
     void cmd_exit()

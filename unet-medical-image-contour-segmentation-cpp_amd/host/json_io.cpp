@@ -42,8 +42,10 @@ std::string size_json_text(const std::string &raw_filename, int w, int h, int sc
     return o;
 }
 
-std::string polygon_json_text(const std::vector<Contour> &contours, const std::string &base_name, int original_width,
-                              int original_height)
+namespace {
+// the document around a list of shapes, each with its label pair (src/mask2polygon.cpp:68-109 with std::setw(4))
+struct Shape { const Contour *pts; int label, label_index; };
+std::string polygon_document(const std::vector<Shape> &shapes, const std::string &base_name, int original_width, int original_height)
 {
     std::string o;
     o += "{\n";
@@ -52,38 +54,58 @@ std::string polygon_json_text(const std::vector<Contour> &contours, const std::s
     o += "    \"imageHeight\": " + std::to_string(original_height) + ",\n";
     o += "    \"imagePath\": \"" + json_escape(base_name + ".raw") + "\",\n";       // always .raw (src/mask2polygon.cpp:76)
     o += "    \"imageWidth\": " + std::to_string(original_width) + ",\n";
-    if (contours.empty()) {
+    if (shapes.empty()) {
         o += "    \"shapes\": [],\n";
     } else {
         o += "    \"shapes\": [\n";
-        for (size_t c = 0; c < contours.size(); ++c) {
+        for (size_t c = 0; c < shapes.size(); ++c) {
+            const Contour &pts = *shapes[c].pts;
             o += "        {\n";
             o += "            \"description\": \"\",\n";
             o += "            \"flags\": {},\n";
             o += "            \"group_id\": null,\n";
-            o += "            \"label\": 1,\n";
-            o += "            \"labelIndex\": 0,\n";
+            o += "            \"label\": " + std::to_string(shapes[c].label) + ",\n";
+            o += "            \"labelIndex\": " + std::to_string(shapes[c].label_index) + ",\n";
             o += "            \"mask\": null,\n";
-            if (contours[c].empty()) {
+            if (pts.empty()) {
                 o += "            \"points\": null,\n";      // a default-constructed nlohmann::json that was never push_back'ed
             } else {
                 o += "            \"points\": [\n";
-                for (size_t k = 0; k < contours[c].size(); ++k) {
+                for (size_t k = 0; k < pts.size(); ++k) {
                     o += "                [\n";
-                    o += "                    " + std::to_string(contours[c][k].x) + ",\n";
-                    o += "                    " + std::to_string(contours[c][k].y) + "\n";
-                    o += (k + 1 < contours[c].size()) ? "                ],\n" : "                ]\n";
+                    o += "                    " + std::to_string(pts[k].x) + ",\n";
+                    o += "                    " + std::to_string(pts[k].y) + "\n";
+                    o += (k + 1 < pts.size()) ? "                ],\n" : "                ]\n";
                 }
                 o += "            ],\n";
             }
             o += "            \"shape_type\": \"polygon\"\n";
-            o += (c + 1 < contours.size()) ? "        },\n" : "        }\n";
+            o += (c + 1 < shapes.size()) ? "        },\n" : "        }\n";
         }
         o += "    ],\n";
     }
     o += "    \"version\": \"1.0.2.812\"\n";
     o += "}\n";
     return o;
+}
+}  // namespace
+
+std::string polygon_json_text(const std::vector<Contour> &contours, const std::string &base_name, int original_width,
+                              int original_height)
+{
+    std::vector<Shape> shapes;
+    for (const Contour &c : contours) shapes.push_back({ &c, 1, 0 });
+    return polygon_document(shapes, base_name, original_width, original_height);
+}
+
+std::string polygon_json_text(const std::vector<ClassContours> &groups, const std::string &base_name, int original_width,
+                              int original_height)
+{
+    if (groups.size() == 1 && groups[0].cls == 2) return polygon_json_text(groups[0].contours, base_name, original_width, original_height);
+    std::vector<Shape> shapes;
+    for (size_t g = 0; g < groups.size(); ++g)
+        for (const Contour &c : groups[g].contours) shapes.push_back({ &c, groups[g].cls, (int)g });
+    return polygon_document(shapes, base_name, original_width, original_height);
 }
 
 namespace {

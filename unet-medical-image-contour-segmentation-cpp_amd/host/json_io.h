@@ -21,6 +21,13 @@ std::string size_json_text(const std::string &raw_filename, int w, int h, int sc
 std::string polygon_json_text(const std::vector<Contour> &contours, const std::string &base_name, int original_width,
                               int original_height);
 
+// The same document for the targets of MedicalSeg::set_targets: the shapes of group g carry "label": groups[g].cls and
+// "labelIndex": g, group after group; a group without contours contributes no shape; everything else as above.  One exception keeps
+// the reference's document: a single group of class 2 -- the default target list -- is the function above ("label": 1,
+// "labelIndex": 0, the reference's name for its one foreground class).
+std::string polygon_json_text(const std::vector<ClassContours> &groups, const std::string &base_name, int original_width,
+                              int original_height);
+
 // Parses an object of objects of integers (the size file).  Throws std::runtime_error on malformed input.
 std::map<std::string, std::map<std::string, long long>> parse_size_json(const std::string &text);
 

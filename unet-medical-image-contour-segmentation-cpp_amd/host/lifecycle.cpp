@@ -41,6 +41,7 @@ mi_unet_group_t *g_lane2 = nullptr;  // a clone of g_group, created by the first
 mi_unet_config g_cfg{};            // per-rank configuration of the group (tile size, topology, max_batch, algorithm)
 int g_thread_batch = 1;            // micro-batch capacity of a per-thread context
 unsigned long g_generation = 0;    // bumped by every (re)initialisation and cleanup: older thread contexts are stale
+std::vector<mi_unet_target> g_targets{ { 2, 0.06f } };   // set_targets: what process_single_image / process_image_batch segment
 std::ofstream g_log_file;
 std::string g_log_path;
 std::mutex g_log_mutex;            // the reference's global log stream is written from any thread unguarded
@@ -124,6 +125,7 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
         if (g_lane2) { mi_unet_group_destroy(g_lane2); g_lane2 = nullptr; }
         if (g_group) { mi_unet_group_destroy(g_group); g_group = nullptr; }
         ++g_generation;
+        g_targets.assign(1, mi_unet_target{ 2, 0.06f });           // the classes belong to the network that is about to load
         mi_unet_default_config(&g_cfg);            // 512x512x1, 3 classes (src/process.cpp:70, :162)
         uint32_t up_mode = 0;
         if (!read_weight_header(trt_cache_path, g_cfg, up_mode)) {
@@ -179,6 +181,50 @@ mi_unet_t *get_engine()
     return g_group ? mi_unet_group_handle(g_group, 0) : nullptr;
 }
 mi_unet_group_t *get_engine_group() { std::lock_guard<std::mutex> lk(g_state_mutex); return g_group; }
+
+bool set_targets(const std::vector<Target> &targets)
+{
+    std::lock_guard<std::mutex> batch(g_batch_mutex);          // never under a running directory-mode call
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    if (!g_group) {
+        std::cerr << "Error: Engine not initialized" << std::endl;
+        return false;
+    }
+    std::vector<mi_unet_target> t;
+    for (const Target &x : targets) t.push_back({ x.cls, x.min_area_frac });
+    // the group validates (class range of the loaded network, repeats, fractions) and changes all of its ranks or none
+    if (mi_unet_group_set_targets(g_group, t.data(), (int)t.size()) != MI_UNET_OK) {
+        std::cerr << "Error: " << mi_unet_last_error() << std::endl;
+        return false;
+    }
+    if (g_lane2) (void)mi_unet_group_set_targets(g_lane2, t.data(), (int)t.size());
+    if (t.empty()) t.push_back({ 2, 0.06f });
+    g_targets = t;
+    if (g_log_file.is_open()) {
+        std::lock_guard<std::mutex> ll(g_log_mutex);
+        g_log_file << "Targets:";
+        for (const auto &x : g_targets) g_log_file << " class " << x.cls << " (min area " << x.min_area_frac << ")";
+        g_log_file << std::endl;
+    }
+    return true;
+}
+
+std::vector<Target> get_targets()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    std::vector<Target> out;
+    for (const auto &x : g_targets) out.push_back({ x.cls, x.min_area_frac });
+    return out;
+}
+
+namespace {
+std::vector<mi_unet_target> current_targets()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    return g_targets;
+}
+bool is_default(const std::vector<mi_unet_target> &t) { return t.size() == 1 && t[0].cls == 2 && t[0].min_area_frac == 0.06f; }
+}  // namespace
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }
 
@@ -595,6 +641,112 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
     return ok;
 }
 
+// ---- a non-default target list (set_targets): K masks per image.  One plain route for both entry points: read the files of a chunk,
+// one device call for the chunk (mi_unet_segment_raw16_multi on `ctx`, or its group form when ctx is null), then the artefacts image
+// by image.  With MEDSEG_HOST_POSTPROCESS / _CONTOURS = 1 the device call ends at the label maps and the CPU chain (postprocess_mask
+// per target, mask picture, extract_contours) takes over; MEDSEG_HOST_PREPROCESS has no effect here (the device's tile is the CPU's
+// bit for bit).  Returns the number of images that succeeded.
+int process_images_targets(const std::vector<std::string> &paths, const std::vector<int> &widths, const std::vector<int> &heights,
+                           const std::string &output_dir, mi_unet_t *ctx, const std::vector<mi_unet_target> &targets, std::ostream &lg)
+{
+    const size_t n = paths.size(), hw = (size_t)g_cfg.height * g_cfg.width, K = targets.size();
+    const int C = g_cfg.in_ch;
+    mi_unet_group_t *group = ctx ? nullptr : get_engine_group();
+    if (!ctx && !group) throw std::runtime_error("Engine not initialized");
+    const bool device_tail = device_postprocess_requested() && device_contours_requested();
+    const size_t step = ctx ? 1 : (size_t)std::max(1, g_cfg.max_batch) * (size_t)std::max(1, mi_unet_group_size(group));
+    int ok = 0;
+    for (size_t first = 0; first < n; first += step) {
+        const size_t count = std::min(step, n - first);
+        std::vector<std::vector<uint16_t>> raws(count);
+        std::vector<const uint16_t *> ptrs;
+        std::vector<int> ws, hs;
+        std::vector<size_t> idx;
+        for (size_t k = 0; k < count; ++k) {
+            const size_t i = first + k;
+            try {
+                raws[k] = Preprocess::read_raw16(paths[i], widths[i], heights[i]);
+            } catch (const std::exception &e) {
+                if (ctx) {                             // process_single_image's wording (src/process.cpp:211-214)
+                    std::cerr << "preprocess_raw error: " << e.what() << '\n';
+                    throw std::runtime_error("Preprocessing failed");
+                }
+                const std::string msg = std::string("Processing error: ") + e.what() + " (" + paths[i] + ")";
+                std::cerr << msg << std::endl;
+                lg << msg << std::endl;
+                continue;
+            }
+            for (int c = 0; c < C; ++c) { ptrs.push_back(raws[k].data()); ws.push_back(widths[i]); hs.push_back(heights[i]); }
+            idx.push_back(i);
+        }
+        const size_t m = idx.size();
+        if (m == 0) continue;
+        std::vector<uint8_t> tiles(hw * m * C), masks(hw * m * K), labels(device_tail ? 0 : hw * m);
+        std::vector<int32_t> xy(device_tail ? m * K * (size_t)kCapPoints * 2 : 0), start(m * K * (kCapContours + 1)), cnt(m * K, -1);
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        int rc;
+        if (device_tail) {
+            rc = ctx ? mi_unet_segment_raw16_multi(ctx, ptrs.data(), ws.data(), hs.data(), (int)m, tiles.data(), masks.data(), xy.data(),
+                                                   kCapPoints, start.data(), kCapContours, cnt.data())
+                     : mi_unet_group_segment_raw16_multi(group, ptrs.data(), ws.data(), hs.data(), (int)m, tiles.data(), masks.data(),
+                                                         xy.data(), kCapPoints, start.data(), kCapContours, cnt.data());
+        } else {
+            rc = ctx ? mi_unet_infer_raw16(ctx, ptrs.data(), ws.data(), hs.data(), (int)m, tiles.data(), labels.data(), nullptr)
+                     : mi_unet_group_infer_raw16(group, ptrs.data(), ws.data(), hs.data(), (int)m, tiles.data(), labels.data(), nullptr);
+        }
+        if (rc != MI_UNET_OK) throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
+        lg << "Inference time: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count()
+           << " ms" << (m > 1 ? " for " + std::to_string(m) + " images" : std::string()) << std::endl;
+        for (size_t k = 0; k < m; ++k) {
+            const size_t i = idx[k];
+            const std::string base_name = fs::path(paths[i]).stem().string();
+            try {
+                if (!ctx) lg << "\n=== Processing Image: " << fs::path(paths[i]).filename().string() << " ===" << std::endl;
+                Image8 tile(g_cfg.height, g_cfg.width, 1);
+                for (size_t p = 0; p < hw; ++p) tile.data[p] = tiles[(k * hw + p) * C];      // channel 0: the planes are replicas
+                if (!Preprocess::write_preprocess_outputs(tile, paths[i], output_dir + "/" + base_name + "_normalized.png",
+                                                          output_dir + "/" + base_name + "_original_sizes.json", widths[i], heights[i]))
+                    throw std::runtime_error("Preprocessing failed");
+                std::vector<medseg::ClassContours> groups;
+                for (size_t t = 0; t < K; ++t) {
+                    const size_t plane = k * K + t;
+                    Image8 vis(g_cfg.height, g_cfg.width, 1);
+                    if (device_tail) {
+                        std::copy(masks.begin() + plane * hw, masks.begin() + (plane + 1) * hw, vis.data.begin());
+                    } else {
+                        Image8 lab(g_cfg.height, g_cfg.width, 1);
+                        std::copy(labels.begin() + k * hw, labels.begin() + (k + 1) * hw, lab.data.begin());
+                        const Image8 pm = postprocess_mask(lab, targets[t].cls, targets[t].min_area_frac);
+                        for (size_t p = 0; p < hw; ++p) vis.data[p] = pm.data[p] ? 255 : 0;
+                    }
+                    if (!medseg::write_png(output_dir + "/" + base_name + "_mask_class" + std::to_string(targets[t].cls) + ".png", vis, /*level0=*/true))
+                        throw std::runtime_error("Failed to save mask");
+                    medseg::ClassContours g{ targets[t].cls, {} };
+                    if (cnt[plane] < 0) {              // the host chain, or a capacity overflow on the device: the host tracer
+                        g.contours = Mask2Polygon::extract_contours(vis);
+                    } else {
+                        const int32_t *st = &start[plane * (kCapContours + 1)], *pts = &xy[plane * (size_t)kCapPoints * 2];
+                        for (int c = 0; c < cnt[plane]; ++c) {
+                            medseg::Contour cc;
+                            for (int q = st[c]; q < st[c + 1]; ++q) cc.emplace_back(pts[2 * q], pts[2 * q + 1]);
+                            g.contours.push_back(std::move(cc));
+                        }
+                    }
+                    groups.push_back(std::move(g));
+                }
+                Mask2Polygon::write_polygon_outputs(groups, tile, output_dir, base_name, widths[i], heights[i]);
+                if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
+                ++ok;
+            } catch (const std::exception &e) {
+                if (ctx) throw;
+                std::cerr << "Processing error: " << e.what() << std::endl;
+                lg << "Processing error: " << e.what() << std::endl;
+            }
+        }
+    }
+    return ok;
+}
+
 }  // namespace
 
 // Device-first form of the pipeline for N images at once (the reference loops files one by one, src/main.cpp:148-164).
@@ -611,6 +763,18 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         if (!group) throw std::runtime_error("Engine not initialized");
         const size_t n = raw_paths.size();
         if (widths.size() != n || heights.size() != n) throw std::runtime_error("widths/heights do not match raw_paths");
+        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets)) {
+            std::lock_guard<std::mutex> lk(g_batch_mutex);
+            std::ostringstream lg;
+            try {
+                ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, targets, lg);
+            } catch (...) {
+                if (log_file.is_open()) log_file << lg.str() << std::flush;
+                throw;
+            }
+            if (log_file.is_open()) log_file << lg.str() << std::flush;
+            return ok;
+        }
         if (n > 0 && device_postprocess_requested() && device_contours_requested()) {
             std::lock_guard<std::mutex> lk(g_batch_mutex);     // one directory-mode call at a time: it owns both device lanes
             return process_batch_pipelined(raw_paths, widths, heights, output_dir);
@@ -701,7 +865,11 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
         const std::string base_name = fs::path(raw_path).stem().string();
         const auto total_start = std::chrono::high_resolution_clock::now();
 
-        if (host_preprocess_requested()) {
+        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets)) {
+            // the thread's context is a clone (default targets): it takes the facade's list before every call
+            if (mi_unet_set_targets(ctx, targets.data(), (int)targets.size()) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            process_images_targets({ raw_path }, { width }, { height }, output_dir, ctx, targets, lg);
+        } else if (host_preprocess_requested()) {
             // the reference's own order: CPU preprocess -> PNG on disk -> read back -> inference (src/process.cpp:211-224)
             const std::string preprocessed_png_path = output_dir + "/" + base_name + "_normalized.png";
             const std::string size_json_path = output_dir + "/" + base_name + "_original_sizes.json";

@@ -176,7 +176,8 @@ void generate_json(const std::vector<Contour> &contours, const std::string &json
     f.flush();
 }
 
-Image8 draw_overlay(const Image8 &src, const std::vector<Contour> &contours)
+namespace {
+Image8 to_bgr(const Image8 &src)
 {
     Image8 img(src.rows, src.cols, 3);
     for (int y = 0; y < src.rows; ++y) {                              // cv::imread(IMREAD_COLOR) of a gray PNG: B = G = R = gray
@@ -186,10 +187,70 @@ Image8 draw_overlay(const Image8 &src, const std::vector<Contour> &contours)
         else
             for (int x = 0; x < src.cols; ++x) { const uint8_t g = s[x]; d[3 * x] = g; d[3 * x + 1] = g; d[3 * x + 2] = g; }
     }
-    const uint8_t red_bgr[3] = { 0, 0, 255 };                         // cv::Scalar(0, 0, 255), src/mask2polygon.cpp:10
-    for (const Contour &c : contours)                                 // drawContours(-1, thickness 1): closed polylines
-        for (size_t k = 0; k < c.size(); ++k) draw_segment(img, c[k], c[(k + 1) % c.size()], red_bgr);
     return img;
+}
+
+// colour of target g (B,G,R): the first is cv::Scalar(0, 0, 255), src/mask2polygon.cpp:10
+constexpr uint8_t kPalette[5][3] = { { 0, 0, 255 }, { 0, 255, 0 }, { 255, 0, 0 }, { 0, 255, 255 }, { 255, 0, 255 } };
+
+void draw_contours(Image8 &img, const std::vector<Contour> &contours, const uint8_t bgr[3])
+{
+    for (const Contour &c : contours)                                 // drawContours(-1, thickness 1): closed polylines
+        for (size_t k = 0; k < c.size(); ++k) draw_segment(img, c[k], c[(k + 1) % c.size()], bgr);
+}
+}  // namespace
+
+Image8 draw_overlay(const Image8 &src, const std::vector<Contour> &contours)
+{
+    Image8 img = to_bgr(src);
+    draw_contours(img, contours, kPalette[0]);
+    return img;
+}
+
+Image8 draw_overlay(const Image8 &src, const std::vector<medseg::ClassContours> &groups)
+{
+    Image8 img = to_bgr(src);
+    for (size_t g = 0; g < groups.size(); ++g) draw_contours(img, groups[g].contours, kPalette[g % 5]);
+    return img;
+}
+
+std::string polygon_json_text(const std::vector<medseg::ClassContours> &groups, const std::string &base_name, int original_width,
+                              int original_height)
+{
+    return medseg::polygon_json_text(groups, base_name, original_width, original_height);
+}
+
+void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const Image8 &normalized_tile, const std::string &output_dir,
+                           const std::string &base_name, int original_width, int original_height, std::ostream &console)
+{
+    try {
+        console << "Processing Mask: " << base_name + ".png" << std::endl;
+        console << "Original Size: " << original_width << "x" << original_height << std::endl;
+        console << "Scaled Size: " << normalized_tile.cols << "x" << normalized_tile.rows << std::endl;
+        size_t total = 0;
+        for (const auto &g : groups) total += g.contours.size();
+        if (total == 0) {
+            console << "Warning: No Contours Detected" << std::endl;
+            return;
+        }
+        for (const auto &g : groups) console << "Extracted " << g.contours.size() << " Contours of class " << g.cls << std::endl;
+        const std::string overlay_path = output_dir + "/" + base_name + "_contour_overlay.png";
+        if (!medseg::write_png(overlay_path, draw_overlay(normalized_tile, groups), /*level0=*/true))
+            throw std::runtime_error("Fail to Save Overlay PNG: " + overlay_path);
+        console << "Overlay Image Saved to: " << overlay_path << std::endl;
+        const double scale_x = static_cast<double>(original_width) / normalized_tile.cols;
+        const double scale_y = static_cast<double>(original_height) / normalized_tile.rows;
+        std::vector<medseg::ClassContours> mapped;
+        for (const auto &g : groups) mapped.push_back({ g.cls, map_contour_points(g.contours, scale_x, scale_y) });
+        const std::string output_json_path = output_dir + "/" + base_name + ".json";
+        std::ofstream f(output_json_path);
+        if (!f.is_open()) throw std::runtime_error("Fail to Create JSON File: " + output_json_path);
+        f << medseg::polygon_json_text(mapped, base_name, original_width, original_height);
+        f.flush();
+        console << "JSON Saved to: " << output_json_path << std::endl;
+    } catch (const std::exception &e) {
+        std::cerr << "Processing Failure: " << e.what() << std::endl;
+    }
 }
 
 void create_overlay_image(const std::vector<Contour> &contours, const std::string &original_png_path,

@@ -3,6 +3,8 @@
 // `labels == i` pass per component, the reference's O(nc*H*W) loops at :41 and :71), separable 3x3 min/max.
 #include "../../include/medseg/postprocess.h"
 
+#include "../../include/mi_unet.h"
+
 #include <algorithm>
 #include <numeric>
 #include <stdexcept>
@@ -98,18 +100,22 @@ void morph3x3(const std::vector<uint8_t> &src, std::vector<uint8_t> &dst, int w,
 
 }  // namespace
 
-medseg::Image8 postprocess_mask(const medseg::Image8 &src)
+medseg::Image8 postprocess_mask(const medseg::Image8 &src) { return postprocess_mask(src, FOREGROUND_VALUE, MIN_AREA_RATIO); }
+
+medseg::Image8 postprocess_mask(const medseg::Image8 &src, int cls, float min_area_frac)
 {
     if (src.empty() || src.channels != 1) throw std::runtime_error("postprocess_mask: need a non-empty single-channel mask");
+    if (cls < 1 || cls > 255) throw std::runtime_error("postprocess_mask: class outside 1..255");
+    const uint8_t fgv = (uint8_t)cls;
     const int w = src.cols, h = src.rows;
     const size_t n = (size_t)w * h;
-    const int min_area = static_cast<int>(w * h * MIN_AREA_RATIO);          // evaluated in float, src/postprocess.cpp:30,:66
+    const int min_area = mi_unet_target_min_area(h, w, min_area_frac);      // evaluated in float, src/postprocess.cpp:30,:66
     std::vector<uint8_t> mask(src.data);
 
-    // 1. fill holes: components of (mask != 2) whose bbox touches no edge and whose area < min_area
+    // 1. fill holes: components of (mask != cls) whose bbox touches no edge and whose area < min_area
     {
         std::vector<uint8_t> inv(n);
-        for (size_t i = 0; i < n; ++i) inv[i] = mask[i] == FOREGROUND_VALUE ? 0 : 255;
+        for (size_t i = 0; i < n; ++i) inv[i] = mask[i] == fgv ? 0 : 255;
         const Labelling L = label8(inv.data(), w, h);
         std::vector<uint8_t> fill(L.stats.size(), 0);
         for (size_t r = 1; r < L.stats.size(); ++r) {
@@ -117,17 +123,17 @@ medseg::Image8 postprocess_mask(const medseg::Image8 &src)
             fill[r] = s.area > 0 && s.left > 0 && s.top > 0 && s.right < w - 1 && s.bottom < h - 1 && s.area < min_area;
         }
         for (size_t i = 0; i < n; ++i)
-            if (L.labels[i] && fill[L.labels[i]]) mask[i] = FOREGROUND_VALUE;
+            if (L.labels[i] && fill[L.labels[i]]) mask[i] = fgv;
     }
     // 2. binarise + 3x3 open
     std::vector<uint8_t> bin(n), er, op;
-    for (size_t i = 0; i < n; ++i) bin[i] = mask[i] == FOREGROUND_VALUE ? 255 : 0;
+    for (size_t i = 0; i < n; ++i) bin[i] = mask[i] == fgv ? 255 : 0;
     morph3x3(bin, er, w, h, false);
     morph3x3(er, op, w, h, true);
-    // 3. area filter, 4. map back to {0, 2}
+    // 3. area filter, 4. map back to {0, cls}
     const Labelling L = label8(op.data(), w, h);
     medseg::Image8 out(h, w, 1, 0);
     for (size_t i = 0; i < n; ++i)
-        if (L.labels[i] && L.stats[L.labels[i]].area >= min_area) out.data[i] = FOREGROUND_VALUE;
+        if (L.labels[i] && L.stats[L.labels[i]].area >= min_area) out.data[i] = fgv;
     return out;
 }

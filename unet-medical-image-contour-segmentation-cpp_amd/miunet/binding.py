@@ -26,6 +26,9 @@ EXPORTS = [
     "mi_unet_group_segment_raw16", "mi_unet_group_destroy", "mi_unet_shard_range",
     "mi_unet_tile_axis", "mi_unet_infer_tiled_u8", "mi_unet_infer_tiled_raw16", "mi_unet_segment_tiled_raw16",
     "mi_unet_set_tile_blend", "mi_unet_get_tile_blend", "mi_unet_tile_blend_weights",
+    "mi_unet_target_min_area", "mi_unet_set_targets", "mi_unet_get_targets", "mi_unet_postprocess_masks_multi",
+    "mi_unet_segment_raw16_multi", "mi_unet_segment_tiled_raw16_multi", "mi_unet_group_set_targets",
+    "mi_unet_group_segment_raw16_multi",
 ]
 
 
@@ -54,6 +57,22 @@ class LayerInfo(C.Structure):
 
 class TileBlend(C.Structure):
     _fields_ = [("mode", C.c_int), ("sigma_scale", C.c_float), ("mirror", C.c_int)]
+
+
+class Target(C.Structure):
+    _fields_ = [("cls", C.c_int), ("min_area_frac", C.c_float)]
+
+
+MAX_TARGETS = 5
+DEFAULT_TARGETS = [(2, 0.06)]
+
+
+def _target_array(targets):
+    """[(cls, min_area_frac), ...] -> (Target array or None, n); None restores the default.  The library checks the values."""
+    if targets is None:
+        return None, 0
+    targets = list(targets)
+    return (Target * max(len(targets), 1))(*[Target(int(c), float(f)) for c, f in targets]), len(targets)
 
 
 BLEND_MODES = {"owner": 0, "constant": 1, "gaussian": 2}
@@ -147,6 +166,14 @@ def lib():
         L.mi_unet_set_tile_blend.argtypes = [C.c_void_p, C.POINTER(TileBlend)]
         L.mi_unet_get_tile_blend.argtypes = [C.c_void_p, C.POINTER(TileBlend)]
         L.mi_unet_tile_blend_weights.argtypes = [C.c_int, C.POINTER(TileBlend), C.c_void_p]
+        L.mi_unet_target_min_area.argtypes = [C.c_int, C.c_int, C.c_float]
+        L.mi_unet_set_targets.argtypes = [C.c_void_p, C.POINTER(Target), C.c_int]
+        L.mi_unet_get_targets.argtypes = [C.c_void_p, C.POINTER(Target), C.c_int, C.POINTER(C.c_int)]
+        L.mi_unet_postprocess_masks_multi.argtypes = L.mi_unet_postprocess_masks.argtypes
+        L.mi_unet_segment_raw16_multi.argtypes = L.mi_unet_segment_raw16.argtypes
+        L.mi_unet_segment_tiled_raw16_multi.argtypes = L.mi_unet_segment_tiled_raw16.argtypes
+        L.mi_unet_group_set_targets.argtypes = [C.c_void_p, C.POINTER(Target), C.c_int]
+        L.mi_unet_group_segment_raw16_multi.argtypes = L.mi_unet_group_segment_raw16.argtypes
         _LIB = L
     return _LIB
 
@@ -401,6 +428,61 @@ class Engine:
         cont = None if n < 0 else [[tuple(q) for q in xy[start[k]:start[k + 1]].tolist()] for k in range(n)]
         return norm, mask, cont
 
+    # ---- targets (mi_unet_set_targets): which classes the _multi calls segment, and each one's area rule
+    def set_targets(self, targets):
+        """targets: [(cls, min_area_frac), ...] (at most MAX_TARGETS); None or [] restores the default [(2, 0.06)]"""
+        arr, n = _target_array(targets)
+        _check(lib().mi_unet_set_targets(self._h, arr, n))
+
+    def get_targets(self):
+        arr, n = (Target * MAX_TARGETS)(), C.c_int()
+        _check(lib().mi_unet_get_targets(self._h, arr, MAX_TARGETS, C.byref(n)))
+        return [(arr[k].cls, float(arr[k].min_area_frac)) for k in range(n.value)]
+
+    def postprocess_masks_multi(self, labels: np.ndarray):
+        """labels u8 [B,H,W] -> u8 [B,K,H,W], plane k in {0, cls_k}"""
+        labels = np.ascontiguousarray(labels, np.uint8)
+        out = np.empty((labels.shape[0], len(self.get_targets())) + labels.shape[1:], np.uint8)
+        _check(lib().mi_unet_postprocess_masks_multi(self._h, _ptr(labels), labels.shape[0], _ptr(out)))
+        return out
+
+    def segment_raw16_multi_prepare(self, raws, cap_points=8192, cap_contours=64):
+        """argument block of mi_unet_segment_raw16_multi for the targets set now (segment_raw16_prepare with [B][K] outputs)"""
+        c, k = self.cfg, len(self.get_targets())
+        raws, ptrs, ws, hs, b = self._raw_args(raws)
+        return dict(raws=raws, ptrs=ptrs, ws=ws, hs=hs, b=b, k=k, cap_points=cap_points, cap_contours=cap_contours,
+                    tiles=self._tile_buf(b), masks=np.empty((b, k, c.height, c.width), np.uint8),
+                    xy=np.zeros((b, k, cap_points, 2), np.int32), start=np.zeros((b, k, cap_contours + 1), np.int32),
+                    counts=np.zeros((b, k), np.int32))
+
+    def segment_raw16_multi_run(self, p):
+        _check(lib().mi_unet_segment_raw16_multi(self._h, p["ptrs"], p["ws"], p["hs"], p["b"], _ptr(p["tiles"]), _ptr(p["masks"]),
+                                                 _ptr(p["xy"]), p["cap_points"], _ptr(p["start"]), p["cap_contours"], _ptr(p["counts"])))
+
+    def segment_raw16_multi(self, raws, cap_points=8192, cap_contours=64, raw_arrays=False):
+        """RAW16 images -> (tiles, masks 0/255 u8 [B,K,H,W], contours[b][k] = list of contours, or None where a capacity of that
+        (image, target) overflowed); raw_arrays=True returns (tiles, masks, xy, start, counts) as the C call filled them"""
+        p = self.segment_raw16_multi_prepare(raws, cap_points, cap_contours)
+        self.segment_raw16_multi_run(p)
+        if raw_arrays:
+            return p["tiles"], p["masks"], p["xy"], p["start"], p["counts"]
+        return p["tiles"], p["masks"], _decode_multi(p["xy"], p["start"], p["counts"])
+
+    def segment_tiled_raw16_multi(self, planes, halo: int, cap_points=65536, cap_contours=256, want_norm=True, raw_arrays=False):
+        """-> (norm or None, masks 0/255 u8 [K,H,W], contours[k] in full-image coordinates, None where a capacity overflowed)"""
+        k = len(self.get_targets())
+        arrs, ptrs, hh, ww = self._tiled_planes(planes)
+        norm = self._norm_buf(hh, ww) if want_norm else None
+        mask = np.empty((k, hh, ww), np.uint8)
+        xy = np.zeros((k, cap_points, 2), np.int32)
+        start = np.zeros((k, cap_contours + 1), np.int32)
+        counts = np.zeros(k, np.int32)
+        _check(lib().mi_unet_segment_tiled_raw16_multi(self._h, ptrs, ww, hh, halo, _ptr(norm), _ptr(mask), _ptr(xy), cap_points,
+                                                       _ptr(start), cap_contours, _ptr(counts)))
+        if raw_arrays:
+            return norm, mask, xy, start, counts
+        return norm, mask, _decode_multi(xy[None], start[None], counts[None])[0]
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -485,6 +567,18 @@ class Engine:
                      ms=arr[i].ms) for i in range(min(n.value, cap))]
 
 
+def _decode_multi(xy, start, counts):
+    """contour arrays [B][K]... -> contours[b][k] = [[(x, y), ...], ...] or None"""
+    return [[None if counts[i, k] < 0 else
+             [[tuple(q) for q in xy[i, k, start[i, k, c]:start[i, k, c + 1]].tolist()] for c in range(counts[i, k])]
+             for k in range(counts.shape[1])] for i in range(counts.shape[0])]
+
+
+def target_min_area(height: int, width: int, frac: float) -> int:
+    """mi_unet_target_min_area: the pixel count behind a target's min_area_frac on a height x width image (needs no device)"""
+    return int(lib().mi_unet_target_min_area(height, width, frac))
+
+
 def shard_range(n_items: int, rank: int, world: int):
     lo, hi = C.c_int(), C.c_int()
     _check(lib().mi_unet_shard_range(n_items, rank, world, C.byref(lo), C.byref(hi)))
@@ -564,6 +658,35 @@ class Group:
 
     def set_postprocess(self, on: bool):
         _check(lib().mi_unet_group_set_postprocess(self._g, int(on)))
+
+    def set_targets(self, targets):
+        """Engine.set_targets on every rank"""
+        arr, n = _target_array(targets)
+        _check(lib().mi_unet_group_set_targets(self._g, arr, n))
+
+    def _n_targets(self):
+        n = C.c_int()
+        _check(lib().mi_unet_get_targets(lib().mi_unet_group_handle(self._g, 0), None, 0, C.byref(n)))
+        return n.value
+
+    def segment_raw16_multi(self, raws, cap_points=8192, cap_contours=64, raw_arrays=False):
+        """Engine.segment_raw16_multi, the batch split across the ranks"""
+        raws = [np.ascontiguousarray(r, dtype=np.uint16) for r in raws]
+        n, c, k = len(raws), self.cfg, self._n_targets()
+        b = n // c.in_ch
+        ptrs = (C.c_void_p * n)(*[r.ctypes.data for r in raws])
+        ws = (C.c_int * n)(*[r.shape[1] for r in raws])
+        hs = (C.c_int * n)(*[r.shape[0] for r in raws])
+        tiles = np.empty((b, c.height, c.width) if c.in_ch == 1 else (b, c.height, c.width, c.in_ch), np.uint8)
+        masks = np.empty((b, k, c.height, c.width), np.uint8)
+        xy = np.zeros((b, k, cap_points, 2), np.int32)
+        start = np.zeros((b, k, cap_contours + 1), np.int32)
+        counts = np.zeros((b, k), np.int32)
+        _check(lib().mi_unet_group_segment_raw16_multi(self._g, ptrs, ws, hs, b, _ptr(tiles), _ptr(masks), _ptr(xy), cap_points,
+                                                       _ptr(start), cap_contours, _ptr(counts)))
+        if raw_arrays:
+            return tiles, masks, xy, start, counts
+        return tiles, masks, _decode_multi(xy, start, counts)
 
     def infer(self, imgs: np.ndarray, want_logits=False):
         imgs = np.ascontiguousarray(imgs, dtype=np.uint8)

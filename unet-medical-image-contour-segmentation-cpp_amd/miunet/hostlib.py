@@ -17,7 +17,8 @@ _i32 = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_process_image_batch", "medseg_cleanup_resources", "medseg_get_log_path",
            "medseg_preprocess_raw", "medseg_resample_normalize", "medseg_postprocess_mask", "medseg_mask_to_image",
            "medseg_extract_contours", "medseg_map_points", "medseg_generate_json", "medseg_draw_overlay", "medseg_process_single_mask",
-           "medseg_write_png", "medseg_read_png"]
+           "medseg_write_png", "medseg_read_png", "medseg_postprocess_mask_target", "medseg_set_targets", "medseg_get_targets",
+           "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups"]
 
 
 def lib():
@@ -44,6 +45,12 @@ def lib():
         L.medseg_process_single_mask.restype = None
         L.medseg_write_png.argtypes = [C.c_char_p, _u8, C.c_int, C.c_int, C.c_int, C.c_int]
         L.medseg_read_png.argtypes = [C.c_char_p, C.c_int, _u8, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _i = C.POINTER(C.c_int)
+        L.medseg_postprocess_mask_target.argtypes = [_u8, C.c_int, C.c_int, C.c_int, C.c_float, _u8]
+        L.medseg_set_targets.argtypes = [_i, C.POINTER(C.c_float), C.c_int]
+        L.medseg_get_targets.argtypes = [_i, C.POINTER(C.c_float), C.c_int]
+        L.medseg_polygon_json_text_groups.argtypes = [_i32, _i32, _i, _i, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+        L.medseg_draw_overlay_groups.argtypes = [_u8, C.c_int, C.c_int, _i32, _i32, _i, _i, C.c_int, _u8]
         _LIB = L
     return _LIB
 
@@ -70,6 +77,60 @@ def postprocess_mask(mask):
     if lib().medseg_postprocess_mask(m, m.shape[1], m.shape[0], out):
         raise RuntimeError("postprocess_mask failed")
     return out
+
+
+def postprocess_mask_target(mask, cls, min_area_frac):
+    """postprocess_mask(src, cls, min_area_frac): u8 [h][w] label map -> u8 [h][w] in {0, cls}"""
+    m = np.ascontiguousarray(mask, np.uint8)
+    out = np.empty_like(m)
+    if lib().medseg_postprocess_mask_target(m, m.shape[1], m.shape[0], int(cls), float(min_area_frac), out):
+        raise RuntimeError("postprocess_mask failed")
+    return out
+
+
+def _flatten_groups(groups):
+    """[(cls, [contour, ...]), ...] -> flattened points, starts, class and contour count per group"""
+    contours = [c for _, cs in groups for c in cs]
+    flat = np.array([p for c in contours for p in c], np.int32).reshape(-1, 2)
+    start = np.zeros(len(contours) + 1, np.int32)
+    start[1:] = np.cumsum([len(c) for c in contours])
+    n = len(groups)
+    return (np.ascontiguousarray(flat).reshape(-1), start, (C.c_int * max(n, 1))(*[int(c) for c, _ in groups]),
+            (C.c_int * max(n, 1))(*[len(cs) for _, cs in groups]), n)
+
+
+def polygon_json_text_groups(groups, base_name, ow, oh) -> bytes:
+    """Mask2Polygon::polygon_json_text for (cls, contours) groups in target order"""
+    flat, start, cls, cnt, n = _flatten_groups(groups)
+    cap = 4096 + 160 * (len(start) + flat.size)
+    buf = C.create_string_buffer(cap)
+    got = lib().medseg_polygon_json_text_groups(flat, start, cls, cnt, n, base_name.encode(), ow, oh, buf, cap)
+    if got < 0:
+        raise RuntimeError("polygon_json_text_groups: buffer too small")
+    return buf.raw[:got]
+
+
+def draw_overlay_groups(gray, groups):
+    """gray u8 [h][w] + (cls, contours) groups -> BGR u8 [h][w][3], group g in colour g of the palette"""
+    g = np.ascontiguousarray(gray, np.uint8)
+    flat, start, cls, cnt, n = _flatten_groups(groups)
+    out = np.empty(g.shape + (3,), np.uint8)
+    if lib().medseg_draw_overlay_groups(g, g.shape[1], g.shape[0], flat, start, cls, cnt, n, out.reshape(-1)):
+        raise RuntimeError("draw_overlay failed")
+    return out
+
+
+def set_targets(targets) -> bool:
+    """MedicalSeg::set_targets: [(cls, min_area_frac), ...]; [] restores the default"""
+    n = len(targets)
+    return lib().medseg_set_targets((C.c_int * max(n, 1))(*[int(c) for c, _ in targets]),
+                                    (C.c_float * max(n, 1))(*[float(f) for _, f in targets]), n) == 0
+
+
+def get_targets():
+    cls, frac = (C.c_int * 8)(), (C.c_float * 8)()
+    n = lib().medseg_get_targets(cls, frac, 8)
+    return [(cls[i], float(frac[i])) for i in range(n)]
 
 
 def mask_to_image(mask):
