@@ -301,6 +301,78 @@ def test_set_targets_validation_clone_and_existing_calls():
         assert len(eng.get_targets()) == 3
 
 
+@functools.lru_cache(maxsize=None)
+def single_target_run():
+    """the entry points without _multi on the four-class maps, B = 5 on max_batch 2 (micro-batches 2, 2, 1): labels of infer_raw16,
+    the labels with set_postprocess(1), the arrays of segment_raw16 and its stage times, and the same call with targets set"""
+    L = binding.lib()
+    with engine(4) as eng:
+        _, labels, _ = eng.infer_raw16(crafted(5))
+        eng.set_postprocess(True)
+        _, post, _ = eng.infer_raw16(crafted(5))
+        eng.set_postprocess(False)
+        out = call_segment(L.mi_unet_segment_raw16, eng._h, crafted(5), 0, 4096, 64, 64, 64)
+        stages = eng.last_stage_ms()
+        eng.set_targets(K3)
+        with_targets = call_segment(L.mi_unet_segment_raw16, eng._h, crafted(5), 0, 4096, 64, 64, 64)
+    return labels, post, out, stages, with_targets
+
+
+def oracle_chain(labels):
+    """postprocess_mask -> mask_to_image -> find_contours of the CPU oracle on one label map"""
+    pm = orc.postprocess_mask(labels)
+    vis = orc.mask_to_image(pm)
+    return pm, vis, orc.find_contours(vis)
+
+
+def assert_oracle_segment(labels, out):
+    tiles, masks, xy, start, counts = out
+    for b in range(len(labels)):
+        pm, vis, cont = oracle_chain(labels[b])
+        assert set(np.unique(vis)) == {0, 255}, b                              # the 832-pixel class-2 block passes min_area 245
+        assert (labels[b] == 1).any() and (labels[b] == 3).any()               # ... next to classes the picture must not show
+        assert np.array_equal(masks[b], vis), b
+        assert counts[b] == len(cont) >= 1, b
+        assert contours_of(xy[b], start[b], counts[b]) == cont, b
+
+
+def test_segment_raw16_on_four_class_maps_equals_the_oracle_chain():
+    labels, _, out, stages, _ = single_target_run()
+    assert int(64 * 64 * np.float32(0.06)) == 245
+    for b in range(5):
+        assert np.array_equal(labels[b], crafted_labels(b))
+        assert np.array_equal(out[0][b], orc.preprocess_raw(crafted(5)[b], 64, 64))
+    assert_oracle_segment(labels, out)
+    assert set(stages) == set(binding.Engine.STAGES)
+    for name, ms in stages.items():
+        assert ms > 0, (name, stages)
+
+
+def test_set_postprocess_infer_raw16_equals_the_oracle_in_place():
+    labels, post, _, _, _ = single_target_run()
+    for b in range(5):
+        want = orc.postprocess_mask(labels[b])
+        assert np.array_equal(post[b], want), b
+        assert set(np.unique(post[b])) == {0, 2}, b
+
+
+def test_targets_on_the_handle_do_not_reach_segment_raw16():
+    labels, _, _, _, with_targets = single_target_run()
+    assert_oracle_segment(labels, with_targets)                                # still class 2 at 6 %, not K3
+
+
+def test_segment_tiled_raw16_equals_the_oracle_chain_on_the_stitched_labels():
+    big = raw_of(crafted_big())
+    with engine(4, max_batch=4) as eng:
+        _, labels, _ = eng.infer_tiled_raw16(big, 8)
+        _, mask, cont = eng.segment_tiled_raw16(big, 8, cap_points=8192, cap_contours=128)
+    assert np.array_equal(labels, crafted_big())
+    assert int(80 * 112 * np.float32(0.06)) == 537                             # min_area of the full image: the 832-pixel block stays
+    pm, vis, want = oracle_chain(labels)
+    assert set(np.unique(vis)) == {0, 255}
+    assert np.array_equal(mask, vis) and cont == want and len(want) >= 1
+
+
 def test_group_of_two_ranks_equals_the_single_handle():
     L = binding.lib()
     rs, targets = crafted(3), [(1, 0.0), (3, 0.01)]

@@ -153,55 +153,67 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
 }
 
 // postprocess_mask on the device, in place on `d_labels`; the network's scratch buffer s1 is free once the head has run
-int device_postprocess(mi_unet *h, const uint8_t *d_in, uint8_t *d_out, int B)
+static int device_postprocess(mi_unet *h, uint8_t *d_labels, int B)
 {
     const int H = h->cfg.height, W = h->cfg.width;
     const size_t cap = sizeof(float) * (size_t)h->cfg.max_batch * H * W * h->ch[0];
     if (postprocess_workspace_bytes(B, H, W) > cap) return fail(MI_UNET_EARG, "postprocess workspace does not fit the scratch buffer");
-    const int min_area = mi_unet_target_min_area(H, W, 0.06f);       // src/postprocess.cpp:9, :30, :66 (evaluated in float)
-    const hipError_t e = launch_postprocess_masks(d_in, d_out, B, H, W, min_area, h->d_s1, h->stream);
-    if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
+    return enqueue_tail(h, d_labels, B, H, W, default_targets(H, W), d_labels, h->d_s1, nullptr, nullptr, h->stream);
+}
+
+int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const TargetTable &t, uint8_t *d_planes, void *ws,
+                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where)
+{
+    hipError_t e = t.K > 0 ? launch_postprocess_masks_multi(d_labels, d_planes, B, H, W, t, ws, s) : hipSuccess;
+    if (e != hipSuccess) return fail(MI_UNET_EHIP, where + "postprocess launch: " + hipGetErrorString(e));
+    if (between) HIP_TRY(hipEventRecord(between, s));
+    if (!cl) return 0;
+    int *const d_cont = h->d_cont;
+    e = launch_mask_to_image_binary(d_planes, d_planes, (size_t)cl->planes * H * W, s);
+    if (e == hipSuccess)
+        e = launch_extract_contours(d_planes, cl->planes, H, W, cl->xy(d_cont), cl->cap_points, cl->start(d_cont), cl->cap_contours,
+                                    cl->count(d_cont), ws, s);
+    if (e != hipSuccess) return fail(MI_UNET_EHIP, where + "segment launch: " + hipGetErrorString(e));
     return 0;
 }
 
-TargetTable target_table(const mi_unet *h, int H, int W)
+TargetTable target_table(const mi_unet_target *targets, int n, int H, int W)
 {
     TargetTable t;
-    t.K = h->n_targets;
-    for (int k = 0; k < t.K; ++k) {
-        t.cls[k] = h->targets[k].cls;
-        t.min_area[k] = mi_unet_target_min_area(H, W, h->targets[k].min_area_frac);
+    t.K = n;
+    for (int k = 0; k < n; ++k) {
+        t.cls[k] = targets[k].cls;
+        t.min_area[k] = mi_unet_target_min_area(H, W, targets[k].min_area_frac);       // src/postprocess.cpp:9, :30, :66 (evaluated in float)
     }
     return t;
 }
 
-int ensure_tail_workspace(mi_unet *h, size_t bytes)
-{
-    if (bytes <= h->tail_ws_bytes) return 0;
-    if (h->tail_stream) HIP_TRY(hipStreamSynchronize(h->tail_stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->tail_ws_bytes = 0;
-    HIP_TRY(h->d_tail_ws.reset(bytes));
-    h->tail_ws_bytes = bytes;
-    return 0;
-}
+TargetTable target_table(const mi_unet *h, int H, int W) { return target_table(h->targets, h->n_targets, H, W); }
+TargetTable default_targets(int H, int W) { return target_table(&kDefaultTarget, 1, H, W); }
 
-int ensure_multi_buffers(mi_unet *h, size_t bytes)
+int ensure_tail_buffers(mi_unet *h, size_t ws_bytes, size_t plane_bytes)
 {
-    if (bytes <= h->multi_cap) return 0;
+    if (ws_bytes <= h->tail_ws_bytes && plane_bytes <= h->multi_cap) return 0;
     if (h->tail_stream) HIP_TRY(hipStreamSynchronize(h->tail_stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->multi_cap = 0;
-    HIP_TRY(h->d_multi.reset(bytes));
-    for (auto &b : h->h_multi) HIP_TRY(b.reset(bytes));
-    h->multi_cap = bytes;
+    if (ws_bytes > h->tail_ws_bytes) {
+        h->tail_ws_bytes = 0;
+        HIP_TRY(h->d_tail_ws.reset(ws_bytes));
+        h->tail_ws_bytes = ws_bytes;
+    }
+    if (plane_bytes > h->multi_cap) {
+        h->multi_cap = 0;
+        HIP_TRY(h->d_multi.reset(plane_bytes));
+        for (auto &b : h->h_multi) HIP_TRY(b.reset(plane_bytes));
+        h->multi_cap = plane_bytes;
+    }
     return 0;
 }
 
 int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits)
 {
     if (int rc = run_microbatch(h, d_imgs, B, d_labels, d_logits)) return rc;
-    return h->postprocess ? device_postprocess(h, d_labels, d_labels, B) : 0;
+    return h->postprocess ? device_postprocess(h, d_labels, B) : 0;
 }
 
 int check_handle(mi_unet *h, bool need_weights)
@@ -368,9 +380,9 @@ hipStream_t engine_stream(const mi_unet_t *h) { return h->stream; }
 
 // contour outputs of `bm` images: device -> pinned mirror (async, behind the kernels), and after the stream has been
 // synchronised only what exists goes on to the caller's arrays (the capacity is mostly air: 2 x 32768 ints per image)
-int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours)
+int grow_contour_buffers(mi_unet *h, const ContourLayout &cl)
 {
-    const size_t need = (size_t)bm * ((size_t)cap_points * 2 + cap_contours + 1 + 1);
+    const size_t need = cl.ints();
     if (need <= h->cont_cap) return 0;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->cont_cap = 0;
@@ -380,18 +392,18 @@ int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours)
     return 0;
 }
 
-int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int half)
+int contours_to_pinned(mi_unet *h, const ContourLayout &cl, hipStream_t s, int half)
 {
     // counts and starts whole (small), the points whole as well: 4 MB at 16 images rides PCIe in 0.1 ms once it is pinned
-    const size_t n = (size_t)bm * ((size_t)cap_points * 2 + cap_contours + 1 + 1);
-    HIP_TRY(hipMemcpyAsync(h->h_cont + half * h->cont_cap, h->d_cont, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->h_cont + half * h->cont_cap, h->d_cont, cl.ints() * sizeof(int), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
-void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contours, int32_t *xy, int32_t *start, int32_t *counts, int half)
+void contours_to_caller(const mi_unet *h, const ContourLayout &cl, int32_t *xy, int32_t *start, int32_t *counts, int half)
 {
-    const int *p_xy = h->h_cont + half * h->cont_cap, *p_start = p_xy + (size_t)bm * cap_points * 2, *p_count = p_start + (size_t)bm * (cap_contours + 1);
-    for (int i = 0; i < bm; ++i) {
+    const int *base = h->h_cont + half * h->cont_cap, *p_xy = cl.xy(base), *p_start = cl.start(base), *p_count = cl.count(base);
+    const int cap_points = cl.cap_points, cap_contours = cl.cap_contours;
+    for (int i = 0; i < cl.planes; ++i) {
         counts[i] = p_count[i];
         memcpy(start + (size_t)i * (cap_contours + 1), p_start + (size_t)i * (cap_contours + 1), sizeof(int) * (cap_contours + 1));
         if (p_count[i] > 0) {
@@ -593,25 +605,6 @@ int mi_unet_set_postprocess(mi_unet_t *h, int on)
     return MI_UNET_OK;
 }
 
-int mi_unet_postprocess_masks(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out)
-{
-    if (int rc = check_handle(h, false)) return rc;
-    if (!labels || !out || B < 0) return fail(MI_UNET_EARG, "mi_unet_postprocess_masks: bad argument");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    const size_t hw = (size_t)h->cfg.height * h->cfg.width;
-    hipStream_t s = h->stream;
-    for (int b0 = 0; b0 < B; b0 += h->cfg.max_batch) {
-        const int bm = (B - b0) < h->cfg.max_batch ? (B - b0) : h->cfg.max_batch;
-        memcpy(h->h_labels, labels + b0 * hw, bm * hw);
-        HIP_TRY(hipMemcpyAsync(h->d_labels, h->h_labels, bm * hw, hipMemcpyHostToDevice, s));
-        if (int rc = device_postprocess(h, h->d_labels, h->d_labels, bm)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->h_labels, h->d_labels, bm * hw, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        memcpy(out + b0 * hw, h->h_labels, bm * hw);
-    }
-    return MI_UNET_OK;
-}
-
 int mi_unet_target_min_area(int H, int W, float frac) { return static_cast<int>(W * H * frac); }
 
 int mi_unet_set_targets(mi_unet_t *h, const mi_unet_target *t, int n)
@@ -619,8 +612,7 @@ int mi_unet_set_targets(mi_unet_t *h, const mi_unet_target *t, int n)
     if (int rc = check_handle(h, false)) return rc;
     if (n < 0 || n > MI_UNET_MAX_TARGETS)
         return fail(MI_UNET_EARG, "mi_unet_set_targets: " + std::to_string(n) + " targets (at most " + std::to_string(MI_UNET_MAX_TARGETS) + ")");
-    const mi_unet_target def{ 2, 0.06f };
-    if (!t || n == 0) { t = &def; n = 1; }
+    if (!t || n == 0) { t = &kDefaultTarget; n = 1; }
     for (int k = 0; k < n; ++k) {
         if (t[k].cls < 1 || t[k].cls >= h->cfg.classes)
             return fail(MI_UNET_EARG, "mi_unet_set_targets: class " + std::to_string(t[k].cls) + " is outside 1.." + std::to_string(h->cfg.classes - 1));
@@ -644,31 +636,45 @@ int mi_unet_get_targets(const mi_unet_t *h, mi_unet_target *t, int cap, int *n)
     return MI_UNET_OK;
 }
 
-int mi_unet_postprocess_masks_multi(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out)
+// mi_unet_postprocess_masks and its _multi form: label maps up, the chain per micro-batch, masks down.  The first runs the reference's
+// target in place in the network's scratch buffer (device_postprocess), _multi the handle's K targets into d_multi on the tail workspace.
+static int postprocess_masks_call(mi_unet_t *h, const char *fn, bool multi, const uint8_t *labels, int B, uint8_t *out)
 {
     if (int rc = check_handle(h, false)) return rc;
-    if (!labels || !out || B < 0) return fail(MI_UNET_EARG, "mi_unet_postprocess_masks_multi: bad argument");
+    if (!labels || !out || B < 0) return fail(MI_UNET_EARG, std::string(fn) + ": bad argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
     const int H = h->cfg.height, W = h->cfg.width, Bm = h->cfg.max_batch;
     const size_t hw = (size_t)H * W;
-    const TargetTable tab = target_table(h, H, W);
+    const TargetTable tab = multi ? target_table(h, H, W) : default_targets(H, W);
     const size_t K = (size_t)tab.K;
-    if ((size_t)std::min(B, Bm) * K * hw > 0x7FFFFFFFull)
-        return fail(MI_UNET_EARG, "mi_unet_postprocess_masks_multi: max_batch x targets x height x width exceeds 2^31 - 1");
+    if (multi && (size_t)std::min(B, Bm) * K * hw > 0x7FFFFFFFull)
+        return fail(MI_UNET_EARG, std::string(fn) + ": max_batch x targets x height x width exceeds 2^31 - 1");
     hipStream_t s = h->stream;
     for (int b0 = 0; b0 < B; b0 += Bm) {
         const int bm = std::min(Bm, B - b0);
-        if (int rc = ensure_tail_workspace(h, postprocess_workspace_bytes(bm * tab.K, H, W))) return rc;
-        if (int rc = ensure_multi_buffers(h, bm * K * hw)) return rc;
+        if (multi)
+            if (int rc = ensure_tail_buffers(h, postprocess_workspace_bytes(bm * tab.K, H, W), bm * K * hw)) return rc;
+        uint8_t *const d_out = multi ? h->d_multi.get() : h->d_labels.get(), *const h_out = multi ? h->h_multi[0].get() : h->h_labels.get();
         memcpy(h->h_labels, labels + b0 * hw, bm * hw);
         HIP_TRY(hipMemcpyAsync(h->d_labels, h->h_labels, bm * hw, hipMemcpyHostToDevice, s));
-        const hipError_t e = launch_postprocess_masks_multi(h->d_labels, h->d_multi, bm, H, W, tab, h->d_tail_ws, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(h->h_multi[0], h->d_multi, bm * K * hw, hipMemcpyDeviceToHost, s));
+        if (int rc = multi ? enqueue_tail(h, h->d_labels, bm, H, W, tab, d_out, h->d_tail_ws, nullptr, nullptr, s)
+                           : device_postprocess(h, h->d_labels, bm))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(h_out, d_out, bm * K * hw, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        memcpy(out + b0 * K * hw, h->h_multi[0], bm * K * hw);
+        memcpy(out + b0 * K * hw, h_out, bm * K * hw);
     }
     return MI_UNET_OK;
+}
+
+int mi_unet_postprocess_masks(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out)
+{
+    return postprocess_masks_call(h, "mi_unet_postprocess_masks", false, labels, B, out);
+}
+
+int mi_unet_postprocess_masks_multi(mi_unet_t *h, const uint8_t *labels, int B, uint8_t *out)
+{
+    return postprocess_masks_call(h, "mi_unet_postprocess_masks_multi", true, labels, B, out);
 }
 
 int mi_unet_extract_contours(mi_unet_t *h, const uint8_t *masks, int B, int32_t *xy, int cap_points, int32_t *start,
@@ -686,15 +692,16 @@ int mi_unet_extract_contours(mi_unet_t *h, const uint8_t *masks, int B, int32_t 
         const int bm = (B - b0) < h->cfg.max_batch ? (B - b0) : h->cfg.max_batch;
         if (contour_workspace_bytes(bm, H, W, cap_contours) > scratch)
             return fail(MI_UNET_EARG, "contour workspace does not fit the scratch buffer (cap_contours too large)");
-        if (int rc = grow_contour_buffers(h, bm, cap_points, cap_contours)) return rc;
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)bm * cap_points * 2, *d_count = d_start + (size_t)bm * (cap_contours + 1);
+        const ContourLayout cl{ bm, cap_points, cap_contours };
+        if (int rc = grow_contour_buffers(h, cl)) return rc;
+        int *const d_cont = h->d_cont;
         memcpy(h->h_labels, masks + b0 * hw, bm * hw);
         HIP_TRY(hipMemcpyAsync(h->d_labels, h->h_labels, bm * hw, hipMemcpyHostToDevice, s));
-        const hipError_t e = launch_extract_contours(h->d_labels, bm, H, W, d_xy, cap_points, d_start, cap_contours, d_count, h->d_s1, s);
+        const hipError_t e = launch_extract_contours(h->d_labels, bm, H, W, cl.xy(d_cont), cap_points, cl.start(d_cont), cap_contours, cl.count(d_cont), h->d_s1, s);
         if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("contour launch: ") + hipGetErrorString(e));
-        if (int rc = contours_to_pinned(h, bm, cap_points, cap_contours)) return rc;
+        if (int rc = contours_to_pinned(h, cl, s)) return rc;
         HIP_TRY(hipStreamSynchronize(s));
-        contours_to_caller(h, bm, cap_points, cap_contours, xy + (size_t)b0 * cap_points * 2, start + (size_t)b0 * (cap_contours + 1), counts + b0);
+        contours_to_caller(h, cl, xy + (size_t)b0 * cap_points * 2, start + (size_t)b0 * (cap_contours + 1), counts + b0);
     }
     return MI_UNET_OK;
 }

@@ -118,33 +118,33 @@ struct mi_unet {
     // stage timing of the last RAW-in call (mi_unet_last_stage_ms): event pairs per micro-batch, summed
     miunet::Event stage_ev[2][5], out_done[2];
     miunet::Event pre_ev[3][2];             // three pairs: micro-batch k + 2 is staged before k's times are read
-    miunet::PinnedBuf<uint8_t> h_labels2;   // second pinned result buffer: micro-batch k + 1 downloads while the host still copies k out
-    // third stream of the RAW-in entry points: postprocess, mask_to_image, contours and the downloads of micro-batch k run
-    // here while the engine's stream already works on the network of k + 1; own workspace (the network's scratch buffers,
-    // which the single-stage entry points borrow, are in use by then), second label buffer
+    miunet::PinnedBuf<uint8_t> h_labels2;   // second pinned label buffer (infer): micro-batch k + 1 downloads while the host still copies k out
+    // third stream of the RAW-in entry points: the tail (enqueue_tail) and the downloads of micro-batch k run here while the
+    // engine's stream already works on the network of k + 1; own workspace (the network's scratch buffers, which the
+    // single-stage entry points borrow, are in use by then), second label buffer
     hipStream_t tail_stream = nullptr;
     hipStream_t dl_stream = nullptr;          // tile downloads: behind the network of k, beside its tail and the upload of k + 1
     miunet::Event tiles_done[2];
     miunet::DeviceBuf<uint8_t> d_tail_ws;
     size_t tail_ws_bytes = 0;
-    miunet::DeviceBuf<uint8_t> d_tail_vis, d_labels2;
+    miunet::DeviceBuf<uint8_t> d_labels2;
     miunet::Event net_done[2], tail_ev[2][4];
     std::unique_ptr<miunet::CopyPool> copy_pool;   // helpers of the pageable -> pinned staging copy (created on first use)
     miunet::PinnedBuf<uint8_t> h_tiles[2];  // pinned mirrors of the tile buffers (a D2H into the caller's pageable memory would block the host)
     float stage_ms[MI_UNET_N_STAGES] = {};
-    // tiled entry points (mi_unet_infer_tiled_*): the full-size image, its label map / visualisation, logits and u16 planes stay
+    // tiled entry points (mi_unet_infer_tiled_*): the full-size image, its label map, logits and u16 planes stay
     // on the device for the whole call.  Grown on demand (ensure_tiled_buffers), owned by this handle, never shared with a clone.
     struct Tiled {
-        miunet::DeviceBuf<uint8_t> d_img, d_labels, d_vis;                           // u8 [H][W][in_ch] (+ slack to a dword), [H][W], [H][W]
-        miunet::PinnedBuf<uint8_t> h_img, h_out;                                     // pinned mirrors of d_img and of d_labels / d_vis
-        size_t px_cap = 0;                                                   // pixels the five above hold
+        miunet::DeviceBuf<uint8_t> d_img, d_labels;                                  // u8 [H][W][in_ch] (+ slack to a dword), [H][W]
+        miunet::PinnedBuf<uint8_t> h_img, h_out;                                     // pinned mirrors of d_img and of d_labels
+        size_t px_cap = 0;                                                   // pixels the four above hold
         miunet::DeviceBuf<float> d_logits;
         size_t logit_cap = 0;                                                // pixels
         miunet::DeviceBuf<uint16_t> d_raw;                                           // in_ch planes of u16 [H][W], device ...
         miunet::PinnedBuf<uint16_t> h_raw;                                           // ... and pinned
         size_t raw_cap = 0;                                                  // pixels per plane
         std::vector<miunet::Event> ev;                                               // stage boundaries of the last call
-        miunet::DeviceBuf<uint8_t> d_multi;                                          // the _multi form: [K][H][W] masks / pictures ...
+        miunet::DeviceBuf<uint8_t> d_multi;                                          // the segment forms: [K][H][W] masks / pictures ...
         miunet::PinnedBuf<uint8_t> h_multi;                                          // ... and their pinned mirror
         size_t multi_cap = 0;                                                // bytes
         miunet::DeviceBuf<float> d_acc;                                              // blending: fp32 accumulator [classes][H][W]
@@ -154,8 +154,9 @@ struct mi_unet {
     // and width (height + width floats), uploaded when the setting changes
     mi_unet_tile_blend blend{ MI_UNET_BLEND_OWNER, 0.125f, 0 };
     miunet::DeviceBuf<float> d_blend_w;
-    // mi_unet_set_targets: what the _multi entry points segment.  d_multi / h_multi hold their [B][K][H][W] planes (masks, then their
-    // 0 / 255 pictures in place) and the pinned mirrors of two micro-batches in flight; grown on demand (ensure_multi_buffers)
+    // mi_unet_set_targets: what the _multi entry points segment.  d_multi / h_multi hold the [B][K][H][W] planes of every segment call
+    // (masks, then their 0 / 255 pictures in place; K = 1 without _multi) and the pinned mirrors of two micro-batches in flight;
+    // grown on demand (ensure_multi_buffers)
     mi_unet_target targets[MI_UNET_MAX_TARGETS] = { { 2, 0.06f } };
     int n_targets = 1;
     miunet::DeviceBuf<uint8_t> d_multi;
@@ -200,15 +201,33 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
 int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);   // graph replay of launch_plan
 int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);  // ... + postprocess when set
 hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s);
-int device_postprocess(mi_unet *h, const uint8_t *d_in, uint8_t *d_out, int B);
-TargetTable target_table(const mi_unet *h, int H, int W);   // the handle's targets with min_area of an H x W image
-int ensure_tail_workspace(mi_unet *h, size_t bytes);    // h->d_tail_ws of at least `bytes` (synchronises its users before it grows)
-int ensure_multi_buffers(mi_unet *h, size_t bytes);     // h->d_multi / h->h_multi[0..1] of at least `bytes` each
+constexpr mi_unet_target kDefaultTarget{ 2, 0.06f };    // the reference's: class 2, 6 % of the image
+TargetTable target_table(const mi_unet_target *targets, int n, int H, int W);   // `n` targets with min_area of an H x W image
+TargetTable target_table(const mi_unet *h, int H, int W);   // ... the handle's (the _multi entry points)
+TargetTable default_targets(int H, int W);              // ... the reference's (every entry point without _multi, whatever the handle's setting)
+// h->d_tail_ws of at least `ws_bytes`, h->d_multi / h->h_multi[0..1] of at least `plane_bytes` each (synchronises their users before they grow)
+int ensure_tail_buffers(mi_unet *h, size_t ws_bytes, size_t plane_bytes);
 int grow_events(std::vector<Event> &ev, size_t n);      // at least n timing events (never inside a capture)
-// contour outputs of `bm` images: device -> pinned mirror half (async on h->stream) -> the caller's arrays (after the synchronise)
-int grow_contour_buffers(mi_unet *h, int bm, int cap_points, int cap_contours);
-int contours_to_pinned(mi_unet *h, int bm, int cap_points, int cap_contours, int half = 0);
-void contours_to_caller(const mi_unet *h, int bm, int cap_points, int cap_contours, int32_t *xy, int32_t *start, int32_t *counts, int half = 0);
+// The contour arrays of `planes` masks (launch_extract_contours) as one run of ints -- xy, start, count -- from `base`: h->d_cont,
+// or a half of its pinned mirror h->h_cont.
+struct ContourLayout {
+    int planes, cap_points, cap_contours;
+    size_t ints() const { return (size_t)planes * ((size_t)cap_points * 2 + cap_contours + 1 + 1); }
+    template <class T> T *xy(T *base) const { return base; }
+    template <class T> T *start(T *base) const { return base + (size_t)planes * cap_points * 2; }
+    template <class T> T *count(T *base) const { return start(base) + (size_t)planes * (cap_contours + 1); }
+};
+// contour outputs: device -> pinned mirror half (async on `s`) -> the caller's arrays (after the synchronise)
+int grow_contour_buffers(mi_unet *h, const ContourLayout &cl);
+int contours_to_pinned(mi_unet *h, const ContourLayout &cl, hipStream_t s, int half = 0);
+void contours_to_caller(const mi_unet *h, const ContourLayout &cl, int32_t *xy, int32_t *start, int32_t *counts, int half = 0);
+// The tail behind the argmax, enqueued on `s`: postprocess_mask of B label maps per target of `t` -> d_planes u8 [B][t.K][H][W] in
+// {0, cls} (d_labels itself allowed when t.K == 1); with `cl` (cl->planes == B * t.K): -> their 0 / 255 pictures in place -> contours
+// into h->d_cont.  `ws` holds both stages' workspaces for B * t.K planes (checked by the caller); `between` (or null) is recorded
+// behind the postprocess, the boundary of the two stage times; `where` prefixes the message of a failed launch.  An empty table
+// (t.K == 0, no cl) enqueues nothing but `between`.
+int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const TargetTable &t, uint8_t *d_planes, void *ws,
+                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where = std::string());
 // ---- pipeline_raw.cpp: large host copies on the handle's helper threads
 void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes);
 // ---- debug.cpp: mi_unet_debug_capture's taps, called by launch_plan around the tapped step

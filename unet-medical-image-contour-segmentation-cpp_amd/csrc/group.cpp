@@ -386,23 +386,35 @@ int mi_unet_group_infer_raw16(mi_unet_group_t *g, const uint16_t *const *raws, c
     });
 }
 
-int mi_unet_group_segment_raw16(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
-                                uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
-                                int32_t *counts)
+// mi_unet_group_segment_raw16 and its _multi form: images sharded over the ranks, K planes per image (1 without _multi)
+static int group_segment_raw16(mi_unet_group_t *g, const char *fn, bool multi, const uint16_t *const *raws, const int *widths, const int *heights,
+                               int B, uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *counts)
 {
     if (!g || !raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
-        return engine_fail(MI_UNET_EARG, "mi_unet_group_segment_raw16: bad argument");
+        return engine_fail(MI_UNET_EARG, std::string(fn) + ": bad argument");
     std::lock_guard<std::mutex> lk(g->call_mutex);
     const int R = (int)g->eng.size(), C = g->cfg.in_ch;
     const size_t hw = (size_t)g->cfg.height * g->cfg.width;
+    int n_targets = 1;
+    if (multi)
+        if (int rc = mi_unet_get_targets(g->eng[0], nullptr, 0, &n_targets)) return rc;
+    const size_t K = (size_t)n_targets;
     return for_all_ranks(g, [&](int r) {
         int lo, hi;
         shard_range(B, r, R, lo, hi);
         if (hi == lo) return 0;
-        return mi_unet_segment_raw16(g->eng[r], raws + (size_t)lo * C, widths + (size_t)lo * C, heights + (size_t)lo * C, hi - lo,
-                                     tiles ? tiles + lo * hw * C : nullptr, masks + lo * hw, xy + (size_t)lo * cap_points * 2, cap_points,
-                                     start + (size_t)lo * (cap_contours + 1), cap_contours, counts + lo);
+        return (multi ? mi_unet_segment_raw16_multi : mi_unet_segment_raw16)(
+            g->eng[r], raws + (size_t)lo * C, widths + (size_t)lo * C, heights + (size_t)lo * C, hi - lo, tiles ? tiles + lo * hw * C : nullptr,
+            masks + lo * K * hw, xy + lo * K * cap_points * 2, cap_points, start + lo * K * (cap_contours + 1), cap_contours, counts + lo * K);
     });
+}
+
+int mi_unet_group_segment_raw16(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
+                                uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
+                                int32_t *counts)
+{
+    return group_segment_raw16(g, "mi_unet_group_segment_raw16", false, raws, widths, heights, B, tiles, masks, xy, cap_points, start,
+                               cap_contours, counts);
 }
 
 int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n)
@@ -419,22 +431,8 @@ int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const 
                                       uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                       int32_t *counts)
 {
-    if (!g || !raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
-        return engine_fail(MI_UNET_EARG, "mi_unet_group_segment_raw16_multi: bad argument");
-    std::lock_guard<std::mutex> lk(g->call_mutex);
-    const int R = (int)g->eng.size(), C = g->cfg.in_ch;
-    const size_t hw = (size_t)g->cfg.height * g->cfg.width;
-    int n_targets = 0;
-    if (int rc = mi_unet_get_targets(g->eng[0], nullptr, 0, &n_targets)) return rc;
-    const size_t K = (size_t)n_targets;
-    return for_all_ranks(g, [&](int r) {
-        int lo, hi;
-        shard_range(B, r, R, lo, hi);
-        if (hi == lo) return 0;
-        return mi_unet_segment_raw16_multi(g->eng[r], raws + (size_t)lo * C, widths + (size_t)lo * C, heights + (size_t)lo * C, hi - lo,
-                                           tiles ? tiles + lo * hw * C : nullptr, masks + lo * K * hw, xy + lo * K * cap_points * 2, cap_points,
-                                           start + lo * K * (cap_contours + 1), cap_contours, counts + lo * K);
-    });
+    return group_segment_raw16(g, "mi_unet_group_segment_raw16_multi", true, raws, widths, heights, B, tiles, masks, xy, cap_points, start,
+                               cap_contours, counts);
 }
 
 void mi_unet_group_destroy(mi_unet_group_t *g)

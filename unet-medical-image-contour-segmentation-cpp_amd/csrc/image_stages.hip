@@ -231,27 +231,6 @@ __global__ __launch_bounds__(256) void cc_stats(int *parent, int *area, int *min
     flush();
 }
 
-__global__ __launch_bounds__(256) void k_inv(const uint8_t *__restrict__ labels, uint8_t *inv, long long n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) inv[i] = labels[i] == 2 ? 0 : 255;               // src/postprocess.cpp:18-22
-}
-
-// bin = 255 where the pixel is foreground after hole filling (src/postprocess.cpp:30-43, :57)
-__global__ __launch_bounds__(256) void k_fill_bin(const uint8_t *__restrict__ labels, const int *__restrict__ parent,
-                                                  const int *__restrict__ area, const int *__restrict__ minx,
-                                                  const int *__restrict__ miny, const int *__restrict__ maxx,
-                                                  const int *__restrict__ maxy, uint8_t *bin, int H, int W, int min_area, long long n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    bool fgd = labels[i] == 2;
-    const int r = parent[i];
-    if (!fgd && r >= 0)
-        fgd = minx[r] > 0 && miny[r] > 0 && maxx[r] < W - 1 && maxy[r] < H - 1 && area[r] < min_area;
-    bin[i] = fgd ? 255 : 0;
-}
-
 template <bool DILATE>
 __global__ __launch_bounds__(256) void k_morph3(const uint8_t *__restrict__ src, uint8_t *dst, int H, int W, long long n)
 {
@@ -272,18 +251,9 @@ __global__ __launch_bounds__(256) void k_morph3(const uint8_t *__restrict__ src,
     dst[i] = (uint8_t)v;
 }
 
-__global__ __launch_bounds__(256) void k_filter(const int *__restrict__ parent, const int *__restrict__ area, uint8_t *out,
-                                                int min_area, long long n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int r = parent[i];
-    out[i] = (r >= 0 && area[r] >= min_area) ? 2 : 0;          // src/postprocess.cpp:70, :75-76
-}
-
-// ---- K targets per image (launch_postprocess_masks_multi): plane p = i / hw of the output is target p % K of image p / K.  Only the
-// three kernels that look at a class or an area bound differ from the chain above; they read the label map of the plane's image
-// in place.  The table is a kernel argument; its entries are picked with a chain of selects, so it stays in registers.
+// ---- the three kernels that look at a class or an area bound.  Plane p = i / hw of the output is target p % K of image p / K; they
+// read the label map of the plane's image in place.  The table is a kernel argument; its entries are picked with a chain of
+// selects, so it stays in registers.  The reference's single target is the table { 1, { 2 }, { min_area } }.
 struct PlaneTarget { int cls, min_area; long long src; };
 __device__ __forceinline__ PlaneTarget plane_target(const TargetTable &t, long long i, int hw)
 {
@@ -300,9 +270,10 @@ __global__ __launch_bounds__(256) void k_inv_multi(const uint8_t *__restrict__ l
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const PlaneTarget pt = plane_target(t, i, hw);
-    inv[i] = labels[pt.src] == pt.cls ? 0 : 255;
+    inv[i] = labels[pt.src] == pt.cls ? 0 : 255;               // src/postprocess.cpp:18-22
 }
 
+// bin = 255 where the pixel is foreground after hole filling (src/postprocess.cpp:30-43, :57)
 __global__ __launch_bounds__(256) void k_fill_bin_multi(const uint8_t *__restrict__ labels, const int *__restrict__ parent,
                                                         const int *__restrict__ area, const int *__restrict__ minx,
                                                         const int *__restrict__ miny, const int *__restrict__ maxx,
@@ -325,7 +296,7 @@ __global__ __launch_bounds__(256) void k_filter_multi(const int *__restrict__ pa
     if (i >= n) return;
     const PlaneTarget pt = plane_target(t, i, hw);
     const int r = parent[i];
-    out[i] = (r >= 0 && area[r] >= pt.min_area) ? (uint8_t)pt.cls : 0;
+    out[i] = (r >= 0 && area[r] >= pt.min_area) ? (uint8_t)pt.cls : 0;      // src/postprocess.cpp:70, :75-76
 }
 
 }  // namespace pp
@@ -336,29 +307,6 @@ size_t postprocess_workspace_bytes(int B, int H, int W)
     return n * (6 * sizeof(int) + 3);                           // parent, area, 4 x bbox, three u8 planes
 }
 
-hipError_t launch_postprocess_masks(const uint8_t *labels_in, uint8_t *labels_out, int B, int H, int W, int min_area, void *ws,
-                                    hipStream_t s)
-{
-    const long long n = (long long)B * H * W;
-    if (n <= 0 || n > 0x7FFFFFFFLL) return hipErrorInvalidValue;
-    int *parent = static_cast<int *>(ws), *area = parent + n, *minx = area + n, *miny = minx + n, *maxx = miny + n, *maxy = maxx + n;
-    uint8_t *u0 = reinterpret_cast<uint8_t *>(maxy + n), *u1 = u0 + n, *u2 = u1 + n;
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    auto label = [&](const uint8_t *fg) {
-        hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, fg, parent, area, minx, miny, maxx, maxy, W, n);
-        hipLaunchKernelGGL(pp::cc_merge, g, b, 0, s, fg, parent, H, W, n);
-        hipLaunchKernelGGL(pp::cc_stats, dim3((unsigned)((n + 256LL * pp::CC_RUN - 1) / (256LL * pp::CC_RUN))), b, 0, s, parent, area, minx, miny, maxx, maxy, H, W, n);
-    };
-    hipLaunchKernelGGL(pp::k_inv, g, b, 0, s, labels_in, u0, n);
-    label(u0);
-    hipLaunchKernelGGL(pp::k_fill_bin, g, b, 0, s, labels_in, parent, area, minx, miny, maxx, maxy, u1, H, W, min_area, n);
-    hipLaunchKernelGGL(pp::k_morph3<false>, g, b, 0, s, u1, u2, H, W, n);
-    hipLaunchKernelGGL(pp::k_morph3<true>, g, b, 0, s, u2, u1, H, W, n);
-    label(u1);
-    hipLaunchKernelGGL(pp::k_filter, g, b, 0, s, parent, area, labels_out, min_area, n);
-    return hipGetLastError();
-}
-
 hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, int B, int H, int W, const TargetTable &t, void *ws,
                                           hipStream_t s)
 {
@@ -366,6 +314,10 @@ hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, i
     const long long n = (long long)B * t.K * H * W;                // the planes of all (image, target) pairs
     if (n <= 0 || n > 0x7FFFFFFFLL) return hipErrorInvalidValue;
     const int hw = H * W;
+    // `out` may be the label map itself when K == 1: k_filter_multi reads no labels, and every read of them is ordered before it on
+    // `s`.  With K > 1 the planes of image b would overwrite the label maps of the images behind it.
+    const uintptr_t l0 = reinterpret_cast<uintptr_t>(labels), o0 = reinterpret_cast<uintptr_t>(out);
+    if (t.K > 1 && o0 < l0 + (uintptr_t)B * hw && l0 < o0 + (uintptr_t)n) return hipErrorInvalidValue;
     int *parent = static_cast<int *>(ws), *area = parent + n, *minx = area + n, *miny = minx + n, *maxx = miny + n, *maxy = maxx + n;
     uint8_t *u0 = reinterpret_cast<uint8_t *>(maxy + n), *u1 = u0 + n, *u2 = u1 + n;
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
@@ -640,20 +592,6 @@ __global__ __launch_bounds__(64) void k_offsets(const int *__restrict__ npts, co
 }
 
 }  // namespace ct
-
-__global__ __launch_bounds__(256) void mask_to_image_kernel(const uint8_t *__restrict__ labels, uint8_t *vis, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned v = labels[i];
-    vis[i] = v == 1 ? 128 : v == 2 ? 255 : 0;
-}
-
-hipError_t launch_mask_to_image(const uint8_t *labels, uint8_t *vis, size_t n, hipStream_t s)
-{
-    hipLaunchKernelGGL(mask_to_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, labels, vis, n);
-    return hipGetLastError();
-}
 
 __global__ __launch_bounds__(256) void mask_to_image_binary_kernel(const uint8_t *masks, uint8_t *vis, size_t n)
 {

@@ -185,21 +185,19 @@ hipError_t launch_tile_blend(const float *tile_logits, int classes, int H, int W
 hipError_t launch_blend_finalize(const float *acc, int classes, int H, int W, int th, int tw, int halo, int mirror, bool owner,
                                  const float *wy, const float *wx, uint8_t *labels, float *logits, hipStream_t s);
 
-// Device form of postprocess_mask (reference: src/postprocess.cpp:13-79), integer-exact.  Workspace `ws` must hold
-// postprocess_workspace_bytes(B, H, W) bytes; labels_in/out are u8 [B][H][W] (in-place allowed).
-//   hole fill : 8-connected components of (label != 2) by lock-free union-find, per-root area + bbox by atomics; a
+// Device form of postprocess_mask (reference: src/postprocess.cpp:13-79), integer-exact, for K targets at once (include/mi_unet.h:
+// mi_unet_set_targets); the reference's own chain is the table { 1, { 2 }, { min_area } }.  One label map u8 [B][H][W], read in
+// place, never replicated; out u8 [B][K][H][W].  Plane p = b * K + k is the chain on image p / K with `== cls[p % K]` and
+// min_area[p % K], its output in {0, cls[p % K]}:
+//   hole fill : 8-connected components of (label != cls) by lock-free union-find, per-root area + bbox by atomics; a
 //               component is filled iff its bbox touches no image edge and area < min_area
 //   open      : 3x3 erode then dilate, windows clipped to the image
-//   filter    : 8-connected components of the opened mask, kept iff area >= min_area;  output in {0, 2}
+//   filter    : 8-connected components of the opened mask, kept iff area >= min_area
+// Every kernel runs over the B * K planes: the number of launches does not depend on K.  The table travels as a kernel argument (at
+// most POSTPROCESS_MAX_TARGETS entries).  Workspace: postprocess_workspace_bytes(B * K, H, W); B * K * H * W must not exceed
+// 2^31 - 1.  With K == 1 `out` may be `labels` (in place: the last kernel, the only one that writes `out`, reads no labels and runs
+// behind every kernel that does); with K > 1 an `out` that overlaps the label maps is refused with hipErrorInvalidValue.
 size_t postprocess_workspace_bytes(int B, int H, int W);
-hipError_t launch_postprocess_masks(const uint8_t *labels_in, uint8_t *labels_out, int B, int H, int W, int min_area,
-                                    void *ws, hipStream_t s);
-
-// The same chain for K targets at once (include/mi_unet.h: mi_unet_set_targets).  One label map u8 [B][H][W], read in place, never
-// replicated; out u8 [B][K][H][W] (must not alias it).  Plane p = b * K + k is the chain above on image p / K with `== cls[p % K]`
-// in place of `== 2` and min_area[p % K], its output in {0, cls[p % K]}.  The labelling, morphology and statistics kernels are the
-// ones above, run over B * K planes: the number of launches does not depend on K.  The table travels as a kernel argument (at most
-// POSTPROCESS_MAX_TARGETS entries).  Workspace: postprocess_workspace_bytes(B * K, H, W); B * K * H * W must not exceed 2^31 - 1.
 constexpr int POSTPROCESS_MAX_TARGETS = 5;
 struct TargetTable {
     int K = 0;
@@ -216,9 +214,8 @@ hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, i
 //   out_start  int32 [B][cap_contours+1]  first point of contour c; entry n_contours = total points
 //   out_count  int32 [B]                  number of contours, or -1 when a capacity was too small
 // Workspace: contour_workspace_bytes(B, H, W, cap_contours).
-// mask_to_image (src/process.cpp:178-185): 0 -> 0, 1 -> 128, 2 -> 255, anything else -> 0
-hipError_t launch_mask_to_image(const uint8_t *labels, uint8_t *vis, size_t n, hipStream_t s);
-// the per-target form: a target's mask holds {0, cls}, its picture 0 / 255 (in place allowed)
+// mask_to_image (src/process.cpp:178-185) behind postprocess_mask: a target's mask holds {0, cls}, its picture 0 / 255 (in place
+// allowed).  For cls == 2 these are the reference's bytes; its 1 -> 128 never meets a postprocessed mask.
 hipError_t launch_mask_to_image_binary(const uint8_t *masks, uint8_t *vis, size_t n, hipStream_t s);
 size_t contour_workspace_bytes(int B, int H, int W, int cap_contours);
 hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, int *out_xy, int cap_points, int *out_start,

@@ -85,13 +85,12 @@ int stage_raw16(mi_unet *h, const uint16_t *const *raws, const int *widths, cons
     return 0;
 }
 
-int ensure_raw_pipeline(mi_unet *h, bool two_buffers)
+int ensure_raw_pipeline(mi_unet *h, bool two_buffers, bool segment)
 {
     if (!h->pre_stream) HIP_TRY(hipStreamCreateWithFlags(&h->pre_stream, hipStreamNonBlocking));
     if (!h->tail_stream) HIP_TRY(hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking));
     if (!h->dl_stream) HIP_TRY(hipStreamCreateWithFlags(&h->dl_stream, hipStreamNonBlocking));
     const size_t npix = (size_t)h->cfg.max_batch * h->cfg.height * h->cfg.width;
-    if (!h->d_tail_vis) HIP_TRY(h->d_tail_vis.reset(npix));
     if (!h->d_labels2) HIP_TRY(h->d_labels2.reset(npix));
     for (int i = 0; i < 2; ++i) {
         for (Event *e : { &h->tiles_done[i], &h->net_done[i], &h->tile_ready[i], &h->out_done[i] })
@@ -104,7 +103,7 @@ int ensure_raw_pipeline(mi_unet *h, bool two_buffers)
     for (int i = 0; i < 3; ++i)
         for (Event &e : h->pre_ev[i])
             if (!e) HIP_TRY(e.reset());
-    if (two_buffers && !h->h_labels2) HIP_TRY(h->h_labels2.reset(npix));
+    if (two_buffers && !segment && !h->h_labels2) HIP_TRY(h->h_labels2.reset(npix));   // (segment calls download into h_multi)
     for (int i = 0; i < (two_buffers ? 2 : 1); ++i)
         if (!h->h_tiles[i]) HIP_TRY(h->h_tiles[i].reset(npix * h->cfg.in_ch));
     if (two_buffers && !h->d_img2) HIP_TRY(h->d_img2.reset(npix * h->cfg.in_ch));
@@ -117,8 +116,8 @@ int ensure_raw_pipeline(mi_unet *h, bool two_buffers)
 struct RawCall {
     const uint16_t *const *raws; const int *widths, *heights; int B;
     uint8_t *tiles, *out_u8; float *logits;            // out_u8: label maps (infer) or 0 / 255 masks (segment)
-    bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *counts;
-    bool multi = false;                                // segment, per target of the handle: out_u8 and the contour arrays are [B][K]...
+    TargetTable targets;                               // segment: K >= 1 targets, out_u8 and the contour arrays are [B][K]...; K = 0: infer
+    int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *counts;
 };
 
 int run_raw_call(mi_unet *h, const RawCall &c)
@@ -128,11 +127,11 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     const size_t hw = (size_t)H * W, C = (size_t)h->cfg.in_ch;
     hipStream_t s = h->stream;
     if (c.B <= 0) return MI_UNET_OK;
-    // the _multi form: K planes per image behind the network, (image, target) pairs as the batch of every tail stage
-    const TargetTable tab = c.multi ? target_table(h, H, W) : TargetTable{};
-    const int K = c.multi ? tab.K : 1;
-    if (c.multi && (size_t)std::min(c.B, Bm) * K * hw > 0x7FFFFFFFull)
-        return fail(MI_UNET_EARG, "segment_raw16_multi: max_batch x targets x height x width exceeds 2^31 - 1");
+    // segment: K planes per image behind the network, (image, target) pairs as the batch of every tail stage, in d_multi / h_multi;
+    // infer: the label maps themselves, postprocessed in place for the reference's target when mi_unet_set_postprocess is on
+    const bool segment = c.targets.K > 0;
+    const TargetTable tab = segment ? c.targets : h->postprocess ? default_targets(H, W) : TargetTable{};
+    const int K = segment ? tab.K : 1;
     // every image description is checked BEFORE anything is enqueued: a bad width in image k + 1 must not be found after the
     // network of micro-batch k has started
     for (size_t i = 0; i < (size_t)c.B * C; ++i)
@@ -173,10 +172,10 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         mbs.insert(mbs.begin(), parts.begin(), parts.end());
     }
     const int n_mb = (int)mbs.size();
-    if (int rc = ensure_raw_pipeline(h, n_mb > 1)) return rc;
+    if (int rc = ensure_raw_pipeline(h, n_mb > 1, segment)) return rc;
     for (float &m : h->stage_ms) m = 0.f;
     auto tile_buf = [&](int k) { return (k & 1) ? h->d_img2.get() : h->d_img.get(); };
-    auto out_buf = [&](int k) { return c.multi ? h->h_multi[k & 1].get() : (k & 1) ? h->h_labels2.get() : h->h_labels.get(); };
+    auto out_buf = [&](int k) { return segment ? h->h_multi[k & 1].get() : (k & 1) ? h->h_labels2.get() : h->h_labels.get(); };
     auto stage = [&](int k) -> int {                   // upload + preprocess micro-batch k on the second stream
         const int bm = mbs[k].bm, par = k & 1;
         const size_t b0 = (size_t)mbs[k].b0;
@@ -193,7 +192,8 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         uint8_t *d_tiles = tile_buf(k);
         uint8_t *d_lab = par ? h->d_labels2.get() : h->d_labels.get();
         hipStream_t ts = h->tail_stream;
-        if (c.segment && contour_workspace_bytes(bm * K, H, W, c.cap_contours) > h->tail_ws_bytes)
+        const ContourLayout cl{ bm * K, c.cap_points, c.cap_contours };
+        if (segment && contour_workspace_bytes(bm * K, H, W, c.cap_contours) > h->tail_ws_bytes)
             return fail(MI_UNET_EARG, "contour workspace does not fit (cap_contours too large)");
         HIP_TRY(hipStreamWaitEvent(s, h->tile_ready[par], 0));
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(s, h->out_done[par], 0));                      // the tail of k - 2 has read this label buffer
@@ -214,37 +214,12 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         HIP_TRY(hipStreamWaitEvent(ts, h->net_done[par], 0));
         Event *tv = h->tail_ev[par];
         HIP_TRY(hipEventRecord(tv[0], ts));
-        const uint8_t *d_result = d_lab;
-        const int planes = bm * K;
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)planes * c.cap_points * 2, *d_count = d_start + (size_t)planes * (c.cap_contours + 1);
-        if (c.multi) {
-            const hipError_t e = launch_postprocess_masks_multi(d_lab, h->d_multi, bm, H, W, tab, h->d_tail_ws, ts);   // {0, cls_k}
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
-        } else if (c.segment || h->postprocess) {
-            const int min_area = mi_unet_target_min_area(H, W, 0.06f);                         // src/postprocess.cpp:9, :30, :66
-            const hipError_t e = launch_postprocess_masks(d_lab, d_lab, bm, H, W, min_area, h->d_tail_ws, ts);      // {0, 2}
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("postprocess launch: ") + hipGetErrorString(e));
-        }
-        HIP_TRY(hipEventRecord(tv[1], ts));
-        if (c.multi) {
-            hipError_t e = launch_mask_to_image_binary(h->d_multi, h->d_multi, planes * hw, ts);
-            if (e == hipSuccess)
-                e = launch_extract_contours(h->d_multi, planes, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_tail_ws, ts);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("segment launch: ") + hipGetErrorString(e));
-            d_result = h->d_multi;
-        } else if (c.segment) {
-            hipError_t e = launch_mask_to_image(d_lab, h->d_tail_vis, bm * hw, ts);
-            if (e == hipSuccess)
-                e = launch_extract_contours(h->d_tail_vis, bm, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_tail_ws, ts);
-            if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("segment launch: ") + hipGetErrorString(e));
-            d_result = h->d_tail_vis;
-        }
+        uint8_t *d_result = segment ? h->d_multi.get() : d_lab;
+        if (int rc = enqueue_tail(h, d_lab, bm, H, W, tab, d_result, h->d_tail_ws, segment ? &cl : nullptr, tv[1], ts)) return rc;
         HIP_TRY(hipEventRecord(tv[2], ts));
-        HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, planes * hw, hipMemcpyDeviceToHost, ts));
-        if (c.segment) {
-            const size_t n = (size_t)planes * ((size_t)c.cap_points * 2 + c.cap_contours + 1 + 1);
-            HIP_TRY(hipMemcpyAsync(h->h_cont + par * h->cont_cap, h->d_cont, n * sizeof(int), hipMemcpyDeviceToHost, ts));
-        }
+        HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, bm * K * hw, hipMemcpyDeviceToHost, ts));
+        if (segment)
+            if (int rc = contours_to_pinned(h, cl, ts, par)) return rc;
         HIP_TRY(hipEventRecord(tv[3], ts));
         HIP_TRY(hipEventRecord(h->out_done[par], ts));
         return 0;
@@ -258,9 +233,9 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         }
         HIP_TRY(hipEventSynchronize(h->out_done[par]));
         host_copy(h, c.out_u8 + b0 * K * hw, out_buf(k), bm * K * hw);
-        if (c.segment)
-            contours_to_caller(h, bm * K, c.cap_points, c.cap_contours, c.xy + b0 * K * c.cap_points * 2, c.start + b0 * K * (c.cap_contours + 1),
-                               c.counts + b0 * K, par);
+        if (segment)
+            contours_to_caller(h, ContourLayout{ bm * K, c.cap_points, c.cap_contours }, c.xy + b0 * K * c.cap_points * 2,
+                               c.start + b0 * K * (c.cap_contours + 1), c.counts + b0 * K, par);
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->pre_ev[k % 3][0], h->pre_ev[k % 3][1]));
         h->stage_ms[MI_UNET_STAGE_UPLOAD_PRE] += ms;
@@ -281,13 +256,12 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     {
         int bmax = 0;
         for (const MB &m : mbs) bmax = std::max(bmax, m.bm);
-        if (c.segment)
-            if (int rc = grow_contour_buffers(h, bmax * K, c.cap_points, c.cap_contours)) return rc;
         size_t need = postprocess_workspace_bytes(bmax * K, H, W);
-        if (c.segment) need = std::max(need, contour_workspace_bytes(bmax * K, H, W, c.cap_contours));
-        if (int rc = ensure_tail_workspace(h, need)) return rc;
-        if (c.multi)
-            if (int rc = ensure_multi_buffers(h, (size_t)bmax * K * hw)) return rc;
+        if (segment) {
+            if (int rc = grow_contour_buffers(h, ContourLayout{ bmax * K, c.cap_points, c.cap_contours })) return rc;
+            need = std::max(need, contour_workspace_bytes(bmax * K, H, W, c.cap_contours));
+        }
+        if (int rc = ensure_tail_buffers(h, need, segment ? (size_t)bmax * K * hw : 0)) return rc;
     }
     // Once the first micro-batch is enqueued, H2D copies read the caller's (possibly page-locked) RAW buffers directly and the tail
     // writes the handle's pinned mirrors: an error return with work still in flight would let the caller free buffers under the
@@ -335,27 +309,35 @@ int mi_unet_infer_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *wi
 {
     if (int rc = check_handle(h, true)) return rc;
     if (!raws || !widths || !heights || !labels || B < 0) return fail(MI_UNET_EARG, "mi_unet_infer_raw16: bad argument");
-    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, labels, logits, false, nullptr, 0, nullptr, 0, nullptr });
+    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, labels, logits, TargetTable{}, nullptr, 0, nullptr, 0, nullptr });
+}
+
+// mi_unet_segment_raw16 (the reference's target, whatever the handle's setting) and its _multi form (the handle's targets)
+static int segment_raw16_call(mi_unet_t *h, const char *name, bool multi, const uint16_t *const *raws, const int *widths, const int *heights,
+                              int B, uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *counts)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
+        return fail(MI_UNET_EARG, std::string("mi_unet_") + name + ": bad argument");
+    const int H = h->cfg.height, W = h->cfg.width;
+    const TargetTable tab = multi ? target_table(h, H, W) : default_targets(H, W);
+    if ((size_t)std::min(B, h->cfg.max_batch) * tab.K * H * W > 0x7FFFFFFFull)
+        return fail(MI_UNET_EARG, std::string(name) + ": max_batch x targets x height x width exceeds 2^31 - 1");
+    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, tab, xy, cap_points, start, cap_contours, counts });
 }
 
 int mi_unet_segment_raw16(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                           uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                           int32_t *counts)
 {
-    if (int rc = check_handle(h, true)) return rc;
-    if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_raw16: bad argument");
-    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts });
+    return segment_raw16_call(h, "segment_raw16", false, raws, widths, heights, B, tiles, masks, xy, cap_points, start, cap_contours, counts);
 }
 
 int mi_unet_segment_raw16_multi(mi_unet_t *h, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                                 uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                 int32_t *counts)
 {
-    if (int rc = check_handle(h, true)) return rc;
-    if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_raw16_multi: bad argument");
-    return run_raw_call(h, RawCall{ raws, widths, heights, B, tiles, masks, nullptr, true, xy, cap_points, start, cap_contours, counts, true });
+    return segment_raw16_call(h, "segment_raw16_multi", true, raws, widths, heights, B, tiles, masks, xy, cap_points, start, cap_contours, counts);
 }
 
 int mi_unet_last_stage_ms(const mi_unet_t *h, float *ms)

@@ -30,8 +30,8 @@ struct TiledCall {
     int H, W, halo;
     uint8_t *norm, *out_u8;                // out_u8: label map (infer) or 0 / 255 mask (segment)
     float *logits;
-    bool segment; int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
-    bool multi = false;                    // segment, per target of the handle: out_u8 and the contour arrays are [K]...
+    const mi_unet_target *targets; int K;  // segment: K >= 1 targets, out_u8 and the contour arrays are [K]...; K = 0: infer
+    int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
 };
 
 int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bool blend)
@@ -44,7 +44,6 @@ int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bo
         t.px_cap = 0;
         HIP_TRY(t.d_img.reset(round_up(npix * C, 4)));            // whole dwords: launch_tile_gather reads aligned dwords
         HIP_TRY(t.d_labels.reset(npix));
-        HIP_TRY(t.d_vis.reset(npix));
         HIP_TRY(t.h_img.reset(npix * C));
         HIP_TRY(t.h_out.reset(npix));
         t.px_cap = npix;
@@ -118,18 +117,20 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     if (!tile_grid(H, W, th, tw, c.halo, g)) return fail(MI_UNET_EARG, fn + ": illegal tile grid");
     const size_t npix = (size_t)H * W, thw = (size_t)th * tw;
     const int nt = g.ny * g.nx;
-    const bool post = c.segment || h->postprocess;
-    // the _multi form: the targets of the handle as K planes of the stitched image, min_area from the full image
-    const TargetTable tab = c.multi ? target_table(h, H, W) : TargetTable{};
-    const int K = c.multi ? tab.K : 1;
+    // segment: the call's targets as K planes of the stitched image, min_area from the full image; infer: the label map itself,
+    // postprocessed in place for the reference's target when mi_unet_set_postprocess is on
+    const bool segment = c.K > 0;
+    const TargetTable tab = segment ? target_table(c.targets, c.K, H, W) : h->postprocess ? default_targets(H, W) : TargetTable{};
+    const int K = segment ? c.K : 1;
+    const ContourLayout cl{ K, c.cap_points, c.cap_contours };
     // the full-size tail stages borrow the network's scratch buffer: checked before anything is enqueued
     const size_t scratch = sizeof(float) * h->s_floats;
     const std::string what = (K > 1 ? std::to_string(K) + " targets of a " : std::string("a ")) + std::to_string(H) + " x " + std::to_string(W) + " image (";
-    if (post && postprocess_workspace_bytes(K, H, W) > scratch)
+    if (tab.K && postprocess_workspace_bytes(K, H, W) > scratch)
         return fail(MI_UNET_EARG, fn + ": the postprocess workspace of " + what +
                                       std::to_string(postprocess_workspace_bytes(K, H, W)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
-    if (c.segment && contour_workspace_bytes(K, H, W, c.cap_contours) > scratch)
+    if (segment && contour_workspace_bytes(K, H, W, c.cap_contours) > scratch)
         return fail(MI_UNET_EARG, fn + ": the contour workspace of " + what +
                                       std::to_string(contour_workspace_bytes(K, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
@@ -143,11 +144,11 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = h->stream;
     if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr && !blend, c.planes != nullptr, blend)) return rc;
-    if (c.segment)
-        if (int rc = grow_contour_buffers(h, K, c.cap_points, c.cap_contours)) return rc;
+    if (segment)
+        if (int rc = grow_contour_buffers(h, cl)) return rc;
     if (c.planes && !h->d_mnmx) HIP_TRY(h->d_mnmx.reset((size_t)2 * Bm * C));
     mi_unet::Tiled &t = h->tiled;
-    if (c.multi && K * npix > t.multi_cap) {
+    if (segment && K * npix > t.multi_cap) {
         HIP_TRY(hipStreamSynchronize(s));
         t.multi_cap = 0;
         HIP_TRY(t.d_multi.reset(K * npix));
@@ -238,42 +239,20 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     }
 
     // ---- the tail, on the stitched image: one image of H x W, never per tile
-    const uint8_t *d_result = t.d_labels;
-    uint8_t *h_result = t.h_out;
-    if (c.multi) {
-        e = launch_postprocess_masks_multi(t.d_labels, t.d_multi, 1, H, W, tab, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
-    } else if (post) {
-        const int min_area = mi_unet_target_min_area(H, W, 0.06f);          // src/postprocess.cpp:9 (evaluated in float), of the full image
-        e = launch_postprocess_masks(t.d_labels, t.d_labels, 1, H, W, min_area, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": postprocess launch: " + hipGetErrorString(e));
-    }
-    HIP_TRY(hipEventRecord(t.ev[mark++], s));
-    if (c.multi) {
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)K * c.cap_points * 2, *d_count = d_start + (size_t)K * (c.cap_contours + 1);
-        e = launch_mask_to_image_binary(t.d_multi, t.d_multi, K * npix, s);
-        if (e == hipSuccess) e = launch_extract_contours(t.d_multi, K, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": segment launch: " + hipGetErrorString(e));
-        d_result = t.d_multi;
-        h_result = t.h_multi;
-    } else if (c.segment) {
-        int *d_xy = h->d_cont, *d_start = d_xy + (size_t)c.cap_points * 2, *d_count = d_start + (c.cap_contours + 1);
-        e = launch_mask_to_image(t.d_labels, t.d_vis, npix, s);
-        if (e == hipSuccess) e = launch_extract_contours(t.d_vis, 1, H, W, d_xy, c.cap_points, d_start, c.cap_contours, d_count, h->d_s1, s);
-        if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": segment launch: " + hipGetErrorString(e));
-        d_result = t.d_vis;
-    }
+    uint8_t *const d_result = segment ? t.d_multi.get() : t.d_labels.get(), *const h_result = segment ? t.h_multi.get() : t.h_out.get();
+    const hipEvent_t post_done = t.ev[mark++];
+    if (int rc = enqueue_tail(h, t.d_labels, 1, H, W, tab, d_result, h->d_s1, segment ? &cl : nullptr, post_done, s, fn + ": ")) return rc;
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipMemcpyAsync(h_result, d_result, K * npix, hipMemcpyDeviceToHost, s));
     if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
-    if (c.segment)
-        if (int rc = contours_to_pinned(h, K, c.cap_points, c.cap_contours)) return rc;
+    if (segment)
+        if (int rc = contours_to_pinned(h, cl, s)) return rc;
     if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, blend ? t.d_acc : t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipStreamSynchronize(s));
     host_copy(h, c.out_u8, h_result, K * npix);
     if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
-    if (c.segment) contours_to_caller(h, K, c.cap_points, c.cap_contours, c.xy, c.start, c.count);
+    if (segment) contours_to_caller(h, cl, c.xy, c.start, c.count);
 
     for (float &m : h->stage_ms) m = 0.f;
     auto span = [&](size_t a, size_t b, int stage) -> int {
@@ -345,7 +324,7 @@ int mi_unet_infer_tiled_u8(mi_unet_t *h, const uint8_t *img, int H, int W, int h
 {
     if (int rc = check_handle(h, true)) return rc;
     if (!img || !labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_u8: null image or label buffer");
-    const TiledCall c{ "mi_unet_infer_tiled_u8", img, nullptr, H, W, halo, nullptr, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
+    const TiledCall c{ "mi_unet_infer_tiled_u8", img, nullptr, H, W, halo, nullptr, labels, logits, nullptr, 0, nullptr, 0, nullptr, 0, nullptr };
     return run_tiled_call(h, c);
 }
 
@@ -355,30 +334,34 @@ int mi_unet_infer_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W
     if (int rc = check_handle(h, true)) return rc;
     if (int rc = check_planes(h, planes, "mi_unet_infer_tiled_raw16")) return rc;
     if (!labels) return fail(MI_UNET_EARG, "mi_unet_infer_tiled_raw16: null label buffer");
-    const TiledCall c{ "mi_unet_infer_tiled_raw16", nullptr, planes, H, W, halo, norm, labels, logits, false, nullptr, 0, nullptr, 0, nullptr };
+    const TiledCall c{ "mi_unet_infer_tiled_raw16", nullptr, planes, H, W, halo, norm, labels, logits, nullptr, 0, nullptr, 0, nullptr, 0, nullptr };
+    return run_tiled_call(h, c);
+}
+
+// mi_unet_segment_tiled_raw16 (the reference's target, whatever the handle's setting) and its _multi form (the handle's targets)
+static int segment_tiled_call(mi_unet_t *h, const char *fn, bool multi, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm,
+                              uint8_t *mask, int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    if (int rc = check_planes(h, planes, fn)) return rc;
+    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
+        return fail(MI_UNET_EARG, std::string(fn) + ": null output buffer or non-positive capacity");
+    const TiledCall c{ fn, nullptr, planes, H, W, halo, norm, mask, nullptr, multi ? h->targets : &kDefaultTarget, multi ? h->n_targets : 1,
+                       xy, cap_points, start, cap_contours, count };
     return run_tiled_call(h, c);
 }
 
 int mi_unet_segment_tiled_raw16(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
                                 int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
 {
-    if (int rc = check_handle(h, true)) return rc;
-    if (int rc = check_planes(h, planes, "mi_unet_segment_tiled_raw16")) return rc;
-    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16: null output buffer or non-positive capacity");
-    const TiledCall c{ "mi_unet_segment_tiled_raw16", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count };
-    return run_tiled_call(h, c);
+    return segment_tiled_call(h, "mi_unet_segment_tiled_raw16", false, planes, W, H, halo, norm, mask, xy, cap_points, start, cap_contours, count);
 }
 
 int mi_unet_segment_tiled_raw16_multi(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
                                       int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count)
 {
-    if (int rc = check_handle(h, true)) return rc;
-    if (int rc = check_planes(h, planes, "mi_unet_segment_tiled_raw16_multi")) return rc;
-    if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
-        return fail(MI_UNET_EARG, "mi_unet_segment_tiled_raw16_multi: null output buffer or non-positive capacity");
-    const TiledCall c{ "mi_unet_segment_tiled_raw16_multi", nullptr, planes, H, W, halo, norm, mask, nullptr, true, xy, cap_points, start, cap_contours, count, true };
-    return run_tiled_call(h, c);
+    return segment_tiled_call(h, "mi_unet_segment_tiled_raw16_multi", true, planes, W, H, halo, norm, mask, xy, cap_points, start, cap_contours,
+                              count);
 }
 
 }  // extern "C"

@@ -427,6 +427,26 @@ struct ChunkText {
 
 constexpr int kCapPoints = 1 << 15, kCapContours = 64;     // postprocess keeps components >= 6 % of the tile: <= 16
 
+// the contours of one mask as the device call returned them (its slices of xy / start and its count); a negative count -- a capacity
+// overflow on the device, or no device tracer at all -- hands `vis` to the host tracer
+std::vector<medseg::Contour> contours_of(const int32_t *xy, const int32_t *start, int count, const Image8 &vis)
+{
+    if (count < 0) return Mask2Polygon::extract_contours(vis);
+    std::vector<medseg::Contour> contours;
+    for (int c = 0; c < count; ++c) {
+        medseg::Contour cc;
+        for (int q = start[c]; q < start[c + 1]; ++q) cc.emplace_back(xy[2 * q], xy[2 * q + 1]);
+        contours.push_back(std::move(cc));
+    }
+    return contours;
+}
+
+// channel 0 of `npix` interleaved pixels with C channels: the grey artefact tile (the planes are replicas).  In place allowed.
+void keep_channel0(const uint8_t *hwc, size_t npix, int C, uint8_t *grey)
+{
+    for (size_t p = 0; p < npix; ++p) grey[p] = hwc[p * C];
+}
+
 // I/O and artefact threads of directory mode: one per image of the chunk up to MEDSEG_IO_THREADS (default 16 -- a GPU's share of a
 // host, never the whole machine: an 8-GPU node runs eight of these pools)
 int io_threads_for(size_t n)
@@ -483,8 +503,7 @@ ChunkOut device_chunk(const ChunkIn &in, const std::vector<int> &widths, const s
                                     out.labels.data(), out.xy.data(), kCapPoints, out.start.data(), kCapContours,
                                     out.cnt.data()) != MI_UNET_OK)
         throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
-    if (C > 1)                                 // the artefact is the grey tile: channel 0 of the replicated planes
-        for (size_t p = 0; p < hw * m; ++p) out.tiles[p] = tiles_c[p * C];
+    if (C > 1) keep_channel0(tiles_c.data(), hw * m, C, out.tiles.data());
     out.device_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count();
     return out;
 }
@@ -514,17 +533,8 @@ ChunkText artefact_chunk(const ChunkIn &in, const ChunkOut &out, const std::vect
                 throw std::runtime_error("Preprocessing failed");
             if (!medseg::write_png(output_dir + "/" + base_name + "_mask.png", vis, /*level0=*/true))
                 throw std::runtime_error("Failed to save mask");
-            std::vector<medseg::Contour> contours;
-            if (out.cnt[k] < 0) {                      // capacity overflow on the device: fall back to the host tracer
-                contours = Mask2Polygon::extract_contours(vis);
-            } else {
-                const int32_t *st = &out.start[k * (kCapContours + 1)], *pts = &out.xy[k * (size_t)kCapPoints * 2];
-                for (int c = 0; c < out.cnt[k]; ++c) {
-                    medseg::Contour cc;
-                    for (int q = st[c]; q < st[c + 1]; ++q) cc.emplace_back(pts[2 * q], pts[2 * q + 1]);
-                    contours.push_back(std::move(cc));
-                }
-            }
+            const std::vector<medseg::Contour> contours =
+                contours_of(&out.xy[k * (size_t)kCapPoints * 2], &out.start[k * (kCapContours + 1)], out.cnt[k], vis);
             Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, widths[i], heights[i], con);
             lg << "Processing completed for: " << base_name << std::endl;
             done[k] = 1;
@@ -703,7 +713,7 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
             try {
                 if (!ctx) lg << "\n=== Processing Image: " << fs::path(paths[i]).filename().string() << " ===" << std::endl;
                 Image8 tile(g_cfg.height, g_cfg.width, 1);
-                for (size_t p = 0; p < hw; ++p) tile.data[p] = tiles[(k * hw + p) * C];      // channel 0: the planes are replicas
+                keep_channel0(&tiles[k * hw * C], hw, C, tile.data.data());
                 if (!Preprocess::write_preprocess_outputs(tile, paths[i], output_dir + "/" + base_name + "_normalized.png",
                                                           output_dir + "/" + base_name + "_original_sizes.json", widths[i], heights[i]))
                     throw std::runtime_error("Preprocessing failed");
@@ -721,18 +731,9 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                     }
                     if (!medseg::write_png(output_dir + "/" + base_name + "_mask_class" + std::to_string(targets[t].cls) + ".png", vis, /*level0=*/true))
                         throw std::runtime_error("Failed to save mask");
-                    medseg::ClassContours g{ targets[t].cls, {} };
-                    if (cnt[plane] < 0) {              // the host chain, or a capacity overflow on the device: the host tracer
-                        g.contours = Mask2Polygon::extract_contours(vis);
-                    } else {
-                        const int32_t *st = &start[plane * (kCapContours + 1)], *pts = &xy[plane * (size_t)kCapPoints * 2];
-                        for (int c = 0; c < cnt[plane]; ++c) {
-                            medseg::Contour cc;
-                            for (int q = st[c]; q < st[c + 1]; ++q) cc.emplace_back(pts[2 * q], pts[2 * q + 1]);
-                            g.contours.push_back(std::move(cc));
-                        }
-                    }
-                    groups.push_back(std::move(g));
+                    // (the host chain leaves cnt at -1 and xy empty: the host tracer)
+                    groups.push_back({ targets[t].cls, contours_of(xy.data() + (device_tail ? plane * (size_t)kCapPoints * 2 : 0),
+                                                                   &start[plane * (kCapContours + 1)], cnt[plane], vis) });
                 }
                 Mask2Polygon::write_polygon_outputs(groups, tile, output_dir, base_name, widths[i], heights[i]);
                 if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
@@ -820,8 +821,8 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             mi_unet_group_set_postprocess(group, 0);
             if (rc != MI_UNET_OK) throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
         }
-        if (C > 1) {                               // keep channel 0 (the planes are replicas): the grey artefact tile
-            for (size_t p = 0; p < hw * idx.size(); ++p) tiles[p] = tiles[p * C];
+        if (C > 1) {
+            keep_channel0(tiles.data(), hw * idx.size(), C, tiles.data());
             tiles.resize(hw * idx.size());
         }
         const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count();
@@ -923,22 +924,12 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
                                                  vis.data.data(), xy.data(), kCapPoints, start.data(), kCapContours, &cnt);
             if (rc != MI_UNET_OK) throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
             raw.reset();
-            if (C > 1)
-                for (size_t p = 0; p < hw; ++p) tile.data[p] = tile_c[p * C];
+            if (C > 1) keep_channel0(tile_c.data(), hw, C, tile.data.data());
             const double device_ms = ms_since(infer_start);
             float st[MI_UNET_N_STAGES] = {};
             mi_unet_last_stage_ms(ctx, st);
             lg << "Inference time: " << (long long)device_ms << " ms" << std::endl;
-            std::vector<medseg::Contour> contours;
-            if (cnt < 0) {                             // capacity overflow on the device: the host tracer takes over
-                contours = Mask2Polygon::extract_contours(vis);
-            } else {
-                for (int k = 0; k < cnt; ++k) {
-                    medseg::Contour cc;
-                    for (int q = start[k]; q < start[k + 1]; ++q) cc.emplace_back(xy[2 * q], xy[2 * q + 1]);
-                    contours.push_back(std::move(cc));
-                }
-            }
+            const std::vector<medseg::Contour> contours = contours_of(xy.data(), start.data(), cnt, vis);
             // artefacts: {normalized.png + sizes.json} || {mask.png} || {overlay.png + polygon json}
             const auto t_art = clk::now();
             double norm_ms = 0, mask_ms = 0, poly_ms = 0;
@@ -995,7 +986,7 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             const int rc = mi_unet_infer_raw16(ctx, planes.data(), ws.data(), hs.data(), 1, tile_c.data(), pred_mask.data.data(), nullptr);
             mi_unet_set_postprocess(ctx, 0);
             if (rc != MI_UNET_OK) throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
-            for (size_t p = 0; p < hw; ++p) tile.data[p] = tile_c[p * C];
+            keep_channel0(tile_c.data(), hw, C, tile.data.data());
             const auto infer_ms = std::chrono::duration_cast<std::chrono::milliseconds>(
                                       std::chrono::high_resolution_clock::now() - infer_start).count();
             lg << "Inference time: " << infer_ms << " ms" << std::endl;
