@@ -3,6 +3,7 @@
 #include <string>
 #include <vector>
 
+#include "../mi_unet.h"
 #include "image.h"
 
 namespace MedicalSeg {
@@ -30,6 +31,14 @@ struct Target {
 };
 bool set_targets(const std::vector<Target> &targets);
 std::vector<Target> get_targets();
+
+// The intensity window of the RAW input (mi_unet_window in include/mi_unet.h) that the two functions above apply, on the
+// device and on the MEDSEG_HOST_PREPROCESS route alike: the default min/max stretch, a percentile clip or a fixed lo..hi.  Needs no
+// engine (the setting survives initialize_engine and is handed to every engine, lane and thread context); false, message on stderr,
+// and nothing changed for a setting the engine refuses.  Under a non-default window the size JSON of an image gains "window_lo" and
+// "window_hi", the window it got; under the default every artefact is what it always was.
+bool set_window(const mi_unet_window &window);
+mi_unet_window get_window();
 
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.

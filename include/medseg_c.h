@@ -5,6 +5,7 @@
  */
 #ifndef MEDSEG_C_H
 #define MEDSEG_C_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -32,6 +33,13 @@ int medseg_postprocess_mask_target(const uint8_t *mask, int w, int h, int cls, f
  * fills at most cap entries. */
 int medseg_set_targets(const int *cls, const float *min_area_frac, int n);
 int medseg_get_targets(int *cls, float *min_area_frac, int cap);
+/* Intensity windows (mi_unet_window in include/mi_unet.h): MedicalSeg::set_window / get_window as (mode, clip_lo_ppm, clip_hi_ppm, lo,
+ * hi) -- 0 on success, 1 and nothing changed for a setting the engine refuses; no engine needed -- and the CPU arithmetic:
+ * Preprocess::window_of (0 on success) and Preprocess::resample_normalize_window */
+int medseg_set_window(int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi);
+void medseg_get_window(int *mode, int *clip_lo_ppm, int *clip_hi_ppm, int *lo, int *hi);
+int medseg_window_of(const uint16_t *src, size_t n, int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi, int *out_lo, int *out_hi);
+int medseg_resample_normalize_window(const uint16_t *src, int w, int h, int lo, int hi, uint8_t *dst, int out_w, int out_h);
 /* Mask2Polygon::polygon_json_text for groups: group g has class group_cls[g] and the next group_contours[g] contours of the flattened
  * list (xy / start as in medseg_generate_json).  Writes the document (no terminator) into out and returns its length, or -1 when cap
  * bytes are too few. */

@@ -237,6 +237,40 @@ int mi_unet_segment_raw16_multi(mi_unet_t *h, const uint16_t *const *raws, const
 int mi_unet_segment_tiled_raw16_multi(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
                                       int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count);
 
+/* ---- Intensity windows: which sample range of a RAW16 plane becomes 0..255 ---------------------------------------
+ * A per-handle setting that every RAW-in entry point reads (mi_unet_infer_raw16, mi_unet_segment_raw16{,_multi},
+ * mi_unet_infer_tiled_raw16, mi_unet_segment_tiled_raw16{,_multi} and their group forms).  The default, MINMAX, is the reference's
+ * stretch of the exact minimum and maximum, unchanged bit for bit.  One hot or dead pixel sets that window; the other two modes do
+ * not depend on single samples.
+ * The window is per plane (every plane of an in_ch > 1 image has its own, as it has its own min / max; a pointer passed in_ch times
+ * is scanned once).  With the plane's n samples sorted ascending as s[0 .. n - 1]:
+ *   PERCENTILE : k_lo = floor(n * clip_lo_ppm / 1000000), k_hi = floor(n * clip_hi_ppm / 1000000) in 64-bit integers;
+ *                lo = s[k_lo], hi = s[n - 1 - k_hi].  Exact (a radix select on the device), never an estimate; 0, 0 ppm is min / max.
+ *   FIXED      : lo, hi as given; nothing is scanned.
+ * Quantisation in these two modes, for the resampling and the tiled path alike: L = lo, Hh = hi if hi > lo else lo + 1 (in int, no
+ * wrap), v = the sample or the fp64 bilinear interpolant of the min/max path, vc = min(max(v, L), Hh),
+ * byte = (uint8_t)(int)((vc - L) * (255.0 / (Hh - L)) + 0.5), every operation rounded once.  PERCENTILE at 0, 0 ppm returns the
+ * bytes of MINMAX.  Planes of 2^32 samples or more are refused with MI_UNET_EARG in PERCENTILE mode.
+ * MI_UNET_EARG, setting unchanged: an unknown mode; PERCENTILE with a negative ppm or clip_lo_ppm + clip_hi_ppm >= 1000000; FIXED
+ * outside 0 <= lo < hi <= 65535.  Fields the mode does not use are ignored.  w == NULL restores the default; a clone starts at the
+ * default.  mi_unet_group_set_window changes every rank or none.
+ * mi_unet_window_of is the definition as pure host arithmetic (needs no device): the window of n samples under *w.
+ * mi_unet_last_windows: the windows the LAST RAW-in call on this handle applied, one (lo, hi) pair per plane in call order (B * in_ch
+ * planes; tiled: in_ch), as found -- before the lo + 1 bump; in MINMAX mode the min / max.  Writes min(count, cap) pairs and the
+ * count to *n; MI_UNET_ESTATE before any RAW-in call has completed.  The selection counts under MI_UNET_STAGE_UPLOAD_PRE. */
+#define MI_UNET_WINDOW_MINMAX     0   /* default: the reference's min/max stretch, unchanged bit for bit */
+#define MI_UNET_WINDOW_PERCENTILE 1   /* clip a share of the samples at each end */
+#define MI_UNET_WINDOW_FIXED      2   /* the caller's lo..hi */
+typedef struct mi_unet_window {
+    int mode;
+    int clip_lo_ppm, clip_hi_ppm;   /* PERCENTILE: samples clipped at the dark / bright end, parts per million of the plane */
+    int lo, hi;                     /* FIXED: 0 <= lo < hi <= 65535 */
+} mi_unet_window;
+int mi_unet_set_window(mi_unet_t *h, const mi_unet_window *w);
+int mi_unet_get_window(const mi_unet_t *h, mi_unet_window *w);
+int mi_unet_window_of(const uint16_t *samples, size_t n, const mi_unet_window *w, int *lo, int *hi);
+int mi_unet_last_windows(const mi_unet_t *h, int32_t *lo_hi, int cap, int *n);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only
@@ -389,6 +423,8 @@ int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n
 int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                                       uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                       int32_t *counts);
+/* mi_unet_set_window on every rank (all or none); the sharded RAW-in calls above then apply it */
+int mi_unet_group_set_window(mi_unet_group_t *g, const mi_unet_window *w);
 void mi_unet_group_destroy(mi_unet_group_t *g);
 /* The split itself (pure host arithmetic, needs no device): rank's range [*lo, *hi) of n_items over `world` ranks. */
 int mi_unet_shard_range(int n_items, int rank, int world, int *lo, int *hi);

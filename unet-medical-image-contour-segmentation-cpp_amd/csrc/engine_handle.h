@@ -104,7 +104,19 @@ struct mi_unet {
     miunet::Event raw_done[RAW_RING];       // the slot's transfer and kernels have completed
     bool raw_busy[RAW_RING] = {};
     size_t raw_cap = 0;             // samples per slot
-    miunet::DeviceBuf<unsigned> d_mnmx;     // [max_batch][2]
+    // one (lo, hi) slot of two u32 per plane of the running RAW-in call ([B * in_ch][2], tiled: [in_ch][2]; grown on demand):
+    // written by the min/max or the window selection of the plane, read by its resample / normalise launch, downloaded once at the
+    // end of the call into h_win for mi_unet_last_windows
+    miunet::DeviceBuf<unsigned> d_mnmx;
+    miunet::PinnedBuf<unsigned> h_win;
+    size_t win_cap = 0;                     // slots of the two above
+    // mi_unet_set_window; d_win_ws = zeroed-per-use scratch of launch_window_select_u16, one slot per plane of a micro-batch
+    mi_unet_window window{ MI_UNET_WINDOW_MINMAX, 0, 0, 0, 65535 };
+    miunet::DeviceBuf<uint8_t> d_win_ws;
+    size_t win_ws_slots = 0;
+    std::vector<int> win_src;               // per plane of the call: the plane whose slot holds its window (a pointer passed in_ch times)
+    std::vector<int32_t> last_win;          // mi_unet_last_windows: (lo, hi) per plane of the last completed call
+    bool last_win_valid = false;
     miunet::DeviceBuf<float> d_ksplit;      // split-K slabs of the Winograd kernel (small batches / deep levels only)
     size_t ksplit_bytes = 0;
     miunet::DeviceBuf<int> d_cont;          // contour outputs of mi_unet_extract_contours (grown on demand)
@@ -228,6 +240,16 @@ void contours_to_caller(const mi_unet *h, const ContourLayout &cl, int32_t *xy, 
 // (t.K == 0, no cl) enqueues nothing but `between`.
 int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const TargetTable &t, uint8_t *d_planes, void *ws,
                  const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where = std::string());
+// ---- window.cpp: the intensity window of the RAW-in entry points
+constexpr mi_unet_window kDefaultWindow{ MI_UNET_WINDOW_MINMAX, 0, 0, 0, 65535 };
+int check_window(const mi_unet_window &w, const char *fn);   // MI_UNET_EARG + message for a setting mi_unet_set_window refuses
+// before a RAW-in call enqueues anything: slots for `planes` windows, scratch for `scratch_planes` selections at once (PERCENTILE only),
+// and the call's bookkeeping reset.  PERCENTILE refuses a plane of 2^32 samples or more (max_samples = the call's largest plane).
+int begin_window_call(mi_unet *h, size_t planes, size_t scratch_planes, unsigned long long max_samples, const std::string &fn);
+// min/max or selection of one plane into slot `slot` (scratch slot `ws_slot`) on `s`; FIXED enqueues nothing
+hipError_t enqueue_window(mi_unet *h, const uint16_t *d_raw, size_t n, size_t slot, size_t ws_slot, hipStream_t s);
+int enqueue_window_download(mi_unet *h, size_t planes, hipStream_t s);     // slots -> h_win (nothing for FIXED)
+void finish_window_call(mi_unet *h, size_t planes);                        // after the download has completed: h_win -> last_win
 // ---- pipeline_raw.cpp: large host copies on the handle's helper threads
 void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes);
 // ---- debug.cpp: mi_unet_debug_capture's taps, called by launch_plan around the tapped step

@@ -427,6 +427,16 @@ int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n
     return MI_UNET_OK;
 }
 
+int mi_unet_group_set_window(mi_unet_group_t *g, const mi_unet_window *w)
+{
+    if (!g) return engine_fail(MI_UNET_EARG, "null group");
+    std::lock_guard<std::mutex> lk(g->call_mutex);       // never while a group call is in flight
+    // the verdict does not depend on the rank: the first rank's is everybody's, so all ranks change or none does
+    for (mi_unet_t *h : g->eng)
+        if (int rc = mi_unet_set_window(h, w)) return rc;
+    return MI_UNET_OK;
+}
+
 int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                                       uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                       int32_t *counts)

@@ -55,18 +55,31 @@ hipError_t launch_minmax_u16(const uint16_t *raw, size_t n, unsigned *mnmx, hipS
     return hipGetLastError();
 }
 
+// WINDOW = false: the reference's min/max stretch (mnmx = launch_minmax_u16's pair).  WINDOW = true: an intensity window (DESIGN.md
+// 7.5) -- the pair from launch_window_select_u16's slot or, with mnmx null, the arguments win_lo / win_hi -- with the interpolant
+// clamped to it; the degenerate-window bump is evaluated in int there, so nothing wraps.
+template <bool WINDOW>
 __global__ __launch_bounds__(256) void resample_u8_kernel(const uint16_t *__restrict__ raw, int w, int h,
-                                                          const unsigned *__restrict__ mnmx, uint8_t *__restrict__ dst,
-                                                          int outW, int outH, int dst_stride)
+                                                          const unsigned *__restrict__ mnmx, int win_lo, int win_hi,
+                                                          uint8_t *__restrict__ dst, int outW, int outH, int dst_stride)
 {
 #pragma clang fp contract(off)
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= outW || y >= outH) return;
-    const unsigned short mn = (unsigned short)mnmx[0];
-    unsigned short mx = (unsigned short)mnmx[1];
-    if (mn == mx) mx = (unsigned short)(mn + 1);                // evaluated in uint16_t: wraps to 0 at 65535 (src/preprocess.cpp:92)
-    const double scale8 = 255.0 / (double)((int)mx - (int)mn);
+    double lo8, hi8 = 0.0, scale8;
+    if constexpr (WINDOW) {
+        const int L = mnmx ? (int)mnmx[0] : win_lo, hi = mnmx ? (int)mnmx[1] : win_hi;
+        const int Hh = hi > L ? hi : L + 1;
+        lo8 = (double)L; hi8 = (double)Hh;
+        scale8 = 255.0 / (double)(Hh - L);
+    } else {
+        const unsigned short mn = (unsigned short)mnmx[0];
+        unsigned short mx = (unsigned short)mnmx[1];
+        if (mn == mx) mx = (unsigned short)(mn + 1);            // evaluated in uint16_t: wraps to 0 at 65535 (src/preprocess.cpp:92)
+        lo8 = (double)mn;
+        scale8 = 255.0 / (double)((int)mx - (int)mn);
+    }
     const double stepX = (double)w / (double)outW, stepY = (double)h / (double)outH;
     const double fx = __dmul_rn((double)x, stepX), fy = __dmul_rn((double)y, stepY);
     const int ix = (int)fx, iy = (int)fy;
@@ -81,7 +94,8 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const uint16_t *__rest
     v = __dadd_rn(v, __dmul_rn(__dmul_rn(dx, omdy), v01));
     v = __dadd_rn(v, __dmul_rn(__dmul_rn(omdx, dy), v10));
     v = __dadd_rn(v, __dmul_rn(__dmul_rn(dx, dy), v11));
-    const double q = __dadd_rn(__dmul_rn(__dsub_rn(v, (double)mn), scale8), 0.5);
+    if constexpr (WINDOW) v = v < lo8 ? lo8 : v > hi8 ? hi8 : v;
+    const double q = __dadd_rn(__dmul_rn(__dsub_rn(v, lo8), scale8), 0.5);
     dst[((size_t)y * outW + x) * dst_stride] = (uint8_t)(int)q;      // dst_stride > 1: one plane of an interleaved (HWC) tile
 }
 
@@ -89,8 +103,145 @@ hipError_t launch_resample_u8(const uint16_t *raw, int w, int h, const unsigned 
                               int dst_stride, hipStream_t s)
 {
     if (w <= 0 || h <= 0 || outW <= 0 || outH <= 0 || dst_stride < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(resample_u8_kernel, dim3((outW + 63) / 64, (outH + 3) / 4), dim3(256), 0, s, raw, w, h, mnmx, dst, outW, outH,
-                       dst_stride);
+    hipLaunchKernelGGL(resample_u8_kernel<false>, dim3((outW + 63) / 64, (outH + 3) / 4), dim3(256), 0, s, raw, w, h, mnmx, 0, 0, dst, outW,
+                       outH, dst_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_u8_window(const uint16_t *raw, int w, int h, const unsigned *mnmx, int lo, int hi, uint8_t *dst, int outW,
+                                     int outH, int dst_stride, hipStream_t s)
+{
+    if (w <= 0 || h <= 0 || outW <= 0 || outH <= 0 || dst_stride < 1) return hipErrorInvalidValue;
+    if (!mnmx && (lo < 0 || lo > hi || hi > 65535)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resample_u8_kernel<true>, dim3((outW + 63) / 64, (outH + 3) / 4), dim3(256), 0, s, raw, w, h, mnmx, lo, hi, dst, outW,
+                       outH, dst_stride);
+    return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// Intensity windows: the two order statistics of a plane by a two-pass radix select.  One 65536-bin histogram
+// would need global atomics (256 KiB of u32 bins do not fit the LDS), and medical images pile onto a few hundred values: every
+// wave of the plane would queue on the same words (see cc_stats below).  Instead: pass 1 counts the HIGH bytes -- 256 bins, one
+// private histogram per wave in LDS, a lane merging the equal neighbours among its 8 samples before it touches LDS, the four waves
+// summed in LDS and one global add per NON-EMPTY bin per workgroup; the head of pass 2 finds the two high bytes that hold the ranks
+// (every workgroup scans the same 256 counts) and counts the LOW bytes of the samples under either; a one-workgroup kernel scans
+// again and writes the pair.  No host round trip; the plane is read twice.
+struct WindowScratch {
+    unsigned hi_hist[256];          // samples per high byte
+    unsigned lo_hist[2][256];       // samples per low byte under the high byte of rank 0 / of rank 1 (unused when both share one)
+};
+constexpr unsigned WIN_NONE = 0xFFFFFFFFu;
+
+// The bin of hist[256] that holds rank k (cum(b - 1) <= k < cum(b)) and k - cum(b - 1), for two ranks at once; all 256 threads
+// call it and all receive the result.  Counts sum to < 2^32.
+struct WindowPick { unsigned bin[2], rest[2]; };
+__device__ __forceinline__ WindowPick window_pick2(const unsigned *hist, unsigned k0, unsigned k1, unsigned *s_tot /*[4]*/,
+                                                   unsigned *s_sel /*[4]*/)
+{
+    const unsigned t = threadIdx.x, c = hist[t];
+    unsigned inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {                          // inclusive scan inside the wave
+        const unsigned u = (unsigned)__shfl_up((int)inc, o, 64);
+        if ((t & 63) >= (unsigned)o) inc += u;
+    }
+    if (t < 4) s_sel[t] = 0;
+    if ((t & 63) == 63) s_tot[t >> 6] = inc;
+    __syncthreads();
+    for (unsigned wv = 0; wv < (t >> 6); ++wv) inc += s_tot[wv];
+    const unsigned exc = inc - c;
+    if (exc <= k0 && k0 < inc) { s_sel[0] = t; s_sel[1] = k0 - exc; }      // exactly one non-empty bin per rank
+    if (exc <= k1 && k1 < inc) { s_sel[2] = t; s_sel[3] = k1 - exc; }
+    __syncthreads();
+    const WindowPick p{ { s_sel[0], s_sel[2] }, { s_sel[1], s_sel[3] } };
+    __syncthreads();                                            // s_tot / s_sel may be reused
+    return p;
+}
+
+// LOW = false: pass 1, hi_hist += high bytes.  LOW = true: pass 2, lo_hist[j] += low bytes of the samples whose high byte holds rank j.
+template <bool LOW>
+__global__ __launch_bounds__(256) void window_hist_kernel(const uint16_t *__restrict__ raw, size_t n, WindowScratch *ws, unsigned k0,
+                                                          unsigned k1)
+{
+    constexpr int NH = LOW ? 2 : 1;
+    __shared__ unsigned s_h[4][NH * 256];
+    __shared__ unsigned s_tot[4], s_sel[4];
+    for (int i = threadIdx.x; i < 4 * NH * 256; i += 256) (&s_h[0][0])[i] = 0;
+    unsigned hb0 = 0, hb1 = 0;
+    if constexpr (LOW) {
+        const WindowPick p = window_pick2(ws->hi_hist, k0, k1, s_tot, s_sel);
+        hb0 = p.bin[0]; hb1 = p.bin[1];
+    }
+    __syncthreads();
+    unsigned *mine = s_h[threadIdx.x >> 6];
+    unsigned cur = WIN_NONE, cnt = 0;                           // a lane's run of equal keys: one LDS add per run
+    auto put = [&](unsigned v) {
+        unsigned key;
+        if constexpr (LOW) key = (v >> 8) == hb0 ? (v & 255u) : (v >> 8) == hb1 ? 256u + (v & 255u) : WIN_NONE;
+        else key = v >> 8;
+        if (key != cur) {
+            if (cnt) atomicAdd(&mine[cur], cnt);
+            cur = key; cnt = 0;
+        }
+        cnt += key != WIN_NONE;                                 // cnt > 0 only under a real key
+    };
+    const size_t n8 = n / 8, stride = (size_t)gridDim.x * 256;  // 16 bytes = 8 samples per lane, four loads in flight
+    const uint4 *v = reinterpret_cast<const uint4 *>(raw);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += 4 * stride) {
+        uint4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u * stride < n8) q[u] = v[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i + u * stride >= n8) break;
+            const unsigned wd[4] = { q[u].x, q[u].y, q[u].z, q[u].w };
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { put(wd[k] & 0xFFFFu); put(wd[k] >> 16); }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) put(raw[n8 * 8 + threadIdx.x]);       // ragged tail
+    if (cnt) atomicAdd(&mine[cur], cnt);
+    __syncthreads();
+    const int used = (LOW && hb0 != hb1) ? 2 : 1;
+    for (int j = 0; j < used; ++j) {
+        const int b = j * 256 + threadIdx.x;
+        const unsigned sum = s_h[0][b] + s_h[1][b] + s_h[2][b] + s_h[3][b];
+        if (sum) atomicAdd(LOW ? &ws->lo_hist[j][threadIdx.x] : &ws->hi_hist[threadIdx.x], sum);
+    }
+}
+
+__global__ __launch_bounds__(256) void window_pick_kernel(const WindowScratch *ws, unsigned k0, unsigned k1, unsigned *mnmx)
+{
+    __shared__ unsigned s_tot[4], s_sel[4];
+    const WindowPick hi = window_pick2(ws->hi_hist, k0, k1, s_tot, s_sel);
+    const bool one = hi.bin[0] == hi.bin[1];                    // both ranks under one high byte: one low-byte histogram serves both
+    const WindowPick a = window_pick2(ws->lo_hist[0], hi.rest[0], one ? hi.rest[1] : hi.rest[0], s_tot, s_sel);
+    unsigned low1 = a.bin[1];
+    if (!one) low1 = window_pick2(ws->lo_hist[1], hi.rest[1], hi.rest[1], s_tot, s_sel).bin[0];
+    if (threadIdx.x == 0) {
+        mnmx[0] = (hi.bin[0] << 8) | a.bin[0];
+        mnmx[1] = (hi.bin[1] << 8) | low1;
+    }
+}
+
+size_t window_scratch_bytes() { return sizeof(WindowScratch); }
+
+hipError_t launch_window_select_u16(const uint16_t *raw, size_t n, int clip_lo_ppm, int clip_hi_ppm, void *scratch, unsigned *mnmx,
+                                    hipStream_t s)
+{
+    if (!raw || !scratch || !mnmx || n == 0 || n >= (1ull << 32) || (reinterpret_cast<uintptr_t>(raw) & 15)) return hipErrorInvalidValue;
+    if (clip_lo_ppm < 0 || clip_hi_ppm < 0 || (long long)clip_lo_ppm + clip_hi_ppm >= 1000000) return hipErrorInvalidValue;
+    // ranks in 64-bit integers: n < 2^32, ppm < 2^20.  k_lo + k_hi <= n - 1, so k0 <= k1
+    const unsigned k0 = (unsigned)((unsigned long long)n * (unsigned)clip_lo_ppm / 1000000ull);
+    const unsigned k1 = (unsigned)(n - 1 - (unsigned long long)n * (unsigned)clip_hi_ppm / 1000000ull);
+    size_t blocks = (n / 8 + 1023) / 1024;                      // four vectors per lane and trip
+    if (blocks > 512) blocks = 512;
+    if (blocks == 0) blocks = 1;
+    WindowScratch *ws = static_cast<WindowScratch *>(scratch);
+    hipLaunchKernelGGL(window_hist_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, raw, n, ws, k0, k1);
+    hipLaunchKernelGGL(window_hist_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, raw, n, ws, k0, k1);
+    hipLaunchKernelGGL(window_pick_kernel, dim3(1), dim3(256), 0, s, ws, k0, k1, mnmx);
     return hipGetLastError();
 }
 

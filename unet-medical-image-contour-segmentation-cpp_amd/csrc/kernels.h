@@ -156,6 +156,23 @@ hipError_t launch_minmax_u16(const uint16_t *raw, size_t n, unsigned *mnmx, hipS
 hipError_t launch_resample_u8(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int outW, int outH,
                               int dst_stride, hipStream_t s);
 
+// Intensity windows (include/mi_unet.h: mi_unet_set_window).
+//   window_select : the exact order statistics s[k_lo] and s[n - 1 - k_hi] of n u16 samples (k = floor(n * ppm / 1e6)) into mnmx[0],
+//                   mnmx[1]: a two-pass radix select -- 256-bin histogram of the high byte, then of the low byte of the samples whose
+//                   high byte holds either rank -- with per-wave histograms in LDS and one global add per non-empty bin per
+//                   workgroup.  `scratch` = window_scratch_bytes() of device memory per plane, ZEROED on the stream by the caller;
+//                   raw 16-byte aligned, 0 < n < 2^32 (u32 counters)
+//   resample_u8_window / normalise_u16_window : launch_resample_u8 / launch_normalise_u16 with the window's quantisation: L = lo,
+//                   Hh = hi > lo ? hi : lo + 1 (in int), vc = min(max(v, L), Hh), byte = (uchar)(int)((vc - L) * (255.0 / (Hh - L)) + 0.5).
+//                   The pair is read from `mnmx` (window_select's slot) or, when mnmx is null, is the arguments lo, hi (a fixed window)
+size_t window_scratch_bytes();
+hipError_t launch_window_select_u16(const uint16_t *raw, size_t n, int clip_lo_ppm, int clip_hi_ppm, void *scratch, unsigned *mnmx,
+                                    hipStream_t s);
+hipError_t launch_resample_u8_window(const uint16_t *raw, int w, int h, const unsigned *mnmx, int lo, int hi, uint8_t *dst, int outW,
+                                     int outH, int dst_stride, hipStream_t s);
+hipError_t launch_normalise_u16_window(const uint16_t *raw, int w, int h, const unsigned *mnmx, int lo, int hi, uint8_t *dst,
+                                       int dst_stride, hipStream_t s);
+
 // Tiled inference (tiles.hip).  The grid is tile_grid.h's: tiles of th x tw with `halo`, numbered row-major.  Every
 // launcher rebuilds the grid from (H, W, th, tw, halo) and checks the tile range [t0, t0 + nb) against it.
 //   gather    : image u8 [H][W][C] -> tiles t0 .. t0 + nb - 1 as u8 [nb][th][tw][C].  img_bytes = bytes readable behind `img`; the

@@ -36,11 +36,14 @@ void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes)
 
 namespace {
 
-int stage_raw16(mi_unet *h, const uint16_t *const *raws, const int *widths, const int *heights, int bm, hipStream_t s, uint8_t *d_tiles)
+// `plane0` = index of the micro-batch's first plane in the call: plane i's window lives in slot plane0 + i (begin_window_call)
+int stage_raw16(mi_unet *h, const uint16_t *const *raws, const int *widths, const int *heights, int bm, size_t plane0, hipStream_t s,
+                uint8_t *d_tiles)
 {
     const int C = h->cfg.in_ch;
     const size_t hw = (size_t)h->cfg.height * h->cfg.width;
-    if (!h->d_mnmx) HIP_TRY(h->d_mnmx.reset((size_t)2 * h->cfg.max_batch * C));
+    const mi_unet_window &win = h->window;
+    const bool minmax = win.mode == MI_UNET_WINDOW_MINMAX, fixed = win.mode == MI_UNET_WINDOW_FIXED;
     int slot = mi_unet::RAW_RING - 1, mn_src = 0;
     for (int i = 0; i < bm * C; ++i) {
         const int w = widths[i], ht = heights[i];
@@ -74,10 +77,14 @@ int stage_raw16(mi_unet *h, const uint16_t *const *raws, const int *widths, cons
             HIP_TRY(hipMemcpyAsync(h->d_raw[slot], pinned ? raws[i] : h->h_raw[slot], n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         }
         const int r = slot;
-        hipError_t e = same_plane ? hipSuccess : launch_minmax_u16(h->d_raw[r], n, h->d_mnmx + 2 * mn_src, s);
+        h->win_src[plane0 + i] = (int)(plane0 + mn_src);
+        const unsigned *pair = h->d_mnmx + 2 * (plane0 + mn_src);
+        uint8_t *dst = d_tiles + (size_t)(i / C) * hw * C + i % C;
+        hipError_t e = same_plane ? hipSuccess : enqueue_window(h, h->d_raw[r], n, plane0 + mn_src, (size_t)mn_src, s);
         if (e == hipSuccess)
-            e = launch_resample_u8(h->d_raw[r], w, ht, h->d_mnmx + 2 * mn_src, d_tiles + (size_t)(i / C) * hw * C + i % C, h->cfg.width,
-                                   h->cfg.height, C, s);
+            e = minmax ? launch_resample_u8(h->d_raw[r], w, ht, pair, dst, h->cfg.width, h->cfg.height, C, s)
+                       : launch_resample_u8_window(h->d_raw[r], w, ht, fixed ? nullptr : pair, win.lo, win.hi, dst, h->cfg.width,
+                                                   h->cfg.height, C, s);
         if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("preprocess launch: ") + hipGetErrorString(e));
         HIP_TRY(hipEventRecord(h->raw_done[r], s));
         h->raw_busy[r] = true;
@@ -134,9 +141,13 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     const int K = segment ? tab.K : 1;
     // every image description is checked BEFORE anything is enqueued: a bad width in image k + 1 must not be found after the
     // network of micro-batch k has started
-    for (size_t i = 0; i < (size_t)c.B * C; ++i)
+    unsigned long long max_samples = 0;
+    for (size_t i = 0; i < (size_t)c.B * C; ++i) {
         if (!c.raws[i] || c.widths[i] <= 0 || c.heights[i] <= 0)
             return fail(MI_UNET_EARG, "RAW16 input: bad image description (image " + std::to_string(i / C) + ", plane " + std::to_string(i % C) + ")");
+        max_samples = std::max(max_samples, (unsigned long long)c.widths[i] * (unsigned long long)c.heights[i]);
+    }
+    if (int rc = begin_window_call(h, (size_t)c.B * C, (size_t)Bm * C, max_samples, "RAW16 input")) return rc;
     // micro-batches: chunks of max_batch images -- and the FIRST chunk is cut once more when it is large (a quarter, at least
     // four images, then the rest), so that the network starts as soon as a few images have been uploaded and preprocessed
     // and the upload of the rest hides under it.
@@ -181,7 +192,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         const size_t b0 = (size_t)mbs[k].b0;
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(h->pre_stream, c.tiles ? h->tiles_done[par].get() : h->net_done[par].get(), 0));   // its last readers: network and tile download of k - 2
         HIP_TRY(hipEventRecord(h->pre_ev[k % 3][0], h->pre_stream));
-        if (int rc = stage_raw16(h, c.raws + b0 * C, c.widths + b0 * C, c.heights + b0 * C, bm, h->pre_stream, tile_buf(k))) return rc;
+        if (int rc = stage_raw16(h, c.raws + b0 * C, c.widths + b0 * C, c.heights + b0 * C, bm, b0 * C, h->pre_stream, tile_buf(k))) return rc;
         HIP_TRY(hipEventRecord(h->pre_ev[k % 3][1], h->pre_stream));
         HIP_TRY(hipEventRecord(h->tile_ready[par], h->pre_stream));
         return 0;
@@ -220,6 +231,8 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, bm * K * hw, hipMemcpyDeviceToHost, ts));
         if (segment)
             if (int rc = contours_to_pinned(h, cl, ts, par)) return rc;
+        if (k == n_mb - 1)                             // every plane of the call has been staged in front of this network: its windows leave too
+            if (int rc = enqueue_window_download(h, (size_t)c.B * C, ts)) return rc;
         HIP_TRY(hipEventRecord(tv[3], ts));
         HIP_TRY(hipEventRecord(h->out_done[par], ts));
         return 0;
@@ -296,6 +309,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         for (int i = 0; i < mi_unet::RAW_RING; ++i) h->raw_busy[i] = false;
         return fail(rc, keep);
     }
+    finish_window_call(h, (size_t)c.B * C);
     mark("done", 0);
     return MI_UNET_OK;
 }

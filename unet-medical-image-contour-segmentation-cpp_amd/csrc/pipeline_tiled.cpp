@@ -146,7 +146,10 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     if (int rc = ensure_tiled_buffers(h, npix, c.logits != nullptr && !blend, c.planes != nullptr, blend)) return rc;
     if (segment)
         if (int rc = grow_contour_buffers(h, cl)) return rc;
-    if (c.planes && !h->d_mnmx) HIP_TRY(h->d_mnmx.reset((size_t)2 * Bm * C));
+    if (c.planes)
+        if (int rc = begin_window_call(h, (size_t)C, (size_t)C, (unsigned long long)npix, fn)) return rc;
+    const mi_unet_window &win = h->window;
+    const bool minmax = win.mode == MI_UNET_WINDOW_MINMAX, fixed = win.mode == MI_UNET_WINDOW_FIXED;
     mi_unet::Tiled &t = h->tiled;
     if (segment && K * npix > t.multi_cap) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -183,11 +186,13 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
                     host_copy(h, t.h_raw + (size_t)p * plane_stride, c.planes[p], npix * sizeof(uint16_t));
                 }
                 HIP_TRY(hipMemcpyAsync(d_plane, pinned ? c.planes[p] : t.h_raw + (size_t)p * plane_stride, npix * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                e = launch_minmax_u16(d_plane, npix, h->d_mnmx + 2 * p, s);
-                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": min/max launch: " + hipGetErrorString(e));
+                e = enqueue_window(h, d_plane, npix, (size_t)p, (size_t)p, s);
+                if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": min/max or window launch: " + hipGetErrorString(e));
             }
+            h->win_src[p] = mn;
             if (int rc = stat_begin(h, s, e1)) return rc;
-            e = launch_normalise_u16(d_plane, W, H, h->d_mnmx + 2 * mn, t.d_img + p, C, s);
+            e = minmax ? launch_normalise_u16(d_plane, W, H, h->d_mnmx + 2 * mn, t.d_img + p, C, s)
+                       : launch_normalise_u16_window(d_plane, W, H, fixed ? nullptr : h->d_mnmx + 2 * mn, win.lo, win.hi, t.d_img + p, C, s);
             if (e != hipSuccess) return fail(MI_UNET_EHIP, fn + ": normalise launch: " + hipGetErrorString(e));
             if (int rc = stat_end(h, s, e1, ("tiled.normalise." + std::to_string(p)).c_str(), "normalise_u16", 3.0 * npix)) return rc;
         }
@@ -245,6 +250,8 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipMemcpyAsync(h_result, d_result, K * npix, hipMemcpyDeviceToHost, s));
     if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
+    if (c.planes)
+        if (int rc = enqueue_window_download(h, (size_t)C, s)) return rc;
     if (segment)
         if (int rc = contours_to_pinned(h, cl, s)) return rc;
     if (c.logits) HIP_TRY(hipMemcpyAsync(c.logits, blend ? t.d_acc : t.d_logits, sizeof(float) * npix * classes, hipMemcpyDeviceToHost, s));
@@ -253,6 +260,7 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     host_copy(h, c.out_u8, h_result, K * npix);
     if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
     if (segment) contours_to_caller(h, cl, c.xy, c.start, c.count);
+    if (c.planes) finish_window_call(h, (size_t)C);
 
     for (float &m : h->stage_ms) m = 0.f;
     auto span = [&](size_t a, size_t b, int stage) -> int {

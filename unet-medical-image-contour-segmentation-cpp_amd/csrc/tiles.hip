@@ -105,20 +105,34 @@ __global__ __launch_bounds__(256) void tile_gather_views_kernel(const uint8_t *_
 // RAW16 -> u8 at the image's own size: resample_u8_kernel (image_stages.hip) at outW == w, outH == h, where dx = dy = 0 and the
 // four-tap sum is the pixel itself.  The quantisation is that kernel's, operation for operation (fp64, one rounding each, no
 // contraction); 8 samples per lane, one 16-byte load.
-__device__ __forceinline__ uint8_t quantise_u16(unsigned v, unsigned short mn, double scale8)
+// WINDOW: an intensity window instead of the min/max stretch: the sample clamped to [lo, hi], as resample_u8_kernel<true>
+template <bool WINDOW>
+__device__ __forceinline__ uint8_t quantise_u16(unsigned v, double lo, double hi, double scale8)
 {
-    const double q = __dadd_rn(__dmul_rn(__dsub_rn((double)v, (double)mn), scale8), 0.5);
+    double x = (double)v;
+    if constexpr (WINDOW) x = x < lo ? lo : x > hi ? hi : x;
+    const double q = __dadd_rn(__dmul_rn(__dsub_rn(x, lo), scale8), 0.5);
     return (uint8_t)(int)q;
 }
 
+template <bool WINDOW>
 __global__ __launch_bounds__(256) void normalise_u16_kernel(const uint16_t *__restrict__ raw, size_t n, const unsigned *__restrict__ mnmx,
-                                                            uint8_t *__restrict__ dst, int dst_stride)
+                                                            int win_lo, int win_hi, uint8_t *__restrict__ dst, int dst_stride)
 {
 #pragma clang fp contract(off)
-    const unsigned short mn = (unsigned short)mnmx[0];
-    unsigned short mx = (unsigned short)mnmx[1];
-    if (mn == mx) mx = (unsigned short)(mn + 1);                // evaluated in uint16_t, as resample_u8_kernel does
-    const double scale8 = 255.0 / (double)((int)mx - (int)mn);
+    double lo, hi = 0.0, scale8;
+    if constexpr (WINDOW) {                                     // the pair of launch_window_select_u16, or (mnmx null) the arguments
+        const int L = mnmx ? (int)mnmx[0] : win_lo, h0 = mnmx ? (int)mnmx[1] : win_hi;
+        const int Hh = h0 > L ? h0 : L + 1;                     // evaluated in int: nothing wraps
+        lo = (double)L; hi = (double)Hh;
+        scale8 = 255.0 / (double)(Hh - L);
+    } else {
+        const unsigned short mn = (unsigned short)mnmx[0];
+        unsigned short mx = (unsigned short)mnmx[1];
+        if (mn == mx) mx = (unsigned short)(mn + 1);            // evaluated in uint16_t, as resample_u8_kernel does
+        lo = (double)mn;
+        scale8 = 255.0 / (double)((int)mx - (int)mn);
+    }
     const size_t n8 = n / 8;
     const uint4 *v = reinterpret_cast<const uint4 *>(raw);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
@@ -127,8 +141,8 @@ __global__ __launch_bounds__(256) void normalise_u16_kernel(const uint16_t *__re
         uint8_t o[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            o[2 * k] = quantise_u16(ws[k] & 0xFFFFu, mn, scale8);
-            o[2 * k + 1] = quantise_u16(ws[k] >> 16, mn, scale8);
+            o[2 * k] = quantise_u16<WINDOW>(ws[k] & 0xFFFFu, lo, hi, scale8);
+            o[2 * k + 1] = quantise_u16<WINDOW>(ws[k] >> 16, lo, hi, scale8);
         }
         if (dst_stride == 1) {                                  // planar: one 8-byte store
             uint2 p;
@@ -142,7 +156,7 @@ __global__ __launch_bounds__(256) void normalise_u16_kernel(const uint16_t *__re
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {             // ragged tail
         const size_t i = n8 * 8 + threadIdx.x;
-        dst[i * dst_stride] = quantise_u16(raw[i], mn, scale8);
+        dst[i * dst_stride] = quantise_u16<WINDOW>(raw[i], lo, hi, scale8);
     }
 }
 
@@ -269,17 +283,32 @@ hipError_t launch_tile_gather_views(const uint8_t *img, size_t img_bytes, int H,
     return hipGetLastError();
 }
 
-hipError_t launch_normalise_u16(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int dst_stride, hipStream_t s)
+template <bool WINDOW>
+static hipError_t normalise_u16(const uint16_t *raw, int w, int h, const unsigned *mnmx, int lo, int hi, uint8_t *dst, int dst_stride,
+                                hipStream_t s)
 {
-    if (!raw || !mnmx || !dst || w <= 0 || h <= 0 || dst_stride < 1) return hipErrorInvalidValue;
+    if (!raw || !dst || w <= 0 || h <= 0 || dst_stride < 1) return hipErrorInvalidValue;
     if (reinterpret_cast<uintptr_t>(raw) & 15) return hipErrorInvalidValue;
     if (dst_stride == 1 && (reinterpret_cast<uintptr_t>(dst) & 7)) return hipErrorInvalidValue;
     const size_t n = (size_t)w * h;
     size_t blocks = (n / 8 + 255) / 256;
     if (blocks == 0) blocks = 1;
     if (blocks >= (1u << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(normalise_u16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, raw, n, mnmx, dst, dst_stride);
+    hipLaunchKernelGGL(normalise_u16_kernel<WINDOW>, dim3((unsigned)blocks), dim3(256), 0, s, raw, n, mnmx, lo, hi, dst, dst_stride);
     return hipGetLastError();
+}
+
+hipError_t launch_normalise_u16(const uint16_t *raw, int w, int h, const unsigned *mnmx, uint8_t *dst, int dst_stride, hipStream_t s)
+{
+    if (!mnmx) return hipErrorInvalidValue;
+    return normalise_u16<false>(raw, w, h, mnmx, 0, 0, dst, dst_stride, s);
+}
+
+hipError_t launch_normalise_u16_window(const uint16_t *raw, int w, int h, const unsigned *mnmx, int lo, int hi, uint8_t *dst,
+                                       int dst_stride, hipStream_t s)
+{
+    if (!mnmx && (lo < 0 || lo > hi || hi > 65535)) return hipErrorInvalidValue;
+    return normalise_u16<true>(raw, w, h, mnmx, lo, hi, dst, dst_stride, s);
 }
 
 hipError_t launch_tile_stitch(const uint8_t *tile_labels, const float *tile_logits, int classes, int H, int W, int th, int tw, int halo,

@@ -109,6 +109,27 @@ int medseg_get_targets(int *cls, float *min_area_frac, int cap)
     for (int i = 0; i < (int)t.size() && i < cap; ++i) { cls[i] = t[i].cls; min_area_frac[i] = t[i].min_area_frac; }
     return (int)t.size();
 }
+int medseg_set_window(int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi)
+{
+    return MedicalSeg::set_window(mi_unet_window{ mode, clip_lo_ppm, clip_hi_ppm, lo, hi }) ? 0 : 1;
+}
+void medseg_get_window(int *mode, int *clip_lo_ppm, int *clip_hi_ppm, int *lo, int *hi)
+{
+    const mi_unet_window w = MedicalSeg::get_window();
+    *mode = w.mode; *clip_lo_ppm = w.clip_lo_ppm; *clip_hi_ppm = w.clip_hi_ppm; *lo = w.lo; *hi = w.hi;
+}
+int medseg_window_of(const uint16_t *src, size_t n, int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi, int *out_lo, int *out_hi)
+{
+    if (!src || !out_lo || !out_hi) return 1;
+    return Preprocess::window_of(src, n, mi_unet_window{ mode, clip_lo_ppm, clip_hi_ppm, lo, hi }, *out_lo, *out_hi) ? 0 : 1;
+}
+int medseg_resample_normalize_window(const uint16_t *src, int w, int h, int lo, int hi, uint8_t *dst, int out_w, int out_h)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || out_w <= 0 || out_h <= 0 || lo < 0 || lo > hi || hi > 65535) return 1;
+    const Image8 r = Preprocess::resample_normalize_window(src, w, h, lo, hi, out_w, out_h);
+    memcpy(dst, r.data.data(), r.data.size());
+    return 0;
+}
 int medseg_polygon_json_text_groups(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                     const char *base_name, int original_width, int original_height, char *out, int cap)
 {

@@ -142,6 +142,7 @@ public:
         table_["init"] = [this](const Words &w) { cmd_init(w); return true; };
         table_["process"] = [this](const Words &w) { cmd_process(w); return true; };
         table_["targets"] = [this](const Words &w) { cmd_targets(w); return true; };
+        table_["window"] = [this](const Words &w) { cmd_window(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -155,6 +156,7 @@ public:
             "  init <weight_file>            - Initialize the UNet engine",
             "  process [-r] <input> <width> <height> [output_dir] - Process file/directory",
             "  targets <cls:frac,...>|default - Classes to segment, each with its minimum area fraction (e.g. 1:0.01,2:0.06)",
+            "  window percentile <lo_ppm> <hi_ppm>|fixed <lo> <hi>|default - Intensity window of the RAW input (default: min/max)",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -257,6 +259,38 @@ private:
         }
         std::cout << "Targets:";
         for (const MedicalSeg::Target &x : MedicalSeg::get_targets()) std::cout << " " << x.cls << ":" << x.min_area_frac;
+        std::cout << std::endl;
+    }
+
+    // window percentile <lo_ppm> <hi_ppm> | window fixed <lo> <hi> | window default | window (prints the window in force)
+    void cmd_window(const Words &w)
+    {
+        if (w.size() >= 2) {
+            mi_unet_window win{ MI_UNET_WINDOW_MINMAX, 0, 0, 0, 65535 };
+            bool ok = false;
+            if (w[1] == "default" && w.size() == 2) {
+                ok = true;
+            } else if (w[1] == "percentile" && w.size() == 4) {
+                win.mode = MI_UNET_WINDOW_PERCENTILE;
+                ok = to_int(w[2], win.clip_lo_ppm) && to_int(w[3], win.clip_hi_ppm);
+            } else if (w[1] == "fixed" && w.size() == 4) {
+                win.mode = MI_UNET_WINDOW_FIXED;
+                ok = to_int(w[2], win.lo) && to_int(w[3], win.hi);
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid window command (expected percentile <lo_ppm> <hi_ppm>, fixed <lo> <hi> or default)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_window(win)) {
+                std::cerr << "Window unchanged" << std::endl;
+                return;
+            }
+        }
+        const mi_unet_window cur = MedicalSeg::get_window();
+        std::cout << "Window:";
+        if (cur.mode == MI_UNET_WINDOW_PERCENTILE) std::cout << " percentile " << cur.clip_lo_ppm << " " << cur.clip_hi_ppm;
+        else if (cur.mode == MI_UNET_WINDOW_FIXED) std::cout << " fixed " << cur.lo << " " << cur.hi;
+        else std::cout << " minmax";
         std::cout << std::endl;
     }
 

@@ -31,13 +31,14 @@ std::string json_escape(const std::string &s)
     return o;
 }
 
-std::string size_json_text(const std::string &raw_filename, int w, int h, int scaled_w, int scaled_h)
+std::string size_json_text(const std::string &raw_filename, int w, int h, int scaled_w, int scaled_h, const int *lo_hi)
 {
     std::string o = "{\"" + json_escape(raw_filename) + "\":{";
     o += "\"original_height\":" + std::to_string(h);
     o += ",\"original_width\":" + std::to_string(w);
     o += ",\"scaled_height\":" + std::to_string(scaled_h);
     o += ",\"scaled_width\":" + std::to_string(scaled_w);
+    if (lo_hi) o += ",\"window_hi\":" + std::to_string(lo_hi[1]) + ",\"window_lo\":" + std::to_string(lo_hi[0]);
     o += "}}\n";
     return o;
 }

@@ -15,7 +15,8 @@ namespace medseg {
 std::string json_escape(const std::string &s);
 
 // {"<raw filename>":{"original_height":h,"original_width":w,"scaled_height":sh,"scaled_width":sw}}\n  (src/preprocess.cpp:126-134)
-std::string size_json_text(const std::string &raw_filename, int w, int h, int scaled_w, int scaled_h);
+// lo_hi (an intensity window, Preprocess::set_window) appends ,"window_hi":hi,"window_lo":lo -- keys in nlohmann's sorted order
+std::string size_json_text(const std::string &raw_filename, int w, int h, int scaled_w, int scaled_h, const int *lo_hi = nullptr);
 
 // src/mask2polygon.cpp:68-109 with std::setw(4)
 std::string polygon_json_text(const std::vector<Contour> &contours, const std::string &base_name, int original_width,

@@ -152,6 +152,8 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
             up = mi_unet_group_create(&g_cfg, nullptr, 1, &g_group) == MI_UNET_OK &&
                  mi_unet_group_load_weights(g_group, trt_cache_path.c_str()) == MI_UNET_OK;
         }
+        const mi_unet_window window = Preprocess::get_window();            // the window in force outlives the engine
+        if (up && mi_unet_group_set_window(g_group, &window) != MI_UNET_OK) up = false;
         if (!up) {
             g_log_file << "Error: Failed to initialize MI355X UNet engine: " << mi_unet_last_error() << std::endl;
             std::cerr << "Initialization error: " << mi_unet_last_error() << std::endl;
@@ -209,6 +211,26 @@ bool set_targets(const std::vector<Target> &targets)
     return true;
 }
 
+bool set_window(const mi_unet_window &window)
+{
+    std::lock_guard<std::mutex> batch(g_batch_mutex);          // never under a running directory-mode call
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    if (!Preprocess::set_window(window)) {                      // validates; thread contexts pick the setting up on their next use
+        std::cerr << "Error: " << mi_unet_last_error() << std::endl;
+        return false;
+    }
+    if (g_group) (void)mi_unet_group_set_window(g_group, &window);
+    if (g_lane2) (void)mi_unet_group_set_window(g_lane2, &window);
+    if (g_log_file.is_open()) {
+        std::lock_guard<std::mutex> ll(g_log_mutex);
+        g_log_file << "Window: mode " << window.mode << ", clip " << window.clip_lo_ppm << " / " << window.clip_hi_ppm << " ppm, fixed "
+                   << window.lo << " .. " << window.hi << std::endl;
+    }
+    return true;
+}
+
+mi_unet_window get_window() { return Preprocess::get_window(); }
+
 std::vector<Target> get_targets()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -234,11 +256,16 @@ mi_unet_t *get_thread_local_context()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
     if (!g_group) throw std::runtime_error("Engine not initialized");
-    if (t_context.h && t_context.generation == g_generation) return t_context.h;
+    const mi_unet_window window = Preprocess::get_window();
+    if (t_context.h && t_context.generation == g_generation) {
+        (void)mi_unet_set_window(t_context.h, &window);         // (validated when it was set)
+        return t_context.h;
+    }
     t_context.release();
     if (mi_unet_clone(mi_unet_group_handle(g_group, 0), g_thread_batch, &t_context.h) != MI_UNET_OK)
         throw std::runtime_error(std::string("context creation failed: ") + mi_unet_last_error());
     t_context.generation = g_generation;
+    (void)mi_unet_set_window(t_context.h, &window);             // a clone starts at the default
     {
         std::lock_guard<std::mutex> ll(g_log_mutex);
         if (g_log_file.is_open())
@@ -572,7 +599,11 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
                 if (log_file.is_open()) log_file << "Warning: second device lane unavailable (" << mi_unet_last_error() << ")" << std::endl;
                 g_lane2 = nullptr;
             }
-            if (g_lane2) { lanes[1] = g_lane2; n_lanes = 2; }
+            if (g_lane2) {
+                const mi_unet_window window = Preprocess::get_window();       // a clone starts at the default
+                (void)mi_unet_group_set_window(g_lane2, &window);
+                lanes[1] = g_lane2; n_lanes = 2;
+            }
         }
     }
     // a chunk = one micro-batch on every device of the group ... unless the whole call fits into one: then it is cut into four
@@ -880,8 +911,14 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             } else {                                           // a tile size the reference never had: same arithmetic, engine's size
                 try {
                     const std::vector<uint16_t> raw = Preprocess::read_raw16(raw_path, width, height);
-                    pre_ok = Preprocess::write_preprocess_outputs(Preprocess::resample_normalize(raw.data(), width, height, g_cfg.width, g_cfg.height),
-                                                                  raw_path, preprocessed_png_path, size_json_path, width, height);
+                    const mi_unet_window window = Preprocess::get_window();
+                    int win[2] = { 0, 0 };
+                    const bool windowed = window.mode != MI_UNET_WINDOW_MINMAX;
+                    if (windowed && !Preprocess::window_of(raw.data(), raw.size(), window, win[0], win[1])) throw std::runtime_error("window_of failed");
+                    pre_ok = Preprocess::write_preprocess_outputs(
+                        windowed ? Preprocess::resample_normalize_window(raw.data(), width, height, win[0], win[1], g_cfg.width, g_cfg.height)
+                                 : Preprocess::resample_normalize(raw.data(), width, height, g_cfg.width, g_cfg.height),
+                        raw_path, preprocessed_png_path, size_json_path, width, height, windowed ? win : nullptr);
                 } catch (const std::exception &e) {
                     std::cerr << "preprocess_raw error: " << e.what() << '\n';
                     pre_ok = false;

@@ -12,6 +12,7 @@
 #include <filesystem>
 #include <fstream>
 #include <iostream>
+#include <mutex>
 #include <stdexcept>
 
 #include "json_io.h"
@@ -92,6 +93,57 @@ medseg::Image8 resample_normalize(const uint16_t *src, int w, int h, int outW, i
     return dst;
 }
 
+namespace {
+std::mutex g_window_mutex;
+mi_unet_window g_window{ MI_UNET_WINDOW_MINMAX, 0, 0, 0, 65535 };
+}  // namespace
+
+bool window_of(const uint16_t *src, size_t n, const mi_unet_window &win, int &lo, int &hi)
+{
+    return mi_unet_window_of(src, n, &win, &lo, &hi) == MI_UNET_OK;          // pure host arithmetic: one definition for both libraries
+}
+
+bool set_window(const mi_unet_window &win)
+{
+    const uint16_t probe = 0;
+    int lo, hi;
+    if (!window_of(&probe, 1, win, lo, hi)) return false;                    // the engine's own validation
+    std::lock_guard<std::mutex> lk(g_window_mutex);
+    g_window = win;
+    return true;
+}
+
+mi_unet_window get_window()
+{
+    std::lock_guard<std::mutex> lk(g_window_mutex);
+    return g_window;
+}
+
+medseg::Image8 resample_normalize_window(const uint16_t *src, int w, int h, int lo, int hi, int outW, int outH)
+{
+    const int L = lo, Hh = hi > lo ? hi : lo + 1;                            // in int: nothing wraps
+    const double dl = (double)L, dh = (double)Hh, scale8 = 255.0 / (Hh - L);
+    const double stepX = (double)w / outW, stepY = (double)h / outH;
+    medseg::Image8 dst(outH, outW, 1);
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < outH; ++y) {
+        const double fy = y * stepY;
+        const int iy = (int)fy, iy1 = std::min(iy + 1, h - 1);
+        const double dy = fy - iy;
+        const uint16_t *r0 = src + (size_t)iy * w, *r1 = src + (size_t)iy1 * w;
+        uint8_t *o = dst.ptr(y);
+        for (int x = 0; x < outW; ++x) {
+            const double fx = x * stepX;
+            const int ix = (int)fx, ix1 = std::min(ix + 1, w - 1);
+            const double dx = fx - ix;
+            const double v = (1 - dx) * (1 - dy) * r0[ix] + dx * (1 - dy) * r0[ix1] + (1 - dx) * dy * r1[ix] + dx * dy * r1[ix1];
+            const double vc = std::min(std::max(v, dl), dh);
+            o[x] = (uint8_t)(int)((vc - dl) * scale8 + 0.5);
+        }
+    }
+    return dst;
+}
+
 RawView::RawView(const std::string &raw_path, int w, int h)
 {
     if (w <= 0 || h <= 0) throw std::runtime_error("width and height must be positive");
@@ -108,14 +160,25 @@ std::vector<uint16_t> read_raw16(const std::string &raw_path, int w, int h)
 }
 
 bool write_preprocess_outputs(const medseg::Image8 &tile, const std::string &raw_path, const std::string &png_path,
-                              const std::string &json_path, int w, int h)
+                              const std::string &json_path, int w, int h, const int *lo_hi)
 {
     try {
+        int win[2];
+        const mi_unet_window cur = get_window();
+        if (!lo_hi && cur.mode != MI_UNET_WINDOW_MINMAX) {       // the window this image got: the definition, on the file
+            if (cur.mode == MI_UNET_WINDOW_FIXED) {
+                win[0] = cur.lo; win[1] = cur.hi;
+            } else {
+                MappedFile file(raw_path, (size_t)w * h * 2);
+                if (!window_of(file.data(), (size_t)w * h, cur, win[0], win[1])) throw std::runtime_error("window_of failed");
+            }
+            lo_hi = win;
+        }
         const fs::path parent = fs::path(png_path).parent_path();
         if (!parent.empty()) fs::create_directories(parent);
         if (!medseg::write_png(png_path, tile, /*level0=*/true)) throw std::runtime_error("imwrite failed");
         std::ofstream jf(json_path);
-        jf << medseg::size_json_text(fs::path(raw_path).filename().string(), w, h, tile.cols, tile.rows);
+        jf << medseg::size_json_text(fs::path(raw_path).filename().string(), w, h, tile.cols, tile.rows, lo_hi);
         jf.flush();
         return jf.good();
     } catch (const std::exception &e) {
@@ -130,8 +193,13 @@ bool preprocess_raw(const std::string &raw_path, const std::string &png_path, co
         if (w <= 0 || h <= 0) throw std::runtime_error("width and height must be positive");
         const int outW = 512, outH = 512;                        // src/preprocess.cpp:81
         MappedFile file(raw_path, (size_t)w * h * 2);
-        const medseg::Image8 dst8 = resample_normalize(file.data(), w, h, outW, outH);
-        return write_preprocess_outputs(dst8, raw_path, png_path, json_path, w, h);
+        const mi_unet_window cur = get_window();
+        if (cur.mode == MI_UNET_WINDOW_MINMAX)
+            return write_preprocess_outputs(resample_normalize(file.data(), w, h, outW, outH), raw_path, png_path, json_path, w, h);
+        int win[2];
+        if (!window_of(file.data(), (size_t)w * h, cur, win[0], win[1])) throw std::runtime_error("window_of failed");
+        const medseg::Image8 dst8 = resample_normalize_window(file.data(), w, h, win[0], win[1], outW, outH);
+        return write_preprocess_outputs(dst8, raw_path, png_path, json_path, w, h, win);
     } catch (const std::exception &e) {
         std::cerr << "preprocess_raw error: " << e.what() << '\n';
         return false;

@@ -29,6 +29,7 @@ EXPORTS = [
     "mi_unet_target_min_area", "mi_unet_set_targets", "mi_unet_get_targets", "mi_unet_postprocess_masks_multi",
     "mi_unet_segment_raw16_multi", "mi_unet_segment_tiled_raw16_multi", "mi_unet_group_set_targets",
     "mi_unet_group_segment_raw16_multi",
+    "mi_unet_set_window", "mi_unet_get_window", "mi_unet_window_of", "mi_unet_last_windows", "mi_unet_group_set_window",
 ]
 
 
@@ -61,6 +62,20 @@ class TileBlend(C.Structure):
 
 class Target(C.Structure):
     _fields_ = [("cls", C.c_int), ("min_area_frac", C.c_float)]
+
+
+class Window(C.Structure):
+    _fields_ = [("mode", C.c_int), ("clip_lo_ppm", C.c_int), ("clip_hi_ppm", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
+
+
+WINDOW_MODES = {"minmax": 0, "percentile": 1, "fixed": 2}
+
+
+def _window(mode, clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
+    """mode by name (WINDOW_MODES) or as the raw C value, which the library checks; None -> None (restores the default)"""
+    if mode is None:
+        return None
+    return C.byref(Window(WINDOW_MODES[mode] if isinstance(mode, str) else int(mode), int(clip_lo_ppm), int(clip_hi_ppm), int(lo), int(hi)))
 
 
 MAX_TARGETS = 5
@@ -174,6 +189,11 @@ def lib():
         L.mi_unet_segment_tiled_raw16_multi.argtypes = L.mi_unet_segment_tiled_raw16.argtypes
         L.mi_unet_group_set_targets.argtypes = [C.c_void_p, C.POINTER(Target), C.c_int]
         L.mi_unet_group_segment_raw16_multi.argtypes = L.mi_unet_group_segment_raw16.argtypes
+        L.mi_unet_set_window.argtypes = [C.c_void_p, C.POINTER(Window)]
+        L.mi_unet_get_window.argtypes = [C.c_void_p, C.POINTER(Window)]
+        L.mi_unet_window_of.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Window), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi_unet_last_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.mi_unet_group_set_window.argtypes = [C.c_void_p, C.POINTER(Window)]
         _LIB = L
     return _LIB
 
@@ -483,6 +503,27 @@ class Engine:
             return norm, mask, xy, start, counts
         return norm, mask, _decode_multi(xy[None], start[None], counts[None])[0]
 
+    # ---- intensity window (mi_unet_set_window): which sample range of a RAW16 plane becomes 0..255 in every RAW-in call
+    def set_window(self, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
+        """mode "minmax" (default: the exact min / max) | "percentile" (clip_lo_ppm / clip_hi_ppm parts per million of the samples
+        clipped at the dark / bright end) | "fixed" (lo..hi); mode=None restores the default"""
+        _check(lib().mi_unet_set_window(self._h, _window(mode, clip_lo_ppm, clip_hi_ppm, lo, hi)))
+
+    def get_window(self):
+        """-> {"mode": name, "clip_lo_ppm", "clip_hi_ppm", "lo", "hi"}"""
+        w = Window()
+        _check(lib().mi_unet_get_window(self._h, C.byref(w)))
+        return {"mode": {v: k for k, v in WINDOW_MODES.items()}[w.mode], "clip_lo_ppm": w.clip_lo_ppm, "clip_hi_ppm": w.clip_hi_ppm,
+                "lo": w.lo, "hi": w.hi}
+
+    def last_windows(self):
+        """the (lo, hi) the last RAW-in call applied, one row per plane in call order: int32 [planes, 2] (mi_unet_last_windows)"""
+        n = C.c_int()
+        _check(lib().mi_unet_last_windows(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 2), np.int32)
+        _check(lib().mi_unet_last_windows(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -579,6 +620,14 @@ def target_min_area(height: int, width: int, frac: float) -> int:
     return int(lib().mi_unet_target_min_area(height, width, frac))
 
 
+def window_of(samples, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
+    """mi_unet_window_of: the (lo, hi) of these u16 samples under a window setting -- the definition the kernels meet (needs no device)"""
+    a = np.ascontiguousarray(samples, np.uint16).reshape(-1)
+    wlo, whi = C.c_int(), C.c_int()
+    _check(lib().mi_unet_window_of(_ptr(a) if a.size else None, a.size, _window(mode, clip_lo_ppm, clip_hi_ppm, lo, hi), C.byref(wlo), C.byref(whi)))
+    return wlo.value, whi.value
+
+
 def shard_range(n_items: int, rank: int, world: int):
     lo, hi = C.c_int(), C.c_int()
     _check(lib().mi_unet_shard_range(n_items, rank, world, C.byref(lo), C.byref(hi)))
@@ -663,6 +712,10 @@ class Group:
         """Engine.set_targets on every rank"""
         arr, n = _target_array(targets)
         _check(lib().mi_unet_group_set_targets(self._g, arr, n))
+
+    def set_window(self, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
+        """Engine.set_window on every rank"""
+        _check(lib().mi_unet_group_set_window(self._g, _window(mode, clip_lo_ppm, clip_hi_ppm, lo, hi)))
 
     def _n_targets(self):
         n = C.c_int()

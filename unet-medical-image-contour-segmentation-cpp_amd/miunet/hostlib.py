@@ -18,7 +18,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_preprocess_raw", "medseg_resample_normalize", "medseg_postprocess_mask", "medseg_mask_to_image",
            "medseg_extract_contours", "medseg_map_points", "medseg_generate_json", "medseg_draw_overlay", "medseg_process_single_mask",
            "medseg_write_png", "medseg_read_png", "medseg_postprocess_mask_target", "medseg_set_targets", "medseg_get_targets",
-           "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups"]
+           "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
+           "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window"]
 
 
 def lib():
@@ -51,6 +52,11 @@ def lib():
         L.medseg_get_targets.argtypes = [_i, C.POINTER(C.c_float), C.c_int]
         L.medseg_polygon_json_text_groups.argtypes = [_i32, _i32, _i, _i, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
         L.medseg_draw_overlay_groups.argtypes = [_u8, C.c_int, C.c_int, _i32, _i32, _i, _i, C.c_int, _u8]
+        L.medseg_set_window.argtypes = [C.c_int] * 5
+        L.medseg_get_window.argtypes = [_i] * 5
+        L.medseg_get_window.restype = None
+        L.medseg_window_of.argtypes = [_u16, C.c_size_t] + [C.c_int] * 5 + [_i, _i]
+        L.medseg_resample_normalize_window.argtypes = [_u16, C.c_int, C.c_int, C.c_int, C.c_int, _u8, C.c_int, C.c_int]
         _LIB = L
     return _LIB
 
@@ -131,6 +137,42 @@ def get_targets():
     cls, frac = (C.c_int * 8)(), (C.c_float * 8)()
     n = lib().medseg_get_targets(cls, frac, 8)
     return [(cls[i], float(frac[i])) for i in range(n)]
+
+
+WINDOW_MODES = {"minmax": 0, "percentile": 1, "fixed": 2}
+
+
+def _mode(mode):
+    return WINDOW_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def set_window(mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535) -> bool:
+    """MedicalSeg::set_window: mode "minmax" | "percentile" | "fixed" (or the raw C value); needs no engine"""
+    return lib().medseg_set_window(_mode(mode), int(clip_lo_ppm), int(clip_hi_ppm), int(lo), int(hi)) == 0
+
+
+def get_window():
+    v = [C.c_int() for _ in range(5)]
+    lib().medseg_get_window(*[C.byref(x) for x in v])
+    return {"mode": {b: a for a, b in WINDOW_MODES.items()}[v[0].value], "clip_lo_ppm": v[1].value, "clip_hi_ppm": v[2].value,
+            "lo": v[3].value, "hi": v[4].value}
+
+
+def window_of(samples, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
+    """Preprocess::window_of: (lo, hi) of the u16 samples under a window setting"""
+    a = np.ascontiguousarray(samples, np.uint16).reshape(-1)
+    wlo, whi = C.c_int(), C.c_int()
+    if lib().medseg_window_of(a, a.size, _mode(mode), int(clip_lo_ppm), int(clip_hi_ppm), int(lo), int(hi), C.byref(wlo), C.byref(whi)):
+        raise ValueError("window_of: illegal window or no samples")
+    return wlo.value, whi.value
+
+
+def resample_normalize_window(raw, lo, hi, out_w=512, out_h=512):
+    raw = np.ascontiguousarray(raw, np.uint16)
+    out = np.empty((out_h, out_w), np.uint8)
+    if lib().medseg_resample_normalize_window(raw, raw.shape[1], raw.shape[0], int(lo), int(hi), out, out_w, out_h):
+        raise RuntimeError("resample_normalize_window failed")
+    return out
 
 
 def mask_to_image(mask):
