@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../mi_unet.h"
+
 namespace medseg {
 
 struct Point {
@@ -20,6 +22,13 @@ using Contour = std::vector<Point>;
 struct ClassContours {
     int cls = 0;
     std::vector<Contour> contours;
+};
+
+// The measured regions behind groups of contours (MedicalSeg::set_measure): regions[g][c] describes groups[g].contours[c], in tile
+// pixels; scale_x / scale_y are the factors map_contour_points applied to the points of the same document.
+struct RegionTable {
+    std::vector<std::vector<mi_unet_region>> regions;
+    double scale_x = 1.0, scale_y = 1.0;
 };
 
 // Row-major, interleaved channels, 8 bits per sample.

@@ -31,7 +31,7 @@ void process_single_mask(const std::string &mask_path, const std::string &output
 medseg::Image8 draw_overlay(const medseg::Image8 &gray_or_bgr, const std::vector<medseg::Contour> &contours);
 void write_polygon_outputs(const std::vector<medseg::Contour> &contours, const medseg::Image8 &normalized_tile,
                            const std::string &output_dir, const std::string &base_name, int original_width,
-                           int original_height, std::ostream &console = std::cout);
+                           int original_height, std::ostream &console = std::cout, const medseg::RegionTable *regions = nullptr);
 
 // The document generate_json writes, as a string (4-space indent, sorted keys, trailing newline).
 std::string polygon_json_text(const std::vector<medseg::Contour> &contours, const std::string &base_name, int original_width,
@@ -40,8 +40,9 @@ std::string polygon_json_text(const std::vector<medseg::Contour> &contours, cons
 // ---- several target classes (MedicalSeg::set_targets): groups of contours in target order
 // The document with "label": cls and "labelIndex": <index of the group> per shape; a group without contours contributes no shape.
 // A single group of class 2 (the default target list) gives the document above, byte for byte.
+// With `regions` (MedicalSeg::set_measure) every shape also carries a "region" object: host/json_io.h.
 std::string polygon_json_text(const std::vector<medseg::ClassContours> &groups, const std::string &base_name, int original_width,
-                              int original_height);
+                              int original_height, const medseg::RegionTable *regions = nullptr);
 // One overlay with every group's contours: group g in colour g of a fixed palette (B,G,R) -- red (the single-class colour), green,
 // blue, yellow, magenta; later groups are drawn over earlier ones.
 medseg::Image8 draw_overlay(const medseg::Image8 &gray_or_bgr, const std::vector<medseg::ClassContours> &groups);
@@ -49,6 +50,6 @@ medseg::Image8 draw_overlay(const medseg::Image8 &gray_or_bgr, const std::vector
 // group is empty.
 void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const medseg::Image8 &normalized_tile,
                            const std::string &output_dir, const std::string &base_name, int original_width, int original_height,
-                           std::ostream &console = std::cout);
+                           std::ostream &console = std::cout, const medseg::RegionTable *regions = nullptr);
 
 }  // namespace Mask2Polygon

@@ -40,6 +40,16 @@ std::vector<Target> get_targets();
 bool set_window(const mi_unet_window &window);
 mi_unet_window get_window();
 
+// Region measurement (mi_unet_set_measure in include/mi_unet.h).  With it on, the all-device routes of
+// process_single_image and process_image_batch measure every contoured region on the device, and each shape of <base>.json gains a
+// "region" object (host/json_io.h: area, bbox, centroid, edges, major, minor, theta, mean, std, imin, imax in tile pixels, and the
+// scale_x / scale_y that map_contour_points applied); the other artefacts are unchanged byte for byte, and so is every artefact with it
+// off.  A shape list the device did not trace (MEDSEG_HOST_POSTPROCESS / _CONTOURS / _PREPROCESS = 1, or a capacity overflow) carries
+// no region.  Needs no engine; the setting survives initialize_engine and reaches the group, the second lane and every thread's
+// context.  false, setting unchanged: a negative channel, or one the loaded network does not have.
+bool set_measure(bool on, int channel = 0);
+mi_unet_measure get_measure();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

@@ -40,6 +40,16 @@ int medseg_set_window(int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi
 void medseg_get_window(int *mode, int *clip_lo_ppm, int *clip_hi_ppm, int *lo, int *hi);
 int medseg_window_of(const uint16_t *src, size_t n, int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi, int *out_lo, int *out_hi);
 int medseg_resample_normalize_window(const uint16_t *src, int w, int h, int lo, int hi, uint8_t *dst, int out_w, int out_h);
+/* Region measurement: MedicalSeg::set_measure / get_measure (0 on success; the setting is unchanged on failure), and
+ * Mask2Polygon::polygon_json_text for groups with a "region" object per shape: regions holds one mi_unet_region (include/mi_unet.h,
+ * 96 bytes) per contour of the flattened list, in tile pixels; scale_x / scale_y are written into every object.  regions == NULL gives
+ * the bytes of medseg_polygon_json_text_groups.  Returns the length, -1 when cap bytes are too few, -2 for a region that cannot be
+ * derived (area < 1). */
+int medseg_set_measure(int on, int channel);
+void medseg_get_measure(int *on, int *channel);
+int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
+                                     const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
+                                     int original_height, char *out, int cap);
 /* Mask2Polygon::polygon_json_text for groups: group g has class group_cls[g] and the next group_contours[g] contours of the flattened
  * list (xy / start as in medseg_generate_json).  Writes the document (no terminator) into out and returns its length, or -1 when cap
  * bytes are too few. */

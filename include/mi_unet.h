@@ -271,6 +271,61 @@ int mi_unet_get_window(const mi_unet_t *h, mi_unet_window *w);
 int mi_unet_window_of(const uint16_t *samples, size_t n, const mi_unet_window *w, int *lo, int *hi);
 int mi_unet_last_windows(const mi_unet_t *h, int32_t *lo_hi, int cap, int *n);
 
+/* ---- Region measurement: area, moments and intensity of every contoured region, on the device ---------------------
+ * A per-handle setting, off by default; with it off every call does exactly what it did before.
+ * A REGION is an 8-connected component of the contour stage's foreground (mask > 127) that has an external contour.  Components nested
+ * inside a hole of another component get no contour under RETR_EXTERNAL, so they get no region.  Region c of plane p describes exactly
+ * contour c of plane p: the order is the same, and the region's raster-first pixel is the contour's first point.  A plane is an image,
+ * or an (image, target) pair, in the same [B][K] order as the contour outputs.  Coordinates are those of the mask the contour stage saw:
+ * tile coordinates for the RAW forms, full-image coordinates for the tiled forms.
+ * All fields are integers and all are exact.  None of the sums can overflow for any input the tail accepts: planes x H x W < 2^31
+ * gives sxx < 2^62.  (Exactly: sxx < H W^3 / 3, syy < W H^3 / 3 and sxy between them, all below H W max(H, W)^2 / 3, which stays under
+ * 2^62 for every image of up to 2^31 pixels whose longer side is below 80264 pixels.  A measuring call on a mask with
+ * H W max(H, W)^2 >= 3 x 2^62 is refused with MI_UNET_EARG before anything runs.)
+ * With mi_unet_measure.on set, every entry point that returns contours also measures: mi_unet_segment_raw16{,_multi},
+ * mi_unet_segment_tiled_raw16{,_multi} and the group forms.  The measured channel is `channel` of the normalised tile the network read
+ * (tiled forms: of the full-size normalised image); plane b * K + k reads image b.
+ * mi_unet_last_regions serves the LAST such call on the handle: *planes and *cap_contours describe the call (regions and counts may be
+ * NULL to query them); regions is [min(planes, cap_planes)][cap_contours]; counts[p] is the number of external components of plane p, or
+ * -1 when it exceeded cap_contours.  counts[p] does not depend on cap_points: a plane whose points overflowed still has valid regions.
+ * Entries at c >= counts[p], and every entry of a -1 plane, are all-zero.  MI_UNET_ESTATE when the last contour-returning call did not
+ * measure, or when there was none.  mi_unet_set_measure: MI_UNET_EARG, setting unchanged, for a channel outside 0 .. in_ch - 1; NULL
+ * restores the default { 0, 0 }; a clone starts at the default.
+ * mi_unet_measure_regions is the stage alone, the counterpart of mi_unet_extract_contours with the same preconditions, on host buffers:
+ * masks u8 [B][H][W], tiles u8 [B][H][W][in_ch] or NULL, regions [B][cap_contours] out, counts [B] out.  With tiles == NULL:
+ * imin = imax = 0, si = sii = 0, channel = -1.  It does not change what mi_unet_last_regions reports.
+ * mi_unet_region_derive is pure host arithmetic (needs no device); MI_UNET_EARG for area < 1 or a null pointer.  With A = area:
+ *   cx = sx / A and cy = sy / A.
+ *   The central second moments have exact 128-bit integer numerators that are converted once: m20 = (A*sxx - sx^2) / A^2, m02 likewise,
+ *   m11 = (A*sxy - sx*sy) / A^2.
+ *   a = m20 + 1/12, c = m02 + 1/12 (a pixel is a unit square), b = m11.
+ *   lambda+- = ((a + c) +- sqrt((a - c)^2 + 4 b^2)) / 2.
+ *   major = 4 sqrt(lambda+) and minor = 4 sqrt(lambda-): the axes of the ellipse with the same second moments.  One pixel gives 1.1547
+ *   for both.
+ *   theta = 0.5 atan2(2 b, a - c): the angle of the major axis from +x, with y pointing down.
+ *   mean = si / A and std = sqrt((A*sii - si^2) / A^2).
+ * The time of the measurement counts under MI_UNET_STAGE_CONTOURS. */
+typedef struct mi_unet_region {      /* 96 bytes, no padding */
+    int32_t area;                    /* pixels of the component; holes are not counted */
+    int32_t x0, y0, x1, y1;          /* bounding box, inclusive */
+    int32_t imin, imax;              /* min / max of the measured channel of the normalised tile over the component */
+    int32_t channel;                 /* the channel measured (echo of the setting; -1 when no tile was given) */
+    int64_t edges;                   /* crack perimeter: pixel edges between a component pixel and a 4-neighbour that is
+                                        not foreground; the image frame counts as not foreground; hole borders count */
+    int64_t sx, sy;                  /* sum of x, sum of y over the component */
+    int64_t sxx, syy, sxy;           /* sum of x*x, y*y, x*y */
+    int64_t si, sii;                 /* sum of v, sum of v*v, with v = the tile byte of the measured channel */
+} mi_unet_region;
+typedef struct mi_unet_measure { int on; int channel; } mi_unet_measure;   /* default {0, 0}; channel in 0 .. in_ch-1 */
+typedef struct mi_unet_region_shape { double cx, cy, mean, std, major, minor, theta; } mi_unet_region_shape;
+int mi_unet_set_measure(mi_unet_t *h, const mi_unet_measure *m);           /* NULL restores the default; a clone starts at it */
+int mi_unet_get_measure(const mi_unet_t *h, mi_unet_measure *m);
+int mi_unet_last_regions(const mi_unet_t *h, mi_unet_region *regions, int32_t *counts, int cap_planes,
+                         int *planes, int *cap_contours);
+int mi_unet_measure_regions(mi_unet_t *h, const uint8_t *masks, const uint8_t *tiles /* [B][H][W][in_ch] or NULL */,
+                            int B, int channel, mi_unet_region *regions, int cap_contours, int32_t *counts);
+int mi_unet_region_derive(const mi_unet_region *r, mi_unet_region_shape *out);   /* EARG for area < 1 or NULL */
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only
@@ -425,6 +480,11 @@ int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const 
                                       int32_t *counts);
 /* mi_unet_set_window on every rank (all or none); the sharded RAW-in calls above then apply it */
 int mi_unet_group_set_window(mi_unet_group_t *g, const mi_unet_window *w);
+/* mi_unet_set_measure on every rank (all or none); mi_unet_last_regions of the last sharded segment call: same arguments, the planes in
+ * image order, assembled from the ranks' shard ranges */
+int mi_unet_group_set_measure(mi_unet_group_t *g, const mi_unet_measure *m);
+int mi_unet_group_last_regions(const mi_unet_group_t *g, mi_unet_region *regions, int32_t *counts, int cap_planes, int *planes,
+                               int *cap_contours);
 void mi_unet_group_destroy(mi_unet_group_t *g);
 /* The split itself (pure host arithmetic, needs no device): rank's range [*lo, *hi) of n_items over `world` ranks. */
 int mi_unet_shard_range(int n_items, int rank, int world, int *lo, int *hi);

@@ -162,7 +162,7 @@ static int device_postprocess(mi_unet *h, uint8_t *d_labels, int B)
 }
 
 int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const TargetTable &t, uint8_t *d_planes, void *ws,
-                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where)
+                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where, const MeasureArgs *m)
 {
     hipError_t e = t.K > 0 ? launch_postprocess_masks_multi(d_labels, d_planes, B, H, W, t, ws, s) : hipSuccess;
     if (e != hipSuccess) return fail(MI_UNET_EHIP, where + "postprocess launch: " + hipGetErrorString(e));
@@ -174,6 +174,14 @@ int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const
         e = launch_extract_contours(d_planes, cl->planes, H, W, cl->xy(d_cont), cl->cap_points, cl->start(d_cont), cl->cap_contours,
                                     cl->count(d_cont), ws, s);
     if (e != hipSuccess) return fail(MI_UNET_EHIP, where + "segment launch: " + hipGetErrorString(e));
+    if (m) {                                             // the measuring half, on the forest and the sorted roots the contours came from
+        const RegionLayout rl{ cl->planes, cl->cap_contours };
+        uint8_t *const d_reg = h->d_regions;
+        e = launch_measure_regions(cl->planes, H, W, t.K, m->d_tiles, h->cfg.in_ch, h->measure.channel, rl.regions(d_reg), rl.counts(d_reg),
+                                   cl->cap_contours, ws, s);
+        if (e != hipSuccess) return fail(MI_UNET_EHIP, where + "region launch: " + hipGetErrorString(e));
+        HIP_TRY(hipMemcpyAsync(h->h_regions[m->half], d_reg, rl.bytes(), hipMemcpyDeviceToHost, s));
+    }
     return 0;
 }
 

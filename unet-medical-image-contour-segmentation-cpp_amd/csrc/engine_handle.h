@@ -122,6 +122,17 @@ struct mi_unet {
     miunet::DeviceBuf<int> d_cont;          // contour outputs of mi_unet_extract_contours (grown on demand)
     miunet::PinnedBuf<int> h_cont;          // pinned mirror: one async D2H, then only the points that exist are copied to the caller
     size_t cont_cap = 0;            // ints
+    // mi_unet_set_measure.  d_regions = the accumulators and the output of one micro-batch, [planes][cap] structs and
+    // behind them [planes] counts; h_regions = its pinned mirrors, one per parity of the RAW pipeline; grown on demand
+    // (grow_region_buffers).  last_regions / last_region_counts: the report of the last contour-returning call, all its planes.
+    mi_unet_measure measure{ 0, 0 };
+    miunet::DeviceBuf<uint8_t> d_regions;
+    miunet::PinnedBuf<uint8_t> h_regions[2];
+    size_t regions_cap = 0;         // bytes of each of the three
+    std::vector<mi_unet_region> last_regions;
+    std::vector<int32_t> last_region_counts;
+    int last_region_planes = 0, last_region_cap = 0;
+    bool last_regions_valid = false;
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;
@@ -238,8 +249,29 @@ void contours_to_caller(const mi_unet *h, const ContourLayout &cl, int32_t *xy, 
 // into h->d_cont.  `ws` holds both stages' workspaces for B * t.K planes (checked by the caller); `between` (or null) is recorded
 // behind the postprocess, the boundary of the two stage times; `where` prefixes the message of a failed launch.  An empty table
 // (t.K == 0, no cl) enqueues nothing but `between`.
+// With `m` (the handle measures, cl given): the regions of the cl->planes masks behind the contours, from m->d_tiles (the u8
+// [B][H][W][in_ch] the planes' images were read from), into h->d_regions and on into the pinned mirror m->half, all on `s`.
+struct MeasureArgs { const uint8_t *d_tiles; int half; };
 int enqueue_tail(mi_unet *h, const uint8_t *d_labels, int B, int H, int W, const TargetTable &t, uint8_t *d_planes, void *ws,
-                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where = std::string());
+                 const ContourLayout *cl, hipEvent_t between, hipStream_t s, const std::string &where = std::string(),
+                 const MeasureArgs *m = nullptr);
+// ---- measure.cpp: region measurement (mi_unet_set_measure)
+// The region arrays of `planes` masks as one run of bytes: [planes][cap] structs, then [planes] counts.
+struct RegionLayout {
+    int planes, cap;
+    size_t bytes() const { return (size_t)planes * cap * sizeof(mi_unet_region) + (size_t)planes * sizeof(int32_t); }
+    mi_unet_region *regions(uint8_t *base) const { return reinterpret_cast<mi_unet_region *>(base); }
+    const mi_unet_region *regions(const uint8_t *base) const { return reinterpret_cast<const mi_unet_region *>(base); }
+    int32_t *counts(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + (size_t)planes * cap * sizeof(mi_unet_region)); }
+    const int32_t *counts(const uint8_t *base) const { return reinterpret_cast<const int32_t *>(base + (size_t)planes * cap * sizeof(mi_unet_region)); }
+};
+int check_measure_size(int H, int W, const std::string &fn);   // MI_UNET_EARG where a moment sum could pass 2^62 (include/mi_unet.h)
+int grow_region_buffers(mi_unet *h, const RegionLayout &rl);   // nothing may be in flight on them
+// a contour-returning call begins: the report is invalid until the call has completed; measuring: room for `planes` planes
+void begin_region_call(mi_unet *h, bool measuring, int planes, int cap);
+// mirror `half` holds the planes [plane0, plane0 + rl.planes) of the running call (after the synchronise)
+void regions_to_report(mi_unet *h, const RegionLayout &rl, int plane0, int half);
+void finish_region_call(mi_unet *h);                           // the call has completed: the report is valid
 // ---- window.cpp: the intensity window of the RAW-in entry points
 constexpr mi_unet_window kDefaultWindow{ MI_UNET_WINDOW_MINMAX, 0, 0, 0, 65535 };
 int check_window(const mi_unet_window &w, const char *fn);   // MI_UNET_EARG + message for a setting mi_unet_set_window refuses

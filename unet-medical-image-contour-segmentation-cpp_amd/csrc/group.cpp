@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -84,7 +85,9 @@ struct mi_unet_group {
     std::vector<size_t> cap_in, cap_out;
     uint8_t *h_all = nullptr;                 // pinned: rank 0's D2H target
     size_t cap_all = 0;
-    std::mutex call_mutex;                    // one group call at a time
+    // the last sharded segment call: B images of K planes each; < 0 = none yet, or it failed (mi_unet_group_last_regions)
+    int seg_B = -1, seg_K = 0;
+    mutable std::mutex call_mutex;            // one group call at a time
 };
 
 namespace {
@@ -399,7 +402,8 @@ static int group_segment_raw16(mi_unet_group_t *g, const char *fn, bool multi, c
     if (multi)
         if (int rc = mi_unet_get_targets(g->eng[0], nullptr, 0, &n_targets)) return rc;
     const size_t K = (size_t)n_targets;
-    return for_all_ranks(g, [&](int r) {
+    g->seg_B = -1;
+    const int rc = for_all_ranks(g, [&](int r) {
         int lo, hi;
         shard_range(B, r, R, lo, hi);
         if (hi == lo) return 0;
@@ -407,6 +411,8 @@ static int group_segment_raw16(mi_unet_group_t *g, const char *fn, bool multi, c
             g->eng[r], raws + (size_t)lo * C, widths + (size_t)lo * C, heights + (size_t)lo * C, hi - lo, tiles ? tiles + lo * hw * C : nullptr,
             masks + lo * K * hw, xy + lo * K * cap_points * 2, cap_points, start + lo * K * (cap_contours + 1), cap_contours, counts + lo * K);
     });
+    if (rc == MI_UNET_OK) { g->seg_B = B; g->seg_K = n_targets; }
+    return rc;
 }
 
 int mi_unet_group_segment_raw16(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
@@ -434,6 +440,44 @@ int mi_unet_group_set_window(mi_unet_group_t *g, const mi_unet_window *w)
     // the verdict does not depend on the rank: the first rank's is everybody's, so all ranks change or none does
     for (mi_unet_t *h : g->eng)
         if (int rc = mi_unet_set_window(h, w)) return rc;
+    return MI_UNET_OK;
+}
+
+int mi_unet_group_set_measure(mi_unet_group_t *g, const mi_unet_measure *m)
+{
+    if (!g) return engine_fail(MI_UNET_EARG, "null group");
+    std::lock_guard<std::mutex> lk(g->call_mutex);       // never while a group call is in flight
+    // the verdict does not depend on the rank: the first rank's is everybody's, so all ranks change or none does
+    for (mi_unet_t *h : g->eng)
+        if (int rc = mi_unet_set_measure(h, m)) return rc;
+    return MI_UNET_OK;
+}
+
+// every rank reports the planes of its own shard; rank r's shard of the last call is [lo, hi) images = [lo * K, hi * K) planes
+int mi_unet_group_last_regions(const mi_unet_group_t *g, mi_unet_region *regions, int32_t *counts, int cap_planes, int *planes,
+                               int *cap_contours)
+{
+    if (!g || !planes || !cap_contours || cap_planes < 0) return engine_fail(MI_UNET_EARG, "mi_unet_group_last_regions: bad argument");
+    std::lock_guard<std::mutex> lk(g->call_mutex);
+    if (g->seg_B < 1) return engine_fail(MI_UNET_ESTATE, "mi_unet_group_last_regions: no sharded segment call has completed on this group");
+    const int R = (int)g->eng.size(), K = g->seg_K;
+    int cap = 0;
+    for (int r = 0; r < R; ++r) {
+        int lo, hi;
+        shard_range(g->seg_B, r, R, lo, hi);
+        if (hi == lo) continue;
+        int pl = 0, cc = 0;
+        if (int rc = mi_unet_last_regions(g->eng[r], nullptr, nullptr, 0, &pl, &cc)) return rc;      // ESTATE: the call did not measure
+        if (pl != (hi - lo) * K || (cap && cc != cap))
+            return engine_fail(MI_UNET_ESTATE, "mi_unet_group_last_regions: rank " + std::to_string(r) + " holds the report of another call");
+        cap = cc;
+        const int room = std::min(std::max(cap_planes - lo * K, 0), pl);
+        if (int rc = mi_unet_last_regions(g->eng[r], regions ? regions + (size_t)lo * K * cap : nullptr, counts ? counts + (size_t)lo * K : nullptr,
+                                          room, &pl, &cc))
+            return rc;
+    }
+    *planes = g->seg_B * K;
+    *cap_contours = cap;
     return MI_UNET_OK;
 }
 

@@ -1,5 +1,6 @@
 // image_stages.hip -- the reference's CPU-side image stages on the device: RAW16 preprocessing (f1), postprocess_mask
 // (f2), mask_to_image + extract_contours (f3).  Integer / byte / fp64 work, bit-exact against the oracle.  gfx950 only.
+#include "cc_common.h"
 #include "kernel_common.h"
 
 namespace miunet {
@@ -250,42 +251,6 @@ hipError_t launch_window_select_u16(const uint16_t *raw, size_t n, int clip_lo_p
 // the point is to keep the label maps on the device and to replace the reference's O(components x H x W) loops
 // (src/postprocess.cpp:41, :71) by one union-find labelling.
 namespace pp {
-
-__device__ __forceinline__ int ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x with path halving: every store writes an ancestor of the node, so racing finds / unions stay consistent
-__device__ __forceinline__ int find_root(int *parent, int x)
-{
-    int p = ld(parent + x);
-    while (p != x) {
-        const int g = ld(parent + p);
-        if (g != p) st(parent + x, g);
-        x = p; p = g;
-    }
-    return x;
-}
-
-// read-only walk for the flatten pass: there every store must be the final root, so no halving stores may race with it
-__device__ __forceinline__ int find_root_ro(const int *parent, int x)
-{
-    for (int p = ld(parent + x); p != x; p = ld(parent + x)) x = p;
-    return x;
-}
-
-// parents only ever decrease, roots satisfy parent[r] == r; atomicMin at L2 makes concurrent unions safe
-__device__ __forceinline__ void unite(int *parent, int a, int b)
-{
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }          // a > b: hang a under b
-        const int old = atomicMin(parent + a, b);
-        if (old == a) return;
-        a = old;                                                // somebody re-parented a meanwhile: retry from there
-    }
-}
 
 // fg[i] != 0 marks foreground.  parent = first pixel of the horizontal run inside the lane's 64-pixel segment (so the
 // forest starts with chains no longer than W/64 per row instead of one node per pixel), -1 for background; stats cleared.
@@ -762,28 +727,37 @@ size_t contour_workspace_bytes(int B, int H, int W, int cap_contours)
     return n * (7 * sizeof(int) + 2) + sizeof(int) * ((size_t)B * (2 * cap_contours + 1) + 64);
 }
 
-hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, int *out_xy, int cap_points, int *out_start,
-                                   int cap_contours, int *out_count, void *ws, hipStream_t s)
+// The labelling half: threshold, both forests, the external roots of every plane collected and sorted (contour order).  Shared by the
+// contour trace below and the region measurement (regions.hip).
+hipError_t launch_label_contours(const uint8_t *masks, int B, int H, int W, int cap_contours, void *ws, hipStream_t s)
+{
+    const long long n = (long long)B * H * W;
+    if (n <= 0 || n > 0x7FFFFFFFLL || cap_contours <= 0) return hipErrorInvalidValue;
+    const ContourWs w = contour_ws(ws, n, B, cap_contours);
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    hipLaunchKernelGGL(ct::k_threshold, g, b, 0, s, masks, w.fg, w.bg, n);
+    // foreground labelling (8-connected): only its roots are asked for (no statistics pass, no flattening)
+    hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, w.fg, w.fparent, w.flag, w.slot, w.miny, w.maxx, w.maxy, W, n);
+    hipLaunchKernelGGL(pp::cc_merge, g, b, 0, s, w.fg, w.fparent, H, W, n);
+    // background labelling (4-connected); `flag` (zeroed by cc_init) becomes the reaches-the-frame flag of its roots
+    hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, w.bg, w.bparent, w.flag, w.slot, w.miny, w.maxx, w.maxy, W, n);
+    hipLaunchKernelGGL(ct::cc_merge4, g, b, 0, s, w.bg, w.bparent, H, W, n);
+    hipLaunchKernelGGL(ct::k_frame_flags, dim3((unsigned)((B * 2 * (H + W) + 255) / 256)), b, 0, s, w.bparent, w.flag, H, W, B);
+    hipLaunchKernelGGL(ct::k_zero_counts, dim3((B + 255) / 256), b, 0, s, w.counts, B);
+    hipLaunchKernelGGL(ct::k_collect, g, b, 0, s, w.fparent, w.bparent, w.flag, w.roots, w.counts, cap_contours, H, W, n);
+    hipLaunchKernelGGL(ct::k_sort_roots, dim3((B + 63) / 64), dim3(64), 0, s, w.roots, w.counts, cap_contours, B);
+    return hipGetLastError();
+}
+
+// The tracing half, behind launch_label_contours on the same workspace.
+hipError_t launch_trace_contours(int B, int H, int W, int *out_xy, int cap_points, int *out_start, int cap_contours, int *out_count,
+                                 void *ws, hipStream_t s)
 {
     const long long n = (long long)B * H * W;
     if (n <= 0 || n > 0x7FFFFFFFLL || cap_contours <= 0 || cap_points <= 0) return hipErrorInvalidValue;
-    int *fparent = static_cast<int *>(ws), *bparent = fparent + n, *area = bparent + n, *minx = area + n, *miny = minx + n,
-        *maxx = miny + n, *maxy = maxx + n;
-    uint8_t *fg = reinterpret_cast<uint8_t *>(maxy + n), *bg = fg + n;
-    int *roots = reinterpret_cast<int *>(bg + n + ((16 - (2 * n) % 16) % 16));
-    int *npts = roots + (size_t)B * cap_contours, *counts = npts + (size_t)B * cap_contours;
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    hipLaunchKernelGGL(ct::k_threshold, g, b, 0, s, masks, fg, bg, n);
-    // foreground labelling (8-connected): only its roots are asked for (no statistics pass, no flattening)
-    hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, fg, fparent, area, minx, miny, maxx, maxy, W, n);
-    hipLaunchKernelGGL(pp::cc_merge, g, b, 0, s, fg, fparent, H, W, n);
-    // background labelling (4-connected); `area` (zeroed by cc_init) becomes the reaches-the-frame flag of its roots
-    hipLaunchKernelGGL(pp::cc_init, g, b, 0, s, bg, bparent, area, minx, miny, maxx, maxy, W, n);
-    hipLaunchKernelGGL(ct::cc_merge4, g, b, 0, s, bg, bparent, H, W, n);
-    hipLaunchKernelGGL(ct::k_frame_flags, dim3((unsigned)((B * 2 * (H + W) + 255) / 256)), b, 0, s, bparent, area, H, W, B);
-    hipLaunchKernelGGL(ct::k_zero_counts, dim3((B + 255) / 256), b, 0, s, counts, B);
-    hipLaunchKernelGGL(ct::k_collect, g, b, 0, s, fparent, bparent, area, roots, counts, cap_contours, H, W, n);
-    hipLaunchKernelGGL(ct::k_sort_roots, dim3((B + 63) / 64), dim3(64), 0, s, roots, counts, cap_contours, B);
+    const ContourWs w = contour_ws(ws, n, B, cap_contours);
+    const uint8_t *fg = w.fg;
+    int *roots = w.roots, *npts = w.npts, *counts = w.counts;
     // one workgroup per image; the mask as an LDS bit plane when it fits
     const size_t plane = (((size_t)H * W + 31) / 32) * 4 + 4;    // + one word of slack behind the plane (k_trace's windows)
     const bool in_lds = plane <= 160 * 1024;                     // the whole LDS of a CU: 1024x1024 is 128 KB + 4
@@ -804,6 +778,14 @@ hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, in
             hipLaunchKernelGGL(ct::k_offsets, dim3((B + 63) / 64), dim3(64), 0, s, npts, counts, cap_contours, cap_points, B, out_start, out_count);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, int *out_xy, int cap_points, int *out_start,
+                                   int cap_contours, int *out_count, void *ws, hipStream_t s)
+{
+    if (cap_points <= 0) return hipErrorInvalidValue;
+    if (hipError_t e = launch_label_contours(masks, B, H, W, cap_contours, ws, s); e != hipSuccess) return e;
+    return launch_trace_contours(B, H, W, out_xy, cap_points, out_start, cap_contours, out_count, ws, s);
 }
 
 

@@ -1,8 +1,10 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, regions.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+struct mi_unet_region;      // include/mi_unet.h
 
 namespace miunet {
 
@@ -237,5 +239,19 @@ hipError_t launch_mask_to_image_binary(const uint8_t *masks, uint8_t *vis, size_
 size_t contour_workspace_bytes(int B, int H, int W, int cap_contours);
 hipError_t launch_extract_contours(const uint8_t *masks, int B, int H, int W, int *out_xy, int cap_points, int *out_start,
                                    int cap_contours, int *out_count, void *ws, hipStream_t s);
+
+// The two halves of launch_extract_contours on one workspace: labelling (threshold, both forests, the sorted external roots and their
+// number per plane) and the trace.  The labelling half alone serves the region measurement below.
+hipError_t launch_label_contours(const uint8_t *masks, int B, int H, int W, int cap_contours, void *ws, hipStream_t s);
+hipError_t launch_trace_contours(int B, int H, int W, int *out_xy, int cap_points, int *out_start, int cap_contours, int *out_count,
+                                 void *ws, hipStream_t s);
+
+// Region measurement (regions.hip; include/mi_unet.h: mi_unet_set_measure), behind launch_label_contours on the same
+// workspace (the trace may run before, between or after: neither touches what the other reads or writes).
+//   planes masks of H x W were labelled; plane p belongs to image p / K.  tiles u8 [planes / K][H][W][in_ch] or null, `channel` of
+//   it is measured.  regions [planes][cap_contours] out: entry c describes contour c of the plane; zero behind the plane's count and
+//   for a plane with more than cap_contours external components.  rcounts [planes] out: that number, or -1.  No workspace of its own.
+hipError_t launch_measure_regions(int planes, int H, int W, int K, const uint8_t *tiles, int in_ch, int channel,
+                                  ::mi_unet_region *regions, int *rcounts, int cap_contours, void *ws, hipStream_t s);
 
 }  // namespace miunet

@@ -139,6 +139,10 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     const bool segment = c.targets.K > 0;
     const TargetTable tab = segment ? c.targets : h->postprocess ? default_targets(H, W) : TargetTable{};
     const int K = segment ? tab.K : 1;
+    // mi_unet_set_measure: the tail of every micro-batch also measures its regions, from the tile buffer the network read
+    const bool measuring = segment && h->measure.on;
+    if (measuring)
+        if (int rc = check_measure_size(H, W, "RAW16 input")) return rc;
     // every image description is checked BEFORE anything is enqueued: a bad width in image k + 1 must not be found after the
     // network of micro-batch k has started
     unsigned long long max_samples = 0;
@@ -191,6 +195,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         const int bm = mbs[k].bm, par = k & 1;
         const size_t b0 = (size_t)mbs[k].b0;
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(h->pre_stream, c.tiles ? h->tiles_done[par].get() : h->net_done[par].get(), 0));   // its last readers: network and tile download of k - 2
+        if (k >= 2 && measuring) HIP_TRY(hipStreamWaitEvent(h->pre_stream, h->out_done[par], 0));   // ... and, measuring, the tail of k - 2
         HIP_TRY(hipEventRecord(h->pre_ev[k % 3][0], h->pre_stream));
         if (int rc = stage_raw16(h, c.raws + b0 * C, c.widths + b0 * C, c.heights + b0 * C, bm, b0 * C, h->pre_stream, tile_buf(k))) return rc;
         HIP_TRY(hipEventRecord(h->pre_ev[k % 3][1], h->pre_stream));
@@ -226,7 +231,10 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         Event *tv = h->tail_ev[par];
         HIP_TRY(hipEventRecord(tv[0], ts));
         uint8_t *d_result = segment ? h->d_multi.get() : d_lab;
-        if (int rc = enqueue_tail(h, d_lab, bm, H, W, tab, d_result, h->d_tail_ws, segment ? &cl : nullptr, tv[1], ts)) return rc;
+        const MeasureArgs ma{ d_tiles, par };
+        if (int rc = enqueue_tail(h, d_lab, bm, H, W, tab, d_result, h->d_tail_ws, segment ? &cl : nullptr, tv[1], ts, std::string(),
+                                  measuring ? &ma : nullptr))
+            return rc;
         HIP_TRY(hipEventRecord(tv[2], ts));
         HIP_TRY(hipMemcpyAsync(out_buf(k), d_result, bm * K * hw, hipMemcpyDeviceToHost, ts));
         if (segment)
@@ -249,6 +257,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         if (segment)
             contours_to_caller(h, ContourLayout{ bm * K, c.cap_points, c.cap_contours }, c.xy + b0 * K * c.cap_points * 2,
                                c.start + b0 * K * (c.cap_contours + 1), c.counts + b0 * K, par);
+        if (measuring) regions_to_report(h, RegionLayout{ bm * K, c.cap_contours }, (int)b0 * K, par);
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->pre_ev[k % 3][0], h->pre_ev[k % 3][1]));
         h->stage_ms[MI_UNET_STAGE_UPLOAD_PRE] += ms;
@@ -272,6 +281,10 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         size_t need = postprocess_workspace_bytes(bmax * K, H, W);
         if (segment) {
             if (int rc = grow_contour_buffers(h, ContourLayout{ bmax * K, c.cap_points, c.cap_contours })) return rc;
+            // (nothing of an earlier call is in flight: every RAW-in call drains its streams before it returns)
+            if (measuring)
+                if (int rc = grow_region_buffers(h, RegionLayout{ bmax * K, c.cap_contours })) return rc;
+            begin_region_call(h, measuring, c.B * K, c.cap_contours);
             need = std::max(need, contour_workspace_bytes(bmax * K, H, W, c.cap_contours));
         }
         if (int rc = ensure_tail_buffers(h, need, segment ? (size_t)bmax * K * hw : 0)) return rc;
@@ -310,6 +323,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         return fail(rc, keep);
     }
     finish_window_call(h, (size_t)c.B * C);
+    if (segment) finish_region_call(h);
     mark("done", 0);
     return MI_UNET_OK;
 }

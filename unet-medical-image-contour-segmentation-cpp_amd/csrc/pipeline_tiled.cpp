@@ -135,6 +135,8 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
                                       std::to_string(contour_workspace_bytes(K, H, W, c.cap_contours)) + " bytes) exceeds the scratch buffer (" +
                                       std::to_string(scratch) + " bytes)");
     if ((long long)K * H * W > 0x7FFFFFFFLL) return fail(MI_UNET_EARG, fn + ": targets x pixels exceeds 2^31 - 1");
+    if (segment && h->measure.on)
+        if (int rc = check_measure_size(H, W, fn)) return rc;
     // blending or mirror averaging (mi_unet_set_tile_blend): nv views per tile, view k = t * nv + v, the network's logits
     // accumulated into t.d_acc, which also returns the blended logits; otherwise the ownership stitch
     const mi_unet_tile_blend bl = h->blend;
@@ -246,7 +248,18 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     // ---- the tail, on the stitched image: one image of H x W, never per tile
     uint8_t *const d_result = segment ? t.d_multi.get() : t.d_labels.get(), *const h_result = segment ? t.h_multi.get() : t.h_out.get();
     const hipEvent_t post_done = t.ev[mark++];
-    if (int rc = enqueue_tail(h, t.d_labels, 1, H, W, tab, d_result, h->d_s1, segment ? &cl : nullptr, post_done, s, fn + ": ")) return rc;
+    // mi_unet_set_measure: intensity from the full-size normalised image, coordinates of the stitched mask; K planes over one image
+    const bool measuring = segment && h->measure.on;
+    const RegionLayout rl{ K, c.cap_contours };
+    if (segment) {
+        if (measuring)
+            if (int rc = grow_region_buffers(h, rl)) return rc;     // (s was synchronised by the call before this one)
+        begin_region_call(h, measuring, K, c.cap_contours);
+    }
+    const MeasureArgs ma{ t.d_img, 0 };
+    if (int rc = enqueue_tail(h, t.d_labels, 1, H, W, tab, d_result, h->d_s1, segment ? &cl : nullptr, post_done, s, fn + ": ",
+                              measuring ? &ma : nullptr))
+        return rc;
     HIP_TRY(hipEventRecord(t.ev[mark++], s));
     HIP_TRY(hipMemcpyAsync(h_result, d_result, K * npix, hipMemcpyDeviceToHost, s));
     if (c.norm) HIP_TRY(hipMemcpyAsync(t.h_img, t.d_img, npix * C, hipMemcpyDeviceToHost, s));
@@ -260,6 +273,8 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     host_copy(h, c.out_u8, h_result, K * npix);
     if (c.norm) host_copy(h, c.norm, t.h_img, npix * C);
     if (segment) contours_to_caller(h, cl, c.xy, c.start, c.count);
+    if (measuring) regions_to_report(h, rl, 0, 0);
+    if (segment) finish_region_call(h);
     if (c.planes) finish_window_call(h, (size_t)C);
 
     for (float &m : h->stage_ms) m = 0.f;

@@ -139,6 +139,31 @@ int medseg_polygon_json_text_groups(const int32_t *xy, const int32_t *start, con
     memcpy(out, s.data(), s.size());
     return (int)s.size();
 }
+int medseg_set_measure(int on, int channel) { return MedicalSeg::set_measure(on != 0, channel) ? 0 : 1; }
+void medseg_get_measure(int *on, int *channel)
+{
+    const mi_unet_measure m = MedicalSeg::get_measure();
+    *on = m.on; *channel = m.channel;
+}
+int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
+                                     const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
+                                     int original_height, char *out, int cap)
+{
+    try {
+        const std::vector<medseg::ClassContours> gs = ungroup(xy, start, group_cls, group_contours, ngroups);
+        medseg::RegionTable table;
+        table.scale_x = scale_x; table.scale_y = scale_y;
+        const mi_unet_region *r = static_cast<const mi_unet_region *>(regions);
+        for (const auto &g : gs) {
+            table.regions.emplace_back(r ? r : nullptr, r ? r + g.contours.size() : nullptr);
+            if (r) r += g.contours.size();
+        }
+        const std::string s = Mask2Polygon::polygon_json_text(gs, base_name, original_width, original_height, regions ? &table : nullptr);
+        if ((int)s.size() > cap) return -1;
+        memcpy(out, s.data(), s.size());
+        return (int)s.size();
+    } catch (...) { return -2; }
+}
 int medseg_draw_overlay_groups(const uint8_t *gray, int w, int h, const int32_t *xy, const int32_t *start, const int *group_cls,
                                const int *group_contours, int ngroups, uint8_t *bgr_out)
 {

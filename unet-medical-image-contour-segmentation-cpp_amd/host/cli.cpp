@@ -143,6 +143,7 @@ public:
         table_["process"] = [this](const Words &w) { cmd_process(w); return true; };
         table_["targets"] = [this](const Words &w) { cmd_targets(w); return true; };
         table_["window"] = [this](const Words &w) { cmd_window(w); return true; };
+        table_["measure"] = [this](const Words &w) { cmd_measure(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -157,6 +158,7 @@ public:
             "  process [-r] <input> <width> <height> [output_dir] - Process file/directory",
             "  targets <cls:frac,...>|default - Classes to segment, each with its minimum area fraction (e.g. 1:0.01,2:0.06)",
             "  window percentile <lo_ppm> <hi_ppm>|fixed <lo> <hi>|default - Intensity window of the RAW input (default: min/max)",
+            "  measure on [channel]|off      - Measure every contoured region on the device (a \"region\" object per shape of the JSON)",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -292,6 +294,26 @@ private:
         else if (cur.mode == MI_UNET_WINDOW_FIXED) std::cout << " fixed " << cur.lo << " " << cur.hi;
         else std::cout << " minmax";
         std::cout << std::endl;
+    }
+
+    // measure on [channel] | measure off | measure (prints the setting in force)
+    void cmd_measure(const Words &w)
+    {
+        if (w.size() >= 2) {
+            int channel = 0;
+            const bool on = w[1] == "on";
+            const bool ok = (on && (w.size() == 2 || (w.size() == 3 && to_int(w[2], channel)))) || (w[1] == "off" && w.size() == 2);
+            if (!ok) {
+                std::cerr << "Error: Invalid measure command (expected on [channel] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_measure(on, channel)) {
+                std::cerr << "Measure unchanged" << std::endl;
+                return;
+            }
+        }
+        const mi_unet_measure cur = MedicalSeg::get_measure();
+        std::cout << "Measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << std::endl;
     }
 
     void cmd_exit()

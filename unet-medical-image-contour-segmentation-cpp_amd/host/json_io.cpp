@@ -1,6 +1,8 @@
 #include "json_io.h"
 
 #include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
 #include <stdexcept>
 
 namespace medseg {
@@ -45,8 +47,40 @@ std::string size_json_text(const std::string &raw_filename, int w, int h, int sc
 
 namespace {
 // the document around a list of shapes, each with its label pair (src/mask2polygon.cpp:68-109 with std::setw(4))
-struct Shape { const Contour *pts; int label, label_index; };
-std::string polygon_document(const std::vector<Shape> &shapes, const std::string &base_name, int original_width, int original_height)
+struct Shape { const Contour *pts; int label, label_index; const mi_unet_region *region = nullptr; };
+
+// the "region" member of a shape (16 spaces deep), keys sorted byte-wise
+std::string region_member(const mi_unet_region &r, double scale_x, double scale_y)
+{
+    mi_unet_region_shape s{};
+    if (mi_unet_region_derive(&r, &s) != MI_UNET_OK) throw std::runtime_error(std::string("region_derive failed: ") + mi_unet_last_error());
+    const std::string in1 = "                ", in2 = "                    ";
+    auto ints = [&](const char *key, std::initializer_list<std::string> vals) {
+        std::string o = in1 + "\"" + key + "\": [\n";
+        size_t k = 0;
+        for (const std::string &v : vals) o += in2 + v + (++k < vals.size() ? ",\n" : "\n");
+        return o + in1 + "],\n";
+    };
+    std::string o = "            \"region\": {\n";
+    o += in1 + "\"area\": " + std::to_string(r.area) + ",\n";
+    o += ints("bbox", { std::to_string(r.x0), std::to_string(r.y0), std::to_string(r.x1), std::to_string(r.y1) });
+    o += ints("centroid", { json_double(s.cx), json_double(s.cy) });
+    o += in1 + "\"edges\": " + std::to_string(r.edges) + ",\n";
+    o += in1 + "\"imax\": " + std::to_string(r.imax) + ",\n";
+    o += in1 + "\"imin\": " + std::to_string(r.imin) + ",\n";
+    o += in1 + "\"major\": " + json_double(s.major) + ",\n";
+    o += in1 + "\"mean\": " + json_double(s.mean) + ",\n";
+    o += in1 + "\"minor\": " + json_double(s.minor) + ",\n";
+    o += in1 + "\"scale_x\": " + json_double(scale_x) + ",\n";
+    o += in1 + "\"scale_y\": " + json_double(scale_y) + ",\n";
+    o += in1 + "\"std\": " + json_double(s.std) + ",\n";
+    o += in1 + "\"theta\": " + json_double(s.theta) + "\n";
+    o += "            },\n";
+    return o;
+}
+
+std::string polygon_document(const std::vector<Shape> &shapes, const std::string &base_name, int original_width, int original_height,
+                             double scale_x = 1.0, double scale_y = 1.0)
 {
     std::string o;
     o += "{\n";
@@ -80,6 +114,7 @@ std::string polygon_document(const std::vector<Shape> &shapes, const std::string
                 }
                 o += "            ],\n";
             }
+            if (shapes[c].region) o += region_member(*shapes[c].region, scale_x, scale_y);
             o += "            \"shape_type\": \"polygon\"\n";
             o += (c + 1 < shapes.size()) ? "        },\n" : "        }\n";
         }
@@ -100,13 +135,34 @@ std::string polygon_json_text(const std::vector<Contour> &contours, const std::s
 }
 
 std::string polygon_json_text(const std::vector<ClassContours> &groups, const std::string &base_name, int original_width,
-                              int original_height)
+                              int original_height, const RegionTable *regions)
 {
-    if (groups.size() == 1 && groups[0].cls == 2) return polygon_json_text(groups[0].contours, base_name, original_width, original_height);
+    if (regions) {
+        if (regions->regions.size() != groups.size()) throw std::runtime_error("polygon_json_text: one list of regions per group");
+        for (size_t g = 0; g < groups.size(); ++g)
+            if (regions->regions[g].size() != groups[g].contours.size()) throw std::runtime_error("polygon_json_text: one region per contour");
+    }
+    const bool reference = groups.size() == 1 && groups[0].cls == 2;      // the reference's name for its one foreground class
+    if (reference && !regions) return polygon_json_text(groups[0].contours, base_name, original_width, original_height);
     std::vector<Shape> shapes;
     for (size_t g = 0; g < groups.size(); ++g)
-        for (const Contour &c : groups[g].contours) shapes.push_back({ &c, groups[g].cls, (int)g });
-    return polygon_document(shapes, base_name, original_width, original_height);
+        for (size_t c = 0; c < groups[g].contours.size(); ++c)
+            shapes.push_back({ &groups[g].contours[c], reference ? 1 : groups[g].cls, reference ? 0 : (int)g,
+                               regions ? &regions->regions[g][c] : nullptr });
+    return polygon_document(shapes, base_name, original_width, original_height, regions ? regions->scale_x : 1.0,
+                            regions ? regions->scale_y : 1.0);
+}
+
+std::string json_double(double v)
+{
+    char b[40];
+    for (int p = 1; p <= 17; ++p) {
+        snprintf(b, sizeof b, "%.*g", p, v);
+        if (strtod(b, nullptr) == v) break;
+    }
+    std::string o = b;
+    if (o.find_first_of(".eE") == std::string::npos) o += ".0";
+    return o;
 }
 
 namespace {

@@ -26,8 +26,15 @@ std::string polygon_json_text(const std::vector<Contour> &contours, const std::s
 // "labelIndex": g, group after group; a group without contours contributes no shape; everything else as above.  One exception keeps
 // the reference's document: a single group of class 2 -- the default target list -- is the function above ("label": 1,
 // "labelIndex": 0, the reference's name for its one foreground class).
+// With `regions` (MedicalSeg::set_measure; regions->regions[g][c] for groups[g].contours[c]) every shape gains a "region" object
+// between "points" and "shape_type", keys in nlohmann's sorted order: area, bbox [x0, y0, x1, y1], centroid [cx, cy], edges, imax,
+// imin, major, mean, minor, scale_x, scale_y, std, theta -- the region's integers and mi_unet_region_derive of it, in TILE pixels;
+// scale_x / scale_y convert to the points' coordinates.  Integers as std::to_string writes them, doubles as nlohmann's dump() does:
+// the shortest decimal that reads back as the same double, with ".0" appended to one without '.', 'e' or 'E'.  Without `regions`
+// the document is unchanged byte for byte.
 std::string polygon_json_text(const std::vector<ClassContours> &groups, const std::string &base_name, int original_width,
-                              int original_height);
+                              int original_height, const RegionTable *regions = nullptr);
+std::string json_double(double v);
 
 // Parses an object of objects of integers (the size file).  Throws std::runtime_error on malformed input.
 std::map<std::string, std::map<std::string, long long>> parse_size_json(const std::string &text);

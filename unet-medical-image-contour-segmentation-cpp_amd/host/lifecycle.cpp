@@ -41,6 +41,7 @@ mi_unet_group_t *g_lane2 = nullptr;  // a clone of g_group, created by the first
 mi_unet_config g_cfg{};            // per-rank configuration of the group (tile size, topology, max_batch, algorithm)
 int g_thread_batch = 1;            // micro-batch capacity of a per-thread context
 unsigned long g_generation = 0;    // bumped by every (re)initialisation and cleanup: older thread contexts are stale
+mi_unet_measure g_measure{ 0, 0 };  // set_measure: outlives the engine, like the window
 std::vector<mi_unet_target> g_targets{ { 2, 0.06f } };   // set_targets: what process_single_image / process_image_batch segment
 std::ofstream g_log_file;
 std::string g_log_path;
@@ -154,6 +155,7 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
         }
         const mi_unet_window window = Preprocess::get_window();            // the window in force outlives the engine
         if (up && mi_unet_group_set_window(g_group, &window) != MI_UNET_OK) up = false;
+        if (up && mi_unet_group_set_measure(g_group, &g_measure) != MI_UNET_OK) up = false;      // (a channel this network does not have)
         if (!up) {
             g_log_file << "Error: Failed to initialize MI355X UNet engine: " << mi_unet_last_error() << std::endl;
             std::cerr << "Initialization error: " << mi_unet_last_error() << std::endl;
@@ -231,6 +233,31 @@ bool set_window(const mi_unet_window &window)
 
 mi_unet_window get_window() { return Preprocess::get_window(); }
 
+bool set_measure(bool on, int channel)
+{
+    std::lock_guard<std::mutex> batch(g_batch_mutex);          // never under a running directory-mode call
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    const mi_unet_measure m{ on ? 1 : 0, channel };
+    // the group validates the channel against the loaded network and changes all of its ranks or none; without an engine only the sign
+    if (channel < 0 || (g_group && mi_unet_group_set_measure(g_group, &m) != MI_UNET_OK)) {
+        std::cerr << "Error: " << (channel < 0 ? "measure: negative channel" : mi_unet_last_error()) << std::endl;
+        return false;
+    }
+    if (g_lane2) (void)mi_unet_group_set_measure(g_lane2, &m);
+    g_measure = m;                                              // thread contexts pick the setting up on their next use
+    if (g_log_file.is_open()) {
+        std::lock_guard<std::mutex> ll(g_log_mutex);
+        g_log_file << "Measure: " << (on ? "on" : "off") << ", channel " << channel << std::endl;
+    }
+    return true;
+}
+
+mi_unet_measure get_measure()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    return g_measure;
+}
+
 std::vector<Target> get_targets()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -259,6 +286,7 @@ mi_unet_t *get_thread_local_context()
     const mi_unet_window window = Preprocess::get_window();
     if (t_context.h && t_context.generation == g_generation) {
         (void)mi_unet_set_window(t_context.h, &window);         // (validated when it was set)
+        (void)mi_unet_set_measure(t_context.h, &g_measure);
         return t_context.h;
     }
     t_context.release();
@@ -266,6 +294,7 @@ mi_unet_t *get_thread_local_context()
         throw std::runtime_error(std::string("context creation failed: ") + mi_unet_last_error());
     t_context.generation = g_generation;
     (void)mi_unet_set_window(t_context.h, &window);             // a clone starts at the default
+    (void)mi_unet_set_measure(t_context.h, &g_measure);
     {
         std::lock_guard<std::mutex> ll(g_log_mutex);
         if (g_log_file.is_open())
@@ -443,6 +472,8 @@ struct ChunkOut {
     std::vector<size_t> idx;                           // files of the range that were read (offsets into the range)
     std::vector<uint8_t> tiles, labels;
     std::vector<int32_t> xy, start, cnt;
+    std::vector<mi_unet_region> regions;               // set_measure: [m][kCapContours] and [m] counts, else empty
+    std::vector<int32_t> rcnt;
     long long device_ms = 0;
 };
 
@@ -466,6 +497,30 @@ std::vector<medseg::Contour> contours_of(const int32_t *xy, const int32_t *start
         contours.push_back(std::move(cc));
     }
     return contours;
+}
+
+// The regions of the last segment call on `ctx` (or, with ctx null, on `group`), when it measured: [planes][kCapContours] structs and
+// [planes] counts; empty vectors when it did not (MedicalSeg::set_measure off).
+void fetch_regions(mi_unet_t *ctx, mi_unet_group_t *group, size_t planes, std::vector<mi_unet_region> &regions, std::vector<int32_t> &rcnt)
+{
+    regions.clear(); rcnt.clear();
+    int pl = 0, cap = 0;
+    const int rc = ctx ? mi_unet_last_regions(ctx, nullptr, nullptr, 0, &pl, &cap) : mi_unet_group_last_regions(group, nullptr, nullptr, 0, &pl, &cap);
+    if (rc != MI_UNET_OK || (size_t)pl != planes || cap != kCapContours) return;
+    regions.resize(planes * (size_t)kCapContours); rcnt.resize(planes);
+    if ((ctx ? mi_unet_last_regions(ctx, regions.data(), rcnt.data(), pl, &pl, &cap)
+             : mi_unet_group_last_regions(group, regions.data(), rcnt.data(), pl, &pl, &cap)) != MI_UNET_OK) {
+        regions.clear(); rcnt.clear();
+    }
+}
+
+// the regions of plane `plane` for a shape list the device traced (count >= 0 contours); false when the plane has none to give
+bool plane_regions(const std::vector<mi_unet_region> &regions, const std::vector<int32_t> &rcnt, size_t plane, int count,
+                   std::vector<mi_unet_region> &out)
+{
+    if (rcnt.empty() || count < 0 || rcnt[plane] != count) return false;
+    out.assign(regions.begin() + plane * (size_t)kCapContours, regions.begin() + plane * (size_t)kCapContours + count);
+    return true;
 }
 
 // channel 0 of `npix` interleaved pixels with C channels: the grey artefact tile (the planes are replicas).  In place allowed.
@@ -530,6 +585,7 @@ ChunkOut device_chunk(const ChunkIn &in, const std::vector<int> &widths, const s
                                     out.labels.data(), out.xy.data(), kCapPoints, out.start.data(), kCapContours,
                                     out.cnt.data()) != MI_UNET_OK)
         throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
+    fetch_regions(nullptr, group, m, out.regions, out.rcnt);
     if (C > 1) keep_channel0(tiles_c.data(), hw * m, C, out.tiles.data());
     out.device_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count();
     return out;
@@ -562,7 +618,10 @@ ChunkText artefact_chunk(const ChunkIn &in, const ChunkOut &out, const std::vect
                 throw std::runtime_error("Failed to save mask");
             const std::vector<medseg::Contour> contours =
                 contours_of(&out.xy[k * (size_t)kCapPoints * 2], &out.start[k * (kCapContours + 1)], out.cnt[k], vis);
-            Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, widths[i], heights[i], con);
+            medseg::RegionTable table;
+            table.regions.resize(1);
+            const bool measured = plane_regions(out.regions, out.rcnt, (size_t)k, out.cnt[k], table.regions[0]);
+            Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, widths[i], heights[i], con, measured ? &table : nullptr);
             lg << "Processing completed for: " << base_name << std::endl;
             done[k] = 1;
         } catch (const std::exception &e) {
@@ -602,6 +661,7 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
             if (g_lane2) {
                 const mi_unet_window window = Preprocess::get_window();       // a clone starts at the default
                 (void)mi_unet_group_set_window(g_lane2, &window);
+                (void)mi_unet_group_set_measure(g_lane2, &g_measure);
                 lanes[1] = g_lane2; n_lanes = 2;
             }
         }
@@ -736,6 +796,9 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                      : mi_unet_group_infer_raw16(group, ptrs.data(), ws.data(), hs.data(), (int)m, tiles.data(), labels.data(), nullptr);
         }
         if (rc != MI_UNET_OK) throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
+        std::vector<mi_unet_region> regions;
+        std::vector<int32_t> rcnt;
+        if (device_tail) fetch_regions(ctx, group, m * K, regions, rcnt);
         lg << "Inference time: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count()
            << " ms" << (m > 1 ? " for " + std::to_string(m) + " images" : std::string()) << std::endl;
         for (size_t k = 0; k < m; ++k) {
@@ -749,6 +812,9 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                                                           output_dir + "/" + base_name + "_original_sizes.json", widths[i], heights[i]))
                     throw std::runtime_error("Preprocessing failed");
                 std::vector<medseg::ClassContours> groups;
+                medseg::RegionTable table;
+                table.regions.resize(K);
+                bool measured = !rcnt.empty();
                 for (size_t t = 0; t < K; ++t) {
                     const size_t plane = k * K + t;
                     Image8 vis(g_cfg.height, g_cfg.width, 1);
@@ -765,8 +831,9 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                     // (the host chain leaves cnt at -1 and xy empty: the host tracer)
                     groups.push_back({ targets[t].cls, contours_of(xy.data() + (device_tail ? plane * (size_t)kCapPoints * 2 : 0),
                                                                    &start[plane * (kCapContours + 1)], cnt[plane], vis) });
+                    measured = measured && plane_regions(regions, rcnt, plane, cnt[plane], table.regions[t]);
                 }
-                Mask2Polygon::write_polygon_outputs(groups, tile, output_dir, base_name, widths[i], heights[i]);
+                Mask2Polygon::write_polygon_outputs(groups, tile, output_dir, base_name, widths[i], heights[i], std::cout, measured ? &table : nullptr);
                 if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
                 ++ok;
             } catch (const std::exception &e) {
@@ -967,6 +1034,12 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             mi_unet_last_stage_ms(ctx, st);
             lg << "Inference time: " << (long long)device_ms << " ms" << std::endl;
             const std::vector<medseg::Contour> contours = contours_of(xy.data(), start.data(), cnt, vis);
+            std::vector<mi_unet_region> regions;
+            std::vector<int32_t> rcnt;
+            fetch_regions(ctx, nullptr, 1, regions, rcnt);
+            medseg::RegionTable table;
+            table.regions.resize(1);
+            const bool measured = plane_regions(regions, rcnt, 0, cnt, table.regions[0]);
             // artefacts: {normalized.png + sizes.json} || {mask.png} || {overlay.png + polygon json}
             const auto t_art = clk::now();
             double norm_ms = 0, mask_ms = 0, poly_ms = 0;
@@ -986,7 +1059,7 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             });
             {
                 const auto t0 = clk::now();
-                Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, width, height, con);
+                Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, width, height, con, measured ? &table : nullptr);
                 poly_ms = ms_since(t0);
             }
             const bool norm_ok = f_norm.get(), mask_ok = f_mask.get();

@@ -215,13 +215,14 @@ Image8 draw_overlay(const Image8 &src, const std::vector<medseg::ClassContours> 
 }
 
 std::string polygon_json_text(const std::vector<medseg::ClassContours> &groups, const std::string &base_name, int original_width,
-                              int original_height)
+                              int original_height, const medseg::RegionTable *regions)
 {
-    return medseg::polygon_json_text(groups, base_name, original_width, original_height);
+    return medseg::polygon_json_text(groups, base_name, original_width, original_height, regions);
 }
 
 void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const Image8 &normalized_tile, const std::string &output_dir,
-                           const std::string &base_name, int original_width, int original_height, std::ostream &console)
+                           const std::string &base_name, int original_width, int original_height, std::ostream &console,
+                           const medseg::RegionTable *regions)
 {
     try {
         console << "Processing Mask: " << base_name + ".png" << std::endl;
@@ -245,7 +246,9 @@ void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, con
         const std::string output_json_path = output_dir + "/" + base_name + ".json";
         std::ofstream f(output_json_path);
         if (!f.is_open()) throw std::runtime_error("Fail to Create JSON File: " + output_json_path);
-        f << medseg::polygon_json_text(mapped, base_name, original_width, original_height);
+        medseg::RegionTable table;                               // the regions stay in tile pixels; the document carries the factors
+        if (regions) { table.regions = regions->regions; table.scale_x = scale_x; table.scale_y = scale_y; }
+        f << medseg::polygon_json_text(mapped, base_name, original_width, original_height, regions ? &table : nullptr);
         f.flush();
         console << "JSON Saved to: " << output_json_path << std::endl;
     } catch (const std::exception &e) {
@@ -264,7 +267,7 @@ void create_overlay_image(const std::vector<Contour> &contours, const std::strin
 
 void write_polygon_outputs(const std::vector<Contour> &contours, const Image8 &normalized_tile, const std::string &output_dir,
                            const std::string &base_name, int original_width, int original_height,
-                           std::ostream &console)
+                           std::ostream &console, const medseg::RegionTable *regions)
 {
     try {
         console << "Processing Mask: " << base_name + ".png" << std::endl;
@@ -286,7 +289,16 @@ void write_polygon_outputs(const std::vector<Contour> &contours, const Image8 &n
         const double scale_x = static_cast<double>(original_width) / normalized_tile.cols;
         const double scale_y = static_cast<double>(original_height) / normalized_tile.rows;
         const std::string output_json_path = output_dir + "/" + base_name + ".json";
-        generate_json(map_contour_points(contours, scale_x, scale_y), output_json_path, base_name, original_width, original_height);
+        if (regions) {          // measured: the same document (the reference's single class) with a "region" object per shape
+            medseg::RegionTable table{ regions->regions, scale_x, scale_y };
+            std::ofstream f(output_json_path);
+            if (!f.is_open()) throw std::runtime_error("Fail to Create JSON File: " + output_json_path);
+            f << medseg::polygon_json_text(std::vector<medseg::ClassContours>{ { 2, map_contour_points(contours, scale_x, scale_y) } }, base_name,
+                                           original_width, original_height, &table);
+            f.flush();
+        } else {
+            generate_json(map_contour_points(contours, scale_x, scale_y), output_json_path, base_name, original_width, original_height);
+        }
         console << "JSON Saved to: " << output_json_path << std::endl;
     } catch (const std::exception &e) {
         std::cerr << "Processing Failure: " << e.what() << std::endl;

@@ -30,6 +30,8 @@ EXPORTS = [
     "mi_unet_segment_raw16_multi", "mi_unet_segment_tiled_raw16_multi", "mi_unet_group_set_targets",
     "mi_unet_group_segment_raw16_multi",
     "mi_unet_set_window", "mi_unet_get_window", "mi_unet_window_of", "mi_unet_last_windows", "mi_unet_group_set_window",
+    "mi_unet_set_measure", "mi_unet_get_measure", "mi_unet_last_regions", "mi_unet_measure_regions", "mi_unet_region_derive",
+    "mi_unet_group_set_measure", "mi_unet_group_last_regions",
 ]
 
 
@@ -66,6 +68,35 @@ class Target(C.Structure):
 
 class Window(C.Structure):
     _fields_ = [("mode", C.c_int), ("clip_lo_ppm", C.c_int), ("clip_hi_ppm", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
+
+
+class Region(C.Structure):
+    """mi_unet_region: 96 bytes, eight int32 then eight int64; REGION_DTYPE is the same layout for numpy"""
+    _fields_ = [("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("imin", C.c_int32),
+                ("imax", C.c_int32), ("channel", C.c_int32), ("edges", C.c_int64), ("sx", C.c_int64), ("sy", C.c_int64),
+                ("sxx", C.c_int64), ("syy", C.c_int64), ("sxy", C.c_int64), ("si", C.c_int64), ("sii", C.c_int64)]
+
+
+REGION_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in Region._fields_])
+
+
+class Measure(C.Structure):
+    _fields_ = [("on", C.c_int), ("channel", C.c_int)]
+
+
+class RegionShape(C.Structure):
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("mean", C.c_double), ("std", C.c_double), ("major", C.c_double),
+                ("minor", C.c_double), ("theta", C.c_double)]
+
+
+def _last_regions(fn, handle):
+    """(regions REGION_DTYPE [planes, cap_contours], counts int32 [planes]) of mi_unet_last_regions or its group form"""
+    planes, cap = C.c_int(), C.c_int()
+    _check(fn(handle, None, None, 0, C.byref(planes), C.byref(cap)))
+    regions = np.zeros((planes.value, cap.value), REGION_DTYPE)
+    counts = np.zeros(planes.value, np.int32)
+    _check(fn(handle, _ptr(regions), _ptr(counts), planes.value, C.byref(planes), C.byref(cap)))
+    return regions, counts
 
 
 WINDOW_MODES = {"minmax": 0, "percentile": 1, "fixed": 2}
@@ -194,6 +225,13 @@ def lib():
         L.mi_unet_window_of.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Window), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi_unet_last_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.mi_unet_group_set_window.argtypes = [C.c_void_p, C.POINTER(Window)]
+        L.mi_unet_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
+        L.mi_unet_get_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
+        L.mi_unet_last_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi_unet_measure_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.mi_unet_region_derive.argtypes = [C.POINTER(Region), C.POINTER(RegionShape)]
+        L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
+        L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         _LIB = L
     return _LIB
 
@@ -524,6 +562,33 @@ class Engine:
         _check(lib().mi_unet_last_windows(self._h, _ptr(out), n.value, C.byref(n)))
         return out
 
+    # ---- region measurement (mi_unet_set_measure): every contour-returning call also measures the regions behind its contours
+    def set_measure(self, on=True, channel=0):
+        """on=None restores the default (off, channel 0)"""
+        _check(lib().mi_unet_set_measure(self._h, None if on is None else C.byref(Measure(int(bool(on)), int(channel)))))
+
+    def get_measure(self):
+        m = Measure()
+        _check(lib().mi_unet_get_measure(self._h, C.byref(m)))
+        return {"on": bool(m.on), "channel": m.channel}
+
+    def last_regions(self):
+        """the regions of the last contour-returning call: (REGION_DTYPE [planes, cap_contours], counts int32 [planes])"""
+        return _last_regions(lib().mi_unet_last_regions, self._h)
+
+    def measure_regions(self, masks: np.ndarray, tiles=None, channel=0, cap_contours=256):
+        """the stage alone: masks u8 [B,H,W], tiles u8 [B,H,W(,C)] or None -> (REGION_DTYPE [B, cap_contours], counts int32 [B])"""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        b = masks.shape[0]
+        if tiles is not None:
+            tiles = np.ascontiguousarray(tiles, np.uint8)
+            if tiles.size != masks.size * self.cfg.in_ch:
+                raise ValueError(f"tiles must be [B,H,W,{self.cfg.in_ch}] for these masks, got {tiles.shape}")
+        regions = np.zeros((b, cap_contours), REGION_DTYPE)
+        counts = np.zeros(b, np.int32)
+        _check(lib().mi_unet_measure_regions(self._h, _ptr(masks), _ptr(tiles), b, int(channel), _ptr(regions), cap_contours, _ptr(counts)))
+        return regions, counts
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -628,6 +693,15 @@ def window_of(samples, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=655
     return wlo.value, whi.value
 
 
+def region_derive(region):
+    """mi_unet_region_derive of one region (a Region, or one REGION_DTYPE record) -> dict of cx, cy, mean, std, major, minor, theta"""
+    if not isinstance(region, Region):
+        region = Region(*[int(region[n]) for n, _ in Region._fields_])
+    out = RegionShape()
+    _check(lib().mi_unet_region_derive(C.byref(region), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in RegionShape._fields_}
+
+
 def shard_range(n_items: int, rank: int, world: int):
     lo, hi = C.c_int(), C.c_int()
     _check(lib().mi_unet_shard_range(n_items, rank, world, C.byref(lo), C.byref(hi)))
@@ -716,6 +790,14 @@ class Group:
     def set_window(self, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
         """Engine.set_window on every rank"""
         _check(lib().mi_unet_group_set_window(self._g, _window(mode, clip_lo_ppm, clip_hi_ppm, lo, hi)))
+
+    def set_measure(self, on=True, channel=0):
+        """Engine.set_measure on every rank"""
+        _check(lib().mi_unet_group_set_measure(self._g, None if on is None else C.byref(Measure(int(bool(on)), int(channel)))))
+
+    def last_regions(self):
+        """Engine.last_regions of the last sharded segment call, planes in image order"""
+        return _last_regions(lib().mi_unet_group_last_regions, self._g)
 
     def _n_targets(self):
         n = C.c_int()

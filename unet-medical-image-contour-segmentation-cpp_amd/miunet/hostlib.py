@@ -19,7 +19,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_extract_contours", "medseg_map_points", "medseg_generate_json", "medseg_draw_overlay", "medseg_process_single_mask",
            "medseg_write_png", "medseg_read_png", "medseg_postprocess_mask_target", "medseg_set_targets", "medseg_get_targets",
            "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
-           "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window"]
+           "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
+           "medseg_set_measure", "medseg_get_measure", "medseg_polygon_json_text_regions"]
 
 
 def lib():
@@ -57,6 +58,11 @@ def lib():
         L.medseg_get_window.restype = None
         L.medseg_window_of.argtypes = [_u16, C.c_size_t] + [C.c_int] * 5 + [_i, _i]
         L.medseg_resample_normalize_window.argtypes = [_u16, C.c_int, C.c_int, C.c_int, C.c_int, _u8, C.c_int, C.c_int]
+        L.medseg_set_measure.argtypes = [C.c_int, C.c_int]
+        L.medseg_get_measure.argtypes = [_i, _i]
+        L.medseg_get_measure.restype = None
+        L.medseg_polygon_json_text_regions.argtypes = [_i32, _i32, _i, _i, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_int,
+                                                       C.c_int, C.c_char_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -114,6 +120,34 @@ def polygon_json_text_groups(groups, base_name, ow, oh) -> bytes:
     if got < 0:
         raise RuntimeError("polygon_json_text_groups: buffer too small")
     return buf.raw[:got]
+
+
+def polygon_json_text_regions(groups, regions, scale_x, scale_y, base_name, ow, oh) -> bytes:
+    """polygon_json_text_groups with a "region" object per shape: regions = one binding.REGION_DTYPE record per contour, in the order of
+    the flattened groups (None: no region objects, the bytes of polygon_json_text_groups)"""
+    flat, start, cls, cnt, n = _flatten_groups(groups)
+    if regions is not None:
+        regions = np.ascontiguousarray(regions)
+        if regions.dtype.itemsize != 96 or regions.size != sum(len(cs) for _, cs in groups):
+            raise ValueError("one 96-byte region record per contour")
+    cap = 4096 + 160 * (len(start) + flat.size) + 1024 * (0 if regions is None else regions.size)
+    buf = C.create_string_buffer(cap)
+    got = lib().medseg_polygon_json_text_regions(flat, start, cls, cnt, n, None if regions is None else regions.ctypes.data, float(scale_x),
+                                                 float(scale_y), base_name.encode(), ow, oh, buf, cap)
+    if got < 0:
+        raise RuntimeError("polygon_json_text_regions: " + ("buffer too small" if got == -1 else "a region cannot be derived"))
+    return buf.raw[:got]
+
+
+def set_measure(on=True, channel=0) -> bool:
+    """MedicalSeg::set_measure: every shape of <base>.json gains a "region" object; needs no engine"""
+    return lib().medseg_set_measure(int(bool(on)), int(channel)) == 0
+
+
+def get_measure():
+    on, ch = C.c_int(), C.c_int()
+    lib().medseg_get_measure(C.byref(on), C.byref(ch))
+    return {"on": bool(on.value), "channel": ch.value}
 
 
 def draw_overlay_groups(gray, groups):
