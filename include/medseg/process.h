@@ -32,6 +32,16 @@ struct Target {
 bool set_targets(const std::vector<Target> &targets);
 std::vector<Target> get_targets();
 
+// The morphology of the targets' clean-up (mi_unet_morph in include/mi_unet.h): one entry for every target or one per
+// target, in target order; an empty list restores the default { { MI_UNET_MORPH_RECT, 1, 0 } }, the reference's 3x3 open, under which
+// every artefact is what it always was.  Needs no engine; the setting survives initialize_engine and reaches the group, the second lane
+// and every thread's context.  false, message on stderr, setting unchanged: an unknown shape, a radius outside 0 ..
+// MI_UNET_MORPH_MAX_R, more than MI_UNET_MAX_TARGETS entries.  A list that is neither 1 nor as long as the target list fails the next
+// process call.  No artefact changes its name or format; MEDSEG_HOST_POSTPROCESS=1 applies the same setting on the CPU.
+using Morph = mi_unet_morph;
+bool set_morphology(const std::vector<Morph> &morph);
+std::vector<Morph> get_morphology();
+
 // The intensity window of the RAW input (mi_unet_window in include/mi_unet.h) that the two functions above apply, on the
 // device and on the MEDSEG_HOST_PREPROCESS route alike: the default min/max stretch, a percentile clip or a fixed lo..hi.  Needs no
 // engine (the setting survives initialize_engine and is handed to every engine, lane and thread context); false, message on stderr,

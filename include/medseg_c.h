@@ -33,6 +33,13 @@ int medseg_postprocess_mask_target(const uint8_t *mask, int w, int h, int cls, f
  * fills at most cap entries. */
 int medseg_set_targets(const int *cls, const float *min_area_frac, int n);
 int medseg_get_targets(int *cls, float *min_area_frac, int cap);
+/* Morphology (mi_unet_morph in include/mi_unet.h): postprocess_mask(src, cls, min_area_frac, morph) on the CPU, and
+ * MedicalSeg::set_morphology / get_morphology as n triples (shape[i], open_r[i], close_r[i]); n == 0 restores the default, no engine
+ * needed; set returns 0 on success, 1 and nothing changed otherwise; get returns the count and fills at most cap entries. */
+int medseg_postprocess_mask_morph(const uint8_t *mask, int w, int h, int cls, float min_area_frac, int shape, int open_r, int close_r,
+                                  uint8_t *out);
+int medseg_set_morphology(const int *shape, const int *open_r, const int *close_r, int n);
+int medseg_get_morphology(int *shape, int *open_r, int *close_r, int cap);
 /* Intensity windows (mi_unet_window in include/mi_unet.h): MedicalSeg::set_window / get_window as (mode, clip_lo_ppm, clip_hi_ppm, lo,
  * hi) -- 0 on success, 1 and nothing changed for a setting the engine refuses; no engine needed -- and the CPU arithmetic:
  * Preprocess::window_of (0 on success) and Preprocess::resample_normalize_window */

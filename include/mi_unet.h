@@ -237,6 +237,40 @@ int mi_unet_segment_raw16_multi(mi_unet_t *h, const uint16_t *const *raws, const
 int mi_unet_segment_tiled_raw16_multi(mi_unet_t *h, const uint16_t *const *planes, int W, int H, int halo, uint8_t *norm, uint8_t *mask,
                                       int32_t *xy, int cap_points, int32_t *start, int cap_contours, int32_t *count);
 
+/* ---- Morphology: the element of a target's clean-up, so that it can scale with the image -------------------------------
+ * The reference's third tunable, MORPH_KERNEL_SIZE (src/postprocess.cpp), per target: a radius for the opening, an optional closing in
+ * front of it and a choice of box or Euclidean disc.  The element of radius r is (2r + 1) x (2r + 1) with its anchor at the centre:
+ *   MI_UNET_MORPH_RECT : every (dx, dy) with |dx| <= r and |dy| <= r, = cv::getStructuringElement(MORPH_RECT, (2r + 1, 2r + 1))
+ *   MI_UNET_MORPH_DISC : { (dx, dy) : dx*dx + dy*dy <= r*r }, in integer arithmetic (r = 1 is the plus)
+ * mi_unet_morph_element writes it as (2r + 1) * (2r + 1) bytes 0 / 1, row after row (pure host arithmetic, needs no device);
+ * MI_UNET_EARG for an unknown shape, r outside 0 .. MI_UNET_MORPH_MAX_R or a null pointer.
+ * With a morphology a target's mask is four steps:
+ *   1. fill holes (as above, unchanged)
+ *   2. close : dilate by the element of radius close_r, then erode by it
+ *   3. open  : erode by the element of radius open_r, then dilate by it
+ *   4. area filter (as above, unchanged)
+ * Border rules for every radius and both shapes: an erosion is constrained only by pixels inside the image (a pixel survives when every
+ * element position that falls inside the image is foreground), a dilation is seeded only by pixels inside the image.  r = 0 is the
+ * identity; { RECT, 1, 0 } is the reference's 3x3 open.  Integer-exact like the rest of the tail.
+ * The setting is per handle and off by default: { { RECT, 1, 0 } }.  mi_unet_set_morph: n = 1 applies the entry to every target, n = K
+ * gives one entry per target in target order; m == NULL or n == 0 restores the default; a clone starts at the default.  MI_UNET_EARG,
+ * setting unchanged: an unknown shape, a radius outside 0 .. MI_UNET_MORPH_MAX_R, n < 0 or n > MI_UNET_MAX_TARGETS.  The list is not tied
+ * to the targets when it is set and mi_unet_set_targets does not touch it: a _multi call whose stored list is longer than 1 and not as
+ * long as its target list fails with MI_UNET_ESTATE and a message before anything is queued.  mi_unet_get_morph writes min(*n, cap)
+ * entries and the number stored to *n.
+ * Only the _multi entry points read the setting (mi_unet_postprocess_masks_multi, mi_unet_segment_raw16_multi,
+ * mi_unet_segment_tiled_raw16_multi, mi_unet_group_segment_raw16_multi); every other entry point -- mi_unet_set_postprocess included --
+ * keeps the 3x3 box.  With the default setting every call enqueues exactly the launches it enqueued before and returns the same bytes.
+ * On the tiled route the tail runs at the image's native resolution: scale the radius with native / tile resolution to reproduce the
+ * clean-up of the resampled route (min_area already scales, being a fraction).  The time counts under MI_UNET_STAGE_POSTPROCESS. */
+#define MI_UNET_MORPH_RECT 0     /* (2r+1) x (2r+1) box: cv::getStructuringElement(MORPH_RECT) */
+#define MI_UNET_MORPH_DISC 1     /* { (dx, dy) : dx*dx + dy*dy <= r*r }, integer arithmetic */
+#define MI_UNET_MORPH_MAX_R 31
+typedef struct mi_unet_morph { int shape; int open_r; int close_r; } mi_unet_morph;   /* default { RECT, 1, 0 } */
+int mi_unet_set_morph(mi_unet_t *h, const mi_unet_morph *m, int n);
+int mi_unet_get_morph(const mi_unet_t *h, mi_unet_morph *m, int cap, int *n);
+int mi_unet_morph_element(int shape, int r, uint8_t *elem /* [(2r+1)*(2r+1)], 0 / 1 */);
+
 /* ---- Intensity windows: which sample range of a RAW16 plane becomes 0..255 ---------------------------------------
  * A per-handle setting that every RAW-in entry point reads (mi_unet_infer_raw16, mi_unet_segment_raw16{,_multi},
  * mi_unet_infer_tiled_raw16, mi_unet_segment_tiled_raw16{,_multi} and their group forms).  The default, MINMAX, is the reference's
@@ -478,6 +512,8 @@ int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n
 int mi_unet_group_segment_raw16_multi(mi_unet_group_t *g, const uint16_t *const *raws, const int *widths, const int *heights, int B,
                                       uint8_t *tiles, uint8_t *masks, int32_t *xy, int cap_points, int32_t *start, int cap_contours,
                                       int32_t *counts);
+/* mi_unet_set_morph on every rank (all or none); mi_unet_group_segment_raw16_multi then applies it */
+int mi_unet_group_set_morph(mi_unet_group_t *g, const mi_unet_morph *m, int n);
 /* mi_unet_set_window on every rank (all or none); the sharded RAW-in calls above then apply it */
 int mi_unet_group_set_window(mi_unet_group_t *g, const mi_unet_window *w);
 /* mi_unet_set_measure on every rank (all or none); mi_unet_last_regions of the last sharded segment call: same arguments, the planes in

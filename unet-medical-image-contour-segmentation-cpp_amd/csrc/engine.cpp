@@ -196,7 +196,27 @@ TargetTable target_table(const mi_unet_target *targets, int n, int H, int W)
     return t;
 }
 
-TargetTable target_table(const mi_unet *h, int H, int W) { return target_table(h->targets, h->n_targets, H, W); }
+void table_morph(TargetTable &t, const mi_unet_morph *m, int n)
+{
+    for (int k = 0; k < t.K; ++k) {
+        const mi_unet_morph &e = m[n == 1 ? 0 : k];
+        t.shape[k] = e.shape; t.open_r[k] = e.open_r; t.close_r[k] = e.close_r;
+    }
+}
+
+int check_morph_list(const mi_unet *h, const char *fn)
+{
+    if (h->n_morph == 1 || h->n_morph == h->n_targets) return 0;
+    return fail(MI_UNET_ESTATE, std::string(fn) + ": the morphology list has " + std::to_string(h->n_morph) + " entries, the target list " +
+                                    std::to_string(h->n_targets) + " (mi_unet_set_morph takes 1 entry or one per target)");
+}
+
+TargetTable target_table(const mi_unet *h, int H, int W)
+{
+    TargetTable t = target_table(h->targets, h->n_targets, H, W);
+    table_morph(t, h->morph, h->n_morph);                   // (check_morph_list passed)
+    return t;
+}
 TargetTable default_targets(int H, int W) { return target_table(&kDefaultTarget, 1, H, W); }
 
 int ensure_tail_buffers(mi_unet *h, size_t ws_bytes, size_t plane_bytes)
@@ -644,6 +664,43 @@ int mi_unet_get_targets(const mi_unet_t *h, mi_unet_target *t, int cap, int *n)
     return MI_UNET_OK;
 }
 
+int mi_unet_set_morph(mi_unet_t *h, const mi_unet_morph *m, int n)
+{
+    if (int rc = check_handle(h, false)) return rc;
+    if (n < 0 || n > MI_UNET_MAX_TARGETS)
+        return fail(MI_UNET_EARG, "mi_unet_set_morph: " + std::to_string(n) + " entries (at most " + std::to_string(MI_UNET_MAX_TARGETS) + ")");
+    if (!m || n == 0) { m = &kDefaultMorph; n = 1; }
+    for (int k = 0; k < n; ++k) {
+        if (m[k].shape != MI_UNET_MORPH_RECT && m[k].shape != MI_UNET_MORPH_DISC)
+            return fail(MI_UNET_EARG, "mi_unet_set_morph: unknown shape " + std::to_string(m[k].shape));
+        if (m[k].open_r < 0 || m[k].open_r > MI_UNET_MORPH_MAX_R || m[k].close_r < 0 || m[k].close_r > MI_UNET_MORPH_MAX_R)
+            return fail(MI_UNET_EARG, "mi_unet_set_morph: radius outside 0.." + std::to_string(MI_UNET_MORPH_MAX_R));
+    }
+    mi_unet_morph keep[MI_UNET_MAX_TARGETS];           // (m may point into h->morph)
+    std::copy(m, m + n, keep);
+    std::copy(keep, keep + n, h->morph);
+    h->n_morph = n;
+    return MI_UNET_OK;
+}
+
+int mi_unet_get_morph(const mi_unet_t *h, mi_unet_morph *m, int cap, int *n)
+{
+    if (!h || !n || cap < 0 || (cap > 0 && !m)) return fail(MI_UNET_EARG, "mi_unet_get_morph: bad argument");
+    *n = h->n_morph;
+    for (int k = 0; k < h->n_morph && k < cap; ++k) m[k] = h->morph[k];
+    return MI_UNET_OK;
+}
+
+int mi_unet_morph_element(int shape, int r, uint8_t *elem)
+{
+    if (!elem || (shape != MI_UNET_MORPH_RECT && shape != MI_UNET_MORPH_DISC) || r < 0 || r > MI_UNET_MORPH_MAX_R)
+        return fail(MI_UNET_EARG, "mi_unet_morph_element: bad argument");
+    for (int dy = -r; dy <= r; ++dy)
+        for (int dx = -r; dx <= r; ++dx)
+            elem[(dy + r) * (2 * r + 1) + dx + r] = shape == MI_UNET_MORPH_RECT || dx * dx + dy * dy <= r * r;
+    return MI_UNET_OK;
+}
+
 // mi_unet_postprocess_masks and its _multi form: label maps up, the chain per micro-batch, masks down.  The first runs the reference's
 // target in place in the network's scratch buffer (device_postprocess), _multi the handle's K targets into d_multi on the tail workspace.
 static int postprocess_masks_call(mi_unet_t *h, const char *fn, bool multi, const uint8_t *labels, int B, uint8_t *out)
@@ -653,6 +710,8 @@ static int postprocess_masks_call(mi_unet_t *h, const char *fn, bool multi, cons
     HIP_TRY(hipSetDevice(h->cfg.device));
     const int H = h->cfg.height, W = h->cfg.width, Bm = h->cfg.max_batch;
     const size_t hw = (size_t)H * W;
+    if (multi)
+        if (int rc = check_morph_list(h, fn)) return rc;
     const TargetTable tab = multi ? target_table(h, H, W) : default_targets(H, W);
     const size_t K = (size_t)tab.K;
     if (multi && (size_t)std::min(B, Bm) * K * hw > 0x7FFFFFFFull)

@@ -185,6 +185,9 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_multi;
     miunet::PinnedBuf<uint8_t> h_multi[2];
     size_t multi_cap = 0;           // bytes of each of the three
+    // mi_unet_set_morph: one entry for every target of a _multi call, or one per target
+    mi_unet_morph morph[MI_UNET_MAX_TARGETS] = { { MI_UNET_MORPH_RECT, 1, 0 } };
+    int n_morph = 1;
     // pinned host staging (the reference used pageable std::vector, src/process.cpp:138,152)
     miunet::PinnedBuf<uint8_t> h_img;
     miunet::PinnedBuf<uint8_t> h_labels;
@@ -226,7 +229,11 @@ int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels
 hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s);
 constexpr mi_unet_target kDefaultTarget{ 2, 0.06f };    // the reference's: class 2, 6 % of the image
 TargetTable target_table(const mi_unet_target *targets, int n, int H, int W);   // `n` targets with min_area of an H x W image
-TargetTable target_table(const mi_unet *h, int H, int W);   // ... the handle's (the _multi entry points)
+TargetTable target_table(const mi_unet *h, int H, int W);   // ... the handle's, with its morphology (the _multi entry points)
+constexpr mi_unet_morph kDefaultMorph{ MI_UNET_MORPH_RECT, 1, 0 };      // the reference's 3x3 open
+// a _multi call begins: MI_UNET_ESTATE + message when the handle's morphology list (mi_unet_set_morph) fits neither every target nor each
+int check_morph_list(const mi_unet *h, const char *fn);
+void table_morph(TargetTable &t, const mi_unet_morph *m, int n);       // entry k % n of `m` for target k (n = 1 or t.K)
 TargetTable default_targets(int H, int W);              // ... the reference's (every entry point without _multi, whatever the handle's setting)
 // h->d_tail_ws of at least `ws_bytes`, h->d_multi / h->h_multi[0..1] of at least `plane_bytes` each (synchronises their users before they grow)
 int ensure_tail_buffers(mi_unet *h, size_t ws_bytes, size_t plane_bytes);

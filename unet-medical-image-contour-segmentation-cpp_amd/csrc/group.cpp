@@ -402,6 +402,13 @@ static int group_segment_raw16(mi_unet_group_t *g, const char *fn, bool multi, c
     if (multi)
         if (int rc = mi_unet_get_targets(g->eng[0], nullptr, 0, &n_targets)) return rc;
     const size_t K = (size_t)n_targets;
+    if (multi) {                                         // the ranks share one setting: refuse a list that fits no rank before any rank starts
+        int n_morph = 1;
+        if (int rc = mi_unet_get_morph(g->eng[0], nullptr, 0, &n_morph)) return rc;
+        if (n_morph != 1 && n_morph != n_targets)
+            return engine_fail(MI_UNET_ESTATE, std::string(fn) + ": the morphology list has " + std::to_string(n_morph) +
+                                                   " entries, the target list " + std::to_string(n_targets));
+    }
     g->seg_B = -1;
     const int rc = for_all_ranks(g, [&](int r) {
         int lo, hi;
@@ -430,6 +437,16 @@ int mi_unet_group_set_targets(mi_unet_group_t *g, const mi_unet_target *t, int n
     // every rank has the same configuration, so the first rank's verdict is everybody's: all ranks change or none does
     for (mi_unet_t *h : g->eng)
         if (int rc = mi_unet_set_targets(h, t, n)) return rc;
+    return MI_UNET_OK;
+}
+
+int mi_unet_group_set_morph(mi_unet_group_t *g, const mi_unet_morph *m, int n)
+{
+    if (!g) return engine_fail(MI_UNET_EARG, "null group");
+    std::lock_guard<std::mutex> lk(g->call_mutex);       // never while a group call is in flight
+    // the verdict does not depend on the rank: the first rank's is everybody's, so all ranks change or none does
+    for (mi_unet_t *h : g->eng)
+        if (int rc = mi_unet_set_morph(h, m, n)) return rc;
     return MI_UNET_OK;
 }
 

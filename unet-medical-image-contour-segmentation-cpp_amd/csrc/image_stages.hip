@@ -445,9 +445,14 @@ hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, i
     hipLaunchKernelGGL(pp::k_inv_multi, g, b, 0, s, labels, u0, hw, t, n);
     label(u0);
     hipLaunchKernelGGL(pp::k_fill_bin_multi, g, b, 0, s, labels, parent, area, minx, miny, maxx, maxy, u1, H, W, t, n);
-    hipLaunchKernelGGL(pp::k_morph3<false>, g, b, 0, s, u1, u2, H, W, n);
-    hipLaunchKernelGGL(pp::k_morph3<true>, g, b, 0, s, u2, u1, H, W, n);
-    label(u1);
+    uint8_t *opened = u1;
+    if (morph_is_default(t)) {
+        hipLaunchKernelGGL(pp::k_morph3<false>, g, b, 0, s, u1, u2, H, W, n);
+        hipLaunchKernelGGL(pp::k_morph3<true>, g, b, 0, s, u2, u1, H, W, n);
+    } else {                                                    // a target's own element (mi_unet_set_morph): between u1 and u2
+        if (hipError_t e = launch_morph_chain(u1, u2, B * t.K, H, W, t, &opened, s); e != hipSuccess) return e;
+    }
+    label(opened);
     hipLaunchKernelGGL(pp::k_filter_multi, g, b, 0, s, parent, area, out, hw, t, n);
     return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, regions.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -210,7 +210,8 @@ hipError_t launch_blend_finalize(const float *acc, int classes, int H, int W, in
 // min_area[p % K], its output in {0, cls[p % K]}:
 //   hole fill : 8-connected components of (label != cls) by lock-free union-find, per-root area + bbox by atomics; a
 //               component is filled iff its bbox touches no image edge and area < min_area
-//   open      : 3x3 erode then dilate, windows clipped to the image
+//   close     : dilate then erode by the target's element of radius close_r (include/mi_unet.h: mi_unet_set_morph; off at 0)
+//   open      : erode then dilate by its element of radius open_r, windows clipped to the image; the reference's is the 3x3 box
 //   filter    : 8-connected components of the opened mask, kept iff area >= min_area
 // Every kernel runs over the B * K planes: the number of launches does not depend on K.  The table travels as a kernel argument (at
 // most POSTPROCESS_MAX_TARGETS entries).  Workspace: postprocess_workspace_bytes(B * K, H, W); B * K * H * W must not exceed
@@ -218,13 +219,24 @@ hipError_t launch_blend_finalize(const float *acc, int classes, int H, int W, in
 // behind every kernel that does); with K > 1 an `out` that overlaps the label maps is refused with hipErrorInvalidValue.
 size_t postprocess_workspace_bytes(int B, int H, int W);
 constexpr int POSTPROCESS_MAX_TARGETS = 5;
+constexpr int POSTPROCESS_MORPH_MAX_R = 31;             // = MI_UNET_MORPH_MAX_R
 struct TargetTable {
     int K = 0;
     int cls[POSTPROCESS_MAX_TARGETS] = {};
     int min_area[POSTPROCESS_MAX_TARGETS] = {};
+    // the element of the target's close / open (mi_unet_morph): the default is the reference's 3x3 open, { RECT, 1, 0 }
+    int shape[POSTPROCESS_MAX_TARGETS] = {};
+    int open_r[POSTPROCESS_MAX_TARGETS] = { 1, 1, 1, 1, 1 };
+    int close_r[POSTPROCESS_MAX_TARGETS] = {};
 };
 hipError_t launch_postprocess_masks_multi(const uint8_t *labels, uint8_t *out, int B, int H, int W, const TargetTable &t, void *ws,
                                           hipStream_t s);
+// The close and open of the chain for tables other than the default (morph.hip): `planes` binary planes u8 [H][W] in
+// `a` (0 / non-zero; plane p is target p % t.K) -> 0 / 255 planes in *result, which is `a` or `b` (same size; both are written).  One
+// launch per erosion or dilation over all planes, each plane with its own shape and radius; a step whose radius is 0 for every
+// target is not launched.  Radii within 0 .. POSTPROCESS_MORPH_MAX_R.
+bool morph_is_default(const TargetTable &t);            // every target { RECT, 1, 0 }: the 3x3 kernels of image_stages.hip serve it
+hipError_t launch_morph_chain(uint8_t *a, uint8_t *b, int planes, int H, int W, const TargetTable &t, uint8_t **result, hipStream_t s);
 
 // Device form of Mask2Polygon::extract_contours (reference: src/mask2polygon.cpp:29-36 = threshold 127 +
 // findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)), exact point sequences and contour order.

@@ -348,6 +348,8 @@ static int segment_raw16_call(mi_unet_t *h, const char *name, bool multi, const 
     if (!raws || !widths || !heights || !masks || !xy || !start || !counts || B < 0 || cap_points <= 0 || cap_contours <= 0)
         return fail(MI_UNET_EARG, std::string("mi_unet_") + name + ": bad argument");
     const int H = h->cfg.height, W = h->cfg.width;
+    if (multi)
+        if (int rc = check_morph_list(h, (std::string("mi_unet_") + name).c_str())) return rc;
     const TargetTable tab = multi ? target_table(h, H, W) : default_targets(H, W);
     if ((size_t)std::min(B, h->cfg.max_batch) * tab.K * H * W > 0x7FFFFFFFull)
         return fail(MI_UNET_EARG, std::string(name) + ": max_batch x targets x height x width exceeds 2^31 - 1");

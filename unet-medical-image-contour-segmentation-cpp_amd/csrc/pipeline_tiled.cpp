@@ -32,6 +32,7 @@ struct TiledCall {
     float *logits;
     const mi_unet_target *targets; int K;  // segment: K >= 1 targets, out_u8 and the contour arrays are [K]...; K = 0: infer
     int32_t *xy; int cap_points; int32_t *start; int cap_contours; int32_t *count;
+    const mi_unet_morph *morph = nullptr; int n_morph = 0;     // segment: the targets' morphology, 1 or K entries; null: the 3x3 open
 };
 
 int ensure_tiled_buffers(mi_unet *h, size_t npix, bool want_logits, bool raw, bool blend)
@@ -120,7 +121,8 @@ int run_tiled_call(mi_unet *h, const TiledCall &c)
     // segment: the call's targets as K planes of the stitched image, min_area from the full image; infer: the label map itself,
     // postprocessed in place for the reference's target when mi_unet_set_postprocess is on
     const bool segment = c.K > 0;
-    const TargetTable tab = segment ? target_table(c.targets, c.K, H, W) : h->postprocess ? default_targets(H, W) : TargetTable{};
+    TargetTable tab = segment ? target_table(c.targets, c.K, H, W) : h->postprocess ? default_targets(H, W) : TargetTable{};
+    if (segment && c.morph) table_morph(tab, c.morph, c.n_morph);
     const int K = segment ? c.K : 1;
     const ContourLayout cl{ K, c.cap_points, c.cap_contours };
     // the full-size tail stages borrow the network's scratch buffer: checked before anything is enqueued
@@ -369,8 +371,10 @@ static int segment_tiled_call(mi_unet_t *h, const char *fn, bool multi, const ui
     if (int rc = check_planes(h, planes, fn)) return rc;
     if (!mask || !xy || !start || !count || cap_points <= 0 || cap_contours <= 0)
         return fail(MI_UNET_EARG, std::string(fn) + ": null output buffer or non-positive capacity");
+    if (multi)
+        if (int rc = check_morph_list(h, fn)) return rc;
     const TiledCall c{ fn, nullptr, planes, H, W, halo, norm, mask, nullptr, multi ? h->targets : &kDefaultTarget, multi ? h->n_targets : 1,
-                       xy, cap_points, start, cap_contours, count };
+                       xy, cap_points, start, cap_contours, count, multi ? h->morph : nullptr, multi ? h->n_morph : 0 };
     return run_tiled_call(h, c);
 }
 

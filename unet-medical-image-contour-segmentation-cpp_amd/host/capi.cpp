@@ -109,6 +109,28 @@ int medseg_get_targets(int *cls, float *min_area_frac, int cap)
     for (int i = 0; i < (int)t.size() && i < cap; ++i) { cls[i] = t[i].cls; min_area_frac[i] = t[i].min_area_frac; }
     return (int)t.size();
 }
+int medseg_postprocess_mask_morph(const uint8_t *mask, int w, int h, int cls, float min_area_frac, int shape, int open_r, int close_r,
+                                  uint8_t *out)
+{
+    try {
+        const Image8 r = postprocess_mask(wrap(mask, w, h), cls, min_area_frac, mi_unet_morph{ shape, open_r, close_r });
+        memcpy(out, r.data.data(), r.data.size());
+        return 0;
+    } catch (...) { return 1; }
+}
+int medseg_set_morphology(const int *shape, const int *open_r, const int *close_r, int n)
+{
+    if (n < 0) return 1;
+    std::vector<MedicalSeg::Morph> m;
+    for (int i = 0; i < n; ++i) m.push_back({ shape[i], open_r[i], close_r[i] });
+    return MedicalSeg::set_morphology(m) ? 0 : 1;
+}
+int medseg_get_morphology(int *shape, int *open_r, int *close_r, int cap)
+{
+    const std::vector<MedicalSeg::Morph> m = MedicalSeg::get_morphology();
+    for (int i = 0; i < (int)m.size() && i < cap; ++i) { shape[i] = m[i].shape; open_r[i] = m[i].open_r; close_r[i] = m[i].close_r; }
+    return (int)m.size();
+}
 int medseg_set_window(int mode, int clip_lo_ppm, int clip_hi_ppm, int lo, int hi)
 {
     return MedicalSeg::set_window(mi_unet_window{ mode, clip_lo_ppm, clip_hi_ppm, lo, hi }) ? 0 : 1;

@@ -144,6 +144,7 @@ public:
         table_["targets"] = [this](const Words &w) { cmd_targets(w); return true; };
         table_["window"] = [this](const Words &w) { cmd_window(w); return true; };
         table_["measure"] = [this](const Words &w) { cmd_measure(w); return true; };
+        table_["morph"] = [this](const Words &w) { cmd_morph(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -159,6 +160,7 @@ public:
             "  targets <cls:frac,...>|default - Classes to segment, each with its minimum area fraction (e.g. 1:0.01,2:0.06)",
             "  window percentile <lo_ppm> <hi_ppm>|fixed <lo> <hi>|default - Intensity window of the RAW input (default: min/max)",
             "  measure on [channel]|off      - Measure every contoured region on the device (a \"region\" object per shape of the JSON)",
+            "  morph rect|disc <open_r> [close_r]|default - Element and radii of the mask clean-up (default: rect 1 0, the 3x3 open)",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -314,6 +316,32 @@ private:
         }
         const mi_unet_measure cur = MedicalSeg::get_measure();
         std::cout << "Measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << std::endl;
+    }
+
+    // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)
+    void cmd_morph(const Words &w)
+    {
+        if (w.size() >= 2) {
+            std::vector<MedicalSeg::Morph> m;
+            bool ok = w[1] == "default" && w.size() == 2;
+            if (!ok && (w[1] == "rect" || w[1] == "disc") && (w.size() == 3 || w.size() == 4)) {
+                MedicalSeg::Morph e{ w[1] == "disc" ? MI_UNET_MORPH_DISC : MI_UNET_MORPH_RECT, 1, 0 };
+                ok = to_int(w[2], e.open_r) && (w.size() == 3 || to_int(w[3], e.close_r));
+                m.push_back(e);
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid morph command (expected rect|disc <open_r> [close_r] or default)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_morphology(m)) {
+                std::cerr << "Morphology unchanged" << std::endl;
+                return;
+            }
+        }
+        std::cout << "Morphology:";
+        for (const MedicalSeg::Morph &e : MedicalSeg::get_morphology())
+            std::cout << " " << (e.shape == MI_UNET_MORPH_DISC ? "disc" : "rect") << " " << e.open_r << " " << e.close_r;
+        std::cout << std::endl;
     }
 
     void cmd_exit()

@@ -43,6 +43,7 @@ int g_thread_batch = 1;            // micro-batch capacity of a per-thread conte
 unsigned long g_generation = 0;    // bumped by every (re)initialisation and cleanup: older thread contexts are stale
 mi_unet_measure g_measure{ 0, 0 };  // set_measure: outlives the engine, like the window
 std::vector<mi_unet_target> g_targets{ { 2, 0.06f } };   // set_targets: what process_single_image / process_image_batch segment
+std::vector<mi_unet_morph> g_morph{ { MI_UNET_MORPH_RECT, 1, 0 } };   // set_morphology: outlives the engine, like the window
 std::ofstream g_log_file;
 std::string g_log_path;
 std::mutex g_log_mutex;            // the reference's global log stream is written from any thread unguarded
@@ -156,6 +157,7 @@ bool initialize_engine(const std::string &trt_cache_path, const std::string &log
         const mi_unet_window window = Preprocess::get_window();            // the window in force outlives the engine
         if (up && mi_unet_group_set_window(g_group, &window) != MI_UNET_OK) up = false;
         if (up && mi_unet_group_set_measure(g_group, &g_measure) != MI_UNET_OK) up = false;      // (a channel this network does not have)
+        if (up && mi_unet_group_set_morph(g_group, g_morph.data(), (int)g_morph.size()) != MI_UNET_OK) up = false;
         if (!up) {
             g_log_file << "Error: Failed to initialize MI355X UNet engine: " << mi_unet_last_error() << std::endl;
             std::cerr << "Initialization error: " << mi_unet_last_error() << std::endl;
@@ -211,6 +213,40 @@ bool set_targets(const std::vector<Target> &targets)
         g_log_file << std::endl;
     }
     return true;
+}
+
+bool set_morphology(const std::vector<Morph> &morph)
+{
+    std::lock_guard<std::mutex> batch(g_batch_mutex);          // never under a running directory-mode call
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    // the engine's rules (mi_unet_set_morph), which do not depend on the network: checked here, so that no engine is needed
+    bool ok = morph.size() <= (size_t)MI_UNET_MAX_TARGETS;
+    for (const Morph &m : morph)
+        ok = ok && (m.shape == MI_UNET_MORPH_RECT || m.shape == MI_UNET_MORPH_DISC) && m.open_r >= 0 && m.open_r <= MI_UNET_MORPH_MAX_R &&
+             m.close_r >= 0 && m.close_r <= MI_UNET_MORPH_MAX_R;
+    if (ok && g_group && mi_unet_group_set_morph(g_group, morph.data(), (int)morph.size()) != MI_UNET_OK) ok = false;
+    if (!ok) {
+        std::cerr << "Error: morphology: at most " << MI_UNET_MAX_TARGETS << " entries of shape rect | disc with radii 0.." << MI_UNET_MORPH_MAX_R
+                  << std::endl;
+        return false;
+    }
+    if (g_lane2) (void)mi_unet_group_set_morph(g_lane2, morph.data(), (int)morph.size());
+    g_morph = morph;                                            // thread contexts take the setting before every call that reads it
+    if (g_morph.empty()) g_morph.push_back({ MI_UNET_MORPH_RECT, 1, 0 });
+    if (g_log_file.is_open()) {
+        std::lock_guard<std::mutex> ll(g_log_mutex);
+        g_log_file << "Morphology:";
+        for (const auto &m : g_morph)
+            g_log_file << " " << (m.shape == MI_UNET_MORPH_DISC ? "disc" : "rect") << " (open " << m.open_r << ", close " << m.close_r << ")";
+        g_log_file << std::endl;
+    }
+    return true;
+}
+
+std::vector<Morph> get_morphology()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    return g_morph;
 }
 
 bool set_window(const mi_unet_window &window)
@@ -273,6 +309,15 @@ std::vector<mi_unet_target> current_targets()
     return g_targets;
 }
 bool is_default(const std::vector<mi_unet_target> &t) { return t.size() == 1 && t[0].cls == 2 && t[0].min_area_frac == 0.06f; }
+std::vector<mi_unet_morph> current_morph()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    return g_morph;
+}
+bool is_default(const std::vector<mi_unet_morph> &m)
+{
+    return m.size() == 1 && m[0].shape == MI_UNET_MORPH_RECT && m[0].open_r == 1 && m[0].close_r == 0;
+}
 }  // namespace
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }
@@ -662,6 +707,7 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
                 const mi_unet_window window = Preprocess::get_window();       // a clone starts at the default
                 (void)mi_unet_group_set_window(g_lane2, &window);
                 (void)mi_unet_group_set_measure(g_lane2, &g_measure);
+                (void)mi_unet_group_set_morph(g_lane2, g_morph.data(), (int)g_morph.size());
                 lanes[1] = g_lane2; n_lanes = 2;
             }
         }
@@ -742,15 +788,20 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
     return ok;
 }
 
-// ---- a non-default target list (set_targets): K masks per image.  One plain route for both entry points: read the files of a chunk,
+// ---- a non-default target list (set_targets) or morphology (set_morphology): K masks per image, named <base>_mask_class<cls>.png, or
+// under the default target list the one <base>_mask.png.  One plain route for both entry points: read the files of a chunk,
 // one device call for the chunk (mi_unet_segment_raw16_multi on `ctx`, or its group form when ctx is null), then the artefacts image
 // by image.  With MEDSEG_HOST_POSTPROCESS / _CONTOURS = 1 the device call ends at the label maps and the CPU chain (postprocess_mask
 // per target, mask picture, extract_contours) takes over; MEDSEG_HOST_PREPROCESS has no effect here (the device's tile is the CPU's
 // bit for bit).  Returns the number of images that succeeded.
 int process_images_targets(const std::vector<std::string> &paths, const std::vector<int> &widths, const std::vector<int> &heights,
-                           const std::string &output_dir, mi_unet_t *ctx, const std::vector<mi_unet_target> &targets, std::ostream &lg)
+                           const std::string &output_dir, mi_unet_t *ctx, const std::vector<mi_unet_target> &targets,
+                           const std::vector<mi_unet_morph> &morph, std::ostream &lg)
 {
     const size_t n = paths.size(), hw = (size_t)g_cfg.height * g_cfg.width, K = targets.size();
+    if (morph.size() != 1 && morph.size() != K)
+        throw std::runtime_error("the morphology list has " + std::to_string(morph.size()) + " entries, the target list " + std::to_string(K));
+    const bool one_mask = is_default(targets);             // the artefact names follow the target list alone
     const int C = g_cfg.in_ch;
     mi_unet_group_t *group = ctx ? nullptr : get_engine_group();
     if (!ctx && !group) throw std::runtime_error("Engine not initialized");
@@ -823,10 +874,11 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                     } else {
                         Image8 lab(g_cfg.height, g_cfg.width, 1);
                         std::copy(labels.begin() + k * hw, labels.begin() + (k + 1) * hw, lab.data.begin());
-                        const Image8 pm = postprocess_mask(lab, targets[t].cls, targets[t].min_area_frac);
+                        const Image8 pm = postprocess_mask(lab, targets[t].cls, targets[t].min_area_frac, morph[morph.size() == 1 ? 0 : t]);
                         for (size_t p = 0; p < hw; ++p) vis.data[p] = pm.data[p] ? 255 : 0;
                     }
-                    if (!medseg::write_png(output_dir + "/" + base_name + "_mask_class" + std::to_string(targets[t].cls) + ".png", vis, /*level0=*/true))
+                    const std::string mask_name = one_mask ? "_mask.png" : "_mask_class" + std::to_string(targets[t].cls) + ".png";
+                    if (!medseg::write_png(output_dir + "/" + base_name + mask_name, vis, /*level0=*/true))
                         throw std::runtime_error("Failed to save mask");
                     // (the host chain leaves cnt at -1 and xy empty: the host tracer)
                     groups.push_back({ targets[t].cls, contours_of(xy.data() + (device_tail ? plane * (size_t)kCapPoints * 2 : 0),
@@ -862,11 +914,12 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         if (!group) throw std::runtime_error("Engine not initialized");
         const size_t n = raw_paths.size();
         if (widths.size() != n || heights.size() != n) throw std::runtime_error("widths/heights do not match raw_paths");
-        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets)) {
+        const std::vector<mi_unet_morph> morph = current_morph();
+        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets) || !is_default(morph)) {
             std::lock_guard<std::mutex> lk(g_batch_mutex);
             std::ostringstream lg;
             try {
-                ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, targets, lg);
+                ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, targets, morph, lg);
             } catch (...) {
                 if (log_file.is_open()) log_file << lg.str() << std::flush;
                 throw;
@@ -964,10 +1017,12 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
         const std::string base_name = fs::path(raw_path).stem().string();
         const auto total_start = std::chrono::high_resolution_clock::now();
 
-        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets)) {
-            // the thread's context is a clone (default targets): it takes the facade's list before every call
+        const std::vector<mi_unet_morph> morph = current_morph();
+        if (const std::vector<mi_unet_target> targets = current_targets(); !is_default(targets) || !is_default(morph)) {
+            // the thread's context is a clone (default targets and morphology): it takes the facade's lists before every call
             if (mi_unet_set_targets(ctx, targets.data(), (int)targets.size()) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            process_images_targets({ raw_path }, { width }, { height }, output_dir, ctx, targets, lg);
+            if (mi_unet_set_morph(ctx, morph.data(), (int)morph.size()) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            process_images_targets({ raw_path }, { width }, { height }, output_dir, ctx, targets, morph, lg);
         } else if (host_preprocess_requested()) {
             // the reference's own order: CPU preprocess -> PNG on disk -> read back -> inference (src/process.cpp:211-224)
             const std::string preprocessed_png_path = output_dir + "/" + base_name + "_normalized.png";

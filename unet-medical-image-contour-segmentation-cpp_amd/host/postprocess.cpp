@@ -1,6 +1,6 @@
 // postprocess.cpp -- label map -> cleaned {0,2} mask.  Reference: src/postprocess.cpp:5-79 (OpenCV there).
 // Own algorithms: run-based two-pass union-find labelling with per-component bbox/area (instead of one full-image
-// `labels == i` pass per component, the reference's O(nc*H*W) loops at :41 and :71), separable 3x3 min/max.
+// `labels == i` pass per component, the reference's O(nc*H*W) loops at :41 and :71), two-pass erosion / dilation by a box or disc.
 #include "../../include/medseg/postprocess.h"
 
 #include "../../include/mi_unet.h"
@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <numeric>
 #include <stdexcept>
+#include <string>
 
 namespace {
 
@@ -72,29 +73,39 @@ Labelling label8(const uint8_t *fg, int w, int h)
     return L;
 }
 
-// 3x3 rectangular erode (is_max = false) / dilate (true); windows are clipped to the image (OpenCV's default morphology
-// border never constrains an erosion and never seeds a dilation).
-void morph3x3(const std::vector<uint8_t> &src, std::vector<uint8_t> &dst, int w, int h, bool is_max)
+// One erosion (dilate = false) or dilation of a 0 / 255 plane by the box or disc of radius r, in two passes.  A stopper is
+// a background pixel for an erosion, a foreground pixel for a dilation; positions outside the image are never stoppers (OpenCV's
+// default morphology border never constrains an erosion and never seeds a dilation).  Pass 1, down and up every column: g = distance
+// to the nearest stopper of the column within r, else r + 1.  Pass 2, along the rows: the pixel is hit when some |dx| <= r inside the
+// image has g <= r (box) or g * g + dx * dx <= r * r (disc).  An erosion keeps what is not hit, a dilation sets what is.
+void morph_step(const std::vector<uint8_t> &src, std::vector<uint8_t> &dst, int w, int h, int shape, int r, bool dilate)
 {
-    std::vector<uint8_t> tmp(src.size());
-    auto pick = [is_max](uint8_t a, uint8_t b) { return is_max ? std::max(a, b) : std::min(a, b); };
-    for (int y = 0; y < h; ++y) {
-        const uint8_t *s = &src[(size_t)y * w];
-        uint8_t *t = &tmp[(size_t)y * w];
-        for (int x = 0; x < w; ++x) {
-            uint8_t v = s[x];
-            if (x) v = pick(v, s[x - 1]);
-            if (x + 1 < w) v = pick(v, s[x + 1]);
-            t[x] = v;
+    if (r == 0) { dst = src; return; }
+    std::vector<uint8_t> g((size_t)w * h);
+    for (int x = 0; x < w; ++x) {
+        int d = r + 1;
+        for (int y = 0; y < h; ++y) {
+            const bool stop = (src[(size_t)y * w + x] != 0) == dilate;
+            d = stop ? 0 : std::min(d + 1, r + 1);
+            g[(size_t)y * w + x] = (uint8_t)d;
+        }
+        d = r + 1;
+        for (int y = h - 1; y >= 0; --y) {
+            const bool stop = (src[(size_t)y * w + x] != 0) == dilate;
+            d = stop ? 0 : std::min(d + 1, r + 1);
+            g[(size_t)y * w + x] = (uint8_t)std::min<int>(g[(size_t)y * w + x], d);
         }
     }
-    dst.resize(src.size());
+    dst.assign(src.size(), 0);
+    const bool disc = shape == MI_UNET_MORPH_DISC;
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
-            uint8_t v = tmp[(size_t)y * w + x];
-            if (y) v = pick(v, tmp[(size_t)(y - 1) * w + x]);
-            if (y + 1 < h) v = pick(v, tmp[(size_t)(y + 1) * w + x]);
-            dst[(size_t)y * w + x] = v;
+            bool hit = false;
+            for (int xx = std::max(0, x - r); xx <= std::min(w - 1, x + r) && !hit; ++xx) {
+                const int gv = g[(size_t)y * w + xx], dx = xx - x;
+                hit = disc ? gv * gv + dx * dx <= r * r : gv <= r;
+            }
+            dst[(size_t)y * w + x] = hit == dilate ? 255 : 0;
         }
 }
 
@@ -104,6 +115,14 @@ medseg::Image8 postprocess_mask(const medseg::Image8 &src) { return postprocess_
 
 medseg::Image8 postprocess_mask(const medseg::Image8 &src, int cls, float min_area_frac)
 {
+    return postprocess_mask(src, cls, min_area_frac, mi_unet_morph{ MI_UNET_MORPH_RECT, 1, 0 });
+}
+
+medseg::Image8 postprocess_mask(const medseg::Image8 &src, int cls, float min_area_frac, const mi_unet_morph &morph)
+{
+    if ((morph.shape != MI_UNET_MORPH_RECT && morph.shape != MI_UNET_MORPH_DISC) || morph.open_r < 0 || morph.open_r > MI_UNET_MORPH_MAX_R ||
+        morph.close_r < 0 || morph.close_r > MI_UNET_MORPH_MAX_R)
+        throw std::runtime_error("postprocess_mask: unknown shape or radius outside 0.." + std::to_string(MI_UNET_MORPH_MAX_R));
     if (src.empty() || src.channels != 1) throw std::runtime_error("postprocess_mask: need a non-empty single-channel mask");
     if (cls < 1 || cls > 255) throw std::runtime_error("postprocess_mask: class outside 1..255");
     const uint8_t fgv = (uint8_t)cls;
@@ -125,11 +144,13 @@ medseg::Image8 postprocess_mask(const medseg::Image8 &src, int cls, float min_ar
         for (size_t i = 0; i < n; ++i)
             if (L.labels[i] && fill[L.labels[i]]) mask[i] = fgv;
     }
-    // 2. binarise + 3x3 open
-    std::vector<uint8_t> bin(n), er, op;
+    // 2. binarise, close (dilate, erode), open (erode, dilate): the reference's is the 3x3 open alone
+    std::vector<uint8_t> bin(n), tmp, op;
     for (size_t i = 0; i < n; ++i) bin[i] = mask[i] == fgv ? 255 : 0;
-    morph3x3(bin, er, w, h, false);
-    morph3x3(er, op, w, h, true);
+    morph_step(bin, tmp, w, h, morph.shape, morph.close_r, true);
+    morph_step(tmp, bin, w, h, morph.shape, morph.close_r, false);
+    morph_step(bin, tmp, w, h, morph.shape, morph.open_r, false);
+    morph_step(tmp, op, w, h, morph.shape, morph.open_r, true);
     // 3. area filter, 4. map back to {0, cls}
     const Labelling L = label8(op.data(), w, h);
     medseg::Image8 out(h, w, 1, 0);

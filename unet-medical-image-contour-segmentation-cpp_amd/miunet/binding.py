@@ -32,6 +32,7 @@ EXPORTS = [
     "mi_unet_set_window", "mi_unet_get_window", "mi_unet_window_of", "mi_unet_last_windows", "mi_unet_group_set_window",
     "mi_unet_set_measure", "mi_unet_get_measure", "mi_unet_last_regions", "mi_unet_measure_regions", "mi_unet_region_derive",
     "mi_unet_group_set_measure", "mi_unet_group_last_regions",
+    "mi_unet_set_morph", "mi_unet_get_morph", "mi_unet_morph_element", "mi_unet_group_set_morph",
 ]
 
 
@@ -64,6 +65,10 @@ class TileBlend(C.Structure):
 
 class Target(C.Structure):
     _fields_ = [("cls", C.c_int), ("min_area_frac", C.c_float)]
+
+
+class Morph(C.Structure):
+    _fields_ = [("shape", C.c_int), ("open_r", C.c_int), ("close_r", C.c_int)]
 
 
 class Window(C.Structure):
@@ -111,6 +116,18 @@ def _window(mode, clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
 
 MAX_TARGETS = 5
 DEFAULT_TARGETS = [(2, 0.06)]
+MORPH_SHAPES = {"rect": 0, "disc": 1}
+MORPH_MAX_R = 31
+DEFAULT_MORPH = [("rect", 1, 0)]
+
+
+def _morph_array(morph):
+    """[(shape, open_r, close_r), ...], shape by name (MORPH_SHAPES) or as the raw C value -> (Morph array or None, n); None restores the
+    default.  The library checks the values."""
+    if morph is None:
+        return None, 0
+    morph = list(morph)
+    return (Morph * max(len(morph), 1))(*[Morph(MORPH_SHAPES[s] if isinstance(s, str) else int(s), int(o), int(c)) for s, o, c in morph]), len(morph)
 
 
 def _target_array(targets):
@@ -232,6 +249,10 @@ def lib():
         L.mi_unet_region_derive.argtypes = [C.POINTER(Region), C.POINTER(RegionShape)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
+        L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
+        L.mi_unet_get_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int, C.POINTER(C.c_int)]
+        L.mi_unet_morph_element.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.mi_unet_group_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
         _LIB = L
     return _LIB
 
@@ -497,6 +518,18 @@ class Engine:
         _check(lib().mi_unet_get_targets(self._h, arr, MAX_TARGETS, C.byref(n)))
         return [(arr[k].cls, float(arr[k].min_area_frac)) for k in range(n.value)]
 
+    # ---- morphology (mi_unet_set_morph): element and radii of the close / open of the _multi calls, one entry or one per target
+    def set_morph(self, morph):
+        """morph: [(shape, open_r, close_r), ...] with shape "rect" | "disc"; None or [] restores the default [("rect", 1, 0)]"""
+        arr, n = _morph_array(morph)
+        _check(lib().mi_unet_set_morph(self._h, arr, n))
+
+    def get_morph(self):
+        arr, n = (Morph * MAX_TARGETS)(), C.c_int()
+        _check(lib().mi_unet_get_morph(self._h, arr, MAX_TARGETS, C.byref(n)))
+        names = {v: k for k, v in MORPH_SHAPES.items()}
+        return [(names[arr[k].shape], arr[k].open_r, arr[k].close_r) for k in range(n.value)]
+
     def postprocess_masks_multi(self, labels: np.ndarray):
         """labels u8 [B,H,W] -> u8 [B,K,H,W], plane k in {0, cls_k}"""
         labels = np.ascontiguousarray(labels, np.uint8)
@@ -680,6 +713,13 @@ def _decode_multi(xy, start, counts):
              for k in range(counts.shape[1])] for i in range(counts.shape[0])]
 
 
+def morph_element(shape, r: int) -> np.ndarray:
+    """mi_unet_morph_element: the structuring element as u8 [2r + 1, 2r + 1] of 0 / 1 (needs no device)"""
+    elem = np.zeros((2 * max(int(r), 0) + 1,) * 2, np.uint8)
+    _check(lib().mi_unet_morph_element(MORPH_SHAPES[shape] if isinstance(shape, str) else int(shape), int(r), _ptr(elem)))
+    return elem
+
+
 def target_min_area(height: int, width: int, frac: float) -> int:
     """mi_unet_target_min_area: the pixel count behind a target's min_area_frac on a height x width image (needs no device)"""
     return int(lib().mi_unet_target_min_area(height, width, frac))
@@ -786,6 +826,11 @@ class Group:
         """Engine.set_targets on every rank"""
         arr, n = _target_array(targets)
         _check(lib().mi_unet_group_set_targets(self._g, arr, n))
+
+    def set_morph(self, morph):
+        """Engine.set_morph on every rank (all or none)"""
+        arr, n = _morph_array(morph)
+        _check(lib().mi_unet_group_set_morph(self._g, arr, n))
 
     def set_window(self, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=65535):
         """Engine.set_window on every rank"""

@@ -20,7 +20,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_write_png", "medseg_read_png", "medseg_postprocess_mask_target", "medseg_set_targets", "medseg_get_targets",
            "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
-           "medseg_set_measure", "medseg_get_measure", "medseg_polygon_json_text_regions"]
+           "medseg_set_measure", "medseg_get_measure", "medseg_polygon_json_text_regions",
+           "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology"]
 
 
 def lib():
@@ -63,6 +64,9 @@ def lib():
         L.medseg_get_measure.restype = None
         L.medseg_polygon_json_text_regions.argtypes = [_i32, _i32, _i, _i, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_int,
                                                        C.c_int, C.c_char_p, C.c_int]
+        L.medseg_postprocess_mask_morph.argtypes = [_u8, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _u8]
+        L.medseg_set_morphology.argtypes = [_i, _i, _i, C.c_int]
+        L.medseg_get_morphology.argtypes = [_i, _i, _i, C.c_int]
         _LIB = L
     return _LIB
 
@@ -98,6 +102,36 @@ def postprocess_mask_target(mask, cls, min_area_frac):
     if lib().medseg_postprocess_mask_target(m, m.shape[1], m.shape[0], int(cls), float(min_area_frac), out):
         raise RuntimeError("postprocess_mask failed")
     return out
+
+
+MORPH_SHAPES = {"rect": 0, "disc": 1}
+
+
+def _shape(shape):
+    return MORPH_SHAPES[shape] if isinstance(shape, str) else int(shape)
+
+
+def postprocess_mask_morph(mask, cls, min_area_frac, shape="rect", open_r=1, close_r=0):
+    """postprocess_mask(src, cls, min_area_frac, morph): the chain with a close / open by a box or disc, u8 [h][w] in {0, cls}"""
+    m = np.ascontiguousarray(mask, np.uint8)
+    out = np.empty_like(m)
+    if lib().medseg_postprocess_mask_morph(m, m.shape[1], m.shape[0], int(cls), float(min_area_frac), _shape(shape), int(open_r), int(close_r), out):
+        raise RuntimeError("postprocess_mask failed")
+    return out
+
+
+def set_morphology(morph) -> bool:
+    """MedicalSeg::set_morphology: [(shape, open_r, close_r), ...], one entry or one per target; [] restores the default; needs no engine"""
+    n = len(morph)
+    cols = [(C.c_int * max(n, 1))(*[int(v) for v in col]) for col in ([_shape(s) for s, _, _ in morph], [o for _, o, _ in morph], [c for _, _, c in morph])]
+    return lib().medseg_set_morphology(cols[0], cols[1], cols[2], n) == 0
+
+
+def get_morphology():
+    s, o, c = (C.c_int * 8)(), (C.c_int * 8)(), (C.c_int * 8)()
+    n = lib().medseg_get_morphology(s, o, c, 8)
+    names = {v: k for k, v in MORPH_SHAPES.items()}
+    return [(names[s[i]], o[i], c[i]) for i in range(n)]
 
 
 def _flatten_groups(groups):
