@@ -60,6 +60,17 @@ mi_unet_window get_window();
 bool set_measure(bool on, int channel = 0);
 mi_unet_measure get_measure();
 
+// Scores against ground truth (mi_unet_score_labels in include/mi_unet.h).  With a truth directory set, the two process
+// functions look for <dir>/<base>_labels.raw per image: headerless u8 [H][W] class indices at the engine's tile size.  When it is there
+// and holds exactly H * W bytes, the final mask of every target is scored against it (the mask as {0, cls}, the truth as == cls), in
+// one mi_unet_score_labels call per device call of the batch, and <base>_score.json is written: "quantile_ppm" and per target "label",
+// "tp", "fp", "fn", "dice", "iou", "hd", "hd_q", "assd", "rmsd", the distance metrics null when undefined.  A missing file is a log
+// line and no score file, a file of another size a warning on stderr and no score file; neither fails the image.  An empty string
+// turns it off, which is the default: then every artefact and every log line is what it always was.  Needs no engine and survives
+// initialize_engine.  MEDSEG_HOST_POSTPROCESS=1 scores with mi_unet_score_labels_host; the routes with a host tail score image by image.
+bool set_truth_dir(const std::string &dir);
+std::string get_truth_dir();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

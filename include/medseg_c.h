@@ -54,6 +54,10 @@ int medseg_resample_normalize_window(const uint16_t *src, int w, int h, int lo, 
  * derived (area < 1). */
 int medseg_set_measure(int on, int channel);
 void medseg_get_measure(int *on, int *channel);
+/* Scores against ground truth: MedicalSeg::set_truth_dir / get_truth_dir.  NULL or "" turns it off (the default); 0 on success.
+ * medseg_get_truth_dir copies the directory (no terminator) into out and returns its length, or -1 when cap is too small. */
+int medseg_set_truth_dir(const char *dir);
+int medseg_get_truth_dir(char *out, int cap);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

@@ -360,6 +360,72 @@ int mi_unet_measure_regions(mi_unet_t *h, const uint8_t *masks, const uint8_t *t
                             int B, int channel, mi_unet_region *regions, int cap_contours, int32_t *counts);
 int mi_unet_region_derive(const mi_unet_region *r, mi_unet_region_shape *out);   /* EARG for area < 1 or NULL */
 
+/* ---- Scores against ground truth: overlap and surface distance per class, on the device ---------------------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.
+ * Inputs are two byte maps pred and truth, each u8 [B][H][W], and n byte values, 1 <= n <= MI_UNET_SCORE_MAX_VALUES.  H and W are
+ * arguments, not the engine's tile size (tiled results are full-size).  Plane (b, k) compares the sets A = { pred == values[k] } and
+ * T = { truth == values[k] } of image b.  That covers label maps (values = class indices), the {0, cls} masks of the tail
+ * (values = { cls }) and 0 / 255 pictures (values = { 255 }, the truth coded alike).
+ *   OVERLAP   tp = |A n T|, fp = |A \ T|, fn = |T \ A|.  Always valid.
+ *   BOUNDARY  dS = every pixel of S with a 4-neighbour that is not in S; positions outside the image are not in S, so a set that
+ *             touches the frame has boundary there (the frame rule of mi_unet_region.edges).  It is S & ~binary_erosion(S) with
+ *             scipy's default cross and border_value = 0: the surface medpy measures.
+ *   DISTANCE  between pixel centres, kept SQUARED, in integers, no radius cap: for p in dA, d2(p) = min over q in dT of |p - q|^2
+ *             (direction a_to_t), and likewise from dT to dA (t_to_a).  Per direction: n = boundary pixels of the source set,
+ *             max_d2 = the directed Hausdorff distance squared, sum_d2 = the sum of d2, sum_d_q16 = the sum of floor(2^16 sqrt(d2)),
+ *             every term the exact integer floor (an integer square root of d2 << 32), so the sum does not depend on the order of
+ *             addition and is bit-reproducible.
+ *   ORDER STATISTIC  by the convention of the window section: with the direction's n values sorted ascending as s[0 .. n - 1] and
+ *             k = floor(n * quantile_ppm / 1000000) in 64-bit integers, q_d2 = s[n - 1 - k].  0 ppm is max_d2; 50000 is the "HD95" cut.
+ *             q_d2_sym is the same statistic over both directions' values together (n = n_a + n_t): the multiset medpy's hd95 takes
+ *             its percentile over.  It is an ORDER STATISTIC, exact, found by a radix select -- never an interpolated percentile:
+ *             numpy.percentile interpolates between neighbours and can differ from it by up to their gap.
+ *   EMPTY     when dA or dT is empty both n fields still hold the counts, every max_d2, q_d2 and q_d2_sym is -1 and the sums are 0.
+ * Limits: H, W in 1 .. 32767 (so d2 <= 2 * 32766^2 < 2^31), B * n * H * W < 2^31 and B * n <= MI_UNET_SCORE_MAX_PLANES = 32767 planes in
+ * one call (the device form numbers its workgroups per plane and row in 31 bits).  No field can overflow under them: a direction has
+ * at most H * W < 2^30 values (H * W <= B * n * H * W), so sum_d2 < 2^30 * 2^31 = 2^61 and sum_d_q16 < 2^30 * 2^16 * 2^15.5 < 2^62.
+ * The confusion matrix (optional; opts->classes in 1 .. MI_UNET_SCORE_MAX_CLASSES, confusion and skipped not NULL): int64 [B][classes][classes], row = the
+ * truth byte, column = the pred byte; pixels where either byte is >= classes are left out of it and counted in int64 skipped[B], so
+ * an image's entries plus its skipped always sum to H * W.
+ * mi_unet_score_labels takes host buffers, like mi_unet_measure_regions; its workspace grows on demand and belongs to the handle.  It
+ * needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing mi_unet_last_regions or
+ * mi_unet_last_stage_ms report.  opts == NULL is { 50000, 0 }.  MI_UNET_EARG with a message, nothing queued and no output written: a
+ * null pred, truth, values or scores; B < 1; n outside 1 .. MI_UNET_SCORE_MAX_VALUES; a value outside 0 .. 255 or repeated;
+ * quantile_ppm outside 0 .. 999999; classes outside 0 .. 16; more than MI_UNET_SCORE_MAX_PLANES planes; confusion given with classes == 0 or without skipped; H, W or
+ * B * n * H * W outside the limits.  confusion == NULL skips the matrix whatever classes says.
+ * mi_unet_score_labels_host is the definition as pure host arithmetic (needs no device), same arguments without the handle, same bytes.
+ * mi_unet_score_derive is pure host arithmetic; MI_UNET_EARG for a null pointer.  A ratio whose denominator is 0 is 1 -- nothing was
+ * there and nothing was claimed, a perfect score -- for all four:
+ *   dice = 2 tp / (2 tp + fp + fn), iou = tp / (tp + fp + fn), precision = tp / (tp + fp), recall = tp / (tp + fn);
+ *   hd = sqrt(max(a_to_t.max_d2, t_to_a.max_d2)), hd_q = sqrt(q_d2_sym);
+ *   assd = (a_to_t.sum_d_q16 + t_to_a.sum_d_q16) / 65536 / (n_a + n_t), rmsd = sqrt((a_to_t.sum_d2 + t_to_a.sum_d2) / (n_a + n_t)).
+ * The four distance metrics are NaN when the distance fields are -1.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_SCORE_MAX_VALUES 8
+#define MI_UNET_SCORE_MAX_CLASSES 16
+#define MI_UNET_SCORE_MAX_PLANES 32767
+typedef struct mi_unet_score_dir {   /* 32 bytes, no padding */
+    int32_t n;                       /* boundary pixels of the source set */
+    int32_t max_d2;                  /* directed Hausdorff distance, squared; -1 when either boundary is empty */
+    int32_t q_d2;                    /* the order statistic of the direction's d2 values; -1 likewise */
+    int32_t reserved;                /* 0 */
+    int64_t sum_d2;                  /* sum of d2 */
+    int64_t sum_d_q16;               /* sum of floor(2^16 sqrt(d2)) */
+} mi_unet_score_dir;
+typedef struct mi_unet_score {       /* 88 bytes, no padding */
+    int32_t tp, fp, fn;
+    int32_t q_d2_sym;                /* the order statistic over both directions' values together; -1 when either boundary is empty */
+    int32_t value, quantile_ppm;     /* echo of the plane's value and of the call's quantile */
+    mi_unet_score_dir a_to_t, t_to_a;
+} mi_unet_score;
+typedef struct mi_unet_score_opts { int quantile_ppm; int classes; } mi_unet_score_opts;   /* default { 50000, 0 }; classes = 0: no matrix */
+typedef struct mi_unet_score_metrics { double dice, iou, precision, recall, hd, hd_q, assd, rmsd; } mi_unet_score_metrics;
+int mi_unet_score_labels(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const int *values, int n,
+                         const mi_unet_score_opts *opts, mi_unet_score *scores /* [B][n] */, int64_t *confusion, int64_t *skipped);
+int mi_unet_score_labels_host(const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const int *values, int n,
+                              const mi_unet_score_opts *opts, mi_unet_score *scores /* [B][n] */, int64_t *confusion, int64_t *skipped);
+int mi_unet_score_derive(const mi_unet_score *s, mi_unet_score_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -133,6 +133,11 @@ struct mi_unet {
     std::vector<int32_t> last_region_counts;
     int last_region_planes = 0, last_region_cap = 0;
     bool last_regions_valid = false;
+    // mi_unet_score_labels: d_score = both maps, the scores and the kernels' workspace of one call; h_score = the pinned
+    // staging of the maps and of the results; grown on demand, never shared with a clone
+    miunet::DeviceBuf<uint8_t> d_score;
+    miunet::PinnedBuf<uint8_t> h_score;
+    size_t score_dev_cap = 0, score_host_cap = 0;   // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

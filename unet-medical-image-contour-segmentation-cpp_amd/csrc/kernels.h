@@ -1,10 +1,11 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 struct mi_unet_region;      // include/mi_unet.h
+struct mi_unet_score;
 
 namespace miunet {
 
@@ -265,5 +266,21 @@ hipError_t launch_trace_contours(int B, int H, int W, int *out_xy, int cap_point
 //   for a plane with more than cap_contours external components.  rcounts [planes] out: that number, or -1.  No workspace of its own.
 hipError_t launch_measure_regions(int planes, int H, int W, int K, const uint8_t *tiles, int in_ch, int channel,
                                   ::mi_unet_region *regions, int *rcounts, int cap_contours, void *ws, hipStream_t s);
+
+// Scores against ground truth (score.hip; include/mi_unet.h: mi_unet_score_labels).  pred, truth u8 [B][H][W] on the
+// device; plane b * n + k compares { pred == v[k] } with { truth == v[k] } of image b.  One launch sequence for all B * n planes:
+//   counts  : tp / fp / fn of every value and, with classes > 0, the confusion matrix -- both maps read once
+//   columns : per plane and set, the boundary and the uncapped vertical distance g to the nearest boundary pixel of the column
+//   rows    : at the source boundary pixels only, d2 = min over x' of (x - x')^2 + g(x', y)^2 with the whole row of g in LDS;
+//             maximum, sum of d2, sum of floor(2^16 sqrt(d2)), and the values themselves into the direction's list
+//   select  : the order statistic n - 1 - floor(n * ppm / 1e6) of either direction and of both together, 16 + 16-bit radix select
+// scores [B * n] out (device).  With classes > 0, *conf receives where the u64 [B][classes][classes] matrix and behind it the [B]
+// skipped counts lie inside the workspace.  Workspace: score_workspace_bytes(B, H, W, n, classes), not zeroed by the caller.
+// H, W in 1 .. 32767, B * n * H * W < 2^31.
+constexpr int SCORE_MAX_VALUES = 8;                     // = MI_UNET_SCORE_MAX_VALUES
+struct ScoreValues { int n = 0; int v[SCORE_MAX_VALUES] = {}; };
+size_t score_workspace_bytes(int B, int H, int W, int n, int classes);
+hipError_t launch_score(const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const ScoreValues &vals, int quantile_ppm,
+                        int classes, void *ws, ::mi_unet_score *scores, const unsigned long long **conf, hipStream_t s);
 
 }  // namespace miunet

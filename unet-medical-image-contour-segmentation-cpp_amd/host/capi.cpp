@@ -167,6 +167,14 @@ void medseg_get_measure(int *on, int *channel)
     const mi_unet_measure m = MedicalSeg::get_measure();
     *on = m.on; *channel = m.channel;
 }
+int medseg_set_truth_dir(const char *dir) { return MedicalSeg::set_truth_dir(dir ? dir : "") ? 0 : 1; }
+int medseg_get_truth_dir(char *out, int cap)
+{
+    const std::string s = MedicalSeg::get_truth_dir();
+    if (!out || (int)s.size() > cap) return -1;
+    memcpy(out, s.data(), s.size());
+    return (int)s.size();
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

@@ -145,6 +145,7 @@ public:
         table_["window"] = [this](const Words &w) { cmd_window(w); return true; };
         table_["measure"] = [this](const Words &w) { cmd_measure(w); return true; };
         table_["morph"] = [this](const Words &w) { cmd_morph(w); return true; };
+        table_["truth"] = [this](const Words &w) { cmd_truth(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -161,6 +162,7 @@ public:
             "  window percentile <lo_ppm> <hi_ppm>|fixed <lo> <hi>|default - Intensity window of the RAW input (default: min/max)",
             "  measure on [channel]|off      - Measure every contoured region on the device (a \"region\" object per shape of the JSON)",
             "  morph rect|disc <open_r> [close_r]|default - Element and radii of the mask clean-up (default: rect 1 0, the 3x3 open)",
+            "  truth <dir>|off               - Score every mask against <dir>/<base>_labels.raw into <base>_score.json (default: off)",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -316,6 +318,23 @@ private:
         }
         const mi_unet_measure cur = MedicalSeg::get_measure();
         std::cout << "Measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << std::endl;
+    }
+
+    // truth <dir> | truth off | truth (prints the setting in force)
+    void cmd_truth(const Words &w)
+    {
+        if (w.size() >= 2) {
+            if (w.size() != 2) {
+                std::cerr << "Error: Invalid truth command (expected <dir> or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_truth_dir(w[1] == "off" ? std::string() : w[1])) {
+                std::cerr << "Truth unchanged" << std::endl;
+                return;
+            }
+        }
+        const std::string cur = MedicalSeg::get_truth_dir();
+        std::cout << "Truth: " << (cur.empty() ? std::string("off") : cur) << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

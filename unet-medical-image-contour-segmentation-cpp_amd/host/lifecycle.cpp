@@ -12,8 +12,10 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <filesystem>
+#include <fstream>
 #include <future>
 #include <memory>
 #include <iostream>
@@ -44,6 +46,7 @@ unsigned long g_generation = 0;    // bumped by every (re)initialisation and cle
 mi_unet_measure g_measure{ 0, 0 };  // set_measure: outlives the engine, like the window
 std::vector<mi_unet_target> g_targets{ { 2, 0.06f } };   // set_targets: what process_single_image / process_image_batch segment
 std::vector<mi_unet_morph> g_morph{ { MI_UNET_MORPH_RECT, 1, 0 } };   // set_morphology: outlives the engine, like the window
+std::string g_truth_dir;           // set_truth_dir: empty = off; outlives the engine, like the morphology
 std::ofstream g_log_file;
 std::string g_log_path;
 std::mutex g_log_mutex;            // the reference's global log stream is written from any thread unguarded
@@ -294,6 +297,24 @@ mi_unet_measure get_measure()
     return g_measure;
 }
 
+bool set_truth_dir(const std::string &dir)
+{
+    std::lock_guard<std::mutex> batch(g_batch_mutex);          // never under a running directory-mode call
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    g_truth_dir = dir;
+    if (g_log_file.is_open()) {
+        std::lock_guard<std::mutex> ll(g_log_mutex);
+        g_log_file << "Truth: " << (dir.empty() ? std::string("off") : dir) << std::endl;
+    }
+    return true;
+}
+
+std::string get_truth_dir()
+{
+    std::lock_guard<std::mutex> lk(g_state_mutex);
+    return g_truth_dir;
+}
+
 std::vector<Target> get_targets()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -424,9 +445,107 @@ Image8 mask_to_image(const Image8 &mask)
 
 namespace {
 
-// One image after the device work is done: write the reference's artefacts and run the CPU tail of the pipeline.
+bool device_postprocess_requested();
+
+// ---- set_truth_dir: the final masks of one device call against <dir>/<base>_labels.raw (u8 class indices at the tile size).
+// masks holds plane (k, t) -- image k, target t, any non-zero byte = foreground -- at (k * K + t) * H * W; an empty base skips the
+// image.  Every plane is recoded to 0 / 1 on both sides (the mask; truth == cls_t), so that ONE mi_unet_score_labels call with
+// values = { 1 } on `h` scores all targets of all images that have a usable truth file (mi_unet_score_labels_host under
+// MEDSEG_HOST_POSTPROCESS=1, or without a handle).  Writes <base>_score.json per scored image.  A missing file is a log line, a file
+// of the wrong size a warning; neither fails the image, and nothing here throws.  Returns one note per image -- text for the log and
+// for stderr -- or nothing at all with the truth directory off.
+struct TruthNote { std::string lg, err; };
+
+std::string json_number(double v)
+{
+    if (!std::isfinite(v)) return "null";
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+std::vector<TruthNote> score_against_truth(mi_unet_t *h, const std::vector<std::string> &bases, const uint8_t *masks,
+                                           const std::vector<mi_unet_target> &targets, const std::string &output_dir)
+{
+    std::vector<TruthNote> notes;
+    const std::string dir = get_truth_dir();
+    if (dir.empty()) return notes;
+    notes.resize(bases.size());
+    try {
+        const size_t hw = (size_t)g_cfg.height * g_cfg.width, K = targets.size();
+        std::vector<size_t> good;
+        std::vector<uint8_t> pred, truth, buf(hw);
+        for (size_t k = 0; k < bases.size(); ++k) {
+            if (bases[k].empty()) continue;
+            const std::string path = dir + "/" + bases[k] + "_labels.raw";
+            std::error_code ec;
+            const auto size = fs::file_size(path, ec);
+            if (ec) {
+                notes[k].lg = "Truth: no " + path + ": not scored\n";
+                continue;
+            }
+            std::ifstream f(path, std::ios::binary);
+            if (size != hw || !f.read(reinterpret_cast<char *>(buf.data()), (std::streamsize)hw)) {
+                notes[k].err = "Warning: " + path + " holds " + std::to_string(size) + " bytes, a label map of the tile " + std::to_string(hw) +
+                               ": not scored\n";
+                notes[k].lg = notes[k].err;
+                continue;
+            }
+            for (size_t t = 0; t < K; ++t) {
+                const uint8_t *const m = masks + (k * K + t) * hw;
+                const size_t at = pred.size();
+                pred.resize(at + hw); truth.resize(at + hw);
+                for (size_t i = 0; i < hw; ++i) {
+                    pred[at + i] = m[i] ? 1 : 0;
+                    truth[at + i] = buf[i] == targets[t].cls ? 1 : 0;
+                }
+            }
+            good.push_back(k);
+        }
+        if (good.empty() || K == 0) return notes;
+        const int one = 1, planes = (int)(good.size() * K);
+        const mi_unet_score_opts opts{ 50000, 0 };
+        std::vector<mi_unet_score> scores((size_t)planes);
+        const int rc = (h && device_postprocess_requested())
+                           ? mi_unet_score_labels(h, pred.data(), truth.data(), planes, g_cfg.height, g_cfg.width, &one, 1, &opts, scores.data(), nullptr, nullptr)
+                           : mi_unet_score_labels_host(pred.data(), truth.data(), planes, g_cfg.height, g_cfg.width, &one, 1, &opts, scores.data(), nullptr, nullptr);
+        for (size_t g = 0; g < good.size(); ++g) {
+            TruthNote &note = notes[good[g]];
+            if (rc != MI_UNET_OK) {
+                note.err = note.lg = std::string("Warning: scoring failed: ") + mi_unet_last_error() + "\n";
+                continue;
+            }
+            std::ostringstream js;
+            js << "{\n  \"quantile_ppm\": " << opts.quantile_ppm << ",\n  \"targets\": [";
+            for (size_t t = 0; t < K; ++t) {
+                const mi_unet_score &sc = scores[g * K + t];
+                mi_unet_score_metrics m{};
+                (void)mi_unet_score_derive(&sc, &m);
+                js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"tp\": " << sc.tp << ", \"fp\": " << sc.fp << ", \"fn\": " << sc.fn
+                   << ", \"dice\": " << json_number(m.dice) << ", \"iou\": " << json_number(m.iou) << ", \"hd\": " << json_number(m.hd)
+                   << ", \"hd_q\": " << json_number(m.hd_q) << ", \"assd\": " << json_number(m.assd) << ", \"rmsd\": " << json_number(m.rmsd) << "}";
+            }
+            js << "\n  ]\n}\n";
+            const std::string out_path = output_dir + "/" + bases[good[g]] + "_score.json";
+            std::ofstream o(out_path, std::ios::binary);
+            o << js.str();
+            o.close();
+            if (!o) note.err = note.lg = "Warning: cannot write " + out_path + "\n";
+            else note.lg = "Score: " + out_path + "\n";
+        }
+    } catch (const std::exception &e) {
+        for (TruthNote &n : notes)
+            if (n.lg.empty()) n.err = n.lg = std::string("Warning: scoring failed: ") + e.what() + "\n";
+    }
+    return notes;
+}
+
+const std::vector<mi_unet_target> kReferenceTarget{ { 2, 0.06f } };
+
+// One image after the device work is done: write the reference's artefacts and run the CPU tail of the pipeline.  With a truth
+// directory the postprocessed mask is scored on `score_h` (under `score_lock` when given), the note going to `lg`.
 void finish_image(const std::string &raw_path, int width, int height, const std::string &output_dir, const Image8 &tile,
-                  Image8 pred_mask, bool already_postprocessed)
+                  Image8 pred_mask, bool already_postprocessed, mi_unet_t *score_h, std::mutex *score_lock, std::ostream *lg)
 {
     const std::string base_name = fs::path(raw_path).stem().string();
     const std::string preprocessed_png_path = output_dir + "/" + base_name + "_normalized.png";
@@ -437,6 +556,14 @@ void finish_image(const std::string &raw_path, int width, int height, const std:
     if (!already_postprocessed) pred_mask = postprocess_mask(pred_mask);
     if (!medseg::write_png(pred_mask_path, mask_to_image(pred_mask), /*level0=*/true))
         throw std::runtime_error("Failed to save mask");
+    if (!get_truth_dir().empty()) {
+        std::unique_lock<std::mutex> lk;
+        if (score_lock) lk = std::unique_lock<std::mutex>(*score_lock);
+        for (const TruthNote &note : score_against_truth(score_h, { base_name }, pred_mask.data.data(), kReferenceTarget, output_dir)) {
+            std::cerr << note.err << std::flush;
+            if (lg) *lg << note.lg << std::flush;
+        }
+    }
     Mask2Polygon::process_single_mask(pred_mask_path, output_dir, size_json_path, preprocessed_png_path, base_name);
 }
 
@@ -519,6 +646,7 @@ struct ChunkOut {
     std::vector<int32_t> xy, start, cnt;
     std::vector<mi_unet_region> regions;               // set_measure: [m][kCapContours] and [m] counts, else empty
     std::vector<int32_t> rcnt;
+    std::vector<TruthNote> truth;                      // set_truth_dir: one note per read file, else empty
     long long device_ms = 0;
 };
 
@@ -606,7 +734,8 @@ ChunkIn read_chunk(const std::vector<std::string> &paths, const std::vector<int>
     return in;
 }
 
-ChunkOut device_chunk(const ChunkIn &in, const std::vector<int> &widths, const std::vector<int> &heights, mi_unet_group_t *group)
+ChunkOut device_chunk(const ChunkIn &in, const std::vector<std::string> &paths, const std::vector<int> &widths, const std::vector<int> &heights,
+                      const std::string &output_dir, mi_unet_group_t *group)
 {
     ChunkOut out;
     std::vector<const uint16_t *> ptrs;
@@ -631,6 +760,11 @@ ChunkOut device_chunk(const ChunkIn &in, const std::vector<int> &widths, const s
                                     out.cnt.data()) != MI_UNET_OK)
         throw std::runtime_error(std::string("Inference failed: ") + mi_unet_last_error());
     fetch_regions(nullptr, group, m, out.regions, out.rcnt);
+    if (!get_truth_dir().empty()) {                    // one scoring call for the chunk, on the lane's first engine
+        std::vector<std::string> bases;
+        for (size_t k : out.idx) bases.push_back(fs::path(paths[in.first + k]).stem().string());
+        out.truth = score_against_truth(mi_unet_group_handle(group, 0), bases, out.labels.data(), kReferenceTarget, output_dir);
+    }
     if (C > 1) keep_channel0(tiles_c.data(), hw * m, C, out.tiles.data());
     out.device_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count();
     return out;
@@ -667,6 +801,10 @@ ChunkText artefact_chunk(const ChunkIn &in, const ChunkOut &out, const std::vect
             table.regions.resize(1);
             const bool measured = plane_regions(out.regions, out.rcnt, (size_t)k, out.cnt[k], table.regions[0]);
             Mask2Polygon::write_polygon_outputs(contours, tile, output_dir, base_name, widths[i], heights[i], con, measured ? &table : nullptr);
+            if (!out.truth.empty()) {
+                lg << out.truth[k].lg;
+                tx.err[k] += out.truth[k].err;
+            }
             lg << "Processing completed for: " << base_name << std::endl;
             done[k] = 1;
         } catch (const std::exception &e) {
@@ -774,9 +912,9 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
             }
         if ((int)dev_q.size() == n_lanes) retire_oldest();          // frees the lane this chunk will use (FIFO: chunk k - n_lanes)
         mi_unet_group_t *lane = lanes[k % n_lanes];
-        dev_q.push_back({ st, std::async(std::launch::async, [st, lane, &widths, &heights] {
+        dev_q.push_back({ st, std::async(std::launch::async, [st, lane, &paths, &widths, &heights, &output_dir] {
             try {
-                st->out = device_chunk(st->in, widths, heights, lane);
+                st->out = device_chunk(st->in, paths, widths, heights, output_dir, lane);
             } catch (const std::exception &e) {
                 st->dev_err = e.what();
             }
@@ -852,6 +990,7 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
         if (device_tail) fetch_regions(ctx, group, m * K, regions, rcnt);
         lg << "Inference time: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count()
            << " ms" << (m > 1 ? " for " + std::to_string(m) + " images" : std::string()) << std::endl;
+        std::vector<std::string> scored(m);            // set_truth_dir: the images whose masks are complete
         for (size_t k = 0; k < m; ++k) {
             const size_t i = idx[k];
             const std::string base_name = fs::path(paths[i]).stem().string();
@@ -876,6 +1015,7 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                         std::copy(labels.begin() + k * hw, labels.begin() + (k + 1) * hw, lab.data.begin());
                         const Image8 pm = postprocess_mask(lab, targets[t].cls, targets[t].min_area_frac, morph[morph.size() == 1 ? 0 : t]);
                         for (size_t p = 0; p < hw; ++p) vis.data[p] = pm.data[p] ? 255 : 0;
+                        std::copy(vis.data.begin(), vis.data.end(), masks.begin() + plane * hw);
                     }
                     const std::string mask_name = one_mask ? "_mask.png" : "_mask_class" + std::to_string(targets[t].cls) + ".png";
                     if (!medseg::write_png(output_dir + "/" + base_name + mask_name, vis, /*level0=*/true))
@@ -887,12 +1027,18 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                 }
                 Mask2Polygon::write_polygon_outputs(groups, tile, output_dir, base_name, widths[i], heights[i], std::cout, measured ? &table : nullptr);
                 if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
+                scored[k] = base_name;
                 ++ok;
             } catch (const std::exception &e) {
                 if (ctx) throw;
                 std::cerr << "Processing error: " << e.what() << std::endl;
                 lg << "Processing error: " << e.what() << std::endl;
             }
+        }
+        // one scoring call for the images of this device call (the group's first engine: the caller holds the batch lock)
+        for (const TruthNote &note : score_against_truth(ctx ? ctx : mi_unet_group_handle(group, 0), scored, masks.data(), targets, output_dir)) {
+            std::cerr << note.err << std::flush;
+            lg << note.lg;
         }
     }
     return ok;
@@ -986,7 +1132,8 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
                 Image8 tile(g_cfg.height, g_cfg.width, 1), mask(g_cfg.height, g_cfg.width, 1);
                 std::copy(tiles.begin() + k * hw, tiles.begin() + (k + 1) * hw, tile.data.begin());
                 std::copy(labels.begin() + k * hw, labels.begin() + (k + 1) * hw, mask.data.begin());
-                finish_image(raw_paths[i], widths[i], heights[i], output_dir, tile, std::move(mask), dev_post);
+                finish_image(raw_paths[i], widths[i], heights[i], output_dir, tile, std::move(mask), dev_post, mi_unet_group_handle(group, 0),
+                             &g_batch_mutex, log_file.is_open() ? &log_file : nullptr);
                 if (log_file.is_open()) log_file << "Processing completed for: " << fs::path(raw_paths[i]).stem().string() << std::endl;
                 ++ok;
             } catch (const std::exception &e) {
@@ -1054,7 +1201,7 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             const auto infer_ms = std::chrono::duration_cast<std::chrono::milliseconds>(
                                       std::chrono::high_resolution_clock::now() - infer_start).count();
             lg << "Inference time: " << infer_ms << " ms" << std::endl;
-            finish_image(raw_path, width, height, output_dir, gray_img, std::move(pred_mask), false);
+            finish_image(raw_path, width, height, output_dir, gray_img, std::move(pred_mask), false, ctx, nullptr, &lg);
         } else if (device_postprocess_requested() && device_contours_requested()) {
             // all-device route: RAW16 -> tile -> UNet -> postprocess_mask -> mask_to_image -> contours in ONE call on this
             // thread's context; the mapped file is copied once, into pinned staging; the five artefacts
@@ -1095,6 +1242,10 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             medseg::RegionTable table;
             table.regions.resize(1);
             const bool measured = plane_regions(regions, rcnt, 0, cnt, table.regions[0]);
+            for (const TruthNote &note : score_against_truth(ctx, { base_name }, vis.data.data(), kReferenceTarget, output_dir)) {
+                std::cerr << note.err << std::flush;
+                lg << note.lg;
+            }
             // artefacts: {normalized.png + sizes.json} || {mask.png} || {overlay.png + polygon json}
             const auto t_art = clk::now();
             double norm_ms = 0, mask_ms = 0, poly_ms = 0;
@@ -1155,7 +1306,7 @@ bool process_single_image(const std::string &raw_path, int width, int height, co
             const auto infer_ms = std::chrono::duration_cast<std::chrono::milliseconds>(
                                       std::chrono::high_resolution_clock::now() - infer_start).count();
             lg << "Inference time: " << infer_ms << " ms" << std::endl;
-            finish_image(raw_path, width, height, output_dir, tile, std::move(pred_mask), dev_post);
+            finish_image(raw_path, width, height, output_dir, tile, std::move(pred_mask), dev_post, ctx, nullptr, &lg);
         }
 
         const auto total_ms = std::chrono::duration_cast<std::chrono::milliseconds>(

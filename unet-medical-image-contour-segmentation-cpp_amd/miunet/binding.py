@@ -33,6 +33,7 @@ EXPORTS = [
     "mi_unet_set_measure", "mi_unet_get_measure", "mi_unet_last_regions", "mi_unet_measure_regions", "mi_unet_region_derive",
     "mi_unet_group_set_measure", "mi_unet_group_last_regions",
     "mi_unet_set_morph", "mi_unet_get_morph", "mi_unet_morph_element", "mi_unet_group_set_morph",
+    "mi_unet_score_labels", "mi_unet_score_labels_host", "mi_unet_score_derive",
 ]
 
 
@@ -92,6 +93,51 @@ class Measure(C.Structure):
 class RegionShape(C.Structure):
     _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("mean", C.c_double), ("std", C.c_double), ("major", C.c_double),
                 ("minor", C.c_double), ("theta", C.c_double)]
+
+
+class ScoreDir(C.Structure):
+    """mi_unet_score_dir: 32 bytes"""
+    _fields_ = [("n", C.c_int32), ("max_d2", C.c_int32), ("q_d2", C.c_int32), ("reserved", C.c_int32), ("sum_d2", C.c_int64),
+                ("sum_d_q16", C.c_int64)]
+
+
+class Score(C.Structure):
+    """mi_unet_score: 88 bytes; SCORE_DTYPE is the same layout for numpy (a_to_t, t_to_a are nested records)"""
+    _fields_ = [("tp", C.c_int32), ("fp", C.c_int32), ("fn", C.c_int32), ("q_d2_sym", C.c_int32), ("value", C.c_int32),
+                ("quantile_ppm", C.c_int32), ("a_to_t", ScoreDir), ("t_to_a", ScoreDir)]
+
+
+SCORE_DIR_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in ScoreDir._fields_])
+SCORE_DTYPE = np.dtype([(n, SCORE_DIR_DTYPE if t is ScoreDir else np.int32) for n, t in Score._fields_])
+SCORE_MAX_VALUES = 8
+SCORE_MAX_CLASSES = 16
+
+
+class ScoreOpts(C.Structure):
+    _fields_ = [("quantile_ppm", C.c_int), ("classes", C.c_int)]
+
+
+class ScoreMetrics(C.Structure):
+    _fields_ = [("dice", C.c_double), ("iou", C.c_double), ("precision", C.c_double), ("recall", C.c_double), ("hd", C.c_double),
+                ("hd_q", C.c_double), ("assd", C.c_double), ("rmsd", C.c_double)]
+
+
+def _score_call(fn, head, pred, truth, values, quantile_ppm, classes):
+    """mi_unet_score_labels (head = (handle,)) or its host form (head = ()): pred, truth u8 [B,H,W] (or [H,W]) -> SCORE_DTYPE
+    [B, n], and (confusion int64 [B, classes, classes], skipped int64 [B]) behind it when classes > 0.  The library checks the values."""
+    pred, truth = np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(truth, np.uint8)
+    if pred.ndim == 2:
+        pred, truth = pred[None], truth[None]
+    if pred.ndim != 3 or pred.shape != truth.shape:
+        raise ValueError(f"pred {pred.shape} and truth {truth.shape} must be two u8 [B,H,W] arrays of one shape")
+    b, hh, ww = pred.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    scores = np.zeros((b, max(vals.size, 1)), SCORE_DTYPE)
+    conf = np.zeros((b, classes, classes), np.int64) if classes > 0 else None
+    skipped = np.zeros(b, np.int64) if classes > 0 else None
+    _check(fn(*head, _ptr(pred), _ptr(truth), b, hh, ww, _ptr(vals), vals.size, C.byref(ScoreOpts(int(quantile_ppm), int(classes))),
+              _ptr(scores), _ptr(conf), _ptr(skipped)))
+    return (scores, conf, skipped) if classes > 0 else scores
 
 
 def _last_regions(fn, handle):
@@ -247,6 +293,10 @@ def lib():
         L.mi_unet_last_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi_unet_measure_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.mi_unet_region_derive.argtypes = [C.POINTER(Region), C.POINTER(RegionShape)]
+        L.mi_unet_score_labels_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_score_labels.argtypes = [C.c_void_p] + L.mi_unet_score_labels_host.argtypes
+        L.mi_unet_score_derive.argtypes = [C.POINTER(Score), C.POINTER(ScoreMetrics)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -622,6 +672,12 @@ class Engine:
         _check(lib().mi_unet_measure_regions(self._h, _ptr(masks), _ptr(tiles), b, int(channel), _ptr(regions), cap_contours, _ptr(counts)))
         return regions, counts
 
+    # ---- scores against ground truth (mi_unet_score_labels): needs the device, not the weights
+    def score_labels(self, pred, truth, values, quantile_ppm=50000, classes=0):
+        """pred, truth u8 [B,H,W] of any size, values = the bytes to compare -> SCORE_DTYPE [B, n]; with classes > 0 also the confusion
+        matrix int64 [B, classes, classes] (row = truth, column = pred) and the pixels left out of it, int64 [B]"""
+        return _score_call(lib().mi_unet_score_labels, (self._h,), pred, truth, values, quantile_ppm, classes)
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -731,6 +787,21 @@ def window_of(samples, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=655
     wlo, whi = C.c_int(), C.c_int()
     _check(lib().mi_unet_window_of(_ptr(a) if a.size else None, a.size, _window(mode, clip_lo_ppm, clip_hi_ppm, lo, hi), C.byref(wlo), C.byref(whi)))
     return wlo.value, whi.value
+
+
+def score_labels_host(pred, truth, values, quantile_ppm=50000, classes=0):
+    """mi_unet_score_labels_host: Engine.score_labels as pure host arithmetic (needs no device)"""
+    return _score_call(lib().mi_unet_score_labels_host, (), pred, truth, values, quantile_ppm, classes)
+
+
+def score_derive(score):
+    """mi_unet_score_derive of one score (a Score, or one SCORE_DTYPE record) -> dict of dice, iou, precision, recall, hd, hd_q, assd, rmsd"""
+    if not isinstance(score, Score):
+        dirs = [ScoreDir(*[int(score[d][n]) for n, _ in ScoreDir._fields_]) for d in ("a_to_t", "t_to_a")]
+        score = Score(*[int(score[n]) for n, _ in Score._fields_[:6]], *dirs)
+    out = ScoreMetrics()
+    _check(lib().mi_unet_score_derive(C.byref(score), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in ScoreMetrics._fields_}
 
 
 def region_derive(region):

@@ -20,7 +20,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_write_png", "medseg_read_png", "medseg_postprocess_mask_target", "medseg_set_targets", "medseg_get_targets",
            "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
-           "medseg_set_measure", "medseg_get_measure", "medseg_polygon_json_text_regions",
+           "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology"]
 
 
@@ -62,6 +62,8 @@ def lib():
         L.medseg_set_measure.argtypes = [C.c_int, C.c_int]
         L.medseg_get_measure.argtypes = [_i, _i]
         L.medseg_get_measure.restype = None
+        L.medseg_set_truth_dir.argtypes = [C.c_char_p]
+        L.medseg_get_truth_dir.argtypes = [C.c_char_p, C.c_int]
         L.medseg_polygon_json_text_regions.argtypes = [_i32, _i32, _i, _i, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_int,
                                                        C.c_int, C.c_char_p, C.c_int]
         L.medseg_postprocess_mask_morph.argtypes = [_u8, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _u8]
@@ -176,6 +178,17 @@ def polygon_json_text_regions(groups, regions, scale_x, scale_y, base_name, ow, 
 def set_measure(on=True, channel=0) -> bool:
     """MedicalSeg::set_measure: every shape of <base>.json gains a "region" object; needs no engine"""
     return lib().medseg_set_measure(int(bool(on)), int(channel)) == 0
+
+
+def set_truth_dir(path="") -> bool:
+    """MedicalSeg::set_truth_dir: score every processed image that has <path>/<base>_labels.raw into <base>_score.json; "" / None = off"""
+    return lib().medseg_set_truth_dir(os.fsencode(path) if path else b"") == 0
+
+
+def get_truth_dir() -> str:
+    buf = C.create_string_buffer(4096)
+    n = lib().medseg_get_truth_dir(buf, 4096)
+    return os.fsdecode(buf.raw[:n]) if n >= 0 else ""
 
 
 def get_measure():
