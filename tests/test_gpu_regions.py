@@ -359,3 +359,65 @@ def test_facade_writes_region_objects(tmp_path, monkeypatch):
     finally:
         hostlib.set_measure(False)
         hostlib.cleanup_resources()
+
+
+def test_settings_reach_the_second_lane_and_thread_contexts(tmp_path, monkeypatch):
+    """16 files is the smallest directory-mode call that creates the second device lane; with max_batch 2 it is 8 chunks alternating
+    between the lanes.  State `a` (measure on, a fixed window 0 .. 4400) is set before the engine exists, so the lane and the thread's
+    context are created after the settings and must take them at creation; `b` (measure off, min/max) and `c` (measure on, a 1 %
+    percentile window) are set after both exist.  In every state each of the five artefacts of file j is, byte for byte, that of
+    process_single_image -- the calling thread's context -- on its source.  The fixed window maps the levels 1360 / 2160 / 4080 of the
+    crafted images to 79 / 125 / 236, inside the same class bands (cuts at 60.5, 110.5, 160.5), so `a`'s tiles differ from `b`'s on
+    every image: a lane or a context that missed the window at its creation would write `b`'s.  On these images both ends of the grey
+    range hold far more than 1 % of the samples, so the window of `c` is the min/max window and `c`'s tiles are `b`'s (only the size JSON
+    names the window)."""
+    monkeypatch.setenv("MEDSEG_TILE_SIZE", "64")
+    monkeypatch.setenv("MEDSEG_MAX_BATCH", "2")
+    wpath = tmp_path / "eng" / "net.miw"
+    os.makedirs(wpath.parent)
+    wpath.write_bytes(blob(4))
+    rs = crafted(4)
+    for i, r in enumerate(rs):
+        r.tofile(tmp_path / f"src{i}.raw")
+    many, mw, mh = [], [], []
+    for j in range(16):
+        os.symlink(tmp_path / f"src{j % 4}.raw", tmp_path / f"m{j:02d}.raw")
+        many.append(str(tmp_path / f"m{j:02d}.raw")); mw.append(rs[j % 4].shape[1]); mh.append(rs[j % 4].shape[0])
+    tails = ["_normalized.png", "_original_sizes.json", "_mask.png", "_contour_overlay.png", ".json"]
+
+    def run(state):
+        """directory mode into <state>, the four sources one by one into <state>_single; -> the artefacts of both, by (name, tail)"""
+        batch, single = tmp_path / state, tmp_path / (state + "_single")
+        os.makedirs(batch), os.makedirs(single)
+        assert hostlib.process_image_batch(many, mw, mh, str(batch)) == 16
+        for i, r in enumerate(rs):
+            assert hostlib.process_single_image(str(tmp_path / f"src{i}.raw"), r.shape[1], r.shape[0], str(single))
+        assert len(os.listdir(batch)) == 16 * 5 and len(os.listdir(single)) == 4 * 5
+        got = {(j, t): (batch / f"m{j:02d}{t}").read_bytes() for j in range(16) for t in tails}
+        want = {(i, t): (single / f"src{i}{t}").read_bytes() for i in range(4) for t in tails}
+        for (j, t), data in got.items():
+            w = want[(j % 4, t)]
+            if t.endswith(".json"):                             # the documents name their file
+                w = w.replace(f"src{j % 4}.raw".encode(), f"m{j:02d}.raw".encode())
+            assert data == w, (state, j, t)
+        return got
+
+    assert hostlib.set_measure(True) and hostlib.set_window("fixed", lo=0, hi=4400)
+    try:
+        assert hostlib.initialize_engine(str(wpath), str(tmp_path / "log"))
+        a = run("a")
+        assert hostlib.set_measure(False) and hostlib.set_window("minmax")
+        b = run("b")
+        assert hostlib.set_measure(True) and hostlib.set_window("percentile", 10000, 10000)
+        c = run("c")
+        for j in range(16):
+            for got, measured in ((a, True), (b, False), (c, True)):
+                shapes = json.loads(got[(j, ".json")])["shapes"]
+                assert len(shapes) >= 1 and all(("region" in sh) == measured for sh in shapes), j
+            assert a[(j, "_normalized.png")] != b[(j, "_normalized.png")], j
+            assert b'"window_lo"' in c[(j, "_original_sizes.json")] and b'"window_lo"' not in b[(j, "_original_sizes.json")]
+            assert c[(j, "_normalized.png")] == b[(j, "_normalized.png")]
+    finally:
+        hostlib.set_measure(False)
+        hostlib.set_window("minmax")
+        hostlib.cleanup_resources()

@@ -349,3 +349,19 @@ def test_process_single_mask_end_to_end(tmp_path, capfd):
     assert "Mask size mismatch: 64x64 (actual) vs 512x512 (JSON)" in capfd.readouterr().err
     hostlib.process_single_mask(str(mp), str(d2), str(sizes), str(norm), "other")
     assert "Cannot Find Size Info in JSON: other.raw/.tif" in capfd.readouterr().err
+
+
+# ---------------------------------------------------------------- the per-image artefact writer of the facade
+def test_artefact_writer_as_a_stand_alone_program(tmp_path):
+    """tests/cpu/artefacts_test.cpp + host/artefacts.cpp and the host units it calls, built by a plain C++ compiler without the facade:
+    MedicalSeg::write_image_artefacts against the three writers called directly, for K = 1 (device arrays, concurrent, host tracer), K = 2
+    (regions for no plane, one plane, both) and an empty mask.  The form in which the writer runs under a sanitizer (its header)."""
+    pkg = os.path.dirname(hostlib.LIB_PATH)
+    exe, out = tmp_path / "artefacts_test", tmp_path / "out"
+    out.mkdir()
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-pthread", "-I", os.path.join(pkg, "host"), "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "artefacts_test.cpp")] +
+                          [os.path.join(pkg, "host", n + ".cpp") for n in ("artefacts", "png_io", "json_io", "mask2polygon", "preprocess", "postprocess")] +
+                          ["-L" + pkg, "-lmiunet", "-Wl,-rpath," + pkg, "-lz"])
+    r = subprocess.run([str(exe), str(out)], capture_output=True, timeout=300)
+    assert r.returncode == 0 and b"artefacts_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]

@@ -1,0 +1,86 @@
+// artefacts.cpp -- write_image_artefacts (artefacts.h): what every route of the facade does with a finished image (the facade's units:
+// routes.cpp).
+#include "artefacts.h"
+
+#include <chrono>
+#include <future>
+#include <stdexcept>
+
+#include "../../include/medseg/mask2polygon.h"
+#include "../../include/medseg/preprocess.h"
+#include "png_io.h"
+
+namespace MedicalSeg {
+
+static std::vector<medseg::Contour> contours_of(const PlaneShapes &p, const medseg::Image8 &vis)
+{
+    if (p.count < 0) return Mask2Polygon::extract_contours(vis);
+    std::vector<medseg::Contour> contours;
+    for (int c = 0; c < p.count; ++c) {
+        medseg::Contour cc;
+        for (int q = p.start[c]; q < p.start[c + 1]; ++q) cc.emplace_back(p.xy[2 * q], p.xy[2 * q + 1]);
+        contours.push_back(std::move(cc));
+    }
+    return contours;
+}
+
+ArtefactTimes write_image_artefacts(const ImageArtefacts &a)
+{
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    const std::vector<mi_unet_target> &targets = *a.targets;
+    const std::string stem = a.output_dir + "/" + a.base_name;
+    std::vector<medseg::ClassContours> groups;
+    medseg::RegionTable table;
+    table.regions.resize(targets.size());
+    bool measured = true;                                  // a table is used only when every plane has one
+    for (size_t t = 0; t < targets.size(); ++t) {
+        const PlaneShapes &p = a.planes[t];
+        groups.push_back({ targets[t].cls, contours_of(p, a.masks[t]) });
+        if (p.regions && p.count >= 0) table.regions[t].assign(p.regions, p.regions + p.count);
+        else measured = false;
+    }
+    ArtefactTimes times;
+    const auto t_all = clk::now();
+    auto normalized = [&] {
+        const auto t0 = clk::now();
+        const bool ok = Preprocess::write_preprocess_outputs(*a.tile, a.raw_path, stem + "_normalized.png", stem + "_original_sizes.json",
+                                                             a.width, a.height);
+        times.norm_ms = ms_since(t0);
+        return ok;
+    };
+    auto masks = [&] {
+        const auto t0 = clk::now();
+        bool ok = true;
+        for (size_t t = 0; t < targets.size() && ok; ++t)
+            ok = medseg::write_png(stem + (is_default(targets) ? "_mask.png" : "_mask_class" + std::to_string(targets[t].cls) + ".png"),
+                                   a.masks[t], /*level0=*/true);
+        times.mask_ms = ms_since(t0);
+        return ok;
+    };
+    auto polygons = [&] {
+        const auto t0 = clk::now();
+        if (a.class_lines)
+            Mask2Polygon::write_polygon_outputs(groups, *a.tile, a.output_dir, a.base_name, a.width, a.height, *a.console,
+                                                measured ? &table : nullptr);
+        else            // one group of the default class: the same files, the reference's console text
+            Mask2Polygon::write_polygon_outputs(groups[0].contours, *a.tile, a.output_dir, a.base_name, a.width, a.height, *a.console,
+                                                measured ? &table : nullptr);
+        times.poly_ms = ms_since(t0);
+    };
+    bool norm_ok, mask_ok = true;
+    if (a.concurrent) {
+        auto f_norm = std::async(std::launch::async, normalized);
+        auto f_mask = std::async(std::launch::async, masks);
+        polygons();
+        norm_ok = f_norm.get(); mask_ok = f_mask.get();
+    } else if ((norm_ok = normalized()) && (mask_ok = masks())) {
+        polygons();
+    }
+    times.total_ms = ms_since(t_all);
+    if (!norm_ok) throw std::runtime_error("Preprocessing failed");
+    if (!mask_ok) throw std::runtime_error("Failed to save mask");
+    return times;
+}
+
+}  // namespace MedicalSeg

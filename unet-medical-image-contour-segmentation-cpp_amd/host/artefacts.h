@@ -1,0 +1,44 @@
+// artefacts.h -- the five artefacts of one image whose device or host work is finished: <base>_normalized.png,
+// <base>_original_sizes.json, the mask picture(s), <base>_contour_overlay.png and <base>.json.  Pure host code: no device call, no
+// facade state (tests/cpu/artefacts_test.cpp builds it without the facade).
+#pragma once
+#include <ostream>
+#include <string>
+#include <vector>
+
+#include "../../include/medseg/image.h"
+
+namespace MedicalSeg {
+
+inline bool is_default(const std::vector<mi_unet_target> &t) { return t.size() == 1 && t[0].cls == 2 && t[0].min_area_frac == 0.06f; }
+
+// What a device call left for one mask plane: its slices of the call's xy / start arrays and its count.  A negative count -- a capacity
+// overflow on the device, or no device tracer at all -- hands the mask picture to the host tracer (xy and start are not read then).
+// `regions`, when the call measured this plane (MedicalSeg::set_measure), are the `count` records of its region report.
+struct PlaneShapes {
+    const int32_t *xy = nullptr, *start = nullptr;
+    int count = -1;
+    const mi_unet_region *regions = nullptr;
+};
+
+struct ImageArtefacts {
+    const medseg::Image8 *tile = nullptr;              // the grey tile the network read
+    const std::vector<mi_unet_target> *targets = nullptr;   // K targets: the default list names the one mask <base>_mask.png,
+    const medseg::Image8 *masks = nullptr;             //   any other list <base>_mask_class<cls>.png; K pictures, 0 / 255
+    const PlaneShapes *planes = nullptr;               // K entries, in target order
+    int width = 0, height = 0;                         // of the original image
+    std::string raw_path, output_dir, base_name;
+    std::ostream *console = nullptr;                   // the text of Mask2Polygon::write_polygon_outputs
+    bool class_lines = false;                          // that text counts the contours per class (the per-target routes), not in one line
+    bool concurrent = false;                           // the three groups below side by side (the single-image all-device route)
+};
+
+// milliseconds of the three artefact groups -- {normalized.png + sizes.json}, {mask pictures}, {overlay.png + polygon json} -- and of
+// all three from the first start to the last end; the contour lists are built before the clocks start
+struct ArtefactTimes { double norm_ms = 0, mask_ms = 0, poly_ms = 0, total_ms = 0; };
+
+// Writes them all.  The .json carries "region" objects only when every plane has regions.  Throws std::runtime_error("Preprocessing
+// failed") / ("Failed to save mask"); with `concurrent` only after all three groups have ended.
+ArtefactTimes write_image_artefacts(const ImageArtefacts &a);
+
+}  // namespace MedicalSeg

@@ -200,13 +200,6 @@ void draw_contours(Image8 &img, const std::vector<Contour> &contours, const uint
 }
 }  // namespace
 
-Image8 draw_overlay(const Image8 &src, const std::vector<Contour> &contours)
-{
-    Image8 img = to_bgr(src);
-    draw_contours(img, contours, kPalette[0]);
-    return img;
-}
-
 Image8 draw_overlay(const Image8 &src, const std::vector<medseg::ClassContours> &groups)
 {
     Image8 img = to_bgr(src);
@@ -214,15 +207,19 @@ Image8 draw_overlay(const Image8 &src, const std::vector<medseg::ClassContours> 
     return img;
 }
 
+Image8 draw_overlay(const Image8 &src, const std::vector<Contour> &contours) { return draw_overlay(src, { { 2, contours } }); }
+
 std::string polygon_json_text(const std::vector<medseg::ClassContours> &groups, const std::string &base_name, int original_width,
                               int original_height, const medseg::RegionTable *regions)
 {
     return medseg::polygon_json_text(groups, base_name, original_width, original_height, regions);
 }
 
-void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const Image8 &normalized_tile, const std::string &output_dir,
-                           const std::string &base_name, int original_width, int original_height, std::ostream &console,
-                           const medseg::RegionTable *regions)
+namespace {
+// both forms of write_polygon_outputs: `class_lines` counts the contours per class on the console, else in the reference's one line
+void write_polygons(const std::vector<medseg::ClassContours> &groups, const Image8 &normalized_tile, const std::string &output_dir,
+                    const std::string &base_name, int original_width, int original_height, std::ostream &console,
+                    const medseg::RegionTable *regions, bool class_lines)
 {
     try {
         console << "Processing Mask: " << base_name + ".png" << std::endl;
@@ -234,8 +231,14 @@ void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, con
             console << "Warning: No Contours Detected" << std::endl;
             return;
         }
-        for (const auto &g : groups) console << "Extracted " << g.contours.size() << " Contours of class " << g.cls << std::endl;
+        if (!class_lines) console << "Extracted " << total << " Contours" << std::endl;
+        else
+            for (const auto &g : groups) console << "Extracted " << g.contours.size() << " Contours of class " << g.cls << std::endl;
         const std::string overlay_path = output_dir + "/" + base_name + "_contour_overlay.png";
+        // stored blocks, like the two PNGs the reference itself writes with IMWRITE_PNG_COMPRESSION 0 (src/preprocess.cpp:116,
+        // src/process.cpp:233): the pixels are the contract, and deflating the 786 KB overlay was the longest artefact of the
+        // device route (1.1 ms of the 3.9 ms per image); create_overlay_image below -- the reference's own
+        // stand-alone mask2polygon entry point -- keeps cv::imwrite's default level 1
         if (!medseg::write_png(overlay_path, draw_overlay(normalized_tile, groups), /*level0=*/true))
             throw std::runtime_error("Fail to Save Overlay PNG: " + overlay_path);
         console << "Overlay Image Saved to: " << overlay_path << std::endl;
@@ -255,6 +258,22 @@ void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, con
         std::cerr << "Processing Failure: " << e.what() << std::endl;
     }
 }
+}  // namespace
+
+void write_polygon_outputs(const std::vector<medseg::ClassContours> &groups, const Image8 &normalized_tile, const std::string &output_dir,
+                           const std::string &base_name, int original_width, int original_height, std::ostream &console,
+                           const medseg::RegionTable *regions)
+{
+    write_polygons(groups, normalized_tile, output_dir, base_name, original_width, original_height, console, regions, true);
+}
+
+// the reference's single class: one group of class 2 is the same document and the same overlay, byte for byte (mask2polygon.h)
+void write_polygon_outputs(const std::vector<Contour> &contours, const Image8 &normalized_tile, const std::string &output_dir,
+                           const std::string &base_name, int original_width, int original_height,
+                           std::ostream &console, const medseg::RegionTable *regions)
+{
+    write_polygons({ { 2, contours } }, normalized_tile, output_dir, base_name, original_width, original_height, console, regions, false);
+}
 
 void create_overlay_image(const std::vector<Contour> &contours, const std::string &original_png_path,
                           const std::string &overlay_path)
@@ -263,46 +282,6 @@ void create_overlay_image(const std::vector<Contour> &contours, const std::strin
     if (img.empty()) throw std::runtime_error("Fail to Read Original Image: " + original_png_path);
     if (!medseg::write_png(overlay_path, draw_overlay(img, contours), /*level0=*/false))
         throw std::runtime_error("Fail to Save Overlay PNG: " + overlay_path);
-}
-
-void write_polygon_outputs(const std::vector<Contour> &contours, const Image8 &normalized_tile, const std::string &output_dir,
-                           const std::string &base_name, int original_width, int original_height,
-                           std::ostream &console, const medseg::RegionTable *regions)
-{
-    try {
-        console << "Processing Mask: " << base_name + ".png" << std::endl;
-        console << "Original Size: " << original_width << "x" << original_height << std::endl;
-        console << "Scaled Size: " << normalized_tile.cols << "x" << normalized_tile.rows << std::endl;
-        if (contours.empty()) {
-            console << "Warning: No Contours Detected" << std::endl;
-            return;
-        }
-        console << "Extracted " << contours.size() << " Contours" << std::endl;
-        const std::string overlay_path = output_dir + "/" + base_name + "_contour_overlay.png";
-        // stored blocks, like the two PNGs the reference itself writes with IMWRITE_PNG_COMPRESSION 0 (src/preprocess.cpp:116,
-        // src/process.cpp:233): the pixels are the contract, and deflating the 786 KB overlay was the longest artefact of the
-        // device route (1.1 ms of the 3.9 ms per image); create_overlay_image above -- the reference's own
-        // stand-alone mask2polygon entry point -- keeps cv::imwrite's default level 1
-        if (!medseg::write_png(overlay_path, draw_overlay(normalized_tile, contours), /*level0=*/true))
-            throw std::runtime_error("Fail to Save Overlay PNG: " + overlay_path);
-        console << "Overlay Image Saved to: " << overlay_path << std::endl;
-        const double scale_x = static_cast<double>(original_width) / normalized_tile.cols;
-        const double scale_y = static_cast<double>(original_height) / normalized_tile.rows;
-        const std::string output_json_path = output_dir + "/" + base_name + ".json";
-        if (regions) {          // measured: the same document (the reference's single class) with a "region" object per shape
-            medseg::RegionTable table{ regions->regions, scale_x, scale_y };
-            std::ofstream f(output_json_path);
-            if (!f.is_open()) throw std::runtime_error("Fail to Create JSON File: " + output_json_path);
-            f << medseg::polygon_json_text(std::vector<medseg::ClassContours>{ { 2, map_contour_points(contours, scale_x, scale_y) } }, base_name,
-                                           original_width, original_height, &table);
-            f.flush();
-        } else {
-            generate_json(map_contour_points(contours, scale_x, scale_y), output_json_path, base_name, original_width, original_height);
-        }
-        console << "JSON Saved to: " << output_json_path << std::endl;
-    } catch (const std::exception &e) {
-        std::cerr << "Processing Failure: " << e.what() << std::endl;
-    }
 }
 
 void process_single_mask(const std::string &mask_path, const std::string &output_dir, const std::string &json_path,

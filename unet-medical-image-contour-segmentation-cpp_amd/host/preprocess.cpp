@@ -62,17 +62,12 @@ private:
 
 namespace Preprocess {
 
-medseg::Image8 resample_normalize(const uint16_t *src, int w, int h, int outW, int outH)
+namespace {
+// the top-left-aligned bilinear resample in double (src/preprocess.cpp:81-118, the reference's operand order); `quantise` maps the
+// interpolant to the tile's byte
+template <class Quantise>
+medseg::Image8 resample(const uint16_t *src, int w, int h, int outW, int outH, Quantise quantise)
 {
-    const size_t n = (size_t)w * h;
-    uint16_t mn = 65535, mx = 0;
-#pragma omp parallel for reduction(min : mn) reduction(max : mx) schedule(static)
-    for (long long i = 0; i < (long long)n; ++i) {
-        mn = std::min(mn, src[i]);
-        mx = std::max(mx, src[i]);
-    }
-    if (mn == mx) mx = (uint16_t)(mn + 1);                       // src/preprocess.cpp:92 (wraps at 65535, kept)
-    const double scale8 = 255.0 / ((int)mx - (int)mn);
     const double stepX = (double)w / outW, stepY = (double)h / outH;
     medseg::Image8 dst(outH, outW, 1);
 #pragma omp parallel for schedule(static)
@@ -86,11 +81,25 @@ medseg::Image8 resample_normalize(const uint16_t *src, int w, int h, int outW, i
             const double fx = x * stepX;
             const int ix = (int)fx, ix1 = std::min(ix + 1, w - 1);
             const double dx = fx - ix;
-            const double v = (1 - dx) * (1 - dy) * r0[ix] + dx * (1 - dy) * r0[ix1] + (1 - dx) * dy * r1[ix] + dx * dy * r1[ix1];
-            o[x] = (uint8_t)(int)((v - mn) * scale8 + 0.5);
+            o[x] = quantise((1 - dx) * (1 - dy) * r0[ix] + dx * (1 - dy) * r0[ix1] + (1 - dx) * dy * r1[ix] + dx * dy * r1[ix1]);
         }
     }
     return dst;
+}
+}  // namespace
+
+medseg::Image8 resample_normalize(const uint16_t *src, int w, int h, int outW, int outH)
+{
+    const size_t n = (size_t)w * h;
+    uint16_t mn = 65535, mx = 0;
+#pragma omp parallel for reduction(min : mn) reduction(max : mx) schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        mn = std::min(mn, src[i]);
+        mx = std::max(mx, src[i]);
+    }
+    if (mn == mx) mx = (uint16_t)(mn + 1);                       // src/preprocess.cpp:92 (wraps at 65535, kept)
+    const double scale8 = 255.0 / ((int)mx - (int)mn);
+    return resample(src, w, h, outW, outH, [=](double v) { return (uint8_t)(int)((v - mn) * scale8 + 0.5); });
 }
 
 namespace {
@@ -123,25 +132,7 @@ medseg::Image8 resample_normalize_window(const uint16_t *src, int w, int h, int 
 {
     const int L = lo, Hh = hi > lo ? hi : lo + 1;                            // in int: nothing wraps
     const double dl = (double)L, dh = (double)Hh, scale8 = 255.0 / (Hh - L);
-    const double stepX = (double)w / outW, stepY = (double)h / outH;
-    medseg::Image8 dst(outH, outW, 1);
-#pragma omp parallel for schedule(static)
-    for (int y = 0; y < outH; ++y) {
-        const double fy = y * stepY;
-        const int iy = (int)fy, iy1 = std::min(iy + 1, h - 1);
-        const double dy = fy - iy;
-        const uint16_t *r0 = src + (size_t)iy * w, *r1 = src + (size_t)iy1 * w;
-        uint8_t *o = dst.ptr(y);
-        for (int x = 0; x < outW; ++x) {
-            const double fx = x * stepX;
-            const int ix = (int)fx, ix1 = std::min(ix + 1, w - 1);
-            const double dx = fx - ix;
-            const double v = (1 - dx) * (1 - dy) * r0[ix] + dx * (1 - dy) * r0[ix1] + (1 - dx) * dy * r1[ix] + dx * dy * r1[ix1];
-            const double vc = std::min(std::max(v, dl), dh);
-            o[x] = (uint8_t)(int)((vc - dl) * scale8 + 0.5);
-        }
-    }
-    return dst;
+    return resample(src, w, h, outW, outH, [=](double v) { return (uint8_t)(int)((std::min(std::max(v, dl), dh) - dl) * scale8 + 0.5); });
 }
 
 RawView::RawView(const std::string &raw_path, int w, int h)
@@ -154,9 +145,8 @@ RawView::RawView(const std::string &raw_path, int w, int h)
 
 std::vector<uint16_t> read_raw16(const std::string &raw_path, int w, int h)
 {
-    if (w <= 0 || h <= 0) throw std::runtime_error("width and height must be positive");
-    MappedFile file(raw_path, (size_t)w * h * 2);
-    return std::vector<uint16_t>(file.data(), file.data() + (size_t)w * h);
+    const RawView view(raw_path, w, h);
+    return std::vector<uint16_t>(view.data(), view.data() + view.samples());
 }
 
 bool write_preprocess_outputs(const medseg::Image8 &tile, const std::string &raw_path, const std::string &png_path,
