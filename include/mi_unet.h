@@ -487,6 +487,10 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
  * probe tile runs through the plan with every 3x3 layer on F(4x4) and again with every 3x3 layer on F(2x2); if the logits differ
  * by more than 5e-4 (half the bar; the difference of the two plans overstates either one's own error), this handle -- and its clones -- runs F(2x2,3x3) on every layer.  The returned
  * text says which (the facade logs it); *tripped / *diff (may be NULL) receive the decision and the measured difference.
+ * The same text reports the one other thing that can change a handle's kernels behind the caller's back: when the code objects of
+ * the two assembly kernels (conv3x3_wino4a, conv3x3_wino4b) were wanted and could not be loaded at mi_unet_create -- a failed
+ * load or symbol look-up, a device that is not gfx950 -- it ends with "; assembly kernels not available (<reason>): ..." and the
+ * handle and its clones run those layers on the hipcc F(4x4,3x3) kernels, as under MIUNET_WINO4_ASM=0.
  * Beyond logits of magnitude ~1e2 no fp32 algorithm holds an ABSOLUTE 1e-3 (fp32 itself resolves 6e-8 of the range per
  * operation); there the guard still picks the tighter algorithm and the meaningful bound is relative (~1e-6 of the range). */
 const char *mi_unet_numeric_guard(const mi_unet_t *h, int *tripped, float *diff);
@@ -526,9 +530,12 @@ int mi_unet_debug_capture(mi_unet_t *h, const uint8_t *imgs, int B, int layer, i
 /* A second context on the SAME device that shares the source engine's weight blob (no second copy, no re-packing) but
  * owns its activation buffers, stream and graphs -- the counterpart of the reference's per-thread TensorRTContext over one
  * shared ICudaEngine (include/process.h:13-26, src/process.cpp:15, :69).  max_batch <= 0 keeps the source's.  The weights
- * stay alive until the last handle that shares them is destroyed, in any order. */
+ * stay alive until the last handle that shares them is destroyed, in any order; so do the assembly kernels' code objects, which
+ * mi_unet_create loaded for the device.  A clone also keeps the source's MIUNET_* switches as the source parsed them at create. */
 int mi_unet_clone(const mi_unet_t *src, int max_batch, mi_unet_t **out);
 
+/* Waits for every stream the handle launched on (a stream given to mi_unet_set_stream included: it must still exist), then frees
+ * what the handle owns and drops its share of the weights and code objects.  The library keeps nothing per process. */
 void mi_unet_destroy(mi_unet_t *h);
 
 /* ---- Multi-device group (the slot is the reference's sequential file loop, src/main.cpp:148-164) -------------

@@ -47,10 +47,12 @@ struct Case {
 struct Routed { std::vector<std::string> layer, route; int convs = 0, convTs = 0; };
 
 // The route of every conv3x3 (after the stand-alone first layer) and transposed-conv step, as route_plan launches a batch of B
-Routed route_names(const Net &n, int algo, int B, bool guard_tripped, bool ksplit)
+// (wino4_asm = 0: a handle whose assembly kernels are switched off or did not load)
+Routed route_names(const Net &n, int algo, int B, bool guard_tripped, bool ksplit, int wino4_asm = 1)
 {
     PlanInput in;
     const std::vector<Step> &plan = plan_of(n, algo, in);
+    in.routing.wino4_asm = wino4_asm;
     in.guard_tripped = guard_tripped;
     in.ksplit = ksplit ? dummy + 11 : nullptr;
     in.ksplit_bytes = ksplit ? (size_t)64 << 20 : 0;
@@ -170,6 +172,23 @@ int main(int argc, char **argv)
         if (got.size() != c.expect.size()) { printf("%s: %zu layers, expected %zu\n", c.what, got.size(), c.expect.size()); ++bad; continue; }
         for (size_t i = 0; i < got.size(); ++i)
             if (got[i] != c.expect[i]) { printf("%s: %s routed to %s, expected %s\n", c.what, r.layer[i].c_str(), got[i].c_str(), c.expect[i].c_str()); ++bad; }
+    }
+    // every fp32 case again as a handle without the assembly kernels routes it (Routing::wino4_asm = 0): no layer on conv3x3_wino4a /
+    // conv3x3_wino4b, and every layer that was on an F(4x4,3x3) kernel still on one (the hipcc kernels conv3x3_wino4 / conv3x3_wino4s)
+    for (const Case &c : cases) {
+        if (c.algo != MI_UNET_CONV_WINOGRAD) continue;
+        const Routed with = route_names(c.net, c.algo, c.B, c.guard_tripped, c.ksplit), r = route_names(c.net, c.algo, c.B, c.guard_tripped, c.ksplit, 0);
+        if (r.route.size() != with.route.size()) { printf("%s, wino4_asm = 0: %zu layers, expected %zu\n", c.what, r.route.size(), with.route.size()); ++bad; continue; }
+        for (size_t i = 0; i < r.route.size(); ++i) {
+            const std::string &g = r.route[i], &w = with.route[i];
+            const bool asm_kernel = g.rfind("conv3x3_wino4a", 0) == 0 || g.rfind("conv3x3_wino4b", 0) == 0;
+            const bool was4 = w.rfind("conv3x3_wino4", 0) == 0, is4 = g.rfind("conv3x3_wino4", 0) == 0;
+            const bool was_asm = w.rfind("conv3x3_wino4a", 0) == 0 || w.rfind("conv3x3_wino4b", 0) == 0;
+            if (asm_kernel || was4 != is4 || (!was_asm && g != w)) {
+                printf("%s, wino4_asm = 0: %s routed to %s (%s with the assembly kernels)\n", c.what, r.layer[i].c_str(), g.c_str(), w.c_str());
+                ++bad;
+            }
+        }
     }
     // batch-invariant mode (MIUNET_SPLITK=0: no split-K workspace): no layer's route depends on B
     const std::vector<std::string> b1 = route_names(FP32, MI_UNET_CONV_WINOGRAD, 1, false, false).route;

@@ -114,3 +114,20 @@ def test_routing_of_every_shipped_layer(tmp_path):
     r = subprocess.run([str(exe)] + files, capture_output=True, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-4000:] + r.stderr.decode()[-2000:]
     assert b"all routing checks passed" in r.stdout
+
+
+def test_assembly_kernel_owner_and_launcher(tmp_path):
+    """csrc/wino4_asm.cpp on a CPU against stubbed HIP module calls (tests/cpu/asm_kernels_test.cpp): an AsmKernels loads and unloads
+    each code object once, two owners share no module, a shared copy keeps the modules past its first holder, a failed load or look-up
+    or another architecture leaves an unavailable owner that holds nothing and says why, and the one launcher refuses shapes outside
+    either contract and fills the 128-byte argument block as the two launch functions it replaced did."""
+    import subprocess
+
+    exe = tmp_path / "asm_kernels_test"
+    pkg = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "asm_kernels_test.cpp")] +
+                          [os.path.join(pkg, "csrc", f) for f in ("wino4_asm.cpp", "routing.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stdout.decode()[-4000:] + r.stderr.decode()[-2000:]
+    assert b"all assembly-kernel owner checks passed" in r.stdout

@@ -302,7 +302,6 @@ def test_conv3x3_wino4a_contract_and_fallback(monkeypatch):
     assert np.array_equal(a, b)
     monkeypatch.setenv("MIUNET_WINO4_ASM", "0")
     c = binding.layer_debug("conv3x3_wino4", x, w)          # the hipcc two-block kernel
-    assert not np.array_equal(a, c) or True
     assert np.max(np.abs(a - c)) < 2e-5 * max(1.0, float(np.abs(a).max()))
 
 

@@ -231,6 +231,7 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
 
     // ---- launch, synchronise
     const float *d_inf = reinterpret_cast<const float *>(d_in.get());
+    std::unique_ptr<AsmKernels> asm_kernels;                  // no handle here: an owner for this call, when the op runs an assembly kernel
     if (up) {
         HIP_TRY(launch_upsample2x_bilinear(d_in, Cin, d_out, Cin, 0, B, H, W, Cin, kind, rt, nullptr));
     } else if (first) {
@@ -246,7 +247,15 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
         if (want_pool) { a.pool_out = d_pool; a.pool_ld = Cout; }
         a.in = d_inf; a.wpk = d_w; a.bias = d_b; a.out = d_out;
         if (pk == Pack::WINO4 || pk == Pack::TAPS) a.wpk4 = d_w;
-        HIP_TRY(launch_route(dop->routed ? route_wino4(a) : dop->route, a, nullptr));
+        Route r = dop->routed ? route_wino4(a) : dop->route;
+        if (r == Route::CONV_WINO4A || r == Route::CONV_WINO4B) {
+            asm_kernels.reset(new AsmKernels(device));
+            if (dop->routed && !asm_kernels->available()) {   // the routing is told, as a handle's is at create
+                a.rt.wino4_asm = 0;
+                r = route_wino4(a);
+            }
+        }
+        HIP_TRY(launch_route(r, a, asm_kernels.get(), nullptr));
     }
     HIP_TRY(hipDeviceSynchronize());
 

@@ -65,7 +65,7 @@ int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, 
     return 0;
 }
 
-hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s)
+hipError_t launch_route(Route r, const ConvArgs &a, const AsmKernels *k, hipStream_t s)
 {
     switch (r) {
 #define MIUNET_ROUTE_LAUNCH(id, name, call) case Route::id: return call;
@@ -123,7 +123,7 @@ int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, flo
             e = launch_upsample2x_bilinear(st.src, st.C, st.dst, st.ld, st.co_off, B, st.H, st.W, st.C, lp_kind, h->routing, s);
             break;
         default:
-            e = launch_route(l.rc.route, l.a, s);
+            e = launch_route(l.rc.route, l.a, h->asm_kernels.get(), s);
         }
         if (e != hipSuccess) return fail(MI_UNET_EHIP, "launch " + st.name + ": " + hipGetErrorString(e));
         if (tapped) {
@@ -317,9 +317,8 @@ int engine_adopt_weights(mi_unet_t *h, const HostWeights &hw, bool upload)
 // from the fp32 oracle, tests/test_gpu_numeric_range.py), so a weight set that passes is inside the bar with margin.
 // MIUNET_WINO4_GUARD=0 skips the probe (F(4x4) kept unconditionally), =2 trips it unconditionally, =3 probes with the noise
 // tile only (tests).
-int engine_calibrate(mi_unet_t *h)
+static int run_numeric_guard(mi_unet_t *h)
 {
-    if (int rc = check_handle(h, true)) return rc;
     h->wino4_guard_tripped = false;
     h->guard_diff = -1.f;
     const char *ge = getenv("MIUNET_WINO4_GUARD");
@@ -400,6 +399,14 @@ int engine_calibrate(mi_unet_t *h)
     return MI_UNET_OK;
 }
 
+int engine_calibrate(mi_unet_t *h)
+{
+    if (int rc = check_handle(h, true)) return rc;
+    const int rc = run_numeric_guard(h);
+    h->guard_text += h->asm_note;                       // (empty unless the assembly kernels were wanted and are not there)
+    return rc;
+}
+
 float *engine_weight_ptr(mi_unet_t *h) { return h ? h->d_weights : nullptr; }
 size_t engine_weight_floats(const mi_unet_t *h) { return h ? h->weight_floats : 0; }
 int engine_algo(const mi_unet_t *h) { return h->algo; }
@@ -462,10 +469,10 @@ void mi_unet_default_config(mi_unet_config *cfg)
     cfg->max_batch = 16; cfg->device = 0; cfg->conv_algo = MI_UNET_CONV_AUTO;
 }
 
-int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
+// mi_unet_create (src == null: every switch from the environment, the assembly kernels loaded here) and the handle half of
+// mi_unet_clone (the source's resolved switches and its assembly kernels, shared)
+static int create_handle(const mi_unet_config *cfg, const mi_unet *src, mi_unet_t **out)
 {
-    if (!cfg || !out) return fail(MI_UNET_EARG, "mi_unet_create: null argument");
-    *out = nullptr;
     const int L = cfg->levels;
     if (L < 1 || L > 6) return fail(MI_UNET_EARG, "levels must be in 1..6");
     if (cfg->height <= 0 || cfg->width <= 0 || cfg->height % (1 << L) || cfg->width % (1 << L))
@@ -497,15 +504,43 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
             else algo = MI_UNET_CONV_DEFAULT;
         }
         h->algo = algo;
+        const char *gr = getenv("MIUNET_GRAPH");
+        h->use_graph = !(gr && !strcmp(gr, "0"));
+    }
+    if (src) {                                           // a clone routes and stages exactly as its source (same device)
+        h->fuse_pool = src->fuse_pool; h->fuse_head = src->fuse_head; h->wino4_min_wg = src->wino4_min_wg;
+        h->routing = src->routing;
+        h->asm_kernels = src->asm_kernels; h->asm_note = src->asm_note;
+        h->copy_threads = src->copy_threads; h->raw_split = src->raw_split; h->raw_trace = src->raw_trace;
+    } else {
         const char *fp = getenv("MIUNET_FUSE_POOL");
         h->fuse_pool = !(fp && !strcmp(fp, "0"));
         const char *fh = getenv("MIUNET_FUSE_HEAD");
         h->fuse_head = !(fh && fh[0] == '0');
         if (const char *mw = getenv("MIUNET_WINO4_MIN_WG")) h->wino4_min_wg = atoi(mw);
         h->routing = Routing::from_env();
-        const char *gr = getenv("MIUNET_GRAPH");
-        h->use_graph = !(gr && !strcmp(gr, "0"));
+        if (const char *ct = getenv("MIUNET_COPY_THREADS")) h->copy_threads = std::min(std::max(atoi(ct), 1), 16);
+        if (const char *sp = getenv("MIUNET_RAW_SPLIT")) {
+            h->raw_split.clear();
+            for (const char *q = sp; *q;) {
+                h->raw_split.push_back(atoi(q));
+                while (*q && *q != ',') ++q;
+                if (*q == ',') ++q;
+            }
+        }
+        const char *tr = getenv("MIUNET_RAW_TRACE");
+        h->raw_trace = tr && tr[0] == '1';
+        // the assembly kernels' code objects, loaded before any plan is built: the routing is told here whether they are there
+        if (h->algo == MI_UNET_CONV_WINOGRAD && h->routing.wino4_asm != 0) {
+            h->asm_kernels = std::make_shared<AsmKernels>(cfg->device);
+            if (!h->asm_kernels->available()) {
+                h->asm_note = "; assembly kernels not available (" + h->asm_kernels->error() + "): their layers run conv3x3_wino4 / conv3x3_wino4s";
+                h->guard_text += h->asm_note;
+                h->asm_kernels.reset();
+            }
+        }
     }
+    if (!h->asm_kernels) h->routing.wino4_asm = 0;
     auto cleanup_fail = [&](int rc) { mi_unet_destroy(h); return rc; };
 #define HIP_TRY_H(expr)                                                                                        \
     do {                                                                                                       \
@@ -543,6 +578,13 @@ int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
     return MI_UNET_OK;
 }
 
+int mi_unet_create(const mi_unet_config *cfg, mi_unet_t **out)
+{
+    if (!cfg || !out) return fail(MI_UNET_EARG, "mi_unet_create: null argument");
+    *out = nullptr;
+    return create_handle(cfg, nullptr, out);
+}
+
 int mi_unet_load_weights_from_memory(mi_unet_t *h, const void *blob, size_t len)
 {
     if (int rc = check_handle(h, false)) return rc;
@@ -575,9 +617,7 @@ int mi_unet_clone(const mi_unet_t *src, int max_batch, mi_unet_t **out)
     if (max_batch > 0) cfg.max_batch = max_batch;
     cfg.conv_algo = src->algo;                       // the resolved algorithm: the shared blob is packed for it
     mi_unet_t *h = nullptr;
-    if (int rc = mi_unet_create(&cfg, &h)) return rc;
-    h->fuse_pool = src->fuse_pool; h->fuse_head = src->fuse_head; h->wino4_min_wg = src->wino4_min_wg;
-    h->routing = src->routing;                       // a clone routes exactly as its source (same device)
+    if (int rc = create_handle(&cfg, src, &h)) return rc;
     h->wino4_guard_tripped = src->wino4_guard_tripped; h->guard_diff = src->guard_diff; h->guard_text = src->guard_text;
     h->weights = src->weights;                       // shared: freed with the last handle that holds it
     h->d_weights = h->weights->d;
@@ -847,20 +887,21 @@ const char *mi_unet_numeric_guard(const mi_unet_t *h, int *tripped, float *diff)
     return h->guard_text.c_str();
 }
 
-// The handle's buffers and events free themselves (engine_handle.h); what is left has an order: no stream of the handle may still
-// be working when they go, and the graph executables go before the stream they were captured on.
+// The handle's buffers and events free themselves (engine_handle.h); what is left has an order: no stream the handle launched on
+// may still be working when they go, and the graph executables go before the stream they were captured on and before the assembly
+// kernels' modules, which the last handle that shares them unloads.
 void mi_unet_destroy(mi_unet_t *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    for (hipStream_t q : { h->own_stream, h->tail_stream, h->dl_stream, h->pre_stream })
+    for (hipStream_t q : { h->stream, h->own_stream, h->tail_stream, h->dl_stream, h->pre_stream })   // (h->stream: the caller's, after mi_unet_set_stream)
         if (q) (void)hipStreamSynchronize(q);
     for (hipStream_t q : { h->tail_stream, h->dl_stream, h->pre_stream })
         if (q) (void)hipStreamDestroy(q);
     for (auto &g : h->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;                                           // ... and with it this handle's hold on the weights and the assembly kernels
 }
 
 }  // extern "C"

@@ -87,6 +87,11 @@ struct mi_unet {
     // one blob: every packed tensor (single allocation -> one broadcast / one free).  Owned by `weights`, which clones of
     // this handle share (mi_unet_clone: the reference's engine is shared by its per-thread contexts, src/process.cpp:15, :69)
     std::shared_ptr<miunet::DeviceWeights> weights;
+    // the assembly kernels' code objects on this handle's device (kernels.h): made by mi_unet_create for the fp32 Winograd plan unless
+    // MIUNET_WINO4_ASM=0, shared with clones, unloaded with the last handle that holds it.  Null = this handle has none, and then
+    // routing.wino4_asm is 0; asm_note (appended to guard_text) says why when they were wanted and could not be loaded
+    std::shared_ptr<miunet::AsmKernels> asm_kernels;
+    std::string asm_note;
     float *d_weights = nullptr;     // = weights->d
     size_t weight_floats = 0;
     miunet::DeviceBuf<float> d_lut;         // 256 floats: i / 255.0f
@@ -205,6 +210,10 @@ struct mi_unet {
     };
     std::vector<GraphEntry> graphs;
     bool use_graph = true;          // MIUNET_GRAPH=0 disables
+    // the RAW-in entry points' switches (pipeline_raw.cpp), parsed at create like the ones above and copied by mi_unet_clone
+    int copy_threads = 4;           // MIUNET_COPY_THREADS (1..16): threads of a large host copy; 1 = plain memcpy
+    std::vector<int> raw_split{ -1 };   // MIUNET_RAW_SPLIT: { 0 } whole chunks only, { a, b, ... } cuts of the first chunk, { -1 } the default cut
+    bool raw_trace = false;         // MIUNET_RAW_TRACE=1: host-side timeline of every RAW-in call on stderr
     bool postprocess = false;       // mi_unet_set_postprocess: label maps -> postprocess_mask output before they leave the device
     // profiling: one event pair per launch, recorded on the launch stream and only read back (synchronised) in
     // mi_unet_get_kernel_stats, so the launches themselves never wait on the host
@@ -231,7 +240,7 @@ PlanInput plan_input(const mi_unet *h);                 // the handle's settings
 int launch_plan(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);
 int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);   // graph replay of launch_plan
 int infer_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);  // ... + postprocess when set
-hipError_t launch_route(Route r, const ConvArgs &a, hipStream_t s);
+hipError_t launch_route(Route r, const ConvArgs &a, const AsmKernels *k, hipStream_t s);   // k: for the CONV_WINO4A / _WINO4B rows
 constexpr mi_unet_target kDefaultTarget{ 2, 0.06f };    // the reference's: class 2, 6 % of the image
 TargetTable target_table(const mi_unet_target *targets, int n, int H, int W);   // `n` targets with min_area of an H x W image
 TargetTable target_table(const mi_unet *h, int H, int W);   // ... the handle's, with its morphology (the _multi entry points)

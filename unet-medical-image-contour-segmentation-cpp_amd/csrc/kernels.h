@@ -1,8 +1,13 @@
 // kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// The hipcc kernels are part of the library's own code object.  The two assembly kernels (csrc/asm/) are code objects of their own,
+// embedded as byte blobs: an AsmKernels (below) loads them for one device when an engine is created and unloads them with the last
+// handle that holds it.  libmiunet.so keeps no process-wide resource: no module, no device memory, no stream outlives its handles.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <string>
 
 struct mi_unet_region;      // include/mi_unet.h
 struct mi_unet_score;
@@ -16,7 +21,8 @@ constexpr int NPAD = 128;     // packed Cout granule (covers both BN = 64 and BN
 // Kernel-routing switches (the MIUNET_* A/B variables) and the device's CU count, resolved ONCE per engine handle at
 // mi_unet_create (once per call in mi_unet_layer_debug) and carried in every launch's arguments: a launch never calls getenv or
 // touches shared tables, so cloned contexts launching from several threads share nothing mutable, and an engine's routing cannot
-// change under it.  Which kernel a layer gets is decided in routing.cpp.
+// change under it.  Which kernel a layer gets is decided in routing.cpp.  wino4_asm is also how the routing is TOLD that the assembly
+// kernels are not there: a handle without an available() AsmKernels carries 0.
 struct Routing {
     int cus = 256;            // compute units of the launch device
     int lp2 = 1;              // MIUNET_LP2: 0 never, 1 default thresholds, 2 every Cout % 128 == 0 layer
@@ -97,12 +103,34 @@ hipError_t launch_conv3x3_wino4(const ConvArgs &a, bool one_block, hipStream_t s
 // The one-block algorithm with single-buffered 70 KB of LDS and <= 256 registers, so that two workgroups share a CU
 // (conv_wino4s.hip); same packing (a.wpk4), bit-identical results, no split-K; can run the first layer in its loader.
 hipError_t launch_conv3x3_wino4s(const ConvArgs &a, hipStream_t s);
-// The two-block kernel hand-scheduled in gfx950 assembly and persistent (csrc/asm/gen_wino4_asm.py, csrc/wino4_asm.cpp): same
-// packing (a.wpk4), same tensors; its contract is conv3x3_wino4a_shape_ok (routing.h).
-hipError_t launch_conv3x3_wino4a(const ConvArgs &a, hipStream_t s);
-// ... and its sibling for the layers with 64 output channels per workgroup: blocks of 16 x 32 pixels (32 tiles) x 64 channels, a wave
-// = 32 tiles x 16 channels, V single-buffered with a transform phase and an MFMA phase per chunk (csrc/asm/gen_wino4b_asm.py)
-hipError_t launch_conv3x3_wino4b(const ConvArgs &a, hipStream_t s);
+// The owner of the two assembly kernels' code objects on ONE device (csrc/wino4_asm.cpp).  The constructor loads both embedded code
+// objects and resolves conv3x3_wino4a_f32 and conv3x3_wino4b_f32; the destructor unloads both (device set and restored, as
+// DeviceWeights::~DeviceWeights does).  A handle holds it as a std::shared_ptr next to its weights: mi_unet_create makes it (fp32
+// Winograd plan, MIUNET_WINO4_ASM != 0), clones share it, the last handle's mi_unet_destroy unloads.  available(): both loads and
+// both look-ups succeeded on a gfx950 device; otherwise error() says why and nothing stays loaded.
+class AsmKernels {
+public:
+    enum Which { WINO4A = 0, WINO4B = 1 };
+    explicit AsmKernels(int device);
+    ~AsmKernels();
+    AsmKernels(const AsmKernels &) = delete;
+    AsmKernels &operator=(const AsmKernels &) = delete;
+    bool available() const { return error_.empty(); }
+    const std::string &error() const { return error_; }
+    hipFunction_t function(Which w) const { return fn_[w]; }
+
+private:
+    void unload();
+    int device_;
+    hipModule_t mod_[2] = {};
+    hipFunction_t fn_[2] = {};
+    std::string error_;
+};
+// WINO4A: the two-block kernel hand-scheduled in gfx950 assembly and persistent (csrc/asm/gen_wino4_asm.py): same packing (a.wpk4),
+// same tensors; its contract is conv3x3_wino4a_shape_ok (routing.h).  WINO4B: its sibling for the layers with 64 output channels per
+// workgroup: blocks of 16 x 32 pixels (32 tiles) x 64 channels, a wave = 32 tiles x 16 channels, V single-buffered with a transform
+// phase and an MFMA phase per chunk (csrc/asm/gen_wino4b_asm.py; conv3x3_wino4b_shape_ok).  An absent or unavailable owner is an error.
+hipError_t launch_conv3x3_wino4_asm(const AsmKernels *owner, AsmKernels::Which which, const ConvArgs &a, hipStream_t s);
 hipError_t launch_wino_splitk_reduce(const ConvArgs &a, hipStream_t s);   // sums a.ksplit slabs of a.ksplit_ws into a.out
 hipError_t launch_convT2x2_mfma(const ConvArgs &a, hipStream_t s);
 // The transposed conv as four per-tap GEMMs sharing one A operand (convt_taps.hip): a.wpk4 holds the weights packed

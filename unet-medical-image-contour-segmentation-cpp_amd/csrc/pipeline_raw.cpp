@@ -24,9 +24,8 @@ namespace miunet {
 // large host copies (RAW staging in, tiles / masks out) on the handle's helper threads (MIUNET_COPY_THREADS, default 4; 1 = plain memcpy)
 void host_copy(mi_unet *h, void *dst, const void *src, size_t bytes)
 {
-    static const int copy_threads = [] { const char *e = getenv("MIUNET_COPY_THREADS"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v > 16 ? 16 : v; }();
-    if (copy_threads > 1 && bytes >= (1u << 20)) {
-        if (!h->copy_pool) h->copy_pool.reset(new CopyPool(copy_threads - 1));
+    if (h->copy_threads > 1 && bytes >= (1u << 20)) {
+        if (!h->copy_pool) h->copy_pool.reset(new CopyPool(h->copy_threads - 1));
         h->copy_pool->copy(dst, src, bytes);
     } else {
         memcpy(dst, src, bytes);
@@ -161,19 +160,9 @@ int run_raw_call(mi_unet *h, const RawCall &c)
     // MIUNET_RAW_SPLIT = 0: whole chunks only; "a" or "a,b,...": the first chunk is cut into a, b, ... images and the rest
     // (default: a quarter of the chunk, at least four, then the rest -- same-card sweep at 16 images: 0 -> 749, 2 -> 780, 4 -> 787,
     // 6 -> 737, 8 -> 779 images/s from pinned memory, tools/dev/split_sweep.py)
-    static const std::vector<int> split_env = [] {
-        std::vector<int> v;
-        const char *e = getenv("MIUNET_RAW_SPLIT");
-        if (!e) return std::vector<int>{ -1 };
-        for (const char *q = e; *q;) {
-            v.push_back(atoi(q));
-            while (*q && *q != ',') ++q;
-            if (*q == ',') ++q;
-        }
-        return v;
-    }();
-    if (!(split_env.size() == 1 && split_env[0] == 0) && mbs[0].bm >= 8) {
-        std::vector<int> cuts = split_env;
+    // (h->raw_split, parsed at create)
+    if (!(h->raw_split.size() == 1 && h->raw_split[0] == 0) && mbs[0].bm >= 8) {
+        std::vector<int> cuts = h->raw_split;
         if (cuts.size() == 1 && cuts[0] < 0) cuts[0] = std::max(4, mbs[0].bm / 4);
         int left = mbs[0].bm, b0 = 0;
         std::vector<MB> parts;
@@ -270,7 +259,7 @@ int run_raw_call(mi_unet *h, const RawCall &c)
         return 0;
     };
     // MIUNET_RAW_TRACE=1: host-side timeline of the call on stderr (when did each enqueue / staging / copy-out start and end)
-    static const bool trace = [] { const char *e = getenv("MIUNET_RAW_TRACE"); return e && e[0] == '1'; }();
+    const bool trace = h->raw_trace;
     const auto t_call = std::chrono::steady_clock::now();
     auto mark = [&](const char *what, int k) {
         if (trace) fprintf(stderr, "[raw %8.3f ms] %s %d\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), what, k);

@@ -210,8 +210,9 @@ static bool wino4_staged(const ConvArgs &a)
 Route route_wino4(const ConvArgs &a)
 {
     const int rem = a.Cout % 128;
-    // staged layers with 64 output channels per workgroup and a shape the assembly takes: conv3x3_wino4b
-    if (wino4_staged(a)) return conv3x3_wino4b_shape_ok(a) && rem != 0 ? Route::CONV_WINO4B : Route::CONV_WINO4S;
+    // staged layers with 64 output channels per workgroup and a shape the assembly takes: conv3x3_wino4b (rt.wino4_asm = 0: the
+    // handle has no assembly kernels -- switched off, or their code objects did not load -- and neither of the two is ever chosen)
+    if (wino4_staged(a)) return a.rt.wino4_asm != 0 && conv3x3_wino4b_shape_ok(a) && rem != 0 ? Route::CONV_WINO4B : Route::CONV_WINO4S;
     if (a.head_w != nullptr) return Route::CONV_WINO4_1B;
     // the hand-scheduled persistent two-block kernel takes the shapes of its contract, unless the grid is one the hipcc kernel
     // would split K for (single images, deep levels)

@@ -9,8 +9,8 @@
 namespace miunet {
 
 // One row per kernel entry the engine can launch: route, the kernel name the launch log reports (bench.py maps kernel families
-// by these names), and the launcher call (engine.cpp expands it with the launch's `a` and stream `s`).  FIRST, POOL, HEAD and
-// UPSAMPLE take operands of their own, not a ConvArgs: the engine launches those itself.
+// by these names), and the launcher call (engine.cpp expands it with the launch's `a`, the handle's assembly kernels `k` and
+// stream `s`).  FIRST, POOL, HEAD and UPSAMPLE take operands of their own, not a ConvArgs: the engine launches those itself.
 #define MIUNET_ROUTES(X)                                                                  \
     X(CONV_MFMA, "conv3x3_mfma", launch_conv3x3_mfma(a, s))                               \
     X(CONV_WINO, "conv3x3_wino", launch_conv3x3_wino(a, s))                               \
@@ -18,8 +18,8 @@ namespace miunet {
     X(CONV_WINO4, "conv3x3_wino4", launch_conv3x3_wino4(a, false, s))                     \
     X(CONV_WINO4_1B, "conv3x3_wino4", launch_conv3x3_wino4(a, true, s))                   \
     X(CONV_WINO4S, "conv3x3_wino4s", launch_conv3x3_wino4s(a, s))                         \
-    X(CONV_WINO4A, "conv3x3_wino4a", launch_conv3x3_wino4a(a, s))                         \
-    X(CONV_WINO4B, "conv3x3_wino4b", launch_conv3x3_wino4b(a, s))                         \
+    X(CONV_WINO4A, "conv3x3_wino4a", launch_conv3x3_wino4_asm(k, AsmKernels::WINO4A, a, s)) \
+    X(CONV_WINO4B, "conv3x3_wino4b", launch_conv3x3_wino4_asm(k, AsmKernels::WINO4B, a, s)) \
     X(CONV_BF16, "conv3x3_bf16", launch_conv3x3_bf16(a, s))                               \
     X(CONV_FP16, "conv3x3_fp16", launch_conv3x3_fp16(a, s))                               \
     X(CONV_BF16W, "conv3x3_bf16w", launch_conv3x3_lp2(a, false, s))                       \
