@@ -476,9 +476,37 @@ int mi_unet_get_kernel_stats(mi_unet_t *h, mi_unet_kernel_stat *stats, int cap, 
  *   op = "maxpool"  : in [B][H][W][Cin]                                          -> out [B][H/2][W/2][Cin]
  *   op = "upsample2x" / "upsample2x_bf16" / "upsample2x_fp16" : in [B][H][W][Cin] -> out [B][2H][2W][Cin], bilinear with
  *                     align_corners=True, Cin % 16 == 0, no weights (the 16-bit ops round the input to 16 bits first)
+ *   op = "maxpool_bf16" / "maxpool_fp16" : the 16-bit stand-alone pooling (non-negative values: it orders bit patterns), C % 8 == 0
  * Weights are given in PyTorch layout exactly as in the weight file. */
 int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
                         const float *scale, const float *shift, int Cout, int relu, float *out);
+
+/* The same launch in a strided layout, to see every byte the kernel was NOT supposed to touch: the engine's tensors are halves of
+ * concat buffers (pixel stride 2 * Cout, first output channel 0 or Cout).  Strides in elements, 0 = the dense default:
+ *   ldc     pixel stride of the input           (>= Cin;  the first layer reads the u8 image and has none)
+ *   ldo     pixel stride of the output          (>= co_off + Cout; maxpool writes dense and has none)
+ *   co_off  first output channel written        (>= 0;    conv, transposed conv and upsample only)
+ *   pool_ld pixel stride of the pooled output   (>= Cout; the _pool forms only)
+ *   guard_bytes  a guard of that size in front of and behind every device tensor of the call (input, output, pooled output); a
+ *           multiple of 256.
+ * The whole output and pooled allocations are filled with 0xFF bytes (a NaN in fp32, bf16 and fp16) before the launch, and so are
+ * the input's guards and its gap channels [Cin, ldc).  A layout outside these bounds, or one the route's own launcher refuses, is an
+ * error and nothing is launched.  out_raw receives the complete output allocation -- guard, [npix][ldo] elements, guard -- as raw
+ * bytes, nothing converted; pool_raw the pooled one for the _pool forms (NULL otherwise).  info: the element size, the two
+ * allocation sizes and the name of the route that ran (as mi_unet_layer_info::kernel).  A capacity that is too small is an error
+ * with info filled in. */
+typedef struct mi_unet_debug_layout {
+    int ldc, ldo, co_off, pool_ld;
+    long long guard_bytes;
+} mi_unet_debug_layout;
+typedef struct mi_unet_debug_strided_info {
+    int elem_bytes;           /* bytes per output element: 4, or 2 for the 16-bit outputs */
+    unsigned long long out_bytes, pool_bytes;   /* the whole allocations, guards included (pool_bytes 0 without _pool) */
+    char kernel[32];
+} mi_unet_debug_strided_info;
+int mi_unet_layer_debug_strided(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
+                                const float *scale, const float *shift, int Cout, int relu, const mi_unet_debug_layout *layout,
+                                void *out_raw, size_t out_cap, void *pool_raw, size_t pool_cap, mi_unet_debug_strided_info *info);
 
 /* Numeric guard of the default fp32 plan (conv_algo auto / winograd).  Winograd F(4x4,3x3) is exact arithmetic re-associated:
  * its rounding error relative to a layer's operand range is about five times that of F(2x2,3x3) (2e-5 against 4e-6 on logits

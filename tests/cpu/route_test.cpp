@@ -199,6 +199,45 @@ int main(int argc, char **argv)
         printf("first / pool / head kernel names changed\n");
         ++bad;
     }
+    // the stride bounds of the shape contracts: a pixel stride shorter than the channels it holds is refused by every one of them,
+    // in either half of a concat buffer (alignment alone would let ldc = Cin - 8 or ldo = co_off + Cout - 8 through)
+    {
+        static const float dummy[4] = {};
+        struct Row { const char *what; bool (*ok)(const ConvArgs &); int Cin, Cout, H, W, out_lp, nmul, pool; };
+        const Row rows[] = {
+            { "conv3x3_lpr_shape_ok", conv3x3_lpr_shape_ok, 64, 64, 16, 32, 1, 1, 1 },
+            { "conv3x3_lprk_shape_ok", conv3x3_lprk_shape_ok, 128, 64, 16, 32, 1, 1, 0 },
+            { "convT2x2_lpr_shape_ok", convT2x2_lpr_shape_ok, 128, 64, 16, 32, 1, 4, 0 },
+            { "conv3x3_wino4a_shape_ok", conv3x3_wino4a_shape_ok, 64, 128, 16, 32, 0, 1, 1 },
+            { "conv3x3_wino4b_shape_ok", conv3x3_wino4b_shape_ok, 64, 64, 16, 32, 0, 1, 1 },
+        };
+        for (const Row &rw : rows) {
+            ConvArgs a{};
+            a.in = a.wpk = a.wpk4 = a.bias = dummy;
+            a.B = 1; a.H = rw.H; a.W = rw.W; a.Cin = rw.Cin; a.ldc = rw.Cin; a.Cout = rw.Cout; a.CoutPad = rw.nmul * 128;
+            a.ldo = rw.Cout; a.co_off = 0; a.out_lp = rw.out_lp;
+            if (rw.pool) { a.pool_out = const_cast<float *>(dummy); a.pool_ld = rw.Cout; }
+            auto expect = [&](const ConvArgs &c, bool want, const char *layout) {
+                if (rw.ok(c) != want) { printf("%s: %s is %s\n", rw.what, layout, want ? "refused" : "taken"); ++bad; }
+            };
+            expect(a, true, "the dense layout");
+            ConvArgs lower = a; lower.ldo = 2 * rw.Cout;
+            expect(lower, true, "the lower half");
+            ConvArgs upper = lower; upper.co_off = rw.Cout;
+            expect(upper, true, "the upper half");
+            ConvArgs wide_in = a; wide_in.ldc = 2 * rw.Cin;
+            expect(wide_in, true, "ldc = 2 * Cin");
+            ConvArgs c = a; c.ldc = rw.Cin - 8;
+            expect(c, false, "ldc < Cin");
+            c = a; c.ldo = rw.Cout - 8;
+            expect(c, false, "ldo < Cout");
+            c = upper; c.ldo = 2 * rw.Cout - 8;
+            expect(c, false, "ldo < co_off + Cout");
+            c = a; c.co_off = -8; c.ldo = 2 * rw.Cout;
+            expect(c, false, "co_off < 0");
+            if (rw.pool) { c = a; c.pool_ld = rw.Cout - 8; expect(c, false, "pool_ld < Cout"); }
+        }
+    }
     if (bad) { printf("%d routing mismatches\n", bad); return 1; }
     printf("all routing checks passed\n");
     return 0;

@@ -293,6 +293,9 @@ def test_conv3x3_wino4a_contract_and_fallback(monkeypatch):
             binding.layer_debug("conv3x3_wino4a", x, w)
         got = binding.layer_debug("conv3x3_wino4", x, w)
         assert np.max(np.abs(got - orc.conv3x3(x, w))) < _tol(got)
+        # the hipcc fallback: each of these is a one-block case (Cin <= 64 without the assembly kernel, or Cout = 64) that no
+        # assembly contract takes, and without a split-K workspace one-block cases go to the staged kernel (route_wino4)
+        assert binding.layer_debug_strided("conv3x3_wino4", x, w)["kernel"] == "conv3x3_wino4s", shape
     B, H, W, Cin, Cout = 2, 32, 32, 128, 128
     x = r.standard_normal((B, H, W, Cin), dtype=np.float32)
     w = (r.standard_normal((Cout, Cin, 3, 3), dtype=np.float32) * 0.03).astype(np.float32)
@@ -300,9 +303,11 @@ def test_conv3x3_wino4a_contract_and_fallback(monkeypatch):
     a = binding.layer_debug("conv3x3_wino4", x, w)          # routed to the assembly kernel (shape fits, no split-K workspace in layer_debug)
     b = binding.layer_debug("conv3x3_wino4a", x, w)
     assert np.array_equal(a, b)
+    assert binding.layer_debug_strided("conv3x3_wino4", x, w)["kernel"] == "conv3x3_wino4a"
     monkeypatch.setenv("MIUNET_WINO4_ASM", "0")
     c = binding.layer_debug("conv3x3_wino4", x, w)          # the hipcc two-block kernel
     assert np.max(np.abs(a - c)) < 2e-5 * max(1.0, float(np.abs(a).max()))
+    assert binding.layer_debug_strided("conv3x3_wino4", x, w)["kernel"] == "conv3x3_wino4"      # the route name of both hipcc F(4x4) kernels
 
 
 # ---------------------------------------------------------------------------------------------------- conv3x3_wino4b (assembly)

@@ -1,4 +1,5 @@
-// debug.cpp -- the test and diagnosis entry points: mi_unet_layer_debug (one kernel on caller-supplied operands),
+// debug.cpp -- the test and diagnosis entry points: mi_unet_layer_debug (one kernel on caller-supplied operands) and its strided form
+// mi_unet_layer_debug_strided (the same launch in a concat-buffer layout between poisoned guards, the raw allocations returned),
 // mi_unet_debug_layer_info / mi_unet_debug_capture and the taps launch_plan calls for them.
 #include <hip/hip_runtime.h>
 
@@ -24,7 +25,8 @@ int download_tensor(hipStream_t s, const void *d, int bits, int lp_kind, size_t 
     const size_t eb = (size_t)bits / 8;
     std::vector<unsigned char> raw(npix * C * eb);
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy2D(raw.data(), C * eb, d, (size_t)ld * eb, C * eb, npix, hipMemcpyDeviceToHost));
+    if (ld == C) HIP_TRY(hipMemcpy(raw.data(), d, npix * C * eb, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy2D(raw.data(), C * eb, d, (size_t)ld * eb, C * eb, npix, hipMemcpyDeviceToHost));
     const size_t n = npix * C;
     if (bits == 32) memcpy(dst, raw.data(), n * 4);
     else if (bits == 8) for (size_t i = 0; i < n; ++i) dst[i] = (float)raw[i];
@@ -139,16 +141,27 @@ const DebugOp kDebugOps[] = {
     { "conv3x3_first_fp16", Route::FIRST, Pack::FIRST, 2, false },   { "maxpool", Route::POOL, Pack::NONE, 0, false },
     { "upsample2x", Route::UPSAMPLE, Pack::UP, 0, false },           { "upsample2x_bf16", Route::UPSAMPLE, Pack::UP, 1, false },
     { "upsample2x_fp16", Route::UPSAMPLE, Pack::UP, 2, false },
+    { "maxpool_bf16", Route::POOL, Pack::NONE, 1, false },           { "maxpool_fp16", Route::POOL, Pack::NONE, 2, false },
 };
 
-}  // namespace
+// The layout of one hook call, in elements (0 = the dense default), and the guard in front of and behind every device tensor
+struct DebugLayout { int ldc = 0, ldo = 0, co_off = 0, pool_ld = 0; size_t guard = 0; };
 
-extern "C" {
+// What the one body leaves behind for its two callers: the output (and pooled) allocations, guards included, still on the device
+struct DebugRun {
+    DeviceBuf<unsigned char> d_out, d_pool;
+    size_t guard = 0, out_bytes = 0, pool_bytes = 0;             // whole allocations: guard + tensor + guard
+    size_t out_npix = 0, pool_npix = 0;
+    int es = 4, lp_kind = 0, C = 0, ldo = 0, co_off = 0, pool_ld = 0;
+    bool pooled = false;
+    std::string kernel;
+};
 
-int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
-                        const float *scale, const float *shift, int Cout, int relu, float *out)
+// The body of mi_unet_layer_debug and mi_unet_layer_debug_strided: pack, upload, launch, synchronise.
+int run_layer(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w, const float *scale,
+              const float *shift, int Cout, int relu, const DebugLayout &lay, DebugRun &run)
 {
-    if (!op || !in || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(MI_UNET_EARG, "layer_debug: bad argument");
+    if (!op || !in || B <= 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(MI_UNET_EARG, "layer_debug: bad argument");
     if (mi_unet_device_count() <= 0) return fail(MI_UNET_ENODEVICE, "no HIP device visible: libmiunet has no CPU fallback");
     HIP_TRY(hipSetDevice(device));
     // ---- resolve the op: "<op>[_pool][_lpout]"; _pool returns the fused 2x2 max-pooled tensor [B][H/2][W/2][Cout] instead
@@ -174,7 +187,8 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
         if (!w || Cout <= 0 || Cout % 4 || (Cin != 1 && Cin != 3) || want_pool || lp_out)
             return fail(MI_UNET_EARG, "layer_debug: conv3x3_first needs weights, Cin 1 or 3, Cout % 4 == 0");
     } else if (pool) {
-        if (Cin % 4 || H % 2 || W % 2) return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 and even H, W");
+        if (Cin % (kind ? 8 : 4) || H % 2 || W % 2 || lp_out)
+            return fail(MI_UNET_EARG, "layer_debug: maxpool needs C % 4 == 0 (16-bit: C % 8 == 0) and even H, W");
     } else if (kind) {
         if (!w || Cout <= 0 || Cin % 8) return fail(MI_UNET_EARG, "layer_debug: 16-bit conv needs weights and Cin % 8 == 0");
     } else if (!w || Cout <= 0 || Cin % 4) {
@@ -182,12 +196,22 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
     }
     if (lp_out && !kind) return fail(MI_UNET_EARG, "layer_debug: _lpout is for the 16-bit conv ops");
     if (want_pool && (pool || T || (H & 1) || (W & 1))) return fail(MI_UNET_EARG, "layer_debug: _pool is for the conv3x3 ops on even sizes");
-    const size_t in_n = (size_t)B * H * W * Cin;
-    size_t out_n = up ? in_n * 4 : pool ? in_n / 4 : (size_t)B * (T ? 4 : 1) * H * W * Cout;
     // the first layer reads the u8 image (`in` holds byte values 0..255), the 16-bit kernels 16-bit activations (rounded here, RNE);
-    // the 16-bit upsample and first layer and the _lpout ops store 16 bits, which come back converted to float
-    const size_t in_es = first ? 1 : (kind && !pool) ? 2 : 4;
-    const bool out16 = kind && (up || first || lp_out);
+    // the 16-bit upsample, pooling and first layer and the _lpout ops store 16 bits
+    const size_t in_es = first ? 1 : kind ? 2 : 4;
+    const bool out16 = kind && (up || first || pool || lp_out);
+    const size_t out_es = out16 ? 2 : 4;
+    const int Co = (up || pool) ? Cin : Cout;                  // channels of the output slice
+
+    // ---- the layout: what the op has no operand for stays at its default, the rest is bounded here and by the route's launcher
+    const int ldc = lay.ldc ? lay.ldc : Cin, ldo = lay.ldo ? lay.ldo : Co, co_off = lay.co_off, pool_ld = lay.pool_ld ? lay.pool_ld : Co;
+    if (lay.guard % 256) return fail(MI_UNET_EARG, "layer_debug: guard_bytes must be a multiple of 256");
+    if (ldc < Cin || co_off < 0 || ldo < co_off + Co || pool_ld < Co)
+        return fail(MI_UNET_EARG, "layer_debug: layout needs ldc >= Cin, co_off >= 0, ldo >= co_off + Cout, pool_ld >= Cout");
+    if ((first && ldc != Cin) || ((first || pool) && co_off != 0) || (pool && ldo != Co) || (!want_pool && pool_ld != Co))
+        return fail(MI_UNET_EARG, "layer_debug: the op has no such stride (first layer: ldo; maxpool: ldc; pool_ld: the _pool forms)");
+    const size_t in_npix = (size_t)B * H * W, in_n = in_npix * Cin;
+    const size_t out_npix = (up || T) ? in_npix * 4 : pool ? in_npix / 4 : in_npix;
     const Routing rt = Routing::from_env();
 
     // ---- pack (weights.cpp)
@@ -207,16 +231,22 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
     float lut[256];
     first_layer_lut(lut);
 
-    // ---- upload; the outputs poisoned with NaN bytes, so that unwritten elements are visible
+    // ---- upload: guard + tensor + guard each.  The outputs are poisoned with NaN bytes (0xFF.. is a NaN in fp32, bf16 and fp16), so
+    // that unwritten elements and stray stores are visible; so are the input's guards and its gap channels [Cin, ldc)
+    const size_t G = lay.guard;
+    const size_t in_bytes = in_npix * ldc * in_es, out_bytes = out_npix * ldo * out_es, pool_bytes = (out_npix / 4) * pool_ld * out_es;
     DeviceBuf<unsigned char> d_in;
-    DeviceBuf<float> d_out, d_pool, d_w, d_b, d_lut;
-    HIP_TRY(d_in.reset(first ? in_n : sizeof(float) * in_n));
-    HIP_TRY(d_out.reset(out_n));
-    HIP_TRY(hipMemcpy(d_in, in_es == 4 ? static_cast<const void *>(in) : in_raw.data(), in_n * in_es, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out, 0xFF, sizeof(float) * out_n));
+    DeviceBuf<float> d_w, d_b, d_lut;
+    HIP_TRY(d_in.reset(2 * G + in_bytes));
+    if (G || ldc != Cin) HIP_TRY(hipMemset(d_in, 0xFF, 2 * G + in_bytes));
+    const void *in_host = in_es == 4 ? static_cast<const void *>(in) : in_raw.data();
+    if (ldc == Cin) HIP_TRY(hipMemcpy(d_in.get() + G, in_host, in_bytes, hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemcpy2D(d_in.get() + G, (size_t)ldc * in_es, in_host, Cin * in_es, Cin * in_es, in_npix, hipMemcpyHostToDevice));
+    HIP_TRY(run.d_out.reset(2 * G + out_bytes));
+    HIP_TRY(hipMemset(run.d_out, 0xFF, 2 * G + out_bytes));
     if (want_pool) {
-        HIP_TRY(d_pool.reset(out_n / 4));
-        HIP_TRY(hipMemset(d_pool, 0xFF, sizeof(float) * (out_n / 4)));
+        HIP_TRY(run.d_pool.reset(2 * G + pool_bytes));
+        HIP_TRY(hipMemset(run.d_pool, 0xFF, 2 * G + pool_bytes));
     }
     if (!wpk.empty()) {
         HIP_TRY(d_w.reset(wpk.size()));
@@ -230,24 +260,27 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
     }
 
     // ---- launch, synchronise
-    const float *d_inf = reinterpret_cast<const float *>(d_in.get());
+    const float *d_inf = reinterpret_cast<const float *>(d_in.get() + G);
+    float *d_outf = reinterpret_cast<float *>(run.d_out.get() + G);
+    Route r = dop->route;
     std::unique_ptr<AsmKernels> asm_kernels;                  // no handle here: an owner for this call, when the op runs an assembly kernel
     if (up) {
-        HIP_TRY(launch_upsample2x_bilinear(d_in, Cin, d_out, Cin, 0, B, H, W, Cin, kind, rt, nullptr));
+        HIP_TRY(launch_upsample2x_bilinear(d_inf, ldc, d_outf, ldo, co_off, B, H, W, Cin, kind, rt, nullptr));
     } else if (first) {
-        HIP_TRY(launch_conv3x3_first(d_in, d_lut, d_w, d_b, d_out, B, H, W, Cin, Cout, Cout, kind, rt, nullptr));
+        HIP_TRY(launch_conv3x3_first(d_in.get() + G, d_lut, d_w, d_b, d_outf, B, H, W, Cin, Cout, ldo, kind, rt, nullptr));
     } else if (pool) {
-        HIP_TRY(launch_maxpool2x2(d_inf, Cin, d_out, B, H, W, Cin, nullptr));
+        if (kind) HIP_TRY(launch_maxpool2x2_u16(d_inf, ldc, d_outf, B, H, W, Cin, nullptr));
+        else HIP_TRY(launch_maxpool2x2(d_inf, ldc, d_outf, B, H, W, Cin, nullptr));
     } else {
         ConvArgs a{};
         a.rt = rt;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = Cin; a.Cout = Cout; a.CoutPad = (int)packed_npad(pk, Cout); a.ldo = Cout; a.co_off = 0;
+        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldc = ldc; a.Cout = Cout; a.CoutPad = (int)packed_npad(pk, Cout); a.ldo = ldo; a.co_off = co_off;
         a.relu = relu;
         a.out_lp = lp_out ? 1 : 0;
-        if (want_pool) { a.pool_out = d_pool; a.pool_ld = Cout; }
-        a.in = d_inf; a.wpk = d_w; a.bias = d_b; a.out = d_out;
+        if (want_pool) { a.pool_out = reinterpret_cast<float *>(run.d_pool.get() + G); a.pool_ld = pool_ld; }
+        a.in = d_inf; a.wpk = d_w; a.bias = d_b; a.out = d_outf;
         if (pk == Pack::WINO4 || pk == Pack::TAPS) a.wpk4 = d_w;
-        Route r = dop->routed ? route_wino4(a) : dop->route;
+        if (dop->routed) r = route_wino4(a);
         if (r == Route::CONV_WINO4A || r == Route::CONV_WINO4B) {
             asm_kernels.reset(new AsmKernels(device));
             if (dop->routed && !asm_kernels->available()) {   // the routing is told, as a handle's is at create
@@ -258,17 +291,50 @@ int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int 
         HIP_TRY(launch_route(r, a, asm_kernels.get(), nullptr));
     }
     HIP_TRY(hipDeviceSynchronize());
+    run.guard = G; run.out_bytes = 2 * G + out_bytes; run.pool_bytes = want_pool ? 2 * G + pool_bytes : 0;
+    run.out_npix = out_npix; run.pool_npix = out_npix / 4;
+    run.es = (int)out_es; run.lp_kind = out16 ? kind : 0; run.C = Co; run.ldo = ldo; run.co_off = co_off; run.pool_ld = pool_ld;
+    run.pooled = want_pool;
+    run.kernel = route_name(r);
+    return MI_UNET_OK;
+}
 
-    // ---- download and convert
-    const float *d_res = want_pool ? d_pool.get() : d_out.get();
-    if (want_pool) out_n /= 4;
-    if (!out16) {
-        HIP_TRY(hipMemcpy(out, d_res, sizeof(float) * out_n, hipMemcpyDeviceToHost));
-        return MI_UNET_OK;
-    }
-    std::vector<uint16_t> out16v(out_n);
-    HIP_TRY(hipMemcpy(out16v.data(), d_res, sizeof(uint16_t) * out_n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < out_n; ++i) out[i] = kind == 2 ? fp16_to_float(out16v[i]) : bf16_to_float(out16v[i]);
+}  // namespace
+
+extern "C" {
+
+int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
+                        const float *scale, const float *shift, int Cout, int relu, float *out)
+{
+    if (!out) return fail(MI_UNET_EARG, "layer_debug: bad argument");
+    DebugRun run;
+    if (int rc = run_layer(device, op, in, B, H, W, Cin, w, scale, shift, Cout, relu, DebugLayout{}, run)) return rc;
+    // ---- download and convert: the full-size tensor, or for _pool the pooled one
+    if (run.pooled) return download_tensor(nullptr, run.d_pool.get() + run.guard, 8 * run.es, run.lp_kind, run.pool_npix, run.C, run.pool_ld, out);
+    return download_tensor(nullptr, run.d_out.get() + run.guard, 8 * run.es, run.lp_kind, run.out_npix, run.C, run.ldo, out);
+}
+
+int mi_unet_layer_debug_strided(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
+                                const float *scale, const float *shift, int Cout, int relu, const mi_unet_debug_layout *layout,
+                                void *out_raw, size_t out_cap, void *pool_raw, size_t pool_cap, mi_unet_debug_strided_info *info)
+{
+    if (!layout || !out_raw || !info) return fail(MI_UNET_EARG, "layer_debug_strided: null argument");
+    if (layout->ldc < 0 || layout->ldo < 0 || layout->pool_ld < 0 || layout->guard_bytes < 0)
+        return fail(MI_UNET_EARG, "layer_debug_strided: negative stride or guard");
+    DebugLayout lay;
+    lay.ldc = layout->ldc; lay.ldo = layout->ldo; lay.co_off = layout->co_off; lay.pool_ld = layout->pool_ld; lay.guard = (size_t)layout->guard_bytes;
+    DebugRun run;
+    if (int rc = run_layer(device, op, in, B, H, W, Cin, w, scale, shift, Cout, relu, lay, run)) return rc;
+    *info = mi_unet_debug_strided_info{};
+    info->elem_bytes = run.es;
+    info->out_bytes = run.out_bytes;
+    info->pool_bytes = run.pool_bytes;
+    snprintf(info->kernel, sizeof info->kernel, "%s", run.kernel.c_str());
+    if (out_cap < run.out_bytes || (run.pooled && (!pool_raw || pool_cap < run.pool_bytes)))
+        return fail(MI_UNET_EARG, "layer_debug_strided: a result buffer is smaller than the allocation it receives (see info)");
+    // ---- the complete allocations as they are: guards and gaps included, nothing converted
+    HIP_TRY(hipMemcpy(out_raw, run.d_out, run.out_bytes, hipMemcpyDeviceToHost));
+    if (run.pooled) HIP_TRY(hipMemcpy(pool_raw, run.d_pool, run.pool_bytes, hipMemcpyDeviceToHost));
     return MI_UNET_OK;
 }
 

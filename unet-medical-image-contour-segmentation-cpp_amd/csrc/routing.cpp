@@ -31,8 +31,8 @@ bool conv3x3_wino4a_shape_ok(const ConvArgs &a)
     if (a.wpk4 == nullptr || a.head_w != nullptr || a.out_lp) return false;
     if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.H % 16 || a.W % 16) return false;
     if (a.Cin % 32 || a.Cin < 64 || a.ldc % 4 || a.ldc < a.Cin) return false;
-    if (a.Cout % 128 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4) return false;
-    if (a.pool_out != nullptr && a.pool_ld % 4) return false;
+    if (a.Cout % 128 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4 || a.co_off < 0 || a.ldo < a.co_off + a.Cout) return false;
+    if (a.pool_out != nullptr && (a.pool_ld % 4 || a.pool_ld < a.Cout)) return false;
     const long long lim = 1ll << 31;
     if ((long long)a.H * a.W * a.ldc * 4 >= lim || (long long)a.H * a.W * a.ldo * 4 >= lim) return false;
     if ((long long)(a.Cin / 16) * 36 * a.CoutPad * 64 >= lim) return false;
@@ -47,8 +47,8 @@ bool conv3x3_wino4b_shape_ok(const ConvArgs &a)
     if (a.wpk4 == nullptr || a.head_w != nullptr || a.out_lp || a.first_img != nullptr) return false;
     if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.H % 16 || a.W % 32) return false;
     if (a.Cin % 32 || a.Cin < 64 || a.ldc % 4 || a.ldc < a.Cin) return false;
-    if (a.Cout % 64 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4) return false;
-    if (a.pool_out != nullptr && a.pool_ld % 4) return false;
+    if (a.Cout % 64 || a.CoutPad < a.Cout || a.ldo % 4 || a.co_off % 4 || a.co_off < 0 || a.ldo < a.co_off + a.Cout) return false;
+    if (a.pool_out != nullptr && (a.pool_ld % 4 || a.pool_ld < a.Cout)) return false;
     const long long lim = 1ll << 31;
     if ((long long)a.H * a.W * a.ldc * 4 >= lim || (long long)a.H * a.W * a.ldo * 4 >= lim) return false;
     if ((long long)(a.Cin / 16) * 36 * a.CoutPad * 64 >= lim) return false;
@@ -75,7 +75,8 @@ bool conv3x3_lpr_shape_ok(const ConvArgs &a)
     }
     if ((a.Cin != 32 && a.Cin != 64) || (a.Cout != 32 && a.Cout != 64)) return false;
     if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < a.Cout) return false;
-    if (a.pool_out != nullptr && (a.pool_ld % 8 || (a.H & 1) || (a.W & 1))) return false;
+    if (a.ldc < a.Cin || a.co_off < 0 || a.ldo < a.co_off + a.Cout) return false;
+    if (a.pool_out != nullptr && (a.pool_ld % 8 || a.pool_ld < a.Cout || (a.H & 1) || (a.W & 1))) return false;
     // 32-bit byte offsets inside one image
     return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && (long long)a.H * a.W * a.ldo * 2 < (1ll << 31);
 }
@@ -93,6 +94,7 @@ bool conv3x3_lprk_shape_ok(const ConvArgs &a)
     if (a.wpk == nullptr || !a.out_lp || a.head_w != nullptr || a.pool_out != nullptr) return false;
     if (a.Cin != LPRK_CIN || a.Cout != LPRK_COUT) return false;
     if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < a.Cout) return false;
+    if (a.ldc < a.Cin || a.co_off < 0 || a.ldo < a.co_off + a.Cout) return false;
     return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && (long long)a.H * a.W * a.ldo * 2 < (1ll << 31);
 }
 
@@ -103,6 +105,7 @@ bool convT2x2_lpr_shape_ok(const ConvArgs &a)
     if (a.wpk == nullptr || !a.out_lp || a.head_w != nullptr || a.pool_out != nullptr) return false;
     if (!((a.Cin == 64 && a.Cout == 32) || (a.Cin == 128 && a.Cout == 64) || (a.Cin == 256 && a.Cout == 128))) return false;
     if (a.ldc % 8 || a.ldo % 8 || a.co_off % 8 || a.CoutPad < 4 * a.Cout) return false;
+    if (a.ldc < a.Cin || a.co_off < 0 || a.ldo < a.co_off + a.Cout) return false;
     return (long long)a.H * a.W * a.ldc * 2 < (1ll << 31) && 4ll * a.H * a.W * a.ldo * 2 < (1ll << 31);
 }
 

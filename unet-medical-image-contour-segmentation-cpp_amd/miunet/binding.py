@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MIUNET_LIB") or os.path.join(PKG_DIR, "libmiunet.so")
 EXPORTS = [
     "mi_unet_default_config", "mi_unet_create", "mi_unet_load_weights", "mi_unet_load_weights_from_memory",
     "mi_unet_infer_u8", "mi_unet_infer_u8_device", "mi_unet_infer_raw16", "mi_unet_set_postprocess", "mi_unet_postprocess_masks", "mi_unet_extract_contours", "mi_unet_segment_raw16", "mi_unet_set_stream", "mi_unet_sync", "mi_unet_timer_begin",
-    "mi_unet_timer_end", "mi_unet_set_profiling", "mi_unet_get_kernel_stats", "mi_unet_layer_debug", "mi_unet_destroy",
+    "mi_unet_timer_end", "mi_unet_set_profiling", "mi_unet_get_kernel_stats", "mi_unet_layer_debug", "mi_unet_layer_debug_strided", "mi_unet_destroy",
     "mi_unet_last_error", "mi_unet_device_count", "mi_unet_clone",
     "mi_unet_debug_layer_count", "mi_unet_debug_layer_info", "mi_unet_debug_capture", "mi_unet_last_stage_ms", "mi_unet_numeric_guard", "mi_unet_host_alloc", "mi_unet_host_free",
     "mi_unet_group_create", "mi_unet_group_clone", "mi_unet_group_size", "mi_unet_group_handle", "mi_unet_group_load_weights",
@@ -58,6 +58,14 @@ class LayerInfo(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["name"], d["kernel"], d["kind"] = self.name.decode(), self.kernel.decode(), self.KINDS[self.kind]
         return d
+
+
+class DebugLayout(C.Structure):
+    _fields_ = [("ldc", C.c_int), ("ldo", C.c_int), ("co_off", C.c_int), ("pool_ld", C.c_int), ("guard_bytes", C.c_longlong)]
+
+
+class DebugStridedInfo(C.Structure):
+    _fields_ = [("elem_bytes", C.c_int), ("out_bytes", C.c_ulonglong), ("pool_bytes", C.c_ulonglong), ("kernel", C.c_char * 32)]
 
 
 class TileBlend(C.Structure):
@@ -231,6 +239,9 @@ def lib():
         L.mi_unet_get_kernel_stats.argtypes = [C.c_void_p, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]
         L.mi_unet_layer_debug.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mi_unet_layer_debug_strided.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DebugLayout), C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(DebugStridedInfo)]
         L.mi_unet_destroy.argtypes = [C.c_void_p]
         L.mi_unet_destroy.restype = None
         L.mi_unet_default_config.argtypes = [C.POINTER(Config)]
@@ -966,33 +977,69 @@ class Group:
         return tiles, masks, cont
 
 
+def _layer_debug_shapes(op, x, w):
+    """(pooled, weights, Cout, output shape [B, Ho, Wo, C], pooled shape or None) of a layer hook call"""
+    b, h, ww, cin = x.shape
+    if op.endswith("_lpout"):         # 16-bit conv ops: the output tensor is 16-bit on the device too
+        op = op[:-6]
+    pooled = op.endswith("_pool")     # conv3x3 ops: the fused 2x2 max-pooled tensor
+    if pooled:
+        op = op[:-5]
+    cout = 0
+    if op.startswith("conv3x3"):
+        w = np.ascontiguousarray(w, np.float32)
+        cout = w.shape[0]
+        shape = (b, h, ww, cout)
+    elif op.startswith("convT2x2"):
+        w = np.ascontiguousarray(w, np.float32)
+        cout = w.shape[1]
+        shape = (b, 2 * h, 2 * ww, cout)
+    elif op in ("maxpool", "maxpool_bf16", "maxpool_fp16"):            # 16-bit: non-negative input, rounded first
+        shape = (b, h // 2, ww // 2, cin)
+    elif op in ("upsample2x", "upsample2x_bf16", "upsample2x_fp16"):   # bilinear x2, align_corners=True (16-bit: input rounded first)
+        shape = (b, 2 * h, 2 * ww, cin)
+    else:
+        raise ValueError(op)
+    return pooled, w, cout, shape, (b, h // 2, ww // 2, cout) if pooled else None
+
+
 def layer_debug(op, x, w=None, scale=None, shift=None, relu=False, device=0):
     """Run one layer kernel on host NHWC fp32 data (parity hook)."""
     x = np.ascontiguousarray(x, np.float32)
     b, h, ww, cin = x.shape
-    cout = 0
-    full_op = op
-    if op.endswith("_lpout"):         # 16-bit conv ops: the output tensor is 16-bit on the device too (converted back here)
-        op = op[:-6]
-    pooled = op.endswith("_pool")     # conv3x3 ops: return the fused 2x2 max-pooled tensor instead of the full-size one
-    if pooled:
-        op = op[:-5]
-    if op.startswith("conv3x3"):
-        w = np.ascontiguousarray(w, np.float32)
-        cout = w.shape[0]
-        out = np.empty((b, h // 2, ww // 2, cout) if pooled else (b, h, ww, cout), np.float32)
-    elif op.startswith("convT2x2"):
-        w = np.ascontiguousarray(w, np.float32)
-        cout = w.shape[1]
-        out = np.empty((b, 2 * h, 2 * ww, cout), np.float32)
-    elif op == "maxpool":
-        out = np.empty((b, h // 2, ww // 2, cin), np.float32)
-    elif op in ("upsample2x", "upsample2x_bf16", "upsample2x_fp16"):   # bilinear x2, align_corners=True (16-bit: input rounded first)
-        out = np.empty((b, 2 * h, 2 * ww, cin), np.float32)
-    else:
-        raise ValueError(op)
+    pooled, w, cout, shape, pshape = _layer_debug_shapes(op, x, w)
+    out = np.empty(pshape if pooled else shape, np.float32)
     scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
     shift = None if shift is None else np.ascontiguousarray(shift, np.float32)
-    _check(lib().mi_unet_layer_debug(device, full_op.encode(), _ptr(x), b, h, ww, cin, _ptr(w), _ptr(scale), _ptr(shift), cout,
+    _check(lib().mi_unet_layer_debug(device, op.encode(), _ptr(x), b, h, ww, cin, _ptr(w), _ptr(scale), _ptr(shift), cout,
                                      int(relu), _ptr(out)))
     return out
+
+
+def layer_debug_strided(op, x, w=None, scale=None, shift=None, relu=False, ldc=0, ldo=0, co_off=0, pool_ld=0, guard_bytes=0, device=0):
+    """The layer hook in a strided layout between poisoned guards (mi_unet_layer_debug_strided).  Returns a dict: `out` / `pool` the
+    complete device allocations as uint8 arrays (pool None without _pool), `elem_bytes`, `kernel` (the route that ran), and the
+    geometry of either tensor as the checker takes it: `out_layout` / `pool_layout` = (npix shape [B, Ho, Wo], C, ld, co_off, guard)."""
+    x = np.ascontiguousarray(x, np.float32)
+    b, h, ww, cin = x.shape
+    pooled, w, cout, shape, pshape = _layer_debug_shapes(op, x, w)
+    c = shape[3]
+    ld, pld = ldo or c, pool_ld or c
+    # room for 4-byte elements; the library says which size the op stores (info.elem_bytes) and how much of the buffers it filled
+    out = np.empty(2 * guard_bytes + shape[0] * shape[1] * shape[2] * ld * 4, np.uint8)
+    pool = np.empty(2 * guard_bytes + pshape[0] * pshape[1] * pshape[2] * pld * 4, np.uint8) if pooled else None
+    scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
+    shift = None if shift is None else np.ascontiguousarray(shift, np.float32)
+    lay = DebugLayout(ldc, ldo, co_off, pool_ld, guard_bytes)
+    info = DebugStridedInfo()
+    _check(lib().mi_unet_layer_debug_strided(device, op.encode(), _ptr(x), b, h, ww, cin, _ptr(w), _ptr(scale), _ptr(shift), cout, int(relu),
+                                             C.byref(lay), _ptr(out), out.nbytes, _ptr(pool), 0 if pool is None else pool.nbytes,
+                                             C.byref(info)))
+    es = info.elem_bytes
+    assert info.out_bytes == 2 * guard_bytes + shape[0] * shape[1] * shape[2] * ld * es
+    out = out[:info.out_bytes]
+    if pooled:
+        assert info.pool_bytes == 2 * guard_bytes + pshape[0] * pshape[1] * pshape[2] * pld * es
+        pool = pool[:info.pool_bytes]
+    return {"out": out, "pool": pool, "elem_bytes": es, "kernel": info.kernel.decode(),
+            "out_layout": (shape[:3], c, ld, co_off, guard_bytes), "pool_layout": (pshape[:3], c, pld, 0, guard_bytes) if pooled else None}
