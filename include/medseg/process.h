@@ -71,6 +71,30 @@ mi_unet_measure get_measure();
 bool set_truth_dir(const std::string &dir);
 std::string get_truth_dir();
 
+// The images of a batch as the slices of one volume (mi_unet_volume_components in include/mi_unet.h).  With it on,
+// process_image_batch treats its paths, in the order given, as slices z = 0, 1, ...: whatever the target list is, the batch takes the
+// per-target route; the K final 0 / 255 planes of every image are collected into one [K][D][H][W] stack at the TILE size (a slice that
+// failed is an all-zero plane), and after the last device call ONE pass labels every target's stack as a volume -- one
+// mi_unet_volume_components call per target with values = { 255 } on the group's first engine, mi_unet_volume_components_host under
+// MEDSEG_HOST_POSTPROCESS=1.  It writes <output_dir>/volume_report.json: "slices" (base names in z order), "missing" (the slices that
+// failed), "connectivity", "min_voxels", "keep_largest", "spacing" and "targets", per target "label", "found", "kept" and "components"
+// in table order (at most MI_UNET_VOLUME_MAX_TABLE), per component "voxels", "kept", "bbox" [x0, y0, z0, x1, y1, z1], "centroid_mm",
+// "volume_mm3", "surface_mm2", "extent_mm" (mi_unet_volume_derive).  Only when a filter is active (min_voxels > 0 or keep_largest > 0)
+// it also writes per slice <base>_volume_mask.png, or <base>_volume_mask_class<cls>.png under a non-default target list: the filtered
+// stack, 0 / 255.  Coordinates and spacing are those of the TILE grid -- the masks are at the tile size; spacing_x / _y are millimetres
+// per tile pixel, spacing_z per slice; an image's scale_x / scale_y to its own pixels are in its <base>_original_sizes.json.  Every
+// artefact that exists without the setting is written exactly as before, and with it off (the default) nothing changes at all.
+// process_single_image is one slice and ignores the setting.  Needs no engine and survives initialize_engine.  false, message on
+// stderr, setting unchanged: a connectivity other than 6, 18, 26, a negative min_voxels or keep_largest, a spacing that is not finite
+// and positive.
+struct Volume {
+    bool on = false;
+    int connectivity = 26, min_voxels = 0, keep_largest = 0;
+    double spacing_x = 1.0, spacing_y = 1.0, spacing_z = 1.0;
+};
+bool set_volume(const Volume &volume);
+Volume get_volume();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

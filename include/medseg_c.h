@@ -58,6 +58,10 @@ void medseg_get_measure(int *on, int *channel);
  * medseg_get_truth_dir copies the directory (no terminator) into out and returns its length, or -1 when cap is too small. */
 int medseg_set_truth_dir(const char *dir);
 int medseg_get_truth_dir(char *out, int cap);
+/* The images of a batch as the slices of one volume: MedicalSeg::set_volume / get_volume (include/medseg/process.h).  0 on success;
+ * medseg_get_volume fills the seven values (spacing: three doubles, x y z). */
+int medseg_set_volume(int on, int connectivity, int min_voxels, int keep_largest, double spacing_x, double spacing_y, double spacing_z);
+void medseg_get_volume(int *on, int *connectivity, int *min_voxels, int *keep_largest, double *spacing_xyz);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

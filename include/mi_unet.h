@@ -426,6 +426,66 @@ int mi_unet_score_labels_host(const uint8_t *pred, const uint8_t *truth, int B, 
                               const mi_unet_score_opts *opts, mi_unet_score *scores /* [B][n] */, int64_t *confusion, int64_t *skipped);
 int mi_unet_score_derive(const mi_unet_score *s, mi_unet_score_metrics *out);
 
+/* ---- Volume components: a stack of masks labelled as one volume, size filter, volumetry -----------------------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.
+ * Input is one byte volume masks, u8 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), and n
+ * byte values, 1 <= n <= MI_UNET_VOLUME_MAX_VALUES.  Plane k is the set S = { masks == values[k] } of the volume; planes are independent.
+ *   ADJACENCY  two voxels of S are adjacent when they differ by at most 1 on every axis and, connectivity 6: on exactly one axis;
+ *              18: on at most two axes; 26: on up to three.  A component is a maximal connected subset of S.  With D = 1, connectivity 6
+ *              is the 2-D 4-connectivity and 18 / 26 are the 8-connectivity.
+ *   FIELDS     per component: voxels; first = its raster-first voxel, z * H * W + y * W + x; the inclusive bounding box; sx, sy, sz = the
+ *              sums of x, y, z over its voxels; faces_x / _y / _z = the voxel faces perpendicular to that axis between a voxel of the
+ *              component and a 6-neighbour that is not in S.  Positions outside the volume are not in S (the frame rule of
+ *              mi_unet_region.edges), and the walls of a closed cavity count.  Every 6-neighbour in S belongs to the same component under
+ *              all three connectivities, so "not in S" is the same as "not in the component".
+ *   ORDER      the components of a plane are ordered by voxels descending, ties by first ascending; first is unique, so the order is
+ *              total.  As one integer the key is (voxels << 31) | (2^31 - 1 - first), descending.
+ *   FILTER     the component at position r of that order is kept iff voxels >= min_voxels and (keep_largest == 0 or r < keep_largest).
+ *              out [n][D][H][W] is values[k] where the voxel's component is kept and 0 elsewhere; it may be masks itself when n == 1,
+ *              and may be NULL.  The filter never depends on cap.
+ *   COUNTS     found[k] = the components of the plane, kept[k] = the number kept; both always exact, whatever cap is.
+ *   TABLE      table[k] ([n][cap]) holds the first min(found, cap) components in the order above; the entries behind them are all-zero.
+ *   IDS        ids [n][D][H][W] (or NULL) holds per voxel: 1 + the table index of a kept component that is in the table; -1 for a voxel
+ *              of a kept component that did not fit; 0 everywhere else.
+ * Limits: D, H, W >= 1; n * D * H * W < 2^31, so every index is an int, sx < 2^62 and a face count is at most 6 * 2^31; values in
+ * 0 .. 255 and not repeated; cap in 1 .. MI_UNET_VOLUME_MAX_TABLE; connectivity in { 6, 18, 26 }; min_voxels >= 0; keep_largest >= 0.
+ * opts == NULL is { 26, 0, 0 }.
+ * mi_unet_volume_components takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued and no output written: a null
+ * masks, values, table, found or kept; D, H or W < 1; n outside 1 .. MI_UNET_VOLUME_MAX_VALUES; a value outside 0 .. 255 or repeated;
+ * n * D * H * W >= 2^31; cap outside 1 .. MI_UNET_VOLUME_MAX_TABLE; a connectivity other than 6, 18, 26; min_voxels < 0; keep_largest < 0.
+ * A workspace that cannot be allocated is MI_UNET_EHIP with a message, before anything runs; the handle stays usable.
+ * mi_unet_volume_components_host is the definition as pure host arithmetic (needs no device), same arguments without the handle, same
+ * bytes.
+ * mi_unet_volume_derive is pure host arithmetic: MI_UNET_EARG for a null pointer, voxels < 1, or a spacing that is not finite and > 0.
+ * A voxel is a box of spacing_xyz[0] x [1] x [2] millimetres and voxel 0 spans 0 .. 1 of the grid:
+ *   volume_mm3 = voxels * sx * sy * sz;  surface_mm2 = faces_x * sy * sz + faces_y * sx * sz + faces_z * sx * sy (s = the spacing);
+ *   c*_mm = (sum / voxels + 0.5) * spacing of the axis;  extent_*_mm = (hi - lo + 1) * spacing of the axis.
+ * The surface is that of the voxel boxes (a crack surface): it overestimates the smooth surface the voxels sample, by up to a factor
+ * 1.5 for a sphere, and does not converge to it as the grid is refined.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VOLUME_MAX_VALUES 8
+#define MI_UNET_VOLUME_MAX_TABLE 4096
+typedef struct mi_unet_vcomp {      /* 88 bytes, no padding */
+    int32_t voxels;                 /* voxels of the component */
+    int32_t first;                  /* its raster-first voxel: z*H*W + y*W + x */
+    int32_t x0, y0, z0, x1, y1, z1; /* bounding box, inclusive */
+    int32_t kept;                   /* 1 when the filter keeps it, else 0 */
+    int32_t value;                  /* echo of the plane's value */
+    int64_t faces_x, faces_y, faces_z; /* voxel faces perpendicular to x / y / z towards a 6-neighbour that is not in the set */
+    int64_t sx, sy, sz;             /* sums of x, y, z over the component */
+} mi_unet_vcomp;
+typedef struct mi_unet_volume_opts { int connectivity; int min_voxels; int keep_largest; } mi_unet_volume_opts; /* default { 26, 0, 0 } */
+typedef struct mi_unet_vcomp_metrics { double volume_mm3, surface_mm2, cx_mm, cy_mm, cz_mm, extent_x_mm, extent_y_mm, extent_z_mm; } mi_unet_vcomp_metrics;
+int mi_unet_volume_components(mi_unet_t *h, const uint8_t *masks /* [D][H][W] host */, int D, int H, int W,
+                              const int *values, int n, const mi_unet_volume_opts *opts,
+                              uint8_t *out /* [n][D][H][W] or NULL */, int32_t *ids /* [n][D][H][W] or NULL */,
+                              mi_unet_vcomp *table /* [n][cap] */, int cap, int32_t *found /* [n] */, int32_t *kept /* [n] */);
+int mi_unet_volume_components_host(const uint8_t *masks, int D, int H, int W, const int *values, int n, const mi_unet_volume_opts *opts,
+                                   uint8_t *out, int32_t *ids, mi_unet_vcomp *table, int cap, int32_t *found, int32_t *kept);
+int mi_unet_volume_derive(const mi_unet_vcomp *c, const double spacing_xyz[3], mi_unet_vcomp_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

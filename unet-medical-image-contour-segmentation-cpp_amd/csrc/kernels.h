@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, volume.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 // The hipcc kernels are part of the library's own code object.  The two assembly kernels (csrc/asm/) are code objects of their own,
 // embedded as byte blobs: an AsmKernels (below) loads them for one device when an engine is created and unloads them with the last
 // handle that holds it.  libmiunet.so keeps no process-wide resource: no module, no device memory, no stream outlives its handles.
@@ -11,6 +11,7 @@
 
 struct mi_unet_region;      // include/mi_unet.h
 struct mi_unet_score;
+struct mi_unet_vcomp;
 
 namespace miunet {
 
@@ -310,5 +311,24 @@ struct ScoreValues { int n = 0; int v[SCORE_MAX_VALUES] = {}; };
 size_t score_workspace_bytes(int B, int H, int W, int n, int classes);
 hipError_t launch_score(const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const ScoreValues &vals, int quantile_ppm,
                         int classes, void *ws, ::mi_unet_score *scores, const unsigned long long **conf, hipStream_t s);
+
+// Volume components (volume.hip; include/mi_unet.h: mi_unet_volume_components).  masks u8 [D][H][W] on the device; plane
+// k is the set { masks == v[k] }.  One launch sequence for all n planes:
+//   init    : run-start parents inside 64-lane segments; a run ends at x = W - 1 (so at every row, slice and plane end)
+//   merge   : unions with the earlier neighbours the connectivity allows, the implied ones left out
+//   roots   : every root takes a slot of its plane (a per-plane cursor) and clears the slot's statistics
+//   stats   : flatten + voxels, bounding box, face counts and coordinate sums, carried per root across a wave's segments
+//   keys    : the 62-bit order key of every slot; the roots that pass min_voxels are counted
+//   select  : the keep_largest-th and the cap-th largest key of every plane, an exact radix select (11 bits a pass)
+//   table   : the selected keys of a plane sorted by one workgroup in LDS -> table entries and the slots' table indices
+//   write   : out and ids in one pass
+// out u8 [n][D][H][W]; ids i32 [n][D][H][W] or null; table [n][cap]; counts i32 [2][n]: found, then kept.  Workspace:
+// volume_workspace_bytes(D, H, W, n), not zeroed by the caller.  n * D * H * W < 2^31, cap <= VOLUME_MAX_TABLE.
+constexpr int VOLUME_MAX_VALUES = 8;                    // = MI_UNET_VOLUME_MAX_VALUES
+constexpr int VOLUME_MAX_TABLE = 4096;                  // = MI_UNET_VOLUME_MAX_TABLE
+struct VolumeArgs { int D = 0, H = 0, W = 0, n = 0, cap = 0, connectivity = 26, min_voxels = 0, keep_largest = 0; int v[VOLUME_MAX_VALUES] = {}; };
+size_t volume_workspace_bytes(int D, int H, int W, int n);
+hipError_t launch_volume_components(const uint8_t *masks, const VolumeArgs &a, uint8_t *out, int32_t *ids, ::mi_unet_vcomp *table,
+                                    int32_t *counts, void *ws, hipStream_t s);
 
 }  // namespace miunet

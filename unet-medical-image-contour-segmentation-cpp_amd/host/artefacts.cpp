@@ -2,7 +2,9 @@
 // routes.cpp).
 #include "artefacts.h"
 
+#include <algorithm>
 #include <chrono>
+#include <fstream>
 #include <future>
 #include <stdexcept>
 
@@ -81,6 +83,26 @@ ArtefactTimes write_image_artefacts(const ImageArtefacts &a)
     if (!norm_ok) throw std::runtime_error("Preprocessing failed");
     if (!mask_ok) throw std::runtime_error("Failed to save mask");
     return times;
+}
+
+void write_volume_artefacts(const VolumeArtefacts &a)
+{
+    std::ofstream o(a.output_dir + "/volume_report.json", std::ios::binary);
+    o << a.report;
+    o.close();
+    if (!o) throw std::runtime_error("Failed to save volume report");
+    if (!a.out) return;
+    const std::vector<mi_unet_target> &targets = *a.targets;
+    const size_t hw = (size_t)a.height * a.width, D = a.bases->size();
+    for (size_t t = 0; t < targets.size(); ++t)
+        for (size_t z = 0; z < D; ++z) {
+            if ((*a.bases)[z].empty()) continue;
+            medseg::Image8 m(a.height, a.width, 1);
+            std::copy(a.out + (t * D + z) * hw, a.out + (t * D + z + 1) * hw, m.data.begin());
+            const std::string name = is_default(targets) ? "_volume_mask.png" : "_volume_mask_class" + std::to_string(targets[t].cls) + ".png";
+            if (!medseg::write_png(a.output_dir + "/" + (*a.bases)[z] + name, m, /*level0=*/true))
+                throw std::runtime_error("Failed to save volume mask");
+        }
 }
 
 }  // namespace MedicalSeg

@@ -175,6 +175,16 @@ int medseg_get_truth_dir(char *out, int cap)
     memcpy(out, s.data(), s.size());
     return (int)s.size();
 }
+int medseg_set_volume(int on, int connectivity, int min_voxels, int keep_largest, double spacing_x, double spacing_y, double spacing_z)
+{
+    return MedicalSeg::set_volume({ on != 0, connectivity, min_voxels, keep_largest, spacing_x, spacing_y, spacing_z }) ? 0 : 1;
+}
+void medseg_get_volume(int *on, int *connectivity, int *min_voxels, int *keep_largest, double *spacing_xyz)
+{
+    const MedicalSeg::Volume v = MedicalSeg::get_volume();
+    *on = v.on; *connectivity = v.connectivity; *min_voxels = v.min_voxels; *keep_largest = v.keep_largest;
+    spacing_xyz[0] = v.spacing_x; spacing_xyz[1] = v.spacing_y; spacing_xyz[2] = v.spacing_z;
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

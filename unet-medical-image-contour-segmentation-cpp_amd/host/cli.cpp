@@ -146,6 +146,7 @@ public:
         table_["measure"] = [this](const Words &w) { cmd_measure(w); return true; };
         table_["morph"] = [this](const Words &w) { cmd_morph(w); return true; };
         table_["truth"] = [this](const Words &w) { cmd_truth(w); return true; };
+        table_["volume"] = [this](const Words &w) { cmd_volume(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -163,6 +164,7 @@ public:
             "  measure on [channel]|off      - Measure every contoured region on the device (a \"region\" object per shape of the JSON)",
             "  morph rect|disc <open_r> [close_r]|default - Element and radii of the mask clean-up (default: rect 1 0, the 3x3 open)",
             "  truth <dir>|off               - Score every mask against <dir>/<base>_labels.raw into <base>_score.json (default: off)",
+            "  volume on [6|18|26] [min N] [keep N] [spacing sx sy sz]|off - Label the slices of a directory as one volume into volume_report.json",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -335,6 +337,48 @@ private:
         }
         const std::string cur = MedicalSeg::get_truth_dir();
         std::cout << "Truth: " << (cur.empty() ? std::string("off") : cur) << std::endl;
+    }
+
+    // volume on [6|18|26] [min N] [keep N] [spacing sx sy sz] | volume off | volume (prints the setting in force)
+    void cmd_volume(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::Volume v;
+            bool ok = (w[1] == "on" || w[1] == "off") && (w[1] == "on" || w.size() == 2);
+            v.on = w[1] == "on";
+            size_t at = 2;
+            if (ok && at < w.size() && to_int(w[at], v.connectivity)) ++at;
+            while (ok && at < w.size()) {
+                if (w[at] == "min" && at + 1 < w.size()) { ok = to_int(w[at + 1], v.min_voxels); at += 2; }
+                else if (w[at] == "keep" && at + 1 < w.size()) { ok = to_int(w[at + 1], v.keep_largest); at += 2; }
+                else if (w[at] == "spacing" && at + 3 < w.size()) {
+                    double *const sp[3] = { &v.spacing_x, &v.spacing_y, &v.spacing_z };
+                    for (int a = 0; a < 3 && ok; ++a) {
+                        try {
+                            size_t used = 0;
+                            *sp[a] = std::stod(w[at + 1 + a], &used);
+                            ok = used == w[at + 1 + a].size();
+                        } catch (const std::exception &) {
+                            ok = false;
+                        }
+                    }
+                    at += 4;
+                } else {
+                    ok = false;
+                }
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volume command (expected on [6|18|26] [min N] [keep N] [spacing sx sy sz] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume(v)) {
+                std::cerr << "Volume unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::Volume cur = MedicalSeg::get_volume();
+        std::cout << "Volume: " << (cur.on ? "on" : "off") << " " << cur.connectivity << " min " << cur.min_voxels << " keep " << cur.keep_largest
+                  << " spacing " << cur.spacing_x << " " << cur.spacing_y << " " << cur.spacing_z << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

@@ -32,6 +32,7 @@ struct Settings {
     std::vector<mi_unet_morph> morph{ { MI_UNET_MORPH_RECT, 1, 0 } };
     mi_unet_measure measure{ 0, 0 };
     std::string truth_dir;                                 // empty = off
+    Volume volume;                                         // off; no handle holds it (process_image_batch reads it)
     // Hands a handle every setting it can hold -- window, measure, morphology, targets -- and returns the first refusal.  This is the one
     // way a group, a lane or a thread's context gets its settings.  Only the _multi entry points read a handle's targets and morphology
     // (include/mi_unet.h), so pushing the default lists in front of any other call is harmless.  A refusal of the DEFAULT target list

@@ -9,6 +9,7 @@
 //           and graphs), created lazily on a thread's first single-image call, so concurrent callers do not serialise
 //   the sequential file loop of directory mode (src/main.cpp:148-164)
 //        -> process_image_batch: chunks of max_batch x devices images, sharded over the group
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
@@ -301,6 +302,25 @@ bool set_truth_dir(const std::string &dir)
                           /*handle_side=*/false);
 }
 
+bool set_volume(const Volume &volume)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume = volume;
+            const bool conn = volume.connectivity == 6 || volume.connectivity == 18 || volume.connectivity == 26;
+            bool spacing = true;
+            for (double v : { volume.spacing_x, volume.spacing_y, volume.spacing_z }) spacing = spacing && std::isfinite(v) && v > 0.0;
+            return std::string(!conn ? "volume: connectivity is 6, 18 or 26"
+                               : volume.min_voxels < 0 || volume.keep_largest < 0 ? "volume: negative min_voxels or keep_largest"
+                               : !spacing ? "volume: the spacing must be finite and positive" : "");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume: " << (volume.on ? "on" : "off") << ", connectivity " << volume.connectivity << ", min " << volume.min_voxels << ", keep "
+               << volume.keep_largest << ", spacing " << volume.spacing_x << " " << volume.spacing_y << " " << volume.spacing_z;
+        },
+        /*handle_side=*/false);
+}
+
 Settings current_settings()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -316,6 +336,7 @@ std::vector<Morph> get_morphology() { return current_settings().morph; }
 mi_unet_window get_window() { return Preprocess::get_window(); }
 mi_unet_measure get_measure() { return current_settings().measure; }
 std::string get_truth_dir() { return current_settings().truth_dir; }
+Volume get_volume() { return current_settings().volume; }
 
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }

@@ -17,6 +17,7 @@
 #include "../../include/medseg/postprocess.h"
 #include "../../include/medseg/preprocess.h"
 #include "facade.h"
+#include "json_io.h"
 #include "png_io.h"
 
 namespace fs = std::filesystem;
@@ -513,6 +514,91 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
     return ok;
 }
 
+// ---- set_volume: the images of a batch as the slices of one volume.  process_images_targets fills the stack as its images finish;
+// label_volume runs once, behind the last device call of the batch.
+struct VolumeStack {
+    VolumeStack(size_t slices, size_t targets, size_t hw) : planes(targets * slices * hw, 0), bases(slices), names(slices), D(slices), hw(hw) {}
+    // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t
+    void add(size_t i, const std::string &base, const uint8_t *pictures, size_t K)
+    {
+        for (size_t t = 0; t < K; ++t) std::copy(pictures + t * hw, pictures + (t + 1) * hw, planes.begin() + (t * D + i) * hw);
+        bases[i] = base;
+    }
+    std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
+    std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
+    size_t D, hw;
+};
+
+// One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
+// MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
+// fails no image.
+void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
+                  std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size(), D = st.D, hw = st.hw, cap = MI_UNET_VOLUME_MAX_TABLE;
+        const bool filter = v.min_voxels > 0 || v.keep_largest > 0;
+        std::vector<uint8_t> out(filter ? K * D * hw : 0);
+        std::vector<mi_unet_vcomp> table(K * cap);
+        std::vector<int32_t> found(K), kept(K);
+        const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
+        const int value = 255;
+        const bool device = h && device_postprocess_requested();
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const uint8_t *const in = st.planes.data() + t * D * hw;
+            uint8_t *const o = filter ? out.data() + t * D * hw : nullptr;
+            const int rc = device ? mi_unet_volume_components(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, nullptr,
+                                                              table.data() + t * cap, (int)cap, &found[t], &kept[t])
+                                  : mi_unet_volume_components_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, nullptr,
+                                                                   table.data() + t * cap, (int)cap, &found[t], &kept[t]);
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+        }
+        lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
+        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
+        std::ostringstream js;
+        auto names = [&](const char *key, bool missing) {
+            js << "  \"" << key << "\": [";
+            bool first = true;
+            for (size_t z = 0; z < D; ++z) {
+                if (missing && !st.bases[z].empty()) continue;
+                js << (first ? "" : ", ") << "\"" << medseg::json_escape(st.names[z]) << "\"";
+                first = false;
+            }
+            js << "],\n";
+        };
+        js << "{\n";
+        names("slices", false);
+        names("missing", true);
+        js << "  \"connectivity\": " << v.connectivity << ",\n  \"min_voxels\": " << v.min_voxels << ",\n  \"keep_largest\": " << v.keep_largest
+           << ",\n  \"spacing\": [" << json_number(spacing[0]) << ", " << json_number(spacing[1]) << ", " << json_number(spacing[2])
+           << "],\n  \"targets\": [";
+        for (size_t t = 0; t < K; ++t) {
+            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"found\": " << found[t] << ", \"kept\": " << kept[t]
+               << ", \"components\": [";
+            const size_t rows = std::min<size_t>((size_t)found[t], cap);
+            for (size_t r = 0; r < rows; ++r) {
+                const mi_unet_vcomp &c = table[t * cap + r];
+                mi_unet_vcomp_metrics m{};
+                if (mi_unet_volume_derive(&c, spacing, &m) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+                js << (r ? "," : "") << "\n      {\"voxels\": " << c.voxels << ", \"kept\": " << c.kept << ", \"bbox\": [" << c.x0 << ", " << c.y0 << ", "
+                   << c.z0 << ", " << c.x1 << ", " << c.y1 << ", " << c.z1 << "], \"centroid_mm\": [" << json_number(m.cx_mm) << ", "
+                   << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
+                   << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
+                   << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]}";
+            }
+            js << (rows ? "\n    " : "") << "]}";
+        }
+        js << "\n  ]\n}\n";
+        VolumeArtefacts a;
+        a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
+        a.height = g_cfg.height; a.width = g_cfg.width;
+        write_volume_artefacts(a);
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume error: ") + e.what());
+    }
+}
+
 // ---- a non-default target list (set_targets) or morphology (set_morphology): K masks per image, named <base>_mask_class<cls>.png, or
 // under the default target list the one <base>_mask.png.  One plain route for both entry points: read the files of a chunk,
 // one device call for the chunk (mi_unet_segment_raw16_multi on `ctx`, or its group form when ctx is null), then the artefacts image
@@ -521,7 +607,7 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
 // bit for bit).  Returns the number of images that succeeded.
 int process_images_targets(const std::vector<std::string> &paths, const std::vector<int> &widths, const std::vector<int> &heights,
                            const std::string &output_dir, mi_unet_t *ctx, const std::vector<mi_unet_target> &targets,
-                           const std::vector<mi_unet_morph> &morph, std::ostream &lg)
+                           const std::vector<mi_unet_morph> &morph, std::ostream &lg, VolumeStack *volume = nullptr)
 {
     const size_t n = paths.size(), hw = (size_t)g_cfg.height * g_cfg.width, K = targets.size();
     if (morph.size() != 1 && morph.size() != K)
@@ -590,6 +676,7 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                 write_image_artefacts(a);
                 if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
                 scored[k] = base_name;
+                if (volume) volume->add(i, base_name, &masks[k * K * hw], K);
                 ++ok;
             } catch (const std::exception &e) {
                 if (ctx) throw;
@@ -621,6 +708,15 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         const size_t n = raw_paths.size();
         if (widths.size() != n || heights.size() != n) throw std::runtime_error("widths/heights do not match raw_paths");
         const Settings settings = current_settings();
+        if (settings.volume.on && n > 0) {                     // the paths are the slices of one volume, whatever the target list is
+            std::lock_guard<std::mutex> lk(g_batch_mutex);
+            Collected lg{ log_file, {} };
+            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width);
+            for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
+            ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
+            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text);
+            return ok;
+        }
         if (!is_default(settings.targets) || !is_default(settings.morph)) {
             std::lock_guard<std::mutex> lk(g_batch_mutex);
             Collected lg{ log_file, {} };

@@ -34,6 +34,7 @@ EXPORTS = [
     "mi_unet_group_set_measure", "mi_unet_group_last_regions",
     "mi_unet_set_morph", "mi_unet_get_morph", "mi_unet_morph_element", "mi_unet_group_set_morph",
     "mi_unet_score_labels", "mi_unet_score_labels_host", "mi_unet_score_derive",
+    "mi_unet_volume_components", "mi_unet_volume_components_host", "mi_unet_volume_derive",
 ]
 
 
@@ -146,6 +147,48 @@ def _score_call(fn, head, pred, truth, values, quantile_ppm, classes):
     _check(fn(*head, _ptr(pred), _ptr(truth), b, hh, ww, _ptr(vals), vals.size, C.byref(ScoreOpts(int(quantile_ppm), int(classes))),
               _ptr(scores), _ptr(conf), _ptr(skipped)))
     return (scores, conf, skipped) if classes > 0 else scores
+
+
+class VComp(C.Structure):
+    """mi_unet_vcomp: 88 bytes, ten int32 then six int64; VCOMP_DTYPE is the same layout for numpy"""
+    _fields_ = [("voxels", C.c_int32), ("first", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("z1", C.c_int32), ("kept", C.c_int32), ("value", C.c_int32), ("faces_x", C.c_int64),
+                ("faces_y", C.c_int64), ("faces_z", C.c_int64), ("sx", C.c_int64), ("sy", C.c_int64), ("sz", C.c_int64)]
+
+
+VCOMP_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VComp._fields_])
+VOLUME_MAX_VALUES = 8
+VOLUME_MAX_TABLE = 4096
+
+
+class VolumeOpts(C.Structure):
+    _fields_ = [("connectivity", C.c_int), ("min_voxels", C.c_int), ("keep_largest", C.c_int)]
+
+
+class VCompMetrics(C.Structure):
+    _fields_ = [("volume_mm3", C.c_double), ("surface_mm2", C.c_double), ("cx_mm", C.c_double), ("cy_mm", C.c_double),
+                ("cz_mm", C.c_double), ("extent_x_mm", C.c_double), ("extent_y_mm", C.c_double), ("extent_z_mm", C.c_double)]
+
+
+def _volume_call(fn, head, masks, values, connectivity, min_voxels, keep_largest, cap, want_ids):
+    """mi_unet_volume_components (head = (handle,)) or its host form (head = ()): masks u8 [D,H,W] (or [H,W]: one slice) ->
+    (out u8 [n,D,H,W], table VCOMP_DTYPE [n, cap], found int32 [n], kept int32 [n], ids int32 [n,D,H,W] or None).  The library
+    checks the values."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    if masks.ndim != 3:
+        raise ValueError(f"masks {masks.shape} must be one u8 [D,H,W] array")
+    d, hh, ww = masks.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    n = max(vals.size, 1)
+    out = np.zeros((n, d, hh, ww), np.uint8)
+    ids = np.zeros((n, d, hh, ww), np.int32) if want_ids else None
+    table = np.zeros((n, max(int(cap), 1)), VCOMP_DTYPE)
+    found, kept = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, C.byref(VolumeOpts(int(connectivity), int(min_voxels), int(keep_largest))),
+              _ptr(out), _ptr(ids), _ptr(table), int(cap), _ptr(found), _ptr(kept)))
+    return out, table, found, kept, ids
 
 
 def _last_regions(fn, handle):
@@ -308,6 +351,10 @@ def lib():
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_score_labels.argtypes = [C.c_void_p] + L.mi_unet_score_labels_host.argtypes
         L.mi_unet_score_derive.argtypes = [C.POINTER(Score), C.POINTER(ScoreMetrics)]
+        L.mi_unet_volume_components_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_components.argtypes = [C.c_void_p] + L.mi_unet_volume_components_host.argtypes
+        L.mi_unet_volume_derive.argtypes = [C.POINTER(VComp), C.POINTER(C.c_double), C.POINTER(VCompMetrics)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -689,6 +736,12 @@ class Engine:
         matrix int64 [B, classes, classes] (row = truth, column = pred) and the pixels left out of it, int64 [B]"""
         return _score_call(lib().mi_unet_score_labels, (self._h,), pred, truth, values, quantile_ppm, classes)
 
+    # ---- a stack of masks as one volume (mi_unet_volume_components): needs the device, not the weights
+    def volume_components(self, masks, values, connectivity=26, min_voxels=0, keep_largest=0, cap=256, want_ids=False):
+        """masks u8 [D,H,W] of any size, values = the bytes whose sets are labelled -> (out u8 [n,D,H,W], table VCOMP_DTYPE [n, cap],
+        found int32 [n], kept int32 [n], ids int32 [n,D,H,W] or None)"""
+        return _volume_call(lib().mi_unet_volume_components, (self._h,), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -803,6 +856,21 @@ def window_of(samples, mode="minmax", clip_lo_ppm=0, clip_hi_ppm=0, lo=0, hi=655
 def score_labels_host(pred, truth, values, quantile_ppm=50000, classes=0):
     """mi_unet_score_labels_host: Engine.score_labels as pure host arithmetic (needs no device)"""
     return _score_call(lib().mi_unet_score_labels_host, (), pred, truth, values, quantile_ppm, classes)
+
+
+def volume_components_host(masks, values, connectivity=26, min_voxels=0, keep_largest=0, cap=256, want_ids=False):
+    """mi_unet_volume_components_host: Engine.volume_components as pure host arithmetic (needs no device)"""
+    return _volume_call(lib().mi_unet_volume_components_host, (), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
+
+
+def volume_derive(comp, spacing):
+    """mi_unet_volume_derive of one component (a VComp, or one VCOMP_DTYPE record) with spacing (sx, sy, sz) in mm -> dict of
+    volume_mm3, surface_mm2, cx_mm, cy_mm, cz_mm, extent_x_mm, extent_y_mm, extent_z_mm"""
+    if not isinstance(comp, VComp):
+        comp = VComp(*[int(comp[n]) for n, _ in VComp._fields_])
+    out = VCompMetrics()
+    _check(lib().mi_unet_volume_derive(C.byref(comp), (C.c_double * 3)(*[float(v) for v in spacing]), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VCompMetrics._fields_}
 
 
 def score_derive(score):

@@ -21,7 +21,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
-           "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology"]
+           "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume"]
 
 
 def lib():
@@ -69,6 +69,9 @@ def lib():
         L.medseg_postprocess_mask_morph.argtypes = [_u8, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _u8]
         L.medseg_set_morphology.argtypes = [_i, _i, _i, C.c_int]
         L.medseg_get_morphology.argtypes = [_i, _i, _i, C.c_int]
+        L.medseg_set_volume.argtypes = [C.c_int] * 4 + [C.c_double] * 3
+        L.medseg_get_volume.argtypes = [_i] * 4 + [C.POINTER(C.c_double)]
+        L.medseg_get_volume.restype = None
         _LIB = L
     return _LIB
 
@@ -189,6 +192,18 @@ def get_truth_dir() -> str:
     buf = C.create_string_buffer(4096)
     n = lib().medseg_get_truth_dir(buf, 4096)
     return os.fsdecode(buf.raw[:n]) if n >= 0 else ""
+
+
+def set_volume(on=True, connectivity=26, min_voxels=0, keep_largest=0, spacing=(1.0, 1.0, 1.0)) -> bool:
+    """MedicalSeg::set_volume: process_image_batch labels its images as the slices of one volume and writes volume_report.json (and
+    <base>_volume_mask*.png under a filter); spacing = (x, y, z) in mm on the tile grid; needs no engine"""
+    return lib().medseg_set_volume(int(bool(on)), int(connectivity), int(min_voxels), int(keep_largest), *[float(v) for v in spacing]) == 0
+
+
+def get_volume():
+    v, sp = [C.c_int() for _ in range(4)], (C.c_double * 3)()
+    lib().medseg_get_volume(*[C.byref(x) for x in v], sp)
+    return {"on": bool(v[0].value), "connectivity": v[1].value, "min_voxels": v[2].value, "keep_largest": v[3].value, "spacing": tuple(sp)}
 
 
 def get_measure():
