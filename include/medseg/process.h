@@ -84,6 +84,11 @@ std::string get_truth_dir();
 // stack, 0 / 255.  Coordinates and spacing are those of the TILE grid -- the masks are at the tile size; spacing_x / _y are millimetres
 // per tile pixel, spacing_z per slice; an image's scale_x / scale_y to its own pixels are in its <base>_original_sizes.json.  Every
 // artefact that exists without the setting is written exactly as before, and with it off (the default) nothing changes at all.
+// With a truth directory set as well (set_truth_dir), the stack -- the filtered one under a filter -- is also scored against
+// <dir>/<base>_labels.raw of every slice as ONE volume (mi_unet_score_volume; one call per target, units from
+// mi_unet_score_volume_units on the spacing): <output_dir>/volume_score.json with "slices", "unit_mm", "spacing_units", "quantile_ppm"
+// and per target "label", "tp", "fp", "fn", "dice", "iou", "hd_mm", "hd_q_mm", "assd_mm", "rmsd_mm".  Only a series whose every slice
+// completed and has a truth file of the tile's size is scored; otherwise one log line says how many slices lack mask or truth.
 // process_single_image is one slice and ignores the setting.  Needs no engine and survives initialize_engine.  false, message on
 // stderr, setting unchanged: a connectivity other than 6, 18, 26, a negative min_voxels or keep_largest, a spacing that is not finite
 // and positive.

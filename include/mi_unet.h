@@ -486,6 +486,64 @@ int mi_unet_volume_components_host(const uint8_t *masks, int D, int H, int W, co
                                    uint8_t *out, int32_t *ids, mi_unet_vcomp *table, int cap, int32_t *found, int32_t *kept);
 int mi_unet_volume_derive(const mi_unet_vcomp *c, const double spacing_xyz[3], mi_unet_vcomp_metrics *out);
 
+/* ---- Scores of a volume: a stack of masks against a stack of ground truth, 3-D overlap and surface distances -------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  It is mi_unet_score_labels with
+ * one more axis and a spacing: the same struct, the same conventions, one mi_unet_score per value.
+ * Input is two byte volumes pred and truth, u8 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile
+ * size), n byte values, 1 <= n <= MI_UNET_SCORE_MAX_VALUES, and the spacing as three positive integers spacing_units = { ux, uy, uz }
+ * in a unit the caller chooses (mi_unet_score_volume_units finds one for a spacing in millimetres).  Plane k compares
+ * A = { pred == values[k] } with T = { truth == values[k] } over the whole volume; planes are independent.
+ *   OVERLAP   tp = |A & T|, fp = |A \ T|, fn = |T \ A|, counted over all D * H * W voxels.
+ *   BOUNDARY  dS = every voxel of S with a 6-neighbour that is not in S; positions outside the volume are not in S, so a set that
+ *             touches a face of the volume has boundary there.  It is S & ~binary_erosion(S) with scipy's 3-D cross and
+ *             border_value = 0: the surface medpy measures.  Consequence: with D = 1 every voxel of S lacks both z-neighbours, so
+ *             EVERY voxel of S is a boundary voxel and n is the set size -- this is not mi_unet_score_labels on one slice.
+ *   DISTANCE  between voxel centres, kept SQUARED, in integers: d2(p, q) = (dx ux)^2 + (dy uy)^2 + (dz uz)^2.  For p in dA,
+ *             d2(p) = min over q in dT of d2(p, q) (direction a_to_t), and likewise from dT to dA (t_to_a).  Per direction, as in the
+ *             2-D stage: n = boundary voxels of the source set, max_d2, sum_d2, sum_d_q16 = the sum of floor(2^16 sqrt(d2)), every
+ *             term the exact integer floor; q_d2 = s[n - 1 - floor(n * quantile_ppm / 1000000)] of the direction's values sorted
+ *             ascending, q_d2_sym the same statistic over both directions' values together.  All of it is independent of the order of
+ *             evaluation and bit-reproducible.
+ *   EMPTY     when dA or dT is empty both n fields still hold the counts, every max_d2, q_d2 and q_d2_sym is -1 and the sums are 0.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE = 8192: the device form keeps one row of 32-bit partial distances (4 W bytes) and
+ *             the row's source list (2 W bytes) in LDS, 6 * 8192 = 48 KiB, inside the 64 KiB a launch gets without opting in;
+ *   n * D * H * W < 2^31: every index and every count is an int;
+ *   every unit >= 1, and ((W - 1) ux)^2 + ((H - 1) uy)^2 + ((D - 1) uz)^2 < 2^31: every d2 is a positive int32_t, so the 16 + 16-bit
+ *             select of the 2-D stage applies.  A direction has fewer than 2^31 values, so sum_d2 < 2^31 * 2^31 = 2^62; every
+ *             sqrt(d2) < 2^15.5 gives a term below 2^31.5 and sum_d_q16 < 2^62.5: both inside int64_t.
+ * A 64 x 512 x 512 stack at 0.7 x 0.7 x 5 mm fits with a unit of 0.02 mm (35, 35, 250) and with 0.1 mm (7, 7, 50).
+ * The confusion matrix (optional; opts->classes in 1 .. MI_UNET_SCORE_MAX_CLASSES, confusion and skipped not NULL) treats the volume
+ * as one image: int64 [classes][classes], row = the truth byte, column = the pred byte; voxels where either byte is >= classes are
+ * left out of it and counted in int64 skipped[1].
+ * mi_unet_score_volume takes host buffers of any size; its workspace grows on demand, belongs to the handle (it is the one
+ * mi_unet_score_labels uses) and is freed by mi_unet_destroy.  It needs the device, not the network: it works before weights are
+ * loaded.  It changes no setting and nothing mi_unet_last_regions or mi_unet_last_stage_ms report.  opts == NULL is { 50000, 0 }.
+ * MI_UNET_EARG with a message, nothing queued and no output written: a null pred, truth, values, spacing_units or scores; D, H or W
+ * outside 1 .. 8192; n outside 1 .. MI_UNET_SCORE_MAX_VALUES; a value outside 0 .. 255 or repeated; n * D * H * W >= 2^31; a unit < 1;
+ * the d2 limit; quantile_ppm outside 0 .. 999999; classes outside 0 .. 16; confusion given with classes == 0 or without skipped.
+ * confusion == NULL skips the matrix whatever classes says.  A workspace that cannot be allocated is MI_UNET_EHIP with a message,
+ * before anything runs; the handle stays usable.
+ * mi_unet_score_volume_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle,
+ * same bytes.
+ * mi_unet_score_volume_units is pure host arithmetic: the largest k in 0 .. 4 such that with unit_mm = 10^-k every
+ * units[a] = llround(spacing_mm[a] / unit_mm) is >= 1 and the d2 limit holds for D, H, W.  The spacing actually used is
+ * units[a] * unit_mm.  MI_UNET_EARG, outputs untouched: a null pointer, D, H or W outside the limits, a spacing that is not finite and
+ * > 0, or no such k.
+ * mi_unet_score_volume_derive is pure host arithmetic: dice, iou, precision and recall as mi_unet_score_derive gives them; hd, hd_q,
+ * assd and rmsd are its values times unit_mm (NaN when the distance fields are -1).  MI_UNET_EARG for a null pointer or a unit_mm that
+ * is not finite and > 0.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_SCORE_VOLUME_MAX_SIDE 8192
+int mi_unet_score_volume(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth, int D, int H, int W, const int *values, int n,
+                         const int spacing_units[3] /* x, y, z */, const mi_unet_score_opts *opts, mi_unet_score *scores /* [n] */,
+                         int64_t *confusion /* [classes][classes] or NULL */, int64_t *skipped /* [1] */);
+int mi_unet_score_volume_host(const uint8_t *pred, const uint8_t *truth, int D, int H, int W, const int *values, int n,
+                              const int spacing_units[3], const mi_unet_score_opts *opts, mi_unet_score *scores, int64_t *confusion,
+                              int64_t *skipped);
+int mi_unet_score_volume_units(const double spacing_mm[3], int D, int H, int W, int units[3], double *unit_mm);
+int mi_unet_score_volume_derive(const mi_unet_score *s, double unit_mm, mi_unet_score_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

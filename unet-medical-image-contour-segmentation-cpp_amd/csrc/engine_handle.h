@@ -138,8 +138,9 @@ struct mi_unet {
     std::vector<int32_t> last_region_counts;
     int last_region_planes = 0, last_region_cap = 0;
     bool last_regions_valid = false;
-    // mi_unet_score_labels: d_score = both maps, the scores and the kernels' workspace of one call; h_score = the pinned
-    // staging of the maps and of the results; grown on demand, never shared with a clone
+    // mi_unet_score_labels and mi_unet_score_volume (7.10): d_score = both maps, the scores and the kernels' workspace of
+    // one call; h_score = the pinned staging of the maps and of the results; grown on demand, never shared with a clone.  Either call ends
+    // with a host synchronisation, so the two stages take turns on it
     miunet::DeviceBuf<uint8_t> d_score;
     miunet::PinnedBuf<uint8_t> h_score;
     size_t score_dev_cap = 0, score_host_cap = 0;   // bytes

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, volume.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
+// kernels.h -- launch interface of the gfx950 kernels (conv_direct.hip, conv_lp.hip, conv_wino.hip, layers_mem.hip, upsample.hip, image_stages.hip, morph.hip, regions.hip, score.hip, score_volume.hip, volume.hip, tiles.hip, blend.hip).  Internal to libmiunet.so.
 // The hipcc kernels are part of the library's own code object.  The two assembly kernels (csrc/asm/) are code objects of their own,
 // embedded as byte blobs: an AsmKernels (below) loads them for one device when an engine is created and unloads them with the last
 // handle that holds it.  libmiunet.so keeps no process-wide resource: no module, no device memory, no stream outlives its handles.
@@ -311,6 +311,25 @@ struct ScoreValues { int n = 0; int v[SCORE_MAX_VALUES] = {}; };
 size_t score_workspace_bytes(int B, int H, int W, int n, int classes);
 hipError_t launch_score(const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const ScoreValues &vals, int quantile_ppm,
                         int classes, void *ws, ::mi_unet_score *scores, const unsigned long long **conf, hipStream_t s);
+
+// Scores of a stack as one volume (score_volume.hip; include/mi_unet.h: mi_unet_score_volume).  pred, truth u8
+// [D][H][W] on the device; plane k compares { pred == v[k] } with { truth == v[k] } over the whole volume.  One launch sequence for
+// all n planes:
+//   counts  : score.hip's, over D * H * W voxels as one image
+//   columns : per plane and set, the 6-neighbour boundary, the index distance g along z to the nearest boundary voxel of the (y, x)
+//             column, and a flag per (z, y) row that holds boundary voxels
+//   y       : f = min over y' of (g * uz)^2 + ((y - y') * uy)^2, only in the rows the other set flagged
+//   rows    : at the source boundary voxels of a flagged row, d2 = min over x' of ((x - x') * ux)^2 + f(x') with the row of f in LDS;
+//             maximum, sums, and the values into the direction's list
+//   select  : score.hip's radix select and final step
+// scores [n] out (device).  With classes > 0, *conf receives where the u64 [classes][classes] matrix and behind it the skipped count
+// lie inside the workspace.  Workspace: score_volume_workspace_bytes(D, H, W, n, classes), not zeroed by the caller.  D, H, W in
+// 1 .. SCORE_VOLUME_MAX_SIDE, n * D * H * W < 2^31, units >= 1, ((W-1) ux)^2 + ((H-1) uy)^2 + ((D-1) uz)^2 < 2^31.
+constexpr int SCORE_VOLUME_MAX_SIDE = 8192;             // = MI_UNET_SCORE_VOLUME_MAX_SIDE
+struct ScoreVolumeArgs { int D = 0, H = 0, W = 0, ux = 1, uy = 1, uz = 1, quantile_ppm = 50000, classes = 0; ScoreValues vals; };
+size_t score_volume_workspace_bytes(int D, int H, int W, int n, int classes);
+hipError_t launch_score_volume(const uint8_t *pred, const uint8_t *truth, const ScoreVolumeArgs &a, void *ws, ::mi_unet_score *scores,
+                               const unsigned long long **conf, hipStream_t s);
 
 // Volume components (volume.hip; include/mi_unet.h: mi_unet_volume_components).  masks u8 [D][H][W] on the device; plane
 // k is the set { masks == v[k] }.  One launch sequence for all n planes:

@@ -3,26 +3,14 @@
 // mi_unet_score_labels).  Byte and integer work, exact.  gfx950 only.
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
+#include "score_common.h"
 
 namespace miunet {
 
 namespace sc {
 
-constexpr unsigned SENT = 0xFFFFu;                      // g of a column without a boundary pixel (real distances are <= 32766)
-constexpr unsigned NONE = 0xFFFFFFFFu;
 constexpr int D2_INF = 0x7FFFFFFF;                      // above every d2 (<= 2 * 32766^2)
 constexpr int HIST_BLOCKS = 8;                          // workgroups per (plane, direction) list in the histogram passes
-
-// The accumulators of one plane, zeroed on the stream before the first kernel.
-struct ScoreAcc {
-    int tp, fp, fn;
-    int n[2];                       // boundary pixels of A, of T
-    int max_d2[2];                  // per direction (0: dA -> dT, 1: dT -> dA)
-    unsigned cursor[2];             // values appended to the direction's list
-    unsigned sel_bin[3], sel_rest[3], sel_lo[3];   // per selection (a_to_t, t_to_a, both): the high half that holds the rank, the rank inside it, the low half
-    unsigned long long sum_d2[2], sum_q[2];
-};
-static_assert(sizeof(ScoreAcc) % 8 == 0, "ScoreAcc rows stay 8-byte aligned");
 
 struct Ws {
     ScoreAcc *acc;                  // [P]
@@ -34,8 +22,6 @@ struct Ws {
     size_t total;
 };
 
-__host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline Ws carve(void *base, int B, int H, int W, int n, int classes)
 {
     const size_t P = (size_t)B * n, hw = (size_t)H * W;
@@ -44,40 +30,12 @@ inline Ws carve(void *base, int B, int H, int W, int n, int classes)
     size_t at = 0;
     w.acc = reinterpret_cast<ScoreAcc *>(p + at); at += up256(P * sizeof(ScoreAcc));
     w.conf = reinterpret_cast<unsigned long long *>(p + at); at += up256((size_t)B * (classes * classes + 1) * 8);
-    w.hist = reinterpret_cast<unsigned *>(p + at); at += P * 5 * 65536 * sizeof(unsigned);
+    w.hist = reinterpret_cast<unsigned *>(p + at); at += P * HIST_BYTES_PER_PLANE;
     w.zero_bytes = at;
     w.g = reinterpret_cast<uint16_t *>(p + at); at += up256(P * 2 * hw * sizeof(uint16_t));
     w.d2 = reinterpret_cast<int *>(p + at); at += up256(P * 2 * hw * sizeof(int));
     w.total = at;
     return w;
-}
-
-__device__ __forceinline__ int pick_value(const ScoreValues &v, int k)
-{
-    int r = v.v[0];
-#pragma unroll
-    for (int j = 1; j < SCORE_MAX_VALUES; ++j)
-        if (k == j) r = v.v[j];
-    return r;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-    return v;
 }
 
 // hist[key] += 1 for every lane whose key is not NONE: the lanes of a wave that hold the same key send ONE add (boundary distances of a
@@ -211,16 +169,6 @@ __global__ __launch_bounds__(256) void k_score_columns(const uint8_t *__restrict
         const int tot = s_n[0] + s_n[1] + s_n[2] + s_n[3];
         if (tot) atomicAdd(&acc[p].n[set], tot);
     }
-}
-
-// floor(2^16 sqrt(d2)) exactly: the fp64 root of d2 << 32 (exact in fp64: 31 significant bits), corrected to the integer floor
-__device__ __forceinline__ unsigned long long sqrt_q16(int d2)
-{
-    const unsigned long long v = (unsigned long long)(unsigned)d2 << 32;
-    unsigned long long r = (unsigned long long)sqrt((double)v);         // r < 2^31.5: r * r and (r + 1)^2 fit
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return r;
 }
 
 // ---- row pass: d2 at the source boundary pixels of one row --------------------------------------------------------------------------
@@ -392,6 +340,27 @@ __global__ __launch_bounds__(256) void k_score_final(int P, ScoreValues vals, in
     out[p] = s;
 }
 
+void launch_score_counts(const uint8_t *pred, const uint8_t *truth, int B, long long hw, const ScoreValues &vals, int classes, ScoreAcc *acc,
+                         unsigned long long *conf, hipStream_t s)
+{
+    long long cblocks = (hw + 256 * 16 - 1) / (256 * 16);      // 16 pixels per lane
+    if (cblocks > 1024) cblocks = 1024;
+    const dim3 cg((unsigned)cblocks, (unsigned)B), blk(256);
+    if (classes > 0) hipLaunchKernelGGL(k_score_counts<true>, cg, blk, 0, s, pred, truth, (int)hw, vals, classes, acc, conf);
+    else hipLaunchKernelGGL(k_score_counts<false>, cg, blk, 0, s, pred, truth, (int)hw, vals, classes, acc, conf);
+}
+
+void launch_score_select(int P, size_t stride, const ScoreValues &vals, int quantile_ppm, ScoreAcc *acc, const int *d2, unsigned *hist,
+                         ::mi_unet_score *scores, hipStream_t s)
+{
+    const dim3 hg((unsigned)(2 * P * HIST_BLOCKS)), pg((unsigned)(3 * P)), blk(256);
+    hipLaunchKernelGGL(k_score_hist<false>, hg, blk, 0, s, stride, d2, acc, hist);
+    hipLaunchKernelGGL(k_score_pick<false>, pg, blk, 0, s, quantile_ppm, acc, hist);
+    hipLaunchKernelGGL(k_score_hist<true>, hg, blk, 0, s, stride, d2, acc, hist);
+    hipLaunchKernelGGL(k_score_pick<true>, pg, blk, 0, s, quantile_ppm, acc, hist);
+    hipLaunchKernelGGL(k_score_final, dim3((unsigned)((P + 255) / 256)), blk, 0, s, P, vals, quantile_ppm, acc, scores);
+}
+
 }  // namespace sc
 
 size_t score_workspace_bytes(int B, int H, int W, int n, int classes) { return sc::carve(nullptr, B, H, W, n, classes).total; }
@@ -411,22 +380,14 @@ hipError_t launch_score(const uint8_t *pred, const uint8_t *truth, int B, int H,
     if (P > 32767) return hipErrorInvalidValue;
     const sc::Ws w = sc::carve(ws, B, H, W, n, classes);
     if (hipError_t e = hipMemsetAsync(w.acc, 0, w.zero_bytes, s)) return e;
-    long long cblocks = (hw + 256 * 16 - 1) / (256 * 16);      // 16 pixels per lane
-    if (cblocks > 1024) cblocks = 1024;
-    const dim3 cg((unsigned)cblocks, (unsigned)B), blk(256);
-    if (classes > 0) hipLaunchKernelGGL(sc::k_score_counts<true>, cg, blk, 0, s, pred, truth, (int)hw, vals, classes, w.acc, w.conf);
-    else hipLaunchKernelGGL(sc::k_score_counts<false>, cg, blk, 0, s, pred, truth, (int)hw, vals, classes, w.acc, w.conf);
+    const dim3 blk(256);
+    sc::launch_score_counts(pred, truth, B, hw, vals, classes, w.acc, w.conf, s);
     hipLaunchKernelGGL(sc::k_score_columns, dim3((unsigned)(2 * P * wblocks)), blk, 0, s, pred, truth, H, W, wblocks, vals, w.g, w.acc);
     const size_t lds = (size_t)2 * ((W + 1) & ~1) * sizeof(uint16_t);      // the row of g and the list: at most 131072 bytes at W = 32767
     if (lds > 65536)
         if (hipError_t e = ensure_dynamic_lds(sc::k_score_rows, lds)) return e;
     hipLaunchKernelGGL(sc::k_score_rows, dim3((unsigned)(2 * P * H)), blk, lds, s, H, W, w.g, w.d2, w.acc);
-    const dim3 hg((unsigned)(2 * P * sc::HIST_BLOCKS)), pg((unsigned)(3 * P));
-    hipLaunchKernelGGL(sc::k_score_hist<false>, hg, blk, 0, s, (size_t)hw, w.d2, w.acc, w.hist);
-    hipLaunchKernelGGL(sc::k_score_pick<false>, pg, blk, 0, s, quantile_ppm, w.acc, w.hist);
-    hipLaunchKernelGGL(sc::k_score_hist<true>, hg, blk, 0, s, (size_t)hw, w.d2, w.acc, w.hist);
-    hipLaunchKernelGGL(sc::k_score_pick<true>, pg, blk, 0, s, quantile_ppm, w.acc, w.hist);
-    hipLaunchKernelGGL(sc::k_score_final, dim3((unsigned)((P + 255) / 256)), blk, 0, s, (int)P, vals, quantile_ppm, w.acc, scores);
+    sc::launch_score_select((int)P, (size_t)hw, vals, quantile_ppm, w.acc, w.d2, w.hist, scores, s);
     if (conf) *conf = w.conf;
     return hipGetLastError();
 }

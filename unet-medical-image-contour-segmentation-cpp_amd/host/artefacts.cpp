@@ -105,4 +105,12 @@ void write_volume_artefacts(const VolumeArtefacts &a)
         }
 }
 
+void write_volume_score(const std::string &output_dir, const std::string &score)
+{
+    std::ofstream o(output_dir + "/volume_score.json", std::ios::binary);
+    o << score;
+    o.close();
+    if (!o) throw std::runtime_error("Failed to save volume score");
+}
+
 }  // namespace MedicalSeg

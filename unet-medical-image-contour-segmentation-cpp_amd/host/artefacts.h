@@ -54,4 +54,8 @@ struct VolumeArtefacts {
 };
 void write_volume_artefacts(const VolumeArtefacts &a);
 
+// The scores of a batch as one volume against ground truth (MedicalSeg::set_volume with set_truth_dir): <output_dir>/volume_score.json
+// with the text `score`.  Throws std::runtime_error("Failed to save volume score").
+void write_volume_score(const std::string &output_dir, const std::string &score);
+
 }  // namespace MedicalSeg

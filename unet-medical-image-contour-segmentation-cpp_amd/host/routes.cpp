@@ -531,10 +531,11 @@ struct VolumeStack {
 
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
-// fails no image.
+// fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
-                  std::ostream &lg)
+                  std::ostream &lg, std::vector<uint8_t> &filtered)
 {
+    filtered.clear();
     try {
         const size_t K = targets.size(), D = st.D, hw = st.hw, cap = MI_UNET_VOLUME_MAX_TABLE;
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0;
@@ -594,8 +595,80 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
         a.height = g_cfg.height; a.width = g_cfg.width;
         write_volume_artefacts(a);
+        filtered.swap(out);
     } catch (const std::exception &e) {
         report(lg, std::string("Volume error: ") + e.what());
+    }
+}
+
+// set_volume with set_truth_dir: the stack against <dir>/<base>_labels.raw of every slice as ONE volume (mi_unet_score_volume in
+// include/mi_unet.h).  One call per target with values = { 255 } on `h` (mi_unet_score_volume_host under
+// MEDSEG_HOST_POSTPROCESS=1): pred is the target's plane of `filtered` when the volume filter is active, else of the stack; truth is
+// recoded to 0 / 255 by truth == cls.  The integer units come from mi_unet_score_volume_units on the setting's spacing.  Writes
+// <output_dir>/volume_score.json.  Only a stack whose every slice completed and has a truth file of the tile's size is scored; a
+// failure is reported and fails no image.
+void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filtered, const std::vector<mi_unet_target> &targets, const Volume &v,
+                        const std::string &truth_dir, mi_unet_t *h, const std::string &output_dir, std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size(), D = st.D, hw = st.hw;
+        const bool filter = v.min_voxels > 0 || v.keep_largest > 0;
+        if (filter && filtered.size() != K * D * hw) throw std::runtime_error("the filtered stack is missing");
+        std::vector<uint8_t> labels(D * hw), truth(D * hw);
+        size_t without = 0;
+        for (size_t z = 0; z < D; ++z) {
+            bool good = !st.bases[z].empty();
+            if (good) {
+                const std::string path = truth_dir + "/" + st.bases[z] + "_labels.raw";
+                std::error_code ec;
+                const auto size = fs::file_size(path, ec);
+                std::ifstream f(path, std::ios::binary);
+                good = !ec && size == hw && f.read(reinterpret_cast<char *>(labels.data() + z * hw), (std::streamsize)hw);
+            }
+            without += !good;
+        }
+        if (without) {
+            lg << "Volume score skipped: " << without << " of " << D << " slices without mask or truth" << std::endl;
+            return;
+        }
+        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
+        int units[3] = { 0, 0, 0 };
+        double unit_mm = 0.0;
+        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
+            throw std::runtime_error(mi_unet_last_error());
+        const mi_unet_score_opts opts{ 50000, 0 };
+        const int value = 255;
+        const bool device = h && device_postprocess_requested();
+        std::vector<mi_unet_score> scores(K);
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const uint8_t *const pred = (filter ? filtered.data() : st.planes.data()) + t * D * hw;
+            for (size_t i = 0; i < D * hw; ++i) truth[i] = labels[i] == targets[t].cls ? 255 : 0;
+            const int rc = device ? mi_unet_score_volume(h, pred, truth.data(), (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, &scores[t],
+                                                         nullptr, nullptr)
+                                  : mi_unet_score_volume_host(pred, truth.data(), (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts,
+                                                              &scores[t], nullptr, nullptr);
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+        }
+        lg << "Volume score: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
+        std::ostringstream js;
+        js << "{\n  \"slices\": [";
+        for (size_t z = 0; z < D; ++z) js << (z ? ", " : "") << "\"" << medseg::json_escape(st.names[z]) << "\"";
+        js << "],\n  \"unit_mm\": " << json_number(unit_mm) << ",\n  \"spacing_units\": [" << units[0] << ", " << units[1] << ", " << units[2]
+           << "],\n  \"quantile_ppm\": " << opts.quantile_ppm << ",\n  \"targets\": [";
+        for (size_t t = 0; t < K; ++t) {
+            const mi_unet_score &sc = scores[t];
+            mi_unet_score_metrics m{};
+            if (mi_unet_score_volume_derive(&sc, unit_mm, &m) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"tp\": " << sc.tp << ", \"fp\": " << sc.fp << ", \"fn\": " << sc.fn
+               << ", \"dice\": " << json_number(m.dice) << ", \"iou\": " << json_number(m.iou) << ", \"hd_mm\": " << json_number(m.hd)
+               << ", \"hd_q_mm\": " << json_number(m.hd_q) << ", \"assd_mm\": " << json_number(m.assd) << ", \"rmsd_mm\": " << json_number(m.rmsd)
+               << "}";
+        }
+        js << "\n  ]\n}\n";
+        write_volume_score(output_dir, js.str());
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume score error: ") + e.what());
     }
 }
 
@@ -714,7 +787,11 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width);
             for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
             ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
-            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text);
+            std::vector<uint8_t> filtered;
+            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered);
+            if (!settings.truth_dir.empty())
+                score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
+                                   lg.text);
             return ok;
         }
         if (!is_default(settings.targets) || !is_default(settings.morph)) {

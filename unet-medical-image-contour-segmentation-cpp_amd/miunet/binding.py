@@ -35,6 +35,7 @@ EXPORTS = [
     "mi_unet_set_morph", "mi_unet_get_morph", "mi_unet_morph_element", "mi_unet_group_set_morph",
     "mi_unet_score_labels", "mi_unet_score_labels_host", "mi_unet_score_derive",
     "mi_unet_volume_components", "mi_unet_volume_components_host", "mi_unet_volume_derive",
+    "mi_unet_score_volume", "mi_unet_score_volume_host", "mi_unet_score_volume_units", "mi_unet_score_volume_derive",
 ]
 
 
@@ -145,6 +146,29 @@ def _score_call(fn, head, pred, truth, values, quantile_ppm, classes):
     conf = np.zeros((b, classes, classes), np.int64) if classes > 0 else None
     skipped = np.zeros(b, np.int64) if classes > 0 else None
     _check(fn(*head, _ptr(pred), _ptr(truth), b, hh, ww, _ptr(vals), vals.size, C.byref(ScoreOpts(int(quantile_ppm), int(classes))),
+              _ptr(scores), _ptr(conf), _ptr(skipped)))
+    return (scores, conf, skipped) if classes > 0 else scores
+
+
+SCORE_VOLUME_MAX_SIDE = 8192
+
+
+def _score_volume_call(fn, head, pred, truth, values, spacing_units, quantile_ppm, classes):
+    """mi_unet_score_volume (head = (handle,)) or its host form (head = ()): pred, truth u8 [D,H,W], spacing_units (ux, uy, uz) ->
+    SCORE_DTYPE [n], and (confusion int64 [classes, classes], skipped int64 [1]) behind it when classes > 0.  The library checks the
+    values."""
+    pred, truth = np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(truth, np.uint8)
+    if pred.ndim != 3 or pred.shape != truth.shape:
+        raise ValueError(f"pred {pred.shape} and truth {truth.shape} must be two u8 [D,H,W] arrays of one shape")
+    d, hh, ww = pred.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    units = np.ascontiguousarray(spacing_units, np.int32).reshape(-1)
+    if units.size != 3:
+        raise ValueError("spacing_units holds three integers: x, y, z")
+    scores = np.zeros(max(vals.size, 1), SCORE_DTYPE)
+    conf = np.zeros((classes, classes), np.int64) if classes > 0 else None
+    skipped = np.zeros(1, np.int64) if classes > 0 else None
+    _check(fn(*head, _ptr(pred), _ptr(truth), d, hh, ww, _ptr(vals), vals.size, _ptr(units), C.byref(ScoreOpts(int(quantile_ppm), int(classes))),
               _ptr(scores), _ptr(conf), _ptr(skipped)))
     return (scores, conf, skipped) if classes > 0 else scores
 
@@ -355,6 +379,11 @@ def lib():
                                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_components.argtypes = [C.c_void_p] + L.mi_unet_volume_components_host.argtypes
         L.mi_unet_volume_derive.argtypes = [C.POINTER(VComp), C.POINTER(C.c_double), C.POINTER(VCompMetrics)]
+        L.mi_unet_score_volume_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_score_volume.argtypes = [C.c_void_p] + L.mi_unet_score_volume_host.argtypes
+        L.mi_unet_score_volume_units.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.mi_unet_score_volume_derive.argtypes = [C.POINTER(Score), C.c_double, C.POINTER(ScoreMetrics)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -742,6 +771,13 @@ class Engine:
         found int32 [n], kept int32 [n], ids int32 [n,D,H,W] or None)"""
         return _volume_call(lib().mi_unet_volume_components, (self._h,), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
 
+    # ---- scores of a stack as one volume (mi_unet_score_volume): needs the device, not the weights
+    def score_volume(self, pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
+        """pred, truth u8 [D,H,W] of any size, values = the bytes to compare, spacing_units = (ux, uy, uz) positive integers ->
+        SCORE_DTYPE [n]; with classes > 0 also the confusion matrix int64 [classes, classes] (row = truth, column = pred) over the whole
+        volume and the voxels left out of it, int64 [1]"""
+        return _score_volume_call(lib().mi_unet_score_volume, (self._h,), pred, truth, values, spacing_units, quantile_ppm, classes)
+
     def infer_device(self, d_imgs_ptr: int, b: int, d_labels_ptr: int, d_logits_ptr: int = 0):
         _check(lib().mi_unet_infer_u8_device(self._h, C.c_void_p(d_imgs_ptr), b, C.c_void_p(d_labels_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
@@ -875,11 +911,36 @@ def volume_derive(comp, spacing):
 
 def score_derive(score):
     """mi_unet_score_derive of one score (a Score, or one SCORE_DTYPE record) -> dict of dice, iou, precision, recall, hd, hd_q, assd, rmsd"""
-    if not isinstance(score, Score):
-        dirs = [ScoreDir(*[int(score[d][n]) for n, _ in ScoreDir._fields_]) for d in ("a_to_t", "t_to_a")]
-        score = Score(*[int(score[n]) for n, _ in Score._fields_[:6]], *dirs)
     out = ScoreMetrics()
-    _check(lib().mi_unet_score_derive(C.byref(score), C.byref(out)))
+    _check(lib().mi_unet_score_derive(C.byref(_as_score(score)), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in ScoreMetrics._fields_}
+
+
+def _as_score(score):
+    if isinstance(score, Score):
+        return score
+    dirs = [ScoreDir(*[int(score[d][n]) for n, _ in ScoreDir._fields_]) for d in ("a_to_t", "t_to_a")]
+    return Score(*[int(score[n]) for n, _ in Score._fields_[:6]], *dirs)
+
+
+def score_volume_host(pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
+    """mi_unet_score_volume_host: Engine.score_volume as sequential host arithmetic (needs no device)"""
+    return _score_volume_call(lib().mi_unet_score_volume_host, (), pred, truth, values, spacing_units, quantile_ppm, classes)
+
+
+def score_volume_units(spacing_mm, shape):
+    """mi_unet_score_volume_units: spacing (sx, sy, sz) in mm and the volume's shape (D, H, W) -> ((ux, uy, uz), unit_mm)"""
+    units, unit_mm = (C.c_int * 3)(), C.c_double()
+    d, hh, ww = (int(v) for v in shape)
+    _check(lib().mi_unet_score_volume_units((C.c_double * 3)(*[float(v) for v in spacing_mm]), d, hh, ww, units, C.byref(unit_mm)))
+    return tuple(units), unit_mm.value
+
+
+def score_volume_derive(score, unit_mm):
+    """mi_unet_score_volume_derive of one score (a Score, or one SCORE_DTYPE record) -> dict of dice, iou, precision, recall and hd,
+    hd_q, assd, rmsd in mm"""
+    out = ScoreMetrics()
+    _check(lib().mi_unet_score_volume_derive(C.byref(_as_score(score)), float(unit_mm), C.byref(out)))
     return {n: getattr(out, n) for n, _ in ScoreMetrics._fields_}
 
 
