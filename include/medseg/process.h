@@ -100,6 +100,25 @@ struct Volume {
 bool set_volume(const Volume &volume);
 Volume get_volume();
 
+// The stack cleaned as a volume before it is labelled (mi_unet_volume_clean in include/mi_unet.h).  It acts only
+// together with set_volume's `on`: before the components are labelled, every target's plane of the stack goes through one
+// mi_unet_volume_clean call with values = { 255 } (mi_unet_volume_clean_host under MEDSEG_HOST_POSTPROCESS=1): the 3-D cavity fill
+// when `fill`, then a close by a ball of close_mm and an open by a ball of open_mm millimetres under the volume setting's spacing.  The
+// integer units come from mi_unet_score_volume_units on that spacing and a radius is llround(mm / unit_mm); a radius or unit past
+// MI_UNET_VOLUME_CLEAN_MAX_R is reported as "Volume clean error: ..." and the volume stage of that batch is skipped.  The cleaned stack
+// is what set_volume's filter sees and what the volume score scores; it is written per slice as <base>_volume_mask*.png whether or not
+// a filter is active, and volume_report.json gains a "clean" object behind "spacing": "fill", "close_mm", "open_mm", "unit_mm",
+// "close_r", "open_r" and "targets" with per target "label", "in_voxels", "filled", "closed", "opened", "out_voxels".  One log line per
+// batch.  With it off (the default) every artefact and every log line is what it is without the setting.  Needs no engine and
+// survives initialize_engine.  false, message on stderr, setting unchanged: a radius that is not finite or is negative.
+struct VolumeClean {
+    bool on = false;
+    bool fill = true;
+    double close_mm = 0, open_mm = 0;
+};
+bool set_volume_clean(const VolumeClean &clean);
+VolumeClean get_volume_clean();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

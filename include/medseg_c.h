@@ -62,6 +62,10 @@ int medseg_get_truth_dir(char *out, int cap);
  * medseg_get_volume fills the seven values (spacing: three doubles, x y z). */
 int medseg_set_volume(int on, int connectivity, int min_voxels, int keep_largest, double spacing_x, double spacing_y, double spacing_z);
 void medseg_get_volume(int *on, int *connectivity, int *min_voxels, int *keep_largest, double *spacing_xyz);
+/* The stack cleaned as a volume before it is labelled: MedicalSeg::set_volume_clean / get_volume_clean (include/medseg/process.h).
+ * 0 on success; medseg_get_volume_clean fills the four values. */
+int medseg_set_volume_clean(int on, int fill, double close_mm, double open_mm);
+void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_mm);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

@@ -544,6 +544,63 @@ int mi_unet_score_volume_host(const uint8_t *pred, const uint8_t *truth, int D, 
 int mi_unet_score_volume_units(const double spacing_mm[3], int D, int H, int W, int units[3], double *unit_mm);
 int mi_unet_score_volume_derive(const mi_unet_score *s, double unit_mm, mi_unet_score_metrics *out);
 
+/* ---- Volume clean-up: 3-D cavity fill, then close and open by a ball in the caller's spacing unit -------------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  It is the 2-D tail's hole fill ->
+ * close -> open (mi_unet_set_morph, 7.7) with one more axis and a spacing; the size filter behind them is mi_unet_volume_components.
+ * Input is one byte volume masks, u8 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), n byte
+ * values, 1 <= n <= MI_UNET_VOLUME_MAX_VALUES, and the spacing as three positive integers spacing_units = { ux, uy, uz } in a unit the
+ * caller chooses (mi_unet_score_volume_units finds one for a spacing in millimetres).
+ *   SETS    plane k is S = { masks == values[k] }; planes are independent.  out[k] ([n][D][H][W]) is values[k] on the cleaned set and 0
+ *           elsewhere (so the plane of value 0 is all zero; its stats are still exact).  out may be masks itself when n == 1.
+ *   BALL    radius r in the caller's unit: B(r) = { (dx, dy, dz) : (dx ux)^2 + (dy uy)^2 + (dz uz)^2 <= r^2 }, in integer arithmetic.
+ *           Its half-widths are ex = r / ux, ey = r / uy, ez = r / uz, rounded down.  r smaller than every unit is the single voxel, the
+ *           identity; r between the in-plane units and uz is a flat disc; with units (1, 1, 1) its slice dz = 0 is MI_UNET_MORPH_DISC.
+ *           mi_unet_volume_ball is pure host arithmetic: it writes extent = { ex, ey, ez } and, when elem is not NULL,
+ *           (2 ez + 1) (2 ey + 1) (2 ex + 1) bytes 0 / 1, z-major (slice after slice, row after row).
+ *   STEPS   in the order of the 2-D tail:
+ *           1. if fill: add every voxel not in S that is not 6-connected, through voxels not in S, to a voxel on one of the six faces
+ *              of the volume (scipy's binary_fill_holes with the 3-D cross).  With D = 1, or any side of 1, every voxel lies on a face
+ *              and nothing is filled -- this is not the 2-D hole fill on one slice.  Background that reaches the outside only across
+ *              an edge or a corner is a cavity and is filled.
+ *           2. close: dilate by B(close_r), then erode by it.
+ *           3. open: erode by B(open_r), then dilate by it.
+ *   BORDER  the rules of the 2-D tail: an erosion is constrained only by voxels inside the volume, a dilation is seeded only by voxels
+ *           inside the volume.  With them close is extensive, open is anti-extensive, both are idempotent, and each is the dual of the
+ *           other under complement.
+ *   STATS   in_voxels = |S|; filled and closed = the voxels steps 1 and 2 add; opened = the voxels step 3 removes;
+ *           out_voxels = in_voxels + filled + closed - opened; value echoes values[k]; reserved is 0.  stats may be NULL.
+ * Limits, each with its reason:
+ *   D, H, W >= 1; n * D * H * W < 2^31: every index and every count of a plane is an int;
+ *   values in 0 .. 255 and not repeated;
+ *   every unit in 1 .. 46340 and both radii in 0 .. MI_UNET_VOLUME_CLEAN_MAX_R = 46340: r * r < 2^31, every offset of the ball has
+ *           dx ux <= r, so every squared term is a positive int32_t and a sum of two stays inside 32 unsigned bits; an index distance
+ *           along z is at most 46340 and is kept in 16 bits.  A half-width larger than the side it runs along acts as the side.
+ *   The device form stages nothing per row in LDS, so there is no limit on a side beyond the product above.
+ * opts == NULL is { 1, 0, 0 }: fill only.  fill is 0 or 1.
+ * mi_unet_volume_clean takes host buffers of any size; its workspace (about 7 bytes per voxel and plane) grows on demand, belongs to
+ * the handle and is freed by mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes
+ * no setting and nothing mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued and no
+ * output written: a null masks, values, spacing_units or out; D, H or W < 1; n outside 1 .. MI_UNET_VOLUME_MAX_VALUES; a value outside
+ * 0 .. 255 or repeated; n * D * H * W >= 2^31; a unit outside 1 .. 46340; fill other than 0 or 1; a radius outside 0 .. 46340; out ==
+ * masks with n > 1.  A workspace that cannot be allocated is MI_UNET_EHIP with a message, before anything runs; the handle stays usable.
+ * mi_unet_volume_clean_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle,
+ * same bytes.
+ * mi_unet_volume_ball: MI_UNET_EARG, outputs untouched, for a null spacing_units or extent, a unit outside 1 .. 46340 or r outside
+ * 0 .. 46340.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VOLUME_CLEAN_MAX_R 46340           /* r*r < 2^31 */
+typedef struct mi_unet_volume_clean_opts { int fill; int close_r; int open_r; } mi_unet_volume_clean_opts;   /* default { 1, 0, 0 } */
+typedef struct mi_unet_volume_clean_stat {         /* 48 bytes, no padding */
+    int32_t value, reserved;                       /* echo of the plane's value; 0 */
+    int64_t in_voxels, filled, closed, opened, out_voxels;
+} mi_unet_volume_clean_stat;
+int mi_unet_volume_clean(mi_unet_t *h, const uint8_t *masks /* [D][H][W] host */, int D, int H, int W, const int *values, int n,
+                         const int spacing_units[3] /* x, y, z */, const mi_unet_volume_clean_opts *opts,
+                         uint8_t *out /* [n][D][H][W] */, mi_unet_volume_clean_stat *stats /* [n] or NULL */);
+int mi_unet_volume_clean_host(const uint8_t *masks, int D, int H, int W, const int *values, int n, const int spacing_units[3],
+                              const mi_unet_volume_clean_opts *opts, uint8_t *out, mi_unet_volume_clean_stat *stats);
+int mi_unet_volume_ball(const int spacing_units[3], int r, int extent[3] /* x, y, z half-widths */, uint8_t *elem /* or NULL */);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -1,0 +1,267 @@
+"""Volume clean-up (include/mi_unet.h: mi_unet_volume_clean) without a device: mi_unet_volume_clean_host against the
+brute-force reference of volume_clean_ref.py byte for byte and count for count, the ball, the properties the definition promises
+(identity, idempotence, duality, symmetry under permutations and mirrors of the axes), the argument checks, the struct size, the host
+half as a stand-alone program, and the facade's setting.  Byte and integer work: every comparison is exact."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import volume_clean_ref as cr
+from miunet import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+
+
+def test_the_cases_are_not_degenerate():
+    cr.assert_not_degenerate()
+    # the figures the generator is known by: the cavity voxels of the two full-size binary cases (few: the fill has cases of its own)
+    assert [cr.clean_set(cr.binary(s) != 0, (1, 1, 1), True, 0, 0)[1]["filled"] for s in cr.SHAPES[:2]] == [40, 13]
+
+
+@pytest.mark.parametrize("shape", cr.SHAPES)
+def test_host_equals_reference(shape):
+    """every unit triple x radius pair, fill on and off: three values of the label volume and one that is absent, and the binary case"""
+    for units in cr.UNITS:
+        for pair in cr.radius_pairs(units):
+            for fill in (True, False):
+                where = f"{shape} {units} {pair} fill={fill}"
+                out, stats = binding.volume_clean_host(cr.case(shape), cr.VALUES, units, fill, pair[0], pair[1])
+                cr.assert_equal(out, stats, cr.case_ref(shape, units, pair, fill), where)
+                out, stats = binding.volume_clean_host(cr.binary(shape), (1,), units, fill, pair[0], pair[1])
+                cr.assert_equal(out, stats, cr.binary_ref(shape, units, pair, fill), where + " binary")
+
+
+@pytest.mark.parametrize("name,vol,added", cr.fill_cases(), ids=[c[0] for c in cr.fill_cases()])
+def test_host_fill_cases(name, vol, added):
+    out, stats = binding.volume_clean_host(vol, (1,), (1, 1, 1), True)
+    cr.assert_equal(out, stats, cr.clean(vol, (1,), (1, 1, 1), True), name)
+    assert stats[0]["filled"] == added and stats[0]["closed"] == 0 and stats[0]["opened"] == 0
+    assert stats[0]["out_voxels"] == int(vol.sum()) + added
+    assert np.array_equal(out[0] >= vol, np.ones(vol.shape, bool))          # the fill only adds
+
+
+def test_ball_equals_the_enumerated_offsets_and_the_disc():
+    for units in cr.UNITS + ((1, 2, 3), (46340, 46340, 46340)):
+        for r in list(range(0, 23)) + [46340]:
+            if r == 46340 and units != (46340, 46340, 46340):
+                continue
+            ext, elem = binding.volume_ball(units, r)
+            want_ext, want = cr.ball_elem(units, r)
+            assert ext == want_ext and elem.shape == want.shape and np.array_equal(elem, want), (units, r)
+    for r in range(0, 6):
+        ext, elem = binding.volume_ball((1, 1, 1), r)
+        assert ext == (r, r, r) and np.array_equal(elem[r], binding.morph_element("disc", r)), r
+    ext, elem = binding.volume_ball((2, 2, 5), 1)                              # smaller than every unit: the single voxel
+    assert ext == (0, 0, 0) and elem.tolist() == [[[1]]]
+    ext, elem = binding.volume_ball((2, 2, 5), 4)                              # between the in-plane units and uz: a flat disc
+    assert ext == (2, 2, 0) and elem.shape == (1, 5, 5) and int(elem.sum()) == 13
+
+
+def test_ball_argument_errors():
+    L = binding.lib()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    ext, elem = np.full(3, 77, np.int32), np.full(27, 0x55, np.uint8)
+    alive = []                                                             # (the arrays behind the pointers)
+
+    def units(*u):
+        alive.append(np.array(u, np.int32))
+        return ptr(alive[-1])
+
+    assert L.mi_unet_volume_ball(units(1, 1, 1), 1, ptr(ext), ptr(elem)) == 0 and ext.tolist() == [1, 1, 1]
+    ext[:] = 77; elem[:] = 0x55
+    for bad in ((None, 1, ptr(ext)), (units(1, 1, 1), 1, None), (units(0, 1, 1), 1, ptr(ext)), (units(1, 46341, 1), 1, ptr(ext)),
+                (units(1, 1, 1), -1, ptr(ext)), (units(1, 1, 1), 46341, ptr(ext))):
+        assert L.mi_unet_volume_ball(bad[0], bad[1], bad[2], ptr(elem)) == 1, bad[1]
+        assert (ext == 77).all() and (elem == 0x55).all() and b"mi_unet_volume_ball" in L.mi_unet_last_error()
+    assert L.mi_unet_volume_ball(units(46340, 1, 1), 46340, ptr(ext), None) == 0 and ext.tolist() == [1, 46340, 46340]
+
+
+# ---- properties, on the host form ----------------------------------------------------------------------------------------------------------
+PROP_SHAPE, PROP_UNITS = (7, 33, 70), (3, 1, 7)
+
+
+def test_single_voxel_balls_without_fill_return_the_input_sets():
+    vol = cr.case(PROP_SHAPE)
+    for pair in ((0, 0), (2, 2)):                                           # 2 < every unit of (3, 3, 7)
+        out, stats = binding.volume_clean_host(vol, cr.VALUES, (3, 3, 7), False, pair[0], pair[1])
+        for k, v in enumerate(cr.VALUES):
+            assert np.array_equal(out[k], np.where(vol == v, v, 0).astype(np.uint8)), (pair, v)
+            assert stats[k]["in_voxels"] == stats[k]["out_voxels"] == int((vol == v).sum())
+            assert stats[k]["filled"] == stats[k]["closed"] == stats[k]["opened"] == 0 and stats[k]["value"] == v
+
+
+@pytest.mark.parametrize("units", cr.UNITS)
+def test_open_and_close_are_idempotent(units):
+    vol = cr.binary(PROP_SHAPE)
+    for r in cr.radius_pairs(units)[1]:
+        once, s1 = binding.volume_clean_host(vol, (1,), units, False, 0, r)
+        twice, s2 = binding.volume_clean_host(once[0], (1,), units, False, 0, r)
+        assert s1[0]["opened"] > 0 and s2[0]["opened"] == 0 and np.array_equal(once, twice), (units, r, "open")
+        once, s1 = binding.volume_clean_host(vol, (1,), units, False, r, 0)
+        twice, s2 = binding.volume_clean_host(once[0], (1,), units, False, r, 0)
+        assert s1[0]["closed"] > 0 and s2[0]["closed"] == 0 and np.array_equal(once, twice), (units, r, "close")
+
+
+@pytest.mark.parametrize("units", cr.UNITS)
+def test_close_is_the_complement_of_opening_the_complement(units):
+    vol = cr.binary(PROP_SHAPE)
+    r = cr.radius_pairs(units)[1][0]
+    closed, sc = binding.volume_clean_host(vol, (1,), units, False, r, 0)
+    # values = {0} on the same volume: the complement's plane; its bytes are all 0 (the value), its counts are exact
+    opened, so = binding.volume_clean_host(vol, (0,), units, False, 0, r)
+    assert not opened.any() and sc[0]["closed"] == so[0]["opened"] > 0
+    assert sc[0]["out_voxels"] + so[0]["out_voxels"] == vol.size
+    # and byte for byte, with the complement under a value of its own
+    two = (vol + 1).astype(np.uint8)                                        # the set is 2, its complement 1
+    closed2, _ = binding.volume_clean_host(two, (2,), units, False, r, 0)
+    opened1, _ = binding.volume_clean_host(two, (1,), units, False, 0, r)
+    assert np.array_equal(closed2[0] != 0, closed[0] != 0) and np.array_equal(closed2[0] != 0, opened1[0] == 0)
+
+
+def test_axis_permutations_and_mirrors_commute():
+    vol, units = cr.case(PROP_SHAPE), PROP_UNITS
+    pair = cr.radius_pairs(units)[0]
+    base_out, base_stats = binding.volume_clean_host(vol, cr.VALUES, units, True, pair[0], pair[1])
+    assert base_stats[0]["closed"] > 0 and base_stats[0]["opened"] > 0
+    for perm in cr.PERMS:
+        pv, pu = cr.permuted(vol, units, perm)
+        out, stats = binding.volume_clean_host(pv, cr.VALUES, pu, True, pair[0], pair[1])
+        assert np.array_equal(out, base_out.transpose((0,) + tuple(1 + a for a in perm))) and np.array_equal(stats, base_stats), perm
+    for axes in cr.MIRRORS:
+        out, stats = binding.volume_clean_host(np.flip(vol, axes), cr.VALUES, units, True, pair[0], pair[1])
+        assert np.array_equal(out, np.flip(base_out, tuple(1 + a for a in axes))) and np.array_equal(stats, base_stats), axes
+
+
+def test_one_slice_has_no_cavity_while_the_2d_tail_fills_its_hole():
+    import morph_ref as mr
+
+    sl = np.zeros((48, 80), np.uint8)
+    sl[10:30, 20:40] = 1
+    sl[15:25, 25:35] = 0                                                    # a ring of 300 pixels around a hole of 100
+    out, stats = binding.volume_clean_host(sl[None], (1,), (1, 1, 1), True)
+    assert stats[0]["filled"] == 0 and np.array_equal(out[0, 0], sl)         # every voxel of one slice lies on a face
+    tail = mr.chain(sl, 1, 200.5 / sl.size, open_r=0, close_r=0)             # min_area 200: the hole is smaller, the ring is not
+    assert int((tail != 0).sum()) == 400
+    stack = np.stack([np.ones_like(sl), sl, np.ones_like(sl)])              # the same slice between two full ones: now a cavity
+    assert binding.volume_clean_host(stack, (1,), (1, 1, 1), True)[1][0]["filled"] == 100
+
+
+# ---- argument errors -----------------------------------------------------------------------------------------------------------------------
+def earg_cases():
+    """(name, dict of overrides of a good call's arguments); every one must return MI_UNET_EARG"""
+    return [("null masks", dict(masks=None)), ("null values", dict(values=None)), ("null units", dict(units=None)), ("null out", dict(out=None)),
+            ("D = 0", dict(D=0)), ("H = 0", dict(H=0)), ("W = -1", dict(W=-1)),
+            ("n = 0", dict(n=0)), ("n = 9", dict(n=9, vals=list(range(9)))), ("value 256", dict(vals=[1, 256])), ("value -1", dict(vals=[-1, 2])),
+            ("repeated", dict(vals=[2, 2])), ("too many voxels", dict(D=2048, H=1024, W=1024)),
+            ("voxels past 64 bits", dict(D=2**31 - 1, H=2**31 - 1, W=2**31 - 1, n=8, vals=list(range(8)))),
+            ("n * voxels", dict(D=1024, H=1024, W=1024, vals=[1, 2])),
+            ("unit 0", dict(u=(1, 0, 1))), ("unit -3", dict(u=(-3, 1, 1))), ("unit 46341", dict(u=(1, 1, 46341))),
+            ("fill 2", dict(fill=2)), ("fill -1", dict(fill=-1)), ("close_r -1", dict(close_r=-1)), ("close_r 46341", dict(close_r=46341)),
+            ("open_r -1", dict(open_r=-1)), ("open_r 46341", dict(open_r=46341)), ("out is masks with two values", dict(alias=True))]
+
+
+def legal_cases():
+    """both sides of each limit: the largest legal radius and unit"""
+    return [("close_r 46340", dict(close_r=46340, u=(46340, 46340, 46340))), ("open_r 46340", dict(open_r=46340, u=(46340, 46340, 46340))),
+            ("unit 46340", dict(u=(46340, 1, 46340), close_r=1)), ("fill 0", dict(fill=0)), ("null stats", dict(stats=None)),
+            ("out is masks with one value", dict(alias=True, vals=[1]))]
+
+
+def call_with(fn, head, case):
+    """a good 2 x 5 x 7 call with the case's overrides, through ctypes; returns (rc, outputs untouched)"""
+    masks = np.ones((2, 5, 7), np.uint8)
+    masks[0, 2, 3] = 2
+    vals = np.asarray(case.get("vals", [1, 2]), np.int32)
+    units = np.asarray(case.get("u", (1, 1, 1)), np.int32)
+    out, stats = np.full((9, 2, 5, 7), 0x55, np.uint8), np.full((9, 48), 0x55, np.uint8)
+    arrays = dict(masks=masks, values=vals, units=units, out=masks if case.get("alias") else out, stats=stats)
+    ptr = lambda name: None if name in case and case[name] is None else arrays[name].ctypes.data_as(C.c_void_p)
+    opts = binding.VolumeCleanOpts(case.get("fill", 1), case.get("close_r", 0), case.get("open_r", 0))
+    before = masks.copy()
+    rc = fn(*head, ptr("masks"), case.get("D", 2), case.get("H", 5), case.get("W", 7), ptr("values"), case.get("n", len(vals)), ptr("units"),
+            C.byref(opts), ptr("out"), ptr("stats"))
+    untouched = (out == 0x55).all() and (stats == 0x55).all() and np.array_equal(masks, before)
+    return rc, bool(untouched)
+
+
+def test_host_argument_errors_leave_outputs_untouched():
+    L = binding.lib()
+    rc, untouched = call_with(L.mi_unet_volume_clean_host, (), {})
+    assert rc == 0 and not untouched                                        # the good call the cases are made from
+    for name, case in earg_cases():
+        rc, untouched = call_with(L.mi_unet_volume_clean_host, (), case)
+        assert rc == 1 and untouched, name
+        assert b"mi_unet_volume_clean_host" in L.mi_unet_last_error(), name
+    for name, case in legal_cases():
+        assert call_with(L.mi_unet_volume_clean_host, (), case)[0] == 0, name
+
+
+def test_opts_null_is_fill_only_and_out_may_alias_masks():
+    name, vol, added = cr.fill_cases()[0]
+    L = binding.lib()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    io, stats = vol.copy(), np.zeros(1, binding.VCLEAN_DTYPE)
+    vals, units = np.array([1], np.int32), np.array([2, 2, 5], np.int32)
+    assert L.mi_unet_volume_clean_host(ptr(io), *vol.shape, ptr(vals), 1, ptr(units), None, ptr(io), ptr(stats)) == 0
+    cr.assert_equal(io[None], stats, cr.clean(vol, (1,), (2, 2, 5), True), name)
+    assert stats[0]["filled"] == added
+
+
+def test_stat_struct_size_is_the_documented_one():
+    assert C.sizeof(binding.VCleanStat) == binding.VCLEAN_DTYPE.itemsize == 48 and C.sizeof(binding.VolumeCleanOpts) == 12
+    assert tuple(n for n, _ in binding.VCleanStat._fields_) == cr.STAT_FIELDS == binding.VCLEAN_DTYPE.names
+    header = open(os.path.join(ROOT, "include", "mi_unet.h")).read()
+    assert "mi_unet_volume_clean_stat {         /* 48 bytes, no padding */" in header
+    assert "#define MI_UNET_VOLUME_CLEAN_MAX_R 46340" in header and binding.VOLUME_CLEAN_MAX_R == 46340
+    for name in ("mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball"):
+        assert hasattr(binding.lib(), name)
+
+
+def test_host_half_as_a_stand_alone_program(tmp_path):
+    """tests/cpu/volume_clean_host_test.cpp + csrc/volume_clean.cpp without its device entry point, built by a plain C++ compiler: the
+    form in which the host half runs under -fsanitize=address,undefined (the command is in the program's header); here it is built
+    without"""
+    exe = tmp_path / "volume_clean_host_test"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_VOLUME_CLEAN_NO_DEVICE", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "volume_clean_host_test.cpp"), os.path.join(PKG, "csrc", "volume_clean.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, timeout=120)
+    assert r.returncode == 0 and b"volume_clean_host_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]
+
+
+# ---- the facade's setting (needs no engine) ---------------------------------------------------------------------------------------------------
+def test_cli_volclean_command():
+    from miunet import hostlib
+    cli = os.path.join(os.path.dirname(hostlib.LIB_PATH), "medseg_cli")
+    script = ("volclean\nvolclean on\nvolclean on nofill close 2.5 open 1\nvolclean\nvolclean on open 3\nvolclean on close\nvolclean on fill\n"
+              "volclean off extra\nvolclean on close -1\nvolclean on close 1 nofill\nvolclean on open 1e400\nvolclean off\nvolume\nhelp\nexit\n")
+    r = subprocess.run([cli], input=script.encode(), capture_output=True, timeout=60)
+    out, err = r.stdout.decode(), r.stderr.decode()
+    assert r.returncode == 0
+    said = [l.replace("> ", "") for l in out.splitlines() if l.replace("> ", "").startswith("Volume clean:")]
+    assert said == ["Volume clean: off fill close 0 open 0", "Volume clean: on fill close 0 open 0", "Volume clean: on nofill close 2.5 open 1",
+                    "Volume clean: on nofill close 2.5 open 1", "Volume clean: on fill close 0 open 3", "Volume clean: off fill close 0 open 0"]
+    # close without a number, fill, off extra, nofill behind a radius, a number no double holds; a negative radius parses and is refused
+    assert err.count("Invalid volclean command") == 5 and err.count("Volume clean unchanged") == 1
+    assert "volclean on [nofill] [close MM] [open MM]|off" in out
+    assert "Volume: off 26 min 0 keep 0 spacing 1 1 1" in out               # the volume command and its setting are untouched
+
+
+def test_volume_clean_setting_round_trips_through_the_c_view():
+    from miunet import hostlib
+    default = {"on": False, "fill": True, "close_mm": 0.0, "open_mm": 0.0}
+    volume = hostlib.get_volume()
+    assert hostlib.get_volume_clean() == default
+    try:
+        assert hostlib.set_volume_clean(True, False, 2.5, 0.7)
+        want = {"on": True, "fill": False, "close_mm": 2.5, "open_mm": 0.7}
+        assert hostlib.get_volume_clean() == want
+        for bad in (dict(close_mm=-0.5), dict(open_mm=float("nan")), dict(close_mm=float("inf"))):
+            assert not hostlib.set_volume_clean(True, **bad) and hostlib.get_volume_clean() == want, bad
+        assert hostlib.get_volume() == volume                               # a setting of its own
+    finally:
+        assert hostlib.set_volume_clean(False)
+    assert hostlib.get_volume_clean() == default

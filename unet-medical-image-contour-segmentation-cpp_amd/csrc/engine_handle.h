@@ -149,6 +149,11 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_volume;
     miunet::PinnedBuf<uint8_t> h_volume;
     size_t volume_dev_cap = 0, volume_host_cap = 0; // bytes
+    // mi_unet_volume_clean: d_vclean = the volume, out, the counts and the kernels' workspace of one call; h_vclean =
+    // the pinned staging of the volume and of the results; grown on demand, never shared with a clone
+    miunet::DeviceBuf<uint8_t> d_vclean;
+    miunet::PinnedBuf<uint8_t> h_vclean;
+    size_t vclean_dev_cap = 0, vclean_host_cap = 0; // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

@@ -350,4 +350,22 @@ size_t volume_workspace_bytes(int D, int H, int W, int n);
 hipError_t launch_volume_components(const uint8_t *masks, const VolumeArgs &a, uint8_t *out, int32_t *ids, ::mi_unet_vcomp *table,
                                     int32_t *counts, void *ws, hipStream_t s);
 
+// Volume clean-up (volume_clean.hip; include/mi_unet.h: mi_unet_volume_clean).  masks u8 [D][H][W] on the device; plane
+// k is the set { masks == v[k] }.  One launch sequence for all n planes:
+//   set / fill : the plane's set as bytes 0 / 1; with fill, volume.hip's union-find on the complement with connectivity 6, the roots
+//                that reach a face flagged from the faces' own voxels, every other background voxel added
+//   dilate     : three passes of a thresholded exact distance transform -- z (index distance in the column, capped at ez + 1), y (min
+//                over |dy| <= ey of (g uz)^2 + (dy uy)^2, saturated at r^2 + 1), x (min over |dx| <= ex, compared with r^2)
+//   erode      : the same three passes on the complement inside the volume, the result complemented
+//   emit       : bytes 0 / 1 -> 0 / v[k]
+// close = dilate, erode by B(close_r); open = erode, dilate by B(open_r); a ball that is the single voxel is skipped.  out u8
+// [n][D][H][W]; counts u64 [n][4]: the voxels of the set at entry, behind the fill, behind the close, behind the open (a skipped step
+// leaves its entry 0).  Workspace: volume_clean_workspace_bytes(D, H, W, n), not zeroed by the caller.  n * D * H * W < 2^31, units
+// and radii at most VOLUME_CLEAN_MAX_R.
+constexpr int VOLUME_CLEAN_MAX_R = 46340;               // = MI_UNET_VOLUME_CLEAN_MAX_R
+struct VolumeCleanArgs { int D = 0, H = 0, W = 0, n = 0, ux = 1, uy = 1, uz = 1, fill = 1, close_r = 0, open_r = 0; int v[VOLUME_MAX_VALUES] = {}; };
+size_t volume_clean_workspace_bytes(int D, int H, int W, int n);
+hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, uint8_t *out, unsigned long long *counts, void *ws,
+                               hipStream_t s);
+
 }  // namespace miunet

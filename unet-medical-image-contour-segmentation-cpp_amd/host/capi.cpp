@@ -185,6 +185,15 @@ void medseg_get_volume(int *on, int *connectivity, int *min_voxels, int *keep_la
     *on = v.on; *connectivity = v.connectivity; *min_voxels = v.min_voxels; *keep_largest = v.keep_largest;
     spacing_xyz[0] = v.spacing_x; spacing_xyz[1] = v.spacing_y; spacing_xyz[2] = v.spacing_z;
 }
+int medseg_set_volume_clean(int on, int fill, double close_mm, double open_mm)
+{
+    return MedicalSeg::set_volume_clean({ on != 0, fill != 0, close_mm, open_mm }) ? 0 : 1;
+}
+void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_mm)
+{
+    const MedicalSeg::VolumeClean c = MedicalSeg::get_volume_clean();
+    *on = c.on; *fill = c.fill; *close_mm = c.close_mm; *open_mm = c.open_mm;
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

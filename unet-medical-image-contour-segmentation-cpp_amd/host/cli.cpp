@@ -147,6 +147,7 @@ public:
         table_["morph"] = [this](const Words &w) { cmd_morph(w); return true; };
         table_["truth"] = [this](const Words &w) { cmd_truth(w); return true; };
         table_["volume"] = [this](const Words &w) { cmd_volume(w); return true; };
+        table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -165,6 +166,7 @@ public:
             "  morph rect|disc <open_r> [close_r]|default - Element and radii of the mask clean-up (default: rect 1 0, the 3x3 open)",
             "  truth <dir>|off               - Score every mask against <dir>/<base>_labels.raw into <base>_score.json (default: off)",
             "  volume on [6|18|26] [min N] [keep N] [spacing sx sy sz]|off - Label the slices of a directory as one volume into volume_report.json",
+            "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -379,6 +381,43 @@ private:
         const MedicalSeg::Volume cur = MedicalSeg::get_volume();
         std::cout << "Volume: " << (cur.on ? "on" : "off") << " " << cur.connectivity << " min " << cur.min_voxels << " keep " << cur.keep_largest
                   << " spacing " << cur.spacing_x << " " << cur.spacing_y << " " << cur.spacing_z << std::endl;
+    }
+
+    // volclean on [nofill] [close MM] [open MM] | volclean off | volclean (prints the setting in force)
+    void cmd_volclean(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeClean c;
+            bool ok = (w[1] == "on" || w[1] == "off") && (w[1] == "on" || w.size() == 2);
+            c.on = w[1] == "on";
+            size_t at = 2;
+            if (ok && at < w.size() && w[at] == "nofill") { c.fill = false; ++at; }
+            while (ok && at < w.size()) {
+                double *const mm = w[at] == "close" ? &c.close_mm : w[at] == "open" ? &c.open_mm : nullptr;
+                ok = mm && at + 1 < w.size();
+                if (ok) {
+                    try {
+                        size_t used = 0;
+                        *mm = std::stod(w[at + 1], &used);
+                        ok = used == w[at + 1].size();
+                    } catch (const std::exception &) {
+                        ok = false;
+                    }
+                }
+                at += 2;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volclean command (expected on [nofill] [close MM] [open MM] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_clean(c)) {
+                std::cerr << "Volume clean unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeClean cur = MedicalSeg::get_volume_clean();
+        std::cout << "Volume clean: " << (cur.on ? "on" : "off") << " " << (cur.fill ? "fill" : "nofill") << " close " << cur.close_mm << " open "
+                  << cur.open_mm << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

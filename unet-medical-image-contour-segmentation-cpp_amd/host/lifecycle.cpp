@@ -321,6 +321,21 @@ bool set_volume(const Volume &volume)
         /*handle_side=*/false);
 }
 
+bool set_volume_clean(const VolumeClean &clean)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_clean = clean;
+            const bool radii = std::isfinite(clean.close_mm) && clean.close_mm >= 0.0 && std::isfinite(clean.open_mm) && clean.open_mm >= 0.0;
+            return std::string(radii ? "" : "volume clean: the radii must be finite and not negative");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume clean: " << (clean.on ? "on" : "off") << ", fill " << (clean.fill ? "on" : "off") << ", close " << clean.close_mm
+               << " mm, open " << clean.open_mm << " mm";
+        },
+        /*handle_side=*/false);
+}
+
 Settings current_settings()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -337,6 +352,7 @@ mi_unet_window get_window() { return Preprocess::get_window(); }
 mi_unet_measure get_measure() { return current_settings().measure; }
 std::string get_truth_dir() { return current_settings().truth_dir; }
 Volume get_volume() { return current_settings().volume; }
+VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }

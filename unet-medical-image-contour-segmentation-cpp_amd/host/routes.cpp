@@ -529,16 +529,71 @@ struct VolumeStack {
     size_t D, hw;
 };
 
+// set_volume_clean: every target's plane of the stack through one mi_unet_volume_clean call with values = { 255 } on `h`
+// (mi_unet_volume_clean_host under MEDSEG_HOST_POSTPROCESS=1), in place, before label_volume.  The integer units come from
+// mi_unet_score_volume_units on the volume setting's spacing; a radius is llround(mm / unit_mm).  `json` receives the "clean" object of
+// volume_report.json.  A failure is reported, leaves the stack as it was and returns false: the batch's volume stage ends there.
+bool clean_volume(VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeClean &c, mi_unet_t *h,
+                  std::ostream &lg, std::string &json)
+{
+    try {
+        const size_t K = targets.size(), D = st.D, hw = st.hw;
+        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
+        int units[3] = { 0, 0, 0 };
+        double unit_mm = 0.0;
+        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
+            throw std::runtime_error(mi_unet_last_error());
+        auto radius = [&](double mm, const char *which) {
+            const double q = mm / unit_mm;
+            if (!(q < 2147483647.0)) throw std::runtime_error(std::string(which) + " radius is out of range");     // (llround of it must fit an int)
+            return (int)std::llround(q);
+        };
+        const mi_unet_volume_clean_opts opts{ c.fill ? 1 : 0, radius(c.close_mm, "close"), radius(c.open_mm, "open") };
+        const int value = 255;
+        const bool device = h && device_postprocess_requested();
+        std::vector<uint8_t> cleaned(K * D * hw);
+        std::vector<mi_unet_volume_clean_stat> stats(K);
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const uint8_t *const in = st.planes.data() + t * D * hw;
+            uint8_t *const o = cleaned.data() + t * D * hw;
+            const int rc = device ? mi_unet_volume_clean(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, o, &stats[t])
+                                  : mi_unet_volume_clean_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, o, &stats[t]);
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+        }
+        lg << "Volume clean: " << D << " slices, " << K << " targets, fill " << (c.fill ? "on" : "off") << ", close " << opts.close_r << ", open "
+           << opts.open_r << " (unit " << unit_mm << " mm), " << ms_since(t0) << " ms" << std::endl;
+        std::ostringstream js;
+        js << "  \"clean\": {\"fill\": " << (c.fill ? "true" : "false") << ", \"close_mm\": " << json_number(c.close_mm) << ", \"open_mm\": "
+           << json_number(c.open_mm) << ", \"unit_mm\": " << json_number(unit_mm) << ", \"close_r\": " << opts.close_r << ", \"open_r\": "
+           << opts.open_r << ", \"targets\": [";
+        for (size_t t = 0; t < K; ++t) {
+            const mi_unet_volume_clean_stat &s = stats[t];
+            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"in_voxels\": " << s.in_voxels << ", \"filled\": " << s.filled
+               << ", \"closed\": " << s.closed << ", \"opened\": " << s.opened << ", \"out_voxels\": " << s.out_voxels << "}";
+        }
+        js << "\n  ]},\n";
+        json = js.str();
+        st.planes.swap(cleaned);
+        return true;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume clean error: ") + e.what());
+        return false;
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
+// A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
+// is active (without one they are the cleaned stack itself).
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
-                  std::ostream &lg, std::vector<uint8_t> &filtered)
+                  std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string())
 {
     filtered.clear();
     try {
         const size_t K = targets.size(), D = st.D, hw = st.hw, cap = MI_UNET_VOLUME_MAX_TABLE;
-        const bool filter = v.min_voxels > 0 || v.keep_largest > 0;
+        const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
         std::vector<int32_t> found(K), kept(K);
@@ -573,7 +628,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         names("missing", true);
         js << "  \"connectivity\": " << v.connectivity << ",\n  \"min_voxels\": " << v.min_voxels << ",\n  \"keep_largest\": " << v.keep_largest
            << ",\n  \"spacing\": [" << json_number(spacing[0]) << ", " << json_number(spacing[1]) << ", " << json_number(spacing[2])
-           << "],\n  \"targets\": [";
+           << "],\n" << clean_json << "  \"targets\": [";
         for (size_t t = 0; t < K; ++t) {
             js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"found\": " << found[t] << ", \"kept\": " << kept[t]
                << ", \"components\": [";
@@ -612,7 +667,7 @@ void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filte
 {
     try {
         const size_t K = targets.size(), D = st.D, hw = st.hw;
-        const bool filter = v.min_voxels > 0 || v.keep_largest > 0;
+        const bool filter = !filtered.empty() || v.min_voxels > 0 || v.keep_largest > 0;       // (a cleaned stack comes filtered too)
         if (filter && filtered.size() != K * D * hw) throw std::runtime_error("the filtered stack is missing");
         std::vector<uint8_t> labels(D * hw), truth(D * hw);
         size_t without = 0;
@@ -788,7 +843,11 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
             ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
             std::vector<uint8_t> filtered;
-            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered);
+            std::string clean_json;
+            if (settings.volume_clean.on &&
+                !clean_volume(stack, settings.targets, settings.volume, settings.volume_clean, mi_unet_group_handle(group, 0), lg.text, clean_json))
+                return ok;
+            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json);
             if (!settings.truth_dir.empty())
                 score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
                                    lg.text);

@@ -36,6 +36,7 @@ EXPORTS = [
     "mi_unet_score_labels", "mi_unet_score_labels_host", "mi_unet_score_derive",
     "mi_unet_volume_components", "mi_unet_volume_components_host", "mi_unet_volume_derive",
     "mi_unet_score_volume", "mi_unet_score_volume_host", "mi_unet_score_volume_units", "mi_unet_score_volume_derive",
+    "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
 ]
 
 
@@ -215,6 +216,41 @@ def _volume_call(fn, head, masks, values, connectivity, min_voxels, keep_largest
     return out, table, found, kept, ids
 
 
+class VCleanStat(C.Structure):
+    """mi_unet_volume_clean_stat: 48 bytes, two int32 then five int64; VCLEAN_DTYPE is the same layout for numpy"""
+    _fields_ = [("value", C.c_int32), ("reserved", C.c_int32), ("in_voxels", C.c_int64), ("filled", C.c_int64), ("closed", C.c_int64),
+                ("opened", C.c_int64), ("out_voxels", C.c_int64)]
+
+
+VCLEAN_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VCleanStat._fields_])
+VOLUME_CLEAN_MAX_R = 46340
+
+
+class VolumeCleanOpts(C.Structure):
+    _fields_ = [("fill", C.c_int), ("close_r", C.c_int), ("open_r", C.c_int)]
+
+
+def _volume_clean_call(fn, head, masks, values, units, fill, close_r, open_r):
+    """mi_unet_volume_clean (head = (handle,)) or its host form (head = ()): masks u8 [D,H,W] (or [H,W]: one slice), units (ux, uy, uz)
+    -> (out u8 [n,D,H,W], stats VCLEAN_DTYPE [n]).  The library checks the values."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    if masks.ndim != 3:
+        raise ValueError(f"masks {masks.shape} must be one u8 [D,H,W] array")
+    d, hh, ww = masks.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: x, y, z")
+    n = max(vals.size, 1)
+    out = np.zeros((n, d, hh, ww), np.uint8)
+    stats = np.zeros(n, VCLEAN_DTYPE)
+    _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, _ptr(un), C.byref(VolumeCleanOpts(int(fill), int(close_r), int(open_r))),
+              _ptr(out), _ptr(stats)))
+    return out, stats
+
+
 def _last_regions(fn, handle):
     """(regions REGION_DTYPE [planes, cap_contours], counts int32 [planes]) of mi_unet_last_regions or its group form"""
     planes, cap = C.c_int(), C.c_int()
@@ -384,6 +420,10 @@ def lib():
         L.mi_unet_score_volume.argtypes = [C.c_void_p] + L.mi_unet_score_volume_host.argtypes
         L.mi_unet_score_volume_units.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.mi_unet_score_volume_derive.argtypes = [C.POINTER(Score), C.c_double, C.POINTER(ScoreMetrics)]
+        L.mi_unet_volume_clean_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_clean.argtypes = [C.c_void_p] + L.mi_unet_volume_clean_host.argtypes
+        L.mi_unet_volume_ball.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -771,6 +811,12 @@ class Engine:
         found int32 [n], kept int32 [n], ids int32 [n,D,H,W] or None)"""
         return _volume_call(lib().mi_unet_volume_components, (self._h,), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
 
+    # ---- a stack of masks cleaned as one volume (mi_unet_volume_clean): needs the device, not the weights
+    def volume_clean(self, masks, values, units, fill=True, close_r=0, open_r=0):
+        """masks u8 [D,H,W] of any size, values = the bytes whose sets are cleaned, units = the spacing (ux, uy, uz) as integers, the
+        radii in the same unit -> (out u8 [n,D,H,W], stats VCLEAN_DTYPE [n])"""
+        return _volume_clean_call(lib().mi_unet_volume_clean, (self._h,), masks, values, units, fill, close_r, open_r)
+
     # ---- scores of a stack as one volume (mi_unet_score_volume): needs the device, not the weights
     def score_volume(self, pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
         """pred, truth u8 [D,H,W] of any size, values = the bytes to compare, spacing_units = (ux, uy, uz) positive integers ->
@@ -897,6 +943,24 @@ def score_labels_host(pred, truth, values, quantile_ppm=50000, classes=0):
 def volume_components_host(masks, values, connectivity=26, min_voxels=0, keep_largest=0, cap=256, want_ids=False):
     """mi_unet_volume_components_host: Engine.volume_components as pure host arithmetic (needs no device)"""
     return _volume_call(lib().mi_unet_volume_components_host, (), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
+
+
+def volume_clean_host(masks, values, units, fill=True, close_r=0, open_r=0):
+    """mi_unet_volume_clean_host: Engine.volume_clean as sequential host arithmetic (needs no device)"""
+    return _volume_clean_call(lib().mi_unet_volume_clean_host, (), masks, values, units, fill, close_r, open_r)
+
+
+def volume_ball(units, r):
+    """mi_unet_volume_ball: the ball of radius r under the spacing units (ux, uy, uz) -> ((ex, ey, ez), elem u8 [2ez+1, 2ey+1, 2ex+1])"""
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: x, y, z")
+    ext = np.zeros(3, np.int32)
+    _check(lib().mi_unet_volume_ball(_ptr(un), int(r), _ptr(ext), None))
+    ex, ey, ez = (int(v) for v in ext)
+    elem = np.zeros((2 * ez + 1, 2 * ey + 1, 2 * ex + 1), np.uint8)
+    _check(lib().mi_unet_volume_ball(_ptr(un), int(r), _ptr(ext), _ptr(elem)))
+    return (ex, ey, ez), elem
 
 
 def volume_derive(comp, spacing):

@@ -21,7 +21,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_polygon_json_text_groups", "medseg_draw_overlay_groups",
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
-           "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume"]
+           "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
+           "medseg_set_volume_clean", "medseg_get_volume_clean"]
 
 
 def lib():
@@ -72,6 +73,9 @@ def lib():
         L.medseg_set_volume.argtypes = [C.c_int] * 4 + [C.c_double] * 3
         L.medseg_get_volume.argtypes = [_i] * 4 + [C.POINTER(C.c_double)]
         L.medseg_get_volume.restype = None
+        L.medseg_set_volume_clean.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
+        L.medseg_get_volume_clean.argtypes = [_i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.medseg_get_volume_clean.restype = None
         _LIB = L
     return _LIB
 
@@ -204,6 +208,18 @@ def get_volume():
     v, sp = [C.c_int() for _ in range(4)], (C.c_double * 3)()
     lib().medseg_get_volume(*[C.byref(x) for x in v], sp)
     return {"on": bool(v[0].value), "connectivity": v[1].value, "min_voxels": v[2].value, "keep_largest": v[3].value, "spacing": tuple(sp)}
+
+
+def set_volume_clean(on=True, fill=True, close_mm=0.0, open_mm=0.0) -> bool:
+    """MedicalSeg::set_volume_clean: with set_volume on, process_image_batch cleans the stack as a volume before it labels it (3-D cavity
+    fill, close and open by a ball in mm) and writes the cleaned stack and a "clean" object in volume_report.json; needs no engine"""
+    return lib().medseg_set_volume_clean(int(bool(on)), int(bool(fill)), float(close_mm), float(open_mm)) == 0
+
+
+def get_volume_clean():
+    on, fill, c, o = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+    lib().medseg_get_volume_clean(C.byref(on), C.byref(fill), C.byref(c), C.byref(o))
+    return {"on": bool(on.value), "fill": bool(fill.value), "close_mm": c.value, "open_mm": o.value}
 
 
 def get_measure():
