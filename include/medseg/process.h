@@ -119,6 +119,26 @@ struct VolumeClean {
 bool set_volume_clean(const VolumeClean &clean);
 VolumeClean get_volume_clean();
 
+// The border of the labelled stack as a surface (mi_unet_volume_mesh in include/mi_unet.h).  It acts only together
+// with set_volume's `on`: once the components are labelled, every target's plane that was labelled -- the filtered stack under a
+// filter, else the (cleaned) stack -- goes through one mi_unet_volume_mesh call with values = { 255 } (mi_unet_volume_mesh_host under
+// MEDSEG_HOST_POSTPROCESS=1) under `placement` (MI_UNET_MESH_FACES or MI_UNET_MESH_NETS), and is written as binary STL in millimetres
+// of the volume setting's spacing: <output_dir>/volume_mesh.stl, or volume_mesh_class<cls>.stl under a non-default target list; a
+// target without quads writes no file.  The file: an 80-byte header that starts "medseg volume mesh" and is padded with zeros, the
+// triangle count as uint32, then per triangle -- (0, 1, 2) and (0, 2, 3) of every quad, in order -- the unit normal of the float
+// positions (computed in double, rounded to float; 0, 0, 0 for a zero cross product), the three mi_unet_volume_mesh_positions vertices
+// and an attribute of 0.  volume_report.json gains a "mesh" object behind "targets": "placement" and "targets" with per target "label",
+// "quads", "verts", "area_mm2", "volume_mm3" (mi_unet_volume_mesh_derive) and "file" (null without quads).  One log line per batch; a
+// failure is reported as "Volume mesh error: ..." and ends only this step.  With it off (the default) every artefact and every log
+// line is what it is without the setting.  Needs no engine and survives initialize_engine.  false, message on stderr, setting
+// unchanged: a placement that is neither of the two.
+struct VolumeMesh {
+    bool on = false;
+    int placement = 0;                                      // MI_UNET_MESH_FACES
+};
+bool set_volume_mesh(const VolumeMesh &mesh);
+VolumeMesh get_volume_mesh();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

@@ -66,6 +66,10 @@ void medseg_get_volume(int *on, int *connectivity, int *min_voxels, int *keep_la
  * 0 on success; medseg_get_volume_clean fills the four values. */
 int medseg_set_volume_clean(int on, int fill, double close_mm, double open_mm);
 void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_mm);
+/* The border of the labelled stack as binary STL: MedicalSeg::set_volume_mesh / get_volume_mesh (include/medseg/process.h); placement is
+ * MI_UNET_MESH_FACES or MI_UNET_MESH_NETS.  0 on success; medseg_get_volume_mesh fills the two values. */
+int medseg_set_volume_mesh(int on, int placement);
+void medseg_get_volume_mesh(int *on, int *placement);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

@@ -601,6 +601,84 @@ int mi_unet_volume_clean_host(const uint8_t *masks, int D, int H, int W, const i
                               const mi_unet_volume_clean_opts *opts, uint8_t *out, mi_unet_volume_clean_stat *stats);
 int mi_unet_volume_ball(const int spacing_units[3], int r, int extent[3] /* x, y, z half-widths */, uint8_t *elem /* or NULL */);
 
+/* ---- Volume mesh: the border of a stack of masks as a closed surface of oriented quads over shared vertices ----------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  It is the 3-D counterpart of the
+ * contour stage: every exposed voxel face of a set becomes one quad.  Exact in integers; millimetres enter only in the two host
+ * functions behind it.
+ * Input is one byte volume masks, u8 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), and n
+ * byte values, 1 <= n <= MI_UNET_VOLUME_MAX_VALUES.  Plane k is the set S = { masks == values[k] }; positions outside the volume are
+ * not in S; planes are independent.
+ *   QUADS        one quad for every voxel v = (x, y, z) of S and every direction d whose 6-neighbour is not in S, the directions in the
+ *                order -x, +x, -y, +y, -z, +z.  The quads of a plane are ordered by (z * H * W + y * W + x, d) ascending.  quads_x /
+ *                _y / _z count them by the axis they are perpendicular to: the sums of faces_x / _y / _z over all components of the plane
+ *                in mi_unet_volume_components, at any connectivity.
+ *   CORNERS      grid corner (i, j, k), 0 <= i <= W, 0 <= j <= H, 0 <= k <= D, has the index c = (k * (H + 1) + j) * (W + 1) + i; voxel
+ *                (x, y, z) spans the corners x .. x + 1, y .. y + 1, z .. z + 1.  A corner is a vertex of the plane iff at least one
+ *                quad uses it.  Vertices are ordered by c ascending; a vertex's index is its rank.
+ *   ORIENTATION  a quad lists its four vertex indices from the corner with the smallest c, then round the face counter-clockwise as
+ *                seen from outside S: the right-hand normal points out of S.  Relative to (x, y, z):
+ *                  -x: (0,0,0) (0,0,1) (0,1,1) (0,1,0)      +x: (1,0,0) (1,1,0) (1,1,1) (1,0,1)
+ *                  -y: (0,0,0) (1,0,0) (1,0,1) (0,0,1)      +y: (0,1,0) (0,1,1) (1,1,1) (1,1,0)
+ *                  -z: (0,0,0) (0,1,0) (1,1,0) (1,0,0)      +z: (0,0,1) (1,0,1) (1,1,1) (0,1,1)
+ *                Wherever triangles are needed they are (0, 1, 2), (0, 2, 3).  Every directed edge is matched by its reverse, so the
+ *                surface is closed; an edge where two voxels of S touch only along it is used by four quads (non-manifold).
+ *   PLACEMENT    a vertex carries its corner (x, y, z) and an offset (ox, oy, oz, n); its position in voxel units is
+ *                corner + o / (2 n) per axis.
+ *                MI_UNET_MESH_FACES: o = 0, n = 1: the vertices sit at the voxel corners, the mesh encloses exactly |S| voxels and its
+ *                  area is the crack surface of mi_unet_volume_derive.
+ *                MI_UNET_MESH_NETS (naive surface nets): the eight voxel positions round the corner, (i - 1 .. i, j - 1 .. j, k - 1 .. k),
+ *                  have twelve axis-parallel edges; an edge is cut when exactly one of its two ends is in S.  n = the number of cut
+ *                  edges (3 .. 9 or 12; n >= 1 holds exactly for the vertices) and o = the sum over the cut edges of the edge's midpoint
+ *                  in doubled units relative to the corner: 0 on the edge's own axis, -1 or +1 on the other two for the lower or higher
+ *                  index.  |o| < n on every axis, so a vertex stays strictly inside the unit cube centred on its corner and no two
+ *                  vertices coincide.  For a digitised ball the area is within a few per cent of the sphere's (1.030, 1.014, 1.025 of
+ *                  4 pi r^2 at r = 6, 12, 20, where FACES gives 1.499, 1.462, 1.500) and the enclosed volume 0.97 .. 0.995 of |S|.
+ *                Both placements have the same quads and the same vertex order.
+ *   COUNTS       stats[k] is always exact, whatever the caps are: value and placement echo the arguments; quads, verts, quads_x, _y, _z.
+ *   CAPS         verts[k] ([n][cap_verts]) and quads[k] ([n][cap_quads][4]) hold the first min(count, cap) entries in the orders above;
+ *                the entries behind them are all zero.  A quad in the kept prefix keeps its true vertex indices even where they are
+ *                >= cap_verts.  verts == NULL requires cap_verts == 0 and is legal, and so for quads: the counting call.
+ * Limits, each with its reason:
+ *   D, H, W >= 1;
+ *   6 * (D + 1) * (H + 1) * (W + 1) < 2^31: every corner index, every quad offset of a plane and every count is an int (1024 x 512 x 512
+ *           fits); planes are processed one after another, so n does not enter;
+ *   values in 0 .. 255 and not repeated; placement one of the two; caps in 0 .. 2^31 - 1.
+ * mi_unet_volume_mesh takes host buffers of any size; its workspace (6 bytes per voxel, the kept prefixes of one plane) grows on demand,
+ * belongs to the handle and is freed by mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It
+ * changes no setting and nothing mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued and
+ * nothing written: a null masks, values or stats; D, H or W < 1; n outside 1 .. MI_UNET_VOLUME_MAX_VALUES; a value outside 0 .. 255 or
+ * repeated; the corner limit; a placement other than the two; a negative cap; a NULL array with a cap other than 0.  A workspace that
+ * cannot be allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_mesh_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle, same
+ * bytes.
+ * mi_unet_volume_mesh_positions and mi_unet_volume_mesh_derive are pure host arithmetic in double.  A voxel is a box of
+ * spacing_xyz[0] x [1] x [2] millimetres and corner 0 is at 0: a vertex lies at (corner + o / (2.0 * n)) * spacing per axis, which
+ * _positions rounds once to float.  _derive walks the quads in order and their two triangles (a, b, c) in order and accumulates
+ * area_mm2 += 0.5 |(b - a) x (c - a)| and volume_mm3 += a . (b x c) / 6 sequentially; the volume is positive for the outward
+ * orientation above.  nq quads refer to nv vertices.  MI_UNET_EARG, outputs untouched: a null pointer (quads may be NULL when nq == 0,
+ * verts and xyz when nv == 0); nv or nq < 0; n == 0 in a vertex; an index outside 0 .. nv - 1; a spacing that is not finite and > 0.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_MESH_FACES 0
+#define MI_UNET_MESH_NETS  1
+typedef struct mi_unet_mesh_vertex {               /* 16 bytes, no padding */
+    int32_t x, y, z;                               /* the grid corner */
+    int8_t ox, oy, oz;                             /* offset in units of 1 / (2 n) voxel */
+    uint8_t n;                                     /* cut edges round the corner (NETS), or 1 (FACES) */
+} mi_unet_mesh_vertex;
+typedef struct mi_unet_mesh_stat {                 /* 48 bytes, no padding */
+    int32_t value, placement;                      /* echo of the plane's value and of the placement */
+    int64_t quads, verts, quads_x, quads_y, quads_z;
+} mi_unet_mesh_stat;
+typedef struct mi_unet_mesh_metrics { double area_mm2, volume_mm3; } mi_unet_mesh_metrics;
+int mi_unet_volume_mesh(mi_unet_t *h, const uint8_t *masks /* [D][H][W] host */, int D, int H, int W, const int *values, int n,
+                        int placement, mi_unet_mesh_vertex *verts /* [n][cap_verts] or NULL */, int cap_verts,
+                        int32_t *quads /* [n][cap_quads][4] or NULL */, int cap_quads, mi_unet_mesh_stat *stats /* [n] */);
+int mi_unet_volume_mesh_host(const uint8_t *masks, int D, int H, int W, const int *values, int n, int placement,
+                             mi_unet_mesh_vertex *verts, int cap_verts, int32_t *quads, int cap_quads, mi_unet_mesh_stat *stats);
+int mi_unet_volume_mesh_positions(const mi_unet_mesh_vertex *verts, int nv, const double spacing_xyz[3], float *xyz /* [nv][3] */);
+int mi_unet_volume_mesh_derive(const mi_unet_mesh_vertex *verts, int nv, const int32_t *quads /* [nq][4] */, int nq,
+                               const double spacing_xyz[3], mi_unet_mesh_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

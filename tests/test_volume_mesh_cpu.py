@@ -1,0 +1,339 @@
+"""The volume mesh (include/mi_unet.h: mi_unet_volume_mesh) without a device: mi_unet_volume_mesh_host against the numpy
+reference of volume_mesh_ref.py vertex for vertex and quad for quad, the known answers, the properties the definition promises
+(closed, outward, Euler's formula, the enclosed volume, the caps), the two functions that turn a mesh into millimetres, the argument
+checks, the struct sizes, the host half as a stand-alone program, and the facade's setting.  Integer work is compared exactly."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import volume_mesh_ref as mr
+import volume_ref as vr
+from miunet import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+BOTH = [p for p, _ in mr.PLACEMENTS]
+
+
+def host_mesh(vol, placement, value=1):
+    """(verts, quads, stat) of one value through the host form"""
+    meshes, stats = binding.volume_mesh_host(vol, (value,), placement)
+    return meshes[0][0], meshes[0][1], stats[0]
+
+
+def test_the_cases_are_not_degenerate():
+    mr.assert_not_degenerate()
+
+
+@pytest.mark.parametrize("name,masks,values,counts", mr.known_answers(), ids=[c[0] for c in mr.known_answers()])
+def test_known_answers(name, masks, values, counts):
+    for pname, placement in mr.PLACEMENTS:
+        got = binding.volume_mesh_host(masks, values, pname)
+        mr.assert_equal(got, mr.mesh(masks, values, placement), f"{name} {pname}")
+        assert (int(got[1][0]["verts"]), int(got[1][0]["quads"])) == counts, (name, pname)
+        assert got[1][0]["value"] == values[0] and got[1][0]["placement"] == placement
+    if counts == (0, 0):                                        # an empty plane: all-zero arrays under caps of any size
+        verts, quads, stats = binding.volume_mesh_host(masks, values, "nets", cap=(5, 3), raw=True)
+        assert not verts[0].tobytes().strip(b"\0") and not quads[0].any() and stats[0]["quads"] == 0 and stats[0]["verts"] == 0
+
+
+def test_label_volume_planes_are_independent():
+    name, labels, values, _ = mr.known_answers()[-1]
+    meshes, stats = binding.volume_mesh_host(labels, values, "nets")
+    for k, v in enumerate(values):
+        (one,), st = binding.volume_mesh_host((labels == v).astype(np.uint8), (1,), "nets")
+        assert one[0].tobytes() == meshes[k][0].tobytes() and np.array_equal(one[1], meshes[k][1]), v
+        assert stats[k]["value"] == v and stats[k]["quads"] == st[0]["quads"] > 0
+
+
+@pytest.mark.parametrize("shape", mr.NOISE_SHAPES + (mr.FLAT_SHAPE,))
+def test_host_equals_reference_on_noise(shape):
+    for pname, placement in mr.PLACEMENTS:
+        mr.assert_equal(binding.volume_mesh_host(mr.noise(shape), mr.NOISE_VALUES, pname), mr.noise_ref(shape, placement), f"{shape} {pname}")
+
+
+def test_host_equals_reference_on_the_larger_shapes():
+    for vol, values in ((mr.two_shells(), (1,)), (mr.checkerboard((6, 9, 70)), (1, 0)), (vr.serpentine(), (1,))):
+        for pname, placement in mr.PLACEMENTS:
+            mr.assert_equal(binding.volume_mesh_host(vol, values, pname), mr.mesh(vol, values, placement), pname)
+
+
+# ---- properties, on the host form ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", mr.NOISE_SHAPES + (mr.FLAT_SHAPE,))
+def test_quad_counts_per_axis_are_the_face_counts_of_the_components_stage(shape):
+    vol = mr.noise(shape)
+    _, stats = binding.volume_mesh_host(vol, mr.NOISE_VALUES, "faces")
+    for connectivity in vr.CONNECTIVITIES:
+        _, table, found, _, _ = binding.volume_components_host(vol, mr.NOISE_VALUES, connectivity, cap=vr.MAX_TABLE)
+        for k, v in enumerate(mr.NOISE_VALUES):
+            assert found[k] <= vr.MAX_TABLE
+            want = tuple(int(s.sum()) for s in vr.faces(vol == v))
+            assert tuple(int(stats[k][f]) for f in ("quads_x", "quads_y", "quads_z")) == want, (shape, v)
+            assert tuple(int(table[k][f].sum()) for f in ("faces_x", "faces_y", "faces_z")) == want, (shape, v, connectivity)
+            assert stats[k]["quads"] == sum(want)
+
+
+@pytest.mark.parametrize("placement", BOTH)
+def test_every_directed_edge_is_matched_by_its_reverse(placement):
+    for vol in (mr.noise(mr.NOISE_SHAPES[0]) == 2, mr.checkerboard(), mr.ball(6), mr.known_answers()[3][1]):
+        verts, quads, _ = host_mesh(vol.astype(np.uint8), placement)
+        assert mr.edge_balance(quads, verts.size)[0]
+        assert quads.min() == 0 and quads.max() == verts.size - 1 and np.unique(quads).size == verts.size      # every vertex is used
+
+
+def test_faces_encloses_exactly_the_voxels():
+    """the integer sum of det(a, b, c) over the triangles of the corner coordinates is 6 |S|: the orientation is outward everywhere,
+    cavities and non-manifold edges included"""
+    for vol in (mr.noise(mr.NOISE_SHAPES[0]) == 1, mr.noise(mr.NOISE_SHAPES[2]) == 3, mr.two_shells(), mr.checkerboard(), mr.ball(6)):
+        vol = np.asarray(vol, np.uint8)
+        for placement in BOTH:                                  # the corners are the same under both placements
+            verts, quads, _ = host_mesh(vol, placement)
+            assert mr.det_sum(verts, quads) == 6 * int(vol.sum())
+
+
+def test_a_mirrored_volume_still_encloses_plus_the_voxels():
+    vol = (mr.noise(mr.NOISE_SHAPES[0]) == 2).astype(np.uint8)
+    for axes in ((0,), (1,), (2,), (0, 1, 2)):
+        verts, quads, st = host_mesh(np.ascontiguousarray(np.flip(vol, axes)), "faces")
+        assert mr.det_sum(verts, quads) == 6 * int(vol.sum())
+        got = binding.volume_mesh_derive(verts, quads, (1, 1, 1))["volume_mm3"]             # (every term is divided by 6: not exact)
+        assert abs(got - float(vol.sum())) <= 1e-9 * float(vol.sum())
+
+
+def test_euler_characteristic_of_a_box_and_of_a_ball():
+    for vol in (np.pad(np.ones((3, 4, 5), np.uint8), 1), mr.ball(6)):
+        for placement in BOTH:
+            verts, quads, _ = host_mesh(vol, placement)
+            balanced, edges, shared = mr.edge_balance(quads, verts.size)
+            assert balanced and shared == 0 and edges == 2 * quads.shape[0]          # a manifold of quads: E = 2 F
+            assert verts.size - edges + quads.shape[0] == 2
+
+
+def test_offsets_stay_inside_the_unit_cube_and_the_placements_share_quads_and_corners():
+    for shape in mr.NOISE_SHAPES:
+        vol = mr.noise(shape)
+        faces, fs = binding.volume_mesh_host(vol, mr.NOISE_VALUES, "faces")
+        nets, ns = binding.volume_mesh_host(vol, mr.NOISE_VALUES, "nets")
+        for (fv, fq), (nv, nq) in zip(faces, nets):
+            assert np.array_equal(fq, nq) and all(np.array_equal(fv[a], nv[a]) for a in "xyz")
+            assert (fv["n"] == 1).all() and not fv["ox"].any() and not fv["oy"].any() and not fv["oz"].any()
+            for a in ("ox", "oy", "oz"):
+                assert (np.abs(nv[a].astype(np.int32)) < nv["n"]).all()
+                assert (np.abs(nv[a] / (2.0 * nv["n"])) <= 1.0 / 3.0 + 1e-15).all()        # no vertex moves more than a third of a voxel
+            assert set(np.unique(nv["n"]).tolist()) <= {3, 4, 5, 6, 7, 8, 9, 12}
+        assert all(np.array_equal(fs[f], ns[f]) for f in mr.STAT_FIELDS if f != "placement")
+
+
+def test_caps_keep_the_prefixes_and_the_counts():
+    shape = mr.NOISE_SHAPES[0]
+    vol = mr.noise(shape)
+    for pname, placement in mr.PLACEMENTS:
+        ref = mr.noise_ref(shape, placement)
+        nv, nq = min(r[0].size for r in ref), min(r[1].shape[0] for r in ref)
+        for cap in ((nv // 2, nq // 2), (0, nq // 2), (nv // 2, 0), (0, 0), (1 << 16, 7)):
+            mr.assert_equal(binding.volume_mesh_host(vol, mr.NOISE_VALUES, pname, cap=cap), ref, f"caps {cap}", cap[0], cap[1])
+            verts, quads, _ = binding.volume_mesh_host(vol, mr.NOISE_VALUES, pname, cap=cap, raw=True)
+            for k, (rv, rq, _) in enumerate(ref):
+                assert not verts[k, min(rv.size, cap[0]):].tobytes().strip(b"\0") and not quads[k, min(rq.shape[0], cap[1]):].any(), (cap, k)
+        (_, gq), = binding.volume_mesh_host(vol, (1,), pname, cap=(3, nq))[0]
+        assert np.array_equal(gq, ref[0][1][:nq]) and gq.max() >= 3              # true indices past cap_verts
+
+
+# ---- millimetres ----------------------------------------------------------------------------------------------------------------------------
+SPACINGS = ((1.0, 1.0, 1.0), (0.7, 0.7, 5.0), (0.3125, 1.25, 0.9))
+
+
+def test_faces_metrics_equal_the_components_stage():
+    """area and volume of the FACES mesh against the sums of mi_unet_volume_derive over the components.  Both sides are sums of fewer
+    than 2^18 positive doubles (asserted), each term correct to a few ulp, accumulated sequentially: the relative error of either is
+    below a few times 2^18 * 2^-53 = 2.9e-11, far inside 1e-9."""
+    for shape in mr.NOISE_SHAPES:
+        vol = mr.noise(shape)
+        meshes, stats = binding.volume_mesh_host(vol, mr.NOISE_VALUES, "faces")
+        _, table, found, _, _ = binding.volume_components_host(vol, mr.NOISE_VALUES, 26, cap=vr.MAX_TABLE)
+        for sp in SPACINGS:
+            for k in range(len(mr.NOISE_VALUES)):
+                assert 2 * stats[k]["quads"] < 2 ** 18 and found[k] <= vr.MAX_TABLE
+                m = binding.volume_mesh_derive(meshes[k][0], meshes[k][1], sp)
+                comps = [binding.volume_derive(table[k][i], sp) for i in range(found[k])]
+                area, volume = sum(c["surface_mm2"] for c in comps), sum(c["volume_mm3"] for c in comps)
+                assert abs(m["area_mm2"] - area) <= 1e-9 * area and abs(m["volume_mm3"] - volume) <= 1e-9 * volume, (shape, sp, k)
+                want = mr.derive(meshes[k][0], meshes[k][1], sp)
+                assert abs(m["area_mm2"] - want["area_mm2"]) <= 1e-9 * area and abs(m["volume_mm3"] - want["volume_mm3"]) <= 1e-9 * volume
+
+
+def test_surface_nets_give_the_area_of_the_ball():
+    """the radius-12 ball at unit spacing: 1.462 of 4 pi r^2 under FACES, 1.014 under NETS (the reference's figures)"""
+    vol, sphere = mr.ball(12), 4 * math.pi * 144
+    ratio = {}
+    for pname, placement in mr.PLACEMENTS:
+        verts, quads, _ = host_mesh(vol, pname)
+        m = binding.volume_mesh_derive(verts, quads, (1, 1, 1))
+        want = mr.derive(*mr.mesh_set(vol == 1, placement)[:2], (1, 1, 1))
+        assert abs(m["area_mm2"] - want["area_mm2"]) <= 1e-9 * sphere and abs(m["volume_mm3"] - want["volume_mm3"]) <= 1e-9 * vol.sum()
+        ratio[pname] = m["area_mm2"] / sphere, m["volume_mm3"] / float(vol.sum())
+    assert ratio["faces"][0] > 1.4 and abs(ratio["faces"][1] - 1.0) <= 1e-9
+    assert abs(ratio["nets"][0] - 1.0) < 0.05 and 0.97 <= ratio["nets"][1] <= 0.995
+    assert (round(ratio["faces"][0], 3), round(ratio["nets"][0], 3)) == (1.462, 1.014)
+
+
+def test_positions_are_the_formula_rounded_once():
+    for sp in SPACINGS:
+        for pname in BOTH:
+            verts, _, _ = host_mesh((mr.noise(mr.NOISE_SHAPES[0]) == 1).astype(np.uint8), pname)
+            got = binding.volume_mesh_positions(verts, sp)
+            assert got.dtype == np.float32 and got.tobytes() == mr.positions64(verts, sp).astype(np.float32).tobytes()
+    assert binding.volume_mesh_positions(np.zeros(0, binding.MESH_VERTEX_DTYPE), (1, 1, 1)).shape == (0, 3)
+    assert binding.volume_mesh_derive(np.zeros(0, binding.MESH_VERTEX_DTYPE), np.zeros((0, 4), np.int32), (1, 1, 1)) == dict(area_mm2=0.0, volume_mm3=0.0)
+
+
+def test_metric_argument_errors_leave_outputs_untouched():
+    L = binding.lib()
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    verts, quads, _ = host_mesh(mr.known_answers()[0][1], "nets")
+    good_sp = np.array([1.0, 2.0, 3.0])
+    bad_n, bad_q = verts.copy(), quads.copy()
+    bad_n["n"][5] = 0
+    bad_q[2, 1] = verts.size
+    neg_q = quads.copy()
+    neg_q[0, 0] = -1
+    spacings = [np.array(s) for s in ((0.0, 1, 1), (1, -1.0, 1), (1, 1, float("nan")), (float("inf"), 1, 1))]
+    m = binding.MeshMetrics(-1.0, -2.0)
+    xyz = np.full((verts.size, 3), 7.0, np.float32)
+    assert L.mi_unet_volume_mesh_derive(ptr(verts), verts.size, ptr(quads), 6, ptr(good_sp), C.byref(m)) == 0 and m.area_mm2 > 0
+    cases = [(None, verts.size, quads, 6, good_sp), (verts, verts.size, None, 6, good_sp), (verts, verts.size, quads, 6, None),
+             (bad_n, verts.size, quads, 6, good_sp), (verts, verts.size, bad_q, 6, good_sp), (verts, verts.size, neg_q, 6, good_sp),
+             (verts, verts.size - 1, quads, 6, good_sp), (verts, -1, quads, 6, good_sp), (verts, verts.size, quads, -1, good_sp)]
+    cases += [(verts, verts.size, quads, 6, s) for s in spacings]
+    for i, (v, nv, q, nq, sp) in enumerate(cases):
+        m = binding.MeshMetrics(-1.0, -2.0)
+        assert L.mi_unet_volume_mesh_derive(ptr(v), nv, ptr(q), nq, ptr(sp), C.byref(m)) == 1, i
+        assert (m.area_mm2, m.volume_mm3) == (-1.0, -2.0) and b"mi_unet_volume_mesh_derive" in L.mi_unet_last_error(), i
+    assert L.mi_unet_volume_mesh_derive(ptr(verts), verts.size, ptr(quads), 6, ptr(good_sp), None) == 1
+    pcases = [(None, verts.size, good_sp, xyz), (verts, verts.size, None, xyz), (verts, verts.size, good_sp, None), (bad_n, verts.size, good_sp, xyz),
+              (verts, -1, good_sp, xyz)] + [(verts, verts.size, s, xyz) for s in spacings]
+    for i, (v, nv, sp, out) in enumerate(pcases):
+        assert L.mi_unet_volume_mesh_positions(ptr(v), nv, ptr(sp), ptr(out)) == 1, i
+        assert (xyz == 7.0).all() and b"mi_unet_volume_mesh_positions" in L.mi_unet_last_error(), i
+
+
+# ---- argument errors -----------------------------------------------------------------------------------------------------------------------
+def earg_cases():
+    """(name, dict of overrides of a good call's arguments); every one must return MI_UNET_EARG"""
+    return [("null masks", dict(masks=None)), ("null values", dict(values=None)), ("null stats", dict(stats=None)),
+            ("D = 0", dict(D=0)), ("H = 0", dict(H=0)), ("W = -1", dict(W=-1)),
+            ("n = 0", dict(n=0)), ("n = 9", dict(n=9, vals=list(range(9)))), ("value 256", dict(vals=[1, 256])), ("value -1", dict(vals=[-1, 2])),
+            ("repeated", dict(vals=[2, 2])), ("too many corners", dict(D=1024, H=1024, W=512)),
+            ("one corner too many", dict(D=1, H=1, W=(2 ** 31 + 23) // 24 - 1)),
+            ("corners past 64 bits", dict(D=2 ** 31 - 1, H=2 ** 31 - 1, W=2 ** 31 - 1)),
+            ("placement 2", dict(placement=2)), ("placement -1", dict(placement=-1)),
+            ("cap_verts -1", dict(cap_verts=-1)), ("cap_quads -1", dict(cap_quads=-1)),
+            ("null verts with a cap", dict(verts=None)), ("null quads with a cap", dict(quads=None))]
+
+
+def legal_cases():
+    """both sides of each limit, and the arrays that may be NULL"""
+    return [("null verts, cap 0", dict(verts=None, cap_verts=0)), ("null quads, cap 0", dict(quads=None, cap_quads=0)),
+            ("caps of 0 with arrays", dict(cap_verts=0, cap_quads=0)), ("placement 1", dict(placement=1)), ("one value", dict(vals=[2])),
+            ("the counting call", dict(verts=None, cap_verts=0, quads=None, cap_quads=0))]
+
+
+def call_with(fn, head, case):
+    """a good 2 x 5 x 7 call with the case's overrides, through ctypes; returns (rc, outputs untouched)"""
+    masks = np.ones((2, 5, 7), np.uint8)
+    masks[0, 2, 3] = 2
+    vals = np.asarray(case.get("vals", [1, 2]), np.int32)
+    verts, quads, stats = np.full((9, 20, 16), 0x55, np.uint8), np.full((9, 20, 4), 0x55555555, np.int32), np.full((9, 48), 0x55, np.uint8)
+    arrays = dict(masks=masks, values=vals, verts=verts, quads=quads, stats=stats)
+    ptr = lambda name: None if name in case and case[name] is None else arrays[name].ctypes.data_as(C.c_void_p)
+    before = masks.copy()
+    rc = fn(*head, ptr("masks"), case.get("D", 2), case.get("H", 5), case.get("W", 7), ptr("values"), case.get("n", len(vals)),
+            case.get("placement", 0), ptr("verts"), case.get("cap_verts", 20), ptr("quads"), case.get("cap_quads", 20), ptr("stats"))
+    untouched = (verts == 0x55).all() and (quads == 0x55555555).all() and (stats == 0x55).all() and np.array_equal(masks, before)
+    return rc, bool(untouched)
+
+
+def test_the_corner_limit_is_where_the_header_says():
+    """6 (D + 1)(H + 1)(W + 1) < 2^31: 1024 x 512 x 512 fits; a row of W voxels has 4 (W + 1) corners"""
+    assert 6 * 1025 * 513 * 513 < 2 ** 31
+    w_bad = (2 ** 31 + 23) // 24 - 1                             # the smallest W with 24 (W + 1) >= 2^31
+    assert 24 * (w_bad + 1) >= 2 ** 31 > 24 * w_bad
+
+
+def test_host_argument_errors_leave_outputs_untouched():
+    L = binding.lib()
+    rc, untouched = call_with(L.mi_unet_volume_mesh_host, (), {})
+    assert rc == 0 and not untouched                                        # the good call the cases are made from
+    for name, case in earg_cases():
+        rc, untouched = call_with(L.mi_unet_volume_mesh_host, (), case)
+        assert rc == 1 and untouched, name
+        assert b"mi_unet_volume_mesh_host" in L.mi_unet_last_error(), name
+    for name, case in legal_cases():
+        assert call_with(L.mi_unet_volume_mesh_host, (), case)[0] == 0, name
+
+
+def test_struct_sizes_are_the_documented_ones():
+    assert C.sizeof(binding.MeshVertex) == binding.MESH_VERTEX_DTYPE.itemsize == mr.VERTEX_DTYPE.itemsize == 16
+    assert C.sizeof(binding.MeshStat) == binding.MESH_STAT_DTYPE.itemsize == 48 and C.sizeof(binding.MeshMetrics) == 16
+    assert tuple(n for n, _ in binding.MeshStat._fields_) == mr.STAT_FIELDS == binding.MESH_STAT_DTYPE.names
+    assert binding.MESH_VERTEX_DTYPE == mr.VERTEX_DTYPE
+    header = open(os.path.join(ROOT, "include", "mi_unet.h")).read()
+    assert "mi_unet_mesh_vertex {               /* 16 bytes, no padding */" in header
+    assert "mi_unet_mesh_stat {                 /* 48 bytes, no padding */" in header
+    assert "#define MI_UNET_MESH_FACES 0" in header and "#define MI_UNET_MESH_NETS  1" in header
+    assert binding.MESH_PLACEMENTS == {"faces": mr.FACES, "nets": mr.NETS}
+    for name in ("mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive"):
+        assert hasattr(binding.lib(), name) and name in binding.EXPORTS
+
+
+def test_host_half_as_a_stand_alone_program(tmp_path):
+    """tests/cpu/volume_mesh_host_test.cpp + csrc/volume_mesh.cpp without its device entry point, built by a plain C++ compiler: the
+    form in which the host half runs under -fsanitize=address,undefined (the command is in the program's header); here it is built
+    without"""
+    exe = tmp_path / "volume_mesh_host_test"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_VOLUME_MESH_NO_DEVICE", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "volume_mesh_host_test.cpp"), os.path.join(PKG, "csrc", "volume_mesh.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, timeout=120)
+    assert r.returncode == 0 and b"volume_mesh_host_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]
+
+
+# ---- the facade's setting (needs no engine) ---------------------------------------------------------------------------------------------------
+def test_cli_volmesh_command():
+    from miunet import hostlib
+    cli = os.path.join(os.path.dirname(hostlib.LIB_PATH), "medseg_cli")
+    script = ("volmesh\nvolmesh on\nvolmesh on nets\nvolmesh\nvolmesh on faces\nvolmesh off nets\nvolmesh on smooth\nvolmesh maybe\n"
+              "volmesh on nets extra\nvolmesh on nets\nvolmesh off\nvolume\nvolclean\nhelp\nexit\n")
+    r = subprocess.run([cli], input=script.encode(), capture_output=True, timeout=60)
+    out, err = r.stdout.decode(), r.stderr.decode()
+    assert r.returncode == 0
+    said = [l.replace("> ", "") for l in out.splitlines() if l.replace("> ", "").startswith("Volume mesh:")]
+    assert said == ["Volume mesh: off faces", "Volume mesh: on faces", "Volume mesh: on nets", "Volume mesh: on nets", "Volume mesh: on faces",
+                    "Volume mesh: on nets", "Volume mesh: off faces"]
+    # off with a placement, an unknown placement, an unknown word, a word too many
+    assert err.count("Invalid volmesh command") == 4 and "Volume mesh unchanged" not in err
+    assert "volmesh on [faces|nets]|off" in out
+    assert "Volume: off 26 min 0 keep 0 spacing 1 1 1" in out and "Volume clean: off fill close 0 open 0" in out      # the siblings are untouched
+
+
+def test_volume_mesh_setting_round_trips_through_the_c_view():
+    from miunet import hostlib
+    default = {"on": False, "placement": "faces"}
+    volume, clean = hostlib.get_volume(), hostlib.get_volume_clean()
+    assert hostlib.get_volume_mesh() == default
+    try:
+        assert hostlib.set_volume_mesh(True, "nets")
+        want = {"on": True, "placement": "nets"}
+        assert hostlib.get_volume_mesh() == want
+        for bad in (2, -1):
+            assert not hostlib.set_volume_mesh(True, bad) and hostlib.get_volume_mesh() == want, bad
+        assert hostlib.set_volume_mesh(True) and hostlib.get_volume_mesh() == {"on": True, "placement": "faces"}
+        assert hostlib.get_volume() == volume and hostlib.get_volume_clean() == clean      # a setting of its own
+    finally:
+        assert hostlib.set_volume_mesh(False)
+    assert hostlib.get_volume_mesh() == default
+    for name in ("medseg_set_volume_mesh", "medseg_get_volume_mesh"):
+        assert name in open(os.path.join(ROOT, "include", "medseg_c.h")).read()

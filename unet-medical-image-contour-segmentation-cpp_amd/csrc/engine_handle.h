@@ -154,6 +154,12 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_vclean;
     miunet::PinnedBuf<uint8_t> h_vclean;
     size_t vclean_dev_cap = 0, vclean_host_cap = 0; // bytes
+    // mi_unet_volume_mesh: d_vmesh = the volume, the counts and the kernels' workspace of one call; h_vmesh = the pinned
+    // staging of the volume and of the counts; d_vmesh_out / h_vmesh_out = the kept vertices and quads of one plane, sized by its counts;
+    // grown on demand, never shared with a clone
+    miunet::DeviceBuf<uint8_t> d_vmesh, d_vmesh_out;
+    miunet::PinnedBuf<uint8_t> h_vmesh, h_vmesh_out;
+    size_t vmesh_dev_cap = 0, vmesh_host_cap = 0, vmesh_out_dev_cap = 0, vmesh_out_host_cap = 0;    // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

@@ -12,6 +12,7 @@
 struct mi_unet_region;      // include/mi_unet.h
 struct mi_unet_score;
 struct mi_unet_vcomp;
+struct mi_unet_mesh_vertex;
 
 namespace miunet {
 
@@ -367,5 +368,24 @@ struct VolumeCleanArgs { int D = 0, H = 0, W = 0, n = 0, ux = 1, uy = 1, uz = 1,
 size_t volume_clean_workspace_bytes(int D, int H, int W, int n);
 hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, uint8_t *out, unsigned long long *counts, void *ws,
                                hipStream_t s);
+
+// Volume mesh (volume_mesh.hip; include/mi_unet.h: mi_unet_volume_mesh).  masks u8 [D][H][W] on the device; one plane,
+// the set { masks == value }, per call pair.  Every output position comes from a scan: nothing depends on the order in which atomics
+// arrive (the three per-axis counts are integer sums).
+//   launch_volume_mesh_count: classify (one lane per voxel: its 6-bit exposure mask into the workspace, the workgroup's quad count, the
+//       per-axis counts), corners (one lane per grid corner: its eight memberships -> n and o packed as the vertex's last four bytes,
+//       0 = no vertex, into the corner map; the workgroup's vertex count), then the exclusive scan of both count arrays (1024 counts per
+//       workgroup, the workgroups' sums scanned the same way one level up, added back) and counts u64 [5] = quads, verts, quads_x, _y, _z.
+//   launch_volume_mesh_emit (after the host has read the counts): corners write their vertex at scan base + rank in the workgroup and
+//       replace their map entry by that index; voxels write their quads at scan base + rank, the four indices looked up in the map.
+//       Entries at keep_verts / keep_quads and beyond are dropped (the map is complete whatever keep_verts is); verts / quads may be
+//       null when their keep is 0.
+// Workspace: volume_mesh_workspace_bytes(D, H, W), not zeroed by the caller.  6 * (D + 1) * (H + 1) * (W + 1) < 2^31.
+constexpr int VOLUME_MESH_FACES = 0, VOLUME_MESH_NETS = 1;  // = MI_UNET_MESH_FACES, _NETS
+struct VolumeMeshArgs { int D = 0, H = 0, W = 0, value = 0, placement = 0; };
+size_t volume_mesh_workspace_bytes(int D, int H, int W);
+hipError_t launch_volume_mesh_count(const uint8_t *masks, const VolumeMeshArgs &a, unsigned long long *counts, void *ws, hipStream_t s);
+hipError_t launch_volume_mesh_emit(const VolumeMeshArgs &a, void *ws, ::mi_unet_mesh_vertex *verts, int keep_verts, int32_t *quads,
+                                   int keep_quads, hipStream_t s);
 
 }  // namespace miunet

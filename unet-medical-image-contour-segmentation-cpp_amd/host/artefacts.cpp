@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstring>
 #include <fstream>
 #include <future>
 #include <stdexcept>
@@ -103,6 +105,36 @@ void write_volume_artefacts(const VolumeArtefacts &a)
             if (!medseg::write_png(a.output_dir + "/" + (*a.bases)[z] + name, m, /*level0=*/true))
                 throw std::runtime_error("Failed to save volume mask");
         }
+}
+
+void write_volume_mesh(const VolumeMeshArtefact &a)
+{
+    static_assert(sizeof(float) == 4, "binary STL holds IEEE single floats");
+    std::string buf(84 + a.nq * 2 * 50, '\0');
+    const char title[] = "medseg volume mesh";
+    std::copy(title, title + sizeof(title) - 1, buf.begin());
+    const uint32_t triangles = (uint32_t)(a.nq * 2);
+    std::memcpy(&buf[80], &triangles, 4);
+    char *at = &buf[84];
+    for (size_t q = 0; q < a.nq; ++q)
+        for (int t = 0; t < 2; ++t) {
+            const float *const p[3] = { a.xyz + 3 * (size_t)a.quads[4 * q], a.xyz + 3 * (size_t)a.quads[4 * q + 1 + t],
+                                        a.xyz + 3 * (size_t)a.quads[4 * q + 2 + t] };
+            const double u[3] = { (double)p[1][0] - p[0][0], (double)p[1][1] - p[0][1], (double)p[1][2] - p[0][2] };
+            const double w[3] = { (double)p[2][0] - p[0][0], (double)p[2][1] - p[0][1], (double)p[2][2] - p[0][2] };
+            const double n[3] = { u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0] };
+            const double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            float rec[12];
+            for (int c = 0; c < 3; ++c) rec[c] = len > 0.0 ? (float)(n[c] / len) : 0.f;
+            for (int v = 0; v < 3; ++v)
+                for (int c = 0; c < 3; ++c) rec[3 + 3 * v + c] = p[v][c];
+            std::memcpy(at, rec, 48);                           // (the two attribute bytes behind it stay 0)
+            at += 50;
+        }
+    std::ofstream o(a.output_dir + "/" + a.file, std::ios::binary);
+    o.write(buf.data(), (std::streamsize)buf.size());
+    o.close();
+    if (!o) throw std::runtime_error("Failed to save volume mesh");
 }
 
 void write_volume_score(const std::string &output_dir, const std::string &score)

@@ -54,6 +54,19 @@ struct VolumeArtefacts {
 };
 void write_volume_artefacts(const VolumeArtefacts &a);
 
+// The border of one target's labelled stack (MedicalSeg::set_volume_mesh) as binary STL, <output_dir>/<file>: `xyz` are the nv vertex
+// positions in millimetres (mi_unet_volume_mesh_positions), `quads` the nq quads over them; every quad gives the triangles (0, 1, 2)
+// and (0, 2, 3).  An 80-byte header that starts "medseg volume mesh" and is padded with zeros, the triangle count as uint32, then per
+// triangle the unit normal of the float positions -- computed in double, rounded to float; 0, 0, 0 for a zero cross product --, the three
+// vertices and an attribute of 0, all little-endian.  Throws std::runtime_error("Failed to save volume mesh").
+struct VolumeMeshArtefact {
+    std::string output_dir, file;
+    const float *xyz = nullptr;
+    const int32_t *quads = nullptr;
+    size_t nv = 0, nq = 0;
+};
+void write_volume_mesh(const VolumeMeshArtefact &a);
+
 // The scores of a batch as one volume against ground truth (MedicalSeg::set_volume with set_truth_dir): <output_dir>/volume_score.json
 // with the text `score`.  Throws std::runtime_error("Failed to save volume score").
 void write_volume_score(const std::string &output_dir, const std::string &score);

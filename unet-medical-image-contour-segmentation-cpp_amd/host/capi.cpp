@@ -194,6 +194,12 @@ void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_
     const MedicalSeg::VolumeClean c = MedicalSeg::get_volume_clean();
     *on = c.on; *fill = c.fill; *close_mm = c.close_mm; *open_mm = c.open_mm;
 }
+int medseg_set_volume_mesh(int on, int placement) { return MedicalSeg::set_volume_mesh({ on != 0, placement }) ? 0 : 1; }
+void medseg_get_volume_mesh(int *on, int *placement)
+{
+    const MedicalSeg::VolumeMesh m = MedicalSeg::get_volume_mesh();
+    *on = m.on; *placement = m.placement;
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

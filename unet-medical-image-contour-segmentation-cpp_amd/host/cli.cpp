@@ -148,6 +148,7 @@ public:
         table_["truth"] = [this](const Words &w) { cmd_truth(w); return true; };
         table_["volume"] = [this](const Words &w) { cmd_volume(w); return true; };
         table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
+        table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -167,6 +168,7 @@ public:
             "  truth <dir>|off               - Score every mask against <dir>/<base>_labels.raw into <base>_score.json (default: off)",
             "  volume on [6|18|26] [min N] [keep N] [spacing sx sy sz]|off - Label the slices of a directory as one volume into volume_report.json",
             "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
+            "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -418,6 +420,30 @@ private:
         const MedicalSeg::VolumeClean cur = MedicalSeg::get_volume_clean();
         std::cout << "Volume clean: " << (cur.on ? "on" : "off") << " " << (cur.fill ? "fill" : "nofill") << " close " << cur.close_mm << " open "
                   << cur.open_mm << std::endl;
+    }
+
+    // volmesh on [faces|nets] | volmesh off | volmesh (prints the setting in force)
+    void cmd_volmesh(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeMesh m;
+            bool ok = (w[1] == "off" && w.size() == 2) || (w[1] == "on" && w.size() <= 3);
+            m.on = w[1] == "on";
+            if (ok && w.size() == 3) {
+                ok = w[2] == "faces" || w[2] == "nets";
+                m.placement = w[2] == "nets" ? MI_UNET_MESH_NETS : MI_UNET_MESH_FACES;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volmesh command (expected on [faces|nets] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_mesh(m)) {
+                std::cerr << "Volume mesh unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeMesh cur = MedicalSeg::get_volume_mesh();
+        std::cout << "Volume mesh: " << (cur.on ? "on" : "off") << " " << (cur.placement == MI_UNET_MESH_NETS ? "nets" : "faces") << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

@@ -336,6 +336,20 @@ bool set_volume_clean(const VolumeClean &clean)
         /*handle_side=*/false);
 }
 
+bool set_volume_mesh(const VolumeMesh &mesh)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_mesh = mesh;
+            const bool placement = mesh.placement == MI_UNET_MESH_FACES || mesh.placement == MI_UNET_MESH_NETS;
+            return std::string(placement ? "" : "volume mesh: the placement is MI_UNET_MESH_FACES or MI_UNET_MESH_NETS");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume mesh: " << (mesh.on ? "on" : "off") << ", " << (mesh.placement == MI_UNET_MESH_NETS ? "nets" : "faces");
+        },
+        /*handle_side=*/false);
+}
+
 Settings current_settings()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -353,6 +367,7 @@ mi_unet_measure get_measure() { return current_settings().measure; }
 std::string get_truth_dir() { return current_settings().truth_dir; }
 Volume get_volume() { return current_settings().volume; }
 VolumeClean get_volume_clean() { return current_settings().volume_clean; }
+VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }

@@ -582,13 +582,71 @@ bool clean_volume(VolumeStack &st, const std::vector<mi_unet_target> &targets, c
     }
 }
 
+// set_volume_mesh: every target's plane of `planes` ([K][D][H][W], the stack label_volume labelled) through mi_unet_volume_mesh with
+// values = { 255 } on `h` (mi_unet_volume_mesh_host under MEDSEG_HOST_POSTPROCESS=1) -- a counting call, then one sized by its counts --
+// then the positions and metrics under the volume setting's spacing and the STL file of every target that has quads.  Returns the
+// "mesh" member of volume_report.json, from its leading comma on.  A failure is reported and returns an empty text: only this step ends.
+std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeMesh &mesh,
+                        mi_unet_t *h, const std::string &output_dir, std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size();
+        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
+        const int value = 255;
+        const bool device = h && device_postprocess_requested();
+        const char *const placement = mesh.placement == MI_UNET_MESH_NETS ? "nets" : "faces";
+        std::ostringstream js;
+        js << ",\n  \"mesh\": {\"placement\": \"" << placement << "\", \"targets\": [";
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const uint8_t *const in = planes + t * D * hw;
+            auto call = [&](mi_unet_mesh_vertex *verts, int cap_verts, int32_t *quads, int cap_quads, mi_unet_mesh_stat *st) {
+                const int rc = device ? mi_unet_volume_mesh(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, mesh.placement, verts, cap_verts, quads,
+                                                            cap_quads, st)
+                                      : mi_unet_volume_mesh_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, mesh.placement, verts, cap_verts,
+                                                                 quads, cap_quads, st);
+                if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            };
+            mi_unet_mesh_stat st{};
+            call(nullptr, 0, nullptr, 0, &st);
+            std::vector<mi_unet_mesh_vertex> verts((size_t)st.verts);
+            std::vector<int32_t> quads((size_t)st.quads * 4);
+            if (st.quads > 0) call(verts.data(), (int)st.verts, quads.data(), (int)st.quads, &st);
+            mi_unet_mesh_metrics m{};
+            if (mi_unet_volume_mesh_derive(verts.data(), (int)verts.size(), quads.data(), (int)st.quads, spacing, &m) != MI_UNET_OK)
+                throw std::runtime_error(mi_unet_last_error());
+            std::string file;
+            if (st.quads > 0) {
+                std::vector<float> xyz(verts.size() * 3);
+                if (mi_unet_volume_mesh_positions(verts.data(), (int)verts.size(), spacing, xyz.data()) != MI_UNET_OK)
+                    throw std::runtime_error(mi_unet_last_error());
+                file = is_default(targets) ? "volume_mesh.stl" : "volume_mesh_class" + std::to_string(targets[t].cls) + ".stl";
+                VolumeMeshArtefact a;
+                a.output_dir = output_dir; a.file = file; a.xyz = xyz.data(); a.quads = quads.data(); a.nv = verts.size(); a.nq = (size_t)st.quads;
+                write_volume_mesh(a);
+            }
+            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"quads\": " << st.quads << ", \"verts\": " << st.verts
+               << ", \"area_mm2\": " << json_number(m.area_mm2) << ", \"volume_mm3\": " << json_number(m.volume_mm3) << ", \"file\": "
+               << (file.empty() ? std::string("null") : "\"" + file + "\"") << "}";
+        }
+        js << "\n  ]}";
+        lg << "Volume mesh: " << D << " slices, " << K << " targets, " << placement << ", " << ms_since(t0) << " ms" << std::endl;
+        return js.str();
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume mesh error: ") + e.what());
+        return std::string();
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
 // A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
-// is active (without one they are the cleaned stack itself).
+// is active (without one they are the cleaned stack itself).  With `mesh` on, the planes that were labelled -- `out` under a filter, else
+// the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
-                  std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string())
+                  std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string(),
+                  const VolumeMesh &mesh = VolumeMesh())
 {
     filtered.clear();
     try {
@@ -611,6 +669,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
             if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
         }
         lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
+        const std::string mesh_json = mesh.on ? mesh_volume(filter ? out.data() : st.planes.data(), D, hw, targets, v, mesh, h, output_dir, lg) : std::string();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -645,7 +704,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
             }
             js << (rows ? "\n    " : "") << "]}";
         }
-        js << "\n  ]\n}\n";
+        js << "\n  ]" << mesh_json << "\n}\n";
         VolumeArtefacts a;
         a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
         a.height = g_cfg.height; a.width = g_cfg.width;
@@ -847,7 +906,8 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             if (settings.volume_clean.on &&
                 !clean_volume(stack, settings.targets, settings.volume, settings.volume_clean, mi_unet_group_handle(group, 0), lg.text, clean_json))
                 return ok;
-            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json);
+            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json,
+                         settings.volume_mesh);
             if (!settings.truth_dir.empty())
                 score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
                                    lg.text);

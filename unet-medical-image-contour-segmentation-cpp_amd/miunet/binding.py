@@ -37,6 +37,7 @@ EXPORTS = [
     "mi_unet_volume_components", "mi_unet_volume_components_host", "mi_unet_volume_derive",
     "mi_unet_score_volume", "mi_unet_score_volume_host", "mi_unet_score_volume_units", "mi_unet_score_volume_derive",
     "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
+    "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
 ]
 
 
@@ -251,6 +252,55 @@ def _volume_clean_call(fn, head, masks, values, units, fill, close_r, open_r):
     return out, stats
 
 
+class MeshVertex(C.Structure):
+    """mi_unet_mesh_vertex: 16 bytes, three int32, three int8, one uint8; MESH_VERTEX_DTYPE is the same layout for numpy"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("ox", C.c_int8), ("oy", C.c_int8), ("oz", C.c_int8), ("n", C.c_uint8)]
+
+
+class MeshStat(C.Structure):
+    """mi_unet_mesh_stat: 48 bytes, two int32 then five int64; MESH_STAT_DTYPE is the same layout for numpy"""
+    _fields_ = [("value", C.c_int32), ("placement", C.c_int32), ("quads", C.c_int64), ("verts", C.c_int64), ("quads_x", C.c_int64),
+                ("quads_y", C.c_int64), ("quads_z", C.c_int64)]
+
+
+class MeshMetrics(C.Structure):
+    _fields_ = [("area_mm2", C.c_double), ("volume_mm3", C.c_double)]
+
+
+MESH_VERTEX_DTYPE = np.dtype([(n, {C.c_int32: np.int32, C.c_int8: np.int8, C.c_uint8: np.uint8}[t]) for n, t in MeshVertex._fields_])
+MESH_STAT_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in MeshStat._fields_])
+MESH_PLACEMENTS = {"faces": 0, "nets": 1}
+
+
+def _volume_mesh_call(fn, head, masks, values, placement, cap, raw=False):
+    """mi_unet_volume_mesh (head = (handle,)) or its host form (head = ()): masks u8 [D,H,W] (or [H,W]: one slice), placement by name
+    (MESH_PLACEMENTS) or as the raw C value, cap = None (a counting call, then one sized by the largest counts), one int for both caps
+    or (cap_verts, cap_quads) -> ([(verts MESH_VERTEX_DTYPE [V], quads int32 [Q, 4]) per value], stats MESH_STAT_DTYPE [n]), the
+    arrays trimmed to min(count, cap); raw=True returns the untrimmed (verts [n, cap_verts], quads [n, cap_quads, 4], stats).  The
+    library checks the values."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    if masks.ndim != 3:
+        raise ValueError(f"masks {masks.shape} must be one u8 [D,H,W] array")
+    d, hh, ww = masks.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    n = max(vals.size, 1)
+    pl = MESH_PLACEMENTS[placement] if isinstance(placement, str) else int(placement)
+    stats = np.zeros(n, MESH_STAT_DTYPE)
+    if cap is None:
+        _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, pl, None, 0, None, 0, _ptr(stats)))
+        cap = (int(stats["verts"].max()), int(stats["quads"].max()))
+    cap_v, cap_q = (int(cap), int(cap)) if np.isscalar(cap) else (int(cap[0]), int(cap[1]))
+    verts = np.zeros((n, max(cap_v, 0)), MESH_VERTEX_DTYPE)
+    quads = np.zeros((n, max(cap_q, 0), 4), np.int32)
+    _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, pl, _ptr(verts) if cap_v else None, cap_v, _ptr(quads) if cap_q else None,
+              cap_q, _ptr(stats)))
+    if raw:
+        return verts, quads, stats
+    return [(verts[k, :min(int(stats[k]["verts"]), cap_v)].copy(), quads[k, :min(int(stats[k]["quads"]), cap_q)].copy()) for k in range(n)], stats
+
+
 def _last_regions(fn, handle):
     """(regions REGION_DTYPE [planes, cap_contours], counts int32 [planes]) of mi_unet_last_regions or its group form"""
     planes, cap = C.c_int(), C.c_int()
@@ -424,6 +474,11 @@ def lib():
                                                 C.c_void_p, C.c_void_p]
         L.mi_unet_volume_clean.argtypes = [C.c_void_p] + L.mi_unet_volume_clean_host.argtypes
         L.mi_unet_volume_ball.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_mesh_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_void_p]
+        L.mi_unet_volume_mesh.argtypes = [C.c_void_p] + L.mi_unet_volume_mesh_host.argtypes
+        L.mi_unet_volume_mesh_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_mesh_derive.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MeshMetrics)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -817,6 +872,13 @@ class Engine:
         radii in the same unit -> (out u8 [n,D,H,W], stats VCLEAN_DTYPE [n])"""
         return _volume_clean_call(lib().mi_unet_volume_clean, (self._h,), masks, values, units, fill, close_r, open_r)
 
+    # ---- the border of a stack as a quad mesh (mi_unet_volume_mesh): needs the device, not the weights
+    def volume_mesh(self, masks, values, placement="faces", cap=None, raw=False):
+        """masks u8 [D,H,W] of any size, values = the bytes whose sets are meshed, placement "faces" or "nets" -> ([(verts
+        MESH_VERTEX_DTYPE [V], quads int32 [Q, 4]) per value], stats MESH_STAT_DTYPE [n]).  cap=None makes a counting call, then a sized
+        one; cap = an int or (cap_verts, cap_quads) makes one call and trims to min(count, cap); raw=True returns the untrimmed arrays"""
+        return _volume_mesh_call(lib().mi_unet_volume_mesh, (self._h,), masks, values, placement, cap, raw)
+
     # ---- scores of a stack as one volume (mi_unet_score_volume): needs the device, not the weights
     def score_volume(self, pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
         """pred, truth u8 [D,H,W] of any size, values = the bytes to compare, spacing_units = (ux, uy, uz) positive integers ->
@@ -948,6 +1010,38 @@ def volume_components_host(masks, values, connectivity=26, min_voxels=0, keep_la
 def volume_clean_host(masks, values, units, fill=True, close_r=0, open_r=0):
     """mi_unet_volume_clean_host: Engine.volume_clean as sequential host arithmetic (needs no device)"""
     return _volume_clean_call(lib().mi_unet_volume_clean_host, (), masks, values, units, fill, close_r, open_r)
+
+
+def volume_mesh_host(masks, values, placement="faces", cap=None, raw=False):
+    """mi_unet_volume_mesh_host: Engine.volume_mesh as sequential host arithmetic (needs no device)"""
+    return _volume_mesh_call(lib().mi_unet_volume_mesh_host, (), masks, values, placement, cap, raw)
+
+
+def _spacing3(spacing):
+    sp = np.ascontiguousarray(spacing, np.float64).reshape(-1)
+    if sp.size != 3:
+        raise ValueError("spacing holds three numbers: x, y, z")
+    return sp
+
+
+def volume_mesh_positions(verts, spacing):
+    """mi_unet_volume_mesh_positions: verts MESH_VERTEX_DTYPE [V], spacing (sx, sy, sz) in mm -> float32 [V, 3] (needs no device)"""
+    verts = np.ascontiguousarray(verts, MESH_VERTEX_DTYPE).reshape(-1)
+    sp = _spacing3(spacing)
+    xyz = np.zeros((verts.size, 3), np.float32)
+    _check(lib().mi_unet_volume_mesh_positions(_ptr(verts) if verts.size else None, verts.size, _ptr(sp), _ptr(xyz) if verts.size else None))
+    return xyz
+
+
+def volume_mesh_derive(verts, quads, spacing):
+    """mi_unet_volume_mesh_derive: one plane's mesh and the spacing in mm -> dict(area_mm2, volume_mm3) (needs no device)"""
+    verts = np.ascontiguousarray(verts, MESH_VERTEX_DTYPE).reshape(-1)
+    quads = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+    sp = _spacing3(spacing)
+    m = MeshMetrics()
+    _check(lib().mi_unet_volume_mesh_derive(_ptr(verts) if verts.size else None, verts.size, _ptr(quads) if quads.size else None, quads.shape[0],
+                                            _ptr(sp), C.byref(m)))
+    return dict(area_mm2=m.area_mm2, volume_mm3=m.volume_mm3)
 
 
 def volume_ball(units, r):

@@ -22,7 +22,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
-           "medseg_set_volume_clean", "medseg_get_volume_clean"]
+           "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh"]
 
 
 def lib():
@@ -76,6 +76,9 @@ def lib():
         L.medseg_set_volume_clean.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
         L.medseg_get_volume_clean.argtypes = [_i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.medseg_get_volume_clean.restype = None
+        L.medseg_set_volume_mesh.argtypes = [C.c_int, C.c_int]
+        L.medseg_get_volume_mesh.argtypes = [_i, _i]
+        L.medseg_get_volume_mesh.restype = None
         _LIB = L
     return _LIB
 
@@ -220,6 +223,21 @@ def get_volume_clean():
     on, fill, c, o = C.c_int(), C.c_int(), C.c_double(), C.c_double()
     lib().medseg_get_volume_clean(C.byref(on), C.byref(fill), C.byref(c), C.byref(o))
     return {"on": bool(on.value), "fill": bool(fill.value), "close_mm": c.value, "open_mm": o.value}
+
+
+MESH_PLACEMENTS = {"faces": 0, "nets": 1}
+
+
+def set_volume_mesh(on=True, placement="faces") -> bool:
+    """MedicalSeg::set_volume_mesh: with set_volume on, process_image_batch meshes every target's labelled plane (placement "faces" or
+    "nets", or the raw C value) into volume_mesh*.stl and a "mesh" object in volume_report.json; needs no engine"""
+    return lib().medseg_set_volume_mesh(int(bool(on)), MESH_PLACEMENTS[placement] if isinstance(placement, str) else int(placement)) == 0
+
+
+def get_volume_mesh():
+    on, placement = C.c_int(), C.c_int()
+    lib().medseg_get_volume_mesh(C.byref(on), C.byref(placement))
+    return {"on": bool(on.value), "placement": {v: k for k, v in MESH_PLACEMENTS.items()}[placement.value]}
 
 
 def get_measure():
