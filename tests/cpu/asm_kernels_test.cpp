@@ -5,6 +5,7 @@
 // Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include asm_kernels_test.cpp ../../<pkg>/csrc/{wino4_asm,routing}.cpp
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -265,7 +266,7 @@ void test_argument_blocks()
         CHECK(g.u_pos_bytes == 8192u && g.u_bytes == 1769472u && g.img_in_bytes == 393216u);
         CHECK(g.pix_out_bytes == 256u && g.co_off_bytes == 0u && g.img_out_bytes == 262144u);
         CHECK(g.pix_pool_bytes == 0u && g.img_pool_bytes == 0u);
-        CHECK(g.relu_lo == -3.402823466e+38f && g.grid == 4 && g.flags == 0);                             // 6 workgroups on 4 CUs: persistent
+        CHECK(g.relu_lo == -INFINITY && g.grid == 4 && g.flags == 0);                             // 6 workgroups on 4 CUs: persistent
     }
 }
 

@@ -56,10 +56,13 @@ def lib():
 
 
 def bf16_round(a):
-    """round-to-nearest-even to bfloat16, kept in float32 (numpy mirror of the oracle's bf16_round)"""
+    """round-to-nearest-even to bfloat16, kept in float32 (numpy mirror of the oracle's bf16_round).  NaN stays NaN: the quiet NaN
+    with the sign and the upper payload bits of the input (the integer add below would carry 0x7FFFFFFF into -0.0)"""
     u = np.ascontiguousarray(a, np.float32).view(np.uint32)
-    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32)
-    return r.reshape(np.shape(a))
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = np.where(nan, (u & np.uint32(0xFFFF0000)) | np.uint32(0x00400000), r).astype(np.uint32)
+    return r.view(np.float32).reshape(np.shape(a))
 
 
 def fp16_round(a):

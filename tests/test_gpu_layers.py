@@ -269,7 +269,7 @@ def test_conv3x3_wino4a_assembly_kernel(B, H, W, Cin, Cout, pool):
 
 def test_conv3x3_wino4a_tap_orientation_and_no_relu_exact():
     # the exact-integer construction of test_conv3x3_wino4_tap_orientation_exact on a shape the assembly kernel takes; no ReLU,
-    # so the lower bound of the epilogue's v_max is -FLT_MAX and negative results must come through
+    # so the lower bound of the epilogue's v_max is -inf and negative results must come through
     r = _rng(17)
     B, H, W, Cin, Cout = 2, 32, 16, 64, 128
     x = r.integers(-2, 3, (B, H, W, Cin)).astype(np.float32)

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_lp2(const ConvArgs a, const in
     const __amdgpu_buffer_rsrc_t pool_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         do_pool ? reinterpret_cast<OutT *>(a.pool_out) + (size_t)b * Hp * Wp * a.pool_ld : reinterpret_cast<OutT *>(a.out), 0,
         do_pool ? (int)((size_t)Hp * Wp * a.pool_ld * ES) : 0, 0x00020000);
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     const int yw = y0 + wave * MT;
     const bool interior = x0 + 32 <= a.W && y0 + TH <= a.H;
     float shj[NB];                                // loaded BEFORE the first store (conv3x3_lp2)
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_lp2n(const ConvArgs a, const i
     const __amdgpu_buffer_rsrc_t pool_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         do_pool ? reinterpret_cast<T *>(a.pool_out) + (size_t)b * Hp * Wp * a.pool_ld : reinterpret_cast<T *>(a.out), 0,
         do_pool ? (int)((size_t)Hp * Wp * a.pool_ld * 2) : 0, 0x00020000);
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     const bool interior = x0 + 32 <= a.W && y0 + TH <= a.H;
     float shj[2];
 #pragma unroll

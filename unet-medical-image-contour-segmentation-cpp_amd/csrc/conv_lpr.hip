@@ -196,7 +196,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_lpr(const ConvArgs a, const in
             const int m = lane >> 2, q = lane & 3;           // pooled: row rp, columns 8 (ch0 + mb) + m, lanes 0..31
             pvoff[mb][j] = lane < 32 ? (unsigned)(((rp * Wp + 8 * (ch0 + mb) + m) * a.pool_ld + 32 * (blk0 + j) + 8 * q) * 2) : 0xFFFFFFFFu;
         }
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     // HEAD: head_w[k][c] (classes past head_classes = 0) goes through LDS once.  Read straight from global its address is
     // uniform, so hipcc keeps the 96 values in SGPRs, spills them into VGPR lanes and restores each with a v_readlane per use
     // (149 per tile); read back from LDS they are ordinary per-lane registers.

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_lprk(const ConvArgs a, const i
         const int e = lane + 64 * it, m = e >> 2, q = e & 3;
         ovoff[it] = (unsigned)((((2 * rp + (m >> 4)) * a.W + 16 * kh + (m & 15)) * a.ldo + a.co_off + 32 * blk + 8 * q) * 2);
     }
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
 
     // ---- this workgroup's tiles: its XCD's logical range, walked with a stride (conv_lpr.hip)
     const int G = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
 
     int c_begin = 0, nchunks = all_chunks;    // this workgroup's K range [c_begin, nchunks)
     // SPLITK: raw partial sums into this slice's slab [B][H][W][Cout]; shift, ReLU and pooling belong to the reduce kernel
-    const float relu_lo = (a.relu && !SPLITK) ? 0.f : -3.402823466e+38f;
+    const float relu_lo = (a.relu && !SPLITK) ? 0.f : -__builtin_inff();
     const int Hp = a.H >> 1, Wp = a.W >> 1;
     const bool do_pool = !SPLITK && a.pool_out != nullptr;
     const int ld_e = SPLITK ? a.Cout : a.ldo, co_e = SPLITK ? 0 : a.co_off;

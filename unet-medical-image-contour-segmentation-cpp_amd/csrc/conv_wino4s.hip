@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
     // (Swapping the MFMA operand roles would give every lane four consecutive CHANNELS of one tile and so 16-byte stores,
     // a quarter of the store instructions: measured 2-4 % slower on these layers -- the stores are bound by the 64-byte
     // segments they scatter, not by their count.)
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     const int Hp = a.H >> 1, Wp = a.W >> 1;
     const bool do_pool = a.pool_out != nullptr;
     const unsigned pix_bytes = (unsigned)a.ldo * 4, row_bytes = (unsigned)a.W * pix_bytes;

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void convT2x2_lpr(const ConvArgs a, const i
         const int e = lane + 64 * it, m = e / PIECES, q = e - m * PIECES;
         ovoff[it] = (unsigned)((((dy * OW) + 2 * m + dx) * a.ldo + a.co_off + co0 + 8 * q) * 2);
     }
-    const float relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
 
     const int G = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int slots = (G >> 3) + (xcd < (G & 7) ? 1 : 0);

@@ -132,7 +132,7 @@ hipError_t launch_conv3x3_wino4_asm(const AsmKernels *owner, AsmKernels::Which w
     const bool pool = a.pool_out != nullptr;
     k.pix_pool_bytes = pool ? (uint32_t)a.pool_ld * 4u : 0u;
     k.img_pool_bytes = pool ? (uint32_t)(a.H / 2) * (a.W / 2) * a.pool_ld * 4u : 0u;
-    k.relu_lo = a.relu ? 0.f : -3.402823466e+38f;
+    k.relu_lo = a.relu ? 0.f : -__builtin_inff();
     const int cus = a.rt.cus;
     k.grid = k.nwg < cus ? k.nwg : cus;             // persistent: one workgroup per CU walks its XCD's tiles
     k.flags = pool ? 1 : 0;
