@@ -139,6 +139,26 @@ struct VolumeMesh {
 bool set_volume_mesh(const VolumeMesh &mesh);
 VolumeMesh get_volume_mesh();
 
+// Every component of the labelled stack measured (mi_unet_volume_measure in include/mi_unet.h).  It acts only together
+// with set_volume's `on`: the stack also keeps `channel` of every slice's normalised tile (the bytes of <base>_normalized.png for
+// channel 0) widened to 16 bits, a failed slice all-zero; mi_unet_volume_components hands out its ids, and one mi_unet_volume_measure
+// call per target (mi_unet_volume_measure_host under MEDSEG_HOST_POSTPROCESS=1) measures the components of the report's table under the
+// integer units mi_unet_score_volume_units finds for the volume setting's spacing, with `max_ends` as the cap of the diameter search.
+// Every component object of volume_report.json gains a last member "measure": "diameter_mm", "diameter_ends" (two [x, y, z]),
+// "axial_diameter_mm", "axial_slice" (the slice's reported name), "axial_ends", "axes_mm", "axes_dir", "mean", "std", "min", "max" and
+// "ends"; the four diameter members of a component past the cap are null, and the whole member is null for a component the volume
+// filter dropped (its voxels carry no id).  One log line per batch; a failure is reported as "Volume measure error: ..." and ends only
+// this step: the report is then written without the member.  With it off (the default) every artefact and every log line is what it is
+// without the setting.  Needs no engine and survives initialize_engine.  false, message on stderr, setting unchanged: a negative
+// channel, or max_ends outside 0 .. MI_UNET_VMEASURE_MAX_ENDS_LIMIT.  A channel the engine does not have is reported when a batch runs.
+struct VolumeMeasure {
+    bool on = false;
+    int channel = 0;
+    int max_ends = 262144;
+};
+bool set_volume_measure(const VolumeMeasure &measure);
+VolumeMeasure get_volume_measure();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

@@ -70,6 +70,10 @@ void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_
  * MI_UNET_MESH_FACES or MI_UNET_MESH_NETS.  0 on success; medseg_get_volume_mesh fills the two values. */
 int medseg_set_volume_mesh(int on, int placement);
 void medseg_get_volume_mesh(int *on, int *placement);
+/* Every component of the labelled stack measured: MedicalSeg::set_volume_measure / get_volume_measure (include/medseg/process.h).  0 on
+ * success; medseg_get_volume_measure fills the three values. */
+int medseg_set_volume_measure(int on, int channel, int max_ends);
+void medseg_get_volume_measure(int *on, int *channel, int *max_ends);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

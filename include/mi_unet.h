@@ -679,6 +679,77 @@ int mi_unet_volume_mesh_positions(const mi_unet_mesh_vertex *verts, int nv, cons
 int mi_unet_volume_mesh_derive(const mi_unet_mesh_vertex *verts, int nv, const int32_t *quads /* [nq][4] */, int nq,
                                const double spacing_xyz[3], mi_unet_mesh_metrics *out);
 
+/* ---- Volume measurement: per component of a labelled stack its moments, its intensity and its longest diameters ------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  It is mi_unet_region (7.6) with one
+ * more axis, plus the longest diameter in 3-D and within one slice (the RECIST long axis).  Exact in integers; millimetres enter only
+ * in mi_unet_volume_measure_derive.
+ * Input is ids, int32 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), optionally intensity,
+ * uint16 [D][H][W], the number of components m and the spacing as three positive integers spacing_units = { ux, uy, uz } in a unit the
+ * caller chooses (mi_unet_score_volume_units finds one for a spacing in millimetres).
+ *   COMPONENT  component r, 0 <= r < m, is the set of voxels with ids == r + 1: exactly what mi_unet_volume_components writes into ids.
+ *              Every other value (0, -1, anything above m) belongs to no component.  The stage does not ask whether a set is connected.
+ *              A voxel's index is z * H * W + y * W + x.  An id that no voxel carries gives an all-zero entry.
+ *   SUMS       voxels, sx, sy, sz and sxx, syy, szz, sxy, sxz, syz are taken over the component's integer coordinates; si, sii (the sums
+ *              of v and v * v), imin and imax over intensity.  The four are 0 when intensity is NULL.
+ *   RUN ENDS   a voxel of the component is a run end when its x - 1 or its x + 1 neighbour on the same row is not in the component;
+ *              positions outside the volume are not in it.  ends is their count and is always exact.
+ *   DIAMETER   with d2(p, q) = (dx ux)^2 + (dy uy)^2 + (dz uz)^2 between voxel centres (the distance of mi_unet_score_volume), d2 is the
+ *              maximum over all pairs of voxels of the component, p == q included.  Among the pairs (p <= q by index) that reach the
+ *              maximum, dp, dq are the one with the smallest p, then the smallest q.  One voxel gives 0 with p = q.  a_d2, a_p, a_q
+ *              follow the same rule over the pairs with equal z.
+ *              The result is defined over all voxels, but only run ends can take part in a maximal pair: squared distance is strictly
+ *              convex, so a voxel strictly between two others of the component on a line is strictly nearer to any q than one of the
+ *              two is (DESIGN.md 7.13 has the proof).  Both forms search the run ends only.
+ *   CAP        the search costs ends^2 per component.  A component with ends > max_ends, and every component when max_ends == 0, gets
+ *              -1 in all six diameter fields; everything else in its entry stays valid (an id that no voxel carries is no component: its
+ *              entry stays all-zero).  The cap acts on ends, a defined quantity, so the two forms agree on who is skipped.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE: a coordinate is below 2^13, so sxx < 2^31 * 2^26 = 2^57;
+ *   D * H * W < 2^31: every index and every count is an int;
+ *   m in 1 .. MI_UNET_VOLUME_MAX_TABLE: what mi_unet_volume_components can have numbered;
+ *   every unit >= 1, and ((W - 1) ux)^2 + ((H - 1) uy)^2 + ((D - 1) uz)^2 < 2^31 (the limit of mi_unet_score_volume): every d2 is an
+ *           int32_t and a pre-scaled coordinate an int;
+ *   max_ends in 0 .. MI_UNET_VMEASURE_MAX_ENDS_LIMIT = 2^20: 2^40 pairs, the most one component may cost;
+ *   sii < 2^31 * 65535^2 < 2^63: inside int64_t.
+ * opts == NULL is { 262144 }.
+ * mi_unet_volume_measure takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued and no output written: a null ids,
+ * spacing_units or table; D, H or W outside 1 .. 8192; D * H * W >= 2^31; m outside 1 .. MI_UNET_VOLUME_MAX_TABLE; a unit < 1; the d2
+ * limit; max_ends outside 0 .. 2^20.  A workspace that cannot be allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_measure_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle,
+ * same bytes.
+ * mi_unet_volume_measure_derive is pure host arithmetic in double.  A voxel is a box of s = spacing_units * unit_mm millimetres per axis
+ * and voxel 0 spans 0 .. 1 of the grid.  With A = voxels:
+ *   c*_mm = (sum / A + 0.5) * s of the axis, as mi_unet_volume_derive gives it.
+ *   The central second moments have exact 128-bit integer numerators that are converted once (as mi_unet_region_derive):
+ *   C_ab = (A * s_ab - s_a * s_b) / A^2 * s[a] * s[b], in mm^2, and every diagonal gains s[a]^2 / 12 because a voxel is a box.
+ *   The eigenvalues of C come from a cyclic Jacobi solver with a fixed number of sweeps (16; no library), descending:
+ *   axis_mm[i] = 2 sqrt(5 lambda_i), the full axes of the solid ellipsoid with these moments (one voxel gives 1.291 s per axis);
+ *   axis_dir[i] is the unit eigenvector (x, y, z), its sign chosen so that its component of largest magnitude is positive.
+ *   mean = si / A and std = sqrt((A * sii - si^2) / A^2).
+ *   diameter_mm = sqrt(d2) * unit_mm and axial_diameter_mm = sqrt(a_d2) * unit_mm; NaN when the field is -1.
+ * MI_UNET_EARG, output untouched: a null pointer, voxels < 1, a unit < 1, or a unit_mm that is not finite and > 0.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VMEASURE_MAX_ENDS_LIMIT 1048576   /* 2^20 */
+typedef struct mi_unet_vmeasure {      /* 128 bytes, no padding */
+    int32_t voxels, ends;              /* voxels with this id; its run ends */
+    int32_t imin, imax;                /* min / max of intensity over the component; 0, 0 without intensity */
+    int32_t d2, dp, dq;                /* longest diameter: squared, in units^2, and the voxel indices of its ends */
+    int32_t a_d2, a_p, a_q;            /* the same restricted to pairs in one slice (dz == 0) */
+    int64_t sx, sy, sz;                /* sums of x, y, z over the component */
+    int64_t sxx, syy, szz, sxy, sxz, syz;
+    int64_t si, sii;                   /* sum v, sum v*v of the intensity */
+} mi_unet_vmeasure;
+typedef struct mi_unet_vmeasure_opts { int max_ends; } mi_unet_vmeasure_opts;     /* default { 262144 } */
+typedef struct mi_unet_vmeasure_shape { double cx_mm, cy_mm, cz_mm, axis_mm[3], axis_dir[3][3], mean, std, diameter_mm, axial_diameter_mm; } mi_unet_vmeasure_shape;
+int mi_unet_volume_measure(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const uint16_t *intensity /* [D][H][W] host or NULL */,
+                           int D, int H, int W, int m, const int spacing_units[3], const mi_unet_vmeasure_opts *opts,
+                           mi_unet_vmeasure *table /* [m] */);
+int mi_unet_volume_measure_host(const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const int spacing_units[3],
+                                const mi_unet_vmeasure_opts *opts, mi_unet_vmeasure *table);
+int mi_unet_volume_measure_derive(const mi_unet_vmeasure *c, const int spacing_units[3], double unit_mm, mi_unet_vmeasure_shape *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

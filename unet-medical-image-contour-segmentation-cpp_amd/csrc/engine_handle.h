@@ -160,6 +160,12 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_vmesh, d_vmesh_out;
     miunet::PinnedBuf<uint8_t> h_vmesh, h_vmesh_out;
     size_t vmesh_dev_cap = 0, vmesh_host_cap = 0, vmesh_out_dev_cap = 0, vmesh_out_host_cap = 0;    // bytes
+    // mi_unet_volume_measure: d_vms = ids, intensity, the table and the per-component arrays of one call; h_vms = their
+    // pinned staging; d_vms_pts = the run ends of the searched components and the work list of the pair search, sized once the ends are
+    // counted; h_vms_pts = the work list's staging; grown on demand, never shared with a clone
+    miunet::DeviceBuf<uint8_t> d_vms, d_vms_pts;
+    miunet::PinnedBuf<uint8_t> h_vms, h_vms_pts;
+    size_t vms_dev_cap = 0, vms_host_cap = 0, vms_pts_dev_cap = 0, vms_pts_host_cap = 0;            // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

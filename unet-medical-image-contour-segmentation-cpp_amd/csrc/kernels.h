@@ -13,6 +13,7 @@ struct mi_unet_region;      // include/mi_unet.h
 struct mi_unet_score;
 struct mi_unet_vcomp;
 struct mi_unet_mesh_vertex;
+struct mi_unet_vmeasure;
 
 namespace miunet {
 
@@ -387,5 +388,31 @@ size_t volume_mesh_workspace_bytes(int D, int H, int W);
 hipError_t launch_volume_mesh_count(const uint8_t *masks, const VolumeMeshArgs &a, unsigned long long *counts, void *ws, hipStream_t s);
 hipError_t launch_volume_mesh_emit(const VolumeMeshArgs &a, void *ws, ::mi_unet_mesh_vertex *verts, int keep_verts, int32_t *quads,
                                    int keep_quads, hipStream_t s);
+
+// Volume measurement (volume_measure.hip; include/mi_unet.h: mi_unet_volume_measure).  ids int32 [D][H][W] and intensity
+// u16 [D][H][W] (or null) on the device; component r = { ids == r + 1 }, 0 <= r < m.  Every result is an integer sum, minimum or maximum:
+// nothing depends on the order in which atomics arrive.  No workgroup waits for another.
+//   launch_volume_measure_sums: zeroes table [m] and fills voxels, ends, the nine coordinate sums, si, sii, imax; imin holds
+//       65535 - the minimum (0 = no voxel), which the caller turns round; the six diameter fields stay 0.
+//   launch_volume_measure_fill (after the host has read `ends` and laid out the segments): seg[r] = (first point, points) of component r,
+//       (0, 0) for one that is not searched; cursor [m] and keys [m][2] are zeroed here; every run end of a searched component goes into
+//       its segment as (x ux, y uy, z uz, index), in any order.
+//   launch_volume_measure_pairs: items[i] = (component, a-tile, first b-tile, b-tiles), tiles of VMS_TILE points of the component's
+//       segment, a-tile <= first b-tile; a workgroup per item holds its a-tile a point per lane, takes the b-tiles through LDS and raises
+//       keys[r][0] (all pairs) and keys[r][1] (pairs with equal z) to (d2 << 31) | (2^31 - 1 - the pair's smaller index).  The caller
+//       bounds the pairs of one launch (volume_measure_item_pairs).
+//   launch_volume_measure_ends: a workgroup per component: the smallest partner index of the winning (d2, p) of both keys ->
+//       diam[r] = (d2, dp, dq, a_d2, a_p, a_q); untouched for a component that is not searched.
+constexpr int VMS_TILE = 256;
+struct VolumeMeasureArgs { int D = 0, H = 0, W = 0, m = 0, ux = 1, uy = 1, uz = 1; };
+struct VmsItem { int comp, a_tile, b_first, b_tiles; };
+hipError_t launch_volume_measure_sums(const int32_t *ids, const uint16_t *intensity, const VolumeMeasureArgs &a, ::mi_unet_vmeasure *table,
+                                      hipStream_t s);
+hipError_t launch_volume_measure_fill(const int32_t *ids, const VolumeMeasureArgs &a, const int2 *seg, int *cursor, unsigned long long *keys,
+                                      int4 *points, hipStream_t s);
+hipError_t launch_volume_measure_pairs(const int4 *points, const int2 *seg, const VmsItem *items, int n_items, unsigned long long *keys,
+                                       hipStream_t s);
+hipError_t launch_volume_measure_ends(const int4 *points, const int2 *seg, const unsigned long long *keys, const VolumeMeasureArgs &a,
+                                      int32_t *diam, hipStream_t s);
 
 }  // namespace miunet

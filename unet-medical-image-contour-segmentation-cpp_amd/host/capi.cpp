@@ -200,6 +200,12 @@ void medseg_get_volume_mesh(int *on, int *placement)
     const MedicalSeg::VolumeMesh m = MedicalSeg::get_volume_mesh();
     *on = m.on; *placement = m.placement;
 }
+int medseg_set_volume_measure(int on, int channel, int max_ends) { return MedicalSeg::set_volume_measure({ on != 0, channel, max_ends }) ? 0 : 1; }
+void medseg_get_volume_measure(int *on, int *channel, int *max_ends)
+{
+    const MedicalSeg::VolumeMeasure m = MedicalSeg::get_volume_measure();
+    *on = m.on; *channel = m.channel; *max_ends = m.max_ends;
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

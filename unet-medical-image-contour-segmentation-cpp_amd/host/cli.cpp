@@ -149,6 +149,7 @@ public:
         table_["volume"] = [this](const Words &w) { cmd_volume(w); return true; };
         table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
         table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
+        table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -169,6 +170,7 @@ public:
             "  volume on [6|18|26] [min N] [keep N] [spacing sx sy sz]|off - Label the slices of a directory as one volume into volume_report.json",
             "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
             "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
+            "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -444,6 +446,31 @@ private:
         }
         const MedicalSeg::VolumeMesh cur = MedicalSeg::get_volume_mesh();
         std::cout << "Volume mesh: " << (cur.on ? "on" : "off") << " " << (cur.placement == MI_UNET_MESH_NETS ? "nets" : "faces") << std::endl;
+    }
+
+    // volmeasure on [channel N] [ends N] | volmeasure off | volmeasure (prints the setting in force)
+    void cmd_volmeasure(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeMeasure m;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            m.on = w[1] == "on";
+            for (size_t i = 2; ok && i < w.size(); i += 2) {
+                int value = 0;
+                ok = i + 1 < w.size() && (w[i] == "channel" || w[i] == "ends") && to_int(w[i + 1], value);
+                (w[i] == "channel" ? m.channel : m.max_ends) = value;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volmeasure command (expected on [channel N] [ends N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_measure(m)) {
+                std::cerr << "Volume measure unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeMeasure cur = MedicalSeg::get_volume_measure();
+        std::cout << "Volume measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " ends " << cur.max_ends << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

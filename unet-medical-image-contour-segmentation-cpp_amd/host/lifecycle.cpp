@@ -350,6 +350,21 @@ bool set_volume_mesh(const VolumeMesh &mesh)
         /*handle_side=*/false);
 }
 
+bool set_volume_measure(const VolumeMeasure &measure)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_measure = measure;
+            if (measure.channel < 0) return std::string("volume measure: the channel is not negative");
+            const bool cap = measure.max_ends >= 0 && measure.max_ends <= MI_UNET_VMEASURE_MAX_ENDS_LIMIT;
+            return std::string(cap ? "" : "volume measure: max_ends is 0 .. MI_UNET_VMEASURE_MAX_ENDS_LIMIT");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume measure: " << (measure.on ? "on" : "off") << ", channel " << measure.channel << ", ends " << measure.max_ends;
+        },
+        /*handle_side=*/false);
+}
+
 Settings current_settings()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -368,6 +383,7 @@ std::string get_truth_dir() { return current_settings().truth_dir; }
 Volume get_volume() { return current_settings().volume; }
 VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
+VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }

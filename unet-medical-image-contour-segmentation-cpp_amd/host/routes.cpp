@@ -517,16 +517,25 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
 // ---- set_volume: the images of a batch as the slices of one volume.  process_images_targets fills the stack as its images finish;
 // label_volume runs once, behind the last device call of the batch.
 struct VolumeStack {
-    VolumeStack(size_t slices, size_t targets, size_t hw) : planes(targets * slices * hw, 0), bases(slices), names(slices), D(slices), hw(hw) {}
-    // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t
-    void add(size_t i, const std::string &base, const uint8_t *pictures, size_t K)
+    // channel >= 0 (set_volume_measure): the stack also keeps that channel of every slice's normalised tile
+    VolumeStack(size_t slices, size_t targets, size_t hw, int channel = -1)
+        : planes(targets * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0), bases(slices), names(slices), D(slices), hw(hw), channel(channel)
+    {
+    }
+    // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t; `tile` is its normalised
+    // tile, [H][W][C]
+    void add(size_t i, const std::string &base, const uint8_t *pictures, size_t K, const uint8_t *tile, size_t C)
     {
         for (size_t t = 0; t < K; ++t) std::copy(pictures + t * hw, pictures + (t + 1) * hw, planes.begin() + (t * D + i) * hw);
+        if (channel >= 0 && (size_t)channel < C)
+            for (size_t p = 0; p < hw; ++p) intensity[i * hw + p] = tile[p * C + (size_t)channel];
         bases[i] = base;
     }
     std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
+    std::vector<uint16_t> intensity;                   // [D][H][W] or empty: the measured channel of the normalised tiles, widened
     std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
     size_t D, hw;
+    int channel;
 };
 
 // set_volume_clean: every target's plane of the stack through one mi_unet_volume_clean call with values = { 255 } on `h`
@@ -638,15 +647,81 @@ std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, const std::v
     }
 }
 
+// set_volume_measure: per target one mi_unet_volume_measure call on `h` (mi_unet_volume_measure_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's intensity, with m = min(found, cap) and the integer units of
+// mi_unet_score_volume_units for the volume setting's spacing.  Returns, per target and table row, the "measure" member of the row's
+// component object in volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
+std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
+                                                     size_t cap, const std::vector<mi_unet_target> &targets, const Volume &v,
+                                                     const VolumeMeasure &measure, mi_unet_t *h, std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size(), D = st.D, hw = st.hw;
+        const int W = g_cfg.width;
+        if (measure.channel >= g_cfg.in_ch)
+            throw std::runtime_error("channel " + std::to_string(measure.channel) + " of " + std::to_string(g_cfg.in_ch));
+        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
+        int units[3] = { 0, 0, 0 };
+        double unit_mm = 0.0;
+        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
+            throw std::runtime_error(mi_unet_last_error());
+        const mi_unet_vmeasure_opts opts{ measure.max_ends };
+        const bool device = h && device_postprocess_requested();
+        std::vector<std::vector<std::string>> members(K);
+        auto point = [&](int32_t idx) {
+            const size_t p = (size_t)idx % hw;
+            return "[" + std::to_string(p % (size_t)W) + ", " + std::to_string(p / (size_t)W) + ", " + std::to_string((size_t)idx / hw) + "]";
+        };
+        auto ends = [&](int32_t p, int32_t q) { return "[" + point(p) + ", " + point(q) + "]"; };
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const int m = (int)std::min<size_t>((size_t)found[t], cap);
+            if (m < 1) continue;
+            std::vector<mi_unet_vmeasure> table((size_t)m);
+            const int32_t *const in = ids.data() + t * D * hw;
+            const int rc = device ? mi_unet_volume_measure(h, in, st.intensity.data(), (int)D, g_cfg.height, g_cfg.width, m, units, &opts, table.data())
+                                  : mi_unet_volume_measure_host(in, st.intensity.data(), (int)D, g_cfg.height, g_cfg.width, m, units, &opts, table.data());
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            for (const mi_unet_vmeasure &c : table) {
+                if (c.voxels < 1) {                             // dropped by the volume filter: its voxels carry no id
+                    members[t].push_back(", \"measure\": null");
+                    continue;
+                }
+                mi_unet_vmeasure_shape s{};
+                if (mi_unet_volume_measure_derive(&c, units, unit_mm, &s) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+                const bool searched = c.d2 >= 0;
+                std::ostringstream js;
+                js << ", \"measure\": {\"diameter_mm\": " << (searched ? json_number(s.diameter_mm) : "null") << ", \"diameter_ends\": "
+                   << (searched ? ends(c.dp, c.dq) : "null") << ", \"axial_diameter_mm\": " << (searched ? json_number(s.axial_diameter_mm) : "null")
+                   << ", \"axial_slice\": " << (searched ? "\"" + medseg::json_escape(st.names[(size_t)c.a_p / hw]) + "\"" : std::string("null"))
+                   << ", \"axial_ends\": " << (searched ? ends(c.a_p, c.a_q) : "null") << ", \"axes_mm\": [" << json_number(s.axis_mm[0]) << ", "
+                   << json_number(s.axis_mm[1]) << ", " << json_number(s.axis_mm[2]) << "], \"axes_dir\": [";
+                for (int i = 0; i < 3; ++i)
+                    js << (i ? ", " : "") << "[" << json_number(s.axis_dir[i][0]) << ", " << json_number(s.axis_dir[i][1]) << ", "
+                       << json_number(s.axis_dir[i][2]) << "]";
+                js << "], \"mean\": " << json_number(s.mean) << ", \"std\": " << json_number(s.std) << ", \"min\": " << c.imin << ", \"max\": "
+                   << c.imax << ", \"ends\": " << c.ends << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume measure: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume measure error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
 // A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
 // is active (without one they are the cleaned stack itself).  With `mesh` on, the planes that were labelled -- `out` under a filter, else
-// the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".
+// the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".  With `measure` on, the components
+// stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member "measure".
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
                   std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string(),
-                  const VolumeMesh &mesh = VolumeMesh())
+                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure())
 {
     filtered.clear();
     try {
@@ -654,7 +729,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K);
+        std::vector<int32_t> found(K), kept(K), ids(measure.on ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const bool device = h && device_postprocess_requested();
@@ -662,14 +737,17 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         for (size_t t = 0; t < K; ++t) {
             const uint8_t *const in = st.planes.data() + t * D * hw;
             uint8_t *const o = filter ? out.data() + t * D * hw : nullptr;
-            const int rc = device ? mi_unet_volume_components(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, nullptr,
+            int32_t *const id = measure.on ? ids.data() + t * D * hw : nullptr;
+            const int rc = device ? mi_unet_volume_components(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
                                                               table.data() + t * cap, (int)cap, &found[t], &kept[t])
-                                  : mi_unet_volume_components_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, nullptr,
+                                  : mi_unet_volume_components_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
                                                                    table.data() + t * cap, (int)cap, &found[t], &kept[t]);
             if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
         }
         lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
         const std::string mesh_json = mesh.on ? mesh_volume(filter ? out.data() : st.planes.data(), D, hw, targets, v, mesh, h, output_dir, lg) : std::string();
+        const std::vector<std::vector<std::string>> measured =
+            measure.on ? measure_volume(st, ids, found, cap, targets, v, measure, h, lg) : std::vector<std::vector<std::string>>();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -700,7 +778,8 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
                    << c.z0 << ", " << c.x1 << ", " << c.y1 << ", " << c.z1 << "], \"centroid_mm\": [" << json_number(m.cx_mm) << ", "
                    << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
-                   << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]}";
+                   << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
+                   << "}";
             }
             js << (rows ? "\n    " : "") << "]}";
         }
@@ -863,7 +942,7 @@ int process_images_targets(const std::vector<std::string> &paths, const std::vec
                 write_image_artefacts(a);
                 if (!ctx) lg << "Processing completed for: " << base_name << std::endl;
                 scored[k] = base_name;
-                if (volume) volume->add(i, base_name, &masks[k * K * hw], K);
+                if (volume) volume->add(i, base_name, &masks[k * K * hw], K, &tiles[k * hw * C], (size_t)C);
                 ++ok;
             } catch (const std::exception &e) {
                 if (ctx) throw;
@@ -898,7 +977,7 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         if (settings.volume.on && n > 0) {                     // the paths are the slices of one volume, whatever the target list is
             std::lock_guard<std::mutex> lk(g_batch_mutex);
             Collected lg{ log_file, {} };
-            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width);
+            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width, settings.volume_measure.on ? settings.volume_measure.channel : -1);
             for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
             ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
             std::vector<uint8_t> filtered;
@@ -907,7 +986,7 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
                 !clean_volume(stack, settings.targets, settings.volume, settings.volume_clean, mi_unet_group_handle(group, 0), lg.text, clean_json))
                 return ok;
             label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json,
-                         settings.volume_mesh);
+                         settings.volume_mesh, settings.volume_measure);
             if (!settings.truth_dir.empty())
                 score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
                                    lg.text);

@@ -38,6 +38,7 @@ EXPORTS = [
     "mi_unet_score_volume", "mi_unet_score_volume_host", "mi_unet_score_volume_units", "mi_unet_score_volume_derive",
     "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
     "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
+    "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
 ]
 
 
@@ -301,6 +302,48 @@ def _volume_mesh_call(fn, head, masks, values, placement, cap, raw=False):
     return [(verts[k, :min(int(stats[k]["verts"]), cap_v)].copy(), quads[k, :min(int(stats[k]["quads"]), cap_q)].copy()) for k in range(n)], stats
 
 
+class VMeasure(C.Structure):
+    """mi_unet_vmeasure: 128 bytes, ten int32 then eleven int64; VMEASURE_DTYPE is the same layout for numpy"""
+    _fields_ = ([(n, C.c_int32) for n in ("voxels", "ends", "imin", "imax", "d2", "dp", "dq", "a_d2", "a_p", "a_q")] +
+                [(n, C.c_int64) for n in ("sx", "sy", "sz", "sxx", "syy", "szz", "sxy", "sxz", "syz", "si", "sii")])
+
+
+class VMeasureOpts(C.Structure):
+    _fields_ = [("max_ends", C.c_int)]
+
+
+class VMeasureShape(C.Structure):
+    _fields_ = [("cx_mm", C.c_double), ("cy_mm", C.c_double), ("cz_mm", C.c_double), ("axis_mm", C.c_double * 3),
+                ("axis_dir", (C.c_double * 3) * 3), ("mean", C.c_double), ("std", C.c_double), ("diameter_mm", C.c_double),
+                ("axial_diameter_mm", C.c_double)]
+
+
+VMEASURE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VMeasure._fields_])
+VMEASURE_MAX_ENDS_LIMIT = 1 << 20
+VMEASURE_DEFAULT_MAX_ENDS = 262144
+
+
+def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
+    """mi_unet_volume_measure (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape or None, m components, units = the spacing (ux, uy, uz) as integers, max_ends = None (the library's default) or the
+    cap -> table VMEASURE_DTYPE [m].  The library checks the values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    if intensity is not None:
+        intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    d, hh, ww = ids.shape
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: ux, uy, uz")
+    table = np.zeros(max(int(m), 1), VMEASURE_DTYPE)
+    opts = None if max_ends is None else C.byref(VMeasureOpts(int(max_ends)))
+    _check(fn(*head, _ptr(ids), _ptr(intensity), d, hh, ww, int(m), _ptr(un), opts, _ptr(table)))
+    return table
+
+
 def _last_regions(fn, handle):
     """(regions REGION_DTYPE [planes, cap_contours], counts int32 [planes]) of mi_unet_last_regions or its group form"""
     planes, cap = C.c_int(), C.c_int()
@@ -479,6 +522,9 @@ def lib():
         L.mi_unet_volume_mesh.argtypes = [C.c_void_p] + L.mi_unet_volume_mesh_host.argtypes
         L.mi_unet_volume_mesh_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_mesh_derive.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MeshMetrics)]
+        L.mi_unet_volume_measure_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_measure.argtypes = [C.c_void_p] + L.mi_unet_volume_measure_host.argtypes
+        L.mi_unet_volume_measure_derive.argtypes = [C.POINTER(VMeasure), C.c_void_p, C.c_double, C.POINTER(VMeasureShape)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -879,6 +925,13 @@ class Engine:
         one; cap = an int or (cap_verts, cap_quads) makes one call and trims to min(count, cap); raw=True returns the untrimmed arrays"""
         return _volume_mesh_call(lib().mi_unet_volume_mesh, (self._h,), masks, values, placement, cap, raw)
 
+    # ---- the components of a labelled stack measured (mi_unet_volume_measure): needs the device, not the weights
+    def volume_measure(self, ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
+        """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W] or None, m = the components
+        to measure (ids 1 .. m), units = the spacing (ux, uy, uz) as integers, max_ends = the cap of the diameter search (None: 262144)
+        -> table VMEASURE_DTYPE [m]"""
+        return _volume_measure_call(lib().mi_unet_volume_measure, (self._h,), ids, intensity, m, units, max_ends)
+
     # ---- scores of a stack as one volume (mi_unet_score_volume): needs the device, not the weights
     def score_volume(self, pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
         """pred, truth u8 [D,H,W] of any size, values = the bytes to compare, spacing_units = (ux, uy, uz) positive integers ->
@@ -1015,6 +1068,24 @@ def volume_clean_host(masks, values, units, fill=True, close_r=0, open_r=0):
 def volume_mesh_host(masks, values, placement="faces", cap=None, raw=False):
     """mi_unet_volume_mesh_host: Engine.volume_mesh as sequential host arithmetic (needs no device)"""
     return _volume_mesh_call(lib().mi_unet_volume_mesh_host, (), masks, values, placement, cap, raw)
+
+
+def volume_measure_host(ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
+    """mi_unet_volume_measure_host: Engine.volume_measure as sequential host arithmetic (needs no device)"""
+    return _volume_measure_call(lib().mi_unet_volume_measure_host, (), ids, intensity, m, units, max_ends)
+
+
+def volume_measure_derive(comp, units, unit_mm):
+    """mi_unet_volume_measure_derive of one component (a VMeasure, or one VMEASURE_DTYPE record) with the spacing units (ux, uy, uz) and
+    the unit in mm -> dict of cx_mm, cy_mm, cz_mm, axis_mm [3], axis_dir [3][3], mean, std, diameter_mm, axial_diameter_mm"""
+    if not isinstance(comp, VMeasure):
+        comp = VMeasure(*[int(comp[n]) for n, _ in VMeasure._fields_])
+    out = VMeasureShape()
+    _check(lib().mi_unet_volume_measure_derive(C.byref(comp), (C.c_int * 3)(*[int(v) for v in units]), float(unit_mm), C.byref(out)))
+    d = {n: getattr(out, n) for n, _ in VMeasureShape._fields_}
+    d["axis_mm"] = [float(v) for v in out.axis_mm]
+    d["axis_dir"] = [[float(v) for v in row] for row in out.axis_dir]
+    return d
 
 
 def _spacing3(spacing):

@@ -22,7 +22,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_window", "medseg_get_window", "medseg_window_of", "medseg_resample_normalize_window",
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
-           "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh"]
+           "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
+           "medseg_set_volume_measure", "medseg_get_volume_measure"]
 
 
 def lib():
@@ -79,6 +80,9 @@ def lib():
         L.medseg_set_volume_mesh.argtypes = [C.c_int, C.c_int]
         L.medseg_get_volume_mesh.argtypes = [_i, _i]
         L.medseg_get_volume_mesh.restype = None
+        L.medseg_set_volume_measure.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.medseg_get_volume_measure.argtypes = [_i, _i, _i]
+        L.medseg_get_volume_measure.restype = None
         _LIB = L
     return _LIB
 
@@ -238,6 +242,18 @@ def get_volume_mesh():
     on, placement = C.c_int(), C.c_int()
     lib().medseg_get_volume_mesh(C.byref(on), C.byref(placement))
     return {"on": bool(on.value), "placement": {v: k for k, v in MESH_PLACEMENTS.items()}[placement.value]}
+
+
+def set_volume_measure(on=True, channel=0, max_ends=262144) -> bool:
+    """MedicalSeg::set_volume_measure: with set_volume on, process_image_batch measures every component of the labelled stack
+    (mi_unet_volume_measure over `channel` of the normalised tiles) into a "measure" member of volume_report.json; needs no engine"""
+    return lib().medseg_set_volume_measure(int(bool(on)), int(channel), int(max_ends)) == 0
+
+
+def get_volume_measure():
+    on, channel, ends = C.c_int(), C.c_int(), C.c_int()
+    lib().medseg_get_volume_measure(C.byref(on), C.byref(channel), C.byref(ends))
+    return {"on": bool(on.value), "channel": channel.value, "max_ends": ends.value}
 
 
 def get_measure():
