@@ -439,9 +439,11 @@ def test_resident_weight_convT_in_the_whole_network(algo, monkeypatch):
 
 @pytest.mark.parametrize("seed", range(12))
 def test_resident_weight_kernels_random_shapes(seed):
-    """Random batch / height / width (odd sizes, tiles past both image edges, tile counts that do not divide by the persistent
-    grid) for every shape the resident-weight kernels take: 3x3 conv, its fused pooling (even sizes) and the transposed conv,
-    each bit-identical to the one-tile-per-workgroup kernel."""
+    """Random batch / height / width (odd sizes, tiles past both image edges, tile counts that are no multiple of 8) for every
+    shape the resident-weight kernels take: 3x3 conv, its fused pooling (even sizes) and the transposed conv, each bit-identical
+    to the one-tile-per-workgroup kernel.  The tile counts stay below the persistent grid (about 100 tiles at the most on 256
+    compute units), so every workgroup takes one tile here: tile counts the grid does not divide are the subject of
+    test_gpu_persistent_walk.py."""
     r = np.random.default_rng(1000 + seed)
     kind = ("conv", "pool", "convT")[seed % 3]
     fp16 = bool(r.integers(0, 2))

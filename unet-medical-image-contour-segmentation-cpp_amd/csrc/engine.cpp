@@ -279,6 +279,7 @@ Routing Routing::from_env()
     hipDeviceProp_t p;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
         r.cus = p.multiProcessorCount;
+    r.cus = persistent_cus(r.cus, getenv("MIUNET_CUS"));      // (tests: a smaller persistent grid, never below one slot per XCD)
     return r;
 }
 

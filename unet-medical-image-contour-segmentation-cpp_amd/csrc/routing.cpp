@@ -22,6 +22,14 @@ std::string route_name(Route r, unsigned fused)
     return n;
 }
 
+int persistent_cus(int device_cus, const char *env_text)
+{
+    const int cus = device_cus < 8 ? 8 : device_cus;
+    if (env_text == nullptr || *env_text == '\0') return cus;
+    const int n = atoi(env_text);
+    return n < 8 ? 8 : n > cus ? cus : n;
+}
+
 // ---- shape contracts
 
 // The shapes the assembly kernel takes: whole 16x16 blocks, an even number (>= 4) of 16-channel K chunks, whole 128-channel

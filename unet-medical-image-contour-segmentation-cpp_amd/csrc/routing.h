@@ -86,6 +86,12 @@ bool first_mfma_takes(const Routing &rt, int Cin, int Cout, int ldo, int H, int 
 struct TapsShape { int mb, nbk, wps; };
 TapsShape convT_taps_shape(const ConvArgs &a);
 
+// Routing::cus from the device's CU count and the text of MIUNET_CUS (nullptr: not set).  The persistent kernels give XCD
+// x = bid & 7 the slots bid >> 3 of a grid of min(tiles, cus) workgroups, so below 8 an XCD that owns tiles would have no slot and
+// its tiles would never be computed: the device's count is floored at 8 (a grid of 8 on fewer CUs is an ordinary launch).
+// MIUNET_CUS=<n> (tests) replaces the count by n clamped to [8, that value]: it only ever lowers the persistent grid.
+int persistent_cus(int device_cus, const char *env_text);
+
 // geometry the predicates share with the kernels (the kernel files take these values)
 constexpr int LP2_TILE_ROWS = 16;                    // conv_lp2.hip LP2::TH
 constexpr int LPRK_TILE_ROWS = 4, LPRK_CIN = 128, LPRK_COUT = 64;   // conv_lprk.hip LPRK
