@@ -159,6 +159,27 @@ struct VolumeMeasure {
 bool set_volume_measure(const VolumeMeasure &measure);
 VolumeMeasure get_volume_measure();
 
+// The scored stack per lesion (mi_unet_volume_match in include/mi_unet.h).  It acts only where set_volume's `on` and
+// set_truth_dir already produce volume_score.json.  Per target the truth stack, recoded by truth == cls, is labelled with
+// mi_unet_volume_components under the volume setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE; the pred ids
+// are the ones the volume report numbers, so a pred index is an index into that target's "components" in volume_report.json (a
+// component the volume filter dropped carries no voxel and counts as absent).  One mi_unet_volume_match call per target
+// (mi_unet_volume_match_host under MEDSEG_HOST_POSTPROCESS=1), then mi_unet_volume_match_assign at iou_num / iou_den and
+// mi_unet_volume_match_derive.  Every target object of volume_score.json gains a last member "lesions": "pred", "truth" (components a
+// side), "iou_threshold" ([num, den]), "tp", "fp", "fn", "precision", "recall", "f1", "pq", "sq", "rq", "mean_dice" (null where
+// undefined), "matches" in pred order ("pred", "truth", "voxels", "iou", "dice", "pred_voxels", "truth_voxels"), "missed" ("truth",
+// "voxels"), "spurious" (pred indices) and, only when a side had more components than the table holds, "truncated": true.  One log line
+// per batch; a failure is reported as "Volume match error: ..." and ends only this step: volume_score.json is then written without the
+// member.  With it off (the default) every artefact and every log line is what it is without the setting.  Needs no engine and
+// survives initialize_engine.  false, message on stderr, setting unchanged: a threshold outside 1 <= iou_num <= iou_den <= 65536.
+struct VolumeMatch {
+    bool on = false;
+    int iou_num = 1;
+    int iou_den = 2;
+};
+bool set_volume_match(const VolumeMatch &match);
+VolumeMatch get_volume_match();
+
 // The device seam (src/process.cpp:123-175): 8-bit tile -> class-index map through mi_unet_infer_u8.
 // Throws std::runtime_error("Inference failed: ...") like the reference.
 medseg::Image8 execute_inference(const medseg::Image8 &gray_img);

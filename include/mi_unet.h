@@ -750,6 +750,74 @@ int mi_unet_volume_measure_host(const int32_t *ids, const uint16_t *intensity, i
                                 const mi_unet_vmeasure_opts *opts, mi_unet_vmeasure *table);
 int mi_unet_volume_measure_derive(const mi_unet_vmeasure *c, const int spacing_units[3], double unit_mm, mi_unet_vmeasure_shape *out);
 
+/* ---- Volume matching: the components of a prediction against the components of a truth, lesion by lesion ----------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  Everything up to
+ * mi_unet_volume_match_derive is an exact integer and independent of the order of evaluation.
+ * Input is pred_ids and truth_ids, both int32 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size),
+ * and the component counts mp and mt.
+ *   COMPONENT  pred component r, 0 <= r < mp, is the set of voxels with pred_ids == r + 1: exactly what mi_unet_volume_components writes
+ *              into ids.  Truth component c, 0 <= c < mt, likewise.  Every other value (0, -1, anything above the side's m) is class 0,
+ *              "no component".  The stage does not ask whether a set is connected.
+ *   TABLE      N[a][b], 0 <= a <= mp, 0 <= b <= mt, is the number of voxels whose pred class is a and whose truth class is b; a class is
+ *              0 or index + 1.  N[0][0] is not reported.
+ *   SIDES      one entry per pred component r, and the mirror image (rows and columns exchanged) per truth component:
+ *                voxels       sum over b of N[r + 1][b];
+ *                covered      voxels - N[r + 1][0]: its voxels that lie in any component of the other side;
+ *                partners     the number of b >= 1 with N[r + 1][b] > 0;
+ *                best         1 + the index of the partner with the largest intersection, ties to the smallest index; 0 when there is none;
+ *                best_voxels  that intersection (0 when there is none).
+ *              They are always exact, whatever cap is.  An id that no voxel carries gives an all-zero entry.
+ *   PAIRS      *found is the number of (a >= 1, b >= 1) with N[a][b] > 0; it is always exact.  pairs [cap] holds the first
+ *              min(found, cap) of them as { p, t, voxels } with p = a - 1 and t = b - 1, ordered by p ascending, then t ascending; the
+ *              entries behind them are all-zero.
+ * Limits, each with its reason:
+ *   D, H, W >= 1;
+ *   D * H * W < 2^31: every count is an int32_t;
+ *   mp, mt in 1 .. MI_UNET_VOLUME_MAX_TABLE: what mi_unet_volume_components can have numbered; the table has at most 4097^2 cells (67 MB);
+ *   cap >= 1.
+ * mi_unet_volume_match takes host buffers of any size; its workspace (both stacks, the dense table, the results) grows on demand,
+ * belongs to the handle and is freed by mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.
+ * It changes no setting and nothing mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued
+ * and no output written: a null pointer, or any limit broken.  A workspace that cannot be allocated is MI_UNET_EHIP with a message; the
+ * handle stays usable.
+ * mi_unet_volume_match_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle, same
+ * bytes.
+ * mi_unet_volume_match_assign is pure host arithmetic: a one-to-one assignment at an IoU threshold iou_num / iou_den,
+ * 1 <= iou_num <= iou_den <= 65536.  With i a pair's voxels, vp and vt the voxels of its two components, the union is u = vp + vt - i.
+ *   A pair is a candidate iff i * iou_den >= iou_num * u, compared in 64-bit integers.
+ *   Candidates are ordered by IoU descending: i1 * u2 against i2 * u1, both below 2^63, so the comparison is exact.  Ties go by p
+ *   ascending, then t ascending, so the order is total.  Walking that order, a candidate is accepted iff neither of its components is
+ *   taken yet.
+ *   match_of_pred [mp] and match_of_truth [mt] hold 1 + the partner, or 0.  counts = { tp, fp, fn } with tp the accepted pairs,
+ *   fp = mp_present - tp and fn = mt_present - tp; a component is present when its voxels > 0.
+ *   Above a threshold of 1/2 the candidates are already one-to-one (two candidates that share a component would each hold more than half
+ *   of it, and they are disjoint), so every assignment rule gives this result.  At or below 1/2 the assignment is greedy, not the optimal
+ *   one.
+ *   MI_UNET_EARG, output untouched: a null pointer, mp or mt outside 1 .. MI_UNET_VOLUME_MAX_TABLE, cap < 1, found < 0, a truncated
+ *   pair list (found > cap), a threshold outside its range, or a pair that names a component outside the tables.
+ * mi_unet_volume_match_derive is pure host arithmetic in double over the matches in pred order, so every sum has one value.  With
+ * IoU = i / u and Dice = 2 i / (vp + vt) of a match:
+ *   precision = tp / (tp + fp), recall = tp / (tp + fn), f1 = 2 tp / (2 tp + fp + fn);
+ *   sq = sum IoU / tp, rq = tp / (tp + fp / 2 + fn / 2), pq = sq * rq (panoptic quality); mean_dice = sum Dice / tp.
+ *   A quantity is NaN where its denominator is 0.  tp, fp, fn are recounted from match_of_pred and the side tables.
+ *   MI_UNET_EARG, output untouched: a null pointer, a size outside its range, found > cap, or a match that is not in the pair list.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+typedef struct mi_unet_vmatch_side { int32_t voxels, covered, partners, best, best_voxels; } mi_unet_vmatch_side;   /* 20 bytes */
+typedef struct mi_unet_vmatch_pair { int32_t p, t, voxels; } mi_unet_vmatch_pair;                                   /* 12 bytes */
+typedef struct mi_unet_vmatch_counts { int32_t tp, fp, fn; } mi_unet_vmatch_counts;
+typedef struct mi_unet_vmatch_scores { double precision, recall, f1, sq, rq, pq, mean_dice; } mi_unet_vmatch_scores;
+int mi_unet_volume_match(mi_unet_t *h, const int32_t *pred_ids /* [D][H][W] host */, const int32_t *truth_ids /* [D][H][W] host */,
+                         int D, int H, int W, int mp, int mt, int cap, mi_unet_vmatch_side *pred_side /* [mp] */,
+                         mi_unet_vmatch_side *truth_side /* [mt] */, mi_unet_vmatch_pair *pairs /* [cap] */, int *found);
+int mi_unet_volume_match_host(const int32_t *pred_ids, const int32_t *truth_ids, int D, int H, int W, int mp, int mt, int cap,
+                              mi_unet_vmatch_side *pred_side, mi_unet_vmatch_side *truth_side, mi_unet_vmatch_pair *pairs, int *found);
+int mi_unet_volume_match_assign(const mi_unet_vmatch_side *pred_side, int mp, const mi_unet_vmatch_side *truth_side, int mt,
+                                const mi_unet_vmatch_pair *pairs, int found, int cap, int iou_num, int iou_den,
+                                int32_t *match_of_pred /* [mp] */, int32_t *match_of_truth /* [mt] */, mi_unet_vmatch_counts *counts);
+int mi_unet_volume_match_derive(const mi_unet_vmatch_side *pred_side, int mp, const mi_unet_vmatch_side *truth_side, int mt,
+                                const mi_unet_vmatch_pair *pairs, int found, int cap, const int32_t *match_of_pred /* [mp] */,
+                                mi_unet_vmatch_scores *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -1,0 +1,285 @@
+"""The volume matching (include/mi_unet.h: mi_unet_volume_match) without a device: mi_unet_volume_match_host against the
+numpy reference of volume_match_ref.py (np.unique over the keys) field for field; mi_unet_volume_match_assign against the same rule over
+fractions.Fraction; mi_unet_volume_match_derive against plain Python floats; the argument checks, the struct sizes and the host half as
+a stand-alone program.  Integer work is compared exactly."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import volume_match_ref as vm
+import volume_ref as vr
+from miunet import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "unet-medical-image-contour-segmentation-cpp_amd")
+WHOLE = [n for n, c in vm.cases().items() if vm.case_ref(n)["found"] <= c[4]]       # the cases whose pair list is not truncated
+
+
+def test_the_cases_are_not_degenerate():
+    vm.assert_not_degenerate()
+    sizes = {n: (c[2], c[3], vm.case_ref(n)["found"]) for n, c in vm.cases().items()}
+    assert sizes["noise(7, 40, 72)"] == (60, 58, 15) and sizes["noise(16, 24, 130)"] == (125, 115, 21), sizes
+
+
+@pytest.mark.parametrize("name", list(vm.cases()))
+def test_host_equals_reference(name):
+    vm.assert_equal(vm.call(binding.volume_match_host, name), vm.case_ref(name), vm.cases()[name][4], name)
+
+
+@pytest.mark.parametrize("name", ["lesions", "noise(7, 40, 72)", "scattered(16, 24, 130)", "D1", "cap_short"])
+def test_exchanging_the_sides_transposes_the_result(name):
+    pred, truth, mp, mt, cap = vm.cases()[name]
+    ps, ts, pairs, found = binding.volume_match_host(pred, truth, mp, mt, cap=vm.CAP)
+    ts2, ps2, pairs2, found2 = binding.volume_match_host(truth, pred, mt, mp, cap=vm.CAP)
+    assert ps.tobytes() == ps2.tobytes() and ts.tobytes() == ts2.tobytes() and found == found2
+    a = sorted((int(q["p"]), int(q["t"]), int(q["voxels"])) for q in pairs[:found])
+    b = sorted((int(q["t"]), int(q["p"]), int(q["voxels"])) for q in pairs2[:found])
+    assert a == b
+
+
+@pytest.mark.parametrize("name", ["lesions", "noise(16, 24, 130)", "scattered(7, 40, 72)", "m4096"])
+def test_side_voxels_are_the_bincount_of_the_ids(name):
+    pred, truth, mp, mt, _ = vm.cases()[name]
+    ps, ts, _, _ = vm.call(binding.volume_match_host, name)
+    for ids, m, side in ((pred, mp, ps), (truth, mt, ts)):
+        flat = ids.reshape(-1)
+        count = np.bincount(flat[(flat >= 1) & (flat <= m)], minlength=m + 1)[1:]
+        assert np.array_equal(side["voxels"], count)
+        assert (side["covered"] <= side["voxels"]).all() and (side["best_voxels"] <= side["covered"]).all()
+
+
+def test_the_cap_cuts_the_list_and_nothing_else():
+    short, exact, long_ = (vm.call(binding.volume_match_host, n) for n in ("cap_short", "cap_exact", "cap_long"))
+    found = vm.case_ref("lesions")["found"]
+    assert short[3] == exact[3] == long_[3] == found and len(short[2]) == found - 4 and len(long_[2]) == found + 13
+    for got in (short, long_):
+        assert got[0].tobytes() == exact[0].tobytes() and got[1].tobytes() == exact[1].tobytes()
+    assert short[2].tobytes() == exact[2][:found - 4].tobytes() and long_[2][:found].tobytes() == exact[2].tobytes()
+    assert not long_[2][found:].tobytes().strip(b"\0")
+
+
+@pytest.mark.parametrize("iou", vm.THRESHOLDS)
+@pytest.mark.parametrize("name", WHOLE)
+def test_assign_equals_the_fraction_model(name, iou):
+    got = vm.call(binding.volume_match_host, name)
+    of_p, of_t, counts = binding.volume_match_assign(*got, iou=iou)
+    want_p, want_t, want_counts, _ = vm.assign(vm.case_ref(name), *iou)
+    assert of_p.tolist() == want_p and of_t.tolist() == want_t and counts == want_counts, (name, iou)
+    assert all(of_t[t - 1] == p + 1 for p, t in enumerate(of_p.tolist()) if t)             # one-to-one, both directions agree
+
+
+@pytest.mark.parametrize("iou", [(1, 2), (2, 3), (32769, 65536), (1, 1)])
+@pytest.mark.parametrize("name", WHOLE)
+def test_above_one_half_every_candidate_is_matched(name, iou):
+    """the uniqueness theorem: two pairs that share a component cannot both have IoU > 1/2, so above 1/2 the candidates are already
+    one-to-one and tp is their number -- no rule, and no model of the rule, takes part.  At exactly 1/2 one candidate may lose."""
+    ps, ts, pairs, found = vm.call(binding.volume_match_host, name)
+    _, _, counts = binding.volume_match_assign(ps, ts, pairs, found, iou=iou)
+    q = pairs[:found]
+    i, u = q["voxels"].astype(np.int64), ps["voxels"][q["p"]].astype(np.int64) + ts["voxels"][q["t"]] - q["voxels"]
+    candidates = int((i * iou[1] >= iou[0] * u).sum())
+    if iou == (1, 2):
+        assert counts["tp"] <= candidates
+    else:
+        assert counts["tp"] == candidates, (name, iou)
+
+
+def test_the_lesions_are_what_the_case_claims():
+    got = vm.call(binding.volume_match_host, "lesions")
+    of_p, of_t, counts = binding.volume_match_assign(*got, iou=(1, 2))
+    assert of_p.tolist() == [1, 0, 0, 0, 0, 6, 0, 7, 0] and of_t.tolist() == [1, 0, 0, 0, 0, 6, 8] and counts == {"tp": 3, "fp": 5, "fn": 4}
+    of_p, of_t, counts = binding.volume_match_assign(*got, iou=(1, 65536))
+    # pred 2 takes truth 2, not truth 3 (4 / 20 both); truth 4 goes to pred 3 (32 / 88) before pred 4 (32 / 96)
+    assert of_p.tolist() == [1, 2, 4, 0, 0, 6, 0, 7, 0] and counts == {"tp": 5, "fp": 3, "fn": 2}
+    ps, ts = got[0], got[1]
+    assert (ps["best"][1], ps["best_voxels"][1], ps["partners"][1]) == (2, 4, 2) and (ts["best"][3], ts["best_voxels"][3], ts["partners"][3]) == (3, 32, 2)
+    assert not ps[6].tobytes().strip(b"\0") and (ps["voxels"][7], ps["covered"][7]) == (13, 9)        # the piece under truth value 8 is not covered
+
+
+@pytest.mark.parametrize("name", WHOLE)
+def test_derive_equals_plain_python_floats(name):
+    got = vm.call(binding.volume_match_host, name)
+    for iou in vm.THRESHOLDS:
+        of_p, _, counts = binding.volume_match_assign(*got, iou=iou)
+        d, want = binding.volume_match_derive(*got, of_p), vm.derive(vm.case_ref(name), of_p.tolist(), counts)
+        assert set(d) == set(want)
+        for k, v in want.items():
+            assert (math.isnan(v) and math.isnan(d[k])) or abs(d[k] - v) <= 1e-12 * abs(v), (name, iou, k, d[k], v)
+
+
+def test_derive_is_nan_where_a_denominator_is_zero():
+    pred, truth = np.zeros((2, 3, 4), np.int32), np.zeros((2, 3, 4), np.int32)
+    pred[0, 0, 0], truth[1, 2, 3] = 1, 1
+    got = binding.volume_match_host(pred, truth, 1, 1, cap=4)
+    of_p, of_t, counts = binding.volume_match_assign(*got)
+    assert got[3] == 0 and counts == {"tp": 0, "fp": 1, "fn": 1} and not of_p.any() and not of_t.any()
+    d = binding.volume_match_derive(*got, of_p)
+    assert d["precision"] == d["recall"] == d["f1"] == d["rq"] == 0.0 and all(math.isnan(d[k]) for k in ("sq", "pq", "mean_dice"))
+    empty = binding.volume_match_host(np.zeros((2, 3, 4), np.int32), np.zeros((2, 3, 4), np.int32), 2, 3, cap=4)
+    of_p, _, counts = binding.volume_match_assign(*empty)
+    assert counts == {"tp": 0, "fp": 0, "fn": 0}
+    assert all(math.isnan(v) for v in binding.volume_match_derive(*empty, of_p).values())
+
+
+def test_ids_of_volume_components_host_chain_in():
+    masks = vr.smooth_noise((7, 40, 72))
+    moved = np.zeros_like(masks)
+    moved[:, 1:, :] = masks[:, :-1, :]
+    sides = []
+    for m in (masks, moved):
+        _, table, found, kept, ids = binding.volume_components_host(m, [1], connectivity=26, cap=vm.MAX_TABLE, want_ids=True)
+        sides.append((ids[0], int(found[0]), table[0]))
+    (pi, mp, ptab), (ti, mt, ttab) = sides
+    ps, ts, pairs, found = binding.volume_match_host(pi, ti, mp, mt, cap=vm.CAP)
+    assert np.array_equal(ps["voxels"], ptab["voxels"][:mp]) and np.array_equal(ts["voxels"], ttab["voxels"][:mt])
+    vm.assert_equal((ps, ts, pairs, found), vm.case_ref("noise(7, 40, 72)"), vm.CAP)          # the case IS this labelling
+
+
+# ---- arguments --------------------------------------------------------------------------------------------------------------------------
+def earg_cases():
+    """(name, dict of overrides of a good call's arguments); every one must return MI_UNET_EARG"""
+    return [("null pred", dict(pred=None)), ("null truth", dict(truth=None)), ("null pred side", dict(ps=None)), ("null truth side", dict(ts=None)),
+            ("null pairs", dict(pairs=None)), ("null found", dict(found=None)), ("D = 0", dict(D=0)), ("H = 0", dict(H=0)), ("W = -1", dict(W=-1)),
+            ("2^31 voxels", dict(D=32, H=8192, W=8192)), ("2^48 voxels", dict(D=65536, H=65536, W=65536)), ("mp = 0", dict(mp=0)),
+            ("mp = 4097", dict(mp=4097)), ("mt = 0", dict(mt=0)), ("mt = 4097", dict(mt=4097)), ("cap = 0", dict(cap=0)), ("cap = -5", dict(cap=-5))]
+
+
+def legal_cases():
+    """the near side of each limit"""
+    return [("mp = 4096", dict(mp=4096, rows_p=4096)), ("mt = 4096", dict(mt=4096, rows_t=4096)), ("cap = 1", dict(cap=1)),
+            ("mp = mt = 1", dict(mp=1, mt=1))]
+
+
+def call_with(fn, head, case):
+    """a good 2 x 5 x 7 call with the case's overrides, through ctypes, its outputs poisoned; returns (rc, outputs untouched)"""
+    pred = np.ones((2, 5, 7), np.int32)
+    truth = np.ones((2, 5, 7), np.int32)
+    pred[0, 2, 3] = truth[1, 1, 1] = 2
+    arrays = dict(pred=pred, truth=truth, ps=np.full((case.get("rows_p", 3), 20), 0x55, np.uint8), ts=np.full((case.get("rows_t", 3), 20), 0x55, np.uint8),
+                  pairs=np.full((6, 12), 0x55, np.uint8), found=np.full(1, 0x55555555, np.int32))
+    ptr = lambda name: None if name in case and case[name] is None else arrays[name].ctypes.data_as(C.c_void_p)
+    before = (pred.copy(), truth.copy())
+    found = None if "found" in case else C.cast(arrays["found"].ctypes.data_as(C.c_void_p), C.POINTER(C.c_int))
+    rc = fn(*head, ptr("pred"), ptr("truth"), case.get("D", 2), case.get("H", 5), case.get("W", 7), case.get("mp", 2), case.get("mt", 2),
+            case.get("cap", 6), ptr("ps"), ptr("ts"), ptr("pairs"), found)
+    untouched = all((arrays[k] == 0x55).all() for k in ("ps", "ts", "pairs")) and arrays["found"][0] == 0x55555555 \
+        and np.array_equal(pred, before[0]) and np.array_equal(truth, before[1])
+    return rc, bool(untouched)
+
+
+def test_host_argument_errors_leave_outputs_untouched():
+    L = binding.lib()
+    rc, untouched = call_with(L.mi_unet_volume_match_host, (), {})
+    assert rc == 0 and not untouched                                        # the good call the cases are made from
+    for name, case in earg_cases():
+        rc, untouched = call_with(L.mi_unet_volume_match_host, (), case)
+        assert rc == 1 and untouched, name
+        assert b"mi_unet_volume_match_host" in L.mi_unet_last_error(), name
+    for name, case in legal_cases():
+        assert call_with(L.mi_unet_volume_match_host, (), case)[0] == 0, name
+
+
+def test_assign_and_derive_argument_errors_leave_outputs_untouched():
+    L = binding.lib()
+    ps, ts, pairs, found = vm.call(binding.volume_match_host, "cap_exact")
+    mp, mt, cap = len(ps), len(ts), len(pairs)
+    good = dict(ps=ps, mp=mp, ts=ts, mt=mt, pairs=pairs, found=found, cap=cap, num=1, den=2)
+    stray = pairs.copy()
+    stray["t"][2] = mt
+    cases = [("null pred side", dict(ps=None)), ("null truth side", dict(ts=None)), ("null pairs", dict(pairs=None)), ("null of_p", dict(of_p=None)),
+             ("null of_t", dict(of_t=None)), ("null counts", dict(counts=None)), ("mp = 0", dict(mp=0)), ("mt = 4097", dict(mt=4097)),
+             ("cap = 0", dict(cap=0)), ("found = -1", dict(found=-1)), ("a truncated list", dict(cap=found - 1)), ("num = 0", dict(num=0)),
+             ("num > den", dict(num=3, den=2)), ("den = 65537", dict(num=1, den=65537)), ("a pair outside the tables", dict(pairs=stray))]
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    for name, over in [("good", {})] + cases:
+        a = dict(good, **over)
+        of_p, of_t, counts = np.full(mp, 0x55555555, np.int32), np.full(mt, 0x55555555, np.int32), np.full(3, 0x55555555, np.int32)
+        outs = dict(of_p=of_p, of_t=of_t, counts=counts)
+        outs.update({k: None for k in outs if k in over})
+        rc = L.mi_unet_volume_match_assign(ptr(a["ps"]), a["mp"], ptr(a["ts"]), a["mt"], ptr(a["pairs"]), a["found"], a["cap"], a["num"], a["den"],
+                                           ptr(outs["of_p"]), ptr(outs["of_t"]), C.cast(ptr(outs["counts"]), C.POINTER(binding.VMatchCounts)))
+        untouched = (of_p == 0x55555555).all() and (of_t == 0x55555555).all() and (counts == 0x55555555).all()
+        assert (rc, bool(untouched)) == ((0, False) if name == "good" else (1, True)), name
+        if name != "good":
+            assert b"mi_unet_volume_match_assign" in L.mi_unet_last_error(), name
+    with pytest.raises(binding.MiUnetError, match="truncated"):
+        binding.volume_match_assign(*vm.call(binding.volume_match_host, "cap_short"))
+    of_p, _, _ = binding.volume_match_assign(ps, ts, pairs, found)
+    wrong = of_p.copy()
+    wrong[4] = 1                                                # pred 5 overlaps nothing: (4, 0) is no pair
+    for name, args in (("a truncated list", (ps, ts, pairs[:found - 1], found, of_p)), ("a match that is no pair", (ps, ts, pairs, found, wrong))):
+        out = np.full(7, np.float64(-7.0))
+        pr = np.ascontiguousarray(args[2])
+        rc = L.mi_unet_volume_match_derive(ptr(args[0]), mp, ptr(args[1]), mt, ptr(pr), args[3], len(pr), ptr(args[4]),
+                                           C.cast(ptr(out), C.POINTER(binding.VMatchScores)))
+        assert rc == 1 and (out == -7.0).all() and b"mi_unet_volume_match_derive" in L.mi_unet_last_error(), name
+
+
+def test_struct_sizes_and_header_strings():
+    assert binding.VMATCH_SIDE_DTYPE.itemsize == 20 and binding.VMATCH_PAIR_DTYPE.itemsize == 12
+    assert binding.VMATCH_SIDE_DTYPE.names == vm.SIDE_FIELDS and binding.VMATCH_PAIR_DTYPE.names == vm.PAIR_FIELDS
+    assert C.sizeof(binding.VMatchCounts) == 12 and C.sizeof(binding.VMatchScores) == 7 * 8
+    header = open(os.path.join(ROOT, "include", "mi_unet.h")).read()
+    assert "Volume matching (DESIGN.md 7.14)" in header and "greedy, not the optimal" in header and "already one-to-one" in header
+    assert "typedef struct mi_unet_vmatch_side { int32_t voxels, covered, partners, best, best_voxels; } mi_unet_vmatch_side;" in header
+    assert "typedef struct mi_unet_vmatch_pair { int32_t p, t, voxels; } mi_unet_vmatch_pair;" in header
+    for name in ("mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive"):
+        assert hasattr(binding.lib(), name) and name in binding.EXPORTS
+    kernel = open(os.path.join(PKG, "csrc", "volume_match.hip")).read()
+    assert f"constexpr int GROUPS = {vm.GROUPS};" in kernel                   # what the crowded segments are counted against
+    assert binding.VOLUME_MAX_TABLE == vm.MAX_TABLE
+
+
+def test_host_half_as_a_stand_alone_program(tmp_path):
+    """tests/cpu/volume_match_host_test.cpp + csrc/volume_match.cpp without its device entry point, built by a plain C++ compiler: the
+    form in which the host half runs under -fsanitize=address,undefined (the command is in the program's header); here it is built
+    without"""
+    exe = tmp_path / "volume_match_host_test"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_VOLUME_MATCH_NO_DEVICE", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "cpu", "volume_match_host_test.cpp"), os.path.join(PKG, "csrc", "volume_match.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, timeout=120)
+    assert r.returncode == 0 and b"volume_match_host_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]
+
+
+# ---- the facade's setting (needs no engine) ---------------------------------------------------------------------------------------------------
+def test_cli_volmatch_command():
+    from miunet import hostlib
+    cli = os.path.join(os.path.dirname(hostlib.LIB_PATH), "medseg_cli")
+    script = ("volmatch\nvolmatch on\nvolmatch on iou 1/4\nvolmatch\nvolmatch on iou 65536/65536\nvolmatch off\nvolmatch off 3\nvolmatch on iou\n"
+              "volmatch on iou 3\nvolmatch on dice 1/2\nvolmatch maybe\nvolmatch on iou 3/2\nvolmatch on iou 0/2\nvolmatch on iou 1/65537\n"
+              "volmatch\nvolume\nvolmeasure\nhelp\nexit\n")
+    r = subprocess.run([cli], input=script.encode(), capture_output=True, timeout=60)
+    out, err = r.stdout.decode(), r.stderr.decode()
+    assert r.returncode == 0
+    said = [l.replace("> ", "") for l in out.splitlines() if l.replace("> ", "").startswith("Volume match:")]
+    assert said == ["Volume match: off iou 1/2", "Volume match: on iou 1/2", "Volume match: on iou 1/4", "Volume match: on iou 1/4",
+                    "Volume match: on iou 65536/65536", "Volume match: off iou 1/2", "Volume match: off iou 1/2"]
+    # off with a word, a key without its value, a value without a slash, an unknown key, an unknown word; then the three thresholds refused
+    assert err.count("Invalid volmatch command") == 5 and err.count("Volume match unchanged") == 3
+    assert "volmatch on [iou N/D]|off" in out
+    assert "Volume: off 26 min 0 keep 0 spacing 1 1 1" in out and "Volume measure: off channel 0 ends 262144" in out    # the siblings are untouched
+
+
+def test_volume_match_setting_round_trips_through_the_c_view():
+    from miunet import hostlib
+    default = {"on": False, "iou": (1, 2)}
+    volume, measure = hostlib.get_volume(), hostlib.get_volume_measure()
+    assert hostlib.get_volume_match() == default
+    try:
+        assert hostlib.set_volume_match(True, (3, 4))
+        want = {"on": True, "iou": (3, 4)}
+        assert hostlib.get_volume_match() == want
+        for bad in ((0, 4), (5, 4), (1, 65537), (-1, 2)):
+            assert not hostlib.set_volume_match(True, bad) and hostlib.get_volume_match() == want, bad
+        assert hostlib.set_volume_match(True, (65536, 65536)) and hostlib.set_volume_match(True, (1, 65536))
+        assert hostlib.set_volume_match(True) and hostlib.get_volume_match() == {"on": True, "iou": (1, 2)}
+        assert hostlib.get_volume() == volume and hostlib.get_volume_measure() == measure      # a setting of its own
+    finally:
+        assert hostlib.set_volume_match(False)
+    assert hostlib.get_volume_match() == default
+    for name in ("medseg_set_volume_match", "medseg_get_volume_match"):
+        assert name in open(os.path.join(ROOT, "include", "medseg_c.h")).read()

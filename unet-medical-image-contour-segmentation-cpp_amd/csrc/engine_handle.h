@@ -166,6 +166,11 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_vms, d_vms_pts;
     miunet::PinnedBuf<uint8_t> h_vms, h_vms_pts;
     size_t vms_dev_cap = 0, vms_host_cap = 0, vms_pts_dev_cap = 0, vms_pts_host_cap = 0;            // bytes
+    // mi_unet_volume_match: d_vmt = both id stacks, the contingency table, the side tables, the row offsets, `found` and
+    // the pair list of one call; h_vmt = the pinned staging of the id stacks and of the results; grown on demand, never shared with a clone
+    miunet::DeviceBuf<uint8_t> d_vmt;
+    miunet::PinnedBuf<uint8_t> h_vmt;
+    size_t vmt_dev_cap = 0, vmt_host_cap = 0;                                                          // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

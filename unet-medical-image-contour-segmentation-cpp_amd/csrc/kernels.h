@@ -14,6 +14,8 @@ struct mi_unet_score;
 struct mi_unet_vcomp;
 struct mi_unet_mesh_vertex;
 struct mi_unet_vmeasure;
+struct mi_unet_vmatch_side;
+struct mi_unet_vmatch_pair;
 
 namespace miunet {
 
@@ -414,5 +416,24 @@ hipError_t launch_volume_measure_pairs(const int4 *points, const int2 *seg, cons
                                        hipStream_t s);
 hipError_t launch_volume_measure_ends(const int4 *points, const int2 *seg, const unsigned long long *keys, const VolumeMeasureArgs &a,
                                       int32_t *diam, hipStream_t s);
+
+// Volume matching (volume_match.hip; include/mi_unet.h: mi_unet_volume_match).  pred and truth int32 [D][H][W] on the
+// device; a voxel's class is its id when 1 <= id <= m of its side, else 0.  table is the dense contingency table, int32 [mp + 1][mt + 1],
+// row = pred class.  Every result is an integer sum or maximum: nothing depends on the order in which atomics arrive.  No workgroup waits
+// for another.
+//   launch_volume_match_count: zeroes table over this call's (mp + 1)(mt + 1) cells, then k_vmt_count adds every voxel whose key
+//       a (mt + 1) + b is not 0 (cell [0][0] stays 0): a wave carries the counts of four keys and sends one atomic when a key is
+//       displaced.
+//   launch_volume_match_tables: k_vmt_rows (a wave per pred component) and k_vmt_cols (a lane per truth component walking 64 rows of the
+//       table; the parts of a column meet in col_acc, mt * VMT_COL_ACC_BYTES bytes aligned to 8, zeroed here) with k_vmt_cols_end write
+//       the finished side tables; k_vmt_rows also writes row_pairs [mp] = the row's partners; k_vmt_scan (one workgroup) turns them into
+//       row_first [mp], the exclusive prefix, and *found; k_vmt_pairs (a wave per row) writes every pair whose position is below
+//       keep_pairs at its final position, in (p, t) order.
+constexpr size_t VMT_COL_ACC_BYTES = 16;
+struct VolumeMatchArgs { int D = 0, H = 0, W = 0, mp = 0, mt = 0; };
+hipError_t launch_volume_match_count(const int32_t *pred, const int32_t *truth, const VolumeMatchArgs &a, int32_t *table, hipStream_t s);
+hipError_t launch_volume_match_tables(const int32_t *table, const VolumeMatchArgs &a, ::mi_unet_vmatch_side *pred_side,
+                                      ::mi_unet_vmatch_side *truth_side, int32_t *row_pairs, int32_t *row_first, int32_t *found,
+                                      void *col_acc, ::mi_unet_vmatch_pair *pairs, int keep_pairs, hipStream_t s);
 
 }  // namespace miunet

@@ -206,6 +206,12 @@ void medseg_get_volume_measure(int *on, int *channel, int *max_ends)
     const MedicalSeg::VolumeMeasure m = MedicalSeg::get_volume_measure();
     *on = m.on; *channel = m.channel; *max_ends = m.max_ends;
 }
+int medseg_set_volume_match(int on, int iou_num, int iou_den) { return MedicalSeg::set_volume_match({ on != 0, iou_num, iou_den }) ? 0 : 1; }
+void medseg_get_volume_match(int *on, int *iou_num, int *iou_den)
+{
+    const MedicalSeg::VolumeMatch m = MedicalSeg::get_volume_match();
+    *on = m.on; *iou_num = m.iou_num; *iou_den = m.iou_den;
+}
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap)

@@ -150,6 +150,7 @@ public:
         table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
         table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
+        table_["volmatch"] = [this](const Words &w) { cmd_volmatch(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
     }
@@ -171,6 +172,7 @@ public:
             "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
             "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
+            "  volmatch on [iou N/D]|off     - With volume on and truth: components matched to truth components, detection F1 and PQ per target",
             "  exit                          - Cleanup and exit",
             "",
             "Options:",
@@ -471,6 +473,31 @@ private:
         }
         const MedicalSeg::VolumeMeasure cur = MedicalSeg::get_volume_measure();
         std::cout << "Volume measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " ends " << cur.max_ends << std::endl;
+    }
+
+    // volmatch on [iou N/D] | volmatch off | volmatch (prints the setting in force)
+    void cmd_volmatch(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeMatch m;
+            bool ok = (w[1] == "off" && w.size() == 2) || (w[1] == "on" && (w.size() == 2 || w.size() == 4));
+            m.on = w[1] == "on";
+            if (ok && w.size() == 4) {
+                const size_t slash = w[3].find('/');
+                ok = w[2] == "iou" && slash != std::string::npos && to_int(w[3].substr(0, slash), m.iou_num) &&
+                     to_int(w[3].substr(slash + 1), m.iou_den);
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volmatch command (expected on [iou N/D] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_match(m)) {
+                std::cerr << "Volume match unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeMatch cur = MedicalSeg::get_volume_match();
+        std::cout << "Volume match: " << (cur.on ? "on" : "off") << " iou " << cur.iou_num << "/" << cur.iou_den << std::endl;
     }
 
     // morph rect|disc <open_r> [close_r] | morph default | morph (prints the setting in force)

@@ -365,6 +365,20 @@ bool set_volume_measure(const VolumeMeasure &measure)
         /*handle_side=*/false);
 }
 
+bool set_volume_match(const VolumeMatch &match)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_match = match;
+            const bool ok = match.iou_num >= 1 && match.iou_num <= match.iou_den && match.iou_den <= 65536;
+            return std::string(ok ? "" : "volume match: the threshold is 1 <= iou_num <= iou_den <= 65536");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume match: " << (match.on ? "on" : "off") << ", iou " << match.iou_num << "/" << match.iou_den;
+        },
+        /*handle_side=*/false);
+}
+
 Settings current_settings()
 {
     std::lock_guard<std::mutex> lk(g_state_mutex);
@@ -384,6 +398,7 @@ Volume get_volume() { return current_settings().volume; }
 VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
+VolumeMatch get_volume_match() { return current_settings().volume_match; }
 
 std::ofstream &get_log_file() { return g_log_file; }
 std::string get_log_path() { return g_log_path; }

@@ -718,10 +718,14 @@ std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, cons
 // A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
 // is active (without one they are the cleaned stack itself).  With `mesh` on, the planes that were labelled -- `out` under a filter, else
 // the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".  With `measure` on, the components
-// stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member "measure".
+// stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member "measure".  With
+// `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays empty after a failure.
+struct VolumeIds {
+    std::vector<int32_t> ids, found;
+};
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
                   std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string(),
-                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure())
+                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure(), VolumeIds *numbered = nullptr)
 {
     filtered.clear();
     try {
@@ -729,7 +733,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(measure.on ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(measure.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const bool device = h && device_postprocess_requested();
@@ -737,7 +741,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         for (size_t t = 0; t < K; ++t) {
             const uint8_t *const in = st.planes.data() + t * D * hw;
             uint8_t *const o = filter ? out.data() + t * D * hw : nullptr;
-            int32_t *const id = measure.on ? ids.data() + t * D * hw : nullptr;
+            int32_t *const id = ids.empty() ? nullptr : ids.data() + t * D * hw;
             const int rc = device ? mi_unet_volume_components(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
                                                               table.data() + t * cap, (int)cap, &found[t], &kept[t])
                                   : mi_unet_volume_components_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
@@ -789,8 +793,103 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         a.height = g_cfg.height; a.width = g_cfg.width;
         write_volume_artefacts(a);
         filtered.swap(out);
+        if (numbered) {
+            numbered->ids.swap(ids);
+            numbered->found.swap(found);
+        }
     } catch (const std::exception &e) {
         report(lg, std::string("Volume error: ") + e.what());
+    }
+}
+
+// set_volume_match: per target the truth stack (0 / 255, [D][H][W] at truth_planes + t * D * hw) labelled by mi_unet_volume_components
+// under the setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE, then one mi_unet_volume_match call on `h`
+// (the host forms under MEDSEG_HOST_POSTPROCESS=1) against the ids label_volume numbered, mi_unet_volume_match_assign at the setting's
+// threshold and mi_unet_volume_match_derive.  Returns per target the "lesions" member of its object in volume_score.json, from its
+// leading comma on.  A failure is reported and returns nothing: only this step ends.
+std::vector<std::string> match_volume(const VolumeIds &numbered, const std::vector<uint8_t> &truth_planes, size_t D, size_t hw,
+                                      const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeMatch &match, mi_unet_t *h,
+                                      std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size(), table_cap = MI_UNET_VOLUME_MAX_TABLE;
+        if (numbered.ids.size() != K * D * hw || numbered.found.size() != K) throw std::runtime_error("the labelled stack is missing");
+        const bool device = h && device_postprocess_requested();
+        const mi_unet_volume_opts opts{ v.connectivity, 0, 0 };
+        const int value = 255;
+        std::vector<std::string> members(K);
+        std::vector<int32_t> truth_ids(D * hw);
+        std::vector<mi_unet_vcomp> truth_table(table_cap);
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const uint8_t *const truth = truth_planes.data() + t * D * hw;
+            int32_t truth_found = 0, truth_kept = 0;
+            int rc = device ? mi_unet_volume_components(h, truth, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, nullptr, truth_ids.data(),
+                                                        truth_table.data(), (int)table_cap, &truth_found, &truth_kept)
+                            : mi_unet_volume_components_host(truth, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, nullptr, truth_ids.data(),
+                                                             truth_table.data(), (int)table_cap, &truth_found, &truth_kept);
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            const size_t mp = std::min<size_t>((size_t)numbered.found[t], table_cap), mt = std::min<size_t>((size_t)truth_found, table_cap);
+            const bool truncated = (size_t)numbered.found[t] > table_cap || (size_t)truth_found > table_cap;
+            // a side without components is matched as one id that no voxel carries: an all-zero entry, which is not present
+            const size_t np = std::max<size_t>(mp, 1), nt = std::max<size_t>(mt, 1);
+            const size_t cap = std::min(np * nt, D * hw);       // a pair holds a cell and a voxel of its own: the list is never truncated
+            std::vector<mi_unet_vmatch_side> ps(np), ts(nt);
+            std::vector<mi_unet_vmatch_pair> pairs(cap);
+            int found = 0;
+            const int32_t *const pred_ids = numbered.ids.data() + t * D * hw;
+            rc = device ? mi_unet_volume_match(h, pred_ids, truth_ids.data(), (int)D, g_cfg.height, g_cfg.width, (int)np, (int)nt, (int)cap, ps.data(),
+                                               ts.data(), pairs.data(), &found)
+                        : mi_unet_volume_match_host(pred_ids, truth_ids.data(), (int)D, g_cfg.height, g_cfg.width, (int)np, (int)nt, (int)cap, ps.data(),
+                                                    ts.data(), pairs.data(), &found);
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            std::vector<int32_t> of_p(np), of_t(nt);
+            mi_unet_vmatch_counts c{};
+            mi_unet_vmatch_scores sc{};
+            if (mi_unet_volume_match_assign(ps.data(), (int)np, ts.data(), (int)nt, pairs.data(), found, (int)cap, match.iou_num, match.iou_den,
+                                            of_p.data(), of_t.data(), &c) != MI_UNET_OK ||
+                mi_unet_volume_match_derive(ps.data(), (int)np, ts.data(), (int)nt, pairs.data(), found, (int)cap, of_p.data(), &sc) != MI_UNET_OK)
+                throw std::runtime_error(mi_unet_last_error());
+            std::ostringstream js;
+            js << ", \"lesions\": {\"pred\": " << mp << ", \"truth\": " << mt << ", \"iou_threshold\": [" << match.iou_num << ", " << match.iou_den
+               << "], \"tp\": " << c.tp << ", \"fp\": " << c.fp << ", \"fn\": " << c.fn << ", \"precision\": " << json_number(sc.precision)
+               << ", \"recall\": " << json_number(sc.recall) << ", \"f1\": " << json_number(sc.f1) << ", \"pq\": " << json_number(sc.pq)
+               << ", \"sq\": " << json_number(sc.sq) << ", \"rq\": " << json_number(sc.rq) << ", \"mean_dice\": " << json_number(sc.mean_dice)
+               << ", \"matches\": [";
+            bool first = true;
+            for (size_t r = 0; r < mp; ++r) {
+                if (!of_p[r]) continue;
+                const int32_t tc = of_p[r] - 1;
+                const mi_unet_vmatch_pair *q = pairs.data();
+                while (q->p != (int32_t)r || q->t != tc) ++q;   // (derive has found it: the match is in the list)
+                const double i = q->voxels, vp = ps[r].voxels, vt = ts[tc].voxels;
+                js << (first ? "" : ", ") << "{\"pred\": " << r << ", \"truth\": " << tc << ", \"voxels\": " << q->voxels << ", \"iou\": "
+                   << json_number(i / (vp + vt - i)) << ", \"dice\": " << json_number(2.0 * i / (vp + vt)) << ", \"pred_voxels\": " << ps[r].voxels
+                   << ", \"truth_voxels\": " << ts[tc].voxels << "}";
+                first = false;
+            }
+            js << "], \"missed\": [";
+            first = true;
+            for (size_t k = 0; k < mt; ++k) {
+                if (of_t[k] || ts[k].voxels < 1) continue;
+                js << (first ? "" : ", ") << "{\"truth\": " << k << ", \"voxels\": " << ts[k].voxels << "}";
+                first = false;
+            }
+            js << "], \"spurious\": [";
+            first = true;
+            for (size_t r = 0; r < mp; ++r) {
+                if (of_p[r] || ps[r].voxels < 1) continue;
+                js << (first ? "" : ", ") << r;
+                first = false;
+            }
+            js << "]" << (truncated ? ", \"truncated\": true" : "") << "}";
+            members[t] = js.str();
+        }
+        lg << "Volume match: " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume match error: ") + e.what());
+        return {};
     }
 }
 
@@ -799,15 +898,17 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
 // MEDSEG_HOST_POSTPROCESS=1): pred is the target's plane of `filtered` when the volume filter is active, else of the stack; truth is
 // recoded to 0 / 255 by truth == cls.  The integer units come from mi_unet_score_volume_units on the setting's spacing.  Writes
 // <output_dir>/volume_score.json.  Only a stack whose every slice completed and has a truth file of the tile's size is scored; a
-// failure is reported and fails no image.
+// failure is reported and fails no image.  With `match` on, every target object gains a last member "lesions" (match_volume) from the
+// ids label_volume numbered.
 void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filtered, const std::vector<mi_unet_target> &targets, const Volume &v,
-                        const std::string &truth_dir, mi_unet_t *h, const std::string &output_dir, std::ostream &lg)
+                        const std::string &truth_dir, mi_unet_t *h, const std::string &output_dir, std::ostream &lg,
+                        const VolumeMatch &match = VolumeMatch(), const VolumeIds &numbered = VolumeIds())
 {
     try {
         const size_t K = targets.size(), D = st.D, hw = st.hw;
         const bool filter = !filtered.empty() || v.min_voxels > 0 || v.keep_largest > 0;       // (a cleaned stack comes filtered too)
         if (filter && filtered.size() != K * D * hw) throw std::runtime_error("the filtered stack is missing");
-        std::vector<uint8_t> labels(D * hw), truth(D * hw);
+        std::vector<uint8_t> labels(D * hw), truth(D * hw), truth_planes(match.on ? K * D * hw : 0);
         size_t without = 0;
         for (size_t z = 0; z < D; ++z) {
             bool good = !st.bases[z].empty();
@@ -842,8 +943,10 @@ void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filte
                                   : mi_unet_score_volume_host(pred, truth.data(), (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts,
                                                               &scores[t], nullptr, nullptr);
             if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            if (match.on) std::copy(truth.begin(), truth.end(), truth_planes.begin() + t * D * hw);
         }
         lg << "Volume score: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
+        const std::vector<std::string> lesions = match.on ? match_volume(numbered, truth_planes, D, hw, targets, v, match, h, lg) : std::vector<std::string>();
         std::ostringstream js;
         js << "{\n  \"slices\": [";
         for (size_t z = 0; z < D; ++z) js << (z ? ", " : "") << "\"" << medseg::json_escape(st.names[z]) << "\"";
@@ -856,7 +959,7 @@ void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filte
             js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"tp\": " << sc.tp << ", \"fp\": " << sc.fp << ", \"fn\": " << sc.fn
                << ", \"dice\": " << json_number(m.dice) << ", \"iou\": " << json_number(m.iou) << ", \"hd_mm\": " << json_number(m.hd)
                << ", \"hd_q_mm\": " << json_number(m.hd_q) << ", \"assd_mm\": " << json_number(m.assd) << ", \"rmsd_mm\": " << json_number(m.rmsd)
-               << "}";
+               << (lesions.empty() ? std::string() : lesions[t]) << "}";
         }
         js << "\n  ]\n}\n";
         write_volume_score(output_dir, js.str());
@@ -985,11 +1088,13 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             if (settings.volume_clean.on &&
                 !clean_volume(stack, settings.targets, settings.volume, settings.volume_clean, mi_unet_group_handle(group, 0), lg.text, clean_json))
                 return ok;
+            const bool match = settings.volume_match.on && !settings.truth_dir.empty();
+            VolumeIds numbered;
             label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json,
-                         settings.volume_mesh, settings.volume_measure);
+                         settings.volume_mesh, settings.volume_measure, match ? &numbered : nullptr);
             if (!settings.truth_dir.empty())
                 score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
-                                   lg.text);
+                                   lg.text, settings.volume_match, numbered);
             return ok;
         }
         if (!is_default(settings.targets) || !is_default(settings.morph)) {

@@ -39,6 +39,7 @@ EXPORTS = [
     "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
     "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
+    "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
 ]
 
 
@@ -344,6 +345,39 @@ def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
     return table
 
 
+class VMatchCounts(C.Structure):
+    _fields_ = [("tp", C.c_int32), ("fp", C.c_int32), ("fn", C.c_int32)]
+
+
+class VMatchScores(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("precision", "recall", "f1", "sq", "rq", "pq", "mean_dice")]
+
+
+VMATCH_SIDE_DTYPE = np.dtype([(n, np.int32) for n in ("voxels", "covered", "partners", "best", "best_voxels")])   # mi_unet_vmatch_side
+VMATCH_PAIR_DTYPE = np.dtype([(n, np.int32) for n in ("p", "t", "voxels")])                                       # mi_unet_vmatch_pair
+
+
+def _volume_match_call(fn, head, pred_ids, truth_ids, mp, mt, cap):
+    """mi_unet_volume_match (head = (handle,)) or its host form (head = ()): pred_ids, truth_ids int32 [D,H,W] (or [H,W]: one slice) of
+    one shape, mp and mt components, cap = the length of the pair list -> (pred_side VMATCH_SIDE_DTYPE [mp], truth_side [mt], pairs
+    VMATCH_PAIR_DTYPE [cap], found).  The library checks the values."""
+    pred_ids = np.ascontiguousarray(pred_ids, np.int32)
+    truth_ids = np.ascontiguousarray(truth_ids, np.int32)
+    if pred_ids.ndim == 2:
+        pred_ids = pred_ids[None]
+    if truth_ids.ndim == 2:
+        truth_ids = truth_ids[None]
+    if pred_ids.ndim != 3 or truth_ids.shape != pred_ids.shape:
+        raise ValueError(f"pred_ids {pred_ids.shape} and truth_ids {truth_ids.shape} must be two int32 [D,H,W] arrays of one shape")
+    d, hh, ww = pred_ids.shape
+    ps = np.zeros(max(int(mp), 1), VMATCH_SIDE_DTYPE)
+    ts = np.zeros(max(int(mt), 1), VMATCH_SIDE_DTYPE)
+    pairs = np.zeros(max(int(cap), 1), VMATCH_PAIR_DTYPE)
+    found = C.c_int(0)
+    _check(fn(*head, _ptr(pred_ids), _ptr(truth_ids), d, hh, ww, int(mp), int(mt), int(cap), _ptr(ps), _ptr(ts), _ptr(pairs), C.byref(found)))
+    return ps, ts, pairs, found.value
+
+
 def _last_regions(fn, handle):
     """(regions REGION_DTYPE [planes, cap_contours], counts int32 [planes]) of mi_unet_last_regions or its group form"""
     planes, cap = C.c_int(), C.c_int()
@@ -525,6 +559,12 @@ def lib():
         L.mi_unet_volume_measure_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_measure.argtypes = [C.c_void_p] + L.mi_unet_volume_measure_host.argtypes
         L.mi_unet_volume_measure_derive.argtypes = [C.POINTER(VMeasure), C.c_void_p, C.c_double, C.POINTER(VMeasureShape)]
+        L.mi_unet_volume_match_host.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
+        L.mi_unet_volume_match.argtypes = [C.c_void_p] + L.mi_unet_volume_match_host.argtypes
+        L.mi_unet_volume_match_assign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(VMatchCounts)]
+        L.mi_unet_volume_match_derive.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                  C.POINTER(VMatchScores)]
         L.mi_unet_group_set_measure.argtypes = [C.c_void_p, C.POINTER(Measure)]
         L.mi_unet_group_last_regions.argtypes = L.mi_unet_last_regions.argtypes
         L.mi_unet_set_morph.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_int]
@@ -932,6 +972,13 @@ class Engine:
         -> table VMEASURE_DTYPE [m]"""
         return _volume_measure_call(lib().mi_unet_volume_measure, (self._h,), ids, intensity, m, units, max_ends)
 
+    # ---- the components of two labelled stacks matched (mi_unet_volume_match): needs the device, not the weights
+    def volume_match(self, pred_ids, truth_ids, mp, mt, cap=4096):
+        """pred_ids, truth_ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, mp and mt = the components a side
+        (ids 1 .. m), cap = the length of the pair list -> (pred_side VMATCH_SIDE_DTYPE [mp], truth_side [mt], pairs VMATCH_PAIR_DTYPE
+        [cap], found)"""
+        return _volume_match_call(lib().mi_unet_volume_match, (self._h,), pred_ids, truth_ids, mp, mt, cap)
+
     # ---- scores of a stack as one volume (mi_unet_score_volume): needs the device, not the weights
     def score_volume(self, pred, truth, values, spacing_units, quantile_ppm=50000, classes=0):
         """pred, truth u8 [D,H,W] of any size, values = the bytes to compare, spacing_units = (ux, uy, uz) positive integers ->
@@ -1086,6 +1133,39 @@ def volume_measure_derive(comp, units, unit_mm):
     d["axis_mm"] = [float(v) for v in out.axis_mm]
     d["axis_dir"] = [[float(v) for v in row] for row in out.axis_dir]
     return d
+
+
+def volume_match_host(pred_ids, truth_ids, mp, mt, cap=4096):
+    """mi_unet_volume_match_host: Engine.volume_match as sequential host arithmetic (needs no device)"""
+    return _volume_match_call(lib().mi_unet_volume_match_host, (), pred_ids, truth_ids, mp, mt, cap)
+
+
+def _vmatch_tables(pred_side, truth_side, pairs):
+    return (np.ascontiguousarray(pred_side, VMATCH_SIDE_DTYPE), np.ascontiguousarray(truth_side, VMATCH_SIDE_DTYPE),
+            np.ascontiguousarray(pairs, VMATCH_PAIR_DTYPE))
+
+
+def volume_match_assign(pred_side, truth_side, pairs, found, iou=(1, 2)):
+    """mi_unet_volume_match_assign: the one-to-one assignment of the pair list (all `found` pairs present) at the IoU threshold
+    iou = (num, den) -> (match_of_pred int32 [mp], match_of_truth int32 [mt], each 1 + the partner or 0, dict of tp, fp, fn)"""
+    ps, ts, pr = _vmatch_tables(pred_side, truth_side, pairs)
+    of_p, of_t = np.zeros(len(ps), np.int32), np.zeros(len(ts), np.int32)
+    counts = VMatchCounts()
+    _check(lib().mi_unet_volume_match_assign(_ptr(ps), len(ps), _ptr(ts), len(ts), _ptr(pr), int(found), len(pr), int(iou[0]), int(iou[1]),
+                                             _ptr(of_p), _ptr(of_t), C.byref(counts)))
+    return of_p, of_t, {"tp": counts.tp, "fp": counts.fp, "fn": counts.fn}
+
+
+def volume_match_derive(pred_side, truth_side, pairs, found, match_of_pred):
+    """mi_unet_volume_match_derive: the scores of an assignment -> dict of precision, recall, f1, sq, rq, pq, mean_dice (NaN where
+    undefined)"""
+    ps, ts, pr = _vmatch_tables(pred_side, truth_side, pairs)
+    of_p = np.ascontiguousarray(match_of_pred, np.int32)
+    if of_p.shape != (len(ps),):
+        raise ValueError("match_of_pred holds one entry per pred component")
+    out = VMatchScores()
+    _check(lib().mi_unet_volume_match_derive(_ptr(ps), len(ps), _ptr(ts), len(ts), _ptr(pr), int(found), len(pr), _ptr(of_p), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VMatchScores._fields_}
 
 
 def _spacing3(spacing):

@@ -23,7 +23,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
            "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
-           "medseg_set_volume_measure", "medseg_get_volume_measure"]
+           "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match"]
 
 
 def lib():
@@ -83,6 +83,9 @@ def lib():
         L.medseg_set_volume_measure.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_measure.argtypes = [_i, _i, _i]
         L.medseg_get_volume_measure.restype = None
+        L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.medseg_get_volume_match.argtypes = [_i, _i, _i]
+        L.medseg_get_volume_match.restype = None
         _LIB = L
     return _LIB
 
@@ -254,6 +257,18 @@ def get_volume_measure():
     on, channel, ends = C.c_int(), C.c_int(), C.c_int()
     lib().medseg_get_volume_measure(C.byref(on), C.byref(channel), C.byref(ends))
     return {"on": bool(on.value), "channel": channel.value, "max_ends": ends.value}
+
+
+def set_volume_match(on=True, iou=(1, 2)) -> bool:
+    """MedicalSeg::set_volume_match: where set_volume on and set_truth_dir produce volume_score.json, every target gains a "lesions"
+    member (mi_unet_volume_match, then the one-to-one assignment at the IoU threshold iou = (num, den)); needs no engine"""
+    return lib().medseg_set_volume_match(int(bool(on)), int(iou[0]), int(iou[1])) == 0
+
+
+def get_volume_match():
+    on, num, den = C.c_int(), C.c_int(), C.c_int()
+    lib().medseg_get_volume_match(C.byref(on), C.byref(num), C.byref(den))
+    return {"on": bool(on.value), "iou": (num.value, den.value)}
 
 
 def get_measure():
