@@ -159,6 +159,32 @@ struct VolumeMeasure {
 bool set_volume_measure(const VolumeMeasure &measure);
 VolumeMeasure get_volume_measure();
 
+// The texture of every component of the labelled stack (mi_unet_volume_texture in include/mi_unet.h).  It acts only
+// together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits (beside the channel
+// set_volume_measure keeps, when the two differ), a failed slice all-zero; one mi_unet_volume_texture call per target
+// (mi_unet_volume_texture_host under MEDSEG_HOST_POSTPROCESS=1) on the ids mi_unet_volume_components hands out, with
+// m = min(found, MI_UNET_VOLUME_MAX_TABLE, 2^22 / levels^2) -- the log line says so when that cuts the table short -- and
+// mi_unet_volume_texture_derive on every row.  mode is MI_UNET_VTEX_COUNT (levels bins over each component's own range) or
+// MI_UNET_VTEX_WIDTH (bins of `width` from `lo`).  Every component object of volume_report.json gains a last member "texture" (behind
+// "measure" when both are on): "levels", "mode" ("count" or "width"), "range" ([imin, imax]), "levels_used", "histogram" ("mean",
+// "variance", "skewness", "kurtosis", "median", "p10", "p90", "mode", "entropy", "uniformity" and "counts") and "glcm" and "glcm_axial"
+// (each "pairs", "joint_max", "joint_average", "joint_variance", "joint_entropy", "contrast", "dissimilarity", "inverse_difference",
+// "inverse_difference_moment", "angular_second_moment", "correlation"); a number that is not defined is null, and the member itself is
+// null for a component the volume filter dropped or one beyond the measured count.  One log line per batch; a failure is reported as
+// "Volume texture error: ..." and ends only this step: the report is then written without the member.  Off (the default), every
+// artefact and every log line is what it was.  false with a message: a negative channel, a mode that does not exist, levels outside
+// 2 .. 64, lo outside 0 .. 65535 or width outside 1 .. 65536.
+struct VolumeTexture {
+    bool on = false;
+    int channel = 0;
+    int mode = 0;                      // MI_UNET_VTEX_COUNT
+    int levels = 32;
+    int lo = 0;
+    int width = 1;
+};
+bool set_volume_texture(const VolumeTexture &texture);
+VolumeTexture get_volume_texture();
+
 // The scored stack per lesion (mi_unet_volume_match in include/mi_unet.h).  It acts only where set_volume's `on` and
 // set_truth_dir already produce volume_score.json.  Per target the truth stack, recoded by truth == cls, is labelled with
 // mi_unet_volume_components under the volume setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE; the pred ids

@@ -818,6 +818,84 @@ int mi_unet_volume_match_derive(const mi_unet_vmatch_side *pred_side, int mp, co
                                 const mi_unet_vmatch_pair *pairs, int found, int cap, const int32_t *match_of_pred /* [mp] */,
                                 mi_unet_vmatch_scores *out);
 
+/* ---- Volume texture: per component of a labelled stack its grey-level histogram and its 3-D co-occurrence tables ----------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  Everything up to
+ * mi_unet_volume_texture_derive is an exact integer count and independent of the order of evaluation.
+ * Input is ids, int32 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), intensity, uint16
+ * [D][H][W], and the number of components m; both buffers are required.
+ *   COMPONENT  as in mi_unet_volume_measure: component r, 0 <= r < m, is the set of voxels with ids == r + 1.  Every other value (0, -1,
+ *              anything above m) belongs to no component.  The stage does not ask whether a set is connected.  An id that no voxel
+ *              carries gives an all-zero entry and all-zero rows.
+ *   OPTIONS    opts = { mode, levels L, lo, width }; NULL is { MI_UNET_VTEX_COUNT, 32, 0, 1 }.  lo and width are read in
+ *              MI_UNET_VTEX_WIDTH only, and checked in both modes.
+ *   LEVEL      of a voxel of component r with value v, in integer arithmetic only:
+ *              MI_UNET_VTEX_COUNT (a fixed number of bins over the component's own range): with imin, imax over the component,
+ *                level = ((v - imin) * L) / (imax - imin + 1).  It is always below L; a constant component is all level 0.
+ *              MI_UNET_VTEX_WIDTH (a fixed bin size, one scale for all components): level = v < lo ? 0 : min(L - 1, (v - lo) / width).
+ *   TABLE      voxels; imin, imax over the component (in both modes); levels_used, the number of non-empty histogram bins; pairs and
+ *              pairs_axial, the sums of the two co-occurrence tables (0 for a table that was not asked for).
+ *   HIST       hist[r][l] is the number of voxels of r at level l.
+ *   GLCM       the 13 offsets d = (dx, dy, dz) are the lexicographically positive half of the 26-neighbourhood: dz = 1 with any dx, dy in
+ *              -1 .. 1, or dz = 0 and dy = 1 with any dx, or (1, 0, 0).  glcm[r][i][j] counts the ordered pairs (p, p + d) over those 13
+ *              offsets with both voxels inside the volume, both in component r, level(p) = i and level(p + d) = j.  glcm_axial counts
+ *              the same over the 4 offsets with dz = 0: the in-plane table a thick-slice series wants.  Either pointer may be NULL: that
+ *              table is not computed.  The tables are not symmetrised; mi_unet_volume_texture_derive does that (P = G + G^T), so the
+ *              counts stay the plain counts.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE (8192);
+ *   D * H * W <= 2^28: a voxel starts at most 13 pairs, so every cell is below 13 * 2^28 < 2^32 and is a uint32_t;
+ *   L in 2 .. MI_UNET_VTEX_MAX_LEVELS (64): a level and a component's number share one 32-bit key, and an L x L table fits a workgroup's LDS;
+ *   m in 1 .. MI_UNET_VOLUME_MAX_TABLE and m * L * L <= MI_UNET_VTEX_MAX_CELLS (2^22): 4096 components at 32 levels, 1024 at 64; a table
+ *           is at most 16 MiB;
+ *   width in 1 .. 65536 and lo in 0 .. 65535: the range of a uint16_t.
+ * mi_unet_volume_texture takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message that begins "mi_unet_volume_texture:", nothing
+ * queued and no output written: a null ids, intensity, table or hist; any limit broken; a mode that does not exist.  A workspace that
+ * cannot be allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_texture_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle,
+ * same bytes.
+ * mi_unet_volume_texture_derive is pure host arithmetic in double over one component's entry, its histogram row and one of its tables, with
+ * a fixed summation order (i ascending, then j ascending).  Levels are numbered 1 .. L in the formulas, as the IBSI numbers them.
+ *   From hist, with p_l = hist[l] / voxels and mu = sum l p_l:
+ *     mean = mu; variance = sum p_l (l - mu)^2; skewness = sum p_l (l - mu)^3 / variance^1.5 and kurtosis = sum p_l (l - mu)^4 /
+ *     variance^2 - 3 (the excess), both 0 when the variance is 0; median, p10 and p90 are the smallest level whose cumulative count reaches
+ *     ceil(q * voxels) for q = 1/2, 1/10, 9/10, in exact integers; mode is the fullest level, ties to the smallest; entropy = - sum p_l
+ *     log2 p_l; uniformity = sum p_l^2.
+ *   From one table G with its sum `pairs` (c->pairs for glcm, c->pairs_axial for glcm_axial: the function adds G up itself), with
+ *   p_ij = (G_ij + G_ji) / (2 pairs) and mu = sum i p_ij:
+ *     joint_max = max p_ij; joint_average = mu; joint_variance = sum (i - mu)^2 p_ij; joint_entropy = - sum p_ij log2 p_ij;
+ *     contrast = sum (i - j)^2 p_ij; dissimilarity = sum |i - j| p_ij; inverse_difference = sum p_ij / (1 + |i - j|);
+ *     inverse_difference_moment = sum p_ij / (1 + (i - j)^2); angular_second_moment = sum p_ij^2;
+ *     correlation = sum (i - mu)(j - mu) p_ij / joint_variance.
+ *   Every one of the ten is NaN when glcm is NULL or the table's sum is 0; correlation is NaN when joint_variance is 0.
+ * MI_UNET_EARG, output untouched: a null c, hist or out; voxels < 1; L outside 2 .. 64.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VTEX_COUNT 0
+#define MI_UNET_VTEX_WIDTH 1
+#define MI_UNET_VTEX_MAX_LEVELS 64
+#define MI_UNET_VTEX_MAX_CELLS 4194304          /* 2^22 */
+#define MI_UNET_VTEX_MAX_VOXELS 268435456       /* 2^28 */
+typedef struct mi_unet_vtexture_opts { int mode, levels, lo, width; } mi_unet_vtexture_opts;    /* default { MI_UNET_VTEX_COUNT, 32, 0, 1 } */
+typedef struct mi_unet_vtexture {      /* 32 bytes, no padding */
+    int32_t voxels, imin, imax;        /* voxels with this id; min / max of intensity over them */
+    int32_t levels_used;               /* non-empty histogram bins */
+    int64_t pairs, pairs_axial;        /* sums of glcm[r] and of glcm_axial[r]; 0 for a table that was not asked for */
+} mi_unet_vtexture;
+typedef struct mi_unet_vtexture_features {     /* 144 bytes, no padding */
+    double mean, variance, skewness, kurtosis, entropy, uniformity;
+    int32_t median, p10, p90, mode;    /* levels 1 .. L */
+    double joint_max, joint_average, joint_variance, joint_entropy, contrast, dissimilarity, inverse_difference,
+           inverse_difference_moment, angular_second_moment, correlation;
+} mi_unet_vtexture_features;
+int mi_unet_volume_texture(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const uint16_t *intensity /* [D][H][W] host */, int D,
+                           int H, int W, int m, const mi_unet_vtexture_opts *opts, mi_unet_vtexture *table /* [m] */,
+                           uint32_t *hist /* [m][L] */, uint32_t *glcm /* [m][L][L] or NULL */, uint32_t *glcm_axial /* [m][L][L] or NULL */);
+int mi_unet_volume_texture_host(const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const mi_unet_vtexture_opts *opts,
+                                mi_unet_vtexture *table, uint32_t *hist, uint32_t *glcm, uint32_t *glcm_axial);
+int mi_unet_volume_texture_derive(const mi_unet_vtexture *c, const uint32_t *hist /* [L] */, const uint32_t *glcm /* [L][L] or NULL */, int L,
+                                  mi_unet_vtexture_features *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -171,6 +171,12 @@ struct mi_unet {
     miunet::DeviceBuf<uint8_t> d_vmt;
     miunet::PinnedBuf<uint8_t> h_vmt;
     size_t vmt_dev_cap = 0, vmt_host_cap = 0;                                                          // bytes
+    // mi_unet_volume_texture: d_vtx = the keys (ids in place), the intensity, the ranges, the table, the histograms and
+    // the two co-occurrence tables of one call; h_vtx = the pinned staging of the two stacks and of the results; grown on demand, never
+    // shared with a clone
+    miunet::DeviceBuf<uint8_t> d_vtx;
+    miunet::PinnedBuf<uint8_t> h_vtx;
+    size_t vtx_dev_cap = 0, vtx_host_cap = 0;                                                          // bytes
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

@@ -16,6 +16,7 @@ struct mi_unet_mesh_vertex;
 struct mi_unet_vmeasure;
 struct mi_unet_vmatch_side;
 struct mi_unet_vmatch_pair;
+struct mi_unet_vtexture;
 
 namespace miunet {
 
@@ -435,5 +436,26 @@ hipError_t launch_volume_match_count(const int32_t *pred, const int32_t *truth, 
 hipError_t launch_volume_match_tables(const int32_t *table, const VolumeMatchArgs &a, ::mi_unet_vmatch_side *pred_side,
                                       ::mi_unet_vmatch_side *truth_side, int32_t *row_pairs, int32_t *row_first, int32_t *found,
                                       void *col_acc, ::mi_unet_vmatch_pair *pairs, int keep_pairs, hipStream_t s);
+
+// Volume texture (volume_texture.hip; include/mi_unet.h: mi_unet_volume_texture).  ids int32 [D][H][W] and intensity u16
+// [D][H][W] on the device; component r = { ids == r + 1 }, 0 <= r < m.  Every result is an integer sum, minimum or maximum: nothing
+// depends on the order in which atomics arrive.  No workgroup waits for another.
+//   launch_volume_texture_keys: zeroes range [m] and fills it with (65535 - imin, imax) (k_vtx_range), then k_vtx_keys turns
+//       ids IN PLACE into keys: (r + 1) << 8 | level for a voxel of component r, 0 for every other voxel.
+//   launch_volume_texture_pairs: zeroes hist [m][L], inter [m][L][L] and axial [m][L][L] over this call's extent, then k_vtx_pairs, the
+//       hot path: a workgroup takes VTX_TILES_PER_WG tiles of VTX_TZ x VTX_TY x VTX_TX voxels, each with its halo in LDS, counts its
+//       voxels into hist, the pairs of the 4 offsets with dz = 0 into axial (want & VTX_WANT_AXIAL) and those of the 9 with dz = 1 into
+//       inter (want & VTX_WANT_INTER).  The counts of the one component that leads a tile are kept in LDS and flushed when that
+//       component changes; lds_table = false sends every count to memory (the comparison of DESIGN.md 7.15).
+//   launch_volume_texture_finish: a workgroup per component: inter += axial (inter then holds the 13-offset table) when both are
+//       wanted, and table[r] = (voxels = the histogram's sum, imin, imax, levels_used, sum of inter, sum of axial).
+constexpr int VTX_TX = 64, VTX_TY = 8, VTX_TZ = 4, VTX_TILES_PER_WG = 8;
+constexpr int VTX_WANT_AXIAL = 1, VTX_WANT_INTER = 2;
+struct VolumeTextureArgs { int D = 0, H = 0, W = 0, m = 0, mode = 0, L = 32, lo = 0, width = 1; };
+hipError_t launch_volume_texture_keys(int32_t *ids, const uint16_t *intensity, const VolumeTextureArgs &a, int2 *range, hipStream_t s);
+hipError_t launch_volume_texture_pairs(const int32_t *keys, const VolumeTextureArgs &a, int want, bool lds_table, uint32_t *hist,
+                                       uint32_t *inter, uint32_t *axial, hipStream_t s);
+hipError_t launch_volume_texture_finish(const int2 *range, const VolumeTextureArgs &a, int want, const uint32_t *hist, uint32_t *inter,
+                                        const uint32_t *axial, ::mi_unet_vtexture *table, hipStream_t s);
 
 }  // namespace miunet

@@ -206,6 +206,15 @@ void medseg_get_volume_measure(int *on, int *channel, int *max_ends)
     const MedicalSeg::VolumeMeasure m = MedicalSeg::get_volume_measure();
     *on = m.on; *channel = m.channel; *max_ends = m.max_ends;
 }
+int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width)
+{
+    return MedicalSeg::set_volume_texture({ on != 0, channel, mode, levels, lo, width }) ? 0 : 1;
+}
+void medseg_get_volume_texture(int *on, int *channel, int *mode, int *levels, int *lo, int *width)
+{
+    const MedicalSeg::VolumeTexture t = MedicalSeg::get_volume_texture();
+    *on = t.on; *channel = t.channel; *mode = t.mode; *levels = t.levels; *lo = t.lo; *width = t.width;
+}
 int medseg_set_volume_match(int on, int iou_num, int iou_den) { return MedicalSeg::set_volume_match({ on != 0, iou_num, iou_den }) ? 0 : 1; }
 void medseg_get_volume_match(int *on, int *iou_num, int *iou_den)
 {

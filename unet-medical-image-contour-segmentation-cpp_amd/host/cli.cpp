@@ -150,6 +150,7 @@ public:
         table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
         table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
+        table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volmatch"] = [this](const Words &w) { cmd_volmatch(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
@@ -172,6 +173,7 @@ public:
             "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
             "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
+            "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volmatch on [iou N/D]|off     - With volume on and truth: components matched to truth components, detection F1 and PQ per target",
             "  exit                          - Cleanup and exit",
             "",
@@ -473,6 +475,46 @@ private:
         }
         const MedicalSeg::VolumeMeasure cur = MedicalSeg::get_volume_measure();
         std::cout << "Volume measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " ends " << cur.max_ends << std::endl;
+    }
+
+    // voltexture on [levels N] [count | width W [lo L]] [channel N] | voltexture off | voltexture (prints the setting in force)
+    void cmd_voltexture(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeTexture t;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            t.on = w[1] == "on";
+            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
+            for (size_t i = 2; ok && i < w.size();) {
+                if (w[i] == "count") {
+                    ok = !binned;
+                    binned = true;
+                    i += 1;
+                    continue;
+                }
+                int value = 0;
+                ok = i + 1 < w.size() && to_int(w[i + 1], value);
+                if (!ok) break;
+                if (w[i] == "levels") t.levels = value;
+                else if (w[i] == "channel") t.channel = value;
+                else if (w[i] == "width" && !binned) { t.mode = MI_UNET_VTEX_WIDTH; t.width = value; binned = true; }
+                else if (w[i] == "lo" && t.mode == MI_UNET_VTEX_WIDTH) t.lo = value;
+                else ok = false;
+                i += 2;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid voltexture command (expected on [levels N] [count|width W [lo L]] [channel N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_texture(t)) {
+                std::cerr << "Volume texture unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeTexture cur = MedicalSeg::get_volume_texture();
+        std::cout << "Volume texture: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
+        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo << std::endl;
+        else std::cout << "count" << std::endl;
     }
 
     // volmatch on [iou N/D] | volmatch off | volmatch (prints the setting in force)

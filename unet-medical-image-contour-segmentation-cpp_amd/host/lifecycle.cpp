@@ -365,6 +365,25 @@ bool set_volume_measure(const VolumeMeasure &measure)
         /*handle_side=*/false);
 }
 
+bool set_volume_texture(const VolumeTexture &texture)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_texture = texture;
+            if (texture.channel < 0) return std::string("volume texture: the channel is not negative");
+            if (texture.mode != MI_UNET_VTEX_COUNT && texture.mode != MI_UNET_VTEX_WIDTH)
+                return std::string("volume texture: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
+            if (texture.levels < 2 || texture.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume texture: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
+            if (texture.lo < 0 || texture.lo > 65535) return std::string("volume texture: lo is 0 .. 65535");
+            return std::string(texture.width >= 1 && texture.width <= 65536 ? "" : "volume texture: width is 1 .. 65536");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume texture: " << (texture.on ? "on" : "off") << ", channel " << texture.channel << ", levels " << texture.levels << ", "
+               << (texture.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(texture.width) + " lo " + std::to_string(texture.lo) : std::string("count"));
+        },
+        /*handle_side=*/false);
+}
+
 bool set_volume_match(const VolumeMatch &match)
 {
     return change_setting(
@@ -398,6 +417,7 @@ Volume get_volume() { return current_settings().volume; }
 VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
+VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeMatch get_volume_match() { return current_settings().volume_match; }
 
 std::ofstream &get_log_file() { return g_log_file; }

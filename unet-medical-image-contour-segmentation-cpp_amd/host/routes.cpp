@@ -517,9 +517,12 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
 // ---- set_volume: the images of a batch as the slices of one volume.  process_images_targets fills the stack as its images finish;
 // label_volume runs once, behind the last device call of the batch.
 struct VolumeStack {
-    // channel >= 0 (set_volume_measure): the stack also keeps that channel of every slice's normalised tile
-    VolumeStack(size_t slices, size_t targets, size_t hw, int channel = -1)
-        : planes(targets * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0), bases(slices), names(slices), D(slices), hw(hw), channel(channel)
+    // channel >= 0 (set_volume_measure): the stack also keeps that channel of every slice's normalised tile; texture_channel >= 0
+    // (set_volume_texture) likewise, in a stack of its own only when the two channels differ
+    VolumeStack(size_t slices, size_t targets, size_t hw, int channel = -1, int texture_channel = -1)
+        : planes(targets * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0),
+          texture_own(texture_channel >= 0 && texture_channel != channel ? slices * hw : 0, 0), bases(slices), names(slices), D(slices), hw(hw),
+          channel(channel), texture_channel(texture_channel)
     {
     }
     // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t; `tile` is its normalised
@@ -529,13 +532,17 @@ struct VolumeStack {
         for (size_t t = 0; t < K; ++t) std::copy(pictures + t * hw, pictures + (t + 1) * hw, planes.begin() + (t * D + i) * hw);
         if (channel >= 0 && (size_t)channel < C)
             for (size_t p = 0; p < hw; ++p) intensity[i * hw + p] = tile[p * C + (size_t)channel];
+        if (!texture_own.empty() && (size_t)texture_channel < C)
+            for (size_t p = 0; p < hw; ++p) texture_own[i * hw + p] = tile[p * C + (size_t)texture_channel];
         bases[i] = base;
     }
+    const uint16_t *texture_intensity() const { return texture_own.empty() ? intensity.data() : texture_own.data(); }
     std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
     std::vector<uint16_t> intensity;                   // [D][H][W] or empty: the measured channel of the normalised tiles, widened
+    std::vector<uint16_t> texture_own;                 // [D][H][W] or empty: the texture's channel where it is not the measured one
     std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
     size_t D, hw;
-    int channel;
+    int channel, texture_channel;
 };
 
 // set_volume_clean: every target's plane of the stack through one mi_unet_volume_clean call with values = { 255 } on `h`
@@ -712,6 +719,79 @@ std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, cons
     }
 }
 
+// set_volume_texture: per target one mi_unet_volume_texture call on `h` (mi_unet_volume_texture_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's texture channel, with m = min(found, cap, 2^22 / levels^2), then
+// mi_unet_volume_texture_derive of every row and of both its tables.  Returns, per target and table row, the "texture" member of the row's
+// component object in volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
+std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
+                                                     size_t cap, const std::vector<mi_unet_target> &targets, const VolumeTexture &texture,
+                                                     mi_unet_t *h, std::ostream &lg)
+{
+    try {
+        const size_t K = targets.size(), D = st.D, hw = st.hw, L = (size_t)texture.levels;
+        if (texture.channel >= g_cfg.in_ch)
+            throw std::runtime_error("channel " + std::to_string(texture.channel) + " of " + std::to_string(g_cfg.in_ch));
+        const mi_unet_vtexture_opts opts{ texture.mode, texture.levels, texture.lo, texture.width };
+        const bool device = h && device_postprocess_requested();
+        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * L);
+        std::vector<std::vector<std::string>> members(K);
+        size_t cut = 0;                                         // components beyond the measured count, over all targets
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const size_t rows = std::min<size_t>((size_t)found[t], cap);
+            const int m = (int)std::min(rows, most);
+            if (m < 1) continue;
+            cut += rows - (size_t)m;
+            std::vector<mi_unet_vtexture> table((size_t)m);
+            std::vector<uint32_t> hist((size_t)m * L), glcm((size_t)m * L * L), axial((size_t)m * L * L);
+            const int32_t *const in = ids.data() + t * D * hw;
+            const int rc = device ? mi_unet_volume_texture(h, in, st.texture_intensity(), (int)D, g_cfg.height, g_cfg.width, m, &opts, table.data(),
+                                                           hist.data(), glcm.data(), axial.data())
+                                  : mi_unet_volume_texture_host(in, st.texture_intensity(), (int)D, g_cfg.height, g_cfg.width, m, &opts, table.data(),
+                                                                hist.data(), glcm.data(), axial.data());
+            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
+            for (size_t r = 0; r < rows; ++r) {
+                if (r >= (size_t)m || table[r].voxels < 1) {    // beyond the measured count, or dropped by the volume filter: no voxel carries its id
+                    members[t].push_back(", \"texture\": null");
+                    continue;
+                }
+                const mi_unet_vtexture &c = table[r];
+                mi_unet_vtexture_features f{}, fa{};
+                if (mi_unet_volume_texture_derive(&c, hist.data() + r * L, glcm.data() + r * L * L, (int)L, &f) != MI_UNET_OK ||
+                    mi_unet_volume_texture_derive(&c, hist.data() + r * L, axial.data() + r * L * L, (int)L, &fa) != MI_UNET_OK)
+                    throw std::runtime_error(mi_unet_last_error());
+                std::ostringstream js;
+                js << ", \"texture\": {\"levels\": " << L << ", \"mode\": \"" << (texture.mode == MI_UNET_VTEX_WIDTH ? "width" : "count")
+                   << "\", \"range\": [" << c.imin << ", " << c.imax << "], \"levels_used\": " << c.levels_used << ", \"histogram\": {\"mean\": "
+                   << json_number(f.mean) << ", \"variance\": " << json_number(f.variance) << ", \"skewness\": " << json_number(f.skewness) << ", \"kurtosis\": "
+                   << json_number(f.kurtosis) << ", \"median\": " << f.median << ", \"p10\": " << f.p10 << ", \"p90\": " << f.p90 << ", \"mode\": "
+                   << f.mode << ", \"entropy\": " << json_number(f.entropy) << ", \"uniformity\": " << json_number(f.uniformity) << ", \"counts\": [";
+                for (size_t l = 0; l < L; ++l) js << (l ? ", " : "") << hist[r * L + l];
+                js << "]}";
+                auto joint = [&](const char *key, int64_t pairs, const mi_unet_vtexture_features &g) {
+                    js << ", \"" << key << "\": {\"pairs\": " << pairs << ", \"joint_max\": " << json_number(g.joint_max) << ", \"joint_average\": "
+                       << json_number(g.joint_average) << ", \"joint_variance\": " << json_number(g.joint_variance) << ", \"joint_entropy\": "
+                       << json_number(g.joint_entropy) << ", \"contrast\": " << json_number(g.contrast) << ", \"dissimilarity\": " << json_number(g.dissimilarity)
+                       << ", \"inverse_difference\": " << json_number(g.inverse_difference) << ", \"inverse_difference_moment\": "
+                       << json_number(g.inverse_difference_moment) << ", \"angular_second_moment\": " << json_number(g.angular_second_moment)
+                       << ", \"correlation\": " << json_number(g.correlation) << "}";
+                };
+                joint("glcm", c.pairs, f);
+                joint("glcm_axial", c.pairs_axial, fa);
+                js << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume texture: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
+        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels; " << cut << " not measured)";
+        lg << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume texture error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -719,13 +799,15 @@ std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, cons
 // is active (without one they are the cleaned stack itself).  With `mesh` on, the planes that were labelled -- `out` under a filter, else
 // the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".  With `measure` on, the components
 // stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member "measure".  With
+// `texture` on, the ids are handed out likewise and every component object gains a last member "texture" (texture_volume).  With
 // `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays empty after a failure.
 struct VolumeIds {
     std::vector<int32_t> ids, found;
 };
 void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
                   std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string(),
-                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure(), VolumeIds *numbered = nullptr)
+                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure(), VolumeIds *numbered = nullptr,
+                  const VolumeTexture &texture = VolumeTexture())
 {
     filtered.clear();
     try {
@@ -733,7 +815,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(measure.on || numbered ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(measure.on || texture.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const bool device = h && device_postprocess_requested();
@@ -752,6 +834,8 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
         const std::string mesh_json = mesh.on ? mesh_volume(filter ? out.data() : st.planes.data(), D, hw, targets, v, mesh, h, output_dir, lg) : std::string();
         const std::vector<std::vector<std::string>> measured =
             measure.on ? measure_volume(st, ids, found, cap, targets, v, measure, h, lg) : std::vector<std::vector<std::string>>();
+        const std::vector<std::vector<std::string>> textured =
+            texture.on ? texture_volume(st, ids, found, cap, targets, texture, h, lg) : std::vector<std::vector<std::string>>();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -783,7 +867,7 @@ void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targ
                    << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
-                   << "}";
+                   << (textured.empty() ? std::string() : textured[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]}";
         }
@@ -1080,7 +1164,8 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         if (settings.volume.on && n > 0) {                     // the paths are the slices of one volume, whatever the target list is
             std::lock_guard<std::mutex> lk(g_batch_mutex);
             Collected lg{ log_file, {} };
-            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width, settings.volume_measure.on ? settings.volume_measure.channel : -1);
+            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width, settings.volume_measure.on ? settings.volume_measure.channel : -1,
+                              settings.volume_texture.on ? settings.volume_texture.channel : -1);
             for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
             ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
             std::vector<uint8_t> filtered;
@@ -1091,7 +1176,7 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
             const bool match = settings.volume_match.on && !settings.truth_dir.empty();
             VolumeIds numbered;
             label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json,
-                         settings.volume_mesh, settings.volume_measure, match ? &numbered : nullptr);
+                         settings.volume_mesh, settings.volume_measure, match ? &numbered : nullptr, settings.volume_texture);
             if (!settings.truth_dir.empty())
                 score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
                                    lg.text, settings.volume_match, numbered);

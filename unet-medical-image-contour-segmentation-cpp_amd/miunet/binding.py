@@ -39,6 +39,7 @@ EXPORTS = [
     "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
     "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
+    "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
 ]
 
@@ -345,6 +346,53 @@ def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
     return table
 
 
+class VTextureOpts(C.Structure):
+    """mi_unet_vtexture_opts; the default is { VTEX_COUNT, 32, 0, 1 }"""
+    _fields_ = [("mode", C.c_int), ("levels", C.c_int), ("lo", C.c_int), ("width", C.c_int)]
+
+
+class VTexture(C.Structure):
+    """mi_unet_vtexture: 32 bytes, four int32 then two int64; VTEXTURE_DTYPE is the same layout for numpy"""
+    _fields_ = ([(n, C.c_int32) for n in ("voxels", "imin", "imax", "levels_used")] + [(n, C.c_int64) for n in ("pairs", "pairs_axial")])
+
+
+class VTextureFeatures(C.Structure):
+    _fields_ = ([(n, C.c_double) for n in ("mean", "variance", "skewness", "kurtosis", "entropy", "uniformity")] +
+                [(n, C.c_int32) for n in ("median", "p10", "p90", "mode")] +
+                [(n, C.c_double) for n in ("joint_max", "joint_average", "joint_variance", "joint_entropy", "contrast", "dissimilarity",
+                                           "inverse_difference", "inverse_difference_moment", "angular_second_moment", "correlation")])
+
+
+VTEXTURE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VTexture._fields_])
+VTEX_MODES = {"count": 0, "width": 1}       # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
+VTEX_MAX_LEVELS = 64
+VTEX_MAX_CELLS = 1 << 22
+
+
+def _volume_texture_call(fn, head, ids, intensity, m, levels, mode, lo, width, want):
+    """mi_unet_volume_texture (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape, m components, levels / mode ("count", "width" or the number) / lo / width = the options, want = which of "glcm" and
+    "axial" to compute -> (table VTEXTURE_DTYPE [m], hist u32 [m, L], glcm u32 [m, L, L] or None, glcm_axial or None).  The library
+    checks the values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    d, hh, ww = ids.shape
+    rows, lv = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS)
+    if rows * lv * lv > 2 * VTEX_MAX_CELLS:
+        rows = 1                                                 # (refused by the library; no need for the memory)
+    table = np.zeros(rows, VTEXTURE_DTYPE)
+    hist = np.zeros((rows, lv), np.uint32)
+    glcm = np.zeros((rows, lv, lv), np.uint32) if "glcm" in want else None
+    axial = np.zeros((rows, lv, lv), np.uint32) if "axial" in want else None
+    opts = VTextureOpts(int(VTEX_MODES.get(mode, mode)), int(levels), int(lo), int(width))
+    _check(fn(*head, _ptr(ids), _ptr(intensity), d, hh, ww, int(m), C.byref(opts), _ptr(table), _ptr(hist), _ptr(glcm), _ptr(axial)))
+    return table, hist, glcm, axial
+
+
 class VMatchCounts(C.Structure):
     _fields_ = [("tp", C.c_int32), ("fp", C.c_int32), ("fn", C.c_int32)]
 
@@ -559,6 +607,10 @@ def lib():
         L.mi_unet_volume_measure_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_measure.argtypes = [C.c_void_p] + L.mi_unet_volume_measure_host.argtypes
         L.mi_unet_volume_measure_derive.argtypes = [C.POINTER(VMeasure), C.c_void_p, C.c_double, C.POINTER(VMeasureShape)]
+        L.mi_unet_volume_texture_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
+        L.mi_unet_volume_texture_derive.argtypes = [C.POINTER(VTexture), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VTextureFeatures)]
         L.mi_unet_volume_match_host.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
         L.mi_unet_volume_match.argtypes = [C.c_void_p] + L.mi_unet_volume_match_host.argtypes
         L.mi_unet_volume_match_assign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -965,6 +1017,13 @@ class Engine:
         one; cap = an int or (cap_verts, cap_quads) makes one call and trims to min(count, cap); raw=True returns the untrimmed arrays"""
         return _volume_mesh_call(lib().mi_unet_volume_mesh, (self._h,), masks, values, placement, cap, raw)
 
+    # ---- the texture of the components of a labelled stack (mi_unet_volume_texture): needs the device, not the weights
+    def volume_texture(self, ids, intensity, m, levels=32, mode="count", lo=0, width=1, want=("glcm", "axial")):
+        """ids int32 [D,H,W], intensity u16 [D,H,W], m components -> (table VTEXTURE_DTYPE [m], hist u32 [m, levels], glcm u32
+        [m, levels, levels] or None, glcm_axial or None): per component its grey-level histogram and its 3-D co-occurrence counts over
+        the 13 forward neighbours and over the 4 in-plane ones (include/mi_unet.h)"""
+        return _volume_texture_call(lib().mi_unet_volume_texture, (self._h,), ids, intensity, m, levels, mode, lo, width, want)
+
     # ---- the components of a labelled stack measured (mi_unet_volume_measure): needs the device, not the weights
     def volume_measure(self, ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
         """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W] or None, m = the components
@@ -1120,6 +1179,24 @@ def volume_mesh_host(masks, values, placement="faces", cap=None, raw=False):
 def volume_measure_host(ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
     """mi_unet_volume_measure_host: Engine.volume_measure as sequential host arithmetic (needs no device)"""
     return _volume_measure_call(lib().mi_unet_volume_measure_host, (), ids, intensity, m, units, max_ends)
+
+
+def volume_texture_host(ids, intensity, m, levels=32, mode="count", lo=0, width=1, want=("glcm", "axial")):
+    """mi_unet_volume_texture_host: Engine.volume_texture as sequential host arithmetic (needs no device)"""
+    return _volume_texture_call(lib().mi_unet_volume_texture_host, (), ids, intensity, m, levels, mode, lo, width, want)
+
+
+def volume_texture_derive(comp, hist, glcm=None):
+    """mi_unet_volume_texture_derive of one component (a VTexture, or one VTEXTURE_DTYPE record), its histogram row u32 [L] and one of its
+    co-occurrence tables u32 [L, L] (or None: the ten joint features are NaN) -> a dict of the features"""
+    if not isinstance(comp, VTexture):
+        comp = VTexture(**{n: int(comp[n]) for n, _ in VTexture._fields_})
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if glcm is not None:
+        glcm = np.ascontiguousarray(glcm, np.uint32).reshape(hist.size, hist.size)
+    out = VTextureFeatures()
+    _check(lib().mi_unet_volume_texture_derive(C.byref(comp), _ptr(hist), _ptr(glcm), int(hist.size), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VTextureFeatures._fields_}
 
 
 def volume_measure_derive(comp, units, unit_mm):

@@ -23,7 +23,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
            "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
-           "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match"]
+           "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
+           "medseg_set_volume_texture", "medseg_get_volume_texture"]
 
 
 def lib():
@@ -86,6 +87,9 @@ def lib():
         L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_match.argtypes = [_i, _i, _i]
         L.medseg_get_volume_match.restype = None
+        L.medseg_set_volume_texture.argtypes = [C.c_int] * 6
+        L.medseg_get_volume_texture.argtypes = [_i] * 6
+        L.medseg_get_volume_texture.restype = None
         _LIB = L
     return _LIB
 
@@ -257,6 +261,24 @@ def get_volume_measure():
     on, channel, ends = C.c_int(), C.c_int(), C.c_int()
     lib().medseg_get_volume_measure(C.byref(on), C.byref(channel), C.byref(ends))
     return {"on": bool(on.value), "channel": channel.value, "max_ends": ends.value}
+
+
+VTEX_MODES = ("count", "width")            # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
+
+
+def set_volume_texture(on=True, channel=0, mode="count", levels=32, lo=0, width=1) -> bool:
+    """MedicalSeg::set_volume_texture: with set_volume on, process_image_batch adds the grey-level histogram and the co-occurrence
+    texture of every component of the labelled stack (mi_unet_volume_texture over `channel` of the normalised tiles) as a "texture"
+    member of volume_report.json; needs no engine"""
+    mode = VTEX_MODES.index(mode) if mode in VTEX_MODES else int(mode)
+    return lib().medseg_set_volume_texture(int(bool(on)), int(channel), mode, int(levels), int(lo), int(width)) == 0
+
+
+def get_volume_texture():
+    v = [C.c_int() for _ in range(6)]
+    lib().medseg_get_volume_texture(*[C.byref(x) for x in v])
+    on, channel, mode, levels, lo, width = (x.value for x in v)
+    return {"on": bool(on), "channel": channel, "mode": VTEX_MODES[mode], "levels": levels, "lo": lo, "width": width}
 
 
 def set_volume_match(on=True, iou=(1, 2)) -> bool:
