@@ -1,6 +1,6 @@
-// The host half of the scores against ground truth (csrc/score.cpp with MIUNET_SCORE_NO_DEVICE: mi_unet_score_labels_host and
+// The host half of the scores against ground truth (csrc/score.cpp with MIUNET_NO_DEVICE: mi_unet_score_labels_host and
 // mi_unet_score_derive) as a stand-alone program, so that it can run under -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_SCORE_NO_DEVICE score_host_test.cpp <csrc>/score.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE score_host_test.cpp <csrc>/score.cpp
 // Cases: 33 x 70 (odd sizes) with two values and the confusion matrix, the three empty-set cases, a refused call.  The numbers are
 // checked against facts that hold by construction; tests/test_score_cpu.py compares the same entry points with the reference.
 #include <cmath>

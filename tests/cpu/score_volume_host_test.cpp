@@ -1,7 +1,7 @@
-// The host half of the scores of a volume (csrc/score_volume.cpp and csrc/score.cpp with MIUNET_SCORE_NO_DEVICE:
+// The host half of the scores of a volume (csrc/score_volume.cpp and csrc/score.cpp with MIUNET_NO_DEVICE:
 // mi_unet_score_volume_host, mi_unet_score_volume_units, mi_unet_score_volume_derive) as a stand-alone program, so that it can run under
 // -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_SCORE_NO_DEVICE score_volume_host_test.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE score_volume_host_test.cpp
 //       <csrc>/score_volume.cpp <csrc>/score.cpp          (one command)
 // Cases: two boxes in 7 x 33 x 70 (odd sizes) under an anisotropic spacing with the confusion matrix, one slice, one row, one column of
 // slices, the empty-set cases, the unit helper, derive, refused calls.  The numbers are checked against facts that hold by construction;

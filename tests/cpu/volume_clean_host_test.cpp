@@ -1,6 +1,6 @@
-// The host half of the volume clean-up (csrc/volume_clean.cpp with MIUNET_VOLUME_CLEAN_NO_DEVICE: mi_unet_volume_clean_host and
+// The host half of the volume clean-up (csrc/volume_clean.cpp with MIUNET_NO_DEVICE: mi_unet_volume_clean_host and
 // mi_unet_volume_ball) as a stand-alone program, so that it can run under -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_CLEAN_NO_DEVICE volume_clean_host_test.cpp <csrc>/volume_clean.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_clean_host_test.cpp <csrc>/volume_clean.cpp
 // Cases: 7 x 9 x 11 (odd sizes) with a closed shell and a speck under two values, the fill, a close and an open by an anisotropic ball
 // whose half-widths pass the sides, out aliasing masks, one slice, one voxel, the largest radius, the ball itself, a refused call.
 // The numbers are checked against facts that hold by construction; tests/test_volume_clean_cpu.py compares the same entry points

@@ -1,6 +1,6 @@
-// The host half of the volume components (csrc/volume.cpp with MIUNET_VOLUME_NO_DEVICE: mi_unet_volume_components_host and
+// The host half of the volume components (csrc/volume.cpp with MIUNET_NO_DEVICE: mi_unet_volume_components_host and
 // mi_unet_volume_derive) as a stand-alone program, so that it can run under -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_NO_DEVICE volume_host_test.cpp <csrc>/volume.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_host_test.cpp <csrc>/volume.cpp
 // Cases: 5 x 9 x 13 (odd sizes) with two values, three connectivities, a filter, a table shorter than the plane, out aliasing masks, the
 // empty volume, a refused call.  The numbers are checked against facts that hold by construction; tests/test_volume_cpu.py compares the
 // same entry points with the reference.

@@ -1,7 +1,7 @@
-// The host half of the volume matching (csrc/volume_match.cpp with MIUNET_VOLUME_MATCH_NO_DEVICE: mi_unet_volume_match_host,
+// The host half of the volume matching (csrc/volume_match.cpp with MIUNET_NO_DEVICE: mi_unet_volume_match_host,
 // mi_unet_volume_match_assign and mi_unet_volume_match_derive) as a stand-alone program, so that it can run under
 // -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_MATCH_NO_DEVICE volume_match_host_test.cpp <csrc>/volume_match.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_match_host_test.cpp <csrc>/volume_match.cpp
 // Cases: 3 x 5 x 9 (odd sizes) with two pred and three truth components, the last voxel of the volume and ids that belong to no
 // component; exact-size buffers (an overrun is the sanitizer's to find); a short, an exact and a long pair list; m = 4096 on both sides;
 // the assignment on both sides of a threshold and its scores; refused calls.  The numbers are checked against facts that hold by

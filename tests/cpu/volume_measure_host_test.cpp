@@ -1,6 +1,6 @@
-// The host half of the volume measurement (csrc/volume_measure.cpp with MIUNET_VOLUME_MEASURE_NO_DEVICE: mi_unet_volume_measure_host and
+// The host half of the volume measurement (csrc/volume_measure.cpp with MIUNET_NO_DEVICE: mi_unet_volume_measure_host and
 // mi_unet_volume_measure_derive) as a stand-alone program, so that it can run under -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_MEASURE_NO_DEVICE volume_measure_host_test.cpp <csrc>/volume_measure.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_measure_host_test.cpp <csrc>/volume_measure.cpp
 // Cases: 5 x 7 x 9 (odd sizes) with a box, a bar that reaches both ends of a row, the last voxel of the volume and ids that belong to no
 // component; exact-size buffers (an overrun is the sanitizer's to find); with and without intensity; the cap; m = 4096; the derived
 // shape; refused calls.  The numbers are checked against facts that hold by construction; tests/test_volume_measure_cpu.py compares the

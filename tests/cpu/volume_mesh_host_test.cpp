@@ -1,7 +1,7 @@
-// The host half of the volume mesh (csrc/volume_mesh.cpp with MIUNET_VOLUME_MESH_NO_DEVICE: mi_unet_volume_mesh_host,
+// The host half of the volume mesh (csrc/volume_mesh.cpp with MIUNET_NO_DEVICE: mi_unet_volume_mesh_host,
 // mi_unet_volume_mesh_positions and mi_unet_volume_mesh_derive) as a stand-alone program, so that it can run under
 // -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_MESH_NO_DEVICE volume_mesh_host_test.cpp <csrc>/volume_mesh.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_mesh_host_test.cpp <csrc>/volume_mesh.cpp
 // Cases: 5 x 7 x 9 (odd sizes) with a box, a voxel that touches it along an edge and the last voxel of the volume under a second value;
 // both placements, exact-size arrays (an overrun is the sanitizer's to find), caps at half, the counting call, one voxel that is the whole
 // volume, the metrics, refused calls.  The numbers are checked against facts that hold by construction; tests/test_volume_mesh_cpu.py

@@ -1,6 +1,6 @@
-// The host half of the volume texture (csrc/volume_texture.cpp with MIUNET_VOLUME_TEXTURE_NO_DEVICE: mi_unet_volume_texture_host and
+// The host half of the volume texture (csrc/volume_texture.cpp with MIUNET_NO_DEVICE: mi_unet_volume_texture_host and
 // mi_unet_volume_texture_derive) as a stand-alone program, so that it can run under -fsanitize=address,undefined on a CPU:
-//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_VOLUME_TEXTURE_NO_DEVICE volume_texture_host_test.cpp <csrc>/volume_texture.cpp
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DMIUNET_NO_DEVICE volume_texture_host_test.cpp <csrc>/volume_texture.cpp
 // Cases: Haralick's 4 x 4 image as a 4 x 1 x 4 volume; 5 x 7 x 9 (odd sizes) with a box, a row that reaches both ends, the last voxel of
 // the volume and ids that belong to no component; exact-size buffers (an overrun is the sanitizer's to find); both modes; either table
 // NULL; the caps; the derived features; refused calls.  The numbers are checked against facts that hold by construction;

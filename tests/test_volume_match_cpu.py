@@ -239,7 +239,7 @@ def test_host_half_as_a_stand_alone_program(tmp_path):
     form in which the host half runs under -fsanitize=address,undefined (the command is in the program's header); here it is built
     without"""
     exe = tmp_path / "volume_match_host_test"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_VOLUME_MATCH_NO_DEVICE", "-o", str(exe),
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_NO_DEVICE", "-o", str(exe),
                            os.path.join(ROOT, "tests", "cpu", "volume_match_host_test.cpp"), os.path.join(PKG, "csrc", "volume_match.cpp")])
     r = subprocess.run([str(exe)], capture_output=True, timeout=120)
     assert r.returncode == 0 and b"volume_match_host_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]

@@ -211,7 +211,7 @@ def test_host_half_as_a_stand_alone_program(tmp_path):
     the form in which the host half runs under -fsanitize=address,undefined (the command is in the program's header); here it is
     built without"""
     exe = tmp_path / "volume_measure_host_test"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_VOLUME_MEASURE_NO_DEVICE", "-o", str(exe),
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DMIUNET_NO_DEVICE", "-o", str(exe),
                            os.path.join(ROOT, "tests", "cpu", "volume_measure_host_test.cpp"), os.path.join(PKG, "csrc", "volume_measure.cpp")])
     r = subprocess.run([str(exe)], capture_output=True, timeout=120)
     assert r.returncode == 0 and b"volume_measure_host_test ok" in r.stdout, r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:]

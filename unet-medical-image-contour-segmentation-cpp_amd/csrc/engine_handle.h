@@ -48,6 +48,33 @@ struct Buffer {
 template <class T> using DeviceBuf = Buffer<T, false>;
 template <class T> using PinnedBuf = Buffer<T, true>;
 
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }      // the parts of a workspace start on 256-byte boundaries
+
+// A stage's device buffer and its pinned staging, in bytes: grown on demand, owned by the handle, never shared with a clone.
+struct Workspace {
+    DeviceBuf<uint8_t> d;
+    PinnedBuf<uint8_t> p;
+    size_t dev_cap = 0, host_cap = 0;
+    // at least dev_need / host_need bytes; whatever `s` still runs on the old memory completes before it is freed.  A failed allocation
+    // leaves that side empty with a cap of 0
+    int reserve(size_t dev_need, size_t host_need, hipStream_t s)
+    {
+        if (dev_need <= dev_cap && host_need <= host_cap) return MI_UNET_OK;
+        HIP_TRY(hipStreamSynchronize(s));
+        if (dev_need > dev_cap) {
+            dev_cap = 0;
+            HIP_TRY(d.reset(dev_need));
+            dev_cap = dev_need;
+        }
+        if (host_need > host_cap) {
+            host_cap = 0;
+            HIP_TRY(p.reset(host_need));
+            host_cap = host_need;
+        }
+        return MI_UNET_OK;
+    }
+};
+
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;
@@ -138,45 +165,20 @@ struct mi_unet {
     std::vector<int32_t> last_region_counts;
     int last_region_planes = 0, last_region_cap = 0;
     bool last_regions_valid = false;
-    // mi_unet_score_labels and mi_unet_score_volume (7.10): d_score = both maps, the scores and the kernels' workspace of
-    // one call; h_score = the pinned staging of the maps and of the results; grown on demand, never shared with a clone.  Either call ends
-    // with a host synchronisation, so the two stages take turns on it
-    miunet::DeviceBuf<uint8_t> d_score;
-    miunet::PinnedBuf<uint8_t> h_score;
-    size_t score_dev_cap = 0, score_host_cap = 0;   // bytes
-    // mi_unet_volume_components: d_volume = the volume, out, ids, the table, the counts and the kernels' workspace of one
-    // call; h_volume = the pinned staging of the volume and of the results; grown on demand, never shared with a clone
-    miunet::DeviceBuf<uint8_t> d_volume;
-    miunet::PinnedBuf<uint8_t> h_volume;
-    size_t volume_dev_cap = 0, volume_host_cap = 0; // bytes
-    // mi_unet_volume_clean: d_vclean = the volume, out, the counts and the kernels' workspace of one call; h_vclean =
-    // the pinned staging of the volume and of the results; grown on demand, never shared with a clone
-    miunet::DeviceBuf<uint8_t> d_vclean;
-    miunet::PinnedBuf<uint8_t> h_vclean;
-    size_t vclean_dev_cap = 0, vclean_host_cap = 0; // bytes
-    // mi_unet_volume_mesh: d_vmesh = the volume, the counts and the kernels' workspace of one call; h_vmesh = the pinned
-    // staging of the volume and of the counts; d_vmesh_out / h_vmesh_out = the kept vertices and quads of one plane, sized by its counts;
-    // grown on demand, never shared with a clone
-    miunet::DeviceBuf<uint8_t> d_vmesh, d_vmesh_out;
-    miunet::PinnedBuf<uint8_t> h_vmesh, h_vmesh_out;
-    size_t vmesh_dev_cap = 0, vmesh_host_cap = 0, vmesh_out_dev_cap = 0, vmesh_out_host_cap = 0;    // bytes
-    // mi_unet_volume_measure: d_vms = ids, intensity, the table and the per-component arrays of one call; h_vms = their
-    // pinned staging; d_vms_pts = the run ends of the searched components and the work list of the pair search, sized once the ends are
-    // counted; h_vms_pts = the work list's staging; grown on demand, never shared with a clone
-    miunet::DeviceBuf<uint8_t> d_vms, d_vms_pts;
-    miunet::PinnedBuf<uint8_t> h_vms, h_vms_pts;
-    size_t vms_dev_cap = 0, vms_host_cap = 0, vms_pts_dev_cap = 0, vms_pts_host_cap = 0;            // bytes
-    // mi_unet_volume_match: d_vmt = both id stacks, the contingency table, the side tables, the row offsets, `found` and
-    // the pair list of one call; h_vmt = the pinned staging of the id stacks and of the results; grown on demand, never shared with a clone
-    miunet::DeviceBuf<uint8_t> d_vmt;
-    miunet::PinnedBuf<uint8_t> h_vmt;
-    size_t vmt_dev_cap = 0, vmt_host_cap = 0;                                                          // bytes
-    // mi_unet_volume_texture: d_vtx = the keys (ids in place), the intensity, the ranges, the table, the histograms and
-    // the two co-occurrence tables of one call; h_vtx = the pinned staging of the two stacks and of the results; grown on demand, never
-    // shared with a clone
-    miunet::DeviceBuf<uint8_t> d_vtx;
-    miunet::PinnedBuf<uint8_t> h_vtx;
-    size_t vtx_dev_cap = 0, vtx_host_cap = 0;                                                          // bytes
+    // The workspaces of the stages behind the network, one per stage: the device side holds one call's inputs,
+    // results and kernel scratch, the pinned side the staging of what crosses the bus.  The stage's entry point (csrc/<stage>.cpp) lays
+    // its workspace out and grows it; no other stage, and no clone, touches it.
+    // mi_unet_score_labels and mi_unet_score_volume: both maps, the scores, the kernels' workspace; pinned: the maps and the results.
+    // Either call ends with a host synchronisation, so the two stages take turns on it
+    miunet::Workspace ws_score;
+    miunet::Workspace ws_volume;       // mi_unet_volume_components: the volume, out, ids, the table, the counts, the kernels' workspace
+    miunet::Workspace ws_vclean;       // mi_unet_volume_clean: the volume, out, the counts, the kernels' workspace
+    miunet::Workspace ws_vmesh;        // mi_unet_volume_mesh: the volume, the counts, the kernels' workspace
+    miunet::Workspace ws_vmesh_out;    // ... the kept vertices and quads of one plane, sized by its counts
+    miunet::Workspace ws_vms;          // mi_unet_volume_measure: ids, intensity, the table and the per-component arrays
+    miunet::Workspace ws_vms_pts;      // ... the run ends of the searched components and the work list of the pair search, sized once the ends are counted
+    miunet::Workspace ws_vmt;          // mi_unet_volume_match: the results (side tables, `found`, pairs), the row offsets, the contingency table, both id stacks
+    miunet::Workspace ws_vtx;          // mi_unet_volume_texture: the keys (ids in place), the intensity, the ranges, the table, the histograms, both co-occurrence tables
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)
     hipStream_t pre_stream = nullptr;

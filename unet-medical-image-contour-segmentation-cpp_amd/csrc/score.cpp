@@ -1,7 +1,7 @@
 // score.cpp -- scores against ground truth (include/mi_unet.h: mi_unet_score_labels): the argument checks, the
 // definition as pure host arithmetic (mi_unet_score_labels_host), the derived metrics (mi_unet_score_derive) and the entry point on
-// the handle, which owns the stage's workspace.  With MIUNET_SCORE_NO_DEVICE only the host arithmetic is compiled, with no HIP header:
-// a plain C++ compiler builds it into a program that supplies miunet::engine_fail (tests/cpu/score_host_test.cpp).
+// the handle, which owns the stage's workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled (stage_common.h;
+// tests/cpu/score_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,17 +9,7 @@
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_SCORE_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_score_dir) == 32, "mi_unet_score_dir is 32 bytes without padding");
 static_assert(sizeof(mi_unet_score) == 88, "mi_unet_score is 88 bytes without padding");
@@ -37,13 +27,7 @@ int check_score_args(const char *fn, const uint8_t *pred, const uint8_t *truth, 
     const std::string f = fn;
     if (!pred || !truth || !values || !scores) return fail(MI_UNET_EARG, f + ": null argument");
     if (B < 1) return fail(MI_UNET_EARG, f + ": B = " + std::to_string(B) + " (at least one image)");
-    if (n < 1 || n > MI_UNET_SCORE_MAX_VALUES)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(n) + " values (1 .. " + std::to_string(MI_UNET_SCORE_MAX_VALUES) + ")");
-    for (int k = 0; k < n; ++k) {
-        if (values[k] < 0 || values[k] > 255) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is not a byte");
-        for (int j = 0; j < k; ++j)
-            if (values[j] == values[k]) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is listed twice");
-    }
+    if (int rc = check_values(f, values, n, MI_UNET_SCORE_MAX_VALUES)) return rc;
     if (o.quantile_ppm < 0 || o.quantile_ppm > 999999)
         return fail(MI_UNET_EARG, f + ": quantile_ppm " + std::to_string(o.quantile_ppm) + " is outside 0 .. 999999");
     if (o.classes < 0 || o.classes > MI_UNET_SCORE_MAX_CLASSES)
@@ -218,7 +202,7 @@ int mi_unet_score_derive(const mi_unet_score *s, mi_unet_score_metrics *out)
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_SCORE_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_score_labels(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth, int B, int H, int W, const int *values, int n,
                          const mi_unet_score_opts *opts, mi_unet_score *scores, int64_t *confusion, int64_t *skipped)
 {
@@ -228,26 +212,13 @@ int mi_unet_score_labels(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth
     HIP_TRY(hipSetDevice(h->cfg.device));
     const int classes = confusion ? o.classes : 0;
     const size_t map_bytes = (size_t)B * H * W, P = (size_t)B * n;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device: both maps, the scores, the kernels' workspace; pinned: both maps, the scores, the matrix with its skipped counts
-    const size_t at_truth = up(map_bytes), at_scores = at_truth + up(map_bytes), at_ws = at_scores + up(P * sizeof(mi_unet_score));
+    const size_t at_truth = up256(map_bytes), at_scores = at_truth + up256(map_bytes), at_ws = at_scores + up256(P * sizeof(mi_unet_score));
     const size_t conf_bytes = (size_t)B * ((size_t)classes * classes + 1) * sizeof(int64_t);
     const size_t dev_need = at_ws + score_workspace_bytes(B, H, W, n, classes), host_need = at_ws + conf_bytes;
     hipStream_t s = h->stream;
-    if (dev_need > h->score_dev_cap || host_need > h->score_host_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (dev_need > h->score_dev_cap) {
-            h->score_dev_cap = 0;
-            HIP_TRY(h->d_score.reset(dev_need));
-            h->score_dev_cap = dev_need;
-        }
-        if (host_need > h->score_host_cap) {
-            h->score_host_cap = 0;
-            HIP_TRY(h->h_score.reset(host_need));
-            h->score_host_cap = host_need;
-        }
-    }
-    uint8_t *const d = h->d_score, *const p = h->h_score;
+    if (int rc = h->ws_score.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_score.d, *const p = h->ws_score.p;
     host_copy(h, p, pred, map_bytes);
     host_copy(h, p + at_truth, truth, map_bytes);
     HIP_TRY(hipMemcpyAsync(d, p, map_bytes, hipMemcpyHostToDevice, s));

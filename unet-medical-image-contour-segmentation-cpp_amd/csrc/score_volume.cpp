@@ -1,8 +1,7 @@
 // score_volume.cpp -- scores of a stack as one volume (include/mi_unet.h: mi_unet_score_volume): the argument checks,
 // the definition as sequential host arithmetic (mi_unet_score_volume_host), the unit helper, the derived metrics in mm and the entry
-// point on the handle, which shares mi_unet_score_labels' workspace.  With MIUNET_SCORE_NO_DEVICE only the host arithmetic is compiled,
-// with no HIP header: a plain C++ compiler builds it, together with score.cpp, into a program that supplies miunet::engine_fail
-// (tests/cpu/score_volume_host_test.cpp).
+// point on the handle, which shares mi_unet_score_labels' workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled
+// (stage_common.h), together with score.cpp (tests/cpu/score_volume_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,17 +9,7 @@
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_SCORE_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 namespace miunet {
 
@@ -28,22 +17,8 @@ namespace {
 
 constexpr mi_unet_score_opts kDefaultOpts{ 50000, 0 };
 constexpr int kMaxSide = MI_UNET_SCORE_VOLUME_MAX_SIDE;
-constexpr int64_t kD2Limit = (int64_t)1 << 31;          // every d2 stays below it
+constexpr int64_t kD2Limit = (int64_t)1 << 31;          // every d2 stays below it (d2_fits)
 constexpr int64_t kNone = std::numeric_limits<int64_t>::max();
-
-bool sides_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && D <= kMaxSide && H <= kMaxSide && W <= kMaxSide; }
-
-// ((W - 1) ux)^2 + ((H - 1) uy)^2 + ((D - 1) uz)^2 < 2^31, without overflow for any unit: a term of 46341 or more fails by itself
-bool d2_fits(int D, int H, int W, const int64_t u[3])
-{
-    const int64_t side[3] = { W - 1, H - 1, D - 1 };
-    int64_t sum = 0;
-    for (int a = 0; a < 3; ++a) {
-        if (side[a] != 0 && u[a] > 46340 / side[a]) return false;
-        sum += side[a] * u[a] * side[a] * u[a];
-    }
-    return sum < kD2Limit;
-}
 
 // every MI_UNET_EARG case of the two entry points; nothing has been queued or written when it fails
 int check_args(const char *fn, const uint8_t *pred, const uint8_t *truth, int D, int H, int W, const int *values, int n, const int *units,
@@ -51,16 +26,8 @@ int check_args(const char *fn, const uint8_t *pred, const uint8_t *truth, int D,
 {
     const std::string f = fn;
     if (!pred || !truth || !values || !units || !scores) return fail(MI_UNET_EARG, f + ": null argument");
-    if (!sides_ok(D, H, W))
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " is outside 1 .. " +
-                                      std::to_string(kMaxSide) + " per side");
-    if (n < 1 || n > MI_UNET_SCORE_MAX_VALUES)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(n) + " values (1 .. " + std::to_string(MI_UNET_SCORE_MAX_VALUES) + ")");
-    for (int k = 0; k < n; ++k) {
-        if (values[k] < 0 || values[k] > 255) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is not a byte");
-        for (int j = 0; j < k; ++j)
-            if (values[j] == values[k]) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is listed twice");
-    }
+    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
+    if (int rc = check_values(f, values, n, MI_UNET_SCORE_MAX_VALUES)) return rc;
     if (o.quantile_ppm < 0 || o.quantile_ppm > 999999)
         return fail(MI_UNET_EARG, f + ": quantile_ppm " + std::to_string(o.quantile_ppm) + " is outside 0 .. 999999");
     if (o.classes < 0 || o.classes > MI_UNET_SCORE_MAX_CLASSES)
@@ -68,10 +35,8 @@ int check_args(const char *fn, const uint8_t *pred, const uint8_t *truth, int D,
     if (confusion && o.classes == 0) return fail(MI_UNET_EARG, f + ": a confusion matrix needs classes >= 1");
     if (confusion && !skipped) return fail(MI_UNET_EARG, f + ": a confusion matrix needs the skipped count beside it");
     if ((int64_t)n * D * H * W >= kD2Limit) return fail(MI_UNET_EARG, f + ": n * D * H * W must stay below 2^31");      // (< 2^42: no overflow)
-    for (int a = 0; a < 3; ++a)
-        if (units[a] < 1) return fail(MI_UNET_EARG, f + ": spacing unit " + std::to_string(units[a]) + " (at least 1)");
-    const int64_t u[3] = { units[0], units[1], units[2] };
-    if (!d2_fits(D, H, W, u)) return fail(MI_UNET_EARG, f + ": the squared diagonal of the volume in spacing units must stay below 2^31");
+    if (int rc = check_units_min1(f, units)) return rc;
+    if (!d2_fits(D, H, W, units)) return fail(MI_UNET_EARG, f + ": the squared diagonal of the volume in spacing units must stay below 2^31");
     return MI_UNET_OK;
 }
 
@@ -231,7 +196,7 @@ int mi_unet_score_volume_host(const uint8_t *pred, const uint8_t *truth, int D, 
 int mi_unet_score_volume_units(const double spacing_mm[3], int D, int H, int W, int units[3], double *unit_mm)
 {
     if (!spacing_mm || !units || !unit_mm) return fail(MI_UNET_EARG, "mi_unet_score_volume_units: null argument");
-    if (!sides_ok(D, H, W)) return fail(MI_UNET_EARG, "mi_unet_score_volume_units: D, H, W must be in 1 .. " + std::to_string(kMaxSide));
+    if (!sides_within(D, H, W, kMaxSide)) return fail(MI_UNET_EARG, "mi_unet_score_volume_units: D, H, W must be in 1 .. " + std::to_string(kMaxSide));
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(spacing_mm[a]) || !(spacing_mm[a] > 0.0))
             return fail(MI_UNET_EARG, "mi_unet_score_volume_units: the spacing must be finite and positive");
@@ -264,7 +229,7 @@ int mi_unet_score_volume_derive(const mi_unet_score *s, double unit_mm, mi_unet_
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_SCORE_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_score_volume(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth, int D, int H, int W, const int *values, int n,
                          const int spacing_units[3], const mi_unet_score_opts *opts, mi_unet_score *scores, int64_t *confusion, int64_t *skipped)
 {
@@ -274,26 +239,13 @@ int mi_unet_score_volume(mi_unet_t *h, const uint8_t *pred, const uint8_t *truth
     HIP_TRY(hipSetDevice(h->cfg.device));
     const int classes = confusion ? o.classes : 0;
     const size_t map_bytes = (size_t)D * H * W;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device: both volumes, the scores, the kernels' workspace; pinned: both volumes, the scores, the matrix with its skipped count
-    const size_t at_truth = up(map_bytes), at_scores = at_truth + up(map_bytes), at_ws = at_scores + up((size_t)n * sizeof(mi_unet_score));
+    const size_t at_truth = up256(map_bytes), at_scores = at_truth + up256(map_bytes), at_ws = at_scores + up256((size_t)n * sizeof(mi_unet_score));
     const size_t conf_bytes = ((size_t)classes * classes + 1) * sizeof(int64_t);
     const size_t dev_need = at_ws + score_volume_workspace_bytes(D, H, W, n, classes), host_need = at_ws + conf_bytes;
     hipStream_t s = h->stream;
-    if (dev_need > h->score_dev_cap || host_need > h->score_host_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (dev_need > h->score_dev_cap) {
-            h->score_dev_cap = 0;
-            HIP_TRY(h->d_score.reset(dev_need));
-            h->score_dev_cap = dev_need;
-        }
-        if (host_need > h->score_host_cap) {
-            h->score_host_cap = 0;
-            HIP_TRY(h->h_score.reset(host_need));
-            h->score_host_cap = host_need;
-        }
-    }
-    uint8_t *const d = h->d_score, *const p = h->h_score;
+    if (int rc = h->ws_score.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_score.d, *const p = h->ws_score.p;
     host_copy(h, p, pred, map_bytes);
     host_copy(h, p + at_truth, truth, map_bytes);
     HIP_TRY(hipMemcpyAsync(d, p, map_bytes, hipMemcpyHostToDevice, s));

@@ -1,24 +1,14 @@
 // volume.cpp -- a stack of masks labelled as one volume (include/mi_unet.h: mi_unet_volume_components): the argument
 // checks, the definition as pure host arithmetic (mi_unet_volume_components_host), the derived metrics (mi_unet_volume_derive) and the
-// entry point on the handle, which owns the stage's workspace.  With MIUNET_VOLUME_NO_DEVICE only the host arithmetic is compiled, with
-// no HIP header: a plain C++ compiler builds it into a program that supplies miunet::engine_fail (tests/cpu/volume_host_test.cpp).
+// entry point on the handle, which owns the stage's workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled
+// (stage_common.h; tests/cpu/volume_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_vcomp) == 88, "mi_unet_vcomp is 88 bytes without padding");
 
@@ -34,26 +24,15 @@ int check_volume_args(const char *fn, const uint8_t *masks, int D, int H, int W,
 {
     const std::string f = fn;
     if (!masks || !values || !table || !found || !kept) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " (every side at least 1)");
-    if (n < 1 || n > MI_UNET_VOLUME_MAX_VALUES)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(n) + " values (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_VALUES) + ")");
-    for (int k = 0; k < n; ++k) {
-        if (values[k] < 0 || values[k] > 255) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is not a byte");
-        for (int j = 0; j < k; ++j)
-            if (values[j] == values[k]) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is listed twice");
-    }
+    if (int rc = check_sides_min1(f, D, H, W)) return rc;
+    if (int rc = check_values(f, values, n, MI_UNET_VOLUME_MAX_VALUES)) return rc;
     if (cap < 1 || cap > MI_UNET_VOLUME_MAX_TABLE)
         return fail(MI_UNET_EARG, f + ": cap " + std::to_string(cap) + " is outside 1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE));
     if (o.connectivity != 6 && o.connectivity != 18 && o.connectivity != 26)
         return fail(MI_UNET_EARG, f + ": connectivity " + std::to_string(o.connectivity) + " is none of 6, 18, 26");
     if (o.min_voxels < 0) return fail(MI_UNET_EARG, f + ": min_voxels " + std::to_string(o.min_voxels) + " is negative");
     if (o.keep_largest < 0) return fail(MI_UNET_EARG, f + ": keep_largest " + std::to_string(o.keep_largest) + " is negative");
-    // step by step: the product itself could pass 64 bits
-    long long v = 0x7FFFFFFFLL / n;
-    v /= D;
-    v /= H;
-    if (v < W) return fail(MI_UNET_EARG, f + ": n * D * H * W must stay below 2^31");
+    if (!product_below_2_31(n, D, H, W)) return fail(MI_UNET_EARG, f + ": n * D * H * W must stay below 2^31");
     return MI_UNET_OK;
 }
 
@@ -178,7 +157,7 @@ int mi_unet_volume_derive(const mi_unet_vcomp *c, const double spacing_xyz[3], m
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_volume_components(mi_unet_t *h, const uint8_t *masks, int D, int H, int W, const int *values, int n,
                               const mi_unet_volume_opts *opts, uint8_t *out, int32_t *ids, mi_unet_vcomp *table, int cap,
                               int32_t *found, int32_t *kept)
@@ -188,26 +167,13 @@ int mi_unet_volume_components(mi_unet_t *h, const uint8_t *masks, int D, int H, 
     if (int rc = check_volume_args("mi_unet_volume_components", masks, D, H, W, values, n, o, table, cap, found, kept)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t dhw = (size_t)D * H * W, N = dhw * n, table_bytes = (size_t)n * cap * sizeof(mi_unet_vcomp);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device and pinned alike: the volume, out, ids (when asked for), the table, found and kept; device only: the kernels' workspace
-    const size_t at_out = up(dhw), at_ids = at_out + up(N), at_table = at_ids + (ids ? up(N * sizeof(int32_t)) : 0);
-    const size_t at_counts = at_table + up(table_bytes), at_ws = at_counts + up((size_t)2 * n * sizeof(int32_t));
+    const size_t at_out = up256(dhw), at_ids = at_out + up256(N), at_table = at_ids + (ids ? up256(N * sizeof(int32_t)) : 0);
+    const size_t at_counts = at_table + up256(table_bytes), at_ws = at_counts + up256((size_t)2 * n * sizeof(int32_t));
     const size_t dev_need = at_ws + volume_workspace_bytes(D, H, W, n), host_need = at_ws;
     hipStream_t s = h->stream;
-    if (dev_need > h->volume_dev_cap || host_need > h->volume_host_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (dev_need > h->volume_dev_cap) {
-            h->volume_dev_cap = 0;
-            HIP_TRY(h->d_volume.reset(dev_need));
-            h->volume_dev_cap = dev_need;
-        }
-        if (host_need > h->volume_host_cap) {
-            h->volume_host_cap = 0;
-            HIP_TRY(h->h_volume.reset(host_need));
-            h->volume_host_cap = host_need;
-        }
-    }
-    uint8_t *const d = h->d_volume, *const p = h->h_volume;
+    if (int rc = h->ws_volume.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_volume.d, *const p = h->ws_volume.p;
     host_copy(h, p, masks, dhw);
     HIP_TRY(hipMemcpyAsync(d, p, dhw, hipMemcpyHostToDevice, s));
     VolumeArgs a;

@@ -1,23 +1,13 @@
 // volume_clean.cpp -- a stack of masks cleaned as one volume (include/mi_unet.h: mi_unet_volume_clean): the argument
 // checks, the ball (mi_unet_volume_ball), the definition as sequential host arithmetic (mi_unet_volume_clean_host) and the entry point
-// on the handle, which owns the stage's workspace.  With MIUNET_VOLUME_CLEAN_NO_DEVICE only the host arithmetic is compiled, with no
-// HIP header: a plain C++ compiler builds it into a program that supplies miunet::engine_fail (tests/cpu/volume_clean_host_test.cpp).
+// on the handle, which owns the stage's workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled (stage_common.h;
+// tests/cpu/volume_clean_host_test.cpp).
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_CLEAN_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_volume_clean_stat) == 48, "mi_unet_volume_clean_stat is 48 bytes without padding");
 
@@ -42,20 +32,9 @@ int check_clean_args(const char *fn, const uint8_t *masks, int D, int H, int W, 
 {
     const std::string f = fn;
     if (!masks || !values || !units || !out) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " (every side at least 1)");
-    if (n < 1 || n > MI_UNET_VOLUME_MAX_VALUES)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(n) + " values (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_VALUES) + ")");
-    for (int k = 0; k < n; ++k) {
-        if (values[k] < 0 || values[k] > 255) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is not a byte");
-        for (int j = 0; j < k; ++j)
-            if (values[j] == values[k]) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is listed twice");
-    }
-    // step by step: the product itself could pass 64 bits
-    long long v = 0x7FFFFFFFLL / n;
-    v /= D;
-    v /= H;
-    if (v < W) return fail(MI_UNET_EARG, f + ": n * D * H * W must stay below 2^31");
+    if (int rc = check_sides_min1(f, D, H, W)) return rc;
+    if (int rc = check_values(f, values, n, MI_UNET_VOLUME_MAX_VALUES)) return rc;
+    if (!product_below_2_31(n, D, H, W)) return fail(MI_UNET_EARG, f + ": n * D * H * W must stay below 2^31");
     if (int rc = check_units(f, units)) return rc;
     if (o.fill != 0 && o.fill != 1) return fail(MI_UNET_EARG, f + ": fill " + std::to_string(o.fill) + " is neither 0 nor 1");
     if (o.close_r < 0 || o.close_r > kMaxR)
@@ -204,7 +183,7 @@ int mi_unet_volume_clean_host(const uint8_t *masks, int D, int H, int W, const i
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_CLEAN_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_volume_clean(mi_unet_t *h, const uint8_t *masks, int D, int H, int W, const int *values, int n, const int spacing_units[3],
                          const mi_unet_volume_clean_opts *opts, uint8_t *out, mi_unet_volume_clean_stat *stats)
 {
@@ -213,25 +192,12 @@ int mi_unet_volume_clean(mi_unet_t *h, const uint8_t *masks, int D, int H, int W
     if (int rc = check_clean_args("mi_unet_volume_clean", masks, D, H, W, values, n, spacing_units, o, out)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t dhw = (size_t)D * H * W, N = dhw * n, count_bytes = (size_t)n * 4 * sizeof(unsigned long long);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device and pinned alike: the volume, out, the counts; device only: the kernels' workspace
-    const size_t at_out = up(dhw), at_counts = at_out + up(N), at_ws = at_counts + up(count_bytes);
+    const size_t at_out = up256(dhw), at_counts = at_out + up256(N), at_ws = at_counts + up256(count_bytes);
     const size_t dev_need = at_ws + volume_clean_workspace_bytes(D, H, W, n), host_need = at_ws;
     hipStream_t s = h->stream;
-    if (dev_need > h->vclean_dev_cap || host_need > h->vclean_host_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (dev_need > h->vclean_dev_cap) {
-            h->vclean_dev_cap = 0;
-            HIP_TRY(h->d_vclean.reset(dev_need));
-            h->vclean_dev_cap = dev_need;
-        }
-        if (host_need > h->vclean_host_cap) {
-            h->vclean_host_cap = 0;
-            HIP_TRY(h->h_vclean.reset(host_need));
-            h->vclean_host_cap = host_need;
-        }
-    }
-    uint8_t *const d = h->d_vclean, *const p = h->h_vclean;
+    if (int rc = h->ws_vclean.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_vclean.d, *const p = h->ws_vclean.p;
     host_copy(h, p, masks, dhw);
     HIP_TRY(hipMemcpyAsync(d, p, dhw, hipMemcpyHostToDevice, s));
     VolumeCleanArgs a;

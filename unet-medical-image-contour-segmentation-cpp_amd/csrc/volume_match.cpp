@@ -1,25 +1,15 @@
 // volume_match.cpp -- the components of a prediction against the components of a truth (include/mi_unet.h: mi_unet_volume_match;
 // DESIGN.md 7.14): the argument checks, the definition as sequential host arithmetic (mi_unet_volume_match_host), the one-to-one
 // assignment at an IoU threshold (mi_unet_volume_match_assign), the scores of an assignment (mi_unet_volume_match_derive) and the entry
-// point on the handle, which owns the stage's workspace.  With MIUNET_VOLUME_MATCH_NO_DEVICE only the host arithmetic is compiled, with no
-// HIP header: a plain C++ compiler builds it into a program that supplies miunet::engine_fail (tests/cpu/volume_match_host_test.cpp).
+// point on the handle, which owns the stage's workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled (stage_common.h;
+// tests/cpu/volume_match_host_test.cpp).
 #include <algorithm>
 #include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_MATCH_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_vmatch_side) == 20, "mi_unet_vmatch_side is five int32 without padding");
 static_assert(sizeof(mi_unet_vmatch_pair) == 12, "mi_unet_vmatch_pair is three int32 without padding");
@@ -34,8 +24,7 @@ int check_match_args(const char *fn, const int32_t *pred, const int32_t *truth, 
 {
     const std::string f = fn;
     if (!pred || !truth || !ps || !ts || !pairs || !found) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " (every side at least 1)");
+    if (int rc = check_sides_min1(f, D, H, W)) return rc;
     // (each factor is below 2^31, so the products are tested one at a time)
     if ((int64_t)D * H >= ((int64_t)1 << 31) || (int64_t)D * H * W >= ((int64_t)1 << 31))
         return fail(MI_UNET_EARG, f + ": D * H * W must stay below 2^31");
@@ -198,7 +187,7 @@ int mi_unet_volume_match_derive(const mi_unet_vmatch_side *pred_side, int mp, co
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_MATCH_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 // Pairs that travel back with the tables in the one copy before the call's synchronisation.  A real series has tens of pairs; a list
 // that holds more is fetched in a second copy, once `found` says how long it is.
 constexpr size_t kEagerPairs = 65536;
@@ -213,29 +202,18 @@ int mi_unet_volume_match(mi_unet_t *h, const int32_t *pred_ids, const int32_t *t
     const size_t dhw = (size_t)D * H * W, MP = (size_t)mp, MT = (size_t)mt, cells = (MP + 1) * (MT + 1);
     // a pair holds at least one voxel and one cell, so this many positions can be filled at all
     const size_t keep = std::min({ (size_t)cap, dhw, MP * MT });
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // results, the same layout on the device and in pinned memory: pred side, truth side, found, pairs; then on the device the row
     // counts, the row offsets, the columns' accumulators, the table and both stacks; in pinned memory both stacks
-    const size_t at_ts = up(MP * sizeof(mi_unet_vmatch_side)), at_found = at_ts + up(MT * sizeof(mi_unet_vmatch_side));
-    const size_t at_pairs = at_found + 256, at_rest = at_pairs + up(keep * sizeof(mi_unet_vmatch_pair));
-    const size_t at_rows = at_rest, at_first = at_rows + up(MP * sizeof(int32_t)), at_acc = at_first + up(MP * sizeof(int32_t));
-    const size_t at_table = at_acc + up(MT * VMT_COL_ACC_BYTES);
-    const size_t at_pred = at_table + up(cells * sizeof(int32_t)), at_truth = at_pred + up(dhw * sizeof(int32_t));
-    const size_t dev_need = at_truth + up(dhw * sizeof(int32_t));
-    const size_t hat_pred = at_rest, hat_truth = hat_pred + up(dhw * sizeof(int32_t)), host_need = hat_truth + up(dhw * sizeof(int32_t));
+    const size_t at_ts = up256(MP * sizeof(mi_unet_vmatch_side)), at_found = at_ts + up256(MT * sizeof(mi_unet_vmatch_side));
+    const size_t at_pairs = at_found + 256, at_rest = at_pairs + up256(keep * sizeof(mi_unet_vmatch_pair));
+    const size_t at_rows = at_rest, at_first = at_rows + up256(MP * sizeof(int32_t)), at_acc = at_first + up256(MP * sizeof(int32_t));
+    const size_t at_table = at_acc + up256(MT * VMT_COL_ACC_BYTES);
+    const size_t at_pred = at_table + up256(cells * sizeof(int32_t)), at_truth = at_pred + up256(dhw * sizeof(int32_t));
+    const size_t dev_need = at_truth + up256(dhw * sizeof(int32_t));
+    const size_t hat_pred = at_rest, hat_truth = hat_pred + up256(dhw * sizeof(int32_t)), host_need = hat_truth + up256(dhw * sizeof(int32_t));
     hipStream_t s = h->stream;
-    // grows one of the stage's buffers; nothing of the stage is in flight on it when this runs
-    auto grow = [&](auto &buf, size_t &have, size_t need) -> int {
-        if (need <= have) return MI_UNET_OK;
-        HIP_TRY(hipStreamSynchronize(s));
-        have = 0;
-        HIP_TRY(buf.reset(need));
-        have = need;
-        return MI_UNET_OK;
-    };
-    if (int rc = grow(h->d_vmt, h->vmt_dev_cap, dev_need)) return rc;
-    if (int rc = grow(h->h_vmt, h->vmt_host_cap, host_need)) return rc;
-    uint8_t *const d = h->d_vmt, *const p = h->h_vmt;
+    if (int rc = h->ws_vmt.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_vmt.d, *const p = h->ws_vmt.p;
     host_copy(h, p + hat_pred, pred_ids, dhw * sizeof(int32_t));
     HIP_TRY(hipMemcpyAsync(d + at_pred, p + hat_pred, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
     host_copy(h, p + hat_truth, truth_ids, dhw * sizeof(int32_t));

@@ -2,8 +2,7 @@
 // mi_unet_volume_measure): the argument checks, the definition as sequential host arithmetic
 // (mi_unet_volume_measure_host), the function that turns an entry into millimetres (mi_unet_volume_measure_derive) and the entry point on
 // the handle, which owns the stage's workspace and splits the pair search into launches of bounded work.  With
-// MIUNET_VOLUME_MEASURE_NO_DEVICE only the host arithmetic is compiled, with no HIP header: a plain C++ compiler builds it into a program
-// that supplies miunet::engine_fail (tests/cpu/volume_measure_host_test.cpp).
+// MIUNET_NO_DEVICE only the host arithmetic is compiled (stage_common.h; tests/cpu/volume_measure_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -11,17 +10,7 @@
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_MEASURE_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_vmeasure) == 128, "mi_unet_vmeasure is 128 bytes without padding");
 static_assert(sizeof(mi_unet_vmeasure_opts) == 4, "mi_unet_vmeasure_opts is one int");
@@ -34,33 +23,17 @@ namespace {
 constexpr mi_unet_vmeasure_opts kDefaultOpts{ 262144 };
 constexpr int kMaxSide = MI_UNET_SCORE_VOLUME_MAX_SIDE;
 
-// ((W - 1) ux)^2 + ((H - 1) uy)^2 + ((D - 1) uz)^2 < 2^31, without overflow for any unit: a term of 46341 or more fails by itself
-// (the limit of mi_unet_score_volume)
-bool d2_fits(int D, int H, int W, const int *units)
-{
-    const int64_t side[3] = { W - 1, H - 1, D - 1 };
-    int64_t sum = 0;
-    for (int a = 0; a < 3; ++a) {
-        if (side[a] != 0 && units[a] > 46340 / side[a]) return false;
-        sum += side[a] * units[a] * side[a] * units[a];
-    }
-    return sum < ((int64_t)1 << 31);
-}
-
 // every MI_UNET_EARG case of the two entry points; nothing has been queued or written when it fails
 int check_measure_args(const char *fn, const int32_t *ids, int D, int H, int W, int m, const int *units, const mi_unet_vmeasure_opts &o,
                        const mi_unet_vmeasure *table)
 {
     const std::string f = fn;
     if (!ids || !units || !table) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1 || D > kMaxSide || H > kMaxSide || W > kMaxSide)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " is outside 1 .. " +
-                                      std::to_string(kMaxSide) + " per side");
+    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
     if ((int64_t)D * H * W >= ((int64_t)1 << 31)) return fail(MI_UNET_EARG, f + ": D * H * W must stay below 2^31");    // (< 2^39: no overflow)
     if (m < 1 || m > MI_UNET_VOLUME_MAX_TABLE)
         return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE) + ")");
-    for (int a = 0; a < 3; ++a)
-        if (units[a] < 1) return fail(MI_UNET_EARG, f + ": spacing unit " + std::to_string(units[a]) + " (at least 1)");
+    if (int rc = check_units_min1(f, units)) return rc;
     if (!d2_fits(D, H, W, units)) return fail(MI_UNET_EARG, f + ": the squared diagonal of the volume in spacing units must stay below 2^31");
     if (o.max_ends < 0 || o.max_ends > MI_UNET_VMEASURE_MAX_ENDS_LIMIT)
         return fail(MI_UNET_EARG, f + ": max_ends " + std::to_string(o.max_ends) + " is outside 0 .. " + std::to_string(MI_UNET_VMEASURE_MAX_ENDS_LIMIT));
@@ -148,8 +121,7 @@ int mi_unet_volume_measure_derive(const mi_unet_vmeasure *c, const int spacing_u
     const std::string f = "mi_unet_volume_measure_derive";
     if (!c || !spacing_units || !out) return fail(MI_UNET_EARG, f + ": null argument");
     if (c->voxels < 1) return fail(MI_UNET_EARG, f + ": voxels " + std::to_string(c->voxels) + " (a component has at least one voxel)");
-    for (int a = 0; a < 3; ++a)
-        if (spacing_units[a] < 1) return fail(MI_UNET_EARG, f + ": spacing unit " + std::to_string(spacing_units[a]) + " (at least 1)");
+    if (int rc = check_units_min1(f, spacing_units)) return rc;
     if (!std::isfinite(unit_mm) || !(unit_mm > 0.0)) return fail(MI_UNET_EARG, f + ": unit_mm must be finite and > 0");
     const double s[3] = { spacing_units[0] * unit_mm, spacing_units[1] * unit_mm, spacing_units[2] * unit_mm };
     const __int128 A = c->voxels;
@@ -212,7 +184,7 @@ int mi_unet_volume_measure_derive(const mi_unet_vmeasure *c, const int spacing_u
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_MEASURE_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 // The pairs one launch of the search may hold.  k_vms_pairs runs at 1e12 pairs / s and more on an MI355X (DESIGN.md 7.13 has the measured
 // rate), so a launch of 2^30 pairs takes about a millisecond, a hundred times the cost of launching it: a component at the default cap of
 // 2^18 run ends (3.4e10 pairs) becomes 32 launches, one at the limit of 2^20 (5.5e11 pairs) 512, and none of them can occupy the device
@@ -227,25 +199,14 @@ int mi_unet_volume_measure(mi_unet_t *h, const int32_t *ids, const uint16_t *int
     if (int rc = check_measure_args("mi_unet_volume_measure", ids, D, H, W, m, spacing_units, o, table)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t dhw = (size_t)D * H * W, M = (size_t)m;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device: ids, intensity, table, seg, diam | cursor, keys; pinned: the same up to diam
-    const size_t at_int = up(dhw * sizeof(int32_t)), at_table = at_int + up(intensity ? dhw * sizeof(uint16_t) : 0);
-    const size_t at_seg = at_table + up(M * sizeof(mi_unet_vmeasure)), at_diam = at_seg + up(M * sizeof(int2));
-    const size_t at_cursor = at_diam + up(M * 6 * sizeof(int32_t)), at_keys = at_cursor + up(M * sizeof(int));
-    const size_t dev_need = at_keys + up(M * 2 * sizeof(unsigned long long)), host_need = at_cursor;
+    const size_t at_int = up256(dhw * sizeof(int32_t)), at_table = at_int + up256(intensity ? dhw * sizeof(uint16_t) : 0);
+    const size_t at_seg = at_table + up256(M * sizeof(mi_unet_vmeasure)), at_diam = at_seg + up256(M * sizeof(int2));
+    const size_t at_cursor = at_diam + up256(M * 6 * sizeof(int32_t)), at_keys = at_cursor + up256(M * sizeof(int));
+    const size_t dev_need = at_keys + up256(M * 2 * sizeof(unsigned long long)), host_need = at_cursor;
     hipStream_t s = h->stream;
-    // grows one of the stage's buffers; nothing of the stage is in flight on it when this runs
-    auto grow = [&](auto &buf, size_t &cap, size_t need) -> int {
-        if (need <= cap) return MI_UNET_OK;
-        HIP_TRY(hipStreamSynchronize(s));
-        cap = 0;
-        HIP_TRY(buf.reset(need));
-        cap = need;
-        return MI_UNET_OK;
-    };
-    if (int rc = grow(h->d_vms, h->vms_dev_cap, dev_need)) return rc;
-    if (int rc = grow(h->h_vms, h->vms_host_cap, host_need)) return rc;
-    uint8_t *const d = h->d_vms, *const p = h->h_vms;
+    if (int rc = h->ws_vms.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_vms.d, *const p = h->ws_vms.p;
     host_copy(h, p, ids, dhw * sizeof(int32_t));
     HIP_TRY(hipMemcpyAsync(d, p, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (intensity) {
@@ -286,10 +247,9 @@ int mi_unet_volume_measure(mi_unet_t *h, const int32_t *ids, const uint16_t *int
         }
     }
     if (points) {
-        const size_t at_items = up(points * sizeof(int4)), item_bytes = items.size() * sizeof(VmsItem);
-        if (int rc = grow(h->d_vms_pts, h->vms_pts_dev_cap, at_items + up(item_bytes))) return rc;
-        if (int rc = grow(h->h_vms_pts, h->vms_pts_host_cap, up(item_bytes))) return rc;
-        uint8_t *const dp = h->d_vms_pts, *const pp = h->h_vms_pts;
+        const size_t at_items = up256(points * sizeof(int4)), item_bytes = items.size() * sizeof(VmsItem);
+        if (int rc = h->ws_vms_pts.reserve(at_items + up256(item_bytes), up256(item_bytes), s)) return rc;     // (nothing of the stage is in flight here)
+        uint8_t *const dp = h->ws_vms_pts.d, *const pp = h->ws_vms_pts.p;
         std::memcpy(pp, items.data(), item_bytes);
         const int2 *const d_seg = reinterpret_cast<const int2 *>(d + at_seg);
         int4 *const d_points = reinterpret_cast<int4 *>(dp);

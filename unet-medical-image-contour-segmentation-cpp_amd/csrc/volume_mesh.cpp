@@ -1,25 +1,14 @@
 // volume_mesh.cpp -- the border of a stack of masks as a quad mesh (include/mi_unet.h: mi_unet_volume_mesh): the argument
 // checks, the definition as sequential host arithmetic (mi_unet_volume_mesh_host), the two functions that turn a mesh into millimetres
 // (mi_unet_volume_mesh_positions, _derive) and the entry point on the handle, which owns the stage's workspace.  With
-// MIUNET_VOLUME_MESH_NO_DEVICE only the host arithmetic is compiled, with no HIP header: a plain C++ compiler builds it into a program
-// that supplies miunet::engine_fail (tests/cpu/volume_mesh_host_test.cpp).
+// MIUNET_NO_DEVICE only the host arithmetic is compiled (stage_common.h; tests/cpu/volume_mesh_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_MESH_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_mesh_vertex) == 16, "mi_unet_mesh_vertex is 16 bytes without padding");
 static_assert(sizeof(mi_unet_mesh_stat) == 48, "mi_unet_mesh_stat is 48 bytes without padding");
@@ -34,20 +23,9 @@ int check_mesh_args(const char *fn, const uint8_t *masks, int D, int H, int W, c
 {
     const std::string f = fn;
     if (!masks || !values || !stats) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " (every side at least 1)");
-    if (n < 1 || n > MI_UNET_VOLUME_MAX_VALUES)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(n) + " values (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_VALUES) + ")");
-    for (int k = 0; k < n; ++k) {
-        if (values[k] < 0 || values[k] > 255) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is not a byte");
-        for (int j = 0; j < k; ++j)
-            if (values[j] == values[k]) return fail(MI_UNET_EARG, f + ": value " + std::to_string(values[k]) + " is listed twice");
-    }
-    // step by step: the product itself could pass 64 bits
-    long long v = 0x7FFFFFFFLL / 6;
-    v /= (long long)D + 1;
-    v /= (long long)H + 1;
-    if (v < (long long)W + 1) return fail(MI_UNET_EARG, f + ": 6 * (D + 1) * (H + 1) * (W + 1) must stay below 2^31");
+    if (int rc = check_sides_min1(f, D, H, W)) return rc;
+    if (int rc = check_values(f, values, n, MI_UNET_VOLUME_MAX_VALUES)) return rc;
+    if (!product_below_2_31(6, (long long)D + 1, (long long)H + 1, (long long)W + 1)) return fail(MI_UNET_EARG, f + ": 6 * (D + 1) * (H + 1) * (W + 1) must stay below 2^31");
     if (placement != MI_UNET_MESH_FACES && placement != MI_UNET_MESH_NETS)
         return fail(MI_UNET_EARG, f + ": placement " + std::to_string(placement) + " is neither MI_UNET_MESH_FACES nor MI_UNET_MESH_NETS");
     if (cap_verts < 0 || cap_quads < 0)
@@ -208,7 +186,7 @@ int mi_unet_volume_mesh_derive(const mi_unet_mesh_vertex *verts, int nv, const i
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_MESH_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_volume_mesh(mi_unet_t *h, const uint8_t *masks, int D, int H, int W, const int *values, int n, int placement,
                         mi_unet_mesh_vertex *verts, int cap_verts, int32_t *quads, int cap_quads, mi_unet_mesh_stat *stats)
 {
@@ -216,24 +194,13 @@ int mi_unet_volume_mesh(mi_unet_t *h, const uint8_t *masks, int D, int H, int W,
     if (int rc = check_mesh_args("mi_unet_volume_mesh", masks, D, H, W, values, n, placement, verts, cap_verts, quads, cap_quads, stats)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t dhw = (size_t)D * H * W, count_bytes = 5 * sizeof(unsigned long long);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device: the volume, the counts, the kernels' workspace; pinned: the volume, the counts.  The kept prefixes of one plane have buffers
     // of their own, sized once its counts are known
-    const size_t at_counts = up(dhw), at_ws = at_counts + up(count_bytes);
+    const size_t at_counts = up256(dhw), at_ws = at_counts + up256(count_bytes);
     const size_t dev_need = at_ws + volume_mesh_workspace_bytes(D, H, W), host_need = at_ws;
     hipStream_t s = h->stream;
-    // grows one of the stage's buffers; nothing of the stage is in flight on it when this runs
-    auto grow = [&](auto &buf, size_t &cap, size_t need) -> int {
-        if (need <= cap) return MI_UNET_OK;
-        HIP_TRY(hipStreamSynchronize(s));
-        cap = 0;
-        HIP_TRY(buf.reset(need));
-        cap = need;
-        return MI_UNET_OK;
-    };
-    if (int rc = grow(h->d_vmesh, h->vmesh_dev_cap, dev_need)) return rc;
-    if (int rc = grow(h->h_vmesh, h->vmesh_host_cap, host_need)) return rc;
-    uint8_t *const d = h->d_vmesh, *const p = h->h_vmesh;
+    if (int rc = h->ws_vmesh.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_vmesh.d, *const p = h->ws_vmesh.p;
     host_copy(h, p, masks, dhw);
     HIP_TRY(hipMemcpyAsync(d, p, dhw, hipMemcpyHostToDevice, s));
     for (int k = 0; k < n; ++k) {
@@ -250,10 +217,9 @@ int mi_unet_volume_mesh(mi_unet_t *h, const uint8_t *masks, int D, int H, int W,
         int32_t *const out_q = quads ? quads + (size_t)k * cap_quads * 4 : nullptr;
         if (keep_v || keep_q) {
             const size_t v_bytes = (size_t)keep_v * sizeof(mi_unet_mesh_vertex), q_bytes = (size_t)keep_q * 4 * sizeof(int32_t);
-            const size_t at_q = up(v_bytes), out_need = at_q + up(q_bytes);
-            if (int rc = grow(h->d_vmesh_out, h->vmesh_out_dev_cap, out_need)) return rc;
-            if (int rc = grow(h->h_vmesh_out, h->vmesh_out_host_cap, out_need)) return rc;
-            uint8_t *const od = h->d_vmesh_out, *const op = h->h_vmesh_out;
+            const size_t at_q = up256(v_bytes), out_need = at_q + up256(q_bytes);
+            if (int rc = h->ws_vmesh_out.reserve(out_need, out_need, s)) return rc;     // (nothing of the stage is in flight on it here)
+            uint8_t *const od = h->ws_vmesh_out.d, *const op = h->ws_vmesh_out.p;
             e = launch_volume_mesh_emit(a, d + at_ws, keep_v ? reinterpret_cast<mi_unet_mesh_vertex *>(od) : nullptr, keep_v,
                                         keep_q ? reinterpret_cast<int32_t *>(od + at_q) : nullptr, keep_q, s);
             if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("volume mesh launch: ") + hipGetErrorString(e));

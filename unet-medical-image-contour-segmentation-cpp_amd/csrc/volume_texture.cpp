@@ -1,9 +1,8 @@
 // volume_texture.cpp -- per component of a labelled stack its grey-level histogram and its 3-D co-occurrence tables (include/mi_unet.h:
 // mi_unet_volume_texture): the argument checks, the definition as sequential host arithmetic
 // (mi_unet_volume_texture_host), the function that turns the counts of one component into features (mi_unet_volume_texture_derive) and
-// the entry point on the handle, which owns the stage's workspace.  With MIUNET_VOLUME_TEXTURE_NO_DEVICE only the host arithmetic is
-// compiled, with no HIP header: a plain C++ compiler builds it into a program that supplies miunet::engine_fail
-// (tests/cpu/volume_texture_host_test.cpp).
+// the entry point on the handle, which owns the stage's workspace.  With MIUNET_NO_DEVICE only the host arithmetic is compiled
+// (stage_common.h; tests/cpu/volume_texture_host_test.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -12,17 +11,7 @@
 #include <string>
 #include <vector>
 
-#ifdef MIUNET_VOLUME_TEXTURE_NO_DEVICE
-#include "../../include/mi_unet.h"
-namespace miunet {
-int engine_fail(int code, const std::string &msg);
-inline int fail(int code, const std::string &msg) { return engine_fail(code, msg); }
-}
-#else
-#include <hip/hip_runtime.h>
-
-#include "engine_handle.h"
-#endif
+#include "stage_common.h"
 
 static_assert(sizeof(mi_unet_vtexture) == 32, "mi_unet_vtexture is 32 bytes without padding");
 static_assert(sizeof(mi_unet_vtexture_opts) == 16, "mi_unet_vtexture_opts is four ints");
@@ -41,10 +30,8 @@ int check_texture_args(const char *fn, const int32_t *ids, const uint16_t *inten
 {
     const std::string f = fn;
     if (!ids || !intensity || !table || !hist) return fail(MI_UNET_EARG, f + ": null argument");
-    if (D < 1 || H < 1 || W < 1 || D > kMaxSide || H > kMaxSide || W > kMaxSide)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(D) + " x " + std::to_string(H) + " x " + std::to_string(W) + " is outside 1 .. " +
-                                      std::to_string(kMaxSide) + " per side");
-    if ((int64_t)D * H * W > (int64_t)MI_UNET_VTEX_MAX_VOXELS) return fail(MI_UNET_EARG, f + ": D * H * W must not pass 2^28");   // (< 2^39: no overflow)
+    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
+    if ((int64_t)D * H * W >(int64_t)MI_UNET_VTEX_MAX_VOXELS) return fail(MI_UNET_EARG, f + ": D * H * W must not pass 2^28");   // (< 2^39: no overflow)
     if (m < 1 || m > MI_UNET_VOLUME_MAX_TABLE)
         return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE) + ")");
     if (o.mode != MI_UNET_VTEX_COUNT && o.mode != MI_UNET_VTEX_WIDTH) return fail(MI_UNET_EARG, f + ": mode " + std::to_string(o.mode) + " does not exist");
@@ -204,7 +191,7 @@ int mi_unet_volume_texture_derive(const mi_unet_vtexture *c, const uint32_t *his
     return MI_UNET_OK;
 }
 
-#ifndef MIUNET_VOLUME_TEXTURE_NO_DEVICE
+#ifndef MIUNET_NO_DEVICE
 int mi_unet_volume_texture(mi_unet_t *h, const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m,
                            const mi_unet_vtexture_opts *opts, mi_unet_vtexture *table, uint32_t *hist, uint32_t *glcm, uint32_t *glcm_axial)
 {
@@ -213,25 +200,14 @@ int mi_unet_volume_texture(mi_unet_t *h, const int32_t *ids, const uint16_t *int
     if (int rc = check_texture_args("mi_unet_volume_texture", ids, intensity, D, H, W, m, o, table, hist)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t dhw = (size_t)D * H * W, M = (size_t)m, L = (size_t)o.levels;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t table_bytes = M * sizeof(mi_unet_vtexture), hist_bytes = M * L * sizeof(uint32_t), cells_bytes = M * L * L * sizeof(uint32_t);
     // device: keys (ids in place), intensity, table, hist, inter (then glcm), axial | range; pinned: the same up to axial
-    const size_t at_int = up(dhw * sizeof(int32_t)), at_table = at_int + up(dhw * sizeof(uint16_t)), at_hist = at_table + up(table_bytes);
-    const size_t at_inter = at_hist + up(hist_bytes), at_axial = at_inter + up(cells_bytes), at_range = at_axial + up(cells_bytes);
-    const size_t dev_need = at_range + up(M * sizeof(int2)), host_need = at_range;
+    const size_t at_int = up256(dhw * sizeof(int32_t)), at_table = at_int + up256(dhw * sizeof(uint16_t)), at_hist = at_table + up256(table_bytes);
+    const size_t at_inter = at_hist + up256(hist_bytes), at_axial = at_inter + up256(cells_bytes), at_range = at_axial + up256(cells_bytes);
+    const size_t dev_need = at_range + up256(M * sizeof(int2)), host_need = at_range;
     hipStream_t s = h->stream;
-    // grows one of the stage's buffers; nothing of the stage is in flight on it when this runs
-    auto grow = [&](auto &buf, size_t &cap, size_t need) -> int {
-        if (need <= cap) return MI_UNET_OK;
-        HIP_TRY(hipStreamSynchronize(s));
-        cap = 0;
-        HIP_TRY(buf.reset(need));
-        cap = need;
-        return MI_UNET_OK;
-    };
-    if (int rc = grow(h->d_vtx, h->vtx_dev_cap, dev_need)) return rc;
-    if (int rc = grow(h->h_vtx, h->vtx_host_cap, host_need)) return rc;
-    uint8_t *const d = h->d_vtx, *const p = h->h_vtx;
+    if (int rc = h->ws_vtx.reserve(dev_need, host_need, s)) return rc;
+    uint8_t *const d = h->ws_vtx.d, *const p = h->ws_vtx.p;
     host_copy(h, p, ids, dhw * sizeof(int32_t));
     HIP_TRY(hipMemcpyAsync(d, p, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
     host_copy(h, p + at_int, intensity, dhw * sizeof(uint16_t));

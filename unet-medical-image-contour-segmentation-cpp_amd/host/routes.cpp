@@ -1,7 +1,8 @@
 // routes.cpp -- MedicalSeg::process_single_image and process_image_batch: which device call an image takes, and what goes on around it
 // (reading the files, scores against ground truth, the pipelined directory mode).  Reference: src/process.cpp:123-262,
 // src/main.cpp:148-164.  The facade's units: lifecycle.cpp (state, settings, log, engine, thread contexts), artefacts.cpp (the files of
-// one finished image), routes.cpp; facade.h is what the first and the last share.
+// one finished image), routes.cpp, volume_route.cpp (the chain behind a batch taken as one volume); facade.h is what the first and the
+// last two share.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -19,23 +20,12 @@
 #include "facade.h"
 #include "json_io.h"
 #include "png_io.h"
+#include "volume_route.h"
 
 namespace fs = std::filesystem;
 using medseg::Image8;
 
 namespace MedicalSeg {
-
-namespace {
-
-using hr_clock = std::chrono::high_resolution_clock;
-long long ms_since(hr_clock::time_point t0) { return std::chrono::duration_cast<std::chrono::milliseconds>(hr_clock::now() - t0).count(); }
-
-// the log file, or while it is closed a stream that takes nothing
-std::ostream g_nothing(nullptr);
-std::ostream &log_or_nothing() { return get_log_file().is_open() ? static_cast<std::ostream &>(get_log_file()) : g_nothing; }
-
-// text collected during a call and written to `to` in one piece when the call ends, however it ends
-struct Collected { std::ostream &to; std::ostringstream text; ~Collected() { to << text.str() << std::flush; } };
 
 // a failure of one image or one batch: on stderr and in the log
 void report(std::ostream &lg, const std::string &msg)
@@ -43,6 +33,23 @@ void report(std::ostream &lg, const std::string &msg)
     std::cerr << msg << std::endl;
     lg << msg << std::endl;
 }
+
+std::string json_number(double v)
+{
+    if (!std::isfinite(v)) return "null";
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+namespace {
+
+// the log file, or while it is closed a stream that takes nothing
+std::ostream g_nothing(nullptr);
+std::ostream &log_or_nothing() { return get_log_file().is_open() ? static_cast<std::ostream &>(get_log_file()) : g_nothing; }
+
+// text collected during a call and written to `to` in one piece when the call ends, however it ends
+struct Collected { std::ostream &to; std::ostringstream text; ~Collected() { to << text.str() << std::flush; } };
 
 // process_single_image's wording for a RAW file that cannot be read or preprocessed (src/process.cpp:211-214)
 template <class Read>
@@ -130,14 +137,6 @@ void keep_channel0(const uint8_t *hwc, size_t npix, int C, uint8_t *grey)
     for (size_t p = 0; p < npix; ++p) grey[p] = hwc[p * C];
 }
 
-std::string json_number(double v)
-{
-    if (!std::isfinite(v)) return "null";
-    char buf[40];
-    std::snprintf(buf, sizeof buf, "%.17g", v);
-    return buf;
-}
-
 // ---- set_truth_dir: the final masks of one device call against <dir>/<base>_labels.raw (u8 class indices at the tile size).
 // masks holds plane (k, t) -- image k, target t, any non-zero byte = foreground -- at (k * K + t) * H * W; an empty base skips the
 // image.  Every plane is recoded to 0 / 1 on both sides (the mask; truth == cls_t), so that ONE mi_unet_score_labels call with
@@ -189,9 +188,8 @@ std::vector<TruthNote> score_against_truth(mi_unet_t *h, const std::vector<std::
         const int one = 1, planes = (int)(good.size() * K);
         const mi_unet_score_opts opts{ 50000, 0 };
         std::vector<mi_unet_score> scores((size_t)planes);
-        const int rc = (h && device_postprocess_requested())
-                           ? mi_unet_score_labels(h, pred.data(), truth.data(), planes, g_cfg.height, g_cfg.width, &one, 1, &opts, scores.data(), nullptr, nullptr)
-                           : mi_unet_score_labels_host(pred.data(), truth.data(), planes, g_cfg.height, g_cfg.width, &one, 1, &opts, scores.data(), nullptr, nullptr);
+        const int rc = stage_rc(h, mi_unet_score_labels, mi_unet_score_labels_host, pred.data(), truth.data(), planes, g_cfg.height, g_cfg.width, &one, 1,
+                                &opts, scores.data(), nullptr, nullptr);
         for (size_t g = 0; g < good.size(); ++g) {
             TruthNote &note = notes[good[g]];
             if (rc != MI_UNET_OK) {
@@ -514,544 +512,6 @@ int process_batch_pipelined(const std::vector<std::string> &paths, const std::ve
     return ok;
 }
 
-// ---- set_volume: the images of a batch as the slices of one volume.  process_images_targets fills the stack as its images finish;
-// label_volume runs once, behind the last device call of the batch.
-struct VolumeStack {
-    // channel >= 0 (set_volume_measure): the stack also keeps that channel of every slice's normalised tile; texture_channel >= 0
-    // (set_volume_texture) likewise, in a stack of its own only when the two channels differ
-    VolumeStack(size_t slices, size_t targets, size_t hw, int channel = -1, int texture_channel = -1)
-        : planes(targets * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0),
-          texture_own(texture_channel >= 0 && texture_channel != channel ? slices * hw : 0, 0), bases(slices), names(slices), D(slices), hw(hw),
-          channel(channel), texture_channel(texture_channel)
-    {
-    }
-    // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t; `tile` is its normalised
-    // tile, [H][W][C]
-    void add(size_t i, const std::string &base, const uint8_t *pictures, size_t K, const uint8_t *tile, size_t C)
-    {
-        for (size_t t = 0; t < K; ++t) std::copy(pictures + t * hw, pictures + (t + 1) * hw, planes.begin() + (t * D + i) * hw);
-        if (channel >= 0 && (size_t)channel < C)
-            for (size_t p = 0; p < hw; ++p) intensity[i * hw + p] = tile[p * C + (size_t)channel];
-        if (!texture_own.empty() && (size_t)texture_channel < C)
-            for (size_t p = 0; p < hw; ++p) texture_own[i * hw + p] = tile[p * C + (size_t)texture_channel];
-        bases[i] = base;
-    }
-    const uint16_t *texture_intensity() const { return texture_own.empty() ? intensity.data() : texture_own.data(); }
-    std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
-    std::vector<uint16_t> intensity;                   // [D][H][W] or empty: the measured channel of the normalised tiles, widened
-    std::vector<uint16_t> texture_own;                 // [D][H][W] or empty: the texture's channel where it is not the measured one
-    std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
-    size_t D, hw;
-    int channel, texture_channel;
-};
-
-// set_volume_clean: every target's plane of the stack through one mi_unet_volume_clean call with values = { 255 } on `h`
-// (mi_unet_volume_clean_host under MEDSEG_HOST_POSTPROCESS=1), in place, before label_volume.  The integer units come from
-// mi_unet_score_volume_units on the volume setting's spacing; a radius is llround(mm / unit_mm).  `json` receives the "clean" object of
-// volume_report.json.  A failure is reported, leaves the stack as it was and returns false: the batch's volume stage ends there.
-bool clean_volume(VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeClean &c, mi_unet_t *h,
-                  std::ostream &lg, std::string &json)
-{
-    try {
-        const size_t K = targets.size(), D = st.D, hw = st.hw;
-        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
-        int units[3] = { 0, 0, 0 };
-        double unit_mm = 0.0;
-        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
-            throw std::runtime_error(mi_unet_last_error());
-        auto radius = [&](double mm, const char *which) {
-            const double q = mm / unit_mm;
-            if (!(q < 2147483647.0)) throw std::runtime_error(std::string(which) + " radius is out of range");     // (llround of it must fit an int)
-            return (int)std::llround(q);
-        };
-        const mi_unet_volume_clean_opts opts{ c.fill ? 1 : 0, radius(c.close_mm, "close"), radius(c.open_mm, "open") };
-        const int value = 255;
-        const bool device = h && device_postprocess_requested();
-        std::vector<uint8_t> cleaned(K * D * hw);
-        std::vector<mi_unet_volume_clean_stat> stats(K);
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const uint8_t *const in = st.planes.data() + t * D * hw;
-            uint8_t *const o = cleaned.data() + t * D * hw;
-            const int rc = device ? mi_unet_volume_clean(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, o, &stats[t])
-                                  : mi_unet_volume_clean_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, o, &stats[t]);
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-        }
-        lg << "Volume clean: " << D << " slices, " << K << " targets, fill " << (c.fill ? "on" : "off") << ", close " << opts.close_r << ", open "
-           << opts.open_r << " (unit " << unit_mm << " mm), " << ms_since(t0) << " ms" << std::endl;
-        std::ostringstream js;
-        js << "  \"clean\": {\"fill\": " << (c.fill ? "true" : "false") << ", \"close_mm\": " << json_number(c.close_mm) << ", \"open_mm\": "
-           << json_number(c.open_mm) << ", \"unit_mm\": " << json_number(unit_mm) << ", \"close_r\": " << opts.close_r << ", \"open_r\": "
-           << opts.open_r << ", \"targets\": [";
-        for (size_t t = 0; t < K; ++t) {
-            const mi_unet_volume_clean_stat &s = stats[t];
-            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"in_voxels\": " << s.in_voxels << ", \"filled\": " << s.filled
-               << ", \"closed\": " << s.closed << ", \"opened\": " << s.opened << ", \"out_voxels\": " << s.out_voxels << "}";
-        }
-        js << "\n  ]},\n";
-        json = js.str();
-        st.planes.swap(cleaned);
-        return true;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume clean error: ") + e.what());
-        return false;
-    }
-}
-
-// set_volume_mesh: every target's plane of `planes` ([K][D][H][W], the stack label_volume labelled) through mi_unet_volume_mesh with
-// values = { 255 } on `h` (mi_unet_volume_mesh_host under MEDSEG_HOST_POSTPROCESS=1) -- a counting call, then one sized by its counts --
-// then the positions and metrics under the volume setting's spacing and the STL file of every target that has quads.  Returns the
-// "mesh" member of volume_report.json, from its leading comma on.  A failure is reported and returns an empty text: only this step ends.
-std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeMesh &mesh,
-                        mi_unet_t *h, const std::string &output_dir, std::ostream &lg)
-{
-    try {
-        const size_t K = targets.size();
-        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
-        const int value = 255;
-        const bool device = h && device_postprocess_requested();
-        const char *const placement = mesh.placement == MI_UNET_MESH_NETS ? "nets" : "faces";
-        std::ostringstream js;
-        js << ",\n  \"mesh\": {\"placement\": \"" << placement << "\", \"targets\": [";
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const uint8_t *const in = planes + t * D * hw;
-            auto call = [&](mi_unet_mesh_vertex *verts, int cap_verts, int32_t *quads, int cap_quads, mi_unet_mesh_stat *st) {
-                const int rc = device ? mi_unet_volume_mesh(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, mesh.placement, verts, cap_verts, quads,
-                                                            cap_quads, st)
-                                      : mi_unet_volume_mesh_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, mesh.placement, verts, cap_verts,
-                                                                 quads, cap_quads, st);
-                if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            };
-            mi_unet_mesh_stat st{};
-            call(nullptr, 0, nullptr, 0, &st);
-            std::vector<mi_unet_mesh_vertex> verts((size_t)st.verts);
-            std::vector<int32_t> quads((size_t)st.quads * 4);
-            if (st.quads > 0) call(verts.data(), (int)st.verts, quads.data(), (int)st.quads, &st);
-            mi_unet_mesh_metrics m{};
-            if (mi_unet_volume_mesh_derive(verts.data(), (int)verts.size(), quads.data(), (int)st.quads, spacing, &m) != MI_UNET_OK)
-                throw std::runtime_error(mi_unet_last_error());
-            std::string file;
-            if (st.quads > 0) {
-                std::vector<float> xyz(verts.size() * 3);
-                if (mi_unet_volume_mesh_positions(verts.data(), (int)verts.size(), spacing, xyz.data()) != MI_UNET_OK)
-                    throw std::runtime_error(mi_unet_last_error());
-                file = is_default(targets) ? "volume_mesh.stl" : "volume_mesh_class" + std::to_string(targets[t].cls) + ".stl";
-                VolumeMeshArtefact a;
-                a.output_dir = output_dir; a.file = file; a.xyz = xyz.data(); a.quads = quads.data(); a.nv = verts.size(); a.nq = (size_t)st.quads;
-                write_volume_mesh(a);
-            }
-            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"quads\": " << st.quads << ", \"verts\": " << st.verts
-               << ", \"area_mm2\": " << json_number(m.area_mm2) << ", \"volume_mm3\": " << json_number(m.volume_mm3) << ", \"file\": "
-               << (file.empty() ? std::string("null") : "\"" + file + "\"") << "}";
-        }
-        js << "\n  ]}";
-        lg << "Volume mesh: " << D << " slices, " << K << " targets, " << placement << ", " << ms_since(t0) << " ms" << std::endl;
-        return js.str();
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume mesh error: ") + e.what());
-        return std::string();
-    }
-}
-
-// set_volume_measure: per target one mi_unet_volume_measure call on `h` (mi_unet_volume_measure_host under MEDSEG_HOST_POSTPROCESS=1) over
-// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's intensity, with m = min(found, cap) and the integer units of
-// mi_unet_score_volume_units for the volume setting's spacing.  Returns, per target and table row, the "measure" member of the row's
-// component object in volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
-                                                     size_t cap, const std::vector<mi_unet_target> &targets, const Volume &v,
-                                                     const VolumeMeasure &measure, mi_unet_t *h, std::ostream &lg)
-{
-    try {
-        const size_t K = targets.size(), D = st.D, hw = st.hw;
-        const int W = g_cfg.width;
-        if (measure.channel >= g_cfg.in_ch)
-            throw std::runtime_error("channel " + std::to_string(measure.channel) + " of " + std::to_string(g_cfg.in_ch));
-        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
-        int units[3] = { 0, 0, 0 };
-        double unit_mm = 0.0;
-        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
-            throw std::runtime_error(mi_unet_last_error());
-        const mi_unet_vmeasure_opts opts{ measure.max_ends };
-        const bool device = h && device_postprocess_requested();
-        std::vector<std::vector<std::string>> members(K);
-        auto point = [&](int32_t idx) {
-            const size_t p = (size_t)idx % hw;
-            return "[" + std::to_string(p % (size_t)W) + ", " + std::to_string(p / (size_t)W) + ", " + std::to_string((size_t)idx / hw) + "]";
-        };
-        auto ends = [&](int32_t p, int32_t q) { return "[" + point(p) + ", " + point(q) + "]"; };
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const int m = (int)std::min<size_t>((size_t)found[t], cap);
-            if (m < 1) continue;
-            std::vector<mi_unet_vmeasure> table((size_t)m);
-            const int32_t *const in = ids.data() + t * D * hw;
-            const int rc = device ? mi_unet_volume_measure(h, in, st.intensity.data(), (int)D, g_cfg.height, g_cfg.width, m, units, &opts, table.data())
-                                  : mi_unet_volume_measure_host(in, st.intensity.data(), (int)D, g_cfg.height, g_cfg.width, m, units, &opts, table.data());
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            for (const mi_unet_vmeasure &c : table) {
-                if (c.voxels < 1) {                             // dropped by the volume filter: its voxels carry no id
-                    members[t].push_back(", \"measure\": null");
-                    continue;
-                }
-                mi_unet_vmeasure_shape s{};
-                if (mi_unet_volume_measure_derive(&c, units, unit_mm, &s) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-                const bool searched = c.d2 >= 0;
-                std::ostringstream js;
-                js << ", \"measure\": {\"diameter_mm\": " << (searched ? json_number(s.diameter_mm) : "null") << ", \"diameter_ends\": "
-                   << (searched ? ends(c.dp, c.dq) : "null") << ", \"axial_diameter_mm\": " << (searched ? json_number(s.axial_diameter_mm) : "null")
-                   << ", \"axial_slice\": " << (searched ? "\"" + medseg::json_escape(st.names[(size_t)c.a_p / hw]) + "\"" : std::string("null"))
-                   << ", \"axial_ends\": " << (searched ? ends(c.a_p, c.a_q) : "null") << ", \"axes_mm\": [" << json_number(s.axis_mm[0]) << ", "
-                   << json_number(s.axis_mm[1]) << ", " << json_number(s.axis_mm[2]) << "], \"axes_dir\": [";
-                for (int i = 0; i < 3; ++i)
-                    js << (i ? ", " : "") << "[" << json_number(s.axis_dir[i][0]) << ", " << json_number(s.axis_dir[i][1]) << ", "
-                       << json_number(s.axis_dir[i][2]) << "]";
-                js << "], \"mean\": " << json_number(s.mean) << ", \"std\": " << json_number(s.std) << ", \"min\": " << c.imin << ", \"max\": "
-                   << c.imax << ", \"ends\": " << c.ends << "}";
-                members[t].push_back(js.str());
-            }
-        }
-        lg << "Volume measure: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
-        return members;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume measure error: ") + e.what());
-        return {};
-    }
-}
-
-// set_volume_texture: per target one mi_unet_volume_texture call on `h` (mi_unet_volume_texture_host under MEDSEG_HOST_POSTPROCESS=1) over
-// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's texture channel, with m = min(found, cap, 2^22 / levels^2), then
-// mi_unet_volume_texture_derive of every row and of both its tables.  Returns, per target and table row, the "texture" member of the row's
-// component object in volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
-                                                     size_t cap, const std::vector<mi_unet_target> &targets, const VolumeTexture &texture,
-                                                     mi_unet_t *h, std::ostream &lg)
-{
-    try {
-        const size_t K = targets.size(), D = st.D, hw = st.hw, L = (size_t)texture.levels;
-        if (texture.channel >= g_cfg.in_ch)
-            throw std::runtime_error("channel " + std::to_string(texture.channel) + " of " + std::to_string(g_cfg.in_ch));
-        const mi_unet_vtexture_opts opts{ texture.mode, texture.levels, texture.lo, texture.width };
-        const bool device = h && device_postprocess_requested();
-        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * L);
-        std::vector<std::vector<std::string>> members(K);
-        size_t cut = 0;                                         // components beyond the measured count, over all targets
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const size_t rows = std::min<size_t>((size_t)found[t], cap);
-            const int m = (int)std::min(rows, most);
-            if (m < 1) continue;
-            cut += rows - (size_t)m;
-            std::vector<mi_unet_vtexture> table((size_t)m);
-            std::vector<uint32_t> hist((size_t)m * L), glcm((size_t)m * L * L), axial((size_t)m * L * L);
-            const int32_t *const in = ids.data() + t * D * hw;
-            const int rc = device ? mi_unet_volume_texture(h, in, st.texture_intensity(), (int)D, g_cfg.height, g_cfg.width, m, &opts, table.data(),
-                                                           hist.data(), glcm.data(), axial.data())
-                                  : mi_unet_volume_texture_host(in, st.texture_intensity(), (int)D, g_cfg.height, g_cfg.width, m, &opts, table.data(),
-                                                                hist.data(), glcm.data(), axial.data());
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            for (size_t r = 0; r < rows; ++r) {
-                if (r >= (size_t)m || table[r].voxels < 1) {    // beyond the measured count, or dropped by the volume filter: no voxel carries its id
-                    members[t].push_back(", \"texture\": null");
-                    continue;
-                }
-                const mi_unet_vtexture &c = table[r];
-                mi_unet_vtexture_features f{}, fa{};
-                if (mi_unet_volume_texture_derive(&c, hist.data() + r * L, glcm.data() + r * L * L, (int)L, &f) != MI_UNET_OK ||
-                    mi_unet_volume_texture_derive(&c, hist.data() + r * L, axial.data() + r * L * L, (int)L, &fa) != MI_UNET_OK)
-                    throw std::runtime_error(mi_unet_last_error());
-                std::ostringstream js;
-                js << ", \"texture\": {\"levels\": " << L << ", \"mode\": \"" << (texture.mode == MI_UNET_VTEX_WIDTH ? "width" : "count")
-                   << "\", \"range\": [" << c.imin << ", " << c.imax << "], \"levels_used\": " << c.levels_used << ", \"histogram\": {\"mean\": "
-                   << json_number(f.mean) << ", \"variance\": " << json_number(f.variance) << ", \"skewness\": " << json_number(f.skewness) << ", \"kurtosis\": "
-                   << json_number(f.kurtosis) << ", \"median\": " << f.median << ", \"p10\": " << f.p10 << ", \"p90\": " << f.p90 << ", \"mode\": "
-                   << f.mode << ", \"entropy\": " << json_number(f.entropy) << ", \"uniformity\": " << json_number(f.uniformity) << ", \"counts\": [";
-                for (size_t l = 0; l < L; ++l) js << (l ? ", " : "") << hist[r * L + l];
-                js << "]}";
-                auto joint = [&](const char *key, int64_t pairs, const mi_unet_vtexture_features &g) {
-                    js << ", \"" << key << "\": {\"pairs\": " << pairs << ", \"joint_max\": " << json_number(g.joint_max) << ", \"joint_average\": "
-                       << json_number(g.joint_average) << ", \"joint_variance\": " << json_number(g.joint_variance) << ", \"joint_entropy\": "
-                       << json_number(g.joint_entropy) << ", \"contrast\": " << json_number(g.contrast) << ", \"dissimilarity\": " << json_number(g.dissimilarity)
-                       << ", \"inverse_difference\": " << json_number(g.inverse_difference) << ", \"inverse_difference_moment\": "
-                       << json_number(g.inverse_difference_moment) << ", \"angular_second_moment\": " << json_number(g.angular_second_moment)
-                       << ", \"correlation\": " << json_number(g.correlation) << "}";
-                };
-                joint("glcm", c.pairs, f);
-                joint("glcm_axial", c.pairs_axial, fa);
-                js << "}";
-                members[t].push_back(js.str());
-            }
-        }
-        lg << "Volume texture: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
-        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels; " << cut << " not measured)";
-        lg << std::endl;
-        return members;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume texture error: ") + e.what());
-        return {};
-    }
-}
-
-// One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
-// MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
-// fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
-// A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
-// is active (without one they are the cleaned stack itself).  With `mesh` on, the planes that were labelled -- `out` under a filter, else
-// the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".  With `measure` on, the components
-// stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member "measure".  With
-// `texture` on, the ids are handed out likewise and every component object gains a last member "texture" (texture_volume).  With
-// `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays empty after a failure.
-struct VolumeIds {
-    std::vector<int32_t> ids, found;
-};
-void label_volume(const VolumeStack &st, const std::vector<mi_unet_target> &targets, const Volume &v, mi_unet_t *h, const std::string &output_dir,
-                  std::ostream &lg, std::vector<uint8_t> &filtered, const std::string &clean_json = std::string(),
-                  const VolumeMesh &mesh = VolumeMesh(), const VolumeMeasure &measure = VolumeMeasure(), VolumeIds *numbered = nullptr,
-                  const VolumeTexture &texture = VolumeTexture())
-{
-    filtered.clear();
-    try {
-        const size_t K = targets.size(), D = st.D, hw = st.hw, cap = MI_UNET_VOLUME_MAX_TABLE;
-        const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
-        std::vector<uint8_t> out(filter ? K * D * hw : 0);
-        std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(measure.on || texture.on || numbered ? K * D * hw : 0);
-        const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
-        const int value = 255;
-        const bool device = h && device_postprocess_requested();
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const uint8_t *const in = st.planes.data() + t * D * hw;
-            uint8_t *const o = filter ? out.data() + t * D * hw : nullptr;
-            int32_t *const id = ids.empty() ? nullptr : ids.data() + t * D * hw;
-            const int rc = device ? mi_unet_volume_components(h, in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
-                                                              table.data() + t * cap, (int)cap, &found[t], &kept[t])
-                                  : mi_unet_volume_components_host(in, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, o, id,
-                                                                   table.data() + t * cap, (int)cap, &found[t], &kept[t]);
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-        }
-        lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
-        const std::string mesh_json = mesh.on ? mesh_volume(filter ? out.data() : st.planes.data(), D, hw, targets, v, mesh, h, output_dir, lg) : std::string();
-        const std::vector<std::vector<std::string>> measured =
-            measure.on ? measure_volume(st, ids, found, cap, targets, v, measure, h, lg) : std::vector<std::vector<std::string>>();
-        const std::vector<std::vector<std::string>> textured =
-            texture.on ? texture_volume(st, ids, found, cap, targets, texture, h, lg) : std::vector<std::vector<std::string>>();
-        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
-        std::ostringstream js;
-        auto names = [&](const char *key, bool missing) {
-            js << "  \"" << key << "\": [";
-            bool first = true;
-            for (size_t z = 0; z < D; ++z) {
-                if (missing && !st.bases[z].empty()) continue;
-                js << (first ? "" : ", ") << "\"" << medseg::json_escape(st.names[z]) << "\"";
-                first = false;
-            }
-            js << "],\n";
-        };
-        js << "{\n";
-        names("slices", false);
-        names("missing", true);
-        js << "  \"connectivity\": " << v.connectivity << ",\n  \"min_voxels\": " << v.min_voxels << ",\n  \"keep_largest\": " << v.keep_largest
-           << ",\n  \"spacing\": [" << json_number(spacing[0]) << ", " << json_number(spacing[1]) << ", " << json_number(spacing[2])
-           << "],\n" << clean_json << "  \"targets\": [";
-        for (size_t t = 0; t < K; ++t) {
-            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"found\": " << found[t] << ", \"kept\": " << kept[t]
-               << ", \"components\": [";
-            const size_t rows = std::min<size_t>((size_t)found[t], cap);
-            for (size_t r = 0; r < rows; ++r) {
-                const mi_unet_vcomp &c = table[t * cap + r];
-                mi_unet_vcomp_metrics m{};
-                if (mi_unet_volume_derive(&c, spacing, &m) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-                js << (r ? "," : "") << "\n      {\"voxels\": " << c.voxels << ", \"kept\": " << c.kept << ", \"bbox\": [" << c.x0 << ", " << c.y0 << ", "
-                   << c.z0 << ", " << c.x1 << ", " << c.y1 << ", " << c.z1 << "], \"centroid_mm\": [" << json_number(m.cx_mm) << ", "
-                   << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
-                   << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
-                   << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
-                   << (textured.empty() ? std::string() : textured[t][r]) << "}";
-            }
-            js << (rows ? "\n    " : "") << "]}";
-        }
-        js << "\n  ]" << mesh_json << "\n}\n";
-        VolumeArtefacts a;
-        a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
-        a.height = g_cfg.height; a.width = g_cfg.width;
-        write_volume_artefacts(a);
-        filtered.swap(out);
-        if (numbered) {
-            numbered->ids.swap(ids);
-            numbered->found.swap(found);
-        }
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume error: ") + e.what());
-    }
-}
-
-// set_volume_match: per target the truth stack (0 / 255, [D][H][W] at truth_planes + t * D * hw) labelled by mi_unet_volume_components
-// under the setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE, then one mi_unet_volume_match call on `h`
-// (the host forms under MEDSEG_HOST_POSTPROCESS=1) against the ids label_volume numbered, mi_unet_volume_match_assign at the setting's
-// threshold and mi_unet_volume_match_derive.  Returns per target the "lesions" member of its object in volume_score.json, from its
-// leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::string> match_volume(const VolumeIds &numbered, const std::vector<uint8_t> &truth_planes, size_t D, size_t hw,
-                                      const std::vector<mi_unet_target> &targets, const Volume &v, const VolumeMatch &match, mi_unet_t *h,
-                                      std::ostream &lg)
-{
-    try {
-        const size_t K = targets.size(), table_cap = MI_UNET_VOLUME_MAX_TABLE;
-        if (numbered.ids.size() != K * D * hw || numbered.found.size() != K) throw std::runtime_error("the labelled stack is missing");
-        const bool device = h && device_postprocess_requested();
-        const mi_unet_volume_opts opts{ v.connectivity, 0, 0 };
-        const int value = 255;
-        std::vector<std::string> members(K);
-        std::vector<int32_t> truth_ids(D * hw);
-        std::vector<mi_unet_vcomp> truth_table(table_cap);
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const uint8_t *const truth = truth_planes.data() + t * D * hw;
-            int32_t truth_found = 0, truth_kept = 0;
-            int rc = device ? mi_unet_volume_components(h, truth, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, nullptr, truth_ids.data(),
-                                                        truth_table.data(), (int)table_cap, &truth_found, &truth_kept)
-                            : mi_unet_volume_components_host(truth, (int)D, g_cfg.height, g_cfg.width, &value, 1, &opts, nullptr, truth_ids.data(),
-                                                             truth_table.data(), (int)table_cap, &truth_found, &truth_kept);
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            const size_t mp = std::min<size_t>((size_t)numbered.found[t], table_cap), mt = std::min<size_t>((size_t)truth_found, table_cap);
-            const bool truncated = (size_t)numbered.found[t] > table_cap || (size_t)truth_found > table_cap;
-            // a side without components is matched as one id that no voxel carries: an all-zero entry, which is not present
-            const size_t np = std::max<size_t>(mp, 1), nt = std::max<size_t>(mt, 1);
-            const size_t cap = std::min(np * nt, D * hw);       // a pair holds a cell and a voxel of its own: the list is never truncated
-            std::vector<mi_unet_vmatch_side> ps(np), ts(nt);
-            std::vector<mi_unet_vmatch_pair> pairs(cap);
-            int found = 0;
-            const int32_t *const pred_ids = numbered.ids.data() + t * D * hw;
-            rc = device ? mi_unet_volume_match(h, pred_ids, truth_ids.data(), (int)D, g_cfg.height, g_cfg.width, (int)np, (int)nt, (int)cap, ps.data(),
-                                               ts.data(), pairs.data(), &found)
-                        : mi_unet_volume_match_host(pred_ids, truth_ids.data(), (int)D, g_cfg.height, g_cfg.width, (int)np, (int)nt, (int)cap, ps.data(),
-                                                    ts.data(), pairs.data(), &found);
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            std::vector<int32_t> of_p(np), of_t(nt);
-            mi_unet_vmatch_counts c{};
-            mi_unet_vmatch_scores sc{};
-            if (mi_unet_volume_match_assign(ps.data(), (int)np, ts.data(), (int)nt, pairs.data(), found, (int)cap, match.iou_num, match.iou_den,
-                                            of_p.data(), of_t.data(), &c) != MI_UNET_OK ||
-                mi_unet_volume_match_derive(ps.data(), (int)np, ts.data(), (int)nt, pairs.data(), found, (int)cap, of_p.data(), &sc) != MI_UNET_OK)
-                throw std::runtime_error(mi_unet_last_error());
-            std::ostringstream js;
-            js << ", \"lesions\": {\"pred\": " << mp << ", \"truth\": " << mt << ", \"iou_threshold\": [" << match.iou_num << ", " << match.iou_den
-               << "], \"tp\": " << c.tp << ", \"fp\": " << c.fp << ", \"fn\": " << c.fn << ", \"precision\": " << json_number(sc.precision)
-               << ", \"recall\": " << json_number(sc.recall) << ", \"f1\": " << json_number(sc.f1) << ", \"pq\": " << json_number(sc.pq)
-               << ", \"sq\": " << json_number(sc.sq) << ", \"rq\": " << json_number(sc.rq) << ", \"mean_dice\": " << json_number(sc.mean_dice)
-               << ", \"matches\": [";
-            bool first = true;
-            for (size_t r = 0; r < mp; ++r) {
-                if (!of_p[r]) continue;
-                const int32_t tc = of_p[r] - 1;
-                const mi_unet_vmatch_pair *q = pairs.data();
-                while (q->p != (int32_t)r || q->t != tc) ++q;   // (derive has found it: the match is in the list)
-                const double i = q->voxels, vp = ps[r].voxels, vt = ts[tc].voxels;
-                js << (first ? "" : ", ") << "{\"pred\": " << r << ", \"truth\": " << tc << ", \"voxels\": " << q->voxels << ", \"iou\": "
-                   << json_number(i / (vp + vt - i)) << ", \"dice\": " << json_number(2.0 * i / (vp + vt)) << ", \"pred_voxels\": " << ps[r].voxels
-                   << ", \"truth_voxels\": " << ts[tc].voxels << "}";
-                first = false;
-            }
-            js << "], \"missed\": [";
-            first = true;
-            for (size_t k = 0; k < mt; ++k) {
-                if (of_t[k] || ts[k].voxels < 1) continue;
-                js << (first ? "" : ", ") << "{\"truth\": " << k << ", \"voxels\": " << ts[k].voxels << "}";
-                first = false;
-            }
-            js << "], \"spurious\": [";
-            first = true;
-            for (size_t r = 0; r < mp; ++r) {
-                if (of_p[r] || ps[r].voxels < 1) continue;
-                js << (first ? "" : ", ") << r;
-                first = false;
-            }
-            js << "]" << (truncated ? ", \"truncated\": true" : "") << "}";
-            members[t] = js.str();
-        }
-        lg << "Volume match: " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
-        return members;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume match error: ") + e.what());
-        return {};
-    }
-}
-
-// set_volume with set_truth_dir: the stack against <dir>/<base>_labels.raw of every slice as ONE volume (mi_unet_score_volume in
-// include/mi_unet.h).  One call per target with values = { 255 } on `h` (mi_unet_score_volume_host under
-// MEDSEG_HOST_POSTPROCESS=1): pred is the target's plane of `filtered` when the volume filter is active, else of the stack; truth is
-// recoded to 0 / 255 by truth == cls.  The integer units come from mi_unet_score_volume_units on the setting's spacing.  Writes
-// <output_dir>/volume_score.json.  Only a stack whose every slice completed and has a truth file of the tile's size is scored; a
-// failure is reported and fails no image.  With `match` on, every target object gains a last member "lesions" (match_volume) from the
-// ids label_volume numbered.
-void score_volume_stack(const VolumeStack &st, const std::vector<uint8_t> &filtered, const std::vector<mi_unet_target> &targets, const Volume &v,
-                        const std::string &truth_dir, mi_unet_t *h, const std::string &output_dir, std::ostream &lg,
-                        const VolumeMatch &match = VolumeMatch(), const VolumeIds &numbered = VolumeIds())
-{
-    try {
-        const size_t K = targets.size(), D = st.D, hw = st.hw;
-        const bool filter = !filtered.empty() || v.min_voxels > 0 || v.keep_largest > 0;       // (a cleaned stack comes filtered too)
-        if (filter && filtered.size() != K * D * hw) throw std::runtime_error("the filtered stack is missing");
-        std::vector<uint8_t> labels(D * hw), truth(D * hw), truth_planes(match.on ? K * D * hw : 0);
-        size_t without = 0;
-        for (size_t z = 0; z < D; ++z) {
-            bool good = !st.bases[z].empty();
-            if (good) {
-                const std::string path = truth_dir + "/" + st.bases[z] + "_labels.raw";
-                std::error_code ec;
-                const auto size = fs::file_size(path, ec);
-                std::ifstream f(path, std::ios::binary);
-                good = !ec && size == hw && f.read(reinterpret_cast<char *>(labels.data() + z * hw), (std::streamsize)hw);
-            }
-            without += !good;
-        }
-        if (without) {
-            lg << "Volume score skipped: " << without << " of " << D << " slices without mask or truth" << std::endl;
-            return;
-        }
-        const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
-        int units[3] = { 0, 0, 0 };
-        double unit_mm = 0.0;
-        if (mi_unet_score_volume_units(spacing, (int)D, g_cfg.height, g_cfg.width, units, &unit_mm) != MI_UNET_OK)
-            throw std::runtime_error(mi_unet_last_error());
-        const mi_unet_score_opts opts{ 50000, 0 };
-        const int value = 255;
-        const bool device = h && device_postprocess_requested();
-        std::vector<mi_unet_score> scores(K);
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const uint8_t *const pred = (filter ? filtered.data() : st.planes.data()) + t * D * hw;
-            for (size_t i = 0; i < D * hw; ++i) truth[i] = labels[i] == targets[t].cls ? 255 : 0;
-            const int rc = device ? mi_unet_score_volume(h, pred, truth.data(), (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts, &scores[t],
-                                                         nullptr, nullptr)
-                                  : mi_unet_score_volume_host(pred, truth.data(), (int)D, g_cfg.height, g_cfg.width, &value, 1, units, &opts,
-                                                              &scores[t], nullptr, nullptr);
-            if (rc != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            if (match.on) std::copy(truth.begin(), truth.end(), truth_planes.begin() + t * D * hw);
-        }
-        lg << "Volume score: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms" << std::endl;
-        const std::vector<std::string> lesions = match.on ? match_volume(numbered, truth_planes, D, hw, targets, v, match, h, lg) : std::vector<std::string>();
-        std::ostringstream js;
-        js << "{\n  \"slices\": [";
-        for (size_t z = 0; z < D; ++z) js << (z ? ", " : "") << "\"" << medseg::json_escape(st.names[z]) << "\"";
-        js << "],\n  \"unit_mm\": " << json_number(unit_mm) << ",\n  \"spacing_units\": [" << units[0] << ", " << units[1] << ", " << units[2]
-           << "],\n  \"quantile_ppm\": " << opts.quantile_ppm << ",\n  \"targets\": [";
-        for (size_t t = 0; t < K; ++t) {
-            const mi_unet_score &sc = scores[t];
-            mi_unet_score_metrics m{};
-            if (mi_unet_score_volume_derive(&sc, unit_mm, &m) != MI_UNET_OK) throw std::runtime_error(mi_unet_last_error());
-            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"tp\": " << sc.tp << ", \"fp\": " << sc.fp << ", \"fn\": " << sc.fn
-               << ", \"dice\": " << json_number(m.dice) << ", \"iou\": " << json_number(m.iou) << ", \"hd_mm\": " << json_number(m.hd)
-               << ", \"hd_q_mm\": " << json_number(m.hd_q) << ", \"assd_mm\": " << json_number(m.assd) << ", \"rmsd_mm\": " << json_number(m.rmsd)
-               << (lesions.empty() ? std::string() : lesions[t]) << "}";
-        }
-        js << "\n  ]\n}\n";
-        write_volume_score(output_dir, js.str());
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume score error: ") + e.what());
-    }
-}
-
 // ---- a non-default target list (set_targets) or morphology (set_morphology): K masks per image, named <base>_mask_class<cls>.png, or
 // under the default target list the one <base>_mask.png.  One plain route for both entry points: read the files of a chunk,
 // one device call for the chunk (mi_unet_segment_raw16_multi on `ctx`, or its group form when ctx is null), then the artefacts image
@@ -1164,22 +624,10 @@ int process_image_batch(const std::vector<std::string> &raw_paths, const std::ve
         if (settings.volume.on && n > 0) {                     // the paths are the slices of one volume, whatever the target list is
             std::lock_guard<std::mutex> lk(g_batch_mutex);
             Collected lg{ log_file, {} };
-            VolumeStack stack(n, settings.targets.size(), (size_t)g_cfg.height * g_cfg.width, settings.volume_measure.on ? settings.volume_measure.channel : -1,
-                              settings.volume_texture.on ? settings.volume_texture.channel : -1);
+            VolumeStack stack(n, (size_t)g_cfg.height * g_cfg.width, settings);
             for (size_t i = 0; i < n; ++i) stack.names[i] = fs::path(raw_paths[i]).stem().string();
             ok = process_images_targets(raw_paths, widths, heights, output_dir, nullptr, settings.targets, settings.morph, lg.text, &stack);
-            std::vector<uint8_t> filtered;
-            std::string clean_json;
-            if (settings.volume_clean.on &&
-                !clean_volume(stack, settings.targets, settings.volume, settings.volume_clean, mi_unet_group_handle(group, 0), lg.text, clean_json))
-                return ok;
-            const bool match = settings.volume_match.on && !settings.truth_dir.empty();
-            VolumeIds numbered;
-            label_volume(stack, settings.targets, settings.volume, mi_unet_group_handle(group, 0), output_dir, lg.text, filtered, clean_json,
-                         settings.volume_mesh, settings.volume_measure, match ? &numbered : nullptr, settings.volume_texture);
-            if (!settings.truth_dir.empty())
-                score_volume_stack(stack, filtered, settings.targets, settings.volume, settings.truth_dir, mi_unet_group_handle(group, 0), output_dir,
-                                   lg.text, settings.volume_match, numbered);
+            finish_volume(stack, settings, mi_unet_group_handle(group, 0), output_dir, lg.text);
             return ok;
         }
         if (!is_default(settings.targets) || !is_default(settings.morph)) {
