@@ -139,6 +139,25 @@ struct VolumeMesh {
 bool set_volume_mesh(const VolumeMesh &mesh);
 VolumeMesh get_volume_mesh();
 
+// Slices put between the slices of the stack before it is meshed (mi_unet_volume_interp in include/mi_unet.h).  It acts
+// only together with set_volume's `on`, and it is deliberately narrow: once the components are labelled, every target's plane that the
+// mesh would have seen -- the filtered stack under a filter, else the (cleaned) stack -- goes through one mi_unet_volume_interp call with
+// values = { 255 } (mi_unet_volume_interp_host under MEDSEG_HOST_POSTPROCESS=1), the in-plane integer units mi_unet_score_volume_units
+// finds for the volume setting's spacing, and `factor`; factor 0 means "iso": clamp(llround(spacing_z / min(spacing_x, spacing_y)), 1,
+// 16).  With set_volume_mesh on, the mesh step then takes the interpolated stack with spacing_z / factor.  Components, measure, texture,
+// score and match stay on the original slices: their reports name slices by file.  volume_report.json gains an "interp" object behind
+// "targets" (in front of "mesh"): "factor", "slices", "spacing_z_mm" and "targets" with per target "label", "in_voxels", "out_voxels",
+// "mixed", "ties" and "volume_mm3" = out_voxels * spacing_x * spacing_y * spacing_z / factor.  One log line per batch; a failure is
+// reported as "Volume interp error: ..." and ends only this step: the mesh then runs on the original stack.  With it off (the default)
+// every artefact and every log line is what it is without the setting.  Needs no engine and survives initialize_engine.  false, message
+// on stderr, setting unchanged: a factor outside 0 .. MI_UNET_VINTERP_MAX_FACTOR.
+struct VolumeInterp {
+    bool on = false;
+    int factor = 0;                                         // 0 = iso
+};
+bool set_volume_interp(const VolumeInterp &interp);
+VolumeInterp get_volume_interp();
+
 // Every component of the labelled stack measured (mi_unet_volume_measure in include/mi_unet.h).  It acts only together
 // with set_volume's `on`: the stack also keeps `channel` of every slice's normalised tile (the bytes of <base>_normalized.png for
 // channel 0) widened to 16 bits, a failed slice all-zero; mi_unet_volume_components hands out its ids, and one mi_unet_volume_measure

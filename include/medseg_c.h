@@ -70,6 +70,10 @@ void medseg_get_volume_clean(int *on, int *fill, double *close_mm, double *open_
  * MI_UNET_MESH_FACES or MI_UNET_MESH_NETS.  0 on success; medseg_get_volume_mesh fills the two values. */
 int medseg_set_volume_mesh(int on, int placement);
 void medseg_get_volume_mesh(int *on, int *placement);
+/* Slices put between the slices of the stack before it is meshed: MedicalSeg::set_volume_interp / get_volume_interp
+ * (include/medseg/process.h); factor is 0 ("iso") .. 16.  0 on success; medseg_get_volume_interp fills the two values. */
+int medseg_set_volume_interp(int on, int factor);
+void medseg_get_volume_interp(int *on, int *factor);
 /* Every component of the labelled stack measured: MedicalSeg::set_volume_measure / get_volume_measure (include/medseg/process.h).  0 on
  * success; medseg_get_volume_measure fills the three values. */
 int medseg_set_volume_measure(int on, int channel, int max_ends);

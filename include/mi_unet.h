@@ -896,6 +896,64 @@ int mi_unet_volume_texture_host(const int32_t *ids, const uint16_t *intensity, i
 int mi_unet_volume_texture_derive(const mi_unet_vtexture *c, const uint32_t *hist /* [L] */, const uint32_t *glcm /* [L][L] or NULL */, int L,
                                   mi_unet_vtexture_features *out);
 
+/* ---- Volume interpolation: slices put between the slices of a stack of masks, shape-based (Raya and Udupa) ------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  A thick-slice stack is a pile of
+ * slabs; this stage fills the gaps with slices whose outline moves linearly from one slice's outline to the next one's.  The signed
+ * in-plane distance of every slice is interpolated linearly between neighbouring slices and cut at zero -- in integers only: comparing
+ * two weighted distances is comparing their weighted squares, so no square root is taken and device, host form and reference agree
+ * byte for byte.
+ * Input is one byte volume masks, u8 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), n byte
+ * values, 1 <= n <= MI_UNET_VOLUME_MAX_VALUES, the in-plane spacing as two positive integers units_xy = { ux, uy } in a unit the caller
+ * chooses (the first two of mi_unet_score_volume_units), and the factor k, 1 .. MI_UNET_VINTERP_MAX_FACTOR.  The units are divided by
+ * their greatest common divisor first: (7, 7) is (1, 1).  The spacing along z does not enter: the new slices divide every gap evenly.
+ *   SIZES     D' = (D - 1) k + 1 output slices.  mi_unet_volume_interp_slices(D, k) returns D', or -1 for a D outside 1 .. 8192 or a k
+ *             outside 1 .. 16; it is pure host arithmetic.
+ *   SETS      plane v is S_z = { masks[z] == values[v] } per slice z; planes are independent.
+ *   DISTANCE  for a pixel p of slice z, e_z(p) = the minimum of (ux (px - qx))^2 + (uy (py - qy))^2 over the pixels q OF THE SAME SLICE
+ *             whose state (in S_z or not) differs from p's.  Positions outside the image are no candidates.  e_z(p) = NONE =
+ *             MI_UNET_VINTERP_NONE = 2^31 - 1 when the slice has no such q: it is all set or all unset.
+ *   SLICES    output slice i k + j, 0 <= i < D - 1, 0 <= j < k, lies between the input slices i and i + 1; output slice D' - 1 is
+ *             S_{D-1}.  For j = 0 it is S_i.  For j >= 1 the weights are w_i = k - j and w_{i+1} = j, and a pixel p
+ *               set in both neighbouring slices is set; set in neither is unset;
+ *               set in exactly one of them (a MIXED voxel) is set iff  w_set^2 e_set(p) >= w_unset^2 e_unset(p)  in 64-bit integers,
+ *               where `set` is the neighbour that holds p and `unset` the other; equality (a TIE) is set.
+ *             This is the sign of (k - j) phi_i + j phi_{i+1} with phi = +sqrt(e) inside and -sqrt(e) outside, zero counted as inside.
+ *             The rule is symmetric under a flip of z.  NONE takes part as the number it is: between an all-set and an all-unset
+ *             slice the nearer one wins and the middle is set.
+ *   OUTPUT    out u8 [n][D'][H][W]: values[v] on the set and 0 elsewhere (so the plane of value 0 is all zero; its stats are still
+ *             exact).  out must not overlap masks.
+ *   INTENSITY optional: intensity u16 [D][H][W] -> intensity_out u16 [D'][H][W]; slice i k + j is ((k - j) a + j b + k / 2) / k in
+ *             integers, a and b the samples of slices i and i + 1; slice D' - 1 is slice D - 1.  Both pointers NULL or both not.
+ *   STATS     per value: in_voxels = the voxels of S over the D input slices, out_voxels = those set in out, mixed = the mixed voxels
+ *             over all new slices (j >= 1), mixed_set = those of them that are set, ties = those of them decided by equality.
+ *             stats may be NULL.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE (8192): a column distance is kept in 15 bits, a row is staged in a workgroup's LDS;
+ *   n * D' * H * W < 2^31: every index of out is an int;
+ *   values in 0 .. 255 and not repeated; both units at least 1;
+ *   ((W - 1) ux)^2 + ((H - 1) uy)^2 < 2^31 - 1 with the reduced units: every e is an int32_t below NONE; w^2 e < 2^39.
+ * mi_unet_volume_interp takes host buffers of any size; its workspace (6 bytes per input voxel and plane, the stacks themselves
+ * beside it) grows on demand, belongs to the handle and is freed by mi_unet_destroy.  It needs the device, not the network: it works
+ * before weights are loaded.  It changes no setting and nothing mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG
+ * with a message that begins "mi_unet_volume_interp:", nothing queued and no output written: a null masks, values, units_xy or out; one
+ * of intensity and intensity_out null and the other not; any limit broken; out overlapping masks.  A workspace that cannot be
+ * allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_interp_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle,
+ * same bytes.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VINTERP_MAX_FACTOR 16
+#define MI_UNET_VINTERP_NONE 2147483647            /* 2^31 - 1 */
+typedef struct mi_unet_vinterp_stat {              /* 40 bytes, no padding */
+    int64_t in_voxels, out_voxels, mixed, mixed_set, ties;
+} mi_unet_vinterp_stat;
+int mi_unet_volume_interp(mi_unet_t *h, const uint8_t *masks /* [D][H][W] host */, int D, int H, int W, const int *values, int n,
+                          const int units_xy[2] /* x, y */, int factor, const uint16_t *intensity /* [D][H][W] or NULL */,
+                          uint8_t *out /* [n][D'][H][W] */, uint16_t *intensity_out /* [D'][H][W] or NULL */,
+                          mi_unet_vinterp_stat *stats /* [n] or NULL */);
+int mi_unet_volume_interp_host(const uint8_t *masks, int D, int H, int W, const int *values, int n, const int units_xy[2], int factor,
+                               const uint16_t *intensity, uint8_t *out, uint16_t *intensity_out, mi_unet_vinterp_stat *stats);
+int mi_unet_volume_interp_slices(int D, int factor);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -458,4 +458,26 @@ hipError_t launch_volume_texture_pairs(const int32_t *keys, const VolumeTextureA
 hipError_t launch_volume_texture_finish(const int2 *range, const VolumeTextureArgs &a, int want, const uint32_t *hist, uint32_t *inter,
                                         const uint32_t *axial, ::mi_unet_vtexture *table, hipStream_t s);
 
+// Volume interpolation (volume_interp.hip; include/mi_unet.h: mi_unet_volume_interp).  masks u8 [D][H][W] and intensity
+// u16 [D][H][W] (or null) on the device; plane v is the set { masks == v[v] } per slice.  Every result is a byte, a sample or an integer
+// sum: nothing depends on the order in which atomics arrive.  No workgroup waits for another.  One launch sequence for all n planes:
+//   columns : a lane per column of one slice of one plane: the index distance along y to the nearest pixel of the other state, 15 bits,
+//             VINTERP_SENT = none in this column, the pixel's own state in bit 15; mixed[v][z] = 1 once a column of the slice holds both
+//   rows    : the hot path.  A workgroup per row: the row of column words in LDS, a lane per pixel searches outwards and stops once
+//             (ux dx)^2 reaches the best so far -> field int32 [n][D][H][W]: + e where set, - e where unset, e = VINTERP_NONE in a slice
+//             that is all one state (no search there).  Computed once per slice, not once per slice pair.
+//   blend   : a lane per (y, x) of the slice pair (z, z + 1) reads the two signed values once and writes the pair's k output bytes
+//             (pair D - 1 is the last slice alone); counts u64 [n][D][5] = per plane and pair in_voxels, out_voxels, mixed, mixed_set,
+//             ties, zeroed here, by a wave reduction, a sum in LDS and one atomic per workgroup and non-zero count; the caller adds the
+//             pairs of a plane up
+//   lerp    : the intensity, a lane per (y, x) of a slice pair
+// out u8 [n][D'][H][W], D' = (D - 1) k + 1.  Workspace: volume_interp_workspace_bytes(D, H, W, n), not zeroed by the caller.
+// n * D' * H * W < 2^31, sides at most VINTERP_MAX_SIDE, ((W - 1) ux)^2 + ((H - 1) uy)^2 < 2^31 - 1.
+constexpr int VINTERP_MAX_SIDE = 8192, VINTERP_MAX_FACTOR = 16;     // = MI_UNET_SCORE_VOLUME_MAX_SIDE, MI_UNET_VINTERP_MAX_FACTOR
+constexpr int VINTERP_NONE = 0x7FFFFFFF;                            // = MI_UNET_VINTERP_NONE
+struct VolumeInterpArgs { int D = 0, H = 0, W = 0, n = 0, ux = 1, uy = 1, k = 1; int v[VOLUME_MAX_VALUES] = {}; };
+size_t volume_interp_workspace_bytes(int D, int H, int W, int n);
+hipError_t launch_volume_interp(const uint8_t *masks, const uint16_t *intensity, const VolumeInterpArgs &a, uint8_t *out,
+                                uint16_t *intensity_out, unsigned long long *counts, void *ws, hipStream_t s);
+
 }  // namespace miunet

@@ -1,5 +1,5 @@
 // stage_common.h -- what the host halves of the stages behind the network share (score.cpp, score_volume.cpp, volume.cpp,
-// volume_clean.cpp, volume_mesh.cpp, volume_measure.cpp, volume_match.cpp, volume_texture.cpp): how a stage file is compiled, and the
+// volume_clean.cpp, volume_mesh.cpp, volume_measure.cpp, volume_match.cpp, volume_texture.cpp, volume_interp.cpp): how a stage file is compiled, and the
 // argument checks that more than one of them makes with the same text.
 // With MIUNET_NO_DEVICE only a stage's host arithmetic is compiled, with no HIP header: a plain C++ compiler builds it into a program that
 // supplies miunet::engine_fail (tests/cpu/*_host_test.cpp).  Without it the stage also has its entry point on the handle.
@@ -53,9 +53,9 @@ inline int check_sides_max(const std::string &f, int D, int H, int W, int max)
     return MI_UNET_OK;
 }
 
-inline int check_units_min1(const std::string &f, const int *units)
+inline int check_units_min1(const std::string &f, const int *units, int count = 3)      // (2: the in-plane units alone)
 {
-    for (int a = 0; a < 3; ++a)
+    for (int a = 0; a < count; ++a)
         if (units[a] < 1) return fail(MI_UNET_EARG, f + ": spacing unit " + std::to_string(units[a]) + " (at least 1)");
     return MI_UNET_OK;
 }

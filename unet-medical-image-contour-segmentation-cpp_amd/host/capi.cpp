@@ -200,6 +200,13 @@ void medseg_get_volume_mesh(int *on, int *placement)
     const MedicalSeg::VolumeMesh m = MedicalSeg::get_volume_mesh();
     *on = m.on; *placement = m.placement;
 }
+int medseg_set_volume_interp(int on, int factor) { return MedicalSeg::set_volume_interp({ on != 0, factor }) ? 0 : 1; }
+void medseg_get_volume_interp(int *on, int *factor)
+{
+    const MedicalSeg::VolumeInterp v = MedicalSeg::get_volume_interp();
+    if (on) *on = v.on ? 1 : 0;
+    if (factor) *factor = v.factor;
+}
 int medseg_set_volume_measure(int on, int channel, int max_ends) { return MedicalSeg::set_volume_measure({ on != 0, channel, max_ends }) ? 0 : 1; }
 void medseg_get_volume_measure(int *on, int *channel, int *max_ends)
 {

@@ -149,6 +149,7 @@ public:
         table_["volume"] = [this](const Words &w) { cmd_volume(w); return true; };
         table_["volclean"] = [this](const Words &w) { cmd_volclean(w); return true; };
         table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
+        table_["volinterp"] = [this](const Words &w) { cmd_volinterp(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volmatch"] = [this](const Words &w) { cmd_volmatch(w); return true; };
@@ -172,6 +173,7 @@ public:
             "  volume on [6|18|26] [min N] [keep N] [spacing sx sy sz]|off - Label the slices of a directory as one volume into volume_report.json",
             "  volclean on [nofill] [close MM] [open MM]|off - With volume on: 3-D cavity fill, close and open by a ball in mm before labelling",
             "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
+            "  volinterp on [factor N|iso]|off - With volume on: shape-based slices between the slices before the stack is meshed (iso: spacing_z / in-plane)",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volmatch on [iou N/D]|off     - With volume on and truth: components matched to truth components, detection F1 and PQ per target",
@@ -450,6 +452,29 @@ private:
         }
         const MedicalSeg::VolumeMesh cur = MedicalSeg::get_volume_mesh();
         std::cout << "Volume mesh: " << (cur.on ? "on" : "off") << " " << (cur.placement == MI_UNET_MESH_NETS ? "nets" : "faces") << std::endl;
+    }
+
+    // volinterp on [factor N | iso] | volinterp off | volinterp (prints the setting in force)
+    void cmd_volinterp(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeInterp v;
+            bool ok = (w[1] == "off" && w.size() == 2) || (w[1] == "on" && (w.size() == 2 || (w.size() == 3 && w[2] == "iso") ||
+                                                                              (w.size() == 4 && w[2] == "factor")));
+            v.on = w[1] == "on";
+            if (ok && w.size() == 4) ok = to_int(w[3], v.factor) && v.factor != 0;      // (0 is spelt iso)
+            if (!ok) {
+                std::cerr << "Error: Invalid volinterp command (expected on [factor N|iso] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_interp(v)) {
+                std::cerr << "Volume interp unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeInterp cur = MedicalSeg::get_volume_interp();
+        std::cout << "Volume interp: " << (cur.on ? "on" : "off") << " " << (cur.factor ? "factor " + std::to_string(cur.factor) : std::string("iso"))
+                  << std::endl;
     }
 
     // volmeasure on [channel N] [ends N] | volmeasure off | volmeasure (prints the setting in force)

@@ -35,6 +35,7 @@ struct Settings {
     Volume volume;                                         // off; no handle holds it (process_image_batch reads it)
     VolumeClean volume_clean;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeMesh volume_mesh;                                // off; acts only with volume.on (process_image_batch reads it)
+    VolumeInterp volume_interp;                            // off; acts only with volume.on (process_image_batch reads it)
     VolumeMeasure volume_measure;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeTexture volume_texture;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeMatch volume_match;                              // off; acts only with volume.on and a truth_dir (process_image_batch reads it)

@@ -350,6 +350,20 @@ bool set_volume_mesh(const VolumeMesh &mesh)
         /*handle_side=*/false);
 }
 
+bool set_volume_interp(const VolumeInterp &interp)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_interp = interp;
+            const bool factor = interp.factor >= 0 && interp.factor <= MI_UNET_VINTERP_MAX_FACTOR;
+            return std::string(factor ? "" : "volume interp: the factor is 0 (iso) .. MI_UNET_VINTERP_MAX_FACTOR");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume interp: " << (interp.on ? "on" : "off") << ", factor " << (interp.factor ? std::to_string(interp.factor) : std::string("iso"));
+        },
+        /*handle_side=*/false);
+}
+
 bool set_volume_measure(const VolumeMeasure &measure)
 {
     return change_setting(
@@ -416,6 +430,7 @@ std::string get_truth_dir() { return current_settings().truth_dir; }
 Volume get_volume() { return current_settings().volume; }
 VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
+VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeMatch get_volume_match() { return current_settings().volume_match; }

@@ -1,5 +1,5 @@
 // volume_route.cpp -- the volume chain of MedicalSeg::process_image_batch (set_volume): the stages of include/mi_unet.h that take the
-// batch's masks as one volume -- clean, components, mesh, measure, texture, scores against a truth directory, lesion matching -- and
+// batch's masks as one volume -- clean, components, interpolation, mesh, measure, texture, scores against a truth directory, lesion matching -- and
 // the reports they write (volume_report.json, volume_score.json, the STL files, the <base>_volume_mask pictures).  routes.cpp fills the
 // stack and calls finish_volume; volume_route.h is what the two share.
 #include <cmath>
@@ -78,12 +78,14 @@ bool clean_volume(VolumeStack &st, const Settings &s, mi_unet_t *h, std::ostream
 // values = { 255 } on `h` (mi_unet_volume_mesh_host under MEDSEG_HOST_POSTPROCESS=1) -- a counting call, then one sized by its counts --
 // then the positions and metrics under the volume setting's spacing and the STL file of every target that has quads.  Returns the
 // "mesh" member of volume_report.json, from its leading comma on.  A failure is reported and returns an empty text: only this step ends.
-std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, const Settings &s, mi_unet_t *h, const std::string &output_dir, std::ostream &lg)
+// `spacing_z` is the distance of the D slices handed in: the volume setting's, or that over the factor behind interp_volume.
+std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, double spacing_z, const Settings &s, mi_unet_t *h, const std::string &output_dir,
+                        std::ostream &lg)
 {
     try {
         const std::vector<mi_unet_target> &targets = s.targets;
         const size_t K = targets.size();
-        const double spacing[3] = { s.volume.spacing_x, s.volume.spacing_y, s.volume.spacing_z };
+        const double spacing[3] = { s.volume.spacing_x, s.volume.spacing_y, spacing_z };
         const int value = 255, where = s.volume_mesh.placement;
         const char *const placement = where == MI_UNET_MESH_NETS ? "nets" : "faces";
         std::ostringstream js;
@@ -120,6 +122,53 @@ std::string mesh_volume(const uint8_t *planes, size_t D, size_t hw, const Settin
         return js.str();
     } catch (const std::exception &e) {
         report(lg, std::string("Volume mesh error: ") + e.what());
+        return std::string();
+    }
+}
+
+// set_volume_interp: every target's plane of `planes` ([K][D][H][W], the stack the mesh would have seen) through one
+// mi_unet_volume_interp call with values = { 255 } on `h` (mi_unet_volume_interp_host under MEDSEG_HOST_POSTPROCESS=1) under the in-plane
+// units of mi_unet_score_volume_units and the setting's factor (0: spacing_z over the smaller in-plane spacing, 1 .. 16).  `fine` receives
+// the interpolated stack [K][D'][H][W] and `factor` the factor used.  Returns the "interp" member of volume_report.json, from its leading
+// comma on.  A failure is reported, leaves `fine` empty and returns an empty text: only this step ends.
+std::string interp_volume(const uint8_t *planes, size_t D, size_t hw, const Settings &s, mi_unet_t *h, std::ostream &lg, std::vector<uint8_t> &fine,
+                          int &factor)
+{
+    try {
+        const std::vector<mi_unet_target> &targets = s.targets;
+        const Volume &v = s.volume;
+        const size_t K = targets.size();
+        const VolumeUnits u = volume_units(v, D);
+        factor = s.volume_interp.factor;
+        if (factor == 0) {
+            const double q = v.spacing_z / std::min(v.spacing_x, v.spacing_y);
+            factor = q < 1.0 ? 1 : q > (double)MI_UNET_VINTERP_MAX_FACTOR ? MI_UNET_VINTERP_MAX_FACTOR : (int)std::llround(q);
+        }
+        const int Dp = mi_unet_volume_interp_slices((int)D, factor);
+        if (Dp < 1) throw std::runtime_error(std::to_string(D) + " slices at factor " + std::to_string(factor) + " cannot be interpolated");
+        const int value = 255;
+        std::vector<uint8_t> out(K * (size_t)Dp * hw);
+        std::vector<mi_unet_vinterp_stat> stats(K);
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t)
+            stage_call(h, mi_unet_volume_interp, mi_unet_volume_interp_host, planes + t * D * hw, (int)D, g_cfg.height, g_cfg.width, &value, 1, u.units,
+                       factor, (const uint16_t *)nullptr, out.data() + t * (size_t)Dp * hw, (uint16_t *)nullptr, &stats[t]);
+        lg << "Volume interp: " << D << " slices -> " << Dp << ", " << K << " targets, factor " << factor << ", " << ms_since(t0) << " ms" << std::endl;
+        std::ostringstream js;
+        js << ",\n  \"interp\": {\"factor\": " << factor << ", \"slices\": " << Dp << ", \"spacing_z_mm\": " << json_number(v.spacing_z / factor)
+           << ", \"targets\": [";
+        for (size_t t = 0; t < K; ++t) {
+            const mi_unet_vinterp_stat &is = stats[t];
+            js << (t ? "," : "") << "\n    {\"label\": " << targets[t].cls << ", \"in_voxels\": " << is.in_voxels << ", \"out_voxels\": " << is.out_voxels
+               << ", \"mixed\": " << is.mixed << ", \"ties\": " << is.ties << ", \"volume_mm3\": "
+               << json_number((double)is.out_voxels * v.spacing_x * v.spacing_y * v.spacing_z / factor) << "}";
+        }
+        js << "\n  ]}";
+        fine.swap(out);
+        return js.str();
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume interp error: ") + e.what());
+        fine.clear();
         return std::string();
     }
 }
@@ -253,7 +302,9 @@ std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, cons
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
 // A stack that clean_volume cleaned comes with its "clean" object for the report and is written as pictures whether or not a filter
 // is active (without one they are the cleaned stack itself).  With set_volume_mesh on, the planes that were labelled -- `out` under a
-// filter, else the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets".  With set_volume_measure on,
+// filter, else the stack -- are meshed (mesh_volume) and the report gains the "mesh" object behind "targets"; with set_volume_interp on
+// those planes are interpolated first (interp_volume), the report gains the "interp" object in front of "mesh", and the mesh sees the
+// interpolated stack.  With set_volume_measure on,
 // the components stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member
 // "measure".  With set_volume_texture on, the ids are handed out likewise and every component object gains a last member "texture"
 // (texture_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
@@ -281,7 +332,15 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                        &value, 1, &opts, filter ? out.data() + t * D * hw : nullptr, ids.empty() ? nullptr : ids.data() + t * D * hw,
                        table.data() + t * cap, (int)cap, &found[t], &kept[t]);
         lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
-        const std::string mesh_json = s.volume_mesh.on ? mesh_volume(filter ? out.data() : st.planes.data(), D, hw, s, h, output_dir, lg) : std::string();
+        // the stack the mesh sees: with set_volume_interp on, its interpolated form under spacing_z / factor (the original after a failure)
+        const uint8_t *const labelled = filter ? out.data() : st.planes.data();
+        std::vector<uint8_t> fine;
+        int factor = 1;
+        const std::string interp_json = s.volume_interp.on ? interp_volume(labelled, D, hw, s, h, lg, fine, factor) : std::string();
+        const bool use_fine = !fine.empty();
+        const std::string mesh_json = !s.volume_mesh.on ? std::string()
+                                      : use_fine ? mesh_volume(fine.data(), fine.size() / (K * hw), hw, v.spacing_z / factor, s, h, output_dir, lg)
+                                                 : mesh_volume(labelled, D, hw, v.spacing_z, s, h, output_dir, lg);
         const std::vector<std::vector<std::string>> measured =
             s.volume_measure.on ? measure_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const std::vector<std::vector<std::string>> textured =
@@ -321,7 +380,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
             }
             js << (rows ? "\n    " : "") << "]}";
         }
-        js << "\n  ]" << mesh_json << "\n}\n";
+        js << "\n  ]" << interp_json << mesh_json << "\n}\n";
         VolumeArtefacts a;
         a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
         a.height = g_cfg.height; a.width = g_cfg.width;

@@ -71,7 +71,7 @@ struct VolumeStack {
 
 // (volume_route.cpp) The chain behind the last device call of a volume batch, every stage on `h` (its host form under
 // MEDSEG_HOST_POSTPROCESS=1): clean_volume when set_volume_clean is on -- its failure ends the chain -- then label_volume with whatever
-// of mesh, measure and texture is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
+// of interpolation, mesh, measure and texture is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
 // A failure of a step is reported to `lg` and fails no image.
 void finish_volume(VolumeStack &stack, const Settings &s, mi_unet_t *h, const std::string &output_dir, std::ostream &lg);
 

@@ -41,6 +41,7 @@ EXPORTS = [
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
+    "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
 ]
 
 
@@ -253,6 +254,43 @@ def _volume_clean_call(fn, head, masks, values, units, fill, close_r, open_r):
     _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, _ptr(un), C.byref(VolumeCleanOpts(int(fill), int(close_r), int(open_r))),
               _ptr(out), _ptr(stats)))
     return out, stats
+
+
+class VInterpStat(C.Structure):
+    """mi_unet_vinterp_stat: 40 bytes, five int64; VINTERP_DTYPE is the same layout for numpy"""
+    _fields_ = [("in_voxels", C.c_int64), ("out_voxels", C.c_int64), ("mixed", C.c_int64), ("mixed_set", C.c_int64), ("ties", C.c_int64)]
+
+
+VINTERP_DTYPE = np.dtype([(n, np.int64) for n, _ in VInterpStat._fields_])
+VINTERP_MAX_FACTOR = 16
+VINTERP_NONE = 2**31 - 1
+
+
+def _volume_interp_call(fn, head, masks, values, units_xy, factor, intensity):
+    """mi_unet_volume_interp (head = (handle,)) or its host form (head = ()): masks u8 [D,H,W] (or [H,W]: one slice), units_xy (ux, uy),
+    factor k, intensity u16 [D,H,W] or None -> (out u8 [n,D',H,W], stats VINTERP_DTYPE [n][, intensity_out u16 [D',H,W]]) with
+    D' = (D - 1) k + 1.  The library checks the values; an argument it refuses leaves D' at D."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    if masks.ndim != 3:
+        raise ValueError(f"masks {masks.shape} must be one u8 [D,H,W] array")
+    d, hh, ww = masks.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    un = np.ascontiguousarray(units_xy, np.int32).reshape(-1)
+    if un.size != 2:
+        raise ValueError("units_xy holds two integers: x, y")
+    if intensity is not None:
+        intensity = np.ascontiguousarray(intensity, np.uint16)
+        if intensity.shape != masks.shape:
+            raise ValueError(f"intensity {intensity.shape} must have the shape of masks {masks.shape}")
+    dp = max(volume_interp_slices(d, factor), d)
+    n = max(vals.size, 1)
+    out = np.zeros((n, dp, hh, ww), np.uint8)
+    stats = np.zeros(n, VINTERP_DTYPE)
+    iout = np.zeros((dp, hh, ww), np.uint16) if intensity is not None else None
+    _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, _ptr(un), int(factor), _ptr(intensity), _ptr(out), _ptr(iout), _ptr(stats)))
+    return (out, stats) if intensity is None else (out, stats, iout)
 
 
 class MeshVertex(C.Structure):
@@ -611,6 +649,10 @@ def lib():
                                                   C.c_void_p, C.c_void_p]
         L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
         L.mi_unet_volume_texture_derive.argtypes = [C.POINTER(VTexture), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VTextureFeatures)]
+        L.mi_unet_volume_interp_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_interp.argtypes = [C.c_void_p] + L.mi_unet_volume_interp_host.argtypes
+        L.mi_unet_volume_interp_slices.argtypes = [C.c_int, C.c_int]
         L.mi_unet_volume_match_host.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
         L.mi_unet_volume_match.argtypes = [C.c_void_p] + L.mi_unet_volume_match_host.argtypes
         L.mi_unet_volume_match_assign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -1004,6 +1046,12 @@ class Engine:
         found int32 [n], kept int32 [n], ids int32 [n,D,H,W] or None)"""
         return _volume_call(lib().mi_unet_volume_components, (self._h,), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
 
+    # ---- slices put between the slices of a stack of masks (mi_unet_volume_interp): needs the device, not the weights
+    def volume_interp(self, masks, values, units_xy, factor, intensity=None):
+        """masks u8 [D,H,W], in-plane units (ux, uy), factor k in 1 .. 16, intensity u16 [D,H,W] or None
+        -> (out u8 [n,D',H,W], stats VINTERP_DTYPE [n][, intensity_out u16 [D',H,W]]), D' = (D - 1) k + 1"""
+        return _volume_interp_call(lib().mi_unet_volume_interp, (self._h,), masks, values, units_xy, factor, intensity)
+
     # ---- a stack of masks cleaned as one volume (mi_unet_volume_clean): needs the device, not the weights
     def volume_clean(self, masks, values, units, fill=True, close_r=0, open_r=0):
         """masks u8 [D,H,W] of any size, values = the bytes whose sets are cleaned, units = the spacing (ux, uy, uz) as integers, the
@@ -1164,6 +1212,16 @@ def score_labels_host(pred, truth, values, quantile_ppm=50000, classes=0):
 def volume_components_host(masks, values, connectivity=26, min_voxels=0, keep_largest=0, cap=256, want_ids=False):
     """mi_unet_volume_components_host: Engine.volume_components as pure host arithmetic (needs no device)"""
     return _volume_call(lib().mi_unet_volume_components_host, (), masks, values, connectivity, min_voxels, keep_largest, cap, want_ids)
+
+
+def volume_interp_host(masks, values, units_xy, factor, intensity=None):
+    """mi_unet_volume_interp_host: Engine.volume_interp as sequential host arithmetic (needs no device)"""
+    return _volume_interp_call(lib().mi_unet_volume_interp_host, (), masks, values, units_xy, factor, intensity)
+
+
+def volume_interp_slices(d, factor) -> int:
+    """mi_unet_volume_interp_slices: (d - 1) factor + 1, or -1 for a d outside 1 .. 8192 or a factor outside 1 .. 16"""
+    return int(lib().mi_unet_volume_interp_slices(int(d), int(factor)))
 
 
 def volume_clean_host(masks, values, units, fill=True, close_r=0, open_r=0):

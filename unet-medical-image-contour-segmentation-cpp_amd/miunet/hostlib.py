@@ -23,6 +23,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_measure", "medseg_get_measure", "medseg_set_truth_dir", "medseg_get_truth_dir", "medseg_polygon_json_text_regions",
            "medseg_postprocess_mask_morph", "medseg_set_morphology", "medseg_get_morphology", "medseg_set_volume", "medseg_get_volume",
            "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
+           "medseg_set_volume_interp", "medseg_get_volume_interp",
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
            "medseg_set_volume_texture", "medseg_get_volume_texture"]
 
@@ -81,6 +82,9 @@ def lib():
         L.medseg_set_volume_mesh.argtypes = [C.c_int, C.c_int]
         L.medseg_get_volume_mesh.argtypes = [_i, _i]
         L.medseg_get_volume_mesh.restype = None
+        L.medseg_set_volume_interp.argtypes = [C.c_int, C.c_int]
+        L.medseg_get_volume_interp.argtypes = [_i, _i]
+        L.medseg_get_volume_interp.restype = None
         L.medseg_set_volume_measure.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_measure.argtypes = [_i, _i, _i]
         L.medseg_get_volume_measure.restype = None
@@ -249,6 +253,19 @@ def get_volume_mesh():
     on, placement = C.c_int(), C.c_int()
     lib().medseg_get_volume_mesh(C.byref(on), C.byref(placement))
     return {"on": bool(on.value), "placement": {v: k for k, v in MESH_PLACEMENTS.items()}[placement.value]}
+
+
+def set_volume_interp(on=True, factor=0) -> bool:
+    """MedicalSeg::set_volume_interp: with set_volume on, process_image_batch puts factor - 1 shape-based slices between the slices of
+    every target's labelled plane before it is meshed (factor 0 or "iso": spacing_z over the smaller in-plane spacing, 1 .. 16) and adds
+    an "interp" object to volume_report.json; needs no engine"""
+    return lib().medseg_set_volume_interp(int(bool(on)), 0 if factor == "iso" else int(factor)) == 0
+
+
+def get_volume_interp():
+    on, factor = C.c_int(), C.c_int()
+    lib().medseg_get_volume_interp(C.byref(on), C.byref(factor))
+    return {"on": bool(on.value), "factor": factor.value}
 
 
 def set_volume_measure(on=True, channel=0, max_ends=262144) -> bool:
