@@ -204,6 +204,34 @@ struct VolumeTexture {
 bool set_volume_texture(const VolumeTexture &texture);
 VolumeTexture get_volume_texture();
 
+// The run-length and size-zone matrices of every component of the labelled stack (mi_unet_volume_zones in include/mi_unet.h, DESIGN.md
+// 7.17).  It acts only together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits
+// (beside the channels set_volume_measure and set_volume_texture keep, when they differ), a failed slice all-zero; one
+// mi_unet_volume_zones call per target (mi_unet_volume_zones_host under MEDSEG_HOST_POSTPROCESS=1) on the ids mi_unet_volume_components
+// hands out, with m = min(found, MI_UNET_VOLUME_MAX_TABLE, 2^22 / (levels * max_run)) -- the log line says so when that cuts the table
+// short -- and a zone list of one record per voxel of the stack, at most 2^24; the list is sorted by component once and its slices go to
+// mi_unet_volume_zones_zone_features, the rows of both tables to mi_unet_volume_zones_run_features.  mode, levels, lo and width are
+// set_volume_texture's; max_run is the length of the last bin of the run tables.  Every component object of volume_report.json gains a
+// last member "zones" (behind "texture" when both are on): "levels", "mode" ("count" or "width"), "max_run", "glrlm" and "glrlm_axial"
+// ("runs", "clamped", "longest" -- the longest run over the 13 offsets, in both -- and the 16 features of mi_unet_vzone_features by their
+// names) and "glszm" ("zones", "largest" and the same 16).  Doubles carry 17 significant digits and a NaN is null.  The member is null
+// for a component that the volume filter dropped (no voxel carries its id) or that lies beyond m; "glszm" is null where the zone list
+// was cut, and the log says so.  The log gains "Volume zones: D slices, K targets, t ms".  A failure is reported as "Volume zones
+// error: ..." and ends only this step: the report is then written without the member.  Off (the default), every artefact and every log
+// line is what it was.  false with a message: a negative channel, a mode that does not exist, levels outside 2 .. 64, lo outside
+// 0 .. 65535, width outside 1 .. 65536 or max_run outside 2 .. 8192.
+struct VolumeZones {
+    bool on = false;
+    int channel = 0;
+    int mode = 0;                      // MI_UNET_VTEX_COUNT
+    int levels = 32;
+    int lo = 0;
+    int width = 1;
+    int max_run = 32;
+};
+bool set_volume_zones(const VolumeZones &zones);
+VolumeZones get_volume_zones();
+
 // The scored stack per lesion (mi_unet_volume_match in include/mi_unet.h).  It acts only where set_volume's `on` and
 // set_truth_dir already produce volume_score.json.  Per target the truth stack, recoded by truth == cls, is labelled with
 // mi_unet_volume_components under the volume setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE; the pred ids

@@ -86,6 +86,10 @@ void medseg_get_volume_match(int *on, int *iou_num, int *iou_den);
  * (include/medseg/process.h).  0 on success; medseg_get_volume_texture fills the six values. */
 int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width);
 void medseg_get_volume_texture(int *on, int *channel, int *mode, int *levels, int *lo, int *width);
+/* The run-length and size-zone matrices of every component of the labelled stack: MedicalSeg::set_volume_zones / get_volume_zones
+ * (include/medseg/process.h).  0 on success; medseg_get_volume_zones fills the seven values. */
+int medseg_set_volume_zones(int on, int channel, int mode, int levels, int lo, int width, int max_run);
+void medseg_get_volume_zones(int *on, int *channel, int *mode, int *levels, int *lo, int *width, int *max_run);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

@@ -954,6 +954,90 @@ int mi_unet_volume_interp_host(const uint8_t *masks, int D, int H, int W, const 
                                const uint16_t *intensity, uint8_t *out, uint16_t *intensity_out, mi_unet_vinterp_stat *stats);
 int mi_unet_volume_interp_slices(int D, int factor);
 
+/* ---- Volume zones: per component of a labelled stack its grey-level run-length and size-zone matrices -------------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  Everything up to the two feature
+ * functions is an exact integer count and independent of the order of evaluation.
+ * Input is ids, int32 [D][H][W], intensity, uint16 [D][H][W], and the number of components m, as mi_unet_volume_texture takes them; both
+ * buffers are required.
+ *   COMPONENT  exactly as in mi_unet_volume_texture: component r, 0 <= r < m, is the set of voxels with ids == r + 1.  0, -1 and anything
+ *              above m belong to no component.  The stage does not ask whether a set is connected.  An id that no voxel carries gives
+ *              an all-zero entry and all-zero rows.
+ *   OPTIONS    opts = { mode, levels L, lo, width, max_run R }; NULL is { MI_UNET_VTEX_COUNT, 32, 0, 1, 32 }.
+ *   LEVEL      mode, L, lo and width mean what they mean in mi_unet_vtexture_opts, and the level of a voxel is mi_unet_volume_texture's
+ *              formula: the same stack at the same options has the same levels in both stages.  A voxel's KEY is (r + 1) << 8 | level,
+ *              0 for a voxel of no component.
+ *   RUNS       the 13 offsets d are mi_unet_volume_texture's, the lexicographically positive half of the 26-neighbourhood.  For an offset
+ *              d a run is a maximal sequence p, p + d, .., p + (n - 1) d inside the volume whose voxels have one key that is not 0: one
+ *              component r and one level l.  rlm[r][l][min(n, R) - 1] counts the runs over all 13 offsets, rlm_axial the same over the 4
+ *              offsets with dz = 0.  The last bin collects every run of length >= R; the entry's `clamped` says how many runs were
+ *              longer than R, so 0 there means the table is the unclamped matrix.  R = 8192 never clamps: no run is longer than the
+ *              longest side.  Either pointer may be NULL: that table is not computed and its sums in the entry are 0.
+ *   ZONES      a zone is a 26-connected set of voxels with one key that is not 0.  Two components that touch at one level do not merge;
+ *              two separated parts of one id at one level are two zones.  *found is the number of zones over all components, always
+ *              exact.  zones[cap] holds the first min(found, cap) zones as { first, component, level, size }: `first` is the linear
+ *              index (z H + y) W + x of the zone's first voxel in raster order, `level` counts from 0, and the order is `first`
+ *              ascending, which is total.  The entries behind them are all-zero (the rule of mi_unet_volume_match's pair list).  With
+ *              zones NULL the zone half is not computed, found must be NULL too, and the entry's zone fields are 0.
+ *   ENTRY      voxels, imin, imax as in mi_unet_vtexture; longest_run over the 13 offsets, unclamped (0 without rlm); zones and
+ *              largest_zone, exact whatever cap is; runs and runs_axial, the two tables' sums; clamped and clamped_axial, the runs of
+ *              length >= R + 1 in each.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE (8192);
+ *   D * H * W <= 2^28: a voxel starts at most 13 runs, so every cell is below 13 * 2^28 < 2^32 and is a uint32_t; an index is an int32_t;
+ *   L in 2 .. MI_UNET_VTEX_MAX_LEVELS (64): the key's 8 level bits, and mi_unet_volume_texture's limit;
+ *   R in 2 .. MI_UNET_VZONES_MAX_RUN (8192): the longest side;
+ *   m in 1 .. MI_UNET_VOLUME_MAX_TABLE and m * L * R <= MI_UNET_VTEX_MAX_CELLS (2^22): 4096 components at 32 x 32; a table is at most
+ *           16 MiB;
+ *   cap in 1 .. MI_UNET_VZONES_MAX_CAP (2^24) when zones is given: the list is at most 256 MiB;
+ *   width in 1 .. 65536 and lo in 0 .. 65535: the range of a uint16_t; a mode that exists.
+ * mi_unet_volume_zones takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message that begins "mi_unet_volume_zones:", nothing queued
+ * and no output written: a null ids, intensity or table; exactly one of zones and found NULL; any limit broken.  A workspace that
+ * cannot be allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_zones_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle, same
+ * bytes.
+ * The two feature functions are pure host arithmetic in double over the non-zero cells (i, j, count) of one component's matrix: i =
+ * level + 1 (the IBSI's numbering), j = the run length (bin + 1) or the zone size, visited with i ascending, then j ascending.  The
+ * marginals n_i = sum over j and n_j = sum over i, N = sum count, sum i n_i and sum j n_j are exact 64-bit integers; everything after is
+ * double, with p = count / N, mu_i = (sum i n_i) / N and mu_j = (sum j n_j) / N:
+ *     short_emphasis = (sum n_j / j^2) / N; long_emphasis = (sum n_j j^2) / N; low_grey_emphasis = (sum n_i / i^2) / N;
+ *     high_grey_emphasis = (sum n_i i^2) / N; short_low = (sum c / (i^2 j^2)) / N; short_high = (sum c i^2 / j^2) / N;
+ *     long_low = (sum c j^2 / i^2) / N; long_high = (sum c i^2 j^2) / N; grey_nonuniformity = (sum n_i^2) / N and _norm = that / N;
+ *     size_nonuniformity = (sum n_j^2) / N and _norm = that / N; percentage = N / (voxels * directions), directions = 1 for zones;
+ *     grey_variance = sum (i - mu_i)^2 p; size_variance = sum (j - mu_j)^2 p; entropy = - sum p log2 p.
+ *   All 16 are NaN when N = 0.  mi_unet_volume_zones_run_features takes one row rlm[r] or rlm_axial[r] and directions 13 or 4;
+ *   mi_unet_volume_zones_zone_features takes nz records, uses only those with component == r (the whole list or a slice) and sorts them
+ *   by (level, size) itself.
+ * MI_UNET_EARG, output untouched: a null c, table, list (with nz > 0) or out; nz < 0; voxels < 1; L or R outside its range; directions
+ * not 13 or 4; a zone record of r whose level is outside 0 .. L - 1 or whose size is below 1.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VZONES_MAX_RUN 8192
+#define MI_UNET_VZONES_MAX_CAP 16777216         /* 2^24 */
+typedef struct mi_unet_vzones_opts { int mode, levels, lo, width, max_run; } mi_unet_vzones_opts;  /* default { MI_UNET_VTEX_COUNT, 32, 0, 1, 32 } */
+typedef struct mi_unet_vzones {        /* 56 bytes, no padding */
+    int32_t voxels, imin, imax;        /* voxels with this id; min / max of intensity over them */
+    int32_t longest_run;               /* over the 13 offsets, unclamped; 0 without rlm */
+    int32_t zones, largest_zone;       /* zones of this component and the voxels of its largest; 0 without zones */
+    int64_t runs, runs_axial;          /* sums of rlm[r] and of rlm_axial[r]; 0 for a table that was not asked for */
+    int64_t clamped, clamped_axial;    /* runs longer than R in each */
+} mi_unet_vzones;
+typedef struct mi_unet_vzone { int32_t first, component, level, size; } mi_unet_vzone;     /* 16 bytes */
+typedef struct mi_unet_vzone_features {        /* 128 bytes: 16 doubles */
+    double short_emphasis, long_emphasis, low_grey_emphasis, high_grey_emphasis, short_low, short_high, long_low, long_high,
+           grey_nonuniformity, grey_nonuniformity_norm, size_nonuniformity, size_nonuniformity_norm, percentage, grey_variance,
+           size_variance, entropy;
+} mi_unet_vzone_features;
+int mi_unet_volume_zones(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const uint16_t *intensity /* [D][H][W] host */, int D, int H,
+                         int W, int m, const mi_unet_vzones_opts *opts, mi_unet_vzones *table /* [m] */,
+                         uint32_t *rlm /* [m][L][R] or NULL */, uint32_t *rlm_axial /* [m][L][R] or NULL */,
+                         mi_unet_vzone *zones /* [cap] or NULL */, int cap, int *found /* NULL iff zones is NULL */);
+int mi_unet_volume_zones_host(const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const mi_unet_vzones_opts *opts,
+                              mi_unet_vzones *table, uint32_t *rlm, uint32_t *rlm_axial, mi_unet_vzone *zones, int cap, int *found);
+int mi_unet_volume_zones_run_features(const mi_unet_vzones *c, const uint32_t *rlm_row /* [L][R] */, int L, int R, int directions /* 13 or 4 */,
+                                      mi_unet_vzone_features *out);
+int mi_unet_volume_zones_zone_features(const mi_unet_vzones *c, const mi_unet_vzone *zones, int nz, int r, int L, mi_unet_vzone_features *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

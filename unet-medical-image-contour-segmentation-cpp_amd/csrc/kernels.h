@@ -17,6 +17,8 @@ struct mi_unet_vmeasure;
 struct mi_unet_vmatch_side;
 struct mi_unet_vmatch_pair;
 struct mi_unet_vtexture;
+struct mi_unet_vzones;
+struct mi_unet_vzone;
 
 namespace miunet {
 
@@ -479,5 +481,39 @@ struct VolumeInterpArgs { int D = 0, H = 0, W = 0, n = 0, ux = 1, uy = 1, k = 1;
 size_t volume_interp_workspace_bytes(int D, int H, int W, int n);
 hipError_t launch_volume_interp(const uint8_t *masks, const uint16_t *intensity, const VolumeInterpArgs &a, uint8_t *out,
                                 uint16_t *intensity_out, unsigned long long *counts, void *ws, hipStream_t s);
+
+// Volume zones (volume_zones.hip; include/mi_unet.h: mi_unet_volume_zones), behind launch_volume_texture_keys on its key
+// stack: keys int32 [D][H][W], (r + 1) << 8 | level, 0 = no component.  Every result is an integer sum, minimum or maximum: nothing depends
+// on the order in which atomics arrive.  No workgroup waits for another; every walk ends at the volume's border at the latest.
+//   launch_volume_zones_part / _join: for a call whose m L^2 passes what launch_volume_texture_keys takes at once (2^22) while m L R does
+//       not: part = the ids of components first .. first + count - 1 renumbered from 1, which that launcher turns into keys in place (its
+//       range at range + first); join moves their component numbers back and writes them into the key stack, zeroed by the caller.
+//   launch_volume_zones_runs: zeroes acc [m] and, over this call's extent, inter [m][L][R] and axial [m][L][R]; k_vzn_voxels counts
+//       acc[r].voxels (a wave carries a component's count across its segments); then, with want != 0, k_vzn_runs, the hot path: 7.15's
+//       tile with the halo of the backward neighbours in LDS, a lane per voxel; for each offset the lane whose backward neighbour has
+//       another key starts a run and walks it forward, through LDS while inside the tile and through memory beyond it, and adds 1 to
+//       cell (r, level, min(n, R) - 1) of axial (the 4 offsets with dz = 0, want & VZN_WANT_AXIAL) or of inter (the 9 with dz = 1,
+//       want & VZN_WANT_INTER); the lanes of a wave that name one cell merge first.  acc[r].longest and the two clamped counts likewise.
+//   launch_volume_zones_list: k_vzn_init (parent = the start of the voxel's run of one key inside its 64-lane segment), k_vzn_merge
+//       (7.9's union-find, two voxels join iff their keys are equal and not 0, 26-connectivity, the implied unions left out; parents only
+//       decrease, so a root is its zone's first voxel in raster order), k_vzn_sizes (size [root], a wave carries a root's count),
+//       k_vzn_flags (roots per 256 voxels into scan), the exclusive scan of those counts in two levels (7.12's scheme: no look-back,
+//       nobody waits) with *found, k_vzn_list: the records whose position is below keep_zones at their final position, `first`
+//       ascending, and k_vzn_tally: acc[r].zones and acc[r].largest from every root, a wave carrying a component's count.  scan holds vzn_scan_ints(D * H * W) ints.
+//   launch_volume_zones_finish: a workgroup per component: inter += axial (inter then holds the 13-offset table) when both are wanted,
+//       and table[r] from range[r], acc[r] and the tables' sums.
+constexpr int VZN_WANT_AXIAL = 1, VZN_WANT_INTER = 2;
+constexpr size_t kVznEagerZones = 65536;                // records that travel with the first copy (volume_zones.cpp)
+struct VolumeZonesArgs { int D = 0, H = 0, W = 0, m = 0, L = 32, R = 32; };
+struct VznAcc { int voxels, longest, zones, largest; unsigned long long clamped_axial, clamped_inter; };      // 32 bytes
+size_t vzn_scan_ints(size_t dhw);
+hipError_t launch_volume_zones_part(const int32_t *ids, const VolumeZonesArgs &a, int first, int count, int32_t *part, hipStream_t s);
+hipError_t launch_volume_zones_join(const int32_t *part, const VolumeZonesArgs &a, int first, int32_t *keys, hipStream_t s);
+hipError_t launch_volume_zones_runs(const int32_t *keys, const VolumeZonesArgs &a, int want, VznAcc *acc, uint32_t *inter, uint32_t *axial,
+                                    hipStream_t s);
+hipError_t launch_volume_zones_list(const int32_t *keys, const VolumeZonesArgs &a, int32_t *parent, int32_t *size, int32_t *scan, VznAcc *acc,
+                                    ::mi_unet_vzone *zones, int keep_zones, int32_t *found, hipStream_t s);
+hipError_t launch_volume_zones_finish(const int2 *range, const VolumeZonesArgs &a, int want, const VznAcc *acc, uint32_t *inter,
+                                      const uint32_t *axial, ::mi_unet_vzones *table, hipStream_t s);
 
 }  // namespace miunet

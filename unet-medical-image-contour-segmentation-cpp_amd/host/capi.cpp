@@ -222,6 +222,15 @@ void medseg_get_volume_texture(int *on, int *channel, int *mode, int *levels, in
     const MedicalSeg::VolumeTexture t = MedicalSeg::get_volume_texture();
     *on = t.on; *channel = t.channel; *mode = t.mode; *levels = t.levels; *lo = t.lo; *width = t.width;
 }
+int medseg_set_volume_zones(int on, int channel, int mode, int levels, int lo, int width, int max_run)
+{
+    return MedicalSeg::set_volume_zones({ on != 0, channel, mode, levels, lo, width, max_run }) ? 0 : 1;
+}
+void medseg_get_volume_zones(int *on, int *channel, int *mode, int *levels, int *lo, int *width, int *max_run)
+{
+    const MedicalSeg::VolumeZones z = MedicalSeg::get_volume_zones();
+    *on = z.on; *channel = z.channel; *mode = z.mode; *levels = z.levels; *lo = z.lo; *width = z.width; *max_run = z.max_run;
+}
 int medseg_set_volume_match(int on, int iou_num, int iou_den) { return MedicalSeg::set_volume_match({ on != 0, iou_num, iou_den }) ? 0 : 1; }
 void medseg_get_volume_match(int *on, int *iou_num, int *iou_den)
 {

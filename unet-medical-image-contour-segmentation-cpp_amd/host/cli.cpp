@@ -152,6 +152,7 @@ public:
         table_["volinterp"] = [this](const Words &w) { cmd_volinterp(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
+        table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
         table_["volmatch"] = [this](const Words &w) { cmd_volmatch(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
@@ -176,6 +177,7 @@ public:
             "  volinterp on [factor N|iso]|off - With volume on: shape-based slices between the slices before the stack is meshed (iso: spacing_z / in-plane)",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
+            "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
             "  volmatch on [iou N/D]|off     - With volume on and truth: components matched to truth components, detection F1 and PQ per target",
             "  exit                          - Cleanup and exit",
             "",
@@ -540,6 +542,48 @@ private:
         std::cout << "Volume texture: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
         if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo << std::endl;
         else std::cout << "count" << std::endl;
+    }
+
+    // volzones on [levels N] [count | width W [lo L]] [run N] [channel N] | volzones off | volzones (prints the setting in force)
+    void cmd_volzones(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeZones z;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            z.on = w[1] == "on";
+            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
+            for (size_t i = 2; ok && i < w.size();) {
+                if (w[i] == "count") {
+                    ok = !binned;
+                    binned = true;
+                    i += 1;
+                    continue;
+                }
+                int value = 0;
+                ok = i + 1 < w.size() && to_int(w[i + 1], value);
+                if (!ok) break;
+                if (w[i] == "levels") z.levels = value;
+                else if (w[i] == "channel") z.channel = value;
+                else if (w[i] == "run") z.max_run = value;
+                else if (w[i] == "width" && !binned) { z.mode = MI_UNET_VTEX_WIDTH; z.width = value; binned = true; }
+                else if (w[i] == "lo" && z.mode == MI_UNET_VTEX_WIDTH) z.lo = value;
+                else ok = false;
+                i += 2;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volzones command (expected on [levels N] [count|width W [lo L]] [run N] [channel N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_zones(z)) {
+                std::cerr << "Volume zones unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeZones cur = MedicalSeg::get_volume_zones();
+        std::cout << "Volume zones: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
+        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
+        else std::cout << "count";
+        std::cout << " run " << cur.max_run << std::endl;
     }
 
     // volmatch on [iou N/D] | volmatch off | volmatch (prints the setting in force)

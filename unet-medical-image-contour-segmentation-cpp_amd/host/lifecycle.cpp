@@ -398,6 +398,27 @@ bool set_volume_texture(const VolumeTexture &texture)
         /*handle_side=*/false);
 }
 
+bool set_volume_zones(const VolumeZones &zones)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_zones = zones;
+            if (zones.channel < 0) return std::string("volume zones: the channel is not negative");
+            if (zones.mode != MI_UNET_VTEX_COUNT && zones.mode != MI_UNET_VTEX_WIDTH)
+                return std::string("volume zones: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
+            if (zones.levels < 2 || zones.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume zones: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
+            if (zones.lo < 0 || zones.lo > 65535) return std::string("volume zones: lo is 0 .. 65535");
+            if (zones.width < 1 || zones.width > 65536) return std::string("volume zones: width is 1 .. 65536");
+            return std::string(zones.max_run >= 2 && zones.max_run <= MI_UNET_VZONES_MAX_RUN ? "" : "volume zones: max_run is 2 .. MI_UNET_VZONES_MAX_RUN");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume zones: " << (zones.on ? "on" : "off") << ", channel " << zones.channel << ", levels " << zones.levels << ", "
+               << (zones.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(zones.width) + " lo " + std::to_string(zones.lo) : std::string("count"))
+               << ", run " << zones.max_run;
+        },
+        /*handle_side=*/false);
+}
+
 bool set_volume_match(const VolumeMatch &match)
 {
     return change_setting(
@@ -433,6 +454,7 @@ VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
+VolumeZones get_volume_zones() { return current_settings().volume_zones; }
 VolumeMatch get_volume_match() { return current_settings().volume_match; }
 
 std::ofstream &get_log_file() { return g_log_file; }

@@ -1,7 +1,8 @@
 // volume_route.cpp -- the volume chain of MedicalSeg::process_image_batch (set_volume): the stages of include/mi_unet.h that take the
-// batch's masks as one volume -- clean, components, interpolation, mesh, measure, texture, scores against a truth directory, lesion matching -- and
+// batch's masks as one volume -- clean, components, interpolation, mesh, measure, texture, zones, scores against a truth directory, lesion matching -- and
 // the reports they write (volume_report.json, volume_score.json, the STL files, the <base>_volume_mask pictures).  routes.cpp fills the
 // stack and calls finish_volume; volume_route.h is what the two share.
+#include <algorithm>
 #include <cmath>
 #include <filesystem>
 #include <fstream>
@@ -297,6 +298,91 @@ std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, cons
     }
 }
 
+// set_volume_zones: per target one mi_unet_volume_zones call on `h` (mi_unet_volume_zones_host under MEDSEG_HOST_POSTPROCESS=1) over the
+// ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's zones channel, with m = min(found, cap, 2^22 / (levels * max_run))
+// and a zone list of one record per voxel of the stack, at most 2^24; the list is sorted by component once (a stable sort: a
+// component's records keep their order), its slices go to mi_unet_volume_zones_zone_features and the rows of both tables to
+// mi_unet_volume_zones_run_features.  Returns, per target and table row, the "zones" member of the row's component object in
+// volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
+std::vector<std::vector<std::string>> zones_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
+                                                   size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+{
+    try {
+        const VolumeZones &zs = s.volume_zones;
+        const size_t K = s.targets.size(), D = st.D, hw = st.hw, L = (size_t)zs.levels, R = (size_t)zs.max_run;
+        if (zs.channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(zs.channel) + " of " + std::to_string(g_cfg.in_ch));
+        const mi_unet_vzones_opts opts{ zs.mode, zs.levels, zs.lo, zs.width, zs.max_run };
+        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * R);
+        const int list_cap = (int)std::min<size_t>(D * hw, (size_t)MI_UNET_VZONES_MAX_CAP);
+        std::vector<std::vector<std::string>> members(K);
+        size_t cut = 0, lists_cut = 0;                          // components beyond the measured count, and targets whose list was cut
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const size_t rows = std::min<size_t>((size_t)found[t], cap);
+            const int m = (int)std::min(rows, most);
+            if (m < 1) continue;
+            cut += rows - (size_t)m;
+            std::vector<mi_unet_vzones> table((size_t)m);
+            std::vector<uint32_t> rlm((size_t)m * L * R), axial((size_t)m * L * R);
+            std::vector<mi_unet_vzone> list((size_t)list_cap);
+            int n_zones = 0;
+            stage_call(h, mi_unet_volume_zones, mi_unet_volume_zones_host, ids.data() + t * D * hw, st.zones_intensity(), (int)D, g_cfg.height,
+                       g_cfg.width, m, &opts, table.data(), rlm.data(), axial.data(), list.data(), list_cap, &n_zones);
+            const bool whole = n_zones <= list_cap;
+            lists_cut += !whole;
+            list.resize((size_t)std::min(n_zones, list_cap));
+            std::stable_sort(list.begin(), list.end(), [](const mi_unet_vzone &a, const mi_unet_vzone &b) { return a.component < b.component; });
+            std::vector<size_t> first((size_t)m + 1, 0);        // component r's records are list[first[r] .. first[r + 1])
+            for (const mi_unet_vzone &z : list) ++first[(size_t)z.component + 1];
+            for (int r = 0; r < m; ++r) first[(size_t)r + 1] += first[(size_t)r];
+            for (size_t r = 0; r < rows; ++r) {
+                if (r >= (size_t)m || table[r].voxels < 1) {    // beyond the measured count, or dropped by the volume filter: no voxel carries its id
+                    members[t].push_back(", \"zones\": null");
+                    continue;
+                }
+                const mi_unet_vzones &c = table[r];
+                std::ostringstream js;
+                auto features = [&](const mi_unet_vzone_features &f) {
+                    const double *const v = &f.short_emphasis;
+                    static const char *const names[16] = { "short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low",
+                                                           "short_high", "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm",
+                                                           "size_nonuniformity", "size_nonuniformity_norm", "percentage", "grey_variance",
+                                                           "size_variance", "entropy" };
+                    for (int k = 0; k < 16; ++k) js << ", \"" << names[k] << "\": " << json_number(v[k]);
+                };
+                auto runs = [&](const char *key, const uint32_t *row, int directions, int64_t n, int64_t clamped) {
+                    mi_unet_vzone_features f{};
+                    checked(mi_unet_volume_zones_run_features, &c, row, (int)L, (int)R, directions, &f);
+                    js << ", \"" << key << "\": {\"runs\": " << n << ", \"clamped\": " << clamped << ", \"longest\": " << c.longest_run;
+                    features(f);
+                    js << "}";
+                };
+                js << ", \"zones\": {\"levels\": " << L << ", \"mode\": \"" << (zs.mode == MI_UNET_VTEX_WIDTH ? "width" : "count") << "\", \"max_run\": " << R;
+                runs("glrlm", rlm.data() + r * L * R, 13, c.runs, c.clamped);
+                runs("glrlm_axial", axial.data() + r * L * R, 4, c.runs_axial, c.clamped_axial);
+                if (whole) {
+                    mi_unet_vzone_features f{};
+                    checked(mi_unet_volume_zones_zone_features, &c, list.data() + first[r], (int)(first[r + 1] - first[r]), (int)r, (int)L, &f);
+                    js << ", \"glszm\": {\"zones\": " << c.zones << ", \"largest\": " << c.largest_zone;
+                    features(f);
+                    js << "}}";
+                } else {
+                    js << ", \"glszm\": null}";
+                }
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume zones: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
+        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels and run " << R << "; " << cut << " not measured)";
+        if (lists_cut) lg << " (the zone list of " << lists_cut << " targets was cut at " << list_cap << " records: no glszm there)";
+        lg << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume zones error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -307,7 +393,7 @@ std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, cons
 // interpolated stack.  With set_volume_measure on,
 // the components stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member
 // "measure".  With set_volume_texture on, the ids are handed out likewise and every component object gains a last member "texture"
-// (texture_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
+// (texture_volume), and with set_volume_zones on a last member "zones" behind it (zones_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
 // empty after a failure.
 struct VolumeIds {
     std::vector<int32_t> ids, found;
@@ -323,7 +409,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || numbered ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const auto t0 = hr_clock::now();
@@ -345,6 +431,8 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
             s.volume_measure.on ? measure_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const std::vector<std::vector<std::string>> textured =
             s.volume_texture.on ? texture_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
+        const std::vector<std::vector<std::string>> zoned =
+            s.volume_zones.on ? zones_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -376,7 +464,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
-                   << (textured.empty() ? std::string() : textured[t][r]) << "}";
+                   << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]}";
         }

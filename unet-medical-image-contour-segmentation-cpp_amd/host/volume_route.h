@@ -42,11 +42,15 @@ void stage_call(mi_unet_t *h, OnDevice on_device, OnHost on_host, Args... args)
 // finish_volume runs once, behind the last device call of the batch.
 struct VolumeStack {
     // `s` decides what the stack keeps beside the planes: with set_volume_measure on, its channel of every slice's normalised tile; with
-    // set_volume_texture on, its channel likewise, in a stack of its own only when the two channels differ
+    // set_volume_texture on, its channel likewise, in a stack of its own only when the two channels differ; with set_volume_zones on, its
+    // channel, in a stack of its own only when neither of the other two holds it
     VolumeStack(size_t slices, size_t hw, const Settings &s)
         : channel(s.volume_measure.on ? s.volume_measure.channel : -1), texture_channel(s.volume_texture.on ? s.volume_texture.channel : -1),
+          zones_channel(s.volume_zones.on ? s.volume_zones.channel : -1),
           planes(s.targets.size() * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0),
-          texture_own(texture_channel >= 0 && texture_channel != channel ? slices * hw : 0, 0), bases(slices), names(slices), D(slices), hw(hw)
+          texture_own(texture_channel >= 0 && texture_channel != channel ? slices * hw : 0, 0),
+          zones_own(zones_channel >= 0 && zones_channel != channel && zones_channel != texture_channel ? slices * hw : 0, 0), bases(slices),
+          names(slices), D(slices), hw(hw)
     {
     }
     // image i of the batch is complete: plane t of its K final 0 / 255 pictures becomes slice i of target t; `tile` is its normalised
@@ -58,20 +62,27 @@ struct VolumeStack {
             for (size_t p = 0; p < hw; ++p) intensity[i * hw + p] = tile[p * C + (size_t)channel];
         if (!texture_own.empty() && (size_t)texture_channel < C)
             for (size_t p = 0; p < hw; ++p) texture_own[i * hw + p] = tile[p * C + (size_t)texture_channel];
+        if (!zones_own.empty() && (size_t)zones_channel < C)
+            for (size_t p = 0; p < hw; ++p) zones_own[i * hw + p] = tile[p * C + (size_t)zones_channel];
         bases[i] = base;
     }
     const uint16_t *texture_intensity() const { return texture_own.empty() ? intensity.data() : texture_own.data(); }
-    int channel, texture_channel;                      // -1: not kept
+    const uint16_t *zones_intensity() const
+    {
+        return !zones_own.empty() ? zones_own.data() : zones_channel == channel ? intensity.data() : texture_intensity();
+    }
+    int channel, texture_channel, zones_channel;       // -1: not kept
     std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
     std::vector<uint16_t> intensity;                   // [D][H][W] or empty: the measured channel of the normalised tiles, widened
     std::vector<uint16_t> texture_own;                 // [D][H][W] or empty: the texture's channel where it is not the measured one
+    std::vector<uint16_t> zones_own;                   // [D][H][W] or empty: the zones' channel where neither of the two above holds it
     std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
     size_t D, hw;
 };
 
 // (volume_route.cpp) The chain behind the last device call of a volume batch, every stage on `h` (its host form under
 // MEDSEG_HOST_POSTPROCESS=1): clean_volume when set_volume_clean is on -- its failure ends the chain -- then label_volume with whatever
-// of interpolation, mesh, measure and texture is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
+// of interpolation, mesh, measure, texture and zones is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
 // A failure of a step is reported to `lg` and fails no image.
 void finish_volume(VolumeStack &stack, const Settings &s, mi_unet_t *h, const std::string &output_dir, std::ostream &lg);
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
+    "mi_unet_volume_zones", "mi_unet_volume_zones_host", "mi_unet_volume_zones_run_features", "mi_unet_volume_zones_zone_features",
 ]
 
 
@@ -431,6 +432,64 @@ def _volume_texture_call(fn, head, ids, intensity, m, levels, mode, lo, width, w
     return table, hist, glcm, axial
 
 
+class VZonesOpts(C.Structure):
+    """mi_unet_vzones_opts; the default is { VTEX_COUNT, 32, 0, 1, 32 }"""
+    _fields_ = [("mode", C.c_int), ("levels", C.c_int), ("lo", C.c_int), ("width", C.c_int), ("max_run", C.c_int)]
+
+
+class VZones(C.Structure):
+    """mi_unet_vzones: 56 bytes, six int32 then four int64; VZONES_DTYPE is the same layout for numpy"""
+    _fields_ = ([(n, C.c_int32) for n in ("voxels", "imin", "imax", "longest_run", "zones", "largest_zone")] +
+                [(n, C.c_int64) for n in ("runs", "runs_axial", "clamped", "clamped_axial")])
+
+
+class VZone(C.Structure):
+    """mi_unet_vzone: 16 bytes; VZONE_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int32) for n in ("first", "component", "level", "size")]
+
+
+class VZoneFeatures(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low", "short_high",
+                                          "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm", "size_nonuniformity",
+                                          "size_nonuniformity_norm", "percentage", "grey_variance", "size_variance", "entropy")]
+
+
+VZONES_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VZones._fields_])
+VZONE_DTYPE = np.dtype([(n, np.int32) for n, _ in VZone._fields_])
+VZONES_MAX_RUN = 8192
+VZONES_MAX_CAP = 1 << 24
+
+
+def _volume_zones_call(fn, head, ids, intensity, m, levels, mode, lo, width, max_run, want_runs, want_axial, cap):
+    """mi_unet_volume_zones (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape, m components, levels / mode ("count", "width" or the number) / lo / width / max_run = the options, want_runs and
+    want_axial = which tables to compute, cap = the length of the zone list (None: a record per voxel, at most 2^24; 0: no zone half)
+    -> (table VZONES_DTYPE [m], rlm u32 [m, L, R] or None, rlm_axial or None, zones VZONE_DTYPE [cap] or None, found or None).  The
+    library checks the values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    d, hh, ww = ids.shape
+    rows, lv, rn = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_run), 1), VZONES_MAX_RUN)
+    if rows * lv * rn > 2 * VTEX_MAX_CELLS:
+        rows = 1                                                 # (refused by the library; no need for the memory)
+    table = np.zeros(rows, VZONES_DTYPE)
+    rlm = np.zeros((rows, lv, rn), np.uint32) if want_runs else None
+    axial = np.zeros((rows, lv, rn), np.uint32) if want_axial else None
+    if cap is None:
+        cap = min(max(ids.size, 1), VZONES_MAX_CAP)
+    cap = int(cap)
+    zones = np.zeros(min(max(cap, 1), VZONES_MAX_CAP), VZONE_DTYPE) if cap else None
+    found = C.c_int(0)
+    opts = VZonesOpts(int(VTEX_MODES.get(mode, mode)), int(levels), int(lo), int(width), int(max_run))
+    _check(fn(*head, _ptr(ids), _ptr(intensity), d, hh, ww, int(m), C.byref(opts), _ptr(table), _ptr(rlm), _ptr(axial), _ptr(zones), cap,
+              C.byref(found) if cap else None))
+    return table, rlm, axial, zones, (found.value if cap else None)
+
+
 class VMatchCounts(C.Structure):
     _fields_ = [("tp", C.c_int32), ("fp", C.c_int32), ("fn", C.c_int32)]
 
@@ -653,6 +712,11 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_interp.argtypes = [C.c_void_p] + L.mi_unet_volume_interp_host.argtypes
         L.mi_unet_volume_interp_slices.argtypes = [C.c_int, C.c_int]
+        L.mi_unet_volume_zones_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.mi_unet_volume_zones.argtypes = [C.c_void_p] + L.mi_unet_volume_zones_host.argtypes
+        L.mi_unet_volume_zones_run_features.argtypes = [C.POINTER(VZones), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(VZoneFeatures)]
+        L.mi_unet_volume_zones_zone_features.argtypes = [C.POINTER(VZones), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(VZoneFeatures)]
         L.mi_unet_volume_match_host.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
         L.mi_unet_volume_match.argtypes = [C.c_void_p] + L.mi_unet_volume_match_host.argtypes
         L.mi_unet_volume_match_assign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -1072,6 +1136,14 @@ class Engine:
         the 13 forward neighbours and over the 4 in-plane ones (include/mi_unet.h)"""
         return _volume_texture_call(lib().mi_unet_volume_texture, (self._h,), ids, intensity, m, levels, mode, lo, width, want)
 
+    # ---- the run-length and size-zone matrices of the components of a labelled stack (mi_unet_volume_zones): needs the device, not the weights
+    def volume_zones(self, ids, intensity, m, levels=32, mode="count", lo=0, width=1, max_run=32, want_runs=True, want_axial=True, cap=None):
+        """ids int32 [D,H,W], intensity u16 [D,H,W], m components -> (table VZONES_DTYPE [m], rlm u32 [m, levels, max_run] or None,
+        rlm_axial or None, zones VZONE_DTYPE [cap] or None, found or None); cap = None: a record per voxel (at most 2^24), 0: no zone
+        half.  The library checks the values and the limits"""
+        return _volume_zones_call(lib().mi_unet_volume_zones, (self._h,), ids, intensity, m, levels, mode, lo, width, max_run, want_runs,
+                                  want_axial, cap)
+
     # ---- the components of a labelled stack measured (mi_unet_volume_measure): needs the device, not the weights
     def volume_measure(self, ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
         """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W] or None, m = the components
@@ -1242,6 +1314,34 @@ def volume_measure_host(ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None
 def volume_texture_host(ids, intensity, m, levels=32, mode="count", lo=0, width=1, want=("glcm", "axial")):
     """mi_unet_volume_texture_host: Engine.volume_texture as sequential host arithmetic (needs no device)"""
     return _volume_texture_call(lib().mi_unet_volume_texture_host, (), ids, intensity, m, levels, mode, lo, width, want)
+
+
+def volume_zones_host(ids, intensity, m, levels=32, mode="count", lo=0, width=1, max_run=32, want_runs=True, want_axial=True, cap=None):
+    """mi_unet_volume_zones_host: Engine.volume_zones as sequential host arithmetic (needs no device)"""
+    return _volume_zones_call(lib().mi_unet_volume_zones_host, (), ids, intensity, m, levels, mode, lo, width, max_run, want_runs, want_axial, cap)
+
+
+def _vzones_entry(comp):
+    return comp if isinstance(comp, VZones) else VZones(**{n: int(comp[n]) for n, _ in VZones._fields_})
+
+
+def volume_zones_run_features(comp, rlm_row, directions=13):
+    """mi_unet_volume_zones_run_features of one component (a VZones, or one VZONES_DTYPE record) and its row u32 [L, R] of rlm (directions
+    13) or rlm_axial (4) -> dict of the 16 features"""
+    rlm_row = np.ascontiguousarray(rlm_row, np.uint32)
+    out = VZoneFeatures()
+    _check(lib().mi_unet_volume_zones_run_features(C.byref(_vzones_entry(comp)), _ptr(rlm_row), int(rlm_row.shape[0]), int(rlm_row.shape[1]),
+                                                   int(directions), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VZoneFeatures._fields_}
+
+
+def volume_zones_zone_features(comp, zones, r, levels):
+    """mi_unet_volume_zones_zone_features of component r (its VZones, or one VZONES_DTYPE record) over zones VZONE_DTYPE [nz] (the whole
+    list or a slice) -> dict of the 16 features"""
+    zones = np.ascontiguousarray(zones, VZONE_DTYPE)
+    out = VZoneFeatures()
+    _check(lib().mi_unet_volume_zones_zone_features(C.byref(_vzones_entry(comp)), _ptr(zones), int(zones.size), int(r), int(levels), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VZoneFeatures._fields_}
 
 
 def volume_texture_derive(comp, hist, glcm=None):

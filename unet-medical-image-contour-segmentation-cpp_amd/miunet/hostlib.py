@@ -25,7 +25,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
            "medseg_set_volume_interp", "medseg_get_volume_interp",
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
-           "medseg_set_volume_texture", "medseg_get_volume_texture"]
+           "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones"]
 
 
 def lib():
@@ -94,6 +94,9 @@ def lib():
         L.medseg_set_volume_texture.argtypes = [C.c_int] * 6
         L.medseg_get_volume_texture.argtypes = [_i] * 6
         L.medseg_get_volume_texture.restype = None
+        L.medseg_set_volume_zones.argtypes = [C.c_int] * 7
+        L.medseg_get_volume_zones.argtypes = [_i] * 7
+        L.medseg_get_volume_zones.restype = None
         _LIB = L
     return _LIB
 
@@ -296,6 +299,21 @@ def get_volume_texture():
     lib().medseg_get_volume_texture(*[C.byref(x) for x in v])
     on, channel, mode, levels, lo, width = (x.value for x in v)
     return {"on": bool(on), "channel": channel, "mode": VTEX_MODES[mode], "levels": levels, "lo": lo, "width": width}
+
+
+def set_volume_zones(on=True, channel=0, mode="count", levels=32, lo=0, width=1, max_run=32) -> bool:
+    """MedicalSeg::set_volume_zones: with set_volume on, process_image_batch adds the run-length and size-zone matrices' features of
+    every component of the labelled stack (mi_unet_volume_zones over `channel` of the normalised tiles) as a "zones" member of
+    volume_report.json; needs no engine"""
+    mode = VTEX_MODES.index(mode) if mode in VTEX_MODES else int(mode)
+    return lib().medseg_set_volume_zones(int(bool(on)), int(channel), mode, int(levels), int(lo), int(width), int(max_run)) == 0
+
+
+def get_volume_zones():
+    v = [C.c_int() for _ in range(7)]
+    lib().medseg_get_volume_zones(*[C.byref(x) for x in v])
+    on, channel, mode, levels, lo, width, max_run = (x.value for x in v)
+    return {"on": bool(on), "channel": channel, "mode": VTEX_MODES[mode], "levels": levels, "lo": lo, "width": width, "max_run": max_run}
 
 
 def set_volume_match(on=True, iou=(1, 2)) -> bool:
