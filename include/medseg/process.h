@@ -232,6 +232,37 @@ struct VolumeZones {
 bool set_volume_zones(const VolumeZones &zones);
 VolumeZones get_volume_zones();
 
+// The neighbourhood-difference, dependence and distance-zone tables of every component of the labelled stack (mi_unet_volume_nbhood in
+// include/mi_unet.h).  It acts only together with set_volume's `on`.  The stack keeps `channel` of every slice's
+// normalised tile widened to 16 bits (beside the channels set_volume_measure, set_volume_texture and set_volume_zones keep, when it
+// differs from all of them), a failed slice all-zero; one mi_unet_volume_nbhood call per target (mi_unet_volume_nbhood_host under
+// MEDSEG_HOST_POSTPROCESS=1) on the ids mi_unet_volume_components hands out, all eight tables, with m = min(found,
+// MI_UNET_VOLUME_MAX_TABLE, 2^22 / (levels * max(levels, 32, max_dist))) -- the log line says so when that cuts the table short -- and
+// the rows of every component go to mi_unet_volume_nbhood_derive, once for the 26 neighbours and once for the 8 in the slice.  mode,
+// levels, lo and width are set_volume_texture's; alpha is the largest difference of levels at which a neighbour still depends; max_dist
+// is the last bin of the distance-zone tables.  Every component object of volume_report.json gains a last member "nbhood" (behind
+// "zones"): "levels", "mode" ("count" or "width"), "alpha", "max_dist", "ngtdm" and "ngtdm_axial" ("valid" and the five features
+// "coarseness", "contrast", "busyness", "complexity", "strength"), "ngldm" and "ngldm_axial" ("dependence_max" -- over the 26
+// neighbours, in both --, the 16 features of mi_unet_vzone_features by their names and "dependence_energy"), "gldzm" and "gldzm_axial"
+// ("zones", "clamped" and the same 16), "deepest" and "deepest_axial".  Doubles carry 17 significant digits and a NaN is null.  The
+// member is null for a component that the volume filter dropped (no voxel carries its id) or that lies beyond m.  The log gains
+// "Volume nbhood: D slices, K targets, t ms".  A failure is reported as "Volume nbhood error: ..." and ends only this step: the report
+// is then written without the member.  Off (the default), every artefact and every log line is what it was.  false with a message: a
+// negative channel, a mode that does not exist, levels outside 2 .. 64, lo outside 0 .. 65535, width outside 1 .. 65536, alpha outside
+// 0 .. levels - 1 or max_dist outside 1 .. 4096.
+struct VolumeNbhood {
+    bool on = false;
+    int channel = 0;
+    int mode = 0;                      // MI_UNET_VTEX_COUNT
+    int levels = 32;
+    int lo = 0;
+    int width = 1;
+    int alpha = 0;
+    int max_dist = 32;
+};
+bool set_volume_nbhood(const VolumeNbhood &nbhood);
+VolumeNbhood get_volume_nbhood();
+
 // The scored stack per lesion (mi_unet_volume_match in include/mi_unet.h).  It acts only where set_volume's `on` and
 // set_truth_dir already produce volume_score.json.  Per target the truth stack, recoded by truth == cls, is labelled with
 // mi_unet_volume_components under the volume setting's connectivity, no filter and a table of MI_UNET_VOLUME_MAX_TABLE; the pred ids

@@ -90,6 +90,11 @@ void medseg_get_volume_texture(int *on, int *channel, int *mode, int *levels, in
  * (include/medseg/process.h).  0 on success; medseg_get_volume_zones fills the seven values. */
 int medseg_set_volume_zones(int on, int channel, int mode, int levels, int lo, int width, int max_run);
 void medseg_get_volume_zones(int *on, int *channel, int *mode, int *levels, int *lo, int *width, int *max_run);
+/* The neighbourhood-difference, dependence and distance-zone tables of every component of the labelled stack:
+ * MedicalSeg::set_volume_nbhood / get_volume_nbhood (include/medseg/process.h).  0 on success; medseg_get_volume_nbhood fills the eight
+ * values. */
+int medseg_set_volume_nbhood(int on, int channel, int mode, int levels, int lo, int width, int alpha, int max_dist);
+void medseg_get_volume_nbhood(int *on, int *channel, int *mode, int *levels, int *lo, int *width, int *alpha, int *max_dist);
 int medseg_polygon_json_text_regions(const int32_t *xy, const int32_t *start, const int *group_cls, const int *group_contours, int ngroups,
                                      const void *regions, double scale_x, double scale_y, const char *base_name, int original_width,
                                      int original_height, char *out, int cap);

@@ -1038,6 +1038,112 @@ int mi_unet_volume_zones_run_features(const mi_unet_vzones *c, const uint32_t *r
                                       mi_unet_vzone_features *out);
 int mi_unet_volume_zones_zone_features(const mi_unet_vzones *c, const mi_unet_vzone *zones, int nz, int r, int L, mi_unet_vzone_features *out);
 
+/* ---- Volume neighbourhoods: per component of a labelled stack its neighbourhood-difference (NGTDM), dependence (NGLDM)
+ * and distance-zone (GLDZM) tables
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  Everything up to the feature function
+ * is an exact integer count and independent of the order of evaluation.
+ * Input is ids, int32 [D][H][W], intensity, uint16 [D][H][W], and the number of components m, as mi_unet_volume_zones takes them; both
+ * buffers are required.
+ *   COMPONENT  exactly as in mi_unet_volume_texture: component r, 0 <= r < m, is the set of voxels with ids == r + 1.  0, -1 and anything
+ *              above m belong to no component.  An id that no voxel carries gives an all-zero entry and all-zero rows.
+ *   OPTIONS    opts = { mode, levels L, lo, width, alpha, max_dist Dm }; NULL is { MI_UNET_VTEX_COUNT, 32, 0, 1, 0, 32 }.
+ *   LEVEL      mode, L, lo and width mean what they mean in mi_unet_vtexture_opts, and the level of a voxel is mi_unet_volume_texture's
+ *              formula: the same stack at the same options has the same levels in all three stages.  A voxel's KEY is
+ *              (r + 1) << 8 | level, 0 for a voxel of no component.
+ *   NEIGHBOURS N26(p) is the set of voxels among the 26 neighbours of p that lie inside the volume and in p's component; N8(p) is the
+ *              same over the 8 neighbours with dz = 0 (what a thick-slice series wants, as glcm_axial and rlm_axial are).  For a voxel
+ *              of level l (from 0) with c = |N| and S = the sum of the levels of N:
+ *                  ngt_count[r][l][c] += 1                uint32 [m][L][27], c = 0 .. 26
+ *                  ngt_diff [r][l][c] += |c l - S|        uint64 [m][L][27]; the column c = 0 stays 0
+ *                  dep      [r][l][k] += 1                uint32 [m][L][27], k = the voxels of N whose level differs from l by at most
+ *                                                         alpha; the dependence j = k + 1 is column k
+ *              and the same over N8 in ngt_count_axial, ngt_diff_axial and dep_axial, [m][L][9].  The tables hold more than the IBSI's
+ *              matrices and determine them exactly: n_i = sum over c >= 1 of count, s_i = sum over c >= 1 of diff / c; a voxel with no
+ *              neighbour in its component is left out, as the IBSI prescribes; |c l - S| does not depend on whether levels count from 0
+ *              or from 1.
+ *   DISTANCE   for a voxel p of component r, d(p) = the minimum of |px - qx| + |py - qy| + |pz - qz| over all positions q that are not
+ *              in component r, positions outside the volume included: a voxel at the volume's border has d = 1.  This is the IBSI's
+ *              6-connected distance.  d_axial(p) is the same inside p's slice: |px - qx| + |py - qy|, q in the slice or outside it in x
+ *              or y.
+ *   ZONES      a zone is mi_unet_volume_zones': a 26-connected set of voxels with one key that is not 0.  A zone's distance is the
+ *              minimum of d over its voxels.  dzm[r][l][min(distance, Dm) - 1] counts zones, uint32 [m][L][Dm]; dzm_axial takes d_axial
+ *              over the same 3-D zones.  The last bin collects every distance >= Dm; the entry's `clamped` says how many zones lay
+ *              deeper than Dm, so 0 there means the table is the unclamped matrix.
+ *   ENTRY      voxels, imin, imax as in mi_unet_vtexture; valid and valid_axial, the voxels with c >= 1 in N26 and in N8 (the sums of
+ *              the two count tables without their column 0); zones, the zones of the component; deepest and deepest_axial, the maximum
+ *              of d and of d_axial over the component: the radius of its largest inscribed L1 ball; clamped and clamped_axial;
+ *              dependence_max, the largest j with a count in dep.
+ *   OUTPUT     every table pointer travels in one mi_unet_vnbhood_out; out == NULL is the struct of eight NULLs.  Each pointer may be
+ *              NULL: that table is not computed and the entry's fields that belong to it are 0 (valid with ngt_count, valid_axial with
+ *              ngt_count_axial, dependence_max with dep, deepest and clamped with dzm, deepest_axial and clamped_axial with dzm_axial,
+ *              zones with either).  ngt_count and ngt_diff are both given or both NULL, and so are the axial two.  Without dzm and
+ *              dzm_axial the zone half and both distance transforms are skipped.
+ * Limits, each with its reason:
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE (8192): a distance along a row is below 2^16;
+ *   D * H * W <= 2^28: a count cell stays below 2^28 and an index is an int32_t; a diff cell stays below 26 * 63 * 2^28 < 2^40, hence
+ *           64 bits;
+ *   L in 2 .. MI_UNET_VTEX_MAX_LEVELS (64): the key's 8 level bits, and mi_unet_volume_texture's limit;
+ *   alpha in 0 .. L - 1: at L - 1 every neighbour depends; Dm in 1 .. MI_UNET_VNBHOOD_MAX_DIST (4096): no voxel of a volume with sides
+ *           of at most 8192 lies deeper;
+ *   m in 1 .. MI_UNET_VOLUME_MAX_TABLE and m * L * max(L, 32, Dm) <= MI_UNET_VTEX_MAX_CELLS (2^22): mi_unet_volume_texture's key step
+ *           takes m * L * L at once, and no table passes 32 MiB (27 columns of 8 bytes are fewer bytes than 32 of 8);
+ *   width in 1 .. 65536 and lo in 0 .. 65535: the range of a uint16_t; a mode that exists.
+ * mi_unet_volume_nbhood takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message that begins "mi_unet_volume_nbhood:", nothing queued
+ * and no output written: a null ids, intensity or table; one of a count / diff pair without the other; any limit broken.  A workspace
+ * that cannot be allocated is MI_UNET_EHIP with a message; the handle stays usable.
+ * mi_unet_volume_nbhood_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle, same
+ * bytes; its messages begin "mi_unet_volume_nbhood_host:".
+ * mi_unet_volume_nbhood_derive is pure host arithmetic in double with a fixed order of summation.  It takes the entry of one component,
+ * `rows`: the pointers to that component's rows (ngt_count + r * L * 27 and so on; a NULL row is an absent matrix), L, Dm and `axial`:
+ * 0 reads the three N26 rows and dzm, anything else the three N8 rows and dzm_axial (the pointers of the other form are not read).
+ * Levels are numbered i = 1 .. L.
+ *   NGTDM  with n_i and s_i as above (s_i summed with c ascending), N = sum n_i, p_i = n_i / N and G = the levels with n_i > 0, sums over
+ *          i and over (i, j) ascending, pairs only over levels with p_i != 0 and p_j != 0:
+ *              coarseness = 1 / sum p_i s_i, 1e6 when that sum is 0 (pyradiomics' convention);
+ *              contrast   = (sum_i sum_j p_i p_j (i - j)^2) / (G (G - 1)) * (sum s_i) / N, 0 when G = 1;
+ *              busyness   = (sum p_i s_i) / (sum_i sum_j |i p_i - j p_j|), 0 when the denominator is 0;
+ *              complexity = (1 / N) sum_i sum_j |i - j| (p_i s_i + p_j s_j) / (p_i + p_j);
+ *              strength   = (sum_i sum_j (p_i + p_j) (i - j)^2) / (sum s_i), 0 when sum s_i = 0.
+ *          All five are NaN when N = 0 or the pair of rows is absent.
+ *   NGLDM and GLDZM  the 16 features of mi_unet_vzone_features by the formulas of the block above, over the non-zero cells (i, j, count)
+ *          with i = level + 1 and j = the dependence (column + 1) or the zone distance (bin + 1); percentage = N / voxels.
+ *          dependence_energy = sum p^2 over the dependence matrix.  All are NaN for an empty or absent matrix.
+ * MI_UNET_EARG, output untouched: a null c, rows or out; voxels < 1; L or Dm outside its range; a count row without its diff row.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VNBHOOD_MAX_DIST 4096
+typedef struct mi_unet_vnbhood_opts { int mode, levels, lo, width, alpha, max_dist; } mi_unet_vnbhood_opts;  /* default { MI_UNET_VTEX_COUNT, 32, 0, 1, 0, 32 } */
+typedef struct mi_unet_vnbhood {       /* 44 bytes, no padding */
+    int32_t voxels, imin, imax;        /* voxels with this id; min / max of intensity over them */
+    int32_t valid, valid_axial;        /* voxels with a neighbour of their component among the 26 / among the 8; 0 without that count table */
+    int32_t zones;                     /* zones of this component; 0 without dzm and dzm_axial */
+    int32_t deepest, deepest_axial;    /* the maximum of d / of d_axial; 0 without dzm / dzm_axial */
+    int32_t clamped, clamped_axial;    /* zones with a distance above Dm in each */
+    int32_t dependence_max;            /* the largest dependence j = k + 1 with a count in dep; 0 without dep */
+} mi_unet_vnbhood;
+typedef struct mi_unet_vnbhood_out {   /* the tables of a call, or the rows of one component; each may be NULL */
+    uint32_t *ngt_count;               /* [m][L][27] */
+    uint64_t *ngt_diff;                /* [m][L][27]; NULL iff ngt_count is NULL */
+    uint32_t *dep;                     /* [m][L][27] */
+    uint32_t *ngt_count_axial;         /* [m][L][9] */
+    uint64_t *ngt_diff_axial;          /* [m][L][9]; NULL iff ngt_count_axial is NULL */
+    uint32_t *dep_axial;               /* [m][L][9] */
+    uint32_t *dzm, *dzm_axial;         /* [m][L][Dm] */
+} mi_unet_vnbhood_out;
+typedef struct mi_unet_vnbhood_features {      /* 304 bytes: 38 doubles */
+    double coarseness, contrast, busyness, complexity, strength;
+    mi_unet_vzone_features ngldm;
+    double dependence_energy;
+    mi_unet_vzone_features gldzm;
+} mi_unet_vnbhood_features;
+int mi_unet_volume_nbhood(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const uint16_t *intensity /* [D][H][W] host */, int D, int H,
+                          int W, int m, const mi_unet_vnbhood_opts *opts, mi_unet_vnbhood *table /* [m] */, const mi_unet_vnbhood_out *out);
+int mi_unet_volume_nbhood_host(const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const mi_unet_vnbhood_opts *opts,
+                               mi_unet_vnbhood *table, const mi_unet_vnbhood_out *out);
+int mi_unet_volume_nbhood_derive(const mi_unet_vnbhood *c, const mi_unet_vnbhood_out *rows, int L, int Dm, int axial,
+                                 mi_unet_vnbhood_features *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

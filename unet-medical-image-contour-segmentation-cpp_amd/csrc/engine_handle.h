@@ -165,7 +165,7 @@ struct mi_unet {
     std::vector<int32_t> last_region_counts;
     int last_region_planes = 0, last_region_cap = 0;
     bool last_regions_valid = false;
-    // The workspaces of the stages behind the network (DESIGN.md 7.8 - 7.17), one per stage: the device side holds one call's inputs,
+    // The workspaces of the stages behind the network (DESIGN.md 7.8 - 7.18), one per stage: the device side holds one call's inputs,
     // results and kernel scratch, the pinned side the staging of what crosses the bus.  The stage's entry point (csrc/<stage>.cpp) lays
     // its workspace out and grows it; no other stage, and no clone, touches it.
     // mi_unet_score_labels and mi_unet_score_volume: both maps, the scores, the kernels' workspace; pinned: the maps and the results.
@@ -180,6 +180,7 @@ struct mi_unet {
     miunet::Workspace ws_vmt;          // mi_unet_volume_match: the results (side tables, `found`, pairs), the row offsets, the contingency table, both id stacks
     miunet::Workspace ws_vtx;          // mi_unet_volume_texture: the keys (ids in place), the intensity, the ranges, the table, the histograms, both co-occurrence tables
     miunet::Workspace ws_vzn;          // mi_unet_volume_zones: the results (table, found, both run tables, the zone list), the keys (ids in place), the intensity, the ranges, the forest
+    miunet::Workspace ws_vnb;          // mi_unet_volume_nbhood: the results (table, the tables asked for), the keys (ids in place), the intensity, the ranges, the forest, both distance stacks
     miunet::Workspace ws_volume_interp; // mi_unet_volume_interp: the masks, out, the counts, both intensity stacks, the kernels' workspace
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)

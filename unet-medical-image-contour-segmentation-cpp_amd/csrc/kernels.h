@@ -19,6 +19,7 @@ struct mi_unet_vmatch_pair;
 struct mi_unet_vtexture;
 struct mi_unet_vzones;
 struct mi_unet_vzone;
+struct mi_unet_vnbhood;
 
 namespace miunet {
 
@@ -515,5 +516,32 @@ hipError_t launch_volume_zones_list(const int32_t *keys, const VolumeZonesArgs &
                                     ::mi_unet_vzone *zones, int keep_zones, int32_t *found, hipStream_t s);
 hipError_t launch_volume_zones_finish(const int2 *range, const VolumeZonesArgs &a, int want, const VznAcc *acc, uint32_t *inter,
                                       const uint32_t *axial, ::mi_unet_vzones *table, hipStream_t s);
+
+// Volume neighbourhoods (volume_nbhood.hip; include/mi_unet.h: mi_unet_volume_nbhood), behind launch_volume_texture_keys on
+// its key stack and, for the zones, behind launch_volume_zones_list on its forest.  Every result is an integer sum, minimum or maximum:
+// nothing depends on the order in which atomics arrive.  No workgroup waits for another.  Tables are cleared over this call's extent.
+//   launch_volume_nbhood_gather: clears the tables named in `want`, then k_vnb_gather, the hot path: 7.15's tile with its full halo
+//       (6 x 10 x 66 keys) in LDS, a lane per voxel reads its 26 neighbours there and forms c, S and k over N26 and over N8 in one
+//       sweep; per wanted table one count and one diff.  With lds_table the counts of the component that leads a tile are kept in
+//       workgroup-private LDS tables (the diff in 32 bits there) and flushed when the leader changes; without it every count goes to
+//       memory after a wave merge (k_vzn_runs' scheme).  kVnbLdsTable is what mi_unet_volume_nbhood passes (DESIGN.md 7.18 has both timings).
+//   launch_volume_nbhood_dist: the multi-label L1 distance transform, separable: k_vnb_dist_x (a wave per row, segmented scans forward
+//       and backward in chunks of 64), k_vnb_dist_y and k_vnb_dist_z (a lane per column, coalesced along x).  axial [D][H][W] u16 holds
+//       d_axial after y; full (or NULL: no z pass) holds d.
+//   launch_volume_nbhood_zones: the minimum of d and of d_axial per root of the forest (zmin, zmin_axial: int [D][H][W], a wave merges
+//       before the atomic), the component's deepest, then from every root one count into dzm / dzm_axial and the clamped counts.
+//   launch_volume_nbhood_finish: a workgroup per component writes the entry from range, zacc (voxels, zones), acc and the tables' sums.
+constexpr int VNB_WANT_NGT = 1, VNB_WANT_DEP = 2, VNB_WANT_NGT_AXIAL = 4, VNB_WANT_DEP_AXIAL = 8, VNB_WANT_DZM = 16, VNB_WANT_DZM_AXIAL = 32;
+constexpr int VNB_COLS = 27, VNB_COLS_AXIAL = 9;
+constexpr bool kVnbLdsTable = true;
+struct VolumeNbhoodArgs { int D = 0, H = 0, W = 0, m = 0, L = 32, alpha = 0, Dm = 32; };
+struct VnbAcc { int deepest, deepest_axial; uint32_t clamped, clamped_axial; };                 // 16 bytes
+struct VnbTables { uint32_t *count, *dep, *count_axial, *dep_axial, *dzm, *dzm_axial; unsigned long long *diff, *diff_axial; };
+hipError_t launch_volume_nbhood_gather(const int32_t *keys, const VolumeNbhoodArgs &a, int want, bool lds_table, const VnbTables &t, hipStream_t s);
+hipError_t launch_volume_nbhood_dist(const int32_t *keys, const VolumeNbhoodArgs &a, uint16_t *axial, uint16_t *full, hipStream_t s);
+hipError_t launch_volume_nbhood_zones(const int32_t *keys, const VolumeNbhoodArgs &a, int want, const int32_t *parent, const uint16_t *axial,
+                                      const uint16_t *full, int32_t *zmin, int32_t *zmin_axial, VnbAcc *acc, const VnbTables &t, hipStream_t s);
+hipError_t launch_volume_nbhood_finish(const int2 *range, const VolumeNbhoodArgs &a, int want, const VznAcc *zacc, const VnbAcc *acc,
+                                       const VnbTables &t, ::mi_unet_vnbhood *table, hipStream_t s);
 
 }  // namespace miunet

@@ -231,6 +231,15 @@ void medseg_get_volume_zones(int *on, int *channel, int *mode, int *levels, int 
     const MedicalSeg::VolumeZones z = MedicalSeg::get_volume_zones();
     *on = z.on; *channel = z.channel; *mode = z.mode; *levels = z.levels; *lo = z.lo; *width = z.width; *max_run = z.max_run;
 }
+int medseg_set_volume_nbhood(int on, int channel, int mode, int levels, int lo, int width, int alpha, int max_dist)
+{
+    return MedicalSeg::set_volume_nbhood({ on != 0, channel, mode, levels, lo, width, alpha, max_dist }) ? 0 : 1;
+}
+void medseg_get_volume_nbhood(int *on, int *channel, int *mode, int *levels, int *lo, int *width, int *alpha, int *max_dist)
+{
+    const MedicalSeg::VolumeNbhood n = MedicalSeg::get_volume_nbhood();
+    *on = n.on; *channel = n.channel; *mode = n.mode; *levels = n.levels; *lo = n.lo; *width = n.width; *alpha = n.alpha; *max_dist = n.max_dist;
+}
 int medseg_set_volume_match(int on, int iou_num, int iou_den) { return MedicalSeg::set_volume_match({ on != 0, iou_num, iou_den }) ? 0 : 1; }
 void medseg_get_volume_match(int *on, int *iou_num, int *iou_den)
 {

@@ -153,6 +153,7 @@ public:
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
+        table_["volnbhood"] = [this](const Words &w) { cmd_volnbhood(w); return true; };
         table_["volmatch"] = [this](const Words &w) { cmd_volmatch(w); return true; };
         table_["help"] = [](const Words &) { banner(); return true; };
         table_["exit"] = [this](const Words &) { cmd_exit(); return false; };
@@ -178,6 +179,7 @@ public:
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
+            "  volnbhood on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N]|off - With volume on: neighbourhood-difference, dependence and distance-zone features of every component in the report",
             "  volmatch on [iou N/D]|off     - With volume on and truth: components matched to truth components, detection F1 and PQ per target",
             "  exit                          - Cleanup and exit",
             "",
@@ -584,6 +586,49 @@ private:
         if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
         else std::cout << "count";
         std::cout << " run " << cur.max_run << std::endl;
+    }
+
+    // volnbhood on [levels N] [count | width W [lo L]] [alpha N] [dist N] [channel N] | volnbhood off | volnbhood (prints the setting in force)
+    void cmd_volnbhood(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeNbhood n;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            n.on = w[1] == "on";
+            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
+            for (size_t i = 2; ok && i < w.size();) {
+                if (w[i] == "count") {
+                    ok = !binned;
+                    binned = true;
+                    i += 1;
+                    continue;
+                }
+                int value = 0;
+                ok = i + 1 < w.size() && to_int(w[i + 1], value);
+                if (!ok) break;
+                if (w[i] == "levels") n.levels = value;
+                else if (w[i] == "channel") n.channel = value;
+                else if (w[i] == "alpha") n.alpha = value;
+                else if (w[i] == "dist") n.max_dist = value;
+                else if (w[i] == "width" && !binned) { n.mode = MI_UNET_VTEX_WIDTH; n.width = value; binned = true; }
+                else if (w[i] == "lo" && n.mode == MI_UNET_VTEX_WIDTH) n.lo = value;
+                else ok = false;
+                i += 2;
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volnbhood command (expected on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_nbhood(n)) {
+                std::cerr << "Volume nbhood unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeNbhood cur = MedicalSeg::get_volume_nbhood();
+        std::cout << "Volume nbhood: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
+        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
+        else std::cout << "count";
+        std::cout << " alpha " << cur.alpha << " dist " << cur.max_dist << std::endl;
     }
 
     // volmatch on [iou N/D] | volmatch off | volmatch (prints the setting in force)

@@ -39,6 +39,7 @@ struct Settings {
     VolumeMeasure volume_measure;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeTexture volume_texture;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeZones volume_zones;                              // off; acts only with volume.on (process_image_batch reads it)
+    VolumeNbhood volume_nbhood;                            // off; acts only with volume.on (process_image_batch reads it)
     VolumeMatch volume_match;                              // off; acts only with volume.on and a truth_dir (process_image_batch reads it)
     // Hands a handle every setting it can hold -- window, measure, morphology, targets -- and returns the first refusal.  This is the one
     // way a group, a lane or a thread's context gets its settings.  Only the _multi entry points read a handle's targets and morphology

@@ -419,6 +419,28 @@ bool set_volume_zones(const VolumeZones &zones)
         /*handle_side=*/false);
 }
 
+bool set_volume_nbhood(const VolumeNbhood &nbhood)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_nbhood = nbhood;
+            if (nbhood.channel < 0) return std::string("volume nbhood: the channel is not negative");
+            if (nbhood.mode != MI_UNET_VTEX_COUNT && nbhood.mode != MI_UNET_VTEX_WIDTH)
+                return std::string("volume nbhood: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
+            if (nbhood.levels < 2 || nbhood.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume nbhood: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
+            if (nbhood.lo < 0 || nbhood.lo > 65535) return std::string("volume nbhood: lo is 0 .. 65535");
+            if (nbhood.width < 1 || nbhood.width > 65536) return std::string("volume nbhood: width is 1 .. 65536");
+            if (nbhood.alpha < 0 || nbhood.alpha > nbhood.levels - 1) return std::string("volume nbhood: alpha is 0 .. levels - 1");
+            return std::string(nbhood.max_dist >= 1 && nbhood.max_dist <= MI_UNET_VNBHOOD_MAX_DIST ? "" : "volume nbhood: max_dist is 1 .. MI_UNET_VNBHOOD_MAX_DIST");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume nbhood: " << (nbhood.on ? "on" : "off") << ", channel " << nbhood.channel << ", levels " << nbhood.levels << ", "
+               << (nbhood.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(nbhood.width) + " lo " + std::to_string(nbhood.lo) : std::string("count"))
+               << ", alpha " << nbhood.alpha << ", dist " << nbhood.max_dist;
+        },
+        /*handle_side=*/false);
+}
+
 bool set_volume_match(const VolumeMatch &match)
 {
     return change_setting(
@@ -455,6 +477,7 @@ VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeZones get_volume_zones() { return current_settings().volume_zones; }
+VolumeNbhood get_volume_nbhood() { return current_settings().volume_nbhood; }
 VolumeMatch get_volume_match() { return current_settings().volume_match; }
 
 std::ofstream &get_log_file() { return g_log_file; }

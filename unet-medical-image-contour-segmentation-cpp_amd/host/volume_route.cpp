@@ -1,5 +1,5 @@
 // volume_route.cpp -- the volume chain of MedicalSeg::process_image_batch (set_volume): the stages of include/mi_unet.h that take the
-// batch's masks as one volume -- clean, components, interpolation, mesh, measure, texture, zones, scores against a truth directory, lesion matching -- and
+// batch's masks as one volume -- clean, components, interpolation, mesh, measure, texture, zones, neighbourhoods, scores against a truth directory, lesion matching -- and
 // the reports they write (volume_report.json, volume_score.json, the STL files, the <base>_volume_mask pictures).  routes.cpp fills the
 // stack and calls finish_volume; volume_route.h is what the two share.
 #include <algorithm>
@@ -383,6 +383,92 @@ std::vector<std::vector<std::string>> zones_volume(const VolumeStack &st, const 
     }
 }
 
+// set_volume_nbhood: per target one mi_unet_volume_nbhood call on `h` (mi_unet_volume_nbhood_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's neighbourhood channel, all eight tables, with m = min(found,
+// cap, 2^22 / (levels * max(levels, 32, max_dist))); the rows of every component go to mi_unet_volume_nbhood_derive twice, for the 26
+// neighbours and for the 8 in the slice.  Returns, per target and table row, the "nbhood" member of the row's component object in
+// volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
+std::vector<std::vector<std::string>> nbhood_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
+                                                    size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+{
+    try {
+        const VolumeNbhood &ns = s.volume_nbhood;
+        const size_t K = s.targets.size(), D = st.D, hw = st.hw, L = (size_t)ns.levels, Dm = (size_t)ns.max_dist;
+        if (ns.channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(ns.channel) + " of " + std::to_string(g_cfg.in_ch));
+        const mi_unet_vnbhood_opts opts{ ns.mode, ns.levels, ns.lo, ns.width, ns.alpha, ns.max_dist };
+        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * std::max<size_t>({ L, 32, Dm }));
+        std::vector<std::vector<std::string>> members(K);
+        size_t cut = 0;                                         // components beyond the measured count
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const size_t rows = std::min<size_t>((size_t)found[t], cap);
+            const int m = (int)std::min(rows, most);
+            if (m < 1) continue;
+            cut += rows - (size_t)m;
+            const size_t M = (size_t)m;
+            std::vector<mi_unet_vnbhood> table(M);
+            std::vector<uint32_t> count(M * L * 27), dep(M * L * 27), count_a(M * L * 9), dep_a(M * L * 9), dzm(M * L * Dm), dzm_a(M * L * Dm);
+            std::vector<uint64_t> diff(M * L * 27), diff_a(M * L * 9);
+            const mi_unet_vnbhood_out out{ count.data(), diff.data(), dep.data(), count_a.data(), diff_a.data(), dep_a.data(), dzm.data(), dzm_a.data() };
+            stage_call(h, mi_unet_volume_nbhood, mi_unet_volume_nbhood_host, ids.data() + t * D * hw, st.nbhood_intensity(), (int)D, g_cfg.height,
+                       g_cfg.width, m, &opts, table.data(), &out);
+            for (size_t r = 0; r < rows; ++r) {
+                if (r >= M || table[r].voxels < 1) {            // beyond the measured count, or dropped by the volume filter: no voxel carries its id
+                    members[t].push_back(", \"nbhood\": null");
+                    continue;
+                }
+                const mi_unet_vnbhood &c = table[r];
+                const mi_unet_vnbhood_out row{ count.data() + r * L * 27, diff.data() + r * L * 27, dep.data() + r * L * 27, count_a.data() + r * L * 9,
+                                               diff_a.data() + r * L * 9,  dep_a.data() + r * L * 9,  dzm.data() + r * L * Dm,  dzm_a.data() + r * L * Dm };
+                mi_unet_vnbhood_features full{}, axial{};
+                checked(mi_unet_volume_nbhood_derive, &c, &row, (int)L, (int)Dm, 0, &full);
+                checked(mi_unet_volume_nbhood_derive, &c, &row, (int)L, (int)Dm, 1, &axial);
+                std::ostringstream js;
+                auto features = [&](const mi_unet_vzone_features &f) {
+                    const double *const v = &f.short_emphasis;
+                    static const char *const names[16] = { "short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low",
+                                                           "short_high", "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm",
+                                                           "size_nonuniformity", "size_nonuniformity_norm", "percentage", "grey_variance",
+                                                           "size_variance", "entropy" };
+                    for (int k = 0; k < 16; ++k) js << ", \"" << names[k] << "\": " << json_number(v[k]);
+                };
+                auto ngtdm = [&](const char *key, const mi_unet_vnbhood_features &f, int valid) {
+                    js << ", \"" << key << "\": {\"valid\": " << valid << ", \"coarseness\": " << json_number(f.coarseness)
+                       << ", \"contrast\": " << json_number(f.contrast) << ", \"busyness\": " << json_number(f.busyness)
+                       << ", \"complexity\": " << json_number(f.complexity) << ", \"strength\": " << json_number(f.strength) << "}";
+                };
+                auto ngldm = [&](const char *key, const mi_unet_vnbhood_features &f) {
+                    js << ", \"" << key << "\": {\"dependence_max\": " << c.dependence_max;
+                    features(f.ngldm);
+                    js << ", \"dependence_energy\": " << json_number(f.dependence_energy) << "}";
+                };
+                auto gldzm = [&](const char *key, const mi_unet_vnbhood_features &f, int clamped) {
+                    js << ", \"" << key << "\": {\"zones\": " << c.zones << ", \"clamped\": " << clamped;
+                    features(f.gldzm);
+                    js << "}";
+                };
+                js << ", \"nbhood\": {\"levels\": " << L << ", \"mode\": \"" << (ns.mode == MI_UNET_VTEX_WIDTH ? "width" : "count")
+                   << "\", \"alpha\": " << ns.alpha << ", \"max_dist\": " << Dm;
+                ngtdm("ngtdm", full, c.valid);
+                ngtdm("ngtdm_axial", axial, c.valid_axial);
+                ngldm("ngldm", full);
+                ngldm("ngldm_axial", axial);
+                gldzm("gldzm", full, c.clamped);
+                gldzm("gldzm_axial", axial, c.clamped_axial);
+                js << ", \"deepest\": " << c.deepest << ", \"deepest_axial\": " << c.deepest_axial << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume nbhood: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
+        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels and dist " << Dm << "; " << cut << " not measured)";
+        lg << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume nbhood error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -393,7 +479,8 @@ std::vector<std::vector<std::string>> zones_volume(const VolumeStack &st, const 
 // interpolated stack.  With set_volume_measure on,
 // the components stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member
 // "measure".  With set_volume_texture on, the ids are handed out likewise and every component object gains a last member "texture"
-// (texture_volume), and with set_volume_zones on a last member "zones" behind it (zones_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
+// (texture_volume), with set_volume_zones on a last member "zones" behind it (zones_volume), and with set_volume_nbhood on a last member
+// "nbhood" behind that (nbhood_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
 // empty after a failure.
 struct VolumeIds {
     std::vector<int32_t> ids, found;
@@ -409,7 +496,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || numbered ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || s.volume_nbhood.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const auto t0 = hr_clock::now();
@@ -433,6 +520,8 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
             s.volume_texture.on ? texture_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const std::vector<std::vector<std::string>> zoned =
             s.volume_zones.on ? zones_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
+        const std::vector<std::vector<std::string>> nbhooded =
+            s.volume_nbhood.on ? nbhood_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -464,7 +553,8 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << json_number(m.cy_mm) << ", " << json_number(m.cz_mm) << "], \"volume_mm3\": " << json_number(m.volume_mm3)
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
-                   << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r]) << "}";
+                   << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r])
+                   << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]}";
         }

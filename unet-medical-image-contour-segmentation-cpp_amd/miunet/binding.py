@@ -43,6 +43,7 @@ EXPORTS = [
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
     "mi_unet_volume_zones", "mi_unet_volume_zones_host", "mi_unet_volume_zones_run_features", "mi_unet_volume_zones_zone_features",
+    "mi_unet_volume_nbhood", "mi_unet_volume_nbhood_host", "mi_unet_volume_nbhood_derive",
 ]
 
 
@@ -490,6 +491,69 @@ def _volume_zones_call(fn, head, ids, intensity, m, levels, mode, lo, width, max
     return table, rlm, axial, zones, (found.value if cap else None)
 
 
+class VNbhoodOpts(C.Structure):
+    """mi_unet_vnbhood_opts; the default is { VTEX_COUNT, 32, 0, 1, 0, 32 }"""
+    _fields_ = [("mode", C.c_int), ("levels", C.c_int), ("lo", C.c_int), ("width", C.c_int), ("alpha", C.c_int), ("max_dist", C.c_int)]
+
+
+class VNbhood(C.Structure):
+    """mi_unet_vnbhood: 44 bytes, eleven int32; VNBHOOD_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int32) for n in ("voxels", "imin", "imax", "valid", "valid_axial", "zones", "deepest", "deepest_axial", "clamped",
+                                         "clamped_axial", "dependence_max")]
+
+
+VNBHOOD_TABLES = ("ngt_count", "ngt_diff", "dep", "ngt_count_axial", "ngt_diff_axial", "dep_axial", "dzm", "dzm_axial")
+
+
+class VNbhoodOut(C.Structure):
+    """mi_unet_vnbhood_out: the eight table pointers of a call, or the row pointers of one component"""
+    _fields_ = [(n, C.c_void_p) for n in VNBHOOD_TABLES]
+
+
+class VNbhoodFeatures(C.Structure):
+    _fields_ = ([(n, C.c_double) for n in ("coarseness", "contrast", "busyness", "complexity", "strength")] + [("ngldm", VZoneFeatures)] +
+                [("dependence_energy", C.c_double), ("gldzm", VZoneFeatures)])
+
+
+VNBHOOD_DTYPE = np.dtype([(n, np.int32) for n, _ in VNbhood._fields_])
+VNBHOOD_MAX_DIST = 4096
+VNBHOOD_WANT = ("ngt", "dep", "ngt_axial", "dep_axial", "dzm", "dzm_axial")
+
+
+def _vnbhood_shapes(rows, lv, dm):
+    return {"ngt_count": ((rows, lv, 27), np.uint32), "ngt_diff": ((rows, lv, 27), np.uint64), "dep": ((rows, lv, 27), np.uint32),
+            "ngt_count_axial": ((rows, lv, 9), np.uint32), "ngt_diff_axial": ((rows, lv, 9), np.uint64), "dep_axial": ((rows, lv, 9), np.uint32),
+            "dzm": ((rows, lv, dm), np.uint32), "dzm_axial": ((rows, lv, dm), np.uint32)}
+
+
+def _volume_nbhood_call(fn, head, ids, intensity, m, levels, mode, lo, width, alpha, max_dist, want):
+    """mi_unet_volume_nbhood (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape, m components, levels / mode ("count", "width" or the number) / lo / width / alpha / max_dist = the options, want =
+    which of VNBHOOD_WANT to compute ("ngt" and "ngt_axial" are a count and a diff table each) -> (table VNBHOOD_DTYPE [m], dict over
+    VNBHOOD_TABLES: u32 / u64 [m, L, 27 | 9 | max_dist], or None for a table that was not asked for).  The library checks the values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    unknown = set(want) - set(VNBHOOD_WANT)
+    if unknown:
+        raise ValueError(f"want {sorted(unknown)} is not among {VNBHOOD_WANT}")
+    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    d, hh, ww = ids.shape
+    rows, lv, dm = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_dist), 1), VNBHOOD_MAX_DIST)
+    if rows * lv * max(lv, 32, dm) > 2 * VTEX_MAX_CELLS:
+        rows = 1                                                 # (refused by the library; no need for the memory)
+    table = np.zeros(rows, VNBHOOD_DTYPE)
+    asked = {"ngt_count": "ngt", "ngt_diff": "ngt", "dep": "dep", "ngt_count_axial": "ngt_axial", "ngt_diff_axial": "ngt_axial",
+             "dep_axial": "dep_axial", "dzm": "dzm", "dzm_axial": "dzm_axial"}
+    tables = {n: (np.zeros(shape, dt) if asked[n] in want else None) for n, (shape, dt) in _vnbhood_shapes(rows, lv, dm).items()}
+    out = VNbhoodOut(*[None if tables[n] is None else tables[n].ctypes.data for n in VNBHOOD_TABLES])
+    opts = VNbhoodOpts(int(VTEX_MODES.get(mode, mode)), int(levels), int(lo), int(width), int(alpha), int(max_dist))
+    _check(fn(*head, _ptr(ids), _ptr(intensity), d, hh, ww, int(m), C.byref(opts), _ptr(table), C.byref(out)))
+    return table, tables
+
+
 class VMatchCounts(C.Structure):
     _fields_ = [("tp", C.c_int32), ("fp", C.c_int32), ("fn", C.c_int32)]
 
@@ -717,6 +781,9 @@ def lib():
         L.mi_unet_volume_zones.argtypes = [C.c_void_p] + L.mi_unet_volume_zones_host.argtypes
         L.mi_unet_volume_zones_run_features.argtypes = [C.POINTER(VZones), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(VZoneFeatures)]
         L.mi_unet_volume_zones_zone_features.argtypes = [C.POINTER(VZones), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(VZoneFeatures)]
+        L.mi_unet_volume_nbhood_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_nbhood.argtypes = [C.c_void_p] + L.mi_unet_volume_nbhood_host.argtypes
+        L.mi_unet_volume_nbhood_derive.argtypes = [C.POINTER(VNbhood), C.POINTER(VNbhoodOut), C.c_int, C.c_int, C.c_int, C.POINTER(VNbhoodFeatures)]
         L.mi_unet_volume_match_host.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
         L.mi_unet_volume_match.argtypes = [C.c_void_p] + L.mi_unet_volume_match_host.argtypes
         L.mi_unet_volume_match_assign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -1144,6 +1211,13 @@ class Engine:
         return _volume_zones_call(lib().mi_unet_volume_zones, (self._h,), ids, intensity, m, levels, mode, lo, width, max_run, want_runs,
                                   want_axial, cap)
 
+    # ---- the neighbourhood-difference, dependence and distance-zone tables of the components of a labelled stack (mi_unet_volume_nbhood):
+    # needs the device, not the weights
+    def volume_nbhood(self, ids, intensity, m, levels=32, mode="count", lo=0, width=1, alpha=0, max_dist=32, want=VNBHOOD_WANT):
+        """ids int32 [D,H,W], intensity u16 [D,H,W], m components -> (table VNBHOOD_DTYPE [m], dict over VNBHOOD_TABLES of u32 / u64
+        [m, levels, 27 | 9 | max_dist], None for a table not in `want`).  The library checks the values and the limits"""
+        return _volume_nbhood_call(lib().mi_unet_volume_nbhood, (self._h,), ids, intensity, m, levels, mode, lo, width, alpha, max_dist, want)
+
     # ---- the components of a labelled stack measured (mi_unet_volume_measure): needs the device, not the weights
     def volume_measure(self, ids, intensity=None, m=1, units=(1, 1, 1), max_ends=None):
         """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W] or None, m = the components
@@ -1342,6 +1416,31 @@ def volume_zones_zone_features(comp, zones, r, levels):
     out = VZoneFeatures()
     _check(lib().mi_unet_volume_zones_zone_features(C.byref(_vzones_entry(comp)), _ptr(zones), int(zones.size), int(r), int(levels), C.byref(out)))
     return {n: getattr(out, n) for n, _ in VZoneFeatures._fields_}
+
+
+def volume_nbhood_host(ids, intensity, m, levels=32, mode="count", lo=0, width=1, alpha=0, max_dist=32, want=VNBHOOD_WANT):
+    """mi_unet_volume_nbhood_host: Engine.volume_nbhood as sequential host arithmetic (needs no device)"""
+    return _volume_nbhood_call(lib().mi_unet_volume_nbhood_host, (), ids, intensity, m, levels, mode, lo, width, alpha, max_dist, want)
+
+
+def volume_nbhood_derive(comp, rows, axial=False):
+    """mi_unet_volume_nbhood_derive of one component (a VNbhood, or one VNBHOOD_DTYPE record) and `rows`: a dict over VNBHOOD_TABLES of
+    that component's rows (tables[name][r]; None or missing: an absent matrix); axial reads the three [L, 9] rows and dzm_axial -> a
+    dict of the five NGTDM features, "ngldm" and "gldzm" (dicts of 16) and dependence_energy"""
+    entry = comp if isinstance(comp, VNbhood) else VNbhood(**{n: int(comp[n]) for n, _ in VNbhood._fields_})
+    kept = {n: np.ascontiguousarray(rows[n], np.uint64 if "diff" in n else np.uint32) for n in VNBHOOD_TABLES if rows.get(n) is not None}
+    shapes = {a.shape[0] for a in kept.values()}
+    if len(shapes) > 1:
+        raise ValueError("the rows of one component have one number of levels")
+    levels = shapes.pop() if shapes else 2
+    dist = [kept[n].shape[1] for n in ("dzm", "dzm_axial") if n in kept]
+    ptrs = VNbhoodOut(*[kept[n].ctypes.data if n in kept else None for n in VNBHOOD_TABLES])
+    out = VNbhoodFeatures()
+    _check(lib().mi_unet_volume_nbhood_derive(C.byref(entry), C.byref(ptrs), int(levels), int(dist[0]) if dist else 1, int(bool(axial)), C.byref(out)))
+    vz = lambda f: {n: getattr(f, n) for n, _ in VZoneFeatures._fields_}
+    res = {n: getattr(out, n) for n in ("coarseness", "contrast", "busyness", "complexity", "strength", "dependence_energy")}
+    res["ngldm"], res["gldzm"] = vz(out.ngldm), vz(out.gldzm)
+    return res
 
 
 def volume_texture_derive(comp, hist, glcm=None):

@@ -25,7 +25,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_clean", "medseg_get_volume_clean", "medseg_set_volume_mesh", "medseg_get_volume_mesh",
            "medseg_set_volume_interp", "medseg_get_volume_interp",
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
-           "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones"]
+           "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones",
+           "medseg_set_volume_nbhood", "medseg_get_volume_nbhood"]
 
 
 def lib():
@@ -97,6 +98,9 @@ def lib():
         L.medseg_set_volume_zones.argtypes = [C.c_int] * 7
         L.medseg_get_volume_zones.argtypes = [_i] * 7
         L.medseg_get_volume_zones.restype = None
+        L.medseg_set_volume_nbhood.argtypes = [C.c_int] * 8
+        L.medseg_get_volume_nbhood.argtypes = [_i] * 8
+        L.medseg_get_volume_nbhood.restype = None
         _LIB = L
     return _LIB
 
@@ -314,6 +318,21 @@ def get_volume_zones():
     lib().medseg_get_volume_zones(*[C.byref(x) for x in v])
     on, channel, mode, levels, lo, width, max_run = (x.value for x in v)
     return {"on": bool(on), "channel": channel, "mode": VTEX_MODES[mode], "levels": levels, "lo": lo, "width": width, "max_run": max_run}
+
+
+def set_volume_nbhood(on=True, channel=0, mode="count", levels=32, lo=0, width=1, alpha=0, max_dist=32) -> bool:
+    """MedicalSeg::set_volume_nbhood: with set_volume on, process_image_batch adds the neighbourhood-difference, dependence and
+    distance-zone features of every component of the labelled stack (mi_unet_volume_nbhood over `channel` of the normalised tiles) as
+    a "nbhood" member of volume_report.json; needs no engine"""
+    mode = VTEX_MODES.index(mode) if mode in VTEX_MODES else int(mode)
+    return lib().medseg_set_volume_nbhood(int(bool(on)), int(channel), mode, int(levels), int(lo), int(width), int(alpha), int(max_dist)) == 0
+
+
+def get_volume_nbhood():
+    v = [C.c_int() for _ in range(8)]
+    lib().medseg_get_volume_nbhood(*[C.byref(x) for x in v])
+    on, channel, mode, levels, lo, width, alpha, max_dist = (x.value for x in v)
+    return {"on": bool(on), "channel": channel, "mode": VTEX_MODES[mode], "levels": levels, "lo": lo, "width": width, "alpha": alpha, "max_dist": max_dist}
 
 
 def set_volume_match(on=True, iou=(1, 2)) -> bool:
