@@ -1,5 +1,6 @@
 // engine_handle.h -- struct mi_unet and what the units that implement include/mi_unet.h share: engine.cpp (create / destroy, weights,
-// launch_plan, the u8 entry points), pipeline_raw.cpp, pipeline_tiled.cpp and debug.cpp.  Internal to libmiunet.so.
+// launch_plan, the u8 entry points), pipeline_raw.cpp, pipeline_tiled.cpp and debug.cpp, and through stage_common.h the host halves of
+// the stages behind the network (texture_common.h for the three texture stages among them).  Internal to libmiunet.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,6 +50,12 @@ template <class T> using DeviceBuf = Buffer<T, false>;
 template <class T> using PinnedBuf = Buffer<T, true>;
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }      // the parts of a workspace start on 256-byte boundaries
+
+// The parts of a workspace, one behind the other: take(bytes) is where the next part starts; `end` is the room taken so far.
+struct Layout {
+    size_t end = 0;
+    size_t take(size_t bytes) { return std::exchange(end, end + up256(bytes)); }
+};
 
 // A stage's device buffer and its pinned staging, in bytes: grown on demand, owned by the handle, never shared with a clone.
 struct Workspace {

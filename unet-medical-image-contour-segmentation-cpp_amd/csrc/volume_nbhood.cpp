@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "stage_common.h"
+#include "texture_common.h"
 
 static_assert(sizeof(mi_unet_vnbhood) == 44, "mi_unet_vnbhood is eleven int32 without padding");
 static_assert(sizeof(mi_unet_vnbhood_opts) == 24, "mi_unet_vnbhood_opts is six ints");
@@ -24,7 +24,6 @@ namespace {
 
 constexpr mi_unet_vnbhood_opts kDefaultOpts{ MI_UNET_VTEX_COUNT, 32, 0, 1, 0, 32 };
 constexpr mi_unet_vnbhood_out kNoTables{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-constexpr int kMaxSide = MI_UNET_SCORE_VOLUME_MAX_SIDE;
 constexpr int kCols = 27, kColsAxial = 9;
 
 // every MI_UNET_EARG case of the two entry points; nothing has been queued or written when it fails
@@ -36,13 +35,7 @@ int check_nbhood_args(const char *fn, const int32_t *ids, const uint16_t *intens
     if ((out.ngt_count == nullptr) != (out.ngt_diff == nullptr)) return fail(MI_UNET_EARG, f + ": ngt_count and ngt_diff are both given or both null");
     if ((out.ngt_count_axial == nullptr) != (out.ngt_diff_axial == nullptr))
         return fail(MI_UNET_EARG, f + ": ngt_count_axial and ngt_diff_axial are both given or both null");
-    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
-    if ((int64_t)D * H * W > (int64_t)MI_UNET_VTEX_MAX_VOXELS) return fail(MI_UNET_EARG, f + ": D * H * W must not pass 2^28");   // (< 2^39: no overflow)
-    if (m < 1 || m > MI_UNET_VOLUME_MAX_TABLE)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE) + ")");
-    if (o.mode != MI_UNET_VTEX_COUNT && o.mode != MI_UNET_VTEX_WIDTH) return fail(MI_UNET_EARG, f + ": mode " + std::to_string(o.mode) + " does not exist");
-    if (o.levels < 2 || o.levels > MI_UNET_VTEX_MAX_LEVELS)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(o.levels) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
+    if (int rc = check_texture_volume(f, D, H, W, m, common_opts(o))) return rc;
     if (o.alpha < 0 || o.alpha > o.levels - 1)
         return fail(MI_UNET_EARG, f + ": alpha " + std::to_string(o.alpha) + " (0 .. " + std::to_string(o.levels - 1) + ")");
     if (o.max_dist < 1 || o.max_dist > MI_UNET_VNBHOOD_MAX_DIST)
@@ -50,91 +43,7 @@ int check_nbhood_args(const char *fn, const int32_t *ids, const uint16_t *intens
     if ((int64_t)m * o.levels * std::max({ o.levels, 32, o.max_dist }) > (int64_t)MI_UNET_VTEX_MAX_CELLS)
         return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components at " + std::to_string(o.levels) + " levels and max_dist " +
                                       std::to_string(o.max_dist) + " pass 2^22 cells per table");
-    if (o.width < 1 || o.width > 65536) return fail(MI_UNET_EARG, f + ": width " + std::to_string(o.width) + " is outside 1 .. 65536");
-    if (o.lo < 0 || o.lo > 65535) return fail(MI_UNET_EARG, f + ": lo " + std::to_string(o.lo) + " is outside 0 .. 65535");
-    return MI_UNET_OK;
-}
-
-struct Cell {
-    int64_t i, j, c;            // level + 1, dependence or zone distance, count
-};
-
-// the 16 features of mi_unet_vzone_features (the formulas of the 7.17 block of the header, in its order of summation) over the non-zero
-// cells of one matrix, sorted by (i, j), and sum p^2
-void matrix_features(const std::vector<Cell> &cells, int L, double space, mi_unet_vzone_features *out, double *energy)
-{
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    mi_unet_vzone_features o;
-    int64_t N = 0, si = 0, sj = 0;
-    std::vector<int64_t> ni((size_t)L + 1, 0);
-    std::vector<std::pair<int64_t, int64_t>> nj;                // (j, n_j), j ascending
-    for (const Cell &c : cells) {
-        N += c.c;
-        ni[(size_t)c.i] += c.c;
-        si += c.i * c.c;
-        sj += c.j * c.c;
-        nj.emplace_back(c.j, c.c);
-    }
-    if (N == 0) {
-        double *const v = reinterpret_cast<double *>(&o);
-        for (int k = 0; k < 16; ++k) v[k] = nan;
-        *out = o;
-        if (energy) *energy = nan;
-        return;
-    }
-    std::sort(nj.begin(), nj.end());
-    size_t u = 0;
-    for (size_t k = 0; k < nj.size(); ++k) {
-        if (u && nj[u - 1].first == nj[k].first) nj[u - 1].second += nj[k].second;
-        else nj[u++] = nj[k];
-    }
-    nj.resize(u);
-    const double n = (double)N, mu_i = (double)si / n, mu_j = (double)sj / n;
-    double se = 0.0, le = 0.0, lg = 0.0, hg = 0.0, gn = 0.0, sn = 0.0;
-    for (const auto &e : nj) {
-        const double j = (double)e.first, c = (double)e.second;
-        se += c / (j * j);
-        le += c * (j * j);
-        sn += c * c;
-    }
-    for (int i = 1; i <= L; ++i) {
-        if (!ni[(size_t)i]) continue;
-        const double c = (double)ni[(size_t)i], ii = (double)i * (double)i;
-        lg += c / ii;
-        hg += c * ii;
-        gn += c * c;
-    }
-    double sl = 0.0, sh = 0.0, ll = 0.0, lh = 0.0, gv = 0.0, sv = 0.0, ent = 0.0, en = 0.0;
-    for (const Cell &cell : cells) {
-        const double c = (double)cell.c, ii = (double)cell.i * (double)cell.i, jj = (double)cell.j * (double)cell.j, p = c / n;
-        const double di = (double)cell.i - mu_i, dj = (double)cell.j - mu_j;
-        sl += c / (ii * jj);
-        sh += c * ii / jj;
-        ll += c * jj / ii;
-        lh += c * ii * jj;
-        gv += di * di * p;
-        sv += dj * dj * p;
-        ent -= p * std::log2(p);
-        en += p * p;
-    }
-    o.short_emphasis = se / n; o.long_emphasis = le / n; o.low_grey_emphasis = lg / n; o.high_grey_emphasis = hg / n;
-    o.short_low = sl / n; o.short_high = sh / n; o.long_low = ll / n; o.long_high = lh / n;
-    o.grey_nonuniformity = gn / n; o.grey_nonuniformity_norm = gn / n / n;
-    o.size_nonuniformity = sn / n; o.size_nonuniformity_norm = sn / n / n;
-    o.percentage = n / space;
-    o.grey_variance = gv; o.size_variance = sv; o.entropy = ent;
-    *out = o;
-    if (energy) *energy = en;
-}
-
-std::vector<Cell> cells_of(const uint32_t *row, int L, int cols)
-{
-    std::vector<Cell> cells;
-    if (!row) return cells;
-    for (int l = 0; l < L; ++l)
-        for (int j = 0; j < cols; ++j)
-            if (const uint32_t v = row[(size_t)l * cols + j]) cells.push_back(Cell{ l + 1, j + 1, (int64_t)v });
-    return cells;
+    return check_texture_bins(f, common_opts(o));
 }
 
 // the five NGTDM features from one component's count and diff rows of `cols` columns
@@ -202,25 +111,7 @@ int mi_unet_volume_nbhood_host(const int32_t *ids, const uint16_t *intensity, in
     const size_t dhw = (size_t)D * H * W, rows = (size_t)m * L;
     std::vector<mi_unet_vnbhood> t((size_t)m);
     std::memset(t.data(), 0, t.size() * sizeof(mi_unet_vnbhood));
-    auto member = [&](int32_t id) { return id >= 1 && id <= m; };
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        mi_unet_vnbhood &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        c.imin = c.voxels ? std::min(c.imin, v) : v;
-        c.imax = c.voxels ? std::max(c.imax, v) : v;
-        ++c.voxels;
-    }
-    std::vector<int32_t> key(dhw, 0);
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        const mi_unet_vnbhood &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        int32_t l;
-        if (o.mode == MI_UNET_VTEX_COUNT) l = ((v - c.imin) * L) / (c.imax - c.imin + 1);
-        else l = v < o.lo ? 0 : std::min(L - 1, (v - o.lo) / o.width);
-        key[i] = (ids[i] << 8) | l;
-    }
+    const std::vector<int32_t> key = texture_keys(ids, intensity, dhw, common_opts(o), t);
     if (w.ngt_count) std::memset(w.ngt_count, 0, rows * kCols * sizeof(uint32_t));
     if (w.ngt_diff) std::memset(w.ngt_diff, 0, rows * kCols * sizeof(uint64_t));
     if (w.dep) std::memset(w.dep, 0, rows * kCols * sizeof(uint32_t));
@@ -296,30 +187,11 @@ int mi_unet_volume_nbhood_host(const int32_t *ids, const uint16_t *intensity, in
             if (w.dzm) c.deepest = std::max<int32_t>(c.deepest, df[i]);
             if (w.dzm_axial) c.deepest_axial = std::max<int32_t>(c.deepest_axial, da[i]);
         }
-        // raster order: the first voxel of a zone that has not been seen opens it; the zone is flooded from there
-        std::vector<uint8_t> seen(dhw, 0);
-        std::vector<int32_t> todo;
-        for (size_t i = 0; i < dhw; ++i) {
-            const int32_t k = key[i];
-            if (!k || seen[i]) continue;
+        for_each_zone(key, D, H, W, [&](int32_t, int32_t k, const std::vector<int32_t> &members) {
             int near_f = 0xFFFF, near_a = 0xFFFF;
-            seen[i] = 1;
-            todo.assign(1, (int32_t)i);
-            while (!todo.empty()) {
-                const int32_t p = todo.back();
-                todo.pop_back();
+            for (const int32_t p : members) {
                 if (w.dzm) near_f = std::min<int>(near_f, df[(size_t)p]);
                 near_a = std::min<int>(near_a, da[(size_t)p]);
-                const int px = p % W, py = (p / W) % H, pz = p / (W * H);
-                for (int dz = -1; dz <= 1; ++dz)
-                    for (int dy = -1; dy <= 1; ++dy)
-                        for (int dx = -1; dx <= 1; ++dx) {
-                            if (!inside(px + dx, py + dy, pz + dz)) continue;
-                            const int32_t q = p + (dz * H + dy) * W + dx;
-                            if (key[(size_t)q] != k || seen[(size_t)q]) continue;
-                            seen[(size_t)q] = 1;
-                            todo.push_back(q);
-                        }
             }
             mi_unet_vnbhood &c = t[(k >> 8) - 1];
             const size_t row = ((size_t)((k >> 8) - 1) * L + (k & 255)) * Dm;
@@ -332,7 +204,7 @@ int mi_unet_volume_nbhood_host(const int32_t *ids, const uint16_t *intensity, in
                 ++w.dzm_axial[row + (size_t)(std::min(near_a, Dm) - 1)];
                 c.clamped_axial += near_a > Dm;
             }
-        }
+        });
     }
     std::memcpy(table, t.data(), t.size() * sizeof(mi_unet_vnbhood));
     return MI_UNET_OK;
@@ -342,8 +214,7 @@ int mi_unet_volume_nbhood_derive(const mi_unet_vnbhood *c, const mi_unet_vnbhood
 {
     const std::string f = "mi_unet_volume_nbhood_derive";
     if (!c || !rows || !out) return fail(MI_UNET_EARG, f + ": null argument");
-    if (c->voxels < 1) return fail(MI_UNET_EARG, f + ": voxels " + std::to_string(c->voxels) + " (a component has at least one voxel)");
-    if (L < 2 || L > MI_UNET_VTEX_MAX_LEVELS) return fail(MI_UNET_EARG, f + ": " + std::to_string(L) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
+    if (int rc = check_texture_component(f, c->voxels, L)) return rc;
     if (Dm < 1 || Dm > MI_UNET_VNBHOOD_MAX_DIST)
         return fail(MI_UNET_EARG, f + ": max_dist " + std::to_string(Dm) + " (1 .. " + std::to_string(MI_UNET_VNBHOOD_MAX_DIST) + ")");
     const uint32_t *const count = axial ? rows->ngt_count_axial : rows->ngt_count, *const dep = axial ? rows->dep_axial : rows->dep;
@@ -378,28 +249,23 @@ int mi_unet_volume_nbhood(mi_unet_t *h, const int32_t *ids, const uint16_t *inte
     const size_t n_count_a = w.ngt_count_axial ? rows * kColsAxial * sizeof(uint32_t) : 0, n_diff_a = w.ngt_count_axial ? rows * kColsAxial * sizeof(uint64_t) : 0;
     const size_t n_dep_a = w.dep_axial ? rows * kColsAxial * sizeof(uint32_t) : 0;
     const size_t n_dzm = w.dzm ? rows * o.max_dist * sizeof(uint32_t) : 0, n_dzm_a = w.dzm_axial ? rows * o.max_dist * sizeof(uint32_t) : 0;
-    const size_t at_count = up256(M * sizeof(mi_unet_vnbhood)), at_diff = at_count + up256(n_count), at_dep = at_diff + up256(n_diff);
-    const size_t at_count_a = at_dep + up256(n_dep), at_diff_a = at_count_a + up256(n_count_a), at_dep_a = at_diff_a + up256(n_diff_a);
-    const size_t at_dzm = at_dep_a + up256(n_dep_a), at_dzm_a = at_dzm + up256(n_dzm), results = at_dzm_a + up256(n_dzm_a);
+    Layout lay;
+    const size_t at_table = lay.take(M * sizeof(mi_unet_vnbhood)), at_count = lay.take(n_count), at_diff = lay.take(n_diff), at_dep = lay.take(n_dep);
+    const size_t at_count_a = lay.take(n_count_a), at_diff_a = lay.take(n_diff_a), at_dep_a = lay.take(n_dep_a);
+    const size_t at_dzm = lay.take(n_dzm), at_dzm_a = lay.take(n_dzm_a), results = lay.end;
     // device only: keys (ids in place), intensity, range, the zone stage's accumulators and ours, the forest with its sizes and scan,
     // one record and `found` that the zone list wants, the zones' minima, both distance stacks
-    const size_t at_keys = results, at_int = at_keys + up256(dhw * sizeof(int32_t)), at_range = at_int + up256(dhw * sizeof(uint16_t));
-    const size_t at_zacc = at_range + up256(M * sizeof(int2)), at_acc = at_zacc + up256(M * sizeof(VznAcc)), at_one = at_acc + up256(M * sizeof(VnbAcc));
-    const size_t stack = zones ? up256(dhw * sizeof(int32_t)) : 0, half = zones ? up256(dhw * sizeof(uint16_t)) : 0;
-    const size_t at_parent = at_one + 512, at_size = at_parent + stack, at_scan = at_size + stack;
-    const size_t at_zmin_a = at_scan + (zones ? up256(vzn_scan_ints(dhw) * sizeof(int32_t)) : 0);
-    const size_t at_da = at_zmin_a + (w.dzm_axial ? stack : 0), at_df = at_da + half, dev_need = at_df + (w.dzm ? half : 0);
-    // the stacks are staged behind the results, where the device keeps what only it needs
-    const size_t host_need = at_int + up256(dhw * sizeof(uint16_t));
+    const size_t at_keys = lay.take(dhw * sizeof(int32_t)), at_int = lay.take(dhw * sizeof(uint16_t));
+    const size_t host_need = lay.end;                           // the stacks are staged behind the results, where the device keeps what only it needs
+    const size_t at_range = lay.take(M * sizeof(int2)), at_zacc = lay.take(M * sizeof(VznAcc)), at_acc = lay.take(M * sizeof(VnbAcc)), at_one = lay.take(512);
+    const size_t stack = zones ? dhw * sizeof(int32_t) : 0, half = zones ? dhw * sizeof(uint16_t) : 0;
+    const size_t at_parent = lay.take(stack), at_size = lay.take(stack), at_scan = lay.take(zones ? vzn_scan_ints(dhw) * sizeof(int32_t) : 0);
+    const size_t at_zmin_a = lay.take(w.dzm_axial ? stack : 0), at_da = lay.take(half), at_df = lay.take(w.dzm ? half : 0);
     hipStream_t s = h->stream;
-    if (int rc = h->ws_vnb.reserve(dev_need, host_need, s)) return rc;
+    if (int rc = h->ws_vnb.reserve(lay.end, host_need, s)) return rc;
     uint8_t *const d = h->ws_vnb.d, *const p = h->ws_vnb.p;
-    host_copy(h, p + at_keys, ids, dhw * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(d + at_keys, p + at_keys, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    host_copy(h, p + at_int, intensity, dhw * sizeof(uint16_t));
-    HIP_TRY(hipMemcpyAsync(d + at_int, p + at_int, dhw * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    VolumeTextureArgs ta;
-    ta.D = D; ta.H = H; ta.W = W; ta.m = m; ta.mode = o.mode; ta.L = o.levels; ta.lo = o.lo; ta.width = o.width;
+    if (int rc = upload_stacks(h, h->ws_vnb, at_keys, ids, at_int, intensity, dhw)) return rc;
+    const VolumeTextureArgs ta = texture_args(D, H, W, m, common_opts(o));
     VolumeZonesArgs za;
     za.D = D; za.H = H; za.W = W; za.m = m; za.L = o.levels; za.R = 1;
     VolumeNbhoodArgs a;
@@ -436,11 +302,11 @@ int mi_unet_volume_nbhood(mi_unet_t *h, const int32_t *ids, const uint16_t *inte
         if (e == hipSuccess)
             e = launch_volume_nbhood_zones(d_keys, a, want, d_parent, d_da, d_df, d_size, reinterpret_cast<int32_t *>(d + at_zmin_a), d_acc, t, s);
     }
-    if (e == hipSuccess) e = launch_volume_nbhood_finish(d_range, a, want, d_zacc, d_acc, t, reinterpret_cast<mi_unet_vnbhood *>(d), s);
+    if (e == hipSuccess) e = launch_volume_nbhood_finish(d_range, a, want, d_zacc, d_acc, t, reinterpret_cast<mi_unet_vnbhood *>(d + at_table), s);
     if (e != hipSuccess) return fail(MI_UNET_EHIP, std::string("volume nbhood launch: ") + hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(p, d, results, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(table, p, M * sizeof(mi_unet_vnbhood));
+    std::memcpy(table, p + at_table, M * sizeof(mi_unet_vnbhood));
     if (w.ngt_count) std::memcpy(w.ngt_count, p + at_count, n_count);
     if (w.ngt_diff) std::memcpy(w.ngt_diff, p + at_diff, n_diff);
     if (w.dep) std::memcpy(w.dep, p + at_dep, n_dep);

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "stage_common.h"
+#include "texture_common.h"
 
 static_assert(sizeof(mi_unet_vtexture) == 32, "mi_unet_vtexture is 32 bytes without padding");
 static_assert(sizeof(mi_unet_vtexture_opts) == 16, "mi_unet_vtexture_opts is four ints");
@@ -22,7 +22,6 @@ namespace miunet {
 namespace {
 
 constexpr mi_unet_vtexture_opts kDefaultOpts{ MI_UNET_VTEX_COUNT, 32, 0, 1 };
-constexpr int kMaxSide = MI_UNET_SCORE_VOLUME_MAX_SIDE;
 
 // every MI_UNET_EARG case of the two entry points; nothing has been queued or written when it fails
 int check_texture_args(const char *fn, const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const mi_unet_vtexture_opts &o,
@@ -30,18 +29,10 @@ int check_texture_args(const char *fn, const int32_t *ids, const uint16_t *inten
 {
     const std::string f = fn;
     if (!ids || !intensity || !table || !hist) return fail(MI_UNET_EARG, f + ": null argument");
-    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
-    if ((int64_t)D * H * W >(int64_t)MI_UNET_VTEX_MAX_VOXELS) return fail(MI_UNET_EARG, f + ": D * H * W must not pass 2^28");   // (< 2^39: no overflow)
-    if (m < 1 || m > MI_UNET_VOLUME_MAX_TABLE)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE) + ")");
-    if (o.mode != MI_UNET_VTEX_COUNT && o.mode != MI_UNET_VTEX_WIDTH) return fail(MI_UNET_EARG, f + ": mode " + std::to_string(o.mode) + " does not exist");
-    if (o.levels < 2 || o.levels > MI_UNET_VTEX_MAX_LEVELS)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(o.levels) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
+    if (int rc = check_texture_volume(f, D, H, W, m, o)) return rc;
     if ((int64_t)m * o.levels * o.levels > (int64_t)MI_UNET_VTEX_MAX_CELLS)
         return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components at " + std::to_string(o.levels) + " levels pass 2^22 cells per table");
-    if (o.width < 1 || o.width > 65536) return fail(MI_UNET_EARG, f + ": width " + std::to_string(o.width) + " is outside 1 .. 65536");
-    if (o.lo < 0 || o.lo > 65535) return fail(MI_UNET_EARG, f + ": lo " + std::to_string(o.lo) + " is outside 0 .. 65535");
-    return MI_UNET_OK;
+    return check_texture_bins(f, o);
 }
 
 }  // namespace
@@ -62,26 +53,11 @@ int mi_unet_volume_texture_host(const int32_t *ids, const uint16_t *intensity, i
     std::vector<mi_unet_vtexture> t((size_t)m);
     std::memset(t.data(), 0, t.size() * sizeof(mi_unet_vtexture));
     auto member = [&](int32_t id) { return id >= 1 && id <= m; };
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        mi_unet_vtexture &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        c.imin = c.voxels ? std::min(c.imin, v) : v;
-        c.imax = c.voxels ? std::max(c.imax, v) : v;
-        ++c.voxels;
-    }
-    std::vector<uint8_t> level(dhw, 0);
+    const std::vector<int32_t> key = texture_keys(ids, intensity, dhw, o, t);
+    auto level = [&](size_t i) { return (size_t)(key[i] & 255); };
     std::memset(hist, 0, (size_t)m * L * sizeof(uint32_t));
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        const mi_unet_vtexture &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        int32_t l;
-        if (o.mode == MI_UNET_VTEX_COUNT) l = ((v - c.imin) * L) / (c.imax - c.imin + 1);
-        else l = v < o.lo ? 0 : std::min(L - 1, (v - o.lo) / o.width);
-        level[i] = (uint8_t)l;
-        ++hist[(size_t)(ids[i] - 1) * L + l];
-    }
+    for (size_t i = 0; i < dhw; ++i)
+        if (key[i]) ++hist[(size_t)(ids[i] - 1) * L + level(i)];
     for (int r = 0; r < m; ++r)
         for (int l = 0; l < L; ++l) t[r].levels_used += hist[(size_t)r * L + l] != 0;
     if (glcm) std::memset(glcm, 0, (size_t)m * LL * sizeof(uint32_t));
@@ -92,15 +68,15 @@ int mi_unet_volume_texture_host(const int32_t *ids, const uint16_t *intensity, i
             for (int y = 0; y < H; ++y)
                 for (int x = 0; x < W; ++x, ++p) {
                     if (!member(*p)) continue;
-                    const size_t i = (size_t)(p - ids), row = ((size_t)(*p - 1) * L + level[i]) * L;
+                    const size_t i = (size_t)(p - ids), row = ((size_t)(*p - 1) * L + level(i)) * L;
                     for (int dz = 0; dz <= (glcm ? 1 : 0); ++dz)
                         for (int dy = dz ? -1 : 0; dy <= 1; ++dy)
                             for (int dx = (dz || dy) ? -1 : 1; dx <= 1; ++dx) {
                                 if (z + dz >= D || y + dy < 0 || y + dy >= H || x + dx < 0 || x + dx >= W) continue;
                                 const size_t q = i + ((size_t)dz * H + dy) * W + dx;     // (dy, dx may be -1: size_t arithmetic wraps back)
                                 if (ids[q] != *p) continue;
-                                if (glcm) ++glcm[row + level[q]];
-                                if (glcm_axial && dz == 0) ++glcm_axial[row + level[q]];
+                                if (glcm) ++glcm[row + level(q)];
+                                if (glcm_axial && dz == 0) ++glcm_axial[row + level(q)];
                             }
                 }
         for (int r = 0; r < m; ++r)
@@ -117,8 +93,7 @@ int mi_unet_volume_texture_derive(const mi_unet_vtexture *c, const uint32_t *his
 {
     const std::string f = "mi_unet_volume_texture_derive";
     if (!c || !hist || !out) return fail(MI_UNET_EARG, f + ": null argument");
-    if (c->voxels < 1) return fail(MI_UNET_EARG, f + ": voxels " + std::to_string(c->voxels) + " (a component has at least one voxel)");
-    if (L < 2 || L > MI_UNET_VTEX_MAX_LEVELS) return fail(MI_UNET_EARG, f + ": " + std::to_string(L) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
+    if (int rc = check_texture_component(f, c->voxels, L)) return rc;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     mi_unet_vtexture_features o;
     const double n = (double)c->voxels;
@@ -202,25 +177,22 @@ int mi_unet_volume_texture(mi_unet_t *h, const int32_t *ids, const uint16_t *int
     const size_t dhw = (size_t)D * H * W, M = (size_t)m, L = (size_t)o.levels;
     const size_t table_bytes = M * sizeof(mi_unet_vtexture), hist_bytes = M * L * sizeof(uint32_t), cells_bytes = M * L * L * sizeof(uint32_t);
     // device: keys (ids in place), intensity, table, hist, inter (then glcm), axial | range; pinned: the same up to axial
-    const size_t at_int = up256(dhw * sizeof(int32_t)), at_table = at_int + up256(dhw * sizeof(uint16_t)), at_hist = at_table + up256(table_bytes);
-    const size_t at_inter = at_hist + up256(hist_bytes), at_axial = at_inter + up256(cells_bytes), at_range = at_axial + up256(cells_bytes);
-    const size_t dev_need = at_range + up256(M * sizeof(int2)), host_need = at_range;
+    Layout lay;
+    const size_t at_keys = lay.take(dhw * sizeof(int32_t)), at_int = lay.take(dhw * sizeof(uint16_t)), at_table = lay.take(table_bytes);
+    const size_t at_hist = lay.take(hist_bytes), at_inter = lay.take(cells_bytes), at_axial = lay.take(cells_bytes), host_need = lay.end;
+    const size_t at_range = lay.take(M * sizeof(int2));
     hipStream_t s = h->stream;
-    if (int rc = h->ws_vtx.reserve(dev_need, host_need, s)) return rc;
+    if (int rc = h->ws_vtx.reserve(lay.end, host_need, s)) return rc;
     uint8_t *const d = h->ws_vtx.d, *const p = h->ws_vtx.p;
-    host_copy(h, p, ids, dhw * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(d, p, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    host_copy(h, p + at_int, intensity, dhw * sizeof(uint16_t));
-    HIP_TRY(hipMemcpyAsync(d + at_int, p + at_int, dhw * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    VolumeTextureArgs a;
-    a.D = D; a.H = H; a.W = W; a.m = m; a.mode = o.mode; a.L = o.levels; a.lo = o.lo; a.width = o.width;
+    if (int rc = upload_stacks(h, h->ws_vtx, at_keys, ids, at_int, intensity, dhw)) return rc;
+    const VolumeTextureArgs a = texture_args(D, H, W, m, o);
     // the 13-offset table is the sum of its two parts, so it needs both
     const int want = glcm ? (VTX_WANT_AXIAL | VTX_WANT_INTER) : glcm_axial ? VTX_WANT_AXIAL : 0;
     bool lds_table = true;
 #ifdef MIUNET_EXPERIMENTS
     if (const char *v = std::getenv("MIUNET_VTX_EXP")) lds_table = std::atoi(v) != 1;            // 1: every count straight to memory
 #endif
-    int32_t *const d_keys = reinterpret_cast<int32_t *>(d);
+    int32_t *const d_keys = reinterpret_cast<int32_t *>(d + at_keys);
     int2 *const d_range = reinterpret_cast<int2 *>(d + at_range);
     mi_unet_vtexture *const d_table = reinterpret_cast<mi_unet_vtexture *>(d + at_table);
     uint32_t *const d_hist = reinterpret_cast<uint32_t *>(d + at_hist), *const d_inter = reinterpret_cast<uint32_t *>(d + at_inter);

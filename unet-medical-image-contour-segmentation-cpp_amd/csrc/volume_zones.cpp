@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "stage_common.h"
+#include "texture_common.h"
 
 static_assert(sizeof(mi_unet_vzones) == 56, "mi_unet_vzones is 56 bytes without padding");
 static_assert(sizeof(mi_unet_vzones_opts) == 20, "mi_unet_vzones_opts is five ints");
@@ -21,7 +21,6 @@ namespace miunet {
 namespace {
 
 constexpr mi_unet_vzones_opts kDefaultOpts{ MI_UNET_VTEX_COUNT, 32, 0, 1, 32 };
-constexpr int kMaxSide = MI_UNET_SCORE_VOLUME_MAX_SIDE;
 
 // every MI_UNET_EARG case of the two entry points; nothing has been queued or written when it fails
 int check_zones_args(const char *fn, const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const mi_unet_vzones_opts &o,
@@ -30,20 +29,13 @@ int check_zones_args(const char *fn, const int32_t *ids, const uint16_t *intensi
     const std::string f = fn;
     if (!ids || !intensity || !table) return fail(MI_UNET_EARG, f + ": null argument");
     if ((zones == nullptr) != (found == nullptr)) return fail(MI_UNET_EARG, f + ": zones and found are both given or both null");
-    if (int rc = check_sides_max(f, D, H, W, kMaxSide)) return rc;
-    if ((int64_t)D * H * W > (int64_t)MI_UNET_VTEX_MAX_VOXELS) return fail(MI_UNET_EARG, f + ": D * H * W must not pass 2^28");   // (< 2^39: no overflow)
-    if (m < 1 || m > MI_UNET_VOLUME_MAX_TABLE)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components (1 .. " + std::to_string(MI_UNET_VOLUME_MAX_TABLE) + ")");
-    if (o.mode != MI_UNET_VTEX_COUNT && o.mode != MI_UNET_VTEX_WIDTH) return fail(MI_UNET_EARG, f + ": mode " + std::to_string(o.mode) + " does not exist");
-    if (o.levels < 2 || o.levels > MI_UNET_VTEX_MAX_LEVELS)
-        return fail(MI_UNET_EARG, f + ": " + std::to_string(o.levels) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
+    if (int rc = check_texture_volume(f, D, H, W, m, common_opts(o))) return rc;
     if (o.max_run < 2 || o.max_run > MI_UNET_VZONES_MAX_RUN)
         return fail(MI_UNET_EARG, f + ": max_run " + std::to_string(o.max_run) + " (2 .. " + std::to_string(MI_UNET_VZONES_MAX_RUN) + ")");
     if ((int64_t)m * o.levels * o.max_run > (int64_t)MI_UNET_VTEX_MAX_CELLS)
         return fail(MI_UNET_EARG, f + ": " + std::to_string(m) + " components at " + std::to_string(o.levels) + " levels and max_run " +
                                       std::to_string(o.max_run) + " pass 2^22 cells per table");
-    if (o.width < 1 || o.width > 65536) return fail(MI_UNET_EARG, f + ": width " + std::to_string(o.width) + " is outside 1 .. 65536");
-    if (o.lo < 0 || o.lo > 65535) return fail(MI_UNET_EARG, f + ": lo " + std::to_string(o.lo) + " is outside 0 .. 65535");
+    if (int rc = check_texture_bins(f, common_opts(o))) return rc;
     if (zones && (cap < 1 || cap > MI_UNET_VZONES_MAX_CAP))
         return fail(MI_UNET_EARG, f + ": cap " + std::to_string(cap) + " (1 .. " + std::to_string(MI_UNET_VZONES_MAX_CAP) + ")");
     return MI_UNET_OK;
@@ -53,80 +45,10 @@ int check_zones_args(const char *fn, const int32_t *ids, const uint16_t *intensi
 constexpr int kOffsets[13][3] = { { 1, 0, 0 }, { -1, 1, 0 }, { 0, 1, 0 }, { 1, 1, 0 }, { -1, -1, 1 }, { 0, -1, 1 }, { 1, -1, 1 }, { -1, 0, 1 },
                                   { 0, 0, 1 }, { 1, 0, 1 }, { -1, 1, 1 }, { 0, 1, 1 }, { 1, 1, 1 } };
 
-struct Cell {
-    int64_t i, j, c;            // level + 1, run length or zone size, count
-};
-
-// the 16 features over the non-zero cells of one matrix, sorted by (i, j); `space` = voxels * directions
-void features(const std::vector<Cell> &cells, int L, double space, mi_unet_vzone_features *out)
-{
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    mi_unet_vzone_features o;
-    int64_t N = 0, si = 0, sj = 0;
-    std::vector<int64_t> ni((size_t)L + 1, 0);
-    std::vector<std::pair<int64_t, int64_t>> nj;                // (j, n_j), j ascending
-    for (const Cell &c : cells) {
-        N += c.c;
-        ni[(size_t)c.i] += c.c;
-        si += c.i * c.c;
-        sj += c.j * c.c;
-        nj.emplace_back(c.j, c.c);
-    }
-    if (N == 0) {
-        double *const v = reinterpret_cast<double *>(&o);
-        for (int k = 0; k < 16; ++k) v[k] = nan;
-        *out = o;
-        return;
-    }
-    std::sort(nj.begin(), nj.end());
-    size_t u = 0;
-    for (size_t k = 0; k < nj.size(); ++k) {
-        if (u && nj[u - 1].first == nj[k].first) nj[u - 1].second += nj[k].second;
-        else nj[u++] = nj[k];
-    }
-    nj.resize(u);
-    const double n = (double)N, mu_i = (double)si / n, mu_j = (double)sj / n;
-    double se = 0.0, le = 0.0, lg = 0.0, hg = 0.0, gn = 0.0, sn = 0.0;
-    for (const auto &e : nj) {
-        const double j = (double)e.first, c = (double)e.second;
-        se += c / (j * j);
-        le += c * (j * j);
-        sn += c * c;
-    }
-    for (int i = 1; i <= L; ++i) {
-        if (!ni[(size_t)i]) continue;
-        const double c = (double)ni[(size_t)i], ii = (double)i * (double)i;
-        lg += c / ii;
-        hg += c * ii;
-        gn += c * c;
-    }
-    double sl = 0.0, sh = 0.0, ll = 0.0, lh = 0.0, gv = 0.0, sv = 0.0, ent = 0.0;
-    for (const Cell &cell : cells) {
-        const double c = (double)cell.c, ii = (double)cell.i * (double)cell.i, jj = (double)cell.j * (double)cell.j, p = c / n;
-        const double di = (double)cell.i - mu_i, dj = (double)cell.j - mu_j;
-        sl += c / (ii * jj);
-        sh += c * ii / jj;
-        ll += c * jj / ii;
-        lh += c * ii * jj;
-        gv += di * di * p;
-        sv += dj * dj * p;
-        ent -= p * std::log2(p);
-    }
-    o.short_emphasis = se / n; o.long_emphasis = le / n; o.low_grey_emphasis = lg / n; o.high_grey_emphasis = hg / n;
-    o.short_low = sl / n; o.short_high = sh / n; o.long_low = ll / n; o.long_high = lh / n;
-    o.grey_nonuniformity = gn / n; o.grey_nonuniformity_norm = gn / n / n;
-    o.size_nonuniformity = sn / n; o.size_nonuniformity_norm = sn / n / n;
-    o.percentage = n / space;
-    o.grey_variance = gv; o.size_variance = sv; o.entropy = ent;
-    *out = o;
-}
-
 int check_feature_args(const std::string &f, const mi_unet_vzones *c, const void *data, const void *out, int L)
 {
     if (!c || !data || !out) return fail(MI_UNET_EARG, f + ": null argument");
-    if (c->voxels < 1) return fail(MI_UNET_EARG, f + ": voxels " + std::to_string(c->voxels) + " (a component has at least one voxel)");
-    if (L < 2 || L > MI_UNET_VTEX_MAX_LEVELS) return fail(MI_UNET_EARG, f + ": " + std::to_string(L) + " levels (2 .. " + std::to_string(MI_UNET_VTEX_MAX_LEVELS) + ")");
-    return MI_UNET_OK;
+    return check_texture_component(f, c->voxels, L);
 }
 
 }  // namespace
@@ -146,25 +68,7 @@ int mi_unet_volume_zones_host(const int32_t *ids, const uint16_t *intensity, int
     const size_t dhw = (size_t)D * H * W, cells = (size_t)m * L * R;
     std::vector<mi_unet_vzones> t((size_t)m);
     std::memset(t.data(), 0, t.size() * sizeof(mi_unet_vzones));
-    auto member = [&](int32_t id) { return id >= 1 && id <= m; };
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        mi_unet_vzones &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        c.imin = c.voxels ? std::min(c.imin, v) : v;
-        c.imax = c.voxels ? std::max(c.imax, v) : v;
-        ++c.voxels;
-    }
-    std::vector<int32_t> key(dhw, 0);
-    for (size_t i = 0; i < dhw; ++i) {
-        if (!member(ids[i])) continue;
-        const mi_unet_vzones &c = t[ids[i] - 1];
-        const int32_t v = intensity[i];
-        int32_t l;
-        if (o.mode == MI_UNET_VTEX_COUNT) l = ((v - c.imin) * L) / (c.imax - c.imin + 1);
-        else l = v < o.lo ? 0 : std::min(L - 1, (v - o.lo) / o.width);
-        key[i] = (ids[i] << 8) | l;
-    }
+    const std::vector<int32_t> key = texture_keys(ids, intensity, dhw, common_opts(o), t);
     if (rlm) std::memset(rlm, 0, cells * sizeof(uint32_t));
     if (rlm_axial) std::memset(rlm_axial, 0, cells * sizeof(uint32_t));
     auto inside = [&](int x, int y, int z) { return x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D; };
@@ -202,37 +106,15 @@ int mi_unet_volume_zones_host(const int32_t *ids, const uint16_t *intensity, int
                 }
     }
     if (zones) {
-        // raster order: the first voxel of a zone that has not been seen opens it; the zone is flooded from there
-        std::vector<uint8_t> seen(dhw, 0);
-        std::vector<int32_t> todo;
         int64_t n_zones = 0;
-        for (size_t i = 0; i < dhw; ++i) {
-            const int32_t k = key[i];
-            if (!k || seen[i]) continue;
-            int32_t size = 0;
-            seen[i] = 1;
-            todo.assign(1, (int32_t)i);
-            while (!todo.empty()) {
-                const int32_t p = todo.back();
-                todo.pop_back();
-                ++size;
-                const int px = p % W, py = (p / W) % H, pz = p / (W * H);
-                for (int dz = -1; dz <= 1; ++dz)
-                    for (int dy = -1; dy <= 1; ++dy)
-                        for (int dx = -1; dx <= 1; ++dx) {
-                            if (!inside(px + dx, py + dy, pz + dz)) continue;
-                            const int32_t q = p + (dz * H + dy) * W + dx;
-                            if (key[(size_t)q] != k || seen[(size_t)q]) continue;
-                            seen[(size_t)q] = 1;
-                            todo.push_back(q);
-                        }
-            }
+        for_each_zone(key, D, H, W, [&](int32_t first, int32_t k, const std::vector<int32_t> &members) {
+            const int32_t size = (int32_t)members.size();
             mi_unet_vzones &c = t[(k >> 8) - 1];
             ++c.zones;
             c.largest_zone = std::max(c.largest_zone, size);
-            if (n_zones < cap) zones[n_zones] = mi_unet_vzone{ (int32_t)i, (k >> 8) - 1, k & 255, size };
+            if (n_zones < cap) zones[n_zones] = mi_unet_vzone{ first, (k >> 8) - 1, k & 255, size };
             ++n_zones;                                          // (at most D * H * W <= 2^28)
-        }
+        });
         if (n_zones < cap) std::memset(zones + n_zones, 0, (size_t)(cap - n_zones) * sizeof(mi_unet_vzone));
         *found = (int)n_zones;
     }
@@ -247,11 +129,7 @@ int mi_unet_volume_zones_run_features(const mi_unet_vzones *c, const uint32_t *r
     if (R < 2 || R > MI_UNET_VZONES_MAX_RUN)
         return fail(MI_UNET_EARG, f + ": max_run " + std::to_string(R) + " (2 .. " + std::to_string(MI_UNET_VZONES_MAX_RUN) + ")");
     if (directions != 13 && directions != 4) return fail(MI_UNET_EARG, f + ": " + std::to_string(directions) + " directions (13 or 4)");
-    std::vector<Cell> cells;
-    for (int l = 0; l < L; ++l)
-        for (int j = 0; j < R; ++j)
-            if (const uint32_t v = rlm_row[(size_t)l * R + j]) cells.push_back(Cell{ l + 1, j + 1, (int64_t)v });
-    features(cells, L, (double)c->voxels * (double)directions, out);
+    matrix_features(cells_of(rlm_row, L, R), L, (double)c->voxels * (double)directions, out, nullptr);
     return MI_UNET_OK;
 }
 
@@ -274,7 +152,7 @@ int mi_unet_volume_zones_zone_features(const mi_unet_vzones *c, const mi_unet_vz
         if (!cells.empty() && cells.back().i == e.first + 1 && cells.back().j == e.second) ++cells.back().c;
         else cells.push_back(Cell{ e.first + 1, e.second, 1 });
     }
-    features(cells, L, (double)c->voxels, out);
+    matrix_features(cells, L, (double)c->voxels, out, nullptr);
     return MI_UNET_OK;
 }
 
@@ -292,28 +170,23 @@ int mi_unet_volume_zones(mi_unet_t *h, const int32_t *ids, const uint16_t *inten
     const size_t scan_ints = zones ? vzn_scan_ints(dhw) : 0;
     // device and pinned alike: table, found, inter (then rlm), axial, zones | device only: keys (ids in place), intensity, range, acc,
     // parent, size, scan
-    const size_t at_found = up256(table_bytes), at_inter = at_found + 256, at_axial = at_inter + up256(cells_bytes);
-    const size_t at_zones = at_axial + up256(cells_bytes), at_keys = at_zones + up256(keep * sizeof(mi_unet_vzone));
-    const size_t at_int = at_keys + up256(dhw * sizeof(int32_t)), at_range = at_int + up256(dhw * sizeof(uint16_t));
-    const size_t at_acc = at_range + up256(M * sizeof(int2)), at_parent = at_acc + up256(M * sizeof(VznAcc));
-    const size_t at_size = at_parent + (zones ? up256(dhw * sizeof(int32_t)) : 0), at_scan = at_size + (zones ? up256(dhw * sizeof(int32_t)) : 0);
+    Layout lay;
+    const size_t at_table = lay.take(table_bytes), at_found = lay.take(256), at_inter = lay.take(cells_bytes), at_axial = lay.take(cells_bytes);
+    const size_t at_zones = lay.take(keep * sizeof(mi_unet_vzone)), at_keys = lay.take(dhw * sizeof(int32_t)), at_int = lay.take(dhw * sizeof(uint16_t));
+    const size_t host_need = lay.end;                           // the stacks are staged behind the results, where the device keeps what only it needs
+    const size_t at_range = lay.take(M * sizeof(int2)), at_acc = lay.take(M * sizeof(VznAcc));
+    const size_t at_parent = lay.take(zones ? dhw * sizeof(int32_t) : 0), at_size = lay.take(zones ? dhw * sizeof(int32_t) : 0);
+    const size_t at_scan = lay.take(scan_ints * sizeof(int32_t));
     // launch_volume_texture_keys takes m L^2 <= 2^22 at once; a call beyond that (L above R) goes through it in parts of `part_m`
     // components, which need the ids kept, a stack for the part and one for the joined keys
     const int part_m = (int)std::min<int64_t>(m, (int64_t)MI_UNET_VTEX_MAX_CELLS / ((int64_t)o.levels * o.levels));
     const bool parts = part_m < m;
-    const size_t at_part = at_scan + up256(scan_ints * sizeof(int32_t)), at_joined = at_part + (parts ? up256(dhw * sizeof(int32_t)) : 0);
-    const size_t dev_need = at_joined + (parts ? up256(dhw * sizeof(int32_t)) : 0);
-    // the stacks are staged behind the results, where the device keeps what only it needs
-    const size_t host_need = at_int + up256(dhw * sizeof(uint16_t));
+    const size_t at_part = lay.take(parts ? dhw * sizeof(int32_t) : 0), at_joined = lay.take(parts ? dhw * sizeof(int32_t) : 0);
     hipStream_t s = h->stream;
-    if (int rc = h->ws_vzn.reserve(dev_need, host_need, s)) return rc;
+    if (int rc = h->ws_vzn.reserve(lay.end, host_need, s)) return rc;
     uint8_t *const d = h->ws_vzn.d, *const p = h->ws_vzn.p;
-    host_copy(h, p + at_keys, ids, dhw * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(d + at_keys, p + at_keys, dhw * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    host_copy(h, p + at_int, intensity, dhw * sizeof(uint16_t));
-    HIP_TRY(hipMemcpyAsync(d + at_int, p + at_int, dhw * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    VolumeTextureArgs ta;
-    ta.D = D; ta.H = H; ta.W = W; ta.m = m; ta.mode = o.mode; ta.L = o.levels; ta.lo = o.lo; ta.width = o.width;
+    if (int rc = upload_stacks(h, h->ws_vzn, at_keys, ids, at_int, intensity, dhw)) return rc;
+    VolumeTextureArgs ta = texture_args(D, H, W, m, common_opts(o));
     VolumeZonesArgs a;
     a.D = D; a.H = H; a.W = W; a.m = m; a.L = o.levels; a.R = o.max_run;
     // the 13-offset table is the sum of its two parts, so it needs both
@@ -322,7 +195,7 @@ int mi_unet_volume_zones(mi_unet_t *h, const int32_t *ids, const uint16_t *inten
     int32_t *const d_keys = parts ? reinterpret_cast<int32_t *>(d + at_joined) : d_ids;      // (one part: the ids become the keys in place)
     int2 *const d_range = reinterpret_cast<int2 *>(d + at_range);
     VznAcc *const d_acc = reinterpret_cast<VznAcc *>(d + at_acc);
-    mi_unet_vzones *const d_table = reinterpret_cast<mi_unet_vzones *>(d);
+    mi_unet_vzones *const d_table = reinterpret_cast<mi_unet_vzones *>(d + at_table);
     int32_t *const d_found = reinterpret_cast<int32_t *>(d + at_found);
     uint32_t *const d_inter = reinterpret_cast<uint32_t *>(d + at_inter), *const d_axial = reinterpret_cast<uint32_t *>(d + at_axial);
     mi_unet_vzone *const d_zones = reinterpret_cast<mi_unet_vzone *>(d + at_zones);
@@ -357,7 +230,7 @@ int mi_unet_volume_zones(mi_unet_t *h, const int32_t *ids, const uint16_t *inten
                                hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    mi_unet_vzones *const t = reinterpret_cast<mi_unet_vzones *>(p);
+    mi_unet_vzones *const t = reinterpret_cast<mi_unet_vzones *>(p + at_table);
     if (!rlm_axial)
         for (int r = 0; r < m; ++r) t[r].runs_axial = t[r].clamped_axial = 0;      // (a part of rlm, not asked for as a table)
     std::memcpy(table, t, table_bytes);

@@ -506,32 +506,50 @@ private:
         std::cout << "Volume measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " ends " << cur.max_ends << std::endl;
     }
 
+    // The words of a texture command behind its name -- on [levels N] [count | width W [lo L]] [channel N] and the command's own `word N`
+    // pairs, which go to own(word, value) -- or off: fills `t` (on, levels, mode, width, lo, channel) and returns whether the words are valid
+    template <class T, class Own>
+    static bool texture_words(const Words &w, T &t, Own own)
+    {
+        bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+        t.on = w[1] == "on";
+        bool binned = false;                                    // `count` or `width` has been given; `lo` belongs to `width`
+        for (size_t i = 2; ok && i < w.size();) {
+            if (w[i] == "count") {
+                ok = !binned;
+                binned = true;
+                i += 1;
+                continue;
+            }
+            int value = 0;
+            ok = i + 1 < w.size() && to_int(w[i + 1], value);
+            if (!ok) break;
+            if (w[i] == "levels") t.levels = value;
+            else if (w[i] == "channel") t.channel = value;
+            else if (own(w[i], value)) {}
+            else if (w[i] == "width" && !binned) { t.mode = MI_UNET_VTEX_WIDTH; t.width = value; binned = true; }
+            else if (w[i] == "lo" && t.mode == MI_UNET_VTEX_WIDTH) t.lo = value;
+            else ok = false;
+            i += 2;
+        }
+        return ok;
+    }
+
+    // the part of a texture setting that every such command prints (no line end)
+    template <class T>
+    static void print_texture_setting(const char *name, const T &cur)
+    {
+        std::cout << "Volume " << name << ": " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
+        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
+        else std::cout << "count";
+    }
+
     // voltexture on [levels N] [count | width W [lo L]] [channel N] | voltexture off | voltexture (prints the setting in force)
     void cmd_voltexture(const Words &w)
     {
         if (w.size() >= 2) {
             MedicalSeg::VolumeTexture t;
-            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
-            t.on = w[1] == "on";
-            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
-            for (size_t i = 2; ok && i < w.size();) {
-                if (w[i] == "count") {
-                    ok = !binned;
-                    binned = true;
-                    i += 1;
-                    continue;
-                }
-                int value = 0;
-                ok = i + 1 < w.size() && to_int(w[i + 1], value);
-                if (!ok) break;
-                if (w[i] == "levels") t.levels = value;
-                else if (w[i] == "channel") t.channel = value;
-                else if (w[i] == "width" && !binned) { t.mode = MI_UNET_VTEX_WIDTH; t.width = value; binned = true; }
-                else if (w[i] == "lo" && t.mode == MI_UNET_VTEX_WIDTH) t.lo = value;
-                else ok = false;
-                i += 2;
-            }
-            if (!ok) {
+            if (!texture_words(w, t, [](const std::string &, int) { return false; })) {
                 std::cerr << "Error: Invalid voltexture command (expected on [levels N] [count|width W [lo L]] [channel N] or off)" << std::endl;
                 return;
             }
@@ -540,10 +558,8 @@ private:
                 return;
             }
         }
-        const MedicalSeg::VolumeTexture cur = MedicalSeg::get_volume_texture();
-        std::cout << "Volume texture: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
-        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo << std::endl;
-        else std::cout << "count" << std::endl;
+        print_texture_setting("texture", MedicalSeg::get_volume_texture());
+        std::cout << std::endl;
     }
 
     // volzones on [levels N] [count | width W [lo L]] [run N] [channel N] | volzones off | volzones (prints the setting in force)
@@ -551,28 +567,12 @@ private:
     {
         if (w.size() >= 2) {
             MedicalSeg::VolumeZones z;
-            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
-            z.on = w[1] == "on";
-            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
-            for (size_t i = 2; ok && i < w.size();) {
-                if (w[i] == "count") {
-                    ok = !binned;
-                    binned = true;
-                    i += 1;
-                    continue;
-                }
-                int value = 0;
-                ok = i + 1 < w.size() && to_int(w[i + 1], value);
-                if (!ok) break;
-                if (w[i] == "levels") z.levels = value;
-                else if (w[i] == "channel") z.channel = value;
-                else if (w[i] == "run") z.max_run = value;
-                else if (w[i] == "width" && !binned) { z.mode = MI_UNET_VTEX_WIDTH; z.width = value; binned = true; }
-                else if (w[i] == "lo" && z.mode == MI_UNET_VTEX_WIDTH) z.lo = value;
-                else ok = false;
-                i += 2;
-            }
-            if (!ok) {
+            auto own = [&](const std::string &word, int value) {
+                if (word != "run") return false;
+                z.max_run = value;
+                return true;
+            };
+            if (!texture_words(w, z, own)) {
                 std::cerr << "Error: Invalid volzones command (expected on [levels N] [count|width W [lo L]] [run N] [channel N] or off)" << std::endl;
                 return;
             }
@@ -582,9 +582,7 @@ private:
             }
         }
         const MedicalSeg::VolumeZones cur = MedicalSeg::get_volume_zones();
-        std::cout << "Volume zones: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
-        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
-        else std::cout << "count";
+        print_texture_setting("zones", cur);
         std::cout << " run " << cur.max_run << std::endl;
     }
 
@@ -593,29 +591,12 @@ private:
     {
         if (w.size() >= 2) {
             MedicalSeg::VolumeNbhood n;
-            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
-            n.on = w[1] == "on";
-            bool binned = false;                                // `count` or `width` has been given; `lo` belongs to `width`
-            for (size_t i = 2; ok && i < w.size();) {
-                if (w[i] == "count") {
-                    ok = !binned;
-                    binned = true;
-                    i += 1;
-                    continue;
-                }
-                int value = 0;
-                ok = i + 1 < w.size() && to_int(w[i + 1], value);
-                if (!ok) break;
-                if (w[i] == "levels") n.levels = value;
-                else if (w[i] == "channel") n.channel = value;
-                else if (w[i] == "alpha") n.alpha = value;
-                else if (w[i] == "dist") n.max_dist = value;
-                else if (w[i] == "width" && !binned) { n.mode = MI_UNET_VTEX_WIDTH; n.width = value; binned = true; }
-                else if (w[i] == "lo" && n.mode == MI_UNET_VTEX_WIDTH) n.lo = value;
-                else ok = false;
-                i += 2;
-            }
-            if (!ok) {
+            auto own = [&](const std::string &word, int value) {
+                if (word != "alpha" && word != "dist") return false;
+                (word == "alpha" ? n.alpha : n.max_dist) = value;
+                return true;
+            };
+            if (!texture_words(w, n, own)) {
                 std::cerr << "Error: Invalid volnbhood command (expected on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N] or off)" << std::endl;
                 return;
             }
@@ -625,9 +606,7 @@ private:
             }
         }
         const MedicalSeg::VolumeNbhood cur = MedicalSeg::get_volume_nbhood();
-        std::cout << "Volume nbhood: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " levels " << cur.levels << " ";
-        if (cur.mode == MI_UNET_VTEX_WIDTH) std::cout << "width " << cur.width << " lo " << cur.lo;
-        else std::cout << "count";
+        print_texture_setting("nbhood", cur);
         std::cout << " alpha " << cur.alpha << " dist " << cur.max_dist << std::endl;
     }
 

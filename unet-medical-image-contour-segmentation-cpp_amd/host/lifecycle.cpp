@@ -379,22 +379,37 @@ bool set_volume_measure(const VolumeMeasure &measure)
         /*handle_side=*/false);
 }
 
+namespace {
+
+// The five fields a texture setting (VolumeTexture, VolumeZones, VolumeNbhood) begins with: what is wrong with the first of them that is
+// out of range, behind the stage's prefix ("volume texture", ...), or nothing; and their part of the log line.
+template <class T>
+std::string check_quantiser(const std::string &stage, const T &t)
+{
+    if (t.channel < 0) return stage + ": the channel is not negative";
+    if (t.mode != MI_UNET_VTEX_COUNT && t.mode != MI_UNET_VTEX_WIDTH) return stage + ": the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH";
+    if (t.levels < 2 || t.levels > MI_UNET_VTEX_MAX_LEVELS) return stage + ": levels is 2 .. MI_UNET_VTEX_MAX_LEVELS";
+    if (t.lo < 0 || t.lo > 65535) return stage + ": lo is 0 .. 65535";
+    if (t.width < 1 || t.width > 65536) return stage + ": width is 1 .. 65536";
+    return std::string();
+}
+template <class T>
+std::string quantiser_text(const T &t)
+{
+    return std::string(t.on ? "on" : "off") + ", channel " + std::to_string(t.channel) + ", levels " + std::to_string(t.levels) + ", " +
+           (t.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(t.width) + " lo " + std::to_string(t.lo) : std::string("count"));
+}
+
+}  // namespace
+
 bool set_volume_texture(const VolumeTexture &texture)
 {
     return change_setting(
         [&](Settings &s) {
             s.volume_texture = texture;
-            if (texture.channel < 0) return std::string("volume texture: the channel is not negative");
-            if (texture.mode != MI_UNET_VTEX_COUNT && texture.mode != MI_UNET_VTEX_WIDTH)
-                return std::string("volume texture: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
-            if (texture.levels < 2 || texture.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume texture: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
-            if (texture.lo < 0 || texture.lo > 65535) return std::string("volume texture: lo is 0 .. 65535");
-            return std::string(texture.width >= 1 && texture.width <= 65536 ? "" : "volume texture: width is 1 .. 65536");
+            return check_quantiser("volume texture", texture);
         },
-        [&](std::ostream &lg, const Settings &) {
-            lg << "Volume texture: " << (texture.on ? "on" : "off") << ", channel " << texture.channel << ", levels " << texture.levels << ", "
-               << (texture.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(texture.width) + " lo " + std::to_string(texture.lo) : std::string("count"));
-        },
+        [&](std::ostream &lg, const Settings &) { lg << "Volume texture: " << quantiser_text(texture); },
         /*handle_side=*/false);
 }
 
@@ -403,19 +418,11 @@ bool set_volume_zones(const VolumeZones &zones)
     return change_setting(
         [&](Settings &s) {
             s.volume_zones = zones;
-            if (zones.channel < 0) return std::string("volume zones: the channel is not negative");
-            if (zones.mode != MI_UNET_VTEX_COUNT && zones.mode != MI_UNET_VTEX_WIDTH)
-                return std::string("volume zones: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
-            if (zones.levels < 2 || zones.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume zones: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
-            if (zones.lo < 0 || zones.lo > 65535) return std::string("volume zones: lo is 0 .. 65535");
-            if (zones.width < 1 || zones.width > 65536) return std::string("volume zones: width is 1 .. 65536");
+            const std::string common = check_quantiser("volume zones", zones);
+            if (!common.empty()) return common;
             return std::string(zones.max_run >= 2 && zones.max_run <= MI_UNET_VZONES_MAX_RUN ? "" : "volume zones: max_run is 2 .. MI_UNET_VZONES_MAX_RUN");
         },
-        [&](std::ostream &lg, const Settings &) {
-            lg << "Volume zones: " << (zones.on ? "on" : "off") << ", channel " << zones.channel << ", levels " << zones.levels << ", "
-               << (zones.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(zones.width) + " lo " + std::to_string(zones.lo) : std::string("count"))
-               << ", run " << zones.max_run;
-        },
+        [&](std::ostream &lg, const Settings &) { lg << "Volume zones: " << quantiser_text(zones) << ", run " << zones.max_run; },
         /*handle_side=*/false);
 }
 
@@ -424,19 +431,13 @@ bool set_volume_nbhood(const VolumeNbhood &nbhood)
     return change_setting(
         [&](Settings &s) {
             s.volume_nbhood = nbhood;
-            if (nbhood.channel < 0) return std::string("volume nbhood: the channel is not negative");
-            if (nbhood.mode != MI_UNET_VTEX_COUNT && nbhood.mode != MI_UNET_VTEX_WIDTH)
-                return std::string("volume nbhood: the mode is MI_UNET_VTEX_COUNT or MI_UNET_VTEX_WIDTH");
-            if (nbhood.levels < 2 || nbhood.levels > MI_UNET_VTEX_MAX_LEVELS) return std::string("volume nbhood: levels is 2 .. MI_UNET_VTEX_MAX_LEVELS");
-            if (nbhood.lo < 0 || nbhood.lo > 65535) return std::string("volume nbhood: lo is 0 .. 65535");
-            if (nbhood.width < 1 || nbhood.width > 65536) return std::string("volume nbhood: width is 1 .. 65536");
+            const std::string common = check_quantiser("volume nbhood", nbhood);
+            if (!common.empty()) return common;
             if (nbhood.alpha < 0 || nbhood.alpha > nbhood.levels - 1) return std::string("volume nbhood: alpha is 0 .. levels - 1");
             return std::string(nbhood.max_dist >= 1 && nbhood.max_dist <= MI_UNET_VNBHOOD_MAX_DIST ? "" : "volume nbhood: max_dist is 1 .. MI_UNET_VNBHOOD_MAX_DIST");
         },
         [&](std::ostream &lg, const Settings &) {
-            lg << "Volume nbhood: " << (nbhood.on ? "on" : "off") << ", channel " << nbhood.channel << ", levels " << nbhood.levels << ", "
-               << (nbhood.mode == MI_UNET_VTEX_WIDTH ? "width " + std::to_string(nbhood.width) + " lo " + std::to_string(nbhood.lo) : std::string("count"))
-               << ", alpha " << nbhood.alpha << ", dist " << nbhood.max_dist;
+            lg << "Volume nbhood: " << quantiser_text(nbhood) << ", alpha " << nbhood.alpha << ", dist " << nbhood.max_dist;
         },
         /*handle_side=*/false);
 }

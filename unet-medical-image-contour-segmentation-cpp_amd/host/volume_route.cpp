@@ -6,6 +6,7 @@
 #include <cmath>
 #include <filesystem>
 #include <fstream>
+#include <functional>
 #include <sstream>
 
 #include "json_io.h"
@@ -231,21 +232,21 @@ std::vector<std::vector<std::string>> measure_volume(const VolumeStack &st, cons
     }
 }
 
-// set_volume_texture: per target one mi_unet_volume_texture call on `h` (mi_unet_volume_texture_host under MEDSEG_HOST_POSTPROCESS=1) over
-// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's texture channel, with m = min(found, cap, 2^22 / levels^2), then
-// mi_unet_volume_texture_derive of every row and of both its tables.  Returns, per target and table row, the "texture" member of the row's
-// component object in volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
-                                                     size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+using Members = std::vector<std::vector<std::string>>;            // per target and table row, one member of the row's component object
+
+// What the texture stages (texture_volume, zones_volume, nbhood_volume) share: per target, `call(t, m)` runs the stage `name` on the first
+// m = min(found, cap, 2^22 / cells) components, then `row(r, js)` writes the object of row r behind "\"<name>\": " and returns whether the
+// row has voxels.  A row beyond m, or one the volume filter dropped (no voxel carries its id), gets null.  `at` is what the log says the
+// count was cut at, `tail` what a stage adds to its log line.  A failure is reported and returns nothing: only this step ends.
+template <class Call, class Row>
+Members per_component(const std::string &name, int channel, size_t cells, const std::string &at, const VolumeStack &st, const std::vector<int32_t> &found,
+                      size_t cap, const Settings &s, std::ostream &lg, Call call, Row row, const std::function<void()> &tail = [] {})
 {
     try {
-        const VolumeTexture &texture = s.volume_texture;
-        const size_t K = s.targets.size(), D = st.D, hw = st.hw, L = (size_t)texture.levels;
-        if (texture.channel >= g_cfg.in_ch)
-            throw std::runtime_error("channel " + std::to_string(texture.channel) + " of " + std::to_string(g_cfg.in_ch));
-        const mi_unet_vtexture_opts opts{ texture.mode, texture.levels, texture.lo, texture.width };
-        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * L);
-        std::vector<std::vector<std::string>> members(K);
+        const size_t K = s.targets.size();
+        if (channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(channel) + " of " + std::to_string(g_cfg.in_ch));
+        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / cells;
+        Members members(K);
         size_t cut = 0;                                         // components beyond the measured count, over all targets
         const auto t0 = hr_clock::now();
         for (size_t t = 0; t < K; ++t) {
@@ -253,49 +254,87 @@ std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, cons
             const int m = (int)std::min(rows, most);
             if (m < 1) continue;
             cut += rows - (size_t)m;
-            std::vector<mi_unet_vtexture> table((size_t)m);
-            std::vector<uint32_t> hist((size_t)m * L), glcm((size_t)m * L * L), axial((size_t)m * L * L);
-            stage_call(h, mi_unet_volume_texture, mi_unet_volume_texture_host, ids.data() + t * D * hw, st.texture_intensity(), (int)D, g_cfg.height,
-                       g_cfg.width, m, &opts, table.data(), hist.data(), glcm.data(), axial.data());
+            call(t, m);
             for (size_t r = 0; r < rows; ++r) {
-                if (r >= (size_t)m || table[r].voxels < 1) {    // beyond the measured count, or dropped by the volume filter: no voxel carries its id
-                    members[t].push_back(", \"texture\": null");
-                    continue;
-                }
-                const mi_unet_vtexture &c = table[r];
-                mi_unet_vtexture_features f{}, fa{};
-                checked(mi_unet_volume_texture_derive, &c, hist.data() + r * L, glcm.data() + r * L * L, (int)L, &f);
-                checked(mi_unet_volume_texture_derive, &c, hist.data() + r * L, axial.data() + r * L * L, (int)L, &fa);
                 std::ostringstream js;
-                js << ", \"texture\": {\"levels\": " << L << ", \"mode\": \"" << (texture.mode == MI_UNET_VTEX_WIDTH ? "width" : "count")
-                   << "\", \"range\": [" << c.imin << ", " << c.imax << "], \"levels_used\": " << c.levels_used << ", \"histogram\": {\"mean\": "
-                   << json_number(f.mean) << ", \"variance\": " << json_number(f.variance) << ", \"skewness\": " << json_number(f.skewness) << ", \"kurtosis\": "
-                   << json_number(f.kurtosis) << ", \"median\": " << f.median << ", \"p10\": " << f.p10 << ", \"p90\": " << f.p90 << ", \"mode\": "
-                   << f.mode << ", \"entropy\": " << json_number(f.entropy) << ", \"uniformity\": " << json_number(f.uniformity) << ", \"counts\": [";
-                for (size_t l = 0; l < L; ++l) js << (l ? ", " : "") << hist[r * L + l];
-                js << "]}";
-                auto joint = [&](const char *key, int64_t pairs, const mi_unet_vtexture_features &g) {
-                    js << ", \"" << key << "\": {\"pairs\": " << pairs << ", \"joint_max\": " << json_number(g.joint_max) << ", \"joint_average\": "
-                       << json_number(g.joint_average) << ", \"joint_variance\": " << json_number(g.joint_variance) << ", \"joint_entropy\": "
-                       << json_number(g.joint_entropy) << ", \"contrast\": " << json_number(g.contrast) << ", \"dissimilarity\": " << json_number(g.dissimilarity)
-                       << ", \"inverse_difference\": " << json_number(g.inverse_difference) << ", \"inverse_difference_moment\": "
-                       << json_number(g.inverse_difference_moment) << ", \"angular_second_moment\": " << json_number(g.angular_second_moment)
-                       << ", \"correlation\": " << json_number(g.correlation) << "}";
-                };
-                joint("glcm", c.pairs, f);
-                joint("glcm_axial", c.pairs_axial, fa);
-                js << "}";
-                members[t].push_back(js.str());
+                js << ", \"" << name << "\": ";
+                members[t].push_back(r < (size_t)m && row(r, js) ? js.str() : ", \"" + name + "\": null");
             }
         }
-        lg << "Volume texture: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
-        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels; " << cut << " not measured)";
+        lg << "Volume " << name << ": " << st.D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
+        if (cut) lg << " (the first " << most << " components of a target at " << at << "; " << cut << " not measured)";
+        tail();
         lg << std::endl;
         return members;
     } catch (const std::exception &e) {
-        report(lg, std::string("Volume texture error: ") + e.what());
+        report(lg, "Volume " + name + " error: " + e.what());
         return {};
     }
+}
+
+// the head of a texture stage's object: the quantiser's levels and mode
+void quantiser_head(std::ostream &js, int levels, int mode)
+{
+    js << "{\"levels\": " << levels << ", \"mode\": \"" << (mode == MI_UNET_VTEX_WIDTH ? "width" : "count") << "\"";
+}
+
+// the 16 features of a level-by-size matrix, each from its leading comma on
+void matrix_features(std::ostream &js, const mi_unet_vzone_features &f)
+{
+    const double *const v = &f.short_emphasis;
+    static const char *const names[16] = { "short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low", "short_high",
+                                           "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm", "size_nonuniformity",
+                                           "size_nonuniformity_norm", "percentage", "grey_variance", "size_variance", "entropy" };
+    for (int k = 0; k < 16; ++k) js << ", \"" << names[k] << "\": " << json_number(v[k]);
+}
+
+// set_volume_texture: per target one mi_unet_volume_texture call on `h` (mi_unet_volume_texture_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's texture channel, with m = min(found, cap, 2^22 / levels^2), then
+// mi_unet_volume_texture_derive of every row and of both its tables.  Returns, per target and table row, the "texture" member of the row's
+// component object in volume_report.json, from its leading comma on.
+Members texture_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
+                       mi_unet_t *h, std::ostream &lg)
+{
+    const VolumeTexture &texture = s.volume_texture;
+    const size_t D = st.D, hw = st.hw, L = (size_t)texture.levels;
+    const mi_unet_vtexture_opts opts{ texture.mode, texture.levels, texture.lo, texture.width };
+    std::vector<mi_unet_vtexture> table;
+    std::vector<uint32_t> hist, glcm, axial;
+    auto call = [&](size_t t, int m) {
+        table.assign((size_t)m, mi_unet_vtexture{});
+        hist.assign((size_t)m * L, 0);
+        glcm.assign((size_t)m * L * L, 0);
+        axial.assign((size_t)m * L * L, 0);
+        stage_call(h, mi_unet_volume_texture, mi_unet_volume_texture_host, ids.data() + t * D * hw, st.texture_intensity(), (int)D, g_cfg.height,
+                   g_cfg.width, m, &opts, table.data(), hist.data(), glcm.data(), axial.data());
+    };
+    auto row = [&](size_t r, std::ostream &js) {
+        const mi_unet_vtexture &c = table[r];
+        if (c.voxels < 1) return false;
+        mi_unet_vtexture_features f{}, fa{};
+        checked(mi_unet_volume_texture_derive, &c, hist.data() + r * L, glcm.data() + r * L * L, (int)L, &f);
+        checked(mi_unet_volume_texture_derive, &c, hist.data() + r * L, axial.data() + r * L * L, (int)L, &fa);
+        quantiser_head(js, texture.levels, texture.mode);
+        js << ", \"range\": [" << c.imin << ", " << c.imax << "], \"levels_used\": " << c.levels_used << ", \"histogram\": {\"mean\": "
+           << json_number(f.mean) << ", \"variance\": " << json_number(f.variance) << ", \"skewness\": " << json_number(f.skewness) << ", \"kurtosis\": "
+           << json_number(f.kurtosis) << ", \"median\": " << f.median << ", \"p10\": " << f.p10 << ", \"p90\": " << f.p90 << ", \"mode\": "
+           << f.mode << ", \"entropy\": " << json_number(f.entropy) << ", \"uniformity\": " << json_number(f.uniformity) << ", \"counts\": [";
+        for (size_t l = 0; l < L; ++l) js << (l ? ", " : "") << hist[r * L + l];
+        js << "]}";
+        auto joint = [&](const char *key, int64_t pairs, const mi_unet_vtexture_features &g) {
+            js << ", \"" << key << "\": {\"pairs\": " << pairs << ", \"joint_max\": " << json_number(g.joint_max) << ", \"joint_average\": "
+               << json_number(g.joint_average) << ", \"joint_variance\": " << json_number(g.joint_variance) << ", \"joint_entropy\": "
+               << json_number(g.joint_entropy) << ", \"contrast\": " << json_number(g.contrast) << ", \"dissimilarity\": " << json_number(g.dissimilarity)
+               << ", \"inverse_difference\": " << json_number(g.inverse_difference) << ", \"inverse_difference_moment\": "
+               << json_number(g.inverse_difference_moment) << ", \"angular_second_moment\": " << json_number(g.angular_second_moment)
+               << ", \"correlation\": " << json_number(g.correlation) << "}";
+        };
+        joint("glcm", c.pairs, f);
+        joint("glcm_axial", c.pairs_axial, fa);
+        js << "}";
+        return true;
+    };
+    return per_component("texture", texture.channel, L * L, std::to_string(L) + " levels", st, found, cap, s, lg, call, row);
 }
 
 // set_volume_zones: per target one mi_unet_volume_zones call on `h` (mi_unet_volume_zones_host under MEDSEG_HOST_POSTPROCESS=1) over the
@@ -303,170 +342,128 @@ std::vector<std::vector<std::string>> texture_volume(const VolumeStack &st, cons
 // and a zone list of one record per voxel of the stack, at most 2^24; the list is sorted by component once (a stable sort: a
 // component's records keep their order), its slices go to mi_unet_volume_zones_zone_features and the rows of both tables to
 // mi_unet_volume_zones_run_features.  Returns, per target and table row, the "zones" member of the row's component object in
-// volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::vector<std::string>> zones_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
-                                                   size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+// volume_report.json, from its leading comma on.
+Members zones_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
+                     mi_unet_t *h, std::ostream &lg)
 {
-    try {
-        const VolumeZones &zs = s.volume_zones;
-        const size_t K = s.targets.size(), D = st.D, hw = st.hw, L = (size_t)zs.levels, R = (size_t)zs.max_run;
-        if (zs.channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(zs.channel) + " of " + std::to_string(g_cfg.in_ch));
-        const mi_unet_vzones_opts opts{ zs.mode, zs.levels, zs.lo, zs.width, zs.max_run };
-        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * R);
-        const int list_cap = (int)std::min<size_t>(D * hw, (size_t)MI_UNET_VZONES_MAX_CAP);
-        std::vector<std::vector<std::string>> members(K);
-        size_t cut = 0, lists_cut = 0;                          // components beyond the measured count, and targets whose list was cut
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const size_t rows = std::min<size_t>((size_t)found[t], cap);
-            const int m = (int)std::min(rows, most);
-            if (m < 1) continue;
-            cut += rows - (size_t)m;
-            std::vector<mi_unet_vzones> table((size_t)m);
-            std::vector<uint32_t> rlm((size_t)m * L * R), axial((size_t)m * L * R);
-            std::vector<mi_unet_vzone> list((size_t)list_cap);
-            int n_zones = 0;
-            stage_call(h, mi_unet_volume_zones, mi_unet_volume_zones_host, ids.data() + t * D * hw, st.zones_intensity(), (int)D, g_cfg.height,
-                       g_cfg.width, m, &opts, table.data(), rlm.data(), axial.data(), list.data(), list_cap, &n_zones);
-            const bool whole = n_zones <= list_cap;
-            lists_cut += !whole;
-            list.resize((size_t)std::min(n_zones, list_cap));
-            std::stable_sort(list.begin(), list.end(), [](const mi_unet_vzone &a, const mi_unet_vzone &b) { return a.component < b.component; });
-            std::vector<size_t> first((size_t)m + 1, 0);        // component r's records are list[first[r] .. first[r + 1])
-            for (const mi_unet_vzone &z : list) ++first[(size_t)z.component + 1];
-            for (int r = 0; r < m; ++r) first[(size_t)r + 1] += first[(size_t)r];
-            for (size_t r = 0; r < rows; ++r) {
-                if (r >= (size_t)m || table[r].voxels < 1) {    // beyond the measured count, or dropped by the volume filter: no voxel carries its id
-                    members[t].push_back(", \"zones\": null");
-                    continue;
-                }
-                const mi_unet_vzones &c = table[r];
-                std::ostringstream js;
-                auto features = [&](const mi_unet_vzone_features &f) {
-                    const double *const v = &f.short_emphasis;
-                    static const char *const names[16] = { "short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low",
-                                                           "short_high", "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm",
-                                                           "size_nonuniformity", "size_nonuniformity_norm", "percentage", "grey_variance",
-                                                           "size_variance", "entropy" };
-                    for (int k = 0; k < 16; ++k) js << ", \"" << names[k] << "\": " << json_number(v[k]);
-                };
-                auto runs = [&](const char *key, const uint32_t *row, int directions, int64_t n, int64_t clamped) {
-                    mi_unet_vzone_features f{};
-                    checked(mi_unet_volume_zones_run_features, &c, row, (int)L, (int)R, directions, &f);
-                    js << ", \"" << key << "\": {\"runs\": " << n << ", \"clamped\": " << clamped << ", \"longest\": " << c.longest_run;
-                    features(f);
-                    js << "}";
-                };
-                js << ", \"zones\": {\"levels\": " << L << ", \"mode\": \"" << (zs.mode == MI_UNET_VTEX_WIDTH ? "width" : "count") << "\", \"max_run\": " << R;
-                runs("glrlm", rlm.data() + r * L * R, 13, c.runs, c.clamped);
-                runs("glrlm_axial", axial.data() + r * L * R, 4, c.runs_axial, c.clamped_axial);
-                if (whole) {
-                    mi_unet_vzone_features f{};
-                    checked(mi_unet_volume_zones_zone_features, &c, list.data() + first[r], (int)(first[r + 1] - first[r]), (int)r, (int)L, &f);
-                    js << ", \"glszm\": {\"zones\": " << c.zones << ", \"largest\": " << c.largest_zone;
-                    features(f);
-                    js << "}}";
-                } else {
-                    js << ", \"glszm\": null}";
-                }
-                members[t].push_back(js.str());
-            }
+    const VolumeZones &zs = s.volume_zones;
+    const size_t D = st.D, hw = st.hw, L = (size_t)zs.levels, R = (size_t)zs.max_run;
+    const mi_unet_vzones_opts opts{ zs.mode, zs.levels, zs.lo, zs.width, zs.max_run };
+    const int list_cap = (int)std::min<size_t>(D * hw, (size_t)MI_UNET_VZONES_MAX_CAP);
+    size_t lists_cut = 0;                                       // targets whose list was cut
+    std::vector<mi_unet_vzones> table;
+    std::vector<uint32_t> rlm, axial;
+    std::vector<mi_unet_vzone> list;
+    std::vector<size_t> first;                                  // component r's records are list[first[r] .. first[r + 1])
+    bool whole = true;
+    auto call = [&](size_t t, int m) {
+        table.assign((size_t)m, mi_unet_vzones{});
+        rlm.assign((size_t)m * L * R, 0);
+        axial.assign((size_t)m * L * R, 0);
+        list.assign((size_t)list_cap, mi_unet_vzone{});
+        int n_zones = 0;
+        stage_call(h, mi_unet_volume_zones, mi_unet_volume_zones_host, ids.data() + t * D * hw, st.zones_intensity(), (int)D, g_cfg.height,
+                   g_cfg.width, m, &opts, table.data(), rlm.data(), axial.data(), list.data(), list_cap, &n_zones);
+        whole = n_zones <= list_cap;
+        lists_cut += !whole;
+        list.resize((size_t)std::min(n_zones, list_cap));
+        std::stable_sort(list.begin(), list.end(), [](const mi_unet_vzone &a, const mi_unet_vzone &b) { return a.component < b.component; });
+        first.assign((size_t)m + 1, 0);
+        for (const mi_unet_vzone &z : list) ++first[(size_t)z.component + 1];
+        for (int r = 0; r < m; ++r) first[(size_t)r + 1] += first[(size_t)r];
+    };
+    auto row = [&](size_t r, std::ostream &js) {
+        const mi_unet_vzones &c = table[r];
+        if (c.voxels < 1) return false;
+        auto runs = [&](const char *key, const uint32_t *cells, int directions, int64_t n, int64_t clamped) {
+            mi_unet_vzone_features f{};
+            checked(mi_unet_volume_zones_run_features, &c, cells, (int)L, (int)R, directions, &f);
+            js << ", \"" << key << "\": {\"runs\": " << n << ", \"clamped\": " << clamped << ", \"longest\": " << c.longest_run;
+            matrix_features(js, f);
+            js << "}";
+        };
+        quantiser_head(js, zs.levels, zs.mode);
+        js << ", \"max_run\": " << R;
+        runs("glrlm", rlm.data() + r * L * R, 13, c.runs, c.clamped);
+        runs("glrlm_axial", axial.data() + r * L * R, 4, c.runs_axial, c.clamped_axial);
+        if (whole) {
+            mi_unet_vzone_features f{};
+            checked(mi_unet_volume_zones_zone_features, &c, list.data() + first[r], (int)(first[r + 1] - first[r]), (int)r, (int)L, &f);
+            js << ", \"glszm\": {\"zones\": " << c.zones << ", \"largest\": " << c.largest_zone;
+            matrix_features(js, f);
+            js << "}}";
+        } else {
+            js << ", \"glszm\": null}";
         }
-        lg << "Volume zones: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
-        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels and run " << R << "; " << cut << " not measured)";
+        return true;
+    };
+    return per_component("zones", zs.channel, L * R, std::to_string(L) + " levels and run " + std::to_string(R), st, found, cap, s, lg, call, row, [&] {
         if (lists_cut) lg << " (the zone list of " << lists_cut << " targets was cut at " << list_cap << " records: no glszm there)";
-        lg << std::endl;
-        return members;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume zones error: ") + e.what());
-        return {};
-    }
+    });
 }
 
 // set_volume_nbhood: per target one mi_unet_volume_nbhood call on `h` (mi_unet_volume_nbhood_host under MEDSEG_HOST_POSTPROCESS=1) over
 // the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's neighbourhood channel, all eight tables, with m = min(found,
 // cap, 2^22 / (levels * max(levels, 32, max_dist))); the rows of every component go to mi_unet_volume_nbhood_derive twice, for the 26
 // neighbours and for the 8 in the slice.  Returns, per target and table row, the "nbhood" member of the row's component object in
-// volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
-std::vector<std::vector<std::string>> nbhood_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found,
-                                                    size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+// volume_report.json, from its leading comma on.
+Members nbhood_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
+                      mi_unet_t *h, std::ostream &lg)
 {
-    try {
-        const VolumeNbhood &ns = s.volume_nbhood;
-        const size_t K = s.targets.size(), D = st.D, hw = st.hw, L = (size_t)ns.levels, Dm = (size_t)ns.max_dist;
-        if (ns.channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(ns.channel) + " of " + std::to_string(g_cfg.in_ch));
-        const mi_unet_vnbhood_opts opts{ ns.mode, ns.levels, ns.lo, ns.width, ns.alpha, ns.max_dist };
-        const size_t most = (size_t)MI_UNET_VTEX_MAX_CELLS / (L * std::max<size_t>({ L, 32, Dm }));
-        std::vector<std::vector<std::string>> members(K);
-        size_t cut = 0;                                         // components beyond the measured count
-        const auto t0 = hr_clock::now();
-        for (size_t t = 0; t < K; ++t) {
-            const size_t rows = std::min<size_t>((size_t)found[t], cap);
-            const int m = (int)std::min(rows, most);
-            if (m < 1) continue;
-            cut += rows - (size_t)m;
-            const size_t M = (size_t)m;
-            std::vector<mi_unet_vnbhood> table(M);
-            std::vector<uint32_t> count(M * L * 27), dep(M * L * 27), count_a(M * L * 9), dep_a(M * L * 9), dzm(M * L * Dm), dzm_a(M * L * Dm);
-            std::vector<uint64_t> diff(M * L * 27), diff_a(M * L * 9);
-            const mi_unet_vnbhood_out out{ count.data(), diff.data(), dep.data(), count_a.data(), diff_a.data(), dep_a.data(), dzm.data(), dzm_a.data() };
-            stage_call(h, mi_unet_volume_nbhood, mi_unet_volume_nbhood_host, ids.data() + t * D * hw, st.nbhood_intensity(), (int)D, g_cfg.height,
-                       g_cfg.width, m, &opts, table.data(), &out);
-            for (size_t r = 0; r < rows; ++r) {
-                if (r >= M || table[r].voxels < 1) {            // beyond the measured count, or dropped by the volume filter: no voxel carries its id
-                    members[t].push_back(", \"nbhood\": null");
-                    continue;
-                }
-                const mi_unet_vnbhood &c = table[r];
-                const mi_unet_vnbhood_out row{ count.data() + r * L * 27, diff.data() + r * L * 27, dep.data() + r * L * 27, count_a.data() + r * L * 9,
-                                               diff_a.data() + r * L * 9,  dep_a.data() + r * L * 9,  dzm.data() + r * L * Dm,  dzm_a.data() + r * L * Dm };
-                mi_unet_vnbhood_features full{}, axial{};
-                checked(mi_unet_volume_nbhood_derive, &c, &row, (int)L, (int)Dm, 0, &full);
-                checked(mi_unet_volume_nbhood_derive, &c, &row, (int)L, (int)Dm, 1, &axial);
-                std::ostringstream js;
-                auto features = [&](const mi_unet_vzone_features &f) {
-                    const double *const v = &f.short_emphasis;
-                    static const char *const names[16] = { "short_emphasis", "long_emphasis", "low_grey_emphasis", "high_grey_emphasis", "short_low",
-                                                           "short_high", "long_low", "long_high", "grey_nonuniformity", "grey_nonuniformity_norm",
-                                                           "size_nonuniformity", "size_nonuniformity_norm", "percentage", "grey_variance",
-                                                           "size_variance", "entropy" };
-                    for (int k = 0; k < 16; ++k) js << ", \"" << names[k] << "\": " << json_number(v[k]);
-                };
-                auto ngtdm = [&](const char *key, const mi_unet_vnbhood_features &f, int valid) {
-                    js << ", \"" << key << "\": {\"valid\": " << valid << ", \"coarseness\": " << json_number(f.coarseness)
-                       << ", \"contrast\": " << json_number(f.contrast) << ", \"busyness\": " << json_number(f.busyness)
-                       << ", \"complexity\": " << json_number(f.complexity) << ", \"strength\": " << json_number(f.strength) << "}";
-                };
-                auto ngldm = [&](const char *key, const mi_unet_vnbhood_features &f) {
-                    js << ", \"" << key << "\": {\"dependence_max\": " << c.dependence_max;
-                    features(f.ngldm);
-                    js << ", \"dependence_energy\": " << json_number(f.dependence_energy) << "}";
-                };
-                auto gldzm = [&](const char *key, const mi_unet_vnbhood_features &f, int clamped) {
-                    js << ", \"" << key << "\": {\"zones\": " << c.zones << ", \"clamped\": " << clamped;
-                    features(f.gldzm);
-                    js << "}";
-                };
-                js << ", \"nbhood\": {\"levels\": " << L << ", \"mode\": \"" << (ns.mode == MI_UNET_VTEX_WIDTH ? "width" : "count")
-                   << "\", \"alpha\": " << ns.alpha << ", \"max_dist\": " << Dm;
-                ngtdm("ngtdm", full, c.valid);
-                ngtdm("ngtdm_axial", axial, c.valid_axial);
-                ngldm("ngldm", full);
-                ngldm("ngldm_axial", axial);
-                gldzm("gldzm", full, c.clamped);
-                gldzm("gldzm_axial", axial, c.clamped_axial);
-                js << ", \"deepest\": " << c.deepest << ", \"deepest_axial\": " << c.deepest_axial << "}";
-                members[t].push_back(js.str());
-            }
-        }
-        lg << "Volume nbhood: " << D << " slices, " << K << " targets, " << ms_since(t0) << " ms";
-        if (cut) lg << " (the first " << most << " components of a target at " << L << " levels and dist " << Dm << "; " << cut << " not measured)";
-        lg << std::endl;
-        return members;
-    } catch (const std::exception &e) {
-        report(lg, std::string("Volume nbhood error: ") + e.what());
-        return {};
-    }
+    const VolumeNbhood &ns = s.volume_nbhood;
+    const size_t D = st.D, hw = st.hw, L = (size_t)ns.levels, Dm = (size_t)ns.max_dist;
+    const mi_unet_vnbhood_opts opts{ ns.mode, ns.levels, ns.lo, ns.width, ns.alpha, ns.max_dist };
+    std::vector<mi_unet_vnbhood> table;
+    std::vector<uint32_t> count, dep, count_a, dep_a, dzm, dzm_a;
+    std::vector<uint64_t> diff, diff_a;
+    auto call = [&](size_t t, int m) {
+        const size_t M = (size_t)m;
+        table.assign(M, mi_unet_vnbhood{});
+        for (std::vector<uint32_t> *v : { &count, &dep }) v->assign(M * L * 27, 0);
+        for (std::vector<uint32_t> *v : { &count_a, &dep_a }) v->assign(M * L * 9, 0);
+        for (std::vector<uint32_t> *v : { &dzm, &dzm_a }) v->assign(M * L * Dm, 0);
+        diff.assign(M * L * 27, 0);
+        diff_a.assign(M * L * 9, 0);
+        const mi_unet_vnbhood_out out{ count.data(), diff.data(), dep.data(), count_a.data(), diff_a.data(), dep_a.data(), dzm.data(), dzm_a.data() };
+        stage_call(h, mi_unet_volume_nbhood, mi_unet_volume_nbhood_host, ids.data() + t * D * hw, st.nbhood_intensity(), (int)D, g_cfg.height,
+                   g_cfg.width, m, &opts, table.data(), &out);
+    };
+    auto row = [&](size_t r, std::ostream &js) {
+        const mi_unet_vnbhood &c = table[r];
+        if (c.voxels < 1) return false;
+        const mi_unet_vnbhood_out rows{ count.data() + r * L * 27, diff.data() + r * L * 27, dep.data() + r * L * 27, count_a.data() + r * L * 9,
+                                        diff_a.data() + r * L * 9,  dep_a.data() + r * L * 9,  dzm.data() + r * L * Dm,  dzm_a.data() + r * L * Dm };
+        mi_unet_vnbhood_features full{}, axial{};
+        checked(mi_unet_volume_nbhood_derive, &c, &rows, (int)L, (int)Dm, 0, &full);
+        checked(mi_unet_volume_nbhood_derive, &c, &rows, (int)L, (int)Dm, 1, &axial);
+        auto ngtdm = [&](const char *key, const mi_unet_vnbhood_features &f, int valid) {
+            js << ", \"" << key << "\": {\"valid\": " << valid << ", \"coarseness\": " << json_number(f.coarseness)
+               << ", \"contrast\": " << json_number(f.contrast) << ", \"busyness\": " << json_number(f.busyness)
+               << ", \"complexity\": " << json_number(f.complexity) << ", \"strength\": " << json_number(f.strength) << "}";
+        };
+        auto ngldm = [&](const char *key, const mi_unet_vnbhood_features &f) {
+            js << ", \"" << key << "\": {\"dependence_max\": " << c.dependence_max;
+            matrix_features(js, f.ngldm);
+            js << ", \"dependence_energy\": " << json_number(f.dependence_energy) << "}";
+        };
+        auto gldzm = [&](const char *key, const mi_unet_vnbhood_features &f, int clamped) {
+            js << ", \"" << key << "\": {\"zones\": " << c.zones << ", \"clamped\": " << clamped;
+            matrix_features(js, f.gldzm);
+            js << "}";
+        };
+        quantiser_head(js, ns.levels, ns.mode);
+        js << ", \"alpha\": " << ns.alpha << ", \"max_dist\": " << Dm;
+        ngtdm("ngtdm", full, c.valid);
+        ngtdm("ngtdm_axial", axial, c.valid_axial);
+        ngldm("ngldm", full);
+        ngldm("ngldm_axial", axial);
+        gldzm("gldzm", full, c.clamped);
+        gldzm("gldzm_axial", axial, c.clamped_axial);
+        js << ", \"deepest\": " << c.deepest << ", \"deepest_axial\": " << c.deepest_axial << "}";
+        return true;
+    };
+    return per_component("nbhood", ns.channel, L * std::max<size_t>({ L, 32, Dm }), std::to_string(L) + " levels and dist " + std::to_string(Dm), st, found,
+                         cap, s, lg, call, row);
 }
 
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under

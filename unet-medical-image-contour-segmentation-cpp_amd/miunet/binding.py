@@ -365,17 +365,29 @@ VMEASURE_MAX_ENDS_LIMIT = 1 << 20
 VMEASURE_DEFAULT_MAX_ENDS = 262144
 
 
-def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
-    """mi_unet_volume_measure (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
-    the same shape or None, m components, units = the spacing (ux, uy, uz) as integers, max_ends = None (the library's default) or the
-    cap -> table VMEASURE_DTYPE [m].  The library checks the values."""
+def _ids_intensity(ids, intensity, optional=False):
+    """ids as one contiguous int32 [D,H,W] array ([H,W] is one slice) and intensity as u16 of its shape (None stays None where optional)"""
     ids = np.ascontiguousarray(ids, np.int32)
     if ids.ndim == 2:
         ids = ids[None]
     if ids.ndim != 3:
         raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
-    if intensity is not None:
+    if intensity is not None or not optional:
         intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    return ids, intensity
+
+
+def _table_rows(m, cells):
+    """the rows to allocate for m components of `cells` cells each: one for a call that the library refuses (no need for the memory)"""
+    rows = max(int(m), 1)
+    return 1 if rows * cells > 2 * VTEX_MAX_CELLS else rows
+
+
+def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
+    """mi_unet_volume_measure (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape or None, m components, units = the spacing (ux, uy, uz) as integers, max_ends = None (the library's default) or the
+    cap -> table VMEASURE_DTYPE [m].  The library checks the values."""
+    ids, intensity = _ids_intensity(ids, intensity, optional=True)
     d, hh, ww = ids.shape
     un = np.ascontiguousarray(units, np.int32).reshape(-1)
     if un.size != 3:
@@ -414,16 +426,10 @@ def _volume_texture_call(fn, head, ids, intensity, m, levels, mode, lo, width, w
     the same shape, m components, levels / mode ("count", "width" or the number) / lo / width = the options, want = which of "glcm" and
     "axial" to compute -> (table VTEXTURE_DTYPE [m], hist u32 [m, L], glcm u32 [m, L, L] or None, glcm_axial or None).  The library
     checks the values."""
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim == 2:
-        ids = ids[None]
-    if ids.ndim != 3:
-        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
-    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    ids, intensity = _ids_intensity(ids, intensity)
     d, hh, ww = ids.shape
-    rows, lv = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS)
-    if rows * lv * lv > 2 * VTEX_MAX_CELLS:
-        rows = 1                                                 # (refused by the library; no need for the memory)
+    lv = min(max(int(levels), 1), VTEX_MAX_LEVELS)
+    rows = _table_rows(m, lv * lv)
     table = np.zeros(rows, VTEXTURE_DTYPE)
     hist = np.zeros((rows, lv), np.uint32)
     glcm = np.zeros((rows, lv, lv), np.uint32) if "glcm" in want else None
@@ -467,16 +473,10 @@ def _volume_zones_call(fn, head, ids, intensity, m, levels, mode, lo, width, max
     want_axial = which tables to compute, cap = the length of the zone list (None: a record per voxel, at most 2^24; 0: no zone half)
     -> (table VZONES_DTYPE [m], rlm u32 [m, L, R] or None, rlm_axial or None, zones VZONE_DTYPE [cap] or None, found or None).  The
     library checks the values."""
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim == 2:
-        ids = ids[None]
-    if ids.ndim != 3:
-        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
-    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
+    ids, intensity = _ids_intensity(ids, intensity)
     d, hh, ww = ids.shape
-    rows, lv, rn = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_run), 1), VZONES_MAX_RUN)
-    if rows * lv * rn > 2 * VTEX_MAX_CELLS:
-        rows = 1                                                 # (refused by the library; no need for the memory)
+    lv, rn = min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_run), 1), VZONES_MAX_RUN)
+    rows = _table_rows(m, lv * rn)
     table = np.zeros(rows, VZONES_DTYPE)
     rlm = np.zeros((rows, lv, rn), np.uint32) if want_runs else None
     axial = np.zeros((rows, lv, rn), np.uint32) if want_axial else None
@@ -531,19 +531,13 @@ def _volume_nbhood_call(fn, head, ids, intensity, m, levels, mode, lo, width, al
     the same shape, m components, levels / mode ("count", "width" or the number) / lo / width / alpha / max_dist = the options, want =
     which of VNBHOOD_WANT to compute ("ngt" and "ngt_axial" are a count and a diff table each) -> (table VNBHOOD_DTYPE [m], dict over
     VNBHOOD_TABLES: u32 / u64 [m, L, 27 | 9 | max_dist], or None for a table that was not asked for).  The library checks the values."""
-    ids = np.ascontiguousarray(ids, np.int32)
-    if ids.ndim == 2:
-        ids = ids[None]
-    if ids.ndim != 3:
-        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    ids, intensity = _ids_intensity(ids, intensity)
     unknown = set(want) - set(VNBHOOD_WANT)
     if unknown:
         raise ValueError(f"want {sorted(unknown)} is not among {VNBHOOD_WANT}")
-    intensity = np.ascontiguousarray(intensity, np.uint16).reshape(ids.shape)
     d, hh, ww = ids.shape
-    rows, lv, dm = max(int(m), 1), min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_dist), 1), VNBHOOD_MAX_DIST)
-    if rows * lv * max(lv, 32, dm) > 2 * VTEX_MAX_CELLS:
-        rows = 1                                                 # (refused by the library; no need for the memory)
+    lv, dm = min(max(int(levels), 1), VTEX_MAX_LEVELS), min(max(int(max_dist), 1), VNBHOOD_MAX_DIST)
+    rows = _table_rows(m, lv * max(lv, 32, dm))
     table = np.zeros(rows, VNBHOOD_DTYPE)
     asked = {"ngt_count": "ngt", "ngt_diff": "ngt", "dep": "dep", "ngt_count_axial": "ngt_axial", "ngt_diff_axial": "ngt_axial",
              "dep_axial": "dep_axial", "dzm": "dzm", "dzm_axial": "dzm_axial"}
