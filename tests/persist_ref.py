@@ -2,7 +2,7 @@
 tests/test_gpu_persistent_walk.py (checked on the CPU by tests/test_persist_cpu.py).
 
 Six kernels launch grid = min(nwg, cus) workgroups and walk nwg logical tiles with one partition (conv_wino4.hip PERSIST, conv_lpr.hip,
-conv_lprk.hip, convt_lpr.hip in C++; csrc/asm/gen_wino4_asm.py restates it in scalar assembly for conv3x3_wino4a / conv3x3_wino4b):
+conv_lprk.hip, convt_lpr.hip in C++; csrc/asm/wino4_asm_lib.py restates it in scalar assembly for conv3x3_wino4a / conv3x3_wino4b):
 
   XCD x = bid & 7 owns the logical tiles [x q + min(x, r), ... + q + (x < r)), q = nwg >> 3, r = nwg & 7;
   the workgroup in slot bid >> 3 takes every slots-th tile of that range, slots = (grid >> 3) + (x < (grid & 7)).

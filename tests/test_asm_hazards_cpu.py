@@ -105,6 +105,7 @@ def test_mfma_scanner_sees_both_hazards(tmp_path):
 
 # ------------------------------------------------------------------------------------------ the generated assembly kernel
 GEN = os.path.join(CSRC, "asm", "gen_wino4_asm.py")
+GEN_B = os.path.join(CSRC, "asm", "gen_wino4b_asm.py")
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
@@ -149,7 +150,7 @@ def test_generated_assembly_kernel_assembles_and_has_its_wait_states(tmp_path):
     assert obj.stat().st_size > 40000
     # the sibling kernel for the 64-channel layers (gen_wino4b_asm.py): the whole 160 KB of LDS, same checks
     asm_b = tmp_path / "wino4b.s"
-    subprocess.run([sys.executable, os.path.join(CSRC, "asm", "gen_wino4b_asm.py"), str(asm_b)], check=True, capture_output=True, timeout=300)
+    subprocess.run([sys.executable, GEN_B, str(asm_b)], check=True, capture_output=True, timeout=300)
     tb = asm_b.read_text()
     assert tb.count("v_mfma_f32_16x16x4_f32") == 4 * 288 and ".amdhsa_group_segment_fixed_size 163840" in tb          # one stream for the four waves
     assert ".fill 256, 4, 3212836864" in tb[tb.rindex("s_endpgm"):]
@@ -157,8 +158,12 @@ def test_generated_assembly_kernel_assembles_and_has_its_wait_states(tmp_path):
     subprocess.run([os.path.join(LLVM_BIN, "clang"), "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", str(asm_b), "-o", str(obj)],
                    check=True, capture_output=True, timeout=300)
     # every timing-only / dump / stamp variant of the generator still assembles (they are bring-up tools, never shipped)
-    for flags in (["--stamps"], ["--stop", "5", "--dump", "lds"], ["--timing-only", "nouload,novread,notransform,nodma"], ["--dma-pos", "0,4,8,12,16,20"]):
+    variants = [(GEN, flags) for flags in (["--stamps"], ["--stop", "5", "--dump", "lds"], ["--timing-only", "nouload,novread,notransform,nodma"],
+                                           ["--dma-pos", "0,4,8,12,16,20"])]
+    variants += [(GEN_B, flags) for flags in (["--ud", "6"], ["--ud", "9"], ["--store-policy", "nt"], ["--dma-pos", "0,1,2,3,4,5,6,7,8,9,10"],
+                                              ["--stop", "5", "--dump", "lds"])]
+    for gen, flags in variants:
         v = tmp_path / "variant.s"
-        subprocess.run([sys.executable, GEN, str(v)] + flags, check=True, capture_output=True, timeout=300)
+        subprocess.run([sys.executable, gen, str(v)] + flags, check=True, capture_output=True, timeout=300)
         subprocess.run([os.path.join(LLVM_BIN, "clang"), "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", str(v), "-o", str(obj)],
                        check=True, capture_output=True, timeout=300)

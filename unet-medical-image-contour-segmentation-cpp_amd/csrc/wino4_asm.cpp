@@ -1,5 +1,5 @@
 // wino4_asm.cpp -- host side of conv3x3_wino4a_f32 and conv3x3_wino4b_f32, the hand-scheduled persistent forms of the Winograd
-// F(4x4,3x3) kernels.  Both are generated assembly (csrc/asm/gen_wino4_asm.py, gen_wino4b_asm.py -> build/wino4?_gfx950.s -> code
+// F(4x4,3x3) kernels.  Both are generated assembly (csrc/asm/gen_wino4_asm.py, gen_wino4b_asm.py on wino4_asm_lib.py -> build/wino4?_gfx950.s -> code
 // object), embedded in this library as byte blobs (build/wino4?_blob.o).  An AsmKernels (kernels.h) loads the two code objects for one
 // device when an engine is created and unloads them with the last handle that holds it: nothing here is process-wide.  Same weights
 // (a.wpk4) and the same tensors as conv3x3_wino4_f32<2> and conv3x3_wino4s_f32 (csrc/conv_wino4.hip, conv_wino4s.hip), which serve
@@ -24,7 +24,7 @@ namespace miunet {
 
 namespace {
 
-// the kernels' argument block (csrc/asm/gen_wino4_asm.py: s[8:39] after two s_load_dwordx16)
+// the kernels' argument block (csrc/asm/wino4_asm_lib.py: s[8:39] after two s_load_dwordx16)
 struct Wino4aArgs {
     const float *in, *u, *bias;
     float *out, *pool;
