@@ -74,6 +74,22 @@ def test_stage_alone_every_field_of_every_region(h, w):
     assert all(counts[by[f"noise{s}"]] > 4 for s in range(3))
 
 
+def test_stage_alone_on_a_plane_that_ends_inside_a_wave_segment():
+    """One 16 x 70 plane, 1120 pixels (an engine of one level takes even sides): six single pixels and a pair in row 2 behind a moat,
+    one component over the rest.  The 64-pixel segment 128 .. 191 holds eight components; the large one runs across every 64-pixel
+    boundary and across pixel 1024, where the second wave's span begins; that span ends in the middle of a segment"""
+    m = np.full((16, 70), 255, np.uint8)
+    m[1:4, 0:25] = 0
+    m[2, [2, 5, 8, 11, 14, 17, 20, 21]] = 200
+    tile = np.random.default_rng(1670).integers(0, 256, m.shape, dtype=np.uint8)
+    with binding.Engine(16, 70, 1, 16, 1, 3, max_batch=1) as eng:
+        regions, counts = eng.measure_regions(m[None], tile[None], 0, cap_contours=16)
+        bare, bare_counts = eng.measure_regions(m[None], None, 0, cap_contours=16)
+    ref.assert_plane(regions[0], counts[0], ref.regions_of(m, tile), "crowded 16x70")
+    ref.assert_plane(bare[0], bare_counts[0], ref.regions_of(m, None), "crowded 16x70 without a tile")
+    assert counts[0] == 8 and sorted(regions[0, :8]["area"].tolist()) == [1] * 6 + [2, 16 * 70 - 75]
+
+
 def test_contour_overflow_zeroes_only_its_plane():
     names, batch, tiles, regions, counts = stage_run(64, 64)
     pick = [names.index("ring"), names.index("noise0"), names.index("full")]

@@ -163,6 +163,8 @@ def cases():
     for cap in (4607, 4608, 0):
         out[f"sheet_cap{cap}"] = (sh, intensity_for(sh.shape, 5), 1, (1, 1, 1), cap)
     out["box"] = (np.ones((4, 6, 9), np.int32), intensity_for((4, 6, 9), 6), 1, (1, 1, 1), None)
+    crowded, m = vr.crowded_ids()                               # more ids in a segment than a wave reduces; a span that ends mid-segment
+    out["crowded_segment"] = (crowded, intensity_for(crowded.shape, 7), m, (1, 1, 1), None)
     n16 = out[f"noise{vr.NOISE_SHAPES[2]}c6"]
     out["m4096"] = (n16[0], n16[1], 4096, (1, 1, 1), 300)       # ids past `found` are carried by no voxel; a cap that skips the large ones
     out["no_intensity"] = (out[f"noise{vr.NOISE_SHAPES[0]}c26"][0], None, 40, (1, 2, 3), None)

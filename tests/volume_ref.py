@@ -220,6 +220,25 @@ def serpentine(d=9, h=33, w=130):
     return vol
 
 
+def crowded_stack():
+    """u8 [3, 5, 70] of 1050 voxels: six single voxels and a pair of value 1 in row 2 of slice 0, a moat of 0 round them, and one
+    component over everything else.  What a wave of the device forms meets in it, all in one input: the 64-voxel segment 128 .. 191
+    holds eight components, more than a wave reduces together, so lanes are left to add their own; the large component runs across every
+    64-voxel boundary and across voxel 1024, where the second wave's span begins; that span ends after 26 voxels, in the middle of a
+    segment; and W = 70 makes the segments straddle rows"""
+    v = np.ones((3, 5, 70), np.uint8)
+    v[0:2, 1:4, 0:25] = 0
+    v[0, 2, [2, 5, 8, 11, 14, 17, 20, 21]] = 1
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def crowded_ids():
+    """(ids int32 [3, 5, 70] of crowded_stack under 7.9's numbering, m = 8)"""
+    _, _, found, _, ids = components(crowded_stack(), (1,), 26)
+    return np.ascontiguousarray(ids[0]), int(found[0])
+
+
 def edge_cases():
     """name -> (masks u8 [D,H,W], values, expectations dict checked by test_volume_cpu.test_edge_cases_are_what_they_claim)"""
     cases = {}
@@ -243,6 +262,7 @@ def edge_cases():
     v[1:6, 1:8, 1:10] = 1
     v[3, 3:6, 4:7] = 0                                          # a closed cavity of 1 x 3 x 3
     cases["cavity"] = (v, (1,), {6: 1, 18: 1, 26: 1})
+    cases["crowded_segment"] = (crowded_stack(), (1,), {6: 8, 18: 8, 26: 8})
     return cases
 
 

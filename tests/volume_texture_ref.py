@@ -186,6 +186,8 @@ def cases():
     out["checkerboard"] = ((1 + (x + y + z) % 2).astype(np.int32), noisy((6, 20, 96), 24), 2, dict(levels=8))
     sc = scattered()
     out["scattered"] = (sc, noisy(sc.shape, 25), 6, dict(levels=32))
+    crowded, m = vr.crowded_ids()                               # more ids in a segment than a wave reduces; a span that ends mid-segment
+    out["crowded_segment"] = (crowded, smooth(crowded.shape, 41), m, dict(levels=8))
     _, _, found, _, ids16 = vr.noise_ref((16, 24, 130), 6)
     out["m4096_L32"] = (np.ascontiguousarray(ids16[2]), noisy((16, 24, 130), 26), 4096, dict(levels=32))
     out["m1024_L64"] = (np.ascontiguousarray(ids16[2]), smooth((16, 24, 130), 27), 1024, dict(levels=64, mode=WIDTH, lo=2000, width=100))

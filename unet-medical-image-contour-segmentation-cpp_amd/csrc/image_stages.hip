@@ -2,6 +2,7 @@
 // (f2), mask_to_image + extract_contours (f3).  Integer / byte / fp64 work, bit-exact against the oracle.  gfx950 only.
 #include "cc_common.h"
 #include "kernel_common.h"
+#include "wave.h"
 
 namespace miunet {
 
@@ -32,11 +33,8 @@ __global__ __launch_bounds__(256) void minmax_u16_kernel(const uint16_t *__restr
         const unsigned a = raw[n8 * 8 + threadIdx.x];
         lo = min(lo, a); hi = max(hi, a);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {                          // wave64 butterfly
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, o, 64));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, o, 64));
-    }
+    lo = wave::wave_min(lo);
+    hi = wave::wave_max(hi);
     if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {                                     // ONE atomic pair per workgroup: same-address atomics serialise
@@ -326,23 +324,13 @@ __global__ __launch_bounds__(256) void cc_stats(int *parent, int *area, int *min
             const int p = (int)(i % ((long long)H * W));
             y = p / W; x = p - y * W;
         }
-        unsigned long long todo = __ballot(r >= 0);
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            const int r0 = __shfl(r, leader, 64);
-            const bool mine = r == r0;
-            const unsigned long long m = __ballot(mine);
-            int lx = mine ? x : 0x7FFFFFFF, hx = mine ? x : -1, ly = mine ? y : 0x7FFFFFFF, hy = mine ? y : -1;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                lx = min(lx, __shfl_xor(lx, o, 64)); hx = max(hx, __shfl_xor(hx, o, 64));
-                ly = min(ly, __shfl_xor(ly, o, 64)); hy = max(hy, __shfl_xor(hy, o, 64));
-            }
+        wave::peel<64>(r, -1, [&](int r0, bool mine, unsigned long long m, int) {
+            const int lx = wave::wave_min(mine ? x : 0x7FFFFFFF), hx = wave::wave_max(mine ? x : -1);
+            const int ly = wave::wave_min(mine ? y : 0x7FFFFFFF), hy = wave::wave_max(mine ? y : -1);
             if (r0 != ar) { flush(); ar = r0; an = 0; alx = 0x7FFFFFFF; ahx = -1; aly = 0x7FFFFFFF; ahy = -1; }
             an += __builtin_popcountll(m);
             alx = min(alx, lx); ahx = max(ahx, hx); aly = min(aly, ly); ahy = max(ahy, hy);
-            todo &= ~m;
-        }
+        });
     }
     flush();
 }

@@ -4,12 +4,15 @@
 #include "../../include/mi_unet.h"
 #include "cc_common.h"
 #include "kernel_common.h"
+#include "wave.h"
 
 static_assert(sizeof(mi_unet_region) == 96, "mi_unet_region is 96 bytes without padding");
 static_assert(offsetof(mi_unet_region, edges) == 32 && offsetof(mi_unet_region, sii) == 88, "mi_unet_region: eight ints, eight int64");
 
 namespace miunet {
 namespace rg {
+
+using namespace wave;
 
 // One thread per (plane, slot): the accumulator is the output struct itself.  A slot in use gets the identities of its min / max
 // fields and its index written at the component's root in the slot map; every other entry -- behind the plane's count, and the whole
@@ -41,34 +44,6 @@ __global__ __launch_bounds__(256) void k_region_slots(const int *__restrict__ ro
 // lanes add the eight int64 sums (64 contiguous bytes), one the area, three take the minima, three the maxima.
 // The forest is read as the contour path left it (not flattened): find_root_ro walks, nothing is stored.
 constexpr int RG_RUN = 16;
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v)      // two-word shuffles
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int lo = __shfl_xor((int)(unsigned)v, o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
-        v += (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-    }
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 template <bool TILES>
 __global__ __launch_bounds__(256) void region_stats(const uint8_t *__restrict__ fg, const int *__restrict__ fparent,
@@ -113,12 +88,7 @@ __global__ __launch_bounds__(256) void region_stats(const uint8_t *__restrict__ 
             e = (x == 0 || !fg[i - 1]) + (x == W - 1 || !fg[i + 1]) + (y == 0 || !fg[i - W]) + (y == H - 1 || !fg[i + W]);
             if constexpr (TILES) v = tiles[((size_t)(pl / K) * hw + p) * in_ch + channel];      // the plane's IMAGE: never replicated
         }
-        unsigned long long todo = __ballot(r >= 0);
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            const int r0 = __shfl(r, leader, 64);
-            const bool mine = r == r0;
-            const unsigned long long m = __ballot(mine);
+        peel<64>(r, -1, [&](int r0, bool mine, u64 m, int) {
             const long long lx = mine ? x : 0, ly = mine ? y : 0;
             const int pe = wave_sum(mine ? e : 0);
             const long long psx = wave_sum(lx), psy = wave_sum(ly), psxx = wave_sum(lx * lx), psyy = wave_sum(ly * ly),
@@ -141,8 +111,7 @@ __global__ __launch_bounds__(256) void region_stats(const uint8_t *__restrict__ 
             } else {
                 c_imin = 0; c_imax = 0;                         // the identities of a slot without a tile (k_region_slots)
             }
-            todo &= ~m;
-        }
+        });
     }
     flush();
 }

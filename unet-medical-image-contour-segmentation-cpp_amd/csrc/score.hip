@@ -44,14 +44,9 @@ inline Ws carve(void *base, int B, int H, int W, int n, int classes)
 __device__ __forceinline__ void wave_hist_add(unsigned *hist, unsigned key)
 {
     const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(key != NONE);
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const unsigned k0 = (unsigned)__shfl((int)key, leader, 64);
-        const unsigned long long m = __ballot(key == k0);
+    peel<64>(key, NONE, [&](unsigned k0, bool, u64 m, int leader) {
         if (lane == leader) atomicAdd(&hist[k0], (unsigned)__builtin_popcountll(m));
-        todo &= ~m;
-    }
+    });
 }
 
 // ---- counts: tp / fp / fn of every value and the confusion matrix, both maps read once ------------------------------------------
@@ -88,14 +83,9 @@ __global__ __launch_bounds__(256) void k_score_counts(const uint8_t *__restrict_
         if constexpr (CONF) {
             unsigned key = NONE;
             if (valid) key = (p < classes && t < classes) ? (unsigned)(t * classes + p) : 256u;
-            unsigned long long todo = __ballot(key != NONE);
-            while (todo) {
-                const int leader = __builtin_ctzll(todo);
-                const unsigned k0 = (unsigned)__shfl((int)key, leader, 64);
-                const unsigned long long m = __ballot(key == k0);
+            peel<64>(key, NONE, [&](unsigned k0, bool, u64 m, int leader) {
                 if (lane == leader) s_conf[wv][k0] += (unsigned)__builtin_popcountll(m);
-                todo &= ~m;
-            }
+            });
         }
     }
     if (lane == 0) {
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(256) void k_score_columns(const uint8_t *__restrict
 {
     __shared__ int s_n[4];
     const int q = blockIdx.x / wblocks, xb = blockIdx.x - q * wblocks, p = q >> 1, set = q & 1;
-    const int b = p / vals.n, v = pick_value(vals, p - b * vals.n);
+    const int b = p / vals.n, v = pick_value(vals.v, p - b * vals.n);
     const size_t hw = (size_t)H * W;
     const uint8_t *const map = (set ? truth : pred) + (size_t)b * hw;
     uint16_t *const g = g_all + (size_t)q * hw;
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(256) void k_score_columns(const uint8_t *__restrict
             if (d < gv) g[(size_t)y * W + x] = (uint16_t)d;
         }
     }
-    count = wave_sum_i(count);
+    count = wave_sum(count);
     if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = count;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -229,9 +219,9 @@ __global__ __launch_bounds__(256) void k_score_rows(int H, int W, const uint16_t
         t_sum += (unsigned)best;
         t_q += sqrt_q16(best);
     }
-    t_max = wave_max_i(t_max);
-    t_sum = wave_sum_u64(t_sum);
-    t_q = wave_sum_u64(t_q);
+    t_max = wave_max(t_max);
+    t_sum = wave_sum(t_sum);
+    t_q = wave_sum(t_q);
     if ((tid & 63) == 0) { s_max[tid >> 6] = t_max; s_sum[tid >> 6] = t_sum; s_q[tid >> 6] = t_q; }
     __syncthreads();
     if (tid == 0) {
@@ -324,7 +314,7 @@ __global__ __launch_bounds__(256) void k_score_final(int P, ScoreValues vals, in
     mi_unet_score s;
     s.tp = a.tp; s.fp = a.fp; s.fn = a.fn;
     s.q_d2_sym = have ? (int)((a.sel_bin[2] << 16) | a.sel_lo[2]) : -1;
-    s.value = pick_value(vals, p % vals.n);
+    s.value = pick_value(vals.v, p % vals.n);
     s.quantile_ppm = quantile_ppm;
     mi_unet_score_dir d[2];
 #pragma unroll

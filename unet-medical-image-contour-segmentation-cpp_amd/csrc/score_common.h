@@ -1,5 +1,4 @@
-// score_common.h -- what score.hip and score_volume.hip (7.10) share: the accumulators of a plane, the wave
-// reductions, the exact q16 root, and the launchers of the kernels that do not care how many axes a plane has -- the counts over a
+// score_common.h -- what score.hip and score_volume.hip (7.10) share: the accumulators of a plane, the exact q16 root, and the launchers of the kernels that do not care how many axes a plane has -- the counts over a
 // run of bytes and the 16 + 16-bit radix select over a direction's list with the final step.  The kernels themselves live in
 // score.hip.  Internal to libmiunet.so.
 #pragma once
@@ -8,10 +7,13 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace sc {
+
+using namespace wave;
 
 constexpr unsigned SENT = 0xFFFFu;                      // g of a column without a boundary pixel (real distances are <= 32766)
 constexpr unsigned NONE = 0xFFFFFFFFu;
@@ -30,34 +32,6 @@ static_assert(sizeof(ScoreAcc) % 8 == 0, "ScoreAcc rows stay 8-byte aligned");
 constexpr size_t HIST_BYTES_PER_PLANE = (size_t)5 * 65536 * sizeof(unsigned);   // high halves of direction 0, 1; low halves of selection 0, 1, 2
 
 __host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ int pick_value(const ScoreValues &v, int k)
-{
-    int r = v.v[0];
-#pragma unroll
-    for (int j = 1; j < SCORE_MAX_VALUES; ++j)
-        if (k == j) r = v.v[j];
-    return r;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-    return v;
-}
 
 // floor(2^16 sqrt(d2)) exactly: the fp64 root of d2 << 32 (exact in fp64: 31 significant bits), corrected to the integer floor
 __device__ __forceinline__ unsigned long long sqrt_q16(int d2)

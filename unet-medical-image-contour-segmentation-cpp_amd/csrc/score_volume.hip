@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_sv_columns(const uint8_t *__restrict__ 
     const int items = 2 * vals.n * cblocks;
     for (int item = blockIdx.x; item < items; item += gridDim.x) {        // (workgroup-uniform)
         const int q = item / cblocks, cb = item - q * cblocks, p = q >> 1, set = q & 1;
-        const int v = sc::pick_value(vals, p);
+        const int v = sc::pick_value(vals.v, p);
         const uint8_t *const map = set ? truth : pred;
         uint16_t *const g = g_all + (size_t)q * dhw;
         uint8_t *const rows = rows_all + (size_t)q * D * H;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_sv_columns(const uint8_t *__restrict__ 
                 if (d < gv) g[(size_t)z * hw + i] = (uint16_t)d;
             }
         }
-        count = sc::wave_sum_i(count);
+        count = sc::wave_sum(count);
         if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = count;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -206,9 +206,9 @@ __global__ __launch_bounds__(256) void k_sv_rows(Dims dm, int n, const uint16_t 
             t_sum += best;
             t_q += sc::sqrt_q16((int)best);
         }
-        t_max = sc::wave_max_i(t_max);
-        t_sum = sc::wave_sum_u64(t_sum);
-        t_q = sc::wave_sum_u64(t_q);
+        t_max = sc::wave_max(t_max);
+        t_sum = sc::wave_sum(t_sum);
+        t_q = sc::wave_sum(t_q);
         if ((tid & 63) == 0) { s_max[tid >> 6] = t_max; s_sum[tid >> 6] = t_sum; s_q[tid >> 6] = t_q; }
         __syncthreads();
         if (tid == 0) {

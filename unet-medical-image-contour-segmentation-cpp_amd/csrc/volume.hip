@@ -4,10 +4,13 @@
 #include "../../include/mi_unet.h"
 #include "cc_common.h"
 #include "kernel_common.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vl {
+
+using namespace wave;
 
 constexpr int NO_SLOT = -1;
 constexpr int RUN = 16;                                  // 64-voxel segments a wave of k_vol_stats carries a root over (cc_stats' CC_RUN)
@@ -55,15 +58,6 @@ inline Ws carve(void *base, size_t dhw, int n)
     return w;
 }
 
-__device__ __forceinline__ int pick_value(const VolumeArgs &a, int k)
-{
-    int r = a.v[0];
-#pragma unroll
-    for (int j = 1; j < VOLUME_MAX_VALUES; ++j)
-        if (k == j) r = a.v[j];
-    return r;
-}
-
 // ---- init: the parent of a set voxel is the first voxel of its run inside the lane's 64-voxel segment -----------------------------------
 // (cc_init in three dimensions.)  Voxel i of plane k is i = k * dhw + z * hw + y * W + x; dhw is a multiple of W, so x == 0 marks the
 // start of every row, of every slice and of every plane: a run never continues from x = W - 1 into any of them.
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(256) void k_vol_init(const uint8_t *__restrict__ ma
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     const bool in = i < N;
     const unsigned k = in ? i / dhw : 0u, src = in ? i - k * dhw : 0u;
-    const bool f = in && masks[src] == pick_value(a, (int)k);
+    const bool f = in && masks[src] == pick_value(a.v, (int)k);
     const unsigned x = src % (unsigned)a.W;
     const int lane = threadIdx.x & 63;
     const unsigned long long fm = __ballot(f);
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(256) void k_vol_merge(const uint8_t *__restrict__ m
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N) return;
     const unsigned k = i / dhw, src = i - k * dhw;
-    const int v = pick_value(a, (int)k);
+    const int v = pick_value(a.v, (int)k);
     if (masks[src] != v) return;
     const int W = a.W, H = a.H, hw = H * W;
     const int z = (int)(src / (unsigned)hw), rem = (int)(src - (unsigned)z * (unsigned)hw), y = rem / W, x = rem - y * W;
@@ -165,28 +159,20 @@ __global__ __launch_bounds__(256) void k_vol_roots(const int *__restrict__ paren
                                                    int *slot, mi_unet_vcomp *stat, int *tidx, unsigned N)
 {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool root = i < N && parent[i] == (int)i;
-    const unsigned k = root ? i / dhw : 0xFFFFFFFFu;
+    unsigned k = root ? i / dhw : 0xFFFFFFFFu;
     unsigned s = 0;
-    unsigned long long todo = __ballot(root);
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const unsigned k0 = (unsigned)__shfl((int)k, leader, 64);
-        const unsigned long long mk = __ballot(k == k0);
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(&acc[k0].nroots, (unsigned)__builtin_popcountll(mk));
-        base = (unsigned)__shfl((int)base, leader, 64);
-        if (k == k0) s = base + (unsigned)__builtin_popcountll(mk & ((1ull << lane) - 1ull));
-        todo &= ~mk;
-    }
+    peel<64>(k, 0xFFFFFFFFu, [&](unsigned k0, bool mine, u64 mk, int leader) {
+        const unsigned slot_k0 = wave_take(&acc[k0].nroots, mk, leader);
+        if (mine) s = slot_k0;
+    });
     if (!root) return;
     if (s >= S) { slot[i] = NO_SLOT; acc[k].overflow = 1u; return; }
     slot[i] = (int)s;
     mi_unet_vcomp c;
     c.voxels = 0; c.first = (int)(i - k * dhw);
     c.x0 = c.y0 = c.z0 = 0x7FFFFFFF; c.x1 = c.y1 = c.z1 = -1;
-    c.kept = 0; c.value = pick_value(a, (int)k);
+    c.kept = 0; c.value = pick_value(a.v, (int)k);
     c.faces_x = c.faces_y = c.faces_z = 0; c.sx = c.sy = c.sz = 0;
     stat[(size_t)k * S + s] = c;
     tidx[(size_t)k * S + s] = 0;
@@ -196,31 +182,6 @@ __global__ __launch_bounds__(256) void k_vol_roots(const int *__restrict__ paren
 // cc_stats in three dimensions: a volume is a handful of roots and same-address atomics serialise, so a wave reduces per distinct root
 // inside a 64-voxel segment and carries that root's sums over RUN consecutive segments; it issues its atomics only when the root
 // changes, thirteen of them from thirteen lanes at once.  The sums a wave carries: at most 64 * RUN voxels, 2 faces per voxel and axis.
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_vol_stats(const uint8_t *__restrict__ masks, VolumeArgs a, unsigned dhw, unsigned S, int *parent,
                                                    const int *__restrict__ slot, mi_unet_vcomp *stat, unsigned N)
 {
@@ -234,7 +195,6 @@ __global__ __launch_bounds__(256) void k_vol_stats(const uint8_t *__restrict__ m
         const int s = slot[ar];
         if (s == NO_SLOT) return;
         mi_unet_vcomp *const c = stat + (size_t)((unsigned)ar / dhw) * S + s;
-        typedef unsigned long long u64;
         switch (lane) {
         case 0: atomicAdd(&c->voxels, an); break;
         case 1: atomicMin(&c->x0, lo[0]); break;
@@ -260,7 +220,7 @@ __global__ __launch_bounds__(256) void k_vol_stats(const uint8_t *__restrict__ m
             r = pp::find_root_ro(parent, (int)i);
             parent[i] = r;
             const unsigned k = (unsigned)i / dhw, src = (unsigned)i - k * dhw;
-            const int v = pick_value(a, (int)k);
+            const int v = pick_value(a.v, (int)k);
             const int z = (int)(src / (unsigned)hw), rem = (int)(src - (unsigned)z * (unsigned)hw), y = rem / W, x = rem - y * W;
             const uint8_t *const m = masks + src;
             co[0] = x; co[1] = y; co[2] = z;
@@ -268,12 +228,7 @@ __global__ __launch_bounds__(256) void k_vol_stats(const uint8_t *__restrict__ m
             f[1] = !(y > 0 && m[-W] == v) + !(y + 1 < H && m[W] == v);
             f[2] = !(z > 0 && m[-hw] == v) + !(z + 1 < D && m[hw] == v);
         }
-        unsigned long long todo = __ballot(r >= 0);
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            const int r0 = __shfl(r, leader, 64);
-            const bool mine = r == r0;
-            const unsigned long long mm = __ballot(mine);
+        peel<64>(r, -1, [&](int r0, bool mine, u64 mm, int) {
             if (r0 != ar) {
                 flush();
                 ar = r0; an = 0;
@@ -286,10 +241,9 @@ __global__ __launch_bounds__(256) void k_vol_stats(const uint8_t *__restrict__ m
                 lo[j] = min(lo[j], wave_min(mine ? co[j] : 0x7FFFFFFF));
                 hi[j] = max(hi[j], wave_max(mine ? co[j] : -1));
                 fc[j] += wave_sum(mine ? f[j] : 0);
-                sm[j] += wave_sum64(mine ? (long long)co[j] : 0LL);
+                sm[j] += wave_sum(mine ? (long long)co[j] : 0LL);
             }
-            todo &= ~mm;
-        }
+        });
     }
     flush();
 }
@@ -340,14 +294,9 @@ __global__ __launch_bounds__(256) void k_vol_select(VolumeArgs a, unsigned S, Pl
                 const unsigned long long q = key[s];
                 if (pass == 0 || (q >> (shift + RADIX_BITS)) == prefix) digit = (unsigned)(q >> shift) & (RADIX_BINS - 1);
             }
-            unsigned long long todo = __ballot(digit != 0xFFFFFFFFu);
-            while (todo) {
-                const int leader = __builtin_ctzll(todo);
-                const unsigned d0 = (unsigned)__shfl((int)digit, leader, 64);
-                const unsigned long long mm = __ballot(digit == d0);
+            peel<64>(digit, 0xFFFFFFFFu, [&](unsigned d0, bool, u64 mm, int leader) {
                 if (lane == leader) atomicAdd(&s_hist[d0], (unsigned)__builtin_popcountll(mm));
-                todo &= ~mm;
-            }
+            });
         }
         __syncthreads();
         // lane t owns the bins RADIX_BINS - 1 - (8 t + j), j = 0 .. 7: from the top down
@@ -450,7 +399,7 @@ __global__ __launch_bounds__(256) void k_vol_write(VolumeArgs a, unsigned dhw, u
         if (s != NO_SLOT) {
             const unsigned long long q = key[(size_t)k * S + s];
             if ((long long)(q >> 31) >= (long long)a.min_voxels && q >= acc[k].thr[0]) {
-                o = pick_value(a, (int)k);
+                o = pick_value(a.v, (int)k);
                 const int ti = tidx[(size_t)k * S + s];
                 id = ti ? ti : -1;
             }

@@ -7,10 +7,13 @@
 #include "../../include/mi_unet.h"
 #include "cc_common.h"
 #include "kernel_common.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vc {
+
+using namespace wave;
 
 // The workspace of a call: N = n * D * H * W voxels of all planes.  The fill's forest and flags lie in f and g, which the passes of
 // the morphology use only after the fill has written cur.
@@ -37,35 +40,14 @@ inline Ws carve(void *base, size_t N)
 
 struct Vals { int v[VOLUME_MAX_VALUES]; };
 
-__device__ __forceinline__ int pick_value(const Vals &a, int k)
-{
-    int r = a.v[0];
-#pragma unroll
-    for (int j = 1; j < VOLUME_MAX_VALUES; ++j)
-        if (k == j) r = a.v[j];
-    return r;
-}
-
 // One ball under one spacing: the half-widths already cut to the sides they run along (a longer one reaches nothing more).
 struct Ball { int ux, uy, uz, ex, ey, ez; unsigned r2; };
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // the workgroup's sum of c, added to *dst by one lane (every lane of the workgroup calls this)
 __device__ __forceinline__ void block_count(int c, unsigned long long *dst, int *s_n)
 {
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = s_n[0] + s_n[1] + s_n[2] + s_n[3];
-        if (tot) atomicAdd(dst, (unsigned long long)tot);
-    }
+    const int tot = wave_offsets(wave_sum(c), s_n).y;
+    if (threadIdx.x == 0 && tot) atomicAdd(dst, (unsigned long long)tot);
 }
 
 // Every kernel below but k_vc_z and k_vc_faces runs one lane per voxel, consecutive lanes along x: workgroup blockIdx.x of plane
@@ -79,7 +61,7 @@ __global__ __launch_bounds__(256) void k_vc_set(const uint8_t *__restrict__ mask
     const unsigned k = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
     int c = 0;
     if (i < dhw) {
-        c = masks[i] == pick_value(a, (int)k);
+        c = masks[i] == pick_value(a.v, (int)k);
         cur[(size_t)k * dhw + i] = (uint8_t)c;
     }
     block_count(c, counts + 4 * k, s_n);
@@ -92,7 +74,7 @@ __global__ __launch_bounds__(256) void k_vc_bg_init(const uint8_t *__restrict__ 
 {
     const unsigned k = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
     const bool in = i < dhw;
-    const bool f = in && masks[i] != pick_value(a, (int)k);
+    const bool f = in && masks[i] != pick_value(a.v, (int)k);
     const unsigned x = (in ? i : 0u) % (unsigned)W;
     const int lane = threadIdx.x & 63;
     const unsigned long long fm = __ballot(f);
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(256) void k_vc_bg_merge(const uint8_t *__restrict__
 {
     const unsigned k = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= dhw) return;
-    const int v = pick_value(a, (int)k);
+    const int v = pick_value(a.v, (int)k);
     if (masks[i] == v) return;
     const int hw = H * W;
     const int z = (int)(i / (unsigned)hw), rem = (int)(i - (unsigned)z * (unsigned)hw), y = rem / W, x = rem - y * W;
@@ -164,7 +146,7 @@ __global__ __launch_bounds__(256) void k_vc_fill_write(const uint8_t *__restrict
     int c0 = 0, c1 = 0;
     if (i < dhw) {
         const int gi = (int)(k * dhw + i);
-        c0 = masks[i] == pick_value(a, (int)k);
+        c0 = masks[i] == pick_value(a.v, (int)k);
         c1 = c0;
         if (!c0 && !flag[pp::find_root_ro(parent, gi)]) c1 = 1;     // (a background voxel: parent[gi] >= 0)
         cur[gi] = (uint8_t)c1;
@@ -256,7 +238,7 @@ __global__ __launch_bounds__(256) void k_vc_emit(const uint8_t *__restrict__ cur
 {
     const unsigned k = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= dhw) return;
-    out[(size_t)k * dhw + i] = cur[(size_t)k * dhw + i] ? (uint8_t)pick_value(a, (int)k) : (uint8_t)0;
+    out[(size_t)k * dhw + i] = cur[(size_t)k * dhw + i] ? (uint8_t)pick_value(a.v, (int)k) : (uint8_t)0;
 }
 
 }  // namespace vc

@@ -6,10 +6,13 @@
 // them by one comparison of 64-bit products.  Byte and integer work, exact.  gfx950 only.
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vi {
+
+using namespace wave;
 
 constexpr unsigned SENT = 0x7FFFu;          // no pixel of the other state in this column (a distance is at most 8191)
 constexpr unsigned STATE = 0x8000u;         // bit 15 of a column word: the pixel is in the set
@@ -38,22 +41,6 @@ inline Ws carve(void *base, size_t N, size_t slices)
 
 struct Vals { int v[VOLUME_MAX_VALUES]; };
 
-__device__ __forceinline__ int pick_value(const Vals &a, int k)
-{
-    int r = a.v[0];
-#pragma unroll
-    for (int j = 1; j < VOLUME_MAX_VALUES; ++j)
-        if (k == j) r = a.v[j];
-    return r;
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- columns: the 1-D distance to the other state ------------------------------------------------------------------------------------
 // One wave per 64 columns of slice blockIdx.y of plane blockIdx.z, a lane per column, consecutive lanes along x.  Down the column the
 // distance to the last pixel above whose state differs from the pixel's own, back up the minimum with the distance to the next one
@@ -62,7 +49,7 @@ __global__ __launch_bounds__(64) void k_vi_columns(const uint8_t *__restrict__ m
                                                    unsigned *both)
 {
     const int z = blockIdx.y, D = gridDim.y, k = blockIdx.z, x = blockIdx.x * 64 + threadIdx.x;
-    const int v = pick_value(a, k);
+    const int v = pick_value(a.v, k);
     const size_t hw = (size_t)H * W;
     const uint8_t *const m = masks + (size_t)z * hw;
     uint16_t *const g = g_all + ((size_t)k * D + z) * hw;
@@ -153,7 +140,7 @@ __global__ __launch_bounds__(256) void k_vi_blend(const int32_t *__restrict__ fi
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     int c_in = 0, c_out = 0, c_mixed = 0, c_mset = 0, c_ties = 0;
     if (i < hw) {
-        const uint8_t v = (uint8_t)pick_value(a, p);
+        const uint8_t v = (uint8_t)pick_value(a.v, p);
         const size_t Dp = (size_t)(D - 1) * kf + 1;
         const int32_t fa = field[((size_t)p * D + z) * hw + i];
         uint8_t *o = out + ((size_t)p * Dp + (size_t)z * kf) * hw + i;

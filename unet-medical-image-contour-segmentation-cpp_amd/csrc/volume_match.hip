@@ -1,43 +1,27 @@
 // volume_match.hip -- the contingency table of two labelled stacks and what is read off it (include/mi_unet.h: mi_unet_volume_match;
 // DESIGN.md 7.14).  k_vmt_count, the hot path: a lane per voxel, the wave reduces per distinct key a (mt + 1) + b and carries the
-// counts of a few keys until they are displaced (k_vol_stats' scheme with four slots).  k_vmt_rows, k_vmt_cols and k_vmt_cols_end: the
+// counts of a few keys until they are displaced (wave.h's peel, written out, with four slots).  k_vmt_rows, k_vmt_cols and k_vmt_cols_end: the
 // side tables of the pred and of the truth components.  k_vmt_scan: the exclusive prefix of the rows' pair counts.  k_vmt_pairs: every
 // pair at its final position.  Every result is an integer sum or maximum, so nothing depends on the order in which atomics arrive; no
 // workgroup waits for another.  gfx950 only.
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vmt {
 
+using namespace wave;
+
 constexpr unsigned WG = 256;                // lanes per workgroup
-constexpr int RUN = 16;                     // 64-voxel segments of one span of a wave's walk (k_vol_stats' RUN)
+constexpr int RUN = 16;                     // 64-voxel segments of one span of a wave's walk
 constexpr int GROUPS = 4;                   // distinct keys of a segment that are reduced across the wave; lanes beyond them add their own
 constexpr int SLOTS = 4;                    // keys a wave of k_vmt_count carries at once (a power of two)
 constexpr unsigned MAX_WGS = 2048;          // workgroups of k_vmt_count: eight a CU on 256 CUs, whatever the volume's size
 constexpr int COL_ROWS = 64;                // rows of the table one workgroup of k_vmt_cols walks
 constexpr int SCAN_PER_LANE = (MI_UNET_VOLUME_MAX_TABLE + (int)WG - 1) / (int)WG;      // rows one lane of k_vmt_scan sums
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ u64 wave_max64(u64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = (u64)__shfl_xor((long long)v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 // the largest count wins, among equal counts the smallest index: one order-free maximum (DESIGN.md 7.13's key)
 __device__ __forceinline__ u64 best_key(int count, int index) { return ((u64)(unsigned)count << 32) | (u64)(~(unsigned)index); }
@@ -55,7 +39,7 @@ __device__ __forceinline__ void store_side(::mi_unet_vmatch_side *o, int voxels,
 // A wave walks spans of RUN 64-voxel segments, span after span at the stride of the grid.  Per segment it takes up to GROUPS distinct
 // keys, each by ballot and popcount, and adds the count to the key's slot: it carries SLOTS keys at once, from segment to segment and
 // from span to span, and a key that finds no slot takes the one whose turn it is, whose count goes out as one atomic; the walk's end
-// sends the rest.  One slot is k_vol_stats' scheme; a row through a lesion alternates between "pred only", "both" and "truth only", and
+// sends the rest.  One slot is what k_vol_stats carries; a row through a lesion alternates between "pred only", "both" and "truth only", and
 // with one slot every change sent an atomic to one of a handful of hot cells (docs/EXPERIMENTS.md R5.11: 282 -> 124 us on the bench's
 // blobs).  A segment without a key changes nothing, so keys are carried across background.  Lanes whose key is none of the segment's
 // first GROUPS add their own voxel.  (Four voxels per lane from one 16-byte load was measured too and is slower.)
@@ -77,6 +61,8 @@ __global__ __launch_bounds__(256) void k_vmt_count(const int32_t *__restrict__ p
                 const int a = pred[i], b = truth[i];
                 k = (a >= 1 && a <= mp ? a : 0) * (mt + 1) + (b >= 1 && b <= mt ? b : 0);     // (< 4097^2)
             }
+            // (wave.h's peel<GROUPS>, written out: with the four slots as the loop's body the compiler turns a select of the peel form into
+            // a branch, and the bench's noise case measured 6 % slower; docs/EXPERIMENTS.md R5.19)
             u64 todo = __ballot(k != 0);
             for (int g = 0; g < GROUPS && todo; ++g) {          // (wave-uniform)
                 const int k0 = __shfl(k, __builtin_ctzll(todo), 64);
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(256) void k_vmt_rows(const int32_t *__restrict__ ta
     const int none = __shfl(lane == 0 ? row[0] : 0, 0, 64);
     voxels = wave_sum(voxels);
     partners = wave_sum(partners);
-    key = wave_max64(key);
+    key = wave_max(key);
     if (lane == 0) {
         store_side(side + r, voxels, none, partners, key);
         row_pairs[r] = partners;

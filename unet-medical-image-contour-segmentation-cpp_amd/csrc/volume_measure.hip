@@ -1,53 +1,25 @@
 // volume_measure.hip -- per component of a labelled stack its sums, its run ends and its longest diameters (include/mi_unet.h:
 // mi_unet_volume_measure).  k_vms_sums: a lane per voxel, the wave reduces per distinct id and carries an id's sums until
-// the id changes (k_vol_stats' scheme).  k_vms_fill: every run end of a searched component into the component's segment.  k_vms_pairs, the
+// the id changes (wave.h's peel).  k_vms_fill: every run end of a searched component into the component's segment.  k_vms_pairs, the
 // hot path: an N-body tiling over the upper-triangular tile pairs of a segment, a point per lane against a tile in LDS.  k_vms_ends: the
 // smallest partner of the winning (d2, p).  Every result is an integer sum, minimum or maximum, so nothing depends on the order in which
 // atomics arrive or in which a segment was filled; no workgroup waits for another.  gfx950 only.
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vms {
 
+using namespace wave;
+
 constexpr unsigned WG = 256;                // lanes per workgroup; = VMS_TILE in k_vms_pairs
-constexpr int RUN = 16;                     // 64-voxel segments a wave of k_vms_sums carries an id over (k_vol_stats' RUN)
+constexpr int RUN = 16;                     // 64-voxel segments a wave of k_vms_sums carries an id over
 constexpr int GROUPS = 4;                   // distinct ids of a segment that are reduced across the wave; lanes beyond them add their own
 constexpr int NONE = 0x7FFFFFFF;
 static_assert(VMS_TILE == (int)WG, "a lane per point of the a-tile, a lane per point of the b-tile's load");
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ long long wave_sum64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ u64 wave_max64(u64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = (u64)__shfl_xor((long long)v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 // the sums of one id: n voxels, e run ends, the nine coordinate sums (x, y, z, xx, yy, zz, xy, xz, yz), si, sii, lo / hi of the intensity
 struct Acc {
@@ -105,11 +77,7 @@ __global__ __launch_bounds__(256) void k_vms_sums(const int32_t *__restrict__ id
                 if (inten) v = inten[i];
             }
         }
-        u64 todo = __ballot(r >= 0);
-        for (int g = 0; g < GROUPS && todo; ++g) {              // (wave-uniform)
-            const int r0 = __shfl(r, __builtin_ctzll(todo), 64);
-            const bool mine = r == r0;
-            const u64 mm = __ballot(mine);
+        peel<GROUPS>(r, -1, [&](int r0, bool mine, u64 mm, int) {
             if (r0 != ar) {
                 flush();
                 reset();
@@ -118,17 +86,15 @@ __global__ __launch_bounds__(256) void k_vms_sums(const int32_t *__restrict__ id
             acc.n += __popcll(mm);
             acc.e += __popcll(__ballot(mine && e));
             const long long cx = mine ? x : 0, cy = mine ? y : 0, cz = mine ? z : 0, cv = mine ? v : 0;
-            acc.s[0] += wave_sum64(cx); acc.s[1] += wave_sum64(cy); acc.s[2] += wave_sum64(cz);
-            acc.s[3] += wave_sum64(cx * cx); acc.s[4] += wave_sum64(cy * cy); acc.s[5] += wave_sum64(cz * cz);
-            acc.s[6] += wave_sum64(cx * cy); acc.s[7] += wave_sum64(cx * cz); acc.s[8] += wave_sum64(cy * cz);
+            acc.s[0] += wave_sum(cx); acc.s[1] += wave_sum(cy); acc.s[2] += wave_sum(cz);
+            acc.s[3] += wave_sum(cx * cx); acc.s[4] += wave_sum(cy * cy); acc.s[5] += wave_sum(cz * cz);
+            acc.s[6] += wave_sum(cx * cy); acc.s[7] += wave_sum(cx * cz); acc.s[8] += wave_sum(cy * cz);
             if (inten) {                                        // (uniform)
-                acc.s[9] += wave_sum64(cv); acc.s[10] += wave_sum64(cv * cv);
+                acc.s[9] += wave_sum(cv); acc.s[10] += wave_sum(cv * cv);
                 acc.lo = min(acc.lo, wave_min(mine ? v : 65535));
                 acc.hi = max(acc.hi, wave_max(mine ? v : 0));
             }
-            todo &= ~mm;
-            if (mine) r = -1;
-        }
+        });
         if (r >= 0) {                                           // a segment of many small components: the lane adds its own voxel
             Acc one;
             one.n = 1; one.e = e; one.lo = v; one.hi = v;
@@ -161,22 +127,13 @@ __global__ __launch_bounds__(256) void k_vms_fill(const int32_t *__restrict__ id
             if ((x == 0 || ids[i - 1] != id) || (x == a.W - 1 || ids[i + 1] != id)) r = id - 1;
         }
     }
-    u64 todo = __ballot(r >= 0);
-    while (todo) {                                              // (wave-uniform)
-        const int leader = __builtin_ctzll(todo);
-        const int r0 = __shfl(r, leader, 64);
-        const bool mine = r == r0;
-        const u64 mm = __ballot(mine);
-        int base = 0;
-        if ((threadIdx.x & 63) == (unsigned)leader) base = atomicAdd(cursor + r0, __popcll(mm));
-        base = __shfl(base, leader, 64);
+    peel<64>(r, -1, [&](int r0, bool mine, u64 mm, int leader) {
+        const int slot = wave_take(cursor + r0, mm, leader);
         if (mine) {
             const int2 sg = seg[r0];
-            const int slot = base + __popcll(mm & lanes_below());
             if (slot < sg.y) points[(size_t)sg.x + slot] = make_int4(x * a.ux, y * a.uy, z * a.uz, (int)i);
         }
-        todo &= ~mm;
-    }
+    });
 }
 
 // ---- pairs: the hot path -------------------------------------------------------------------------------------------------------------------
@@ -220,8 +177,8 @@ __global__ __launch_bounds__(256) void k_vms_pairs(const int4 *__restrict__ poin
     u64 k = 0, k_a = 0;
     if (valid && best) k = ((best >> 32) << 31) | (u64)(unsigned)(NONE - min(a.w, (int)~(unsigned)best));
     if (valid && best_a) k_a = ((best_a >> 32) << 31) | (u64)(unsigned)(NONE - min(a.w, (int)~(unsigned)best_a));
-    k = wave_max64(k);
-    k_a = wave_max64(k_a);
+    k = wave_max(k);
+    k_a = wave_max(k_a);
     if ((threadIdx.x & 63) == 0) {
         if (k) atomicMax(keys + 2 * it.comp, k);
         if (k_a) atomicMax(keys + 2 * it.comp + 1, k_a);

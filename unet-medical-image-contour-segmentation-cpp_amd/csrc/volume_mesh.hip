@@ -6,10 +6,13 @@
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vm {
+
+using namespace wave;
 
 constexpr unsigned WG = 256;                // lanes per workgroup of the voxel and corner kernels
 constexpr unsigned CHUNK = 1024;            // counts one workgroup of the scan takes: four per lane
@@ -56,28 +59,6 @@ inline Ws carve(void *base, int D, int H, int W)
     return w;
 }
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
-// the four waves' counts -> (the sum of the waves before this one, the workgroup's sum); every lane of the workgroup calls this
-__device__ __forceinline__ int2 wave_offsets(int wave_total, int *s_w)
-{
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = wave_total;
-    __syncthreads();
-    const int w = threadIdx.x >> 6;
-    int before = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (j < w) before += s_w[j];
-    return make_int2(before, s_w[0] + s_w[1] + s_w[2] + s_w[3]);
-}
-
 // ---- classify: one lane per voxel, consecutive lanes along x ------------------------------------------------------------------------------
 // The six neighbours are read straight from the volume: a row's x neighbours lie in the lane's own cache line, the rows above and below
 // and the two neighbouring slices are the lines the workgroups beside this one read, so the volume leaves HBM about once.  The per-axis
@@ -102,11 +83,8 @@ __global__ __launch_bounds__(256) void k_vm_classify(const uint8_t *__restrict__
         }
         expo[i] = (uint8_t)m;
     }
-    const int packed = wave_sum(__popc(m & 3) | (__popc(m & 12) << 10) | (__popc(m & 48) << 20));
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = packed;
-    __syncthreads();
+    const int t = wave_offsets(wave_sum(__popc(m & 3) | (__popc(m & 12) << 10) | (__popc(m & 48) << 20)), s_w).y;
     if (threadIdx.x == 0) {
-        const int t = s_w[0] + s_w[1] + s_w[2] + s_w[3];
         const int cx = t & 1023, cy = (t >> 10) & 1023, cz = (t >> 20) & 1023;
         qtot[blockIdx.x] = cx + cy + cz;
         if (cx) atomicAdd(axis + 0, (unsigned long long)cx);
@@ -151,10 +129,8 @@ __global__ __launch_bounds__(256) void k_vm_corners(const uint8_t *__restrict__ 
         word = corner_word(in, placement);
         cmap[c] = word;
     }
-    const int n = __popcll(__ballot(word != 0));
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) vtot[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const int n = wave_offsets(__popcll(__ballot(word != 0)), s_w).y;
+    if (threadIdx.x == 0) vtot[blockIdx.x] = n;
 }
 
 // ---- scan: exclusive, in place, CHUNK counts per workgroup; the workgroup's sum goes to sums[blockIdx.x] ------------------------------------

@@ -11,89 +11,30 @@
 #include "cc_common.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "key_tile.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vnb {
 
+using namespace wave;
+using namespace key_tile;
+
 constexpr unsigned WG = 256;                // lanes per workgroup
 constexpr int MERGE = 3;                    // distinct cells of one table that a wave merges; lanes beyond them add their own
 constexpr int GROUPS = 4;                   // distinct roots of a 64-voxel segment that are reduced across the wave
-constexpr int TX = VTX_TX, TY = VTX_TY, TZ = VTX_TZ;                   // 7.15's tile
-constexpr int KX = TX + 2, KY = TY + 2, KZ = TZ + 2;                   // the tile with its full halo
+constexpr int KZ = TZ + 2;                  // key_tile.h's tile with its full halo: z - 1 .. z + 1
 constexpr int TILE_KEYS = KX * KY * KZ;     // 3960 keys, 15 840 bytes
-constexpr int ROWS = TY * TZ;               // rows of 64 voxels in a tile, ROWS / 4 per wave
 constexpr int FAR = 0x7f7f7f7f;             // what hipMemsetAsync(.., 0x7f, ..) leaves: above every distance
-static_assert(TX == 64, "a wave per row of the tile");
-static_assert(ROWS % 4 == 0, "the rows of a tile are shared out among four waves");
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-    return v;
-}
-
-// A word that only grows (raise) or only shrinks (lower): a plain read that already shows a value at least as good makes the atomic
-// unnecessary (a stale read costs an atomic, never a result).
-__device__ __forceinline__ void raise(int *word, int v)
-{
-    if (__builtin_nontemporal_load(word) < v) atomicMax(word, v);
-}
-__device__ __forceinline__ void lower(int *word, int v)
-{
-    if (__builtin_nontemporal_load(word) > v) atomicMin(word, v);
-}
-
-// One count into `tab` (k_vzn_runs' scheme): the wave merges the lanes that name the same cell, for the first MERGE distinct cells, into
-// one atomic each; the lanes left over add their own.  With `sums` the same lanes add `val` (below 2^11 a lane) into sums[cell]: 64 bits
-// in memory, 32 in a workgroup's LDS.
-template <class S>
-__device__ __forceinline__ void count(uint32_t *tab, S *sums, bool on, unsigned cell, unsigned val)
-{
-    u64 todo = __ballot(on);
-#pragma unroll
-    for (int g = 0; g < MERGE; ++g) {
-        if (!todo) break;                                       // (wave-uniform)
-        const int leader = __builtin_ctzll(todo);
-        const unsigned c0 = (unsigned)__shfl((int)cell, leader, 64);
-        const bool same = on && cell == c0;
-        const u64 mm = __ballot(same);
-        unsigned total = 0;
-        if (sums) total = wave_sum(same ? val : 0u);            // (sums is wave-uniform)
-        if ((int)(threadIdx.x & 63) == leader) {
-            atomicAdd(tab + c0, (uint32_t)__popcll(mm));
-            if (total) atomicAdd(sums + c0, (S)total);
-        }
-        todo &= ~mm;
-        if (same) on = false;
-    }
-    if (on) {
-        atomicAdd(tab + cell, 1u);
-        if (sums && val) atomicAdd(sums + cell, (S)val);
-    }
-}
+// Every count goes through wave.h's merged_add; with `sums` a lane's `val` is below 2^11.
 
 // ---- the neighbourhoods: the hot path -----------------------------------------------------------------------------------------------------
 // LDS: the keys of the tile with its halo; a position outside the volume holds 0, which is no neighbour of anything.  A workgroup takes
 // VTX_TILES_PER_WG tiles that follow each other along x.  Every key is fetched from memory once per tile.  With LDS_TABLE the six tables
 // of one component follow the keys: count, diff and dep of 27 columns, then of 9, L rows each, the diff in 32 bits (a workgroup's
 // 8 x 2048 voxels add less than 2^25 to a cell).  That component is the one of the first voxel of the tile (in lane order) that belongs
-// to any (k_vtx_pairs' rule); when it differs from the tables' owner and holds LDS_SHARE voxels of the tile, the tables are flushed, only
+// to any (as in k_vtx_pairs); when it differs from the tables' owner and holds LDS_SHARE voxels of the tile, the tables are flushed, only
 // their non-zero cells, cleared, and are its own from then on.  Counts of every other component of the tile go to memory.
 constexpr int NO_PICK = 0x7fffffff;
 constexpr int LDS_COLS = 3 * VNB_COLS + 3 * VNB_COLS_AXIAL;    // words a level in the LDS tables
@@ -131,16 +72,8 @@ __global__ __launch_bounds__(256) void k_vnb_gather(const int32_t *__restrict__ 
     };
     const int t_end = min(n_tiles, ((int)blockIdx.x + 1) * VTX_TILES_PER_WG);
     for (int tile = (int)blockIdx.x * VTX_TILES_PER_WG; tile < t_end; ++tile) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / (tiles_x * tiles_y);
-        const int x0 = tx * TX - 1, y0 = ty * TY - 1, z0 = tz * TZ - 1;
         __syncthreads();                                        // the tile before is done with s_keys and s_pick
-        for (int e = tid; e < TILE_KEYS; e += WG) {
-            const int lz = e / (KX * KY), rem = e - lz * (KX * KY), ly = rem / KX, lx = rem - ly * KX;
-            const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            int k = 0;
-            if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H && gz >= 0 && gz < a.D) k = keys[((size_t)gz * a.H + gy) * a.W + gx];
-            s_keys[e] = k;
-        }
+        load_key_tile<KZ, 1>(s_keys, keys, tile_origin<1>(tile, tiles_x, tiles_y), a.D, a.H, a.W);
         if (LDS_TABLE) {
             if (tid == 0) {
                 s_pick = NO_PICK;
@@ -214,20 +147,20 @@ __global__ __launch_bounds__(256) void k_vnb_gather(const int32_t *__restrict__ 
             const unsigned base = (unsigned)(id - 1) * (unsigned)L + (unsigned)l;           // (below 2^17; only used when k != 0)
             uint32_t *const none = nullptr;
             if (want & VNB_WANT_NGT) {
-                if (LDS_TABLE) count(s_count, s_diff, in_lds, (unsigned)(l * VNB_COLS + c26), d26);
-                count(t.count, t.diff, in_mem, base * VNB_COLS + (unsigned)c26, d26);
+                if (LDS_TABLE) merged_add<MERGE>(s_count, s_diff, in_lds, (unsigned)(l * VNB_COLS + c26), d26);
+                merged_add<MERGE>(t.count, t.diff, in_mem, base * VNB_COLS + (unsigned)c26, d26);
             }
             if (want & VNB_WANT_DEP) {
-                if (LDS_TABLE) count(s_dep, none, in_lds, (unsigned)(l * VNB_COLS + k26), 0u);
-                count(t.dep, none, in_mem, base * VNB_COLS + (unsigned)k26, 0u);
+                if (LDS_TABLE) merged_add<MERGE>(s_dep, none, in_lds, (unsigned)(l * VNB_COLS + k26), 0u);
+                merged_add<MERGE>(t.dep, none, in_mem, base * VNB_COLS + (unsigned)k26, 0u);
             }
             if (want & VNB_WANT_NGT_AXIAL) {
-                if (LDS_TABLE) count(s_count_a, s_diff_a, in_lds, (unsigned)(l * VNB_COLS_AXIAL + c8), d8);
-                count(t.count_axial, t.diff_axial, in_mem, base * VNB_COLS_AXIAL + (unsigned)c8, d8);
+                if (LDS_TABLE) merged_add<MERGE>(s_count_a, s_diff_a, in_lds, (unsigned)(l * VNB_COLS_AXIAL + c8), d8);
+                merged_add<MERGE>(t.count_axial, t.diff_axial, in_mem, base * VNB_COLS_AXIAL + (unsigned)c8, d8);
             }
             if (want & VNB_WANT_DEP_AXIAL) {
-                if (LDS_TABLE) count(s_dep_a, none, in_lds, (unsigned)(l * VNB_COLS_AXIAL + k8), 0u);
-                count(t.dep_axial, none, in_mem, base * VNB_COLS_AXIAL + (unsigned)k8, 0u);
+                if (LDS_TABLE) merged_add<MERGE>(s_dep_a, none, in_lds, (unsigned)(l * VNB_COLS_AXIAL + k8), 0u);
+                merged_add<MERGE>(t.dep_axial, none, in_mem, base * VNB_COLS_AXIAL + (unsigned)k8, 0u);
             }
         }
     }
@@ -329,11 +262,7 @@ __global__ __launch_bounds__(256) void k_vnb_zone_min(const int32_t *__restrict_
         if (full) df = full[i];
     }
     const int comp = k >> 8;
-    u64 todo = __ballot(root >= 0);
-    for (int g = 0; g < GROUPS && todo; ++g) {                  // (wave-uniform)
-        const int leader = __builtin_ctzll(todo);
-        const int r0 = __shfl(root, leader, 64);
-        const bool mine = root == r0;
+    peel<GROUPS>(root, -1, [&](int r0, bool mine, u64, int leader) {
         if (axial) {                                            // (wave-uniform)
             const int lo = wave_min(mine ? da : FAR), hi = wave_max(mine ? da : 0);
             if (lane == leader) {
@@ -348,9 +277,7 @@ __global__ __launch_bounds__(256) void k_vnb_zone_min(const int32_t *__restrict_
                 raise(&acc[comp - 1].deepest, hi);
             }
         }
-        todo &= ~__ballot(mine);
-        if (mine) root = -1;
-    }
+    });
     if (root >= 0) {
         if (axial) {
             lower(zmin_axial + root, da);
@@ -377,13 +304,13 @@ __global__ __launch_bounds__(256) void k_vnb_zone_tally(const int32_t *__restric
     uint32_t *const words = reinterpret_cast<uint32_t *>(acc);  // (VnbAcc is four words; clamped is word 2, clamped_axial word 3)
     if (dzm) {                                                  // (wave-uniform)
         const int d = root ? max(zmin[i], 1) : 1;
-        count(dzm, (uint32_t *)nullptr, root, base + (unsigned)(min(d, Dm) - 1), 0u);
-        count(words, (uint32_t *)nullptr, root && d > Dm, r * 4u + 2u, 0u);
+        merged_add<MERGE>(dzm, (uint32_t *)nullptr, root, base + (unsigned)(min(d, Dm) - 1), 0u);
+        merged_add<MERGE>(words, (uint32_t *)nullptr, root && d > Dm, r * 4u + 2u, 0u);
     }
     if (dzm_axial) {
         const int d = root ? max(zmin_axial[i], 1) : 1;
-        count(dzm_axial, (uint32_t *)nullptr, root, base + (unsigned)(min(d, Dm) - 1), 0u);
-        count(words, (uint32_t *)nullptr, root && d > Dm, r * 4u + 3u, 0u);
+        merged_add<MERGE>(dzm_axial, (uint32_t *)nullptr, root, base + (unsigned)(min(d, Dm) - 1), 0u);
+        merged_add<MERGE>(words, (uint32_t *)nullptr, root && d > Dm, r * 4u + 3u, 0u);
     }
 }
 

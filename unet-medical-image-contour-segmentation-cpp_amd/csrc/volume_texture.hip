@@ -1,6 +1,6 @@
 // volume_texture.hip -- per component of a labelled stack its grey-level histogram and its 3-D co-occurrence tables (include/mi_unet.h:
 // mi_unet_volume_texture).  k_vtx_range: a lane per voxel, the wave reduces per distinct id and carries an id's
-// minimum and maximum until the id changes (k_vol_stats' scheme).  k_vtx_keys: ids in place into (r + 1) << 8 | level.  k_vtx_pairs, the
+// minimum and maximum until the id changes (wave.h's peel).  k_vtx_keys: ids in place into (r + 1) << 8 | level.  k_vtx_pairs, the
 // hot path: a tile of keys with its halo in LDS, the 13 forward neighbours of every voxel compared there, the counts of the component
 // that leads the tile kept in LDS-private tables.  k_vtx_finish: the 13-offset table from its two parts, and the table entries.  Every
 // result is an integer sum, minimum or maximum, so nothing depends on the order in which atomics arrive; no workgroup waits for another.
@@ -8,53 +8,27 @@
 #include "../../include/mi_unet.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "key_tile.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vtx {
 
+using namespace wave;
+using namespace key_tile;
+
 constexpr unsigned WG = 256;                // lanes per workgroup
-constexpr int RUN = 16;                     // 64-voxel segments a wave of k_vtx_range carries an id over (k_vol_stats' RUN)
+constexpr int RUN = 16;                     // 64-voxel segments a wave of k_vtx_range carries an id over
 constexpr int GROUPS = 4;                   // distinct ids of a segment that are reduced across the wave; lanes beyond them add their own
 constexpr int MERGE = 3;                    // distinct cells of one offset that a wave of k_vtx_pairs merges; lanes beyond them add their own
-constexpr int KX = VTX_TX + 2, KY = VTX_TY + 2, KZ = VTX_TZ + 1;       // the tile with its halo: x - 1 .. x + 1, y - 1 .. y + 1, z .. z + 1
+constexpr int KZ = TZ + 1;                  // key_tile.h's tile with the slice behind it: z .. z + 1
 constexpr int TILE_KEYS = KX * KY * KZ;
-constexpr int ROWS = VTX_TY * VTX_TZ;       // rows of 64 voxels in a tile, ROWS / 4 per wave
 constexpr int NO_PICK = 0x7FFFFFFF;
-static_assert(VTX_TX == 64, "a wave per row of the tile");
-static_assert(ROWS % 4 == 0, "the rows of a tile are shared out among four waves");
 static_assert(MI_UNET_VOLUME_MAX_TABLE < (1 << 13), "a pick holds a component's number in 13 bits");
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ long long wave_sum64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- range: 65535 - imin and imax per component; one lane per voxel ---------------------------------------------------------------------------
-// Both only grow, so a plain read that already shows a value at least as large makes the atomic unnecessary (a stale read is a smaller
-// one and costs an atomic, never a result): atomics of thousands of waves on the two words of one large component are served one after
-// another, and after the first few none of them changes anything.
-__device__ __forceinline__ void raise(int *word, int v)
-{
-    if (__builtin_nontemporal_load(word) < v) atomicMax(word, v);
-}
-
+// Both only grow: wave.h's raise.
 __global__ __launch_bounds__(256) void k_vtx_range(const int32_t *__restrict__ ids, const uint16_t *__restrict__ inten, unsigned dhw, int m,
                                                    int2 *range)
 {
@@ -78,20 +52,14 @@ __global__ __launch_bounds__(256) void k_vtx_range(const int32_t *__restrict__ i
                 v = inten[i];
             }
         }
-        u64 todo = __ballot(r >= 0);
-        for (int g = 0; g < GROUPS && todo; ++g) {              // (wave-uniform)
-            const int r0 = __shfl(r, __builtin_ctzll(todo), 64);
-            const bool mine = r == r0;
-            const u64 mm = __ballot(mine);
+        peel<GROUPS>(r, -1, [&](int r0, bool mine, u64, int) {
             if (r0 != ar) {
                 flush();
                 ar = r0; lo = 65535; hi = 0;
             }
             lo = min(lo, wave_min(mine ? v : 65535));
             hi = max(hi, wave_max(mine ? v : 0));
-            todo &= ~mm;
-            if (mine) r = -1;
-        }
+        });
         if (r >= 0) {                                           // a segment of many small components: the lane adds its own voxel
             int *const c = reinterpret_cast<int *>(range + r);
             raise(c, 65535 - v);
@@ -125,26 +93,7 @@ __global__ __launch_bounds__(256) void k_vtx_keys(int32_t *__restrict__ ids, con
 }
 
 // ---- pairs: the hot path -------------------------------------------------------------------------------------------------------------------
-// One count into `tab`, a table in LDS or in memory (where the cell also names the component): the wave merges the lanes that name the
-// same cell, for the first MERGE distinct cells, into one atomic each (in a homogeneous component nearly every lane names the same
-// diagonal cell, and 64 atomics on one address would be served one after another); the lanes left over add their own.
-__device__ __forceinline__ void count(uint32_t *tab, bool on, unsigned cell)
-{
-    u64 todo = __ballot(on);
-#pragma unroll
-    for (int g = 0; g < MERGE; ++g) {
-        if (!todo) break;                                       // (wave-uniform)
-        const int leader = __builtin_ctzll(todo);
-        const unsigned c0 = (unsigned)__shfl((int)cell, leader, 64);
-        const bool same = on && cell == c0;
-        const u64 mm = __ballot(same);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(tab + c0, (uint32_t)__popcll(mm));
-        todo &= ~mm;
-        if (same) on = false;
-    }
-    if (on) atomicAdd(tab + cell, 1u);
-}
-
+// Every count goes through wave.h's merged_add: into a table in LDS or in memory (where the cell also names the component).
 // LDS: the keys of the tile with its halo, then (LDS_TABLE) the owned component's axial table [L][L], inter table [L][L] and
 // histogram [L].  A workgroup takes VTX_TILES_PER_WG tiles that follow each other along x.  The component that owns the LDS tables is
 // the one of the first voxel of the tile (in lane order) that belongs to any; when it differs from the tile before, the tables are
@@ -179,16 +128,8 @@ __global__ __launch_bounds__(256) void k_vtx_pairs(const int32_t *__restrict__ k
     };
     const int t_end = min(n_tiles, ((int)blockIdx.x + 1) * VTX_TILES_PER_WG);
     for (int t = (int)blockIdx.x * VTX_TILES_PER_WG; t < t_end; ++t) {
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, tz = t / (tiles_x * tiles_y);
-        const int x0 = tx * VTX_TX - 1, y0 = ty * VTX_TY - 1, z0 = tz * VTX_TZ;
         __syncthreads();                                        // the tile before is done with s_keys and s_pick
-        for (int e = tid; e < TILE_KEYS; e += WG) {
-            const int lz = e / (KX * KY), rem = e - lz * (KX * KY), ly = rem / KX, lx = rem - ly * KX;
-            const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            int k = 0;
-            if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H && gz < a.D) k = keys[((size_t)gz * a.H + gy) * a.W + gx];
-            s_keys[e] = k;
-        }
+        load_key_tile<KZ, 0>(s_keys, keys, tile_origin<0>(t, tiles_x, tiles_y), a.D, a.H, a.W);
         if (tid == 0) s_pick = NO_PICK;
         __syncthreads();
         // the lane's voxels: row = wave * (ROWS / 4) + it of the tile, column = lane
@@ -216,15 +157,15 @@ __global__ __launch_bounds__(256) void k_vtx_pairs(const int32_t *__restrict__ k
             const int id = k >> 8, i = k & 255;                 // (id 0: no component; then nothing below counts)
             const bool in_lds = LDS_TABLE && id == owned;
             const bool in_mem = id != 0 && !in_lds;
-            if (LDS_TABLE) count(s_hist, in_lds, (unsigned)i);
-            count(hist, in_mem, (unsigned)((id - 1) * L + i));
+            if (LDS_TABLE) merged_add<MERGE>(s_hist, in_lds, (unsigned)i);
+            merged_add<MERGE>(hist, in_mem, (unsigned)((id - 1) * L + i));
             const unsigned mem_base = (unsigned)(id - 1) * (unsigned)LL + (unsigned)(i * L);     // (below 2^22)
             auto offset = [&](int dx, int dy, int dz, uint32_t *s_tab, uint32_t *g_tab) {
                 const int kq = p[dz * (KX * KY) + dy * KX + dx];
                 const bool pair = id != 0 && (kq >> 8) == id;
                 const int j = kq & 255;
-                if (LDS_TABLE) count(s_tab, pair && in_lds, (unsigned)(i * L + j));
-                count(g_tab, pair && !in_lds, mem_base + (unsigned)j);
+                if (LDS_TABLE) merged_add<MERGE>(s_tab, pair && in_lds, (unsigned)(i * L + j));
+                merged_add<MERGE>(g_tab, pair && !in_lds, mem_base + (unsigned)j);
             };
             if (do_axial) {
                 offset(1, 0, 0, s_axial, axial);
@@ -268,7 +209,7 @@ __global__ __launch_bounds__(256) void k_vtx_finish(const int2 *__restrict__ ran
         voxels = hist[(size_t)r * L + threadIdx.x];
         used = voxels != 0;
     }
-    all = wave_sum64(all); ax = wave_sum64(ax); used = wave_sum64(used); voxels = wave_sum64(voxels);
+    all = wave_sum(all); ax = wave_sum(ax); used = wave_sum(used); voxels = wave_sum(voxels);
     if ((threadIdx.x & 63) == 0) {
         s_sum[0][threadIdx.x >> 6] = all; s_sum[1][threadIdx.x >> 6] = ax; s_sum[2][threadIdx.x >> 6] = used; s_sum[3][threadIdx.x >> 6] = voxels;
     }

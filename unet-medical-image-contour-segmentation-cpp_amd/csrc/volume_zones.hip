@@ -1,6 +1,6 @@
 // volume_zones.hip -- per component of a labelled stack its grey-level run-length and size-zone matrices (include/mi_unet.h:
 // mi_unet_volume_zones), on the key stack that volume_texture.hip's launch_volume_texture_keys makes.  k_vzn_voxels: a
-// lane per voxel, a wave carries a component's count until the component changes (k_vol_stats' scheme).  k_vzn_runs, the hot path: a
+// lane per voxel, a wave carries a component's count until the component changes (wave.h's peel).  k_vzn_runs, the hot path: a
 // tile of keys with the halo of the backward neighbours in LDS; the lane whose backward neighbour has another key walks its run forward,
 // and the lanes of a wave that name one cell merge before the atomic.  k_vzn_init / k_vzn_merge: 7.9's lock-free union-find on keys.
 // k_vzn_sizes: a wave carries a root's count.  k_vzn_flags / k_vzn_scan / k_vzn_list: the roots in raster order at scanned positions;
@@ -12,45 +12,23 @@
 #include "cc_common.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "key_tile.h"
+#include "wave.h"
 
 namespace miunet {
 
 namespace vzn {
 
+using namespace wave;
+using namespace key_tile;
+
 constexpr unsigned WG = 256;                // lanes per workgroup
 constexpr int RUN = 16;                     // 64-voxel segments a wave of k_vzn_voxels / k_vzn_sizes carries a count over
 constexpr int GROUPS = 4;                   // distinct owners of a segment that are reduced across the wave; lanes beyond them add their own
 constexpr int MERGE = 3;                    // distinct cells of one offset that a wave merges; lanes beyond them add their own
-constexpr int TX = VTX_TX, TY = VTX_TY, TZ = VTX_TZ;                   // 7.15's tile
-constexpr int KX = TX + 2, KY = TY + 2, KZ = TZ + 1;                   // the tile with its halo: x - 1 .. x + 1, y - 1 .. y + 1, z - 1 .. z
+constexpr int KZ = TZ + 1;                  // key_tile.h's tile with the slice before it: z - 1 .. z
 constexpr int TILE_KEYS = KX * KY * KZ;
-constexpr int ROWS = TY * TZ;               // rows of 64 voxels in a tile, ROWS / 4 per wave
 constexpr int SCAN = 1024;                  // counts a workgroup of k_vzn_scan takes, four a lane
-static_assert(TX == 64, "a wave per row of the tile");
-static_assert(ROWS % 4 == 0, "the rows of a tile are shared out among four waves");
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ long long wave_sum64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// A word that only grows: a plain read that already shows a value at least as large makes the atomic unnecessary (a stale read is a
-// smaller one and costs an atomic, never a result).
-__device__ __forceinline__ void raise(int *word, int v)
-{
-    if (__builtin_nontemporal_load(word) < v) atomicMax(word, v);
-}
-
 // ---- keys of more components than launch_volume_texture_keys takes at once (m L^2 above 2^22 while m L R is not) -----------------------------
 // part: the ids of components first .. first + count - 1, renumbered from 1, every other voxel 0: what the launcher turns into keys.
 __global__ __launch_bounds__(256) void k_vzn_part(const int32_t *__restrict__ ids, unsigned dhw, int first, int count, int32_t *__restrict__ part)
@@ -82,44 +60,20 @@ __global__ __launch_bounds__(256) void k_vzn_voxels(const int32_t *__restrict__ 
         if (first + 64LL * sg >= (long long)dhw) break;         // (wave-uniform)
         const long long i = first + 64LL * sg + lane;
         int r = i < (long long)dhw ? keys[i] >> 8 : 0;
-        u64 todo = __ballot(r != 0);
-        for (int g = 0; g < GROUPS && todo; ++g) {              // (wave-uniform)
-            const int r0 = __shfl(r, __builtin_ctzll(todo), 64);
-            const bool mine = r == r0;
-            const u64 mm = __ballot(mine);
+        peel<GROUPS>(r, 0, [&](int r0, bool, u64 mm, int) {
             if (r0 != ar) {
                 flush();
                 ar = r0; cnt = 0;
             }
             cnt += __popcll(mm);
-            todo &= ~mm;
-            if (mine) r = 0;
-        }
+        });
         if (r) atomicAdd(&acc[r - 1].voxels, 1);                // a segment of many small components: the lane adds its own voxel
     }
     flush();
 }
 
 // ---- runs: the hot path -----------------------------------------------------------------------------------------------------------------
-// One count into `tab` (k_vtx_pairs' scheme): the wave merges the lanes that name the same cell, for the first MERGE distinct cells, into
-// one atomic each; the lanes left over add their own.
-__device__ __forceinline__ void count(uint32_t *tab, bool on, unsigned cell)
-{
-    u64 todo = __ballot(on);
-#pragma unroll
-    for (int g = 0; g < MERGE; ++g) {
-        if (!todo) break;                                       // (wave-uniform)
-        const int leader = __builtin_ctzll(todo);
-        const unsigned c0 = (unsigned)__shfl((int)cell, leader, 64);
-        const bool same = on && cell == c0;
-        const u64 mm = __ballot(same);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(tab + c0, (uint32_t)__popcll(mm));
-        todo &= ~mm;
-        if (same) on = false;
-    }
-    if (on) atomicAdd(tab + cell, 1u);
-}
-
+// Every count goes through wave.h's merged_add.
 // LDS: the keys of the tile with its halo; a position outside the volume holds 0, which ends every run.  A workgroup takes
 // VTX_TILES_PER_WG tiles that follow each other along x.  A run belongs to the tile of its first voxel, so every run is counted once.
 __global__ __launch_bounds__(256) void k_vzn_runs(const int32_t *__restrict__ keys, VolumeZonesArgs a, int want, int tiles_x, int tiles_y,
@@ -131,16 +85,10 @@ __global__ __launch_bounds__(256) void k_vzn_runs(const int32_t *__restrict__ ke
     const int L = a.L, R = a.R;
     const int t_end = min(n_tiles, ((int)blockIdx.x + 1) * VTX_TILES_PER_WG);
     for (int t = (int)blockIdx.x * VTX_TILES_PER_WG; t < t_end; ++t) {
-        const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, tz = t / (tiles_x * tiles_y);
-        const int x0 = tx * TX - 1, y0 = ty * TY - 1, z0 = tz * TZ - 1;
+        const int3 o = tile_origin<1>(t, tiles_x, tiles_y);
+        const int x0 = o.x, y0 = o.y, z0 = o.z;
         __syncthreads();                                        // the tile before is done with s_keys
-        for (int e = tid; e < TILE_KEYS; e += WG) {
-            const int lz = e / (KX * KY), rem = e - lz * (KX * KY), ly = rem / KX, lx = rem - ly * KX;
-            const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            int k = 0;
-            if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H && gz >= 0 && gz < a.D) k = keys[((size_t)gz * a.H + gy) * a.W + gx];
-            s_keys[e] = k;
-        }
+        load_key_tile<KZ, 1>(s_keys, keys, o, a.D, a.H, a.W);
         __syncthreads();
 #pragma unroll 1
         for (int it = 0; it < ROWS / 4; ++it) {
@@ -175,7 +123,7 @@ __global__ __launch_bounds__(256) void k_vzn_runs(const int32_t *__restrict__ ke
                     if (n > R) atomicAdd(inter_half ? &acc[id - 1].clamped_inter : &acc[id - 1].clamped_axial, 1ULL);
                     best = max(best, n);
                 }
-                count(tab, start, row_cell + (unsigned)(min(n, R) - 1));
+                merged_add<MERGE>(tab, start, row_cell + (unsigned)(min(n, R) - 1));
             };
             if (do_axial) {
                 offset(1, 0, 0, axial, false);
@@ -191,16 +139,10 @@ __global__ __launch_bounds__(256) void k_vzn_runs(const int32_t *__restrict__ ke
                 // the longest run: one atomic per wave and component for the first two components of the row, and only when a plain
                 // read does not already show it
                 int rid = best > 0 ? id : 0;
-                u64 todo = __ballot(rid != 0);
-                for (int g = 0; g < 2 && todo; ++g) {           // (wave-uniform)
-                    const int leader = __builtin_ctzll(todo);
-                    const int r0 = __shfl(rid, leader, 64);
-                    const bool mine = rid == r0;
+                peel<2>(rid, 0, [&](int r0, bool mine, u64, int leader) {
                     const int v = wave_max(mine ? best : 0);
                     if (lane == leader) raise(&acc[r0 - 1].longest, v);
-                    todo &= ~__ballot(mine);
-                    if (mine) rid = 0;
-                }
+                });
                 if (rid) raise(&acc[rid - 1].longest, best);
             }
         }
@@ -272,19 +214,13 @@ __global__ __launch_bounds__(256) void k_vzn_sizes(const int32_t *__restrict__ k
         const long long i = first + 64LL * sg + lane;
         int r = -1;
         if (i < (long long)dhw && keys[i] != 0) r = pp::find_root_ro(parent, (int)i);
-        u64 todo = __ballot(r >= 0);
-        for (int g = 0; g < GROUPS && todo; ++g) {              // (wave-uniform)
-            const int r0 = __shfl(r, __builtin_ctzll(todo), 64);
-            const bool mine = r == r0;
-            const u64 mm = __ballot(mine);
+        peel<GROUPS>(r, -1, [&](int r0, bool, u64 mm, int) {
             if (r0 != ar) {
                 flush();
                 ar = r0; cnt = 0;
             }
             cnt += __popcll(mm);
-            todo &= ~mm;
-            if (mine) r = -1;
-        }
+        });
         if (r >= 0) atomicAdd(size + r, 1);
     }
     flush();
@@ -300,10 +236,8 @@ __global__ __launch_bounds__(256) void k_vzn_flags(const int32_t *__restrict__ k
 {
     __shared__ int s_n[4];
     const unsigned i = blockIdx.x * WG + threadIdx.x;
-    const u64 mm = __ballot(is_root(keys, parent, i, dhw));
-    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(mm);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const int total = wave_offsets(__popcll(__ballot(is_root(keys, parent, i, dhw))), s_n).y;
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // scan: the exclusive prefix of SCAN counts per workgroup in place, four a lane; the workgroup's sum into sums[workgroup] (or, for the
@@ -311,7 +245,7 @@ __global__ __launch_bounds__(256) void k_vzn_flags(const int32_t *__restrict__ k
 __global__ __launch_bounds__(256) void k_vzn_scan(int *data, int n, int *sums, int *total)
 {
     __shared__ int s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int base = (int)blockIdx.x * SCAN + tid * 4;
     int v[4], s = 0;
 #pragma unroll
@@ -325,10 +259,7 @@ __global__ __launch_bounds__(256) void k_vzn_scan(int *data, int n, int *sums, i
         const int u = __shfl_up(inc, o, 64);
         if (lane >= o) inc += u;
     }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int off = inc - s;
-    for (int w = 0; w < wave; ++w) off += s_w[w];
+    int off = wave_offsets(__shfl(inc, 63, 64), s_w).x + inc - s;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (base + j < n) data[base + j] = off;
@@ -347,19 +278,15 @@ __global__ __launch_bounds__(256) void k_vzn_list(const int32_t *__restrict__ ke
 {
     __shared__ int s_n[4];
     const unsigned i = blockIdx.x * WG + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool root = is_root(keys, parent, i, dhw);
     const u64 mm = __ballot(root);
-    if (lane == 0) s_n[wave] = __popcll(mm);
-    __syncthreads();
-    int pos = counts[blockIdx.x] + sums[blockIdx.x / SCAN] + __popcll(mm & ((1ULL << lane) - 1ULL));
-    for (int w = 0; w < wave; ++w) pos += s_n[w];
+    const int pos = counts[blockIdx.x] + sums[blockIdx.x / SCAN] + wave_offsets(__popcll(mm), s_n).x + __popcll(mm & lanes_below());
     const int k = root ? keys[i] : 0, r = (k >> 8) - 1, sz = root ? size[i] : 0;
     if (root && pos < keep) zones[pos] = mi_unet_vzone{ (int32_t)i, r, k & 255, sz };
 }
 
 // tally: acc[r].zones and acc[r].largest from every root.  A wave carries a component's count and maximum over consecutive voxels
-// (k_vzn_voxels' scheme): in noise a large component has a root in nearly every voxel, and one atomic per root on its two words would
+// (as k_vzn_voxels does): in noise a large component has a root in nearly every voxel, and one atomic per root on its two words would
 // be served one after another.
 __global__ __launch_bounds__(256) void k_vzn_tally(const int32_t *__restrict__ keys, unsigned dhw, const int *__restrict__ parent,
                                                    const int *__restrict__ size, VznAcc *acc)
@@ -381,20 +308,14 @@ __global__ __launch_bounds__(256) void k_vzn_tally(const int32_t *__restrict__ k
             r = keys[i] >> 8;
             sz = size[i];
         }
-        u64 todo = __ballot(r != 0);
-        for (int g = 0; g < GROUPS && todo; ++g) {              // (wave-uniform)
-            const int r0 = __shfl(r, __builtin_ctzll(todo), 64);
-            const bool mine = r == r0;
-            const u64 mm = __ballot(mine);
+        peel<GROUPS>(r, 0, [&](int r0, bool mine, u64 mm, int) {
             if (r0 != ar) {
                 flush();
                 ar = r0; cnt = 0; big = 0;
             }
             cnt += __popcll(mm);
             big = max(big, wave_max(mine ? sz : 0));
-            todo &= ~mm;
-            if (mine) r = 0;
-        }
+        });
         if (r) {                                                // a segment of many small components: the lane adds its own root
             atomicAdd(&acc[r - 1].zones, 1);
             raise(&acc[r - 1].largest, sz);
@@ -421,7 +342,7 @@ __global__ __launch_bounds__(256) void k_vzn_finish(const int2 *__restrict__ ran
                 all += v;
             }
         }
-    all = wave_sum64(all); ax = wave_sum64(ax);
+    all = wave_sum(all); ax = wave_sum(ax);
     if ((threadIdx.x & 63) == 0) {
         s_sum[0][threadIdx.x >> 6] = all; s_sum[1][threadIdx.x >> 6] = ax;
     }
