@@ -4,7 +4,7 @@ mi_unet_create takes 2..6 classes and the class count steers code written separa
 instances of head_argmax_kernel and its lane groups (Cin / 4 = 4 .. 64 lanes per pixel), the fused heads of conv_wino4.hip,
 conv_wino4s.hip, conv_lp.hip (sized for 4 classes) and conv_lpr.hip (sized for 3, guarded by routing.cpp), the plan's
 `classes <= 4` fusion rule, the plane strides of the tiled stitch and blend, and the logits offsets of every micro-batch, rank
-and captured image.  The inputs (six small nets, balanced head biases so that every class wins somewhere) are defined and
+and captured image.  The inputs (seven small nets, balanced head biases so that every class wins somewhere) are defined and
 proven fit by the oracle alone in test_classes_cpu.py.
 
 Tolerances, all the project's own:
@@ -77,15 +77,16 @@ def _rows():
 
     # fp32 stand-alone: all five instances of head_argmax_kernel, lane groups 4 (C), 8 (B, D), 16 (A), 32 (E), 64 (F)
     add("standalone", "direct", {"MIUNET_FUSE_HEAD": "0"}, "ABCDEF", CLASSES, lambda k: "head_argmax")
-    # fp32 F(4x4,3x3): the persistent one-block kernel and the staged one; the plan fuses the head up to 4 classes
-    add("wino4", "auto", {"MIUNET_WINO4_MIN_WG": "1", "MIUNET_WINO4S": "0"}, "A", CLASSES,
+    # fp32 F(4x4,3x3): the persistent one-block kernel and the staged one; the plan fuses the head up to 4 classes.  Net G
+    # (22 x 38) puts the image edge inside the head's tile on both sides; A never does
+    add("wino4", "auto", {"MIUNET_WINO4_MIN_WG": "1", "MIUNET_WINO4S": "0"}, "AG", CLASSES,
         lambda k: "conv3x3_wino4+head" if k <= 4 else "head_argmax")
-    add("wino4s", "auto", {"MIUNET_WINO4_MIN_WG": "1", "MIUNET_WINO4S": "2"}, "A", CLASSES,
+    add("wino4s", "auto", {"MIUNET_WINO4_MIN_WG": "1", "MIUNET_WINO4S": "2"}, "AG", CLASSES,
         lambda k: "conv3x3_wino4s+head" if k <= 4 else "head_argmax")
     for algo in ("bf16", "fp16"):
         name = _fused_name(algo)
         # conv_lp.hip, 64-wide tile (base 64)
-        add(f"{algo}-tile64", algo, {}, "A", CLASSES, lambda k, name=name: name + "+head" if k <= 4 else "head_argmax")
+        add(f"{algo}-tile64", algo, {}, "AG", CLASSES, lambda k, name=name: name + "+head" if k <= 4 else "head_argmax")
         # conv_lp.hip, 32-wide tile (base 32; base 16: Cout = 16 < tile, masked columns)
         add(f"{algo}-tile32", algo, {"MIUNET_LPR": "0"}, "BCD", (2, 3, 4), lambda k, name=name: name + "+head")
         # conv_lpr.hip (resident weights): its fused head is sized for three classes; conv3x3_lpr_shape_ok refuses four, which

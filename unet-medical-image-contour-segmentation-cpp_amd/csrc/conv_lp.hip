@@ -24,8 +24,6 @@ namespace miunet {
 //     (the MFMAs are volatile asms: the software pipeline is written out) -- the kernel is bound by its staging and LDS traffic
 //     and by HBM, not by the matrix pipe.
 // The same kernel serves fp16 operands (BASELINE config 5's arithmetic): T = __bf16 or _Float16, 16 bits either way.
-template <typename T> struct LpVec { typedef T x8 __attribute__((ext_vector_type(8))); };
-
 
 // OUT_LP: the output tensor (and the pooled one) is 16-bit like the input; false = fp32 output (the layer in front of the head)
 // HEAD: the layer feeds the network's fp32 1x1 head + argmax (ConvArgs::head_w): the post-ReLU fp32 tile crosses LDS instead
@@ -34,10 +32,10 @@ template <typename T, int TAPS, int TH, int BN, bool NFAST, bool OUT_LP, bool HE
 __global__ __launch_bounds__(256, 2) void conv_mfma_bf16(const ConvArgs a, const int tiles_x, const int tiles_y,
                                                          const int m_tiles, const int nwg)
 {
-    typedef typename LpVec<T>::x8 bf16x8;
+    typedef typename LprVec<T>::x8 bf16x8;
     static_assert(BN == 32 || BN % 64 == 0, "n-tile of 32 (narrow layers: base 32) or a multiple of 64 output channels");
     constexpr int ROW = KC_BF16;                         // 16-bit elements per LDS row (64 bytes, pieces permuted)
-    constexpr int HEAD_ROW = BN + 4;                     // floats per pixel of the fused head's LDS tile
+    constexpr int HEAD_ROW = head_row(BN);               // floats per pixel of the fused head's LDS tile (fused_head_tile, kernel_common.h)
     constexpr int HALO = (TAPS == 9) ? 1 : 0;
     constexpr int PW = 32 + 2 * HALO, PH = TH + 2 * HALO, NPIX = PW * PH;
     constexpr int NA8 = NPIX * (KC_BF16 / 8);            // 8-channel pieces of the A patch
@@ -289,35 +287,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_bf16(const ConvArgs a, const
     }
     if constexpr (HEAD) {
         static_assert(TAPS == 9 && TH * 32 == 256 && (BN == 64 || BN == 32) && !OUT_LP, "one pixel per thread, every channel in the workgroup");
-        float *const Wh = lds + 256 * HEAD_ROW;            // [classes][BN]
-        if (tid < a.head_classes * BN) Wh[tid] = (tid % BN) < a.Cout ? a.head_w[(tid / BN) * a.Cout + (tid % BN)] : 0.f;
-        __syncthreads();
-        f32x4 d4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d4[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-        const float *yrow = lds + tid * HEAD_ROW;
-#pragma unroll
-        for (int c4 = 0; c4 < BN / 4; ++c4) {
-            const f32x4 yv = *reinterpret_cast<const f32x4 *>(yrow + 4 * c4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < a.head_classes) d4[k] += yv * *reinterpret_cast<const f32x4 *>(Wh + BN * k + 4 * c4);
-        }
-        const int py = y0 + (tid >> 5), px = x0 + (tid & 31);
-        if (py < a.H && px < a.W) {
-            const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
-            float best = -3.402823466e+38f;
-            int idx = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k < a.head_classes) {
-                    const float d = ((d4[k].x + d4[k].y) + (d4[k].z + d4[k].w)) + a.head_b[k];
-                    if (a.head_logits != nullptr) a.head_logits[((size_t)b * a.head_classes + k) * hw + pin] = d;
-                    if (d > best) { best = d; idx = k; }          // first maximum wins (src/process.cpp:158-170)
-                }
-            }
-            a.head_labels[(size_t)b * hw + pin] = (uint8_t)idx;
-        }
+        fused_head_tile<BN, 32>(a, lds, tid, b, y0, x0);
     }
 }
 
@@ -331,7 +301,7 @@ static hipError_t launch_bf16_cfg(const ConvArgs &a, hipStream_t s)
     const int nwg = m_tiles * n_tiles;
     constexpr int HALO = (TAPS == 9) ? 1 : 0;
     constexpr size_t lds_stage = 2 * (size_t)KC_BF16 * ((32 + 2 * HALO) * (TH + 2 * HALO) + TAPS * BN);
-    constexpr size_t lds_head = HEAD ? sizeof(float) * (256 * (size_t)(BN + 4) + 4 * BN) : 0;     // [256 px][BN + 4] + [4 classes][BN]
+    constexpr size_t lds_head = HEAD ? head_lds_bytes(BN) : 0;     // [256 px][BN + 4] + [4 classes][BN]
     constexpr size_t lds = lds_stage > lds_head ? lds_stage : lds_head;
     auto kern = conv_mfma_bf16<T, TAPS, TH, BN, NFAST, OUT_LP, HEAD>;
     if (hipError_t e = ensure_dynamic_lds(kern, lds); e != hipSuccess) return e;

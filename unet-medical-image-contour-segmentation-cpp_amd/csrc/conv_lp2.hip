@@ -60,8 +60,6 @@
 
 namespace miunet {
 
-template <typename T> struct Lp2Vec { typedef T x8 __attribute__((ext_vector_type(8))); };
-
 struct LP2 {
     static constexpr int TH = LP2_TILE_ROWS, MT = 4;
     static constexpr int ROW = KC_BF16;                      // 16-bit elements per pixel (64 bytes, unpadded: pieces are swizzled)
@@ -73,12 +71,13 @@ struct LP2 {
 
 // In-place accumulation through inline asm (lpr_common.h): "+a" pins each block to its own AGPR quad.  Hazards: no accumulator
 // is touched again for 32 MFMAs inside the loop, and a wait plus a barrier separate the last MFMA from the epilogue's first
-// accumulator read.
-__device__ __forceinline__ void mfma_lp2s(f32x4 &c, Lp2Vec<__bf16>::x8 a, Lp2Vec<__bf16>::x8 b)
+// accumulator read.  The same instructions as mfma16_lpr (lpr_common.h); what differs is the accumulator's constraint: "+a" here,
+// "+v" there -- these kernels keep all 64 blocks of a wave in AGPRs, the others' accumulators live among their VGPRs.
+__device__ __forceinline__ void mfma_lp2s(f32x4 &c, LprVec<__bf16>::x8 a, LprVec<__bf16>::x8 b)
 {
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void mfma_lp2s(f32x4 &c, Lp2Vec<_Float16>::x8 a, Lp2Vec<_Float16>::x8 b)
+__device__ __forceinline__ void mfma_lp2s(f32x4 &c, LprVec<_Float16>::x8 a, LprVec<_Float16>::x8 b)
 {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
@@ -90,7 +89,7 @@ template <typename T, bool OUT_LP, int EXP = 0, int WD = 6>
 __global__ __launch_bounds__(256, 1) void conv3x3_lp2(const ConvArgs a, const int tiles_x, const int tiles_y,
                                                        const int m_tiles, const int nwg)
 {
-    typedef typename Lp2Vec<T>::x8 x8;
+    typedef typename LprVec<T>::x8 x8;
     constexpr int ROW = LP2::ROW, PW = LP2::PW, MT = LP2::MT, BN = 128, TH = LP2::TH;
     constexpr int MB = 2 * MT, NB = BN / 16;                 // 8 pixel blocks x 8 channel blocks per wave; WD = weight ring depth in groups
     static_assert(18 % WD == 0, "the ring depth must divide the groups of a chunk");
@@ -338,7 +337,7 @@ template <typename T, int AD = 8>
 __global__ __launch_bounds__(256, 1) void conv3x3_lp2n(const ConvArgs a, const int tiles_x, const int tiles_y,
                                                         const int m_tiles, const int nwg)
 {
-    typedef typename Lp2Vec<T>::x8 x8;
+    typedef typename LprVec<T>::x8 x8;
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     constexpr int ROW = LP2::ROW, PW = LP2::PW, BN = 128, TH = LP2::TH, TROW = 40;
     constexpr int MB = 2 * TH, WT = 9;                       // 32 pixel blocks (row m >> 1, column half m & 1); weight ring in taps; AD = patch-fragment ring

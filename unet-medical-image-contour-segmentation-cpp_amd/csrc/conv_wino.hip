@@ -35,6 +35,41 @@ struct WinoGeom {
     static constexpr size_t LDS_BYTES = sizeof(float) * (2 * VBUF + RAW_FLOATS);
 };
 
+// The tile finish of both kernels below, per (2x2 tile, channel) of a lane: Y = A^T M A from the tile's 16 positions
+// (m[p], p = 4 xi + nu) ...
+static __device__ inline void wino_tile_y(const float (&m)[16], float (&y)[2][2])
+{
+    float s0[4], s1[4];
+#pragma unroll
+    for (int nu = 0; nu < 4; ++nu) {
+        const float m0 = m[0 + nu], m1 = m[4 + nu], m2 = m[8 + nu], m3 = m[12 + nu];
+        s0[nu] = m0 + m1 + m2;
+        s1[nu] = m1 - m2 - m3;
+    }
+    y[0][0] = s0[0] + s0[1] + s0[2]; y[0][1] = s0[1] - s0[2] - s0[3];
+    y[1][0] = s1[0] + s1[1] + s1[2]; y[1][1] = s1[1] - s1[2] - s1[3];
+}
+// ... then + shift, ReLU, the guarded stores of the tile at (oy, ox) of image b, channel ncol, and its pooled maximum (the
+// lane's 2x2 tile IS one pooling window).  (ConvArgs by value, as the kernels hold it: through a reference hipcc schedules the
+// stores differently, 11 - 32 instructions more per kernel.)
+static __device__ inline void wino_tile_store(const ConvArgs a, const float (&y)[2][2], const float sh, const bool n_ok, const int b,
+                                              const int oy, const int ox, const int ncol)
+{
+    float vmax = -3.402823466e+38f;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            float v = y[dy][dx] + sh;
+            if (a.relu) v = v > 0.f ? v : 0.f;
+            vmax = fmaxf(vmax, v);
+            if (n_ok && oy + dy < a.H && ox + dx < a.W)
+                a.out[(((size_t)b * a.H + oy + dy) * a.W + ox + dx) * a.ldo + a.co_off + ncol] = v;
+        }
+    if (a.pool_out != nullptr && n_ok && oy + 1 < a.H && ox + 1 < a.W)
+        a.pool_out[(((size_t)b * (a.H >> 1) + (oy >> 1)) * (a.W >> 1) + (ox >> 1)) * a.pool_ld + ncol] = vmax;
+}
+
 // SPLITK = false compiles the split-K paths out entirely (the full-K kernel's register allocation and schedule are
 // exactly those of a kernel without them: measured, a runtime ksplit == 1 path costs 4 % at batch 16).
 template <int WM, int WN, bool SPLITK>
@@ -239,18 +274,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a, con
     const float sh = n_ok ? a.bias[ncol] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
+        float m[16], y[2][2];
+#pragma unroll
+        for (int p = 0; p < 16; ++p) m[p] = acc[p][r];
+        wino_tile_y(m, y);                    // (ahead of the tile's coordinates: behind them, the split-K kernels spill a register)
         const int i = (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int oy = by0 + 2 * ((i >> 3) + 4 * wm), ox = bx0 + 2 * (i & 7);
-        float s0[4], s1[4];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            const float m0 = acc[0 + nu][r], m1 = acc[4 + nu][r], m2 = acc[8 + nu][r], m3 = acc[12 + nu][r];
-            s0[nu] = m0 + m1 + m2;
-            s1[nu] = m1 - m2 - m3;
-        }
-        float y[2][2];
-        y[0][0] = s0[0] + s0[1] + s0[2]; y[0][1] = s0[1] - s0[2] - s0[3];
-        y[1][0] = s1[0] + s1[1] + s1[2]; y[1][1] = s1[1] - s1[2] - s1[3];
         if constexpr (SPLITK) {               // partial sums of this K slice: the reduce kernel finishes the layer
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy)
@@ -260,19 +289,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a, con
                         a.ksplit_ws[((((size_t)ks * a.B + b) * a.H + oy + dy) * a.W + ox + dx) * a.Cout + ncol] = y[dy][dx];
             continue;
         }
-        float vmax = -3.402823466e+38f;
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                float v = y[dy][dx] + sh;
-                if (a.relu) v = v > 0.f ? v : 0.f;
-                vmax = fmaxf(vmax, v);
-                if (n_ok && oy + dy < a.H && ox + dx < a.W)
-                    a.out[(((size_t)b * a.H + oy + dy) * a.W + ox + dx) * a.ldo + a.co_off + ncol] = v;
-            }
-        if (a.pool_out != nullptr && n_ok && oy + 1 < a.H && ox + 1 < a.W)    // the lane's 2x2 tile IS one pooling window
-            a.pool_out[(((size_t)b * (a.H >> 1) + (oy >> 1)) * (a.W >> 1) + (ox >> 1)) * a.pool_ld + ncol] = vmax;
+        wino_tile_store(a, y, sh, n_ok, b, oy, ox, ncol);
     }
 }
 
@@ -450,29 +467,11 @@ __global__ __launch_bounds__(W16_THREADS, 2) void conv3x3_wino16_f32(const ConvA
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * mb + 4 * kq + r;
             const int oy = by0 + 2 * ((i >> 3) + 4 * wm), ox = bx0 + 2 * (i & 7);
-            float s0[4], s1[4];
+            float m[16], y[2][2];
 #pragma unroll
-            for (int nu = 0; nu < 4; ++nu) {
-                const float m0 = acc[0 + nu][mb][r], m1 = acc[4 + nu][mb][r], m2 = acc[8 + nu][mb][r], m3 = acc[12 + nu][mb][r];
-                s0[nu] = m0 + m1 + m2;
-                s1[nu] = m1 - m2 - m3;
-            }
-            float y[2][2];
-            y[0][0] = s0[0] + s0[1] + s0[2]; y[0][1] = s0[1] - s0[2] - s0[3];
-            y[1][0] = s1[0] + s1[1] + s1[2]; y[1][1] = s1[1] - s1[2] - s1[3];
-            float vmax = -3.402823466e+38f;
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    float v = y[dy][dx] + sh;
-                    if (a.relu) v = v > 0.f ? v : 0.f;
-                    vmax = fmaxf(vmax, v);
-                    if (n_ok && oy + dy < a.H && ox + dx < a.W)
-                        a.out[(((size_t)b * a.H + oy + dy) * a.W + ox + dx) * a.ldo + a.co_off + ncol] = v;
-                }
-            if (a.pool_out != nullptr && n_ok && oy + 1 < a.H && ox + 1 < a.W)
-                a.pool_out[(((size_t)b * (a.H >> 1) + (oy >> 1)) * (a.W >> 1) + (ox >> 1)) * a.pool_ld + ncol] = vmax;
+            for (int p = 0; p < 16; ++p) m[p] = acc[p][mb][r];
+            wino_tile_y(m, y);
+            wino_tile_store(a, y, sh, n_ok, b, oy, ox, ncol);
         }
 }
 

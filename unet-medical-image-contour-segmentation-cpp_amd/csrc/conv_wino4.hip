@@ -1,6 +1,5 @@
 // conv_wino4.hip -- Winograd F(4x4,3x3) convolution on the fp32 MFMA (v_mfma_f32_16x16x4_f32), gfx950 only.
 #include <cstdlib>
-#include <type_traits>
 
 #include "kernel_common.h"
 #include "wino4_common.h"
@@ -61,7 +60,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
                                                             const int m_tiles, const int nwg)
 {
     constexpr int VROW = W4::VROW, VPOS = W4::VPOS, VBUF = W4::VBUF;
-    constexpr int HEAD_ROW = 64 + 4;          // floats per pixel of the head's LDS tile (conflict-free b128 rows)
     static_assert(!HEAD || NB == 1, "the fused head needs every channel of a pixel in one workgroup");
     constexpr int UD = NB == 1 ? 9 : W4_UD2;  // U prefetch distance in positions (36 % UD == 0); the one-block variant has registers to spare
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -101,34 +99,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
         int ln = lane;
         if constexpr (NB == 2 && EXP == 5) asm volatile("" : "+v"(ln));
 #pragma unroll
-        for (int s = 0; s < W4::RAW_ITERS; ++s) {
-            const int g = (wave + 4 * s) * 16 + (ln >> 2);                    // linear slot of this lane in load wave + 4s
-            const int py = g / W4::RAW_ROW, sl = g - py * W4::RAW_ROW;
-            const int px = 4 * (sl % 5) + sl / 5;
-            const int gy = by0 - 1 + py, gx = bx0 - 1 + px;
-            const bool inb = g < W4::RAW_SLOTS && px < 18 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            raw_voff[s] = inb ? (unsigned)(((gy * a.W + gx) * a.ldc + 4 * (ln & 3)) * 4) : 0xFFFFFFFFu;
-        }
+        for (int s = 0; s < W4::RAW_ITERS; ++s) raw_voff[s] = w4_raw_slot(a, by0, bx0, wave + 4 * s, ln).voff;
     };
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    auto raw_dma_one = [&](int chunk, int buf, int s) {        // the wave's s-th load of a chunk's patch
-        const int c0 = chunk * WINO4_KC;
-        const bool c_ok = c0 + 4 * (lane & 3) < a.Cin;
-        if (wave + 4 * s < W4::RAW_LOADS)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, (lds_ptr)(Raw + buf * W4::RAW_FLOATS + (wave + 4 * s) * 16 * WINO4_KC), 16,
-                                                     c_ok ? raw_voff[s] : 0xFFFFFFFFu, c0 * 4, 0, 0);
+    auto dma_one = [&](int chunk, int buf, int s) {            // the wave's s-th load (load wave + 4s) of a chunk's patch
+        raw_dma_one(in_rsrc, Raw + buf * W4::RAW_FLOATS, chunk, wave + 4 * s, raw_voff[s], raw_chunk_ok(a.Cin, chunk, lane));
     };
-    auto raw_dma = [&](int chunk, int buf) {   // global -> LDS directly: no registers, no ds_write; completion = vmcnt
-        const int c0 = chunk * WINO4_KC;
-        const bool c_ok = c0 + 4 * (lane & 3) < a.Cin;
+    auto raw_dma = [&](int chunk, int buf) {   // the wave's whole share at once
+        const bool c_ok = raw_chunk_ok(a.Cin, chunk, lane);
 #pragma unroll
-        for (int s = 0; s < W4::RAW_ITERS; ++s)
-            if (wave + 4 * s < W4::RAW_LOADS)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, (lds_ptr)(Raw + buf * W4::RAW_FLOATS + (wave + 4 * s) * 16 * WINO4_KC), 16,
-                                                         c_ok ? raw_voff[s] : 0xFFFFFFFFu, c0 * 4, 0, 0);
+        for (int s = 0; s < W4::RAW_ITERS; ++s) raw_dma_one(in_rsrc, Raw + buf * W4::RAW_FLOATS, chunk, wave + 4 * s, raw_voff[s], c_ok);
     };
 
-    // ---- stage 2: V = B^T d B for one 16-channel chunk; lane = (tile, channel quad), wave = row group of B^T:
+    // ---- stage 2: V = B^T d B for one 16-channel chunk; lane = (tile, channel quad), wave = row group of B^T.  These pieces are
+    // the steps of wino4_common.h (w4_role, w4_col_load, w4_col, w4_row_prep, w4_row_out), which conv_wino4s.hip calls, WRITTEN OUT:
+    // built from those calls the two-block kernel's layers measured 0.5 - 1.1 % slower than the parent's, outside its run-to-run
+    // spread (EXPERIMENTS R5.20).  A change to the transform is made there AND here.
     //   wave 0: xi 1, 2 = (d4 - 4 d2) +- (d3 - 4 d1)        wave 1: xi 3, 4 = (d4 - d2) +- (2 d3 - 2 d1)
     //   wave 2: xi 0    = 4 d0 - 5 d2 + d4                  wave 3: xi 5    = 4 d1 - 5 d3 + d5
     const int wrole = EXP == 1 ? 2 : EXP == 2 ? 0 : wave;      // the transform role this wave plays
@@ -201,12 +186,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
     // ---- MFMA role: wave w, channels n0 + 16 NB w .. (NB 16-column blocks), all 36 positions
     const unsigned u_pos_bytes = (unsigned)a.CoutPad * WINO4_KC * 4;
     const int all_chunks = (a.Cin + WINO4_KC - 1) / WINO4_KC;
-    const __amdgpu_buffer_rsrc_t u_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wpk4), 0, (int)(all_chunks * 36 * u_pos_bytes), 0x00020000);
-    auto u_load = [&](int chunk, int p, int blk) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, u_voff + blk * 16 * WINO4_KC * 4,
-                                                                              (chunk * 36 + p) * u_pos_bytes, 0));
-    };
+    const __amdgpu_buffer_rsrc_t u_rsrc = w4_u_rsrc(a);
+    auto u_load = [&](int chunk, int p, int blk) { return w4_u_load(u_rsrc, u_voff + blk * 16 * WINO4_KC * 4, u_pos_bytes, chunk, p); };
     const float *const v_rd = Vs + j16 * VROW + 4 * (kq ^ v_swz(j16));                       // + buf*VBUF + pos*VPOS
 
     int c_begin = 0, nchunks = all_chunks;    // this workgroup's K range [c_begin, nchunks)
@@ -215,8 +196,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
     const int Hp = a.H >> 1, Wp = a.W >> 1;
     const bool do_pool = !SPLITK && a.pool_out != nullptr;
     const int ld_e = SPLITK ? a.Cout : a.ldo, co_e = SPLITK ? 0 : a.co_off;
-    const unsigned pix_bytes = (unsigned)ld_e * 4, row_bytes = (unsigned)a.W * pix_bytes;
-    const unsigned ppix_bytes = (unsigned)a.pool_ld * 4, prow_bytes = (unsigned)Wp * ppix_bytes;
     f32x4 u[UD][NB];
     // the loads that open a tile: the raw patches of chunks 0 and 1 straight into LDS, then the U ring
     auto open_tile = [&]() {
@@ -264,8 +243,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
     for (int p = 0; p < 36; ++p)
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk) {
-            // position (xi, nu) = (1, 1) starts at the shift: A^T e_1 e_1^T A is the all-ones tile, so the bias add is free
-            const float init = (!SPLITK && p == 7 && ncol0 + 16 * blk < a.Cout) ? a.bias[ncol0 + 16 * blk] : 0.f;
+            const float init = SPLITK ? 0.f : w4_acc_init(a, p, ncol0 + 16 * blk);     // (split-K: the shift belongs to the reduce kernel)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[p][blk][r] = init;
         }
@@ -302,7 +280,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
             if (p + 1 < 36) avn = *reinterpret_cast<const f32x4 *>(vb + (p + 1) * VPOS);   // V fragment one position ahead
             // one load every fourth position, not a burst: 16 line misses at a time keep the VMEM queue moving, so the U loads
             // issued behind each of them are delayed by less than the U ring covers
-            if (p % 4 == 0 && p / 4 < W4::RAW_ITERS) raw_dma_one(chunk + 2, par, p / 4);
+            if (p % 4 == 0 && p / 4 < W4::RAW_ITERS) dma_one(chunk + 2, par, p / 4);
             if (EXP != 3 && p == 2) piece_load(0, rbuf);
             __builtin_amdgcn_sched_barrier(0);        // ... issued BEFORE this position's MFMAs (hipcc would sink them to their use)
             f32x4 bv[NB];
@@ -341,11 +319,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
         __syncthreads();
     }
 
-    // ---- epilogue: Y = A^T M A in-lane on all four tiles of a lane at once (the accumulator's four registers = tile
-    // columns r = 0..3 of tile row kq, lane = channel), ReLU, 4x4 stores (+ the 2x2 pooled maxima).  The shift was the
-    // initial value of position (1,1), whose inverse transform is the all-ones tile.  Stores are buffer stores on a
-    // per-image descriptor: one per-lane byte offset for the whole tile row, the pixel displacement in the scalar offset;
-    // pixels past the image edge and masked channels get voffset 0xFFFFFFFF, which the range check drops.
+    // ---- epilogue (w4_epilogue, wino4_common.h): inverse transform in-lane, ReLU, stores, pooled maxima or the head's tile
     if constexpr (EXP == 4) {
         f32x4 sum = f32x4{ 0.f, 0.f, 0.f, 0.f };
 #pragma unroll
@@ -367,128 +341,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
         a.H * a.W * ld_e * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t pool_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         do_pool ? a.pool_out + (size_t)e_b * Hp * Wp * a.pool_ld : a.out, 0, do_pool ? Hp * Wp * a.pool_ld * 4 : 0, 0x00020000);
-    const int oy = e_by0 + 4 * kq;
-    auto epilogue = [&](auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int blk = 0; blk < NB; ++blk) {
-            const int ncol = e_ncol0 + 16 * blk;
-            const bool n_ok = ncol < a.Cout;
-            const unsigned vbase = n_ok ? (unsigned)((oy * a.W + e_bx0) * ld_e + co_e + ncol) * 4 : 0xFFFFFFFFu;
-            const unsigned pbase = n_ok ? (unsigned)(((oy >> 1) * Wp + (e_bx0 >> 1)) * a.pool_ld + ncol) * 4 : 0xFFFFFFFFu;
-            unsigned vcol[4][4], pcol[4][2];          // edge workgroups: per-column offsets (dead columns -> dropped stores)
-            if constexpr (!INTERIOR) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) vcol[r][k] = e_bx0 + 4 * r + k < a.W ? vbase : 0xFFFFFFFFu;
-                    pcol[r][0] = e_bx0 + 4 * r + 1 < a.W ? pbase : 0xFFFFFFFFu;
-                    pcol[r][1] = e_bx0 + 4 * r + 3 < a.W ? pbase : 0xFFFFFFFFu;
-                }
-            }
-            // two tile columns (r = 2 h2, 2 h2 + 1) at a time: the same packed instructions as four at once, half the live
-            // temporaries (the epilogue runs with every accumulator still resident)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                auto half = [&](const f32x4 &v) { return h2 ? v.hi : v.lo; };
-                f32x2 t[4][6];
-#pragma unroll
-                for (int nu = 0; nu < 6; ++nu) {
-                    const f32x2 m0 = half(acc[nu][blk]), m1 = half(acc[6 + nu][blk]), m2 = half(acc[12 + nu][blk]),
-                                m3 = half(acc[18 + nu][blk]), m4 = half(acc[24 + nu][blk]), m5 = half(acc[30 + nu][blk]);
-                    const f32x2 s12 = m1 + m2, d12 = pk_sub2(m1, m2), s34 = m3 + m4, d34 = pk_sub2(m3, m4);
-                    t[0][nu] = m0 + s12 + s34;
-                    t[1][nu] = d12 + 2.f * d34;
-                    t[2][nu] = s12 + 4.f * s34;
-                    t[3][nu] = d12 + 8.f * d34 + m5;
-                }
-                f32x2 carry0, carry1;                 // horizontal maxima of the even row, for the 2x2 pooling
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x2 s12 = t[i][1] + t[i][2], d12 = pk_sub2(t[i][1], t[i][2]), s34 = t[i][3] + t[i][4], d34 = pk_sub2(t[i][3], t[i][4]);
-                    f32x2 y[4];
-                    y[0] = t[i][0] + s12 + s34;
-                    y[1] = d12 + 2.f * d34;
-                    y[2] = s12 + 4.f * s34;
-                    y[3] = d12 + 8.f * d34 + t[i][5];
-                    const bool row_ok = INTERIOR || oy + i < a.H;      // per-lane (kq) row predicate of an edge workgroup
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-#pragma unroll
-                        for (int rr = 0; rr < 2; ++rr) {
-                            const int r = 2 * h2 + rr;
-                            const float v = fmaxf(y[k][rr], relu_lo);
-                            y[k][rr] = v;
-                            if constexpr (HEAD) {     // pixel (4 kq + i, 4 r + k) of the 16x16 block, channel ncol -> LDS
-                                lds[((4 * kq + i) * 16 + 4 * r + k) * HEAD_ROW + ncol] = v;
-                                continue;
-                            }
-                            unsigned voff = vbase;
-                            if constexpr (!INTERIOR) voff = row_ok ? vcol[r][k] : 0xFFFFFFFFu;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, voff,
-                                                                  i * row_bytes + (4 * r + k) * pix_bytes, 0);
-                        }
-                    if (!HEAD && do_pool) {
-                        f32x2 hm0, hm1;               // horizontal maxima of this row: pooled columns 2r and 2r + 1
-#pragma unroll
-                        for (int rr = 0; rr < 2; ++rr) { hm0[rr] = fmaxf(y[0][rr], y[1][rr]); hm1[rr] = fmaxf(y[2][rr], y[3][rr]); }
-                        if ((i & 1) == 0) { carry0 = hm0; carry1 = hm1; }
-                        else {
-#pragma unroll
-                            for (int rr = 0; rr < 2; ++rr) {
-                                const int r = 2 * h2 + rr;
-                                const float p0 = fmaxf(hm0[rr], carry0[rr]), p1 = fmaxf(hm1[rr], carry1[rr]);
-                                unsigned v0 = pbase, v1 = pbase;
-                                if constexpr (!INTERIOR) { v0 = row_ok ? pcol[r][0] : 0xFFFFFFFFu; v1 = row_ok ? pcol[r][1] : 0xFFFFFFFFu; }
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0), pool_rsrc, v0,
-                                                                      (i >> 1) * prow_bytes + (2 * r) * ppix_bytes, 0);
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1), pool_rsrc, v1,
-                                                                      (i >> 1) * prow_bytes + (2 * r + 1) * ppix_bytes, 0);
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    };
-    if (HEAD || (e_by0 + 16 <= a.H && e_bx0 + 16 <= a.W)) epilogue(std::true_type{});   // workgroup-uniform: no per-pixel predicates
-    else epilogue(std::false_type{});
-    if constexpr (HEAD) {
-        // 1x1 head + argmax on the tile: the four waves hold 16 channels each, so the tile crossed LDS above
-        // ([256 pixels][64 + 4 pad], in the V region, which is dead until the next tile's first transform -- behind the
-        // next prologue's barrier); thread = pixel, a fixed summation order, first-max-wins argmax (src/process.cpp:158-170).
-        float *const Wh = lds + 256 * HEAD_ROW;            // [classes][64]
-        if (tid < a.head_classes * 64) Wh[tid] = (tid & 63) < a.Cout ? a.head_w[(tid >> 6) * a.Cout + (tid & 63)] : 0.f;
-        __syncthreads();
-        f32x4 d4[4];                            // four interleaved partial sums per class (packed fma), folded at the end
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d4[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-        const float *yrow = lds + tid * HEAD_ROW;
-#pragma unroll
-        for (int c4 = 0; c4 < 16; ++c4) {
-            const f32x4 yv = *reinterpret_cast<const f32x4 *>(yrow + 4 * c4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < a.head_classes) d4[k] += yv * *reinterpret_cast<const f32x4 *>(Wh + 64 * k + 4 * c4);
-        }
-        float d[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] = k < a.head_classes ? ((d4[k].x + d4[k].y) + (d4[k].z + d4[k].w)) + a.head_b[k] : 0.f;
-        const int py = e_by0 + (tid >> 4), px = e_bx0 + (tid & 15);
-        if (py < a.H && px < a.W) {
-            const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
-            float best = -3.402823466e+38f;
-            int idx = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k < a.head_classes) {
-                    if (a.head_logits != nullptr) a.head_logits[((size_t)e_b * a.head_classes + k) * hw + pin] = d[k];
-                    if (d[k] > best) { best = d[k]; idx = k; }
-                }
-            }
-            a.head_labels[(size_t)e_b * hw + pin] = (uint8_t)idx;
-        }
-    }
+    W4Out o;
+    o.ld = ld_e; o.co_off = co_e; o.by0 = e_by0; o.bx0 = e_bx0; o.relu_lo = relu_lo; o.do_pool = do_pool;
+    w4_epilogue<HEAD, 0, NB>(a, o, out_rsrc, pool_rsrc, &acc[0][0], e_ncol0, e_ncol0, kq, lds);
+    // HEAD: the four waves hold 16 channels each, so the tile crossed LDS above, in the V region, which is dead until the next
+    // tile's first transform -- behind the next prologue's barrier
+    if constexpr (HEAD) fused_head_tile<64, 16>(a, lds, tid, e_b, e_by0, e_bx0);
     if constexpr (U_LATE) { if (tt + slots < t_count) open_tile_u(); }
     }   // persistent tile loop
 }

@@ -20,9 +20,10 @@
 // Single buffers cost two barriers per chunk and serialise transform and MFMAs inside a workgroup; the co-resident
 // workgroup runs its MFMAs meanwhile.  Everything else -- the slot-permuted raw image, the row-split forward transform,
 // the in-lane inverse transform, the free bias at position (1,1), buffer stores, fused pooling, the fused 1x1 head -- is
-// the arithmetic of conv_wino4.hip, so the two kernels give bit-identical results.
+// the arithmetic of conv_wino4.hip, and since both kernels take it from wino4_common.h it is one definition.  Their results
+// are still not promised bit for bit: hipcc contracts multiply-adds per instruction stream, and the two schedules differ
+// (test_conv3x3_wino4s_two_workgroups_per_cu allows 2e-5 between them).
 #include <cstdlib>
-#include <type_traits>
 
 #include "kernel_common.h"
 #include "routing.h"
@@ -31,13 +32,12 @@
 namespace miunet {
 
 struct W4S {
-    static constexpr int HEAD_ROW = 64 + 4;                 // floats per pixel of the head's LDS tile (conflict-free b128 rows)
     static constexpr size_t LDS_BYTES = sizeof(float) * (W4::VBUF + W4::RAW_FLOATS);          // 60,416
-    static constexpr size_t LDS_BYTES_HEAD = sizeof(float) * (256 * HEAD_ROW + 4 * 64);       // the head tile (larger than V + raw) + its weights
+    static constexpr size_t LDS_BYTES_HEAD = head_lds_bytes(64);                              // the head tile (larger than V + raw) + its weights
     static constexpr int FIRST_WIN = 20;                    // fused first layer: the normalised (16 + 4)^2 window of the image behind V + raw
     static constexpr int FIRST_WMAX = WINO4S_FIRST_WMAX;                  // ... and the first layer's weights [9][Cin] + shift [Cin] (Cin <= 64: no long-lived registers)
     static constexpr size_t LDS_BYTES_FIRST = LDS_BYTES + sizeof(float) * (FIRST_WIN * FIRST_WIN + 10 * FIRST_WMAX);
-    static_assert(LDS_BYTES <= sizeof(float) * 256 * HEAD_ROW, "the head launch's allocation must cover the K loop's V + raw images");
+    static_assert(LDS_BYTES <= sizeof(float) * 256 * W4::HEAD_ROW, "the head launch's allocation must cover the K loop's V + raw images");
 };
 
 // UD = U prefetch distance in positions (36 % UD == 0).  The ring is carried across the chunk boundary: its first UD loads of
@@ -65,7 +65,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
                                                              const int m_tiles, const int nwg)
 {
     constexpr int VROW = W4::VROW, VPOS = W4::VPOS;
-    constexpr int HEAD_ROW = W4S::HEAD_ROW;
     static_assert(36 % UD == 0, "ring depth must divide the position count");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *const Vs = lds;                    // [36][16][VROW]
@@ -95,20 +94,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
     // past Cin and dead slots through the buffer range check: voffset 0xFFFFFFFF reads zeros)
     unsigned raw_voff[W4::RAW_ITERS];
 #pragma unroll
-    for (int s = 0; s < W4::RAW_ITERS; ++s) {
-        const int g = (wave + 4 * s) * 16 + (lane >> 2);                  // linear slot of this lane in load wave + 4s
-        const int py = g / W4::RAW_ROW, sl = g - py * W4::RAW_ROW;
-        const int px = 4 * (sl % 5) + sl / 5;
-        const int gy = by0 - 1 + py, gx = bx0 - 1 + px;
-        const bool inb = g < W4::RAW_SLOTS && px < 18 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        raw_voff[s] = inb ? (unsigned)(((gy * a.W + gx) * a.ldc + 4 * (lane & 3)) * 4) : 0xFFFFFFFFu;
-    }
+    for (int s = 0; s < W4::RAW_ITERS; ++s) raw_voff[s] = w4_raw_slot(a, by0, bx0, wave + 4 * s, lane).voff;
     auto first_patch = [&](int chunk) {                        // FIRST: this thread's pieces of a chunk's patch, computed
         const int cq = chunk * WINO4_KC + 4 * (lane & 3);
         const float *wq = Wf + cq;                             // tap t: wq[t * Cin .. + 3]; the shifts behind the ninth tap
 #pragma unroll 1                                               // a real loop: unrolled, hipcc hoists 6 x 18 LDS reads and spills accumulators
         for (int s = 0; s < W4::RAW_ITERS; ++s) {
             if (wave + 4 * s >= W4::RAW_LOADS) break;
+            // (w4_raw_slot's map written out: called from this real loop it costs inc.c2 0.03 ms of 1.13, EXPERIMENTS R5.20)
             const int g = (wave + 4 * s) * 16 + (lane >> 2);
             const int py = g / W4::RAW_ROW, sl = g - py * W4::RAW_ROW;
             const int px = 4 * (sl % 5) + sl / 5;
@@ -126,73 +119,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
             *reinterpret_cast<f32x4 *>(Raw + (size_t)g * WINO4_KC + 4 * (lane & 3)) = r;
         }
     };
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    auto raw_dma_one = [&](int chunk, int s) {                 // the wave's s-th load of a chunk's patch
-        const int c0 = chunk * WINO4_KC;
-        const bool c_ok = c0 + 4 * (lane & 3) < a.Cin;
-        if (wave + 4 * s < W4::RAW_LOADS)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, (lds_ptr)(Raw + (wave + 4 * s) * 16 * WINO4_KC), 16,
-                                                     c_ok ? raw_voff[s] : 0xFFFFFFFFu, c0 * 4, 0, 0);
+    auto dma_one = [&](int chunk, int s) {                     // the wave's s-th load (load wave + 4s) of a chunk's patch
+        raw_dma_one(in_rsrc, Raw, chunk, wave + 4 * s, raw_voff[s], raw_chunk_ok(a.Cin, chunk, lane));
     };
 
-    // ---- forward transform V = B^T d B of one chunk; lane = (tile, channel quad), wave = row group of B^T:
-    //   wave 0: xi 1, 2 = (d4 - 4 d2) +- (d3 - 4 d1)        wave 1: xi 3, 4 = (d4 - d2) +- (2 d3 - 2 d1)
-    //   wave 2: xi 0    = 4 d0 - 5 d2 + d4                  wave 3: xi 5    = 4 d1 - 5 d3 + d5
-    const bool two = wave < 2;
-    const int t_tile = lane >> 2, t_quad = lane & 3;
-    const int row0 = two ? 1 : wave - 2, rstep = two ? 1 : 2;
-    const float *const p_rd = Raw + (((4 * (t_tile >> 2) + row0) * W4::RAW_ROW + (t_tile & 3)) * 4 + t_quad) * 4;
-    const int p_rstride = rstep * W4::RAW_ROW * WINO4_KC;
-    const int xi_a = two ? (wave == 0 ? 1 : 3) : (wave == 2 ? 0 : 5);
-    const float c_alpha = wave == 0 ? -4.f : -1.f, c_beta = wave == 0 ? 1.f : 2.f;
-    float *const v_wr_a = Vs + xi_a * 6 * VPOS + t_tile * VROW + 4 * (t_quad ^ v_swz(t_tile));      // + nu*VPOS; row b = + 6*VPOS
-    auto column_pass = [&](const f32x4 *c, float *dst) {
-        const f32x4 e0 = c[4] - 4.f * c[2], e1 = c[3] - 4.f * c[1], e2 = pk_sub(c[4], c[2]), e3 = pk_sub(c[3], c[1]);
-        *reinterpret_cast<f32x4 *>(dst + 0 * VPOS) = 4.f * c[0] - 5.f * c[2] + c[4];
-        *reinterpret_cast<f32x4 *>(dst + 1 * VPOS) = e0 + e1;
-        *reinterpret_cast<f32x4 *>(dst + 2 * VPOS) = pk_sub(e0, e1);
-        *reinterpret_cast<f32x4 *>(dst + 3 * VPOS) = e2 + 2.f * e3;
-        *reinterpret_cast<f32x4 *>(dst + 4 * VPOS) = e2 - 2.f * e3;
-        *reinterpret_cast<f32x4 *>(dst + 5 * VPOS) = 4.f * c[1] - 5.f * c[3] + c[5];
-    };
+    // ---- forward transform V = B^T d B of one chunk: the steps of wino4_common.h back to back, wave w in role w
+    const W4Role role = w4_role(wave, lane);
     auto transform = [&]() {
         f32x4 cR[2][6];                       // rows of B^T d (row b only on the two-row waves)
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {         // patch column k of this lane's rows: pixel 4*tx + k -> slot 5*(k&3) + tx + (k>>2)
-            const float *src = p_rd + ((k & 3) * 5 + (k >> 2)) * WINO4_KC;
+        for (int k = 0; k < 6; ++k) {
             f32x4 d[4];
-            d[0] = *reinterpret_cast<const f32x4 *>(src);
-            d[1] = *reinterpret_cast<const f32x4 *>(src + p_rstride);
-            d[2] = *reinterpret_cast<const f32x4 *>(src + 2 * p_rstride);
-            d[3] = *reinterpret_cast<const f32x4 *>(src + 3 * p_rstride);       // (unused by the one-row waves: patch rows 6, 7)
-            f32x4 ra, rb;
-            if (two) {                        // waves 0 and 1: one instruction sequence, wave-uniform coefficients (conv_wino4.hip)
-                const f32x4 ta = d[3] + c_alpha * d[1];
-                const f32x4 tb = d[2] + c_alpha * d[0];
-                ra = ta + c_beta * tb;
-                rb = ta - c_beta * tb;
-            } else {
-                ra = 4.f * d[0] - 5.f * d[1] + d[2];
-                rb = ra;
-            }
-            cR[0][k] = ra;
-            cR[1][k] = rb;
+            w4_col_load(Raw + role.rd_off, role.rstride, k, d);
+            w4_col(role.two, role.c_alpha, role.c_beta, d, cR[0][k], cR[1][k]);
         }
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
-            if (row == 1 && !two) break;
-            column_pass(cR[row], v_wr_a + row * 6 * VPOS);
+            if (row == 1 && !role.two) break;
+            w4_row_pass(cR[row], Vs + role.wr_off + row * 6 * VPOS);
         }
     };
 
     // ---- MFMA role: wave w, channels n0 + 16 w .. + 15, all 36 positions
     const unsigned u_pos_bytes = (unsigned)a.CoutPad * WINO4_KC * 4;
     const int nchunks = (a.Cin + WINO4_KC - 1) / WINO4_KC;
-    const __amdgpu_buffer_rsrc_t u_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wpk4), 0, (int)(nchunks * 36 * u_pos_bytes), 0x00020000);
-    auto u_load = [&](int chunk, int p) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, u_voff, (chunk * 36 + p) * u_pos_bytes, 0));
-    };
+    const __amdgpu_buffer_rsrc_t u_rsrc = w4_u_rsrc(a);
+    auto u_load = [&](int chunk, int p) { return w4_u_load(u_rsrc, u_voff, u_pos_bytes, chunk, p); };
     const float *const v_rd = Vs + j16 * VROW + 4 * (kq ^ v_swz(j16));                       // + pos*VPOS
 
     // the loads that open the tile: the raw patch of chunk 0 straight into LDS, then the U ring
@@ -205,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
         for (int i = tid; i < 10 * a.Cin; i += 256) Wf[i] = i < 9 * a.Cin ? a.first_w[i] : a.first_shift[i - 9 * a.Cin];
     } else {
 #pragma unroll
-        for (int s = 0; s < W4::RAW_ITERS; ++s) raw_dma_one(0, s);
+        for (int s = 0; s < W4::RAW_ITERS; ++s) dma_one(0, s);
     }
     f32x4 u[UD];
 #pragma unroll
@@ -214,8 +166,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
     f32x4 acc[36];
 #pragma unroll
     for (int p = 0; p < 36; ++p) {
-        // position (xi, nu) = (1, 1) starts at the shift: A^T e_1 e_1^T A is the all-ones tile, so the bias add is free
-        const float init = (p == 7 && ncol0 < a.Cout) ? a.bias[ncol0] : 0.f;
+        const float init = w4_acc_init(a, p, ncol0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[p][r] = init;
     }
@@ -242,8 +193,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
             if (p + 1 < 36) avn = *reinterpret_cast<const f32x4 *>(v_rd + (p + 1) * VPOS);   // V fragment one position ahead
             // one DMA load every fourth position, not a burst: 16 line misses at a time keep the VMEM queue moving
             if (!FIRST && more && !(EXP & 2)) {   // one DMA load per position (16 line misses at a time keep the VMEM queue moving)
-                if (!LATE && p % 4 == 0 && p / 4 < W4::RAW_ITERS) raw_dma_one(chunk + 1, p / 4);
-                if (LATE && p >= 36 - W4::RAW_ITERS) raw_dma_one(chunk + 1, p - (36 - W4::RAW_ITERS));
+                if (!LATE && p % 4 == 0 && p / 4 < W4::RAW_ITERS) dma_one(chunk + 1, p / 4);
+                if (LATE && p >= 36 - W4::RAW_ITERS) dma_one(chunk + 1, p - (36 - W4::RAW_ITERS));
             }
             __builtin_amdgcn_sched_barrier(0);
             const f32x4 bv = u[p % UD];
@@ -256,138 +207,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4s_f32(const ConvArgs a, c
         }
     } while (++chunk < nchunks);
 
-    // ---- epilogue: Y = A^T M A in-lane on all four tiles of a lane at once (the accumulator's four registers = tile
-    // columns r = 0..3 of tile row kq, lane = channel), ReLU, 4x4 stores (+ the 2x2 pooled maxima).  Stores are buffer
-    // stores on a per-image descriptor; pixels past the image edge and masked channels get voffset 0xFFFFFFFF (dropped).
+    // ---- epilogue (w4_epilogue, wino4_common.h): inverse transform in-lane, ReLU, stores, pooled maxima or the head's tile.
     // (Swapping the MFMA operand roles would give every lane four consecutive CHANNELS of one tile and so 16-byte stores,
     // a quarter of the store instructions: measured 2-4 % slower on these layers -- the stores are bound by the 64-byte
     // segments they scatter, not by their count.)
-    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     const int Hp = a.H >> 1, Wp = a.W >> 1;
     const bool do_pool = a.pool_out != nullptr;
-    const unsigned pix_bytes = (unsigned)a.ldo * 4, row_bytes = (unsigned)a.W * pix_bytes;
-    const unsigned ppix_bytes = (unsigned)a.pool_ld * 4, prow_bytes = (unsigned)Wp * ppix_bytes;
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * a.H * a.W * a.ldo, 0,
-                                                                              a.H * a.W * a.ldo * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * a.H * a.W * a.ldo, 0, a.H * a.W * a.ldo * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t pool_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         do_pool ? a.pool_out + (size_t)b * Hp * Wp * a.pool_ld : a.out, 0, do_pool ? Hp * Wp * a.pool_ld * 4 : 0, 0x00020000);
-    const int oy = by0 + 4 * kq;
+    W4Out o;
+    o.ld = a.ldo; o.co_off = a.co_off; o.by0 = by0; o.bx0 = bx0; o.relu_lo = a.relu ? 0.f : -__builtin_inff(); o.do_pool = do_pool;
     if constexpr (HEAD) __syncthreads();      // the head tile overwrites V: every wave must be past its last MFMA phase
-    auto epilogue = [&](auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-        const int ncol = ncol0;
-        const bool n_ok = ncol < a.Cout;
-        const unsigned vbase = n_ok ? (unsigned)((oy * a.W + bx0) * a.ldo + a.co_off + ncol) * 4 : 0xFFFFFFFFu;
-        const unsigned pbase = n_ok ? (unsigned)(((oy >> 1) * Wp + (bx0 >> 1)) * a.pool_ld + ncol) * 4 : 0xFFFFFFFFu;
-        unsigned vcol[4][4], pcol[4][2];          // edge workgroups: per-column offsets (dead columns -> dropped stores)
-        if constexpr (!INTERIOR) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) vcol[r][k] = bx0 + 4 * r + k < a.W ? vbase : 0xFFFFFFFFu;
-                pcol[r][0] = bx0 + 4 * r + 1 < a.W ? pbase : 0xFFFFFFFFu;
-                pcol[r][1] = bx0 + 4 * r + 3 < a.W ? pbase : 0xFFFFFFFFu;
-            }
-        }
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {          // two tile columns (r = 2 h2, 2 h2 + 1) at a time
-            auto half = [&](const f32x4 &v) { return h2 ? v.hi : v.lo; };
-            f32x2 t[4][6];
-#pragma unroll
-            for (int nu = 0; nu < 6; ++nu) {
-                const f32x2 m0 = half(acc[nu]), m1 = half(acc[6 + nu]), m2 = half(acc[12 + nu]),
-                            m3 = half(acc[18 + nu]), m4 = half(acc[24 + nu]), m5 = half(acc[30 + nu]);
-                const f32x2 s12 = m1 + m2, d12 = pk_sub2(m1, m2), s34 = m3 + m4, d34 = pk_sub2(m3, m4);
-                t[0][nu] = m0 + s12 + s34;
-                t[1][nu] = d12 + 2.f * d34;
-                t[2][nu] = s12 + 4.f * s34;
-                t[3][nu] = d12 + 8.f * d34 + m5;
-            }
-            f32x2 carry0, carry1;                 // horizontal maxima of the even row, for the 2x2 pooling
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x2 s12 = t[i][1] + t[i][2], d12 = pk_sub2(t[i][1], t[i][2]), s34 = t[i][3] + t[i][4], d34 = pk_sub2(t[i][3], t[i][4]);
-                f32x2 y[4];
-                y[0] = t[i][0] + s12 + s34;
-                y[1] = d12 + 2.f * d34;
-                y[2] = s12 + 4.f * s34;
-                y[3] = d12 + 8.f * d34 + t[i][5];
-                const bool row_ok = INTERIOR || oy + i < a.H;      // per-lane (kq) row predicate of an edge workgroup
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int rr = 0; rr < 2; ++rr) {
-                        const int r = 2 * h2 + rr;
-                        const float v = fmaxf(y[k][rr], relu_lo);
-                        y[k][rr] = v;
-                        if constexpr (HEAD) {     // pixel (4 kq + i, 4 r + k) of the 16x16 block, channel ncol -> LDS
-                            lds[((4 * kq + i) * 16 + 4 * r + k) * HEAD_ROW + (ncol & 63)] = v;
-                            continue;
-                        }
-                        unsigned voff = vbase;
-                        if constexpr (!INTERIOR) voff = row_ok ? vcol[r][k] : 0xFFFFFFFFu;
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, voff,
-                                                              i * row_bytes + (4 * r + k) * pix_bytes, ST_AUX);
-                    }
-                if (!HEAD && do_pool) {
-                    f32x2 hm0, hm1;               // horizontal maxima of this row: pooled columns 2r and 2r + 1
-#pragma unroll
-                    for (int rr = 0; rr < 2; ++rr) { hm0[rr] = fmaxf(y[0][rr], y[1][rr]); hm1[rr] = fmaxf(y[2][rr], y[3][rr]); }
-                    if ((i & 1) == 0) { carry0 = hm0; carry1 = hm1; }
-                    else {
-#pragma unroll
-                        for (int rr = 0; rr < 2; ++rr) {
-                            const int r = 2 * h2 + rr;
-                            const float p0 = fmaxf(hm0[rr], carry0[rr]), p1 = fmaxf(hm1[rr], carry1[rr]);
-                            unsigned v0 = pbase, v1 = pbase;
-                            if constexpr (!INTERIOR) { v0 = row_ok ? pcol[r][0] : 0xFFFFFFFFu; v1 = row_ok ? pcol[r][1] : 0xFFFFFFFFu; }
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0), pool_rsrc, v0,
-                                                                  (i >> 1) * prow_bytes + (2 * r) * ppix_bytes, ST_AUX);
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1), pool_rsrc, v1,
-                                                                  (i >> 1) * prow_bytes + (2 * r + 1) * ppix_bytes, ST_AUX);
-                        }
-                    }
-                }
-            }
-        }
-    };
-    if (HEAD || (by0 + 16 <= a.H && bx0 + 16 <= a.W)) epilogue(std::true_type{});   // workgroup-uniform: no per-pixel predicates
-    else epilogue(std::false_type{});
-    if constexpr (HEAD) {
-        // 1x1 head + argmax on the tile: the four waves hold 16 channels each, so the tile crossed LDS above
-        // ([256 pixels][64 + 4 pad]); thread = pixel, a fixed summation order, first-max-wins argmax (src/process.cpp:158-170).
-        float *const Wh = lds + 256 * HEAD_ROW;            // [classes][64]
-        if (tid < a.head_classes * 64) Wh[tid] = (tid & 63) < a.Cout ? a.head_w[(tid >> 6) * a.Cout + (tid & 63)] : 0.f;
-        __syncthreads();
-        f32x4 d4[4];                            // four interleaved partial sums per class (packed fma), folded at the end
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d4[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-        const float *yrow = lds + tid * HEAD_ROW;
-#pragma unroll
-        for (int c4 = 0; c4 < 16; ++c4) {
-            const f32x4 yv = *reinterpret_cast<const f32x4 *>(yrow + 4 * c4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < a.head_classes) d4[k] += yv * *reinterpret_cast<const f32x4 *>(Wh + 64 * k + 4 * c4);
-        }
-        float d[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] = k < a.head_classes ? ((d4[k].x + d4[k].y) + (d4[k].z + d4[k].w)) + a.head_b[k] : 0.f;
-        const int py = by0 + (tid >> 4), px = bx0 + (tid & 15);
-        if (py < a.H && px < a.W) {
-            const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
-            float best = -3.402823466e+38f;
-            int idx = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k < a.head_classes) {
-                    if (a.head_logits != nullptr) a.head_logits[((size_t)b * a.head_classes + k) * hw + pin] = d[k];
-                    if (d[k] > best) { best = d[k]; idx = k; }
-                }
-            }
-            a.head_labels[(size_t)b * hw + pin] = (uint8_t)idx;
-        }
-    }
+    w4_epilogue<HEAD, ST_AUX, 1>(a, o, out_rsrc, pool_rsrc, acc, ncol0, ncol0 & 63, kq, lds);
+    if constexpr (HEAD) fused_head_tile<64, 16>(a, lds, tid, b, by0, bx0);     // the four waves hold 16 channels each: the tile crossed LDS
 }
 
 template <bool HEAD>

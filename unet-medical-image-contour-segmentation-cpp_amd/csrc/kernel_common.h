@@ -46,6 +46,48 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg)
     return start + (bid >> 3);
 }
 
+// ---- the network's 1x1 head + argmax fused behind a layer's epilogue (ConvArgs::head_w; conv_wino4.hip, conv_wino4s.hip,
+// conv_lp.hip).  The layer's post-ReLU fp32 tile of 256 pixels x C channels crossed LDS ([pixel][C + 4 pad]: conflict-free b128
+// rows; masked channels hold zeros); the head's weights follow it as [4 classes][C].  Thread = pixel tid of the (256 / TW) x TW
+// block at (y0, x0) of image b: four interleaved packed partial sums per class, folded in a fixed order, the logits store,
+// first-max-wins argmax (src/process.cpp:158-170), the label store.  Plain inline, not forced (see wino4_common.h).
+constexpr int head_row(int C) { return C + 4; }                                        // floats per pixel of the tile
+constexpr size_t head_lds_bytes(int C) { return sizeof(float) * (256 * (size_t)head_row(C) + 4 * C); }
+template <int C, int TW>
+static __device__ inline void fused_head_tile(const ConvArgs a, float *const lds, const int tid, const int b, const int y0, const int x0)
+{
+    constexpr int HEAD_ROW = head_row(C);
+    float *const Wh = lds + 256 * HEAD_ROW;            // [classes][C]
+    if (tid < a.head_classes * C) Wh[tid] = (tid % C) < a.Cout ? a.head_w[(tid / C) * a.Cout + (tid % C)] : 0.f;
+    __syncthreads();
+    f32x4 d4[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d4[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
+    const float *yrow = lds + tid * HEAD_ROW;
+#pragma unroll
+    for (int c4 = 0; c4 < C / 4; ++c4) {
+        const f32x4 yv = *reinterpret_cast<const f32x4 *>(yrow + 4 * c4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < a.head_classes) d4[k] += yv * *reinterpret_cast<const f32x4 *>(Wh + C * k + 4 * c4);
+    }
+    const int py = y0 + tid / TW, px = x0 + tid % TW;
+    if (py < a.H && px < a.W) {
+        const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
+        float best = -3.402823466e+38f;
+        int idx = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < a.head_classes) {
+                const float d = ((d4[k].x + d4[k].y) + (d4[k].z + d4[k].w)) + a.head_b[k];
+                if (a.head_logits != nullptr) a.head_logits[((size_t)b * a.head_classes + k) * hw + pin] = d;
+                if (d > best) { best = d; idx = k; }
+            }
+        }
+        a.head_labels[(size_t)b * hw + pin] = (uint8_t)idx;
+    }
+}
+
 // Kernels that need more than 64 KB of dynamic LDS must opt in once per (kernel, device).  Keyed by the kernel's address:
 // template instantiations share one function-pointer TYPE, so a per-type flag would cover only the first of them.
 // The table is read without a lock on the launch path (an eager launch used to take a process-wide mutex here: contexts of
