@@ -178,6 +178,29 @@ struct VolumeMeasure {
 bool set_volume_measure(const VolumeMeasure &measure);
 VolumeMeasure get_volume_measure();
 
+// Where the intensity of every component of the labelled stack sits (mi_unet_volume_spatial in include/mi_unet.h).  It
+// acts only together with set_volume's `on`: the stack also keeps `channel` of every slice's normalised tile widened to 16 bits (beside
+// the channels the other settings keep, when it differs from all of them), a failed slice all-zero; mi_unet_volume_components hands out
+// its ids, and one mi_unet_volume_spatial call per target (mi_unet_volume_spatial_host under MEDSEG_HOST_POSTPROCESS=1) takes the
+// components of the report's table under the integer units mi_unet_score_volume_units finds for the volume setting's spacing, with
+// `max_voxels` as the cap of the pair sums and peak_r = llround(peak_mm / unit_mm) as the radius of the peak sphere (6.2035 mm: the
+// sphere of 1 cm^3).  Every component object of volume_report.json gains a last member "spatial": "morans_i", "gearys_c", "pairs",
+// "com_shift_mm", "intensity_centroid_mm" ([x, y, z]), "integrated_intensity", "local_peak", "local_peak_at" ([x, y, z]), "global_peak"
+// and "global_peak_at"; the first two are null for a component past the cap or of one voxel, and the whole member is null for a component
+// the volume filter dropped (its voxels carry no id).  One log line per batch; a failure is reported as "Volume spatial error: ..." and
+// ends only this step: the report is then written without the member.  With it off (the default) every artefact and every log line is
+// what it is without the setting.  Needs no engine and survives initialize_engine.  false, message on stderr, setting unchanged: a
+// negative channel, max_voxels outside 0 .. MI_UNET_VSPATIAL_MAX_VOXELS_LIMIT, or a peak_mm that is not finite and >= 0.  A channel
+// the engine does not have, or a sphere past the stage's limits under the batch's units, is reported when a batch runs.
+struct VolumeSpatial {
+    bool on = false;
+    int channel = 0;
+    int max_voxels = 131072;
+    double peak_mm = 6.2035;
+};
+bool set_volume_spatial(const VolumeSpatial &spatial);
+VolumeSpatial get_volume_spatial();
+
 // The texture of every component of the labelled stack (mi_unet_volume_texture in include/mi_unet.h).  It acts only
 // together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits (beside the channel
 // set_volume_measure keeps, when the two differ), a failed slice all-zero; one mi_unet_volume_texture call per target

@@ -78,6 +78,10 @@ void medseg_get_volume_interp(int *on, int *factor);
  * success; medseg_get_volume_measure fills the three values. */
 int medseg_set_volume_measure(int on, int channel, int max_ends);
 void medseg_get_volume_measure(int *on, int *channel, int *max_ends);
+/* Where the intensity of every component of the labelled stack sits: MedicalSeg::set_volume_spatial / get_volume_spatial
+ * (include/medseg/process.h).  0 on success; medseg_get_volume_spatial fills the four values. */
+int medseg_set_volume_spatial(int on, int channel, int max_voxels, double peak_mm);
+void medseg_get_volume_spatial(int *on, int *channel, int *max_voxels, double *peak_mm);
 /* The scored stack per lesion: MedicalSeg::set_volume_match / get_volume_match (include/medseg/process.h).  0 on success;
  * medseg_get_volume_match fills the three values. */
 int medseg_set_volume_match(int on, int iou_num, int iou_den);

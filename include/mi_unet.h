@@ -1144,6 +1144,88 @@ int mi_unet_volume_nbhood_host(const int32_t *ids, const uint16_t *intensity, in
 int mi_unet_volume_nbhood_derive(const mi_unet_vnbhood *c, const mi_unet_vnbhood_out *rows, int L, int Dm, int axial,
                                  mi_unet_vnbhood_features *out);
 
+/* ---- Volume spatial statistics: per component of a labelled stack where its intensity sits: Moran's I, Geary's C, the
+ * intensity-weighted centre, the integrated intensity and the local / global intensity peak ---------------------------------------------
+ * A stage of its own, not a setting: nothing else in this header changes behaviour because of it.  These are the IBSI morphology and
+ * local-intensity features that need the intensity stack.  Everything but four sums of doubles is an exact integer; millimetres enter
+ * only in mi_unet_volume_spatial_derive.
+ * Input is ids, int32 [D][H][W] (slice z, row y, column x; D, H, W are arguments, not the engine's tile size), intensity, uint16
+ * [D][H][W] (required, as in mi_unet_volume_texture), the number of components m, the spacing as three positive integers
+ * spacing_units = { ux, uy, uz } in a unit the caller chooses (mi_unet_score_volume_units finds one for a spacing in millimetres) and
+ * opts = { max_voxels, peak_r }.
+ *   COMPONENT  as in mi_unet_volume_measure: component r, 0 <= r < m, is the set of voxels with ids == r + 1.  Every other value (0, -1,
+ *              anything above m) belongs to no component.  A voxel's index is z * H * W + y * W + x.  An id that no voxel carries gives
+ *              an all-zero entry.
+ *   SUMS       voxels = A; sx, sy, sz over the integer coordinates; si, sii (the sums of v and v * v), imin, imax over the intensity v;
+ *              six, siy, siz = sum v x, sum v y, sum v z (below 2^13 * 2^16 * 2^31 = 2^60).
+ *   CENTRE     centre = c = floor((2 si + A) / (2 A)), the integer nearest the mean intensity.  With y = v - c, |mean - c| <= 1/2: nothing
+ *              that is derived from the pair sums cancels badly.
+ *   PEAKS      the sphere of a voxel p is { p + o : o in B(peak_r) } cut to the volume, B(r) the ball of mi_unet_volume_ball in
+ *              spacing_units.  Whether a voxel of the sphere belongs to the component is NOT asked (IBSI).  n(p) is the sphere's voxel
+ *              count and s(p) the sum of its intensities; mean a > mean b <=> s_a n_b > s_b n_a, in unsigned 64 bits.
+ *              Global peak: over all p of the component the largest mean, ties to the smallest index: gp_sum, gp_n, gp_at = s, n, p.
+ *              Local peak: the same over the p of the component with v(p) == imax: lp_sum, lp_n, lp_at.
+ *              peak_r == 0 makes both the first voxel that carries imax.  Every component gets its peaks: their cost is linear.
+ *   PAIRS      for a component with 2 <= A <= max_voxels (and max_voxels > 0), over the unordered pairs i < j of its voxels, with
+ *              d2(i, j) = (dx ux)^2 + (dy uy)^2 + (dz uz)^2 between voxel centres (an int32_t, as in mi_unet_volume_measure; its
+ *              conversion to double is exact) and w = 1 / sqrt(d2) in double:
+ *                s0 = sum w,  s1 = sum w (y_i + y_j),  s2 = sum w y_i y_j,  s3 = sum w (y_i - y_j)^2.
+ *              The integer factors are formed exactly and converted once; w is within 4 ulp of the real 1 / sqrt(d2) in either form.
+ *              pairs = A (A - 1) / 2 and searched = 1.  A component above the cap, or with A < 2, has searched = 0, pairs = 0 and the
+ *              four doubles 0.0; everything else in its entry stays valid.  The cap acts on voxels, a defined quantity, so the two
+ *              forms agree on who is skipped.  The four doubles depend on the order of summation: the two forms agree within
+ *              2 (P + 8) eps sum |term| for P pairs; the device form gives the same bits from call to call.
+ * Limits, each with its reason:
+ *   those of mi_unet_volume_measure: D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE; D * H * W < 2^31; m in 1 .. MI_UNET_VOLUME_MAX_TABLE;
+ *           every unit >= 1 and the squared diagonal of the volume in spacing units below 2^31;
+ *   max_voxels in 0 .. MI_UNET_VSPATIAL_MAX_VOXELS_LIMIT = 2^20: 2^39 pairs, the most one component may cost;
+ *   peak_r in 0 .. MI_UNET_VOLUME_CLEAN_MAX_R = 46340: r * r < 2^31;
+ *   B(peak_r) has (2 ey + 1) (2 ez + 1) <= MI_UNET_VSPATIAL_MAX_BALL_ROWS = 4096 rows (ey = peak_r / uy, ez = peak_r / uz) and at most
+ *           MI_UNET_VSPATIAL_MAX_BALL_VOXELS = 2^23 voxels: s < 2^23 * 2^16 = 2^39 and s * n < 2^62, inside 64 unsigned bits.
+ * opts == NULL is { 131072, 0 }.
+ * mi_unet_volume_spatial takes host buffers of any size; its workspace grows on demand, belongs to the handle and is freed by
+ * mi_unet_destroy.  It needs the device, not the network: it works before weights are loaded.  It changes no setting and nothing
+ * mi_unet_last_regions or mi_unet_last_stage_ms report.  MI_UNET_EARG with a message, nothing queued and no output written: a null ids,
+ * intensity, spacing_units or table; a limit above.  A workspace that cannot be allocated is MI_UNET_EHIP with a message; the handle
+ * stays usable.
+ * mi_unet_volume_spatial_host is the definition as sequential host arithmetic (needs no device), same arguments without the handle: the
+ * same bytes in every integer field; the pairs are summed in index order (i ascending, then j).
+ * mi_unet_volume_spatial_derive is pure host arithmetic in double.  A voxel is a box of s = spacing_units * unit_mm millimetres per axis
+ * and voxel 0 spans 0 .. 1 of the grid.  With A = voxels:
+ *   c*_mm = (sum / A + 0.5) * s of the axis, as mi_unet_volume_measure_derive gives it;
+ *   ic*_mm = (si* / si + 0.5) * s of the axis, the intensity-weighted centre; NaN when si == 0;
+ *   com_shift_mm = the distance of the two; integrated_intensity = si * (the volume of a voxel in mm^3);
+ *   local_peak = lp_sum / lp_n and global_peak = gp_sum / gp_n;
+ *   with V = (A * sii - si^2) / A from an exact 128-bit numerator and delta = si / A - c:
+ *   morans_i = A / (2 s0) * 2 (s2 - delta s1 + delta^2 s0) / V and gearys_c = (A - 1) / (2 * 2 s0) * 2 s3 / V: IBSI's sums over
+ *   ordered pairs written over unordered ones.  Both are NaN when searched == 0 or V == 0.
+ * MI_UNET_EARG, output untouched: a null pointer, voxels < 1, a unit < 1, or a unit_mm that is not finite and > 0.
+ * There is no group form: mi_unet_group_handle(g, rank) hands out an engine to call this on. */
+#define MI_UNET_VSPATIAL_MAX_VOXELS_LIMIT 1048576 /* 2^20 */
+#define MI_UNET_VSPATIAL_MAX_BALL_ROWS 4096
+#define MI_UNET_VSPATIAL_MAX_BALL_VOXELS 8388608  /* 2^23 */
+typedef struct mi_unet_vspatial {      /* 168 bytes, no padding */
+    int32_t voxels, searched;          /* voxels with this id; 1 when the pair sums were taken */
+    int32_t imin, imax;                /* min / max of intensity over the component */
+    int32_t centre, reserved;          /* the integer nearest the mean intensity; 0 */
+    int32_t gp_at, lp_at;              /* the voxel index of the global and of the local peak */
+    int64_t sx, sy, sz;                /* sums of x, y, z over the component */
+    int64_t si, sii;                   /* sum v, sum v*v of the intensity */
+    int64_t six, siy, siz;             /* sum v x, sum v y, sum v z */
+    int64_t gp_sum, gp_n, lp_sum, lp_n; /* the peak spheres: intensity sum and voxel count */
+    int64_t pairs;                     /* A (A - 1) / 2 when searched, else 0 */
+    double s0, s1, s2, s3;             /* the pair sums */
+} mi_unet_vspatial;
+typedef struct mi_unet_vspatial_opts { int max_voxels, peak_r; } mi_unet_vspatial_opts;     /* default { 131072, 0 } */
+typedef struct mi_unet_vspatial_metrics {
+    double cx_mm, cy_mm, cz_mm, icx_mm, icy_mm, icz_mm, com_shift_mm, integrated_intensity, local_peak, global_peak, morans_i, gearys_c;
+} mi_unet_vspatial_metrics;
+int mi_unet_volume_spatial(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const uint16_t *intensity /* [D][H][W] host */, int D, int H,
+                           int W, int m, const int spacing_units[3], const mi_unet_vspatial_opts *opts, mi_unet_vspatial *table /* [m] */);
+int mi_unet_volume_spatial_host(const int32_t *ids, const uint16_t *intensity, int D, int H, int W, int m, const int spacing_units[3],
+                                const mi_unet_vspatial_opts *opts, mi_unet_vspatial *table);
+int mi_unet_volume_spatial_derive(const mi_unet_vspatial *c, const int spacing_units[3], double unit_mm, mi_unet_vspatial_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -184,6 +184,8 @@ struct mi_unet {
     miunet::Workspace ws_vmesh_out;    // ... the kept vertices and quads of one plane, sized by its counts
     miunet::Workspace ws_vms;          // mi_unet_volume_measure: ids, intensity, the table and the per-component arrays
     miunet::Workspace ws_vms_pts;      // ... the run ends of the searched components and the work list of the pair search, sized once the ends are counted
+    miunet::Workspace ws_vsp;          // mi_unet_volume_spatial: ids, intensity, the table, the per-component arrays, the ball's rows, the row prefix sums
+    miunet::Workspace ws_vsp_pts;      // ... the candidates, their ranks, the points of the searched components, both work lists and the slots, sized once the voxels are counted
     miunet::Workspace ws_vmt;          // mi_unet_volume_match: the results (side tables, `found`, pairs), the row offsets, the contingency table, both id stacks
     miunet::Workspace ws_vtx;          // mi_unet_volume_texture: the keys (ids in place), the intensity, the ranges, the table, the histograms, both co-occurrence tables
     miunet::Workspace ws_vzn;          // mi_unet_volume_zones: the results (table, found, both run tables, the zone list), the keys (ids in place), the intensity, the ranges, the forest

@@ -14,6 +14,7 @@ struct mi_unet_score;
 struct mi_unet_vcomp;
 struct mi_unet_mesh_vertex;
 struct mi_unet_vmeasure;
+struct mi_unet_vspatial;
 struct mi_unet_vmatch_side;
 struct mi_unet_vmatch_pair;
 struct mi_unet_vtexture;
@@ -420,6 +421,42 @@ hipError_t launch_volume_measure_pairs(const int4 *points, const int2 *seg, cons
                                        hipStream_t s);
 hipError_t launch_volume_measure_ends(const int4 *points, const int2 *seg, const unsigned long long *keys, const VolumeMeasureArgs &a,
                                       int32_t *diam, hipStream_t s);
+
+// Volume spatial statistics (volume_spatial.hip; include/mi_unet.h: mi_unet_volume_spatial).  ids int32 [D][H][W] and
+// intensity u16 [D][H][W] on the device; component r = { ids == r + 1 }, 0 <= r < m.  Integer results are sums, minima, maxima and a
+// maximum under a total order: nothing depends on the order in which atomics arrive.  The pair sums are doubles: every one of them is
+// added up in a fixed order, a slot per work item, no floating-point atomic.  No workgroup waits for another.
+//   launch_volume_spatial_sums: zeroes table [m] and fills voxels, imax, sx, sy, sz, si, sii, six, siy, siz; imin holds 65535 - the
+//       minimum (0 = no voxel), which the caller turns round; every other field stays 0.
+//   launch_volume_spatial_prefix: prefix u32 [D][H][W + 1], prefix[row][k] = the sum of the row's first k intensities.
+//   launch_volume_spatial_fill (after the host has read `voxels` and laid out the segments): seg[r] = (first candidate, voxels, first
+//       point or -1 for a component that is not searched, centre) of component r; cursor [m] and rank [candidates] are zeroed here; every
+//       voxel of a component goes into its segment, in any order, as (s << 24 | n, index, r << 1 | (v == imax)), s and n of its sphere
+//       from two prefix reads per row of the ball.  rows[k] = (dy, dz, the row's x half-width, 0) of the ball's n_rows rows.
+//   launch_volume_spatial_peaks: a workgroup per component: the candidate with the largest mean, ties to the smallest index, over the
+//       segment and over its candidates with v == imax -> peaks[r] = (gp_sum, gp_n, gp_at, lp_sum, lp_n, lp_at); zero without a voxel.
+//   launch_volume_spatial_rank: items[i] = (component, a-tile, first b-tile, b-tiles) over the whole square of the tiles of a searched
+//       component's segment: rank[candidate] += the candidates of the b-tiles with a smaller index.  Integer atomics.
+//   launch_volume_spatial_place: candidate -> points[first point + rank] = (x ux, y uy, z uz, v - centre): the points of a searched
+//       component in index order, whatever order the fill left.
+//   launch_volume_spatial_pairs: items[i] = (component, a-tile, first b-tile, b-tiles), a-tile <= first b-tile: a workgroup per item holds
+//       its a-tile a point per lane, takes the b-tiles through LDS and writes slots[i] = (s0, s1, s2, s3) over the item's pairs i < j.
+//       The caller bounds the pairs of one launch.
+constexpr int VSP_TILE = 256;
+struct VolumeSpatialArgs { int D = 0, H = 0, W = 0, m = 0, ux = 1, uy = 1, uz = 1; };
+struct VspItem { int comp, a_tile, b_first, b_tiles; };
+struct VspCand { unsigned long long sn; int index, tag; };     // (s << 24) | n of the voxel's sphere; its index; r << 1 | (v == imax)
+hipError_t launch_volume_spatial_sums(const int32_t *ids, const uint16_t *intensity, const VolumeSpatialArgs &a, ::mi_unet_vspatial *table,
+                                      hipStream_t s);
+hipError_t launch_volume_spatial_prefix(const uint16_t *intensity, const VolumeSpatialArgs &a, uint32_t *prefix, hipStream_t s);
+hipError_t launch_volume_spatial_fill(const int32_t *ids, const uint16_t *intensity, const uint32_t *prefix, const VolumeSpatialArgs &a,
+                                      const ::mi_unet_vspatial *table, const int4 *seg, const int4 *rows, int n_rows, int *cursor, int *rank,
+                                      size_t candidates, VspCand *cand, hipStream_t s);
+hipError_t launch_volume_spatial_peaks(const VspCand *cand, const int4 *seg, int m, long long *peaks, hipStream_t s);
+hipError_t launch_volume_spatial_rank(const VspCand *cand, const int4 *seg, const VspItem *items, int n_items, int *rank, hipStream_t s);
+hipError_t launch_volume_spatial_place(const VspCand *cand, const int *rank, const uint16_t *intensity, const VolumeSpatialArgs &a,
+                                       const int4 *seg, size_t candidates, int4 *points, hipStream_t s);
+hipError_t launch_volume_spatial_pairs(const int4 *points, const int4 *seg, const VspItem *items, int n_items, double *slots, hipStream_t s);
 
 // Volume matching (volume_match.hip; include/mi_unet.h: mi_unet_volume_match).  pred and truth int32 [D][H][W] on the
 // device; a voxel's class is its id when 1 <= id <= m of its side, else 0.  table is the dense contingency table, int32 [mp + 1][mt + 1],

@@ -24,7 +24,8 @@ __device__ __forceinline__ T wave_reduce(T v, Op op)
     for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     return v;
 }
-// (T: int, unsigned, long long, unsigned long long)
+// (T: int, unsigned, long long, unsigned long long; k_vsp_pairs adds doubles with wave_sum: the butterfly is the same tree on every run
+// and a + b == b + a bit for bit, so every lane ends with the same bits, call after call)
 template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
 template <class T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, [](T a, T b) { return b < a ? b : a; }); }
 template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T a, T b) { return b > a ? b : a; }); }

@@ -213,6 +213,15 @@ void medseg_get_volume_measure(int *on, int *channel, int *max_ends)
     const MedicalSeg::VolumeMeasure m = MedicalSeg::get_volume_measure();
     *on = m.on; *channel = m.channel; *max_ends = m.max_ends;
 }
+int medseg_set_volume_spatial(int on, int channel, int max_voxels, double peak_mm)
+{
+    return MedicalSeg::set_volume_spatial({ on != 0, channel, max_voxels, peak_mm }) ? 0 : 1;
+}
+void medseg_get_volume_spatial(int *on, int *channel, int *max_voxels, double *peak_mm)
+{
+    const MedicalSeg::VolumeSpatial v = MedicalSeg::get_volume_spatial();
+    *on = v.on; *channel = v.channel; *max_voxels = v.max_voxels; *peak_mm = v.peak_mm;
+}
 int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width)
 {
     return MedicalSeg::set_volume_texture({ on != 0, channel, mode, levels, lo, width }) ? 0 : 1;

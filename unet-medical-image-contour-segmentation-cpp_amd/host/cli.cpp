@@ -135,6 +135,17 @@ bool to_int(const std::string &s, int &v)
     }
 }
 
+bool to_double(const std::string &s, double &v)
+{
+    try {
+        size_t used = 0;
+        v = std::stod(s, &used);
+        return used == s.size();
+    } catch (const std::exception &) {
+        return false;
+    }
+}
+
 class Shell {
 public:
     Shell()
@@ -151,6 +162,7 @@ public:
         table_["volmesh"] = [this](const Words &w) { cmd_volmesh(w); return true; };
         table_["volinterp"] = [this](const Words &w) { cmd_volinterp(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
+        table_["volspatial"] = [this](const Words &w) { cmd_volspatial(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
         table_["volnbhood"] = [this](const Words &w) { cmd_volnbhood(w); return true; };
@@ -177,6 +189,7 @@ public:
             "  volmesh on [faces|nets]|off   - With volume on: the labelled stack's border as binary STL (voxel faces, or surface nets) in mm",
             "  volinterp on [factor N|iso]|off - With volume on: shape-based slices between the slices before the stack is meshed (iso: spacing_z / in-plane)",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
+            "  volspatial on [channel N] [voxels N] [peak MM]|off - With volume on: Moran's I, Geary's C, centre-of-mass shift and intensity peaks of every component in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
             "  volnbhood on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N]|off - With volume on: neighbourhood-difference, dependence and distance-zone features of every component in the report",
@@ -504,6 +517,36 @@ private:
         }
         const MedicalSeg::VolumeMeasure cur = MedicalSeg::get_volume_measure();
         std::cout << "Volume measure: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " ends " << cur.max_ends << std::endl;
+    }
+
+    // volspatial on [channel N] [voxels N] [peak MM] | volspatial off | volspatial (prints the setting in force)
+    void cmd_volspatial(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeSpatial v;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            v.on = w[1] == "on";
+            for (size_t i = 2; ok && i < w.size(); i += 2) {
+                int value = 0;
+                if (i + 1 < w.size() && w[i] == "peak") {
+                    ok = to_double(w[i + 1], v.peak_mm);
+                } else {
+                    ok = i + 1 < w.size() && (w[i] == "channel" || w[i] == "voxels") && to_int(w[i + 1], value);
+                    (w[i] == "channel" ? v.channel : v.max_voxels) = value;
+                }
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volspatial command (expected on [channel N] [voxels N] [peak MM] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_spatial(v)) {
+                std::cerr << "Volume spatial unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeSpatial cur = MedicalSeg::get_volume_spatial();
+        std::cout << "Volume spatial: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " voxels " << cur.max_voxels << " peak " << cur.peak_mm
+                  << std::endl;
     }
 
     // The words of a texture command behind its name -- on [levels N] [count | width W [lo L]] [channel N] and the command's own `word N`

@@ -379,6 +379,24 @@ bool set_volume_measure(const VolumeMeasure &measure)
         /*handle_side=*/false);
 }
 
+bool set_volume_spatial(const VolumeSpatial &spatial)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_spatial = spatial;
+            if (spatial.channel < 0) return std::string("volume spatial: the channel is not negative");
+            if (spatial.max_voxels < 0 || spatial.max_voxels > MI_UNET_VSPATIAL_MAX_VOXELS_LIMIT)
+                return std::string("volume spatial: max_voxels is 0 .. MI_UNET_VSPATIAL_MAX_VOXELS_LIMIT");
+            const bool peak = std::isfinite(spatial.peak_mm) && spatial.peak_mm >= 0.0;
+            return std::string(peak ? "" : "volume spatial: peak_mm is finite and not negative");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume spatial: " << (spatial.on ? "on" : "off") << ", channel " << spatial.channel << ", voxels " << spatial.max_voxels << ", peak "
+               << spatial.peak_mm << " mm";
+        },
+        /*handle_side=*/false);
+}
+
 namespace {
 
 // The five fields a texture setting (VolumeTexture, VolumeZones, VolumeNbhood) begins with: what is wrong with the first of them that is
@@ -476,6 +494,7 @@ VolumeClean get_volume_clean() { return current_settings().volume_clean; }
 VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
+VolumeSpatial get_volume_spatial() { return current_settings().volume_spatial; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeZones get_volume_zones() { return current_settings().volume_zones; }
 VolumeNbhood get_volume_nbhood() { return current_settings().volume_nbhood; }

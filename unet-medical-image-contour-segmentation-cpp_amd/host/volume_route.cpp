@@ -466,6 +466,60 @@ Members nbhood_volume(const VolumeStack &st, const std::vector<int32_t> &ids, co
                          cap, s, lg, call, row);
 }
 
+// set_volume_spatial: per target one mi_unet_volume_spatial call on `h` (mi_unet_volume_spatial_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids mi_unet_volume_components wrote ([K][D][H][W]) and the stack's spatial channel, with m = min(found, cap), the integer units of
+// mi_unet_score_volume_units for the volume setting's spacing and peak_r = llround(peak_mm / unit_mm), then
+// mi_unet_volume_spatial_derive of every row.  Returns, per target and table row, the "spatial" member of the row's component object in
+// volume_report.json, from its leading comma on.  A failure is reported and returns nothing: only this step ends.
+Members spatial_volume(const VolumeStack &st, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
+                       mi_unet_t *h, std::ostream &lg)
+{
+    try {
+        const size_t K = s.targets.size(), D = st.D, hw = st.hw;
+        const int W = g_cfg.width;
+        const VolumeSpatial &sp = s.volume_spatial;
+        if (sp.channel >= g_cfg.in_ch) throw std::runtime_error("channel " + std::to_string(sp.channel) + " of " + std::to_string(g_cfg.in_ch));
+        const VolumeUnits u = volume_units(s.volume, D);
+        const double r = sp.peak_mm / u.unit_mm;
+        if (!(r <= (double)MI_UNET_VOLUME_CLEAN_MAX_R))
+            throw std::runtime_error("a peak sphere of " + json_number(sp.peak_mm) + " mm is more than " + std::to_string(MI_UNET_VOLUME_CLEAN_MAX_R) + " units");
+        const mi_unet_vspatial_opts opts{ sp.max_voxels, (int)std::llround(r) };
+        Members members(K);
+        auto point = [&](int32_t idx) {
+            const size_t p = (size_t)idx % hw;
+            return "[" + std::to_string(p % (size_t)W) + ", " + std::to_string(p / (size_t)W) + ", " + std::to_string((size_t)idx / hw) + "]";
+        };
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const int m = (int)std::min<size_t>((size_t)found[t], cap);
+            if (m < 1) continue;
+            std::vector<mi_unet_vspatial> table((size_t)m);
+            stage_call(h, mi_unet_volume_spatial, mi_unet_volume_spatial_host, ids.data() + t * D * hw, st.spatial_intensity(), (int)D, g_cfg.height,
+                       g_cfg.width, m, u.units, &opts, table.data());
+            for (const mi_unet_vspatial &c : table) {
+                if (c.voxels < 1) {                             // dropped by the volume filter: its voxels carry no id
+                    members[t].push_back(", \"spatial\": null");
+                    continue;
+                }
+                mi_unet_vspatial_metrics f{};
+                checked(mi_unet_volume_spatial_derive, &c, u.units, u.unit_mm, &f);
+                std::ostringstream js;
+                js << ", \"spatial\": {\"morans_i\": " << json_number(f.morans_i) << ", \"gearys_c\": " << json_number(f.gearys_c) << ", \"pairs\": "
+                   << c.pairs << ", \"com_shift_mm\": " << json_number(f.com_shift_mm) << ", \"intensity_centroid_mm\": [" << json_number(f.icx_mm)
+                   << ", " << json_number(f.icy_mm) << ", " << json_number(f.icz_mm) << "], \"integrated_intensity\": "
+                   << json_number(f.integrated_intensity) << ", \"local_peak\": " << json_number(f.local_peak) << ", \"local_peak_at\": "
+                   << point(c.lp_at) << ", \"global_peak\": " << json_number(f.global_peak) << ", \"global_peak_at\": " << point(c.gp_at) << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume spatial: " << D << " slices, " << K << " targets, peak radius " << opts.peak_r << " units, " << ms_since(t0) << " ms" << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume spatial error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -477,7 +531,7 @@ Members nbhood_volume(const VolumeStack &st, const std::vector<int32_t> &ids, co
 // the components stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member
 // "measure".  With set_volume_texture on, the ids are handed out likewise and every component object gains a last member "texture"
 // (texture_volume), with set_volume_zones on a last member "zones" behind it (zones_volume), and with set_volume_nbhood on a last member
-// "nbhood" behind that (nbhood_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
+// "nbhood" behind that (nbhood_volume), and with set_volume_spatial on a last member "spatial" behind them all (spatial_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
 // empty after a failure.
 struct VolumeIds {
     std::vector<int32_t> ids, found;
@@ -493,7 +547,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || s.volume_nbhood.on || numbered ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || s.volume_nbhood.on || s.volume_spatial.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const auto t0 = hr_clock::now();
@@ -519,6 +573,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
             s.volume_zones.on ? zones_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const std::vector<std::vector<std::string>> nbhooded =
             s.volume_nbhood.on ? nbhood_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
+        const Members spatialised = s.volume_spatial.on ? spatial_volume(st, ids, found, cap, s, h, lg) : Members();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names = [&](const char *key, bool missing) {
@@ -551,7 +606,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
                    << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r])
-                   << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << "}";
+                   << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << (spatialised.empty() ? std::string() : spatialised[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]}";
         }

@@ -44,10 +44,12 @@ struct VolumeStack {
     // `s` decides what the stack keeps beside the planes: with set_volume_measure on, its channel of every slice's normalised tile; with
     // set_volume_texture on, its channel likewise, in a stack of its own only when the two channels differ; with set_volume_zones on, its
     // channel, in a stack of its own only when neither of the other two holds it; with set_volume_nbhood on, its channel, in a stack of
-    // its own only when none of the other three holds it
+    // its own only when none of the other three holds it; with set_volume_spatial on, its channel, in a stack of its own only when none of
+    // the other four holds it
     VolumeStack(size_t slices, size_t hw, const Settings &s)
         : channel(s.volume_measure.on ? s.volume_measure.channel : -1), texture_channel(s.volume_texture.on ? s.volume_texture.channel : -1),
           zones_channel(s.volume_zones.on ? s.volume_zones.channel : -1), nbhood_channel(s.volume_nbhood.on ? s.volume_nbhood.channel : -1),
+          spatial_channel(s.volume_spatial.on ? s.volume_spatial.channel : -1),
           planes(s.targets.size() * slices * hw, 0), intensity(channel >= 0 ? slices * hw : 0, 0),
           texture_own(texture_channel >= 0 && texture_channel != channel ? slices * hw : 0, 0),
           zones_own(zones_channel >= 0 && zones_channel != channel && zones_channel != texture_channel ? slices * hw : 0, 0),
@@ -55,6 +57,11 @@ struct VolumeStack {
                          ? slices * hw
                          : 0,
                      0),
+          spatial_own(spatial_channel >= 0 && spatial_channel != channel && spatial_channel != texture_channel && spatial_channel != zones_channel &&
+                              spatial_channel != nbhood_channel
+                          ? slices * hw
+                          : 0,
+                      0),
           bases(slices), names(slices), D(slices), hw(hw)
     {
     }
@@ -71,6 +78,8 @@ struct VolumeStack {
             for (size_t p = 0; p < hw; ++p) zones_own[i * hw + p] = tile[p * C + (size_t)zones_channel];
         if (!nbhood_own.empty() && (size_t)nbhood_channel < C)
             for (size_t p = 0; p < hw; ++p) nbhood_own[i * hw + p] = tile[p * C + (size_t)nbhood_channel];
+        if (!spatial_own.empty() && (size_t)spatial_channel < C)
+            for (size_t p = 0; p < hw; ++p) spatial_own[i * hw + p] = tile[p * C + (size_t)spatial_channel];
         bases[i] = base;
     }
     const uint16_t *texture_intensity() const { return texture_own.empty() ? intensity.data() : texture_own.data(); }
@@ -82,19 +91,24 @@ struct VolumeStack {
     {
         return !nbhood_own.empty() ? nbhood_own.data() : nbhood_channel == zones_channel ? zones_intensity() : nbhood_channel == channel ? intensity.data() : texture_intensity();
     }
-    int channel, texture_channel, zones_channel, nbhood_channel;       // -1: not kept
+    const uint16_t *spatial_intensity() const
+    {
+        return !spatial_own.empty() ? spatial_own.data() : spatial_channel == nbhood_channel ? nbhood_intensity() : spatial_channel == zones_channel ? zones_intensity() : spatial_channel == channel ? intensity.data() : texture_intensity();
+    }
+    int channel, texture_channel, zones_channel, nbhood_channel, spatial_channel;      // -1: not kept
     std::vector<uint8_t> planes;                       // [K][D][H][W]; a slice that failed stays all-zero
     std::vector<uint16_t> intensity;                   // [D][H][W] or empty: the measured channel of the normalised tiles, widened
     std::vector<uint16_t> texture_own;                 // [D][H][W] or empty: the texture's channel where it is not the measured one
     std::vector<uint16_t> zones_own;                   // [D][H][W] or empty: the zones' channel where neither of the two above holds it
     std::vector<uint16_t> nbhood_own;                  // [D][H][W] or empty: the neighbourhoods' channel where none of the three above holds it
+    std::vector<uint16_t> spatial_own;                 // [D][H][W] or empty: the spatial statistics' channel where none of the four above holds it
     std::vector<std::string> bases, names;             // per slice: the base name once it is complete (else empty); the name it is reported by
     size_t D, hw;
 };
 
 // (volume_route.cpp) The chain behind the last device call of a volume batch, every stage on `h` (its host form under
 // MEDSEG_HOST_POSTPROCESS=1): clean_volume when set_volume_clean is on -- its failure ends the chain -- then label_volume with whatever
-// of interpolation, mesh, measure, texture, zones and neighbourhoods is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
+// of interpolation, mesh, measure, texture, zones, neighbourhoods and spatial statistics is on, then score_volume_stack with a truth directory, and in it match_volume when set_volume_match is on.
 // A failure of a step is reported to `lg` and fails no image.
 void finish_volume(VolumeStack &stack, const Settings &s, mi_unet_t *h, const std::string &output_dir, std::ostream &lg);
 

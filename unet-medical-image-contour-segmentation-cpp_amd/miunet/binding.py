@@ -39,6 +39,7 @@ EXPORTS = [
     "mi_unet_volume_clean", "mi_unet_volume_clean_host", "mi_unet_volume_ball",
     "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
+    "mi_unet_volume_spatial", "mi_unet_volume_spatial_host", "mi_unet_volume_spatial_derive",
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
@@ -381,6 +382,47 @@ def _table_rows(m, cells):
     """the rows to allocate for m components of `cells` cells each: one for a call that the library refuses (no need for the memory)"""
     rows = max(int(m), 1)
     return 1 if rows * cells > 2 * VTEX_MAX_CELLS else rows
+
+
+class VSpatial(C.Structure):
+    """mi_unet_vspatial: 168 bytes, eight int32, thirteen int64, then the four pair sums as doubles; VSPATIAL_DTYPE is the same layout
+    for numpy"""
+    _fields_ = ([(n, C.c_int32) for n in ("voxels", "searched", "imin", "imax", "centre", "reserved", "gp_at", "lp_at")] +
+                [(n, C.c_int64) for n in ("sx", "sy", "sz", "si", "sii", "six", "siy", "siz", "gp_sum", "gp_n", "lp_sum", "lp_n", "pairs")] +
+                [(n, C.c_double) for n in ("s0", "s1", "s2", "s3")])
+
+
+class VSpatialOpts(C.Structure):
+    _fields_ = [("max_voxels", C.c_int), ("peak_r", C.c_int)]
+
+
+class VSpatialMetrics(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("cx_mm", "cy_mm", "cz_mm", "icx_mm", "icy_mm", "icz_mm", "com_shift_mm", "integrated_intensity",
+                                          "local_peak", "global_peak", "morans_i", "gearys_c")]
+
+
+VSPATIAL_DTYPE = np.dtype([(n, {C.c_int32: np.int32, C.c_int64: np.int64, C.c_double: np.float64}[t]) for n, t in VSpatial._fields_])
+VSPATIAL_INT_BYTES = 8 * 4 + 13 * 8         # the integer part of an entry; the doubles follow
+VSPATIAL_MAX_VOXELS_LIMIT = 1 << 20
+VSPATIAL_DEFAULT_MAX_VOXELS = 1 << 17
+VSPATIAL_MAX_BALL_ROWS = 4096
+VSPATIAL_MAX_BALL_VOXELS = 1 << 23
+
+
+def _volume_spatial_call(fn, head, ids, intensity, m, units, max_voxels, peak_r):
+    """mi_unet_volume_spatial (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), intensity u16 of
+    the same shape, m components, units = the spacing (ux, uy, uz) as integers, max_voxels = None (the library's default) or the cap
+    of the pair sums, peak_r = the radius of the peak sphere in the spacing unit -> table VSPATIAL_DTYPE [m].  The library checks the
+    values."""
+    ids, intensity = _ids_intensity(ids, intensity)
+    d, hh, ww = ids.shape
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: ux, uy, uz")
+    table = np.zeros(max(int(m), 1), VSPATIAL_DTYPE)
+    opts = C.byref(VSpatialOpts(VSPATIAL_DEFAULT_MAX_VOXELS if max_voxels is None else int(max_voxels), int(peak_r)))
+    _check(fn(*head, _ptr(ids), _ptr(intensity), d, hh, ww, int(m), _ptr(un), opts, _ptr(table)))
+    return table
 
 
 def _volume_measure_call(fn, head, ids, intensity, m, units, max_ends):
@@ -762,6 +804,9 @@ def lib():
         L.mi_unet_volume_measure_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_measure.argtypes = [C.c_void_p] + L.mi_unet_volume_measure_host.argtypes
         L.mi_unet_volume_measure_derive.argtypes = [C.POINTER(VMeasure), C.c_void_p, C.c_double, C.POINTER(VMeasureShape)]
+        L.mi_unet_volume_spatial_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_spatial.argtypes = [C.c_void_p] + L.mi_unet_volume_spatial_host.argtypes
+        L.mi_unet_volume_spatial_derive.argtypes = [C.POINTER(VSpatial), C.c_void_p, C.c_double, C.POINTER(VSpatialMetrics)]
         L.mi_unet_volume_texture_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
@@ -1219,6 +1264,13 @@ class Engine:
         -> table VMEASURE_DTYPE [m]"""
         return _volume_measure_call(lib().mi_unet_volume_measure, (self._h,), ids, intensity, m, units, max_ends)
 
+    # ---- where the intensity of the components of a labelled stack sits (mi_unet_volume_spatial): needs the device, not the weights
+    def volume_spatial(self, ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, peak_r=0):
+        """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W], m = the components to take
+        (ids 1 .. m), units = the spacing (ux, uy, uz) as integers, max_voxels = the cap of the pair sums (None: 131072), peak_r = the
+        radius of the peak sphere in the spacing unit -> table VSPATIAL_DTYPE [m]"""
+        return _volume_spatial_call(lib().mi_unet_volume_spatial, (self._h,), ids, intensity, m, units, max_voxels, peak_r)
+
     # ---- the components of two labelled stacks matched (mi_unet_volume_match): needs the device, not the weights
     def volume_match(self, pred_ids, truth_ids, mp, mt, cap=4096):
         """pred_ids, truth_ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, mp and mt = the components a side
@@ -1448,6 +1500,22 @@ def volume_texture_derive(comp, hist, glcm=None):
     out = VTextureFeatures()
     _check(lib().mi_unet_volume_texture_derive(C.byref(comp), _ptr(hist), _ptr(glcm), int(hist.size), C.byref(out)))
     return {n: getattr(out, n) for n, _ in VTextureFeatures._fields_}
+
+
+def volume_spatial_host(ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, peak_r=0):
+    """mi_unet_volume_spatial_host: Engine.volume_spatial as sequential host arithmetic (needs no device)"""
+    return _volume_spatial_call(lib().mi_unet_volume_spatial_host, (), ids, intensity, m, units, max_voxels, peak_r)
+
+
+def volume_spatial_derive(comp, units, unit_mm):
+    """mi_unet_volume_spatial_derive of one component (a VSpatial, or one VSPATIAL_DTYPE record) with the spacing units (ux, uy, uz) and
+    the unit in mm -> dict of cx_mm .. cz_mm, icx_mm .. icz_mm, com_shift_mm, integrated_intensity, local_peak, global_peak, morans_i,
+    gearys_c"""
+    if not isinstance(comp, VSpatial):
+        comp = VSpatial(*[(float if t is C.c_double else int)(comp[n]) for n, t in VSpatial._fields_])
+    out = VSpatialMetrics()
+    _check(lib().mi_unet_volume_spatial_derive(C.byref(comp), (C.c_int * 3)(*[int(v) for v in units]), float(unit_mm), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VSpatialMetrics._fields_}
 
 
 def volume_measure_derive(comp, units, unit_mm):

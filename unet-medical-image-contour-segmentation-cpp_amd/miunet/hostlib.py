@@ -26,7 +26,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_interp", "medseg_get_volume_interp",
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
            "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones",
-           "medseg_set_volume_nbhood", "medseg_get_volume_nbhood"]
+           "medseg_set_volume_nbhood", "medseg_get_volume_nbhood", "medseg_set_volume_spatial", "medseg_get_volume_spatial"]
 
 
 def lib():
@@ -89,6 +89,9 @@ def lib():
         L.medseg_set_volume_measure.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_measure.argtypes = [_i, _i, _i]
         L.medseg_get_volume_measure.restype = None
+        L.medseg_set_volume_spatial.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
+        L.medseg_get_volume_spatial.argtypes = [_i, _i, _i, C.POINTER(C.c_double)]
+        L.medseg_get_volume_spatial.restype = None
         L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_match.argtypes = [_i, _i, _i]
         L.medseg_get_volume_match.restype = None
@@ -285,6 +288,22 @@ def get_volume_measure():
     on, channel, ends = C.c_int(), C.c_int(), C.c_int()
     lib().medseg_get_volume_measure(C.byref(on), C.byref(channel), C.byref(ends))
     return {"on": bool(on.value), "channel": channel.value, "max_ends": ends.value}
+
+
+VSPATIAL_DEFAULT_PEAK_MM = 6.2035           # the radius of the sphere of 1 cm^3
+
+
+def set_volume_spatial(on=True, channel=0, max_voxels=131072, peak_mm=VSPATIAL_DEFAULT_PEAK_MM) -> bool:
+    """MedicalSeg::set_volume_spatial: with set_volume on, process_image_batch adds Moran's I, Geary's C, the centre-of-mass shift, the
+    integrated intensity and the local / global intensity peak of every component of the labelled stack (mi_unet_volume_spatial over
+    `channel` of the normalised tiles) as a "spatial" member of volume_report.json; needs no engine"""
+    return lib().medseg_set_volume_spatial(int(bool(on)), int(channel), int(max_voxels), float(peak_mm)) == 0
+
+
+def get_volume_spatial():
+    on, channel, voxels, peak = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+    lib().medseg_get_volume_spatial(C.byref(on), C.byref(channel), C.byref(voxels), C.byref(peak))
+    return {"on": bool(on.value), "channel": channel.value, "max_voxels": voxels.value, "peak_mm": peak.value}
 
 
 VTEX_MODES = ("count", "width")            # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
