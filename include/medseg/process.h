@@ -201,6 +201,26 @@ struct VolumeSpatial {
 bool set_volume_spatial(const VolumeSpatial &spatial);
 VolumeSpatial get_volume_spatial();
 
+// Touching objects of the labelled stack split into pieces (mi_unet_volume_split in include/mi_unet.h).  It acts only
+// together with set_volume's `on`: behind the components stage, which still applies the size filter, one mi_unet_volume_split call per
+// target (mi_unet_volume_split_host under MEDSEG_HOST_POSTPROCESS=1) takes the stack that stage kept, under the setting's connectivity,
+// the integer units mi_unet_score_volume_units finds for the volume setting's spacing, neck_r = llround(neck_mm / unit_mm) as
+// set_volume_clean converts its radii, and `min_core`.  The PIECES' table, counts and ids then stand where the components' stood for
+// everything downstream: the report, measure, texture, zones, nbhood, spatial and the lesion matching of set_volume_match.  Every
+// component object of volume_report.json gains a last member "split": "core_voxels", "reach_mm", "cut_mm2"; every target object gains
+// a last member "split": "neck_mm", "cores", "cores_kept", "pieces", "coreless".  One log line per batch; a failure is reported as
+// "Volume split error: ..." and ends only this step: the report then shows the components, without the members.  With it off (the
+// default) every artefact and every log line is what it is without the setting.  Needs no engine and survives initialize_engine.
+// false, message on stderr, setting unchanged: a neck_mm that is not finite and >= 0, or a negative min_core.  A neck past the stage's
+// limit under the batch's units is reported when a batch runs.
+struct VolumeSplit {
+    bool on = false;
+    double neck_mm = 0.0;
+    int min_core = 1;
+};
+bool set_volume_split(const VolumeSplit &split);
+VolumeSplit get_volume_split();
+
 // The texture of every component of the labelled stack (mi_unet_volume_texture in include/mi_unet.h).  It acts only
 // together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits (beside the channel
 // set_volume_measure keeps, when the two differ), a failed slice all-zero; one mi_unet_volume_texture call per target

@@ -82,6 +82,10 @@ void medseg_get_volume_measure(int *on, int *channel, int *max_ends);
  * (include/medseg/process.h).  0 on success; medseg_get_volume_spatial fills the four values. */
 int medseg_set_volume_spatial(int on, int channel, int max_voxels, double peak_mm);
 void medseg_get_volume_spatial(int *on, int *channel, int *max_voxels, double *peak_mm);
+/* Touching objects of the labelled stack split into pieces: MedicalSeg::set_volume_split / get_volume_split
+ * (include/medseg/process.h).  0 on success; medseg_get_volume_split fills the three values. */
+int medseg_set_volume_split(int on, double neck_mm, int min_core);
+void medseg_get_volume_split(int *on, double *neck_mm, int *min_core);
 /* The scored stack per lesion: MedicalSeg::set_volume_match / get_volume_match (include/medseg/process.h).  0 on success;
  * medseg_get_volume_match fills the three values. */
 int medseg_set_volume_match(int on, int iou_num, int iou_den);

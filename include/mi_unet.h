@@ -1226,6 +1226,69 @@ int mi_unet_volume_spatial_host(const int32_t *ids, const uint16_t *intensity, i
                                 const mi_unet_vspatial_opts *opts, mi_unet_vspatial *table);
 int mi_unet_volume_spatial_derive(const mi_unet_vspatial *c, const int spacing_units[3], double unit_mm, mi_unet_vspatial_metrics *out);
 
+/* ---- Touching objects split: cores regrown by geodesic distance ----------------------------------------------------
+ * Two objects joined by a thin bridge are one component for every stage above.  This stage erodes a plane to its cores, labels the
+ * cores and grows them back inside the plane, and hands out the pieces in the layout of mi_unet_volume_components, so that every
+ * stage that takes a table or an id stack takes the pieces unchanged.  Exact integers; the bytes do not depend on scheduling.
+ *
+ * masks, values and n are those of mi_unet_volume_components: plane k is S = { masks == values[k] }, planes are independent.
+ * spacing_units = { ux, uy, uz } as mi_unet_volume_clean takes them.  opts = { connectivity, neck_r, min_core }, default { 26, 0, 1 }.
+ *   CORES   C = the erosion of S by mi_unet_volume_ball(spacing_units, neck_r), with mi_unet_volume_clean's border rule (only voxels
+ *           inside the volume constrain an erosion); a neck_r below every unit is the single voxel and C = S.  The cores are the
+ *           components of C under `connectivity` (6, 18, 26); one with fewer than min_core voxels is dropped.  The MARKER of a kept
+ *           core is its raster-first voxel index z * H * W + y * W + x.
+ *   GROWTH  Two voxels of S adjacent under `connectivity` are joined by a step whose cost is the sum of the units of the axes on
+ *           which they differ (a face step in x: ux; an edge step in x and z: ux + uz).  The length of a path inside S is the sum
+ *           of its steps.  key(v) = the lexicographic minimum of (length, marker) over all kept cores and all paths inside S from a
+ *           voxel of that core to v (core voxels: length 0); v belongs to the piece of that marker.  Ties in length go to the
+ *           smaller marker, so the rule is total.
+ *   REST    The voxels of S that no kept core reaches: their components under `connectivity` are pieces of their own, with no core.
+ * The pieces partition S, every piece is connected under `connectivity`, and inside one component of S either every piece has a
+ * core or the component is one coreless piece (DESIGN.md 7.21 proves the three).
+ *
+ * found[k]    the number of pieces of the plane, always exact.
+ * table[k]    [n][cap]: the first min(found, cap) pieces in mi_unet_volume_components' ORDER (voxels descending, `first` ascending);
+ *             voxels, first, the bounding box and sx, sy, sz are over the piece; kept = 1; value = values[k]; faces_x / _y / _z
+ *             count the faces towards a 6-neighbour that is NOT IN THE PIECE (outside S, outside the volume, or in another piece).
+ *             Entries behind found are zero.
+ * info[k]     [n][cap], may be NULL: mi_unet_vpiece of the same piece: core_first = the marker or -1 for a coreless piece,
+ *             core_voxels, reach = the largest length among the piece's keys (0 for a coreless piece), cut_x / _y / _z = those of the
+ *             table's faces whose neighbour is in S but in another piece.
+ * ids         [n][D][H][W] int32, may be NULL: 1 + the table index, -1 for a piece beyond cap, 0 outside S.
+ * stats[k]    may be NULL: value, in_voxels = |S|, core_voxels = |C|, cores, cores_kept, pieces, coreless, max_reach.
+ * rounds      int32 [n], may be NULL: how many rounds of the growth ran for the plane (the host form: 0).  Diagnostic; it depends on
+ *             scheduling and is no part of the stage's bytes.
+ *
+ * MI_UNET_EARG, nothing queued and no output touched:
+ *   D, H, W >= 1 and n * D * H * W < 2^31     voxel indices, markers and the forest are int32;
+ *   values are bytes, 1 .. MI_UNET_VOLUME_MAX_VALUES of them, none twice     a kernel argument holds them;
+ *   units and neck_r in 1 / 0 .. MI_UNET_VOLUME_CLEAN_MAX_R     r * r < 2^31, as in mi_unet_volume_clean;
+ *   connectivity one of 6, 18, 26; min_core >= 0; cap in 1 .. MI_UNET_VOLUME_MAX_TABLE     the table is sorted in one workgroup's LDS;
+ *   D * H * W * (ux + uy + uz) < 2^33     a shortest path visits a voxel at most once and a step costs at most ux + uy + uz, so every
+ *           length stays below 2^33 and a key is (length << 31) | marker in one unsigned 64-bit word; all ones = unreached.
+ * A workspace that cannot be allocated is MI_UNET_EHIP and the handle stays usable.  Works before weights are loaded, changes no
+ * setting, has no group form (mi_unet_group_handle(g, rank) hands out an engine to call it on).  mi_unet_volume_split_host takes the
+ * same arguments without the handle, is sequential (erosion from the definition, flood fill, Dijkstra) and gives the same bytes.
+ * mi_unet_volume_split_derive: reach_mm = reach * unit_mm, cut_mm2 = cut_x sy sz + cut_y sx sz + cut_z sx sy for a spacing in mm. */
+typedef struct mi_unet_vsplit_opts { int connectivity, neck_r, min_core; } mi_unet_vsplit_opts;     /* default { 26, 0, 1 } */
+typedef struct mi_unet_vpiece {        /* 40 bytes, no padding */
+    int32_t core_first, core_voxels;
+    int64_t reach;
+    int64_t cut_x, cut_y, cut_z;
+} mi_unet_vpiece;
+typedef struct mi_unet_vsplit_stat {   /* 64 bytes: 8 int64 */
+    int64_t value, in_voxels, core_voxels, cores, cores_kept, pieces, coreless, max_reach;
+} mi_unet_vsplit_stat;
+typedef struct mi_unet_vpiece_metrics { double reach_mm, cut_mm2; } mi_unet_vpiece_metrics;
+int mi_unet_volume_split(mi_unet_t *h, const uint8_t *masks /* [D][H][W] host */, int D, int H, int W, const int *values, int n,
+                         const int spacing_units[3], const mi_unet_vsplit_opts *opts, int32_t *ids /* [n][D][H][W] or NULL */,
+                         mi_unet_vcomp *table /* [n][cap] */, mi_unet_vpiece *info /* [n][cap] or NULL */, int cap, int32_t *found /* [n] */,
+                         mi_unet_vsplit_stat *stats /* [n] or NULL */, int32_t *rounds /* [n] or NULL */);
+int mi_unet_volume_split_host(const uint8_t *masks, int D, int H, int W, const int *values, int n, const int spacing_units[3],
+                              const mi_unet_vsplit_opts *opts, int32_t *ids, mi_unet_vcomp *table, mi_unet_vpiece *info, int cap,
+                              int32_t *found, mi_unet_vsplit_stat *stats, int32_t *rounds);
+int mi_unet_volume_split_derive(const mi_unet_vpiece *p, const double spacing_xyz[3], double unit_mm, mi_unet_vpiece_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

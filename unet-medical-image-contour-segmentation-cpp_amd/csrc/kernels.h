@@ -20,6 +20,7 @@ struct mi_unet_vmatch_pair;
 struct mi_unet_vtexture;
 struct mi_unet_vzones;
 struct mi_unet_vzone;
+struct mi_unet_vpiece;
 struct mi_unet_vnbhood;
 
 namespace miunet {
@@ -358,6 +359,18 @@ struct VolumeArgs { int D = 0, H = 0, W = 0, n = 0, cap = 0, connectivity = 26, 
 size_t volume_workspace_bytes(int D, int H, int W, int n);
 hipError_t launch_volume_components(const uint8_t *masks, const VolumeArgs &a, uint8_t *out, int32_t *ids, ::mi_unet_vcomp *table,
                                     int32_t *counts, void *ws, hipStream_t s);
+// The exact selection of volume.hip by itself, for a stage that ranks slots of its own by the same keys (volume_split.hip): acc [n],
+// key [n][S]; acc[k].nroots keys of plane k are looked at; acc[k].thr[0] = the a.keep_largest-th largest of them, thr[1] = the a.cap-th
+// largest, each left alone (the caller zeroes it: every key passes) when the plane has no more keys than that.
+struct VolumeRankAcc {
+    unsigned nroots;                // the cursor of the plane's slots: its components
+    unsigned n_min;                 // roots with voxels >= min_voxels
+    unsigned overflow;              // a root found no slot (cannot happen: see slots_per_plane); the call fails instead of writing past the end
+    unsigned pad;
+    unsigned long long thr[2];      // the smallest key the filter's keep_largest keeps, the smallest key in the table; 0 = every key
+};
+size_t volume_slots_per_plane(size_t dhw);
+hipError_t launch_volume_select(const VolumeArgs &a, unsigned S, VolumeRankAcc *acc, const unsigned long long *key, hipStream_t s);
 
 // Volume clean-up (volume_clean.hip; include/mi_unet.h: mi_unet_volume_clean).  masks u8 [D][H][W] on the device; plane
 // k is the set { masks == v[k] }.  One launch sequence for all n planes:
@@ -376,6 +389,34 @@ struct VolumeCleanArgs { int D = 0, H = 0, W = 0, n = 0, ux = 1, uy = 1, uz = 1,
 size_t volume_clean_workspace_bytes(int D, int H, int W, int n);
 hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, uint8_t *out, unsigned long long *counts, void *ws,
                                hipStream_t s);
+// the erosion by B(a.open_r) alone: cores u8 [n][D][H][W] = 0 / 1; counts[4 k] = the plane's voxels, counts[4 k + 3] = its core voxels
+// unless the ball is the single voxel (then the cores are the set).  The same workspace.
+hipError_t launch_volume_erode(const uint8_t *masks, const VolumeCleanArgs &a, uint8_t *cores, unsigned long long *counts, void *ws,
+                               hipStream_t s);
+
+// Volume split (volume_split.hip; include/mi_unet.h: mi_unet_volume_split).  masks u8 [D][H][W] on the device; plane k
+// is the set { masks == v[k] }.  Exact integers: minima of unique 64-bit keys, sums, counts; nothing depends on the order of atomics.
+//   launch_volume_split_seed   : the cores (launch_volume_erode), their labels by the lock-free union-find, their sizes, then the keys:
+//                                a voxel of a kept core holds (0, marker), every other voxel the all-ones "unreached"; the tiles that
+//                                hold a voxel of a kept core, or a neighbour of one, are flagged for round 0.
+//   launch_volume_split_round  : one round of the growth: a workgroup per flagged tile of VTX_TZ x VTX_TY x VTX_TX voxels relaxes the
+//                                tile in LDS to its fixed point under the halo it read, stores what changed and flags the neighbour
+//                                tiles that share a changed boundary voxel for round + 1.  active[k] += the tiles of plane k that ran.
+//                                The caller queues rounds until one reports no tile; rounds that find no flag do nothing.
+//   launch_volume_split_finish : the rest labelled by the union-find, a slot per piece, the pieces' sums, the order (launch_volume_select),
+//                                table, info and ids; res[k] = the plane's counts, found = -1 should the slot table overflow.
+// Workspace: volume_split_workspace_bytes(D, H, W, n), not zeroed by the caller.  n * D * H * W < 2^31, D H W (ux + uy + uz) < 2^33.
+constexpr int VSPLIT_BATCH = 8;                         // rounds queued between two looks at the activity
+struct VolumeSplitArgs {
+    int D = 0, H = 0, W = 0, n = 0, cap = 0, ux = 1, uy = 1, uz = 1, connectivity = 26, neck_r = 0, min_core = 1;
+    int v[VOLUME_MAX_VALUES] = {};
+};
+struct VolumeSplitResult { long long in_voxels, core_voxels, cores, cores_kept, coreless, max_reach; int found, reserved; };
+size_t volume_split_workspace_bytes(int D, int H, int W, int n);
+hipError_t launch_volume_split_seed(const uint8_t *masks, const VolumeSplitArgs &a, void *ws, hipStream_t s);
+hipError_t launch_volume_split_round(const uint8_t *masks, const VolumeSplitArgs &a, void *ws, int round, unsigned *active, hipStream_t s);
+hipError_t launch_volume_split_finish(const uint8_t *masks, const VolumeSplitArgs &a, int32_t *ids, ::mi_unet_vcomp *table,
+                                      ::mi_unet_vpiece *info, VolumeSplitResult *res, void *ws, hipStream_t s);
 
 // Volume mesh (volume_mesh.hip; include/mi_unet.h: mi_unet_volume_mesh).  masks u8 [D][H][W] on the device; one plane,
 // the set { masks == value }, per call pair.  Every output position comes from a scan: nothing depends on the order in which atomics

@@ -17,14 +17,7 @@ constexpr int RUN = 16;                                  // 64-voxel segments a 
 constexpr int RADIX_BITS = 11, RADIX_BINS = 1 << RADIX_BITS, RADIX_PASSES = 6;      // 6 x 11 = 66 bits cover the 62-bit key
 constexpr int LIST_BLOCKS = 1024;                        // most workgroups per plane in the pass over the slots
 
-// The accumulators of one plane, zeroed on the stream before the first kernel.
-struct PlaneAcc {
-    unsigned nroots;                // the cursor of the plane's slots: its components
-    unsigned n_min;                 // roots with voxels >= min_voxels
-    unsigned overflow;              // a root found no slot (cannot happen: see slots_per_plane); the call fails instead of writing past the end
-    unsigned pad;
-    unsigned long long thr[2];      // the smallest key the filter's keep_largest keeps, the smallest key in the table; 0 = every key
-};
+typedef VolumeRankAcc PlaneAcc;       // (kernels.h) the accumulators of one plane, zeroed on the stream before the first kernel
 
 // A plane has at most ceil(D H W / 2) components under every connectivity: one voxel of each is an independent set of the grid graph,
 // which has a Hamiltonian path (the serpentine), and an independent set takes at most every other vertex of a path.
@@ -410,6 +403,14 @@ __global__ __launch_bounds__(256) void k_vol_write(VolumeArgs a, unsigned dhw, u
 }
 
 }  // namespace vl
+
+size_t volume_slots_per_plane(size_t dhw) { return vl::slots_per_plane(dhw); }
+
+hipError_t launch_volume_select(const VolumeArgs &a, unsigned S, VolumeRankAcc *acc, const unsigned long long *key, hipStream_t s)
+{
+    hipLaunchKernelGGL(vl::k_vol_select, dim3(2u * a.n), dim3(256), 0, s, a, S, acc, key);
+    return hipGetLastError();
+}
 
 size_t volume_workspace_bytes(int D, int H, int W, int n) { return vl::carve(nullptr, (size_t)D * H * W, n).total; }
 

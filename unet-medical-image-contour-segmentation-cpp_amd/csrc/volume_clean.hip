@@ -241,6 +241,33 @@ __global__ __launch_bounds__(256) void k_vc_emit(const uint8_t *__restrict__ cur
     out[(size_t)k * dhw + i] = cur[(size_t)k * dhw + i] ? (uint8_t)pick_value(a.v, (int)k) : (uint8_t)0;
 }
 
+// One ball of a call: the half-widths cut to the sides they run along.  A radius below every unit is the single voxel: no morphology.
+inline Ball make_ball(const VolumeCleanArgs &a, int r)
+{
+    Ball b;
+    b.ux = a.ux; b.uy = a.uy; b.uz = a.uz; b.r2 = (unsigned)r * (unsigned)r;
+    b.ex = r / a.ux < a.W - 1 ? r / a.ux : a.W - 1;
+    b.ey = r / a.uy < a.H - 1 ? r / a.uy : a.H - 1;
+    b.ez = r / a.uz < a.D - 1 ? r / a.uz : a.D - 1;
+    return b;
+}
+inline bool single_voxel(const VolumeCleanArgs &a, int r) { return r / a.ux == 0 && r / a.uy == 0 && r / a.uz == 0; }
+
+// one dilation (inv == 0) or erosion (inv == 1) of every plane by the ball b, in place in w.cur: the three passes
+struct Morph {
+    Ws w;
+    const VolumeCleanArgs &a;
+    hipStream_t s;
+    void run(const Ball &b, int inv, unsigned long long *count) const
+    {
+        const unsigned hw = (unsigned)a.H * (unsigned)a.W, dhw = (unsigned)a.D * hw;
+        const dim3 blk(256), gv((dhw + 255u) / 256u, (unsigned)a.n), gc((hw + 255u) / 256u, (unsigned)a.n);
+        hipLaunchKernelGGL(k_vc_z, gc, blk, 0, s, w.cur, inv, a.D, hw, b.ez, w.g);
+        hipLaunchKernelGGL(k_vc_y, gv, blk, 0, s, w.g, dhw, a.H, a.W, b, w.f);
+        hipLaunchKernelGGL(k_vc_x, gv, blk, 0, s, w.f, inv, dhw, a.W, b, w.cur, count);
+    }
+};
+
 }  // namespace vc
 
 size_t volume_clean_workspace_bytes(int D, int H, int W, int n) { return vc::carve(nullptr, (size_t)D * H * W * n).total; }
@@ -260,7 +287,7 @@ hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, u
     vc::Vals vals;
     for (int k = 0; k < VOLUME_MAX_VALUES; ++k) vals.v[k] = a.v[k];
     if (hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * 4 * sizeof(unsigned long long), s)) return e;
-    const dim3 blk(256), gv((dhw + 255u) / 256u, (unsigned)n), gc((hw + 255u) / 256u, (unsigned)n);
+    const dim3 blk(256), gv((dhw + 255u) / 256u, (unsigned)n);
     if (a.fill) {
         int *const parent = reinterpret_cast<int *>(w.f);
         uint8_t *const flag = reinterpret_cast<uint8_t *>(w.g);
@@ -273,21 +300,10 @@ hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, u
     } else {
         hipLaunchKernelGGL(vc::k_vc_set, gv, blk, 0, s, masks, vals, dhw, w.cur, counts);
     }
-    // one dilation (inv == 0) or erosion (inv == 1) of every plane by the ball b, in place in cur
-    auto morph = [&](const vc::Ball &b, int inv, unsigned long long *count) {
-        hipLaunchKernelGGL(vc::k_vc_z, gc, blk, 0, s, w.cur, inv, D, hw, b.ez, w.g);
-        hipLaunchKernelGGL(vc::k_vc_y, gv, blk, 0, s, w.g, dhw, H, W, b, w.f);
-        hipLaunchKernelGGL(vc::k_vc_x, gv, blk, 0, s, w.f, inv, dhw, W, b, w.cur, count);
-    };
-    auto ball = [&](int r) {
-        vc::Ball b;
-        b.ux = a.ux; b.uy = a.uy; b.uz = a.uz; b.r2 = (unsigned)r * (unsigned)r;
-        b.ex = r / a.ux < W - 1 ? r / a.ux : W - 1;
-        b.ey = r / a.uy < H - 1 ? r / a.uy : H - 1;
-        b.ez = r / a.uz < D - 1 ? r / a.uz : D - 1;
-        return b;
-    };
-    auto single = [&](int r) { return r / a.ux == 0 && r / a.uy == 0 && r / a.uz == 0; };
+    const vc::Morph m{ w, a, s };
+    auto morph = [&](const vc::Ball &b, int inv, unsigned long long *count) { m.run(b, inv, count); };
+    auto ball = [&](int r) { return vc::make_ball(a, r); };
+    auto single = [&](int r) { return vc::single_voxel(a, r); };
     if (!single(a.close_r)) {
         const vc::Ball b = ball(a.close_r);
         morph(b, 0, nullptr);
@@ -299,6 +315,29 @@ hipError_t launch_volume_clean(const uint8_t *masks, const VolumeCleanArgs &a, u
         morph(b, 0, counts + 3);
     }
     hipLaunchKernelGGL(vc::k_vc_emit, gv, blk, 0, s, w.cur, vals, dhw, out);
+    return hipGetLastError();
+}
+
+// The erosion alone, for mi_unet_volume_split's cores: cores [n][D][H][W] = 0 / 1, the erosion of every plane's set by B(a.open_r);
+// counts[4 k] = the plane's voxels, counts[4 k + 3] = its core voxels (a single-voxel ball: the cores are the set and only
+// counts[4 k] is written).  a.fill and a.close_r are not looked at.  The same workspace as launch_volume_clean.
+hipError_t launch_volume_erode(const uint8_t *masks, const VolumeCleanArgs &a, uint8_t *cores, unsigned long long *counts, void *ws, hipStream_t s)
+{
+    const int D = a.D, H = a.H, W = a.W, n = a.n;
+    if (!masks || !cores || !counts || !ws || D < 1 || H < 1 || W < 1 || n < 1 || n > VOLUME_MAX_VALUES) return hipErrorInvalidValue;
+    const unsigned long long dhw64 = (unsigned long long)D * H * W, N64 = dhw64 * n;
+    if ((unsigned long long)D * H > 0x7FFFFFFFull || N64 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    for (int u : { a.ux, a.uy, a.uz })
+        if (u < 1 || u > VOLUME_CLEAN_MAX_R) return hipErrorInvalidValue;
+    if (a.open_r < 0 || a.open_r > VOLUME_CLEAN_MAX_R) return hipErrorInvalidValue;
+    const unsigned dhw = (unsigned)dhw64;
+    vc::Ws w = vc::carve(ws, (size_t)N64);
+    w.cur = cores;                                              // the passes work in place in the caller's array
+    vc::Vals vals;
+    for (int k = 0; k < VOLUME_MAX_VALUES; ++k) vals.v[k] = a.v[k];
+    if (hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * 4 * sizeof(unsigned long long), s)) return e;
+    hipLaunchKernelGGL(vc::k_vc_set, dim3((dhw + 255u) / 256u, (unsigned)n), dim3(256), 0, s, masks, vals, dhw, w.cur, counts);
+    if (!vc::single_voxel(a, a.open_r)) vc::Morph{ w, a, s }.run(vc::make_ball(a, a.open_r), 1, counts + 3);
     return hipGetLastError();
 }
 

@@ -222,6 +222,12 @@ void medseg_get_volume_spatial(int *on, int *channel, int *max_voxels, double *p
     const MedicalSeg::VolumeSpatial v = MedicalSeg::get_volume_spatial();
     *on = v.on; *channel = v.channel; *max_voxels = v.max_voxels; *peak_mm = v.peak_mm;
 }
+int medseg_set_volume_split(int on, double neck_mm, int min_core) { return MedicalSeg::set_volume_split({ on != 0, neck_mm, min_core }) ? 0 : 1; }
+void medseg_get_volume_split(int *on, double *neck_mm, int *min_core)
+{
+    const MedicalSeg::VolumeSplit v = MedicalSeg::get_volume_split();
+    *on = v.on; *neck_mm = v.neck_mm; *min_core = v.min_core;
+}
 int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width)
 {
     return MedicalSeg::set_volume_texture({ on != 0, channel, mode, levels, lo, width }) ? 0 : 1;

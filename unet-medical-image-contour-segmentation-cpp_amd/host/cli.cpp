@@ -163,6 +163,7 @@ public:
         table_["volinterp"] = [this](const Words &w) { cmd_volinterp(w); return true; };
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["volspatial"] = [this](const Words &w) { cmd_volspatial(w); return true; };
+        table_["volsplit"] = [this](const Words &w) { cmd_volsplit(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
         table_["volnbhood"] = [this](const Words &w) { cmd_volnbhood(w); return true; };
@@ -190,6 +191,7 @@ public:
             "  volinterp on [factor N|iso]|off - With volume on: shape-based slices between the slices before the stack is meshed (iso: spacing_z / in-plane)",
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  volspatial on [channel N] [voxels N] [peak MM]|off - With volume on: Moran's I, Geary's C, centre-of-mass shift and intensity peaks of every component in the report",
+            "  volsplit on [neck MM] [mincore N]|off - With volume on: touching components split into pieces (cores of a ball of MM regrown by geodesic distance); the report and every stage behind it take the pieces",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
             "  volnbhood on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N]|off - With volume on: neighbourhood-difference, dependence and distance-zone features of every component in the report",
@@ -547,6 +549,30 @@ private:
         const MedicalSeg::VolumeSpatial cur = MedicalSeg::get_volume_spatial();
         std::cout << "Volume spatial: " << (cur.on ? "on" : "off") << " channel " << cur.channel << " voxels " << cur.max_voxels << " peak " << cur.peak_mm
                   << std::endl;
+    }
+
+    // volsplit on [neck MM] [mincore N] | volsplit off | volsplit (prints the setting in force)
+    void cmd_volsplit(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeSplit v;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            v.on = w[1] == "on";
+            for (size_t i = 2; ok && i < w.size(); i += 2) {
+                if (i + 1 < w.size() && w[i] == "neck") ok = to_double(w[i + 1], v.neck_mm);
+                else ok = i + 1 < w.size() && w[i] == "mincore" && to_int(w[i + 1], v.min_core);
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volsplit command (expected on [neck MM] [mincore N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_split(v)) {
+                std::cerr << "Volume split unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeSplit cur = MedicalSeg::get_volume_split();
+        std::cout << "Volume split: " << (cur.on ? "on" : "off") << " neck " << cur.neck_mm << " mincore " << cur.min_core << std::endl;
     }
 
     // The words of a texture command behind its name -- on [levels N] [count | width W [lo L]] [channel N] and the command's own `word N`

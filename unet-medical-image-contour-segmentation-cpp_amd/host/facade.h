@@ -38,6 +38,7 @@ struct Settings {
     VolumeInterp volume_interp;                            // off; acts only with volume.on (process_image_batch reads it)
     VolumeMeasure volume_measure;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeSpatial volume_spatial;                          // off; acts only with volume.on (process_image_batch reads it)
+    VolumeSplit volume_split;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeTexture volume_texture;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeZones volume_zones;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeNbhood volume_nbhood;                            // off; acts only with volume.on (process_image_batch reads it)

@@ -397,6 +397,20 @@ bool set_volume_spatial(const VolumeSpatial &spatial)
         /*handle_side=*/false);
 }
 
+bool set_volume_split(const VolumeSplit &split)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_split = split;
+            if (!(std::isfinite(split.neck_mm) && split.neck_mm >= 0.0)) return std::string("volume split: neck_mm is finite and not negative");
+            return std::string(split.min_core >= 0 ? "" : "volume split: min_core is not negative");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume split: " << (split.on ? "on" : "off") << ", neck " << split.neck_mm << " mm, mincore " << split.min_core;
+        },
+        /*handle_side=*/false);
+}
+
 namespace {
 
 // The five fields a texture setting (VolumeTexture, VolumeZones, VolumeNbhood) begins with: what is wrong with the first of them that is
@@ -495,6 +509,7 @@ VolumeMesh get_volume_mesh() { return current_settings().volume_mesh; }
 VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeSpatial get_volume_spatial() { return current_settings().volume_spatial; }
+VolumeSplit get_volume_split() { return current_settings().volume_split; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeZones get_volume_zones() { return current_settings().volume_zones; }
 VolumeNbhood get_volume_nbhood() { return current_settings().volume_nbhood; }

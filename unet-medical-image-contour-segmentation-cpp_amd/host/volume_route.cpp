@@ -520,6 +520,70 @@ Members spatial_volume(const VolumeStack &st, const std::vector<int32_t> &ids, c
     }
 }
 
+// set_volume_split: per target one mi_unet_volume_split call on `h` (mi_unet_volume_split_host under MEDSEG_HOST_POSTPROCESS=1) over
+// `labelled` ([K][D][H][W], the stack the components stage kept) with values = { 255 }, the volume setting's connectivity, the integer
+// units of mi_unet_score_volume_units and neck_r = llround(neck_mm / unit_mm).  On success the pieces' table, counts and (when `ids` is
+// not empty) ids stand where the components' stood -- every piece is kept -- and `members` / `target_members` hold the "split" member of
+// every row and of every target, from its leading comma on.  A failure is reported and leaves everything as the components stage
+// wrote it: only this step ends.
+struct SplitMembers {
+    std::vector<std::vector<std::string>> rows;
+    std::vector<std::string> targets;
+};
+SplitMembers split_volume(const uint8_t *labelled, size_t D, size_t hw, size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg,
+                          std::vector<mi_unet_vcomp> &table, std::vector<int32_t> &found, std::vector<int32_t> &kept, std::vector<int32_t> &ids)
+{
+    try {
+        const size_t K = s.targets.size();
+        const VolumeSplit &sp = s.volume_split;
+        const VolumeUnits u = volume_units(s.volume, D);
+        const double q = sp.neck_mm / u.unit_mm;
+        if (!(q <= (double)MI_UNET_VOLUME_CLEAN_MAX_R))
+            throw std::runtime_error("a neck of " + json_number(sp.neck_mm) + " mm is more than " + std::to_string(MI_UNET_VOLUME_CLEAN_MAX_R) + " units");
+        const mi_unet_vsplit_opts opts{ s.volume.connectivity, (int)std::llround(q), sp.min_core };
+        const double spacing[3] = { s.volume.spacing_x, s.volume.spacing_y, s.volume.spacing_z };
+        const int value = 255;
+        std::vector<mi_unet_vcomp> pieces(K * cap);
+        std::vector<mi_unet_vpiece> info(K * cap);
+        std::vector<int32_t> piece_ids(ids.size()), piece_found(K);
+        std::vector<mi_unet_vsplit_stat> stats(K);
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t)
+            stage_call(h, mi_unet_volume_split, mi_unet_volume_split_host, labelled + t * D * hw, (int)D, g_cfg.height, g_cfg.width, &value, 1, u.units,
+                       &opts, piece_ids.empty() ? nullptr : piece_ids.data() + t * D * hw, pieces.data() + t * cap, info.data() + t * cap, (int)cap,
+                       &piece_found[t], &stats[t], nullptr);
+        SplitMembers m;
+        m.rows.resize(K);
+        m.targets.resize(K);
+        int64_t all = 0;
+        for (size_t t = 0; t < K; ++t) {
+            const size_t rows = std::min<size_t>((size_t)piece_found[t], cap);
+            for (size_t r = 0; r < rows; ++r) {
+                const mi_unet_vpiece &p = info[t * cap + r];
+                mi_unet_vpiece_metrics pm{};
+                checked(mi_unet_volume_split_derive, &p, spacing, u.unit_mm, &pm);
+                m.rows[t].push_back(", \"split\": {\"core_voxels\": " + std::to_string(p.core_voxels) + ", \"reach_mm\": " + json_number(pm.reach_mm) +
+                                    ", \"cut_mm2\": " + json_number(pm.cut_mm2) + "}");
+            }
+            const mi_unet_vsplit_stat &st = stats[t];
+            m.targets[t] = ", \"split\": {\"neck_mm\": " + json_number(sp.neck_mm) + ", \"cores\": " + std::to_string(st.cores) + ", \"cores_kept\": " +
+                           std::to_string(st.cores_kept) + ", \"pieces\": " + std::to_string(st.pieces) + ", \"coreless\": " +
+                           std::to_string(st.coreless) + "}";
+            all += st.pieces;
+        }
+        lg << "Volume split: " << D << " slices, " << K << " targets, neck " << opts.neck_r << " units (unit " << u.unit_mm << " mm), " << all
+           << " pieces, " << ms_since(t0) << " ms" << std::endl;
+        table.swap(pieces);
+        ids.swap(piece_ids);
+        kept = piece_found;
+        found.swap(piece_found);
+        return m;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume split error: ") + e.what());
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -531,7 +595,9 @@ Members spatial_volume(const VolumeStack &st, const std::vector<int32_t> &ids, c
 // the components stage also hands out its ids, they are measured (measure_volume) and every component object gains a last member
 // "measure".  With set_volume_texture on, the ids are handed out likewise and every component object gains a last member "texture"
 // (texture_volume), with set_volume_zones on a last member "zones" behind it (zones_volume), and with set_volume_nbhood on a last member
-// "nbhood" behind that (nbhood_volume), and with set_volume_spatial on a last member "spatial" behind them all (spatial_volume).  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
+// "nbhood" behind that (nbhood_volume), and with set_volume_spatial on a last member "spatial" behind them all (spatial_volume).  With set_volume_split on, the planes that were labelled are split behind the components stage
+// (split_volume) and everything below -- the report, the stages above, `numbered` -- takes the pieces' table, counts and ids; every
+// component object gains a last member "split" and every target object one too.  With `numbered` given (set_volume_match) the ids [K][D][H][W] and the counts per target are handed out too; it stays
 // empty after a failure.
 struct VolumeIds {
     std::vector<int32_t> ids, found;
@@ -558,6 +624,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         lg << "Volume: " << D << " slices, " << K << " targets, connectivity " << v.connectivity << ", " << ms_since(t0) << " ms" << std::endl;
         // the stack the mesh sees: with set_volume_interp on, its interpolated form under spacing_z / factor (the original after a failure)
         const uint8_t *const labelled = filter ? out.data() : st.planes.data();
+        const SplitMembers split = s.volume_split.on ? split_volume(labelled, D, hw, cap, s, h, lg, table, found, kept, ids) : SplitMembers();
         std::vector<uint8_t> fine;
         int factor = 1;
         const std::string interp_json = s.volume_interp.on ? interp_volume(labelled, D, hw, s, h, lg, fine, factor) : std::string();
@@ -606,9 +673,10 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << ", \"surface_mm2\": " << json_number(m.surface_mm2) << ", \"extent_mm\": [" << json_number(m.extent_x_mm) << ", "
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
                    << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r])
-                   << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << (spatialised.empty() ? std::string() : spatialised[t][r]) << "}";
+                   << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << (spatialised.empty() ? std::string() : spatialised[t][r])
+                   << (split.rows.empty() ? std::string() : split.rows[t][r]) << "}";
             }
-            js << (rows ? "\n    " : "") << "]}";
+            js << (rows ? "\n    " : "") << "]" << (split.targets.empty() ? std::string() : split.targets[t]) << "}";
         }
         js << "\n  ]" << interp_json << mesh_json << "\n}\n";
         VolumeArtefacts a;

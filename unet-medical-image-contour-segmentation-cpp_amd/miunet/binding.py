@@ -40,6 +40,7 @@ EXPORTS = [
     "mi_unet_volume_mesh", "mi_unet_volume_mesh_host", "mi_unet_volume_mesh_positions", "mi_unet_volume_mesh_derive",
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
     "mi_unet_volume_spatial", "mi_unet_volume_spatial_host", "mi_unet_volume_spatial_derive",
+    "mi_unet_volume_split", "mi_unet_volume_split_host", "mi_unet_volume_split_derive",
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
@@ -222,6 +223,54 @@ def _volume_call(fn, head, masks, values, connectivity, min_voxels, keep_largest
     _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, C.byref(VolumeOpts(int(connectivity), int(min_voxels), int(keep_largest))),
               _ptr(out), _ptr(ids), _ptr(table), int(cap), _ptr(found), _ptr(kept)))
     return out, table, found, kept, ids
+
+
+class VPiece(C.Structure):
+    """mi_unet_vpiece: 40 bytes, two int32 then four int64; VPIECE_DTYPE is the same layout for numpy"""
+    _fields_ = [("core_first", C.c_int32), ("core_voxels", C.c_int32), ("reach", C.c_int64), ("cut_x", C.c_int64), ("cut_y", C.c_int64),
+                ("cut_z", C.c_int64)]
+
+
+class VSplitStat(C.Structure):
+    """mi_unet_vsplit_stat: 64 bytes, eight int64; VSPLIT_STAT_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int64) for n in ("value", "in_voxels", "core_voxels", "cores", "cores_kept", "pieces", "coreless", "max_reach")]
+
+
+VPIECE_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in VPiece._fields_])
+VSPLIT_STAT_DTYPE = np.dtype([(n, np.int64) for n, _ in VSplitStat._fields_])
+
+
+class VSplitOpts(C.Structure):
+    _fields_ = [("connectivity", C.c_int), ("neck_r", C.c_int), ("min_core", C.c_int)]
+
+
+class VPieceMetrics(C.Structure):
+    _fields_ = [("reach_mm", C.c_double), ("cut_mm2", C.c_double)]
+
+
+def _volume_split_call(fn, head, masks, values, units, connectivity, neck_r, min_core, cap, want_ids):
+    """mi_unet_volume_split (head = (handle,)) or its host form (head = ()): masks u8 [D,H,W] (or [H,W]: one slice), units (ux, uy, uz)
+    -> dict(table VCOMP_DTYPE [n, cap], info VPIECE_DTYPE [n, cap], found int32 [n], stats VSPLIT_STAT_DTYPE [n], ids int32 [n,D,H,W] or
+    None, rounds int32 [n]).  The library checks the values."""
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if masks.ndim == 2:
+        masks = masks[None]
+    if masks.ndim != 3:
+        raise ValueError(f"masks {masks.shape} must be one u8 [D,H,W] array")
+    d, hh, ww = masks.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: x, y, z")
+    n = max(vals.size, 1)
+    ids = np.zeros((n, d, hh, ww), np.int32) if want_ids else None
+    table = np.zeros((n, max(int(cap), 1)), VCOMP_DTYPE)
+    info = np.zeros((n, max(int(cap), 1)), VPIECE_DTYPE)
+    found, rounds = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    stats = np.zeros(n, VSPLIT_STAT_DTYPE)
+    _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, _ptr(un), C.byref(VSplitOpts(int(connectivity), int(neck_r), int(min_core))),
+              _ptr(ids), _ptr(table), _ptr(info), int(cap), _ptr(found), _ptr(stats), _ptr(rounds)))
+    return dict(table=table, info=info, found=found, stats=stats, ids=ids, rounds=rounds)
 
 
 class VCleanStat(C.Structure):
@@ -807,6 +856,10 @@ def lib():
         L.mi_unet_volume_spatial_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_spatial.argtypes = [C.c_void_p] + L.mi_unet_volume_spatial_host.argtypes
         L.mi_unet_volume_spatial_derive.argtypes = [C.POINTER(VSpatial), C.c_void_p, C.c_double, C.POINTER(VSpatialMetrics)]
+        L.mi_unet_volume_split_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_split.argtypes = [C.c_void_p] + L.mi_unet_volume_split_host.argtypes
+        L.mi_unet_volume_split_derive.argtypes = [C.POINTER(VPiece), C.POINTER(C.c_double), C.c_double, C.POINTER(VPieceMetrics)]
         L.mi_unet_volume_texture_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
@@ -1264,6 +1317,13 @@ class Engine:
         -> table VMEASURE_DTYPE [m]"""
         return _volume_measure_call(lib().mi_unet_volume_measure, (self._h,), ids, intensity, m, units, max_ends)
 
+    # ---- touching objects split into pieces (mi_unet_volume_split): needs the device, not the weights
+    def volume_split(self, masks, values, units=(1, 1, 1), connectivity=26, neck_r=0, min_core=1, cap=256, want_ids=False):
+        """masks u8 [D,H,W] of any size, values = the bytes whose sets are split, units = the spacing (ux, uy, uz), neck_r = the radius
+        of the eroding ball in the spacing unit -> dict(table VCOMP_DTYPE [n, cap], info VPIECE_DTYPE [n, cap], found, stats
+        VSPLIT_STAT_DTYPE [n], ids int32 [n,D,H,W] when want_ids, rounds)"""
+        return _volume_split_call(lib().mi_unet_volume_split, (self._h,), masks, values, units, connectivity, neck_r, min_core, cap, want_ids)
+
     # ---- where the intensity of the components of a labelled stack sits (mi_unet_volume_spatial): needs the device, not the weights
     def volume_spatial(self, ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, peak_r=0):
         """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W], m = the components to take
@@ -1505,6 +1565,21 @@ def volume_texture_derive(comp, hist, glcm=None):
 def volume_spatial_host(ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, peak_r=0):
     """mi_unet_volume_spatial_host: Engine.volume_spatial as sequential host arithmetic (needs no device)"""
     return _volume_spatial_call(lib().mi_unet_volume_spatial_host, (), ids, intensity, m, units, max_voxels, peak_r)
+
+
+def volume_split_host(masks, values, units=(1, 1, 1), connectivity=26, neck_r=0, min_core=1, cap=256, want_ids=False):
+    """mi_unet_volume_split_host: Engine.volume_split as sequential host arithmetic (needs no device)"""
+    return _volume_split_call(lib().mi_unet_volume_split_host, (), masks, values, units, connectivity, neck_r, min_core, cap, want_ids)
+
+
+def volume_split_derive(piece, spacing, unit_mm):
+    """mi_unet_volume_split_derive of one piece (a VPiece, or one VPIECE_DTYPE record) with spacing (sx, sy, sz) in mm and the length of
+    the spacing unit in mm -> dict(reach_mm, cut_mm2)"""
+    if not isinstance(piece, VPiece):
+        piece = VPiece(*[int(piece[n]) for n, _ in VPiece._fields_])
+    out = VPieceMetrics()
+    _check(lib().mi_unet_volume_split_derive(C.byref(piece), (C.c_double * 3)(*[float(v) for v in spacing]), float(unit_mm), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VPieceMetrics._fields_}
 
 
 def volume_spatial_derive(comp, units, unit_mm):

@@ -26,7 +26,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_interp", "medseg_get_volume_interp",
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
            "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones",
-           "medseg_set_volume_nbhood", "medseg_get_volume_nbhood", "medseg_set_volume_spatial", "medseg_get_volume_spatial"]
+           "medseg_set_volume_nbhood", "medseg_get_volume_nbhood", "medseg_set_volume_spatial", "medseg_get_volume_spatial",
+           "medseg_set_volume_split", "medseg_get_volume_split"]
 
 
 def lib():
@@ -92,6 +93,9 @@ def lib():
         L.medseg_set_volume_spatial.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
         L.medseg_get_volume_spatial.argtypes = [_i, _i, _i, C.POINTER(C.c_double)]
         L.medseg_get_volume_spatial.restype = None
+        L.medseg_set_volume_split.argtypes = [C.c_int, C.c_double, C.c_int]
+        L.medseg_get_volume_split.argtypes = [_i, C.POINTER(C.c_double), _i]
+        L.medseg_get_volume_split.restype = None
         L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_match.argtypes = [_i, _i, _i]
         L.medseg_get_volume_match.restype = None
@@ -304,6 +308,20 @@ def get_volume_spatial():
     on, channel, voxels, peak = C.c_int(), C.c_int(), C.c_int(), C.c_double()
     lib().medseg_get_volume_spatial(C.byref(on), C.byref(channel), C.byref(voxels), C.byref(peak))
     return {"on": bool(on.value), "channel": channel.value, "max_voxels": voxels.value, "peak_mm": peak.value}
+
+
+def set_volume_split(on=True, neck_mm=0.0, min_core=1) -> bool:
+    """MedicalSeg::set_volume_split: with set_volume on, process_image_batch splits the touching objects of the labelled stack
+    (mi_unet_volume_split behind the components stage: cores of the erosion by a ball of neck_mm, regrown by geodesic distance) and
+    hands the pieces to the report and to every stage behind it; every component and every target of volume_report.json gains a
+    "split" member; needs no engine"""
+    return lib().medseg_set_volume_split(int(bool(on)), float(neck_mm), int(min_core)) == 0
+
+
+def get_volume_split():
+    on, neck, core = C.c_int(), C.c_double(), C.c_int()
+    lib().medseg_get_volume_split(C.byref(on), C.byref(neck), C.byref(core))
+    return {"on": bool(on.value), "neck_mm": neck.value, "min_core": core.value}
 
 
 VTEX_MODES = ("count", "width")            # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
