@@ -1340,6 +1340,13 @@ int mi_unet_get_kernel_stats(mi_unet_t *h, mi_unet_kernel_stat *stats, int cap, 
  *   op = "upsample2x" / "upsample2x_bf16" / "upsample2x_fp16" : in [B][H][W][Cin] -> out [B][2H][2W][Cin], bilinear with
  *                     align_corners=True, Cin % 16 == 0, no weights (the 16-bit ops round the input to 16 bits first)
  *   op = "maxpool_bf16" / "maxpool_fp16" : the 16-bit stand-alone pooling (non-negative values: it orders bit patterns), C % 8 == 0
+ *   op = "conv3x3_wino_splitk" / "conv3x3_wino4_splitk" (the suffix stands in front of _pool: "conv3x3_wino4_splitk_pool"; these
+ *                     two ops only): the launch gets a split-K workspace, as the engine's plan gives every 3x3 layer -- 8 slabs
+ *                     [B][H][W][Cout] of floats, at most 64 MiB, filled with 0xFF bytes, between the call's guards -- and the launcher
+ *                     decides as in the plan whether and how often it cuts K.  "_splitk<N>", N = 2 .. 8: a workspace of exactly N
+ *                     slabs, which the launcher's split has to shrink to.  The strided entry point reports the route name +
+ *                     "+splitk<slices>" when K was split ("conv3x3_wino4+splitk3"), the bare route name when the shape admits no
+ *                     split.  A touched workspace guard fails the call.
  * Weights are given in PyTorch layout exactly as in the weight file. */
 int mi_unet_layer_debug(int device, const char *op, const float *in, int B, int H, int W, int Cin, const float *w,
                         const float *scale, const float *shift, int Cout, int relu, float *out);

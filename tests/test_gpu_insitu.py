@@ -153,6 +153,37 @@ def test_fp32_plan_every_layer_at_512_batch_16():
     assert "conv3x3_first" not in kernels and len(rep) == 21          # inc.c1 runs inside inc.c2's loader: one launch and 1 GiB of traffic less
 
 
+def test_fp32_plan_every_layer_at_64_batch_1_and_2():
+    """The reference's own call pattern is one image: at batch 1 most 3x3 layers of the default network run as a split-K launch (a
+    slice of K per workgroup, then wino_splitk_reduce).  Every launch of the 64 x 64 plan at batch 1 and 2 against the oracle on the
+    device's own input, the fp32 bar of this file.
+    The capture does not report how many slices a launch was cut into.  What ties the count printed here to the launch is no more
+    than this: the launchers ask csrc/routing.cpp's wino4_ksplit / wino_ksplit, tests/test_splitk_cpu.py holds those functions
+    against the model of tests/splitk_ref.py over a sweep, and the model is applied here to the plan's layer shapes (conv3x3 steps
+    write the lower half of a concat pixel or a dense tensor: aligned either way)."""
+    import splitk_ref as kr
+
+    spec = UNetSpec()
+    with binding.Engine(64, 64, in_ch=spec.in_ch, base=spec.base, levels=spec.levels, classes=spec.classes, max_batch=2, conv_algo="winograd") as eng:
+        eng.load_weights(pack_weights(spec, synth.make_weights(spec, 1234)))
+        shapes = {l["name"]: (l["in_h"], l["in_w"], l["in_c"], l["out_c"]) for l in eng.layers() if l["kind"] == "conv3x3"}
+    split_layers = {}
+    for B in (1, 2):
+        rep = _check_layers("winograd", spec, 64, B, 1234 + B, img=B - 1)
+        _show(f"fp32 64^2 x{B}", rep)
+        print(f"  split-K slices the model gives the launches of batch {B}:")
+        n = 0
+        for name, kern, _, _ in rep:
+            fam = {"conv3x3_wino4": kr.F4, "conv3x3_wino": kr.F2}.get(kern)      # the two hipcc kernels that can split; fused and staged ones never do
+            if fam is None or name not in shapes:
+                continue
+            ks = kr.layer(fam, (B,) + shapes[name]).ks
+            print(f"    {name:12s} {kern:16s} {'x'.join(map(str, (B,) + shapes[name])):>18s} ks {ks}")
+            n += ks > 1
+        split_layers[B] = n
+    assert split_layers[1] >= 10, split_layers
+
+
 def test_bf16_plan_every_layer_at_512_batch_16():
     """BASELINE configs[2]'s micro-batch: resident-weight, wide and 2x2 kernels of the bf16 pipeline"""
     rep = _check_layers("bf16", UNetSpec(), 512, 16, 4321, img=11)

@@ -210,9 +210,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a, con
     const int all_chunks = (a.Cin + WINO_KC - 1) / WINO_KC;
     int c_begin = 0, nchunks = all_chunks;
     if constexpr (SPLITK) {
-        const int per_slice = ((all_chunks + a.ksplit - 1) / a.ksplit + CPS - 1) / CPS * CPS;
-        c_begin = ks * per_slice;
-        nchunks = (c_begin + per_slice < all_chunks) ? c_begin + per_slice : all_chunks;
+        const KRange kr = ksplit_range(all_chunks, a.ksplit, ks, CPS);
+        c_begin = kr.begin;
+        nchunks = kr.end;
     }
     const int nsuper = (nchunks + CPS - 1) / CPS;
     f32x4 u[16];
@@ -546,19 +546,9 @@ static hipError_t launch_wino_cfg(const ConvArgs &a0, hipStream_t s)
     const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 8 * WM - 1) / (8 * WM);
     const int m_tiles = tiles_x * tiles_y * a.B;
     const int n_tiles = (a.Cout + 32 * WN - 1) / (32 * WN);
-    // split K only when the grid cannot fill half of the 256 CUs (one workgroup per CU): each slice keeps >= 2 super-chunks
-    a.ksplit = 1;
-    const int chunks = (a.Cin + WINO_KC - 1) / WINO_KC, tiles = m_tiles * n_tiles;
-    if (a.ksplit_ws != nullptr && tiles <= 128 && chunks >= 16 && a.Cout % 4 == 0 && a.ldo % 4 == 0 && a.co_off % 4 == 0) {
-        int ks = 256 / tiles;
-        if (ks > 8) ks = 8;
-        if (ks > chunks / 8) ks = chunks / 8;
-        while (ks > 1 && (size_t)ks * a.B * a.H * a.W * a.Cout * sizeof(float) > a.ksplit_ws_bytes) --ks;
-        // every slice must own at least one chunk after rounding its share up to whole super-chunks
-        while (ks > 1 && (ks - 1) * (((chunks + ks - 1) / ks + 3) / 4 * 4) >= chunks) --ks;
-        a.ksplit = ks;
-    }
-    const int nwg = tiles * a.ksplit;
+    // split K only when the grid cannot fill half of the 256 CUs (wino_ksplit, routing.cpp)
+    a.ksplit = wino_ksplit(a);
+    const int nwg = m_tiles * n_tiles * a.ksplit;
     constexpr size_t lds = WinoGeom<WM, WN>::LDS_BYTES;
     if (a.ksplit > 1) {
         auto kern = conv3x3_wino_f32<WM, WN, true>;

@@ -200,9 +200,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino4_f32(const ConvArgs a, co
     // the loads that open a tile: the raw patches of chunks 0 and 1 straight into LDS, then the U ring
     auto open_tile = [&]() {
         if constexpr (SPLITK) {
-            const int per_slice = (all_chunks + a.ksplit - 1) / a.ksplit;
-            c_begin = ks * per_slice;
-            nchunks = c_begin + per_slice < all_chunks ? c_begin + per_slice : all_chunks;
+            const KRange kr = ksplit_range(all_chunks, a.ksplit, ks, 1);
+            c_begin = kr.begin;
+            nchunks = kr.end;
         }
         raw_dma(c_begin, 0);
         raw_dma(c_begin + 1, 1);
@@ -359,17 +359,8 @@ static hipError_t launch_wino4_cfg(const ConvArgs &a0, hipStream_t s)
     const int m_tiles = tiles_x * tiles_y * a.B;
     const int n_tiles = (a.Cout + 64 * NB - 1) / (64 * NB);
     const int nwg = m_tiles * n_tiles;
-    // split K when the (tile, channel) grid alone leaves most CUs idle: every slice keeps at least four chunks
-    a.ksplit = 1;
-    const int chunks = (a.Cin + WINO4_KC - 1) / WINO4_KC;
-    if (!HEAD && a.ksplit_ws != nullptr && nwg <= 128 && chunks >= 8 && a.Cout % 4 == 0 && a.ldo % 4 == 0 && a.co_off % 4 == 0) {
-        int ks = 256 / nwg;
-        if (ks > 8) ks = 8;
-        if (ks > chunks / 4) ks = chunks / 4;
-        while (ks > 1 && (size_t)ks * a.B * a.H * a.W * a.Cout * sizeof(float) > a.ksplit_ws_bytes) --ks;
-        while (ks > 1 && (ks - 1) * ((chunks + ks - 1) / ks) >= chunks) --ks;      // no empty slice
-        a.ksplit = ks;
-    }
+    // split K when the (tile, channel) grid alone leaves most CUs idle (wino4_ksplit, routing.cpp; never with the fused head)
+    a.ksplit = HEAD ? 1 : wino4_ksplit(a, NB);
     if (a.ksplit > 1) {
         auto kern = conv3x3_wino4_f32<NB, false, true>;
         if (hipError_t e = ensure_dynamic_lds(kern, W4::LDS_BYTES); e != hipSuccess) return e;

@@ -164,7 +164,9 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
     if (!op || !in || B <= 0 || H <= 0 || W <= 0 || Cin <= 0) return fail(MI_UNET_EARG, "layer_debug: bad argument");
     if (mi_unet_device_count() <= 0) return fail(MI_UNET_ENODEVICE, "no HIP device visible: libmiunet has no CPU fallback");
     HIP_TRY(hipSetDevice(device));
-    // ---- resolve the op: "<op>[_pool][_lpout]"; _pool returns the fused 2x2 max-pooled tensor [B][H/2][W/2][Cout] instead
+    // ---- resolve the op: "<op>[_splitk[N]][_pool][_lpout]"; _pool returns the fused 2x2 max-pooled tensor [B][H/2][W/2][Cout] instead;
+    // _splitk hands the launch a split-K workspace as the plan does (8 slabs [B][H][W][Cout], at most the engine's 64 MiB), _splitk<N>,
+    // N = 2 .. 8, one of exactly N slabs (the launcher's shrink-to-fit)
     std::string o(op);
     auto strip = [&](const char *suffix) {
         const size_t n = strlen(suffix);
@@ -173,6 +175,11 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
         return true;
     };
     const bool lp_out = strip("_lpout"), want_pool = strip("_pool");
+    int splitk_slabs = strip("_splitk") ? 8 : 0;
+    const bool splitk_exact = splitk_slabs == 0 && o.size() > 8 && o.compare(o.size() - 8, 7, "_splitk") == 0 && o.back() >= '2' && o.back() <= '8';
+    if (splitk_exact) { splitk_slabs = o.back() - '0'; o.resize(o.size() - 8); }
+    if (splitk_slabs && o != "conv3x3_wino" && o != "conv3x3_wino4")
+        return fail(MI_UNET_EARG, "layer_debug: _splitk is for conv3x3_wino and conv3x3_wino4");
     const DebugOp *dop = nullptr;
     for (const DebugOp &k : kDebugOps)
         if (o == k.op) dop = &k;
@@ -248,6 +255,15 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
         HIP_TRY(run.d_pool.reset(2 * G + pool_bytes));
         HIP_TRY(hipMemset(run.d_pool, 0xFF, 2 * G + pool_bytes));
     }
+    // the split-K workspace: poisoned too, so a slab element that no slice wrote reaches the output as NaN
+    DeviceBuf<unsigned char> d_ws;
+    size_t ws_bytes = 0;
+    if (splitk_slabs) {
+        ws_bytes = (size_t)splitk_slabs * out_npix * Cout * sizeof(float);
+        if (!splitk_exact && ws_bytes > ((size_t)64 << 20)) ws_bytes = (size_t)64 << 20;
+        HIP_TRY(d_ws.reset(2 * G + ws_bytes));
+        HIP_TRY(hipMemset(d_ws, 0xFF, 2 * G + ws_bytes));
+    }
     if (!wpk.empty()) {
         HIP_TRY(d_w.reset(wpk.size()));
         HIP_TRY(d_b.reset(bias.size()));
@@ -263,6 +279,7 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
     const float *d_inf = reinterpret_cast<const float *>(d_in.get() + G);
     float *d_outf = reinterpret_cast<float *>(run.d_out.get() + G);
     Route r = dop->route;
+    int ks = 1;                                               // K slices of the launch (wino4_ksplit / wino_ksplit, as the launcher asks them)
     std::unique_ptr<AsmKernels> asm_kernels;                  // no handle here: an owner for this call, when the op runs an assembly kernel
     if (up) {
         HIP_TRY(launch_upsample2x_bilinear(d_inf, ldc, d_outf, ldo, co_off, B, H, W, Cin, kind, rt, nullptr));
@@ -280,6 +297,7 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
         if (want_pool) { a.pool_out = reinterpret_cast<float *>(run.d_pool.get() + G); a.pool_ld = pool_ld; }
         a.in = d_inf; a.wpk = d_w; a.bias = d_b; a.out = d_outf;
         if (pk == Pack::WINO4 || pk == Pack::TAPS) a.wpk4 = d_w;
+        if (splitk_slabs) { a.ksplit_ws = reinterpret_cast<float *>(d_ws.get() + G); a.ksplit_ws_bytes = ws_bytes; }      // before the routing, as plan.cpp
         if (dop->routed) r = route_wino4(a);
         if (r == Route::CONV_WINO4A || r == Route::CONV_WINO4B) {
             asm_kernels.reset(new AsmKernels(device));
@@ -288,14 +306,24 @@ int run_layer(int device, const char *op, const float *in, int B, int H, int W, 
                 r = route_wino4(a);
             }
         }
+        ks = r == Route::CONV_WINO ? wino_ksplit(a) : r == Route::CONV_WINO4 ? wino4_ksplit(a, 2) : r == Route::CONV_WINO4_1B ? wino4_ksplit(a, 1) : 1;
         HIP_TRY(launch_route(r, a, asm_kernels.get(), nullptr));
     }
     HIP_TRY(hipDeviceSynchronize());
+    if (splitk_slabs && G) {                                  // the workspace stays here: its guards are looked at here
+        std::vector<unsigned char> g(2 * G);
+        HIP_TRY(hipMemcpy(g.data(), d_ws.get(), G, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g.data() + G, d_ws.get() + G + ws_bytes, G, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < 2 * G; ++i)
+            if (g[i] != 0xFF)
+                return fail(MI_UNET_ESTATE, "layer_debug: the launch wrote into the " + std::string(i < G ? "front" : "back") +
+                                                " guard of the split-K workspace, byte " + std::to_string(i < G ? i : i - G));
+    }
     run.guard = G; run.out_bytes = 2 * G + out_bytes; run.pool_bytes = want_pool ? 2 * G + pool_bytes : 0;
     run.out_npix = out_npix; run.pool_npix = out_npix / 4;
     run.es = (int)out_es; run.lp_kind = out16 ? kind : 0; run.C = Co; run.ldo = ldo; run.co_off = co_off; run.pool_ld = pool_ld;
     run.pooled = want_pool;
-    run.kernel = route_name(r);
+    run.kernel = route_name(r) + (ks > 1 ? "+splitk" + std::to_string(ks) : std::string());
     return MI_UNET_OK;
 }
 

@@ -143,6 +143,21 @@ private:
 // phase and an MFMA phase per chunk (csrc/asm/gen_wino4b_asm.py; conv3x3_wino4b_shape_ok).  An absent or unavailable owner is an error.
 hipError_t launch_conv3x3_wino4_asm(const AsmKernels *owner, AsmKernels::Which which, const ConvArgs &a, hipStream_t s);
 hipError_t launch_wino_splitk_reduce(const ConvArgs &a, hipStream_t s);   // sums a.ksplit slabs of a.ksplit_ws into a.out
+// Split-K, one owner for the decision (routing.cpp; tests/cpu/ksplit_test.cpp sweeps it on a CPU): the number of K slices the
+// launcher of the F(4x4) kernel with nb = 1 or 2 channel blocks per wave (one-block / two-block), or of the F(2x2) kernel, gives
+// this launch; 1 = the full-K kernel.  Reads a.ksplit_ws / a.ksplit_ws_bytes, the shape, the output layout and a.head_w.
+int wino4_ksplit(const ConvArgs &a, int nb);
+int wino_ksplit(const ConvArgs &a);
+// ... and the K chunks [begin, end) slice k of ks walks: ceil(chunks / ks) chunks rounded up to whole granules, the last slice
+// what is left.  granule: 1 chunk on F(4x4), WINO_SC / WINO_KC = 4 (a super-chunk of the raw patch) on F(2x2).  The two
+// functions above return a ks for which no slice is empty.  Kernels and host share it.
+struct KRange { int begin, end; };
+constexpr KRange ksplit_range(int chunks, int ks, int k, int granule)
+{
+    const int per_slice = ((chunks + ks - 1) / ks + granule - 1) / granule * granule;
+    const int begin = k * per_slice;
+    return { begin, begin + per_slice < chunks ? begin + per_slice : chunks };
+}
 hipError_t launch_convT2x2_mfma(const ConvArgs &a, hipStream_t s);
 // The transposed conv as four per-tap GEMMs sharing one A operand (convt_taps.hip): a.wpk4 holds the weights packed
 // [ceil(Cin/32)*4 chunks of 8][4 taps (dy*2+dx)][convT_taps_cpad(Cout)][8], zero-padded; other fields as above.

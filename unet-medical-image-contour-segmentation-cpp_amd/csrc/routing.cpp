@@ -234,6 +234,42 @@ Route route_wino4(const ConvArgs &a)
     return a.Cout >= 128 && (rem == 0 || rem > 64) ? Route::CONV_WINO4 : Route::CONV_WINO4_1B;
 }
 
+// ---- split-K (kernels.h): how many K slices a launch of the hipcc Winograd kernels is cut into
+
+// the slabs [ks][B][H][W][Cout] must fit the workspace, and after rounding a slice's share up to whole granules none may be empty
+static int ksplit_fit(const ConvArgs &a, int ks, int chunks, int granule)
+{
+    while (ks > 1 && (size_t)ks * a.B * a.H * a.W * a.Cout * sizeof(float) > a.ksplit_ws_bytes) --ks;
+    while (ks > 1 && ksplit_range(chunks, ks, ks - 1, granule).begin >= chunks) --ks;
+    return ks;
+}
+
+// F(4x4): split K when the (tile, channel) grid alone leaves most CUs idle; every slice keeps at least four chunks.  The reduce
+// kernel moves 16 bytes at a time (Cout, ldo, co_off in fours) and knows no head.
+int wino4_ksplit(const ConvArgs &a, int nb)
+{
+    const int nwg = ((a.W + 15) / 16) * ((a.H + 15) / 16) * a.B * ((a.Cout + 64 * nb - 1) / (64 * nb));
+    const int chunks = (a.Cin + WINO4_KC - 1) / WINO4_KC;
+    if (a.head_w != nullptr || a.ksplit_ws == nullptr || nwg > 128 || chunks < 8 || a.Cout % 4 || a.ldo % 4 || a.co_off % 4) return 1;
+    int ks = 256 / nwg;
+    if (ks > 8) ks = 8;
+    if (ks > chunks / 4) ks = chunks / 4;
+    return ksplit_fit(a, ks, chunks, 1);
+}
+
+// F(2x2): only when the grid cannot fill half of the 256 CUs (one workgroup per CU); each slice keeps >= 2 super-chunks
+int wino_ksplit(const ConvArgs &a)
+{
+    const bool wide = a.Cout > 64;              // 32 tiles x 128 channels per workgroup, else 64 x 64 (launch_conv3x3_wino)
+    const int tiles = ((a.W + 15) / 16) * ((a.H + (wide ? 8 : 16) - 1) / (wide ? 8 : 16)) * a.B * ((a.Cout + (wide ? 128 : 64) - 1) / (wide ? 128 : 64));
+    const int chunks = (a.Cin + WINO_KC - 1) / WINO_KC;
+    if (a.ksplit_ws == nullptr || tiles > 128 || chunks < 16 || a.Cout % 4 || a.ldo % 4 || a.co_off % 4) return 1;
+    int ks = 256 / tiles;
+    if (ks > 8) ks = 8;
+    if (ks > chunks / 8) ks = chunks / 8;
+    return ksplit_fit(a, ks, chunks, WINO_SC / WINO_KC);
+}
+
 // ---- the routing functions
 
 RouteChoice route_conv(const ConvArgs &a, const RoutePolicy &p, unsigned want)
