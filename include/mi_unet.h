@@ -82,8 +82,26 @@ int mi_unet_load_weights_from_memory(mi_unet_t *h, const void *blob, size_t len)
  * B may exceed max_batch (processed in micro-batches). */
 int mi_unet_infer_u8(mi_unet_t *h, const uint8_t *imgs, int B, uint8_t *labels, float *logits);
 
-/* Same, with all three buffers already resident in device memory (HBM); asynchronous on the engine's stream.
- * Call mi_unet_sync() before reading results from another stream. */
+/* Same, with all three buffers already resident in device memory (HBM), 16-byte aligned; d_logits may be NULL.  The contract of the
+ * device form:
+ *  - Ordering.  The call enqueues on the handle's CURRENT stream -- the engine's own, or the one last given to mi_unet_set_stream --
+ *    and returns without waiting.  It is ordered behind everything enqueued on that stream before it (a copy into d_imgs, say) and
+ *    ahead of everything enqueued after it, as a kernel launch there would be; with mi_unet_set_postprocess on, the clean-up follows
+ *    on the same stream.  Another stream, or the host, reads the results after mi_unet_sync() or after an event of that stream.
+ *  - Buffers.  All three must stay valid, and d_imgs unchanged by anyone else, until the stream has passed the call.  Nothing outside
+ *    B * H * W * in_ch bytes of d_imgs is read and nothing outside B * H * W bytes of d_labels and B * classes * H * W floats of
+ *    d_logits is written.
+ *  - B > max_batch.  The call walks the buffers in micro-batches: micro-batch k covers images [k * max_batch, min(B, (k + 1) *
+ *    max_batch)), i.e. the contiguous slices d_imgs + k * max_batch * H * W * in_ch, d_labels + k * max_batch * H * W and d_logits +
+ *    k * max_batch * classes * H * W, one behind the other on the stream.  B = 0 succeeds and enqueues nothing.
+ *  - Graphs.  A micro-batch is keyed on (stream, its three slice pointers, its size).  The first call of a key launches kernel by
+ *    kernel, the second captures those launches into a hipGraph, every later one replays it: the graph reads whatever the buffers hold
+ *    when it runs.  The handle caches up to 64 keys and drops the oldest one first; before a dropped graph is destroyed the handle
+ *    waits (on the host) for the work that may still replay it.  A caller that cycles through more than 64 keys (more than 64
+ *    micro-batches in one call, or more than 64 buffer / stream combinations in turn) therefore never replays, and every call costs a
+ *    kernel-by-kernel launch; keep the working set at 64 keys or raise max_batch.  MIUNET_GRAPH=0 and profiling launch kernel by
+ *    kernel always.
+ * One handle is driven by one host thread at a time; two handles (mi_unet_clone) on two streams run side by side. */
 int mi_unet_infer_u8_device(mi_unet_t *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits);
 
 /* SURVEY §8f row f1 -- the arithmetic of Preprocess::preprocess_raw (src/preprocess.cpp:65-118) on the device, fused in
@@ -1308,11 +1326,21 @@ void mi_unet_host_free(void *p);
 #define MI_UNET_N_STAGES 5
 int mi_unet_last_stage_ms(const mi_unet_t *h, float *ms /* [MI_UNET_N_STAGES] */);
 
-/* Use an external hipStream_t (e.g. the caller framework's current stream) instead of the engine's own. NULL restores it. */
+/* Use an external hipStream_t (e.g. the caller framework's current stream) instead of the engine's own; NULL restores the engine's
+ * own, a non-blocking stream that is NOT ordered against the legacy default stream.  From the next call on, every entry point of
+ * the handle enqueues on that stream.
+ *  - The switch waits for nothing.  Work the handle enqueued on the stream it leaves keeps running there, and it uses the handle's
+ *    activation buffers: before the first call on the new stream the CALLER orders the two -- synchronise the stream being left, or
+ *    make the new stream wait on an event recorded on it.  Calls on two streams that are not ordered race on those buffers.
+ *  - The stream being left must still exist when mi_unet_set_stream is called (the handle may record an event on it); the caller may
+ *    destroy it afterwards, once its work has completed.  The stream that is current when the handle is destroyed, or weights are
+ *    loaded, must exist then.
+ *  - Graphs are cached per stream (mi_unet_infer_u8_device): coming back to a stream replays what was captured on it.
+ * mi_unet_sync waits for the CURRENT stream only, i.e. for the calls made since the last switch, not for a stream left earlier. */
 int mi_unet_set_stream(mi_unet_t *h, void *hip_stream);
 int mi_unet_sync(mi_unet_t *h);
 
-/* Time the last `mi_unet_infer_u8_device` calls: brackets with hipEvents on the engine's stream.
+/* Time the last `mi_unet_infer_u8_device` calls: brackets with hipEvents on the handle's current stream (both on the same one).
  * mi_unet_timer_begin/end return elapsed milliseconds through *ms at end (end synchronises the stop event). */
 int mi_unet_timer_begin(mi_unet_t *h);
 int mi_unet_timer_end(mi_unet_t *h, float *ms);

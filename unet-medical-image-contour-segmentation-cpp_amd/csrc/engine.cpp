@@ -32,21 +32,29 @@ PlanInput plan_input(const mi_unet *h)
     return in;
 }
 
+// An executable leaves the graph cache (eviction, new weights, destroy).  The device entry point returns once it has enqueued, so a
+// replay of `exec` may still be in flight on the stream of its key; destroying it then is not something the runtime promises to
+// defer.  That stream is the handle's current one or its own, which are alive and are waited for directly, or a caller's stream the
+// handle was switched away from: the caller may have destroyed that one since, so the wait is for the event that mi_unet_set_stream
+// recorded on it at the switch, behind everything this handle enqueued there.  Not on the path of a cached key.
+void GraphRetire::operator()(const GraphKey &key, hipGraphExec_t exec) const
+{
+    if (key.stream == h->stream || key.stream == h->own_stream) {
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(const_cast<void *>(key.stream)));
+    } else {
+        for (const mi_unet::LeftStream &l : h->left_streams)
+            if (l.stream == key.stream) (void)hipEventSynchronize(l.done);
+    }
+    (void)hipGraphExecDestroy(exec);
+}
+
 int run_microbatch(mi_unet *h, const uint8_t *d_imgs, int B, uint8_t *d_labels, float *d_logits)
 {
     if (!h->use_graph || h->profiling) return launch_plan(h, d_imgs, B, d_labels, d_logits);
     hipStream_t s = h->stream;
-    mi_unet::GraphEntry *ge = nullptr;
-    for (auto &g : h->graphs)
-        if (g.stream == s && g.imgs == d_imgs && g.labels == d_labels && g.logits == d_logits && g.B == B) ge = &g;
-    if (!ge) {
-        if (h->graphs.size() >= 64) {                    // bounded cache (a batch of 512 is 32 micro-batch keys): drop the oldest entry
-            if (h->graphs.front().exec) (void)hipGraphExecDestroy(h->graphs.front().exec);
-            h->graphs.erase(h->graphs.begin());
-        }
-        h->graphs.push_back({ s, d_imgs, d_labels, d_logits, B, 0, nullptr });
-        ge = &h->graphs.back();
-    }
+    const GraphKey key{ s, d_imgs, d_labels, d_logits, B };
+    mi_unet::GraphCache::Entry *ge = h->graphs.find(key);
+    if (!ge) ge = &h->graphs.insert(key);                // at 64 entries in the oldest one's place: GraphRetire below
     if (ge->exec) {
         HIP_TRY(hipGraphLaunch(ge->exec, s));
         return 0;
@@ -288,9 +296,7 @@ int engine_adopt_weights(mi_unet_t *h, const HostWeights &hw, bool upload)
     if (int rc = check_handle(h, false)) return rc;
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (auto &g : h->graphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->graphs.clear();
+    h->graphs.clear();                                   // (GraphRetire: also waits for the streams the handle has left)
     h->weights_loaded = false;
     h->weights.reset();
     h->d_weights = nullptr;
@@ -831,7 +837,25 @@ void mi_unet_host_free(void *p)
 int mi_unet_set_stream(mi_unet_t *h, void *hip_stream)
 {
     if (int rc = check_handle(h, false)) return rc;
-    h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+    hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+    if (next == h->stream) return MI_UNET_OK;
+    // Leaving a caller's stream on which cached graphs may still be replaying: an event behind them, for GraphRetire.  (The handle's
+    // own stream outlives its entries and is waited for directly.)  Nothing waits here: the caller orders the switch.
+    if (h->stream != h->own_stream && h->graphs.holds_stream(h->stream)) {
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        auto &ls = h->left_streams;
+        ls.erase(std::remove_if(ls.begin(), ls.end(), [h](const mi_unet::LeftStream &l) { return !h->graphs.holds_stream(l.stream); }), ls.end());
+        auto it = std::find_if(ls.begin(), ls.end(), [h](const mi_unet::LeftStream &l) { return l.stream == h->stream; });
+        if (it == ls.end()) {
+            ls.emplace_back();
+            it = ls.end() - 1;
+            it->stream = h->stream;
+            const hipError_t e = it->done.reset(hipEventDisableTiming);
+            if (e != hipSuccess) { ls.pop_back(); return fail(MI_UNET_EHIP, std::string("mi_unet_set_stream: hipEventCreate: ") + hipGetErrorString(e)); }
+        }
+        HIP_TRY(hipEventRecord(it->done, h->stream));
+    }
+    h->stream = next;
     return MI_UNET_OK;
 }
 
@@ -899,8 +923,7 @@ void mi_unet_destroy(mi_unet_t *h)
         if (q) (void)hipStreamSynchronize(q);
     for (hipStream_t q : { h->tail_stream, h->dl_stream, h->pre_stream })
         if (q) (void)hipStreamDestroy(q);
-    for (auto &g : h->graphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    h->graphs.clear();
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;                                           // ... and with it this handle's hold on the weights and the assembly kernels
 }

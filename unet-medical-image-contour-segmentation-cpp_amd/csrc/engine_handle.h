@@ -12,6 +12,7 @@
 #include "../../include/mi_unet.h"
 #include "copy_pool.h"
 #include "engine_internal.h"
+#include "graph_cache.h"
 #include "kernels.h"
 #include "plan.h"
 #include "routing.h"
@@ -88,6 +89,7 @@ struct Event {
     Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
     Event(const Event &) = delete;
     Event &operator=(const Event &) = delete;
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
     ~Event() { if (e) (void)hipEventDestroy(e); }
     hipError_t reset(unsigned flags = hipEventDefault)
     {
@@ -97,6 +99,13 @@ struct Event {
     }
     hipEvent_t get() const { return e; }
     operator hipEvent_t() const { return e; }
+};
+
+// What the graph cache of a handle does with an executable that leaves it (engine.cpp): wait until nothing can still replay it,
+// then hipGraphExecDestroy.
+struct GraphRetire {
+    mi_unet *h;
+    void operator()(const GraphKey &key, hipGraphExec_t exec) const;
 };
 
 }  // namespace miunet
@@ -252,12 +261,16 @@ struct mi_unet {
     miunet::PinnedBuf<uint8_t> h_labels;
     std::vector<miunet::Step> plan;
     // hipGraph replay of the forward pass (the reference replays a captured CUDA graph per image, src/process.cpp:99-105,
-    // :147): one captured graph per (stream, buffers, batch) key; the first call of a key runs eagerly.
-    struct GraphEntry {
-        hipStream_t stream; const uint8_t *imgs; uint8_t *labels; float *logits; int B;
-        int uses; hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs;
+    // :147): one captured graph per (stream, buffers, batch) key; the first call of a key runs eagerly.  graph_cache.h holds the
+    // policy (64 entries, first in first out); an executable that leaves the cache goes through GraphRetire, which waits for the
+    // work that may still replay it.  left_streams: one event per caller's stream the handle was switched away from while the
+    // cache held an executable captured on it, recorded on that stream at the switch (mi_unet_set_stream) -- behind everything the
+    // handle ever enqueued there, and all GraphRetire needs of a stream that may be gone by the time its entries are evicted.
+    static constexpr size_t GRAPH_CACHE_ENTRIES = 64;
+    struct LeftStream { hipStream_t stream; miunet::Event done; };
+    std::vector<LeftStream> left_streams;
+    using GraphCache = miunet::GraphCache<hipGraphExec_t, miunet::GraphRetire>;
+    GraphCache graphs{ GRAPH_CACHE_ENTRIES, miunet::GraphRetire{ this } };     // (mi_unet_destroy clears it while the streams live)
     bool use_graph = true;          // MIUNET_GRAPH=0 disables
     // the RAW-in entry points' switches (pipeline_raw.cpp), parsed at create like the ones above and copied by mi_unet_clone
     int copy_threads = 4;           // MIUNET_COPY_THREADS (1..16): threads of a large host copy; 1 = plain memcpy
