@@ -221,6 +221,27 @@ struct VolumeSplit {
 bool set_volume_split(const VolumeSplit &split);
 VolumeSplit get_volume_split();
 
+// Every component of the labelled stack thinned to its medial line (mi_unet_volume_skeleton in include/mi_unet.h).  It
+// acts only together with set_volume's `on`: one mi_unet_volume_skeleton call per target (mi_unet_volume_skeleton_host under
+// MEDSEG_HOST_POSTPROCESS=1) on the ids the components stage hands out -- the pieces' ids with set_volume_split on -- with
+// m = min(found, MI_UNET_VOLUME_MAX_TABLE), the integer units mi_unet_score_volume_units finds for the volume setting's spacing and
+// `max_passes` (0: until a pass deletes nothing), then mi_unet_volume_skeleton_derive of every row.  Every component object of
+// volume_report.json gains a last member "skeleton": "voxels", "ends", "junctions", "isolated", "loops", "length_mm", "radius_min_mm",
+// "radius_max_mm", "radius_rms_mm" (the three null with `radius` off, which also skips the distance work) and "stable"; the member is
+// null for a component the volume filter dropped.  With `png` per slice <base>_volume_skeleton.png is written (0 / 255; or
+// <base>_volume_skeleton_class<cls>.png under a non-default target list).  One log line per batch, "Volume skeleton: D slices, K
+// targets, P passes, t ms" (P over all targets); a failure is reported as "Volume skeleton error: ..." and ends only this step.  With it
+// off (the default) every artefact and every log line is what it is without the setting.  Needs no engine and survives
+// initialize_engine.  false, message on stderr, setting unchanged: a negative max_passes.
+struct VolumeSkeleton {
+    bool on = false;
+    bool radius = true;
+    bool png = false;
+    int max_passes = 0;
+};
+bool set_volume_skeleton(const VolumeSkeleton &skeleton);
+VolumeSkeleton get_volume_skeleton();
+
 // The texture of every component of the labelled stack (mi_unet_volume_texture in include/mi_unet.h).  It acts only
 // together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits (beside the channel
 // set_volume_measure keeps, when the two differ), a failed slice all-zero; one mi_unet_volume_texture call per target

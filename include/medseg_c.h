@@ -86,6 +86,10 @@ void medseg_get_volume_spatial(int *on, int *channel, int *max_voxels, double *p
  * (include/medseg/process.h).  0 on success; medseg_get_volume_split fills the three values. */
 int medseg_set_volume_split(int on, double neck_mm, int min_core);
 void medseg_get_volume_split(int *on, double *neck_mm, int *min_core);
+/* Every component of the labelled stack thinned to its medial line: MedicalSeg::set_volume_skeleton / get_volume_skeleton
+ * (include/medseg/process.h).  0 on success; medseg_get_volume_skeleton fills the four values. */
+int medseg_set_volume_skeleton(int on, int radius, int png, int max_passes);
+void medseg_get_volume_skeleton(int *on, int *radius, int *png, int *max_passes);
 /* The scored stack per lesion: MedicalSeg::set_volume_match / get_volume_match (include/medseg/process.h).  0 on success;
  * medseg_get_volume_match fills the three values. */
 int medseg_set_volume_match(int on, int iou_num, int iou_den);

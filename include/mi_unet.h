@@ -1307,6 +1307,83 @@ int mi_unet_volume_split_host(const uint8_t *masks, int D, int H, int W, const i
                               int32_t *found, mi_unet_vsplit_stat *stats, int32_t *rounds);
 int mi_unet_volume_split_derive(const mi_unet_vpiece *p, const double spacing_xyz[3], double unit_mm, mi_unet_vpiece_metrics *out);
 
+/* ---- Component skeletons: topology-preserving thinning to a medial line ----------------------------------------------
+ * A tubular or branching component (vessel, airway, duct) is described by its medial line: its length, its calibre, its free ends and
+ * branch points, whether it closes into a loop.  This stage peels every component of an id stack down to one voxel of thickness without
+ * ever changing its topology, and counts the result.  Exact integers; the bytes do not depend on scheduling.
+ *
+ * INPUT    ids int32 [D][H][W]; component r (0 <= r < m) is { ids == r + 1 }, what mi_unet_volume_components and mi_unet_volume_split
+ *          write.  Every other value belongs to nothing, and so does everything outside the volume.  Two voxels are SAME-OBJECT
+ *          NEIGHBOURS when they are 26-adjacent and carry the same id in 1 .. m.  Components are thinned independently in one run and
+ *          may touch (ids made under connectivity 6, or of two target values).
+ * CODE     The neighbourhood of a voxel p as 26 bits: bit i belongs to the i-th offset (dz, dy, dx) of the raster order
+ *          (-1,-1,-1), (-1,-1,0), ... (1,1,1) with (0,0,0) left out, and is set when that neighbour is a same-object neighbour of p.
+ * SIMPLE   (26-connected object, 6-connected background; Malandain and Bertrand.)  O = the set bits of the code.  B = the 18-neighbours
+ *          of p (offsets with |dz| + |dy| + |dx| <= 2) whose bit is clear.  p is simple iff O is not empty and is one 26-connected
+ *          component inside the 26 neighbours, and exactly one 6-connected component of B, connectivity taken inside the 18 neighbours,
+ *          holds a face neighbour of p.  It depends on the code alone.
+ * END      An end point is an object voxel with exactly one same-object neighbour.
+ * SCHEDULE A pass first marks the end points of the current state.  Then six phases run in the order z - 1, z + 1, y - 1, y + 1, x - 1,
+ *          x + 1.  Phase d first fixes its candidates: the object voxels whose neighbour in direction d is not a same-object neighbour,
+ *          in the state at the phase's start.  Then eight sub-steps s = 0 .. 7 follow; the subfield of a voxel is
+ *          (x & 1) | (y & 1) << 1 | (z & 1) << 2.  In sub-step s every candidate of subfield s is deleted at once if it was not marked an
+ *          end point at the pass's start and is simple in the current state.  Passes repeat until one deletes nothing.  max_passes > 0
+ *          stops after that many passes; stable = 1 iff the last pass that ran deleted nothing.
+ *          Two voxels of one subfield are never 26-adjacent, so a sub-step's deletions do not see each other: the parallel deletion
+ *          equals a sequential one in any order, only simple points go, and components, tunnels and cavities are preserved.
+ * RADIUS   r2[p], for a skeleton voxel p, = the minimum of (dx ux)^2 + (dy uy)^2 + (dz uz)^2 over every voxel q with ids[q] != ids[p]
+ *          (the ids as given, before the thinning), the volume wrapped in one layer of "nothing" voxels at index -1 and at D / H / W: a
+ *          component that touches the border has a finite radius.
+ *
+ * opts     { max_passes, radius }, default { 0, 1 }.  radius = 0 leaves r2_min / r2_max / r2_sum zero; with radius = 0 and r2 == NULL no
+ *          distance is computed.
+ * out_ids  [D][H][W] int32, may be NULL: the id on skeleton voxels, 0 elsewhere.
+ * r2       [D][H][W] int32, may be NULL: the radius above on skeleton voxels, 0 elsewhere.
+ * table    [m] mi_unet_vskel: voxels_in (of the input), voxels (of the skeleton), ends (one same-object skeleton neighbour), isolated
+ *          (none), junctions (three or more), links[c] = the unordered 26-adjacent same-object skeleton pairs of class
+ *          c = |dx| + 2 |dy| + 4 |dz| - 1, r2_min / r2_max / r2_sum over the skeleton voxels.  An id no voxel carries: all zero.
+ * info     may be NULL: passes (the one that deleted nothing included), deleted (voxels over all passes), stable.  `passes` is part of
+ *          the definition: the device, the host form and a sequential reading of SCHEDULE report the same number.
+ *
+ * MI_UNET_EARG with a message that begins with the entry point's name, nothing queued and no output touched:
+ *   a null ids, spacing_units or table;
+ *   D, H, W in 1 .. MI_UNET_SCORE_VOLUME_MAX_SIDE and D * H * W < 2^31; m in 1 .. MI_UNET_VOLUME_MAX_TABLE; units >= 1;
+ *   ((W + 1) ux)^2 + ((H + 1) uy)^2 + ((D + 1) uz)^2 < 2^31     mi_unet_volume_measure's limit on the wrapped volume: every r2 is int32;
+ *   max_passes >= 0; radius 0 or 1.
+ * A workspace that cannot be allocated is MI_UNET_EHIP and the handle stays usable.  Works before weights are loaded, changes no
+ * setting and nothing that mi_unet_last_regions or mi_unet_last_stage_ms report, has no group form.  mi_unet_volume_skeleton_host takes
+ * the same arguments without the handle, follows SCHEDULE voxel by voxel and gives the same bytes.
+ *
+ * mi_unet_volume_skeleton_derive (pure host arithmetic in double; spacing in mm, unit_mm = the length of a spacing unit):
+ *   length_mm      sum over c of links[c] * |offset c * spacing|.  A final skeleton holds no deletable voxel, so its curve portions hold no
+ *                  adjacency triangles and the sum is the polyline length there; a junction cluster (voxels that are pairwise adjacent)
+ *                  counts every pair and OVER-COUNTS.  A surface skeleton (a closed shell) has no length in this sense.
+ *   radius_min_mm, radius_max_mm = sqrt(r2_min / r2_max) * unit_mm; radius_rms_mm = sqrt(r2_sum / voxels) * unit_mm; all three 0 for a component
+ *                  without skeleton voxels or a call with radius = 0.
+ *   loops          links - voxels + 1 for a component with voxels, else 0: the first Betti number ONLY when the skeleton is a curve (a
+ *                  connected graph without adjacency triangles); junction clusters and surfaces make it larger.
+ *
+ * mi_unet_volume_skeleton_simple / _simple_host: SIMPLE for the codes 32 * first_word .. 32 * (first_word + n_words) - 1, as bits
+ * (code c is bit c & 31 of bits[(c >> 5) - first_word]), by the kernels' form of the test and by the host form's.  first_word + n_words
+ * <= 2^21.  They are how a test compares the two forms on all 2^26 codes. */
+typedef struct mi_unet_vskel_opts { int max_passes, radius; } mi_unet_vskel_opts;   /* default { 0, 1 } */
+typedef struct mi_unet_vskel {         /* 112 bytes, no padding */
+    int64_t voxels_in, voxels, ends, isolated, junctions;
+    int64_t links[7];
+    int64_t r2_sum;
+    int32_t r2_min, r2_max;
+} mi_unet_vskel;
+typedef struct mi_unet_vskel_info { int64_t deleted; int32_t passes, stable; } mi_unet_vskel_info;     /* 16 bytes */
+typedef struct mi_unet_vskel_metrics { double length_mm, radius_min_mm, radius_max_mm, radius_rms_mm; int64_t loops; } mi_unet_vskel_metrics;
+int mi_unet_volume_skeleton(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, int D, int H, int W, int m, const int spacing_units[3],
+                            const mi_unet_vskel_opts *opts, int32_t *out_ids /* [D][H][W] or NULL */, int32_t *r2 /* [D][H][W] or NULL */,
+                            mi_unet_vskel *table /* [m] */, mi_unet_vskel_info *info /* or NULL */);
+int mi_unet_volume_skeleton_host(const int32_t *ids, int D, int H, int W, int m, const int spacing_units[3], const mi_unet_vskel_opts *opts,
+                                 int32_t *out_ids, int32_t *r2, mi_unet_vskel *table, mi_unet_vskel_info *info);
+int mi_unet_volume_skeleton_derive(const mi_unet_vskel *c, const double spacing_xyz[3], double unit_mm, mi_unet_vskel_metrics *out);
+int mi_unet_volume_skeleton_simple(mi_unet_t *h, uint32_t first_word, uint32_t n_words, uint32_t *bits /* [n_words] host */);
+int mi_unet_volume_skeleton_simple_host(uint32_t first_word, uint32_t n_words, uint32_t *bits /* [n_words] */);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

@@ -21,6 +21,7 @@ struct mi_unet_vtexture;
 struct mi_unet_vzones;
 struct mi_unet_vzone;
 struct mi_unet_vpiece;
+struct mi_unet_vskel;
 struct mi_unet_vnbhood;
 
 namespace miunet {
@@ -636,5 +637,29 @@ hipError_t launch_volume_nbhood_zones(const int32_t *keys, const VolumeNbhoodArg
                                       const uint16_t *full, int32_t *zmin, int32_t *zmin_axial, VnbAcc *acc, const VnbTables &t, hipStream_t s);
 hipError_t launch_volume_nbhood_finish(const int2 *range, const VolumeNbhoodArgs &a, int want, const VznAcc *zacc, const VnbAcc *acc,
                                        const VnbTables &t, ::mi_unet_vnbhood *table, hipStream_t s);
+
+// Volume skeleton (volume_skeleton.hip; include/mi_unet.h: mi_unet_volume_skeleton).  cur i32 [D][H][W] on the device: the
+// ids on entry, the state of the thinning from then on, the skeleton at the end.  Exact integers: sums, counts, minima and maxima; nothing
+// depends on the order of atomics.  No workgroup waits for another and every launch has a grid fixed by (D, H, W).
+//   launch_volume_skeleton_begin  : ids outside 1 .. m become 0, voxels_in counted, the table cleared; with want_dist the exact squared
+//                                   distance to the nearest voxel of another id, the volume wrapped in one layer of "nothing": z (a lane
+//                                   per column), y and x (a lane per voxel, the scan cut off where the step alone reaches the best so far).
+//   launch_volume_skeleton_pass   : one pass of the schedule: the pass state cleared, the end points marked (7.15's tile with its halo in
+//                                   LDS), then per phase the candidates compacted into eight lists, one per subfield, and eight sub-step
+//                                   launches, each over its list.  pass_state->deleted = what the pass deleted.
+//   launch_volume_skeleton_finish : one sweep over the skeleton in the same tile: neighbour counts, link classes and radii per component
+//                                   (a wave merges per id before its atomics), r2 [D][H][W] written when not null, the table finished.
+//   launch_volume_skeleton_simple : the kernels' simple-point test on codes 32 first_word .. 32 (first_word + n_words) - 1 as bits.
+// Workspace: volume_skeleton_workspace_bytes(D, H, W), not zeroed by the caller.  D H W < 2^31, m <= VOLUME_MAX_TABLE, sides at most
+// SCORE_VOLUME_MAX_SIDE, ((W + 1) ux)^2 + ((H + 1) uy)^2 + ((D + 1) uz)^2 < 2^31.
+struct VolumeSkeletonArgs { int D = 0, H = 0, W = 0, m = 0, ux = 1, uy = 1, uz = 1; };
+struct VskPass { unsigned deleted; unsigned count[6][8]; unsigned pad[3]; };             // 208 bytes
+size_t volume_skeleton_workspace_bytes(int D, int H, int W);
+hipError_t launch_volume_skeleton_begin(int32_t *cur, const VolumeSkeletonArgs &a, bool want_dist, ::mi_unet_vskel *table, void *ws,
+                                        hipStream_t s);
+hipError_t launch_volume_skeleton_pass(int32_t *cur, const VolumeSkeletonArgs &a, void *ws, VskPass *pass_state, hipStream_t s);
+hipError_t launch_volume_skeleton_finish(const int32_t *cur, const VolumeSkeletonArgs &a, bool want_dist, bool want_radius, int32_t *r2,
+                                         ::mi_unet_vskel *table, void *ws, hipStream_t s);
+hipError_t launch_volume_skeleton_simple(uint32_t first_word, uint32_t n_words, uint32_t *bits, hipStream_t s);
 
 }  // namespace miunet

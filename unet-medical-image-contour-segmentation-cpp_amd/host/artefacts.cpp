@@ -93,18 +93,22 @@ void write_volume_artefacts(const VolumeArtefacts &a)
     o << a.report;
     o.close();
     if (!o) throw std::runtime_error("Failed to save volume report");
-    if (!a.out) return;
-    const std::vector<mi_unet_target> &targets = *a.targets;
-    const size_t hw = (size_t)a.height * a.width, D = a.bases->size();
-    for (size_t t = 0; t < targets.size(); ++t)
-        for (size_t z = 0; z < D; ++z) {
-            if ((*a.bases)[z].empty()) continue;
-            medseg::Image8 m(a.height, a.width, 1);
-            std::copy(a.out + (t * D + z) * hw, a.out + (t * D + z + 1) * hw, m.data.begin());
-            const std::string name = is_default(targets) ? "_volume_mask.png" : "_volume_mask_class" + std::to_string(targets[t].cls) + ".png";
-            if (!medseg::write_png(a.output_dir + "/" + (*a.bases)[z] + name, m, /*level0=*/true))
-                throw std::runtime_error("Failed to save volume mask");
-        }
+    // a stack u8 [K][D][H][W] as one picture per target and named slice: <base>_volume_<what>.png or <base>_volume_<what>_class<cls>.png
+    auto pictures = [&](const uint8_t *stack, const std::string &what) {
+        const std::vector<mi_unet_target> &targets = *a.targets;
+        const size_t hw = (size_t)a.height * a.width, D = a.bases->size();
+        for (size_t t = 0; t < targets.size(); ++t)
+            for (size_t z = 0; z < D; ++z) {
+                if ((*a.bases)[z].empty()) continue;
+                medseg::Image8 m(a.height, a.width, 1);
+                std::copy(stack + (t * D + z) * hw, stack + (t * D + z + 1) * hw, m.data.begin());
+                const std::string name = "_volume_" + what + (is_default(targets) ? std::string() : "_class" + std::to_string(targets[t].cls)) + ".png";
+                if (!medseg::write_png(a.output_dir + "/" + (*a.bases)[z] + name, m, /*level0=*/true))
+                    throw std::runtime_error("Failed to save volume " + what);
+            }
+    };
+    if (a.out) pictures(a.out, "mask");
+    if (a.skeleton) pictures(a.skeleton, "skeleton");
 }
 
 void write_volume_mesh(const VolumeMeshArtefact &a)

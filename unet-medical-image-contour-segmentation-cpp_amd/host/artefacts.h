@@ -44,12 +44,15 @@ ArtefactTimes write_image_artefacts(const ImageArtefacts &a);
 // The artefacts of a batch labelled as one volume (MedicalSeg::set_volume): <output_dir>/volume_report.json with the text `report`
 // and, when `out` is given -- the filtered stack u8 [K][D][H][W], 0 / 255, K = targets, D = bases -- per slice
 // <base>_volume_mask.png, or <base>_volume_mask_class<cls>.png under a non-default target list.  A slice without a name has no
-// picture.  Throws std::runtime_error("Failed to save volume report") / ("Failed to save volume mask").
+// picture.  When `skeleton` is given (MedicalSeg::set_volume_skeleton with png) -- the same layout -- per slice
+// <base>_volume_skeleton.png, or <base>_volume_skeleton_class<cls>.png.  Throws std::runtime_error("Failed to save volume report") /
+// ("Failed to save volume mask") / ("Failed to save volume skeleton").
 struct VolumeArtefacts {
     std::string output_dir, report;
     const std::vector<mi_unet_target> *targets = nullptr;
     const std::vector<std::string> *bases = nullptr;
     const uint8_t *out = nullptr;
+    const uint8_t *skeleton = nullptr;
     int height = 0, width = 0;
 };
 void write_volume_artefacts(const VolumeArtefacts &a);

@@ -228,6 +228,15 @@ void medseg_get_volume_split(int *on, double *neck_mm, int *min_core)
     const MedicalSeg::VolumeSplit v = MedicalSeg::get_volume_split();
     *on = v.on; *neck_mm = v.neck_mm; *min_core = v.min_core;
 }
+int medseg_set_volume_skeleton(int on, int radius, int png, int max_passes)
+{
+    return MedicalSeg::set_volume_skeleton({ on != 0, radius != 0, png != 0, max_passes }) ? 0 : 1;
+}
+void medseg_get_volume_skeleton(int *on, int *radius, int *png, int *max_passes)
+{
+    const MedicalSeg::VolumeSkeleton v = MedicalSeg::get_volume_skeleton();
+    *on = v.on; *radius = v.radius; *png = v.png; *max_passes = v.max_passes;
+}
 int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width)
 {
     return MedicalSeg::set_volume_texture({ on != 0, channel, mode, levels, lo, width }) ? 0 : 1;

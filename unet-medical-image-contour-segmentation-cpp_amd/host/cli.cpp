@@ -164,6 +164,7 @@ public:
         table_["volmeasure"] = [this](const Words &w) { cmd_volmeasure(w); return true; };
         table_["volspatial"] = [this](const Words &w) { cmd_volspatial(w); return true; };
         table_["volsplit"] = [this](const Words &w) { cmd_volsplit(w); return true; };
+        table_["volskeleton"] = [this](const Words &w) { cmd_volskeleton(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
         table_["volnbhood"] = [this](const Words &w) { cmd_volnbhood(w); return true; };
@@ -192,6 +193,7 @@ public:
             "  volmeasure on [channel N] [ends N]|off - With volume on: diameters, principal axes and intensity of every component in the report",
             "  volspatial on [channel N] [voxels N] [peak MM]|off - With volume on: Moran's I, Geary's C, centre-of-mass shift and intensity peaks of every component in the report",
             "  volsplit on [neck MM] [mincore N]|off - With volume on: touching components split into pieces (cores of a ball of MM regrown by geodesic distance); the report and every stage behind it take the pieces",
+            "  volskeleton on [radius off] [png on] [passes N]|off - With volume on: every component thinned to its medial line; length, radii, ends, junctions and loops in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
             "  volnbhood on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N]|off - With volume on: neighbourhood-difference, dependence and distance-zone features of every component in the report",
@@ -573,6 +575,37 @@ private:
         }
         const MedicalSeg::VolumeSplit cur = MedicalSeg::get_volume_split();
         std::cout << "Volume split: " << (cur.on ? "on" : "off") << " neck " << cur.neck_mm << " mincore " << cur.min_core << std::endl;
+    }
+
+    // volskeleton on [radius off] [png on] [passes N] | volskeleton off | volskeleton (prints the setting in force)
+    void cmd_volskeleton(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeSkeleton v;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            v.on = w[1] == "on";
+            for (size_t i = 2; ok && i < w.size(); i += 2) {
+                ok = i + 1 < w.size();
+                if (!ok) break;
+                if (w[i] == "radius" || w[i] == "png") {
+                    ok = w[i + 1] == "on" || w[i + 1] == "off";
+                    (w[i] == "radius" ? v.radius : v.png) = w[i + 1] == "on";
+                } else {
+                    ok = w[i] == "passes" && to_int(w[i + 1], v.max_passes);
+                }
+            }
+            if (!ok) {
+                std::cerr << "Error: Invalid volskeleton command (expected on [radius on|off] [png on|off] [passes N] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_skeleton(v)) {
+                std::cerr << "Volume skeleton unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeSkeleton cur = MedicalSeg::get_volume_skeleton();
+        std::cout << "Volume skeleton: " << (cur.on ? "on" : "off") << " radius " << (cur.radius ? "on" : "off") << " png " << (cur.png ? "on" : "off")
+                  << " passes " << cur.max_passes << std::endl;
     }
 
     // The words of a texture command behind its name -- on [levels N] [count | width W [lo L]] [channel N] and the command's own `word N`

@@ -39,6 +39,7 @@ struct Settings {
     VolumeMeasure volume_measure;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeSpatial volume_spatial;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeSplit volume_split;                              // off; acts only with volume.on (process_image_batch reads it)
+    VolumeSkeleton volume_skeleton;                        // off; acts only with volume.on (process_image_batch reads it)
     VolumeTexture volume_texture;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeZones volume_zones;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeNbhood volume_nbhood;                            // off; acts only with volume.on (process_image_batch reads it)

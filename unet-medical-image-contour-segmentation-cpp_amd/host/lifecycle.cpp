@@ -411,6 +411,20 @@ bool set_volume_split(const VolumeSplit &split)
         /*handle_side=*/false);
 }
 
+bool set_volume_skeleton(const VolumeSkeleton &skeleton)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_skeleton = skeleton;
+            return std::string(skeleton.max_passes >= 0 ? "" : "volume skeleton: max_passes is not negative");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume skeleton: " << (skeleton.on ? "on" : "off") << ", radius " << (skeleton.radius ? "on" : "off") << ", png "
+               << (skeleton.png ? "on" : "off") << ", passes " << skeleton.max_passes;
+        },
+        /*handle_side=*/false);
+}
+
 namespace {
 
 // The five fields a texture setting (VolumeTexture, VolumeZones, VolumeNbhood) begins with: what is wrong with the first of them that is
@@ -510,6 +524,7 @@ VolumeInterp get_volume_interp() { return current_settings().volume_interp; }
 VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeSpatial get_volume_spatial() { return current_settings().volume_spatial; }
 VolumeSplit get_volume_split() { return current_settings().volume_split; }
+VolumeSkeleton get_volume_skeleton() { return current_settings().volume_skeleton; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeZones get_volume_zones() { return current_settings().volume_zones; }
 VolumeNbhood get_volume_nbhood() { return current_settings().volume_nbhood; }

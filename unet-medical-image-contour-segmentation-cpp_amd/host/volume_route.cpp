@@ -584,6 +584,60 @@ SplitMembers split_volume(const uint8_t *labelled, size_t D, size_t hw, size_t c
     }
 }
 
+// set_volume_skeleton: per target one mi_unet_volume_skeleton call on `h` (mi_unet_volume_skeleton_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the ids the components stage -- or split_volume -- wrote ([K][D][H][W]), with m = min(found, cap), the integer units of
+// mi_unet_score_volume_units for the volume setting's spacing and the setting's max_passes, then mi_unet_volume_skeleton_derive of every
+// row.  Returns, per target and table row, the "skeleton" member of the row's component object in volume_report.json, from its leading
+// comma on; with the setting's png, `picture` receives the skeletons as 0 / 255 ([K][D][H][W]).  A failure is reported, returns nothing
+// and leaves `picture` empty: only this step ends.
+Members skeleton_volume(size_t D, size_t hw, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
+                        mi_unet_t *h, std::ostream &lg, std::vector<uint8_t> &picture)
+{
+    try {
+        const size_t K = s.targets.size();
+        const VolumeSkeleton &sk = s.volume_skeleton;
+        const VolumeUnits u = volume_units(s.volume, D);
+        const mi_unet_vskel_opts opts{ sk.max_passes, sk.radius ? 1 : 0 };
+        Members members(K);
+        std::vector<uint8_t> drawn(sk.png ? K * D * hw : 0);
+        std::vector<int32_t> thin(sk.png ? D * hw : 0);
+        int64_t passes = 0;
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const int m = (int)std::min<size_t>((size_t)found[t], cap);
+            if (m < 1) continue;
+            std::vector<mi_unet_vskel> table((size_t)m);
+            mi_unet_vskel_info info{};
+            stage_call(h, mi_unet_volume_skeleton, mi_unet_volume_skeleton_host, ids.data() + t * D * hw, (int)D, g_cfg.height, g_cfg.width, m, u.units,
+                       &opts, sk.png ? thin.data() : nullptr, nullptr, table.data(), &info);
+            passes += info.passes;
+            for (size_t i = 0; i < thin.size(); ++i) drawn[t * D * hw + i] = thin[i] > 0 ? 255 : 0;
+            for (const mi_unet_vskel &c : table) {
+                if (c.voxels_in < 1) {                          // dropped by the volume filter: its voxels carry no id
+                    members[t].push_back(", \"skeleton\": null");
+                    continue;
+                }
+                mi_unet_vskel_metrics f{};
+                checked(mi_unet_volume_skeleton_derive, &c, u.spacing, u.unit_mm, &f);
+                auto radius = [&](double mm) { return sk.radius ? json_number(mm) : std::string("null"); };
+                std::ostringstream js;
+                js << ", \"skeleton\": {\"voxels\": " << c.voxels << ", \"ends\": " << c.ends << ", \"junctions\": " << c.junctions << ", \"isolated\": "
+                   << c.isolated << ", \"loops\": " << f.loops << ", \"length_mm\": " << json_number(f.length_mm) << ", \"radius_min_mm\": "
+                   << radius(f.radius_min_mm) << ", \"radius_max_mm\": " << radius(f.radius_max_mm) << ", \"radius_rms_mm\": "
+                   << radius(f.radius_rms_mm) << ", \"stable\": " << info.stable << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume skeleton: " << D << " slices, " << K << " targets, " << passes << " passes, " << ms_since(t0) << " ms" << std::endl;
+        picture.swap(drawn);
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume skeleton error: ") + e.what());
+        picture.clear();
+        return {};
+    }
+}
+
 // One mi_unet_volume_components call per target with values = { 255 } on `h` (mi_unet_volume_components_host under
 // MEDSEG_HOST_POSTPROCESS=1), then volume_report.json and, under a filter, the <base>_volume_mask pictures.  A failure is reported and
 // fails no image.  Under a filter `filtered` receives the filtered stack [K][D][H][W]; it stays empty without one, or after a failure.
@@ -613,7 +667,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         const bool filter = v.min_voxels > 0 || v.keep_largest > 0 || !clean_json.empty();
         std::vector<uint8_t> out(filter ? K * D * hw : 0);
         std::vector<mi_unet_vcomp> table(K * cap);
-        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || s.volume_nbhood.on || s.volume_spatial.on || numbered ? K * D * hw : 0);
+        std::vector<int32_t> found(K), kept(K), ids(s.volume_measure.on || s.volume_texture.on || s.volume_zones.on || s.volume_nbhood.on || s.volume_spatial.on || s.volume_skeleton.on || numbered ? K * D * hw : 0);
         const mi_unet_volume_opts opts{ v.connectivity, v.min_voxels, v.keep_largest };
         const int value = 255;
         const auto t0 = hr_clock::now();
@@ -641,9 +695,11 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         const std::vector<std::vector<std::string>> nbhooded =
             s.volume_nbhood.on ? nbhood_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const Members spatialised = s.volume_spatial.on ? spatial_volume(st, ids, found, cap, s, h, lg) : Members();
+        std::vector<uint8_t> skeleton_picture;
+        const Members skeletons = s.volume_skeleton.on ? skeleton_volume(D, hw, ids, found, cap, s, h, lg, skeleton_picture) : Members();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
-        auto names = [&](const char *key, bool missing) {
+        auto names =[&](const char *key, bool missing) {
             js << "  \"" << key << "\": [";
             bool first = true;
             for (size_t z = 0; z < D; ++z) {
@@ -674,7 +730,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
                    << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r])
                    << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << (spatialised.empty() ? std::string() : spatialised[t][r])
-                   << (split.rows.empty() ? std::string() : split.rows[t][r]) << "}";
+                   << (split.rows.empty() ? std::string() : split.rows[t][r]) << (skeletons.empty() ? std::string() : skeletons[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]" << (split.targets.empty() ? std::string() : split.targets[t]) << "}";
         }
@@ -682,6 +738,7 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
         VolumeArtefacts a;
         a.output_dir = output_dir; a.report = js.str(); a.targets = &targets; a.bases = &st.bases; a.out = filter ? out.data() : nullptr;
         a.height = g_cfg.height; a.width = g_cfg.width;
+        a.skeleton = skeleton_picture.empty() ? nullptr : skeleton_picture.data();
         write_volume_artefacts(a);
         filtered.swap(out);
         if (numbered) {

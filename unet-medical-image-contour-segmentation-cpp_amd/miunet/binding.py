@@ -41,6 +41,8 @@ EXPORTS = [
     "mi_unet_volume_measure", "mi_unet_volume_measure_host", "mi_unet_volume_measure_derive",
     "mi_unet_volume_spatial", "mi_unet_volume_spatial_host", "mi_unet_volume_spatial_derive",
     "mi_unet_volume_split", "mi_unet_volume_split_host", "mi_unet_volume_split_derive",
+    "mi_unet_volume_skeleton", "mi_unet_volume_skeleton_host", "mi_unet_volume_skeleton_derive",
+    "mi_unet_volume_skeleton_simple", "mi_unet_volume_skeleton_simple_host",
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
@@ -271,6 +273,54 @@ def _volume_split_call(fn, head, masks, values, units, connectivity, neck_r, min
     _check(fn(*head, _ptr(masks), d, hh, ww, _ptr(vals), vals.size, _ptr(un), C.byref(VSplitOpts(int(connectivity), int(neck_r), int(min_core))),
               _ptr(ids), _ptr(table), _ptr(info), int(cap), _ptr(found), _ptr(stats), _ptr(rounds)))
     return dict(table=table, info=info, found=found, stats=stats, ids=ids, rounds=rounds)
+
+
+class VSkel(C.Structure):
+    """mi_unet_vskel: 112 bytes, thirteen int64 then two int32; VSKEL_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int64) for n in ("voxels_in", "voxels", "ends", "isolated", "junctions")] + [("links", C.c_int64 * 7), ("r2_sum", C.c_int64),
+                                                                                                    ("r2_min", C.c_int32), ("r2_max", C.c_int32)]
+
+
+VSKEL_DTYPE = np.dtype([(n, np.int64) for n in ("voxels_in", "voxels", "ends", "isolated", "junctions")] +
+                       [("links", np.int64, (7,)), ("r2_sum", np.int64), ("r2_min", np.int32), ("r2_max", np.int32)])
+
+
+class VSkelOpts(C.Structure):
+    _fields_ = [("max_passes", C.c_int), ("radius", C.c_int)]
+
+
+class VSkelInfo(C.Structure):
+    _fields_ = [("deleted", C.c_int64), ("passes", C.c_int32), ("stable", C.c_int32)]
+
+
+class VSkelMetrics(C.Structure):
+    _fields_ = [("length_mm", C.c_double), ("radius_min_mm", C.c_double), ("radius_max_mm", C.c_double), ("radius_rms_mm", C.c_double),
+                ("loops", C.c_int64)]
+
+
+def _volume_skeleton_call(fn, head, ids, m, units, max_passes, radius, want_ids, want_r2):
+    """mi_unet_volume_skeleton (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice), units (ux, uy, uz)
+    -> dict(table VSKEL_DTYPE [m], ids int32 [D,H,W] or None, r2 int32 [D,H,W] or None, passes, deleted, stable).  The library checks m
+    and the units."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    d, hh, ww = ids.shape
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: x, y, z")
+    out = np.zeros((d, hh, ww), np.int32) if want_ids else None
+    r2 = np.zeros((d, hh, ww), np.int32) if want_r2 else None
+    table = np.zeros(max(int(m), 1), VSKEL_DTYPE)
+    info = VSkelInfo()
+    _check(fn(*head, _ptr(ids), d, hh, ww, int(m), _ptr(un), C.byref(VSkelOpts(int(max_passes), int(radius))), _ptr(out), _ptr(r2), _ptr(table),
+              C.byref(info)))
+    return dict(table=table, ids=out, r2=r2, passes=int(info.passes), deleted=int(info.deleted), stable=int(info.stable))
+
+
+SKELETON_CODE_WORDS = 1 << 21      # 2^26 neighbourhood codes, 32 to a word
 
 
 class VCleanStat(C.Structure):
@@ -860,6 +910,12 @@ def lib():
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi_unet_volume_split.argtypes = [C.c_void_p] + L.mi_unet_volume_split_host.argtypes
         L.mi_unet_volume_split_derive.argtypes = [C.POINTER(VPiece), C.POINTER(C.c_double), C.c_double, C.POINTER(VPieceMetrics)]
+        L.mi_unet_volume_skeleton_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_skeleton.argtypes = [C.c_void_p] + L.mi_unet_volume_skeleton_host.argtypes
+        L.mi_unet_volume_skeleton_derive.argtypes = [C.POINTER(VSkel), C.POINTER(C.c_double), C.c_double, C.POINTER(VSkelMetrics)]
+        L.mi_unet_volume_skeleton_simple_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        L.mi_unet_volume_skeleton_simple.argtypes = [C.c_void_p] + L.mi_unet_volume_skeleton_simple_host.argtypes
         L.mi_unet_volume_texture_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
@@ -1324,6 +1380,19 @@ class Engine:
         VSPLIT_STAT_DTYPE [n], ids int32 [n,D,H,W] when want_ids, rounds)"""
         return _volume_split_call(lib().mi_unet_volume_split, (self._h,), masks, values, units, connectivity, neck_r, min_core, cap, want_ids)
 
+    # ---- components thinned to medial lines (mi_unet_volume_skeleton): needs the device, not the weights
+    def volume_skeleton(self, ids, m=1, units=(1, 1, 1), max_passes=0, radius=True, want_ids=True, want_r2=False):
+        """mi_unet_volume_skeleton: ids int32 [D,H,W] (component r is ids == r + 1), units (ux, uy, uz) -> dict(table VSKEL_DTYPE [m], ids
+        int32 [D,H,W] when want_ids, r2 int32 [D,H,W] when want_r2, passes, deleted, stable)"""
+        return _volume_skeleton_call(lib().mi_unet_volume_skeleton, (self._h,), ids, m, units, max_passes, radius, want_ids, want_r2)
+
+    def volume_skeleton_simple(self, first_word=0, n_words=SKELETON_CODE_WORDS):
+        """mi_unet_volume_skeleton_simple: the kernels' simple-point test on codes 32 * first_word .. 32 * (first_word + n_words) - 1 ->
+        uint32 [n_words], the layout of volume_skeleton_simple_host"""
+        bits = np.zeros(max(int(n_words), 1), np.uint32)
+        _check(lib().mi_unet_volume_skeleton_simple(self._h, int(first_word), int(n_words), _ptr(bits)))
+        return bits
+
     # ---- where the intensity of the components of a labelled stack sits (mi_unet_volume_spatial): needs the device, not the weights
     def volume_spatial(self, ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, peak_r=0):
         """ids int32 [D,H,W] of any size as mi_unet_volume_components writes them, intensity u16 [D,H,W], m = the components to take
@@ -1570,6 +1639,35 @@ def volume_spatial_host(ids, intensity, m=1, units=(1, 1, 1), max_voxels=None, p
 def volume_split_host(masks, values, units=(1, 1, 1), connectivity=26, neck_r=0, min_core=1, cap=256, want_ids=False):
     """mi_unet_volume_split_host: Engine.volume_split as sequential host arithmetic (needs no device)"""
     return _volume_split_call(lib().mi_unet_volume_split_host, (), masks, values, units, connectivity, neck_r, min_core, cap, want_ids)
+
+
+def volume_skeleton_host(ids, m=1, units=(1, 1, 1), max_passes=0, radius=True, want_ids=True, want_r2=False):
+    """mi_unet_volume_skeleton_host: Engine.volume_skeleton as sequential host arithmetic (needs no device)"""
+    return _volume_skeleton_call(lib().mi_unet_volume_skeleton_host, (), ids, m, units, max_passes, radius, want_ids, want_r2)
+
+
+def volume_skeleton_derive(comp, spacing, unit_mm):
+    """mi_unet_volume_skeleton_derive of one component (a VSkel, or one VSKEL_DTYPE record) with spacing (sx, sy, sz) in mm and the length
+    of the spacing unit in mm -> dict(length_mm, radius_min_mm, radius_max_mm, radius_rms_mm, loops)"""
+    if not isinstance(comp, VSkel):
+        rec = comp
+        comp = VSkel()
+        for n, _ in VSkel._fields_:
+            if n == "links":
+                comp.links = (C.c_int64 * 7)(*[int(v) for v in rec["links"]])
+            else:
+                setattr(comp, n, int(rec[n]))
+    out = VSkelMetrics()
+    _check(lib().mi_unet_volume_skeleton_derive(C.byref(comp), (C.c_double * 3)(*[float(v) for v in spacing]), float(unit_mm), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VSkelMetrics._fields_}
+
+
+def volume_skeleton_simple_host(first_word=0, n_words=SKELETON_CODE_WORDS):
+    """mi_unet_volume_skeleton_simple_host: the host form's simple-point test on codes 32 * first_word .. 32 * (first_word + n_words) - 1
+    -> uint32 [n_words], code c in bit c & 31 of word (c >> 5) - first_word"""
+    bits = np.zeros(max(int(n_words), 1), np.uint32)
+    _check(lib().mi_unet_volume_skeleton_simple_host(int(first_word), int(n_words), _ptr(bits)))
+    return bits
 
 
 def volume_split_derive(piece, spacing, unit_mm):

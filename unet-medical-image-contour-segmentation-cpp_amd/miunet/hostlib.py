@@ -27,7 +27,7 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
            "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones",
            "medseg_set_volume_nbhood", "medseg_get_volume_nbhood", "medseg_set_volume_spatial", "medseg_get_volume_spatial",
-           "medseg_set_volume_split", "medseg_get_volume_split"]
+           "medseg_set_volume_split", "medseg_get_volume_split", "medseg_set_volume_skeleton", "medseg_get_volume_skeleton"]
 
 
 def lib():
@@ -96,6 +96,9 @@ def lib():
         L.medseg_set_volume_split.argtypes = [C.c_int, C.c_double, C.c_int]
         L.medseg_get_volume_split.argtypes = [_i, C.POINTER(C.c_double), _i]
         L.medseg_get_volume_split.restype = None
+        L.medseg_set_volume_skeleton.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.medseg_get_volume_skeleton.argtypes = [_i, _i, _i, _i]
+        L.medseg_get_volume_skeleton.restype = None
         L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_match.argtypes = [_i, _i, _i]
         L.medseg_get_volume_match.restype = None
@@ -324,7 +327,20 @@ def get_volume_split():
     return {"on": bool(on.value), "neck_mm": neck.value, "min_core": core.value}
 
 
-VTEX_MODES = ("count", "width")            # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
+def set_volume_skeleton(on=True, radius=True, png=False, max_passes=0) -> bool:
+    """MedicalSeg::set_volume_skeleton: with set_volume on, process_image_batch thins every component of the labelled stack to its
+    medial line (mi_unet_volume_skeleton on the ids of the components stage, or of the split) and every component of
+    volume_report.json gains a last member "skeleton"; with png the skeleton of every slice is written as a picture; needs no engine"""
+    return lib().medseg_set_volume_skeleton(int(bool(on)), int(bool(radius)), int(bool(png)), int(max_passes)) == 0
+
+
+def get_volume_skeleton():
+    on, radius, png, passes = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    lib().medseg_get_volume_skeleton(C.byref(on), C.byref(radius), C.byref(png), C.byref(passes))
+    return {"on": bool(on.value), "radius": bool(radius.value), "png": bool(png.value), "max_passes": passes.value}
+
+
+VTEX_MODES = ("count", "width")           # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
 
 
 def set_volume_texture(on=True, channel=0, mode="count", levels=32, lo=0, width=1) -> bool:
