@@ -242,6 +242,27 @@ struct VolumeSkeleton {
 bool set_volume_skeleton(const VolumeSkeleton &skeleton);
 VolumeSkeleton get_volume_skeleton();
 
+// The skeleton of every component split into nodes and branches (mi_unet_volume_branches in include/mi_unet.h).  It acts
+// only together with set_volume's `on` and set_volume_skeleton's `on`: one mi_unet_volume_branches call per target
+// (mi_unet_volume_branches_host under MEDSEG_HOST_POSTPROCESS=1) on the skeleton stage's out_ids, and its r2 unless that setting's
+// `radius` is off, with `prune_voxels` and `prune_rounds`, tables of 4096 nodes and 4096 branches, then
+// mi_unet_volume_branches_derive per component and mi_unet_volume_branches_derive_branch per listed branch.  Every component object of
+// volume_report.json gains a last member "branches": "nodes", "ends", "junctions" (junction nodes), "branches", "closed", "parts",
+// "loops", "length_mm", "pruned_spurs", a "list" of at most 64 of the component's branches in table order, each with "node_a", "node_b",
+// "kind", "voxels", "length_mm", "chord_mm", "tortuosity", "radius_min_mm", "radius_max_mm", "radius_rms_mm" (the three null without
+// radii), and "listed" / "found"; "parts" and "loops" are null where the table of 4096 did not hold every branch of the component; the
+// member is null for a component the volume filter dropped.  One log line per batch, "Volume branches: D slices, K targets, N nodes, B
+// branches, R rounds, t ms" (over all targets); a failure is reported as "Volume branches error: ..." and ends only this step.  With it
+// off (the default) every artefact and every log line is what it is without the setting.  Needs no engine and survives
+// initialize_engine.  false, message on stderr, setting unchanged: prune_voxels or prune_rounds outside 0 .. 2^20.
+struct VolumeBranches {
+    bool on = false;
+    int prune_voxels = 0;
+    int prune_rounds = 0;
+};
+bool set_volume_branches(const VolumeBranches &branches);
+VolumeBranches get_volume_branches();
+
 // The texture of every component of the labelled stack (mi_unet_volume_texture in include/mi_unet.h).  It acts only
 // together with set_volume's `on`.  The stack keeps `channel` of every slice's normalised tile widened to 16 bits (beside the channel
 // set_volume_measure keeps, when the two differ), a failed slice all-zero; one mi_unet_volume_texture call per target

@@ -90,6 +90,10 @@ void medseg_get_volume_split(int *on, double *neck_mm, int *min_core);
  * (include/medseg/process.h).  0 on success; medseg_get_volume_skeleton fills the four values. */
 int medseg_set_volume_skeleton(int on, int radius, int png, int max_passes);
 void medseg_get_volume_skeleton(int *on, int *radius, int *png, int *max_passes);
+/* Every skeleton split into nodes and branches, short spurs pruned: MedicalSeg::set_volume_branches / get_volume_branches
+ * (include/medseg/process.h).  0 on success; medseg_get_volume_branches fills the three values. */
+int medseg_set_volume_branches(int on, int prune_voxels, int prune_rounds);
+void medseg_get_volume_branches(int *on, int *prune_voxels, int *prune_rounds);
 /* The scored stack per lesion: MedicalSeg::set_volume_match / get_volume_match (include/medseg/process.h).  0 on success;
  * medseg_get_volume_match fills the three values. */
 int medseg_set_volume_match(int on, int iou_num, int iou_den);

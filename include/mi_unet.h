@@ -1384,6 +1384,101 @@ int mi_unet_volume_skeleton_derive(const mi_unet_vskel *c, const double spacing_
 int mi_unet_volume_skeleton_simple(mi_unet_t *h, uint32_t first_word, uint32_t n_words, uint32_t *bits /* [n_words] host */);
 int mi_unet_volume_skeleton_simple_host(uint32_t first_word, uint32_t n_words, uint32_t *bits /* [n_words] */);
 
+/* ---- The branch graph of a skeleton: nodes, branches between them, short spurs pruned --------------------------------------
+ * mi_unet_volume_skeleton reports a medial line as totals per component.  This stage splits the line into the NODES where it ends or
+ * forks and the BRANCHES between them, each branch with its own length, calibre and the nodes it joins, and can prune short spurs.
+ * Exact integers and one total rule: the device, the host form and a reading of this text give the same bytes.
+ *
+ * INPUT    ids int32 [D][H][W] and m as mi_unet_volume_skeleton writes out_ids: component r is { ids == r + 1 }, every other value is
+ *          nothing, and so is everything outside the volume.  ANY id stack is legal: nothing below assumes a thin set.  r2 int32
+ *          [D][H][W] or NULL: the skeleton stage's radius field, read only at object voxels.  Same-object neighbours are 7.22's: 26-adjacent
+ *          voxels that carry the same id in 1 .. m.  The linear index of voxel (z, y, x) is (z H + y) W + x.
+ * CLASS    deg(p) = the number of same-object neighbours of p.  deg 0: ISOLATED; 1: END; 2: BRANCH VOXEL; 3 or more: JUNCTION VOXEL.
+ * NODES    Every isolated voxel and every end voxel is a node.  Every 26-connected set of junction voxels of one id (a CLUSTER) is one
+ *          node.  A node's `first` is the lowest linear index among its voxels; nodes are numbered 0 .. in increasing `first`.
+ * BRANCHES (a) Every 26-connected set of branch voxels of one id is a branch.  Each of its voxels has exactly two neighbours, so the set
+ *          is a path or a cycle.  An ATTACHMENT is an (ordered) pair (branch voxel, same-object neighbour that is a node voxel); a path
+ *          has exactly two, a cycle none: it is CLOSED.  The branch's key is its lowest-index voxel.
+ *          (b) Zero-voxel branches: an end voxel whose only neighbour is a junction voxel makes one, keyed by the end voxel; two end voxels
+ *          that are each other's only neighbour make one, keyed by the lower index.  Its two node voxels are its two attachments.
+ *          Keys are distinct voxels; branches are numbered 0 .. in increasing key.
+ *
+ * mi_unet_vbranch (88 bytes): first (the key); att_lo / att_hi = the smaller and the larger linear index of the two attached node voxels
+ *          (equal when both attachments meet one voxel), -1 / -1 when closed; r2_sum; id; kind 0 = path, 1 = closed, 2 = zero-voxel;
+ *          node_a / node_b = the nodes of att_lo / att_hi (-1 / -1 when closed, equal for a loop back into one cluster); voxels = its
+ *          branch voxels; links[c] = its adjacent pairs of class c = |dx| + 2 |dy| + 4 |dz| - 1 (7.22's): every pair of two of its voxels
+ *          once, every attachment pair, and for a zero-voxel branch the one pair of its two node voxels.  A pair of two voxels of one
+ *          node belongs to no branch.  r2_min / r2_max / r2_sum over the branch voxels; all 0 without r2 or with voxels = 0.
+ * mi_unet_vnode (56 bytes): first; sz / sy / sx = the coordinate sums of its voxels; id; kind 0 = isolated, 1 = end, 2 = junction; voxels;
+ *          degree = the attachments of all branches at its voxels (a loop counts two); r2_min / r2_max over its voxels (0 without r2).
+ * mi_unet_vgraph [m] (128 bytes, per id): nodes, ends, junction_nodes, isolated (nodes by kind), junction_voxels, branches, closed,
+ *          links[7] summed over the id's branches, pruned_spurs, pruned_voxels.  Always complete; an id no voxel carries: all zero.
+ *          Over every id: the sum of degree = 2 (branches - closed), and branch voxels + node voxels = object voxels.
+ * TABLES   The caller gives cap_nodes and cap_branches, each 0 .. MI_UNET_VBRANCH_MAX_ROWS; a cap of 0 with a NULL table is legal.  Rows
+ *          0 .. min(found, cap) - 1 are written, no other; info reports found_nodes and found_branches.  node_a / node_b and the values of
+ *          `map` are ranks in the full numbering, whatever the caps.
+ * map      int32 [D][H][W] or NULL: branch index + 1 on branch voxels, -(node index + 1) on node voxels, 0 elsewhere.
+ * out_ids  int32 [D][H][W] or NULL: the ids (outside 1 .. m: 0) after pruning.
+ * PRUNING  opts { prune_voxels, prune_rounds }, default { 0, 0 }.  A SPUR is a branch that is not closed, has one node of kind end and the
+ *          other of kind junction, and voxels + 1 <= prune_voxels (with prune_voxels = 0 nothing is a spur).  A round builds the graph of
+ *          the current state; if it has a spur, the round deletes the branch voxels and the end voxel of EVERY spur of that graph at once;
+ *          junction voxels stay.  Rounds repeat until a state has no spur, or until prune_rounds > 0 rounds have deleted.  info.rounds =
+ *          the rounds that deleted something; info.stable = 1 iff the final state has no spur.  The reported graph, map and out_ids are
+ *          those of the final state: a junction voxel left with two neighbours is then a branch voxel, and the two branches it joined
+ *          are one.  A star whose arms are all spurs COLLAPSES to its junction: all its arms go in one round and the junction is left
+ *          an isolated node; prune with a smaller prune_voxels, or not at all, where that is not wanted.  pruned_spurs / pruned_voxels
+ *          count, per id and over all rounds, the spurs and the voxels deleted (end voxels included).  The result is a set function of
+ *          the input: nothing depends on scheduling.  The thinned set is not re-thinned; mi_unet_volume_skeleton on out_ids does that.
+ *
+ * MI_UNET_EARG with a message that begins with the entry point's name, nothing queued and no output touched:
+ *   a null ids, spacing_units or graph; nodes NULL with cap_nodes > 0, branches NULL with cap_branches > 0;
+ *   cap_nodes, cap_branches in 0 .. MI_UNET_VBRANCH_MAX_ROWS; prune_voxels, prune_rounds in 0 .. MI_UNET_VBRANCH_MAX_PRUNE;
+ *   mi_unet_volume_skeleton's limits on D, H, W, m and spacing_units (which only the derived metrics use).
+ * A workspace that cannot be allocated is MI_UNET_EHIP and the handle stays usable.  Works before weights are loaded, changes no
+ * setting, has no group form.  mi_unet_volume_branches_host takes the same arguments without the handle, follows the text above voxel
+ * by voxel and gives the same bytes.
+ *
+ * mi_unet_volume_branches_derive_branch (host arithmetic in double; H, W of the volume, spacing in mm, unit_mm as in 7.22):
+ *   length_mm = sum over c of links[c] * |offset c * spacing|; chord_mm = the distance from att_lo to att_hi (0 when closed);
+ *   tortuosity = length_mm / chord_mm, 0 when closed or when the chord is 0; radius_min_mm / radius_max_mm / radius_rms_mm as 7.22's.
+ * mi_unet_volume_branches_derive (g = the row of `id` in the per-id table; branches = the table of the call, n_branches = the rows it
+ *   holds, found_nodes = info's): length_mm from g->links, which has no over-count inside clusters; parts = the connected components of
+ *   the id's graph, by a union-find over node_a / node_b in which every closed branch and every isolated node is a part of its own;
+ *   loops = branches - nodes - closed + parts, the cycle rank.  MI_UNET_EARG when the table holds fewer than g->branches rows of the id:
+ *   it was truncated. */
+#define MI_UNET_VBRANCH_MAX_ROWS (1 << 20)
+#define MI_UNET_VBRANCH_MAX_PRUNE (1 << 20)
+typedef struct mi_unet_vbranch_opts { int prune_voxels, prune_rounds; } mi_unet_vbranch_opts;   /* default { 0, 0 } */
+typedef struct mi_unet_vbranch {       /* 88 bytes, no padding */
+    int64_t first, att_lo, att_hi, r2_sum;
+    int32_t id, kind, node_a, node_b, voxels;
+    int32_t links[7];
+    int32_t r2_min, r2_max;
+} mi_unet_vbranch;
+typedef struct mi_unet_vnode {         /* 56 bytes, no padding */
+    int64_t first, sz, sy, sx;
+    int32_t id, kind, voxels, degree, r2_min, r2_max;
+} mi_unet_vnode;
+typedef struct mi_unet_vgraph {        /* 128 bytes, no padding */
+    int64_t nodes, ends, junction_nodes, isolated, junction_voxels, branches, closed;
+    int64_t links[7];
+    int64_t pruned_spurs, pruned_voxels;
+} mi_unet_vgraph;
+typedef struct mi_unet_vbranch_info { int64_t found_nodes, found_branches; int32_t rounds, stable; } mi_unet_vbranch_info;    /* 24 bytes */
+typedef struct mi_unet_vbranch_metrics { double length_mm, chord_mm, tortuosity, radius_min_mm, radius_max_mm, radius_rms_mm; } mi_unet_vbranch_metrics;
+typedef struct mi_unet_vgraph_metrics { double length_mm; int64_t parts, loops; } mi_unet_vgraph_metrics;
+int mi_unet_volume_branches(mi_unet_t *h, const int32_t *ids /* [D][H][W] host */, const int32_t *r2 /* [D][H][W] or NULL */, int D, int H, int W,
+                            int m, const int spacing_units[3], const mi_unet_vbranch_opts *opts, mi_unet_vnode *nodes /* [cap_nodes] or NULL */,
+                            int cap_nodes, mi_unet_vbranch *branches /* [cap_branches] or NULL */, int cap_branches, mi_unet_vgraph *graph /* [m] */,
+                            int32_t *map /* [D][H][W] or NULL */, int32_t *out_ids /* [D][H][W] or NULL */, mi_unet_vbranch_info *info /* or NULL */);
+int mi_unet_volume_branches_host(const int32_t *ids, const int32_t *r2, int D, int H, int W, int m, const int spacing_units[3],
+                                 const mi_unet_vbranch_opts *opts, mi_unet_vnode *nodes, int cap_nodes, mi_unet_vbranch *branches, int cap_branches,
+                                 mi_unet_vgraph *graph, int32_t *map, int32_t *out_ids, mi_unet_vbranch_info *info);
+int mi_unet_volume_branches_derive_branch(const mi_unet_vbranch *row, int H, int W, const double spacing_xyz[3], double unit_mm,
+                                          mi_unet_vbranch_metrics *out);
+int mi_unet_volume_branches_derive(const mi_unet_vgraph *g, const mi_unet_vbranch *branches, int64_t n_branches, int64_t found_nodes, int id,
+                                   const double spacing_xyz[3], double unit_mm, mi_unet_vgraph_metrics *out);
+
 /* Page-locked host memory.  RAW images handed to mi_unet_infer_raw16 / mi_unet_segment_raw16 (and their group forms) from such
  * a buffer are read by the DMA engine directly -- no staging copy on the calling thread (100 MB for sixteen 2048 x 1536 images:
  * 3 - 5 ms of memcpy that the pageable route pays).  Any hipHostMalloc'd / hipHostRegister'ed pointer is recognised, not only

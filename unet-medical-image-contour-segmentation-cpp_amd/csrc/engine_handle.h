@@ -201,6 +201,7 @@ struct mi_unet {
     miunet::Workspace ws_vnb;          // mi_unet_volume_nbhood: the results (table, the tables asked for), the keys (ids in place), the intensity, the ranges, the forest, both distance stacks
     miunet::Workspace ws_vsplit;       // mi_unet_volume_split: the volume, ids, the table, the info, the plane results, the rounds' activity, the kernels' workspace
     miunet::Workspace ws_vskel;        // mi_unet_volume_skeleton: the ids (the state, the skeleton), r2, the table, the pass state, the kernels' workspace
+    miunet::Workspace ws_vbranch;      // mi_unet_volume_branches: the ids (the state), r2, the map, both tables, the per-id table, the round's words, the kernels' workspace
     miunet::Workspace ws_volume_interp; // mi_unet_volume_interp: the masks, out, the counts, both intensity stacks, the kernels' workspace
     // RAW-in entry points: a second stream uploads and preprocesses micro-batch k+1 into the other tile buffer while the
     // network of micro-batch k runs (d_img / d_img2 alternate)

@@ -22,6 +22,9 @@ struct mi_unet_vzones;
 struct mi_unet_vzone;
 struct mi_unet_vpiece;
 struct mi_unet_vskel;
+struct mi_unet_vbranch;
+struct mi_unet_vnode;
+struct mi_unet_vgraph;
 struct mi_unet_vnbhood;
 
 namespace miunet {
@@ -661,5 +664,29 @@ hipError_t launch_volume_skeleton_pass(int32_t *cur, const VolumeSkeletonArgs &a
 hipError_t launch_volume_skeleton_finish(const int32_t *cur, const VolumeSkeletonArgs &a, bool want_dist, bool want_radius, int32_t *r2,
                                          ::mi_unet_vskel *table, void *ws, hipStream_t s);
 hipError_t launch_volume_skeleton_simple(uint32_t first_word, uint32_t n_words, uint32_t *bits, hipStream_t s);
+
+// Volume branches (volume_branches.hip; include/mi_unet.h: mi_unet_volume_branches).  cur i32 [D][H][W] on the device: the
+// ids on entry, the state of the pruning from then on.  Exact integers; nothing depends on the order of atomics; no workgroup waits for
+// another.  Only the classification sweep, the normalisation and the clears are proportional to the volume; the rest runs over the list
+// of object voxels.
+//   launch_volume_branches_begin  : ids outside 1 .. m become 0, the per-id table and `state` cleared.
+//   launch_volume_branches_round  : the graph of the current state: classes (first: the sweep over key_tile.h's tile, which also makes the
+//                                   list; later: degrees regathered from memory over the list), the forest of clusters and branches, each
+//                                   branch's voxels and attached node voxels, the spurs flagged.  state->spurs = the spurs of that graph.
+//   launch_volume_branches_delete : the flagged voxels deleted, pruned_spurs / pruned_voxels added per id.
+//   launch_volume_branches_number : the nodes and the branches of the last round's graph numbered in raster order; state->found_*.
+//   launch_volume_branches_rows   : rows 0 .. n_nodes - 1 and 0 .. n_branches - 1 (the host's min(found, cap)), the per-id table, the map.
+// Workspace: volume_branches_workspace_bytes(D, H, W), not zeroed by the caller.  D H W < 2^31, m <= VOLUME_MAX_TABLE, sides at most
+// SCORE_VOLUME_MAX_SIDE.
+struct VolumeBranchesArgs { int D = 0, H = 0, W = 0, m = 0, prune_voxels = 0; };
+struct VbrState { unsigned spurs, listed, found_nodes, found_branches; };                // 16 bytes
+size_t volume_branches_workspace_bytes(int D, int H, int W);
+hipError_t launch_volume_branches_begin(int32_t *cur, const VolumeBranchesArgs &a, ::mi_unet_vgraph *graph, VbrState *state, void *ws, hipStream_t s);
+hipError_t launch_volume_branches_round(int32_t *cur, const VolumeBranchesArgs &a, bool first, VbrState *state, void *ws, hipStream_t s);
+hipError_t launch_volume_branches_delete(int32_t *cur, const VolumeBranchesArgs &a, ::mi_unet_vgraph *graph, VbrState *state, void *ws, hipStream_t s);
+hipError_t launch_volume_branches_number(int32_t *cur, const VolumeBranchesArgs &a, VbrState *state, void *ws, hipStream_t s);
+hipError_t launch_volume_branches_rows(int32_t *cur, const int32_t *r2, const VolumeBranchesArgs &a, ::mi_unet_vnode *nodes, int n_nodes,
+                                       ::mi_unet_vbranch *branches, int n_branches, ::mi_unet_vgraph *graph, int32_t *map, VbrState *state, void *ws,
+                                       hipStream_t s);
 
 }  // namespace miunet

@@ -1,5 +1,5 @@
 // stage_common.h -- what the host halves of the stages behind the network share (score.cpp, score_volume.cpp, volume.cpp,
-// volume_clean.cpp, volume_mesh.cpp, volume_measure.cpp, volume_spatial.cpp, volume_match.cpp, volume_texture.cpp, volume_interp.cpp, volume_zones.cpp, volume_nbhood.cpp, volume_split.cpp, volume_skeleton.cpp): how a stage file is compiled, and the
+// volume_clean.cpp, volume_mesh.cpp, volume_measure.cpp, volume_spatial.cpp, volume_match.cpp, volume_texture.cpp, volume_interp.cpp, volume_zones.cpp, volume_nbhood.cpp, volume_split.cpp, volume_skeleton.cpp, volume_branches.cpp): how a stage file is compiled, and the
 // argument checks that more than one of them makes with the same text.  What only the texture stages share (volume_texture.cpp,
 // volume_zones.cpp, volume_nbhood.cpp) is in texture_common.h, which includes this file.
 // With MIUNET_NO_DEVICE only a stage's host arithmetic is compiled, with no HIP header: a plain C++ compiler builds it into a program that

@@ -24,6 +24,7 @@ using key_tile::ROWS;
 using key_tile::TX;
 using key_tile::TY;
 using key_tile::TZ;
+using key_tile::walk_tile;
 
 constexpr int WG = 256;
 constexpr int KZ = TZ + 2;                               // a tile with one voxel of halo on every side: 66 x 10 x 6 keys, 15.5 KiB
@@ -194,37 +195,6 @@ __global__ __launch_bounds__(WG) void k_vsk_dist_x(const int32_t *__restrict__ c
         if (!cur[i]) continue;
         const unsigned x = i % (unsigned)W;
         dist[i] = dist_scan(cur, f, (size_t)(i - x), (size_t)1, (int)x, W, ux);
-    }
-}
-
-// ---- the tile walk of the two sweeps that need all 26 neighbours ------------------------------------------------------------------------------
-// body(i, inside, v, code) for every row of the tile inside the volume, wave-uniformly (a wave per row of 64; a lane past W has inside
-// false and v = 0): i the voxel's index, v its id, code its 26 same-object bits
-template <class F>
-__device__ __forceinline__ void walk_tile(const int *s_keys, int3 o, int D, int H, int W, F body)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int it = 0; it < ROWS / 4; ++it) {
-        const int row = wave * (ROWS / 4) + it, lz = row / TY + 1, ly = row % TY + 1, lx = lane + 1;
-        const int gx = o.x + lx, gy = o.y + ly, gz = o.z + lz;
-        if (gy >= H || gz >= D) continue;                       // (wave-uniform)
-        const int *const c = s_keys + (lz * KY + ly) * KX + lx;
-        const int v = gx < W ? *c : 0;
-        uint32_t code = 0;
-        if (v) {
-            int bit = 0;
-#pragma unroll
-            for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-                for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        if (!dz && !dy && !dx) continue;
-                        code |= (uint32_t)(c[(dz * KY + dy) * KX + dx] == v) << bit;
-                        ++bit;
-                    }
-        }
-        body(((size_t)gz * H + gy) * W + gx, gx < W, v, code);
     }
 }
 

@@ -237,6 +237,15 @@ void medseg_get_volume_skeleton(int *on, int *radius, int *png, int *max_passes)
     const MedicalSeg::VolumeSkeleton v = MedicalSeg::get_volume_skeleton();
     *on = v.on; *radius = v.radius; *png = v.png; *max_passes = v.max_passes;
 }
+int medseg_set_volume_branches(int on, int prune_voxels, int prune_rounds)
+{
+    return MedicalSeg::set_volume_branches({ on != 0, prune_voxels, prune_rounds }) ? 0 : 1;
+}
+void medseg_get_volume_branches(int *on, int *prune_voxels, int *prune_rounds)
+{
+    const MedicalSeg::VolumeBranches v = MedicalSeg::get_volume_branches();
+    *on = v.on; *prune_voxels = v.prune_voxels; *prune_rounds = v.prune_rounds;
+}
 int medseg_set_volume_texture(int on, int channel, int mode, int levels, int lo, int width)
 {
     return MedicalSeg::set_volume_texture({ on != 0, channel, mode, levels, lo, width }) ? 0 : 1;

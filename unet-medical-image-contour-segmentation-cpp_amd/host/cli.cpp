@@ -165,6 +165,7 @@ public:
         table_["volspatial"] = [this](const Words &w) { cmd_volspatial(w); return true; };
         table_["volsplit"] = [this](const Words &w) { cmd_volsplit(w); return true; };
         table_["volskeleton"] = [this](const Words &w) { cmd_volskeleton(w); return true; };
+        table_["volbranches"] = [this](const Words &w) { cmd_volbranches(w); return true; };
         table_["voltexture"] = [this](const Words &w) { cmd_voltexture(w); return true; };
         table_["volzones"] = [this](const Words &w) { cmd_volzones(w); return true; };
         table_["volnbhood"] = [this](const Words &w) { cmd_volnbhood(w); return true; };
@@ -194,6 +195,7 @@ public:
             "  volspatial on [channel N] [voxels N] [peak MM]|off - With volume on: Moran's I, Geary's C, centre-of-mass shift and intensity peaks of every component in the report",
             "  volsplit on [neck MM] [mincore N]|off - With volume on: touching components split into pieces (cores of a ball of MM regrown by geodesic distance); the report and every stage behind it take the pieces",
             "  volskeleton on [radius off] [png on] [passes N]|off - With volume on: every component thinned to its medial line; length, radii, ends, junctions and loops in the report",
+            "  volbranches on [prune N] [rounds R]|off - With volume on and volskeleton on: every skeleton split into nodes and branches, spurs of at most N voxels pruned; per-branch length, tortuosity and radii in the report",
             "  voltexture on [levels N] [count|width W [lo L]] [channel N]|off - With volume on: histogram and co-occurrence texture of every component in the report",
             "  volzones on [levels N] [count|width W [lo L]] [run N] [channel N]|off - With volume on: run-length and size-zone features of every component in the report",
             "  volnbhood on [levels N] [count|width W [lo L]] [alpha N] [dist N] [channel N]|off - With volume on: neighbourhood-difference, dependence and distance-zone features of every component in the report",
@@ -606,6 +608,28 @@ private:
         const MedicalSeg::VolumeSkeleton cur = MedicalSeg::get_volume_skeleton();
         std::cout << "Volume skeleton: " << (cur.on ? "on" : "off") << " radius " << (cur.radius ? "on" : "off") << " png " << (cur.png ? "on" : "off")
                   << " passes " << cur.max_passes << std::endl;
+    }
+
+    // volbranches on [prune N] [rounds R] | volbranches off | volbranches (prints the setting in force)
+    void cmd_volbranches(const Words &w)
+    {
+        if (w.size() >= 2) {
+            MedicalSeg::VolumeBranches v;
+            bool ok = (w[1] == "off" && w.size() == 2) || w[1] == "on";
+            v.on = w[1] == "on";
+            for (size_t i = 2; ok && i < w.size(); i += 2)
+                ok = i + 1 < w.size() && (w[i] == "prune" ? to_int(w[i + 1], v.prune_voxels) : w[i] == "rounds" && to_int(w[i + 1], v.prune_rounds));
+            if (!ok) {
+                std::cerr << "Error: Invalid volbranches command (expected on [prune N] [rounds R] or off)" << std::endl;
+                return;
+            }
+            if (!MedicalSeg::set_volume_branches(v)) {
+                std::cerr << "Volume branches unchanged" << std::endl;
+                return;
+            }
+        }
+        const MedicalSeg::VolumeBranches cur = MedicalSeg::get_volume_branches();
+        std::cout << "Volume branches: " << (cur.on ? "on" : "off") << " prune " << cur.prune_voxels << " rounds " << cur.prune_rounds << std::endl;
     }
 
     // The words of a texture command behind its name -- on [levels N] [count | width W [lo L]] [channel N] and the command's own `word N`

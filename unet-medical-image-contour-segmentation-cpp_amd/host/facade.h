@@ -40,6 +40,7 @@ struct Settings {
     VolumeSpatial volume_spatial;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeSplit volume_split;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeSkeleton volume_skeleton;                        // off; acts only with volume.on (process_image_batch reads it)
+    VolumeBranches volume_branches;                        // off; acts only with volume.on and volume_skeleton.on (process_image_batch reads it)
     VolumeTexture volume_texture;                          // off; acts only with volume.on (process_image_batch reads it)
     VolumeZones volume_zones;                              // off; acts only with volume.on (process_image_batch reads it)
     VolumeNbhood volume_nbhood;                            // off; acts only with volume.on (process_image_batch reads it)

@@ -425,6 +425,21 @@ bool set_volume_skeleton(const VolumeSkeleton &skeleton)
         /*handle_side=*/false);
 }
 
+bool set_volume_branches(const VolumeBranches &branches)
+{
+    return change_setting(
+        [&](Settings &s) {
+            s.volume_branches = branches;
+            const bool ok = branches.prune_voxels >= 0 && branches.prune_voxels <= MI_UNET_VBRANCH_MAX_PRUNE && branches.prune_rounds >= 0 &&
+                            branches.prune_rounds <= MI_UNET_VBRANCH_MAX_PRUNE;
+            return std::string(ok ? "" : "volume branches: prune and rounds are 0 .. 1048576");
+        },
+        [&](std::ostream &lg, const Settings &) {
+            lg << "Volume branches: " << (branches.on ? "on" : "off") << ", prune " << branches.prune_voxels << ", rounds " << branches.prune_rounds;
+        },
+        /*handle_side=*/false);
+}
+
 namespace {
 
 // The five fields a texture setting (VolumeTexture, VolumeZones, VolumeNbhood) begins with: what is wrong with the first of them that is
@@ -525,6 +540,7 @@ VolumeMeasure get_volume_measure() { return current_settings().volume_measure; }
 VolumeSpatial get_volume_spatial() { return current_settings().volume_spatial; }
 VolumeSplit get_volume_split() { return current_settings().volume_split; }
 VolumeSkeleton get_volume_skeleton() { return current_settings().volume_skeleton; }
+VolumeBranches get_volume_branches() { return current_settings().volume_branches; }
 VolumeTexture get_volume_texture() { return current_settings().volume_texture; }
 VolumeZones get_volume_zones() { return current_settings().volume_zones; }
 VolumeNbhood get_volume_nbhood() { return current_settings().volume_nbhood; }

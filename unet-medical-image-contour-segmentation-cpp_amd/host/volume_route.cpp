@@ -588,19 +588,22 @@ SplitMembers split_volume(const uint8_t *labelled, size_t D, size_t hw, size_t c
 // the ids the components stage -- or split_volume -- wrote ([K][D][H][W]), with m = min(found, cap), the integer units of
 // mi_unet_score_volume_units for the volume setting's spacing and the setting's max_passes, then mi_unet_volume_skeleton_derive of every
 // row.  Returns, per target and table row, the "skeleton" member of the row's component object in volume_report.json, from its leading
-// comma on; with the setting's png, `picture` receives the skeletons as 0 / 255 ([K][D][H][W]).  A failure is reported, returns nothing
+// comma on; with the setting's png, `picture` receives the skeletons as 0 / 255 ([K][D][H][W]).  With set_volume_branches on, `lines`
+// receives the skeletons' ids ([K][D][H][W]) and, unless `radius` is off, `radii` their r2.  A failure is reported, returns nothing
 // and leaves `picture` empty: only this step ends.
 Members skeleton_volume(size_t D, size_t hw, const std::vector<int32_t> &ids, const std::vector<int32_t> &found, size_t cap, const Settings &s,
-                        mi_unet_t *h, std::ostream &lg, std::vector<uint8_t> &picture)
+                        mi_unet_t *h, std::ostream &lg, std::vector<uint8_t> &picture, std::vector<int32_t> &lines, std::vector<int32_t> &radii)
 {
     try {
         const size_t K = s.targets.size();
         const VolumeSkeleton &sk = s.volume_skeleton;
+        const bool keep = s.volume_branches.on;
+        std::vector<int32_t> kept_ids(keep ? K * D * hw : 0), kept_r2(keep && sk.radius ? K * D * hw : 0);
         const VolumeUnits u = volume_units(s.volume, D);
         const mi_unet_vskel_opts opts{ sk.max_passes, sk.radius ? 1 : 0 };
         Members members(K);
         std::vector<uint8_t> drawn(sk.png ? K * D * hw : 0);
-        std::vector<int32_t> thin(sk.png ? D * hw : 0);
+        std::vector<int32_t> thin(sk.png || keep ? D * hw : 0);
         int64_t passes = 0;
         const auto t0 = hr_clock::now();
         for (size_t t = 0; t < K; ++t) {
@@ -609,9 +612,10 @@ Members skeleton_volume(size_t D, size_t hw, const std::vector<int32_t> &ids, co
             std::vector<mi_unet_vskel> table((size_t)m);
             mi_unet_vskel_info info{};
             stage_call(h, mi_unet_volume_skeleton, mi_unet_volume_skeleton_host, ids.data() + t * D * hw, (int)D, g_cfg.height, g_cfg.width, m, u.units,
-                       &opts, sk.png ? thin.data() : nullptr, nullptr, table.data(), &info);
+                       &opts, thin.empty() ? nullptr : thin.data(), kept_r2.empty() ? nullptr : kept_r2.data() + t * D * hw, table.data(), &info);
             passes += info.passes;
-            for (size_t i = 0; i < thin.size(); ++i) drawn[t * D * hw + i] = thin[i] > 0 ? 255 : 0;
+            for (size_t i = 0; i < drawn.size() / K; ++i) drawn[t * D * hw + i] = thin[i] > 0 ? 255 : 0;
+            if (keep) std::copy(thin.begin(), thin.end(), kept_ids.begin() + t * D * hw);
             for (const mi_unet_vskel &c : table) {
                 if (c.voxels_in < 1) {                          // dropped by the volume filter: its voxels carry no id
                     members[t].push_back(", \"skeleton\": null");
@@ -630,10 +634,90 @@ Members skeleton_volume(size_t D, size_t hw, const std::vector<int32_t> &ids, co
         }
         lg << "Volume skeleton: " << D << " slices, " << K << " targets, " << passes << " passes, " << ms_since(t0) << " ms" << std::endl;
         picture.swap(drawn);
+        lines.swap(kept_ids);
+        radii.swap(kept_r2);
         return members;
     } catch (const std::exception &e) {
         report(lg, std::string("Volume skeleton error: ") + e.what());
         picture.clear();
+        lines.clear();
+        radii.clear();
+        return {};
+    }
+}
+
+// set_volume_branches: per target one mi_unet_volume_branches call on `h` (mi_unet_volume_branches_host under MEDSEG_HOST_POSTPROCESS=1) over
+// the skeletons skeleton_volume kept (`lines` [K][D][H][W], `radii` the same or empty), with m = min(found, cap), the setting's pruning and
+// tables of kRows nodes and branches, then mi_unet_volume_branches_derive per component and mi_unet_volume_branches_derive_branch per
+// listed branch.  Returns, per target and table row, the "branches" member of the row's component object in volume_report.json, from its
+// leading comma on.  A failure is reported and returns nothing: only this step ends.
+Members branches_volume(size_t D, size_t hw, const std::vector<int32_t> &lines, const std::vector<int32_t> &radii, const std::vector<int32_t> &found,
+                        size_t cap, const Settings &s, mi_unet_t *h, std::ostream &lg)
+{
+    constexpr int kRows = 4096, kListed = 64;
+    try {
+        const size_t K = s.targets.size();
+        const VolumeUnits u = volume_units(s.volume, D);
+        const mi_unet_vbranch_opts opts{ s.volume_branches.prune_voxels, s.volume_branches.prune_rounds };
+        Members members(K);
+        std::vector<mi_unet_vnode> nodes(kRows);
+        std::vector<mi_unet_vbranch> rows(kRows);
+        int64_t n_nodes = 0, n_branches = 0, rounds = 0;
+        const auto t0 = hr_clock::now();
+        for (size_t t = 0; t < K; ++t) {
+            const int m = (int)std::min<size_t>((size_t)found[t], cap);
+            if (m < 1) continue;
+            std::vector<mi_unet_vgraph> graph((size_t)m);
+            mi_unet_vbranch_info info{};
+            stage_call(h, mi_unet_volume_branches, mi_unet_volume_branches_host, lines.data() + t * D * hw,
+                       radii.empty() ? nullptr : radii.data() + t * D * hw, (int)D, g_cfg.height, g_cfg.width, m, u.units, &opts, nodes.data(), kRows,
+                       rows.data(), kRows, graph.data(), nullptr, nullptr, &info);
+            n_nodes += info.found_nodes; n_branches += info.found_branches; rounds += info.rounds;
+            const int64_t held = std::min<int64_t>(info.found_branches, kRows);
+            for (int r = 0; r < m; ++r) {
+                const mi_unet_vgraph &g = graph[r];
+                if (g.nodes + g.branches + g.pruned_voxels < 1) {   // no skeleton voxel: dropped by the volume filter
+                    members[t].push_back(", \"branches\": null");
+                    continue;
+                }
+                mi_unet_vgraph_metrics f{};
+                int64_t mine = 0;
+                for (int64_t b = 0; b < held; ++b) mine += rows[b].id == r + 1;
+                const bool whole = mine >= g.branches;
+                if (whole) checked(mi_unet_volume_branches_derive, &g, rows.data(), held, info.found_nodes, r + 1, u.spacing, u.unit_mm, &f);
+                else f.length_mm = 0.0;
+                std::ostringstream js;
+                js << ", \"branches\": {\"nodes\": " << g.nodes << ", \"ends\": " << g.ends << ", \"junctions\": " << g.junction_nodes << ", \"branches\": "
+                   << g.branches << ", \"closed\": " << g.closed << ", \"parts\": " << (whole ? std::to_string(f.parts) : "null") << ", \"loops\": "
+                   << (whole ? std::to_string(f.loops) : "null") << ", \"length_mm\": ";
+                if (!whole) {                                       // the length needs the per-id links alone
+                    mi_unet_vgraph bare = g;
+                    bare.branches = 0;
+                    checked(mi_unet_volume_branches_derive, &bare, rows.data(), (int64_t)0, info.found_nodes, r + 1, u.spacing, u.unit_mm, &f);
+                }
+                js << json_number(f.length_mm) << ", \"pruned_spurs\": " << g.pruned_spurs << ", \"list\": [";
+                int listed = 0;
+                for (int64_t b = 0; b < held && listed < kListed; ++b) {
+                    if (rows[b].id != r + 1) continue;
+                    mi_unet_vbranch_metrics bm{};
+                    checked(mi_unet_volume_branches_derive_branch, &rows[b], g_cfg.height, g_cfg.width, u.spacing, u.unit_mm, &bm);
+                    auto radius = [&](double mm) { return radii.empty() ? std::string("null") : json_number(mm); };
+                    js << (listed ? ", " : "") << "{\"node_a\": " << rows[b].node_a << ", \"node_b\": " << rows[b].node_b << ", \"kind\": " << rows[b].kind
+                       << ", \"voxels\": " << rows[b].voxels << ", \"length_mm\": " << json_number(bm.length_mm) << ", \"chord_mm\": "
+                       << json_number(bm.chord_mm) << ", \"tortuosity\": " << json_number(bm.tortuosity) << ", \"radius_min_mm\": "
+                       << radius(bm.radius_min_mm) << ", \"radius_max_mm\": " << radius(bm.radius_max_mm) << ", \"radius_rms_mm\": "
+                       << radius(bm.radius_rms_mm) << "}";
+                    ++listed;
+                }
+                js << "], \"listed\": " << listed << ", \"found\": " << g.branches << "}";
+                members[t].push_back(js.str());
+            }
+        }
+        lg << "Volume branches: " << D << " slices, " << K << " targets, " << n_nodes << " nodes, " << n_branches << " branches, " << rounds
+           << " rounds, " << ms_since(t0) << " ms" << std::endl;
+        return members;
+    } catch (const std::exception &e) {
+        report(lg, std::string("Volume branches error: ") + e.what());
         return {};
     }
 }
@@ -696,7 +780,9 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
             s.volume_nbhood.on ? nbhood_volume(st, ids, found, cap, s, h, lg) : std::vector<std::vector<std::string>>();
         const Members spatialised = s.volume_spatial.on ? spatial_volume(st, ids, found, cap, s, h, lg) : Members();
         std::vector<uint8_t> skeleton_picture;
-        const Members skeletons = s.volume_skeleton.on ? skeleton_volume(D, hw, ids, found, cap, s, h, lg, skeleton_picture) : Members();
+        std::vector<int32_t> lines, radii;
+        const Members skeletons = s.volume_skeleton.on ? skeleton_volume(D, hw, ids, found, cap, s, h, lg, skeleton_picture, lines, radii) : Members();
+        const Members branched = s.volume_branches.on && !lines.empty() ? branches_volume(D, hw, lines, radii, found, cap, s, h, lg) : Members();
         const double spacing[3] = { v.spacing_x, v.spacing_y, v.spacing_z };
         std::ostringstream js;
         auto names =[&](const char *key, bool missing) {
@@ -730,7 +816,8 @@ void label_volume(const VolumeStack &st, const Settings &s, mi_unet_t *h, const 
                    << json_number(m.extent_y_mm) << ", " << json_number(m.extent_z_mm) << "]" << (measured.empty() ? std::string() : measured[t][r])
                    << (textured.empty() ? std::string() : textured[t][r]) << (zoned.empty() ? std::string() : zoned[t][r])
                    << (nbhooded.empty() ? std::string() : nbhooded[t][r]) << (spatialised.empty() ? std::string() : spatialised[t][r])
-                   << (split.rows.empty() ? std::string() : split.rows[t][r]) << (skeletons.empty() ? std::string() : skeletons[t][r]) << "}";
+                   << (split.rows.empty() ? std::string() : split.rows[t][r]) << (skeletons.empty() ? std::string() : skeletons[t][r])
+                   << (branched.empty() ? std::string() : branched[t][r]) << "}";
             }
             js << (rows ? "\n    " : "") << "]" << (split.targets.empty() ? std::string() : split.targets[t]) << "}";
         }

@@ -43,6 +43,7 @@ EXPORTS = [
     "mi_unet_volume_split", "mi_unet_volume_split_host", "mi_unet_volume_split_derive",
     "mi_unet_volume_skeleton", "mi_unet_volume_skeleton_host", "mi_unet_volume_skeleton_derive",
     "mi_unet_volume_skeleton_simple", "mi_unet_volume_skeleton_simple_host",
+    "mi_unet_volume_branches", "mi_unet_volume_branches_host", "mi_unet_volume_branches_derive_branch", "mi_unet_volume_branches_derive",
     "mi_unet_volume_texture", "mi_unet_volume_texture_host", "mi_unet_volume_texture_derive",
     "mi_unet_volume_match", "mi_unet_volume_match_host", "mi_unet_volume_match_assign", "mi_unet_volume_match_derive",
     "mi_unet_volume_interp", "mi_unet_volume_interp_host", "mi_unet_volume_interp_slices",
@@ -321,6 +322,76 @@ def _volume_skeleton_call(fn, head, ids, m, units, max_passes, radius, want_ids,
 
 
 SKELETON_CODE_WORDS = 1 << 21      # 2^26 neighbourhood codes, 32 to a word
+
+
+class VBranch(C.Structure):
+    """mi_unet_vbranch: 88 bytes, four int64 then fourteen int32; VBRANCH_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int64) for n in ("first", "att_lo", "att_hi", "r2_sum")] + [(n, C.c_int32) for n in ("id", "kind", "node_a", "node_b", "voxels")] + [
+        ("links", C.c_int32 * 7), ("r2_min", C.c_int32), ("r2_max", C.c_int32)]
+
+
+VBRANCH_DTYPE = np.dtype([(n, np.int64) for n in ("first", "att_lo", "att_hi", "r2_sum")] + [(n, np.int32) for n in ("id", "kind", "node_a", "node_b", "voxels")] +
+                         [("links", np.int32, (7,)), ("r2_min", np.int32), ("r2_max", np.int32)])
+VNODE_DTYPE = np.dtype([(n, np.int64) for n in ("first", "sz", "sy", "sx")] + [(n, np.int32) for n in ("id", "kind", "voxels", "degree", "r2_min", "r2_max")])
+VGRAPH_DTYPE = np.dtype([(n, np.int64) for n in ("nodes", "ends", "junction_nodes", "isolated", "junction_voxels", "branches", "closed")] +
+                        [("links", np.int64, (7,)), ("pruned_spurs", np.int64), ("pruned_voxels", np.int64)])
+VBRANCH_MAX_ROWS = 1 << 20         # MI_UNET_VBRANCH_MAX_ROWS
+VBRANCH_KINDS = ("path", "closed", "zero-voxel")
+VNODE_KINDS = ("isolated", "end", "junction")
+
+
+class VGraph(C.Structure):
+    """mi_unet_vgraph: 128 bytes, sixteen int64; VGRAPH_DTYPE is the same layout for numpy"""
+    _fields_ = [(n, C.c_int64) for n in ("nodes", "ends", "junction_nodes", "isolated", "junction_voxels", "branches", "closed")] + [
+        ("links", C.c_int64 * 7), ("pruned_spurs", C.c_int64), ("pruned_voxels", C.c_int64)]
+
+
+class VBranchOpts(C.Structure):
+    _fields_ = [("prune_voxels", C.c_int), ("prune_rounds", C.c_int)]
+
+
+class VBranchInfo(C.Structure):
+    _fields_ = [("found_nodes", C.c_int64), ("found_branches", C.c_int64), ("rounds", C.c_int32), ("stable", C.c_int32)]
+
+
+class VBranchMetrics(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("length_mm", "chord_mm", "tortuosity", "radius_min_mm", "radius_max_mm", "radius_rms_mm")]
+
+
+class VGraphMetrics(C.Structure):
+    _fields_ = [("length_mm", C.c_double), ("parts", C.c_int64), ("loops", C.c_int64)]
+
+
+def _volume_branches_call(fn, head, ids, m, r2, units, prune_voxels, prune_rounds, cap_nodes, cap_branches, want_map, want_ids):
+    """mi_unet_volume_branches (head = (handle,)) or its host form (head = ()): ids int32 [D,H,W] (or [H,W]: one slice) as
+    volume_skeleton writes them, r2 int32 of the same shape or None -> dict(nodes VNODE_DTYPE [min(found, cap)], branches VBRANCH_DTYPE
+    [min(found, cap)], graph VGRAPH_DTYPE [m], map int32 [D,H,W] or None, ids int32 [D,H,W] or None, found_nodes, found_branches, rounds,
+    stable).  The library checks m, the units, the caps and the options."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim == 2:
+        ids = ids[None]
+    if ids.ndim != 3:
+        raise ValueError(f"ids {ids.shape} must be one int32 [D,H,W] array")
+    d, hh, ww = ids.shape
+    if r2 is not None:
+        r2 = np.ascontiguousarray(r2, np.int32).reshape(-1)
+        if r2.size != ids.size:
+            raise ValueError("r2 has the shape of ids")
+    un = np.ascontiguousarray(units, np.int32).reshape(-1)
+    if un.size != 3:
+        raise ValueError("units holds three integers: x, y, z")
+    nodes = np.zeros(max(int(cap_nodes), 0), VNODE_DTYPE)
+    branches = np.zeros(max(int(cap_branches), 0), VBRANCH_DTYPE)
+    graph = np.zeros(max(int(m), 1), VGRAPH_DTYPE)
+    vmap = np.zeros((d, hh, ww), np.int32) if want_map else None
+    out = np.zeros((d, hh, ww), np.int32) if want_ids else None
+    info = VBranchInfo()
+    _check(fn(*head, _ptr(ids), _ptr(r2), d, hh, ww, int(m), _ptr(un), C.byref(VBranchOpts(int(prune_voxels), int(prune_rounds))),
+              _ptr(nodes) if nodes.size else None, int(cap_nodes), _ptr(branches) if branches.size else None, int(cap_branches), _ptr(graph),
+              _ptr(vmap), _ptr(out), C.byref(info)))
+    return dict(nodes=nodes[:min(int(info.found_nodes), nodes.size)], branches=branches[:min(int(info.found_branches), branches.size)], graph=graph,
+                map=vmap, ids=out, found_nodes=int(info.found_nodes), found_branches=int(info.found_branches), rounds=int(info.rounds),
+                stable=int(info.stable))
 
 
 class VCleanStat(C.Structure):
@@ -916,6 +987,13 @@ def lib():
         L.mi_unet_volume_skeleton_derive.argtypes = [C.POINTER(VSkel), C.POINTER(C.c_double), C.c_double, C.POINTER(VSkelMetrics)]
         L.mi_unet_volume_skeleton_simple_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
         L.mi_unet_volume_skeleton_simple.argtypes = [C.c_void_p] + L.mi_unet_volume_skeleton_simple_host.argtypes
+        L.mi_unet_volume_branches_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi_unet_volume_branches.argtypes = [C.c_void_p] + L.mi_unet_volume_branches_host.argtypes
+        L.mi_unet_volume_branches_derive_branch.argtypes = [C.POINTER(VBranch), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                                            C.POINTER(VBranchMetrics)]
+        L.mi_unet_volume_branches_derive.argtypes = [C.POINTER(VGraph), C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                                     C.POINTER(VGraphMetrics)]
         L.mi_unet_volume_texture_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.mi_unet_volume_texture.argtypes = [C.c_void_p] + L.mi_unet_volume_texture_host.argtypes
@@ -1386,6 +1464,15 @@ class Engine:
         int32 [D,H,W] when want_ids, r2 int32 [D,H,W] when want_r2, passes, deleted, stable)"""
         return _volume_skeleton_call(lib().mi_unet_volume_skeleton, (self._h,), ids, m, units, max_passes, radius, want_ids, want_r2)
 
+    # ---- a skeleton split into nodes and branches (mi_unet_volume_branches): needs the device, not the weights
+    def volume_branches(self, ids, m=1, r2=None, units=(1, 1, 1), prune_voxels=0, prune_rounds=0, cap_nodes=4096, cap_branches=4096, want_map=True,
+                        want_ids=False):
+        """mi_unet_volume_branches: ids int32 [D,H,W] as volume_skeleton writes them, r2 its radius field or None -> dict(nodes VNODE_DTYPE,
+        branches VBRANCH_DTYPE (the first min(found, cap) rows of each), graph VGRAPH_DTYPE [m], map int32 [D,H,W] when want_map, ids int32
+        [D,H,W] when want_ids (the ids after pruning), found_nodes, found_branches, rounds, stable)"""
+        return _volume_branches_call(lib().mi_unet_volume_branches, (self._h,), ids, m, r2, units, prune_voxels, prune_rounds, cap_nodes, cap_branches,
+                                     want_map, want_ids)
+
     def volume_skeleton_simple(self, first_word=0, n_words=SKELETON_CODE_WORDS):
         """mi_unet_volume_skeleton_simple: the kernels' simple-point test on codes 32 * first_word .. 32 * (first_word + n_words) - 1 ->
         uint32 [n_words], the layout of volume_skeleton_simple_host"""
@@ -1660,6 +1747,44 @@ def volume_skeleton_derive(comp, spacing, unit_mm):
     out = VSkelMetrics()
     _check(lib().mi_unet_volume_skeleton_derive(C.byref(comp), (C.c_double * 3)(*[float(v) for v in spacing]), float(unit_mm), C.byref(out)))
     return {n: getattr(out, n) for n, _ in VSkelMetrics._fields_}
+
+
+def volume_branches_host(ids, m=1, r2=None, units=(1, 1, 1), prune_voxels=0, prune_rounds=0, cap_nodes=4096, cap_branches=4096, want_map=True,
+                         want_ids=False):
+    """mi_unet_volume_branches_host: Engine.volume_branches as sequential host arithmetic (needs no device)"""
+    return _volume_branches_call(lib().mi_unet_volume_branches_host, (), ids, m, r2, units, prune_voxels, prune_rounds, cap_nodes, cap_branches, want_map,
+                                 want_ids)
+
+
+def _fill(struct, rec):
+    """a ctypes structure from one record of the numpy dtype of the same layout"""
+    out = struct()
+    for n, t in struct._fields_:
+        setattr(out, n, t(*[int(v) for v in rec[n]]) if hasattr(t, "_length_") else int(rec[n]))
+    return out
+
+
+def volume_branches_derive_branch(row, shape, spacing, unit_mm):
+    """mi_unet_volume_branches_derive_branch of one branch (a VBranch, or one VBRANCH_DTYPE record) of a volume of shape (D, H, W) with
+    spacing (sx, sy, sz) in mm and the length of the spacing unit in mm -> dict(length_mm, chord_mm, tortuosity, radius_min_mm,
+    radius_max_mm, radius_rms_mm)"""
+    if not isinstance(row, VBranch):
+        row = _fill(VBranch, row)
+    out = VBranchMetrics()
+    _check(lib().mi_unet_volume_branches_derive_branch(C.byref(row), int(shape[-2]), int(shape[-1]), (C.c_double * 3)(*[float(v) for v in spacing]),
+                                                       float(unit_mm), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VBranchMetrics._fields_}
+
+
+def volume_branches_derive(graph_row, branches, found_nodes, comp_id, spacing, unit_mm):
+    """mi_unet_volume_branches_derive of one id (its VGRAPH_DTYPE record, the call's VBRANCH_DTYPE table, info's found_nodes) ->
+    dict(length_mm, parts, loops); RuntimeError when the table holds fewer rows of the id than the record counts"""
+    g = graph_row if isinstance(graph_row, VGraph) else _fill(VGraph, graph_row)
+    table = np.ascontiguousarray(branches, VBRANCH_DTYPE)
+    out = VGraphMetrics()
+    _check(lib().mi_unet_volume_branches_derive(C.byref(g), _ptr(table) if table.size else None, int(table.size), int(found_nodes), int(comp_id),
+                                                (C.c_double * 3)(*[float(v) for v in spacing]), float(unit_mm), C.byref(out)))
+    return {n: getattr(out, n) for n, _ in VGraphMetrics._fields_}
 
 
 def volume_skeleton_simple_host(first_word=0, n_words=SKELETON_CODE_WORDS):

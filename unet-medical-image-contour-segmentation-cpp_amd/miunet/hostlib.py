@@ -27,7 +27,8 @@ EXPORTS = ["medseg_initialize_engine", "medseg_process_single_image", "medseg_pr
            "medseg_set_volume_measure", "medseg_get_volume_measure", "medseg_set_volume_match", "medseg_get_volume_match",
            "medseg_set_volume_texture", "medseg_get_volume_texture", "medseg_set_volume_zones", "medseg_get_volume_zones",
            "medseg_set_volume_nbhood", "medseg_get_volume_nbhood", "medseg_set_volume_spatial", "medseg_get_volume_spatial",
-           "medseg_set_volume_split", "medseg_get_volume_split", "medseg_set_volume_skeleton", "medseg_get_volume_skeleton"]
+           "medseg_set_volume_split", "medseg_get_volume_split", "medseg_set_volume_skeleton", "medseg_get_volume_skeleton",
+           "medseg_set_volume_branches", "medseg_get_volume_branches"]
 
 
 def lib():
@@ -99,6 +100,9 @@ def lib():
         L.medseg_set_volume_skeleton.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_skeleton.argtypes = [_i, _i, _i, _i]
         L.medseg_get_volume_skeleton.restype = None
+        L.medseg_set_volume_branches.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.medseg_get_volume_branches.argtypes = [_i, _i, _i]
+        L.medseg_get_volume_branches.restype = None
         L.medseg_set_volume_match.argtypes = [C.c_int, C.c_int, C.c_int]
         L.medseg_get_volume_match.argtypes = [_i, _i, _i]
         L.medseg_get_volume_match.restype = None
@@ -338,6 +342,19 @@ def get_volume_skeleton():
     on, radius, png, passes = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     lib().medseg_get_volume_skeleton(C.byref(on), C.byref(radius), C.byref(png), C.byref(passes))
     return {"on": bool(on.value), "radius": bool(radius.value), "png": bool(png.value), "max_passes": passes.value}
+
+
+def set_volume_branches(on=True, prune_voxels=0, prune_rounds=0) -> bool:
+    """MedicalSeg::set_volume_branches: with set_volume and set_volume_skeleton on, process_image_batch splits every skeleton into nodes
+    and branches (mi_unet_volume_branches on the skeleton stage's ids and radii), prunes spurs of at most prune_voxels voxels, and every
+    component of volume_report.json gains a last member "branches"; needs no engine"""
+    return lib().medseg_set_volume_branches(int(bool(on)), int(prune_voxels), int(prune_rounds)) == 0
+
+
+def get_volume_branches():
+    on, prune, rounds = C.c_int(), C.c_int(), C.c_int()
+    lib().medseg_get_volume_branches(C.byref(on), C.byref(prune), C.byref(rounds))
+    return {"on": bool(on.value), "prune_voxels": prune.value, "prune_rounds": rounds.value}
 
 
 VTEX_MODES = ("count", "width")           # MI_UNET_VTEX_COUNT, MI_UNET_VTEX_WIDTH
